@@ -38,6 +38,10 @@ line with the driver's contract fields plus
   "with_color" / "levels6_f16w" / "mesh" / "dropin" / "alt_precision"   (N=1 only) the other
                   BASELINE configs and surfaces, each with its own timing and parity deltas
 
+``--dump-outputs DIR`` writes what the timed path returned for its last step (the last frame of the last pass) as
+float32 / float64 ``DIR/<name>.npy`` files (dump_last_step); the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
+
 Test hooks for the N > 1 code on a ONE-GPU box (tests/test_dropin_gpu.py): MONOPORT_BENCH_ONE_GPU_TEST=1 (--gpus 2,
 both ranks on device 0, collectives over gloo) and MONOPORT_BENCH_FORCE_GROUP=1 (--gpus 1 inside a one-rank RCCL
 group: the same collective calls on the real backend).
@@ -344,6 +348,46 @@ def timed_passes(job, pipe, batch, with_color, passes, collective=True, want_sta
     return elapsed, statuses, gather_checked[0]
 
 
+DUMP_VOLUME_SAMPLE = 1 << 22  # voxels of the volume --dump-outputs writes (16 MB; a 257^3 volume is 68 MB)
+DUMP_MAX_BYTES = 64 << 20
+DROPIN_MIN_FRAMES = 96  # the default run's drop-in leg: long against the stage pipeline's fill and drain
+
+
+def dump_last_step(job, pipe, with_color, out_dir):
+    """--dump-outputs: what a caller of the timed path holds after its last step (frame steps + warmup - 1 of the
+    last pass), as .npy files in `out_dir`: `render` (and `render_color` with netC), `status` (success flag, then
+    the points evaluated per octree level), `vertices_x` / `_y` / `_z` / `_normal` (forward_vertices, `count`
+    rows) and `volume_sample` (the volume at DUMP_VOLUME_SAMPLE flat voxel indices drawn with replacement from a
+    generator seeded with 0, in increasing order: the same voxels in every run).  Integer outputs are written as float64
+    (exact).  Rank 0 writes its own frame; returns the frame id and the file names."""
+    if job.rank != 0:
+        return None
+    slot = pipe.slots[(pipe.n_submitted - 1) % len(pipe.slots)]
+    slot.wait()
+    b = slot.n_active - 1
+    x, y, z, nrm, count = slot.vertices[b]
+    c = min(int(count.item()), x.shape[0])
+    vol = slot.volumes[b].reshape(-1)
+    idx = np.sort(np.random.default_rng(0).integers(0, vol.numel(), DUMP_VOLUME_SAMPLE))
+    arrays = {"render": slot.renders[b].cpu().numpy(),
+              "status": slot.status[b].cpu().numpy().astype(np.float64),
+              "vertices_x": x[:c].cpu().numpy().astype(np.float64),
+              "vertices_y": y[:c].cpu().numpy().astype(np.float64),
+              "vertices_z": z[:c].cpu().numpy(),
+              "vertices_normal": nrm[:c].cpu().numpy(),
+              "volume_sample": vol[torch.from_numpy(idx).to(vol.device)].cpu().numpy()}
+    if with_color:
+        arrays["render_color"] = slot.renders_tex[b].cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "--dump-outputs: %d bytes" % total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return {"dir": out_dir, "frame": (job.steps + job.warm - 1) * job.world + job.rank, "bytes": int(total),
+            "files": sorted(name + ".npy" for name in arrays)}
+
+
 def roofline_leg(job, pipe, batch, resolutions, with_color):
     """The same frames again on ONE stream with every fused-query launch bracketed by HIP events on
     its launch stream (concurrent slots would share CUs) -> per-launch durations and point counts
@@ -621,11 +665,13 @@ def build_pipeline(job, depth, batch, use_graph, resolutions, with_color, precis
 
 
 def measure_config(job, depth, batch, use_graph, resolutions, with_color, precision, passes,
-                   roofline=True, final_level="dilate3"):
+                   roofline=True, final_level="dilate3", dump_dir=None):
     """Build a pipeline for one configuration, run the timed passes (+ the roofline leg), return
-    (summary dict, pipeline).  The caller closes the pipeline."""
+    (summary dict, pipeline).  The caller closes the pipeline.  With `dump_dir` the outputs of the last
+    timed step are written there (dump_last_step) before anything else runs on the pipeline."""
     pipe, use_graph = build_pipeline(job, depth, batch, use_graph, resolutions, with_color, precision, final_level)
     elapsed, statuses, checked = timed_passes(job, pipe, batch, with_color, passes)
+    dumped = dump_last_step(job, pipe, with_color, dump_dir) if dump_dir else None
     # a pass is as slow as its slowest rank; the median pass is the reported one
     per_pass = job.reduce_max(elapsed)
     order = sorted(per_pass)
@@ -646,6 +692,7 @@ def measure_config(job, depth, batch, use_graph, resolutions, with_color, precis
         "points_per_level": (statuses[:, 1:].sum(0) / float(statuses.shape[0])).tolist() if statuses is not None else None,
         "ms_per_step_per_rank": [e / job.steps * 1e3
                                  for e in job.gather_floats(sorted(elapsed)[len(elapsed) // 2])],
+        "dumped_outputs": dumped,
     }
     if roofline:
         res["roof"] = roofline_leg(job, pipe, batch, resolutions, with_color)
@@ -659,7 +706,8 @@ def parse_args(argv):
                     help="frames in the timed region (default 32 = ONE slot submission of 32 frames, every octree level one "
                          "launch of kMaxFrames frames: 194-195 recon/s, passes within 0.5 %%; the driver's 20 = one "
                          "submission of 20: 190; several overlapping submissions -- 48 = 3 x 16, 64 = 2 x 32 -- are no "
-                         "faster since round 5 and their passes scatter by +- 4 %%)")
+                         "faster since round 5 and their passes scatter by +- 4 %%).  With --mode dropin the stage "
+                         "pipeline's fill and drain are inside those frames: 96 or more for a steady-state figure")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--depth", type=int, default=3, help="pipeline slots (streams) per GPU")
     ap.add_argument("--batch", type=int, default=None,
@@ -715,6 +763,10 @@ def parse_args(argv):
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="join the ranks, census the devices, one frame-sized gather, print JSON; no "
                          "measurement (launch-path check; runs without GPUs over gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed passes, write the outputs of the last timed step (render, status, vertices, "
+                         "a seeded sample of the volume) as DIR/<name>.npy, float32 / float64, at most 64 MB "
+                         "(dump_last_step; --mode pipeline only)")
     return ap.parse_args(argv)
 
 
@@ -723,6 +775,10 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if args.dump_outputs and args.mode != "pipeline":
+        raise SystemExit("--dump-outputs is for --mode pipeline (the timed path whose outputs it writes)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args, argv)  # does not return
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
@@ -794,7 +850,8 @@ def main(argv=None):
     else:
         depth, batch = args.depth, pick_batch(args.steps, args.batch, args.depth)
     main_res, pipe = measure_config(job, depth, batch, not args.no_graph, resolutions,
-                                    args.with_color, args.precision, args.passes, final_level=args.final_level)
+                                    args.with_color, args.precision, args.passes, final_level=args.final_level,
+                                    dump_dir=args.dump_outputs)
     use_graph = main_res["use_graph"]
     roof = main_res["roof"]
     # what the f32 matrix pipe of THIS box holds right now, and at which clock (mp_mfma_clock_probe, a 30-50 ms
@@ -1108,11 +1165,14 @@ def main(argv=None):
                             "100 MHz s_memrealtime tick averaged over the workgroups"},
             },
         }
+        if main_res["dumped_outputs"] is not None:
+            out["dumped_outputs"] = main_res["dumped_outputs"]
         out.update(extras)
         if alt is not None:
             out["alt_precision"] = alt
         if world == 1 and not args.no_dropin and not args.with_color and args.precision == "f32":
-            out["dropin"] = dropin_surface(device, args.steps, args.warmup, resolutions, args.passes)
+            out["dropin"] = dropin_surface(device, max(args.steps, DROPIN_MIN_FRAMES), args.warmup, resolutions,
+                                           args.passes)
             out["latency_ms_single_frame"] = out["dropin"]["latency_ms_single_frame"]
             if args.soak > 0:
                 out["dropin"]["soak"] = soak(device, args.soak, resolutions)

@@ -23,8 +23,8 @@ def dropin_surface(device, n_frames, n_warm, resolutions, passes=5, legs=("per_f
     structure; and the headline of this leg, the same list with the three heavy stages wrapped in
     stage_pipeline.Coalesced -- when frames queue up in front of a stage it serves up to 8 of them in
     one call (a batched netG.filter, Seg3dLossless.forward_many = one mp_recon_batch, one host sync
-    for all vertex counts); per-frame results are unchanged.  Also the latency of a single frame run
-    stage by stage."""
+    for all vertex counts); per-frame results are unchanged.  A timed pass is exactly `n_frames` frames, the
+    pipeline's fill and drain included.  Also the latency of a single frame run stage by stage."""
     from monoport_amd.implicit_seg.functional import Seg3dLossless
     from monoport_amd.recon import colorization, forward_vertices, forward_vertices_many
     from monoport_amd.stage_pipeline import Coalesced, StagePipeline
@@ -138,7 +138,6 @@ def dropin_surface(device, n_frames, n_warm, resolutions, passes=5, legs=("per_f
     latency_ms = float(np.median(lat[3:])) * 1e3
 
     # throughput: the same list on the stage pipeline (thread + stream per stage, FIFO order)
-    n_frames = max(n_frames, 96)  # long against the pipeline's fill and drain, which are INSIDE the timed region
     passes = max(passes, 5)
 
     def one_pass(coalesce, in_flight, validate):

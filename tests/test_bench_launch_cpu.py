@@ -78,6 +78,16 @@ def test_measurement_refuses_without_enough_gpus():
         assert "needs MI355X" in res.stderr
 
 
+def test_arguments_without_a_timed_path_are_refused():
+    """No timed step (--steps 0), or --dump-outputs where the timed path is not the one it writes (--mode dropin):
+    refused before anything is measured or written."""
+    for args, msg in ((["--steps", "0"], "--steps must be >= 1"),
+                      (["--mode", "dropin", "--dump-outputs", "unused_dump_dir"], "--dump-outputs is for --mode pipeline")):
+        res = _run([sys.executable, BENCH, "--gpus", "1"] + args)
+        assert res.returncode != 0 and msg in res.stderr and not _json_lines(res.stdout)
+    assert not os.path.exists(os.path.join(ROOT, "unused_dump_dir"))
+
+
 def test_in_flight_layout():
     sys.path.insert(0, ROOT)
     import bench

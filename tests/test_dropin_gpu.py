@@ -530,6 +530,45 @@ def test_bench_collectives_on_rccl_one_rank_group():
     assert 0.5 < out["scaling_vs_single_rank"]["efficiency"] < 1.5
 
 
+def test_bench_dump_outputs_of_the_last_step(tmp_path):
+    """bench.py --dump-outputs DIR: the last timed step's render, status row, vertices and volume sample as float32 /
+    float64 .npy files within 64 MB -- and, the inputs being seeded, the same files from a second run of the same
+    command (what lets two builds be compared output for output)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+               "--passes", "1", "--no-extras", "--dump-outputs", str(d)]
+        res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == 4 and out["dumped_outputs"]["frame"] == 4 + 2 - 1
+        files = sorted(os.listdir(d))
+        assert files == out["dumped_outputs"]["files"]
+        arrays = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        assert arrays["render"].shape == (257, 257, 3) and arrays["status"][0] == 1 and arrays["status"][1] == 17 ** 3
+        n = arrays["vertices_x"].shape[0]
+        assert n > 0 and arrays["vertices_y"].shape == arrays["vertices_z"].shape == (n,)
+        assert arrays["vertices_normal"].shape == (n, 3)
+        v = arrays["volume_sample"]
+        assert v.shape == (1 << 22,) and 0 < float((v > 0.5).mean()) < 1
+        dumps.append(arrays)
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name]), name
+
+
 def test_netg_query_uses_the_skip_table_by_default(monkeypatch):
     """MonoPortNet.bind makes and registers the skip table of a newly bound feature map
     (ops.SKIP_TABLE, default on): netG.query and the fused octree engine then blend table rows.  The
