@@ -194,9 +194,10 @@ def test_f16x3_query_is_f32_class(ops, oracle, name):
     assert (out16[:, outside] == 0).all()
 
 
-@pytest.mark.parametrize("n", [1, 127, 128, 129, 1000])
+@pytest.mark.parametrize("n", [1, 95, 96, 97, 127, 128, 129, 1000])
 def test_f16x3_ragged_sizes_and_large_weights(ops, oracle, n):
-    """128-point tiles: ragged tails; weights spanning 1e-3..40 exercise the per-layer scaling."""
+    """96-point tiles (kQ16Nb = 3): ragged tails at the tile edges and past them; weights spanning
+    1e-3..40 exercise the per-layer scaling."""
     layers = syn.body_mlp("G", noise=0.3, seed=n)  # entries from ~1e-3 up to k = 40
     f = syn.body_feat(256, 128, 128, 6)
     p = syn.rand_points(n, 200 + n, 1.05)

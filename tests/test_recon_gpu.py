@@ -460,7 +460,7 @@ def test_config5_513_fp16_weights(ops, oracle, precision):
     assert dmax <= (1e-3 if precision == "f16w" else 0.5)
 
 
-@pytest.mark.parametrize("precision", ["f32", "f16x3"])
+@pytest.mark.parametrize("precision", ["f32", "f16x3", "f16w", "f16"])
 def test_recon_batch_equals_single_frames(ops, oracle, precision):
     """mp_recon_batch (one fused-query launch per level for all frames) is bit-identical to one
     mp_recon per frame: different feature maps and cameras per frame, including an EMPTY frame."""
