@@ -100,20 +100,37 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &p, const float (&v
   // workgroup's per-group sums (fixed order) and hands them on (gn_tail.h: fire-and-forget) ----
   double *cs1 = reinterpret_cast<double *>(smem);         // [CW][NCH][2] per-channel sums of y
   double *cs2 = reinterpret_cast<double *>(smem + 2048);  // ... of y2
-  auto to_lds = [&](double *cs, float (&a1)[TN], float (&a2)[TN]) {
+  // (a1, a2): a lane's sums of x - k over its NR pixels x[.][tt] of channel register tt, k = that half-wave's pivot
+  // (read again from x, which stays live for the stores, rather than kept in TN registers through the sums)
+  auto to_lds = [&](double *cs, float (&a1)[TN], float (&a2)[TN], const float (&x)[NR][TN]) {
     // sum over the 32 lanes that share h (the pixels); lane kHalfSumLane of each half then holds the row sums
+    float k[TN];
 #pragma unroll
     for (int tt = 0; tt < TN; ++tt) {
       a1[tt] = half_wave_sum(a1[tt]);
       a2[tt] = half_wave_sum(a2[tt]);
+      k[tt] = half_wave_pivot(x[0][tt]);  // the whole wave: DPP reads lanes the branch below turns off
     }
     if (j == kHalfSumLane) {
 #pragma unroll
       for (int tt = 0; tt < TN; ++tt) {
         const int t = t0 + tt;
         const int idx = cwi * NCH + 32 * rbi + (t & 3) + 8 * (t >> 2) + 4 * h;
-        cs[2 * idx] = (double)a1[tt];
-        cs[2 * idx + 1] = (double)a2[tt];
+        gn_unpivot(a1[tt], a2[tt], k[tt], 32.0 * NR, cs[2 * idx], cs[2 * idx + 1]);
+      }
+    }
+  };
+  // f32 sums of x - k around the half-wave pivot k of each channel register (gn_tail.h: gn_unpivot)
+  auto run_sums = [&](const float (&x)[NR][TN], float (&a1)[TN], float (&a2)[TN]) {
+#pragma unroll
+    for (int tt = 0; tt < TN; ++tt) {
+      const float k = half_wave_pivot(x[0][tt]);
+      a1[tt] = a2[tt] = 0.0f;
+#pragma unroll
+      for (int n = 0; n < NR; ++n) {
+        const float d = x[n][tt] - k;
+        a1[tt] += d;
+        a2[tt] = fmaf(d, d, a2[tt]);
       }
     }
   };
@@ -127,30 +144,19 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs &p, const float (&v
   }
   if (st1) {
     float s1[TN], s2[TN];
-#pragma unroll
-    for (int tt = 0; tt < TN; ++tt) s1[tt] = s2[tt] = 0.0f;
-#pragma unroll
-    for (int n = 0; n < NR; ++n)
-#pragma unroll
-      for (int tt = 0; tt < TN; ++tt) {
-        s1[tt] += v[n][tt];
-        s2[tt] = fmaf(v[n][tt], v[n][tt], s2[tt]);
-      }
-    to_lds(cs1, s1, s2);
+    run_sums(v, s1, s2);
+    to_lds(cs1, s1, s2, v);
   }
   if (cat) {
-    float q1[TN], q2[TN];
-#pragma unroll
-    for (int tt = 0; tt < TN; ++tt) q1[tt] = q2[tt] = 0.0f;
 #pragma unroll
     for (int n = 0; n < NR; ++n)
 #pragma unroll
-      for (int tt = 0; tt < TN; ++tt) {
-        u[n][tt] += v[n][tt];
-        q1[tt] += u[n][tt];
-        q2[tt] = fmaf(u[n][tt], u[n][tt], q2[tt]);
-      }
-    if (st2) to_lds(cs2, q1, q2);
+      for (int tt = 0; tt < TN; ++tt) u[n][tt] += v[n][tt];
+    if (st2) {
+      float q1[TN], q2[TN];
+      run_sums(u, q1, q2);
+      to_lds(cs2, q1, q2, u);
+    }
   }
   if (st1 || st2) {
     __syncthreads();
@@ -1368,31 +1374,34 @@ __global__ __launch_bounds__(256, 2) void conv1x1_kernel(Conv1Args p, const floa
     for (int t = 0; t < 16; ++t) {
       float b = 0.0f;
       if constexpr (F16) b = p.bias ? p.bias[32 * (rb0 + m) + (t & 3) + 8 * (t >> 2) + 4 * h] : 0.0f;
-      s1[t] = s2[t] = 0.0f;
 #pragma unroll
       for (int n = 0; n < 2; ++n) {
         float v = F16 ? acc[m][n][t] * inv_scale + b : acc[m][n][t];
         if (p.res)
           v += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_res, vo + 128 * n, so_of(m, t), 0));
         acc[m][n][t] = v;
-        s1[t] += v;
-        s2[t] = fmaf(v, v, s2[t]);
       }
+      // f32 sums of x - k around the half-wave pivot k (gn_tail.h: gn_unpivot)
+      const float k = half_wave_pivot(acc[m][0][t]);
+      const float d0 = acc[m][0][t] - k, d1 = acc[m][1][t] - k;
+      s1[t] = d0 + d1;
+      s2[t] = fmaf(d1, d1, d0 * d0);
     }
     if (gn_wanted(p.fin)) {
       // GroupNorm(32, Cout) statistics of the output (bn_end after conv_last; the first GroupNorm of
       // the next stack after x + bl(.) + al(.)), handed on before the bulk stores (gn_tail.h)
+      float k[16];
 #pragma unroll
       for (int t = 0; t < 16; ++t) {
         s1[t] = half_wave_sum(s1[t]);
         s2[t] = half_wave_sum(s2[t]);
+        k[t] = half_wave_pivot(acc[m][0][t]);  // the whole wave: DPP reads lanes the branch below turns off
       }
       if (j == kHalfSumLane) {
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
           const int lc = 32 * (MRW * wv + m) + (t & 3) + 8 * (t >> 2) + 4 * h;
-          cs[2 * lc] = (double)s1[t];
-          cs[2 * lc + 1] = (double)s2[t];
+          gn_unpivot(s1[t], s2[t], k[t], 64.0, cs[2 * lc], cs[2 * lc + 1]);
         }
       }
     }

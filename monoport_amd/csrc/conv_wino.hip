@@ -145,29 +145,41 @@ struct WinoTail {
 
   // per-channel (sum, sum of squares) of a wave's pixels -> LDS, the channels of one lane that share a GroupNorm group
   // added up first: rows (t & 3) of a register quad are 4 consecutive channels, so with >= 4 channels per group one
-  // cross-lane sum serves four registers (2 with 2 channels per group): 4 (2) x fewer DPP chains
-  __device__ __forceinline__ void to_lds(double *cs, const float (&a1)[TN], const float (&a2)[TN], int cpg) const {
+  // cross-lane sum serves four registers (2 with 2 channels per group): 4 (2) x fewer DPP chains.  The f32 sums are of
+  // x - k, k = the half-wave pivot of the quad's (pair's) first register (gn_tail.h: gn_unpivot).
+  __device__ __forceinline__ void to_lds(double *cs, const f32x2 (&x)[TN], int cpg) const {
+    auto sums = [&](int t, float k, float &a1, float &a2) {
+      const float d0 = x[t].x - k, d1 = x[t].y - k;
+      a1 = d0 + d1;
+      a2 = fmaf(d1, d1, d0 * d0);
+    };
     if (cpg >= 4) {
 #pragma unroll
       for (int q = 0; q < TN / 4; ++q) {
-        const float s1 = half_wave_sum((a1[4 * q] + a1[4 * q + 1]) + (a1[4 * q + 2] + a1[4 * q + 3]));
-        const float s2 = half_wave_sum((a2[4 * q] + a2[4 * q + 1]) + (a2[4 * q + 2] + a2[4 * q + 3]));
+        const float k = half_wave_pivot(x[4 * q].x);
+        float a1[4], a2[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sums(4 * q + i, k, a1[i], a2[i]);
+        const float s1 = half_wave_sum((a1[0] + a1[1]) + (a1[2] + a1[3]));
+        const float s2 = half_wave_sum((a2[0] + a2[1]) + (a2[2] + a2[3]));
         if (j == kHalfSumLane) {
           const int idx = r_o * NCH + 32 * rbi + 8 * ((t0 >> 2) + q) + 4 * h;
-          cs[2 * idx] = (double)s1;
-          cs[2 * idx + 1] = (double)s2;
+          gn_unpivot(s1, s2, k, 256.0, cs[2 * idx], cs[2 * idx + 1]);
         }
       }
     } else {
 #pragma unroll
       for (int q = 0; q < TN / 2; ++q) {
-        const float s1 = half_wave_sum(a1[2 * q] + a1[2 * q + 1]);
-        const float s2 = half_wave_sum(a2[2 * q] + a2[2 * q + 1]);
+        const float k = half_wave_pivot(x[2 * q].x);
+        float a1[2], a2[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) sums(2 * q + i, k, a1[i], a2[i]);
+        const float s1 = half_wave_sum(a1[0] + a1[1]);
+        const float s2 = half_wave_sum(a2[0] + a2[1]);
         if (j == kHalfSumLane) {
           const int tr = t0 + 2 * q;
           const int idx = r_o * NCH + 32 * rbi + (tr & 3) + 8 * (tr >> 2) + 4 * h;
-          cs[2 * idx] = (double)s1;
-          cs[2 * idx + 1] = (double)s2;
+          gn_unpivot(s1, s2, k, 128.0, cs[2 * idx], cs[2 * idx + 1]);
         }
       }
     }
@@ -178,24 +190,11 @@ struct WinoTail {
     const int tid = threadIdx.x;
     double *cs1 = reinterpret_cast<double *>(smem);             // [2 rows][NCH][2] sums of y (first channel of a quad / pair)
     double *cs2 = reinterpret_cast<double *>(smem + NCH * 32);  // ... of y2
-    if (st1) {
-      float s1[TN], s2[TN];
-#pragma unroll
-      for (int t = 0; t < TN; ++t) {
-        s1[t] = pr[t].x + pr[t].y;
-        s2[t] = fmaf(pr[t].y, pr[t].y, pr[t].x * pr[t].x);
-      }
-      to_lds(cs1, s1, s2, p.fin.c / 32);
-    }
+    if (st1) to_lds(cs1, pr, p.fin.c / 32);
     if (cat) {
-      float q1[TN], q2[TN];
 #pragma unroll
-      for (int t = 0; t < TN; ++t) {
-        u[t] = u[t] + pr[t];
-        q1[t] = u[t].x + u[t].y;
-        q2[t] = fmaf(u[t].y, u[t].y, u[t].x * u[t].x);
-      }
-      if (st2) to_lds(cs2, q1, q2, p.fin2.c / 32);
+      for (int t = 0; t < TN; ++t) u[t] = u[t] + pr[t];
+      if (st2) to_lds(cs2, u, p.fin2.c / 32);
     }
     if (st1 || st2) {
       __syncthreads();

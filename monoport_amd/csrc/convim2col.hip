@@ -204,18 +204,20 @@ __global__ __launch_bounds__(256, kConvkWg) void convk_kernel(ConvKArgs p) {
   // ---- epilogue: + bias, NCHW store, GroupNorm statistics of the output ----
   constexpr int NCH = 32 * RBW;
   const long long hwo = (long long)p.ho * p.wo;
-  float s1[16], s2[16];
+  float s1[16], s2[16], k[16];  // f32 sums of x - k around the half-wave pivot k (gn_tail.h: gn_unpivot)
 #pragma unroll
   for (int t = 0; t < 16; ++t) {
     const int co = 32 * rb + (t & 3) + 8 * (t >> 2) + 4 * h;
     const float b = p.bias ? p.bias[co] : 0.0f;
+    k[t] = half_wave_pivot(acc[0][t] + b);
     s1[t] = s2[t] = 0.0f;
 #pragma unroll
     for (int n = 0; n < NR; ++n) {
       const float v = acc[n][t] + b;
       p.y[((long long)img * p.cout + co) * hwo + (long long)oy * p.wo + ox0 + 32 * (cwi * NR + n) + j] = v;
-      s1[t] += v;
-      s2[t] = fmaf(v, v, s2[t]);
+      const float d = v - k[t];
+      s1[t] += d;
+      s2[t] = fmaf(d, d, s2[t]);
     }
   }
   if (gn_wanted(p.fin)) {
@@ -229,8 +231,7 @@ __global__ __launch_bounds__(256, kConvkWg) void convk_kernel(ConvKArgs p) {
 #pragma unroll
       for (int t = 0; t < 16; ++t) {
         const int idx = cwi * NCH + 32 * rbi + (t & 3) + 8 * (t >> 2) + 4 * h;
-        cs[2 * idx] = (double)s1[t];
-        cs[2 * idx + 1] = (double)s2[t];
+        gn_unpivot(s1[t], s2[t], k[t], 32.0 * NR, cs[2 * idx], cs[2 * idx + 1]);
       }
     }
     __syncthreads();

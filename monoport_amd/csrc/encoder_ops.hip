@@ -27,22 +27,27 @@ __global__ __launch_bounds__(kGnThreads) void gn_partial_kernel(const float *__r
   const long long per = (group_elems / 4 + kGnSlices - 1) / kGnSlices;  // float4 per slice
   const long long v0 = s * per, v1 = min(v0 + per, group_elems / 4);
   const f32x4 *xp = reinterpret_cast<const f32x4 *>(x + g * group_elems);
-  float s1 = 0.f, s2 = 0.f;  // per-thread f32 partials over <= a few hundred values
-  double d1 = 0.0, d2 = 0.0;
-  int k = 0;
+  // per-thread f32 partials of x - pv over <= a few hundred values, pv = the thread's first value (gn_tail.h: gn_unpivot)
+  const float pv = v0 + threadIdx.x < v1 ? xp[v0 + threadIdx.x][0] : 0.f;
+  float s1 = 0.f, s2 = 0.f;
+  double e1 = 0.0, e2 = 0.0;
+  int k = 0, cnt = 0;
   for (long long i = v0 + threadIdx.x; i < v1; i += kGnThreads) {
-    const f32x4 v = xp[i];
+    const f32x4 v = xp[i] - pv;
     s1 += (v[0] + v[1]) + (v[2] + v[3]);
     s2 += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+    cnt += 4;
     if (++k == 64) {  // flush to double regularly: keeps the f32 running sums short
-      d1 += s1;
-      d2 += s2;
+      e1 += s1;
+      e2 += s2;
       s1 = s2 = 0.f;
       k = 0;
     }
   }
-  d1 += s1;
-  d2 += s2;
+  e1 += s1;
+  e2 += s2;
+  double d1, d2;
+  gn_unpivot_d(e1, e2, pv, cnt, d1, d2);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     d1 += __shfl_down(d1, o);
@@ -207,29 +212,37 @@ __global__ __launch_bounds__(kGnThreads) void ew_gn_kernel(Op op, long long grou
   const long long per = (group_elems / V + kGnSlices - 1) / kGnSlices;  // steps per slice
   const long long v0 = s * per, v1 = min(v0 + per, group_elems / V);
   op.begin(gi);
-  float s1 = 0.f, s2 = 0.f;
-  double d1 = 0.0, d2 = 0.0;
-  int k = 0;
+  // per-thread f32 partials of x - pv, pv = the thread's first output (gn_tail.h: gn_unpivot)
+  float s1 = 0.f, s2 = 0.f, pv = 0.f;
+  double e1 = 0.0, e2 = 0.0;
+  int k = 0, cnt = 0;
   for (long long i = v0 + threadIdx.x; i < v1; i += kGnThreads) {
     if constexpr (V == 4) {
-      const f32x4 v = op.run(gi, i, group_elems);
+      f32x4 v = op.run(gi, i, group_elems);
+      if (cnt == 0) pv = v[0];
+      v -= pv;
       s1 += (v[0] + v[1]) + (v[2] + v[3]);
       s2 += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
     } else {
-      const float v = op.run(gi, i, group_elems);
+      float v = op.run(gi, i, group_elems);
+      if (cnt == 0) pv = v;
+      v -= pv;
       s1 += v;
       s2 += v * v;
     }
+    cnt += V;
     if (++k == 64) {
-      d1 += s1;
-      d2 += s2;
+      e1 += s1;
+      e2 += s2;
       s1 = s2 = 0.f;
       k = 0;
     }
   }
   if (!gn_wanted(fin)) return;
-  d1 += s1;
-  d2 += s2;
+  e1 += s1;
+  e2 += s2;
+  double d1, d2;
+  gn_unpivot_d(e1, e2, pv, cnt, d1, d2);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     d1 += __shfl_down(d1, o);
@@ -409,7 +422,8 @@ __global__ __launch_bounds__(kGnThreads) void upsample_add_gn_kernel(const float
 #pragma unroll
   for (int i = 0; i < 4; ++i) xx[i] = min(max(ix - 1 + i, 0), w - 1);
 
-  float s1 = 0.f, s2 = 0.f;
+  float s1 = 0.f, s2 = 0.f, pv = 0.f;  // f32 sums of x - pv, pv = the thread's first output (gn_tail.h: gn_unpivot)
+  int cnt = 0;
   for (int r0 = s * rps; r0 < (s + 1) * rps; r0 += kUpBand) {  // row index inside the group's cpg * ho rows
     const int pl = r0 / ho, oy0 = r0 - pl * ho;                // bands do not cross planes: ho % kUpBand == 0
     const long long plane = (long long)gi * cpg + pl;
@@ -436,12 +450,16 @@ __global__ __launch_bounds__(kGnThreads) void upsample_add_gn_kernel(const float
       const long long e = (plane * ho + oy) * wo + ox;
       const float v = add ? add[e] + acc : acc;
       y[e] = v;
-      s1 += v;
-      s2 += v * v;
+      if (cnt == 0) pv = v;
+      const float d = v - pv;
+      s1 += d;
+      s2 += d * d;
+      ++cnt;
     }
   }
   if (!gn_wanted(fin)) return;
-  double d1 = s1, d2 = s2;  // <= a few hundred values per thread
+  double d1, d2;  // <= a few hundred values per thread
+  gn_unpivot(s1, s2, pv, cnt, d1, d2);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     d1 += __shfl_down(d1, o);

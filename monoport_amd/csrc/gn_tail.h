@@ -24,7 +24,9 @@
 //     on ONE address serialise at ~80 ns each, and a batch-1 launch sends 250-1000 of them per
 //     group (+20 us on a 20 us convolution, profiles/r03f); workgroup w adds to copy w % R, the
 //     consumer adds the copies up (integers again: exact);
-//   * a producer workgroup folds its per-channel sums to per-group doubles in LDS (fixed order) and
+//   * a producer adds its values in short f32 runs around a pivot (gn_unpivot below: the f32 sums never hold
+//     the group's mean, only the deviations from it), restores the plain sums in double,
+//   * folds its per-channel sums to per-group doubles in LDS (fixed order) and
 //     issues 4 atomics per group it covers, without using their return values or waiting for them;
 //   * a consumer workgroup reads the R x 32 x 4 words of its image (L2 hits after the first workgroup),
 //     computes mean / rstd in double with gn_finalize_kernel's formulas, keeps them in LDS and
@@ -56,6 +58,35 @@ __device__ __forceinline__ float half_wave_sum(float v) {
   // row_bcast15 into rows 1 and 3: lanes 16-31 / 48-63 add the sum of lanes 0-15 / 32-47
   v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x142, 0xA, 0xF, false));
   return v;
+}
+
+// Producers never add x and x^2 in f32: a group with |mean| / std = r puts r^2 times its variance into the sum of
+// squares, and f32 rounding of that sum swamps the variance from r ~ 100 on (oracle/gn_stats.py).  Every f32 run
+// -- the values one lane, or the 32 lanes half_wave_sum adds, take before going to double -- sums d = x - k and
+// d^2 around a pivot k shared by the run (one of its real values), and gn_unpivot restores the plain sums in
+// double: sum x = sum d + n k, sum x^2 = sum d^2 + 2 k sum d + n k^2, n = the run's count of real values.
+
+// The pivot of a half-wave run: lane 0's value in lanes 0-31, lane 32's in lanes 32-63, in a VGPR (two DPP moves,
+// no scalar registers): row_newbcast:0 gives every row of 16 lanes its lane 0, row_bcast15 then gives rows 1 / 3 the
+// value of lane 15 / 47 (= lane 0 / 32).  Called by the whole wave.
+__device__ __forceinline__ float half_wave_pivot(float v) {
+  int x = __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x150, 0xF, 0xF, false);
+  x = __builtin_amdgcn_update_dpp(x, x, 0x142, 0xA, 0xF, false);
+  return __builtin_bit_cast(float, x);
+}
+
+// (s1, s2) = f32 (sum, sum of squares) of n values x - k -> (a, b) = (sum x, sum x^2) in double
+__device__ __forceinline__ void gn_unpivot(float s1, float s2, float k, double n, double &a, double &b) {
+  const double dk = k, d1 = s1;
+  a = d1 + n * dk;
+  b = (double)s2 + 2.0 * dk * d1 + n * dk * dk;
+}
+
+// the same with the f32 run sums already added up in double (runs that share one pivot)
+__device__ __forceinline__ void gn_unpivot_d(double e1, double e2, float k, double n, double &a, double &b) {
+  const double dk = k;
+  a = e1 + n * dk;
+  b = e2 + 2.0 * dk * e1 + n * dk * dk;
 }
 
 // x -> (hi, lo) with x = hi * 2^-16 + lo * 2^-64, lo in [0, 2^48); exact for |x| < 2^36, rounded to a
