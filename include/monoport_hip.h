@@ -50,6 +50,16 @@ enum {
 /* SurfaceClassifier last_op (heads/SurfaceClassifier.py:68-69, :77, :85) */
 enum { MP_ACT_NONE = 0, MP_ACT_SIGMOID = 1, MP_ACT_TANH = 2 };
 
+/* projection of a frame's points into its image (MonoPortNet's opt_net.projection, MonoPortNet.py:20-27).
+ * Every entry point without a `projection` argument projects orthogonally. */
+enum {
+  MP_PROJ_ORTHOGONAL = 0, /* xyz = R p + t (geometry.py:19-34) */
+  MP_PROJ_PERSPECTIVE = 1 /* (R p + t) = (u, v, z) -> xyz = (u / z, v / z, z) (geometry.py:37-55); a point with
+                             z == 0 projects to +-inf / NaN, and a fused query returns NaN for it in every channel
+                             (the reference's grid_sample samples NaN there) -- every other out-of-image point is
+                             exactly 0.0f; points behind the camera (z < 0) are sampled like any other */
+};
+
 /* arithmetic of the MLP GEMMs (mp_mlp_set_precision) */
 enum {
   MP_PREC_F32 = 0,   /* v_mfma_f32_32x32x2_f32: exact f32 products, the default */
@@ -164,6 +174,10 @@ int mp_index(mp_ctx *ctx, const float *feat_hwc, int c, int h, int w, const floa
  * points/out [3,N]; calib = row-major [>=3,4] matrix (rows 0-2 used, row stride 4). */
 int mp_orthogonal(mp_ctx *ctx, const float *points, int64_t n, const float *calib, float *out,
                   mp_stream stream);
+/* perspective(points, calib) (geometry.py:37-55, transforms=None): u, v, z = R p + t as in mp_orthogonal,
+ * then out = (u / z, v / z, z) with IEEE divisions (+-inf / NaN where z == 0).  Layout as mp_orthogonal. */
+int mp_perspective(mp_ctx *ctx, const float *points, int64_t n, const float *calib, float *out,
+                   mp_stream stream);
 /* MonoPortNet.query in eval mode, one feature stage (MonoPortNet.py:48-91):
  * project -> in-image mask -> z*z_scale -> bilinear sample -> skip-concat MLP -> mask.
  * points: element (c, i) at points[i*stride_n + c*stride_c] (so both the [3,N] layout netG.query
@@ -172,6 +186,17 @@ int mp_orthogonal(mp_ctx *ctx, const float *points, int64_t n, const float *cali
 int mp_query(mp_ctx *ctx, int mlp, const float *feat_hwc, int c, int h, int w,
              const float *points, int64_t n, int64_t stride_n, int64_t stride_c,
              const float *calib, float z_scale, float *out, mp_stream stream);
+
+/* mp_query over n_frames (1..32) independent frames in ONE launch, n points each (MonoPortNet.query with
+ * B > 1).  feat_hwc / points / calib / out are HOST arrays of n_frames device pointers, each as in mp_query
+ * (one n and one stride convention for all); projection is a HOST array of n_frames MP_PROJ_* modes.  Each
+ * frame takes its registered skip table under the same all-or-none rule as every fused launch: if EVERY
+ * frame's map has one, the launch blends table rows.  A frame's result equals mp_query's bit for bit when
+ * both take the same kernel. */
+int mp_query_batch(mp_ctx *ctx, int mlp, int n_frames, const float *const *feat_hwc, int c, int h, int w,
+                   const float *const *points, int64_t n, int64_t stride_n, int64_t stride_c,
+                   const float *const *calib, const int *projection /*host*/, float z_scale,
+                   float *const *out, mp_stream stream);
 
 /* SurfaceClassifier.forward on explicit features (heads/SurfaceClassifier.py:39-71; the shape of
  * the reference's own micro-benchmark, :95-116): feature [C+1,N] (sampled features + z_feat as
@@ -194,6 +219,13 @@ int mp_query_counted_batch(mp_ctx *ctx, int mlp, int n_frames, const float *cons
                            int h, int w, const float *const *points, int64_t capacity,
                            const int32_t *const *count, const float *const *calib, float z_scale,
                            float *const *out, mp_stream stream);
+/* mp_query_counted_batch with a per-frame projection: projection is a HOST array of n_frames MP_PROJ_*
+ * modes (NULL = every frame orthogonal, which is mp_query_counted_batch). */
+int mp_query_counted_batch_proj(mp_ctx *ctx, int mlp, int n_frames, const float *const *feat_hwc, int c,
+                                int h, int w, const float *const *points, int64_t capacity,
+                                const int32_t *const *count, const float *const *calib,
+                                const int *projection /*host*/, float z_scale, float *const *out,
+                                mp_stream stream);
 
 /* ---- coarse-to-fine reconstruction --------------------------------------------------------- */
 /* Replaces implicit_seg.functional.Seg3dLossless.forward(faster=True) driving query_func
@@ -241,7 +273,7 @@ int mp_recon_batch_ex(mp_ctx *ctx, int mlp, int n_frames, const float *const *fe
  * a ~3.5 ms call.  With `early`, right after that level the call
  *   - compares frame f's coarsest-level values with expect_level0[f] (device, res[0]^3 floats in (z,y,x) order:
  *     what query_func returned for those nodes; NULL entry or NULL array = no comparison),
- *   - writes flags_dev[2f] = status[f][0] and flags_dev[2f+1] = 1 if any value differs (bitwise float !=),
+ *   - writes flags_dev[2f] = status[f][0] and flags_dev[2f+1] = 1 if any value differs (float !=, a NaN agrees with a NaN),
  *   - copies the 2*n_frames flags to flags_host (PINNED host memory) and records `event` (a hipEvent_t, may be
  *     NULL) on `stream`, then enqueues the remaining levels.
  * A stage thread waits for `event`, reads two integers and hands the volume on while the GPU is still refining
@@ -257,6 +289,14 @@ int mp_recon_batch_early(mp_ctx *ctx, int mlp, int n_frames, const float *const 
                          const float *b_max, const int *resolutions, int n_levels, float balance,
                          int final_level, float *const *volume, int32_t *const *status,
                          const mp_recon_early *early, mp_stream stream);
+/* mp_recon_batch_early with a per-frame projection: projection is a HOST array of n_frames MP_PROJ_* modes
+ * (NULL = every frame orthogonal, which is mp_recon_batch_early); early may be NULL (mp_recon_batch_ex).
+ * Nodes of a perspective frame with z == 0 take the value NaN, which no threshold selects. */
+int mp_recon_batch_proj(mp_ctx *ctx, int mlp, int n_frames, const float *const *feat_hwc, int c, int h,
+                        int w, const float *const *calib, const int *projection /*host*/, float z_scale,
+                        const float *b_min, const float *b_max, const int *resolutions, int n_levels,
+                        float balance, int final_level, float *const *volume, int32_t *const *status,
+                        const mp_recon_early *early, mp_stream stream);
 
 /* The same engine one level at a time, for an arbitrary Python ``query_func`` (the general
  * Seg3dLossless contract, RTL/main.py:169-195): the caller evaluates the selected nodes itself.

@@ -85,6 +85,8 @@ class PlanWaitArgs(ctypes.Structure):
 
 # MP_PLAN_* command kinds (include/monoport_hip.h)
 PLAN_CONVK, PLAN_GN_APPLY, PLAN_CONV3X3, PLAN_CONV1X1, PLAN_AVGPOOL2, PLAN_UPSAMPLE2X, PLAN_MEMSET, PLAN_WAIT = range(1, 9)
+# MP_PROJ_* projection modes (include/monoport_hip.h)
+PROJ_ORTHOGONAL, PROJ_PERSPECTIVE = 0, 1
 
 # name -> (restype, argtypes); kept in one table so tests can check the exported surface against
 # the header (tests/test_abi.py)
@@ -109,13 +111,18 @@ SIGNATURES = {
     "mp_skip_table_release": (c_int, [c_vp, c_vp, c_vp]),
     "mp_index": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_vp]),
     "mp_orthogonal": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    "mp_perspective": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
     "mp_query": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_vp,
                          c_f32, c_vp, c_vp]),
+    "mp_query_batch": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_vp,
+                               _pint, c_f32, c_vp, c_vp]),
     "mp_mlp_forward": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_vp]),
     "mp_query_counted": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_vp,
                                  c_f32, c_vp, c_vp]),
     "mp_query_counted_batch": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp,
                                        c_vp, c_f32, c_vp, c_vp]),
+    "mp_query_counted_batch_proj": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp,
+                                            c_vp, _pint, c_f32, c_vp, c_vp]),
     "mp_recon": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_f32, _pf32, _pf32, _pint,
                          c_int, c_f32, c_vp, c_vp, c_vp]),
     "mp_recon_batch": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_f32, _pf32, _pf32,
@@ -124,6 +131,8 @@ SIGNATURES = {
                                   _pint, c_int, c_f32, c_int, c_vp, c_vp, c_vp]),
     "mp_recon_batch_early": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_f32, _pf32, _pf32,
                                      _pint, c_int, c_f32, c_int, c_vp, c_vp, ctypes.POINTER(ReconEarly), c_vp]),
+    "mp_recon_batch_proj": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, _pint, c_f32, _pf32,
+                                    _pf32, _pint, c_int, c_f32, c_int, c_vp, c_vp, ctypes.POINTER(ReconEarly), c_vp]),
     "mp_concat3_add": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_i64, c_vp, c_vp]),
     "mp_prepare_inputs": (c_int, [c_vp, c_vp, c_i64, _pf32, _pf32, c_vp, c_vp, c_vp]),
     "mp_octree_select": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_f32, c_vp,

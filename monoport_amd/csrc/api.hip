@@ -107,6 +107,16 @@ static int check_ready(mp_ctx *ctx, const Mlp *m, int c) {
   return MP_OK;
 }
 
+// per-frame projection modes of a call (host array; NULL = every frame orthogonal)
+static int check_projection(mp_ctx *ctx, const char *who, const int *proj, int n_frames) {
+  if (!proj) return MP_OK;
+  for (int f = 0; f < n_frames; ++f)
+    if (proj[f] != MP_PROJ_ORTHOGONAL && proj[f] != MP_PROJ_PERSPECTIVE)
+      return fail(ctx, MP_ERR_ARG, "%s: frame %d has projection %d (MP_PROJ_ORTHOGONAL / MP_PROJ_PERSPECTIVE)", who,
+                  f, proj[f]);
+  return MP_OK;
+}
+
 }  // namespace mp
 
 using namespace mp;
@@ -495,6 +505,16 @@ int mp_orthogonal(mp_ctx *ctx, const float *points, int64_t n, const float *cali
   return launch_orthogonal(ctx, points, n, calib, out, (hipStream_t)stream);
 }
 
+int mp_perspective(mp_ctx *ctx, const float *points, int64_t n, const float *calib, float *out,
+                   mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (n < 0 || !calib || (n > 0 && (!points || !out)))
+    return fail(ctx, MP_ERR_ARG, "mp_perspective: bad argument");
+  DeviceGuard g(ctx->device);
+  return launch_perspective(ctx, points, n, calib, out, (hipStream_t)stream);
+}
+
 int mp_query(mp_ctx *ctx, int mlp, const float *feat_hwc, int c, int h, int w, const float *points,
              int64_t n, int64_t stride_n, int64_t stride_c, const float *calib, float z_scale,
              float *out, mp_stream stream) {
@@ -516,6 +536,45 @@ int mp_query(mp_ctx *ctx, int mlp, const float *feat_hwc, int c, int h, int w, c
   src.out_stride = n;
   DeviceGuard g(ctx->device);
   return launch_query(ctx, *m, feat_hwc, h, w, calib, z_scale, src, out, n, (hipStream_t)stream);
+}
+
+int mp_query_batch(mp_ctx *ctx, int mlp, int n_frames, const float *const *feat_hwc, int c, int h, int w,
+                   const float *const *points, int64_t n, int64_t stride_n, int64_t stride_c,
+                   const float *const *calib, const int *projection, float z_scale, float *const *out,
+                   mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const Mlp *m = get_mlp(ctx, mlp);
+  int rc = check_ready(ctx, m, c);
+  if (rc != MP_OK) return rc;
+  if (n_frames < 1 || n_frames > kMaxFrames)
+    return fail(ctx, MP_ERR_ARG, "mp_query_batch: 1..%d frames per call, got %d", kMaxFrames, n_frames);
+  if (!feat_hwc || !points || !calib || !projection || !out || n < 0 || h <= 0 || w <= 0)
+    return fail(ctx, MP_ERR_ARG, "mp_query_batch: bad argument");
+  rc = check_projection(ctx, "mp_query_batch", projection, n_frames);
+  if (rc != MP_OK) return rc;
+  QuerySet set;
+  std::memset(&set, 0, sizeof(set));
+  set.n = n_frames;
+  for (int f = 0; f < n_frames; ++f) {
+    if (!feat_hwc[f] || !calib[f] || (n > 0 && (!points[f] || !out[f])))
+      return fail(ctx, MP_ERR_ARG, "mp_query_batch: null buffer for frame %d", f);
+    if (!aligned16(feat_hwc[f]))
+      return fail(ctx, MP_ERR_ARG, "mp_query_batch: feat_hwc must be 16-byte aligned");
+    QueryItem &q = set.it[f];
+    q.feat = feat_hwc[f];
+    q.calib = calib[f];
+    q.proj = projection[f];
+    q.out = out[f];
+    q.src.pts = points[f];
+    q.src.sn = stride_n;
+    q.src.sc = stride_c;
+    q.src.n = n;
+    q.src.out_stride = n;
+  }
+  if (n == 0) return MP_OK;
+  DeviceGuard g(ctx->device);
+  return launch_query_set(ctx, *m, set, h, w, z_scale, n * n_frames, false, (hipStream_t)stream);
 }
 
 int mp_mlp_forward(mp_ctx *ctx, int mlp, const float *feature, int64_t n, float *out,
@@ -570,6 +629,14 @@ int mp_query_counted_batch(mp_ctx *ctx, int mlp, int n_frames, const float *cons
                            int h, int w, const float *const *points, int64_t capacity,
                            const int32_t *const *count, const float *const *calib, float z_scale,
                            float *const *out, mp_stream stream) {
+  return mp_query_counted_batch_proj(ctx, mlp, n_frames, feat_hwc, c, h, w, points, capacity, count, calib,
+                                     nullptr, z_scale, out, stream);
+}
+
+int mp_query_counted_batch_proj(mp_ctx *ctx, int mlp, int n_frames, const float *const *feat_hwc, int c,
+                                int h, int w, const float *const *points, int64_t capacity,
+                                const int32_t *const *count, const float *const *calib,
+                                const int *projection, float z_scale, float *const *out, mp_stream stream) {
   if (!ctx) return MP_ERR_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
   const Mlp *m = get_mlp(ctx, mlp);
@@ -580,6 +647,8 @@ int mp_query_counted_batch(mp_ctx *ctx, int mlp, int n_frames, const float *cons
                 n_frames);
   if (!feat_hwc || !points || !count || !calib || !out || capacity < 0 || h <= 0 || w <= 0)
     return fail(ctx, MP_ERR_ARG, "mp_query_counted_batch: bad argument");
+  rc = check_projection(ctx, "mp_query_counted_batch", projection, n_frames);
+  if (rc != MP_OK) return rc;
   if (capacity == 0) return MP_OK;
   QuerySet set;
   std::memset(&set, 0, sizeof(set));
@@ -592,6 +661,7 @@ int mp_query_counted_batch(mp_ctx *ctx, int mlp, int n_frames, const float *cons
     QueryItem &q = set.it[f];
     q.feat = feat_hwc[f];
     q.calib = calib[f];
+    q.proj = projection ? projection[f] : MP_PROJ_ORTHOGONAL;
     q.out = out[f];
     q.src.pts = points[f];
     q.src.sn = 1;
@@ -635,6 +705,15 @@ int mp_recon_batch_early(mp_ctx *ctx, int mlp, int n_frames, const float *const 
                          const float *b_max, const int *resolutions, int n_levels, float balance,
                          int final_level, float *const *volume, int32_t *const *status,
                          const mp_recon_early *early, mp_stream stream) {
+  return mp_recon_batch_proj(ctx, mlp, n_frames, feat_hwc, c, h, w, calib, nullptr, z_scale, b_min, b_max,
+                             resolutions, n_levels, balance, final_level, volume, status, early, stream);
+}
+
+int mp_recon_batch_proj(mp_ctx *ctx, int mlp, int n_frames, const float *const *feat_hwc, int c, int h,
+                        int w, const float *const *calib, const int *projection, float z_scale,
+                        const float *b_min, const float *b_max, const int *resolutions, int n_levels,
+                        float balance, int final_level, float *const *volume, int32_t *const *status,
+                        const mp_recon_early *early, mp_stream stream) {
   if (!ctx) return MP_ERR_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
   const Mlp *m = get_mlp(ctx, mlp);
@@ -657,6 +736,8 @@ int mp_recon_batch_early(mp_ctx *ctx, int mlp, int n_frames, const float *const 
                 final_level);
   rc = check_resolutions(ctx, "mp_recon", resolutions, n_levels);
   if (rc != MP_OK) return rc;
+  rc = check_projection(ctx, "mp_recon_batch_proj", projection, n_frames);
+  if (rc != MP_OK) return rc;
   if (early && (!early->flags_dev || !early->flags_host))
     return fail(ctx, MP_ERR_ARG, "mp_recon_batch_early: flags_dev and flags_host are required");
   DeviceGuard g(ctx->device);
@@ -664,7 +745,7 @@ int mp_recon_batch_early(mp_ctx *ctx, int mlp, int n_frames, const float *const 
   rc = ensure_scratch(ctx, (hipStream_t)stream, n_frames * recon_scratch_bytes(resolutions, n_levels),
                       &scratch);
   if (rc != MP_OK) return rc;
-  return launch_recon(ctx, scratch, *m, n_frames, feat_hwc, h, w, calib, z_scale, b_min, b_max,
+  return launch_recon(ctx, scratch, *m, n_frames, feat_hwc, h, w, calib, projection, z_scale, b_min, b_max,
                       resolutions, n_levels, balance, final_level, volume, status, early, (hipStream_t)stream);
 }
 

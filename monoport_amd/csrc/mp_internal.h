@@ -78,6 +78,7 @@ struct QueryItem {
   float *out;
   PointSrc src;
   const float *l0;     // optional skip table of `feat` [H,W,kTableRows] (mp_skip_table; filled in by the launcher)
+  int proj;            // MP_PROJ_ORTHOGONAL / MP_PROJ_PERSPECTIVE (query_common.h: project_mode)
 };
 // host-side description of a launch (the launchers turn it into a QuerySetDev)
 struct QuerySet {
@@ -87,7 +88,7 @@ struct QuerySet {
 
 // What the kernels receive (kernel arguments are limited to 4 KB: 32 full QueryItems would be 4.1 KB).
 // The frames of one launch share the point layout (explicit strides, or the lattice of one octree level);
-// per frame only the pointers and the count differ.
+// per frame only the pointers, the count and the projection mode differ: 64 B per item, 2 KB for 32.
 struct QueryItemDev {
   const float *feat, *calib;
   float *out;
@@ -95,7 +96,9 @@ struct QueryItemDev {
   const void *pts;        // PointSrc::packed when `lattice`, else PointSrc::pts
   const int32_t *n_dev;
   long long n;
+  int proj;
 };
+static_assert(sizeof(QueryItemDev) == 64, "QueryItemDev: 64 B per frame");
 struct QuerySetDev {
   int n;
   int lattice;
@@ -115,6 +118,7 @@ struct QuerySetDev {
     q.calib = d.calib;
     q.out = d.out;
     q.l0 = d.l0;
+    q.proj = d.proj;
     q.src.pts = lattice ? nullptr : static_cast<const float *>(d.pts);
     q.src.packed = lattice ? static_cast<const uint32_t *>(d.pts) : nullptr;
     q.src.sn = sn;
@@ -228,6 +232,8 @@ int launch_index(mp_ctx *ctx, const float *feat_hwc, int c, int h, int w, const 
                  long long n, float *out, hipStream_t st);
 int launch_orthogonal(mp_ctx *ctx, const float *pts, long long n, const float *calib, float *out,
                       hipStream_t st);
+int launch_perspective(mp_ctx *ctx, const float *pts, long long n, const float *calib, float *out,
+                       hipStream_t st);
 // pack.hip
 int launch_pack_hwc(mp_ctx *ctx, const float *src, int c_src, int h, int w, float *dst, int c_dst,
                     int c_off, hipStream_t st);
@@ -264,9 +270,9 @@ int launch_prepare_inputs(mp_ctx *ctx, const float *segm, long long hw, const fl
 size_t recon_scratch_bytes(const int *res, int n_levels);
 int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
                  const float *const *feat_hwc, int h, int w, const float *const *calib,
-                 float z_scale, const float *bmin, const float *bmax, const int *res, int n_levels,
-                 float balance, int final_level, float *const *volume, int32_t *const *status,
-                 const mp_recon_early *early, hipStream_t st);
+                 const int *proj, float z_scale, const float *bmin, const float *bmax, const int *res,
+                 int n_levels, float balance, int final_level, float *const *volume,
+                 int32_t *const *status, const mp_recon_early *early, hipStream_t st);
 int launch_octree_select(mp_ctx *ctx, const float *prev, int rp, float *cur, int r,
                          const unsigned long long *ev_prev, unsigned long long *ev_cur,
                          unsigned long long *bnd, int box, float balance, uint32_t *packed,

@@ -110,7 +110,10 @@ __global__ void early_flags_kernel(EarlyBufs eb, int n, int32_t *__restrict__ fl
   const float *__restrict__ expect = eb.expect[f];
   int hit = 0;
   if (expect)
-    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) hit |= occ[t] != expect[t];
+    for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
+      const float a = occ[t], e = expect[t];
+      hit |= !(a == e || (a != a && e != e));  // NaN (a perspective node at z == 0) agrees with NaN
+    }
   if (__any(hit) && (threadIdx.x & 63) == 0) atomicOr(flags + 2 * f + 1, 1);
   if (blockIdx.x == 0 && threadIdx.x == 0) flags[2 * f] = *eb.flag[f];
 }
@@ -475,9 +478,9 @@ int launch_scatter_nodes(mp_ctx *ctx, const uint32_t *packed, const int32_t *cou
 // ---- driver ------------------------------------------------------------------------------------
 int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
                  const float *const *feat_hwc, int h, int w, const float *const *calib,
-                 float z_scale, const float *bmin, const float *bmax, const int *res, int n_levels,
-                 float balance, int final_level, float *const *volume, int32_t *const *status,
-                 const mp_recon_early *early, hipStream_t st) {
+                 const int *proj, float z_scale, const float *bmin, const float *bmax, const int *res,
+                 int n_levels, float balance, int final_level, float *const *volume,
+                 int32_t *const *status, const mp_recon_early *early, hipStream_t st) {
   // carve the scratch arena: one private set of level buffers per frame
   const size_t per_frame = recon_scratch_bytes(res, n_levels);
   LevelBufs lv[kMaxFrames][8];
@@ -509,6 +512,7 @@ int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
     QueryItem &q = set.it[f];
     q.feat = feat_hwc[f];
     q.calib = calib[f];
+    q.proj = proj ? proj[f] : MP_PROJ_ORTHOGONAL;  // NULL: every frame orthogonal
     q.src.packed = packed[f];
     q.src.res_final = (float)rf;
     q.src.half_step = (1.0f / (float)rf) / 2.0f;

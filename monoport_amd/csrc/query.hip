@@ -85,6 +85,7 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_kernel(
     const QueryItem item = set.item(fi);
     const float *__restrict__ feat = item.feat;
     const float *__restrict__ calib = item.calib;
+    const int proj = item.proj;  // uniform over the tile
     float *__restrict__ out = item.out;
     const PointSrc &src = item.src;
     const long long n_pts = src.n_dev ? (long long)*src.n_dev : src.n;
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_kernel(
         float px = 0, py = 0, pz = 0, x, y, z;
         uint32_t code;
         if (live_n) load_point(src, n, px, py, pz, code);
-        project(cal, px, py, pz, x, y, z);
+        project_mode(cal, proj, px, py, pz, x, y, z);
         t[u] = make_taps(x, y, fh, fw, C, live_n && in_image(x, y));
       }
       f32x4 v[GB][C / 256][4];
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_kernel(
       float px = 0, py = 0, pz = 0, x, y, z;
       uint32_t code;
       if (n < n_pts) load_point(src, n, px, py, pz, code);
-      project(cal, px, py, pz, x, y, z);
+      project_mode(cal, proj, px, py, pz, x, y, z);
       zb[cb] = (h == 0 && n < n_pts) ? __fmul_rn(z, z_scale) : 0.0f;
     }
     }
@@ -363,9 +364,9 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_kernel(
           float px, py, pz, x, y, z;
           uint32_t code;
           load_point(src, n, px, py, pz, code);
-          project(cal, px, py, pz, x, y, z);
+          project_mode(cal, proj, px, py, pz, x, y, z);
           v = fmaf(wz, __fmul_rn(z, z_scale), v);
-          v = in_image(x, y) ? activate(v, act) : 0.0f;  // MonoPortNet.py:89
+          v = in_image(x, y) ? activate(v, act) : outside_value(x, y, proj);  // MonoPortNet.py:89
           if (src.packed) {
             const int ix = code & 1023u, iy = (code >> 10) & 1023u, iz = code >> 20;
             out[((long long)iz * src.level_res + iy) * src.level_res + ix] = v;
@@ -379,7 +380,7 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_kernel(
   }
 }
 
-// ---- stand-alone index() and orthogonal() -------------------------------------------------------
+// ---- stand-alone index(), orthogonal() and perspective() ------------------------------------
 // geometry.py:4-16.  One wave per point and 256-channel slice; out is [C, N] like the reference.
 __global__ __launch_bounds__(256) void index_kernel(const float *__restrict__ feat, int c, int fh,
                                                     int fw, const float *__restrict__ uv,
@@ -412,6 +413,23 @@ __global__ void orthogonal_kernel(const float *__restrict__ pts, long long n,
        i += (long long)gridDim.x * blockDim.x) {
     float x, y, z;
     project(cal, pts[i], pts[n + i], pts[2 * n + i], x, y, z);
+    out[i] = x;
+    out[n + i] = y;
+    out[2 * n + i] = z;
+  }
+}
+
+// geometry.py:37-55 (transforms=None): [x/z, y/z, z] of the same rows; x/z and y/z are +-inf or NaN
+// where z == 0, as in the reference.
+__global__ void perspective_kernel(const float *__restrict__ pts, long long n,
+                                   const float *__restrict__ calib, float *__restrict__ out) {
+  float cal[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) cal[i] = calib[i];
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n;
+       i += (long long)gridDim.x * blockDim.x) {
+    float x, y, z;
+    project_mode(cal, MP_PROJ_PERSPECTIVE, pts[i], pts[n + i], pts[2 * n + i], x, y, z);
     out[i] = x;
     out[n + i] = y;
     out[2 * n + i] = z;
@@ -530,6 +548,7 @@ int compact_query_set(mp_ctx *ctx, const QuerySet &set, QuerySetDev &d) {
     o.calib = q.calib;
     o.out = q.out;
     o.l0 = q.l0;
+    o.proj = q.proj;
     o.pts = s.packed ? static_cast<const void *>(s.packed) : static_cast<const void *>(s.pts);
     o.n_dev = s.n_dev;
     o.n = s.n;
@@ -592,6 +611,17 @@ int launch_orthogonal(mp_ctx *ctx, const float *pts, long long n, const float *c
   long long blocks = (n + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(orthogonal_kernel, dim3((unsigned)blocks), dim3(256), 0, st, pts, n, calib,
+                     out);
+  MP_HIP(ctx, hipGetLastError());
+  return MP_OK;
+}
+
+int launch_perspective(mp_ctx *ctx, const float *pts, long long n, const float *calib, float *out,
+                       hipStream_t st) {
+  if (n <= 0) return MP_OK;
+  long long blocks = (n + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(perspective_kernel, dim3((unsigned)blocks), dim3(256), 0, st, pts, n, calib,
                      out);
   MP_HIP(ctx, hipGetLastError());
   return MP_OK;

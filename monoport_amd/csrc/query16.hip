@@ -381,6 +381,7 @@ __global__ __launch_bounds__(kThreads16 * CS, NB >= 3 ? CS : 2) void pifu_query1
     const QueryItem item = set.item(fi);
     const float *__restrict__ feat = item.feat;
     const float *__restrict__ calib = item.calib;
+    const int proj = item.proj;  // uniform over the tile
     float *__restrict__ out = item.out;
     const PointSrc &src = item.src;
     const long long n_pts = src.n_dev ? (long long)*src.n_dev : src.n;
@@ -403,7 +404,7 @@ __global__ __launch_bounds__(kThreads16 * CS, NB >= 3 ? CS : 2) void pifu_query1
           float px = 0, py = 0, pz = 0, x, y, z;
           uint32_t code;
           if (live_n) load_point(src, n, px, py, pz, code);
-          project(cal, px, py, pz, x, y, z);
+          project_mode(cal, proj, px, py, pz, x, y, z);
           t[u] = make_taps(x, y, fh, fw, C, live_n && in_image(x, y));
         }
         f32x4 v[GB][4];
@@ -430,7 +431,7 @@ __global__ __launch_bounds__(kThreads16 * CS, NB >= 3 ? CS : 2) void pifu_query1
         float px = 0, py = 0, pz = 0, x, y, z;
         uint32_t code;
         if (n < n_pts) load_point(src, n, px, py, pz, code);
-        project(cal, px, py, pz, x, y, z);
+        project_mode(cal, proj, px, py, pz, x, y, z);
         const float zf = (hh == 0 && n < n_pts) ? __fmul_rn(z, z_scale) : 0.0f;
         zc[cb].hi = (_Float16)zf;
         zc[cb].lo = (_Float16)(zf - (float)zc[cb].hi);
@@ -658,9 +659,9 @@ __global__ __launch_bounds__(kThreads16 * CS, NB >= 3 ? CS : 2) void pifu_query1
         float px, py, pz, x, y, z;
         uint32_t code;
         load_point(src, n, px, py, pz, code);
-        project(cal, px, py, pz, x, y, z);
+        project_mode(cal, proj, px, py, pz, x, y, z);
         v = fmaf((wbase + mlp32.w4)[o * K4 + kHidden[3] + C], __fmul_rn(z, z_scale), v);
-        v = in_image(x, y) ? activate(v, act) : 0.0f;  // MonoPortNet.py:89
+        v = in_image(x, y) ? activate(v, act) : outside_value(x, y, proj);  // MonoPortNet.py:89
         if (src.packed) {
           const int ix = code & 1023u, iy = (code >> 10) & 1023u, iz = code >> 20;
           out[((long long)iz * src.level_res + iy) * src.level_res + ix] = v;
@@ -741,6 +742,7 @@ __global__ __launch_bounds__(kThreads16, 1) void pifu_query16_tab_kernel(MlpPack
     if (fi < 0) break;
     const QueryItem item = set.item(fi);
     const float *__restrict__ calib = item.calib;
+    const int proj = item.proj;  // uniform over the tile
     float *__restrict__ out = item.out;
     const PointSrc &src = item.src;
     const long long n_pts = src.n_dev ? (long long)*src.n_dev : src.n;
@@ -763,7 +765,7 @@ __global__ __launch_bounds__(kThreads16, 1) void pifu_query16_tab_kernel(MlpPack
         float px = 0, py = 0, pz = 0, x, y, z;
         uint32_t code;
         if (pn < n_pts) load_point(src, pn, px, py, pz, code);
-        project(cal, px, py, pz, x, y, z);
+        project_mode(cal, proj, px, py, pz, x, y, z);
         zf[n] = pn < n_pts ? __fmul_rn(z, z_scale) : 0.0f;
         const float zm = hh == 0 ? zf[n] : 0.0f;  // B operand of the z column: k = 0 of lanes 0-31
         zc[n].hi = (_Float16)zm;
@@ -979,13 +981,13 @@ __global__ __launch_bounds__(kThreads16, 1) void pifu_query16_tab_kernel(MlpPack
         float px, py, pz, x, y, z;
         uint32_t code;
         load_point(src, n, px, py, pz, code);
-        project(cal, px, py, pz, x, y, z);
+        project_mode(cal, proj, px, py, pz, x, y, z);
         const bool inside = in_image(x, y);
         const Taps t = make_taps(x, y, fh, fw, kTableRows, inside);
         const float *row = item.l0 + kTableL[4] + o;
         v += fmaf(row[t.o[3]], t.w[3], fmaf(row[t.o[2]], t.w[2], fmaf(row[t.o[1]], t.w[1], __fmul_rn(row[t.o[0]], t.w[0]))));
         v = fmaf((wbase + mlp32.w4)[o * K4 + kHidden[3] + 256], __fmul_rn(z, z_scale), v);
-        v = inside ? activate(v, act) : 0.0f;  // MonoPortNet.py:89
+        v = inside ? activate(v, act) : outside_value(x, y, proj);  // MonoPortNet.py:89
         if (src.packed) {
           const int ix = code & 1023u, iy = (code >> 10) & 1023u, iz = code >> 20;
           out[((long long)iz * src.level_res + iy) * src.level_res + ix] = v;

@@ -90,8 +90,31 @@ __device__ __forceinline__ void project(const float *__restrict__ cal, float px,
   z = project_row(cal + 8, px, py, pz);
 }
 
+// The frame's projection (MonoPortNet.py:69): MP_PROJ_ORTHOGONAL is project() itself;
+// MP_PROJ_PERSPECTIVE (geometry.py:37-55) divides x and y by z -- the same three rows, then two IEEE
+// divisions, as the reference's baddbmm followed by `homo[:, :2] / homo[:, 2:3]`.  z stays the row's
+// value (the depth feature).  `proj` is uniform over a tile (one frame), so the branch is scalar.
+__device__ __forceinline__ void project_mode(const float *__restrict__ cal, int proj, float px,
+                                             float py, float pz, float &x, float &y, float &z) {
+  project(cal, px, py, pz, x, y, z);
+  if (proj == MP_PROJ_PERSPECTIVE) {
+    x = __fdiv_rn(x, z);
+    y = __fdiv_rn(y, z);
+  }
+}
+
 __device__ __forceinline__ bool in_image(float x, float y) {  // MonoPortNet.py:74
   return x >= -1.0f && x <= 1.0f && y >= -1.0f && y <= 1.0f;
+}
+
+// The value of a point outside the image (MonoPortNet.py:89: in_img * pred).  A finite (x, y) gives
+// exactly 0.  A perspective point with z == 0 projects to +-inf / NaN: grid_sample then samples NaN
+// features, the head's prediction is NaN and the reference's 0 * NaN is NaN in every channel.
+__device__ __forceinline__ bool non_finite(float x, float y) {
+  return !(__builtin_isfinite(x) && __builtin_isfinite(y));
+}
+__device__ __forceinline__ float outside_value(float x, float y, int proj) {
+  return (proj == MP_PROJ_PERSPECTIVE && non_finite(x, y)) ? __builtin_nanf("") : 0.0f;
 }
 
 // grid_sample(align_corners=True, padding zeros): 4 tap offsets (in floats) + weights.

@@ -85,6 +85,7 @@ __global__ __launch_bounds__(kQueryThreads, kT32Wps) void pifu_query_t32_kernel(
     const QueryItem item = set.item(fi);
     const float *__restrict__ feat = item.feat;
     const float *__restrict__ calib = item.calib;
+    const int proj = item.proj;  // uniform over the tile
     float *__restrict__ out = item.out;
     const PointSrc &src = item.src;
     const long long n_pts = src.n_dev ? (long long)*src.n_dev : src.n;
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(kQueryThreads, kT32Wps) void pifu_query_t32_kernel(
           float px = 0, py = 0, pz = 0, x, y, z;
           uint32_t code;
           if (live_n) load_point(src, n, px, py, pz, code);
-          project(cal, px, py, pz, x, y, z);
+          project_mode(cal, proj, px, py, pz, x, y, z);
           t[u] = make_taps(x, y, fh, fw, C, live_n && in_image(x, y));
         }
         f32x4 v[GB][4];
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(kQueryThreads, kT32Wps) void pifu_query_t32_kernel(
         float px = 0, py = 0, pz = 0, x, y, z;
         uint32_t code;
         if (n < n_pts) load_point(src, n, px, py, pz, code);
-        project(cal, px, py, pz, x, y, z);
+        project_mode(cal, proj, px, py, pz, x, y, z);
         zb[0] = (h == 0 && n < n_pts) ? __fmul_rn(z, z_scale) : 0.0f;
       }
     }
@@ -296,9 +297,9 @@ __global__ __launch_bounds__(kQueryThreads, kT32Wps) void pifu_query_t32_kernel(
         float px, py, pz, x, y, z;
         uint32_t code;
         load_point(src, n, px, py, pz, code);
-        project(cal, px, py, pz, x, y, z);
+        project_mode(cal, proj, px, py, pz, x, y, z);
         v = fmaf(wz, __fmul_rn(z, z_scale), v);
-        v = in_image(x, y) ? activate(v, act) : 0.0f;  // MonoPortNet.py:89
+        v = in_image(x, y) ? activate(v, act) : outside_value(x, y, proj);  // MonoPortNet.py:89
         if (src.packed) {
           const int ix = code & 1023u, iy = (code >> 10) & 1023u, iz = code >> 20;
           out[((long long)iz * src.level_res + iy) * src.level_res + ix] = v;

@@ -85,7 +85,7 @@ struct WsFrame {  // per frame
   const void *pts;  // packed node codes (WsShared::lattice) or explicit coordinates
   float *out;
   const float *l0;
-  int npts, pad;
+  int npts, proj;  // proj: MP_PROJ_*
 };
 struct WsShared {  // the point layout / lattice of the launch, shared by its frames (QuerySetDev)
   long long sn, sc, out_stride;
@@ -143,7 +143,7 @@ struct WsPoint {
   float zf;      // z * z_scale (0 for a dead point)
   float r4;      // layer 4's blended skip row of output 2 * (producer wave) + (lane >> 5)
   uint32_t code; // packed lattice coordinates (scatter address of the output)
-  int ok;        // bit 0: the point exists, bit 1: it projects into the image
+  int ok;        // bit 0: the point exists, bit 1: it projects into the image, bit 2: to +-inf / NaN (outside_value)
 };
 
 template <int COUT>
@@ -190,6 +190,7 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
       fr.pts = it.pts;
       fr.out = it.out;
       fr.l0 = it.l0;
+      fr.proj = it.proj;
       if (tid == 0) {
         WsShared &sh = *reinterpret_cast<WsShared *>(smem + kWsShared);
         sh.sn = set.sn;
@@ -428,13 +429,13 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
         pz = c3[2];
       }
       float x, y, z;
-      project(cal, px, py, pz, x, y, z);
+      project_mode(cal, fr.proj, px, py, pz, x, y, z);
       pt.zf = rp.live ? __fmul_rn(z, z_scale) : 0.0f;
       if (pw == 0 && h == 0) zvec[zpar * P + j] = pt.zf;  // the consumers' B operand of the z column
       const bool inside = in_image(x, y);
       const Taps t = make_taps(x, y, fh, fw, kTableRows, rp.live && inside);
       pt.code = rp.code;
-      pt.ok = (rp.live ? 1 : 0) | (inside ? 2 : 0);
+      pt.ok = (rp.live ? 1 : 0) | (inside ? 2 : 0) | (fr.proj == MP_PROJ_PERSPECTIVE && non_finite(x, y) ? 4 : 0);
       pt.r4 = 0.0f;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -520,7 +521,7 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
 #pragma unroll
         for (int part = 1; part < 4; ++part) v += red[(part * COUT + my_o) * P + j];
         v += pt.r4;
-        v = (pt.ok & 2) ? activate(v, act) : 0.0f;  // MonoPortNet.py:89
+        v = (pt.ok & 2) ? activate(v, act) : (pt.ok & 4) ? __builtin_nanf("") : 0.0f;  // MonoPortNet.py:89, outside_value
         if (sh.lattice) {
           const int ix = pt.code & 1023u, iy = (pt.code >> 10) & 1023u, iz = pt.code >> 20;
           fr.out[((long long)iz * sh.level_res + iy) * sh.level_res + ix] = v;

@@ -102,7 +102,7 @@ class Seg3dLossless(nn.Module):
         self.validate = validate
         self._agreed = 0          # consecutive validated calls that agreed
         self._since_check = 0     # trusted calls since the last validated one
-        self._trusted_key = None  # (id(packed head), precision, z scale) those calls were bound to
+        self._trusted_key = None  # (id(packed head), precision, z scale, projection) those calls were bound to
         # nn.Module.to(device) is called on the engine (RTL/main.py:195): carry a buffer so it
         # has a device like the upstream module does
         self.register_buffer("_device_tag", torch.zeros(1), persistent=False)
@@ -165,7 +165,7 @@ class Seg3dLossless(nn.Module):
             volume, status = ops.recon(binding.mlp, binding.feat_hwc, binding.calib, binding.z_scale,
                                        self.b_min[0], self.b_max[0], self.resolutions,
                                        self.balance_value, final_level=self.final_level, early=early,
-                                       expect_level0=eng.cur)
+                                       expect_level0=eng.cur, projection=binding.projection)
             # the one host sync of a reconstruction (upstream syncs at every level) -- and it waits for the
             # coarsest level only: "None or a volume" and "is query_func the fused kernels' function" are both
             # known there, the finer levels go on refining `volume` on this stream after the call has returned
@@ -195,7 +195,7 @@ class Seg3dLossless(nn.Module):
 
     @staticmethod
     def _binding_key(binding):
-        return (id(binding.mlp), binding.mlp.precision, float(binding.z_scale))
+        return (id(binding.mlp), binding.mlp.precision, float(binding.z_scale), binding.projection)
 
     def _forward_trusted(self, kwargs):
         """A query_func whose last VALIDATE_CALLS calls were plain MonoPortNet.query calls agreeing
@@ -211,7 +211,8 @@ class Seg3dLossless(nn.Module):
             return NotImplemented
         early = self._early_flags(self._device_tag.device)
         volume, status = ops.recon(b.mlp, b.feat_hwc, b.calib, b.z_scale, self.b_min[0], self.b_max[0],
-                                   self.resolutions, self.balance_value, final_level=self.final_level, early=early)
+                                   self.resolutions, self.balance_value, final_level=self.final_level, early=early,
+                                   projection=b.projection)
         nonempty = int(early.wait()[0, 0])  # waits for the coarsest level only (see forward)
         self.last_status, self.last_path = status, "fused"
         return None if nonempty == 0 else volume[None, None]
@@ -245,7 +246,8 @@ class Seg3dLossless(nn.Module):
         early = self._early_flags(self._device_tag.device, n)
         volumes, status = ops.recon_batch(b0.mlp, [b.feat_hwc for b in bindings], [b.calib for b in bindings],
                                           b0.z_scale, self.b_min[0], self.b_max[0], self.resolutions,
-                                          self.balance_value, final_level=self.final_level, early=early)
+                                          self.balance_value, final_level=self.final_level, early=early,
+                                          projections=[b.projection for b in bindings])
         flags = early.wait().clone()  # the one host sync of the whole batch: its coarsest level (see forward)
         self._since_check += n
         self.last_status, self.last_path = status[-1], "fused"
@@ -264,7 +266,7 @@ class Seg3dLossless(nn.Module):
         if b is None:
             raise NotImplementedError("forward_async needs a query_func ending in MonoPortNet.query")
         return ops.recon(b.mlp, b.feat_hwc, b.calib, b.z_scale, self.b_min[0], self.b_max[0],
-                         self.resolutions, self.balance_value, final_level=self.final_level)
+                         self.resolutions, self.balance_value, final_level=self.final_level, projection=b.projection)
 
 
 class Seg3dTopk(nn.Module):

@@ -1,6 +1,6 @@
 """Per-point geometry ops of the PIFu query (mirror of monoport/lib/modeling/geometry.py).
 
-``index`` and ``orthogonal`` run as HIP kernels (monoport_amd/csrc/query.hip) -- inside
+``index``, ``orthogonal`` and ``perspective`` run as HIP kernels (monoport_amd/csrc/query.hip) -- inside
 ``MonoPortNet.query`` they are fused with the MLP and never launched on their own; the
 stand-alone entry points exist for callers such as colorization (RTL/main.py:237).
 """
@@ -38,10 +38,20 @@ def orthogonal(points, calibrations, transforms=None):
 
 
 def perspective(points, calibrations, transforms=None):
-    """Pinhole projection (geometry.py:37-55).  No PIFu config selects it (config.py:33,:59);
-    kept importable for API parity, computed with stock tensor ops."""
+    """Pinhole projection (geometry.py:37-55): (u, v, z) = R p + t, xyz = (u / z, v / z, z).
+
+    points [B,3,N]; calibrations [B,>=3,4].  CUDA tensors run the HIP kernel (csrc/query.hip:
+    perspective_kernel) frame by frame, CPU tensors the reference's own tensor ops; both are bit-identical
+    to it, +-inf / NaN where z == 0 included.  ``transforms`` raises: the reference's own code cannot run
+    it (``transforms[:2, 2:3]`` of a [B,2,3] / [2,3] tensor is empty and its baddbmm fails).
+    """
     if transforms is not None:
-        raise NotImplementedError("perspective(transforms=...) is outside the reconstruction path")
-    cam = calibrations[:, :3, :3] @ points + calibrations[:, :3, 3:4]
-    depth = cam[:, 2:3, :]
-    return torch.cat([cam[:, :2, :] / depth, depth], 1)
+        raise NotImplementedError("perspective(transforms=...): the reference's own perspective() fails on "
+                                  "every shape of it (transforms[:2, 2:3] is empty, baddbmm raises)")
+    if not points.is_cuda:
+        homo = torch.baddbmm(calibrations[:, :3, 3:4], calibrations[:, :3, :3], points)
+        return torch.cat([homo[:, :2, :] / homo[:, 2:3, :], homo[:, 2:3, :]], 1)
+    if points.shape[0] != 1:
+        return torch.cat([perspective(points[b:b + 1], calibrations[b:b + 1])
+                          for b in range(points.shape[0])], 0)
+    return ops.perspective(points, calibrations)

@@ -184,6 +184,22 @@ def index(feat_hwc, uv):
     return out
 
 
+PROJECTIONS = {"orthogonal": _lib.PROJ_ORTHOGONAL, "perspective": _lib.PROJ_PERSPECTIVE}  # MP_PROJ_*
+
+
+def _projection(p):
+    """A projection given as MP_PROJ_* int or as its name -> the int."""
+    if isinstance(p, str):
+        try:
+            return PROJECTIONS[p]
+        except KeyError:
+            raise ValueError("projection must be one of %s, got %r" % (sorted(PROJECTIONS), p)) from None
+    p = int(p)
+    if p not in PROJECTIONS.values():
+        raise ValueError("unknown projection mode %d" % p)
+    return p
+
+
 def orthogonal(points, calib):
     """geometry.py:19-34 (transforms=None): points [1,3,N] -> [1,3,N]."""
     ctx = get_context(points.device)
@@ -193,6 +209,19 @@ def orthogonal(points, calib):
     out = torch.empty((1, 3, n), dtype=torch.float32, device=points.device)
     ctx.check(ctx.lib.mp_orthogonal(ctx.handle, _ptr(p), n, _ptr(cal), _ptr(out), _stream(out)),
               "mp_orthogonal")
+    return out
+
+
+def perspective(points, calib):
+    """geometry.py:37-55 (transforms=None): points [1,3,N] -> [1,3,N] = (u/z, v/z, z) of (u, v, z) = R p + t
+    (+-inf / NaN where z == 0, as the reference)."""
+    ctx = get_context(points.device)
+    p = _f32c(points.reshape(3, -1))
+    n = p.shape[1]
+    cal = _calib_dev(calib, points.device)
+    out = torch.empty((1, 3, n), dtype=torch.float32, device=points.device)
+    ctx.check(ctx.lib.mp_perspective(ctx.handle, _ptr(p), n, _ptr(cal), _ptr(out), _stream(out)),
+              "mp_perspective")
     return out
 
 
@@ -307,12 +336,16 @@ def skip_table_release(ctx, feat_hwc=None):
               "mp_skip_table_release")
 
 
-def query(mlp, feat_hwc, points, calib, z_scale):
+def query(mlp, feat_hwc, points, calib, z_scale, projection=_lib.PROJ_ORTHOGONAL):
     """MonoPortNet.query (eval, one stage).  points [1,3,N] with ANY strides (the permuted view
-    query_func builds at RTL/main.py:176-177 is consumed in place) -> [1,Cout,N]."""
+    query_func builds at RTL/main.py:176-177 is consumed in place) -> [1,Cout,N].  ``projection``:
+    MP_PROJ_* int or "orthogonal" / "perspective" (a perspective query is a one-frame ``query_batch``)."""
     ctx = mlp.ctx
     if points.dim() != 3 or points.shape[0] != 1 or points.shape[1] != 3:
         raise ValueError("points must be [1,3,N], got %s" % (tuple(points.shape),))
+    projection = _projection(projection)
+    if projection != _lib.PROJ_ORTHOGONAL:
+        return query_batch(mlp, [feat_hwc], points, [calib], [projection], z_scale)
     if points.dtype != torch.float32:
         points = points.float()
     h, w, c = feat_hwc.shape
@@ -322,6 +355,48 @@ def query(mlp, feat_hwc, points, calib, z_scale):
     ctx.check(ctx.lib.mp_query(ctx.handle, mlp.id, _ptr(feat_hwc), c, h, w, _ptr(points), n,
                                points.stride(2), points.stride(1), _ptr(cal), float(z_scale),
                                _ptr(out), _stream(out)), "mp_query")
+    return out
+
+
+def query_batch(mlp, feats_hwc, points, calibs, projections, z_scale, out=None):
+    """mp_query_batch: MonoPortNet.query for F <= MAX_FRAMES frames in one launch.  feats_hwc: F channels-last
+    maps [H,W,C]; points [F,3,N] with ANY strides; calibs: F calibrations ([>=3,4] or [1,>=3,4] each, or one
+    [F,>=3,4] tensor); projections: F MP_PROJ_* ints or names.  -> [F,Cout,N] (or into ``out``, whose frames
+    must each be contiguous [Cout,N])."""
+    ctx = mlp.ctx
+    f_n = len(feats_hwc)
+    if points.dim() != 3 or points.shape[0] != f_n or points.shape[1] != 3:
+        raise ValueError("points must be [%d,3,N], got %s" % (f_n, tuple(points.shape)))
+    if not 1 <= f_n <= MAX_FRAMES:
+        raise ValueError("query_batch: 1..%d frames per call, got %d" % (MAX_FRAMES, f_n))
+    if points.dtype != torch.float32:
+        points = points.float()
+    h, w, c = feats_hwc[0].shape
+    dev = feats_hwc[0].device
+    for f in feats_hwc:
+        if tuple(f.shape) != (h, w, c) or not f.is_contiguous() or f.dtype != torch.float32:
+            raise ValueError("query_batch: the maps must be contiguous float32 [%d,%d,%d]" % (h, w, c))
+    if torch.is_tensor(calibs) and calibs.dim() == 3:
+        calibs = [calibs[b] for b in range(calibs.shape[0])]
+    if len(calibs) != f_n or len(projections) != f_n:
+        raise ValueError("query_batch: %d maps, %d calibrations, %d projections" % (f_n, len(calibs), len(projections)))
+    proj = (ctypes.c_int * f_n)(*[_projection(p) for p in projections])
+    cals = [_calib_dev(cb, dev) for cb in calibs]
+    n = points.shape[2]
+    if out is None:
+        out = torch.empty((f_n, mlp.cout, n), dtype=torch.float32, device=dev)
+    elif (out.shape != (f_n, mlp.cout, n) or out.dtype != torch.float32
+          or (n > 0 and not all(out[b].is_contiguous() for b in range(f_n)))):
+        raise ValueError("query_batch: out must be float32 [%d,%d,%d] with contiguous frames" % (f_n, mlp.cout, n))
+    ptrs = ctypes.c_void_p * f_n
+    ctx.check(ctx.lib.mp_query_batch(
+        ctx.handle, mlp.id, f_n, ptrs(*[f.data_ptr() for f in feats_hwc]), c, h, w,
+        ptrs(*[points[b].data_ptr() for b in range(f_n)]), n, points.stride(2), points.stride(1),
+        ptrs(*[cb.data_ptr() for cb in cals]), proj, float(z_scale), ptrs(*[out[b].data_ptr() for b in range(f_n)]),
+        _stream(out)), "mp_query_batch")
+    stream = torch.cuda.current_stream(dev)
+    for t in cals:
+        t.record_stream(stream)
     return out
 
 
@@ -352,10 +427,11 @@ def query_counted(mlp, feat_hwc, points, count, calib, z_scale, out=None):
     return out
 
 
-def query_counted_batch(mlp, feats_hwc, points, counts, calibs, z_scale, outs=None):
+def query_counted_batch(mlp, feats_hwc, points, counts, calibs, z_scale, outs=None, projections=None):
     """mp_query_counted_batch: one fused-query launch for up to MAX_FRAMES frames.  feats_hwc / points
     ([3,cap] each, one cap) / counts (int32[1] each) / calibs: lists of per-frame device tensors
-    -> list of [Cout,cap]."""
+    -> list of [Cout,cap].  ``projections``: per-frame MP_PROJ_* ints or names (None: all orthogonal;
+    otherwise the call is mp_query_counted_batch_proj)."""
     ctx = mlp.ctx
     n = len(feats_hwc)
     h, w, c = feats_hwc[0].shape
@@ -367,11 +443,21 @@ def query_counted_batch(mlp, feats_hwc, points, counts, calibs, z_scale, outs=No
     for f, p in zip(feats_hwc, points):
         assert f.shape == (h, w, c) and f.is_contiguous() and p.shape == (3, cap) and p.is_contiguous()
     ptrs = ctypes.c_void_p * n
-    ctx.check(ctx.lib.mp_query_counted_batch(
-        ctx.handle, mlp.id, n, ptrs(*[f.data_ptr() for f in feats_hwc]), c, h, w,
-        ptrs(*[p.data_ptr() for p in points]), cap, ptrs(*[k.data_ptr() for k in counts]),
-        ptrs(*[cb.data_ptr() for cb in cals]), float(z_scale), ptrs(*[o.data_ptr() for o in outs]),
-        _stream(outs[0])), "mp_query_counted_batch")
+    if projections is None:
+        ctx.check(ctx.lib.mp_query_counted_batch(
+            ctx.handle, mlp.id, n, ptrs(*[f.data_ptr() for f in feats_hwc]), c, h, w,
+            ptrs(*[p.data_ptr() for p in points]), cap, ptrs(*[k.data_ptr() for k in counts]),
+            ptrs(*[cb.data_ptr() for cb in cals]), float(z_scale), ptrs(*[o.data_ptr() for o in outs]),
+            _stream(outs[0])), "mp_query_counted_batch")
+    else:
+        if len(projections) != n:
+            raise ValueError("query_counted_batch: %d frames, %d projections" % (n, len(projections)))
+        proj = (ctypes.c_int * n)(*[_projection(p) for p in projections])
+        ctx.check(ctx.lib.mp_query_counted_batch_proj(
+            ctx.handle, mlp.id, n, ptrs(*[f.data_ptr() for f in feats_hwc]), c, h, w,
+            ptrs(*[p.data_ptr() for p in points]), cap, ptrs(*[k.data_ptr() for k in counts]),
+            ptrs(*[cb.data_ptr() for cb in cals]), proj, float(z_scale), ptrs(*[o.data_ptr() for o in outs]),
+            _stream(outs[0])), "mp_query_counted_batch_proj")
     stream = torch.cuda.current_stream(dev)
     for t in cals:
         t.record_stream(stream)
@@ -417,26 +503,28 @@ def _final_level(final_level):
 
 
 def recon(mlp, feat_hwc, calib, z_scale, b_min, b_max, resolutions, balance=0.5, volume=None,
-          status=None, final_level="dilate3", early=None, expect_level0=None):
+          status=None, final_level="dilate3", early=None, expect_level0=None, projection=_lib.PROJ_ORTHOGONAL):
     """Coarse-to-fine occupancy volume (Seg3dLossless replacement).  Returns (volume [R,R,R]
-    f32, status int32[1+levels]) -- both on device, nothing synchronised.  ``early`` / ``expect_level0``: see
-    ``recon_batch``."""
+    f32, status int32[1+levels]) -- both on device, nothing synchronised.  ``early`` / ``expect_level0`` /
+    ``projection``: see ``recon_batch``."""
     st = None if status is None else status.reshape(1, -1)
     volumes, st = recon_batch(mlp, [feat_hwc], [calib], z_scale, b_min, b_max, resolutions, balance,
                               None if volume is None else [volume], st, final_level, early,
-                              None if expect_level0 is None else [expect_level0])
+                              None if expect_level0 is None else [expect_level0],
+                              None if _projection(projection) == _lib.PROJ_ORTHOGONAL else [projection])
     return volumes[0], st[0]
 
 
 def recon_batch(mlp, feats_hwc, calibs, z_scale, b_min, b_max, resolutions, balance=0.5,
-                volumes=None, status=None, final_level="dilate3", early=None, expect_level0=None):
+                volumes=None, status=None, final_level="dilate3", early=None, expect_level0=None, projections=None):
     """``recon`` over up to MAX_FRAMES independent frames in one call: every octree level evaluates the
     selected nodes of all frames in ONE fused-query launch (the coarse levels of a single frame
     cannot fill 256 CUs).  feats_hwc: list of [H,W,C] maps; calibs: [B,4,4] (or list of [1,4,4]);
     volumes: list of [R,R,R]; status: [B, 1+levels] int32.  Results equal B separate ``recon``
     calls bit for bit.  ``early``: an ``EarlyFlags`` for B frames -- mp_recon_batch_early: after the coarsest level
     the call hands (non-empty, differs-from-``expect_level0[b]``) per frame to the host (``early.wait()``) and goes
-    on refining; ``expect_level0``: list of [r0,r0,r0] f32 tensors (or None entries)."""
+    on refining; ``expect_level0``: list of [r0,r0,r0] f32 tensors (or None entries).  ``projections``: per-frame
+    MP_PROJ_* ints or names (None: all orthogonal, mp_recon_batch_early; otherwise mp_recon_batch_proj)."""
     ctx = mlp.ctx
     n = len(feats_hwc)
     h, w, c = feats_hwc[0].shape
@@ -468,11 +556,21 @@ def recon_batch(mlp, feats_hwc, calibs, z_scale, b_min, b_max, resolutions, bala
         early_arg = ctypes.byref(est)
     else:
         early_arg = None
-    ctx.check(ctx.lib.mp_recon_batch_early(
-        ctx.handle, mlp.id, n, ptrs(*[f.data_ptr() for f in feats_hwc]), c, h, w,
-        ptrs(*[cb.data_ptr() for cb in cals]), float(z_scale), bmin, bmax, res_c, len(res),
-        float(balance), _final_level(final_level), ptrs(*[v.data_ptr() for v in volumes]),
-        ptrs(*[status[b].data_ptr() for b in range(n)]), early_arg, _stream(volumes[0])), "mp_recon_batch_early")
+    if projections is None:
+        ctx.check(ctx.lib.mp_recon_batch_early(
+            ctx.handle, mlp.id, n, ptrs(*[f.data_ptr() for f in feats_hwc]), c, h, w,
+            ptrs(*[cb.data_ptr() for cb in cals]), float(z_scale), bmin, bmax, res_c, len(res),
+            float(balance), _final_level(final_level), ptrs(*[v.data_ptr() for v in volumes]),
+            ptrs(*[status[b].data_ptr() for b in range(n)]), early_arg, _stream(volumes[0])), "mp_recon_batch_early")
+    else:
+        if len(projections) != n:
+            raise ValueError("recon_batch: %d frames, %d projections" % (n, len(projections)))
+        proj = (ctypes.c_int * n)(*[_projection(p) for p in projections])
+        ctx.check(ctx.lib.mp_recon_batch_proj(
+            ctx.handle, mlp.id, n, ptrs(*[f.data_ptr() for f in feats_hwc]), c, h, w,
+            ptrs(*[cb.data_ptr() for cb in cals]), proj, float(z_scale), bmin, bmax, res_c, len(res),
+            float(balance), _final_level(final_level), ptrs(*[v.data_ptr() for v in volumes]),
+            ptrs(*[status[b].data_ptr() for b in range(n)]), early_arg, _stream(volumes[0])), "mp_recon_batch_proj")
     stream = torch.cuda.current_stream(dev)
     if expect_level0 is not None:
         for e in expect_level0:

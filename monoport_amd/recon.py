@@ -89,8 +89,12 @@ def colorization(netC, feat_tensor_C, X, Y, Z, calib_tensor, norm=None, resoluti
     X, Y, Z = X.to(device), Y.to(device), Z.to(device)
     pts = ops.vertex_points(X, Y, Z.float(), count.to(device), resolution, mat_color)
     binding = netC.bind(feat_tensor_C, calib_tensor)
-    preds = ops.query_counted(binding.mlp, binding.feat_hwc, pts, count.to(device), binding.calib,
-                              binding.z_scale)
+    if binding.projection == ops.PROJECTIONS["orthogonal"]:
+        preds = ops.query_counted(binding.mlp, binding.feat_hwc, pts, count.to(device), binding.calib,
+                                  binding.z_scale)
+    else:  # a perspective netC: the counted launch with its projection mode
+        preds = ops.query_counted_batch(binding.mlp, [binding.feat_hwc], [pts], [count.to(device)], [binding.calib],
+                                        binding.z_scale, projections=[binding.projection])[0]
     return ops.paint(X, Y, preds, 1, count.to(device), resolution, 0.5, 0.5, -np.inf, np.inf)
 
 
