@@ -198,6 +198,32 @@ int mp_query_batch(mp_ctx *ctx, int mlp, int n_frames, const float *const *feat_
                    const float *const *calib, const int *projection /*host*/, float z_scale,
                    float *const *out, mp_stream stream);
 
+/* ---- multi-view queries (SurfaceClassifier num_views = V > 1, heads/SurfaceClassifier.py:60-66) ---- */
+/* Views one mp_query_views / mp_mlp_forward_views call accepts. */
+#define MP_MAX_VIEWS 8
+
+/* MonoPortNet.query with a multi-view head (multi-view PIFu): the same n points seen by n_views (1..MP_MAX_VIEWS)
+ * calibrated cameras.  Row v of the reference's [V,Cout,N] result: view v projects the points with calib[v]
+ * (one MP_PROJ_* `projection` for all views) and samples feat_hwc[v]; layers 0-2 run per view; after layer 2
+ * the hidden rows and the features (z_feat included) are averaged over the views; layers 3-4 run once on the
+ * means, and out[v] [Cout,N] is that prediction times view v's in-image mask (MonoPortNet.py:89).  A finite
+ * view outside its image still feeds the mean with grid_sample's zero-padded samples; a view with a non-finite
+ * projection (perspective, z == 0) makes the point NaN in every row.  feat_hwc / points / calib / out are HOST
+ * arrays of n_views device pointers, each as in mp_query.  The f32 kernel only (query_views.hip): a head whose
+ * precision is not MP_PREC_F32 returns MP_ERR_UNSUPPORTED, as does n_views outside 1..MP_MAX_VIEWS.  Registered
+ * skip tables are not used; with n_views = 1 the result equals mp_query's on the plain kernels bit for bit. */
+int mp_query_views(mp_ctx *ctx, int mlp, int n_views, const float *const *feat_hwc, int c, int h, int w,
+                   const float *const *points, int64_t n, int64_t stride_n, int64_t stride_c,
+                   const float *const *calib, int projection, float z_scale, float *const *out,
+                   mp_stream stream);
+
+/* SurfaceClassifier.forward of a multi-view head on explicit features of ONE point set: feature
+ * [n_views][C+1][N] (row v*(C+1) + c, contiguous) -> out [Cout,N], the view means taken after layer 2 as in
+ * mp_query_views (no mask).  As in mp_query_views, n_views outside 1..MP_MAX_VIEWS or a head whose precision is not
+ * MP_PREC_F32 (at any n_views) returns MP_ERR_UNSUPPORTED.  With n_views = 1 the result is mp_mlp_forward's. */
+int mp_mlp_forward_views(mp_ctx *ctx, int mlp, int n_views, const float *feature, int64_t n, float *out,
+                         mp_stream stream);
+
 /* SurfaceClassifier.forward on explicit features (heads/SurfaceClassifier.py:39-71; the shape of
  * the reference's own micro-benchmark, :95-116): feature [C+1,N] (sampled features + z_feat as
  * the last row, MonoPortNet.py:82-83) -> out [Cout,N] with the last_op applied. */

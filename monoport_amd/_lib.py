@@ -87,6 +87,7 @@ class PlanWaitArgs(ctypes.Structure):
 PLAN_CONVK, PLAN_GN_APPLY, PLAN_CONV3X3, PLAN_CONV1X1, PLAN_AVGPOOL2, PLAN_UPSAMPLE2X, PLAN_MEMSET, PLAN_WAIT = range(1, 9)
 # MP_PROJ_* projection modes (include/monoport_hip.h)
 PROJ_ORTHOGONAL, PROJ_PERSPECTIVE = 0, 1
+MAX_VIEWS = 8  # MP_MAX_VIEWS: views per mp_query_views / mp_mlp_forward_views call
 
 # name -> (restype, argtypes); kept in one table so tests can check the exported surface against
 # the header (tests/test_abi.py)
@@ -117,6 +118,9 @@ SIGNATURES = {
     "mp_query_batch": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_vp,
                                _pint, c_f32, c_vp, c_vp]),
     "mp_mlp_forward": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_vp]),
+    "mp_query_views": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_i64, c_vp,
+                               c_int, c_f32, c_vp, c_vp]),
+    "mp_mlp_forward_views": (c_int, [c_vp, c_int, c_int, c_vp, c_i64, c_vp, c_vp]),
     "mp_query_counted": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_vp,
                                  c_f32, c_vp, c_vp]),
     "mp_query_counted_batch": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp,

@@ -599,6 +599,75 @@ int mp_mlp_forward(mp_ctx *ctx, int mlp, const float *feature, int64_t n, float 
                       (hipStream_t)stream);
 }
 
+int mp_query_views(mp_ctx *ctx, int mlp, int n_views, const float *const *feat_hwc, int c, int h, int w,
+                   const float *const *points, int64_t n, int64_t stride_n, int64_t stride_c,
+                   const float *const *calib, int projection, float z_scale, float *const *out,
+                   mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const Mlp *m = get_mlp(ctx, mlp);
+  int rc = check_ready(ctx, m, c);
+  if (rc != MP_OK) return rc;
+  if (n_views < 1 || n_views > kMaxViews)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_query_views: 1..%d views per call, got %d", kMaxViews, n_views);
+  if (m->precision != MP_PREC_F32)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_query_views: the multi-view kernel is f32 only (head precision %d)",
+                m->precision);
+  if (!feat_hwc || !points || !calib || !out || n < 0 || h <= 0 || w <= 0)
+    return fail(ctx, MP_ERR_ARG, "mp_query_views: bad argument");
+  rc = check_projection(ctx, "mp_query_views", &projection, 1);
+  if (rc != MP_OK) return rc;
+  ViewSetDev set;
+  std::memset(&set, 0, sizeof(set));
+  set.nv = n_views;
+  set.proj = projection;
+  set.n = n;
+  set.sn = stride_n;
+  set.sc = stride_c;
+  set.out_stride = n;
+  for (int v = 0; v < n_views; ++v) {
+    if (!feat_hwc[v] || !calib[v] || (n > 0 && (!points[v] || !out[v])))
+      return fail(ctx, MP_ERR_ARG, "mp_query_views: null buffer for view %d", v);
+    if (!aligned16(feat_hwc[v]))
+      return fail(ctx, MP_ERR_ARG, "mp_query_views: feat_hwc must be 16-byte aligned");
+    set.feat[v] = feat_hwc[v];
+    set.calib[v] = calib[v];
+    set.pts[v] = points[v];
+    set.out[v] = out[v];
+  }
+  if (n == 0) return MP_OK;
+  DeviceGuard g(ctx->device);
+  return launch_query_views(ctx, *m, set, h, w, z_scale, (hipStream_t)stream);
+}
+
+int mp_mlp_forward_views(mp_ctx *ctx, int mlp, int n_views, const float *feature, int64_t n, float *out,
+                         mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const Mlp *m = get_mlp(ctx, mlp);
+  if (!m) return fail(ctx, MP_ERR_ARG, "mp_mlp_forward_views: unknown mlp id %d", mlp);
+  int rc = check_ready(ctx, m, m->c);
+  if (rc != MP_OK) return rc;
+  if (n_views < 1 || n_views > kMaxViews)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_mlp_forward_views: 1..%d views per call, got %d", kMaxViews, n_views);
+  if (m->precision != MP_PREC_F32)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_mlp_forward_views: the multi-view kernel is f32 only (head precision %d)",
+                m->precision);
+  if (n < 0 || (n > 0 && (!feature || !out))) return fail(ctx, MP_ERR_ARG, "mp_mlp_forward_views: bad argument");
+  if (n == 0) return MP_OK;
+  ViewSetDev set;
+  std::memset(&set, 0, sizeof(set));
+  set.nv = n_views;
+  set.n = n;
+  set.sn = 1;
+  set.sc = n;
+  set.out_stride = n;
+  for (int v = 0; v < n_views; ++v) set.pts[v] = feature + (long long)v * (m->c + 1) * n;
+  set.out[0] = out;
+  DeviceGuard g(ctx->device);
+  return launch_query_views(ctx, *m, set, 0, 0, 0.0f, (hipStream_t)stream);
+}
+
 int mp_query_counted(mp_ctx *ctx, int mlp, const float *feat_hwc, int c, int h, int w,
                      const float *points, int64_t capacity, const int32_t *count,
                      const float *calib, float z_scale, float *out, mp_stream stream) {

@@ -140,6 +140,21 @@ struct QuerySetDev {
 };
 static_assert(sizeof(QuerySetDev) + 256 <= 4096, "kernel arguments: the set + two MLP descriptors must stay below 4 KB");
 
+// One multi-view launch (query_views.hip, SurfaceClassifier num_views = V > 1): V views of the same N points,
+// each with its own feature map, calibration, points and output row; one projection mode and one point layout
+// (element (c, i) of view v at pts[v][i*sn + c*sc]; output (o, i) at out[v][o*out_stride + i]).  feat[0] ==
+// nullptr: SurfaceClassifier.forward on explicit features, pts[v] = view v's [C+1, N] rows (row stride sc),
+// one output out[0].
+constexpr int kMaxViews = MP_MAX_VIEWS;
+struct ViewSetDev {
+  int nv, proj;
+  long long n, sn, sc, out_stride;
+  const float *feat[kMaxViews];
+  const float *calib[kMaxViews];
+  const float *pts[kMaxViews];
+  float *out[kMaxViews];
+};
+
 struct Mlp {
   bool used = false;
   int c = 0, cout = 0, act = 0;
@@ -233,6 +248,9 @@ int launch_index(mp_ctx *ctx, const float *feat_hwc, int c, int h, int w, const 
 int launch_orthogonal(mp_ctx *ctx, const float *pts, long long n, const float *calib, float *out,
                       hipStream_t st);
 int launch_perspective(mp_ctx *ctx, const float *pts, long long n, const float *calib, float *out,
+                       hipStream_t st);
+// query_views.hip: the multi-view query (f32, plain kernel only: registered skip tables are not looked at)
+int launch_query_views(mp_ctx *ctx, const Mlp &m, const ViewSetDev &set, int h, int w, float z_scale,
                        hipStream_t st);
 // pack.hip
 int launch_pack_hwc(mp_ctx *ctx, const float *src, int c_src, int h, int w, float *dst, int c_dst,

@@ -1,0 +1,465 @@
+// Multi-view PIFu query for gfx950 (MI355X): SurfaceClassifier(num_views = V > 1) in eval mode
+// (heads/SurfaceClassifier.py:39-71 with the view mean of :60-66) behind MonoPortNet.query
+// (MonoPortNet.py:48-91), fused like pifu_query_kernel (query.hip).
+//
+// Tile mapping: a tile's 64 MFMA columns are (point, view) pairs, column p = V g + v for the
+// G = floor(64 / V) points g of the tile and the V views v; a point's views never split across
+// tiles, columns >= G V stay dead.  Per column the kernel is the plain kernel:
+//   * gather: column p samples view v's map at view v's projection of point g.  Unlike the plain
+//     kernel a finite point OUTSIDE the image is sampled too (grid_sample's zero padding, partial
+//     taps at the border): its features feed the view mean.  Non-finite projections sample 0 and
+//     poison the whole point at the end (NaN in every row, as the reference's NaN samples do).
+//   * layers 0-2 unchanged, each column on its own features and z.
+//   * after layer 2's leaky ReLU (i == len(filters) // 2) every column of a group is replaced by
+//     the group mean IN PLACE, once per 64-row chunk of layer 2's output as it passes through the
+//     hidden-chunk buffer `hb` on its way into layer 3, and once for the feature tile `xs` (which
+//     layer 3's and layer 4's skip segments read): tmpy = feature.view(-1,V,C+1,N).mean(1).  The
+//     mean sums in view order and divides by V with one IEEE division -- torch's CPU mean over the
+//     view axis bit for bit -- so it adds no rounding of its own.  No LDS beyond the plain kernel's.
+//   * layers 3-4 run per column (redundantly within a group, ~6 % of the FLOPs); column (g, v)
+//     writes row v of the result with view v's in-image mask: preds = in_img[:, None] * pred
+//     ([V,1,N] * [1,Cout,N], MonoPortNet.py:89).
+// With V = 1 every column is its own group and the result equals pifu_query_kernel's bit for bit.
+#include <cstring>
+
+#include "mp_internal.h"
+#include "query_common.h"
+
+#include "query_mfma.h"
+
+#pragma clang fp contract(off)
+
+namespace mp {
+
+// group mean of V consecutive point rows of a swizzled point-major LDS tile, in place: the point's
+// view sum in view order, then one IEEE division by V (SurfaceClassifier.py:61-66, torch CPU mean)
+template <int ROWBYTES>
+__device__ __forceinline__ void group_mean_inplace(unsigned char *buf, int nv, int groups, int tid) {
+  constexpr int SLOTS = ROWBYTES / 16;
+  const float fv = (float)nv;
+  for (int u = tid; u < groups * SLOTS; u += kQueryThreads) {
+    const int g = u / SLOTS, s = u - g * SLOTS;
+    const int p0 = g * nv;
+    f32x4 sum = *reinterpret_cast<const f32x4 *>(buf + p0 * ROWBYTES + ((s ^ (p0 & 15)) << 4));
+    for (int v = 1; v < nv; ++v) {
+      const int p = p0 + v;
+      sum += *reinterpret_cast<const f32x4 *>(buf + p * ROWBYTES + ((s ^ (p & 15)) << 4));
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) sum[i] = __fdiv_rn(sum[i], fv);
+    for (int v = 0; v < nv; ++v) {
+      const int p = p0 + v;
+      *reinterpret_cast<f32x4 *>(buf + p * ROWBYTES + ((s ^ (p & 15)) << 4)) = sum;
+    }
+  }
+}
+
+// column p (< 64) of a tile -> (point g, view v) = (p / V, p % V) with one multiply and shift: magic =
+// ceil(65536 / V) is exact for p < 64, V <= 8, and keeps the per-lane integer division out of the kernel
+__device__ __forceinline__ void column_view(int p, int nv, int magic, int &g, int &v) {
+  g = (p * magic) >> 16;
+  v = p - g * nv;
+}
+
+// z_feat of point n in view u: the view's projection z times z_scale (MonoPortNet.py:72, :78);
+// DIRECT: row C of view u's explicit feature columns
+template <int C, bool DIRECT>
+__device__ __forceinline__ float view_z(const ViewSetDev &set, int u, long long n, float z_scale,
+                                        float &x, float &y) {
+  if constexpr (DIRECT) {
+    x = 0.0f;
+    y = 0.0f;
+    return set.pts[u][(long long)C * set.sc + n];
+  } else {
+    const float *__restrict__ cal = set.calib[u];
+    const float *__restrict__ q = set.pts[u] + n * set.sn;
+    float z;
+    project_mode(cal, set.proj, q[0], q[set.sc], q[2 * set.sc], x, y, z);
+    return __fmul_rn(z, z_scale);
+  }
+}
+
+// z_feat of column p of the tile starting at point n0: its own view's, or (mean) the group mean over the
+// views, summed in view order and divided by V like the feature means; 0 for dead columns
+template <int C, bool DIRECT>
+__device__ __forceinline__ float column_z(const ViewSetDev &set, int p, int magic, long long n0, int ncol,
+                                          float z_scale, bool mean) {
+  const int nv = set.nv;
+  int g, v;
+  column_view(p, nv, magic, g, v);
+  const long long n = n0 + g;
+  if (p >= ncol || n >= set.n) return 0.0f;
+  if (!mean) {
+    float x, y;
+    return view_z<C, DIRECT>(set, v, n, z_scale, x, y);
+  }
+  float sum = 0.0f;
+  for (int u = 0; u < nv; ++u) {
+    float x, y;
+    const float zf = view_z<C, DIRECT>(set, u, n, z_scale, x, y);
+    sum = u == 0 ? zf : sum + zf;
+  }
+  return __fdiv_rn(sum, (float)nv);
+}
+
+// DIRECT = true: SurfaceClassifier.forward on explicit features [V][C+1][N] (set.pts[v], row
+// stride set.sc), one output [Cout, N] written by the view-0 columns.
+template <int C, int COUT, int WPS, bool DIRECT>
+__global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
+    MlpPack mlp, int fh, int fw, float z_scale, int act, ViewSetDev set) {
+  constexpr int ROWB = C * 4;
+  constexpr int NGX = C / 8;  // K groups of the feature segment
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  unsigned char *xs = smem;                    // [64 columns][C] f32, swizzled 16-byte slots
+  unsigned char *hb = smem + kTilePts * ROWB;  // [64 columns][64 rows] f32, swizzled
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int j = lane & 31, h = lane >> 5;
+  const int nv = set.nv;
+  const int gpts = kTilePts / nv;  // points per tile
+  const int ncol = gpts * nv;      // live columns
+  const int magic = (65536 + nv - 1) / nv;  // column_view
+  const long long n_pts = set.n;
+  const long long tiles = (n_pts + gpts - 1) / gpts;
+
+  const int swz = h ^ (j & 15);
+  const WStream ws = make_wstream(mlp.base, mlp.n_floats, lane);
+
+  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const long long n0 = tile * gpts;
+
+    // ---------------- gather ----------------
+    if constexpr (DIRECT) {
+      // lane = column; each wave moves C/16 four-channel slots
+      int g, v;
+      column_view(lane, nv, magic, g, v);
+      const long long n = n0 + g;
+      const bool live = lane < ncol && n < n_pts;
+      const float *__restrict__ fp = set.pts[0];
+      for (int u = 1; u < nv; ++u)
+        if (u == v) fp = set.pts[u];
+      for (int s0 = wv; s0 < C / 4; s0 += 4) {
+        f32x4 r = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (live) {
+#pragma unroll
+          for (int k = 0; k < 4; ++k) r[k] = fp[(long long)(4 * s0 + k) * set.sc + n];
+        }
+        *reinterpret_cast<f32x4 *>(xs + lane * ROWB + ((s0 ^ (lane & 15)) << 4)) = r;
+      }
+    } else {
+      // 16 columns per wave, one column at a time across the wave (lane = 16-byte channel slot):
+      // the column, hence its view, is wave-uniform
+      constexpr int GB = 4;
+#pragma unroll 1
+      for (int i0 = 0; i0 < 16; i0 += GB) {
+        Taps t[GB];
+        const float *fmap[GB];
+#pragma unroll
+        for (int u = 0; u < GB; ++u) {
+          const int p = 16 * wv + i0 + u;
+          int g, v;
+          column_view(p, nv, magic, g, v);
+          const long long n = n0 + g;
+          const bool live_n = p < ncol && n < n_pts;
+          fmap[u] = set.feat[v];
+          float x = 0.0f, y = 0.0f;
+          if (live_n) (void)view_z<C, false>(set, v, n, z_scale, x, y);
+          // grid_sample on every finite projection, in the image or not (zero padding)
+          t[u] = make_taps(x, y, fh, fw, C, live_n && !non_finite(x, y));
+        }
+        f32x4 val[GB][C / 256][4];
+#pragma unroll
+        for (int u = 0; u < GB; ++u)
+#pragma unroll
+          for (int part = 0; part < C / 256; ++part)
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+              val[u][part][k] =
+                  *reinterpret_cast<const f32x4 *>(fmap[u] + t[u].o[k] + 4 * (lane + 64 * part));
+#pragma unroll
+        for (int u = 0; u < GB; ++u) {
+          const int p = 16 * wv + i0 + u;
+#pragma unroll
+          for (int part = 0; part < C / 256; ++part) {
+            const int slot = lane + 64 * part;
+            const f32x4 r = blend(val[u][part][0], val[u][part][1], val[u][part][2], val[u][part][3], t[u]);
+            *reinterpret_cast<f32x4 *>(xs + p * ROWB + ((slot ^ (p & 15)) << 4)) = r;
+          }
+        }
+      }
+    }
+    // z_feat of this wave's two column blocks for the z k-steps of layers 0-2 (lanes 0-31 carry it, 32-63 supply 0)
+    float zb[2];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) zb[cb] = h == 0 ? column_z<C, DIRECT>(set, 32 * cb + j, magic, n0, ncol, z_scale, false) : 0.0f;
+    __syncthreads();
+
+    const unsigned char *xrow = xs + j * ROWB;       // this lane's column row, column block 0
+    const unsigned char *hrow = hb + j * kHbRowBytes;
+
+    // ---------------- layers 0 + 1, fused over 64-row chunks of layer 0 (as query.hip) ----------------
+    f32x16 acc1[4][2];
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      init_from_bias(acc1[m][0], ws, mlp.bias[1] + 32 * (4 * wv + m));
+      acc1[m][1] = acc1[m][0];
+    }
+    {
+      const int rb0 = wv >> 1, cb0 = wv & 1;
+      const int a0 = mlp.ax[0] / 4;
+      const int a1 = mlp.ah[1] / 4 + (4 * wv) * (kHidden[0] / 8) * 64;
+      const float zz[1] = {zb[cb0]};
+      f32x4 ring0[kPrefetch0 + 1][1];
+      f32x16 acc0[1][1];
+      float az0[1];
+      seg_prefetch<1, kPrefetch0>(ring0, ws, a0 + rb0 * NGX * 64, 0, NGX);
+      init_from_bias(acc0[0][0], ws, mlp.bias[0] + 32 * rb0);
+      az0[0] = wload32(ws, mlp.az[0] + rb0 * 64);
+#pragma unroll 1
+      for (int ck = 0; ck < kHidden[0] / 64; ++ck) {
+        const int rb = 2 * ck + rb0;
+        seg_main<1, 1, kPrefetch0, ROWB>(acc0, ring0, ws, a0 + rb * NGX * 64, 0, NGX,
+                                         xrow + cb0 * 32 * ROWB, swz);
+        f32x4 ring1[kPrefetch1 + 1][4];
+        seg_prefetch<4, kPrefetch1>(ring1, ws, a1 + ck * 8 * 64, (kHidden[0] / 8) * 64, 8);
+        gemm_z<1, 1>(acc0, az0, zz);
+        lrelu(acc0[0][0]);
+        store_hidden(hb, acc0[0][0], rb0, cb0, j, h);
+        const int rbn = min(rb + 2, kHidden[0] / 32 - 2 + rb0);
+        seg_prefetch<1, kPrefetch0>(ring0, ws, a0 + rbn * NGX * 64, 0, NGX);
+        init_from_bias(acc0[0][0], ws, mlp.bias[0] + 32 * rbn);
+        az0[0] = wload32(ws, mlp.az[0] + rbn * 64);
+        MP_CHUNK_SYNC();
+        seg_main<4, 2, kPrefetch1, kHbRowBytes>(acc1, ring1, ws, a1 + ck * 8 * 64, (kHidden[0] / 8) * 64, 8,
+                                                hrow, swz);
+        MP_CHUNK_SYNC();
+      }
+      const int a1x = mlp.ax[1] / 4 + (4 * wv) * NGX * 64;
+      f32x4 ring1[kPrefetch1 + 1][4];
+      float az1[4];
+      seg_prefetch<4, kPrefetch1>(ring1, ws, a1x, NGX * 64, NGX);
+#pragma unroll
+      for (int m = 0; m < 4; ++m) az1[m] = wload32(ws, mlp.az[1] + (4 * wv + m) * 64);
+      seg_main<4, 2, kPrefetch1, ROWB>(acc1, ring1, ws, a1x, NGX * 64, NGX, xrow, swz);
+      gemm_z<4, 2>(acc1, az1, zb);
+#pragma unroll
+      for (int m = 0; m < 4; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) lrelu(acc1[m][n]);
+    }
+
+    // ---------------- layer 2: rows [64 wv, +64), K = 512 hidden (8 chunks) + skip ----------------
+    f32x16 acc2[2][2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+      init_from_bias(acc2[m][0], ws, mlp.bias[2] + 32 * (2 * wv + m));
+      acc2[m][1] = acc2[m][0];
+    }
+    {
+      const int a2 = mlp.ah[2] / 4 + (2 * wv) * (kHidden[1] / 8) * 64;
+      f32x4 ring2[2][2];
+      seg_prefetch<2, 1>(ring2, ws, a2, (kHidden[1] / 8) * 64, 8);
+#pragma unroll
+      for (int ck = 0; ck < 8; ++ck) {
+        if (wv == (ck >> 1)) {
+#pragma unroll
+          for (int mm = 0; mm < 2; ++mm)
+#pragma unroll
+            for (int n = 0; n < 2; ++n) store_hidden(hb, acc1[2 * (ck & 1) + mm][n], mm, n, j, h);
+        }
+        MP_CHUNK_SYNC();
+        seg_main<2, 2, 1, kHbRowBytes>(acc2, ring2, ws, a2 + ck * 8 * 64, (kHidden[1] / 8) * 64, 8,
+                                       hrow, swz);
+        if (ck < 7) seg_prefetch<2, 1>(ring2, ws, a2 + (ck + 1) * 8 * 64, (kHidden[1] / 8) * 64, 8);
+        MP_CHUNK_SYNC();
+      }
+      const int a2x = mlp.ax[2] / 4 + (2 * wv) * NGX * 64;
+      float az2[2];
+      seg_prefetch<2, 1>(ring2, ws, a2x, NGX * 64, NGX);
+#pragma unroll
+      for (int m = 0; m < 2; ++m) az2[m] = wload32(ws, mlp.az[2] + (2 * wv + m) * 64);
+      seg_main<2, 2, 1, ROWB>(acc2, ring2, ws, a2x, NGX * 64, NGX, xrow, swz);
+      gemm_z<2, 2>(acc2, az2, zb);
+#pragma unroll
+      for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) lrelu(acc2[m][n]);
+    }
+
+    // ---------------- layer 3 on the view means: rows [32 wv, +32), K = 256 hidden (4 chunks) + skip ----------------
+    f32x16 acc3[1][2];
+    init_from_bias(acc3[0][0], ws, mlp.bias[3] + 32 * wv);
+    acc3[0][1] = acc3[0][0];
+    {
+      const int a3 = mlp.ah[3] / 4 + wv * (kHidden[2] / 8) * 64;
+      f32x4 ring3[4][1];
+      seg_prefetch<1, 3>(ring3, ws, a3, 0, 8);
+#pragma unroll
+      for (int ck = 0; ck < 4; ++ck) {
+        if (wv == ck) {
+#pragma unroll
+          for (int mm = 0; mm < 2; ++mm)
+#pragma unroll
+            for (int n = 0; n < 2; ++n) store_hidden(hb, acc2[mm][n], mm, n, j, h);
+        }
+        MP_CHUNK_SYNC();
+        if (nv > 1) {
+          // y = y.view(-1,V,256,N).mean(1), this chunk's 64 rows; the first chunk also takes
+          // tmpy = feature.view(-1,V,C+1,N).mean(1) -- every wave is past layer 2's reads of xs
+          group_mean_inplace<kHbRowBytes>(hb, nv, gpts, tid);
+          if (ck == 0) group_mean_inplace<ROWB>(xs, nv, gpts, tid);
+          __syncthreads();
+        }
+        seg_main<1, 2, 3, kHbRowBytes>(acc3, ring3, ws, a3 + ck * 8 * 64, 0, 8, hrow, swz);
+        if (ck < 3) seg_prefetch<1, 3>(ring3, ws, a3 + (ck + 1) * 8 * 64, 0, 8);
+        MP_CHUNK_SYNC();
+      }
+      const int a3x = mlp.ax[3] / 4 + wv * NGX * 64;
+      float az3[1];
+      seg_prefetch<1, 3>(ring3, ws, a3x, 0, NGX);
+      az3[0] = wload32(ws, mlp.az[3] + wv * 64);
+      seg_main<1, 2, 3, ROWB>(acc3, ring3, ws, a3x, 0, NGX, xrow, swz);
+      // the z row of tmpy: the group mean of z_feat (made here rather than kept live through layers 0-2)
+      float zm[2];
+#pragma unroll
+      for (int cb = 0; cb < 2; ++cb) zm[cb] = h == 0 ? column_z<C, DIRECT>(set, 32 * cb + j, magic, n0, ncol, z_scale, true) : 0.0f;
+      gemm_z<1, 2>(acc3, az3, zm);
+#pragma unroll
+      for (int n = 0; n < 2; ++n) lrelu(acc3[0][n]);
+    }
+
+    // ---------------- layer 4 (Cout x (128 + C + 1)) on the VALU, as query.hip ----------------
+    float *red = reinterpret_cast<float *>(hb);
+    constexpr int K4 = (kHidden[3] + C + 1 + 3) & ~3;
+    {
+#pragma unroll
+      for (int o = 0; o < COUT; ++o) {
+        const float *w4 = (mlp.base + mlp.w4) + o * K4 + 32 * wv + 4 * h;
+        float s0 = 0.0f, s1 = 0.0f;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const f32x4 wq = *reinterpret_cast<const f32x4 *>(w4 + 8 * q);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            s0 = fmaf(wq[i], acc3[0][0][4 * q + i], s0);
+            s1 = fmaf(wq[i], acc3[0][1][4 * q + i], s1);
+          }
+        }
+        s0 += __shfl_xor(s0, 32);
+        s1 += __shfl_xor(s1, 32);
+        if (h == 0) {
+          red[(wv * COUT + o) * kTilePts + j] = s0;
+          red[(wv * COUT + o) * kTilePts + 32 + j] = s1;
+        }
+      }
+      const int p = lane;
+      float sx[COUT];
+#pragma unroll
+      for (int o = 0; o < COUT; ++o) sx[o] = 0.0f;
+      constexpr int SLOTS = C / 16;
+#pragma unroll 4
+      for (int s = 0; s < SLOTS; ++s) {
+        const int slot = wv * SLOTS + s;
+        const f32x4 xv =
+            *reinterpret_cast<const f32x4 *>(xs + p * ROWB + ((slot ^ (p & 15)) << 4));
+#pragma unroll
+        for (int o = 0; o < COUT; ++o) {
+          const f32x4 wq =
+              *reinterpret_cast<const f32x4 *>((mlp.base + mlp.w4) + o * K4 + kHidden[3] + 4 * slot);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) sx[o] = fmaf(wq[i], xv[i], sx[o]);
+        }
+      }
+#pragma unroll
+      for (int o = 0; o < COUT; ++o) red[((4 + wv) * COUT + o) * kTilePts + p] = sx[o];
+    }
+    __syncthreads();
+    if (tid < COUT * kTilePts) {
+      const int o = tid / kTilePts, p = tid % kTilePts;
+      int g, v;
+      column_view(p, nv, magic, g, v);
+      const long long n = n0 + g;
+      if (p < ncol && n < n_pts) {
+        float val = (mlp.base + mlp.bias[4])[o];
+#pragma unroll
+        for (int part = 0; part < 8; ++part) val += red[(part * COUT + o) * kTilePts + p];
+        const float wz = (mlp.base + mlp.w4)[o * K4 + kHidden[3] + C];
+        // the group's z mean, this column's own projection and whether any view is non-finite
+        float zsum = 0.0f, xo = 0.0f, yo = 0.0f;
+        bool poisoned = false;
+        float *__restrict__ out = set.out[0];
+        for (int u = 0; u < nv; ++u) {
+          float x, y;
+          const float zf = view_z<C, DIRECT>(set, u, n, z_scale, x, y);
+          zsum = u == 0 ? zf : zsum + zf;
+          poisoned = poisoned || (set.proj == MP_PROJ_PERSPECTIVE && non_finite(x, y));
+          if (u == v) {
+            xo = x;
+            yo = y;
+            if (!DIRECT) out = set.out[u];
+          }
+        }
+        val = fmaf(wz, __fdiv_rn(zsum, (float)nv), val);
+        if constexpr (DIRECT) {
+          if (v == 0) out[o * set.out_stride + n] = activate(val, act);
+        } else {
+          // MonoPortNet.py:89 per view; a non-finite view's NaN samples reach every row through the mean
+          const float r = poisoned ? __builtin_nanf("") : in_image(xo, yo) ? activate(val, act) : 0.0f;
+          out[o * set.out_stride + n] = r;
+        }
+      }
+    }
+    __syncthreads();  // red / xs are rewritten by the next tile
+  }
+}
+
+// ---- host side -----------------------------------------------------------------------------------
+template <int C, int COUT, int WPS, bool DIRECT>
+static int launch_views_t(mp_ctx *ctx, const Mlp &m, const ViewSetDev &set, int h, int w, float z_scale,
+                          hipStream_t st) {
+  constexpr int lds = kTilePts * C * 4 + kHbBytes;
+  auto kern = pifu_query_views_kernel<C, COUT, WPS, DIRECT>;
+  const void *kern_id = reinterpret_cast<const void *>(kern);
+  if (!ctx->lds_attr_done.count(kern_id)) {
+    MP_HIP(ctx, hipFuncSetAttribute(kern_id, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    ctx->lds_attr_done.insert(kern_id);
+  }
+  const long long gpts = kTilePts / set.nv;
+  const long long tiles = (set.n + gpts - 1) / gpts;
+  if (tiles <= 0) return MP_OK;
+  const long long resident = (long long)cus_of(ctx, st) * WPS;
+  const long long grid = tiles < 8 * resident ? tiles : 8 * resident;
+  const bool prof = 2 * (ctx->prof_used + 1) <= (int)ctx->prof_events.size();
+  if (prof) MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used], st));
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kQueryThreads), lds, st, m.pack(), h, w, z_scale, m.act,
+                     set);
+  if (prof) {
+    MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used + 1], st));
+    ++ctx->prof_used;
+  }
+  MP_HIP(ctx, hipGetLastError());
+  return MP_OK;
+}
+
+int launch_query_views(mp_ctx *ctx, const Mlp &m, const ViewSetDev &set, int h, int w, float z_scale,
+                       hipStream_t st) {
+  if (set.nv < 1 || set.nv > kMaxViews)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "multi-view query: 1..%d views, got %d", kMaxViews, set.nv);
+  const bool direct = set.feat[0] == nullptr;
+#define MP_VCASE(CC, CO, WP)                                                                     \
+  if (m.c == CC && m.cout == CO) {                                                               \
+    if (direct) return launch_views_t<CC, CO, WP, true>(ctx, m, set, h, w, z_scale, st);         \
+    return launch_views_t<CC, CO, WP, false>(ctx, m, set, h, w, z_scale, st);                    \
+  }
+  MP_VCASE(256, 1, 2)
+  MP_VCASE(256, 3, 2)
+  MP_VCASE(512, 1, 1)
+  MP_VCASE(512, 3, 1)
+#undef MP_VCASE
+  return fail(ctx, MP_ERR_UNSUPPORTED,
+              "multi-view query kernels are built for C in {256,512}, Cout in {1,3}; got C=%d Cout=%d", m.c, m.cout);
+}
+
+}  // namespace mp

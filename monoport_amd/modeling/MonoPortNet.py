@@ -143,6 +143,11 @@ class MonoPortNet(nn.Module):
         map gets a skip table (``_skip_table``)."""
         if self.training:
             raise NotImplementedError("monoport_amd implements the inference path (net.eval())")
+        if self.surface_classifier.num_views > 1:
+            # a binding is one frame on the single-view kernels (octree engine, skip tables, colour queries); a
+            # multi-view head runs through query() only
+            raise NotImplementedError("bind(): the head has num_views = %d; multi-view heads are served by query() "
+                                      "(mp_query_views), not by the single-view engines" % self.surface_classifier.num_views)
         feats = list(feats_stages[-1])  # eval keeps the last stage only (MonoPortNet.py:63-64)
         dev = feats[0].device
         if calibs is None:
@@ -209,13 +214,19 @@ class MonoPortNet(nn.Module):
         """points [B,3,N] world coords (any strides) -> [ [B,Cout,N] ] (MonoPortNet.py:48-91, eval mode).
         Out-of-image points come back as exactly 0 (:89); under the perspective projection a point with
         z == 0 comes back as NaN, as in the reference (0 * the NaN grid_sample samples there).  B > 1 runs as
-        one mp_query_batch launch per ops.MAX_FRAMES frames; each frame's map keeps its own skip-table policy."""
+        one mp_query_batch launch per ops.MAX_FRAMES frames; each frame's map keeps its own skip-table policy.
+        A multi-view head (num_views = V > 1) takes points [V,3,N] of one point set and returns [V,Cout,N]
+        (``_query_views``)."""
         if transforms is not None:
             raise NotImplementedError("query(transforms=...): the reference's own orthogonal() / perspective() "
                                       "fail on every shape of it (transforms[:2, 2:3] is empty, baddbmm raises)")
         cap = getattr(_tls, "capture", None)
         if points.dim() != 3 or points.shape[1] != 3:
             raise ValueError("points must be [B,3,N], got %s" % (tuple(points.shape),))
+        if self.surface_classifier.num_views > 1:
+            if cap is not None:
+                cap.calls += 1  # never a binding: the fused octree engine is single-view (INTEGRATION.md section 1)
+            return [self._query_views(feats_stages, points, calibs)]
         if points.shape[0] != 1:
             if cap is not None:
                 cap.calls += 1  # B > 1 is not a binding of the fused octree engine (RTL/main.py:175 is B = 1)
@@ -249,6 +260,42 @@ class MonoPortNet(nn.Module):
             ops.query_batch(bs[0].mlp, [b.feat_hwc for b in bs], points[b0:b1], [b.calib for b in bs],
                             [b.projection for b in bs], bs[0].z_scale, out=out[b0:b1])
         return out
+
+    def _query_views(self, feats_stages, points, calibs):
+        """Multi-view head (SurfaceClassifier num_views = V > 1): rows = B*V views of B point sets.  The
+        reference's result is [B*V,Cout,N] only for B = 1 (MonoPortNet.py:89 broadcasts in_img [B*V,1,N] against
+        pred [B,Cout,N]); like it, B > 1 and rows that are not groups of V raise RuntimeError.  One
+        mp_query_views launch; skip tables are not made or used."""
+        if self.training:
+            raise NotImplementedError("monoport_amd implements the inference path (net.eval())")
+        v_n, rows, n = self.surface_classifier.num_views, points.shape[0], points.shape[2]
+        if rows % v_n:
+            raise RuntimeError("query: %d point rows are not groups of num_views = %d (the reference's "
+                               "view(-1, %d, C, N) raises)" % (rows, v_n, v_n))
+        if rows != v_n:
+            raise RuntimeError("query: a multi-view head takes ONE point set of %d views; %d rows would be %d sets, "
+                               "and the reference's in_img * pred cannot broadcast [%d,1,N] against [%d,Cout,N]"
+                               % (v_n, rows, rows // v_n, rows, rows // v_n))
+        feats = feats_stages[-1]
+        if any(f.shape[0] != v_n for f in feats) or (calibs is not None and calibs.dim() == 3
+                                                      and calibs.shape[0] != v_n):
+            raise ValueError("query: %d views, feature maps of batch %s, calibrations %s"
+                             % (v_n, [f.shape[0] for f in feats], None if calibs is None else tuple(calibs.shape)))
+        dev = feats[0].device
+        if calibs is None:
+            # xyz = points for every view (MonoPortNet.py:66-67)
+            calibs = torch.eye(4, device=dev)[None].expand(v_n, 4, 4)
+            projection = ops.PROJECTIONS["orthogonal"]
+        else:
+            if calibs.dim() == 2:
+                calibs = calibs[None].expand(v_n, *calibs.shape)
+            projection = ops.PROJECTIONS["perspective" if self.projection is perspective else "orthogonal"]
+        mlp = self.surface_classifier.packed()
+        if mlp.ctx.device_index != (dev.index if dev.index is not None else torch.cuda.current_device()):
+            raise RuntimeError("surface_classifier and the feature maps must be on one GPU "
+                               "(RTL/main.py:382-387 moves the features first)")
+        maps = [self._packed_features(feats, v) for v in range(v_n)]
+        return ops.query_views(mlp, maps, points, calibs, projection, self.normalizer.scale)
 
     def get_loss(self, pred_stages, labels):
         """Average MSE / L1 over stages (MonoPortNet.py:93-117); plain tensor ops."""

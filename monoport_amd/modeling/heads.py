@@ -6,6 +6,8 @@ The parameters live in ``filters.{i}`` Conv1d(k=1) modules so checkpoints load u
 the weights re-packed into MFMA fragment order.  The copy is refreshed automatically whenever a
 parameter tensor is replaced or modified in place.
 """
+import numbers
+
 import torch
 import torch.nn as nn
 
@@ -17,13 +19,14 @@ _ACT_CODES = {None: 0, "sigmoid": 1, "tanh": 2}
 class SurfaceClassifier(nn.Module):
     def __init__(self, filter_channels, num_views=1, no_residual=False, last_op=None):
         super().__init__()
-        if num_views != 1:
-            raise NotImplementedError("multi-view averaging (SurfaceClassifier.py:60-66) is unused "
-                                      "by the PIFu configs")
+        if (isinstance(num_views, bool) or not isinstance(num_views, numbers.Integral)
+                or not 1 <= num_views <= ops.MAX_VIEWS):
+            raise ValueError("num_views must be an integer 1..%d (the multi-view kernel's MP_MAX_VIEWS), got %r"
+                             % (ops.MAX_VIEWS, num_views))
         if no_residual:
             raise NotImplementedError("only the skip-concat variant (no_residual=False) is used")
         self.filter_channels = list(filter_channels)
-        self.num_views = num_views
+        self.num_views = int(num_views)  # V > 1: multi-view PIFu, views averaged after layer 2 (:60-66)
         self.no_residual = no_residual
         if isinstance(last_op, nn.Sigmoid):
             last_op = "sigmoid"
@@ -47,6 +50,8 @@ class SurfaceClassifier(nn.Module):
     def set_precision(self, precision):
         if precision not in ops.PRECISIONS:
             raise ValueError("precision must be one of %s" % sorted(ops.PRECISIONS))
+        if self.num_views > 1 and precision != "f32":
+            raise ValueError("a multi-view head (num_views = %d) runs the f32 kernel only" % self.num_views)
         self.precision = precision
         self._packed_key = None  # re-pack on next use
         return self
@@ -75,9 +80,17 @@ class SurfaceClassifier(nn.Module):
     def forward(self, feature):
         """[B, C_in, N] -> [B, C_out, N] on explicit features (SurfaceClassifier.py:39-71): the same
         fused MFMA kernel as MonoPortNet.query with the gather stage reading the given features
-        (the reconstruction path itself never materialises this tensor)."""
+        (the reconstruction path itself never materialises this tensor).  A multi-view head takes
+        [B*V, C_in, N] (V consecutive rows per point set) and returns [B, C_out, N]."""
         mlp = self.packed()
-        return torch.cat([ops.mlp_forward(mlp, feature[b:b + 1]) for b in range(feature.shape[0])], 0)
+        v = self.num_views
+        if v == 1:
+            return torch.cat([ops.mlp_forward(mlp, feature[b:b + 1]) for b in range(feature.shape[0])], 0)
+        if feature.dim() != 3 or feature.shape[0] % v:
+            # the reference's y.view(-1, V, C, N) raises RuntimeError on these
+            raise RuntimeError("SurfaceClassifier(num_views=%d): %s rows are not groups of %d views"
+                               % (v, tuple(feature.shape), v))
+        return torch.cat([ops.mlp_forward_views(mlp, feature[b:b + v]) for b in range(0, feature.shape[0], v)], 0)
 
 
 def PIFuNetGMLP(*args, **kwargs):

@@ -413,6 +413,72 @@ def mlp_forward(mlp, feature):
     return out
 
 
+MAX_VIEWS = _lib.MAX_VIEWS  # MP_MAX_VIEWS
+
+
+def _check_views(mlp, v_n, who):
+    if not 1 <= v_n <= MAX_VIEWS:
+        raise ValueError("%s: 1..%d views per call, got %d" % (who, MAX_VIEWS, v_n))
+
+
+def query_views(mlp, feats_hwc, points, calibs, projection, z_scale, out=None):
+    """mp_query_views: MonoPortNet.query of a multi-view head (SurfaceClassifier num_views = V, multi-view PIFu).
+    feats_hwc: V channels-last maps [H,W,C]; points [V,3,N] with ANY strides (row v = the points as view v's
+    caller passes them); calibs: V calibrations ([>=3,4] each, or one [V,>=3,4] tensor); projection: ONE MP_PROJ_*
+    int or name for all views.  -> [V,Cout,N] (or into ``out``, whose views must each be contiguous [Cout,N]):
+    row v is the view-averaged prediction times view v's in-image mask.  f32 heads only; registered skip tables
+    are not used."""
+    ctx = mlp.ctx
+    v_n = len(feats_hwc)
+    _check_views(mlp, v_n, "query_views")
+    if points.dim() != 3 or points.shape[0] != v_n or points.shape[1] != 3:
+        raise ValueError("points must be [%d,3,N], got %s" % (v_n, tuple(points.shape)))
+    if points.dtype != torch.float32:
+        points = points.float()
+    h, w, c = feats_hwc[0].shape
+    dev = feats_hwc[0].device
+    for f in feats_hwc:
+        if tuple(f.shape) != (h, w, c) or not f.is_contiguous() or f.dtype != torch.float32:
+            raise ValueError("query_views: the maps must be contiguous float32 [%d,%d,%d]" % (h, w, c))
+    if torch.is_tensor(calibs) and calibs.dim() == 3:
+        calibs = [calibs[v] for v in range(calibs.shape[0])]
+    if len(calibs) != v_n:
+        raise ValueError("query_views: %d maps, %d calibrations" % (v_n, len(calibs)))
+    cals = [_calib_dev(cb, dev) for cb in calibs]
+    n = points.shape[2]
+    if out is None:
+        out = torch.empty((v_n, mlp.cout, n), dtype=torch.float32, device=dev)
+    elif (out.shape != (v_n, mlp.cout, n) or out.dtype != torch.float32
+          or (n > 0 and not all(out[v].is_contiguous() for v in range(v_n)))):
+        raise ValueError("query_views: out must be float32 [%d,%d,%d] with contiguous views" % (v_n, mlp.cout, n))
+    ptrs = ctypes.c_void_p * v_n
+    ctx.check(ctx.lib.mp_query_views(
+        ctx.handle, mlp.id, v_n, ptrs(*[f.data_ptr() for f in feats_hwc]), c, h, w,
+        ptrs(*[points[v].data_ptr() for v in range(v_n)]), n, points.stride(2), points.stride(1),
+        ptrs(*[cb.data_ptr() for cb in cals]), _projection(projection), float(z_scale),
+        ptrs(*[out[v].data_ptr() for v in range(v_n)]), _stream(out)), "mp_query_views")
+    stream = torch.cuda.current_stream(dev)
+    for t in cals:
+        t.record_stream(stream)
+    return out
+
+
+def mlp_forward_views(mlp, feature):
+    """SurfaceClassifier.forward of a multi-view head on ONE point set: feature [V,C+1,N] (the V views' rows,
+    SurfaceClassifier.py:60-66) -> [1,Cout,N] (mp_mlp_forward_views)."""
+    ctx = mlp.ctx
+    if feature.dim() != 3 or feature.shape[1] != mlp.c + 1:
+        raise ValueError("feature must be [V,%d,N], got %s" % (mlp.c + 1, tuple(feature.shape)))
+    v_n = feature.shape[0]
+    _check_views(mlp, v_n, "mlp_forward_views")
+    f = _f32c(feature)
+    n = f.shape[2]
+    out = torch.empty((1, mlp.cout, n), dtype=torch.float32, device=f.device)
+    ctx.check(ctx.lib.mp_mlp_forward_views(ctx.handle, mlp.id, v_n, _ptr(f), n, _ptr(out), _stream(f)),
+              "mp_mlp_forward_views")
+    return out
+
+
 def query_counted(mlp, feat_hwc, points, count, calib, z_scale, out=None):
     """mp_query_counted: points [3,cap] contiguous, count int32[1] on device -> [Cout,cap]."""
     ctx = mlp.ctx

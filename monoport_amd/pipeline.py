@@ -45,6 +45,10 @@ class FrameSlot:
     def __init__(self, netG, device, resolutions=RESOLUTIONS, b_min=(-1, -1, -1), b_max=(1, 1, 1),
                  balance=0.5, feature_hook=None, use_graph=False, netC=None, batch=1, skip_table=None,
                  final_level="dilate3"):
+        for name, net in (("netG", netG), ("netC", netC)):
+            if net is not None and net.surface_classifier.num_views > 1:
+                raise NotImplementedError("FrameSlot: %s has a multi-view head (num_views = %d); the slot runs the "
+                                          "single-view octree / colour engines" % (name, net.surface_classifier.num_views))
         self.net = netG
         self.netC = netC
         self.device = torch.device(device)
