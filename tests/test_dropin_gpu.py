@@ -351,12 +351,21 @@ def test_frame_pipeline_matches_direct_calls(skip_table):
             slot.wait()
             assert slot.n_active == min(batch, 6 - s0)
             for b in range(slot.n_active):
-                got.append((slot.status[b].cpu(), slot.renders[b].cpu()))
+                got.append((slot.status[b].cpu(), slot.renders[b].cpu(), slot.feats_hwc[b].clone()))
         assert len(got) == 6
-        for (st_d, r_d), (st_p, r_p) in zip(direct, got):
+        for f, ((st_d, r_d), (st_p, r_p, fh_p)) in enumerate(zip(direct, got)):
             assert torch.equal(st_d, st_p)  # same points queried at every level
             # at batch > 1 the convolution launches pick other tile shapes (another summation order): features differ in the last bits
             assert (r_d - r_p).abs().max().item() <= (0.0 if batch == 1 else 2e-3)
+            # given the slot's own features, everything downstream of them is the single-frame calls bit for bit
+            with torch.no_grad():
+                table = ops.skip_table(mlp, fh_p) if skip_table else None
+                vol, st = ops.recon(mlp, fh_p, calibs[f], syn.Z_SCALE, [-1] * 3, [1] * 3, res)
+                x, y, z, n, c = ops.forward_vertices_raw(vol, "front")
+                r_own = ops.paint(x, y, n, 0, c, res[-1], 0.5, 0.5, 0.0, 1.0).cpu()
+                if skip_table:
+                    table.release()
+            assert torch.equal(st.cpu(), st_p) and torch.equal(r_own, r_p)
 
 
 def test_frame_pipeline_is_deterministic_under_concurrency():
