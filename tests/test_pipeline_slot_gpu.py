@@ -7,7 +7,10 @@ the 128-channel Winograd kernel once tiles * n * cout / 128 >= 2048, the direct 
 GroupNorm statistics slices), so the whole encoder is compared with a float64 copy of itself on every 3x3 route, and
 the slot's results are split into two checks: its features against float64, and everything downstream of them
 against the single-frame calls on those same features, bit for bit (recon_batch == recon, paint_batch == paint and
-query_counted_batch == query_counted are contracts of their own).  Needs an MI355X."""
+query_counted_batch == query_counted are contracts of their own).  The bench's other legs are built and checked
+the same way: f16x3 encoder and head in slots of 16 / 10 (`alt_precision`), 17..513 with the f16w head in slots of
+16 (`levels6_f16w`), the upstream / interpolate last levels (`final_level_rules`) and two slots of 4 in flight
+(`in_flight_8`).  Needs an MI355X."""
 import time
 
 import numpy as np
@@ -210,54 +213,66 @@ def test_netc_filter_with_prior_at_batch_20_vs_float64(nets):
     assert err <= ENCODER_BAR
 
 
-def _run_bench_slots(batch, n_frames, warm, with_color):
-    """bench.make_pipeline's pipeline (3 slots, hipGraph encoder, f32, BASELINE resolutions); ``warm`` frames, then
-    ``n_frames`` frames submitted back to back as bench.timed_passes does, with a device-side snapshot of every
-    submission's results on the slot's stream (no host sync).  Returns (snapshots, slot-0 facts)."""
+def _run_bench_slots(batch, n_frames, warm, with_color, precision="f32", resolutions=None, final_level="dilate3",
+                     depth=3):
+    """bench.make_pipeline's pipeline (``depth`` slots, hipGraph encoder; bench.RESOLUTIONS, f32 and the dilate3 last
+    level unless told otherwise); ``warm`` frames, then ``n_frames`` frames submitted back to back as
+    bench.timed_passes does, with a device-side snapshot of every submission's results on the slot's stream (no host
+    sync).  Returns (snapshots, slot-0 facts).  bench.build_netg(dev, "f16x3") switches the encoder's 3x3
+    convolutions to f16x3 process-wide: the switch is set back to f32 before this returns."""
     import bench
-    pipe = bench.make_pipeline(torch.device(DEV), 3, True, bench.RESOLUTIONS, with_color, "f32", batch)
+    from monoport_amd.modeling import backbones
     try:
-        s = pipe.slots[0]
-        assert all(sl.hwc_direct and sl.graph is not None for sl in pipe.slots)
-        facts = {"mlp": s.net.surface_classifier.packed(), "tables": s.tables is not None,
-                 "mlp_c": s.netC.surface_classifier.packed() if with_color else None,
-                 "mat_color": s.mat_color if with_color else None}
-        snaps = []
-        total = warm + n_frames
-        for s0 in range(0, total, batch):
-            s1 = min(s0 + batch, total)
-            frames = list(range(s0, s1))
-            slot = pipe.submit([_image(f % N_DISTINCT)[None] for f in frames], [_calib(f) for f in frames])
-            if s0 < warm:
-                continue
-            n = s1 - s0
-            assert slot.n_active == n
-            with torch.cuda.stream(slot.stream):
-                snap = {"frames": frames, "feat": slot.feat_hwc_all[:n].clone(), "status": slot.status[:n].clone(),
-                        "render": [slot.renders[b].clone() for b in range(n)],
-                        "volume": [slot.volumes[b].clone() for b in range(n)]}
-                if with_color:
-                    snap["feat_c"] = [slot.feats_hwc_c[b].clone() for b in range(n)]
-                    snap["tex"] = [slot.renders_tex[b].clone() for b in range(n)]
-            snaps.append(snap)
-        pipe.synchronize()
+        pipe = bench.make_pipeline(torch.device(DEV), depth, True, resolutions or bench.RESOLUTIONS, with_color,
+                                   precision, batch, final_level)
+        try:
+            s = pipe.slots[0]
+            assert all(sl.hwc_direct and sl.graph is not None for sl in pipe.slots)
+            assert s.net.surface_classifier.precision == precision and s.final_level == final_level
+            facts = {"mlp": s.net.surface_classifier.packed(), "tables": s.tables is not None,
+                     "mlp_c": s.netC.surface_classifier.packed() if with_color else None,
+                     "mat_color": s.mat_color if with_color else None,
+                     "res": list(s.res), "final_level": s.final_level}
+            snaps = []
+            total = warm + n_frames
+            for s0 in range(0, total, batch):
+                s1 = min(s0 + batch, total)
+                frames = list(range(s0, s1))
+                slot = pipe.submit([_image(f % N_DISTINCT)[None] for f in frames], [_calib(f) for f in frames])
+                if s0 < warm:
+                    continue
+                n = s1 - s0
+                assert slot.n_active == n
+                with torch.cuda.stream(slot.stream):
+                    snap = {"frames": frames, "feat": slot.feat_hwc_all[:n].clone(),
+                            "status": slot.status[:n].clone(),
+                            "render": [slot.renders[b].clone() for b in range(n)],
+                            "volume": [slot.volumes[b].clone() for b in range(n)]}
+                    if with_color:
+                        snap["feat_c"] = [slot.feats_hwc_c[b].clone() for b in range(n)]
+                        snap["tex"] = [slot.renders_tex[b].clone() for b in range(n)]
+                snaps.append(snap)
+            pipe.synchronize()
+        finally:
+            pipe.close()
     finally:
-        pipe.close()
+        backbones.set_encoder_conv_precision("f32")
     torch.cuda.synchronize()
     return snaps, facts
 
 
 def _single_frame_geometry(facts, feat, calib):
-    """The single-frame calls on one frame's features: skip table (when the slot makes them), octree, visible
-    vertices, normal render."""
+    """The single-frame calls on one frame's features, with the slot's head (its precision), grids and last-level
+    rule: skip table (when the slot makes them), octree, visible vertices, normal render."""
     from monoport_amd import ops
     import bench
     table = ops.skip_table(facts["mlp"], feat) if facts["tables"] else None
     try:
-        vol, st = ops.recon(facts["mlp"], feat, calib, syn.Z_SCALE, bench.B_MIN, bench.B_MAX, bench.RESOLUTIONS)
+        vol, st = ops.recon(facts["mlp"], feat, calib, syn.Z_SCALE, bench.B_MIN, bench.B_MAX, facts["res"],
+                            final_level=facts["final_level"])
         raw = ops.forward_vertices_raw(vol, "front")
         x, y, _, nrm, count = raw
-        render = ops.paint(x, y, nrm, 0, count, bench.RESOLUTIONS[-1], 0.5, 0.5, 0.0, 1.0)
+        render = ops.paint(x, y, nrm, 0, count, facts["res"][-1], 0.5, 0.5, 0.0, 1.0)
         torch.cuda.synchronize()
     finally:
         if table is not None:
@@ -268,7 +283,6 @@ def _single_frame_geometry(facts, feat, calib):
 def _check_slot_frames(snaps, facts, ref, f64_positions):
     """Per frame: hook channels exact, features vs float64 where asked, downstream of the features bit for bit.
     Returns the largest feature error against float64."""
-    import bench
     from monoport_amd import ops
     planes = torch.from_numpy(syn.body_feature_planes(128, 128)).to(DEV).permute(1, 2, 0)
     worst = 0.0
@@ -294,7 +308,7 @@ def _check_slot_frames(snaps, facts, ref, f64_positions):
                 feat_c = snap["feat_c"][b]
                 assert torch.equal(feat_c[..., :256], feat), "frame %d: netC's prior is not netG's map" % f
                 x, y, z, _, count = raw
-                r = bench.RESOLUTIONS[-1]
+                r = facts["res"][-1]
                 pts = ops.vertex_points(x, y, z, count, r, facts["mat_color"])
                 pred = ops.query_counted(facts["mlp_c"], feat_c, pts, count, calib, syn.Z_SCALE)
                 tex = ops.paint(x, y, pred, 1, count, r, 0.5, 0.5, -np.inf, np.inf)
@@ -335,3 +349,132 @@ def test_bench_colour_slot_frame_by_frame(nets):
     print("bench colour slot of 20, 45 frames: netG features vs float64 max %.3g, netC features %.3g; geometry and "
           "texture renders equal the single-frame calls (%.1f s)" % (worst, worst_c, time.perf_counter() - t0))
     assert worst_c <= ENCODER_BAR
+
+
+def _oracle_decisions(oracle, facts, feat, calib):
+    """oracle.seg3d_lossless (the CPU restatement of the octree) with the slot's grids and last-level rule, driven
+    by the slot's HIP query kernel on one frame's features (through the frame's skip table when the slot makes
+    them): (volume, points per level).  Both sides get their occupancies from the same kernel, so they take the
+    same decisions and give the same volume bits."""
+    import bench
+    from monoport_amd import ops
+    table = ops.skip_table(facts["mlp"], feat) if facts["tables"] else None
+    try:
+        def gpu_query(pts):
+            return ops.query(facts["mlp"], feat, torch.from_numpy(np.ascontiguousarray(pts))[None].to(DEV), calib,
+                             syn.Z_SCALE)[0, 0].cpu().numpy()
+
+        stats = []
+        vol = oracle.seg3d_lossless(gpu_query, bench.B_MIN, bench.B_MAX, facts["res"], stats=stats,
+                                    final_level=facts["final_level"])
+    finally:
+        if table is not None:
+            table.release()
+    return vol, stats
+
+
+@pytest.mark.parametrize("steps,n_frames", [(32, 40), (20, 25)])
+def test_bench_f16x3_slot_frame_by_frame(nets, steps, n_frames):
+    """The bench's `alt_precision` leg as bench.py builds it: bench.make_pipeline(..., "f16x3",
+    pick_batch(steps, 16)) -- slots of 16 frames at the default 32 steps and of 10 at --steps 20, here with a short
+    last slot (16 + 16 + 8, 10 + 10 + 5).  The encoder's 3x3 convolutions and the query run f16x3; the f16x3 head
+    reads skip tables.  Frames 0, n/2 and n-1 of every slot: features against float64 (1e-4); the first slot's
+    features differ from the f32 encoder's at the same batch on the same images (the f16x3 kernels ran, not a
+    stale f32 graph or pack); every frame: status, volume and render = the single-frame calls with the f16x3 head,
+    bit for bit."""
+    import bench
+    from monoport_amd.modeling import backbones
+    netg, _, ref = nets
+    batch = bench.pick_batch(steps, 16)
+    assert batch == {32: 16, 20: 10}[steps]
+    t0 = time.perf_counter()
+    snaps, facts = _run_bench_slots(batch, n_frames, 0, False, precision="f16x3")
+    assert backbones.ENCODER_CONV_PRECISION == "f32"
+    assert [len(s["frames"]) for s in snaps] == [batch, batch, n_frames - 2 * batch]
+    assert facts["tables"] and facts["mlp"].precision == "f16x3"
+    worst = _check_slot_frames(snaps, facts, ref, lambda n: {0, n // 2, n - 1})
+    first = snaps[0]
+    imgs = torch.stack([_image(f % N_DISTINCT) for f in first["frames"]])
+    with torch.no_grad():
+        f32 = netg.image_filter(imgs, last_only=True, graphed=False)[-1][0].permute(0, 2, 3, 1)
+    moved = [(first["feat"][b, ..., 2:] - f32[b, ..., 2:]).abs().max().item() for b in _checked(batch)]
+    del f32
+    print("bench f16x3 slot of %d, %d frames: features vs float64 max %.3g, vs the f32 encoder at batch %d %s; "
+          "status / volume / render of %d frames equal the single-frame calls (%.1f s)"
+          % (batch, n_frames, worst, batch, ["%.3g" % d for d in moved], n_frames, time.perf_counter() - t0))
+    assert all(d > 0 for d in moved), "f16x3 slot features equal the f32 encoder's"
+
+
+def test_bench_levels6_f16w_slot_frame_by_frame(nets):
+    """The bench's `levels6_f16w` leg (BASELINE configs[4]): bench.RESOLUTIONS + [513], f16w head, slots of
+    pick_batch(32, 16) = 16 frames; 20 frames (16 + a short 4).  Features against float64 (1e-4); every frame's
+    status, 513^3 volume and 513^2 render = the single-frame calls with the f16w head, bit for bit; frame 0's
+    volume against the f32 head's volume on the same features and camera: IoU >= 0.9999 (the bench's own
+    `iou_vs_f32_volume`, at the bar of test_config5_513_fp16_weights)."""
+    import bench
+    from monoport_amd import ops
+    _, _, ref = nets
+    res6 = bench.RESOLUTIONS + [513]
+    batch = bench.pick_batch(32, 16)
+    assert batch == 16
+    t0 = time.perf_counter()
+    snaps, facts = _run_bench_slots(batch, 20, 0, False, precision="f16w", resolutions=res6)
+    assert [len(s["frames"]) for s in snaps] == [16, 4]
+    assert facts["res"] == res6 and not facts["tables"] and facts["mlp"].precision == "f16w"
+    worst = _check_slot_frames(snaps, facts, ref, lambda n: {0, n // 2, n - 1})
+    mlp32 = ops.PackedMLP.from_layers(DEV, syn.body_mlp("G", noise=0.05, seed=1), syn.LAST_OP["G"])
+    vol32, st32 = ops.recon(mlp32, snaps[0]["feat"][0], _calib(0), syn.Z_SCALE, bench.B_MIN, bench.B_MAX, res6)
+    occ32, occ16 = vol32 > 0.5, snaps[0]["volume"][0] > 0.5
+    iou = (occ32 & occ16).sum().item() / max((occ32 | occ16).sum().item(), 1)
+    del snaps, vol32, occ32, occ16
+    torch.cuda.empty_cache()
+    print("bench levels6_f16w slot of 16, 20 frames at 17..513: features vs float64 max %.3g; status / volume / "
+          "render of 20 frames equal the single-frame calls; frame 0 IoU vs the f32 volume %.6f (%.1f s)"
+          % (worst, iou, time.perf_counter() - t0))
+    assert int(st32[0]) == 1 and iou >= 0.9999
+
+
+@pytest.mark.parametrize("rule", ["upstream", "interpolate"])
+def test_bench_final_level_slot_frame_by_frame(nets, oracle, rule):
+    """The bench's `final_level_rules` leg: bench.make_pipeline(..., final_level=rule) in slots of 20, 45 frames
+    after 20 warm-up frames (20 + 20 + 5: the short slot on a slot that held an earlier submission).  Features of
+    frames 0, n/2, n-1 against float64; every frame's status, volume and render = the single-frame
+    ops.recon(..., final_level=rule) calls, bit for bit; the last frame (of the short slot) = the CPU restatement
+    oracle.seg3d_lossless(final_level=rule) driven by the same HIP query on the slot's own features."""
+    _, _, ref = nets
+    t0 = time.perf_counter()
+    snaps, facts = _run_bench_slots(20, 45, 20, False, final_level=rule)
+    assert [len(s["frames"]) for s in snaps] == [20, 20, 5]
+    assert facts["final_level"] == rule
+    worst = _check_slot_frames(snaps, facts, ref, lambda n: {0, n // 2, n - 1})
+    last = torch.cat([s["status"][:, -1] for s in snaps])
+    if rule == "interpolate":
+        assert (last == 0).all()  # nothing is evaluated at 257^3
+    else:
+        assert (last > 0).all()
+    t1 = time.perf_counter()
+    snap = snaps[-1]
+    b, f = len(snap["frames"]) - 1, snap["frames"][-1]
+    want, stats = _oracle_decisions(oracle, facts, snap["feat"][b], _calib(f))
+    t2 = time.perf_counter()
+    assert snap["status"][b].tolist() == [1] + stats, "frame %d: points per level vs the CPU restatement" % f
+    assert np.array_equal(snap["volume"][b].cpu().numpy(), want), "frame %d: volume vs the CPU restatement" % f
+    print("bench slot of 20, final_level=%s, 45 frames: features vs float64 max %.3g; status / volume / render of "
+          "45 frames equal the single-frame calls; frame %d = oracle.seg3d_lossless (points per level %s, %.1f s); "
+          "%.1f s in all" % (rule, worst, f, stats, t2 - t1, time.perf_counter() - t0))
+
+
+def test_bench_in_flight_8_slots_frame_by_frame(nets):
+    """The bench's `in_flight_8` leg (BASELINE configs[3]): depth, batch = in_flight_layout(8, 1) = 2 slots of 4
+    frames alternating on two streams; 16 frames back to back at bench.RESOLUTIONS.  Every frame's features against
+    float64 (1e-4), and its status, volume and render = the single-frame calls, bit for bit."""
+    import bench
+    _, _, ref = nets
+    depth, batch = bench.in_flight_layout(8, 1)
+    assert (depth, batch) == (2, 4)
+    t0 = time.perf_counter()
+    snaps, facts = _run_bench_slots(batch, 16, 0, False, depth=depth)
+    assert [len(s["frames"]) for s in snaps] == [4, 4, 4, 4]
+    worst = _check_slot_frames(snaps, facts, ref, lambda n: set(range(n)))
+    print("bench in_flight_8 (2 slots of 4), 16 frames: features of every frame vs float64 max %.3g; status / "
+          "volume / render of 16 frames equal the single-frame calls (%.1f s)" % (worst, time.perf_counter() - t0))

@@ -776,3 +776,98 @@ def test_final_level_rules_through_seg3d_lossless_257(ops, oracle, body):
         Seg3dLossless(query_func=query_func, faster=False, final_level="upstream", **box)
     with pytest.raises(ValueError):
         Seg3dLossless(query_func=query_func, faster=True, final_level="nope", **box)
+
+
+def _distinct_frames(ops, oracle, n, empty=None):
+    """``n`` frames with their own feature maps (body_feat seed 2 + i) and cameras (scene_camera(25 i)); frame
+    ``empty`` gets a camera that looks past the box, so every node projects out of the image."""
+    feats, cals = [], []
+    for i in range(n):
+        feats.append(ops.pack_features(torch.from_numpy(syn.body_feat(256, 128, 128, 2 + i))[None].to(DEV)))
+        calib = oracle.pifu_calib(*syn.scene_camera(25 * i))
+        if i == empty:
+            calib[0, 0, 3] = 5.0
+        cals.append(torch.from_numpy(calib).to(DEV))
+    return feats, cals
+
+
+@pytest.mark.parametrize("rule", ["upstream", "interpolate"])
+@pytest.mark.parametrize("res", [[17, 33, 65, 129], [17, 33, 65, 129, 257]])
+def test_final_level_rules_batch_of_distinct_frames(ops, oracle, rule, res):
+    """mp_recon_batch_ex(final_level=rule) over 7 frames with different feature maps and cameras, one of them
+    empty: every frame's status row and volume = ops.recon(..., final_level=rule) on that frame alone, bit for bit
+    (the rule's kernels index every buffer by frame: a kernel reading frame 0's buffers passes on identical
+    frames), and frames 1 and 5 = the CPU restatement oracle.seg3d_lossless(final_level=rule) driven by the same
+    HIP query kernel on that frame's map and camera (volume and points per level)."""
+    import time
+    mlp = ops.PackedMLP.from_layers(DEV, syn.body_mlp("G", noise=0.05, seed=1), 1)
+    feats, cals = _distinct_frames(ops, oracle, 7, empty=4)
+    vols, status = ops.recon_batch(mlp, feats, cals, syn.Z_SCALE, BMIN, BMAX, res, final_level=rule)
+    st = status.cpu().numpy()
+    assert st[:, 1].tolist() == [17 ** 3] * 7
+    assert st[4, 0] == 0 and (st[[0, 1, 2, 3, 5, 6], 0] == 1).all()
+    for i in range(7):
+        v1, s1 = ops.recon(mlp, feats[i], cals[i], syn.Z_SCALE, BMIN, BMAX, res, final_level=rule)
+        assert np.array_equal(s1.cpu().numpy(), st[i]), i
+        if st[i, 0]:
+            assert torch.equal(v1, vols[i]), i
+    # the frames really differ: per-level counts, and every non-empty frame's volume against frame 0's
+    assert len({tuple(r) for r in st[[0, 1, 2, 3, 5, 6], 2:].tolist()}) > 1
+    assert all(not torch.equal(vols[i], vols[0]) for i in (1, 2, 3, 5, 6))
+    last = st[[0, 1, 2, 3, 5, 6], -1]
+    if rule == "interpolate":
+        assert (last == 0).all()  # nothing is evaluated at the last level
+    else:
+        assert (last > 0).all()
+    t0 = time.perf_counter()
+    for i in (1, 5):
+        def gpu_query(pts, i=i):
+            return ops.query(mlp, feats[i], torch.from_numpy(np.ascontiguousarray(pts))[None].to(DEV), cals[i],
+                             syn.Z_SCALE)[0, 0].cpu().numpy()
+
+        stats = []
+        ref = oracle.seg3d_lossless(gpu_query, BMIN, BMAX, res, stats=stats, final_level=rule)
+        assert list(st[i]) == [1] + stats, i
+        assert np.array_equal(vols[i].cpu().numpy(), ref), i
+    print("final_level=%s, %d^3, 7 distinct frames: batch == single frames; frames 1 and 5 == oracle driver "
+          "(%.1f s)" % (rule, res[-1], time.perf_counter() - t0))
+
+
+@pytest.mark.parametrize("precision,res", [(p, [17, 33, 65, 129, 257]) for p in ("f16x3", "f16w", "f16")]
+                         + [(p, [17, 33, 65, 129, 257, 513]) for p in ("f16w", "f16")])
+def test_recon_batch_of_16_at_large_grids_equals_single_frames(ops, oracle, precision, res):
+    """mp_recon_batch with the f16 heads at 257^3 and 513^3 (BASELINE configs[4] runs 16 frames of 17..513 per
+    fused launch): 16 frames cycling through 5 distinct maps and cameras (frames 8 and 15 hold other inputs than
+    frames 0 and 7), every frame = ops.recon on that frame alone, bit for bit.  At 513^3 every distinct frame's
+    volume against the f32 head's on the same inputs: IoU >= 0.9999 (f16w) / 0.999 (f16), the bars of
+    test_config5_513_fp16_weights."""
+    import time
+    t0 = time.perf_counter()
+    layers = syn.body_mlp("G", noise=0.05, seed=1)
+    mlp = ops.PackedMLP.from_layers(DEV, layers, 1)
+    mlp.set_precision(precision)
+    feats, cals = _distinct_frames(ops, oracle, 5)
+    k = [f % 5 for f in range(16)]
+    vols, status = ops.recon_batch(mlp, [feats[i] for i in k], [cals[i] for i in k], syn.Z_SCALE, BMIN, BMAX, res)
+    st = status.cpu().numpy()
+    assert (st[:, 0] == 1).all() and len({tuple(r) for r in st[:5, 2:].tolist()}) > 1
+    assert all(not torch.equal(vols[i], vols[0]) for i in range(1, 5))  # the frames really differ
+    ious = []
+    for i in range(5):
+        v1, s1 = ops.recon(mlp, feats[i], cals[i], syn.Z_SCALE, BMIN, BMAX, res)
+        s1 = s1.cpu().numpy()
+        for f in range(i, 16, 5):
+            assert np.array_equal(s1, st[f]), f
+            assert torch.equal(v1, vols[f]), f
+        if res[-1] == 513:
+            mlp32 = ops.PackedMLP.from_layers(DEV, layers, 1)
+            v32, _ = ops.recon(mlp32, feats[i], cals[i], syn.Z_SCALE, BMIN, BMAX, res)
+            occ32, occ16 = v32 > 0.5, v1 > 0.5
+            ious.append((occ32 & occ16).sum().item() / (occ32 | occ16).sum().item())
+            del v32, occ32, occ16, mlp32
+        del v1
+    del vols
+    torch.cuda.empty_cache()
+    print("recon_batch %s, 16 frames at %d^3 == single frames; IoU vs f32 %s (%.1f s)"
+          % (precision, res[-1], ["%.6f" % v for v in ious], time.perf_counter() - t0))
+    assert all(v >= (0.9999 if precision == "f16w" else 0.999) for v in ious)
