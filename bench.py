@@ -9,13 +9,23 @@ render.  Inputs are resident in HBM before the timed region.  With --gpus N ever
 reconstructs its own frames (frame-parallel, weak scaling) and the renders are gathered to rank 0
 over RCCL.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full]
 
 ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment launches its own N ranks (one per
 GPU, ``python -m torch.distributed.run --standalone``-style on 127.0.0.1) and fails loudly when
 fewer than N GPUs are visible; under ``python -m torch.distributed.run --nproc-per-node N ...
 bench.py --gpus N ...`` it joins the ranks the launcher made.  Either way rank 0 prints ONE JSON
-line with the driver's contract fields plus
+line.
+
+A plain run does only what the headline needs: it sets up, warms up, times the passes, writes
+--dump-outputs if given, and prints the contract fields (`metric`, `value`, `unit`, `ms_per_step`,
+`higher_is_better`, `dtype`, ...) with the configuration of that one measurement and
+
+  "passes"        the timed region is run 5 times (each EXACTLY --steps frames between barrier +
+                  synchronize pairs); `value` is the median pass, min / max are listed
+
+``--full`` adds every other leg, each with runs of its own (the --no-* options switch legs off
+again: ``--full --no-extras`` keeps "roofline", "breakdown" and, at N > 1, "scaling_vs_single_rank"):
 
   "roofline"      the fused query kernel against the f32 MFMA peak (HIP-event timed, live): `frac` prices the
                   FLOPs it EXECUTES (`frac_definition`); `like_for_like_frac` = the plain kernel of this run, where
@@ -27,16 +37,16 @@ line with the driver's contract fields plus
                   passes at this frames-per-launch (20 with --steps 20, 32 with the default 32);
                   `roofline.sustained` = what a register-only loop of the same MFMA instruction delivers on this
                   box right after the timed launches, with the shader clock it ran at (`peak` stays nominal)
+  "breakdown"     encoder-only and encoder-excluded time per frame on one stream
   "plain_query_path"  (N=1 only) the headline configuration without skip tables (--no-skip-table)
   "cpu_baseline"  the CPU oracle path timed on this box's host cores (rank 0, N=1 only); "cpu_baseline_reference_ops" =
                   the same reconstruction with the query through the reference's own torch CPU operators, op for op
                   (oracle/torch_ops.py: what the reference's CPU recon path costs on THIS box)
-  "passes"        the timed region is run 5 times (each EXACTLY --steps frames between barrier +
-                  synchronize pairs); `value` is the median pass, min / max are listed
   "scaling_vs_single_rank"  (N > 1) rank 0 alone on the same frames while the others wait: efficiency inside ONE run
   "in_flight_8"   BASELINE configs[3]: 8 frames in flight across the node (8/N per rank)
-  "with_color" / "levels6_f16w" / "mesh" / "dropin" / "alt_precision"   (N=1 only) the other
-                  BASELINE configs and surfaces, each with its own timing and parity deltas
+  "with_color" / "levels6_f16w" / "mesh" / "dropin" / "alt_precision" / "final_level_rules" /
+  "two_slot_submissions"   (N=1 only) the other BASELINE configs, surfaces and layouts, each with its
+                  own timing and parity deltas
 
 ``--dump-outputs DIR`` writes what the timed path returned for its last step (the last frame of the last pass) as
 float32 / float64 ``DIR/<name>.npy`` files (dump_last_step); the inputs are seeded, so two builds run with the same
@@ -350,7 +360,7 @@ def timed_passes(job, pipe, batch, with_color, passes, collective=True, want_sta
 
 DUMP_VOLUME_SAMPLE = 1 << 22  # voxels of the volume --dump-outputs writes (16 MB; a 257^3 volume is 68 MB)
 DUMP_MAX_BYTES = 64 << 20
-DROPIN_MIN_FRAMES = 96  # the default run's drop-in leg: long against the stage pipeline's fill and drain
+DROPIN_MIN_FRAMES = 96  # the drop-in leg of --full: long against the stage pipeline's fill and drain
 
 
 def dump_last_step(job, pipe, with_color, out_dir):
@@ -719,7 +729,7 @@ def parse_args(argv):
     ap.add_argument("--in-flight", type=int, default=0,
                     help="K > 0: exactly K frames in flight across the node (K / --gpus per rank; "
                          "BASELINE configs[3] is K = 8) instead of --depth x --batch per GPU; the "
-                         "default run reports this configuration as `in_flight_8` next to `value`")
+                         "--full run reports this configuration as `in_flight_8` next to `value`")
     ap.add_argument("--passes", type=int, default=5,
                     help="timed regions of exactly --steps frames each; `value` is the median (5: with three slots "
                          "overlapping, single passes of the default run differ by +- 4 %%; the driver's one-submission "
@@ -737,7 +747,7 @@ def parse_args(argv):
     ap.add_argument("--mode", default="pipeline", choices=["pipeline", "dropin"],
                     help="pipeline (default): the headline -- FramePipeline, frames batched per slot, no "
                          "host sync; dropin: `value` is measured through the reference's call surface "
-                         "(StagePipeline + Seg3dLossless + forward_vertices), as the default run's "
+                         "(StagePipeline + Seg3dLossless + forward_vertices), as the --full run's "
                          "`dropin` object")
     ap.add_argument("--soak", type=float, default=10.0,
                     help="seconds of the per-frame drop-in pipeline's soak leg (dropin.soak: latency distribution and "
@@ -746,18 +756,23 @@ def parse_args(argv):
                     help="selection rule of the LAST octree level (Seg3dLossless(final_level=...)): dilate3 = the "
                          "lossless schedule (default, the headline); upstream = nodes whose upsampled mask is exactly "
                          "0.5, undilated (the rule recalled from the un-vendored implicit_seg package); interpolate = "
-                         "no evaluation at the last level.  The default run reports the other two as "
+                         "no evaluation at the last level.  A --full run reports the other two as "
                          "`final_level_rules`")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg: roofline (+ the sustained MFMA probe), breakdown, "
+                         "scaling_vs_single_rank (N > 1), plain_query_path, final_level_rules, two_slot_submissions, "
+                         "in_flight_8, alt_precision, mesh, with_color, levels6_f16w, dropin, cpu_baseline.  Without "
+                         "it a run does only the headline measurement (and --dump-outputs)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the headline measurement + roofline (skips every leg below)")
+                    help="with --full: only the headline measurement + roofline + breakdown (skips every leg below)")
     ap.add_argument("--no-dropin", action="store_true",
-                    help="skip the drop-in-surface pass a default N=1 run appends")
+                    help="skip the drop-in-surface pass a --full N=1 run appends")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-skip-table", action="store_true",
                     help="plain query path: layer 0 on the MFMAs for every point instead of the per-frame "
                          "layer-0 tables (mp_skip_table)")
     ap.add_argument("--no-alt", action="store_true",
-                    help="skip the informational f16x3 pass that a default N=1 run appends")
+                    help="skip the informational f16x3 pass that a --full N=1 run appends")
     ap.add_argument("--no-configs", action="store_true",
                     help="skip the with_color / levels6_f16w / in_flight_8 / mesh legs")
     ap.add_argument("--rendezvous-only", action="store_true",
@@ -785,7 +800,10 @@ def main(argv=None):
         raise SystemExit("--gpus %d but WORLD_SIZE=%s" % (args.gpus, os.environ.get("WORLD_SIZE")))
     if args.rendezvous_only:
         return rendezvous_only(args)
-    if args.no_extras:
+    launch_log = os.environ.get("MONOPORT_BENCH_LAUNCH_LOG")
+    if launch_log and args.mode == "pipeline" and not args.full:
+        raise SystemExit("MONOPORT_BENCH_LAUNCH_LOG logs the roofline leg: run with --full")
+    if args.no_extras or not args.full:
         args.no_dropin = args.no_cpu_baseline = args.no_alt = args.no_configs = True
     if args.no_skip_table:
         ops.SKIP_TABLE = False
@@ -850,16 +868,16 @@ def main(argv=None):
     else:
         depth, batch = args.depth, pick_batch(args.steps, args.batch, args.depth)
     main_res, pipe = measure_config(job, depth, batch, not args.no_graph, resolutions,
-                                    args.with_color, args.precision, args.passes, final_level=args.final_level,
-                                    dump_dir=args.dump_outputs)
+                                    args.with_color, args.precision, args.passes, roofline=args.full,
+                                    final_level=args.final_level, dump_dir=args.dump_outputs)
     use_graph = main_res["use_graph"]
-    roof = main_res["roof"]
+    roof = main_res.get("roof")
     # what the f32 matrix pipe of THIS box holds right now, and at which clock (mp_mfma_clock_probe, a 30-50 ms
     # register-only MFMA loop straight after the roofline leg): boxes of one pool differ by a few per cent
     # On N > 1 EVERY rank probes its own GPU at the same time (all eight under matrix load, as in the timed region)
     # and rank 0 prints all of them: a slow or down-clocked GPU is visible in the one line.
     sustained = sustained_per_rank = None
-    if args.precision == "f32":
+    if args.full and args.precision == "f32":
         torch.cuda.synchronize()
         if dist is not None:
             job.barrier()
@@ -874,7 +892,7 @@ def main(argv=None):
 
     # single-rank leg of an N > 1 run: rank 0 repeats the passes alone (no gather, no barriers)
     # while the other ranks wait -> scaling efficiency against a line measured in THIS run
-    if dist is not None:
+    if args.full and dist is not None:
         job.barrier()
         if rank == 0:
             el, _, _ = timed_passes(job, pipe, batch, args.with_color, args.passes, collective=False,
@@ -992,7 +1010,7 @@ def main(argv=None):
                "note": "opt-in (--precision f16x3); not the headline"}
 
     breakdown = None
-    if rank == 0 or world == 1:
+    if args.full and (rank == 0 or world == 1):
         breakdown = breakdown_leg(job, pipe, batch, resolutions)
         breakdown["points_per_level"] = [float(v) / args.steps for v in roof["points_per_level"]]
 
@@ -1109,7 +1127,7 @@ def main(argv=None):
             "ms_per_step_per_rank": main_res["ms_per_step_per_rank"],
             "mpts_per_s": main_res["points"] / main_res["elapsed"] / 1e6,
             "breakdown": breakdown,
-            "roofline": {
+            "roofline": None if roof is None else {
                 "kernel": ("pifu_query_tabws_kernel<1> (fused MLP on 32-point tiles, wave-specialised: 4 MFMA-only consumer "
                            "waves + 4 producer waves that blend the products with the sampled feature from the frame's "
                            "skip table, skip_table_kernel)" if skip_on else
@@ -1165,6 +1183,8 @@ def main(argv=None):
                             "100 MHz s_memrealtime tick averaged over the workgroups"},
             },
         }
+        if roof is None:  # a plain run: no roofline leg, no breakdown
+            del out["roofline"], out["breakdown"]
         if main_res["dumped_outputs"] is not None:
             out["dumped_outputs"] = main_res["dumped_outputs"]
         out.update(extras)
@@ -1181,7 +1201,6 @@ def main(argv=None):
             out["cpu_baseline"] = cpu_baseline(min(os.cpu_count() or 1, 32))
             out["cpu_baseline_reference_ops"] = out["cpu_baseline"].pop("reference_ops")
             out["cpu_baseline_reference"] = CPU_BASELINE_REFERENCE
-        launch_log = os.environ.get("MONOPORT_BENCH_LAUNCH_LOG")
         if launch_log:  # tools/profile_summary.py: per-launch (ms, points) of the roofline leg
             with open(launch_log, "w") as f:
                 json.dump({"launch_ms": [float(v) for v in roof["launch_ms"]],

@@ -88,6 +88,18 @@ def test_arguments_without_a_timed_path_are_refused():
     assert not os.path.exists(os.path.join(ROOT, "unused_dump_dir"))
 
 
+def test_plain_run_is_the_default_and_the_launch_log_needs_full(tmp_path):
+    """The other legs run only with --full; MONOPORT_BENCH_LAUNCH_LOG, which logs the roofline leg, is refused without it
+    before anything is measured or written."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args([]).full is False and bench.parse_args(["--full"]).full is True
+    log = tmp_path / "launch_log.json"
+    res = _run([sys.executable, BENCH, "--gpus", "1", "--steps", "2", "--warmup", "1"], MONOPORT_BENCH_LAUNCH_LOG=str(log))
+    assert res.returncode != 0 and "run with --full" in res.stderr and not _json_lines(res.stdout)
+    assert not log.exists()
+
+
 def test_in_flight_layout():
     sys.path.insert(0, ROOT)
     import bench

@@ -495,7 +495,7 @@ def test_bench_two_ranks_on_one_gpu():
     env = dict(os.environ, MONOPORT_BENCH_ONE_GPU_TEST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4",
-           "--warmup", "2", "--depth", "1", "--batch", "2", "--passes", "2"]
+           "--warmup", "2", "--depth", "1", "--batch", "2", "--passes", "2", "--full"]
     res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -526,7 +526,7 @@ def test_bench_collectives_on_rccl_one_rank_group():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-           "--passes", "2", "--no-extras"]
+           "--passes", "2", "--full", "--no-extras"]
     res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -542,7 +542,8 @@ def test_bench_collectives_on_rccl_one_rank_group():
 def test_bench_dump_outputs_of_the_last_step(tmp_path):
     """bench.py --dump-outputs DIR: the last timed step's render, status row, vertices and volume sample as float32 /
     float64 .npy files within 64 MB -- and, the inputs being seeded, the same files from a second run of the same
-    command (what lets two builds be compared output for output)."""
+    command (what lets two builds be compared output for output).  The runs are plain ones (no --full): the headline
+    alone, none of the other legs."""
     import json
     import os
     import subprocess
@@ -555,13 +556,17 @@ def test_bench_dump_outputs_of_the_last_step(tmp_path):
     for run in ("a", "b"):
         d = tmp_path / run
         cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
-               "--passes", "1", "--no-extras", "--dump-outputs", str(d)]
+               "--passes", "1", "--dump-outputs", str(d)]
         res = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
         assert res.returncode == 0, res.stderr[-3000:]
         lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
         assert len(lines) == 1
         out = json.loads(lines[0])
         assert out["steps"] == 4 and out["dumped_outputs"]["frame"] == 4 + 2 - 1
+        assert out["value"] > 0 and out["ms_per_step"] > 0 and out["passes"]["n"] == 1
+        assert not {"roofline", "breakdown", "plain_query_path", "final_level_rules", "two_slot_submissions",
+                    "in_flight_8", "alt_precision", "mesh", "with_color", "levels6_f16w", "dropin",
+                    "cpu_baseline"} & set(out)
         files = sorted(os.listdir(d))
         assert files == out["dumped_outputs"]["files"]
         arrays = {f[:-4]: np.load(d / f) for f in files}

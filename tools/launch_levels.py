@@ -1,7 +1,7 @@
 """Per octree level: points, time and fraction of the f32 MFMA roof of the fused-query launches of bench.py's
 roofline leg, from the log bench.py writes when MONOPORT_BENCH_LAUNCH_LOG is set.
 
-    MONOPORT_BENCH_LAUNCH_LOG=log.json python bench.py --no-extras --no-cpu-baseline; python tools/launch_levels.py log.json
+    MONOPORT_BENCH_LAUNCH_LOG=log.json python bench.py --full --no-extras --no-cpu-baseline; python tools/launch_levels.py log.json
 """
 import json
 import sys

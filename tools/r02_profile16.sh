@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 out=$R/gpurun_out/${1:-r02k}; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python $R/bench.py --steps 20 --warmup 5 --precision f16x3 --no-dropin --no-cpu-baseline > $out/bench_prof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python $R/bench.py --full --steps 20 --warmup 5 --precision f16x3 --no-dropin --no-cpu-baseline > $out/bench_prof.log 2>&1
 cd $R
 f=$(find $out/trace -name "*kernel_stats.csv" | head -1)
 head -45 $f > $out/r02_bench_f16x3_kernel_stats.csv

@@ -6,7 +6,7 @@ cd $R
 timeout 1500 python -m pytest tests -q -m gpu -x > $out/tests.log 2>&1
 echo "pytest rc=$?" >> $out/tests.log
 grep -E "passed|failed|^FAILED|^ERROR|rc=" $out/tests.log | tail -8
-timeout 900 python bench.py > $out/bench.json 2> $out/bench.err
+timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err
 tail -c 600 $out/bench.err
 python - $out/bench.json <<'PY'
 import json,sys

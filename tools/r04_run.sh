@@ -35,7 +35,7 @@ ws)
   timeout 300 python tools/tab_ws_probe.py > $out/probe.txt 2>&1; echo "probe rc=$?"; tail -6 $out/probe.txt
   run_tests
   for v in ws v1; do
-    MONOPORT_TAB_KERNEL=$v timeout 600 python bench.py --no-extras --no-cpu-baseline > $out/bench_$v.json 2> $out/bench_$v.err
+    MONOPORT_TAB_KERNEL=$v timeout 600 python bench.py --full --no-extras --no-cpu-baseline > $out/bench_$v.json 2> $out/bench_$v.err
     bench_line $out/bench_$v.json $v
   done
   ;;
@@ -89,8 +89,8 @@ PY
   ;;
 prof)  # kernel trace + stats of the default bench with the per-launch point counts of the roofline leg
   cd /tmp && export TMPDIR=/tmp
-  CMD="python bench.py --warmup 5 --no-alt --no-dropin --no-cpu-baseline"
-  MONOPORT_BENCH_LAUNCH_LOG=$out/launch_log.json rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python $R/bench.py --warmup 5 --no-alt --no-dropin --no-cpu-baseline > $out/bench_prof.log 2>&1
+  CMD="python bench.py --full --warmup 5 --no-alt --no-dropin --no-cpu-baseline"
+  MONOPORT_BENCH_LAUNCH_LOG=$out/launch_log.json rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python $R/bench.py --full --warmup 5 --no-alt --no-dropin --no-cpu-baseline > $out/bench_prof.log 2>&1
   cd $R
   python tools/profile_summary.py $out/trace $out/r04_bench "$CMD" 10 $out/launch_log.json > $out/summary.log 2>&1
   tail -1 $out/bench_prof.log | cut -c1-300; cat $out/summary.log | tail -30
@@ -98,7 +98,7 @@ prof)  # kernel trace + stats of the default bench with the per-launch point cou
   ;;
 profhl)  # kernel stats of the headline configuration alone (no extras): where a frame's GPU time goes
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python $R/bench.py --no-extras --no-cpu-baseline > $out/bench.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python $R/bench.py --full --no-extras --no-cpu-baseline > $out/bench.log 2>&1
   cd $R
   tail -1 $out/bench.log | cut -c1-200
   f=$(find $out/trace -name "*kernel_stats.csv" | head -1)
@@ -170,7 +170,7 @@ tab16)  # the f16 query kernels through the skip table: hang check, probe, their
   ;;
 shapes)  # headline by slot layout / encoder launch mode
   for flags in "" "--no-graph" "--depth 4 --batch 8 --steps 64" "--depth 6 --batch 8 --steps 96" "--depth 2 --batch 16 --steps 64" "--depth 4 --batch 8 --steps 64 --no-graph" "--depth 6 --batch 4 --steps 96"; do
-    timeout 600 python bench.py --no-extras --no-cpu-baseline $flags > $out/b.json 2> $out/b.err
+    timeout 600 python bench.py --full --no-extras --no-cpu-baseline $flags > $out/b.json 2> $out/b.err
     bench_line $out/b.json "$flags"
   done
   ;;
@@ -180,27 +180,27 @@ conv)  # the encoder's convolutions per shape (batch 1 and 16) + the encoder tes
   ;;
 shapes20)  # the driver's --steps 20 by slot layout
   for flags in "" "--batch 5" "--batch 4" "--batch 20" "--batch 10 --depth 2" "--batch 5 --depth 4" "--batch 2"; do
-    timeout 600 python bench.py --steps 20 --warmup 5 --no-extras --no-cpu-baseline $flags > $out/b.json 2> $out/b.err
+    timeout 600 python bench.py --full --steps 20 --warmup 5 --no-extras --no-cpu-baseline $flags > $out/b.json 2> $out/b.err
     bench_line $out/b.json "$flags"
   done
   ;;
 color)  # configs[2] + the convk tests
   timeout 600 python -m pytest tests/test_conv_gpu.py tests/test_encoder_dataflow_gpu.py tests/test_dropin_gpu.py -q -m gpu -k "convk or netc or encoder or stem" 2>&1 | tail -3
-  timeout 600 python bench.py --with-color --no-extras --no-cpu-baseline > $out/color.json 2> $out/color.err; tail -c 200 $out/color.err
+  timeout 600 python bench.py --full --with-color --no-extras --no-cpu-baseline > $out/color.json 2> $out/color.err; tail -c 200 $out/color.err
   bench_line $out/color.json with-color
   timeout 300 python tools/netc_encoder_probe.py 2>&1 | tail -6
   ;;
 levels)  # the headline bench + the per-level fractions of its roofline leg
-  MONOPORT_BENCH_LAUNCH_LOG=$out/launch_log.json timeout 600 python bench.py --no-extras --no-cpu-baseline > $out/bench.json 2> $out/bench.err
+  MONOPORT_BENCH_LAUNCH_LOG=$out/launch_log.json timeout 600 python bench.py --full --no-extras --no-cpu-baseline > $out/bench.json 2> $out/bench.err
   bench_line $out/bench.json headline
   python tools/launch_levels.py $out/launch_log.json | tee $out/levels.txt
   ;;
 tests) run_tests ;;
 bench)
-  timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; tail -c 400 $out/bench.err
+  timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; tail -c 400 $out/bench.err
   bench_line $out/bench.json default ;;
 bench20)  # the driver's invocation
-  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench20.json 2> $out/bench20.err; tail -c 300 $out/bench20.err
+  timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench20.json 2> $out/bench20.err; tail -c 300 $out/bench20.err
   bench_line $out/bench20.json steps20
   python - $out/bench20.json <<'PY'
 import json,sys
@@ -213,7 +213,7 @@ for k in ("plain_query_path","in_flight_8","alt_precision","with_color","levels6
 PY
   ;;
 benchq)  # headline only, no extras
-  timeout 600 python bench.py --no-extras --no-cpu-baseline > $out/bench.json 2> $out/bench.err; tail -c 400 $out/bench.err
+  timeout 600 python bench.py --full --no-extras --no-cpu-baseline > $out/bench.json 2> $out/bench.err; tail -c 400 $out/bench.err
   bench_line $out/bench.json quick
   python - $out/bench.json <<'PY'
 import json,sys

@@ -2,7 +2,7 @@ cd $GRAFT_REPO_ROOT
 out=gpurun_out/r06h; mkdir -p $out
 run() { # label, env, flags
   label=$1; shift; envs=$1; shift
-  env $envs timeout 600 python bench.py --no-extras --no-cpu-baseline "$@" > $out/b_$label.json 2> $out/b_$label.err
+  env $envs timeout 600 python bench.py --full --no-extras --no-cpu-baseline "$@" > $out/b_$label.json 2> $out/b_$label.err
   python - $out/b_$label.json "$label $envs $*" <<'PY'
 import json,sys
 try:

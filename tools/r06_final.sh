@@ -1,6 +1,6 @@
 cd $GRAFT_REPO_ROOT; out=gpurun_out/${1:-r06y}; mkdir -p $out
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-timeout 900 python bench.py > $out/bench_default.json 2> $out/bench_default.err; tail -c 300 $out/bench_default.err
+timeout 900 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; tail -c 300 $out/bench_default.err
 python - $out/bench_default.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -1,6 +1,6 @@
 cd $GRAFT_REPO_ROOT; out=gpurun_out/${1:-r06w}; mkdir -p $out
 timeout 1700 python -m pytest tests -m gpu -x -q > $out/tests.log 2>&1; echo "pytest rc=$?" >> $out/tests.log; tail -3 $out/tests.log
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench20.json 2> $out/bench20.err; tail -c 400 $out/bench20.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench20.json 2> $out/bench20.err; tail -c 400 $out/bench20.err
 python - $out/bench20.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -8,7 +8,7 @@ run mult8 MONOPORT_QUERY_GRID_MULT=8
 run mult16 MONOPORT_QUERY_GRID_MULT=16
 done
 for m in 1 4; do
-MONOPORT_QUERY_GRID_MULT=$m timeout 300 python bench.py --steps 20 --warmup 5 --no-extras 2>/dev/null | python -c "
+MONOPORT_QUERY_GRID_MULT=$m timeout 300 python bench.py --full --steps 20 --warmup 5 --no-extras 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('[headline mult $m] value %.1f frac %.4f passes %s' % (d['value'], d['roofline']['frac'], d['passes']['ms_per_step_all']))" | tee -a $out/overlap.txt
 done

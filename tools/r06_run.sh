@@ -47,7 +47,7 @@ run_tests() {
 }
 levels() {  # $1 = label, rest = bench flags
   label=$1; shift
-  MONOPORT_BENCH_LAUNCH_LOG=$out/launch_log_$label.json timeout 600 python bench.py --no-extras --no-cpu-baseline "$@" > $out/bench_$label.json 2> $out/bench_$label.err
+  MONOPORT_BENCH_LAUNCH_LOG=$out/launch_log_$label.json timeout 600 python bench.py --full --no-extras --no-cpu-baseline "$@" > $out/bench_$label.json 2> $out/bench_$label.err
   tail -c 300 $out/bench_$label.err
   bench_line $out/bench_$label.json $label
   python tools/launch_levels.py $out/launch_log_$label.json | tee $out/levels_$label.txt
@@ -56,20 +56,20 @@ case $step in
 first)
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
   run_tests
-  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench20.json 2> $out/bench20.err; tail -c 300 $out/bench20.err
+  timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench20.json 2> $out/bench20.err; tail -c 300 $out/bench20.err
   bench_line $out/bench20.json steps20
   levels s20 --steps 20 --warmup 5
   levels s32
   ;;
 tests|tests_k) run_tests ;;
 bench)
-  timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; tail -c 400 $out/bench.err
+  timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; tail -c 400 $out/bench.err
   bench_line $out/bench.json default ;;
 bench20)
-  timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench20.json 2> $out/bench20.err; tail -c 300 $out/bench20.err
+  timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench20.json 2> $out/bench20.err; tail -c 300 $out/bench20.err
   bench_line $out/bench20.json steps20 ;;
 benchq)
-  timeout 600 python bench.py --no-extras --no-cpu-baseline $FLAGS > $out/bench.json 2> $out/bench.err; tail -c 400 $out/bench.err
+  timeout 600 python bench.py --full --no-extras --no-cpu-baseline $FLAGS > $out/bench.json 2> $out/bench.err; tail -c 400 $out/bench.err
   bench_line $out/bench.json "quick $FLAGS" ;;
 levels) levels s32 ;;
 levels20) levels s20 --steps 20 --warmup 5 ;;
@@ -84,8 +84,8 @@ pmc)  # counters of the shipped table query kernel on one 885 k-point lattice la
   cd $R ;;
 prof20)  # kernel trace + stats of the driver's invocation with the per-launch point counts of the roofline leg
   cd /tmp && export TMPDIR=/tmp
-  CMD="python bench.py --gpus 1 --steps 20 --warmup 5"
-  MONOPORT_BENCH_LAUNCH_LOG=$out/launch_log.json rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-dropin --no-cpu-baseline > $out/bench_prof.log 2>&1
+  CMD="python bench.py --full --gpus 1 --steps 20 --warmup 5"
+  MONOPORT_BENCH_LAUNCH_LOG=$out/launch_log.json rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python $R/bench.py --full --gpus 1 --steps 20 --warmup 5 --no-dropin --no-cpu-baseline > $out/bench_prof.log 2>&1
   cd $R
   python tools/profile_summary.py $out/trace $out/r06_bench "$CMD --no-dropin --no-cpu-baseline" 20 $out/launch_log.json > $out/summary.log 2>&1
   tail -1 $out/bench_prof.log | cut -c1-300; tail -30 $out/summary.log
@@ -139,11 +139,11 @@ PY
   ;;
 shapes)
   for flags in "--steps 20 --warmup 5" "--steps 20 --warmup 5 --batch 10" "--steps 20 --warmup 5 --batch 10 --depth 2" "" "--batch 16" "--steps 96" "--steps 64 --batch 32 --depth 2"; do
-    timeout 600 python bench.py --no-extras --no-cpu-baseline $flags > $out/b.json 2> $out/b.err
+    timeout 600 python bench.py --full --no-extras --no-cpu-baseline $flags > $out/b.json 2> $out/b.err
     bench_line $out/b.json "$flags"
   done
   ;;
 f16w)
-  timeout 600 python bench.py --levels 6 --precision f16w --no-extras --no-cpu-baseline $FLAGS > $out/f16w.json 2> $out/f16w.err; tail -c 300 $out/f16w.err
+  timeout 600 python bench.py --full --levels 6 --precision f16w --no-extras --no-cpu-baseline $FLAGS > $out/f16w.json 2> $out/f16w.err; tail -c 300 $out/f16w.err
   bench_line $out/f16w.json "513 f16w $FLAGS" ;;
 esac
