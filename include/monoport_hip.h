@@ -447,14 +447,20 @@ int mp_concat3_add(mp_ctx *ctx, const float *a, int ca, const float *b, int cb, 
  * partial sums the NEXT GroupNorm(32, Cout) needs.  x [N,Cin,H,W], y [N,Cout,H,W] contiguous NCHW;
  * ss [N,Cin,2] = (scale, shift) from mp_gn_finalize; packed = W re-ordered by mp_conv3x3_pack
  * (Cout*Cin*9 floats).  stats: NULL or double [N,32,S,2] (per image, group and tile) with S = mp_conv3x3_stat_slices(Cout,N,H,W,f16) (f16 = 0 here, 1 for mp_conv3x3_gn16).
- * Needs Cin % 16 == 0, Cout % 32 == 0, H and W powers of two (W >= 32); else MP_ERR_UNSUPPORTED.
+ * Needs Cin % 16 == 0 (16 .. 512), Cout % 32 == 0, H and W powers of two (H >= 8, W >= 32); else
+ * MP_ERR_UNSUPPORTED.  The statistics of y (stats here, fin of mp_conv3x3_ex and mp_convk) are served where
+ * mp_conv_stats_supported(Cout): Cout / 32 divides 32 (Cout = 32, 64, 128, 256, 512, 1024) -- the epilogues fold
+ * whole groups out of a workgroup's 32- / 64- / 128-channel block; any other Cout gets y (and y2 / fin2) but
+ * MP_ERR_UNSUPPORTED when its own statistics are requested.
  * mp_conv3x3_tune(nr): measurement hook -- force nr (1, 2, 4) 32-pixel column blocks per wave
  * instead of the launch-size heuristic (0 restores it); | 0x100 forces the large-tile kernel, | 0x200
- * the split-K kernel, | mrw << 12 the row blocks per wave of mp_conv1x1; process-wide, not for
- * production use. */
+ * the split-K kernel, | 0x400 the direct kernels by the heuristic, | 0x800 / | 0x1000 the 64- / 128-channel Winograd
+ * kernel, | mrw << 12 the row blocks per wave of mp_conv1x1 (mrw = 1, the same bit as 0x1000, is that kernel's own
+ * choice); process-wide, not for production use. */
 int mp_conv3x3_pack(mp_ctx *ctx, const float *w /*[Cout,Cin,3,3]*/, int cout, int cin, float *packed,
                     mp_stream stream);
 int mp_conv3x3_supported(int cin, int cout, int h, int w); /* 1 if the shape is built, else 0 */
+int mp_conv_stats_supported(int cout); /* 1 if a 3x3 / ks x ks launch can emit GroupNorm(32, Cout) statistics of y */
 int mp_conv3x3_stat_slices(int cout, int n, int h, int w, int f16);
 void mp_conv3x3_tune(int nr);
 /* mp_query_tune(small_tiles): measurement hook for the fused f32 query of the netG heads on
@@ -610,7 +616,9 @@ int mp_conv1x1_stat_slices(int64_t hw);
  * ks = 3, stride 2, zero padding 1, Cin % 16 == 0, Cout % 128 == 0 (netC's two down-sampling
  * convolutions, ResBlkFilters.py:115-121).  y [N, Cout, H/stride, W/stride], W/stride % 64 == 0.
  * gn / relu: GroupNorm (+ReLU) of the INPUT applied while gathering, as in mp_conv3x3_ex; bias may be
- * NULL; fin: GroupNorm(32, Cout) over y.  packed: mp_convk_packed_floats floats from mp_convk_pack. */
+ * NULL; fin: GroupNorm(32, Cout) over y (where mp_conv_stats_supported(Cout): 128, 256, 512 ...; Cout = 384 gets y
+ * only).  reflect needs H and W larger than the padding, as nn.ReflectionPad2d does.  packed:
+ * mp_convk_packed_floats floats from mp_convk_pack. */
 typedef struct mp_convk_args {
   const float *x;
   int n, cin, h, w;

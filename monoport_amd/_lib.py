@@ -170,6 +170,7 @@ SIGNATURES = {
                               c_vp, c_vp]),
     "mp_scale_shift_add": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_i64, c_vp, c_vp]),
     "mp_conv3x3_supported": (c_int, [c_int, c_int, c_int, c_int]),
+    "mp_conv_stats_supported": (c_int, [c_int]),
     "mp_conv3x3_pack16": (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
     "mp_conv3x3_gn16": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_int,
                                 c_vp, c_vp, c_vp]),

@@ -1137,6 +1137,7 @@ int mp_scale_shift_add(mp_ctx *ctx, const float *t, const float *ss, const float
 }
 
 int mp_conv3x3_supported(int cin, int cout, int h, int w) { return conv3x3_supported(cin, cout, h, w) ? 1 : 0; }
+int mp_conv_stats_supported(int cout) { return conv_stats_supported(cout) ? 1 : 0; }
 
 int mp_gn_stat_slices(void) { return gn_stat_slices(); }
 
@@ -1148,7 +1149,9 @@ int mp_conv3x3_stat_slices(int cout, int n, int h, int w, int f16) {
 void mp_query_tune(int small_tiles) { mp::query_small_set_gate(small_tiles); }
 
 void mp_conv3x3_tune(int nr) {
-  conv3x3_set_nr(nr & 0xfff);
+  // bit 12 is both | 0x1000 (the 128-channel Winograd kernel) and mrw = 1, which is mp_conv1x1's own choice: the two
+  // do not collide.  (Masking with 0xfff here used to strip 0x1000, so that word left the 3x3 launches on the heuristic.)
+  conv3x3_set_nr(nr & 0x1fff);
   conv1x1_set_mrw((nr >> 12) & 3);
 }
 

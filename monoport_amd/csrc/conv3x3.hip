@@ -944,6 +944,14 @@ bool conv3x3_supported(int cin, int cout, int h, int w) {
            (h & (h - 1)));
 }
 
+// Statistics of a convolution's own output (GroupNorm(32, Cout) over y): the epilogues of conv3x3.hip,
+// conv_wino.hip and convim2col.hip fold WHOLE groups out of a workgroup's 32-, 64- or 128-channel block
+// (ng = NCH / cpg groups from (NCH * blockIdx.y) / cpg on), which is only right when Cout / 32 divides the
+// block -- for every kernel and route when it divides 32.  At Cout = 96, 160, 192, 320, 384 ... a block
+// would drop its last channels and file the next block's under the wrong group, so the launchers refuse
+// the request instead (the y2 statistics have the same guard on y2_channels in launch_conv3x3).
+bool conv_stats_supported(int cout) { return cout >= 32 && cout % 32 == 0 && 32 % (cout / 32) == 0; }
+
 int launch_absmax(mp_ctx *ctx, const float *src, long long n, unsigned int *out_bits, hipStream_t st);
 
 int launch_conv3x3_pack16(mp_ctx *ctx, const float *w, int cout, int cin, void *wp, float *wmax,
@@ -1010,7 +1018,7 @@ int launch_conv3x3(mp_ctx *ctx, ConvArgs a, const float *wmax16, const long long
   const int n = a.n_img, cin = a.cin, cout = a.cout, h = a.h, w = a.w;
   if (!conv3x3_supported(cin, cout, h, w))
     return fail(ctx, MP_ERR_UNSUPPORTED,
-                "conv3x3: needs Cin %% 16 == 0, Cout %% 32 == 0, H and W powers of two (W >= 32, H >= 8); got %d -> %d at %dx%d",
+                "conv3x3: needs Cin %% 16 == 0 (16 .. 512), Cout %% 32 == 0, H and W powers of two (W >= 32, H >= 8); got %d -> %d at %dx%d",
                 cin, cout, h, w);
   if (cin > kMaxCin)
     return fail(ctx, MP_ERR_UNSUPPORTED, "conv3x3: at most %d input channels (got %d)", kMaxCin, cin);
@@ -1043,6 +1051,9 @@ int launch_conv3x3(mp_ctx *ctx, ConvArgs a, const float *wmax16, const long long
     GnOut &f = k ? a.fin2 : a.fin;
     if (!gn_wanted(f)) continue;
     if (k && !a.y2) return fail(ctx, MP_ERR_ARG, "conv3x3: statistics of y2 requested without y2");
+    if (!k && !conv_stats_supported(cout))
+      return fail(ctx, MP_ERR_UNSUPPORTED,
+                  "conv3x3: statistics of y need Cout / 32 to divide 32 (Cout = 32, 64, 128, 256, 512, 1024); got %d", cout);
     f.c = k ? a.y2_c : cout;
     f.S = c.tiles;
     f.n = n;

@@ -691,6 +691,9 @@ long long conv3x3_wino_workgroups(const ConvArgs &a) {
 }
 
 int launch_conv3x3_wino(mp_ctx *ctx, const ConvArgs &a, hipStream_t st) {
+  if (gn_wanted(a.fin) && !conv_stats_supported(a.cout))  // the quads to_lds pre-sums would straddle groups
+    return fail(ctx, MP_ERR_UNSUPPORTED,
+                "conv3x3: statistics of y need Cout / 32 to divide 32 (Cout = 32, 64, 128, 256, 512, 1024); got %d", a.cout);
   const int tiles = conv3x3_wino_tiles(a.h, a.w);
   if (wino_use64(a)) {
     auto kern = conv3x3_wino64_kernel;

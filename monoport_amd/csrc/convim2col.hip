@@ -298,6 +298,12 @@ int launch_convk(mp_ctx *ctx, ConvKArgs a, long long partial_cap, hipStream_t st
                 "output width a multiple of 64; got %dx%d stride %d, %d -> %d at %dx%d", a.ks, a.ks, a.stride,
                 a.cin, a.cout, a.h, a.w);
   if (a.pad != a.ks / 2) return fail(ctx, MP_ERR_UNSUPPORTED, "convk: padding must be ks / 2");
+  if (a.reflect && (a.h <= a.pad || a.w <= a.pad))  // the gather mirrors once (nn.ReflectionPad2d asks the same)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "convk: reflection padding %d needs a map larger than the padding (got %dx%d)",
+                a.pad, a.h, a.w);
+  if (gn_wanted(a.fin) && !conv_stats_supported(a.cout))
+    return fail(ctx, MP_ERR_UNSUPPORTED,
+                "convk: statistics of y need Cout / 32 to divide 32 (Cout = 64, 128, 256, 512, 1024); got %d", a.cout);
   a.ho = a.h / a.stride;
   a.wo = a.w / a.stride;
   a.wp_floats = (int)convk_packed_floats(a.cin, a.cout, a.ks);

@@ -335,6 +335,7 @@ int launch_conv3x3_pack(mp_ctx *ctx, const float *w, int cout, int cin, float *w
 int conv3x3_stat_slices(int cout, int n, int h, int w, bool f16);
 void conv3x3_set_nr(int nr);
 bool conv3x3_supported(int cin, int cout, int h, int w);
+bool conv_stats_supported(int cout);
 int launch_conv3x3_pack16(mp_ctx *ctx, const float *w, int cout, int cin, void *wp, float *wmax,
                           hipStream_t st);
 int launch_conv3x3_gn(mp_ctx *ctx, const float *x, int n, int cin, int h, int w, const float *ss,

@@ -347,8 +347,11 @@ class ConvBlock(nn.Module):
             return False
         h, w = x.shape[2], x.shape[3]
         min_h = ENCODER_CONV_MIN_H if ENCODER_CONV_PRECISION == "f32" else min(ENCODER_CONV_MIN_H, 32)
+        # conv1 and conv2 also emit the statistics bn2 / bn3 read: widths whose groups straddle the kernels'
+        # channel blocks (Cout = 96, 192 ... of a ConvBlock(., 384)) stay on the torch ops
         return (h >= min_h and (h * w) % 4 == 0 and all(ops.conv3x3_supported(c.in_channels, c.out_channels, h, w)
-                                         for c in (self.conv1, self.conv2, self.conv3)))
+                                         for c in (self.conv1, self.conv2, self.conv3))
+                and all(ops.conv3x3_stats_supported(c.out_channels) for c in (self.conv1, self.conv2)))
 
     def _forward_fused(self, x):
         """GroupNorm -> ReLU -> conv3x3, three times, as three kernels: the normalisation is
@@ -708,8 +711,9 @@ class _ResBlock(nn.Module):
         if not _inference_only(x, self):
             return False
         c = self.conv_block[1]
-        return (x.shape[2] * x.shape[3]) % 4 == 0 and ops.conv3x3_supported(c.in_channels, c.out_channels,
-                                                                           x.shape[2], x.shape[3])
+        return ((x.shape[2] * x.shape[3]) % 4 == 0 and ops.conv3x3_supported(c.in_channels, c.out_channels,
+                                                                            x.shape[2], x.shape[3])
+                and ops.conv3x3_stats_supported(c.out_channels))  # the GroupNorms read the convolutions' statistics
 
     def _forward_fused(self, x):
         """Two kernels + the residual: the reflection padding is index arithmetic in the staging
@@ -772,7 +776,9 @@ class ResnetFilter(nn.Module):
         return (_pow2(h) and _pow2(w) and h >= 32 and w >= 256
                 and ops.convk_supported(3, m[1].out_channels, 7, 1, h, w)
                 and ops.convk_supported(m[4].in_channels, m[4].out_channels, 3, 2, h, w)
-                and ops.convk_supported(m[7].in_channels, m[7].out_channels, 3, 2, h // 2, w // 2))
+                and ops.convk_supported(m[7].in_channels, m[7].out_channels, 3, 2, h // 2, w // 2)
+                # every convolution of the chain hands its statistics to the next GroupNorm
+                and all(ops.conv3x3_stats_supported(c.out_channels) for c in (m[1], m[4], m[7])))
 
     def _packed_k(self, conv):
         cache = self.__dict__.setdefault("_packed_cache", {})

@@ -1117,6 +1117,12 @@ def conv3x3_supported(cin, cout, h, w):
     return bool(_lib.load().mp_conv3x3_supported(int(cin), int(cout), int(h), int(w)))
 
 
+def conv3x3_stats_supported(cout):
+    """True if the convolution kernels can emit the GroupNorm(32, Cout) statistics of their own output
+    (mp_conv_stats_supported: Cout / 32 divides 32).  Other widths get y, and the launchers refuse ``stats``."""
+    return bool(_lib.load().mp_conv_stats_supported(int(cout)))
+
+
 def scale_shift_add(t, ss, res):
     """res + (t * scale + shift): x + GroupNorm(t) with (scale, shift) from ``gn_finalize``."""
     ctx = get_encoder_context(t.device)

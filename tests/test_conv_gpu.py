@@ -276,6 +276,17 @@ def test_conv3x3_rejects_unsupported_shapes():
     packed = ops.PackedConv3x3(torch.zeros((64, 64, 3, 3), device=DEV))
     with pytest.raises(MonoportError):
         ops.conv3x3_gn(x, None, packed)
+    assert not ops.conv3x3_supported(64, 64, 4, 32)       # H < 8
+    with pytest.raises(MonoportError, match="H >= 8"):
+        ops.conv3x3_gn(torch.zeros((1, 64, 4, 32), device=DEV), None, packed)
+    wide = ops.PackedConv3x3(torch.zeros((64, 528, 3, 3), device=DEV))  # Cin > 512: the launcher's limit
+    with pytest.raises(MonoportError, match="at most 512 input channels"):
+        ops.conv3x3_gn(torch.zeros((1, 528, 16, 32), device=DEV), None, wide)
+    odd = ops.PackedConv3x3(torch.zeros((64, 48, 3, 3), device=DEV))    # a GroupNorm(32, Cin) input needs Cin % 32 == 0
+    x48 = torch.zeros((1, 48, 16, 32), device=DEV)
+    assert ops.conv3x3_gn(x48, None, odd, relu=False)[0].shape == (1, 64, 16, 32)
+    with pytest.raises(MonoportError, match="Cin % 32"):
+        ops.conv3x3_gn(x48, torch.ones((1, 48, 2), device=DEV), odd)
 
 
 def test_convblock_fused_equals_unfused_module(monkeypatch):

@@ -33,6 +33,18 @@ def _acc_of(x):
     return acc
 
 
+def _ss64(t, gn, channels=slice(None)):
+    """(scale, shift) [N,C,2] of GroupNorm gn over t from the definition: float64 two-pass moments per (image, group)."""
+    n, c = t.shape[:2]
+    cpg = c // 32
+    v = t.double().reshape(n, 32, -1)
+    mean = v.mean(2)
+    rstd = 1.0 / torch.sqrt(((v - mean[..., None]) ** 2).mean(2) + gn.eps)
+    sc = rstd.repeat_interleave(cpg, 1) * gn.weight.double()[None]
+    sh = gn.bias.double()[None] - mean.repeat_interleave(cpg, 1) * sc
+    return torch.stack((sc, sh), 2)[:, channels]
+
+
 def _run(tune, x, gn_arg, packed, relu, reflect, res, off, ctot):
     from monoport_amd import _lib, ops
     lib = _lib.load()
@@ -96,6 +108,13 @@ def test_winograd_kernels_vs_fp64_and_the_direct_kernel(n, cin, cout, h, w, ctot
         cpg = ctot // 32
         sso = (ops.gn_reference_ss(acc_o, go, cpg * h * w) - ops.gn_reference_ss(accod, go, cpg * h * w))[:, off:off + cout]
         assert sso.abs().max().item() <= 2e-5
+        # ... and as from the float64 moments of what this launch wrote (a fault both kernels share would pass the above)
+        with torch.no_grad():
+            want_y = _ss64(y, gy)
+            want_o = _ss64(out, go, slice(off, off + cout))  # groups never straddle the launch's channels
+            e_y = (ops.gn_reference_ss(acc_y, gy, (cout // 32) * h * w).double() - want_y).abs().max().item()
+            e_o = (ops.gn_reference_ss(acc_o, go, cpg * h * w).double()[:, off:off + cout] - want_o).abs().max().item()
+        assert e_y <= 2e-5 * max(1.0, want_y.abs().max().item()) and e_o <= 2e-5 * max(1.0, want_o.abs().max().item())
         assert (acc_o[:, :, :off // cpg] == 0).all() and (acc_o[:, :, (off + cout) // cpg:] == 0).all()
         # deterministic (integer statistics, fixed summation order)
         y2, out2, acc_y2, acc_o2 = _run(tune, x, gn_arg, packed, relu, reflect, res, off, ctot)
