@@ -324,6 +324,25 @@ int mp_recon_batch_proj(mp_ctx *ctx, int mlp, int n_frames, const float *const *
                         float balance, int final_level, float *const *volume, int32_t *const *status,
                         const mp_recon_early *early, mp_stream stream);
 
+/* mp_recon for a multi-view head (multi-view PIFu, SurfaceClassifier num_views = n_views): the occupancy volume of
+ * ONE subject seen by n_views (1..MP_MAX_VIEWS) cameras, as one call.  Every octree level evaluates its nodes with
+ * the multi-view kernel of mp_query_views reading the level's packed node list directly (no point tensor exists) and
+ * writes row `view` (0..n_views-1) of the reference's [n_views,1,N] result -- the view-averaged prediction times
+ * view `view`'s in-image mask (MonoPortNet.py:89) -- straight into the level's volume; the other rows are never
+ * made.  feat_hwc / calib: HOST arrays of n_views device pointers as in mp_query_views (maps [h,w,c], 16-byte
+ * aligned; 4x4 calibrations); projection: ONE MP_PROJ_* mode for all views (a node whose perspective projection
+ * is non-finite in ANY view takes the value NaN).  b_min .. final_level, volume and status as in
+ * mp_recon_batch_proj with one frame; early (may be NULL) likewise: expect_level0[0] and two flags.  Fully
+ * asynchronous.  n_views outside 1..MP_MAX_VIEWS or a head whose precision is not MP_PREC_F32 returns
+ * MP_ERR_UNSUPPORTED; `view` outside 0..n_views-1, a null or misaligned buffer, or resolutions that break
+ * r[i+1] = 2 r[i] - 1 return MP_ERR_ARG.  Registered skip tables are not used; with n_views = 1 the volume and
+ * status equal mp_recon's on the plain kernels (no table registered for the map) bit for bit. */
+int mp_recon_views(mp_ctx *ctx, int mlp, int n_views, const float *const *feat_hwc, int c, int h, int w,
+                   const float *const *calib, int projection, float z_scale,
+                   const float *b_min, const float *b_max, const int *resolutions, int n_levels,
+                   float balance, int final_level, int view, float *volume, int32_t *status,
+                   const mp_recon_early *early, mp_stream stream);
+
 /* The same engine one level at a time, for an arbitrary Python ``query_func`` (the general
  * Seg3dLossless contract, RTL/main.py:169-195): the caller evaluates the selected nodes itself.
  *   mp_octree_select: level 0 (prev == NULL) selects every node; otherwise upsamples prev [rp^3]

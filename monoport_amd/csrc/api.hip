@@ -818,6 +818,56 @@ int mp_recon_batch_proj(mp_ctx *ctx, int mlp, int n_frames, const float *const *
                       resolutions, n_levels, balance, final_level, volume, status, early, (hipStream_t)stream);
 }
 
+int mp_recon_views(mp_ctx *ctx, int mlp, int n_views, const float *const *feat_hwc, int c, int h, int w,
+                   const float *const *calib, int projection, float z_scale,
+                   const float *b_min, const float *b_max, const int *resolutions, int n_levels,
+                   float balance, int final_level, int view, float *volume, int32_t *status,
+                   const mp_recon_early *early, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const Mlp *m = get_mlp(ctx, mlp);
+  int rc = check_ready(ctx, m, c);
+  if (rc != MP_OK) return rc;
+  if (n_views < 1 || n_views > kMaxViews)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_recon_views: 1..%d views per call, got %d", kMaxViews, n_views);
+  if (m->precision != MP_PREC_F32)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_recon_views: the multi-view kernel is f32 only (head precision %d)",
+                m->precision);
+  if (m->c != 256 || m->cout != 1)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_recon_views: needs a netG head (C=256, 1 occupancy channel); got C=%d Cout=%d",
+                m->c, m->cout);
+  if (view < 0 || view >= n_views)
+    return fail(ctx, MP_ERR_ARG, "mp_recon_views: view %d outside 0..%d", view, n_views - 1);
+  if (!feat_hwc || !calib || !b_min || !b_max || !resolutions || !volume || !status || n_levels < 1 ||
+      n_levels > 8 || h <= 0 || w <= 0)
+    return fail(ctx, MP_ERR_ARG, "mp_recon_views: bad argument");
+  for (int v = 0; v < n_views; ++v) {
+    if (!feat_hwc[v] || !calib[v]) return fail(ctx, MP_ERR_ARG, "mp_recon_views: null buffer for view %d", v);
+    if (!aligned16(feat_hwc[v])) return fail(ctx, MP_ERR_ARG, "mp_recon_views: feat_hwc must be 16-byte aligned");
+  }
+  if (final_level != MP_FINAL_DILATE3 && final_level != MP_FINAL_UPSTREAM && final_level != MP_FINAL_INTERPOLATE)
+    return fail(ctx, MP_ERR_ARG, "mp_recon_views: final_level must be MP_FINAL_DILATE3 / _UPSTREAM / _INTERPOLATE, got %d",
+                final_level);
+  for (int l = 0; l < n_levels; ++l) {
+    if (resolutions[l] < 2 || resolutions[l] > 1023)
+      return fail(ctx, MP_ERR_ARG, "mp_recon_views: resolution %d outside [2,1023]", resolutions[l]);
+    if (l > 0 && resolutions[l] != 2 * resolutions[l - 1] - 1)
+      return fail(ctx, MP_ERR_ARG, "mp_recon_views: resolutions must follow r -> 2r-1 (got %d after %d)",
+                  resolutions[l], resolutions[l - 1]);
+  }
+  rc = check_projection(ctx, "mp_recon_views", &projection, 1);
+  if (rc != MP_OK) return rc;
+  if (early && (!early->flags_dev || !early->flags_host))
+    return fail(ctx, MP_ERR_ARG, "mp_recon_views: early->flags_dev and flags_host are required");
+  DeviceGuard g(ctx->device);
+  void *scratch = nullptr;
+  rc = ensure_scratch(ctx, (hipStream_t)stream, recon_scratch_bytes(resolutions, n_levels), &scratch);
+  if (rc != MP_OK) return rc;
+  const ReconViews views = {n_views, view};
+  return launch_recon(ctx, scratch, *m, 1, feat_hwc, h, w, calib, &projection, z_scale, b_min, b_max, resolutions,
+                      n_levels, balance, final_level, &volume, &status, early, (hipStream_t)stream, &views);
+}
+
 int mp_recon(mp_ctx *ctx, int mlp, const float *feat_hwc, int c, int h, int w, const float *calib,
              float z_scale, const float *b_min, const float *b_max, const int *resolutions,
              int n_levels, float balance, float *volume, int32_t *status, mp_stream stream) {

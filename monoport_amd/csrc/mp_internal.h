@@ -154,6 +154,20 @@ struct ViewSetDev {
   const float *pts[kMaxViews];
   float *out[kMaxViews];
 };
+// The views of one octree level (mp_recon_views): the points are the level's packed node list `src` (lattice
+// mode of PointSrc, count *src.n_dev or src.n), shared by all views; n / sn / sc / pts / out of the base are
+// unused.  Only row `view` of the [V,1,N] result exists: it is scattered to vol[z,y,x] of the level's
+// src.level_res^3 buffer.
+struct ViewLatticeDev : ViewSetDev {
+  PointSrc src;
+  float *vol;
+  int view;
+};
+// launch_recon's second way to evaluate a level's nodes: feat_hwc / calib are then the nv views' arrays, proj[0]
+// their one projection, and the call has one frame
+struct ReconViews {
+  int nv, view;
+};
 
 struct Mlp {
   bool used = false;
@@ -252,6 +266,10 @@ int launch_perspective(mp_ctx *ctx, const float *pts, long long n, const float *
 // query_views.hip: the multi-view query (f32, plain kernel only: registered skip tables are not looked at)
 int launch_query_views(mp_ctx *ctx, const Mlp &m, const ViewSetDev &set, int h, int w, float z_scale,
                        hipStream_t st);
+// one octree level of mp_recon_views (netG f32 heads): at most max_points nodes, counted on the device when
+// set.src.n_dev is set
+int launch_query_views_lattice(mp_ctx *ctx, const Mlp &m, const ViewLatticeDev &set, int h, int w, float z_scale,
+                               long long max_points, hipStream_t st);
 // pack.hip
 int launch_pack_hwc(mp_ctx *ctx, const float *src, int c_src, int h, int w, float *dst, int c_dst,
                     int c_off, hipStream_t st);
@@ -290,7 +308,8 @@ int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
                  const float *const *feat_hwc, int h, int w, const float *const *calib,
                  const int *proj, float z_scale, const float *bmin, const float *bmax, const int *res,
                  int n_levels, float balance, int final_level, float *const *volume,
-                 int32_t *const *status, const mp_recon_early *early, hipStream_t st);
+                 int32_t *const *status, const mp_recon_early *early, hipStream_t st,
+                 const ReconViews *views = nullptr);
 int launch_octree_select(mp_ctx *ctx, const float *prev, int rp, float *cur, int r,
                          const unsigned long long *ev_prev, unsigned long long *ev_cur,
                          unsigned long long *bnd, int box, float balance, uint32_t *packed,

@@ -12,7 +12,8 @@
 //      shift-OR on the 64-bit words, minus the nodes evaluated at earlier levels, popcount +
 //      wave prefix sum + one atomic per wave -> a packed (x | y<<10 | z<<20) point list.
 //   3. the fused query kernel (query.hip) reads the list and its device-side count, and scatters
-//      exact occupancies straight into the level volume.
+//      exact occupancies straight into the level volume.  For a multi-view head (mp_recon_views) step 3 is
+//      the lattice variant of the multi-view kernel (query_views.hip); steps 1-2 are the same kernels.
 // No host synchronisation anywhere: counts stay on the device (`status`).
 #include <cstdlib>
 #include <cstring>
@@ -480,7 +481,8 @@ int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
                  const float *const *feat_hwc, int h, int w, const float *const *calib,
                  const int *proj, float z_scale, const float *bmin, const float *bmax, const int *res,
                  int n_levels, float balance, int final_level, float *const *volume,
-                 int32_t *const *status, const mp_recon_early *early, hipStream_t st) {
+                 int32_t *const *status, const mp_recon_early *early, hipStream_t st,
+                 const ReconViews *views) {
   // carve the scratch arena: one private set of level buffers per frame
   const size_t per_frame = recon_scratch_bytes(res, n_levels);
   LevelBufs lv[kMaxFrames][8];
@@ -522,6 +524,24 @@ int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
     }
     MP_HIP(ctx, hipMemsetAsync(status[f], 0, sizeof(int32_t) * (1 + n_levels), st));
   }
+
+  // Step 3 of a level: the frames' single-view set through launch_query_set, or (views: one frame) the nv views
+  // of feat_hwc / calib on the level's node list, row views->view of their result into the level's volume
+  auto eval_level = [&](long long max_points, bool device_counts) -> int {
+    if (!views) return launch_query_set(ctx, m, set, h, w, z_scale, max_points, device_counts, st);
+    ViewLatticeDev vs;
+    std::memset(&vs, 0, sizeof(vs));
+    vs.nv = views->nv;
+    vs.proj = set.it[0].proj;
+    for (int v = 0; v < views->nv; ++v) {
+      vs.feat[v] = feat_hwc[v];
+      vs.calib[v] = calib[v];
+    }
+    vs.src = set.it[0].src;
+    vs.vol = set.it[0].out;
+    vs.view = views->view;
+    return launch_query_views_lattice(ctx, m, vs, h, w, z_scale, max_points, st);
+  };
 
   FrameBufs fb;
   std::memset(&fb, 0, sizeof(fb));
@@ -568,7 +588,7 @@ int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
       hipLaunchKernelGGL(iota_nodes_kernel, dim3((total + 255) / 256, 1, nf), dim3(256), 0, st, r, sub(f0, nf), words64(r),
                          (int)octree_y_major());
     }
-    int rc = launch_query_set(ctx, m, set, h, w, z_scale, (long long)total * n_frames, false, st);
+    int rc = eval_level((long long)total * n_frames, false);
     if (rc != MP_OK) return rc;
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
       const int nf = min(chunk, n_frames - f0);
@@ -619,7 +639,7 @@ int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
         launch_select(rule == MP_FINAL_UPSTREAM ? 1 : octree_box_of_level(l), st, c, nf, rp, words64(rp), r, w64);
     }
     if (rule == MP_FINAL_INTERPOLATE) continue;  // status[1 + l] stays 0, no query
-    int rc = launch_query_set(ctx, m, set, h, w, z_scale, (long long)r * r * r * n_frames, true, st);
+    int rc = eval_level((long long)r * r * r * n_frames, true);
     if (rc != MP_OK) return rc;
   }
   MP_HIP(ctx, hipGetLastError());

@@ -20,6 +20,11 @@
 //     writes row v of the result with view v's in-image mask: preds = in_img[:, None] * pred
 //     ([V,1,N] * [1,Cout,N], MonoPortNet.py:89).
 // With V = 1 every column is its own group and the result equals pifu_query_kernel's bit for bit.
+//
+// LATTICE = true (mp_recon_views, one octree level): the points are the level's packed node list
+// (x | y<<10 | z<<20, shared by all views) turned into world coordinates by lattice_coord, their number is read
+// from device memory, and only the columns of ONE view write: row `view` of the result, scattered to
+// volume[z,y,x].  Gather, layers, view mean and tile mapping are those of the explicit-point kernel.
 #include <cstring>
 
 #include "mp_internal.h"
@@ -63,13 +68,20 @@ __device__ __forceinline__ void column_view(int p, int nv, int magic, int &g, in
 
 // z_feat of point n in view u: the view's projection z times z_scale (MonoPortNet.py:72, :78);
 // DIRECT: row C of view u's explicit feature columns
-template <int C, bool DIRECT>
-__device__ __forceinline__ float view_z(const ViewSetDev &set, int u, long long n, float z_scale,
+// LATTICE: node n of the level's list instead of view u's explicit point
+template <int C, bool DIRECT, bool LATTICE, typename SET>
+__device__ __forceinline__ float view_z(const SET &set, int u, long long n, float z_scale,
                                         float &x, float &y) {
   if constexpr (DIRECT) {
     x = 0.0f;
     y = 0.0f;
     return set.pts[u][(long long)C * set.sc + n];
+  } else if constexpr (LATTICE) {
+    float px, py, pz, z;
+    uint32_t code;
+    load_point(set.src, n, px, py, pz, code);
+    project_mode(set.calib[u], set.proj, px, py, pz, x, y, z);
+    return __fmul_rn(z, z_scale);
   } else {
     const float *__restrict__ cal = set.calib[u];
     const float *__restrict__ q = set.pts[u] + n * set.sn;
@@ -81,22 +93,22 @@ __device__ __forceinline__ float view_z(const ViewSetDev &set, int u, long long 
 
 // z_feat of column p of the tile starting at point n0: its own view's, or (mean) the group mean over the
 // views, summed in view order and divided by V like the feature means; 0 for dead columns
-template <int C, bool DIRECT>
-__device__ __forceinline__ float column_z(const ViewSetDev &set, int p, int magic, long long n0, int ncol,
-                                          float z_scale, bool mean) {
+template <int C, bool DIRECT, bool LATTICE, typename SET>
+__device__ __forceinline__ float column_z(const SET &set, int p, int magic, long long n0, long long n_pts,
+                                          int ncol, float z_scale, bool mean) {
   const int nv = set.nv;
   int g, v;
   column_view(p, nv, magic, g, v);
   const long long n = n0 + g;
-  if (p >= ncol || n >= set.n) return 0.0f;
+  if (p >= ncol || n >= n_pts) return 0.0f;
   if (!mean) {
     float x, y;
-    return view_z<C, DIRECT>(set, v, n, z_scale, x, y);
+    return view_z<C, DIRECT, LATTICE>(set, v, n, z_scale, x, y);
   }
   float sum = 0.0f;
   for (int u = 0; u < nv; ++u) {
     float x, y;
-    const float zf = view_z<C, DIRECT>(set, u, n, z_scale, x, y);
+    const float zf = view_z<C, DIRECT, LATTICE>(set, u, n, z_scale, x, y);
     sum = u == 0 ? zf : sum + zf;
   }
   return __fdiv_rn(sum, (float)nv);
@@ -104,9 +116,20 @@ __device__ __forceinline__ float column_z(const ViewSetDev &set, int p, int magi
 
 // DIRECT = true: SurfaceClassifier.forward on explicit features [V][C+1][N] (set.pts[v], row
 // stride set.sc), one output [Cout, N] written by the view-0 columns.
-template <int C, int COUT, int WPS, bool DIRECT>
+// LATTICE = true: one octree level (see the head of this file); `set` is then a ViewLatticeDev.
+template <bool LATTICE>
+struct ViewSetArg {
+  typedef ViewSetDev type;
+};
+template <>
+struct ViewSetArg<true> {
+  typedef ViewLatticeDev type;
+};
+
+template <int C, int COUT, int WPS, bool DIRECT, bool LATTICE = false>
 __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
-    MlpPack mlp, int fh, int fw, float z_scale, int act, ViewSetDev set) {
+    MlpPack mlp, int fh, int fw, float z_scale, int act, typename ViewSetArg<LATTICE>::type set) {
+  static_assert(!(DIRECT && LATTICE), "explicit features have no lattice");
   constexpr int ROWB = C * 4;
   constexpr int NGX = C / 8;  // K groups of the feature segment
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -121,7 +144,11 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
   const int gpts = kTilePts / nv;  // points per tile
   const int ncol = gpts * nv;      // live columns
   const int magic = (65536 + nv - 1) / nv;  // column_view
-  const long long n_pts = set.n;
+  long long n_pts;
+  if constexpr (LATTICE)
+    n_pts = set.src.n_dev ? (long long)*set.src.n_dev : set.src.n;  // a level's count lives on the device
+  else
+    n_pts = set.n;
   const long long tiles = (n_pts + gpts - 1) / gpts;
 
   const int swz = h ^ (j & 15);
@@ -165,7 +192,7 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
           const bool live_n = p < ncol && n < n_pts;
           fmap[u] = set.feat[v];
           float x = 0.0f, y = 0.0f;
-          if (live_n) (void)view_z<C, false>(set, v, n, z_scale, x, y);
+          if (live_n) (void)view_z<C, false, LATTICE>(set, v, n, z_scale, x, y);
           // grid_sample on every finite projection, in the image or not (zero padding)
           t[u] = make_taps(x, y, fh, fw, C, live_n && !non_finite(x, y));
         }
@@ -193,7 +220,7 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
     // z_feat of this wave's two column blocks for the z k-steps of layers 0-2 (lanes 0-31 carry it, 32-63 supply 0)
     float zb[2];
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb) zb[cb] = h == 0 ? column_z<C, DIRECT>(set, 32 * cb + j, magic, n0, ncol, z_scale, false) : 0.0f;
+    for (int cb = 0; cb < 2; ++cb) zb[cb] = h == 0 ? column_z<C, DIRECT, LATTICE>(set, 32 * cb + j, magic, n0, n_pts, ncol, z_scale, false) : 0.0f;
     __syncthreads();
 
     const unsigned char *xrow = xs + j * ROWB;       // this lane's column row, column block 0
@@ -324,7 +351,7 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
       // the z row of tmpy: the group mean of z_feat (made here rather than kept live through layers 0-2)
       float zm[2];
 #pragma unroll
-      for (int cb = 0; cb < 2; ++cb) zm[cb] = h == 0 ? column_z<C, DIRECT>(set, 32 * cb + j, magic, n0, ncol, z_scale, true) : 0.0f;
+      for (int cb = 0; cb < 2; ++cb) zm[cb] = h == 0 ? column_z<C, DIRECT, LATTICE>(set, 32 * cb + j, magic, n0, n_pts, ncol, z_scale, true) : 0.0f;
       gemm_z<1, 2>(acc3, az3, zm);
 #pragma unroll
       for (int n = 0; n < 2; ++n) lrelu(acc3[0][n]);
@@ -392,18 +419,26 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
         float *__restrict__ out = set.out[0];
         for (int u = 0; u < nv; ++u) {
           float x, y;
-          const float zf = view_z<C, DIRECT>(set, u, n, z_scale, x, y);
+          const float zf = view_z<C, DIRECT, LATTICE>(set, u, n, z_scale, x, y);
           zsum = u == 0 ? zf : zsum + zf;
           poisoned = poisoned || (set.proj == MP_PROJ_PERSPECTIVE && non_finite(x, y));
           if (u == v) {
             xo = x;
             yo = y;
-            if (!DIRECT) out = set.out[u];
+            if (!DIRECT && !LATTICE) out = set.out[u];
           }
         }
         val = fmaf(wz, __fdiv_rn(zsum, (float)nv), val);
         if constexpr (DIRECT) {
           if (v == 0) out[o * set.out_stride + n] = activate(val, act);
+        } else if constexpr (LATTICE) {
+          // row `view` only, straight into the level's volume (COUT = 1: o == 0)
+          if (v == set.view) {
+            const float r = poisoned ? __builtin_nanf("") : in_image(xo, yo) ? activate(val, act) : 0.0f;
+            const uint32_t code = set.src.packed[n];
+            const long long lr = set.src.level_res;
+            set.vol[((long long)(code >> 20) * lr + ((code >> 10) & 1023u)) * lr + (code & 1023u)] = r;
+          }
         } else {
           // MonoPortNet.py:89 per view; a non-finite view's NaN samples reach every row through the mean
           const float r = poisoned ? __builtin_nanf("") : in_image(xo, yo) ? activate(val, act) : 0.0f;
@@ -431,6 +466,43 @@ static int launch_views_t(mp_ctx *ctx, const Mlp &m, const ViewSetDev &set, int 
   if (tiles <= 0) return MP_OK;
   const long long resident = (long long)cus_of(ctx, st) * WPS;
   const long long grid = tiles < 8 * resident ? tiles : 8 * resident;
+  const bool prof = 2 * (ctx->prof_used + 1) <= (int)ctx->prof_events.size();
+  if (prof) MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used], st));
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kQueryThreads), lds, st, m.pack(), h, w, z_scale, m.act,
+                     set);
+  if (prof) {
+    MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used + 1], st));
+    ++ctx->prof_used;
+  }
+  MP_HIP(ctx, hipGetLastError());
+  return MP_OK;
+}
+
+// One octree level.  The level's count is on the device (set.src.n_dev) except at level 0: the grid is the
+// stream's resident share striding over the tiles, and a count of 0 leaves every workgroup at its loop test.
+int launch_query_views_lattice(mp_ctx *ctx, const Mlp &m, const ViewLatticeDev &set, int h, int w, float z_scale,
+                               long long max_points, hipStream_t st) {
+  if (set.nv < 1 || set.nv > kMaxViews)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "multi-view octree: 1..%d views, got %d", kMaxViews, set.nv);
+  if (m.c != 256 || m.cout != 1 || m.precision != MP_PREC_F32)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "multi-view octree: f32 netG heads (C=256, Cout=1); got C=%d Cout=%d precision %d",
+                m.c, m.cout, m.precision);
+  if (set.view < 0 || set.view >= set.nv)
+    return fail(ctx, MP_ERR_ARG, "multi-view octree: view %d of %d", set.view, set.nv);
+  constexpr int C = 256, WPS = 2;
+  constexpr int lds = kTilePts * C * 4 + kHbBytes;
+  auto kern = pifu_query_views_kernel<C, 1, WPS, false, true>;
+  const void *kern_id = reinterpret_cast<const void *>(kern);
+  if (!ctx->lds_attr_done.count(kern_id)) {
+    MP_HIP(ctx, hipFuncSetAttribute(kern_id, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    ctx->lds_attr_done.insert(kern_id);
+  }
+  const long long gpts = kTilePts / set.nv;
+  const long long tiles = (max_points + gpts - 1) / gpts;
+  if (tiles <= 0) return MP_OK;
+  const long long resident = (long long)cus_of(ctx, st) * WPS;
+  const long long grid = set.src.n_dev ? (tiles < resident ? tiles : resident)
+                                       : (tiles < 8 * resident ? tiles : 8 * resident);
   const bool prof = 2 * (ctx->prof_used + 1) <= (int)ctx->prof_events.size();
   if (prof) MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used], st));
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kQueryThreads), lds, st, m.pack(), h, w, z_scale, m.act,

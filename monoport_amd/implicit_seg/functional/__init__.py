@@ -29,6 +29,13 @@ Constructor flags (upstream names):
                     level (the other reading of upstream's "last step no examine").  Nothing under the
                     reference pins this; a maintainer who has implicit_seg
                     installed picks the mode that reproduces it.
+  ``fuse_views``    (monoport_amd extension, faster=True only) serve a ``query_func`` whose one call is a
+                    MULTI-VIEW MonoPortNet.query (SurfaceClassifier num_views = V > 1) through the fused
+                    engine too (ops.recon_views: one asynchronous call, every level on the multi-view
+                    kernel).  ``view`` (0..V-1) names the row of the [V,1,N] result the caller's
+                    ``query_func`` returns: the view-averaged prediction times THAT view's in-image mask
+                    (``[:1]`` of RTL/main.py's get_preds()[0][0] is view 0).  Off by default: a multi-view
+                    ``query_func`` then runs on the level-at-a-time engine.
   ``align_corners=True``, ``visualize=True``, ``use_shadow=True``, ``channels != 1``: not built,
                     NotImplementedError at construction.
 """
@@ -40,14 +47,15 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ...modeling.MonoPortNet import record_query
+from ...modeling.MonoPortNet import ViewsBinding, record_query
 from . import utils  # noqa: F401
 
 
 class Seg3dLossless(nn.Module):
     def __init__(self, query_func, b_min, b_max, resolutions, channels=1, balance_value=0.5,
                  align_corners=False, visualize=False, debug=False, use_cuda_impl=False,
-                 faster=False, use_shadow=False, final_level="dilate3", validate="always", **kwargs):
+                 faster=False, use_shadow=False, final_level="dilate3", validate="always", fuse_views=False,
+                 view=0, **kwargs):
         super().__init__()
         if kwargs:  # the upstream constructor swallows **kwargs: stay drop-in, but say so
             warnings.warn("Seg3dLossless: ignoring unknown arguments %s" % sorted(kwargs))
@@ -84,6 +92,12 @@ class Seg3dLossless(nn.Module):
         if final_level != "dilate3" and not self.faster:
             raise NotImplementedError("final_level=%r is a variant of the faster=True schedule" % final_level)
         self.final_level = final_level
+        if fuse_views and not self.faster:
+            raise NotImplementedError("fuse_views=True is a variant of the faster=True schedule")
+        if int(view) != view or view < 0:
+            raise ValueError("view must be a row 0..V-1 of the multi-view result, got %r" % (view,))
+        self.fuse_views = bool(fuse_views)
+        self.view = int(view)
         self.use_cuda_impl = bool(use_cuda_impl)  # same kernels either way (see module docstring)
         self.debug = bool(debug)
         self._status = None    # CPU tensor, or the device tensor of a call whose refinement may still be running
@@ -102,7 +116,8 @@ class Seg3dLossless(nn.Module):
         self.validate = validate
         self._agreed = 0          # consecutive validated calls that agreed
         self._since_check = 0     # trusted calls since the last validated one
-        self._trusted_key = None  # (id(packed head), precision, z scale, projection) those calls were bound to
+        # (id(packed head), precision, z scale, [views, view,] projection) those calls were bound to
+        self._trusted_key = None
         # nn.Module.to(device) is called on the engine (RTL/main.py:195): carry a buffer so it
         # has a device like the upstream module does
         self.register_buffer("_device_tag", torch.zeros(1), persistent=False)
@@ -156,16 +171,14 @@ class Seg3dLossless(nn.Module):
         eng = ops.LevelEngine(dev, self.b_min[0], self.b_max[0], self.resolutions,
                               self.balance_value, self.faster, self.final_level)
         pts0 = eng.select()
-        with record_query() as rec:
+        with record_query(views=self.fuse_views) as rec:
             occ0 = self.query_func(points=pts0[None], **kwargs)
         binding = rec.binding if rec.calls == 1 else None
         if binding is not None and self.faster:
+            self._check_view(binding)
             eng.scatter(occ0)  # the caller's values on the coarsest lattice, [r0,r0,r0]
             early = self._early_flags(dev)
-            volume, status = ops.recon(binding.mlp, binding.feat_hwc, binding.calib, binding.z_scale,
-                                       self.b_min[0], self.b_max[0], self.resolutions,
-                                       self.balance_value, final_level=self.final_level, early=early,
-                                       expect_level0=eng.cur, projection=binding.projection)
+            volume, status = self._recon(binding, early, eng.cur)
             # the one host sync of a reconstruction (upstream syncs at every level) -- and it waits for the
             # coarsest level only: "None or a volume" and "is query_func the fused kernels' function" are both
             # known there, the finer levels go on refining `volume` on this stream after the call has returned
@@ -193,9 +206,27 @@ class Seg3dLossless(nn.Module):
     VALIDATE_CALLS = 3
     REVALIDATE_EVERY = 32  # a trusted query_func is validated again on every 32nd call
 
-    @staticmethod
-    def _binding_key(binding):
+    def _binding_key(self, binding):
+        if isinstance(binding, ViewsBinding):
+            return (id(binding.mlp), binding.mlp.precision, float(binding.z_scale), binding.num_views, self.view,
+                    binding.projection)
         return (id(binding.mlp), binding.mlp.precision, float(binding.z_scale), binding.projection)
+
+    def _check_view(self, binding):
+        if isinstance(binding, ViewsBinding) and self.view >= binding.num_views:
+            raise ValueError("Seg3dLossless(view=%d): the head has %d views (rows 0..%d)"
+                             % (self.view, binding.num_views, binding.num_views - 1))
+
+    def _recon(self, b, early=None, expect_level0=None):
+        """The fused reconstruction of a recorded binding: one frame (ops.recon) or, with ``fuse_views``, the V
+        views of one subject (ops.recon_views, row ``self.view``) -> (volume, status) on the device."""
+        if isinstance(b, ViewsBinding):
+            return ops.recon_views(b.mlp, b.maps, b.calibs, b.projection, b.z_scale, self.b_min[0], self.b_max[0],
+                                   self.resolutions, self.balance_value, final_level=self.final_level,
+                                   view=self.view, early=early, expect_level0=expect_level0)
+        return ops.recon(b.mlp, b.feat_hwc, b.calib, b.z_scale, self.b_min[0], self.b_max[0], self.resolutions,
+                         self.balance_value, final_level=self.final_level, early=early,
+                         expect_level0=expect_level0, projection=b.projection)
 
     def _forward_trusted(self, kwargs):
         """A query_func whose last VALIDATE_CALLS calls were plain MonoPortNet.query calls agreeing
@@ -203,16 +234,14 @@ class Seg3dLossless(nn.Module):
         (recorded, not launched) and run the fused engine without the 17^3 validation query (one
         host sync instead of two).  NotImplemented = the binding changed: validate again."""
         probe = torch.zeros((1, 1, 3), dtype=torch.float32, device=self._device_tag.device)
-        with record_query(capture_only=True) as rec:
+        with record_query(capture_only=True, views=self.fuse_views) as rec:
             self.query_func(points=probe, **kwargs)
         b = rec.binding
         if b is None or rec.calls != 1 or self._binding_key(b) != self._trusted_key:
             self._agreed, self._trusted_key = 0, None
             return NotImplemented
         early = self._early_flags(self._device_tag.device)
-        volume, status = ops.recon(b.mlp, b.feat_hwc, b.calib, b.z_scale, self.b_min[0], self.b_max[0],
-                                   self.resolutions, self.balance_value, final_level=self.final_level, early=early,
-                                   projection=b.projection)
+        volume, status = self._recon(b, early)
         nonempty = int(early.wait()[0, 0])  # waits for the coarsest level only (see forward)
         self.last_status, self.last_path = status, "fused"
         return None if nonempty == 0 else volume[None, None]
@@ -236,10 +265,12 @@ class Seg3dLossless(nn.Module):
         probe = torch.zeros((1, 1, 3), dtype=torch.float32, device=self._device_tag.device)
         bindings = []
         for kw in kwargs_list:
-            with record_query(capture_only=True) as rec:
+            with record_query(capture_only=True, views=self.fuse_views) as rec:
                 self.query_func(points=probe, **kw)
             b = rec.binding
-            if b is None or rec.calls != 1 or self._binding_key(b) != self._trusted_key:
+            # a multi-view binding is one point set per call (mp_recon_views): its frames go one by one
+            if (b is None or rec.calls != 1 or isinstance(b, ViewsBinding)
+                    or self._binding_key(b) != self._trusted_key):
                 return [self(**kw) for kw in kwargs_list]  # forward() re-validates
             bindings.append(b)
         b0 = bindings[0]
@@ -260,13 +291,13 @@ class Seg3dLossless(nn.Module):
         if not self.faster:
             raise NotImplementedError("forward_async is the faster=True schedule")
         probe = torch.zeros((1, 1, 3), dtype=torch.float32, device=self._device_tag.device)
-        with record_query(capture_only=True) as rec:
+        with record_query(capture_only=True, views=self.fuse_views) as rec:
             self.query_func(points=probe, **kwargs)
         b = rec.binding
         if b is None:
             raise NotImplementedError("forward_async needs a query_func ending in MonoPortNet.query")
-        return ops.recon(b.mlp, b.feat_hwc, b.calib, b.z_scale, self.b_min[0], self.b_max[0],
-                         self.resolutions, self.balance_value, final_level=self.final_level, projection=b.projection)
+        self._check_view(b)
+        return self._recon(b)
 
 
 class Seg3dTopk(nn.Module):

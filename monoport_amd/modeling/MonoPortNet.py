@@ -48,14 +48,31 @@ class QueryBinding:
         self.projection = projection
 
 
+class ViewsBinding:
+    """What one ``MonoPortNet.query`` call of a multi-view head (num_views = V > 1) binds together for one point
+    set: packed MLP + the V views' channels-last maps + [V,4,4] calibrations + z scale + the one projection.  The
+    octree engine records it (``record_query(views=True)``) and drives all levels through ops.recon_views."""
+
+    def __init__(self, net, mlp, maps, calibs, z_scale, projection=ops.PROJECTIONS["orthogonal"]):
+        self.net, self.mlp, self.maps, self.calibs, self.z_scale = net, mlp, maps, calibs, z_scale
+        self.projection = projection
+
+    @property
+    def num_views(self):
+        return len(self.maps)
+
+
 class record_query:
     """Context manager (per host thread): counts the ``MonoPortNet.query`` calls made inside it
     and keeps the QueryBinding of the first one in ``.binding``.  The calls run normally.  With
     ``capture_only=True`` the first call returns zeros instead of launching (a probe).  Used by
-    Seg3dLossless to see through an opaque ``query_func`` closure such as RTL/main.py:169-183."""
+    Seg3dLossless to see through an opaque ``query_func`` closure such as RTL/main.py:169-183.
+    ``views=True``: the capture also takes the ViewsBinding of a multi-view head's call (by default
+    such a call is counted and never bound)."""
 
-    def __init__(self, capture_only=False):
+    def __init__(self, capture_only=False, views=False):
         self.capture_only = capture_only
+        self.views = views
 
     def __enter__(self):
         self.binding = None
@@ -225,7 +242,15 @@ class MonoPortNet(nn.Module):
             raise ValueError("points must be [B,3,N], got %s" % (tuple(points.shape),))
         if self.surface_classifier.num_views > 1:
             if cap is not None:
-                cap.calls += 1  # never a binding: the fused octree engine is single-view
+                # a binding only for a capture that asks for view bindings (Seg3dLossless(fuse_views=True)): the
+                # default fused octree engine is single-view
+                cap.calls += 1
+                if cap.views and cap.binding is None:
+                    self._check_view_rows(feats_stages, points, calibs)
+                    cap.binding = self.bind_views(feats_stages, calibs)
+                    if cap.capture_only:
+                        return [torch.zeros((points.shape[0], cap.binding.mlp.cout, points.shape[2]),
+                                            dtype=torch.float32, device=points.device)]
             return [self._query_views(feats_stages, points, calibs)]
         if points.shape[0] != 1:
             if cap is not None:
@@ -266,9 +291,15 @@ class MonoPortNet(nn.Module):
         reference's result is [B*V,Cout,N] only for B = 1 (MonoPortNet.py:89 broadcasts in_img [B*V,1,N] against
         pred [B,Cout,N]); like it, B > 1 and rows that are not groups of V raise RuntimeError.  One
         mp_query_views launch; skip tables are not made or used."""
+        self._check_view_rows(feats_stages, points, calibs)
+        b = self.bind_views(feats_stages, calibs)
+        return ops.query_views(b.mlp, b.maps, points, b.calibs, b.projection, b.z_scale)
+
+    def _check_view_rows(self, feats_stages, points, calibs):
+        """The shape rules of a multi-view query (see ``_query_views``)."""
         if self.training:
             raise NotImplementedError("monoport_amd implements the inference path (net.eval())")
-        v_n, rows, n = self.surface_classifier.num_views, points.shape[0], points.shape[2]
+        v_n, rows = self.surface_classifier.num_views, points.shape[0]
         if rows % v_n:
             raise RuntimeError("query: %d point rows are not groups of num_views = %d (the reference's "
                                "view(-1, %d, C, N) raises)" % (rows, v_n, v_n))
@@ -280,6 +311,21 @@ class MonoPortNet(nn.Module):
         if any(f.shape[0] != v_n for f in feats) or (calibs is not None and calibs.dim() == 3
                                                       and calibs.shape[0] != v_n):
             raise ValueError("query: %d views, feature maps of batch %s, calibrations %s"
+                             % (v_n, [f.shape[0] for f in feats], None if calibs is None else tuple(calibs.shape)))
+
+    def bind_views(self, feats_stages, calibs):
+        """ViewsBinding for eval-mode queries of a multi-view head (num_views = V > 1) against the V views of
+        ``feats_stages`` (batch V) / ``calibs`` ([V,4,4], one [4,4] for all views, or None).  No skip tables."""
+        if self.training:
+            raise NotImplementedError("monoport_amd implements the inference path (net.eval())")
+        v_n = self.surface_classifier.num_views
+        if v_n <= 1:
+            raise NotImplementedError("bind_views(): the head has num_views = %d; single-view heads bind through "
+                                      "bind()" % v_n)
+        feats = list(feats_stages[-1])  # eval keeps the last stage only (MonoPortNet.py:63-64)
+        if any(f.shape[0] != v_n for f in feats) or (calibs is not None and calibs.dim() == 3
+                                                      and calibs.shape[0] != v_n):
+            raise ValueError("bind_views: %d views, feature maps of batch %s, calibrations %s"
                              % (v_n, [f.shape[0] for f in feats], None if calibs is None else tuple(calibs.shape)))
         dev = feats[0].device
         if calibs is None:
@@ -295,7 +341,7 @@ class MonoPortNet(nn.Module):
             raise RuntimeError("surface_classifier and the feature maps must be on one GPU "
                                "(RTL/main.py:382-387 moves the features first)")
         maps = [self._packed_features(feats, v) for v in range(v_n)]
-        return ops.query_views(mlp, maps, points, calibs, projection, self.normalizer.scale)
+        return ViewsBinding(self, mlp, maps, calibs, self.normalizer.scale, projection)
 
     def get_loss(self, pred_stages, labels):
         """Average MSE / L1 over stages (MonoPortNet.py:93-117); plain tensor ops."""

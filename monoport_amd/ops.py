@@ -647,6 +647,56 @@ def recon_batch(mlp, feats_hwc, calibs, z_scale, b_min, b_max, resolutions, bala
     return volumes, status
 
 
+def recon_views(mlp, maps, calibs, projection, z_scale, b_min, b_max, resolutions, balance=0.5,
+                final_level="dilate3", view=0, early=None, expect_level0=None):
+    """mp_recon_views: ``recon`` for a multi-view head (SurfaceClassifier num_views = V).  maps: V channels-last
+    maps [H,W,C]; calibs: V calibrations ([>=3,4] each, or one [V,>=3,4] tensor); projection: ONE MP_PROJ_* int or
+    name for all views; ``view``: which row of the reference's [V,1,N] result the volume holds (the view-averaged
+    prediction times view ``view``'s in-image mask).  Returns (volume [R,R,R] f32, status int32[1+levels]) -- both
+    on device, nothing synchronised.  ``early``: an ``EarlyFlags`` for one frame, ``expect_level0``: [r0,r0,r0] f32
+    (see ``recon_batch``).  f32 netG heads only; registered skip tables are not used."""
+    ctx = mlp.ctx
+    v_n = len(maps)
+    _check_views(mlp, v_n, "recon_views")
+    h, w, c = maps[0].shape
+    dev = maps[0].device
+    for f in maps:
+        if tuple(f.shape) != (h, w, c) or not f.is_contiguous() or f.dtype != torch.float32:
+            raise ValueError("recon_views: the maps must be contiguous float32 [%d,%d,%d]" % (h, w, c))
+    if torch.is_tensor(calibs) and calibs.dim() == 3:
+        calibs = [calibs[v] for v in range(calibs.shape[0])]
+    if len(calibs) != v_n:
+        raise ValueError("recon_views: %d maps, %d calibrations" % (v_n, len(calibs)))
+    cals = [_calib_dev(cb, dev) for cb in calibs]
+    res = [int(r) for r in resolutions]
+    volume = torch.empty((res[-1],) * 3, dtype=torch.float32, device=dev)
+    status = torch.empty((1 + len(res),), dtype=torch.int32, device=dev)
+    bmin = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(b_min, np.float32).reshape(3)])
+    bmax = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(b_max, np.float32).reshape(3)])
+    if early is not None:
+        if early.n != 1:
+            raise ValueError("recon_views: EarlyFlags for %d frames, the call has one" % early.n)
+        if expect_level0 is not None:
+            assert (expect_level0.numel() == res[0] ** 3 and expect_level0.is_contiguous()
+                    and expect_level0.dtype == torch.float32)
+        est = early.struct(None if expect_level0 is None else [expect_level0])
+        early_arg = ctypes.byref(est)
+    else:
+        early_arg = None
+    ptrs = ctypes.c_void_p * v_n
+    ctx.check(ctx.lib.mp_recon_views(
+        ctx.handle, mlp.id, v_n, ptrs(*[f.data_ptr() for f in maps]), c, h, w, ptrs(*[cb.data_ptr() for cb in cals]),
+        _projection(projection), float(z_scale), bmin, bmax, (ctypes.c_int * len(res))(*res), len(res),
+        float(balance), _final_level(final_level), int(view), _ptr(volume), _ptr(status), early_arg,
+        _stream(volume)), "mp_recon_views")
+    stream = torch.cuda.current_stream(dev)
+    if expect_level0 is not None:
+        expect_level0.record_stream(stream)
+    for t in cals:
+        t.record_stream(stream)
+    return volume, status
+
+
 class LevelEngine:
     """The coarse-to-fine engine one step at a time, for an ARBITRARY ``query_func``: node
     selection, lattice coordinates, conflict detection and scatter run as HIP kernels
