@@ -438,6 +438,28 @@ int mp_marching_cubes(mp_ctx *ctx, const float *volume, int r, float level,
                       int64_t max_verts, int32_t *faces, int64_t max_faces, int32_t *counts,
                       mp_stream stream);
 
+/* Per-vertex normals of a triangle mesh: compute_normal (monoport/lib/mesh_util.py:201-220).  Each face has the
+ * unit normal n = normalize_v3(cross(v1 - v0, v2 - v0)) (normalize_v3: length clamped from below at 1e-8, so a
+ * zero-area face has n = 0); a vertex's normal is normalize_v3 of a sum of its faces' n, added in f32 to +0:
+ *   MP_NORMALS_REFERENCE   what the reference computes, bit for bit on f32 vertices: its `norm[faces[:,c]] += n`
+ *                          does not accumulate over repeated indices, so for each corner c = 0, 1, 2 (in this order)
+ *                          only the LAST face (highest index) that has the vertex at corner c is added;
+ *   MP_NORMALS_ACCUMULATE  what its comments describe: every incident (face, corner) is added, in ascending
+ *                          (face index, corner) order (numpy's np.add.at), bit for bit and independent of the run.
+ * A vertex no face references gets (0, 0, 0). */
+enum { MP_NORMALS_REFERENCE = 0, MP_NORMALS_ACCUMULATE = 1 };
+/* verts f32 [max_verts,3], faces int32 [max_faces,3]; counts (device int32[2]) = vertices and faces present, as
+ * mp_marching_cubes writes them: only min(counts[0], max_verts) vertices and min(counts[1], max_faces) faces are
+ * read / written (rows of `normals` beyond them are left untouched).  normals f32 [max_verts,3].  A face with an
+ * index outside [0, vertices) is skipped (never read out of bounds).  Asynchronous; no float atomics. */
+int mp_mesh_normals(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                    const int32_t *counts, int mode, float *normals, mp_stream stream);
+/* verts [max_verts,3] -> points [3,max_verts] (the layout mp_query_counted reads, capacity = max_verts) for the
+ * first min(counts[0], max_verts) vertices, and count_out (device int32[1]) = that number: the per-vertex colour
+ * query of a marching-cubes mesh without a host round trip. */
+int mp_mesh_points(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *counts, float *points,
+                   int32_t *count_out, mp_stream stream);
+
 /* ---- encoder helpers (stand-alone GroupNorm / upsample / concat kernels -- the
  * convolutions are the mp_conv* entry points below, nothing of the inference path is left on MIOpen) ---------- */
 /* y = [relu](GroupNorm(groups, C)(x)): x, y [N,C,HW] f32 (contiguous NCHW), gamma/beta [C];

@@ -87,6 +87,8 @@ class PlanWaitArgs(ctypes.Structure):
 PLAN_CONVK, PLAN_GN_APPLY, PLAN_CONV3X3, PLAN_CONV1X1, PLAN_AVGPOOL2, PLAN_UPSAMPLE2X, PLAN_MEMSET, PLAN_WAIT = range(1, 9)
 # MP_PROJ_* projection modes (include/monoport_hip.h)
 PROJ_ORTHOGONAL, PROJ_PERSPECTIVE = 0, 1
+# MP_NORMALS_* modes of mp_mesh_normals (include/monoport_hip.h)
+NORMALS_REFERENCE, NORMALS_ACCUMULATE = 0, 1
 MAX_VIEWS = 8  # MP_MAX_VIEWS: views per mp_query_views / mp_mlp_forward_views call
 
 # name -> (restype, argtypes); kept in one table so tests can check the exported surface against
@@ -159,6 +161,8 @@ SIGNATURES = {
     "mp_visualize": (c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
     "mp_marching_cubes": (c_int, [c_vp, c_vp, c_int, c_f32, _pf32, _pf32, c_vp, c_i64, c_vp, c_i64,
                                   c_vp, c_vp]),
+    "mp_mesh_normals": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_vp, c_vp]),
+    "mp_mesh_points": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mp_group_norm": (c_int, [c_vp, c_vp, c_int, c_int, c_i64, c_int, c_vp, c_vp, c_f32, c_int, c_vp,
                               c_vp]),
     "mp_upsample_bicubic2x": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),

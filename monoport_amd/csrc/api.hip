@@ -1059,6 +1059,33 @@ int mp_marching_cubes(mp_ctx *ctx, const float *volume, int r, float level, cons
                                faces, max_faces, counts, (hipStream_t)stream);
 }
 
+int mp_mesh_normals(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                    const int32_t *counts, int mode, float *normals, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!counts || max_verts < 0 || max_faces < 0 || (max_verts > 0 && (!verts || !normals)) ||
+      (max_faces > 0 && !faces) || (mode != MP_NORMALS_REFERENCE && mode != MP_NORMALS_ACCUMULATE))
+    return fail(ctx, MP_ERR_ARG, "mp_mesh_normals: bad argument");
+  if (max_verts > 0x7fffffffLL / 3 || max_faces > 0x7fffffffLL / 3)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_mesh_normals: capacities beyond 2^31 / 3 need 64-bit indices");
+  DeviceGuard g(ctx->device);
+  void *scratch = nullptr;
+  int rc = ensure_scratch(ctx, (hipStream_t)stream, mesh_normals_scratch_bytes(max_verts, max_faces), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_mesh_normals(ctx, scratch, verts, max_verts, faces, max_faces, counts, mode, normals,
+                             (hipStream_t)stream);
+}
+
+int mp_mesh_points(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *counts, float *points,
+                   int32_t *count_out, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!counts || !count_out || max_verts < 0 || (max_verts > 0 && (!verts || !points)))
+    return fail(ctx, MP_ERR_ARG, "mp_mesh_points: bad argument");
+  DeviceGuard g(ctx->device);
+  return launch_mesh_points(ctx, verts, max_verts, counts, points, count_out, (hipStream_t)stream);
+}
+
 int mp_group_norm(mp_ctx *ctx, const float *x, int n, int c, int64_t hw, int groups,
                   const float *gamma, const float *beta, float eps, int relu, float *y,
                   mp_stream stream) {

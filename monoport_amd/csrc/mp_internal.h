@@ -348,6 +348,12 @@ size_t mc_scratch_bytes(int r);
 int launch_marching_cubes(mp_ctx *ctx, void *scratch, const float *vol, int r, float level,
                           const float *bmin, const float *bmax, float *verts, long long max_v,
                           int32_t *faces, long long max_f, int32_t *counts, hipStream_t st);
+// mesh.hip
+size_t mesh_normals_scratch_bytes(long long max_v, long long max_f);
+int launch_mesh_normals(mp_ctx *ctx, void *scratch, const float *verts, long long max_v, const int32_t *faces,
+                        long long max_f, const int32_t *counts, int mode, float *normals, hipStream_t st);
+int launch_mesh_points(mp_ctx *ctx, const float *verts, long long max_v, const int32_t *counts, float *points,
+                       int32_t *count_out, hipStream_t st);
 
 // conv3x3.hip
 int launch_conv3x3_pack(mp_ctx *ctx, const float *w, int cout, int cin, float *wp, hipStream_t st);

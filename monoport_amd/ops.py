@@ -1079,6 +1079,57 @@ def marching_cubes_raw(volume, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), m
     return verts, faces, counts
 
 
+# MP_NORMALS_* (include/monoport_hip.h): what the reference's compute_normal computes / what its comments describe
+NORMALS_MODES = {"reference": _lib.NORMALS_REFERENCE, "accumulate": _lib.NORMALS_ACCUMULATE}
+
+
+def _normals_mode(mode):
+    if isinstance(mode, str):
+        if mode not in NORMALS_MODES:
+            raise ValueError("normals mode must be one of %s, got %r" % (sorted(NORMALS_MODES), mode))
+        return NORMALS_MODES[mode]
+    return int(mode)
+
+
+def _mesh_buffers(verts, faces, counts):
+    if verts.dtype != torch.float32 or verts.dim() != 2 or verts.shape[1] != 3 or not verts.is_contiguous():
+        raise ValueError("verts must be a contiguous [V,3] float32 tensor")
+    if faces is not None and (faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3
+                              or not faces.is_contiguous()):
+        raise ValueError("faces must be a contiguous [F,3] int32 tensor")
+    if counts.dtype != torch.int32 or counts.numel() < 2 or not counts.is_contiguous():
+        raise ValueError("counts must be a contiguous int32 tensor of (vertices, faces)")
+    for t in (faces, counts):
+        if t is not None and t.device != verts.device:
+            raise ValueError("verts, faces and counts must live on one device")
+
+
+def mesh_normals_raw(verts, faces, counts, mode="accumulate", out=None):
+    """mp_mesh_normals: verts [max_v,3] f32, faces [max_f,3] int32, counts int32[2] on device (as
+    ``marching_cubes_raw`` returns them) -> normals [max_v,3] f32; rows beyond counts[0] are not written.
+    No host sync."""
+    _mesh_buffers(verts, faces, counts)
+    ctx = get_context(verts.device)
+    if out is None:
+        out = torch.empty_like(verts)
+    ctx.check(ctx.lib.mp_mesh_normals(ctx.handle, _ptr(verts), verts.shape[0], _ptr(faces), faces.shape[0],
+                                      _ptr(counts), _normals_mode(mode), _ptr(out), _stream(verts)),
+              "mp_mesh_normals")
+    return out
+
+
+def mesh_points_raw(verts, counts):
+    """mp_mesh_points: verts [max_v,3] -> (points [3,max_v], count int32[1] = min(counts[0], max_v)) on device,
+    the operands of ``query_counted``.  No host sync."""
+    _mesh_buffers(verts, None, counts)
+    ctx = get_context(verts.device)
+    pts = torch.zeros((3, verts.shape[0]), dtype=torch.float32, device=verts.device)
+    count = torch.empty((1,), dtype=torch.int32, device=verts.device)
+    ctx.check(ctx.lib.mp_mesh_points(ctx.handle, _ptr(verts), verts.shape[0], _ptr(counts), _ptr(pts),
+                                     _ptr(count), _stream(verts)), "mp_mesh_points")
+    return pts, count
+
+
 def group_norm(x, groups, weight, bias, eps=1e-5, relu=False):
     """[relu](GroupNorm(x)) for x [N,C,H,W] f32 contiguous on the GPU (mp_group_norm)."""
     ctx = get_encoder_context(x.device)

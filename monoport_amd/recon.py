@@ -1,5 +1,7 @@
 """Drop-ins for RTL/recon.py (``pifu_calib``, ``forward_vertices``) and for the colorization
 closure of RTL/main.py:201-249, on top of the HIP kernels in csrc/vertices.hip."""
+import collections
+
 import numpy as np
 import torch
 
@@ -112,6 +114,58 @@ def marching_cubes(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1)):
         verts, faces, counts = ops.marching_cubes_raw(sdf, level, b_min, b_max, max_verts=nv,
                                                       max_faces=nf)
     return verts[:nv], faces[:nf]
+
+
+Mesh = collections.namedtuple("Mesh", ["verts", "faces", "normals", "colors"])
+Mesh.__doc__ = """Triangle mesh of ``reconstruct_mesh``: verts [V,3] f32 world coordinates, faces [F,3] int32,
+normals [V,3] f32 or None, colors [V,3] f32 in [0,1] or None."""
+
+
+def _mesh_chain(sdf, level, b_min, b_max, normals, binding, max_verts=None, max_faces=None):
+    """volume -> verts, faces -> normals -> colours, enqueued without a host value in between."""
+    verts, faces, counts = ops.marching_cubes_raw(sdf, level, b_min, b_max, max_verts=max_verts,
+                                                  max_faces=max_faces)
+    nrm = ops.mesh_normals_raw(verts, faces, counts, normals) if normals is not None else None
+    col = None
+    if binding is not None:
+        pts, count = ops.mesh_points_raw(verts, counts)
+        if binding.projection == ops.PROJECTIONS["orthogonal"]:
+            preds = ops.query_counted(binding.mlp, binding.feat_hwc, pts, count, binding.calib, binding.z_scale)
+        else:  # a perspective netC: the counted launch with its projection mode
+            preds = ops.query_counted_batch(binding.mlp, [binding.feat_hwc], [pts], [count], [binding.calib],
+                                            binding.z_scale, projections=[binding.projection])[0]
+        col = (preds * 0.5 + 0.5).t()
+    return verts, faces, counts, nrm, col
+
+
+@torch.no_grad()
+def reconstruct_mesh(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normals="accumulate", netC=None,
+                     feat_tensor_C=None, calib_tensor=None):
+    """The finished mesh of an occupancy volume [1,1,D,H,W] (or [D,H,W]) as one device chain: marching cubes,
+    per-vertex normals (``normals``: "accumulate", "reference" -- mesh_util.compute_normal's two modes -- or
+    None to skip them) and, with ``netC``, per-vertex colours netC.query(vertices) * 0.5 + 0.5 as
+    ``mesh_util.vertex_colors`` gives them.  Returns a ``Mesh``; None for ``sdf is None``.  One host sync
+    per mesh (the two counts, read after everything is enqueued); if a capacity guess was short the chain
+    runs once more with exact capacities.  A multi-view ``netC`` is not served here."""
+    if sdf is None:
+        return None
+    if normals is not None and normals not in ops.NORMALS_MODES:
+        raise ValueError("normals must be None or one of %s, got %r" % (sorted(ops.NORMALS_MODES), normals))
+    binding = None
+    if netC is not None:
+        if netC.surface_classifier.num_views > 1:
+            raise NotImplementedError("reconstruct_mesh: netC has num_views = %d; colour the vertices of a "
+                                      "multi-view head with mesh_util.vertex_colors"
+                                      % netC.surface_classifier.num_views)
+        device = sdf.device
+        feat_tensor_C = [[f.to(device) for f in feats] for feats in feat_tensor_C]
+        binding = netC.bind(feat_tensor_C, calib_tensor)
+    verts, faces, counts, nrm, col = _mesh_chain(sdf, level, b_min, b_max, normals, binding)
+    nv, nf = (int(c) for c in counts.cpu())
+    if nv > verts.shape[0] or nf > faces.shape[0]:
+        verts, faces, counts, nrm, col = _mesh_chain(sdf, level, b_min, b_max, normals, binding, nv, nf)
+    return Mesh(verts[:nv], faces[:nf], None if nrm is None else nrm[:nv],
+                None if col is None else col[:nv].contiguous())
 
 
 @torch.no_grad()

@@ -284,3 +284,36 @@ def obj_mesh_inputs():
     f = rng.randint(0, 500, size=(900, 3)).astype(np.int32)
     c = rng.rand(500, 3).astype(np.float32)
     return v, f, c
+
+
+def normals_soup_mesh():
+    """``obj_mesh_inputs()`` (random triangle soup: a vertex twice in one face, huge and tiny coordinates,
+    unreferenced vertices) plus the cases the per-vertex normals must get exactly right: degenerate faces
+    ``[i,i,j]`` and ``[i,i,i]``, three exactly collinear points (zero-area faces have the normal 0), four
+    vertices no face names, and a fan of 200 faces around one vertex.  Returns (verts [708,3] f32,
+    faces [1105,3] int32, index of the fan's centre)."""
+    v, f, _ = obj_mesh_inputs()
+    rng = np.random.RandomState(4343)
+    n0 = v.shape[0]
+    line = np.array([[0.0, 0.0, 0.0], [1.0, 2.0, 4.0], [2.0, 4.0, 8.0]], np.float32)  # n0 .. n0+2: collinear
+    lonely = rng.standard_normal((4, 3)).astype(np.float32)                             # n0+3 .. n0+6: unreferenced
+    ang = np.linspace(0.0, 2.0 * np.pi, 200, endpoint=False)
+    rim = np.stack([np.cos(ang), np.sin(ang), 0.3 * rng.standard_normal(200)], 1).astype(np.float32)
+    centre = n0 + 7
+    v = np.concatenate([v, line, lonely, np.array([[0.0, 0.0, 0.5]], np.float32), rim]).astype(np.float32)
+    r0 = centre + 1
+    fan = np.array([[centre, r0 + k, r0 + (k + 1) % 200] for k in range(200)], np.int32)
+    fan[1::3] = fan[1::3][:, [2, 0, 1]]  # the centre sits at every corner position
+    fan[2::3] = fan[2::3][:, [1, 2, 0]]
+    degenerate = np.array([[1, 1, 2], [3, 3, 3], [n0, n0 + 1, n0 + 2], [n0 + 2, n0, n0 + 1], [centre, centre, r0]],
+                          np.int32)
+    return v, np.concatenate([f, degenerate, fan[rng.permutation(200)]]).astype(np.int32), centre
+
+
+def sphere_volume(res, radius=0.6, sharp=8.0):
+    """Occupancy-like volume [res,res,res] f32 of a sphere about the origin of the [-1,1]^3 box (sigmoid of the
+    signed distance): a surface whose true normal is the radial direction."""
+    g = ((np.arange(res) + 0.5) / res) * 2 - 1
+    z, y, x = np.meshgrid(g, g, g, indexing="ij")
+    d = np.sqrt(x * x + y * y + z * z)
+    return (1.0 / (1.0 + np.exp(-sharp * (radius - d) / radius))).astype(np.float32)
