@@ -90,6 +90,7 @@ PROJ_ORTHOGONAL, PROJ_PERSPECTIVE = 0, 1
 # MP_NORMALS_* modes of mp_mesh_normals (include/monoport_hip.h)
 NORMALS_REFERENCE, NORMALS_ACCUMULATE = 0, 1
 MAX_VIEWS = 8  # MP_MAX_VIEWS: views per mp_query_views / mp_mlp_forward_views call
+MAX_FRAMES = 32  # kMaxFrames (csrc/mp_internal.h) = mp_max_frames(): frames per batched query / recon call
 
 # name -> (restype, argtypes); kept in one table so tests can check the exported surface against
 # the header (tests/test_abi.py)

@@ -117,6 +117,156 @@ static int check_projection(mp_ctx *ctx, const char *who, const int *proj, int n
   return MP_OK;
 }
 
+// ---- the argument checks and marshalling the query / recon entry points share ----------------------------------
+// Every check refuses before anything is launched or allocated; `who` is the entry point's name in the message.
+
+// Prologue of an entry point that evaluates a head: context, lock, the head exists, is loaded and was built for `c`
+// feature channels.  The lock is held while the object lives.  `who` != nullptr (mp_mlp_forward*: no feature map):
+// the head's own width is taken, and an unknown id is reported under that name.
+struct HeadCall {
+  std::unique_lock<std::mutex> lk;
+  const Mlp *m = nullptr;
+  int rc = MP_ERR_ARG;
+  HeadCall(mp_ctx *ctx, int mlp, int c, const char *who = nullptr) {
+    if (!ctx) return;
+    lk = std::unique_lock<std::mutex>(ctx->mu);
+    m = get_mlp(ctx, mlp);
+    if (who && !m)
+      rc = fail(ctx, MP_ERR_ARG, "%s: unknown mlp id %d", who, mlp);
+    else
+      rc = check_ready(ctx, m, who ? m->c : c);
+  }
+};
+
+static int bad_argument(mp_ctx *ctx, const char *who) { return fail(ctx, MP_ERR_ARG, "%s: bad argument", who); }
+
+// 1..max frames (MP_ERR_ARG) / views (MP_ERR_UNSUPPORTED) per call
+static int check_count(mp_ctx *ctx, const char *who, const char *what, int n, int max, int code) {
+  if (n < 1 || n > max) return fail(ctx, code, "%s: 1..%d %ss per call, got %d", who, max, what, n);
+  return MP_OK;
+}
+
+// The n items of a call's host arrays, one per frame / view (`what`): every device map set and 16-byte aligned (the
+// kernels read texels as float4), every item of the `other` arrays set; an array passed as nullptr is one this call
+// does not read.  The arrays themselves and the map size are part of the caller's own "bad argument" line, which keeps
+// each entry point's order of refusals.
+template <class... P>
+static int check_maps(mp_ctx *ctx, const char *who, const char *what, int n, const float *const *maps, P... other) {
+  for (int i = 0; i < n; ++i) {
+    if (!maps[i] || (... || (other && !other[i])))
+      return fail(ctx, MP_ERR_ARG, "%s: null buffer for %s %d", who, what, i);
+    if (!aligned16(maps[i])) return fail(ctx, MP_ERR_ARG, "%s: feat_hwc must be 16-byte aligned", who);
+  }
+  return MP_OK;
+}
+
+static int check_f32_views(mp_ctx *ctx, const char *who, const Mlp *m) {
+  if (m->precision != MP_PREC_F32)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: the multi-view kernel is f32 only (head precision %d)", who,
+                m->precision);
+  return MP_OK;
+}
+
+static int check_final_level(mp_ctx *ctx, const char *who, int final_level) {
+  if (final_level != MP_FINAL_DILATE3 && final_level != MP_FINAL_UPSTREAM && final_level != MP_FINAL_INTERPOLATE)
+    return fail(ctx, MP_ERR_ARG, "%s: final_level must be MP_FINAL_DILATE3 / _UPSTREAM / _INTERPOLATE, got %d", who,
+                final_level);
+  return MP_OK;
+}
+
+// `code`: MP_ERR_UNSUPPORTED from the single-view family, MP_ERR_ARG from mp_recon_views (include/monoport_hip.h)
+static int check_resolutions(mp_ctx *ctx, const char *who, const int *resolutions, int n_levels, int code) {
+  for (int l = 0; l < n_levels; ++l) {
+    if (resolutions[l] < 2 || resolutions[l] > 1023)
+      return fail(ctx, code, "%s: resolution %d outside [2,1023]", who, resolutions[l]);
+    if (l > 0 && resolutions[l] != 2 * resolutions[l - 1] - 1)
+      return fail(ctx, code, "%s: resolutions must follow r -> 2r-1 (got %d after %d)", who, resolutions[l],
+                  resolutions[l - 1]);
+  }
+  return MP_OK;
+}
+
+// `field`: how the entry point's message names the first of the two buffers
+static int check_early(mp_ctx *ctx, const char *who, const mp_recon_early *early, const char *field) {
+  if (early && (!early->flags_dev || !early->flags_host))
+    return fail(ctx, MP_ERR_ARG, "%s: %s and flags_host are required", who, field);
+  return MP_OK;
+}
+
+// Point layouts of the explicit (non-lattice) query calls: element (c, i) at pts[i*sn + c*sc], output (o, i) at
+// out[o*n + i], n points counted on the host ...
+static PointSrc strided_points(const float *pts, long long n, long long sn, long long sc) {
+  PointSrc src;
+  std::memset(&src, 0, sizeof(src));
+  src.pts = pts;
+  src.sn = sn;
+  src.sc = sc;
+  src.n = n;
+  src.out_stride = n;
+  return src;
+}
+
+// ... or contiguous rows [rows,capacity] of which the first *count (device) are points
+static PointSrc counted_points(const float *pts, long long capacity, const int32_t *count) {
+  PointSrc src = strided_points(pts, 0, 1, capacity);
+  src.n_dev = count;
+  src.out_stride = capacity;
+  return src;
+}
+
+// n frames of one layout: frame f takes its points (and device count, if the layout has one) from points[f] / count[f]
+static QuerySet query_set(int n, const float *const *feat_hwc, const float *const *calib, const int *projection,
+                          const float *const *points, const int32_t *const *count, float *const *out,
+                          const PointSrc &layout) {
+  QuerySet set;
+  std::memset(&set, 0, sizeof(set));
+  set.n = n;
+  for (int f = 0; f < n; ++f) {
+    QueryItem &q = set.it[f];
+    q.feat = feat_hwc[f];
+    q.calib = calib[f];
+    q.proj = projection ? projection[f] : MP_PROJ_ORTHOGONAL;
+    q.out = out[f];
+    q.src = layout;
+    q.src.pts = points[f];
+    if (count) q.src.n_dev = count[f];
+  }
+  return set;
+}
+
+// nv views of n points in the layout of strided_points
+static ViewSetDev view_set(int nv, int projection, long long n, long long sn, long long sc) {
+  ViewSetDev set;
+  std::memset(&set, 0, sizeof(set));
+  set.nv = nv;
+  set.proj = projection;
+  set.n = n;
+  set.sn = sn;
+  set.sc = sc;
+  set.out_stride = n;
+  return set;
+}
+
+// What mp_recon_batch_proj (views == nullptr: n_frames frames with a projection each, NULL = orthogonal) and
+// mp_recon_views (one frame seen by views->nv maps with projection[0]) do once head, counts and maps are accepted.
+static int recon_checked(mp_ctx *ctx, const char *who, const Mlp &m, int n_frames, const float *const *feat_hwc, int h,
+                         int w, const float *const *calib, const int *projection, float z_scale, const float *b_min,
+                         const float *b_max, const int *resolutions, int n_levels, int resolution_code, float balance,
+                         int final_level, float *const *volume, int32_t *const *status, const mp_recon_early *early,
+                         const char *early_field, mp_stream stream, const ReconViews *views) {
+  int rc = check_final_level(ctx, who, final_level);
+  if (rc == MP_OK) rc = check_resolutions(ctx, who, resolutions, n_levels, resolution_code);
+  if (rc == MP_OK) rc = check_projection(ctx, who, projection, views ? 1 : n_frames);
+  if (rc == MP_OK) rc = check_early(ctx, who, early, early_field);
+  if (rc != MP_OK) return rc;
+  DeviceGuard g(ctx->device);
+  void *scratch = nullptr;
+  rc = ensure_scratch(ctx, (hipStream_t)stream, n_frames * recon_scratch_bytes(resolutions, n_levels), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_recon(ctx, scratch, m, n_frames, feat_hwc, h, w, calib, projection, z_scale, b_min, b_max, resolutions,
+                      n_levels, balance, final_level, volume, status, early, (hipStream_t)stream, views);
+}
+
 }  // namespace mp
 
 using namespace mp;
@@ -518,180 +668,105 @@ int mp_perspective(mp_ctx *ctx, const float *points, int64_t n, const float *cal
 int mp_query(mp_ctx *ctx, int mlp, const float *feat_hwc, int c, int h, int w, const float *points,
              int64_t n, int64_t stride_n, int64_t stride_c, const float *calib, float z_scale,
              float *out, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const Mlp *m = get_mlp(ctx, mlp);
-  int rc = check_ready(ctx, m, c);
-  if (rc != MP_OK) return rc;
+  HeadCall call(ctx, mlp, c);
+  if (call.rc != MP_OK) return call.rc;
   if (!feat_hwc || !calib || n < 0 || h <= 0 || w <= 0 || (n > 0 && (!points || !out)))
-    return fail(ctx, MP_ERR_ARG, "mp_query: bad argument");
-  if (!aligned16(feat_hwc)) return fail(ctx, MP_ERR_ARG, "mp_query: feat_hwc must be 16-byte aligned");
-  if (n == 0) return MP_OK;
-  PointSrc src;
-  std::memset(&src, 0, sizeof(src));
-  src.pts = points;
-  src.sn = stride_n;
-  src.sc = stride_c;
-  src.n = n;
-  src.out_stride = n;
+    return bad_argument(ctx, "mp_query");
+  const int rc = check_maps(ctx, "mp_query", "frame", 1, &feat_hwc);
+  if (rc != MP_OK || n == 0) return rc;
   DeviceGuard g(ctx->device);
-  return launch_query(ctx, *m, feat_hwc, h, w, calib, z_scale, src, out, n, (hipStream_t)stream);
+  return launch_query(ctx, *call.m, feat_hwc, h, w, calib, z_scale, strided_points(points, n, stride_n, stride_c), out,
+                      n, (hipStream_t)stream);
 }
 
 int mp_query_batch(mp_ctx *ctx, int mlp, int n_frames, const float *const *feat_hwc, int c, int h, int w,
                    const float *const *points, int64_t n, int64_t stride_n, int64_t stride_c,
                    const float *const *calib, const int *projection, float z_scale, float *const *out,
                    mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const Mlp *m = get_mlp(ctx, mlp);
-  int rc = check_ready(ctx, m, c);
+  const char *who = "mp_query_batch";
+  HeadCall call(ctx, mlp, c);
+  if (call.rc != MP_OK) return call.rc;
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
   if (rc != MP_OK) return rc;
-  if (n_frames < 1 || n_frames > kMaxFrames)
-    return fail(ctx, MP_ERR_ARG, "mp_query_batch: 1..%d frames per call, got %d", kMaxFrames, n_frames);
   if (!feat_hwc || !points || !calib || !projection || !out || n < 0 || h <= 0 || w <= 0)
-    return fail(ctx, MP_ERR_ARG, "mp_query_batch: bad argument");
-  rc = check_projection(ctx, "mp_query_batch", projection, n_frames);
-  if (rc != MP_OK) return rc;
-  QuerySet set;
-  std::memset(&set, 0, sizeof(set));
-  set.n = n_frames;
-  for (int f = 0; f < n_frames; ++f) {
-    if (!feat_hwc[f] || !calib[f] || (n > 0 && (!points[f] || !out[f])))
-      return fail(ctx, MP_ERR_ARG, "mp_query_batch: null buffer for frame %d", f);
-    if (!aligned16(feat_hwc[f]))
-      return fail(ctx, MP_ERR_ARG, "mp_query_batch: feat_hwc must be 16-byte aligned");
-    QueryItem &q = set.it[f];
-    q.feat = feat_hwc[f];
-    q.calib = calib[f];
-    q.proj = projection[f];
-    q.out = out[f];
-    q.src.pts = points[f];
-    q.src.sn = stride_n;
-    q.src.sc = stride_c;
-    q.src.n = n;
-    q.src.out_stride = n;
-  }
-  if (n == 0) return MP_OK;
+    return bad_argument(ctx, who);
+  rc = check_projection(ctx, who, projection, n_frames);
+  if (rc == MP_OK)
+    rc = check_maps(ctx, who, "frame", n_frames, feat_hwc, calib, n > 0 ? points : nullptr, n > 0 ? out : nullptr);
+  if (rc != MP_OK || n == 0) return rc;
   DeviceGuard g(ctx->device);
-  return launch_query_set(ctx, *m, set, h, w, z_scale, n * n_frames, false, (hipStream_t)stream);
+  return launch_query_set(ctx, *call.m,
+                          query_set(n_frames, feat_hwc, calib, projection, points, nullptr, out,
+                                    strided_points(nullptr, n, stride_n, stride_c)),
+                          h, w, z_scale, n * n_frames, false, (hipStream_t)stream);
 }
 
 int mp_mlp_forward(mp_ctx *ctx, int mlp, const float *feature, int64_t n, float *out,
                    mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const Mlp *m = get_mlp(ctx, mlp);
-  if (!m) return fail(ctx, MP_ERR_ARG, "mp_mlp_forward: unknown mlp id %d", mlp);
-  int rc = check_ready(ctx, m, m->c);
-  if (rc != MP_OK) return rc;
-  if (n < 0 || (n > 0 && (!feature || !out))) return fail(ctx, MP_ERR_ARG, "mp_mlp_forward: bad argument");
+  HeadCall call(ctx, mlp, 0, "mp_mlp_forward");
+  if (call.rc != MP_OK) return call.rc;
+  if (n < 0 || (n > 0 && (!feature || !out))) return bad_argument(ctx, "mp_mlp_forward");
   if (n == 0) return MP_OK;
-  PointSrc src;
-  std::memset(&src, 0, sizeof(src));
-  src.pts = feature;
-  src.sn = 1;
-  src.sc = n;
-  src.n = n;
-  src.out_stride = n;
   DeviceGuard g(ctx->device);
-  return launch_query(ctx, *m, /*feat_hwc=*/nullptr, 0, 0, /*calib=*/nullptr, 0.0f, src, out, n,
-                      (hipStream_t)stream);
+  return launch_query(ctx, *call.m, /*feat_hwc=*/nullptr, 0, 0, /*calib=*/nullptr, 0.0f,
+                      strided_points(feature, n, 1, n), out, n, (hipStream_t)stream);
 }
 
 int mp_query_views(mp_ctx *ctx, int mlp, int n_views, const float *const *feat_hwc, int c, int h, int w,
                    const float *const *points, int64_t n, int64_t stride_n, int64_t stride_c,
                    const float *const *calib, int projection, float z_scale, float *const *out,
                    mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const Mlp *m = get_mlp(ctx, mlp);
-  int rc = check_ready(ctx, m, c);
+  const char *who = "mp_query_views";
+  HeadCall call(ctx, mlp, c);
+  if (call.rc != MP_OK) return call.rc;
+  int rc = check_count(ctx, who, "view", n_views, kMaxViews, MP_ERR_UNSUPPORTED);
+  if (rc == MP_OK) rc = check_f32_views(ctx, who, call.m);
   if (rc != MP_OK) return rc;
-  if (n_views < 1 || n_views > kMaxViews)
-    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_query_views: 1..%d views per call, got %d", kMaxViews, n_views);
-  if (m->precision != MP_PREC_F32)
-    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_query_views: the multi-view kernel is f32 only (head precision %d)",
-                m->precision);
-  if (!feat_hwc || !points || !calib || !out || n < 0 || h <= 0 || w <= 0)
-    return fail(ctx, MP_ERR_ARG, "mp_query_views: bad argument");
-  rc = check_projection(ctx, "mp_query_views", &projection, 1);
-  if (rc != MP_OK) return rc;
-  ViewSetDev set;
-  std::memset(&set, 0, sizeof(set));
-  set.nv = n_views;
-  set.proj = projection;
-  set.n = n;
-  set.sn = stride_n;
-  set.sc = stride_c;
-  set.out_stride = n;
+  if (!feat_hwc || !points || !calib || !out || n < 0 || h <= 0 || w <= 0) return bad_argument(ctx, who);
+  rc = check_projection(ctx, who, &projection, 1);
+  if (rc == MP_OK)
+    rc = check_maps(ctx, who, "view", n_views, feat_hwc, calib, n > 0 ? points : nullptr, n > 0 ? out : nullptr);
+  if (rc != MP_OK || n == 0) return rc;
+  ViewSetDev set = view_set(n_views, projection, n, stride_n, stride_c);
   for (int v = 0; v < n_views; ++v) {
-    if (!feat_hwc[v] || !calib[v] || (n > 0 && (!points[v] || !out[v])))
-      return fail(ctx, MP_ERR_ARG, "mp_query_views: null buffer for view %d", v);
-    if (!aligned16(feat_hwc[v]))
-      return fail(ctx, MP_ERR_ARG, "mp_query_views: feat_hwc must be 16-byte aligned");
     set.feat[v] = feat_hwc[v];
     set.calib[v] = calib[v];
     set.pts[v] = points[v];
     set.out[v] = out[v];
   }
-  if (n == 0) return MP_OK;
   DeviceGuard g(ctx->device);
-  return launch_query_views(ctx, *m, set, h, w, z_scale, (hipStream_t)stream);
+  return launch_query_views(ctx, *call.m, set, h, w, z_scale, (hipStream_t)stream);
 }
 
 int mp_mlp_forward_views(mp_ctx *ctx, int mlp, int n_views, const float *feature, int64_t n, float *out,
                          mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const Mlp *m = get_mlp(ctx, mlp);
-  if (!m) return fail(ctx, MP_ERR_ARG, "mp_mlp_forward_views: unknown mlp id %d", mlp);
-  int rc = check_ready(ctx, m, m->c);
+  const char *who = "mp_mlp_forward_views";
+  HeadCall call(ctx, mlp, 0, who);
+  if (call.rc != MP_OK) return call.rc;
+  int rc = check_count(ctx, who, "view", n_views, kMaxViews, MP_ERR_UNSUPPORTED);
+  if (rc == MP_OK) rc = check_f32_views(ctx, who, call.m);
   if (rc != MP_OK) return rc;
-  if (n_views < 1 || n_views > kMaxViews)
-    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_mlp_forward_views: 1..%d views per call, got %d", kMaxViews, n_views);
-  if (m->precision != MP_PREC_F32)
-    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_mlp_forward_views: the multi-view kernel is f32 only (head precision %d)",
-                m->precision);
-  if (n < 0 || (n > 0 && (!feature || !out))) return fail(ctx, MP_ERR_ARG, "mp_mlp_forward_views: bad argument");
+  if (n < 0 || (n > 0 && (!feature || !out))) return bad_argument(ctx, who);
   if (n == 0) return MP_OK;
-  ViewSetDev set;
-  std::memset(&set, 0, sizeof(set));
-  set.nv = n_views;
-  set.n = n;
-  set.sn = 1;
-  set.sc = n;
-  set.out_stride = n;
-  for (int v = 0; v < n_views; ++v) set.pts[v] = feature + (long long)v * (m->c + 1) * n;
+  ViewSetDev set = view_set(n_views, /*projection=*/0, n, 1, n);
+  for (int v = 0; v < n_views; ++v) set.pts[v] = feature + (long long)v * (call.m->c + 1) * n;
   set.out[0] = out;
   DeviceGuard g(ctx->device);
-  return launch_query_views(ctx, *m, set, 0, 0, 0.0f, (hipStream_t)stream);
+  return launch_query_views(ctx, *call.m, set, 0, 0, 0.0f, (hipStream_t)stream);
 }
 
 int mp_query_counted(mp_ctx *ctx, int mlp, const float *feat_hwc, int c, int h, int w,
                      const float *points, int64_t capacity, const int32_t *count,
                      const float *calib, float z_scale, float *out, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const Mlp *m = get_mlp(ctx, mlp);
-  int rc = check_ready(ctx, m, c);
-  if (rc != MP_OK) return rc;
-  if (!feat_hwc || !calib || !count || capacity < 0 || h <= 0 || w <= 0 ||
-      (capacity > 0 && (!points || !out)))
-    return fail(ctx, MP_ERR_ARG, "mp_query_counted: bad argument");
-  if (!aligned16(feat_hwc))
-    return fail(ctx, MP_ERR_ARG, "mp_query_counted: feat_hwc must be 16-byte aligned");
-  if (capacity == 0) return MP_OK;
-  PointSrc src;
-  std::memset(&src, 0, sizeof(src));
-  src.pts = points;
-  src.sn = 1;
-  src.sc = capacity;
-  src.n_dev = count;
-  src.out_stride = capacity;
+  HeadCall call(ctx, mlp, c);
+  if (call.rc != MP_OK) return call.rc;
+  if (!feat_hwc || !calib || !count || capacity < 0 || h <= 0 || w <= 0 || (capacity > 0 && (!points || !out)))
+    return bad_argument(ctx, "mp_query_counted");
+  const int rc = check_maps(ctx, "mp_query_counted", "frame", 1, &feat_hwc);
+  if (rc != MP_OK || capacity == 0) return rc;
   DeviceGuard g(ctx->device);
-  return launch_query(ctx, *m, feat_hwc, h, w, calib, z_scale, src, out, capacity,
-                      (hipStream_t)stream);
+  return launch_query(ctx, *call.m, feat_hwc, h, w, calib, z_scale, counted_points(points, capacity, count), out,
+                      capacity, (hipStream_t)stream);
 }
 
 int mp_query_counted_batch(mp_ctx *ctx, int mlp, int n_frames, const float *const *feat_hwc, int c,
@@ -706,51 +781,22 @@ int mp_query_counted_batch_proj(mp_ctx *ctx, int mlp, int n_frames, const float 
                                 int h, int w, const float *const *points, int64_t capacity,
                                 const int32_t *const *count, const float *const *calib,
                                 const int *projection, float z_scale, float *const *out, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const Mlp *m = get_mlp(ctx, mlp);
-  int rc = check_ready(ctx, m, c);
+  const char *who = "mp_query_counted_batch";  // the name both entry points report under
+  HeadCall call(ctx, mlp, c);
+  if (call.rc != MP_OK) return call.rc;
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
   if (rc != MP_OK) return rc;
-  if (n_frames < 1 || n_frames > kMaxFrames)
-    return fail(ctx, MP_ERR_ARG, "mp_query_counted_batch: 1..%d frames per call, got %d", kMaxFrames,
-                n_frames);
   if (!feat_hwc || !points || !count || !calib || !out || capacity < 0 || h <= 0 || w <= 0)
-    return fail(ctx, MP_ERR_ARG, "mp_query_counted_batch: bad argument");
-  rc = check_projection(ctx, "mp_query_counted_batch", projection, n_frames);
+    return bad_argument(ctx, who);
+  rc = check_projection(ctx, who, projection, n_frames);
+  if (rc != MP_OK || capacity == 0) return rc;  // an empty call returns before its frames' buffers are looked at
+  rc = check_maps(ctx, who, "frame", n_frames, feat_hwc, points, count, calib, out);
   if (rc != MP_OK) return rc;
-  if (capacity == 0) return MP_OK;
-  QuerySet set;
-  std::memset(&set, 0, sizeof(set));
-  set.n = n_frames;
-  for (int f = 0; f < n_frames; ++f) {
-    if (!feat_hwc[f] || !points[f] || !count[f] || !calib[f] || !out[f])
-      return fail(ctx, MP_ERR_ARG, "mp_query_counted_batch: null buffer for frame %d", f);
-    if (!aligned16(feat_hwc[f]))
-      return fail(ctx, MP_ERR_ARG, "mp_query_counted_batch: feat_hwc must be 16-byte aligned");
-    QueryItem &q = set.it[f];
-    q.feat = feat_hwc[f];
-    q.calib = calib[f];
-    q.proj = projection ? projection[f] : MP_PROJ_ORTHOGONAL;
-    q.out = out[f];
-    q.src.pts = points[f];
-    q.src.sn = 1;
-    q.src.sc = capacity;
-    q.src.n_dev = count[f];
-    q.src.out_stride = capacity;
-  }
   DeviceGuard g(ctx->device);
-  return launch_query_set(ctx, *m, set, h, w, z_scale, capacity * n_frames, true, (hipStream_t)stream);
-}
-
-static int check_resolutions(mp_ctx *ctx, const char *who, const int *resolutions, int n_levels) {
-  for (int l = 0; l < n_levels; ++l) {
-    if (resolutions[l] < 2 || resolutions[l] > 1023)
-      return fail(ctx, MP_ERR_UNSUPPORTED, "%s: resolution %d outside [2,1023]", who, resolutions[l]);
-    if (l > 0 && resolutions[l] != 2 * resolutions[l - 1] - 1)
-      return fail(ctx, MP_ERR_UNSUPPORTED, "%s: resolutions must follow r -> 2r-1 (got %d after %d)",
-                  who, resolutions[l], resolutions[l - 1]);
-  }
-  return MP_OK;
+  return launch_query_set(ctx, *call.m,
+                          query_set(n_frames, feat_hwc, calib, projection, points, count, out,
+                                    counted_points(nullptr, capacity, nullptr)),
+                          h, w, z_scale, capacity * n_frames, true, (hipStream_t)stream);
 }
 
 int mp_recon_batch(mp_ctx *ctx, int mlp, int n_frames, const float *const *feat_hwc, int c, int h,
@@ -778,44 +824,26 @@ int mp_recon_batch_early(mp_ctx *ctx, int mlp, int n_frames, const float *const 
                              resolutions, n_levels, balance, final_level, volume, status, early, stream);
 }
 
+// mp_recon, mp_recon_batch, _ex and _early end here: all five report under this one's name
 int mp_recon_batch_proj(mp_ctx *ctx, int mlp, int n_frames, const float *const *feat_hwc, int c, int h,
                         int w, const float *const *calib, const int *projection, float z_scale,
                         const float *b_min, const float *b_max, const int *resolutions, int n_levels,
                         float balance, int final_level, float *const *volume, int32_t *const *status,
                         const mp_recon_early *early, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const Mlp *m = get_mlp(ctx, mlp);
-  int rc = check_ready(ctx, m, c);
+  const char *who = "mp_recon_batch_proj";
+  HeadCall call(ctx, mlp, c);
+  if (call.rc != MP_OK) return call.rc;
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
   if (rc != MP_OK) return rc;
-  if (n_frames < 1 || n_frames > kMaxFrames)
-    return fail(ctx, MP_ERR_ARG, "mp_recon_batch: 1..%d frames per call, got %d", kMaxFrames, n_frames);
-  if (!feat_hwc || !calib || !b_min || !b_max || !resolutions || !volume || !status ||
-      n_levels < 1 || n_levels > 8 || h <= 0 || w <= 0)
-    return fail(ctx, MP_ERR_ARG, "mp_recon: bad argument");
-  for (int f = 0; f < n_frames; ++f) {
-    if (!feat_hwc[f] || !calib[f] || !volume[f] || !status[f])
-      return fail(ctx, MP_ERR_ARG, "mp_recon: null buffer for frame %d", f);
-    if (!aligned16(feat_hwc[f]))
-      return fail(ctx, MP_ERR_ARG, "mp_recon: feat_hwc must be 16-byte aligned");
-  }
-  if (m->cout != 1) return fail(ctx, MP_ERR_ARG, "mp_recon: needs a 1-channel (occupancy) mlp");
-  if (final_level != MP_FINAL_DILATE3 && final_level != MP_FINAL_UPSTREAM && final_level != MP_FINAL_INTERPOLATE)
-    return fail(ctx, MP_ERR_ARG, "mp_recon: final_level must be MP_FINAL_DILATE3 / _UPSTREAM / _INTERPOLATE, got %d",
-                final_level);
-  rc = check_resolutions(ctx, "mp_recon", resolutions, n_levels);
+  if (!feat_hwc || !calib || !b_min || !b_max || !resolutions || !volume || !status || n_levels < 1 ||
+      n_levels > 8 || h <= 0 || w <= 0)
+    return bad_argument(ctx, who);
+  rc = check_maps(ctx, who, "frame", n_frames, feat_hwc, calib, volume, status);
   if (rc != MP_OK) return rc;
-  rc = check_projection(ctx, "mp_recon_batch_proj", projection, n_frames);
-  if (rc != MP_OK) return rc;
-  if (early && (!early->flags_dev || !early->flags_host))
-    return fail(ctx, MP_ERR_ARG, "mp_recon_batch_early: flags_dev and flags_host are required");
-  DeviceGuard g(ctx->device);
-  void *scratch = nullptr;
-  rc = ensure_scratch(ctx, (hipStream_t)stream, n_frames * recon_scratch_bytes(resolutions, n_levels),
-                      &scratch);
-  if (rc != MP_OK) return rc;
-  return launch_recon(ctx, scratch, *m, n_frames, feat_hwc, h, w, calib, projection, z_scale, b_min, b_max,
-                      resolutions, n_levels, balance, final_level, volume, status, early, (hipStream_t)stream);
+  if (call.m->cout != 1) return fail(ctx, MP_ERR_ARG, "%s: needs a 1-channel (occupancy) mlp", who);
+  return recon_checked(ctx, who, *call.m, n_frames, feat_hwc, h, w, calib, projection, z_scale, b_min, b_max,
+                       resolutions, n_levels, MP_ERR_UNSUPPORTED, balance, final_level, volume, status, early,
+                       "flags_dev", stream, nullptr);
 }
 
 int mp_recon_views(mp_ctx *ctx, int mlp, int n_views, const float *const *feat_hwc, int c, int h, int w,
@@ -823,49 +851,27 @@ int mp_recon_views(mp_ctx *ctx, int mlp, int n_views, const float *const *feat_h
                    const float *b_min, const float *b_max, const int *resolutions, int n_levels,
                    float balance, int final_level, int view, float *volume, int32_t *status,
                    const mp_recon_early *early, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  const Mlp *m = get_mlp(ctx, mlp);
-  int rc = check_ready(ctx, m, c);
+  const char *who = "mp_recon_views";
+  HeadCall call(ctx, mlp, c);
+  if (call.rc != MP_OK) return call.rc;
+  const Mlp *m = call.m;
+  int rc = check_count(ctx, who, "view", n_views, kMaxViews, MP_ERR_UNSUPPORTED);
+  if (rc == MP_OK) rc = check_f32_views(ctx, who, m);
   if (rc != MP_OK) return rc;
-  if (n_views < 1 || n_views > kMaxViews)
-    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_recon_views: 1..%d views per call, got %d", kMaxViews, n_views);
-  if (m->precision != MP_PREC_F32)
-    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_recon_views: the multi-view kernel is f32 only (head precision %d)",
-                m->precision);
   if (m->c != 256 || m->cout != 1)
-    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_recon_views: needs a netG head (C=256, 1 occupancy channel); got C=%d Cout=%d",
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: needs a netG head (C=256, 1 occupancy channel); got C=%d Cout=%d", who,
                 m->c, m->cout);
   if (view < 0 || view >= n_views)
-    return fail(ctx, MP_ERR_ARG, "mp_recon_views: view %d outside 0..%d", view, n_views - 1);
+    return fail(ctx, MP_ERR_ARG, "%s: view %d outside 0..%d", who, view, n_views - 1);
   if (!feat_hwc || !calib || !b_min || !b_max || !resolutions || !volume || !status || n_levels < 1 ||
       n_levels > 8 || h <= 0 || w <= 0)
-    return fail(ctx, MP_ERR_ARG, "mp_recon_views: bad argument");
-  for (int v = 0; v < n_views; ++v) {
-    if (!feat_hwc[v] || !calib[v]) return fail(ctx, MP_ERR_ARG, "mp_recon_views: null buffer for view %d", v);
-    if (!aligned16(feat_hwc[v])) return fail(ctx, MP_ERR_ARG, "mp_recon_views: feat_hwc must be 16-byte aligned");
-  }
-  if (final_level != MP_FINAL_DILATE3 && final_level != MP_FINAL_UPSTREAM && final_level != MP_FINAL_INTERPOLATE)
-    return fail(ctx, MP_ERR_ARG, "mp_recon_views: final_level must be MP_FINAL_DILATE3 / _UPSTREAM / _INTERPOLATE, got %d",
-                final_level);
-  for (int l = 0; l < n_levels; ++l) {
-    if (resolutions[l] < 2 || resolutions[l] > 1023)
-      return fail(ctx, MP_ERR_ARG, "mp_recon_views: resolution %d outside [2,1023]", resolutions[l]);
-    if (l > 0 && resolutions[l] != 2 * resolutions[l - 1] - 1)
-      return fail(ctx, MP_ERR_ARG, "mp_recon_views: resolutions must follow r -> 2r-1 (got %d after %d)",
-                  resolutions[l], resolutions[l - 1]);
-  }
-  rc = check_projection(ctx, "mp_recon_views", &projection, 1);
-  if (rc != MP_OK) return rc;
-  if (early && (!early->flags_dev || !early->flags_host))
-    return fail(ctx, MP_ERR_ARG, "mp_recon_views: early->flags_dev and flags_host are required");
-  DeviceGuard g(ctx->device);
-  void *scratch = nullptr;
-  rc = ensure_scratch(ctx, (hipStream_t)stream, recon_scratch_bytes(resolutions, n_levels), &scratch);
+    return bad_argument(ctx, who);
+  rc = check_maps(ctx, who, "view", n_views, feat_hwc, calib);
   if (rc != MP_OK) return rc;
   const ReconViews views = {n_views, view};
-  return launch_recon(ctx, scratch, *m, 1, feat_hwc, h, w, calib, &projection, z_scale, b_min, b_max, resolutions,
-                      n_levels, balance, final_level, &volume, &status, early, (hipStream_t)stream, &views);
+  return recon_checked(ctx, who, *m, 1, feat_hwc, h, w, calib, &projection, z_scale, b_min, b_max, resolutions,
+                       n_levels, MP_ERR_ARG, balance, final_level, &volume, &status, early, "early->flags_dev", stream,
+                       &views);
 }
 
 int mp_recon(mp_ctx *ctx, int mlp, const float *feat_hwc, int c, int h, int w, const float *calib,

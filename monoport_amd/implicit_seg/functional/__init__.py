@@ -47,7 +47,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from ...modeling.MonoPortNet import ViewsBinding, record_query
+from ...modeling.MonoPortNet import record_query
 from . import utils  # noqa: F401
 
 
@@ -175,7 +175,7 @@ class Seg3dLossless(nn.Module):
             occ0 = self.query_func(points=pts0[None], **kwargs)
         binding = rec.binding if rec.calls == 1 else None
         if binding is not None and self.faster:
-            self._check_view(binding)
+            binding.check_view(self.view)
             eng.scatter(occ0)  # the caller's values on the coarsest lattice, [r0,r0,r0]
             early = self._early_flags(dev)
             volume, status = self._recon(binding, early, eng.cur)
@@ -185,7 +185,7 @@ class Seg3dLossless(nn.Module):
             nonempty, differs = (int(v) for v in early.wait()[0])
             if differs == 0:
                 self.last_status, self.last_path = status, "fused"
-                key = self._binding_key(binding)
+                key = binding.trust_key(self.view)
                 self._agreed = self._agreed + 1 if key == self._trusted_key else 1
                 self._trusted_key = key
                 return None if nonempty == 0 else volume[None, None]
@@ -206,27 +206,11 @@ class Seg3dLossless(nn.Module):
     VALIDATE_CALLS = 3
     REVALIDATE_EVERY = 32  # a trusted query_func is validated again on every 32nd call
 
-    def _binding_key(self, binding):
-        if isinstance(binding, ViewsBinding):
-            return (id(binding.mlp), binding.mlp.precision, float(binding.z_scale), binding.num_views, self.view,
-                    binding.projection)
-        return (id(binding.mlp), binding.mlp.precision, float(binding.z_scale), binding.projection)
-
-    def _check_view(self, binding):
-        if isinstance(binding, ViewsBinding) and self.view >= binding.num_views:
-            raise ValueError("Seg3dLossless(view=%d): the head has %d views (rows 0..%d)"
-                             % (self.view, binding.num_views, binding.num_views - 1))
-
     def _recon(self, b, early=None, expect_level0=None):
         """The fused reconstruction of a recorded binding: one frame (ops.recon) or, with ``fuse_views``, the V
         views of one subject (ops.recon_views, row ``self.view``) -> (volume, status) on the device."""
-        if isinstance(b, ViewsBinding):
-            return ops.recon_views(b.mlp, b.maps, b.calibs, b.projection, b.z_scale, self.b_min[0], self.b_max[0],
-                                   self.resolutions, self.balance_value, final_level=self.final_level,
-                                   view=self.view, early=early, expect_level0=expect_level0)
-        return ops.recon(b.mlp, b.feat_hwc, b.calib, b.z_scale, self.b_min[0], self.b_max[0], self.resolutions,
-                         self.balance_value, final_level=self.final_level, early=early,
-                         expect_level0=expect_level0, projection=b.projection)
+        return b.recon(self.b_min[0], self.b_max[0], self.resolutions, self.balance_value, self.final_level,
+                       view=self.view, early=early, expect_level0=expect_level0)
 
     def _forward_trusted(self, kwargs):
         """A query_func whose last VALIDATE_CALLS calls were plain MonoPortNet.query calls agreeing
@@ -237,7 +221,7 @@ class Seg3dLossless(nn.Module):
         with record_query(capture_only=True, views=self.fuse_views) as rec:
             self.query_func(points=probe, **kwargs)
         b = rec.binding
-        if b is None or rec.calls != 1 or self._binding_key(b) != self._trusted_key:
+        if b is None or rec.calls != 1 or b.trust_key(self.view) != self._trusted_key:
             self._agreed, self._trusted_key = 0, None
             return NotImplemented
         early = self._early_flags(self._device_tag.device)
@@ -269,8 +253,8 @@ class Seg3dLossless(nn.Module):
                 self.query_func(points=probe, **kw)
             b = rec.binding
             # a multi-view binding is one point set per call (mp_recon_views): its frames go one by one
-            if (b is None or rec.calls != 1 or isinstance(b, ViewsBinding)
-                    or self._binding_key(b) != self._trusted_key):
+            if (b is None or rec.calls != 1 or not b.batchable
+                    or b.trust_key(self.view) != self._trusted_key):
                 return [self(**kw) for kw in kwargs_list]  # forward() re-validates
             bindings.append(b)
         b0 = bindings[0]
@@ -296,7 +280,7 @@ class Seg3dLossless(nn.Module):
         b = rec.binding
         if b is None:
             raise NotImplementedError("forward_async needs a query_func ending in MonoPortNet.query")
-        self._check_view(b)
+        b.check_view(self.view)
         return self._recon(b)
 
 

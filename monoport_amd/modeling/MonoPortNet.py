@@ -43,9 +43,24 @@ class QueryBinding:
     features + calibration + projection (ops.PROJECTIONS: MP_PROJ_*).  The octree engine records it once
     per frame and drives all levels natively."""
 
+    batchable = True  # the frames of several such bindings can share one ops.recon_batch call
+
     def __init__(self, net, mlp, feat_hwc, calib, z_scale, projection=ops.PROJECTIONS["orthogonal"]):
         self.net, self.mlp, self.feat_hwc, self.calib, self.z_scale = net, mlp, feat_hwc, calib, z_scale
         self.projection = projection
+
+    def trust_key(self, view=0):
+        """What must stay the same between calls for Seg3dLossless to keep trusting a validated ``query_func``."""
+        return (id(self.mlp), self.mlp.precision, float(self.z_scale), self.projection)
+
+    def check_view(self, view):
+        """One view: the engine's ``view`` is not looked at."""
+
+    def recon(self, b_min, b_max, resolutions, balance, final_level, view=0, early=None, expect_level0=None):
+        """The fused reconstruction of the bound frame (ops.recon) -> (volume, status) on the device."""
+        return ops.recon(self.mlp, self.feat_hwc, self.calib, self.z_scale, b_min, b_max, resolutions, balance,
+                         final_level=final_level, early=early, expect_level0=expect_level0,
+                         projection=self.projection)
 
 
 class ViewsBinding:
@@ -53,9 +68,25 @@ class ViewsBinding:
     set: packed MLP + the V views' channels-last maps + [V,4,4] calibrations + z scale + the one projection.  The
     octree engine records it (``record_query(views=True)``) and drives all levels through ops.recon_views."""
 
+    batchable = False  # one point set per call (mp_recon_views)
+
     def __init__(self, net, mlp, maps, calibs, z_scale, projection=ops.PROJECTIONS["orthogonal"]):
         self.net, self.mlp, self.maps, self.calibs, self.z_scale = net, mlp, maps, calibs, z_scale
         self.projection = projection
+
+    def trust_key(self, view=0):
+        return (id(self.mlp), self.mlp.precision, float(self.z_scale), self.num_views, view, self.projection)
+
+    def check_view(self, view):
+        if view >= self.num_views:
+            raise ValueError("Seg3dLossless(view=%d): the head has %d views (rows 0..%d)"
+                             % (view, self.num_views, self.num_views - 1))
+
+    def recon(self, b_min, b_max, resolutions, balance, final_level, view=0, early=None, expect_level0=None):
+        """The fused reconstruction of the V bound views (ops.recon_views, row ``view``) -> (volume, status)."""
+        return ops.recon_views(self.mlp, self.maps, self.calibs, self.projection, self.z_scale, b_min, b_max,
+                               resolutions, balance, final_level=final_level, view=view, early=early,
+                               expect_level0=expect_level0)
 
     @property
     def num_views(self):
@@ -158,30 +189,36 @@ class MonoPortNet(nn.Module):
         ``n_points``: how many points the caller is about to query; ``for_engine``: the caller is
         the octree engine (a whole reconstruction follows) -- both feed the decision whether the
         map gets a skip table (``_skip_table``)."""
-        if self.training:
-            raise NotImplementedError("monoport_amd implements the inference path (net.eval())")
         if self.surface_classifier.num_views > 1:
             # a binding is one frame on the single-view kernels (octree engine, skip tables, colour queries); a
             # multi-view head runs through query() only
             raise NotImplementedError("bind(): the head has num_views = %d; multi-view heads are served by query() "
                                       "(mp_query_views), not by the single-view engines" % self.surface_classifier.num_views)
+        feats, calibs, projection, mlp = self._bind_common(feats_stages, calibs)
+        if calibs.dim() == 3:  # [B,4,4]; one [4,4] (or none: the identity) serves every frame
+            calibs = calibs[frame:frame + 1]
+        packed = self._packed_features(feats, frame)
+        self._skip_table(mlp, packed, int(n_points), for_engine)
+        return QueryBinding(self, mlp, packed, calibs, self.normalizer.scale, projection)
+
+    def _bind_common(self, feats_stages, calibs):
+        """What ``bind`` and ``bind_views`` share -> (last stage's maps, calibs, projection, packed head): eval mode
+        only; no calibration = identity under the orthogonal projection; head and maps on one GPU."""
+        if self.training:
+            raise NotImplementedError("monoport_amd implements the inference path (net.eval())")
         feats = list(feats_stages[-1])  # eval keeps the last stage only (MonoPortNet.py:63-64)
         dev = feats[0].device
         if calibs is None:
             # xyz = points (MonoPortNet.py:66-67): no projection at all, whatever opt_net.projection says
-            calibs = torch.eye(4, device=dev)[None]
+            calibs = torch.eye(4, device=dev)
             projection = ops.PROJECTIONS["orthogonal"]
         else:
-            if calibs.dim() == 3:
-                calibs = calibs[frame:frame + 1]
             projection = ops.PROJECTIONS["perspective" if self.projection is perspective else "orthogonal"]
         mlp = self.surface_classifier.packed()
         if mlp.ctx.device_index != (dev.index if dev.index is not None else torch.cuda.current_device()):
             raise RuntimeError("surface_classifier and the feature maps must be on one GPU "
                                "(RTL/main.py:382-387 moves the features first)")
-        packed = self._packed_features(feats, frame)
-        self._skip_table(mlp, packed, int(n_points), for_engine)
-        return QueryBinding(self, mlp, packed, calibs, self.normalizer.scale, projection)
+        return feats, calibs, projection, mlp
 
     def _skip_table(self, mlp, packed, n_points=0, for_engine=True):
         """The skip table of the bound feature map (ops.skip_table: the MLP's products with the
@@ -316,30 +353,18 @@ class MonoPortNet(nn.Module):
     def bind_views(self, feats_stages, calibs):
         """ViewsBinding for eval-mode queries of a multi-view head (num_views = V > 1) against the V views of
         ``feats_stages`` (batch V) / ``calibs`` ([V,4,4], one [4,4] for all views, or None).  No skip tables."""
-        if self.training:
-            raise NotImplementedError("monoport_amd implements the inference path (net.eval())")
         v_n = self.surface_classifier.num_views
         if v_n <= 1:
             raise NotImplementedError("bind_views(): the head has num_views = %d; single-view heads bind through "
                                       "bind()" % v_n)
-        feats = list(feats_stages[-1])  # eval keeps the last stage only (MonoPortNet.py:63-64)
-        if any(f.shape[0] != v_n for f in feats) or (calibs is not None and calibs.dim() == 3
+        if any(f.shape[0] != v_n for f in feats_stages[-1]) or (calibs is not None and calibs.dim() == 3
                                                       and calibs.shape[0] != v_n):
             raise ValueError("bind_views: %d views, feature maps of batch %s, calibrations %s"
-                             % (v_n, [f.shape[0] for f in feats], None if calibs is None else tuple(calibs.shape)))
-        dev = feats[0].device
-        if calibs is None:
-            # xyz = points for every view (MonoPortNet.py:66-67)
-            calibs = torch.eye(4, device=dev)[None].expand(v_n, 4, 4)
-            projection = ops.PROJECTIONS["orthogonal"]
-        else:
-            if calibs.dim() == 2:
-                calibs = calibs[None].expand(v_n, *calibs.shape)
-            projection = ops.PROJECTIONS["perspective" if self.projection is perspective else "orthogonal"]
-        mlp = self.surface_classifier.packed()
-        if mlp.ctx.device_index != (dev.index if dev.index is not None else torch.cuda.current_device()):
-            raise RuntimeError("surface_classifier and the feature maps must be on one GPU "
-                               "(RTL/main.py:382-387 moves the features first)")
+                             % (v_n, [f.shape[0] for f in feats_stages[-1]],
+                                None if calibs is None else tuple(calibs.shape)))
+        feats, calibs, projection, mlp = self._bind_common(feats_stages, calibs)
+        if calibs.dim() == 2:  # one calibration (or none: the identity) for every view
+            calibs = calibs[None].expand(v_n, *calibs.shape)
         maps = [self._packed_features(feats, v) for v in range(v_n)]
         return ViewsBinding(self, mlp, maps, calibs, self.normalizer.scale, projection)
 

@@ -25,6 +25,7 @@ class Context:
 
     def __init__(self, device_index):
         self.lib = _lib.load()
+        assert self.lib.mp_max_frames() == MAX_FRAMES, "_lib.MAX_FRAMES and the library's kMaxFrames disagree"
         self.device_index = int(device_index)
         handle = ctypes.c_void_p()
         rc = self.lib.mp_create(self.device_index, ctypes.byref(handle))
@@ -76,6 +77,89 @@ def _f32c(t):
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
+
+
+# ---- argument checks and marshalling shared by the wrappers below (no context needed: CPU tensors pass them too) ----
+MAX_FRAMES = _lib.MAX_FRAMES  # kMaxFrames: frames per mp_recon_batch / mp_query_batch / mp_query_counted_batch call
+MAX_VIEWS = _lib.MAX_VIEWS  # MP_MAX_VIEWS
+
+
+def _float3(v):
+    """Three numbers (sequence, array, tensor) -> the float[3] the C side reads."""
+    return (ctypes.c_float * 3)(*[float(x) for x in np.asarray(v, np.float32).reshape(3)])
+
+
+def _ptr_array(tensors):
+    """The host array of device addresses a batched entry point takes: one per tensor (of a tensor: per row), NULL
+    for None."""
+    return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _cubic_volume(t, who):
+    """[...,R,R,R] with leading dimensions of size 1 (the engines return [1,1,R,R,R]) -> contiguous f32 [R,R,R]."""
+    while t.dim() > 3:
+        t = t[0]
+    if t.dim() != 3 or t.shape[0] != t.shape[1] or t.shape[1] != t.shape[2]:
+        raise ValueError("%s wants a cubic volume, got %s" % (who, tuple(t.shape)))
+    return _f32c(t)
+
+
+def _check_count(who, what, n, most):
+    if not 1 <= n <= most:
+        raise ValueError("%s: 1..%d %s per call, got %d" % (who, most, what, n))
+
+
+def _calib_list(calibs, n, who):
+    """n calibrations given as a sequence or as one [n,>=3,4] tensor -> the list of them."""
+    if torch.is_tensor(calibs) and calibs.dim() == 3:
+        calibs = list(calibs)
+    if len(calibs) != n:
+        raise ValueError("%s: %d maps, %d calibrations" % (who, n, len(calibs)))
+    return calibs
+
+
+def _maps(who, maps):
+    """Channels-last maps of one call -> (h, w, c, device); all contiguous float32 [h,w,c]."""
+    if len(maps) == 0 or maps[0].dim() != 3:
+        raise ValueError("%s: wants a non-empty list of [H,W,C] maps" % who)
+    h, w, c = maps[0].shape
+    for f in maps:
+        if tuple(f.shape) != (h, w, c) or not f.is_contiguous() or f.dtype != torch.float32:
+            raise ValueError("%s: the maps must be contiguous float32 [%d,%d,%d]" % (who, h, w, c))
+    return h, w, c, maps[0].device
+
+
+def _out_rows(who, out, n, cout, npts):
+    """A caller's result buffer of a batched query: float32 [n,cout,npts] whose rows are each contiguous."""
+    if (tuple(out.shape) != (n, cout, npts) or out.dtype != torch.float32
+            or (npts > 0 and not all(o.is_contiguous() for o in out))):
+        raise ValueError("%s: out must be float32 [%d,%d,%d] with contiguous rows" % (who, n, cout, npts))
+
+
+def _early_arg(who, early, n, expect, r0):
+    """``early`` (EarlyFlags or None) + ``expect`` (n level-0 volumes [r0,r0,r0] f32, None entries allowed; or None)
+    -> the mp_recon_early* argument.  ``early`` keeps the pointer array alive, the argument the struct."""
+    if early is None:
+        return None
+    if early.n != n:
+        raise ValueError("%s: EarlyFlags for %d frames, the call has %d" % (who, early.n, n))
+    if expect is not None:
+        if len(expect) != n:
+            raise ValueError("%s: %d frames, %d expected level-0 volumes" % (who, n, len(expect)))
+        for e in expect:
+            if e is not None and (e.numel() != r0 ** 3 or not e.is_contiguous() or e.dtype != torch.float32):
+                raise ValueError("%s: expect_level0 must be contiguous float32 [%d,%d,%d]" % (who, r0, r0, r0))
+    return ctypes.byref(early.struct(expect))
+
+
+def _keep_until_done(device, *tensor_lists):
+    """The call just enqueued reads these tensors on ``device``'s current stream: the allocator must not hand their
+    memory to another stream before it has."""
+    stream = torch.cuda.current_stream(device)
+    for tensors in tensor_lists:
+        for t in tensors or ():
+            if t is not None:
+                t.record_stream(stream)
 
 
 # mp_mlp_set_precision codes (include/monoport_hip.h)
@@ -358,46 +442,40 @@ def query(mlp, feat_hwc, points, calib, z_scale, projection=_lib.PROJ_ORTHOGONAL
     return out
 
 
+def _query_rows(who, entry, mlp, maps, points, calibs, projection, z_scale, out):
+    """mp_query_batch / mp_query_views (``entry``; one signature but for the projection argument, marshalled by the
+    caller): row i = map i, points[i] (any strides), calibration i -> out[i]."""
+    ctx = mlp.ctx
+    n = len(maps)
+    if points.dim() != 3 or points.shape[0] != n or points.shape[1] != 3:
+        raise ValueError("%s: points must be [%d,3,N], got %s" % (who, n, tuple(points.shape)))
+    if points.dtype != torch.float32:
+        points = points.float()
+    h, w, c, dev = _maps(who, maps)
+    cals = [_calib_dev(cb, dev) for cb in _calib_list(calibs, n, who)]
+    npts = points.shape[2]
+    if out is None:
+        out = torch.empty((n, mlp.cout, npts), dtype=torch.float32, device=dev)
+    else:
+        _out_rows(who, out, n, mlp.cout, npts)
+    ctx.check(getattr(ctx.lib, entry)(
+        ctx.handle, mlp.id, n, _ptr_array(maps), c, h, w, _ptr_array(points), npts, points.stride(2), points.stride(1),
+        _ptr_array(cals), projection, float(z_scale), _ptr_array(out), _stream(out)), entry)
+    _keep_until_done(dev, cals)
+    return out
+
+
 def query_batch(mlp, feats_hwc, points, calibs, projections, z_scale, out=None):
     """mp_query_batch: MonoPortNet.query for F <= MAX_FRAMES frames in one launch.  feats_hwc: F channels-last
     maps [H,W,C]; points [F,3,N] with ANY strides; calibs: F calibrations ([>=3,4] or [1,>=3,4] each, or one
     [F,>=3,4] tensor); projections: F MP_PROJ_* ints or names.  -> [F,Cout,N] (or into ``out``, whose frames
     must each be contiguous [Cout,N])."""
-    ctx = mlp.ctx
-    f_n = len(feats_hwc)
-    if points.dim() != 3 or points.shape[0] != f_n or points.shape[1] != 3:
-        raise ValueError("points must be [%d,3,N], got %s" % (f_n, tuple(points.shape)))
-    if not 1 <= f_n <= MAX_FRAMES:
-        raise ValueError("query_batch: 1..%d frames per call, got %d" % (MAX_FRAMES, f_n))
-    if points.dtype != torch.float32:
-        points = points.float()
-    h, w, c = feats_hwc[0].shape
-    dev = feats_hwc[0].device
-    for f in feats_hwc:
-        if tuple(f.shape) != (h, w, c) or not f.is_contiguous() or f.dtype != torch.float32:
-            raise ValueError("query_batch: the maps must be contiguous float32 [%d,%d,%d]" % (h, w, c))
-    if torch.is_tensor(calibs) and calibs.dim() == 3:
-        calibs = [calibs[b] for b in range(calibs.shape[0])]
-    if len(calibs) != f_n or len(projections) != f_n:
-        raise ValueError("query_batch: %d maps, %d calibrations, %d projections" % (f_n, len(calibs), len(projections)))
-    proj = (ctypes.c_int * f_n)(*[_projection(p) for p in projections])
-    cals = [_calib_dev(cb, dev) for cb in calibs]
-    n = points.shape[2]
-    if out is None:
-        out = torch.empty((f_n, mlp.cout, n), dtype=torch.float32, device=dev)
-    elif (out.shape != (f_n, mlp.cout, n) or out.dtype != torch.float32
-          or (n > 0 and not all(out[b].is_contiguous() for b in range(f_n)))):
-        raise ValueError("query_batch: out must be float32 [%d,%d,%d] with contiguous frames" % (f_n, mlp.cout, n))
-    ptrs = ctypes.c_void_p * f_n
-    ctx.check(ctx.lib.mp_query_batch(
-        ctx.handle, mlp.id, f_n, ptrs(*[f.data_ptr() for f in feats_hwc]), c, h, w,
-        ptrs(*[points[b].data_ptr() for b in range(f_n)]), n, points.stride(2), points.stride(1),
-        ptrs(*[cb.data_ptr() for cb in cals]), proj, float(z_scale), ptrs(*[out[b].data_ptr() for b in range(f_n)]),
-        _stream(out)), "mp_query_batch")
-    stream = torch.cuda.current_stream(dev)
-    for t in cals:
-        t.record_stream(stream)
-    return out
+    n = len(feats_hwc)
+    _check_count("query_batch", "frames", n, MAX_FRAMES)
+    if len(projections) != n:
+        raise ValueError("query_batch: %d maps, %d projections" % (n, len(projections)))
+    proj = (ctypes.c_int * n)(*[_projection(p) for p in projections])
+    return _query_rows("query_batch", "mp_query_batch", mlp, feats_hwc, points, calibs, proj, z_scale, out)
 
 
 def mlp_forward(mlp, feature):
@@ -413,14 +491,6 @@ def mlp_forward(mlp, feature):
     return out
 
 
-MAX_VIEWS = _lib.MAX_VIEWS  # MP_MAX_VIEWS
-
-
-def _check_views(mlp, v_n, who):
-    if not 1 <= v_n <= MAX_VIEWS:
-        raise ValueError("%s: 1..%d views per call, got %d" % (who, MAX_VIEWS, v_n))
-
-
 def query_views(mlp, feats_hwc, points, calibs, projection, z_scale, out=None):
     """mp_query_views: MonoPortNet.query of a multi-view head (SurfaceClassifier num_views = V, multi-view PIFu).
     feats_hwc: V channels-last maps [H,W,C]; points [V,3,N] with ANY strides (row v = the points as view v's
@@ -428,39 +498,9 @@ def query_views(mlp, feats_hwc, points, calibs, projection, z_scale, out=None):
     int or name for all views.  -> [V,Cout,N] (or into ``out``, whose views must each be contiguous [Cout,N]):
     row v is the view-averaged prediction times view v's in-image mask.  f32 heads only; registered skip tables
     are not used."""
-    ctx = mlp.ctx
-    v_n = len(feats_hwc)
-    _check_views(mlp, v_n, "query_views")
-    if points.dim() != 3 or points.shape[0] != v_n or points.shape[1] != 3:
-        raise ValueError("points must be [%d,3,N], got %s" % (v_n, tuple(points.shape)))
-    if points.dtype != torch.float32:
-        points = points.float()
-    h, w, c = feats_hwc[0].shape
-    dev = feats_hwc[0].device
-    for f in feats_hwc:
-        if tuple(f.shape) != (h, w, c) or not f.is_contiguous() or f.dtype != torch.float32:
-            raise ValueError("query_views: the maps must be contiguous float32 [%d,%d,%d]" % (h, w, c))
-    if torch.is_tensor(calibs) and calibs.dim() == 3:
-        calibs = [calibs[v] for v in range(calibs.shape[0])]
-    if len(calibs) != v_n:
-        raise ValueError("query_views: %d maps, %d calibrations" % (v_n, len(calibs)))
-    cals = [_calib_dev(cb, dev) for cb in calibs]
-    n = points.shape[2]
-    if out is None:
-        out = torch.empty((v_n, mlp.cout, n), dtype=torch.float32, device=dev)
-    elif (out.shape != (v_n, mlp.cout, n) or out.dtype != torch.float32
-          or (n > 0 and not all(out[v].is_contiguous() for v in range(v_n)))):
-        raise ValueError("query_views: out must be float32 [%d,%d,%d] with contiguous views" % (v_n, mlp.cout, n))
-    ptrs = ctypes.c_void_p * v_n
-    ctx.check(ctx.lib.mp_query_views(
-        ctx.handle, mlp.id, v_n, ptrs(*[f.data_ptr() for f in feats_hwc]), c, h, w,
-        ptrs(*[points[v].data_ptr() for v in range(v_n)]), n, points.stride(2), points.stride(1),
-        ptrs(*[cb.data_ptr() for cb in cals]), _projection(projection), float(z_scale),
-        ptrs(*[out[v].data_ptr() for v in range(v_n)]), _stream(out)), "mp_query_views")
-    stream = torch.cuda.current_stream(dev)
-    for t in cals:
-        t.record_stream(stream)
-    return out
+    _check_count("query_views", "views", len(feats_hwc), MAX_VIEWS)
+    return _query_rows("query_views", "mp_query_views", mlp, feats_hwc, points, calibs, _projection(projection),
+                       z_scale, out)
 
 
 def mlp_forward_views(mlp, feature):
@@ -470,7 +510,7 @@ def mlp_forward_views(mlp, feature):
     if feature.dim() != 3 or feature.shape[1] != mlp.c + 1:
         raise ValueError("feature must be [V,%d,N], got %s" % (mlp.c + 1, tuple(feature.shape)))
     v_n = feature.shape[0]
-    _check_views(mlp, v_n, "mlp_forward_views")
+    _check_count("mlp_forward_views", "views", v_n, MAX_VIEWS)
     f = _f32c(feature)
     n = f.shape[2]
     out = torch.empty((1, mlp.cout, n), dtype=torch.float32, device=f.device)
@@ -494,45 +534,35 @@ def query_counted(mlp, feat_hwc, points, count, calib, z_scale, out=None):
 
 
 def query_counted_batch(mlp, feats_hwc, points, counts, calibs, z_scale, outs=None, projections=None):
-    """mp_query_counted_batch: one fused-query launch for up to MAX_FRAMES frames.  feats_hwc / points
+    """mp_query_counted_batch_proj: one fused-query launch for up to MAX_FRAMES frames.  feats_hwc / points
     ([3,cap] each, one cap) / counts (int32[1] each) / calibs: lists of per-frame device tensors
-    -> list of [Cout,cap].  ``projections``: per-frame MP_PROJ_* ints or names (None: all orthogonal;
-    otherwise the call is mp_query_counted_batch_proj)."""
+    -> list of [Cout,cap].  ``projections``: per-frame MP_PROJ_* ints or names (None: all orthogonal, which is
+    mp_query_counted_batch)."""
+    who = "query_counted_batch"
     ctx = mlp.ctx
     n = len(feats_hwc)
-    h, w, c = feats_hwc[0].shape
-    cap = points[0].shape[1]
-    dev = feats_hwc[0].device
-    cals = [_calib_dev(cb, dev) for cb in calibs]
+    h, w, c, dev = _maps(who, feats_hwc)
+    if len(points) != n or len(counts) != n or (projections is not None and len(projections) != n):
+        raise ValueError("%s: %d maps, %d point sets, %d counts, %s projections"
+                         % (who, n, len(points), len(counts), None if projections is None else len(projections)))
+    cap = points[0].shape[-1]
+    if any(tuple(p.shape) != (3, cap) or not p.is_contiguous() or p.dtype != torch.float32 for p in points):
+        raise ValueError("%s: the point sets must be contiguous float32 [3,%d]" % (who, cap))
+    cals = [_calib_dev(cb, dev) for cb in _calib_list(calibs, n, who)]
     if outs is None:
         outs = [torch.zeros((mlp.cout, cap), dtype=torch.float32, device=dev) for _ in range(n)]
-    for f, p in zip(feats_hwc, points):
-        assert f.shape == (h, w, c) and f.is_contiguous() and p.shape == (3, cap) and p.is_contiguous()
-    ptrs = ctypes.c_void_p * n
-    if projections is None:
-        ctx.check(ctx.lib.mp_query_counted_batch(
-            ctx.handle, mlp.id, n, ptrs(*[f.data_ptr() for f in feats_hwc]), c, h, w,
-            ptrs(*[p.data_ptr() for p in points]), cap, ptrs(*[k.data_ptr() for k in counts]),
-            ptrs(*[cb.data_ptr() for cb in cals]), float(z_scale), ptrs(*[o.data_ptr() for o in outs]),
-            _stream(outs[0])), "mp_query_counted_batch")
-    else:
-        if len(projections) != n:
-            raise ValueError("query_counted_batch: %d frames, %d projections" % (n, len(projections)))
-        proj = (ctypes.c_int * n)(*[_projection(p) for p in projections])
-        ctx.check(ctx.lib.mp_query_counted_batch_proj(
-            ctx.handle, mlp.id, n, ptrs(*[f.data_ptr() for f in feats_hwc]), c, h, w,
-            ptrs(*[p.data_ptr() for p in points]), cap, ptrs(*[k.data_ptr() for k in counts]),
-            ptrs(*[cb.data_ptr() for cb in cals]), proj, float(z_scale), ptrs(*[o.data_ptr() for o in outs]),
-            _stream(outs[0])), "mp_query_counted_batch_proj")
-    stream = torch.cuda.current_stream(dev)
-    for t in cals:
-        t.record_stream(stream)
+    elif len(outs) != n:
+        raise ValueError("%s: %d maps, %d outputs" % (who, n, len(outs)))
+    proj = None if projections is None else (ctypes.c_int * n)(*[_projection(p) for p in projections])
+    ctx.check(ctx.lib.mp_query_counted_batch_proj(
+        ctx.handle, mlp.id, n, _ptr_array(feats_hwc), c, h, w, _ptr_array(points), cap, _ptr_array(counts),
+        _ptr_array(cals), proj, float(z_scale), _ptr_array(outs), _stream(outs[0])), "mp_query_counted_batch_proj")
+    _keep_until_done(dev, cals)
     return outs
 
 
 # Selection rule of the LAST octree level (include/monoport_hip.h, MP_FINAL_*; Seg3dLossless docstring)
 FINAL_LEVELS = {"dilate3": 0, "upstream": 1, "interpolate": 2}
-MAX_FRAMES = _lib.load().mp_max_frames()  # kMaxFrames: frames per mp_recon_batch / mp_query_counted_batch call
 
 
 class EarlyFlags:
@@ -549,10 +579,9 @@ class EarlyFlags:
         self.event.record(torch.cuda.current_stream(device))  # materialises the hipEvent_t the C side re-records
 
     def struct(self, expect):
-        n = self.n
         self._expect = None
-        if expect is not None:
-            self._expect = (ctypes.c_void_p * n)(*[None if e is None else e.data_ptr() for e in expect])
+        if expect is not None:  # the C side reads self.n entries
+            self._expect = _ptr_array(list(expect) + [None] * (self.n - len(expect)))
         return _lib.ReconEarly(ctypes.cast(self._expect, ctypes.c_void_p) if self._expect is not None else None,
                                self.dev.data_ptr(), self.host.data_ptr(), self.event.cuda_event)
 
@@ -590,60 +619,31 @@ def recon_batch(mlp, feats_hwc, calibs, z_scale, b_min, b_max, resolutions, bala
     calls bit for bit.  ``early``: an ``EarlyFlags`` for B frames -- mp_recon_batch_early: after the coarsest level
     the call hands (non-empty, differs-from-``expect_level0[b]``) per frame to the host (``early.wait()``) and goes
     on refining; ``expect_level0``: list of [r0,r0,r0] f32 tensors (or None entries).  ``projections``: per-frame
-    MP_PROJ_* ints or names (None: all orthogonal, mp_recon_batch_early; otherwise mp_recon_batch_proj)."""
+    MP_PROJ_* ints or names (None: all orthogonal).  One mp_recon_batch_proj call, which with no projections is
+    mp_recon_batch_early."""
+    who = "recon_batch"
     ctx = mlp.ctx
     n = len(feats_hwc)
-    h, w, c = feats_hwc[0].shape
+    h, w, c, dev = _maps(who, feats_hwc)
     res = [int(r) for r in resolutions]
-    r_last = res[-1]
-    dev = feats_hwc[0].device
-    if torch.is_tensor(calibs):
-        calibs = [calibs[b:b + 1] for b in range(n)]
-    cals = [_calib_dev(cb, dev) for cb in calibs]
+    cals = [_calib_dev(cb, dev) for cb in _calib_list(calibs, n, who)]
+    if projections is not None and len(projections) != n:
+        raise ValueError("%s: %d frames, %d projections" % (who, n, len(projections)))
+    proj = None if projections is None else (ctypes.c_int * n)(*[_projection(p) for p in projections])
     if volumes is None:
-        volumes = [torch.empty((r_last, r_last, r_last), dtype=torch.float32, device=dev)
-                   for _ in range(n)]
+        volumes = [torch.empty((res[-1],) * 3, dtype=torch.float32, device=dev) for _ in range(n)]
+    elif len(volumes) != n:
+        raise ValueError("%s: %d frames, %d volumes" % (who, n, len(volumes)))
     if status is None:
         status = torch.empty((n, 1 + len(res)), dtype=torch.int32, device=dev)
-    assert status.is_contiguous() and status.shape == (n, 1 + len(res))
-    for f in feats_hwc:
-        assert f.shape == (h, w, c) and f.is_contiguous() and f.dtype == torch.float32
-    bmin = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(b_min, np.float32).reshape(3)])
-    bmax = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(b_max, np.float32).reshape(3)])
-    res_c = (ctypes.c_int * len(res))(*res)
-    ptrs = ctypes.c_void_p * n
-    if early is not None:
-        if early.n != n:
-            raise ValueError("recon_batch: EarlyFlags for %d frames, call has %d" % (early.n, n))
-        if expect_level0 is not None:
-            for e in expect_level0:
-                assert e is None or (e.numel() == res[0] ** 3 and e.is_contiguous() and e.dtype == torch.float32)
-        est = early.struct(expect_level0)
-        early_arg = ctypes.byref(est)
-    else:
-        early_arg = None
-    if projections is None:
-        ctx.check(ctx.lib.mp_recon_batch_early(
-            ctx.handle, mlp.id, n, ptrs(*[f.data_ptr() for f in feats_hwc]), c, h, w,
-            ptrs(*[cb.data_ptr() for cb in cals]), float(z_scale), bmin, bmax, res_c, len(res),
-            float(balance), _final_level(final_level), ptrs(*[v.data_ptr() for v in volumes]),
-            ptrs(*[status[b].data_ptr() for b in range(n)]), early_arg, _stream(volumes[0])), "mp_recon_batch_early")
-    else:
-        if len(projections) != n:
-            raise ValueError("recon_batch: %d frames, %d projections" % (n, len(projections)))
-        proj = (ctypes.c_int * n)(*[_projection(p) for p in projections])
-        ctx.check(ctx.lib.mp_recon_batch_proj(
-            ctx.handle, mlp.id, n, ptrs(*[f.data_ptr() for f in feats_hwc]), c, h, w,
-            ptrs(*[cb.data_ptr() for cb in cals]), proj, float(z_scale), bmin, bmax, res_c, len(res),
-            float(balance), _final_level(final_level), ptrs(*[v.data_ptr() for v in volumes]),
-            ptrs(*[status[b].data_ptr() for b in range(n)]), early_arg, _stream(volumes[0])), "mp_recon_batch_proj")
-    stream = torch.cuda.current_stream(dev)
-    if expect_level0 is not None:
-        for e in expect_level0:
-            if e is not None:
-                e.record_stream(stream)
-    for t in cals:
-        t.record_stream(stream)
+    elif tuple(status.shape) != (n, 1 + len(res)) or not status.is_contiguous() or status.dtype != torch.int32:
+        raise ValueError("%s: status must be contiguous int32 [%d,%d]" % (who, n, 1 + len(res)))
+    early_arg = _early_arg(who, early, n, expect_level0, res[0])
+    ctx.check(ctx.lib.mp_recon_batch_proj(
+        ctx.handle, mlp.id, n, _ptr_array(feats_hwc), c, h, w, _ptr_array(cals), proj, float(z_scale), _float3(b_min),
+        _float3(b_max), (ctypes.c_int * len(res))(*res), len(res), float(balance), _final_level(final_level),
+        _ptr_array(volumes), _ptr_array(status), early_arg, _stream(volumes[0])), "mp_recon_batch_proj")
+    _keep_until_done(dev, cals, expect_level0)
     return volumes, status
 
 
@@ -655,45 +655,22 @@ def recon_views(mlp, maps, calibs, projection, z_scale, b_min, b_max, resolution
     prediction times view ``view``'s in-image mask).  Returns (volume [R,R,R] f32, status int32[1+levels]) -- both
     on device, nothing synchronised.  ``early``: an ``EarlyFlags`` for one frame, ``expect_level0``: [r0,r0,r0] f32
     (see ``recon_batch``).  f32 netG heads only; registered skip tables are not used."""
+    who = "recon_views"
     ctx = mlp.ctx
     v_n = len(maps)
-    _check_views(mlp, v_n, "recon_views")
-    h, w, c = maps[0].shape
-    dev = maps[0].device
-    for f in maps:
-        if tuple(f.shape) != (h, w, c) or not f.is_contiguous() or f.dtype != torch.float32:
-            raise ValueError("recon_views: the maps must be contiguous float32 [%d,%d,%d]" % (h, w, c))
-    if torch.is_tensor(calibs) and calibs.dim() == 3:
-        calibs = [calibs[v] for v in range(calibs.shape[0])]
-    if len(calibs) != v_n:
-        raise ValueError("recon_views: %d maps, %d calibrations" % (v_n, len(calibs)))
-    cals = [_calib_dev(cb, dev) for cb in calibs]
+    _check_count(who, "views", v_n, MAX_VIEWS)
+    h, w, c, dev = _maps(who, maps)
+    cals = [_calib_dev(cb, dev) for cb in _calib_list(calibs, v_n, who)]
     res = [int(r) for r in resolutions]
     volume = torch.empty((res[-1],) * 3, dtype=torch.float32, device=dev)
     status = torch.empty((1 + len(res),), dtype=torch.int32, device=dev)
-    bmin = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(b_min, np.float32).reshape(3)])
-    bmax = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(b_max, np.float32).reshape(3)])
-    if early is not None:
-        if early.n != 1:
-            raise ValueError("recon_views: EarlyFlags for %d frames, the call has one" % early.n)
-        if expect_level0 is not None:
-            assert (expect_level0.numel() == res[0] ** 3 and expect_level0.is_contiguous()
-                    and expect_level0.dtype == torch.float32)
-        est = early.struct(None if expect_level0 is None else [expect_level0])
-        early_arg = ctypes.byref(est)
-    else:
-        early_arg = None
-    ptrs = ctypes.c_void_p * v_n
+    expect = None if expect_level0 is None else [expect_level0]
+    early_arg = _early_arg(who, early, 1, expect, res[0])
     ctx.check(ctx.lib.mp_recon_views(
-        ctx.handle, mlp.id, v_n, ptrs(*[f.data_ptr() for f in maps]), c, h, w, ptrs(*[cb.data_ptr() for cb in cals]),
-        _projection(projection), float(z_scale), bmin, bmax, (ctypes.c_int * len(res))(*res), len(res),
-        float(balance), _final_level(final_level), int(view), _ptr(volume), _ptr(status), early_arg,
-        _stream(volume)), "mp_recon_views")
-    stream = torch.cuda.current_stream(dev)
-    if expect_level0 is not None:
-        expect_level0.record_stream(stream)
-    for t in cals:
-        t.record_stream(stream)
+        ctx.handle, mlp.id, v_n, _ptr_array(maps), c, h, w, _ptr_array(cals), _projection(projection), float(z_scale),
+        _float3(b_min), _float3(b_max), (ctypes.c_int * len(res))(*res), len(res), float(balance),
+        _final_level(final_level), int(view), _ptr(volume), _ptr(status), early_arg, _stream(volume)), "mp_recon_views")
+    _keep_until_done(dev, cals, expect)
     return volume, status
 
 
@@ -715,8 +692,7 @@ class LevelEngine:
         self.rf = self.res[-1]
         self.balance = float(balance)
         self.faster = bool(faster)
-        self.bmin = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(b_min, np.float32).reshape(3)])
-        self.bmax = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(b_max, np.float32).reshape(3)])
+        self.bmin, self.bmax = _float3(b_min), _float3(b_max)
         self.count = torch.zeros((1,), dtype=torch.int32, device=self.dev)
         self.level = -1
         self.prev = self.ev_prev = None
@@ -917,13 +893,8 @@ def plan_wait(waiter, signaller):
 
 def forward_vertices_raw(volume, direction="front"):
     """mp_forward_vertices: returns capacity-sized (X, Y, Z, norm, count) device tensors."""
-    vol = volume
-    while vol.dim() > 3:
-        vol = vol[0]
-    vol = _f32c(vol)
-    r = vol.shape[2]
-    if vol.shape != (r, r, r):
-        raise ValueError("forward_vertices wants a cubic volume, got %s" % (tuple(vol.shape),))
+    vol = _cubic_volume(volume, "forward_vertices")
+    r = vol.shape[0]
     ctx = get_context(vol.device)
     cap = r * r
     dev = vol.device
@@ -941,14 +912,10 @@ def forward_vertices_raw(volume, direction="front"):
 def forward_vertices_raw_batch(volumes, direction="front"):
     """mp_forward_vertices_batch: ``[forward_vertices_raw(v, direction) for v in volumes]`` (up to MAX_FRAMES cubic
     volumes of one size) in one set of launches; every frame's (X, Y, Z, norm, count) are views of five tensors."""
-    vols = []
-    for v in volumes:
-        while v.dim() > 3:
-            v = v[0]
-        vols.append(_f32c(v))
+    vols = [_cubic_volume(v, "forward_vertices_raw_batch") for v in volumes]
     n = len(vols)
-    r = vols[0].shape[2]
-    if any(tuple(v.shape) != (r, r, r) for v in vols):
+    r = vols[0].shape[0]
+    if any(v.shape[0] != r for v in vols):
         raise ValueError("forward_vertices_raw_batch wants cubic volumes of one size")
     dev = vols[0].device
     ctx = get_context(dev)
@@ -961,15 +928,11 @@ def forward_vertices_raw_batch(volumes, direction="front"):
     out = []
     for f0 in range(0, n, MAX_FRAMES):
         f1 = min(f0 + MAX_FRAMES, n)
-        ptrs = ctypes.c_void_p * (f1 - f0)
         ctx.check(ctx.lib.mp_forward_vertices_batch(
-            ctx.handle, f1 - f0, ptrs(*[vols[f].data_ptr() for f in range(f0, f1)]), r, DIRECTIONS[direction],
-            ptrs(*[x[f].data_ptr() for f in range(f0, f1)]), ptrs(*[y[f].data_ptr() for f in range(f0, f1)]),
-            ptrs(*[z[f].data_ptr() for f in range(f0, f1)]), ptrs(*[nrm[f].data_ptr() for f in range(f0, f1)]),
-            ptrs(*[count[f].data_ptr() for f in range(f0, f1)]), _stream(x)), "mp_forward_vertices_batch")
-    stream = torch.cuda.current_stream(dev)
-    for v in vols:
-        v.record_stream(stream)
+            ctx.handle, f1 - f0, _ptr_array(vols[f0:f1]), r, DIRECTIONS[direction], _ptr_array(x[f0:f1]),
+            _ptr_array(y[f0:f1]), _ptr_array(z[f0:f1]), _ptr_array(nrm[f0:f1]), _ptr_array(count[f0:f1]), _stream(x)),
+            "mp_forward_vertices_batch")
+    _keep_until_done(dev, vols)
     for f in range(n):
         out.append((x[f], y[f], z[f], nrm[f], count[f]))
     return out
@@ -986,16 +949,11 @@ def paint_batch(xs, ys, values, channel_major, counts, res, scale, bias, lo, hi)
     images = torch.empty((n, res, res, 3), dtype=torch.float32, device=dev)
     for f0 in range(0, n, MAX_FRAMES):
         f1 = min(f0 + MAX_FRAMES, n)
-        ptrs = ctypes.c_void_p * (f1 - f0)
         ctx.check(ctx.lib.mp_paint_batch(
-            ctx.handle, f1 - f0, ptrs(*[xs[f].data_ptr() for f in range(f0, f1)]),
-            ptrs(*[ys[f].data_ptr() for f in range(f0, f1)]), ptrs(*[vals[f].data_ptr() for f in range(f0, f1)]),
-            int(channel_major), ptrs(*[counts[f].data_ptr() for f in range(f0, f1)]), cap, int(res), float(scale),
-            float(bias), float(lo), float(hi), ptrs(*[images[f].data_ptr() for f in range(f0, f1)]), _stream(images)),
-            "mp_paint_batch")
-    stream = torch.cuda.current_stream(dev)
-    for v in vals:
-        v.record_stream(stream)
+            ctx.handle, f1 - f0, _ptr_array(xs[f0:f1]), _ptr_array(ys[f0:f1]), _ptr_array(vals[f0:f1]),
+            int(channel_major), _ptr_array(counts[f0:f1]), cap, int(res), float(scale), float(bias), float(lo),
+            float(hi), _ptr_array(images[f0:f1]), _stream(images)), "mp_paint_batch")
+    _keep_until_done(dev, vals)
     return [images[f] for f in range(n)]
 
 
@@ -1045,9 +1003,7 @@ def prepare_inputs(segm, mean, std, with_color=True):
     hw = sg.shape[2] * sg.shape[3]
     g = torch.empty((1, 3) + tuple(sg.shape[2:]), dtype=torch.float32, device=sg.device)
     c = torch.empty_like(g) if with_color else None
-    mean_c = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(mean, np.float32).reshape(3)])
-    std_c = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(std, np.float32).reshape(3)])
-    ctx.check(ctx.lib.mp_prepare_inputs(ctx.handle, _ptr(sg), hw, mean_c, std_c, _ptr(g),
+    ctx.check(ctx.lib.mp_prepare_inputs(ctx.handle, _ptr(sg), hw, _float3(mean), _float3(std), _ptr(g),
                                         _ptr(c) if c is not None else None, _stream(sg)),
               "mp_prepare_inputs")
     return g, c
@@ -1057,10 +1013,7 @@ def marching_cubes_raw(volume, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), m
                        max_faces=None):
     """mp_marching_cubes: capacity-sized (verts [max_v,3] f32, faces [max_f,3] int32,
     counts int32[2] = needed vertices / faces) on device, no host sync."""
-    vol = volume
-    while vol.dim() > 3:
-        vol = vol[0]
-    vol = _f32c(vol)
+    vol = _cubic_volume(volume, "marching_cubes")
     r = vol.shape[0]
     ctx = get_context(vol.device)
     if max_verts is None:
@@ -1071,9 +1024,7 @@ def marching_cubes_raw(volume, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), m
     verts = torch.empty((max_verts, 3), dtype=torch.float32, device=dev)
     faces = torch.empty((max_faces, 3), dtype=torch.int32, device=dev)
     counts = torch.empty((2,), dtype=torch.int32, device=dev)
-    bmin = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(b_min, np.float32).reshape(3)])
-    bmax = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(b_max, np.float32).reshape(3)])
-    ctx.check(ctx.lib.mp_marching_cubes(ctx.handle, _ptr(vol), r, float(level), bmin, bmax,
+    ctx.check(ctx.lib.mp_marching_cubes(ctx.handle, _ptr(vol), r, float(level), _float3(b_min), _float3(b_max),
                                         _ptr(verts), max_verts, _ptr(faces), max_faces,
                                         _ptr(counts), _stream(vol)), "mp_marching_cubes")
     return verts, faces, counts
