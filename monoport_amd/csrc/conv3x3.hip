@@ -967,14 +967,6 @@ int launch_conv3x3_pack16(mp_ctx *ctx, const float *w, int cout, int cin, void *
   return MP_OK;
 }
 
-static int raise_lds_limit(mp_ctx *ctx, const void *kern_id, int bytes) {
-  if (!ctx->lds_attr_done.count(kern_id)) {
-    MP_HIP(ctx, hipFuncSetAttribute(kern_id, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    ctx->lds_attr_done.insert(kern_id);
-  }
-  return MP_OK;
-}
-
 template <int RBW, int NR>
 static int launch_conv16_t(mp_ctx *ctx, const ConvArgs &a, const float *wmax, int tiles, hipStream_t st) {
   const int lds = 2 * (a.th + 2) * (a.tw + 2) * kPixBytes;

@@ -697,19 +697,11 @@ int launch_conv3x3_wino(mp_ctx *ctx, const ConvArgs &a, hipStream_t st) {
   const int tiles = conv3x3_wino_tiles(a.h, a.w);
   if (wino_use64(a)) {
     auto kern = conv3x3_wino64_kernel;
-    const void *kern_id = reinterpret_cast<const void *>(kern);
-    if (!ctx->lds_attr_done.count(kern_id)) {
-      MP_HIP(ctx, hipFuncSetAttribute(kern_id, hipFuncAttributeMaxDynamicSharedMemorySize, kW8Lds));
-      ctx->lds_attr_done.insert(kern_id);
-    }
+    if (const int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kern), kW8Lds)) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * a.n_img), (unsigned)(a.cout / 64)), dim3(kWnThreads), kW8Lds, st, a);
   } else {
     auto kern = conv3x3_wino_kernel<2>;
-    const void *kern_id = reinterpret_cast<const void *>(kern);
-    if (!ctx->lds_attr_done.count(kern_id)) {
-      MP_HIP(ctx, hipFuncSetAttribute(kern_id, hipFuncAttributeMaxDynamicSharedMemorySize, kWnLds));
-      ctx->lds_attr_done.insert(kern_id);
-    }
+    if (const int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kern), kWnLds)) return rc;
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * a.n_img), (unsigned)(a.cout / 128)), dim3(kWnThreads), kWnLds, st, a);
   }
   MP_HIP(ctx, hipGetLastError());

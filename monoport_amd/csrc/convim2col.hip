@@ -279,11 +279,7 @@ static int launch_convk_t(mp_ctx *ctx, const ConvKArgs &a, hipStream_t st) {
   constexpr int lds_tile = PX * ceil8(CC * KS * KS) * 4;
   constexpr int lds = lds_tile > 4096 ? lds_tile : 4096;
   auto kern = convk_kernel<RBW, NR, KS, CC>;
-  const void *kern_id = reinterpret_cast<const void *>(kern);
-  if (!ctx->lds_attr_done.count(kern_id)) {
-    MP_HIP(ctx, hipFuncSetAttribute(kern_id, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    ctx->lds_attr_done.insert(kern_id);
-  }
+  if (const int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
   const int tiles = a.ho * (a.wo / PX);
   hipLaunchKernelGGL(kern, dim3((unsigned)(tiles * a.n_img), (unsigned)(a.cout / (32 * RBW))), dim3(256), lds, st, a);
   MP_HIP(ctx, hipGetLastError());

@@ -252,6 +252,19 @@ int ensure_scratch(mp_ctx *ctx, hipStream_t st, size_t bytes, void **out);
 int launch_mfma_clock_probe(mp_ctx *ctx, float ms_target, double *out, hipStream_t st);
 
 // query.hip
+// raises a kernel's dynamic-LDS limit to `bytes`, once per kernel and context (= device); every launcher with
+// more than 64 KB of dynamic LDS calls it
+int raise_lds_limit(mp_ctx *ctx, const void *kern, int bytes);
+// what the launchers of the query kernels share:
+// workgroups of a launch that strides over `tiles`.  Device-side counts: the resident grid, which strides;
+// host-side counts: one workgroup per tile up to a few waves of the machine
+inline long long query_grid(long long tiles, long long resident, bool device_counts) {
+  const long long cap = device_counts ? resident : 8 * resident;
+  return tiles < cap ? tiles : cap;
+}
+// the event pair around one query launch while mp_profile_begin's pairs last (mp_profile_end reads them)
+int prof_begin(mp_ctx *ctx, hipStream_t st);
+int prof_end(mp_ctx *ctx, hipStream_t st);
 int launch_query(mp_ctx *ctx, const Mlp &m, const float *feat_hwc, int h, int w,
                  const float *calib, float z_scale, const PointSrc &src, float *out,
                  long long max_points, hipStream_t st);

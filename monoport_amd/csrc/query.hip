@@ -48,39 +48,15 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_kernel(
   const int lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 31, h = lane >> 5;
-
-  // The tiles of all frames of the set form one index space: frame f owns the next
-  // ceil(n_f / tile) global tiles.  The owner of a global tile is looked up from the (device-side)
-  // counts at the top of every iteration -- eight scalar loads -- instead of keeping a prefix
-  // table alive in SGPRs across the whole MLP.
   const int swz = h ^ (j & 15);  // this lane's 16-byte-slot swizzle (see gemm_seg)
   const WStream ws = make_wstream(mlp.base, mlp.n_floats, lane);
 
   for (long long gtile = blockIdx.x;; gtile += gridDim.x) {
-    int fi = -1;
-    long long tile0 = 0;
-    {
-      long long acc = 0;
-      // groups of 8 frames: the 8 count loads of a group are in flight together, and the dynamic group offset
-      // keeps the compiler from hoisting all kMaxFrames kernel-argument loads into SGPRs (spills)
-      for (int f0 = 0; f0 < set.n; f0 += 8)
-#pragma unroll
-      for (int fk = 0; fk < 8; ++fk) {
-        const int f = f0 + fk;
-        if (f < set.n) {
-          const long long nf = set.count(f);
-          const long long t = (nf + kTilePts - 1) / kTilePts;
-          if (fi < 0 && gtile < acc + t) {
-            fi = f;
-            tile0 = acc;
-          }
-          acc += t;
-        }
-      }
-      // launches of fewer than gate_tiles tiles belong to the 32-point kernel (query_small.hip),
-      // which was launched next to this one because the counts live on the device
-      if (acc < gate_tiles) break;
-    }
+    int fi;
+    long long tile0;
+    // launches of fewer than gate_tiles tiles belong to the 32-point kernel (query_small.hip),
+    // which was launched next to this one because the counts live on the device
+    if (tile_owner<kTilePts>(set, gtile, fi, tile0) < gate_tiles) break;
     if (fi < 0) break;  // past the last tile of the last frame
     const QueryItem item = set.item(fi);
     const float *__restrict__ feat = item.feat;
@@ -112,159 +88,21 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_kernel(
         zb[cb] = (h == 0 && m < n_pts) ? src.pts[(long long)C * src.sc + m] : 0.0f;
       }
     } else {
-    // ---------------- gather: 16 points per wave ----------------
-    {
-    float cal[12];
+      float cal[12];
 #pragma unroll
-    for (int i = 0; i < 12; ++i) cal[i] = calib[i];
-    // 4 points per batch: 16 (C=256) / 32 (C=512) independent 16-byte loads in flight per lane.
-    // Dead points (past the end / out of image) read a clamped in-bounds tap with weight 0, so
-    // the loads need no branch and the compiler can issue the whole batch back to back.
-    constexpr int GB = 4;
-#pragma unroll 1
-    for (int i0 = 0; i0 < 16; i0 += GB) {
-      Taps t[GB];
+      for (int i = 0; i < 12; ++i) cal[i] = calib[i];
+      gather_f32<C, 16>(xs, feat, fh, fw, cal, proj, src, n0, n_pts, wv, lane);
 #pragma unroll
-      for (int u = 0; u < GB; ++u) {
-        const long long n = n0 + 16 * wv + i0 + u;
-        const bool live_n = n < n_pts;
-        float px = 0, py = 0, pz = 0, x, y, z;
-        uint32_t code;
-        if (live_n) load_point(src, n, px, py, pz, code);
-        project_mode(cal, proj, px, py, pz, x, y, z);
-        t[u] = make_taps(x, y, fh, fw, C, live_n && in_image(x, y));
-      }
-      f32x4 v[GB][C / 256][4];
-#pragma unroll
-      for (int u = 0; u < GB; ++u)
-#pragma unroll
-        for (int part = 0; part < C / 256; ++part)
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            v[u][part][k] =
-                *reinterpret_cast<const f32x4 *>(feat + t[u].o[k] + 4 * (lane + 64 * part));
-#pragma unroll
-      for (int u = 0; u < GB; ++u) {
-        const int p = 16 * wv + i0 + u;
-#pragma unroll
-        for (int part = 0; part < C / 256; ++part) {
-          const int slot = lane + 64 * part;
-          const f32x4 r = blend(v[u][part][0], v[u][part][1], v[u][part][2], v[u][part][3], t[u]);
-          *reinterpret_cast<f32x4 *>(xs + p * ROWB + ((slot ^ (p & 15)) << 4)) = r;
-        }
-      }
-    }
-
-    // z_feat for the z k-step: lanes 0-31 carry it, lanes 32-63 supply 0
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-      const long long n = n0 + 32 * cb + j;
-      float px = 0, py = 0, pz = 0, x, y, z;
-      uint32_t code;
-      if (n < n_pts) load_point(src, n, px, py, pz, code);
-      project_mode(cal, proj, px, py, pz, x, y, z);
-      zb[cb] = (h == 0 && n < n_pts) ? __fmul_rn(z, z_scale) : 0.0f;
-    }
-    }
+      for (int cb = 0; cb < 2; ++cb) zb[cb] = z_operand(cal, proj, src, n0 + 32 * cb + j, n_pts, z_scale, h);
     }
     __syncthreads();
 
-    const unsigned char *xrow = xs + j * ROWB;       // this lane's point row, column block 0
-    const unsigned char *hrow = hb + j * kHbRowBytes;
-
-    // ---------------- layers 0 + 1, fused over 64-row chunks of layer 0 ----------------
-    f32x16 acc1[4][2];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      init_from_bias(acc1[m][0], ws, mlp.bias[1] + 32 * (4 * wv + m));
-      acc1[m][1] = acc1[m][0];
-    }
-    {
-      const int rb0 = wv >> 1, cb0 = wv & 1;  // this wave's tile inside a layer-0 chunk
-      const int a0 = mlp.ax[0] / 4;           // 16-byte units (segments are 256-byte aligned)
-      const int a1 = mlp.ah[1] / 4 + (4 * wv) * (kHidden[0] / 8) * 64;
-      const float zz[1] = {zb[cb0]};
-      f32x4 ring0[kPrefetch0 + 1][1];
-      f32x16 acc0[1][1];
-      float az0[1];
-      seg_prefetch<1, kPrefetch0, (kAHot & 1) != 0>(ring0, ws, a0 + rb0 * NGX * 64, 0, NGX);
-      init_from_bias(acc0[0][0], ws, mlp.bias[0] + 32 * rb0);
-      az0[0] = wload32(ws, mlp.az[0] + rb0 * 64);
-#pragma unroll 1
-      for (int ck = 0; ck < kHidden[0] / 64; ++ck) {
-        // layer-0 rows [64 ck + 32 rb0, +32) x points [32 cb0, +32)
-        const int rb = 2 * ck + rb0;
-        seg_main<1, 1, kPrefetch0, ROWB, (kAHot & 1) != 0>(acc0, ring0, ws, a0 + rb * NGX * 64, 0, NGX,
-                                xrow + cb0 * 32 * ROWB, swz);
-        // layer-1 weights of this chunk start streaming before the chunk is even stored
-        f32x4 ring1[kPrefetch1 + 1][4];
-        seg_prefetch<4, kPrefetch1, (kAHot & 2) != 0>(ring1, ws, a1 + ck * 8 * 64, (kHidden[0] / 8) * 64, 8);
-        gemm_z<1, 1>(acc0, az0, zz);
-        lrelu(acc0[0][0]);
-        store_hidden(hb, acc0[0][0], rb0, cb0, j, h);
-        // next chunk's layer-0 operands
-        const int rbn = min(rb + 2, kHidden[0] / 32 - 2 + rb0);
-        seg_prefetch<1, kPrefetch0, (kAHot & 1) != 0>(ring0, ws, a0 + rbn * NGX * 64, 0, NGX);
-        init_from_bias(acc0[0][0], ws, mlp.bias[0] + 32 * rbn);
-        az0[0] = wload32(ws, mlp.az[0] + rbn * 64);
-        MP_CHUNK_SYNC();
-        // layer-1 rows [128 wv, +128) += W1[:, 64 ck .. +64) * chunk
-        seg_main<4, 2, kPrefetch1, kHbRowBytes, (kAHot & 2) != 0>(acc1, ring1, ws, a1 + ck * 8 * 64, (kHidden[0] / 8) * 64, 8,
-                                       hrow, swz);
-        MP_CHUNK_SYNC();
-      }
-      // skip segment of layer 1: W1[:, 1024 .. 1024 + C] * x, then the z column
-      const int a1x = mlp.ax[1] / 4 + (4 * wv) * NGX * 64;
-      f32x4 ring1[kPrefetch1 + 1][4];
-      float az1[4];
-      seg_prefetch<4, kPrefetch1>(ring1, ws, a1x, NGX * 64, NGX);
-#pragma unroll
-      for (int m = 0; m < 4; ++m) az1[m] = wload32(ws, mlp.az[1] + (4 * wv + m) * 64);
-      seg_main<4, 2, kPrefetch1, ROWB>(acc1, ring1, ws, a1x, NGX * 64, NGX, xrow, swz);
-      gemm_z<4, 2>(acc1, az1, zb);
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) lrelu(acc1[m][n]);
-    }
-
-    // ---------------- layer 2: rows [64 wv, +64), K = 512 hidden (8 chunks) + skip ----------------
+    // ---------------- layers 0-2 (query_mfma.h) ----------------
     f32x16 acc2[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      init_from_bias(acc2[m][0], ws, mlp.bias[2] + 32 * (2 * wv + m));
-      acc2[m][1] = acc2[m][0];
-    }
-    {
-      const int a2 = mlp.ah[2] / 4 + (2 * wv) * (kHidden[1] / 8) * 64;
-      f32x4 ring2[2][2];
-      seg_prefetch<2, 1>(ring2, ws, a2, (kHidden[1] / 8) * 64, 8);
-#pragma unroll
-      for (int ck = 0; ck < 8; ++ck) {
-        if (wv == (ck >> 1)) {  // owner of hidden rows [64 ck, +64): row blocks 2(ck&1), +1
-#pragma unroll
-          for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-            for (int n = 0; n < 2; ++n) store_hidden(hb, acc1[2 * (ck & 1) + mm][n], mm, n, j, h);
-        }
-        MP_CHUNK_SYNC();
-        seg_main<2, 2, 1, kHbRowBytes>(acc2, ring2, ws, a2 + ck * 8 * 64, (kHidden[1] / 8) * 64, 8,
-                                       hrow, swz);
-        if (ck < 7) seg_prefetch<2, 1>(ring2, ws, a2 + (ck + 1) * 8 * 64, (kHidden[1] / 8) * 64, 8);
-        MP_CHUNK_SYNC();
-      }
-      const int a2x = mlp.ax[2] / 4 + (2 * wv) * NGX * 64;
-      float az2[2];
-      seg_prefetch<2, 1>(ring2, ws, a2x, NGX * 64, NGX);
-#pragma unroll
-      for (int m = 0; m < 2; ++m) az2[m] = wload32(ws, mlp.az[2] + (2 * wv + m) * 64);
-      seg_main<2, 2, 1, ROWB>(acc2, ring2, ws, a2x, NGX * 64, NGX, xrow, swz);
-      gemm_z<2, 2>(acc2, az2, zb);
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) lrelu(acc2[m][n]);
-    }
+    mlp64_layers012<C>(acc2, mlp, ws, xs, hb, zb, wv, j, h, swz);
+
+    const unsigned char *xrow = xs + j * ROWB;  // this lane's point row, column block 0
+    const unsigned char *hrow = hb + j * kHbRowBytes;
 
     // ---------------- layer 3: rows [32 wv, +32), K = 256 hidden (4 chunks) + skip ----------------
     f32x16 acc3[1][2];
@@ -282,10 +120,10 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_kernel(
 #pragma unroll
             for (int n = 0; n < 2; ++n) store_hidden(hb, acc2[mm][n], mm, n, j, h);
         }
-        MP_CHUNK_SYNC();
+        __syncthreads();
         seg_main<1, 2, 3, kHbRowBytes>(acc3, ring3, ws, a3 + ck * 8 * 64, 0, 8, hrow, swz);
         if (ck < 3) seg_prefetch<1, 3>(ring3, ws, a3 + (ck + 1) * 8 * 64, 0, 8);
-        MP_CHUNK_SYNC();
+        __syncthreads();
       }
       const int a3x = mlp.ax[3] / 4 + wv * NGX * 64;
       float az3[1];
@@ -298,53 +136,9 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_kernel(
     }
 
     // ---------------- layer 4 (Cout x (128 + C + 1)) on the VALU ----------------
-    // red[part][o][p]: parts 0-3 = hidden rows of wave `part`, parts 4-7 = feature quarter
-    float *red = reinterpret_cast<float *>(hb);
+    float *red = reinterpret_cast<float *>(hb);  // red[part][o][p], see mlp64_layer4_partials
     constexpr int K4 = (kHidden[3] + C + 1 + 3) & ~3;  // padded row stride (pack.hip)
-    {
-      // hidden part: this lane holds rows 32 wv + 8q + 4h + i of points 32 cb + j
-#pragma unroll
-      for (int o = 0; o < COUT; ++o) {
-        const float *w4 = (mlp.base + mlp.w4) + o * K4 + 32 * wv + 4 * h;
-        float s0 = 0.0f, s1 = 0.0f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 wq = *reinterpret_cast<const f32x4 *>(w4 + 8 * q);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            s0 = fmaf(wq[i], acc3[0][0][4 * q + i], s0);
-            s1 = fmaf(wq[i], acc3[0][1][4 * q + i], s1);
-          }
-        }
-        s0 += __shfl_xor(s0, 32);
-        s1 += __shfl_xor(s1, 32);
-        if (h == 0) {
-          red[(wv * COUT + o) * kTilePts + j] = s0;
-          red[(wv * COUT + o) * kTilePts + 32 + j] = s1;
-        }
-      }
-      // feature part: lane = point, wave = quarter of the C channels
-      const int p = lane;
-      float sx[COUT];
-#pragma unroll
-      for (int o = 0; o < COUT; ++o) sx[o] = 0.0f;
-      constexpr int SLOTS = C / 16;  // 16-byte slots per quarter
-#pragma unroll 4
-      for (int s = 0; s < SLOTS; ++s) {
-        const int slot = wv * SLOTS + s;
-        const f32x4 xv =
-            *reinterpret_cast<const f32x4 *>(xs + p * ROWB + ((slot ^ (p & 15)) << 4));
-#pragma unroll
-        for (int o = 0; o < COUT; ++o) {
-          const f32x4 wq =
-              *reinterpret_cast<const f32x4 *>((mlp.base + mlp.w4) + o * K4 + kHidden[3] + 4 * slot);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) sx[o] = fmaf(wq[i], xv[i], sx[o]);
-        }
-      }
-#pragma unroll
-      for (int o = 0; o < COUT; ++o) red[((4 + wv) * COUT + o) * kTilePts + p] = sx[o];
-    }
+    mlp64_layer4_partials<C, COUT>(red, acc3, mlp, xs, wv, lane, j, h);
     __syncthreads();
     if (tid < COUT * kTilePts) {
       const int o = tid / kTilePts, p = tid % kTilePts;
@@ -358,21 +152,7 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_kernel(
           v = fmaf(wz, src.pts[(long long)C * src.sc + n], v);
           out[o * src.out_stride + n] = activate(v, act);
         } else {
-          float cal[12];
-#pragma unroll
-          for (int i = 0; i < 12; ++i) cal[i] = calib[i];
-          float px, py, pz, x, y, z;
-          uint32_t code;
-          load_point(src, n, px, py, pz, code);
-          project_mode(cal, proj, px, py, pz, x, y, z);
-          v = fmaf(wz, __fmul_rn(z, z_scale), v);
-          v = in_image(x, y) ? activate(v, act) : outside_value(x, y, proj);  // MonoPortNet.py:89
-          if (src.packed) {
-            const int ix = code & 1023u, iy = (code >> 10) & 1023u, iz = code >> 20;
-            out[((long long)iz * src.level_res + iy) * src.level_res + ix] = v;
-          } else {
-            out[o * src.out_stride + n] = v;
-          }
+          point_epilogue(v, o, n, wz, calib, proj, z_scale, act, src, out);
         }
       }
     }
@@ -437,25 +217,39 @@ __global__ void perspective_kernel(const float *__restrict__ pts, long long n,
 }
 
 // ---- host side -----------------------------------------------------------------------------------
+int raise_lds_limit(mp_ctx *ctx, const void *kern, int bytes) {
+  if (!ctx->lds_attr_done.count(kern)) {
+    MP_HIP(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    ctx->lds_attr_done.insert(kern);
+  }
+  return MP_OK;
+}
+
+int prof_begin(mp_ctx *ctx, hipStream_t st) {
+  if (2 * (ctx->prof_used + 1) <= (int)ctx->prof_events.size())
+    MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used], st));
+  return MP_OK;
+}
+
+int prof_end(mp_ctx *ctx, hipStream_t st) {
+  if (2 * (ctx->prof_used + 1) <= (int)ctx->prof_events.size()) {
+    MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used + 1], st));
+    ++ctx->prof_used;
+  }
+  return MP_OK;
+}
+
 template <int C, int COUT, int WPS, bool DIRECT>
 static int launch_query_t(mp_ctx *ctx, const Mlp &m, const QuerySet &set, int h, int w,
                           float z_scale, long long max_points, bool device_counts,
                           hipStream_t st) {
   constexpr int lds = kTilePts * C * 4 + kHbBytes;
   auto kern = pifu_query_kernel<C, COUT, WPS, DIRECT>;
-  const void *kern_id = reinterpret_cast<const void *>(kern);
-  if (!ctx->lds_attr_done.count(kern_id)) {  // once per kernel and context (= device)
-    MP_HIP(ctx, hipFuncSetAttribute(kern_id, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    ctx->lds_attr_done.insert(kern_id);
-  }
+  if (const int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
   if (max_points <= 0) return MP_OK;
   // every frame of the set rounds its own tail tile up
   const long long tiles = (max_points + kTilePts - 1) / kTilePts + (set.n - 1);
-  const long long resident = (long long)cus_of(ctx, st) * WPS;
-  // device-side counts: launch the resident grid and let it stride; host-side counts: one
-  // workgroup per tile up to a few waves of the machine
-  long long grid = device_counts ? (tiles < resident ? tiles : resident)
-                                 : (tiles < 8 * resident ? tiles : 8 * resident);
+  const long long grid = query_grid(tiles, (long long)cus_of(ctx, st) * WPS, device_counts);
   // Launches with few 64-point tiles (long tail on 256 CUs) go to the 32-point kernel
   // (query_small.hip, same bits).  With host-side counts the choice is made here; with device-side
   // counts both kernels are launched and each looks at the counts (the excluded one leaves at its
@@ -479,8 +273,7 @@ static int launch_query_t(mp_ctx *ctx, const Mlp &m, const QuerySet &set, int h,
       }
     }
   }
-  const bool prof = 2 * (ctx->prof_used + 1) <= (int)ctx->prof_events.size();
-  if (prof) MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used], st));
+  if (const int rc = prof_begin(ctx, st)) return rc;
   if (table) {  // query_table.hip: 32-point tiles at every launch size
     small = 1;
     const int rc = launch_query_tab(ctx, m, tset, h, w, z_scale, max_points, device_counts, st);
@@ -497,10 +290,7 @@ static int launch_query_t(mp_ctx *ctx, const Mlp &m, const QuerySet &set, int h,
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kQueryThreads), lds, st, m.pack(), h, w,
                        z_scale, m.act, dset, small == 2 ? gate : 0);
   }
-  if (prof) {
-    MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used + 1], st));
-    ++ctx->prof_used;
-  }
+  if (const int rc = prof_end(ctx, st)) return rc;
   MP_HIP(ctx, hipGetLastError());
   return MP_OK;
 }

@@ -11,7 +11,7 @@
 //     file: layer 1's 128 rows x 96 points per wave are 192 accumulator registers, a layer-0 chunk
 //     48 more -- 240, which fit the 256 AGPRs, so no accumulator tile ever moves between the two
 //     register files (the 128-point tile of round 1 needed 256 + 32 and the allocator shuffled
-//     tiles and spilled 100 registers; kQ16Nb=4 still builds it);
+//     tiles and spilled 100 registers);
 //   * LDS: xs[96][hi 512 B | lo 512 B] = 96 KB + one 128-row hidden chunk [96][hi 256 B | lo 256 B]
 //     = 48 KB (144 KB, one workgroup per CU);
 //   * layer 0 is produced in 128-row chunks -- one row block x all three column blocks per wave, so
@@ -28,7 +28,7 @@
 // Status (round 2): 1 M points in 6.44-6.60 ms = 160 M points/s (2.7x the f32 kernel) = 375-385
 // TFLOP/s-equivalent = 0.45-0.46 of the three-MFMA-per-product roof (2.5 PFLOP/s / 3); 0.44 over a
 // reconstruction's launches (128-point tile: 0.42).
-// What bounds it (side builds, tools/ablate.py -DMP16_ABLATE=..., profiles/r02w_f16x3_ablation.txt):
+// What bounds it (side builds with parts of the kernel left out, profiles/r02w_f16x3_ablation.txt):
 // removing the layer-0 conversion buys 2 %, the barriers 1.6 %, the LDS reads 4 % -- and removing
 // the WEIGHT LOADS 27 % (6.60 -> 4.81 ms; layers 0-1 alone 4.42 -> 3.03 ms against a 2.69 ms MFMA
 // floor).  The loads' cost is ADDITIVE, ~76 cycles of a SIMD's matrix-pipe time per 1-KB fragment
@@ -45,8 +45,8 @@
 // 96 points per tile, 707 at 128): 0.45-0.47 of the roof here; 0.6 would need a tile of >= 240 points
 // = 240 KB of split features in LDS.  The f32 kernel streams the same bytes per point but spends 4x
 // the matrix-pipe time per fragment, which is why it sits at 0.91.  Also measured and dropped: a
-// software-pipelined layer-0/1 loop over 32-row chunks (6.97 vs 6.65 ms), kQ16Cs=2 (column split,
-// duplicated loads: 9.3 ms) and the skip-connection MFMAs of layer 1 issued under the layer-0
+// software-pipelined layer-0/1 loop over 32-row chunks (6.97 vs 6.65 ms), a column split over eight waves
+// (duplicated loads: 9.3 ms; see the kernel) and the skip-connection MFMAs of layer 1 issued under the layer-0
 // conversion (correct, the interleave comes out as written, neutral: 6.60-6.62 vs 6.57-6.59 ms).
 #include <cstdlib>
 #include <type_traits>
@@ -65,13 +65,6 @@ typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 constexpr int kThreads16 = 256;  // 4 waves = one per SIMD, each with the full 512-register file
 constexpr int kXRow = 1024;      // bytes per point in xs: 32 hi slots | 32 lo slots (16 B each)
 constexpr int kHRow = 256;       // bytes per point in the hidden chunk: 8 hi slots | 8 lo slots
-constexpr int kQ16Nb = 3;  // tile shape the launcher instantiates (see pifu_query16_kernel)
-// column split: 2 = eight waves, two per SIMD (see the kernel).  Correct (the f16 tests pass with
-// it) but MEASURED SLOWER for f16x3 -- 1 M points 9.3 ms vs 7.0 ms: 128 accumulator registers + the
-// A ring + double-buffered hi/lo B fragments do not fit 256 registers (103 spilled, scratch traffic
-// inside the chunk loop) and both waves of a row group load every weight fragment.  Plain f16 gains
-// 5 % (3.63 vs 3.82 ms).  Kept for tools/ablate.py; the product uses 1.
-constexpr int kQ16Cs = 1;
 
 struct AFrag {
   h8 hi, lo;
@@ -249,23 +242,6 @@ __device__ __forceinline__ void finish16(f32x16 &v, float inv_scale) {
   }
 }
 
-// C-layout tile (rows 32 rb_local + 8q + 4hh + i of point p = 32 cb + j) -> hidden chunk halves:
-// hi slot 4 rb_local + q, lo slot 8 + that, 8 bytes at offset 8 hh inside the slot.
-__device__ __forceinline__ void store_hidden16(unsigned char *hb, const f32x16 &v, int rb_local,
-                                               int cb, int j, int hh) {
-  const int p = 32 * cb + j;
-  unsigned char *row = hb + p * kHRow + 8 * hh;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const f32x4 f = {v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
-    h4 hi, lo;
-    split4(f, hi, lo);
-    const int slot = 4 * rb_local + q;
-    *reinterpret_cast<h4 *>(row + ((slot ^ (p & 15)) << 4)) = hi;
-    *reinterpret_cast<h4 *>(row + (((8 + slot) ^ (p & 15)) << 4)) = lo;
-  }
-}
-
 // registers 4q .. 4q+3 of a C-layout tile (rows 32 rb_local + 8q + 4hh + i of point p = 32 cb + j):
 // y = lrelu(acc / S), split, store into the 128-row chunk buffer of the 96-point tile: 512 bytes
 // per point = 16 hi slots | 16 lo slots, row block rb_local (= the wave) owns slots 4 rb_local .. +3
@@ -307,76 +283,46 @@ __device__ __forceinline__ void store_hidden16_part(unsigned char *hb, const f32
   }
 }
 
-// NB = 32-point column blocks per tile: 3 = the 96-point tile described above (the product);
-// 4 = round 1's 128-point tile (160 KB of LDS, 64-row layer-0 chunks computed by two waves per row
-// block: 0.42 of the roof over a reconstruction vs 0.44; build it with -DMP16_SGB=0, the
-// interleaved prefetches spill next to its 288 accumulator registers: 9.7 ms); 2 = a 64-point tile with half the LDS,
-// two workgroups per CU (the partner hides barriers and epilogues, at twice the weight bytes per
-// point).  Measured (1 M points, -DMP16_NB=2): f16x3 11.3 ms, plain f16 4.4 vs 4.0 -- weight
-// streaming wins.
-//
-// CS = column split: 1 = four waves, each with all NB column blocks of its rows (one wave per SIMD,
-// 512 registers); 2 = EIGHT waves -- wave (rg, cg) owns row group rg (as before) but only the column
-// blocks [cg NB/2, +NB/2) -- so every SIMD holds two waves of 256 registers: while one converts a
-// chunk (VALU) or waits at a barrier / for the gather, the other keeps the matrix pipe busy.  Both
-// waves of a row group stream the same weight fragments (the second one hits the CU's L1); LDS
-// traffic, MFMA count and the chunk-buffer layout are unchanged.
-template <int COUT, int TERMS, int NB, int CS>
-__global__ __launch_bounds__(kThreads16 * CS, NB >= 3 ? CS : 2) void pifu_query16_kernel(
+// One tile shape: 96 points = three 32-point column blocks, four waves that each hold all three column blocks
+// of their rows.  The kernel was a template over the column blocks per tile and a column split until commit
+// 90bb2b1; what the other shapes measured (1 M points):
+//   * four column blocks (round 1's 128-point tile, 160 KB of LDS, 64-row layer-0 chunks computed by two waves
+//     per row block): 0.42 of the roof over a reconstruction vs 0.44; with the interleaved prefetches next to
+//     its 288 accumulator registers it spilled: 9.7 ms;
+//   * two column blocks (a 64-point tile with half the LDS, two workgroups per CU: the partner hides barriers
+//     and epilogues, at twice the weight bytes per point): f16x3 11.3 ms, plain f16 4.4 vs 4.0 -- weight
+//     streaming wins;
+//   * the 128-point tile split by columns over EIGHT waves, two per SIMD with 256 registers each, so that one
+//     keeps the matrix pipe busy while the other converts a chunk or waits at a barrier: correct (the f16 tests
+//     passed with it) but f16x3 took 9.3 ms vs 7.0 ms -- 128 accumulator registers + the A ring + double-buffered
+//     hi/lo B fragments did not fit 256 registers (103 spilled, scratch traffic inside the chunk loop) and both
+//     waves of a row group loaded every weight fragment.  Plain f16 gained 5 % (3.63 vs 3.82 ms).
+template <int COUT, int TERMS>
+__global__ __launch_bounds__(kThreads16, 1) void pifu_query16_kernel(
     MlpPack mlp32, MlpPack16 mlp, int fh, int fw, float z_scale, int act, QuerySetDev set) {
   constexpr int C = 256;
-  constexpr int NGX = C / 16;        // k16 groups of the feature segment
-  constexpr int P = 32 * NB;         // points per tile
-  constexpr int THREADS = kThreads16 * CS;
-  constexpr int NBW = NB / CS;       // column blocks per wave in layers 1-3
-  constexpr int NR0 = NB == 3 ? 3 : NB / 2 / CS;  // column blocks per wave in a layer-0 chunk
-  constexpr int PW = P / (4 * CS);   // points gathered per wave
-  static_assert(CS == 1 || (CS == 2 && NB == 4), "column split is built for the 128-point tile");
+  constexpr int NGX = C / 16;  // k16 groups of the feature segment
+  constexpr int NB = 3;        // 32-point column blocks per tile
+  constexpr int P = 32 * NB;   // points per tile
+  constexpr int PW = P / 4;    // points gathered per wave
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char *xs = smem;
   unsigned char *hb = smem + P * kXRow;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wv = wave & 3;           // 0..3 = row group of layers 1-3
-  const int cbase = (wave >> 2) * NBW;  // first column block of this wave in layers 1-3
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);  // 0..3 = row group of layers 1-3
   const int j = lane & 31, hh = lane >> 5;
   const int swz = hh ^ (j & 15);
-  // layer-0 chunk (2 row blocks x NB column blocks): row block / first column block of this wave
-  const int rb0 = CS == 1 ? wv >> 1 : wave & 1;
-  const int c0 = CS == 1 ? NR0 * (wv & 1) : wave >> 1;
 
-  // The tiles of all frames of the set form one index space: frame f owns the next
-  // ceil(n_f / tile) global tiles.  The owner of a global tile is looked up from the (device-side)
-  // counts at the top of every iteration -- eight scalar loads -- instead of keeping a prefix
-  // table alive in SGPRs across the whole MLP.
   const float *wbase = mlp32.base;  // last layer (VALU) only
   const WStream w32 = make_wstream(mlp32.base, mlp32.n_floats, lane);        // biases
   const WStream ws = make_wstream(static_cast<const float *>(mlp.base), mlp.n16 * 4, lane);  // f16 fragments
 
   for (long long gtile = blockIdx.x;; gtile += gridDim.x) {
-    int fi = -1;
-    long long tile0 = 0;
-    {
-      long long acc = 0;
-      // groups of 8 frames: the 8 count loads of a group are in flight together, and the dynamic group offset
-      // keeps the compiler from hoisting all kMaxFrames kernel-argument loads into SGPRs (spills)
-      for (int f0 = 0; f0 < set.n; f0 += 8)
-#pragma unroll
-      for (int fk = 0; fk < 8; ++fk) {
-        const int f = f0 + fk;
-        if (f < set.n) {
-          const long long nf = set.count(f);
-          const long long t = (nf + P - 1) / P;
-          if (fi < 0 && gtile < acc + t) {
-            fi = f;
-            tile0 = acc;
-          }
-          acc += t;
-        }
-      }
-    }
+    int fi;
+    long long tile0;
+    tile_owner<P>(set, gtile, fi, tile0);
     if (fi < 0) break;  // past the last tile of the last frame
     const QueryItem item = set.item(fi);
     const float *__restrict__ feat = item.feat;
@@ -399,7 +345,7 @@ __global__ __launch_bounds__(kThreads16 * CS, NB >= 3 ? CS : 2) void pifu_query1
         Taps t[GB];
 #pragma unroll
         for (int u = 0; u < GB; ++u) {
-          const long long n = n0 + PW * wave + i0 + u;
+          const long long n = n0 + PW * wv + i0 + u;
           const bool live_n = n < n_pts;
           float px = 0, py = 0, pz = 0, x, y, z;
           uint32_t code;
@@ -415,7 +361,7 @@ __global__ __launch_bounds__(kThreads16 * CS, NB >= 3 ? CS : 2) void pifu_query1
             v[u][k] = *reinterpret_cast<const f32x4 *>(feat + t[u].o[k] + 4 * lane);
 #pragma unroll
         for (int u = 0; u < GB; ++u) {
-          const int p = PW * wave + i0 + u;
+          const int p = PW * wv + i0 + u;
           const f32x4 r = blend(v[u][0], v[u][1], v[u][2], v[u][3], t[u]);
           h4 hi, lo;
           split4(r, hi, lo);
@@ -439,20 +385,16 @@ __global__ __launch_bounds__(kThreads16 * CS, NB >= 3 ? CS : 2) void pifu_query1
     }
     __syncthreads();
 
-    const unsigned char *xrow = xs + (32 * cbase + j) * kXRow;  // this wave's first column block
-    const unsigned char *hrow = hb + (32 * cbase + j) * kHRow;
-    const unsigned char *xrow0 = xs + j * kXRow;                // column block 0 (layer-0 chunks)
-    ZPair zw[NBW];  // z_feat of this wave's column blocks
-#pragma unroll
-    for (int n = 0; n < NBW; ++n) zw[n] = zc[cbase + n];
+    const unsigned char *xrow = xs + j * kXRow;  // this lane's point row, column block 0
+    const unsigned char *hrow = hb + j * kHRow;
 
-    // ---------------- layers 0 + 1, fused over 64-row chunks of layer 0 ----------------
-    f32x16 acc1[4][NBW];  // layer-1 rows [128 wv, +128) x this wave's points (256 / CS registers)
+    // ---------------- layers 0 + 1, fused over 128-row chunks of layer 0 ----------------
+    f32x16 acc1[4][NB];  // layer-1 rows [128 wv, +128) x the tile's points
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       init_from_bias16(acc1[m][0], w32, mlp32.bias[1] + 32 * (4 * wv + m), mlp.scale[1]);
 #pragma unroll
-      for (int n = 1; n < NBW; ++n) acc1[m][n] = acc1[m][0];
+      for (int n = 1; n < NB; ++n) acc1[m][n] = acc1[m][0];
     }
     {
       const int a0 = mlp.ax[0];                 // [rb][g][part][lane]
@@ -460,90 +402,55 @@ __global__ __launch_bounds__(kThreads16 * CS, NB >= 3 ? CS : 2) void pifu_query1
       const int a1 = mlp.ah[1] + (4 * wv) * rs1;
       const float inv0 = 1.0f / mlp.scale[0];
       AFrag ring0[4][1];
-      f32x16 acc0[1][NR0];
+      f32x16 acc0[1][NB];
       const int a1x = mlp.ax[1] + (4 * wv) * NGX * 128;
-      if constexpr (NB == 3) {
-        // 96-point tile: a chunk is 128 rows of layer 0 = one row block x all three column blocks
-        // per wave -- every layer-0 weight fragment is loaded by exactly one wave and feeds 9 MFMAs
-        // -- and 8 k16 groups of layer 1; 240 accumulator registers (192 + 48) fit the AGPR file.
-        static_assert(CS == 1, "the 96-point tile has no column split");
-        const unsigned char *hrow1 = hb + j * kHRow128;
-        seg_prefetch16<1, 3, TERMS>(ring0, ws, a0 + wv * NGX * 128, 0, NGX);
-        init_from_bias16(acc0[0][0], w32, mlp32.bias[0] + 32 * wv, mlp.scale[0]);
+      // a chunk is 128 rows of layer 0 = one row block x all three column blocks per wave -- every
+      // layer-0 weight fragment is loaded by exactly one wave and feeds 9 MFMAs -- and 8 k16 groups
+      // of layer 1; 240 accumulator registers (192 + 48) fit the AGPR file.
+      const unsigned char *hrow1 = hb + j * kHRow128;
+      seg_prefetch16<1, 3, TERMS>(ring0, ws, a0 + wv * NGX * 128, 0, NGX);
+      init_from_bias16(acc0[0][0], w32, mlp32.bias[0] + 32 * wv, mlp.scale[0]);
 #pragma unroll
-        for (int n = 1; n < NB; ++n) acc0[0][n] = acc0[0][0];
+      for (int n = 1; n < NB; ++n) acc0[0][n] = acc0[0][0];
 #pragma unroll 1
-        for (int ck = 0; ck < kHidden[0] / 128; ++ck) {
-          const int rb = 4 * ck + wv;
-          seg_main16<1, NB, 3, kXRow, 32, TERMS>(acc0, ring0, ws, a0 + rb * NGX * 128, 0, NGX, xrow0, swz);
-          AFrag ring1[2][4];
-          seg_prefetch16<4, 1, TERMS>(ring1, ws, a1 + ck * 8 * 128, rs1, 8);
-          gemm_z16<1, NB, TERMS>(acc0, ws, mlp.az[0] + rb * 128, zc);
-#pragma unroll
-          for (int n = 0; n < NB; ++n)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) convert_store_q128(hb, acc0[0][n], q, wv, n, j, hh, inv0);
-          const int rbn = min(rb + 4, kHidden[0] / 32 - 4 + wv);
-          seg_prefetch16<1, 3, TERMS>(ring0, ws, a0 + rbn * NGX * 128, 0, NGX);
-          init_from_bias16(acc0[0][0], w32, mlp32.bias[0] + 32 * rbn, mlp.scale[0]);
-#pragma unroll
-          for (int n = 1; n < NB; ++n) acc0[0][n] = acc0[0][0];
-          __syncthreads();
-          seg_main16<4, NB, 1, kHRow128, 16, TERMS>(acc1, ring1, ws, a1 + ck * 8 * 128, rs1, 8, hrow1, swz);
-          __syncthreads();
-        }
-      } else {
-      ZPair z0[NR0];
-#pragma unroll
-      for (int n = 0; n < NR0; ++n) z0[n] = zc[c0 + n];
-      seg_prefetch16<1, 3, TERMS>(ring0, ws, a0 + rb0 * NGX * 128, 0, NGX);
-      init_from_bias16(acc0[0][0], w32, mlp32.bias[0] + 32 * rb0, mlp.scale[0]);
-#pragma unroll
-      for (int n = 1; n < NR0; ++n) acc0[0][n] = acc0[0][0];
-#pragma unroll 1
-      for (int ck = 0; ck < kHidden[0] / 64; ++ck) {
-        // layer-0 rows [64 ck + 32 rb0, +32) x column blocks [NR0 cp0, +NR0)
-        const int rb = 2 * ck + rb0;
-        seg_main16<1, NR0, 3, kXRow, 32, TERMS>(acc0, ring0, ws, a0 + rb * NGX * 128, 0, NGX,
-                                         xrow0 + c0 * 32 * kXRow, swz);
+      for (int ck = 0; ck < kHidden[0] / 128; ++ck) {
+        const int rb = 4 * ck + wv;
+        seg_main16<1, NB, 3, kXRow, 32, TERMS>(acc0, ring0, ws, a0 + rb * NGX * 128, 0, NGX, xrow, swz);
         AFrag ring1[2][4];
-        seg_prefetch16<4, 1, TERMS>(ring1, ws, a1 + ck * 4 * 128, rs1, 4);
-        gemm_z16<1, NR0, TERMS>(acc0, ws, mlp.az[0] + rb * 128, z0);
+        seg_prefetch16<4, 1, TERMS>(ring1, ws, a1 + ck * 8 * 128, rs1, 8);
+        gemm_z16<1, NB, TERMS>(acc0, ws, mlp.az[0] + rb * 128, zc);
 #pragma unroll
-        for (int n = 0; n < NR0; ++n) {
-          finish16(acc0[0][n], inv0);
-          store_hidden16(hb, acc0[0][n], rb0, c0 + n, j, hh);
-        }
-        // next chunk's layer-0 operands stream in underneath the layer-1 MFMAs
-        const int rbn = min(rb + 2, kHidden[0] / 32 - 2 + rb0);
+        for (int n = 0; n < NB; ++n)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) convert_store_q128(hb, acc0[0][n], q, wv, n, j, hh, inv0);
+        const int rbn = min(rb + 4, kHidden[0] / 32 - 4 + wv);
         seg_prefetch16<1, 3, TERMS>(ring0, ws, a0 + rbn * NGX * 128, 0, NGX);
         init_from_bias16(acc0[0][0], w32, mlp32.bias[0] + 32 * rbn, mlp.scale[0]);
 #pragma unroll
-        for (int n = 1; n < NR0; ++n) acc0[0][n] = acc0[0][0];
+        for (int n = 1; n < NB; ++n) acc0[0][n] = acc0[0][0];
         __syncthreads();
-        seg_main16<4, NBW, 1, kHRow, 8, TERMS>(acc1, ring1, ws, a1 + ck * 4 * 128, rs1, 4, hrow, swz);
+        seg_main16<4, NB, 1, kHRow128, 16, TERMS>(acc1, ring1, ws, a1 + ck * 8 * 128, rs1, 8, hrow1, swz);
         __syncthreads();
-      }
       }
       // skip segment + z column of layer 1
       AFrag ring1[2][4];
       seg_prefetch16<4, 1, TERMS>(ring1, ws, a1x, NGX * 128, NGX);
-      seg_main16<4, NBW, 1, kXRow, 32, TERMS>(acc1, ring1, ws, a1x, NGX * 128, NGX, xrow, swz);
-      gemm_z16<4, NBW, TERMS>(acc1, ws, mlp.az[1] + (4 * wv) * 128, zw);
+      seg_main16<4, NB, 1, kXRow, 32, TERMS>(acc1, ring1, ws, a1x, NGX * 128, NGX, xrow, swz);
+      gemm_z16<4, NB, TERMS>(acc1, ws, mlp.az[1] + (4 * wv) * 128, zc);
       const float inv1 = 1.0f / mlp.scale[1];
 #pragma unroll
       for (int m = 0; m < 4; ++m)
 #pragma unroll
-        for (int n = 0; n < NBW; ++n) finish16(acc1[m][n], inv1);
+        for (int n = 0; n < NB; ++n) finish16(acc1[m][n], inv1);
     }
 
     // ---------------- layer 2: rows [64 wv, +64) x 128 points ----------------
-    f32x16 acc2[2][NBW];
+    f32x16 acc2[2][NB];
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
       init_from_bias16(acc2[m][0], w32, mlp32.bias[2] + 32 * (2 * wv + m), mlp.scale[2]);
 #pragma unroll
-      for (int n = 1; n < NBW; ++n) acc2[m][n] = acc2[m][0];
+      for (int n = 1; n < NB; ++n) acc2[m][n] = acc2[m][0];
     }
     {
       const int rs2 = (kHidden[1] / 16) * 128;
@@ -553,28 +460,28 @@ __global__ __launch_bounds__(kThreads16 * CS, NB >= 3 ? CS : 2) void pifu_query1
 #pragma unroll
       for (int ck = 0; ck < 8; ++ck) {
 #pragma unroll
-        for (int n = 0; n < NBW; ++n) store_hidden16_part(hb, acc1[ck >> 1][n], ck & 1, wv, cbase + n, j, hh);
+        for (int n = 0; n < NB; ++n) store_hidden16_part(hb, acc1[ck >> 1][n], ck & 1, wv, n, j, hh);
         __syncthreads();
-        seg_main16<2, NBW, 1, kHRow, 8, TERMS>(acc2, ring2, ws, a2 + ck * 4 * 128, rs2, 4, hrow, swz);
+        seg_main16<2, NB, 1, kHRow, 8, TERMS>(acc2, ring2, ws, a2 + ck * 4 * 128, rs2, 4, hrow, swz);
         if (ck < 7) seg_prefetch16<2, 1, TERMS>(ring2, ws, a2 + (ck + 1) * 4 * 128, rs2, 4);
         __syncthreads();
       }
       const int a2x = mlp.ax[2] + (2 * wv) * NGX * 128;
       seg_prefetch16<2, 1, TERMS>(ring2, ws, a2x, NGX * 128, NGX);
-      seg_main16<2, NBW, 1, kXRow, 32, TERMS>(acc2, ring2, ws, a2x, NGX * 128, NGX, xrow, swz);
-      gemm_z16<2, NBW, TERMS>(acc2, ws, mlp.az[2] + (2 * wv) * 128, zw);
+      seg_main16<2, NB, 1, kXRow, 32, TERMS>(acc2, ring2, ws, a2x, NGX * 128, NGX, xrow, swz);
+      gemm_z16<2, NB, TERMS>(acc2, ws, mlp.az[2] + (2 * wv) * 128, zc);
       const float inv2 = 1.0f / mlp.scale[2];
 #pragma unroll
       for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int n = 0; n < NBW; ++n) finish16(acc2[m][n], inv2);
+        for (int n = 0; n < NB; ++n) finish16(acc2[m][n], inv2);
     }
 
     // ---------------- layer 3: rows [32 wv, +32) x 128 points ----------------
-    f32x16 acc3[1][NBW];
+    f32x16 acc3[1][NB];
     init_from_bias16(acc3[0][0], w32, mlp32.bias[3] + 32 * wv, mlp.scale[3]);
 #pragma unroll
-    for (int n = 1; n < NBW; ++n) acc3[0][n] = acc3[0][0];
+    for (int n = 1; n < NB; ++n) acc3[0][n] = acc3[0][0];
     {
       const int a3 = mlp.ah[3] + wv * (kHidden[2] / 16) * 128;
       AFrag ring3[4][1];
@@ -582,24 +489,24 @@ __global__ __launch_bounds__(kThreads16 * CS, NB >= 3 ? CS : 2) void pifu_query1
 #pragma unroll
       for (int ck = 0; ck < 4; ++ck) {
 #pragma unroll
-        for (int n = 0; n < NBW; ++n) store_hidden16_part(hb, acc2[ck >> 1][n], ck & 1, wv, cbase + n, j, hh);
+        for (int n = 0; n < NB; ++n) store_hidden16_part(hb, acc2[ck >> 1][n], ck & 1, wv, n, j, hh);
         __syncthreads();
-        seg_main16<1, NBW, 3, kHRow, 8, TERMS>(acc3, ring3, ws, a3 + ck * 4 * 128, 0, 4, hrow, swz);
+        seg_main16<1, NB, 3, kHRow, 8, TERMS>(acc3, ring3, ws, a3 + ck * 4 * 128, 0, 4, hrow, swz);
         if (ck < 3) seg_prefetch16<1, 3, TERMS>(ring3, ws, a3 + (ck + 1) * 4 * 128, 0, 4);
         __syncthreads();
       }
       const int a3x = mlp.ax[3] + wv * NGX * 128;
       seg_prefetch16<1, 3, TERMS>(ring3, ws, a3x, 0, NGX);
-      seg_main16<1, NBW, 3, kXRow, 32, TERMS>(acc3, ring3, ws, a3x, 0, NGX, xrow, swz);
-      gemm_z16<1, NBW, TERMS>(acc3, ws, mlp.az[3] + wv * 128, zw);
+      seg_main16<1, NB, 3, kXRow, 32, TERMS>(acc3, ring3, ws, a3x, 0, NGX, xrow, swz);
+      gemm_z16<1, NB, TERMS>(acc3, ws, mlp.az[3] + wv * 128, zc);
       const float inv3 = 1.0f / mlp.scale[3];
 #pragma unroll
-      for (int n = 0; n < NBW; ++n) finish16(acc3[0][n], inv3);
+      for (int n = 0; n < NB; ++n) finish16(acc3[0][n], inv3);
     }
 
     // ---------------- layer 4 (Cout x (128 + C + 1)) on the VALU, f32 ----------------
     // red[part][o][p]: parts 0-3 = hidden rows of wave `part`, parts 4.. = slices of the features
-    constexpr int FP = THREADS / P;     // feature slices (threads per point)
+    constexpr int FP = kThreads16 / P;     // feature slices (threads per point)
     constexpr int SL = 32 / FP;         // 8-channel slots per slice
     float *red = reinterpret_cast<float *>(hb);
     constexpr int K4 = (kHidden[3] + C + 1 + 3) & ~3;  // padded row stride (pack.hip)
@@ -607,21 +514,21 @@ __global__ __launch_bounds__(kThreads16 * CS, NB >= 3 ? CS : 2) void pifu_query1
 #pragma unroll
       for (int o = 0; o < COUT; ++o) {
         const float *w4 = wbase + mlp32.w4 + o * K4 + 32 * wv + 4 * hh;
-        float sv[NBW];
+        float sv[NB];
 #pragma unroll
-        for (int n = 0; n < NBW; ++n) sv[n] = 0.0f;
+        for (int n = 0; n < NB; ++n) sv[n] = 0.0f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const f32x4 wq = *reinterpret_cast<const f32x4 *>(w4 + 8 * q);
 #pragma unroll
           for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int n = 0; n < NBW; ++n) sv[n] = fmaf(wq[i], acc3[0][n][4 * q + i], sv[n]);
+            for (int n = 0; n < NB; ++n) sv[n] = fmaf(wq[i], acc3[0][n][4 * q + i], sv[n]);
         }
 #pragma unroll
-        for (int n = 0; n < NBW; ++n) {
+        for (int n = 0; n < NB; ++n) {
           sv[n] += __shfl_xor(sv[n], 32);
-          if (hh == 0) red[(wv * COUT + o) * P + 32 * (cbase + n) + j] = sv[n];
+          if (hh == 0) red[(wv * COUT + o) * P + 32 * (n) + j] = sv[n];
         }
       }
       // feature part: thread = (point, slice of the channels); x = hi + lo
@@ -646,28 +553,14 @@ __global__ __launch_bounds__(kThreads16 * CS, NB >= 3 ? CS : 2) void pifu_query1
         if (hf < FP) red[((4 + hf) * COUT + o) * P + p] = sx[o];
     }
     __syncthreads();
-    for (int idx = tid; idx < COUT * P; idx += THREADS) {
+    for (int idx = tid; idx < COUT * P; idx += kThreads16) {
       const int o = idx / P, p = idx % P;
       const long long n = n0 + p;
       if (n < n_pts) {
         float v = (wbase + mlp32.bias[4])[o];
 #pragma unroll
         for (int part = 0; part < 4 + FP; ++part) v += red[(part * COUT + o) * P + p];
-        float cal[12];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) cal[i] = calib[i];
-        float px, py, pz, x, y, z;
-        uint32_t code;
-        load_point(src, n, px, py, pz, code);
-        project_mode(cal, proj, px, py, pz, x, y, z);
-        v = fmaf((wbase + mlp32.w4)[o * K4 + kHidden[3] + C], __fmul_rn(z, z_scale), v);
-        v = in_image(x, y) ? activate(v, act) : outside_value(x, y, proj);  // MonoPortNet.py:89
-        if (src.packed) {
-          const int ix = code & 1023u, iy = (code >> 10) & 1023u, iz = code >> 20;
-          out[((long long)iz * src.level_res + iy) * src.level_res + ix] = v;
-        } else {
-          out[o * src.out_stride + n] = v;
-        }
+        point_epilogue(v, o, n, (wbase + mlp32.w4)[o * K4 + kHidden[3] + C], calib, proj, z_scale, act, src, out);
       }
     }
     __syncthreads();  // red / xs are rewritten by the next tile
@@ -718,27 +611,9 @@ __global__ __launch_bounds__(kThreads16, 1) void pifu_query16_tab_kernel(MlpPack
   __syncthreads();
 
   for (long long gtile = blockIdx.x;; gtile += gridDim.x) {
-    int fi = -1;
-    long long tile0 = 0;
-    {
-      long long acc = 0;
-      // groups of 8 frames: the 8 count loads of a group are in flight together, and the dynamic group offset
-      // keeps the compiler from hoisting all kMaxFrames kernel-argument loads into SGPRs (spills)
-      for (int f0 = 0; f0 < set.n; f0 += 8)
-#pragma unroll
-      for (int fk = 0; fk < 8; ++fk) {
-        const int f = f0 + fk;
-        if (f < set.n) {
-          const long long nf = set.count(f);
-          const long long t = (nf + P - 1) / P;
-          if (fi < 0 && gtile < acc + t) {
-            fi = f;
-            tile0 = acc;
-          }
-          acc += t;
-        }
-      }
-    }
+    int fi;
+    long long tile0;
+    tile_owner<P>(set, gtile, fi, tile0);
     if (fi < 0) break;
     const QueryItem item = set.item(fi);
     const float *__restrict__ calib = item.calib;
@@ -982,18 +857,10 @@ __global__ __launch_bounds__(kThreads16, 1) void pifu_query16_tab_kernel(MlpPack
         uint32_t code;
         load_point(src, n, px, py, pz, code);
         project_mode(cal, proj, px, py, pz, x, y, z);
-        const bool inside = in_image(x, y);
-        const Taps t = make_taps(x, y, fh, fw, kTableRows, inside);
+        const Taps t = make_taps(x, y, fh, fw, kTableRows, in_image(x, y));
         const float *row = item.l0 + kTableL[4] + o;
         v += fmaf(row[t.o[3]], t.w[3], fmaf(row[t.o[2]], t.w[2], fmaf(row[t.o[1]], t.w[1], __fmul_rn(row[t.o[0]], t.w[0]))));
-        v = fmaf((wbase + mlp32.w4)[o * K4 + kHidden[3] + 256], __fmul_rn(z, z_scale), v);
-        v = inside ? activate(v, act) : outside_value(x, y, proj);  // MonoPortNet.py:89
-        if (src.packed) {
-          const int ix = code & 1023u, iy = (code >> 10) & 1023u, iz = code >> 20;
-          out[((long long)iz * src.level_res + iy) * src.level_res + ix] = v;
-        } else {
-          out[o * src.out_stride + n] = v;
-        }
+        finish_point(v, o, n, (wbase + mlp32.w4)[o * K4 + kHidden[3] + 256], x, y, z, code, proj, z_scale, act, src, out);
       }
     }
     __syncthreads();  // red / hb are rewritten by the next tile
@@ -1005,63 +872,43 @@ static int launch_query16_tab_t(mp_ctx *ctx, const Mlp &m, const QuerySet &set, 
                                 long long max_points, bool device_counts, hipStream_t st) {
   constexpr int P = 96;
   auto kern = pifu_query16_tab_kernel<COUT, TERMS>;
-  const void *kern_id = reinterpret_cast<const void *>(kern);
-  if (!ctx->lds_attr_done.count(kern_id)) {
-    MP_HIP(ctx, hipFuncSetAttribute(kern_id, hipFuncAttributeMaxDynamicSharedMemorySize, kQ16TabLds));
-    ctx->lds_attr_done.insert(kern_id);
-  }
+  if (const int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kern), kQ16TabLds)) return rc;
   if (max_points <= 0) return MP_OK;
   const long long tiles = (max_points + P - 1) / P + (set.n - 1);
-  const long long resident = (long long)cus_of(ctx, st);
-  const long long grid = device_counts ? (tiles < resident ? tiles : resident)
-                                       : (tiles < 8 * resident ? tiles : 8 * resident);
+  const long long grid = query_grid(tiles, cus_of(ctx, st), device_counts);  // one workgroup per CU
   QuerySetDev dset;
   {
     const int rc_set = compact_query_set(ctx, set, dset);
     if (rc_set != MP_OK) return rc_set;
   }
-  const bool prof = 2 * (ctx->prof_used + 1) <= (int)ctx->prof_events.size();
-  if (prof) MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used], st));
+  if (const int rc = prof_begin(ctx, st)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads16), kQ16TabLds, st, m.pack(), m.pack16(), h, w, z_scale,
                      m.act, dset);
-  if (prof) {
-    MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used + 1], st));
-    ++ctx->prof_used;
-  }
+  if (const int rc = prof_end(ctx, st)) return rc;
   MP_HIP(ctx, hipGetLastError());
   return MP_OK;
 }
 
-template <int COUT, int TERMS, int NB, int CS>
+template <int COUT, int TERMS>
 static int launch_query16_t(mp_ctx *ctx, const Mlp &m, const QuerySet &set, int h, int w,
                             float z_scale, long long max_points, bool device_counts,
                             hipStream_t st) {
-  constexpr int P = 32 * NB;
-  constexpr int lds = P * (kXRow + (NB == 3 ? kHRow128 : kHRow));
-  auto kern = pifu_query16_kernel<COUT, TERMS, NB, CS>;
-  const void *kern_id = reinterpret_cast<const void *>(kern);
-  if (!ctx->lds_attr_done.count(kern_id)) {  // once per kernel and context (= device)
-    MP_HIP(ctx, hipFuncSetAttribute(kern_id, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    ctx->lds_attr_done.insert(kern_id);
-  }
+  constexpr int P = 96;
+  constexpr int lds = P * (kXRow + kHRow128);  // 144 KB: one workgroup per CU
+  auto kern = pifu_query16_kernel<COUT, TERMS>;
+  if (const int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
   if (max_points <= 0) return MP_OK;
   const long long tiles = (max_points + P - 1) / P + (set.n - 1);
-  const long long resident = (long long)cus_of(ctx, st) * (NB >= 3 ? 1 : 2);  // 160 / 144 / 80 KB of LDS each
-  const long long grid = device_counts ? (tiles < resident ? tiles : resident)
-                                       : (tiles < 8 * resident ? tiles : 8 * resident);
+  const long long grid = query_grid(tiles, cus_of(ctx, st), device_counts);
   QuerySetDev dset;
   {
     const int rc_set = compact_query_set(ctx, set, dset);
     if (rc_set != MP_OK) return rc_set;
   }
-  const bool prof = 2 * (ctx->prof_used + 1) <= (int)ctx->prof_events.size();
-  if (prof) MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used], st));
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads16 * CS), lds, st, m.pack(), m.pack16(),
+  if (const int rc = prof_begin(ctx, st)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kThreads16), lds, st, m.pack(), m.pack16(),
                      h, w, z_scale, m.act, dset);
-  if (prof) {
-    MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used + 1], st));
-    ++ctx->prof_used;
-  }
+  if (const int rc = prof_end(ctx, st)) return rc;
   MP_HIP(ctx, hipGetLastError());
   return MP_OK;
 }
@@ -1077,7 +924,7 @@ int launch_query16(mp_ctx *ctx, const Mlp &m, const QuerySet &set, int h, int w,
   const char *t16 = getenv("MONOPORT_TAB16");
   const bool want_tab = t16 && t16[0] == 'a' ? true : t16 && t16[0] == 'o' ? false : m.precision == MP_PREC_F16X3;
   QuerySet tset;
-  if (want_tab && kQ16Nb == 3 && kQ16Cs == 1 && find_skip_tables(ctx, m, set, h, w, tset)) {
+  if (want_tab && find_skip_tables(ctx, m, set, h, w, tset)) {
     if ((long long)h * w * kTableRows * 4 >= (1LL << 31))
       return fail(ctx, MP_ERR_UNSUPPORTED, "table query: %dx%d map is too large for 32-bit table offsets", h, w);
 #define MP_Q16TCASE(CO, PREC, TERMS) \
@@ -1093,7 +940,7 @@ int launch_query16(mp_ctx *ctx, const Mlp &m, const QuerySet &set, int h, int w,
   }
 #define MP_Q16CASE(CO, PREC, TERMS)                                                         \
   if (m.cout == CO && m.precision == PREC)                                                 \
-    return launch_query16_t<CO, TERMS, kQ16Nb, kQ16Cs>(ctx, m, set, h, w, z_scale, max_points, device_counts, st);
+    return launch_query16_t<CO, TERMS>(ctx, m, set, h, w, z_scale, max_points, device_counts, st);
   MP_Q16CASE(1, MP_PREC_F16X3, 3)
   MP_Q16CASE(3, MP_PREC_F16X3, 3)
   MP_Q16CASE(1, MP_PREC_F16W, 2)

@@ -166,4 +166,127 @@ __device__ __forceinline__ float activate(float v, int act) {
   return v;
 }
 
+// ---- tiles of a launch -------------------------------------------------------------------------
+// The tiles of all frames of the set form one index space: frame f owns the next ceil(n_f / P)
+// global tiles.  The owner of a global tile is looked up from the (device-side) counts at the top
+// of every iteration -- eight scalar loads -- instead of keeping a prefix table alive in SGPRs
+// across the whole MLP.  fi = the frame that owns `gtile` (-1: past the last tile of the last
+// frame), tile0 = its first tile.  Returns the launch's tile count in tiles of PG points (the gate
+// between the two f32 kernels is stated in 64-point tiles).
+template <int P, int PG = P>
+__device__ __forceinline__ long long tile_owner(const QuerySetDev &set, long long gtile, int &fi_out,
+                                                long long &tile0_out) {
+  int fi = -1;
+  long long tile0 = 0;
+  long long acc = 0, total = 0;
+  // groups of 8 frames: the 8 count loads of a group are in flight together, and the dynamic group offset
+  // keeps the compiler from hoisting all kMaxFrames kernel-argument loads into SGPRs (spills)
+  for (int f0 = 0; f0 < set.n; f0 += 8)
+#pragma unroll
+    for (int fk = 0; fk < 8; ++fk) {
+      const int f = f0 + fk;
+      if (f < set.n) {
+        const long long nf = set.count(f);
+        const long long t = (nf + P - 1) / P;
+        if (fi < 0 && gtile < acc + t) {
+          fi = f;
+          tile0 = acc;
+        }
+        acc += t;
+        total += (nf + PG - 1) / PG;
+      }
+    }
+  fi_out = fi;
+  tile0_out = tile0;
+  return total;
+}
+
+// ---- f32 gather ----------------------------------------------------------------------------------
+// PW points per wave into the tile xs[point][C] (f32, point-major, 16-byte slots XOR-swizzled by the
+// point): a tap is one coalesced 16 B/lane read of a channels-last feature row.
+// 4 points per batch: 16 (C=256) / 32 (C=512) independent 16-byte loads in flight per lane.
+// Dead points (past the end / out of image) read a clamped in-bounds tap with weight 0, so
+// the loads need no branch and the compiler can issue the whole batch back to back.
+template <int C, int PW>
+__device__ __forceinline__ void gather_f32(unsigned char *xs, const float *__restrict__ feat, int fh, int fw,
+                                           const float (&cal)[12], int proj, const PointSrc &src,
+                                           long long n0, long long n_pts, int wv, int lane) {
+  constexpr int ROWB = C * 4;
+  constexpr int GB = 4;
+#pragma unroll 1
+  for (int i0 = 0; i0 < PW; i0 += GB) {
+    Taps t[GB];
+#pragma unroll
+    for (int u = 0; u < GB; ++u) {
+      const long long n = n0 + PW * wv + i0 + u;
+      const bool live_n = n < n_pts;
+      float px = 0, py = 0, pz = 0, x, y, z;
+      uint32_t code;
+      if (live_n) load_point(src, n, px, py, pz, code);
+      project_mode(cal, proj, px, py, pz, x, y, z);
+      t[u] = make_taps(x, y, fh, fw, C, live_n && in_image(x, y));
+    }
+    f32x4 v[GB][C / 256][4];
+#pragma unroll
+    for (int u = 0; u < GB; ++u)
+#pragma unroll
+      for (int part = 0; part < C / 256; ++part)
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          v[u][part][k] = *reinterpret_cast<const f32x4 *>(feat + t[u].o[k] + 4 * (lane + 64 * part));
+#pragma unroll
+    for (int u = 0; u < GB; ++u) {
+      const int p = PW * wv + i0 + u;
+#pragma unroll
+      for (int part = 0; part < C / 256; ++part) {
+        const int slot = lane + 64 * part;
+        const f32x4 r = blend(v[u][part][0], v[u][part][1], v[u][part][2], v[u][part][3], t[u]);
+        *reinterpret_cast<f32x4 *>(xs + p * ROWB + ((slot ^ (p & 15)) << 4)) = r;
+      }
+    }
+  }
+}
+
+// z_feat of point n as B operand of the z k-step: lanes 0-31 (h == 0) carry it, lanes 32-63 supply 0
+__device__ __forceinline__ float z_operand(const float (&cal)[12], int proj, const PointSrc &src, long long n,
+                                           long long n_pts, float z_scale, int h) {
+  float px = 0, py = 0, pz = 0, x, y, z;
+  uint32_t code;
+  if (n < n_pts) load_point(src, n, px, py, pz, code);
+  project_mode(cal, proj, px, py, pz, x, y, z);
+  return (h == 0 && n < n_pts) ? __fmul_rn(z, z_scale) : 0.0f;
+}
+
+// ---- point epilogue ------------------------------------------------------------------------------
+// v = output o of point n without its z term (weight wz); (x, y, z) = the point's projection, code = its
+// lattice node: z term, in-image mask, activation, then the lattice scatter to the level's volume or the
+// [o, n] store
+__device__ __forceinline__ void finish_point(float v, int o, long long n, float wz, float x, float y, float z,
+                                             uint32_t code, int proj, float z_scale, int act, const PointSrc &src,
+                                             float *__restrict__ out) {
+  v = fmaf(wz, __fmul_rn(z, z_scale), v);
+  v = in_image(x, y) ? activate(v, act) : outside_value(x, y, proj);  // MonoPortNet.py:89
+  if (src.packed) {
+    const int ix = code & 1023u, iy = (code >> 10) & 1023u, iz = code >> 20;
+    out[((long long)iz * src.level_res + iy) * src.level_res + ix] = v;
+  } else {
+    out[o * src.out_stride + n] = v;
+  }
+}
+
+// the same for the thread that has nothing of point n yet: the calibration is reloaded and the point
+// projected once more rather than kept live through the MLP
+__device__ __forceinline__ void point_epilogue(float v, int o, long long n, float wz, const float *__restrict__ calib,
+                                               int proj, float z_scale, int act, const PointSrc &src,
+                                               float *__restrict__ out) {
+  float cal[12];
+#pragma unroll
+  for (int i = 0; i < 12; ++i) cal[i] = calib[i];
+  float px, py, pz, x, y, z;
+  uint32_t code;
+  load_point(src, n, px, py, pz, code);
+  project_mode(cal, proj, px, py, pz, x, y, z);
+  finish_point(v, o, n, wz, x, y, z, code, proj, z_scale, act, src, out);
+}
+
 }  // namespace mp

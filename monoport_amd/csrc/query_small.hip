@@ -58,29 +58,10 @@ __global__ __launch_bounds__(kQueryThreads, kT32Wps) void pifu_query_t32_kernel(
   const WStream ws = make_wstream(mlp.base, mlp.n_floats, lane);
 
   for (long long gtile = blockIdx.x;; gtile += gridDim.x) {
-    int fi = -1;
-    long long tile0 = 0;
-    {
-      long long acc = 0, acc64 = 0;
-      // groups of 8 frames: the 8 count loads of a group are in flight together, and the dynamic group offset
-      // keeps the compiler from hoisting all kMaxFrames kernel-argument loads into SGPRs (spills)
-      for (int f0 = 0; f0 < set.n; f0 += 8)
-#pragma unroll
-      for (int fk = 0; fk < 8; ++fk) {
-        const int f = f0 + fk;
-        if (f < set.n) {
-          const long long nf = set.count(f);
-          const long long t = (nf + P - 1) / P;
-          if (fi < 0 && gtile < acc + t) {
-            fi = f;
-            tile0 = acc;
-          }
-          acc += t;
-          acc64 += (nf + kTilePts - 1) / kTilePts;
-        }
-      }
-      if (gate_tiles64 > 0 && acc64 >= gate_tiles64) break;  // the 64-point kernel serves this launch
-    }
+    int fi;
+    long long tile0;
+    const long long tiles64 = tile_owner<P, kTilePts>(set, gtile, fi, tile0);
+    if (gate_tiles64 > 0 && tiles64 >= gate_tiles64) break;  // the 64-point kernel serves this launch
     if (fi < 0) break;
     const QueryItem item = set.item(fi);
     const float *__restrict__ feat = item.feat;
@@ -97,41 +78,8 @@ __global__ __launch_bounds__(kQueryThreads, kT32Wps) void pifu_query_t32_kernel(
       float cal[12];
 #pragma unroll
       for (int i = 0; i < 12; ++i) cal[i] = calib[i];
-      constexpr int GB = 4, PW = P / 4;
-#pragma unroll 1
-      for (int i0 = 0; i0 < PW; i0 += GB) {
-        Taps t[GB];
-#pragma unroll
-        for (int u = 0; u < GB; ++u) {
-          const long long n = n0 + PW * wv + i0 + u;
-          const bool live_n = n < n_pts;
-          float px = 0, py = 0, pz = 0, x, y, z;
-          uint32_t code;
-          if (live_n) load_point(src, n, px, py, pz, code);
-          project_mode(cal, proj, px, py, pz, x, y, z);
-          t[u] = make_taps(x, y, fh, fw, C, live_n && in_image(x, y));
-        }
-        f32x4 v[GB][4];
-#pragma unroll
-        for (int u = 0; u < GB; ++u)
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            v[u][k] = *reinterpret_cast<const f32x4 *>(feat + t[u].o[k] + 4 * lane);
-#pragma unroll
-        for (int u = 0; u < GB; ++u) {
-          const int p = PW * wv + i0 + u;
-          const f32x4 r = blend(v[u][0], v[u][1], v[u][2], v[u][3], t[u]);
-          *reinterpret_cast<f32x4 *>(xs + p * ROWB + ((lane ^ (p & 15)) << 4)) = r;
-        }
-      }
-      {
-        const long long n = n0 + j;
-        float px = 0, py = 0, pz = 0, x, y, z;
-        uint32_t code;
-        if (n < n_pts) load_point(src, n, px, py, pz, code);
-        project_mode(cal, proj, px, py, pz, x, y, z);
-        zb[0] = (h == 0 && n < n_pts) ? __fmul_rn(z, z_scale) : 0.0f;
-      }
+      gather_f32<C, P / 4>(xs, feat, fh, fw, cal, proj, src, n0, n_pts, wv, lane);
+      zb[0] = z_operand(cal, proj, src, n0 + j, n_pts, z_scale, h);
     }
     __syncthreads();
 
@@ -291,21 +239,7 @@ __global__ __launch_bounds__(kQueryThreads, kT32Wps) void pifu_query_t32_kernel(
 #pragma unroll
         for (int part = 0; part < 8; ++part) v += red[(part * COUT + o) * P + p];
         const float wz = (mlp.base + mlp.w4)[o * K4 + kHidden[3] + C];
-        float cal[12];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) cal[i] = calib[i];
-        float px, py, pz, x, y, z;
-        uint32_t code;
-        load_point(src, n, px, py, pz, code);
-        project_mode(cal, proj, px, py, pz, x, y, z);
-        v = fmaf(wz, __fmul_rn(z, z_scale), v);
-        v = in_image(x, y) ? activate(v, act) : outside_value(x, y, proj);  // MonoPortNet.py:89
-        if (src.packed) {
-          const int ix = code & 1023u, iy = (code >> 10) & 1023u, iz = code >> 20;
-          out[((long long)iz * src.level_res + iy) * src.level_res + ix] = v;
-        } else {
-          out[o * src.out_stride + n] = v;
-        }
+        point_epilogue(v, o, n, wz, calib, proj, z_scale, act, src, out);
       }
     }
     __syncthreads();  // red / xs are rewritten by the next tile
@@ -322,18 +256,10 @@ int launch_query32_t(mp_ctx *ctx, const Mlp &m, const QuerySet &set, int h, int 
                      long long max_points, bool device_counts, int gate_tiles64, hipStream_t st) {
   constexpr int lds = kSmallPts * 256 * 4 + kSmallPts * kSmallHbRow;
   auto kern = pifu_query_t32_kernel<COUT>;
-  const void *kern_id = reinterpret_cast<const void *>(kern);
-  if (!ctx->lds_attr_done.count(kern_id)) {
-    MP_HIP(ctx, hipFuncSetAttribute(kern_id, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    ctx->lds_attr_done.insert(kern_id);
-  }
+  if (const int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
   if (max_points <= 0) return MP_OK;
   const long long tiles = (max_points + kSmallPts - 1) / kSmallPts + (set.n - 1);
-  const long long resident = (long long)cus_of(ctx, st) * kT32Wps;
-  // device-side counts: launch the resident grid and let it stride; host-side counts: one
-  // workgroup per tile up to a few waves of the machine
-  long long grid = device_counts ? (tiles < resident ? tiles : resident)
-                                 : (tiles < 8 * resident ? tiles : 8 * resident);
+  long long grid = query_grid(tiles, (long long)cus_of(ctx, st) * kT32Wps, device_counts);
   // gated: this kernel only works on launches of < gate_tiles64 64-point tiles
   if (gate_tiles64 > 0 && grid > 2LL * gate_tiles64 + set.n) grid = 2LL * gate_tiles64 + set.n;
   QuerySetDev dset;

@@ -99,10 +99,6 @@ constexpr int kWsShared = kWsFrames + kMaxFrames * (int)sizeof(WsFrame);
 constexpr int kWsLds = kWsShared + (int)sizeof(WsShared);
 static_assert(2 * kWsLds <= 160 * 1024, "two workgroups per CU");
 
-// timing experiments (tools/ablate.py; wrong results): the producers do no work / no barriers;
-// kWsConsumerPrio: s_setprio of the consumer waves
-#define WS_SYNC() __syncthreads()
-#define WS_MARK(i)
 constexpr int kWsTabAux = 0;  // cache policy of the table-row loads (2 = nt: stream past the L2-resident weights)
 constexpr int kWsFinishAt = 8;  // the interval (8 = T0) in which the producers store the previous tile's outputs
 constexpr int kWsSetupAt = 7;  // ... and in which they project the next tile's points
@@ -259,7 +255,7 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
         *reinterpret_cast<f32x4 *>(x + region * kWsXBytes + (st0 ^ ((8 * m + 2 * q) << 4))) = o;
       }
     };
-    WS_SYNC();  // the producers' first chunk
+    __syncthreads();  // the producers' first chunk
     int par = 0;
     for (long long gtile = tile_first;; gtile += tile_step, par ^= 1) {
       if (gtile >= tile_end) break;
@@ -289,7 +285,7 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
               for (int m = 0; m < 4; ++m) store_k(wv == 0 ? 2 : 0, acc1[m][0], m);
             }
           }
-          WS_SYNC();
+          __syncthreads();
         }
       }
       // ---------------- T0-T3: layer 2, rows [64 wv, +64); K pair p = hidden-1 rows [128 p, +128) in X[2], X[0], X[1], PB ----------------
@@ -320,7 +316,7 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
               for (int m = 0; m < 2; ++m) store_k(2, acc2[m][0], 2 * wv + m);
             }
           }
-          WS_SYNC();
+          __syncthreads();
         }
       }
       // ---------------- U0-U1: layer 3, rows [32 wv, +32), K = 256 hidden in 2 pairs ----------------
@@ -360,11 +356,11 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
               if (h == 0) red[(wv * COUT + o) * P + j] = s0;
             }
           }
-          WS_SYNC();
+          __syncthreads();
         }
       }
     }
-    WS_SYNC();  // the producers' last final pass reads `red` behind this one
+    __syncthreads();  // the producers' last final pass reads `red` behind this one
   } else {
     // =============================== producers: everything per point ===============================
     const int pw = wv - 4;  // partner of consumer wave pw
@@ -544,7 +540,7 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
     }
     prs_nxt = prs_cur;
     nxt = cur;
-    WS_SYNC();  // the first chunk
+    __syncthreads();  // the first chunk
     int prev_fi = -1, par = 0;
     long long prev_n0 = 0;
     for (long long gtile = tile_first;; gtile += tile_step, par ^= 1) {
@@ -573,27 +569,23 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
           // S7, where the producers have the least to do: the next tile's points (needed in U0) and the
           // previous tile's outputs.  Nothing is in flight at its top, so the outputs (which wait for a few
           // spilled values: s_waitcnt vmcnt(0)) go between the point load and the table rows of piece 4.
-          WS_MARK(0);
           // the next tile's points are a chain of dependent steps (count, load, divide, project, texels) on the
           // critical path of the interval: they run at raised priority -- at the consumers' priority or below, a
           // producer instruction waits ~100 cycles for an issue slot between the MFMAs
           if (kWsSetupPrio) __builtin_amdgcn_s_setprio(kWsSetupPrio);
           RawPoint raw_n = {};
           if (kWsSetupAt == 7 && loc_n.fi >= 0) point_load(loc_n.fi, loc_n.n0, raw_n);
-          WS_MARK(1);
           if (kWsFinishAt == 7 && prev_fi >= 0) finish_tile(prev, prev_fi, prev_n0);
           if (kWsP4First) job_issue(tp, prs_cur, cur, kTableL[2] + 32 * (2 * pw));  // piece 4 (layer 2, row block 2 pw) in flight
-          WS_MARK(2);
           if (kWsSetupAt == 7 && loc_n.fi >= 0) {
             point_setup(loc_n.fi, raw_n, nxt, par ^ 1);
             if (!kWsR4Late) point_r4(loc_n.fi, nxt);
             prs_nxt = table_rsrc(loc_n.fi);
           }
           if (kWsSetupPrio) __builtin_amdgcn_s_setprio(kWsProducerPrio);
-          WS_MARK(3);
           if (!kWsP4First) job_issue(tp, prs_cur, cur, kTableL[2] + 32 * (2 * pw));  // with all 64 row registers free until here
         }
-        WS_SYNC();
+        __syncthreads();
       }
       // ---------------- T0-T3, U0-U1: split jobs -- loads in one interval, blend + write in a later one ----------------
       if (kWsFinishAt == 8 && prev_fi >= 0) {  // T0: nothing else to do
@@ -602,22 +594,22 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
         if (kWsSetupPrio) __builtin_amdgcn_s_setprio(kWsProducerPrio);
       }
       loc_ahead = gtile + 2 * tile_step < tile_end ? locate_tile(tend, gtile + 2 * tile_step, lane) : no_tile;
-      WS_SYNC();  // T0: every region holds a K pair of layer 2 or is being filled with one
+      __syncthreads();  // T0: every region holds a K pair of layer 2 or is being filled with one
       piece_finish(tp, cur, kHidden[1] + 32 * (2 * pw), 2);         // T1: piece 4 -> X[2] (pair 0 was read in T0; read in T2)
       job_issue(tp, prs_cur, cur, kTableL[2] + 32 * (2 * pw + 1));  //     piece 5 in flight
-      WS_SYNC();
+      __syncthreads();
       piece_finish(tp, cur, kHidden[1] + 32 * (2 * pw + 1), 0);  // T2: piece 5 -> X[0] (pair 1 was read in T1; read in T3)
       job_issue(tp, prs_cur, cur, kTableL[3] + 32 * pw);         //     piece 6 in flight
-      WS_SYNC();
+      __syncthreads();
       if (kWsSetupAt == 7 && kWsR4Late && loc_n.fi >= 0) point_r4(loc_n.fi, nxt);  // T3: nothing else to do
-      WS_SYNC();  // T3: the consumers read pair 3 in PB and piece 5
+      __syncthreads();  // T3: the consumers read pair 3 in PB and piece 5
       piece_finish(tp, cur, kHidden[1] + kHidden[2] + 32 * pw, 3);            // U0: piece 6 -> PB (read in U1)
       if (loc_n.fi >= 0) job_issue(tp, prs_nxt, nxt, kTableL[0] + 32 * pw);  //     the next tile's chunk 0 in flight
-      WS_SYNC();
+      __syncthreads();
       if (loc_n.fi >= 0) {
         chunk_finish(tp, nxt, 0, 0);  // U1: -> X[0] (piece 5 was read in T3)
       }
-      WS_SYNC();
+      __syncthreads();
       prev_fi = loc.fi;
       prev_n0 = loc.n0;
       prev = cur;
@@ -625,7 +617,7 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
       cur = nxt;
       prs_cur = prs_nxt;
     }
-    WS_SYNC();
+    __syncthreads();
     if (prev_fi >= 0) finish_tile(prev, prev_fi, prev_n0);
   }
 }
@@ -636,10 +628,7 @@ static int launch_query_tabws_t(mp_ctx *ctx, const Mlp &m, const QuerySet &set, 
   if (max_points <= 0) return MP_OK;
   auto kern = pifu_query_tabws_kernel<COUT>;
   const void *kern_id = reinterpret_cast<const void *>(kern);
-  if (!ctx->lds_attr_done.count(kern_id)) {
-    MP_HIP(ctx, hipFuncSetAttribute(kern_id, hipFuncAttributeMaxDynamicSharedMemorySize, kWsLds));
-    ctx->lds_attr_done.insert(kern_id);
-  }
+  if (const int rc = raise_lds_limit(ctx, kern_id, kWsLds)) return rc;
   const long long tiles = (max_points + kTabPts - 1) / kTabPts + (set.n - 1);
   // MONOPORT_QUERY_WGS_PER_CU (measurement switch, results do not depend on it): 2 = the kernel takes both
   // workgroup slots of every CU (all of its LDS); 1 = half of them, so that a launch of ANOTHER stream -- a second
@@ -769,10 +758,7 @@ int launch_skip_table(mp_ctx *ctx, const Mlp &m, const float *feat_hwc, int h, i
   constexpr int lds = 64 * 256 * 4;
   const void *kern_id = m.cout == 1 ? reinterpret_cast<const void *>(skip_table_kernel<1>)
                                     : reinterpret_cast<const void *>(skip_table_kernel<3>);
-  if (!ctx->lds_attr_done.count(kern_id)) {
-    MP_HIP(ctx, hipFuncSetAttribute(kern_id, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    ctx->lds_attr_done.insert(kern_id);
-  }
+  if (const int rc = raise_lds_limit(ctx, kern_id, lds)) return rc;
   const long long tiles = texels / 64, resident = (long long)cus_of(ctx, st) * 2;
   const dim3 grid((unsigned)(tiles < resident ? tiles : resident));
   if (m.cout == 1)

@@ -223,97 +223,12 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
     for (int cb = 0; cb < 2; ++cb) zb[cb] = h == 0 ? column_z<C, DIRECT, LATTICE>(set, 32 * cb + j, magic, n0, n_pts, ncol, z_scale, false) : 0.0f;
     __syncthreads();
 
-    const unsigned char *xrow = xs + j * ROWB;       // this lane's column row, column block 0
-    const unsigned char *hrow = hb + j * kHbRowBytes;
-
-    // ---------------- layers 0 + 1, fused over 64-row chunks of layer 0 (as query.hip) ----------------
-    f32x16 acc1[4][2];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      init_from_bias(acc1[m][0], ws, mlp.bias[1] + 32 * (4 * wv + m));
-      acc1[m][1] = acc1[m][0];
-    }
-    {
-      const int rb0 = wv >> 1, cb0 = wv & 1;
-      const int a0 = mlp.ax[0] / 4;
-      const int a1 = mlp.ah[1] / 4 + (4 * wv) * (kHidden[0] / 8) * 64;
-      const float zz[1] = {zb[cb0]};
-      f32x4 ring0[kPrefetch0 + 1][1];
-      f32x16 acc0[1][1];
-      float az0[1];
-      seg_prefetch<1, kPrefetch0>(ring0, ws, a0 + rb0 * NGX * 64, 0, NGX);
-      init_from_bias(acc0[0][0], ws, mlp.bias[0] + 32 * rb0);
-      az0[0] = wload32(ws, mlp.az[0] + rb0 * 64);
-#pragma unroll 1
-      for (int ck = 0; ck < kHidden[0] / 64; ++ck) {
-        const int rb = 2 * ck + rb0;
-        seg_main<1, 1, kPrefetch0, ROWB>(acc0, ring0, ws, a0 + rb * NGX * 64, 0, NGX,
-                                         xrow + cb0 * 32 * ROWB, swz);
-        f32x4 ring1[kPrefetch1 + 1][4];
-        seg_prefetch<4, kPrefetch1>(ring1, ws, a1 + ck * 8 * 64, (kHidden[0] / 8) * 64, 8);
-        gemm_z<1, 1>(acc0, az0, zz);
-        lrelu(acc0[0][0]);
-        store_hidden(hb, acc0[0][0], rb0, cb0, j, h);
-        const int rbn = min(rb + 2, kHidden[0] / 32 - 2 + rb0);
-        seg_prefetch<1, kPrefetch0>(ring0, ws, a0 + rbn * NGX * 64, 0, NGX);
-        init_from_bias(acc0[0][0], ws, mlp.bias[0] + 32 * rbn);
-        az0[0] = wload32(ws, mlp.az[0] + rbn * 64);
-        MP_CHUNK_SYNC();
-        seg_main<4, 2, kPrefetch1, kHbRowBytes>(acc1, ring1, ws, a1 + ck * 8 * 64, (kHidden[0] / 8) * 64, 8,
-                                                hrow, swz);
-        MP_CHUNK_SYNC();
-      }
-      const int a1x = mlp.ax[1] / 4 + (4 * wv) * NGX * 64;
-      f32x4 ring1[kPrefetch1 + 1][4];
-      float az1[4];
-      seg_prefetch<4, kPrefetch1>(ring1, ws, a1x, NGX * 64, NGX);
-#pragma unroll
-      for (int m = 0; m < 4; ++m) az1[m] = wload32(ws, mlp.az[1] + (4 * wv + m) * 64);
-      seg_main<4, 2, kPrefetch1, ROWB>(acc1, ring1, ws, a1x, NGX * 64, NGX, xrow, swz);
-      gemm_z<4, 2>(acc1, az1, zb);
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) lrelu(acc1[m][n]);
-    }
-
-    // ---------------- layer 2: rows [64 wv, +64), K = 512 hidden (8 chunks) + skip ----------------
+    // ---------------- layers 0-2, each column on its own features and z (query_mfma.h) ----------------
     f32x16 acc2[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      init_from_bias(acc2[m][0], ws, mlp.bias[2] + 32 * (2 * wv + m));
-      acc2[m][1] = acc2[m][0];
-    }
-    {
-      const int a2 = mlp.ah[2] / 4 + (2 * wv) * (kHidden[1] / 8) * 64;
-      f32x4 ring2[2][2];
-      seg_prefetch<2, 1>(ring2, ws, a2, (kHidden[1] / 8) * 64, 8);
-#pragma unroll
-      for (int ck = 0; ck < 8; ++ck) {
-        if (wv == (ck >> 1)) {
-#pragma unroll
-          for (int mm = 0; mm < 2; ++mm)
-#pragma unroll
-            for (int n = 0; n < 2; ++n) store_hidden(hb, acc1[2 * (ck & 1) + mm][n], mm, n, j, h);
-        }
-        MP_CHUNK_SYNC();
-        seg_main<2, 2, 1, kHbRowBytes>(acc2, ring2, ws, a2 + ck * 8 * 64, (kHidden[1] / 8) * 64, 8,
-                                       hrow, swz);
-        if (ck < 7) seg_prefetch<2, 1>(ring2, ws, a2 + (ck + 1) * 8 * 64, (kHidden[1] / 8) * 64, 8);
-        MP_CHUNK_SYNC();
-      }
-      const int a2x = mlp.ax[2] / 4 + (2 * wv) * NGX * 64;
-      float az2[2];
-      seg_prefetch<2, 1>(ring2, ws, a2x, NGX * 64, NGX);
-#pragma unroll
-      for (int m = 0; m < 2; ++m) az2[m] = wload32(ws, mlp.az[2] + (2 * wv + m) * 64);
-      seg_main<2, 2, 1, ROWB>(acc2, ring2, ws, a2x, NGX * 64, NGX, xrow, swz);
-      gemm_z<2, 2>(acc2, az2, zb);
-#pragma unroll
-      for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int n = 0; n < 2; ++n) lrelu(acc2[m][n]);
-    }
+    mlp64_layers012<C>(acc2, mlp, ws, xs, hb, zb, wv, j, h, swz);
+
+    const unsigned char *xrow = xs + j * ROWB;  // this lane's column row, column block 0
+    const unsigned char *hrow = hb + j * kHbRowBytes;
 
     // ---------------- layer 3 on the view means: rows [32 wv, +32), K = 256 hidden (4 chunks) + skip ----------------
     f32x16 acc3[1][2];
@@ -331,7 +246,7 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
 #pragma unroll
             for (int n = 0; n < 2; ++n) store_hidden(hb, acc2[mm][n], mm, n, j, h);
         }
-        MP_CHUNK_SYNC();
+        __syncthreads();
         if (nv > 1) {
           // y = y.view(-1,V,256,N).mean(1), this chunk's 64 rows; the first chunk also takes
           // tmpy = feature.view(-1,V,C+1,N).mean(1) -- every wave is past layer 2's reads of xs
@@ -341,7 +256,7 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
         }
         seg_main<1, 2, 3, kHbRowBytes>(acc3, ring3, ws, a3 + ck * 8 * 64, 0, 8, hrow, swz);
         if (ck < 3) seg_prefetch<1, 3>(ring3, ws, a3 + (ck + 1) * 8 * 64, 0, 8);
-        MP_CHUNK_SYNC();
+        __syncthreads();
       }
       const int a3x = mlp.ax[3] / 4 + wv * NGX * 64;
       float az3[1];
@@ -357,51 +272,10 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
       for (int n = 0; n < 2; ++n) lrelu(acc3[0][n]);
     }
 
-    // ---------------- layer 4 (Cout x (128 + C + 1)) on the VALU, as query.hip ----------------
-    float *red = reinterpret_cast<float *>(hb);
+    // ---------------- layer 4 (Cout x (128 + C + 1)) on the VALU ----------------
+    float *red = reinterpret_cast<float *>(hb);  // red[part][o][column], see mlp64_layer4_partials
     constexpr int K4 = (kHidden[3] + C + 1 + 3) & ~3;
-    {
-#pragma unroll
-      for (int o = 0; o < COUT; ++o) {
-        const float *w4 = (mlp.base + mlp.w4) + o * K4 + 32 * wv + 4 * h;
-        float s0 = 0.0f, s1 = 0.0f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 wq = *reinterpret_cast<const f32x4 *>(w4 + 8 * q);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            s0 = fmaf(wq[i], acc3[0][0][4 * q + i], s0);
-            s1 = fmaf(wq[i], acc3[0][1][4 * q + i], s1);
-          }
-        }
-        s0 += __shfl_xor(s0, 32);
-        s1 += __shfl_xor(s1, 32);
-        if (h == 0) {
-          red[(wv * COUT + o) * kTilePts + j] = s0;
-          red[(wv * COUT + o) * kTilePts + 32 + j] = s1;
-        }
-      }
-      const int p = lane;
-      float sx[COUT];
-#pragma unroll
-      for (int o = 0; o < COUT; ++o) sx[o] = 0.0f;
-      constexpr int SLOTS = C / 16;
-#pragma unroll 4
-      for (int s = 0; s < SLOTS; ++s) {
-        const int slot = wv * SLOTS + s;
-        const f32x4 xv =
-            *reinterpret_cast<const f32x4 *>(xs + p * ROWB + ((slot ^ (p & 15)) << 4));
-#pragma unroll
-        for (int o = 0; o < COUT; ++o) {
-          const f32x4 wq =
-              *reinterpret_cast<const f32x4 *>((mlp.base + mlp.w4) + o * K4 + kHidden[3] + 4 * slot);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) sx[o] = fmaf(wq[i], xv[i], sx[o]);
-        }
-      }
-#pragma unroll
-      for (int o = 0; o < COUT; ++o) red[((4 + wv) * COUT + o) * kTilePts + p] = sx[o];
-    }
+    mlp64_layer4_partials<C, COUT>(red, acc3, mlp, xs, wv, lane, j, h);
     __syncthreads();
     if (tid < COUT * kTilePts) {
       const int o = tid / kTilePts, p = tid % kTilePts;
@@ -456,24 +330,15 @@ static int launch_views_t(mp_ctx *ctx, const Mlp &m, const ViewSetDev &set, int 
                           hipStream_t st) {
   constexpr int lds = kTilePts * C * 4 + kHbBytes;
   auto kern = pifu_query_views_kernel<C, COUT, WPS, DIRECT>;
-  const void *kern_id = reinterpret_cast<const void *>(kern);
-  if (!ctx->lds_attr_done.count(kern_id)) {
-    MP_HIP(ctx, hipFuncSetAttribute(kern_id, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    ctx->lds_attr_done.insert(kern_id);
-  }
+  if (const int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
   const long long gpts = kTilePts / set.nv;
   const long long tiles = (set.n + gpts - 1) / gpts;
   if (tiles <= 0) return MP_OK;
-  const long long resident = (long long)cus_of(ctx, st) * WPS;
-  const long long grid = tiles < 8 * resident ? tiles : 8 * resident;
-  const bool prof = 2 * (ctx->prof_used + 1) <= (int)ctx->prof_events.size();
-  if (prof) MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used], st));
+  const long long grid = query_grid(tiles, (long long)cus_of(ctx, st) * WPS, false);
+  if (const int rc = prof_begin(ctx, st)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kQueryThreads), lds, st, m.pack(), h, w, z_scale, m.act,
                      set);
-  if (prof) {
-    MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used + 1], st));
-    ++ctx->prof_used;
-  }
+  if (const int rc = prof_end(ctx, st)) return rc;
   MP_HIP(ctx, hipGetLastError());
   return MP_OK;
 }
@@ -492,25 +357,15 @@ int launch_query_views_lattice(mp_ctx *ctx, const Mlp &m, const ViewLatticeDev &
   constexpr int C = 256, WPS = 2;
   constexpr int lds = kTilePts * C * 4 + kHbBytes;
   auto kern = pifu_query_views_kernel<C, 1, WPS, false, true>;
-  const void *kern_id = reinterpret_cast<const void *>(kern);
-  if (!ctx->lds_attr_done.count(kern_id)) {
-    MP_HIP(ctx, hipFuncSetAttribute(kern_id, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
-    ctx->lds_attr_done.insert(kern_id);
-  }
+  if (const int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
   const long long gpts = kTilePts / set.nv;
   const long long tiles = (max_points + gpts - 1) / gpts;
   if (tiles <= 0) return MP_OK;
-  const long long resident = (long long)cus_of(ctx, st) * WPS;
-  const long long grid = set.src.n_dev ? (tiles < resident ? tiles : resident)
-                                       : (tiles < 8 * resident ? tiles : 8 * resident);
-  const bool prof = 2 * (ctx->prof_used + 1) <= (int)ctx->prof_events.size();
-  if (prof) MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used], st));
+  const long long grid = query_grid(tiles, (long long)cus_of(ctx, st) * WPS, set.src.n_dev != nullptr);
+  if (const int rc = prof_begin(ctx, st)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kQueryThreads), lds, st, m.pack(), h, w, z_scale, m.act,
                      set);
-  if (prof) {
-    MP_HIP(ctx, hipEventRecord(ctx->prof_events[2 * ctx->prof_used + 1], st));
-    ++ctx->prof_used;
-  }
+  if (const int rc = prof_end(ctx, st)) return rc;
   MP_HIP(ctx, hipGetLastError());
   return MP_OK;
 }

@@ -1,4 +1,4 @@
-"""VGPR / spill / scratch / occupancy of every kernel in one .hip file (hipcc -Rpass-analysis=kernel-resource-usage).
+"""VGPR / spill / scratch / occupancy / static LDS of every kernel in one .hip file (hipcc -Rpass-analysis=kernel-resource-usage).
    python tools/kernel_resources.py monoport_amd/csrc/conv3x3.hip [filter]"""
 import os, re, subprocess, sys
 src = os.path.abspath(sys.argv[1]); flt = sys.argv[2] if len(sys.argv) > 2 else ""
@@ -16,6 +16,6 @@ for line in err.splitlines():
     elif cur: rows[cur][k] = v
 for name, r in rows.items():
     if flt and flt not in name: continue
-    print("%-70s VGPR %3s AGPR %3s spill %3s scratch %4s occ %s sgpr-spill %s" % (
+    print("%-70s VGPR %3s AGPR %3s spill %3s scratch %4s occ %s lds %s sgpr-spill %s" % (
         name[:70], r.get("VGPRs"), r.get("AGPRs"), r.get("VGPRs Spill"), r.get("ScratchSize [bytes/lane]"),
-        r.get("Occupancy [waves/SIMD]"), r.get("SGPRs Spill")))
+        r.get("Occupancy [waves/SIMD]"), r.get("LDS Size [bytes/block]"), r.get("SGPRs Spill")))
