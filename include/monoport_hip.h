@@ -460,6 +460,34 @@ int mp_mesh_normals(mp_ctx *ctx, const float *verts, int64_t max_verts, const in
 int mp_mesh_points(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *counts, float *points,
                    int32_t *count_out, mp_stream stream);
 
+/* The three calls above over n_frames (1..mp_max_frames(), else MP_ERR_ARG) meshes in ONE set of launches each: four
+ * for marching cubes, three (reference) or six (accumulate, memsets included) for the normals, one for the points --
+ * the numbers of a single mesh.  volume / verts / faces / counts / gate / normals / points / count_out are HOST
+ * arrays of n_frames device pointers, each as in the per-mesh call; all volumes have resolution r, and ONE capacity
+ * (max_verts, max_faces) serves all frames.
+ *   Frame f's outputs equal those of the per-mesh call (mp_marching_cubes, mp_mesh_normals, mp_mesh_points) on frame
+ * f's inputs BIT FOR BIT, truncation included: counts[f] holds the vertices and faces needed, only the capacities
+ * are written, faces that name a vertex outside [0, vertices) are skipped by the normals, and rows beyond a frame's
+ * counts are left untouched.  All per-frame sizes are read from that frame's device counts; no float atomics.
+ *   gate (mp_marching_cubes_batch; NULL, or entries NULL = frame on): gate[f] is a device int32; if it reads 0, frame
+ * f's counts become {0, 0} and nothing else of that frame is read or written (its volume may hold anything: the
+ * unspecified volume of an mp_recon_batch frame whose status[0] is 0) -- the normals / points calls then see a zero
+ * count and leave that frame alone.
+ *   Scratch comes from the stream's arena: n_frames * (4 r^3 + 8 ceil(r^3 / 1024) + 1024) bytes for marching cubes
+ * (68 MB per frame at 257^3), n_frames * (24 max_faces + 12 max_verts + 4) + 256 bytes for the normals, none for the
+ * points.  Refusals as in the per-mesh calls, each with an mp_last_error message: r^3 >= 2^31 and capacities beyond
+ * 2^31 / 3 (MP_ERR_UNSUPPORTED), a null or not 4-byte aligned buffer of any frame (MP_ERR_ARG).  Asynchronous. */
+int mp_marching_cubes_batch(mp_ctx *ctx, int n_frames, const float *const *volume, int r, float level,
+                            const float *b_min /*host[3]*/, const float *b_max /*host[3]*/, float *const *verts,
+                            int64_t max_verts, int32_t *const *faces, int64_t max_faces, int32_t *const *counts,
+                            const int32_t *const *gate, mp_stream stream);
+int mp_mesh_normals_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                          const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts, int mode,
+                          float *const *normals, mp_stream stream);
+int mp_mesh_points_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                         const int32_t *const *counts, float *const *points, int32_t *const *count_out,
+                         mp_stream stream);
+
 /* ---- encoder helpers (stand-alone GroupNorm / upsample / concat kernels -- the
  * convolutions are the mp_conv* entry points below, nothing of the inference path is left on MIOpen) ---------- */
 /* y = [relu](GroupNorm(groups, C)(x)): x, y [N,C,HW] f32 (contiguous NCHW), gamma/beta [C];

@@ -165,6 +165,10 @@ SIGNATURES = {
                                   c_vp, c_vp]),
     "mp_mesh_normals": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_vp, c_vp]),
     "mp_mesh_points": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "mp_marching_cubes_batch": (c_int, [c_vp, c_int, c_vp, c_int, c_f32, _pf32, _pf32, c_vp, c_i64, c_vp, c_i64,
+                                        c_vp, c_vp, c_vp]),
+    "mp_mesh_normals_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_vp, c_vp]),
+    "mp_mesh_points_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "mp_group_norm": (c_int, [c_vp, c_vp, c_int, c_int, c_i64, c_int, c_vp, c_vp, c_f32, c_int, c_vp,
                               c_vp]),
     "mp_upsample_bicubic2x": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp]),

@@ -1076,7 +1076,7 @@ int mp_mesh_normals(mp_ctx *ctx, const float *verts, int64_t max_verts, const in
     return fail(ctx, MP_ERR_UNSUPPORTED, "mp_mesh_normals: capacities beyond 2^31 / 3 need 64-bit indices");
   DeviceGuard g(ctx->device);
   void *scratch = nullptr;
-  int rc = ensure_scratch(ctx, (hipStream_t)stream, mesh_normals_scratch_bytes(max_verts, max_faces), &scratch);
+  int rc = ensure_scratch(ctx, (hipStream_t)stream, mesh_normals_scratch_bytes(1, max_verts, max_faces), &scratch);
   if (rc != MP_OK) return rc;
   return launch_mesh_normals(ctx, scratch, verts, max_verts, faces, max_faces, counts, mode, normals,
                              (hipStream_t)stream);
@@ -1090,6 +1090,92 @@ int mp_mesh_points(mp_ctx *ctx, const float *verts, int64_t max_verts, const int
     return fail(ctx, MP_ERR_ARG, "mp_mesh_points: bad argument");
   DeviceGuard g(ctx->device);
   return launch_mesh_points(ctx, verts, max_verts, counts, points, count_out, (hipStream_t)stream);
+}
+
+int mp_marching_cubes_batch(mp_ctx *ctx, int n_frames, const float *const *volume, int r, float level,
+                            const float *b_min, const float *b_max, float *const *verts, int64_t max_verts,
+                            int32_t *const *faces, int64_t max_faces, int32_t *const *counts,
+                            const int32_t *const *gate, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (n_frames < 1 || n_frames > kMaxFrames)
+    return fail(ctx, MP_ERR_ARG, "mp_marching_cubes_batch: 1..%d frames per call, got %d", kMaxFrames, n_frames);
+  if (!volume || !b_min || !b_max || !counts || r < 2 || r > 1023 || max_verts < 0 || max_faces < 0 ||
+      (max_verts > 0 && !verts) || (max_faces > 0 && !faces))
+    return fail(ctx, MP_ERR_ARG, "mp_marching_cubes_batch: bad argument");
+  for (int f = 0; f < n_frames; ++f) {
+    if (!volume[f] || !counts[f] || (max_verts > 0 && !verts[f]) || (max_faces > 0 && !faces[f]))
+      return fail(ctx, MP_ERR_ARG, "mp_marching_cubes_batch: null buffer for frame %d", f);
+    if (((uintptr_t)volume[f] | (uintptr_t)counts[f] | (uintptr_t)(gate ? gate[f] : nullptr) |
+         (uintptr_t)(max_verts > 0 ? verts[f] : nullptr) | (uintptr_t)(max_faces > 0 ? faces[f] : nullptr)) & 3)
+      return fail(ctx, MP_ERR_ARG, "mp_marching_cubes_batch: misaligned buffer for frame %d", f);
+  }
+  // a frame without vertex / face rows gets no pointer at all
+  float *verts_p[kMaxFrames];
+  int32_t *faces_p[kMaxFrames];
+  for (int f = 0; f < n_frames; ++f) {
+    verts_p[f] = max_verts > 0 ? verts[f] : nullptr;
+    faces_p[f] = max_faces > 0 ? faces[f] : nullptr;
+  }
+  DeviceGuard g(ctx->device);
+  void *scratch = nullptr;
+  int rc = ensure_scratch(ctx, (hipStream_t)stream, (size_t)n_frames * mc_scratch_bytes(r), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_marching_cubes_batch(ctx, scratch, n_frames, volume, r, level, b_min, b_max, verts_p, max_verts,
+                                     faces_p, max_faces, counts, gate, (hipStream_t)stream);
+}
+
+int mp_mesh_normals_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                          const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts, int mode,
+                          float *const *normals, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (n_frames < 1 || n_frames > kMaxFrames)
+    return fail(ctx, MP_ERR_ARG, "mp_mesh_normals_batch: 1..%d frames per call, got %d", kMaxFrames, n_frames);
+  if (!counts || max_verts < 0 || max_faces < 0 || (max_verts > 0 && (!verts || !normals)) ||
+      (max_faces > 0 && !faces) || (mode != MP_NORMALS_REFERENCE && mode != MP_NORMALS_ACCUMULATE))
+    return fail(ctx, MP_ERR_ARG, "mp_mesh_normals_batch: bad argument");
+  if (max_verts > 0x7fffffffLL / 3 || max_faces > 0x7fffffffLL / 3)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_mesh_normals_batch: capacities beyond 2^31 / 3 need 64-bit indices");
+  const int32_t *faces_p[kMaxFrames];
+  for (int f = 0; f < n_frames; ++f) {
+    if (!counts[f] || (max_verts > 0 && (!verts[f] || !normals[f])) || (max_faces > 0 && !faces[f]))
+      return fail(ctx, MP_ERR_ARG, "mp_mesh_normals_batch: null buffer for frame %d", f);
+    faces_p[f] = max_faces > 0 ? faces[f] : nullptr;
+    if (((uintptr_t)counts[f] | (uintptr_t)faces_p[f] | (uintptr_t)(max_verts > 0 ? verts[f] : nullptr) |
+         (uintptr_t)(max_verts > 0 ? normals[f] : nullptr)) & 3)
+      return fail(ctx, MP_ERR_ARG, "mp_mesh_normals_batch: misaligned buffer for frame %d", f);
+  }
+  if (max_verts == 0) return MP_OK;
+  DeviceGuard g(ctx->device);
+  void *scratch = nullptr;
+  int rc = ensure_scratch(ctx, (hipStream_t)stream, mesh_normals_scratch_bytes(n_frames, max_verts, max_faces), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_mesh_normals_batch(ctx, scratch, n_frames, verts, max_verts, faces_p, max_faces, counts, mode, normals,
+                                   (hipStream_t)stream);
+}
+
+int mp_mesh_points_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                         const int32_t *const *counts, float *const *points, int32_t *const *count_out,
+                         mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (n_frames < 1 || n_frames > kMaxFrames)
+    return fail(ctx, MP_ERR_ARG, "mp_mesh_points_batch: 1..%d frames per call, got %d", kMaxFrames, n_frames);
+  if (!counts || !count_out || max_verts < 0 || (max_verts > 0 && (!verts || !points)))
+    return fail(ctx, MP_ERR_ARG, "mp_mesh_points_batch: bad argument");
+  const float *verts_p[kMaxFrames];
+  float *points_p[kMaxFrames];
+  for (int f = 0; f < n_frames; ++f) {
+    if (!counts[f] || !count_out[f] || (max_verts > 0 && (!verts[f] || !points[f])))
+      return fail(ctx, MP_ERR_ARG, "mp_mesh_points_batch: null buffer for frame %d", f);
+    verts_p[f] = max_verts > 0 ? verts[f] : nullptr;
+    points_p[f] = max_verts > 0 ? points[f] : nullptr;
+    if (((uintptr_t)counts[f] | (uintptr_t)count_out[f] | (uintptr_t)verts_p[f] | (uintptr_t)points_p[f]) & 3)
+      return fail(ctx, MP_ERR_ARG, "mp_mesh_points_batch: misaligned buffer for frame %d", f);
+  }
+  DeviceGuard g(ctx->device);
+  return launch_mesh_points_batch(ctx, n_frames, verts_p, max_verts, counts, points_p, count_out, (hipStream_t)stream);
 }
 
 int mp_group_norm(mp_ctx *ctx, const float *x, int n, int c, int64_t hw, int groups,

@@ -16,7 +16,13 @@
 //                 reads, exact for any valence.
 // The sizes come from device memory (counts of mp_marching_cubes); the grids are sized from the
 // capacities and blocks beyond the counts leave at once.
+//
+// Every kernel serves up to kMaxFrames meshes of one capacity per launch (blockIdx.y = frame: mp_mesh_normals_batch /
+// mp_mesh_points_batch; the per-mesh calls are the one-frame case).  Each frame reads its own counts and has its own
+// part of the scratch (MeshScratch), the running total of the segment allocation included.
 #include "mp_internal.h"
+
+#include <cstring>
 
 #pragma clang fp contract(off)
 
@@ -46,14 +52,40 @@ __device__ __forceinline__ bool face_indices(const int32_t *__restrict__ faces, 
   return idx[0] >= 0 && idx[0] < nv && idx[1] >= 0 && idx[1] < nv && idx[2] >= 0 && idx[2] < nv;
 }
 
-__global__ __launch_bounds__(kMeshBlock) void mesh_face_kernel(
-    const float *__restrict__ verts, long long max_v, const int32_t *__restrict__ faces, long long max_f,
-    const int32_t *__restrict__ counts, int mode, float *__restrict__ fn, int *__restrict__ per_vertex) {
+struct MeshFrames {
+  const float *verts[kMaxFrames];
+  const int32_t *faces[kMaxFrames];
+  const int32_t *counts[kMaxFrames];
+  float *normals[kMaxFrames];
+};
+
+// Scratch of n frames: face normals n x [max_f,3] f32 | keys n x [3 max_f] int | per-vertex ints n x [3 max_v] |
+// totals [n].  The per-vertex part is last[v][corner] per frame in reference mode; in accumulate mode it is the
+// valences of ALL frames (n x [max_v], cleared by one memset) followed by their cursors (n x [max_v]).
+struct MeshScratch {
+  float *fn;
+  int *keys, *per_vertex, *total;
+  long long max_v, max_f;
+  int n_frames;
+  __host__ __device__ float *face_normals(int f) const { return fn + 3 * max_f * f; }
+  __host__ __device__ int *key_list(int f) const { return keys + 3 * max_f * f; }
+  __host__ __device__ int *last(int f) const { return per_vertex + 3 * max_v * f; }
+  __host__ __device__ int *valence(int f) const { return per_vertex + max_v * f; }
+  __host__ __device__ int *cursor(int f) const { return per_vertex + max_v * (n_frames + f); }
+};
+
+__global__ __launch_bounds__(kMeshBlock) void mesh_face_kernel(MeshFrames fr, MeshScratch sc, int mode) {
+  const int32_t *__restrict__ counts = fr.counts[blockIdx.y];
+  const long long max_v = sc.max_v, max_f = sc.max_f;
   const int nf = mesh_min(counts[1], max_f);
   const long long f = (long long)blockIdx.x * kMeshBlock + threadIdx.x;
   if (f >= nf) return;
   const int nv = mesh_min(counts[0], max_v);
   int idx[3];
+  const float *__restrict__ verts = fr.verts[blockIdx.y];
+  const int32_t *__restrict__ faces = fr.faces[blockIdx.y];
+  float *__restrict__ fn = sc.face_normals(blockIdx.y);
+  int *__restrict__ per_vertex = mode == MP_NORMALS_REFERENCE ? sc.last(blockIdx.y) : sc.valence(blockIdx.y);
   if (!face_indices(faces, (int)f, nv, idx)) return;
   float p[3][3];
 #pragma unroll
@@ -79,12 +111,13 @@ __global__ __launch_bounds__(kMeshBlock) void mesh_face_kernel(
   }
 }
 
-__global__ __launch_bounds__(kMeshBlock) void mesh_reference_kernel(
-    long long max_v, const int32_t *__restrict__ counts, const float *__restrict__ fn,
-    const int *__restrict__ last, float *__restrict__ normals) {
-  const int nv = mesh_min(counts[0], max_v);
+__global__ __launch_bounds__(kMeshBlock) void mesh_reference_kernel(MeshFrames fr, MeshScratch sc) {
+  const int nv = mesh_min(fr.counts[blockIdx.y][0], sc.max_v);
   const long long v = (long long)blockIdx.x * kMeshBlock + threadIdx.x;
   if (v >= nv) return;
+  const float *__restrict__ fn = sc.face_normals(blockIdx.y);
+  const int *__restrict__ last = sc.last(blockIdx.y);
+  float *__restrict__ normals = fr.normals[blockIdx.y];
   float x = 0.0f, y = 0.0f, z = 0.0f;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -100,14 +133,13 @@ __global__ __launch_bounds__(kMeshBlock) void mesh_reference_kernel(
   normals[3 * v + 2] = z;
 }
 
-// cursor[v] = start of vertex v's segment of the corner list; *total counts the entries handed out
-__global__ __launch_bounds__(kMeshBlock) void mesh_segments_kernel(long long max_v,
-                                                                   const int32_t *__restrict__ counts,
-                                                                   const int *__restrict__ valence,
-                                                                   int *__restrict__ cursor,
-                                                                   int *__restrict__ total) {
-  const int nv = mesh_min(counts[0], max_v);
+// cursor[v] = start of vertex v's segment of the frame's corner list; the frame's total counts the entries handed out
+__global__ __launch_bounds__(kMeshBlock) void mesh_segments_kernel(MeshFrames fr, MeshScratch sc) {
+  const int nv = mesh_min(fr.counts[blockIdx.y][0], sc.max_v);
   if ((long long)blockIdx.x * kMeshBlock >= nv) return;
+  const int *__restrict__ valence = sc.valence(blockIdx.y);
+  int *__restrict__ cursor = sc.cursor(blockIdx.y);
+  int *__restrict__ total = sc.total + blockIdx.y;
   const long long v = (long long)blockIdx.x * kMeshBlock + threadIdx.x;
   const int n = v < nv ? valence[v] : 0;
   const int lane = threadIdx.x & 63;
@@ -123,16 +155,15 @@ __global__ __launch_bounds__(kMeshBlock) void mesh_segments_kernel(long long max
   if (v < nv) cursor[v] = base + incl - n;
 }
 
-__global__ __launch_bounds__(kMeshBlock) void mesh_fill_kernel(long long max_v,
-                                                               const int32_t *__restrict__ faces,
-                                                               long long max_f,
-                                                               const int32_t *__restrict__ counts,
-                                                               int *__restrict__ cursor,
-                                                               int *__restrict__ keys) {
-  const int nf = mesh_min(counts[1], max_f);
+__global__ __launch_bounds__(kMeshBlock) void mesh_fill_kernel(MeshFrames fr, MeshScratch sc) {
+  const int32_t *__restrict__ counts = fr.counts[blockIdx.y];
+  const int nf = mesh_min(counts[1], sc.max_f);
   const long long f = (long long)blockIdx.x * kMeshBlock + threadIdx.x;
   if (f >= nf) return;
-  const int nv = mesh_min(counts[0], max_v);
+  const int nv = mesh_min(counts[0], sc.max_v);
+  const int32_t *__restrict__ faces = fr.faces[blockIdx.y];
+  int *__restrict__ cursor = sc.cursor(blockIdx.y);
+  int *__restrict__ keys = sc.key_list(blockIdx.y);
   int idx[3];
   if (!face_indices(faces, (int)f, nv, idx)) return;
 #pragma unroll
@@ -140,13 +171,15 @@ __global__ __launch_bounds__(kMeshBlock) void mesh_fill_kernel(long long max_v,
 }
 
 // after the fill cursor[v] is the END of the segment; the keys of a segment are distinct
-__global__ __launch_bounds__(kMeshBlock) void mesh_accumulate_kernel(
-    long long max_v, const int32_t *__restrict__ counts, const float *__restrict__ fn,
-    const int *__restrict__ valence, const int *__restrict__ cursor, const int *__restrict__ keys,
-    float *__restrict__ normals) {
-  const int nv = mesh_min(counts[0], max_v);
+__global__ __launch_bounds__(kMeshBlock) void mesh_accumulate_kernel(MeshFrames fr, MeshScratch sc) {
+  const int nv = mesh_min(fr.counts[blockIdx.y][0], sc.max_v);
   const long long v = (long long)blockIdx.x * kMeshBlock + threadIdx.x;
   if (v >= nv) return;
+  const float *__restrict__ fn = sc.face_normals(blockIdx.y);
+  const int *__restrict__ valence = sc.valence(blockIdx.y);
+  const int *__restrict__ cursor = sc.cursor(blockIdx.y);
+  const int *__restrict__ keys = sc.key_list(blockIdx.y);
+  float *__restrict__ normals = fr.normals[blockIdx.y];
   const int n = valence[v];
   const int *seg = keys + (cursor[v] - n);
   float x = 0.0f, y = 0.0f, z = 0.0f;
@@ -170,68 +203,96 @@ __global__ __launch_bounds__(kMeshBlock) void mesh_accumulate_kernel(
   normals[3 * v + 2] = z;
 }
 
-__global__ __launch_bounds__(kMeshBlock) void mesh_points_kernel(const float *__restrict__ verts, long long max_v,
-                                                                 const int32_t *__restrict__ counts,
-                                                                 float *__restrict__ points,
-                                                                 int32_t *__restrict__ count_out) {
-  const int nv = mesh_min(counts[0], max_v);
+struct PointFrames {
+  const float *verts[kMaxFrames];
+  const int32_t *counts[kMaxFrames];
+  float *points[kMaxFrames];
+  int32_t *count_out[kMaxFrames];
+};
+
+__global__ __launch_bounds__(kMeshBlock) void mesh_points_kernel(PointFrames fr, long long max_v) {
+  const float *__restrict__ verts = fr.verts[blockIdx.y];
+  float *__restrict__ points = fr.points[blockIdx.y];
+  const int nv = mesh_min(fr.counts[blockIdx.y][0], max_v);
   const long long v = (long long)blockIdx.x * kMeshBlock + threadIdx.x;
-  if (v == 0) count_out[0] = nv;
+  if (v == 0) fr.count_out[blockIdx.y][0] = nv;
   if (v >= nv) return;
 #pragma unroll
   for (int k = 0; k < 3; ++k) points[k * max_v + v] = verts[3 * v + k];
 }
 
-// face normals [max_f,3] f32 | keys [3 max_f] int | per-vertex ints [3 max_v] | total [1]
-size_t mesh_normals_scratch_bytes(long long max_v, long long max_f) {
-  return (size_t)(6 * max_f + 3 * max_v + 1) * 4 + 256;
+// per frame: face normals [max_f,3] f32 | keys [3 max_f] int | per-vertex ints [3 max_v] | total [1] (MeshScratch)
+size_t mesh_normals_scratch_bytes(int n_frames, long long max_v, long long max_f) {
+  return (size_t)n_frames * (size_t)(6 * max_f + 3 * max_v + 1) * 4 + 256;
 }
 
-int launch_mesh_normals(mp_ctx *ctx, void *scratch, const float *verts, long long max_v, const int32_t *faces,
-                        long long max_f, const int32_t *counts, int mode, float *normals, hipStream_t st) {
+int launch_mesh_normals_batch(mp_ctx *ctx, void *scratch, int n_frames, const float *const *verts, long long max_v,
+                              const int32_t *const *faces, long long max_f, const int32_t *const *counts, int mode,
+                              float *const *normals, hipStream_t st) {
   // keys are 3 * face + corner in an int
   if (max_f > 0x7fffffffLL / 3 || max_v > 0x7fffffffLL / 3)
     return fail(ctx, MP_ERR_UNSUPPORTED, "mesh normals: %lld vertices / %lld faces need 64-bit indices", max_v, max_f);
   if (max_v == 0) return MP_OK;
-  float *fn = static_cast<float *>(scratch);
-  int *keys = reinterpret_cast<int *>(fn + 3 * max_f);
-  int *per_vertex = keys + 3 * max_f;
-  int *total = per_vertex + 3 * max_v;
-  const unsigned fb = (unsigned)((max_f + kMeshBlock - 1) / kMeshBlock);
-  const unsigned vb = (unsigned)((max_v + kMeshBlock - 1) / kMeshBlock);
-  if (mode == MP_NORMALS_REFERENCE) {
-    MP_HIP(ctx, hipMemsetAsync(per_vertex, 0xff, (size_t)3 * max_v * sizeof(int), st));  // last[v][corner] = -1
-    if (fb)
-      hipLaunchKernelGGL(mesh_face_kernel, dim3(fb), dim3(kMeshBlock), 0, st, verts, max_v, faces, max_f, counts,
-                         mode, fn, per_vertex);
-    hipLaunchKernelGGL(mesh_reference_kernel, dim3(vb), dim3(kMeshBlock), 0, st, max_v, counts, fn, per_vertex,
-                       normals);
-  } else {
-    int *valence = per_vertex, *cursor = per_vertex + max_v;
-    MP_HIP(ctx, hipMemsetAsync(valence, 0, (size_t)max_v * sizeof(int), st));
-    MP_HIP(ctx, hipMemsetAsync(total, 0, sizeof(int), st));
-    if (fb)
-      hipLaunchKernelGGL(mesh_face_kernel, dim3(fb), dim3(kMeshBlock), 0, st, verts, max_v, faces, max_f, counts,
-                         mode, fn, valence);
-    hipLaunchKernelGGL(mesh_segments_kernel, dim3(vb), dim3(kMeshBlock), 0, st, max_v, counts, valence, cursor,
-                       total);
-    if (fb)
-      hipLaunchKernelGGL(mesh_fill_kernel, dim3(fb), dim3(kMeshBlock), 0, st, max_v, faces, max_f, counts, cursor,
-                         keys);
-    hipLaunchKernelGGL(mesh_accumulate_kernel, dim3(vb), dim3(kMeshBlock), 0, st, max_v, counts, fn, valence,
-                       cursor, keys, normals);
+  MeshFrames fr;
+  std::memset(&fr, 0, sizeof(fr));
+  for (int f = 0; f < n_frames; ++f) {
+    fr.verts[f] = verts[f];
+    fr.faces[f] = faces[f];
+    fr.counts[f] = counts[f];
+    fr.normals[f] = normals[f];
   }
+  MeshScratch sc;
+  sc.fn = static_cast<float *>(scratch);
+  sc.keys = reinterpret_cast<int *>(sc.fn + 3 * max_f * n_frames);
+  sc.per_vertex = sc.keys + 3 * max_f * n_frames;
+  sc.total = sc.per_vertex + 3 * max_v * n_frames;
+  sc.max_v = max_v;
+  sc.max_f = max_f;
+  sc.n_frames = n_frames;
+  const dim3 fb((unsigned)((max_f + kMeshBlock - 1) / kMeshBlock), n_frames);
+  const dim3 vb((unsigned)((max_v + kMeshBlock - 1) / kMeshBlock), n_frames);
+  if (mode == MP_NORMALS_REFERENCE) {
+    // last[v][corner] = -1, all frames
+    MP_HIP(ctx, hipMemsetAsync(sc.per_vertex, 0xff, (size_t)3 * max_v * n_frames * sizeof(int), st));
+    if (fb.x) hipLaunchKernelGGL(mesh_face_kernel, fb, dim3(kMeshBlock), 0, st, fr, sc, mode);
+    hipLaunchKernelGGL(mesh_reference_kernel, vb, dim3(kMeshBlock), 0, st, fr, sc);
+  } else {
+    MP_HIP(ctx, hipMemsetAsync(sc.per_vertex, 0, (size_t)max_v * n_frames * sizeof(int), st));  // the valences
+    MP_HIP(ctx, hipMemsetAsync(sc.total, 0, (size_t)n_frames * sizeof(int), st));
+    if (fb.x) hipLaunchKernelGGL(mesh_face_kernel, fb, dim3(kMeshBlock), 0, st, fr, sc, mode);
+    hipLaunchKernelGGL(mesh_segments_kernel, vb, dim3(kMeshBlock), 0, st, fr, sc);
+    if (fb.x) hipLaunchKernelGGL(mesh_fill_kernel, fb, dim3(kMeshBlock), 0, st, fr, sc);
+    hipLaunchKernelGGL(mesh_accumulate_kernel, vb, dim3(kMeshBlock), 0, st, fr, sc);
+  }
+  MP_HIP(ctx, hipGetLastError());
+  return MP_OK;
+}
+
+int launch_mesh_normals(mp_ctx *ctx, void *scratch, const float *verts, long long max_v, const int32_t *faces,
+                        long long max_f, const int32_t *counts, int mode, float *normals, hipStream_t st) {
+  return launch_mesh_normals_batch(ctx, scratch, 1, &verts, max_v, &faces, max_f, &counts, mode, &normals, st);
+}
+
+int launch_mesh_points_batch(mp_ctx *ctx, int n_frames, const float *const *verts, long long max_v,
+                             const int32_t *const *counts, float *const *points, int32_t *const *count_out,
+                             hipStream_t st) {
+  PointFrames fr;
+  std::memset(&fr, 0, sizeof(fr));
+  for (int f = 0; f < n_frames; ++f) {
+    fr.verts[f] = verts[f];
+    fr.counts[f] = counts[f];
+    fr.points[f] = points[f];
+    fr.count_out[f] = count_out[f];
+  }
+  const unsigned vb = (unsigned)((max_v + kMeshBlock - 1) / kMeshBlock);
+  hipLaunchKernelGGL(mesh_points_kernel, dim3(vb ? vb : 1, n_frames), dim3(kMeshBlock), 0, st, fr, max_v);
   MP_HIP(ctx, hipGetLastError());
   return MP_OK;
 }
 
 int launch_mesh_points(mp_ctx *ctx, const float *verts, long long max_v, const int32_t *counts, float *points,
                        int32_t *count_out, hipStream_t st) {
-  const unsigned vb = (unsigned)((max_v + kMeshBlock - 1) / kMeshBlock);
-  hipLaunchKernelGGL(mesh_points_kernel, dim3(vb ? vb : 1), dim3(kMeshBlock), 0, st, verts, max_v, counts, points,
-                     count_out);
-  MP_HIP(ctx, hipGetLastError());
-  return MP_OK;
+  return launch_mesh_points_batch(ctx, 1, &verts, max_v, &counts, &points, &count_out, st);
 }
 
 }  // namespace mp

@@ -361,8 +361,19 @@ size_t mc_scratch_bytes(int r);
 int launch_marching_cubes(mp_ctx *ctx, void *scratch, const float *vol, int r, float level,
                           const float *bmin, const float *bmax, float *verts, long long max_v,
                           int32_t *faces, long long max_f, int32_t *counts, hipStream_t st);
+// n_frames volumes of one resolution; scratch: n_frames * mc_scratch_bytes(r); gate: NULL or n_frames entries
+int launch_marching_cubes_batch(mp_ctx *ctx, void *scratch, int n_frames, const float *const *vol, int r, float level,
+                                const float *bmin, const float *bmax, float *const *verts, long long max_v,
+                                int32_t *const *faces, long long max_f, int32_t *const *counts,
+                                const int32_t *const *gate, hipStream_t st);
 // mesh.hip
-size_t mesh_normals_scratch_bytes(long long max_v, long long max_f);
+size_t mesh_normals_scratch_bytes(int n_frames, long long max_v, long long max_f);
+int launch_mesh_normals_batch(mp_ctx *ctx, void *scratch, int n_frames, const float *const *verts, long long max_v,
+                              const int32_t *const *faces, long long max_f, const int32_t *const *counts, int mode,
+                              float *const *normals, hipStream_t st);
+int launch_mesh_points_batch(mp_ctx *ctx, int n_frames, const float *const *verts, long long max_v,
+                             const int32_t *const *counts, float *const *points, int32_t *const *count_out,
+                             hipStream_t st);
 int launch_mesh_normals(mp_ctx *ctx, void *scratch, const float *verts, long long max_v, const int32_t *faces,
                         long long max_f, const int32_t *counts, int mode, float *normals, hipStream_t st);
 int launch_mesh_points(mp_ctx *ctx, const float *verts, long long max_v, const int32_t *counts, float *points,

@@ -1081,6 +1081,126 @@ def mesh_points_raw(verts, counts):
     return pts, count
 
 
+def _frame_rows(who, what, t, n, shape, dtype, device):
+    """A caller's buffer of a batched mesh call: ``dtype`` [n, *shape] on ``device`` whose frames are each contiguous."""
+    if (t is None or tuple(t.shape) != (n,) + tuple(shape) or t.dtype != dtype or t.device != device
+            or not all(row.is_contiguous() for row in t)):
+        raise ValueError("%s: %s must be %s %s on %s with contiguous frames"
+                         % (who, what, str(dtype).replace("torch.", ""), [n] + list(shape), device))
+    return t
+
+
+def _mesh_frames(who, verts, faces, counts):
+    """The meshes of one batched call (``_mesh_buffers`` each, one capacity for all) -> (n, max_v, max_f, device)."""
+    n = len(verts)
+    if n == 0:
+        raise ValueError("%s wants at least one mesh" % who)
+    if len(counts) != n or (faces is not None and len(faces) != n):
+        raise ValueError("%s: %d vertex buffers, %s face buffers, %d counts"
+                         % (who, n, None if faces is None else len(faces), len(counts)))
+    for f in range(n):
+        _mesh_buffers(verts[f], None if faces is None else faces[f], counts[f])
+    max_v = verts[0].shape[0]
+    max_f = 0 if faces is None else faces[0].shape[0]
+    if (any(v.shape[0] != max_v or v.device != verts[0].device for v in verts)
+            or (faces is not None and any(f.shape[0] != max_f for f in faces))):
+        raise ValueError("%s: one capacity (and one device) serves all meshes of a call" % who)
+    return n, max_v, max_f, verts[0].device
+
+
+def marching_cubes_raw_batch(volumes, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), max_verts=None,
+                             max_faces=None, gates=None, out=None):
+    """mp_marching_cubes_batch: ``[marching_cubes_raw(v, ...) for v in volumes]`` (cubic volumes of one size, one
+    capacity) in one set of four launches per MAX_FRAMES volumes; every frame's (verts [max_v,3], faces [max_f,3],
+    counts int32[2]) are views of three tensors, bit for bit what the per-volume call gives.  ``gates``: per-frame
+    device int32 tensors (or None entries = frame on); a frame whose gate reads 0 gets counts (0, 0) and nothing
+    else of it is read or written.  ``out``: (verts [n,max_v,3] f32, faces [n,max_f,3] int32, counts [n,2] int32)
+    to write into.  No host sync."""
+    who = "marching_cubes_raw_batch"
+    vols = [_cubic_volume(v, who) for v in volumes]
+    n = len(vols)
+    if n == 0:
+        raise ValueError("%s wants at least one volume" % who)
+    r = vols[0].shape[0]
+    dev = vols[0].device
+    if any(v.shape[0] != r or v.device != dev for v in vols):
+        raise ValueError("%s wants cubic volumes of one size on one device" % who)
+    if gates is not None:
+        if len(gates) != n:
+            raise ValueError("%s: %d volumes, %d gates" % (who, n, len(gates)))
+        if any(g is not None and (g.dtype != torch.int32 or g.numel() < 1 or g.device != dev) for g in gates):
+            raise ValueError("%s: a gate is an int32 tensor on the volumes' device" % who)
+    if out is not None:
+        verts, faces, counts = out
+        if max_verts is None:
+            max_verts = verts.shape[1]
+        if max_faces is None:
+            max_faces = faces.shape[1]
+    if max_verts is None:
+        max_verts = 12 * r * r  # marching_cubes_raw's guess
+    if max_faces is None:
+        max_faces = 2 * max_verts
+    if out is None:
+        verts = torch.empty((n, max_verts, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((n, max_faces, 3), dtype=torch.int32, device=dev)
+        counts = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    else:
+        _frame_rows(who, "out[0] (verts)", verts, n, (max_verts, 3), torch.float32, dev)
+        _frame_rows(who, "out[1] (faces)", faces, n, (max_faces, 3), torch.int32, dev)
+        _frame_rows(who, "out[2] (counts)", counts, n, (2,), torch.int32, dev)
+    ctx = get_context(dev)
+    for f0 in range(0, n, MAX_FRAMES):
+        f1 = min(f0 + MAX_FRAMES, n)
+        ctx.check(ctx.lib.mp_marching_cubes_batch(
+            ctx.handle, f1 - f0, _ptr_array(vols[f0:f1]), r, float(level), _float3(b_min), _float3(b_max),
+            _ptr_array(verts[f0:f1]), max_verts, _ptr_array(faces[f0:f1]), max_faces, _ptr_array(counts[f0:f1]),
+            None if gates is None else _ptr_array(gates[f0:f1]), _stream(verts)), "mp_marching_cubes_batch")
+    _keep_until_done(dev, vols, gates)
+    return [(verts[f], faces[f], counts[f]) for f in range(n)]
+
+
+def mesh_normals_raw_batch(verts, faces, counts, mode="accumulate", out=None):
+    """mp_mesh_normals_batch: ``[mesh_normals_raw(v, f, c, mode) for v, f, c in zip(verts, faces, counts)]`` (lists
+    of per-mesh device tensors as ``marching_cubes_raw_batch`` returns them, one capacity) in the launches of ONE
+    mesh per MAX_FRAMES meshes; the normals are views of one [n,max_v,3] tensor (``out`` if given), bit for bit what
+    the per-mesh call gives; rows beyond a mesh's counts[0] are not written.  No host sync."""
+    who = "mesh_normals_raw_batch"
+    n, max_v, max_f, dev = _mesh_frames(who, verts, faces, counts)
+    code = _normals_mode(mode)
+    if out is None:
+        out = torch.empty((n, max_v, 3), dtype=torch.float32, device=dev)
+    else:
+        _frame_rows(who, "out", out, n, (max_v, 3), torch.float32, dev)
+    ctx = get_context(dev)
+    for f0 in range(0, n, MAX_FRAMES):
+        f1 = min(f0 + MAX_FRAMES, n)
+        ctx.check(ctx.lib.mp_mesh_normals_batch(
+            ctx.handle, f1 - f0, _ptr_array(verts[f0:f1]), max_v, _ptr_array(faces[f0:f1]), max_f,
+            _ptr_array(counts[f0:f1]), code, _ptr_array(out[f0:f1]), _stream(out)), "mp_mesh_normals_batch")
+    return [out[f] for f in range(n)]
+
+
+def mesh_points_raw_batch(verts, counts, out=None):
+    """mp_mesh_points_batch: ``[mesh_points_raw(v, c) for v, c in zip(verts, counts)]`` in one launch per MAX_FRAMES
+    meshes: per mesh (points [3,max_v], count int32[1]), views of two tensors (``out`` = (points [n,3,max_v],
+    count [n,1]) if given; else the points start as zeros, as ``mesh_points_raw``'s).  No host sync."""
+    who = "mesh_points_raw_batch"
+    n, max_v, _, dev = _mesh_frames(who, verts, None, counts)
+    if out is None:
+        pts = torch.zeros((n, 3, max_v), dtype=torch.float32, device=dev)
+        count = torch.empty((n, 1), dtype=torch.int32, device=dev)
+    else:
+        pts = _frame_rows(who, "out[0] (points)", out[0], n, (3, max_v), torch.float32, dev)
+        count = _frame_rows(who, "out[1] (count)", out[1], n, (1,), torch.int32, dev)
+    ctx = get_context(dev)
+    for f0 in range(0, n, MAX_FRAMES):
+        f1 = min(f0 + MAX_FRAMES, n)
+        ctx.check(ctx.lib.mp_mesh_points_batch(
+            ctx.handle, f1 - f0, _ptr_array(verts[f0:f1]), max_v, _ptr_array(counts[f0:f1]), _ptr_array(pts[f0:f1]),
+            _ptr_array(count[f0:f1]), _stream(pts)), "mp_mesh_points_batch")
+    return [(pts[f], count[f]) for f in range(n)]
+
+
 def group_norm(x, groups, weight, bias, eps=1e-5, relu=False):
     """[relu](GroupNorm(x)) for x [N,C,H,W] f32 contiguous on the GPU (mp_group_norm)."""
     ctx = get_encoder_context(x.device)

@@ -36,6 +36,38 @@ RESOLUTIONS = (17, 33, 65, 129, 257)  # RTL/main.py:187
 _vb = os.environ.get("MONOPORT_VERTEX_BATCH", "4")
 VERTEX_BATCH = 0 if _vb == "off" else (int(_vb) if _vb.isdigit() else 10 ** 6)
 MAX_RECON_BATCH = ops.MAX_FRAMES  # kMaxFrames of the C-ABI (include/monoport_hip.h, mp_recon_batch): 32
+# frames per launch set of the mesh chain of a slot (FrameSlot(mesh=...); results are identical): "on" = all frames of
+# the slot (at most MAX_RECON_BATCH), "off" = one, or a number.  The chunk trades launches against the stream's scratch
+# arena (68 MB of marching-cubes vbase + 48 MB of normals scratch per frame at 257^3: 2.3 GB for 20 frames) and against
+# holding up the other slots' chains.  on: measured on 20-frame slots with netC colours and accumulate normals
+# (tools/mesh_timing.py --batched --passes 9, median ms per frame, meshes() included) 9.09 (1) / 8.87 (4) / 8.80 (all)
+# on single submissions, min-max spreads <= 0.06; with three slots submitted back to back 8.94 / 8.78 / 8.76, where
+# 4 and all lie inside each other's spread (0.16-0.19).  The same slots without mesh output: 6.34 / 6.31
+_mb = os.environ.get("MONOPORT_MESH_BATCH", "on")
+MESH_BATCH = 1 if _mb == "off" else min(int(_mb) if _mb.isdigit() and int(_mb) > 0 else MAX_RECON_BATCH, MAX_RECON_BATCH)
+MESH_KEYS = ("normals", "level", "colors")
+
+
+def _mesh_options(mesh, balance, has_netc):
+    """FrameSlot's ``mesh`` argument (a dict or an object with these attributes) -> (normals, level, colors)."""
+    if isinstance(mesh, dict):
+        unknown = sorted(set(mesh) - set(MESH_KEYS))
+        if unknown:
+            raise ValueError("FrameSlot(mesh=...): unknown keys %s (known: %s)" % (unknown, list(MESH_KEYS)))
+        get = mesh.get
+    else:
+        def get(key, default=None):
+            return getattr(mesh, key, default)
+    normals = get("normals", "accumulate")
+    if normals is not None and normals not in ops.NORMALS_MODES:
+        raise ValueError("FrameSlot(mesh=...): normals must be None or one of %s, got %r"
+                         % (sorted(ops.NORMALS_MODES), normals))
+    level = get("level")
+    colors = get("colors")
+    colors = has_netc if colors is None else bool(colors)
+    if colors and not has_netc:
+        raise ValueError("FrameSlot(mesh=...): colors need netC")
+    return normals, float(balance if level is None else level), colors
 
 
 class FrameSlot:
@@ -44,7 +76,13 @@ class FrameSlot:
 
     def __init__(self, netG, device, resolutions=RESOLUTIONS, b_min=(-1, -1, -1), b_max=(1, 1, 1),
                  balance=0.5, feature_hook=None, use_graph=False, netC=None, batch=1, skip_table=None,
-                 final_level="dilate3"):
+                 final_level="dilate3", mesh=None):
+        """``mesh``: None (no mesh output; nothing is allocated or enqueued for it), or a dict / options object with
+        ``normals`` ("accumulate" -- the default --, "reference" or None), ``level`` (the iso-level; default: the
+        slot's ``balance``) and ``colors`` (per-vertex netC colours; default: ``netC is not None``).  The slot then
+        owns static per-frame mesh buffers at the capacities of ``ops.marching_cubes_raw`` (12 r^2 vertices and
+        24 r^2 faces: vertices, faces, normals, query points and predictions are about 57 MB per frame at 257^3), the
+        batched mesh chain runs behind the octree on the slot's stream, and ``meshes()`` hands the results out."""
         for name, net in (("netG", netG), ("netC", netC)):
             if net is not None and net.surface_classifier.num_views > 1:
                 raise NotImplementedError("FrameSlot: %s has a multi-view head (num_views = %d); the slot runs the "
@@ -98,6 +136,21 @@ class FrameSlot:
                                 for _ in range(b)]
             self.mat_color = color_matrix(b_min, b_max, r)
             self.image_c = torch.zeros((b, 3, 512, 512), dtype=torch.float32, device=dev)
+        self.mesh = None if mesh is None else _mesh_options(mesh, self.balance, netC is not None)
+        if self.mesh is not None:
+            normals, _, colors = self.mesh
+            cap_v = 12 * r * r  # ops.marching_cubes_raw's capacities
+            cap_f = 2 * cap_v
+            self.mesh_buffers = {"verts": torch.empty((b, cap_v, 3), dtype=torch.float32, device=dev),
+                                 "faces": torch.empty((b, cap_f, 3), dtype=torch.int32, device=dev),
+                                 "counts": torch.zeros((b, 2), dtype=torch.int32, device=dev)}
+            if normals is not None:
+                self.mesh_buffers["normals"] = torch.empty((b, cap_v, 3), dtype=torch.float32, device=dev)
+            if colors:
+                self.mesh_buffers["points"] = torch.zeros((b, 3, cap_v), dtype=torch.float32, device=dev)
+                self.mesh_buffers["point_counts"] = torch.zeros((b, 1), dtype=torch.int32, device=dev)
+                self.mesh_buffers["preds"] = torch.zeros((b, 3, cap_v), dtype=torch.float32, device=dev)
+            self._mesh_chains = [None] * b
 
     # convenience views for batch == 1 callers
     @property
@@ -192,6 +245,56 @@ class FrameSlot:
                                       preds, 1, [self.vertices[b][4] for b in range(b0, b1)], r, 0.5, 0.5, -np.inf, np.inf)
                 for b in range(b0, b1):
                     self.renders_tex[b] = tex[b - b0]
+        if self.mesh is not None:
+            self._mesh_chain(n)
+
+    def _mesh_binding(self, b):
+        """Frame b's colour query as recon._mesh_chain takes it: netC's head on the slot's own map and calibration."""
+        from .modeling.MonoPortNet import QueryBinding
+        return QueryBinding(self.netC, self.netC.surface_classifier.packed(), self.feats_hwc_c[b],
+                            self.calib[b:b + 1], Z_SCALE)
+
+    def _mesh_chain(self, n):
+        """Marching cubes -> normals -> points -> netC colours of the slot's n frames into the slot's mesh buffers,
+        MESH_BATCH frames per set of launches, each frame gated by its status[b, 0] (the volume of a frame whose
+        coarsest octree level is empty is unspecified: its counts become (0, 0) and nothing else of it is touched)."""
+        from .recon import _mesh_chain_batch
+        normals, level, colors = self.mesh
+        for b0 in range(0, n, MESH_BATCH):
+            b1 = min(b0 + MESH_BATCH, n)
+            out = {k: v[b0:b1] for k, v in self.mesh_buffers.items()}
+            if colors:
+                out["preds"] = list(out["preds"])
+            self._mesh_chains[b0:b1] = _mesh_chain_batch(
+                self.volumes[b0:b1], level, self.b_min, self.b_max, normals,
+                [self._mesh_binding(b) for b in range(b0, b1)] if colors else None,
+                gates=[self.status[b, 0:1] for b in range(b0, b1)], out=out)
+
+    def meshes(self):
+        """The meshes of the current submission, to be called after ``wait()`` (it waits if the caller has not): a
+        list of ``n_active`` entries, a ``recon.Mesh`` per frame or None where the frame's coarsest octree level
+        was empty (status[b, 0] == 0).  ONE device-to-host copy (counts and status of all frames).  verts, faces and
+        normals are views of the slot's buffers, valid until the next ``submit`` (colours are fresh tensors).  A
+        frame whose mesh overflowed the slot's capacities (12 r^2 vertices, 24 r^2 faces) is re-run alone with
+        exact capacities here: all of its tensors are then fresh ones."""
+        if self.mesh is None:
+            raise RuntimeError("FrameSlot.meshes(): the slot was made without mesh=...")
+        from .recon import _finish_mesh, _mesh_chain
+        self.wait()
+        n = self.n_active
+        normals, level, colors = self.mesh
+        host = torch.cat([self.mesh_buffers["counts"][:n], self.status[:n, 0:1]], dim=1).cpu().tolist()
+        out = []
+        for b, (nv, nf, alive) in enumerate(host):
+            if not alive:
+                out.append(None)
+                continue
+            chain, short = self._mesh_chains[b], False
+            if nv > chain[0].shape[0] or nf > chain[1].shape[0]:
+                chain, short = _mesh_chain(self.volumes[b], level, self.b_min, self.b_max, normals,
+                                           self._mesh_binding(b) if colors else None, nv, nf), True
+            out.append(_finish_mesh(chain, nv, nf, raw_preds=not short))
+        return out
 
     def prepare(self, warmup=2):
         """Warm up (scratch arenas, GroupNorm accumulator arena); with ``use_graph`` capture the ENCODER into a

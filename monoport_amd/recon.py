@@ -149,8 +149,7 @@ def reconstruct_mesh(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normal
     runs once more with exact capacities.  A multi-view ``netC`` is not served here."""
     if sdf is None:
         return None
-    if normals is not None and normals not in ops.NORMALS_MODES:
-        raise ValueError("normals must be None or one of %s, got %r" % (sorted(ops.NORMALS_MODES), normals))
+    _check_normals(normals)
     binding = None
     if netC is not None:
         if netC.surface_classifier.num_views > 1:
@@ -166,6 +165,98 @@ def reconstruct_mesh(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normal
         verts, faces, counts, nrm, col = _mesh_chain(sdf, level, b_min, b_max, normals, binding, nv, nf)
     return Mesh(verts[:nv], faces[:nf], None if nrm is None else nrm[:nv],
                 None if col is None else col[:nv].contiguous())
+
+
+def _check_normals(normals):
+    if normals is not None and normals not in ops.NORMALS_MODES:
+        raise ValueError("normals must be None or one of %s, got %r" % (sorted(ops.NORMALS_MODES), normals))
+
+
+def _mesh_chain_batch(sdfs, level, b_min, b_max, normals, bindings, gates=None, out=None):
+    """``_mesh_chain`` for volumes of one size, every stage one set of launches for all of them: a list of
+    (verts, faces, counts, normals or None, netC predictions [3,max_v] or None) per volume, nothing synchronised
+    (``_finish_mesh(..., raw_preds=True)`` turns the predictions of the vertices present into colours).
+    ``bindings``: None or one QueryBinding per volume (one head).  ``out``: None or a dict of the caller's buffers
+    (verts, faces, counts, normals, points, point_counts, preds: [n, ...] tensors, preds a list)."""
+    out = out or {}
+    n = len(sdfs)
+    mc_out = (out["verts"], out["faces"], out["counts"]) if "verts" in out else None
+    raws = ops.marching_cubes_raw_batch(sdfs, level, b_min, b_max, gates=gates, out=mc_out)
+    verts, faces, counts = ([r[k] for r in raws] for k in range(3))
+    nrm = [None] * n
+    if normals is not None:
+        nrm = ops.mesh_normals_raw_batch(verts, faces, counts, normals, out=out.get("normals"))
+    preds = [None] * n
+    if bindings is not None:
+        pt_out = (out["points"], out["point_counts"]) if "points" in out else None
+        pts = ops.mesh_points_raw_batch(verts, counts, out=pt_out)
+        b0 = bindings[0]
+        ortho = all(b.projection == ops.PROJECTIONS["orthogonal"] for b in bindings)
+        preds = []
+        for f0 in range(0, n, ops.MAX_FRAMES):
+            f1 = min(f0 + ops.MAX_FRAMES, n)
+            preds += ops.query_counted_batch(
+                b0.mlp, [b.feat_hwc for b in bindings[f0:f1]], [p[0] for p in pts[f0:f1]],
+                [p[1] for p in pts[f0:f1]], [b.calib for b in bindings[f0:f1]], b0.z_scale,
+                outs=None if "preds" not in out else out["preds"][f0:f1],
+                projections=None if ortho else [b.projection for b in bindings[f0:f1]])
+    return [(verts[f], faces[f], counts[f], nrm[f], preds[f]) for f in range(n)]
+
+
+def _finish_mesh(chain, nv, nf, raw_preds=False):
+    """The ``Mesh`` of a chain's capacity-sized tensors once the counts are on the host."""
+    verts, faces, _, nrm, col = chain
+    if col is not None:  # elementwise: the same bits whether the rows are cut before or after
+        col = ((col[:, :nv] * 0.5 + 0.5).t() if raw_preds else col[:nv]).contiguous()
+    return Mesh(verts[:nv], faces[:nf], None if nrm is None else nrm[:nv], col)
+
+
+@torch.no_grad()
+def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normals="accumulate", netC=None,
+                          feat_tensors_C=None, calib_tensors=None):
+    """``[reconstruct_mesh(s, level, b_min, b_max, normals, netC, feat_tensors_C[i], calib_tensors[i]) for i, s in
+    enumerate(sdfs)]`` -- every field of every ``Mesh`` the same bits -- with the chain enqueued ONCE for all volumes
+    (batched marching cubes, normals, points and one counted colour query per ops.MAX_FRAMES volumes) and ONE host
+    sync for all the counts (monoport_amd extension; the hook of a coalescing stage).  ``None`` entries of ``sdfs``
+    give ``None``; the other volumes must be of one size (ValueError).  ``feat_tensors_C`` / ``calib_tensors``: one
+    entry per volume (those of ``None`` volumes are not looked at).  A volume whose capacity guess was short is
+    re-run alone with exact capacities, as ``reconstruct_mesh`` does.  A multi-view ``netC`` is not served here."""
+    sdfs = list(sdfs)
+    _check_normals(normals)
+    if netC is not None:
+        if netC.surface_classifier.num_views > 1:
+            raise NotImplementedError("reconstruct_mesh_many: netC has num_views = %d; colour the vertices of a "
+                                      "multi-view head with mesh_util.vertex_colors"
+                                      % netC.surface_classifier.num_views)
+        if feat_tensors_C is None or calib_tensors is None:
+            raise ValueError("reconstruct_mesh_many: netC needs feat_tensors_C and calib_tensors")
+        if len(feat_tensors_C) != len(sdfs) or len(calib_tensors) != len(sdfs):
+            raise ValueError("reconstruct_mesh_many: %d volumes, %d feature sets, %d calibrations"
+                             % (len(sdfs), len(feat_tensors_C), len(calib_tensors)))
+    idx = [i for i, s in enumerate(sdfs) if s is not None]
+    if len({tuple(sdfs[i].shape[-3:]) for i in idx}) > 1:
+        raise ValueError("reconstruct_mesh_many wants volumes of one size, got %s"
+                         % sorted({tuple(sdfs[i].shape[-3:]) for i in idx}))
+    meshes = [None] * len(sdfs)
+    if not idx:
+        return meshes
+    live = [sdfs[i] for i in idx]
+    bindings = None
+    if netC is not None:
+        bindings = []
+        for i in idx:
+            feats = [[f.to(sdfs[i].device) for f in fs] for fs in feat_tensors_C[i]]
+            bindings.append(netC.bind(feats, calib_tensors[i]))
+    chains = _mesh_chain_batch(live, level, b_min, b_max, normals, bindings)
+    sizes = torch.stack([c[2] for c in chains]).cpu().tolist()  # the one host sync
+    for k, i in enumerate(idx):
+        nv, nf = sizes[k]
+        chain, short = chains[k], False
+        if nv > chain[0].shape[0] or nf > chain[1].shape[0]:
+            chain, short = _mesh_chain(live[k], level, b_min, b_max, normals,
+                                       None if bindings is None else bindings[k], nv, nf), True
+        meshes[i] = _finish_mesh(chain, nv, nf, raw_preds=not short)
+    return meshes
 
 
 @torch.no_grad()

@@ -7,6 +7,14 @@
 
     python tools/mesh_timing.py [--passes 5] [--meshes 20] [--out profiles/mesh_timing.json]
 
+``--batched`` measures the batched chain instead (profiles/mesh_batch_timing.json): on the same volume and netC, at
+n = 4 and n = 20 meshes, n calls of recon.reconstruct_mesh against ONE recon.reconstruct_mesh_many, with and without
+colours (normals="accumulate" in both), per-mesh milliseconds; and a pipeline.FrameSlot(mesh=...) of 20 frames
+(encoders as a hipGraph, netC, the bench's synthetic frames) with pipeline.MESH_BATCH at 1 / 4 / all frames, alone and
+as three slots submitted back to back, per-frame milliseconds -- next to the same slots without mesh output.
+
+    python tools/mesh_timing.py --batched [--passes 5] [--out profiles/mesh_batch_timing.json]
+
 The protocol of tools/recon_views_timing.py: after a warm-up of all, the passes alternate; a pass is `meshes`
 meshes, wall clock around a final stream sync.  Prints (and writes) one JSON line: per way the median, minimum and
 maximum time per mesh (ms) over the passes.  The verdict fields restate what to check: (b) not slower than (a) by
@@ -25,7 +33,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from monoport_amd import mesh_util, ops, synthetic as syn  # noqa: E402
 from monoport_amd.modeling import PIFuNetC  # noqa: E402
-from monoport_amd.recon import marching_cubes, reconstruct_mesh  # noqa: E402
+from monoport_amd.recon import marching_cubes, reconstruct_mesh, reconstruct_mesh_many  # noqa: E402
 from oracle import pifu_oracle as orc  # noqa: E402
 
 DEV = "cuda:0"
@@ -37,8 +45,11 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--passes", type=int, default=5)
     ap.add_argument("--meshes", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_timing.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--batched", action="store_true", help="the batched chain and the slot's MESH_BATCH settings")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "mesh_batch_timing.json" if a.batched else "mesh_timing.json")
     mlp = ops.PackedMLP.from_layers(DEV, syn.body_mlp("G", noise=0.05, seed=1), 1)
     fh = ops.pack_features(torch.from_numpy(syn.body_feat(256, 128, 128, 2))[None].to(DEV))
     cal = torch.from_numpy(orc.pifu_calib(*syn.scene_camera(30))).to(DEV)
@@ -54,6 +65,12 @@ def main():
     netC.eval()
     feat_C = [[torch.from_numpy(syn.rand_feat(512, 128, 128, 62))[None].to(DEV)]]
     calib = torch.eye(4, device=DEV)[None]
+
+    if a.batched:
+        out = batched(a, vol, netC, feat_C, calib)
+        out["slot"] = slot_mesh_batch(a)
+        write(a, out)
+        return
 
     def two_calls():
         verts, faces = marching_cubes(vol, 0.5, BMIN, BMAX)
@@ -95,11 +112,114 @@ def main():
         out["chain"]["median_ms"] <= out["two_calls"]["median_ms"] + spread)
     out["normals_add_ms"] = round(out["chain_normals"]["median_ms"] - out["chain"]["median_ms"], 4)
     out["reference_normals_add_ms"] = round(out["chain_normals_reference"]["median_ms"] - out["chain"]["median_ms"], 4)
+    write(a, out)
+
+
+def write(a, out):
     line = json.dumps(out)
     print(line, flush=True)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as fh_:
         fh_.write(line + "\n")
+
+
+def stats(ms):
+    t = np.array(ms)
+    return {"median_ms": round(float(np.median(t)), 4), "min_ms": round(float(t.min()), 4),
+            "max_ms": round(float(t.max()), 4)}
+
+
+def alternate(ways, passes, per):
+    """Warm-up of all, then ``passes`` alternating passes: wall clock around a final device sync, per ``per`` items."""
+    for fn in ways.values():
+        fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in ways}
+    for _ in range(passes):
+        for name, fn in ways.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) * 1e3 / per)
+    return {name: stats(t) for name, t in times.items()}
+
+
+def batched(a, vol, netC, feat_C, calib):
+    """n x reconstruct_mesh against one reconstruct_mesh_many, per-mesh ms, with and without colours."""
+    out = {"resolutions": RES, "passes": a.passes, "normals": "accumulate", "unit": "ms per mesh"}
+    for n in (4, 20):
+        def calls(colour):
+            kw = dict(netC=netC, feat_tensor_C=feat_C, calib_tensor=calib) if colour else {}
+            return lambda: [reconstruct_mesh(vol, 0.5, BMIN, BMAX, **kw) for _ in range(n)]
+
+        def many(colour):
+            kw = dict(netC=netC, feat_tensors_C=[feat_C] * n, calib_tensors=[calib] * n) if colour else {}
+            return lambda: reconstruct_mesh_many([vol] * n, 0.5, BMIN, BMAX, **kw)
+
+        ways = {"calls_colours": calls(True), "many_colours": many(True), "calls": calls(False), "many": many(False)}
+        one, all_ = ways["calls_colours"]()[0], ways["many_colours"]()
+        same = all(torch.equal(x, y) for m in all_ for x, y in zip(m, one))
+        res = alternate(ways, a.passes, n)
+        res["equal"] = bool(same)
+        res["many_over_calls_colours"] = round(res["many_colours"]["median_ms"] / res["calls_colours"]["median_ms"], 4)
+        res["many_over_calls"] = round(res["many"]["median_ms"] / res["calls"]["median_ms"], 4)
+        out["n%d" % n] = res
+        out["vertices"], out["faces"] = int(one.verts.shape[0]), int(one.faces.shape[0])
+    return out
+
+
+def slot_mesh_batch(a, frames=20):
+    """A slot of ``frames`` frames with mesh output, pipeline.MESH_BATCH at 1 / 4 / all, per-frame ms of a submission
+    (wait and the one host read of ``meshes()`` included); alone and as three slots submitted back to back."""
+    from bench_common import B_MAX, B_MIN, RESOLUTIONS, build_netc, build_netg
+    from monoport_amd import pipeline
+    from monoport_amd.recon import pifu_calib
+    dev = torch.device(DEV)
+    netg, netc = build_netg(dev)[0], build_netc(dev)
+    planes = torch.from_numpy(syn.body_feature_planes(128, 128)).to(dev)
+    planes_hwc = planes.permute(1, 2, 0).contiguous()
+
+    def hook(feat):  # the bench's synthetic-data hook: channels 0 / 1 are the body's depth planes
+        feat[:, 0:2].copy_(planes[None].expand(feat.shape[0], -1, -1, -1))
+
+    def hook_hwc(feat_hwc):
+        feat_hwc[..., 0:2].copy_(planes_hwc[None].expand(feat_hwc.shape[0], -1, -1, -1))
+
+    hook.hwc = hook_hwc
+    images = torch.stack([torch.from_numpy(syn.synthetic_image(f % 8)) for f in range(frames)]).to(dev)
+    calibs = torch.cat([pifu_calib(*syn.scene_camera(3 * f), device=DEV) for f in range(frames)])
+    out = {"frames_per_slot": frames, "unit": "ms per frame", "normals": "accumulate", "colors": True}
+    for depth in (1, 3):
+        pipes = {}
+        for name, mesh in (("mesh", {"normals": "accumulate"}), ("no_mesh", None)):
+            pipes[name] = pipeline.FramePipeline(netg, dev, depth=depth, batch=frames, resolutions=RESOLUTIONS,
+                                                 b_min=B_MIN, b_max=B_MAX, feature_hook=hook, use_graph=True,
+                                                 netC=netc, mesh=mesh)
+            pipes[name].prepare()
+
+        def run(name, mesh_batch):
+            def fn():
+                pipeline.MESH_BATCH = mesh_batch
+                slots = [pipes[name].submit(images, calibs) for _ in range(depth)]
+                for s in slots:
+                    if name == "mesh":
+                        assert all(m is not None for m in s.meshes())
+                    else:
+                        s.wait()
+            return fn
+
+        ways = {"mesh_batch_1": run("mesh", 1), "mesh_batch_4": run("mesh", 4), "mesh_batch_all": run("mesh", frames),
+                "no_mesh": run("no_mesh", 4)}
+        res = alternate(ways, a.passes, frames * depth)
+        m = pipes["mesh"].slots[0].meshes()[0]
+        res["vertices"], res["faces"] = int(m.verts.shape[0]), int(m.faces.shape[0])
+        out["depth%d" % depth] = res
+        for p_ in pipes.values():
+            p_.close()
+        del pipes
+        torch.cuda.empty_cache()
+    return out
 
 
 if __name__ == "__main__":
