@@ -488,6 +488,36 @@ int mp_mesh_points_batch(mp_ctx *ctx, int n_frames, const float *const *verts, i
                          const int32_t *const *counts, float *const *points, int32_t *const *count_out,
                          mp_stream stream);
 
+/* The largest connected body of an occupancy volume [R,R,R] (no counterpart in the reference; the clean-up in front
+ * of marching cubes that drops floating blobs).
+ *   Foreground: voxels with value > level (marching cubes' "inside"; a NaN and value == level are background).
+ *   Components: those of the foreground under `connectivity`: MP_CONN_6 (face neighbours) or MP_CONN_26 (face, edge
+ * and corner neighbours).  A component's id is the smallest linear index (z*R + y)*R + x among its voxels.  The
+ * component with the most voxels is kept; of several that large, the one with the smallest id.
+ *   out[v] = volume[v] (the same bits) for every background voxel and every voxel of the kept component, `fill` for
+ * every other foreground voxel; without foreground, out == volume.  `fill` must not be foreground itself: fill > level
+ * and a NaN fill are refused (MP_ERR_ARG).  `out` may be `volume`.
+ *   stats (device int32[4]): [0] foreground voxels, [1] components, [2] voxels of the kept component, [3] its id
+ * (-1 without foreground).
+ *   A union-find labelling with integer atomics only: the result is a pure function of the input, the same bits in
+ * every run.  Six launches; scratch from the stream's arena: 4 * ceil4(r^3) + 1024 bytes (68 MB at 257^3).
+ * r^3 >= 2^31: MP_ERR_UNSUPPORTED.  Asynchronous. */
+enum { MP_CONN_6 = 6, MP_CONN_26 = 26 };
+int mp_volume_keep_largest(mp_ctx *ctx, const float *volume, int r, float level, int connectivity, float fill,
+                           float *out, int32_t *stats, mp_stream stream);
+/* The call above over n_frames (1..mp_max_frames(), else MP_ERR_ARG) volumes of one resolution in ONE set of six
+ * launches; volume / out / stats / gate are HOST arrays of n_frames device pointers, each as in the per-volume call.
+ * Frame f's out and stats equal those of mp_volume_keep_largest on frame f's inputs BIT FOR BIT; every per-frame size
+ * comes from that frame's own device data.
+ *   gate (NULL, or entries NULL = frame on), as in mp_marching_cubes_batch: gate[f] is a device int32; if it reads 0,
+ * frame f's stats become {0, 0, 0, -1} and nothing else of that frame is read or written (its volume may be the
+ * unspecified volume of an mp_recon_batch frame whose status[0] is 0).
+ *   Scratch from the stream's arena: n_frames * (4 * ceil4(r^3) + 1024) bytes.  Refusals as in the per-volume call,
+ * each with an mp_last_error message; a null or not 4-byte aligned buffer of any frame: MP_ERR_ARG.  Asynchronous. */
+int mp_volume_keep_largest_batch(mp_ctx *ctx, int n_frames, const float *const *volume, int r, float level,
+                                 int connectivity, float fill, float *const *out, int32_t *const *stats,
+                                 const int32_t *const *gate, mp_stream stream);
+
 /* ---- encoder helpers (stand-alone GroupNorm / upsample / concat kernels -- the
  * convolutions are the mp_conv* entry points below, nothing of the inference path is left on MIOpen) ---------- */
 /* y = [relu](GroupNorm(groups, C)(x)): x, y [N,C,HW] f32 (contiguous NCHW), gamma/beta [C];

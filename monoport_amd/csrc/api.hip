@@ -1178,6 +1178,41 @@ int mp_mesh_points_batch(mp_ctx *ctx, int n_frames, const float *const *verts, i
   return launch_mesh_points_batch(ctx, n_frames, verts_p, max_verts, counts, points_p, count_out, (hipStream_t)stream);
 }
 
+int mp_volume_keep_largest_batch(mp_ctx *ctx, int n_frames, const float *const *volume, int r, float level,
+                                 int connectivity, float fill, float *const *out, int32_t *const *stats,
+                                 const int32_t *const *gate, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (n_frames < 1 || n_frames > kMaxFrames)
+    return fail(ctx, MP_ERR_ARG, "mp_volume_keep_largest_batch: 1..%d frames per call, got %d", kMaxFrames, n_frames);
+  if (!volume || !out || !stats || r < 1)
+    return fail(ctx, MP_ERR_ARG, "mp_volume_keep_largest_batch: bad argument");
+  if (connectivity != MP_CONN_6 && connectivity != MP_CONN_26)
+    return fail(ctx, MP_ERR_ARG, "mp_volume_keep_largest_batch: connectivity must be 6 or 26, got %d", connectivity);
+  if (!(fill <= level))  // a NaN fill fails this test too
+    return fail(ctx, MP_ERR_ARG, "mp_volume_keep_largest_batch: fill %g would be foreground at level %g", (double)fill,
+                (double)level);
+  for (int f = 0; f < n_frames; ++f) {
+    if (!volume[f] || !out[f] || !stats[f])
+      return fail(ctx, MP_ERR_ARG, "mp_volume_keep_largest_batch: null buffer for frame %d", f);
+    if (((uintptr_t)volume[f] | (uintptr_t)out[f] | (uintptr_t)stats[f] | (uintptr_t)(gate ? gate[f] : nullptr)) & 3)
+      return fail(ctx, MP_ERR_ARG, "mp_volume_keep_largest_batch: misaligned buffer for frame %d", f);
+  }
+  if (r > 1290)  // 1291^3 > 2^31
+    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_volume_keep_largest_batch: resolution %d needs 64-bit voxel indices", r);
+  DeviceGuard g(ctx->device);
+  void *scratch = nullptr;
+  int rc = ensure_scratch(ctx, (hipStream_t)stream, (size_t)n_frames * cc_scratch_bytes(r), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_keep_largest_batch(ctx, scratch, n_frames, volume, r, level, connectivity, fill, out, stats, gate,
+                                   (hipStream_t)stream);
+}
+
+int mp_volume_keep_largest(mp_ctx *ctx, const float *volume, int r, float level, int connectivity, float fill,
+                           float *out, int32_t *stats, mp_stream stream) {
+  return mp_volume_keep_largest_batch(ctx, 1, &volume, r, level, connectivity, fill, &out, &stats, nullptr, stream);
+}
+
 int mp_group_norm(mp_ctx *ctx, const float *x, int n, int c, int64_t hw, int groups,
                   const float *gamma, const float *beta, float eps, int relu, float *y,
                   mp_stream stream) {

@@ -366,6 +366,12 @@ int launch_marching_cubes_batch(mp_ctx *ctx, void *scratch, int n_frames, const 
                                 const float *bmin, const float *bmax, float *const *verts, long long max_v,
                                 int32_t *const *faces, long long max_f, int32_t *const *counts,
                                 const int32_t *const *gate, hipStream_t st);
+// components.hip: the largest connected body of n_frames volumes of one resolution (out[f] may be vol[f]); scratch:
+// n_frames * cc_scratch_bytes(r); gate: NULL or n_frames entries
+size_t cc_scratch_bytes(int r);
+int launch_keep_largest_batch(mp_ctx *ctx, void *scratch, int n_frames, const float *const *vol, int r, float level,
+                              int connectivity, float fill, float *const *out, int32_t *const *stats,
+                              const int32_t *const *gate, hipStream_t st);
 // mesh.hip
 size_t mesh_normals_scratch_bytes(int n_frames, long long max_v, long long max_f);
 int launch_mesh_normals_batch(mp_ctx *ctx, void *scratch, int n_frames, const float *const *verts, long long max_v,

@@ -1201,6 +1201,77 @@ def mesh_points_raw_batch(verts, counts, out=None):
     return [(pts[f], count[f]) for f in range(n)]
 
 
+# MP_CONN_* (include/monoport_hip.h): face neighbours / face, edge and corner neighbours
+CONNECTIVITIES = (_lib.CONN_6, _lib.CONN_26)
+
+
+def _keep_largest_args(who, level, connectivity, fill):
+    if connectivity not in CONNECTIVITIES:
+        raise ValueError("%s: connectivity must be one of %s, got %r" % (who, list(CONNECTIVITIES), connectivity))
+    if not float(fill) <= float(level):  # a NaN fill fails this test too
+        raise ValueError("%s: fill %r would be foreground at level %r" % (who, fill, level))
+    return float(level), int(connectivity), float(fill)
+
+
+def keep_largest_raw(sdf, level=0.5, connectivity=6, fill=0.0, out=None):
+    """mp_volume_keep_largest: the cubic volume with every voxel > level outside its largest connected body
+    (``connectivity`` 6 or 26; ties: the smallest linear index) replaced by ``fill`` -> (volume [R,R,R] f32, stats
+    int32[4] = foreground voxels, components, voxels kept, id of the kept component or -1) on device.  ``out``: a
+    contiguous f32 [R,R,R] tensor to write into (it may be the volume itself).  No host sync."""
+    who = "keep_largest_raw"
+    vol = _cubic_volume(sdf, who)
+    level, connectivity, fill = _keep_largest_args(who, level, connectivity, fill)
+    r = vol.shape[0]
+    if out is None:
+        out = torch.empty_like(vol)
+    elif tuple(out.shape) != (r, r, r) or out.dtype != torch.float32 or out.device != vol.device or not out.is_contiguous():
+        raise ValueError("%s: out must be a contiguous float32 %s on %s" % (who, [r, r, r], vol.device))
+    stats = torch.empty((4,), dtype=torch.int32, device=vol.device)
+    ctx = get_context(vol.device)
+    ctx.check(ctx.lib.mp_volume_keep_largest(ctx.handle, _ptr(vol), r, level, connectivity, fill, _ptr(out),
+                                             _ptr(stats), _stream(vol)), "mp_volume_keep_largest")
+    _keep_until_done(vol.device, [vol])
+    return out, stats
+
+
+def keep_largest_raw_batch(sdfs, level=0.5, connectivity=6, fill=0.0, gates=None, out=None):
+    """mp_volume_keep_largest_batch: ``[keep_largest_raw(s, ...) for s in sdfs]`` (cubic volumes of one size on one
+    device) in one set of six launches per MAX_FRAMES volumes: per volume (volume [R,R,R], stats int32[4]), views of
+    two tensors and bit for bit what the per-volume call gives.  ``gates``: per-frame device int32 tensors (or None
+    entries = frame on); a frame whose gate reads 0 gets stats (0, 0, 0, -1) and nothing else of it is read or
+    written.  ``out``: (volumes [n,R,R,R] f32, stats [n,4] int32) to write into.  No host sync."""
+    who = "keep_largest_raw_batch"
+    vols = [_cubic_volume(v, who) for v in sdfs]
+    n = len(vols)
+    if n == 0:
+        raise ValueError("%s wants at least one volume" % who)
+    level, connectivity, fill = _keep_largest_args(who, level, connectivity, fill)
+    r = vols[0].shape[0]
+    dev = vols[0].device
+    if any(v.shape[0] != r or v.device != dev for v in vols):
+        raise ValueError("%s wants cubic volumes of one size on one device" % who)
+    if gates is not None:
+        if len(gates) != n:
+            raise ValueError("%s: %d volumes, %d gates" % (who, n, len(gates)))
+        if any(g is not None and (g.dtype != torch.int32 or g.numel() < 1 or g.device != dev) for g in gates):
+            raise ValueError("%s: a gate is an int32 tensor on the volumes' device" % who)
+    if out is None:
+        cleaned = torch.empty((n, r, r, r), dtype=torch.float32, device=dev)
+        stats = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    else:
+        cleaned = _frame_rows(who, "out[0] (volumes)", out[0], n, (r, r, r), torch.float32, dev)
+        stats = _frame_rows(who, "out[1] (stats)", out[1], n, (4,), torch.int32, dev)
+    ctx = get_context(dev)
+    for f0 in range(0, n, MAX_FRAMES):
+        f1 = min(f0 + MAX_FRAMES, n)
+        ctx.check(ctx.lib.mp_volume_keep_largest_batch(
+            ctx.handle, f1 - f0, _ptr_array(vols[f0:f1]), r, level, connectivity, fill, _ptr_array(cleaned[f0:f1]),
+            _ptr_array(stats[f0:f1]), None if gates is None else _ptr_array(gates[f0:f1]), _stream(cleaned)),
+            "mp_volume_keep_largest_batch")
+    _keep_until_done(dev, vols, gates)
+    return [(cleaned[f], stats[f]) for f in range(n)]
+
+
 def group_norm(x, groups, weight, bias, eps=1e-5, relu=False):
     """[relu](GroupNorm(x)) for x [N,C,H,W] f32 contiguous on the GPU (mp_group_norm)."""
     ctx = get_encoder_context(x.device)

@@ -45,7 +45,7 @@ MAX_RECON_BATCH = ops.MAX_FRAMES  # kMaxFrames of the C-ABI (include/monoport_hi
 # 4 and all lie inside each other's spread (0.16-0.19).  The same slots without mesh output: 6.34 / 6.31
 _mb = os.environ.get("MONOPORT_MESH_BATCH", "on")
 MESH_BATCH = 1 if _mb == "off" else min(int(_mb) if _mb.isdigit() and int(_mb) > 0 else MAX_RECON_BATCH, MAX_RECON_BATCH)
-MESH_KEYS = ("normals", "level", "colors")
+MESH_KEYS = ("normals", "level", "colors", "clean")
 
 
 def _mesh_options(mesh, balance, has_netc):
@@ -70,6 +70,14 @@ def _mesh_options(mesh, balance, has_netc):
     return normals, float(balance if level is None else level), colors
 
 
+def _mesh_clean_option(mesh, level):
+    """The ``clean`` entry of FrameSlot's ``mesh`` argument: None, or the connectivity of recon.keep_largest."""
+    from .recon import _check_clean
+    clean = mesh.get("clean") if isinstance(mesh, dict) else getattr(mesh, "clean", None)
+    _check_clean(clean, level)
+    return clean
+
+
 class FrameSlot:
     """Static buffers for ``batch`` in-flight frames (geometry chain of RTL/main.py:366-428, plus
     the netC texture stages :373-441 when ``netC`` is given)."""
@@ -79,7 +87,10 @@ class FrameSlot:
                  final_level="dilate3", mesh=None):
         """``mesh``: None (no mesh output; nothing is allocated or enqueued for it), or a dict / options object with
         ``normals`` ("accumulate" -- the default --, "reference" or None), ``level`` (the iso-level; default: the
-        slot's ``balance``) and ``colors`` (per-vertex netC colours; default: ``netC is not None``).  The slot then
+        slot's ``balance``) and ``colors`` (per-vertex netC colours; default: ``netC is not None``) and ``clean`` (None -- the default: nothing
+        is allocated or enqueued for it --, or 6 / 26: marching cubes sees only the largest connected body of each
+        volume, ``recon.keep_largest`` into copies that live in mesh buffers of one mesh chunk of frames;
+        ``volumes``, the renders and every other consumer see the unchanged volume).  The slot then
         owns static per-frame mesh buffers at the capacities of ``ops.marching_cubes_raw`` (12 r^2 vertices and
         24 r^2 faces: vertices, faces, normals, query points and predictions are about 57 MB per frame at 257^3), the
         batched mesh chain runs behind the octree on the slot's stream, and ``meshes()`` hands the results out."""
@@ -151,6 +162,12 @@ class FrameSlot:
                 self.mesh_buffers["point_counts"] = torch.zeros((b, 1), dtype=torch.int32, device=dev)
                 self.mesh_buffers["preds"] = torch.zeros((b, 3, cap_v), dtype=torch.float32, device=dev)
             self._mesh_chains = [None] * b
+        # kept beside ``mesh`` (which stays the (normals, level, colors) triple)
+        self.mesh_clean = None if mesh is None else _mesh_clean_option(mesh, self.mesh[1])
+        if self.mesh_clean is not None:
+            chunk = min(MESH_BATCH, b)  # the cleaned copies are consumed chunk by chunk (68 MB per frame at 257^3)
+            self.mesh_buffers["cleaned"] = torch.empty((chunk, r, r, r), dtype=torch.float32, device=dev)
+            self.mesh_buffers["clean_stats"] = torch.zeros((b, 4), dtype=torch.int32, device=dev)
 
     # convenience views for batch == 1 callers
     @property
@@ -257,18 +274,24 @@ class FrameSlot:
     def _mesh_chain(self, n):
         """Marching cubes -> normals -> points -> netC colours of the slot's n frames into the slot's mesh buffers,
         MESH_BATCH frames per set of launches, each frame gated by its status[b, 0] (the volume of a frame whose
-        coarsest octree level is empty is unspecified: its counts become (0, 0) and nothing else of it is touched)."""
+        coarsest octree level is empty is unspecified: its counts become (0, 0) and nothing else of it is touched).  With
+        ``clean`` the chain starts with recon.keep_largest of the chunk's volumes, under the same gates."""
         from .recon import _mesh_chain_batch
         normals, level, colors = self.mesh
-        for b0 in range(0, n, MESH_BATCH):
-            b1 = min(b0 + MESH_BATCH, n)
+        chunk = MESH_BATCH
+        if self.mesh_clean is not None:  # one chunk's cleaned volumes at a time, in the same buffer
+            chunk = min(chunk, self.mesh_buffers["cleaned"].shape[0])
+        for b0 in range(0, n, chunk):
+            b1 = min(b0 + chunk, n)
             out = {k: v[b0:b1] for k, v in self.mesh_buffers.items()}
+            if self.mesh_clean is not None:
+                out["cleaned"] = self.mesh_buffers["cleaned"][:b1 - b0]
             if colors:
                 out["preds"] = list(out["preds"])
             self._mesh_chains[b0:b1] = _mesh_chain_batch(
                 self.volumes[b0:b1], level, self.b_min, self.b_max, normals,
                 [self._mesh_binding(b) for b in range(b0, b1)] if colors else None,
-                gates=[self.status[b, 0:1] for b in range(b0, b1)], out=out)
+                gates=[self.status[b, 0:1] for b in range(b0, b1)], out=out, clean=self.mesh_clean)
 
     def meshes(self):
         """The meshes of the current submission, to be called after ``wait()`` (it waits if the caller has not): a
@@ -292,7 +315,8 @@ class FrameSlot:
             chain, short = self._mesh_chains[b], False
             if nv > chain[0].shape[0] or nf > chain[1].shape[0]:
                 chain, short = _mesh_chain(self.volumes[b], level, self.b_min, self.b_max, normals,
-                                           self._mesh_binding(b) if colors else None, nv, nf), True
+                                           self._mesh_binding(b) if colors else None, nv, nf,
+                                           clean=self.mesh_clean), True
             out.append(_finish_mesh(chain, nv, nf, raw_preds=not short))
         return out
 

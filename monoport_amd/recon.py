@@ -116,13 +116,56 @@ def marching_cubes(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1)):
     return verts[:nv], faces[:nf]
 
 
+CLEAN_FILL = 0.0  # what ``clean`` puts into dropped voxels: below every level a sigmoid field is cut at
+
+
+@torch.no_grad()
+def keep_largest(sdf, level=0.5, connectivity=6, fill=0.0):
+    """The occupancy volume [1,1,D,H,W] (or [D,H,W]) without its floating blobs: of the voxels > ``level`` only the
+    largest connected body stays (``connectivity`` 6: face neighbours, 26: edges and corners too; of equally large
+    bodies the one with the smallest linear index), every other such voxel becomes ``fill`` (<= level); all other
+    voxels keep their bits.  Returns a new volume of the input's shape, None for ``sdf is None``.  On the device,
+    nothing synchronised (``ops.keep_largest_raw`` also hands out the statistics).  Not part of the reference."""
+    if sdf is None:
+        return None
+    return ops.keep_largest_raw(sdf, level, connectivity, fill)[0].reshape(sdf.shape)
+
+
+@torch.no_grad()
+def keep_largest_many(sdfs, level=0.5, connectivity=6, fill=0.0):
+    """``[keep_largest(s, level, connectivity, fill) for s in sdfs]`` -- the same bits -- in one set of launches per
+    ops.MAX_FRAMES volumes.  ``None`` entries give ``None``; the other volumes must be of one size (ValueError)."""
+    sdfs = list(sdfs)
+    idx = [i for i, s in enumerate(sdfs) if s is not None]
+    out = [None] * len(sdfs)
+    if idx:
+        raws = ops.keep_largest_raw_batch([sdfs[i] for i in idx], level, connectivity, fill)
+        for i, (vol, _) in zip(idx, raws):
+            out[i] = vol.reshape(sdfs[i].shape)
+    return out
+
+
 Mesh = collections.namedtuple("Mesh", ["verts", "faces", "normals", "colors"])
 Mesh.__doc__ = """Triangle mesh of ``reconstruct_mesh``: verts [V,3] f32 world coordinates, faces [F,3] int32,
 normals [V,3] f32 or None, colors [V,3] f32 in [0,1] or None."""
 
 
-def _mesh_chain(sdf, level, b_min, b_max, normals, binding, max_verts=None, max_faces=None):
-    """volume -> verts, faces -> normals -> colours, enqueued without a host value in between."""
+def _check_clean(clean, level):
+    """The ``clean`` option of the mesh calls: None, or the connectivity (6 / 26) of ``keep_largest`` in front of
+    marching cubes; dropped voxels become 0.0, which must lie below the level."""
+    if clean is None:
+        return
+    if clean not in ops.CONNECTIVITIES:
+        raise ValueError("clean must be None or one of %s, got %r" % (list(ops.CONNECTIVITIES), clean))
+    if not float(level) > 0.0:
+        raise ValueError("clean fills the dropped voxels with 0.0: it needs level > 0, got %r" % (level,))
+
+
+def _mesh_chain(sdf, level, b_min, b_max, normals, binding, max_verts=None, max_faces=None, clean=None):
+    """volume [-> its largest body] -> verts, faces -> normals -> colours, enqueued without a host value in
+    between."""
+    if clean is not None:  # into a scratch volume: the caller's is never modified
+        sdf = ops.keep_largest_raw(sdf, level, clean, CLEAN_FILL)[0]
     verts, faces, counts = ops.marching_cubes_raw(sdf, level, b_min, b_max, max_verts=max_verts,
                                                   max_faces=max_faces)
     nrm = ops.mesh_normals_raw(verts, faces, counts, normals) if normals is not None else None
@@ -140,16 +183,19 @@ def _mesh_chain(sdf, level, b_min, b_max, normals, binding, max_verts=None, max_
 
 @torch.no_grad()
 def reconstruct_mesh(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normals="accumulate", netC=None,
-                     feat_tensor_C=None, calib_tensor=None):
+                     feat_tensor_C=None, calib_tensor=None, clean=None):
     """The finished mesh of an occupancy volume [1,1,D,H,W] (or [D,H,W]) as one device chain: marching cubes,
     per-vertex normals (``normals``: "accumulate", "reference" -- mesh_util.compute_normal's two modes -- or
     None to skip them) and, with ``netC``, per-vertex colours netC.query(vertices) * 0.5 + 0.5 as
     ``mesh_util.vertex_colors`` gives them.  Returns a ``Mesh``; None for ``sdf is None``.  One host sync
     per mesh (the two counts, read after everything is enqueued); if a capacity guess was short the chain
-    runs once more with exact capacities.  A multi-view ``netC`` is not served here."""
+    runs once more with exact capacities.  A multi-view ``netC`` is not served here.  ``clean``: None, or 6 / 26 =
+    ``keep_largest(sdf, level, clean)`` in front of marching cubes inside the same chain (into a scratch volume;
+    ``sdf`` is not modified; needs level > 0)."""
     if sdf is None:
         return None
     _check_normals(normals)
+    _check_clean(clean, level)
     binding = None
     if netC is not None:
         if netC.surface_classifier.num_views > 1:
@@ -159,10 +205,10 @@ def reconstruct_mesh(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normal
         device = sdf.device
         feat_tensor_C = [[f.to(device) for f in feats] for feats in feat_tensor_C]
         binding = netC.bind(feat_tensor_C, calib_tensor)
-    verts, faces, counts, nrm, col = _mesh_chain(sdf, level, b_min, b_max, normals, binding)
+    verts, faces, counts, nrm, col = _mesh_chain(sdf, level, b_min, b_max, normals, binding, clean=clean)
     nv, nf = (int(c) for c in counts.cpu())
     if nv > verts.shape[0] or nf > faces.shape[0]:
-        verts, faces, counts, nrm, col = _mesh_chain(sdf, level, b_min, b_max, normals, binding, nv, nf)
+        verts, faces, counts, nrm, col = _mesh_chain(sdf, level, b_min, b_max, normals, binding, nv, nf, clean=clean)
     return Mesh(verts[:nv], faces[:nf], None if nrm is None else nrm[:nv],
                 None if col is None else col[:nv].contiguous())
 
@@ -172,14 +218,19 @@ def _check_normals(normals):
         raise ValueError("normals must be None or one of %s, got %r" % (sorted(ops.NORMALS_MODES), normals))
 
 
-def _mesh_chain_batch(sdfs, level, b_min, b_max, normals, bindings, gates=None, out=None):
+def _mesh_chain_batch(sdfs, level, b_min, b_max, normals, bindings, gates=None, out=None, clean=None):
     """``_mesh_chain`` for volumes of one size, every stage one set of launches for all of them: a list of
     (verts, faces, counts, normals or None, netC predictions [3,max_v] or None) per volume, nothing synchronised
     (``_finish_mesh(..., raw_preds=True)`` turns the predictions of the vertices present into colours).
     ``bindings``: None or one QueryBinding per volume (one head).  ``out``: None or a dict of the caller's buffers
-    (verts, faces, counts, normals, points, point_counts, preds: [n, ...] tensors, preds a list)."""
+    (verts, faces, counts, normals, points, point_counts, preds: [n, ...] tensors, preds a list; with ``clean`` also
+    cleaned [n,R,R,R] and clean_stats [n,4]).  ``clean``: None or the connectivity of ``keep_largest`` in front of
+    marching cubes, under the same gates."""
     out = out or {}
     n = len(sdfs)
+    if clean is not None:
+        cc_out = (out["cleaned"], out["clean_stats"]) if "cleaned" in out else None
+        sdfs = [c[0] for c in ops.keep_largest_raw_batch(sdfs, level, clean, CLEAN_FILL, gates=gates, out=cc_out)]
     mc_out = (out["verts"], out["faces"], out["counts"]) if "verts" in out else None
     raws = ops.marching_cubes_raw_batch(sdfs, level, b_min, b_max, gates=gates, out=mc_out)
     verts, faces, counts = ([r[k] for r in raws] for k in range(3))
@@ -213,9 +264,9 @@ def _finish_mesh(chain, nv, nf, raw_preds=False):
 
 @torch.no_grad()
 def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normals="accumulate", netC=None,
-                          feat_tensors_C=None, calib_tensors=None):
-    """``[reconstruct_mesh(s, level, b_min, b_max, normals, netC, feat_tensors_C[i], calib_tensors[i]) for i, s in
-    enumerate(sdfs)]`` -- every field of every ``Mesh`` the same bits -- with the chain enqueued ONCE for all volumes
+                          feat_tensors_C=None, calib_tensors=None, clean=None):
+    """``[reconstruct_mesh(s, level, b_min, b_max, normals, netC, feat_tensors_C[i], calib_tensors[i], clean) for i, s
+    in enumerate(sdfs)]`` -- every field of every ``Mesh`` the same bits -- with the chain enqueued ONCE for all volumes
     (batched marching cubes, normals, points and one counted colour query per ops.MAX_FRAMES volumes) and ONE host
     sync for all the counts (monoport_amd extension; the hook of a coalescing stage).  ``None`` entries of ``sdfs``
     give ``None``; the other volumes must be of one size (ValueError).  ``feat_tensors_C`` / ``calib_tensors``: one
@@ -223,6 +274,7 @@ def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), 
     re-run alone with exact capacities, as ``reconstruct_mesh`` does.  A multi-view ``netC`` is not served here."""
     sdfs = list(sdfs)
     _check_normals(normals)
+    _check_clean(clean, level)
     if netC is not None:
         if netC.surface_classifier.num_views > 1:
             raise NotImplementedError("reconstruct_mesh_many: netC has num_views = %d; colour the vertices of a "
@@ -247,14 +299,14 @@ def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), 
         for i in idx:
             feats = [[f.to(sdfs[i].device) for f in fs] for fs in feat_tensors_C[i]]
             bindings.append(netC.bind(feats, calib_tensors[i]))
-    chains = _mesh_chain_batch(live, level, b_min, b_max, normals, bindings)
+    chains = _mesh_chain_batch(live, level, b_min, b_max, normals, bindings, clean=clean)
     sizes = torch.stack([c[2] for c in chains]).cpu().tolist()  # the one host sync
     for k, i in enumerate(idx):
         nv, nf = sizes[k]
         chain, short = chains[k], False
         if nv > chain[0].shape[0] or nf > chain[1].shape[0]:
             chain, short = _mesh_chain(live[k], level, b_min, b_max, normals,
-                                       None if bindings is None else bindings[k], nv, nf), True
+                                       None if bindings is None else bindings[k], nv, nf, clean=clean), True
         meshes[i] = _finish_mesh(chain, nv, nf, raw_preds=not short)
     return meshes
 

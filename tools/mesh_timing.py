@@ -15,6 +15,14 @@ as three slots submitted back to back, per-frame milliseconds -- next to the sam
 
     python tools/mesh_timing.py --batched [--passes 5] [--out profiles/mesh_batch_timing.json]
 
+``--clean`` measures what keeping the largest connected body costs (profiles/keep_largest_timing.json): on the same
+volume with three planted floaters, recon.keep_largest alone and per frame of one recon.keep_largest_many of 20 (both
+connectivities), ops.marching_cubes_raw alone (the stage cleaning precedes), recon.reconstruct_mesh and
+recon.reconstruct_mesh_many of 20 with netC colours without / with clean=6; and the 20-frame colour slot of ``--batched``
+with a mesh per frame without / with ``"clean": 6``.  ``--clean --no-slot`` leaves the slot out.
+
+    python tools/mesh_timing.py --clean [--passes 5] [--out profiles/keep_largest_timing.json]
+
 The protocol of tools/recon_views_timing.py: after a warm-up of all, the passes alternate; a pass is `meshes`
 meshes, wall clock around a final stream sync.  Prints (and writes) one JSON line: per way the median, minimum and
 maximum time per mesh (ms) over the passes.  The verdict fields restate what to check: (b) not slower than (a) by
@@ -33,6 +41,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from monoport_amd import mesh_util, ops, synthetic as syn  # noqa: E402
 from monoport_amd.modeling import PIFuNetC  # noqa: E402
+from monoport_amd import recon  # noqa: E402
 from monoport_amd.recon import marching_cubes, reconstruct_mesh, reconstruct_mesh_many  # noqa: E402
 from oracle import pifu_oracle as orc  # noqa: E402
 
@@ -47,9 +56,12 @@ def main():
     ap.add_argument("--meshes", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--batched", action="store_true", help="the batched chain and the slot's MESH_BATCH settings")
+    ap.add_argument("--clean", action="store_true", help="what keeping the largest connected body costs")
+    ap.add_argument("--no-slot", action="store_true", help="with --clean: leave the frame slot out")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "mesh_batch_timing.json" if a.batched else "mesh_timing.json")
+        a.out = os.path.join(ROOT, "profiles", "keep_largest_timing.json" if a.clean else
+                             "mesh_batch_timing.json" if a.batched else "mesh_timing.json")
     mlp = ops.PackedMLP.from_layers(DEV, syn.body_mlp("G", noise=0.05, seed=1), 1)
     fh = ops.pack_features(torch.from_numpy(syn.body_feat(256, 128, 128, 2))[None].to(DEV))
     cal = torch.from_numpy(orc.pifu_calib(*syn.scene_camera(30))).to(DEV)
@@ -66,6 +78,12 @@ def main():
     feat_C = [[torch.from_numpy(syn.rand_feat(512, 128, 128, 62))[None].to(DEV)]]
     calib = torch.eye(4, device=DEV)[None]
 
+    if a.clean:
+        out = clean(a, vol, netC, feat_C, calib)
+        if not a.no_slot:
+            out["slot"] = slot_clean(a)
+        write(a, out)
+        return
     if a.batched:
         out = batched(a, vol, netC, feat_C, calib)
         out["slot"] = slot_mesh_batch(a)
@@ -167,6 +185,84 @@ def batched(a, vol, netC, feat_C, calib):
         out["n%d" % n] = res
         out["vertices"], out["faces"] = int(one.verts.shape[0]), int(one.faces.shape[0])
     return out
+
+
+def clean(a, vol, netC, feat_C, calib, n=20):
+    """keep_largest alone and batched, marching cubes alone, and the mesh calls without / with clean=6."""
+    dirty = vol.clone()
+    for k, (z, y, x, h) in enumerate(((12, 12, 12, 4), (240, 30, 200, 3), (20, 236, 128, 2))):  # three floaters
+        dirty[0, 0, z:z + h, y:y + h, x:x + h] = 0.9
+    stats = {c: ops.keep_largest_raw(dirty, 0.5, c, 0.0)[1].cpu().tolist() for c in (6, 26)}
+    kw = dict(netC=netC, feat_tensor_C=feat_C, calib_tensor=calib)
+    kwn = dict(netC=netC, feat_tensors_C=[feat_C] * n, calib_tensors=[calib] * n)
+    ways = {
+        "keep_largest_6": lambda: [recon.keep_largest(dirty, 0.5, 6) for _ in range(n)],
+        "keep_largest_26": lambda: [recon.keep_largest(dirty, 0.5, 26) for _ in range(n)],
+        "keep_largest_many_6": lambda: recon.keep_largest_many([dirty] * n, 0.5, 6),
+        "keep_largest_many_26": lambda: recon.keep_largest_many([dirty] * n, 0.5, 26),
+        "marching_cubes_raw": lambda: [ops.marching_cubes_raw(dirty, 0.5, BMIN, BMAX) for _ in range(n)],
+        "marching_cubes_raw_batch": lambda: ops.marching_cubes_raw_batch([dirty] * n, 0.5, BMIN, BMAX),
+        "mesh": lambda: [reconstruct_mesh(dirty, 0.5, BMIN, BMAX, **kw) for _ in range(n)],
+        "mesh_clean": lambda: [reconstruct_mesh(dirty, 0.5, BMIN, BMAX, clean=6, **kw) for _ in range(n)],
+        "mesh_many": lambda: reconstruct_mesh_many([dirty] * n, 0.5, BMIN, BMAX, **kwn),
+        "mesh_many_clean": lambda: reconstruct_mesh_many([dirty] * n, 0.5, BMIN, BMAX, clean=6, **kwn),
+    }
+    one, cleaned = ways["mesh"]()[0], ways["mesh_clean"]()[0]
+    out = {"resolutions": RES, "passes": a.passes, "per_pass": n, "unit": "ms per volume / mesh",
+           "stats_6": stats[6], "stats_26": stats[26], "vertices": int(one.verts.shape[0]),
+           "vertices_clean": int(cleaned.verts.shape[0])}
+    out.update(alternate(ways, a.passes, n))
+    for name in ("mesh", "mesh_many"):
+        out[name + "_clean_adds_ms"] = round(out[name + "_clean"]["median_ms"] - out[name]["median_ms"], 4)
+    return out
+
+
+def slot_clean(a, frames=20):
+    """The 20-frame colour slot with a mesh per frame, without and with "clean": 6, per-frame ms of a submission
+    (``meshes()`` included)."""
+    pipes, fn = _slot_pipes(frames, 1, (("mesh", {"normals": "accumulate"}),
+                                        ("mesh_clean", {"normals": "accumulate", "clean": 6})))
+    out = {"frames_per_slot": frames, "unit": "ms per frame", "normals": "accumulate", "colors": True}
+    out.update(alternate({name: fn(name) for name in pipes}, a.passes, frames))
+    out["clean_adds_ms"] = round(out["mesh_clean"]["median_ms"] - out["mesh"]["median_ms"], 4)
+    out["clean_stats_frame0"] = pipes["mesh_clean"].slots[0].mesh_buffers["clean_stats"][0].cpu().tolist()
+    for p_ in pipes.values():
+        p_.close()
+    return out
+
+
+def _slot_pipes(frames, depth, meshes):
+    """FramePipelines of the bench's synthetic frames, one per (name, mesh option), and fn(name) -> a submission."""
+    from bench_common import B_MAX, B_MIN, RESOLUTIONS, build_netc, build_netg
+    from monoport_amd import pipeline
+    from monoport_amd.recon import pifu_calib
+    dev = torch.device(DEV)
+    netg, netc = build_netg(dev)[0], build_netc(dev)
+    planes = torch.from_numpy(syn.body_feature_planes(128, 128)).to(dev)
+    planes_hwc = planes.permute(1, 2, 0).contiguous()
+
+    def hook(feat):  # the bench's synthetic-data hook: channels 0 / 1 are the body's depth planes
+        feat[:, 0:2].copy_(planes[None].expand(feat.shape[0], -1, -1, -1))
+
+    def hook_hwc(feat_hwc):
+        feat_hwc[..., 0:2].copy_(planes_hwc[None].expand(feat_hwc.shape[0], -1, -1, -1))
+
+    hook.hwc = hook_hwc
+    images = torch.stack([torch.from_numpy(syn.synthetic_image(f % 8)) for f in range(frames)]).to(dev)
+    calibs = torch.cat([pifu_calib(*syn.scene_camera(3 * f), device=DEV) for f in range(frames)])
+    pipes = {}
+    for name, mesh in meshes:
+        pipes[name] = pipeline.FramePipeline(netg, dev, depth=depth, batch=frames, resolutions=RESOLUTIONS,
+                                             b_min=B_MIN, b_max=B_MAX, feature_hook=hook, use_graph=True,
+                                             netC=netc, mesh=mesh)
+        pipes[name].prepare()
+
+    def fn(name):
+        def run():
+            for s in [pipes[name].submit(images, calibs) for _ in range(depth)]:
+                assert all(m is not None for m in s.meshes())
+        return run
+    return pipes, fn
 
 
 def slot_mesh_batch(a, frames=20):
