@@ -748,6 +748,10 @@ int mp_upsample_bicubic2x_gn(mp_ctx *ctx, const float *x, int n, int c, int h, i
                              const mp_gn_out *fin, mp_stream stream);
 int mp_gn_apply(mp_ctx *ctx, const float *x, const mp_gn_in *gn, int relu, int n, int c, int64_t hw,
                 const float *res, float *y, const mp_gn_out *fin, mp_stream stream);
+/* 1 if mp_upsample_bicubic2x_gn runs the shape on the banded kernel that shares the horizontal sums through LDS
+ * (2W divides 256, 2H % 16 == 0, (C / 32 * 2H) % 256 == 0), 0 if on the one-output-per-thread kernel.  Host only: the
+ * rule the launcher itself dispatches by; both kernels write the same bits. */
+int mp_upsample_gn_banded(int c, int h, int w);
 
 /* ---- recorded launch sequences ------------------------------------------------------------------
  * The reference calls netG.filter once per frame from a stage thread (RTL/main.py:366-370): here that is ~137

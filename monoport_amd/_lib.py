@@ -209,6 +209,7 @@ SIGNATURES = {
     "mp_avgpool2_gn": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, ctypes.POINTER(GnOut), c_vp]),
     "mp_upsample_bicubic2x_gn": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp,
                                          ctypes.POINTER(GnOut), c_vp]),
+    "mp_upsample_gn_banded": (c_int, [c_int, c_int, c_int]),
     "mp_gn_apply": (c_int, [c_vp, c_vp, ctypes.POINTER(GnIn), c_int, c_int, c_int, c_i64, c_vp, c_vp,
                             ctypes.POINTER(GnOut), c_vp]),
     "mp_plan_create": (c_int, [c_vp, c_int, ctypes.POINTER(c_vp)]),

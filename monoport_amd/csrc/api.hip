@@ -1564,6 +1564,8 @@ int mp_upsample_bicubic2x_gn(mp_ctx *ctx, const float *x, int n, int c, int h, i
   return launch_upsample_add_gn(ctx, x, n, c, h, w, add, y, to_out(fin), out_cap(fin), (hipStream_t)stream);
 }
 
+int mp_upsample_gn_banded(int c, int h, int w) { return upsample_gn_banded(c, h, w) ? 1 : 0; }
+
 int mp_gn_apply(mp_ctx *ctx, const float *x, const mp_gn_in *gn, int relu, int n, int c, int64_t hw,
                 const float *res, float *y, const mp_gn_out *fin, mp_stream stream) {
   if (!ctx) return MP_ERR_ARG;

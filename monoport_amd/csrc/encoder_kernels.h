@@ -108,6 +108,7 @@ int launch_convk(mp_ctx *ctx, ConvKArgs a, long long partial_cap, hipStream_t st
 // encoder_ops.hip: elementwise producers that publish the GroupNorm statistics of their output
 int launch_avgpool2_gn(mp_ctx *ctx, const float *x, int n, int c, int h, int w, float *y, GnOut fin,
                        long long partial_cap, hipStream_t st);
+bool upsample_gn_banded(int c, int h, int w);  // launch_upsample_add_gn takes the banded LDS kernel for the shape
 int launch_upsample_add_gn(mp_ctx *ctx, const float *x, int n, int c, int h, int w, const float *add, float *y,
                            GnOut fin, long long partial_cap, hipStream_t st);
 int launch_gn_apply_gn(mp_ctx *ctx, const float *x, GnIn gn, int relu, int n, int c, long long hw,

@@ -480,15 +480,22 @@ __global__ __launch_bounds__(kGnThreads) void upsample_add_gn_kernel(const float
   gn_emit(fin, gi / 32, gi % 32, 1, s, a, b);
 }
 
+// The shapes upsample_add_gn_kernel serves: a row of 2W outputs divides the workgroup, bands do not cross planes, and
+// a slice is a whole number of bands.  Every other admitted shape runs ew_gn_kernel<UpsampleAddOp>.
+bool upsample_gn_banded(int c, int h, int w) {
+  if (c < 32 || c % 32 || h < 1 || w < 1 || w > kGnThreads / 2) return false;
+  const int cpg = c / 32, ho = 2 * h, wo = 2 * w;
+  return kGnThreads % wo == 0 && ho % kUpBand == 0 && ((long long)cpg * ho) % (kGnSlices * kUpBand) == 0;
+}
+
 int launch_upsample_add_gn(mp_ctx *ctx, const float *x, int n, int c, int h, int w, const float *add, float *y,
                            GnOut fin, long long partial_cap, hipStream_t st) {
   const long long hw_out = 4LL * h * w;
   int rc = check_fin(ctx, fin, n, c, partial_cap, "upsample_add_gn");
   if (rc != MP_OK) return rc;
-  const int cpg = c / 32, ho = 2 * h, wo = 2 * w;
+  const int cpg = c / 32;
   static const bool old_form = getenv("MONOPORT_UPSAMPLE") && getenv("MONOPORT_UPSAMPLE")[0] == 'o';  // A/B: "old"
-  if (!old_form && c % 32 == 0 && wo <= kGnThreads && kGnThreads % wo == 0 && ho % kUpBand == 0 &&
-      (cpg * ho) % (kGnSlices * kUpBand) == 0) {
+  if (!old_form && upsample_gn_banded(c, h, w)) {
     hipLaunchKernelGGL(upsample_add_gn_kernel, dim3(n * 32 * kGnSlices), dim3(kGnThreads), 0, st, x, add, y, h, w,
                        cpg, (float)(h - 1) / (float)(2 * h - 1), (float)(w - 1) / (float)(2 * w - 1), fin);
     MP_HIP(ctx, hipGetLastError());

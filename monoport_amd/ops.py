@@ -1735,6 +1735,12 @@ def upsample_add_gn(x, add, stats=None):
     return y
 
 
+def upsample_banded(c, h, w):
+    """True if ``upsample_add_gn`` runs an [N,c,h,w] input on the banded kernel, False if on the one-output-per-thread
+    kernel (mp_upsample_gn_banded: the launcher's own rule)."""
+    return bool(_lib.load().mp_upsample_gn_banded(int(c), int(h), int(w)))
+
+
 def gn_apply(x, gn, relu=True, res=None, stats=None):
     """[res +] relu?(GroupNorm(x)) materialised (gn = (acc, module) or a legacy ss tensor), adding the
     statistics of the result into ``stats``."""

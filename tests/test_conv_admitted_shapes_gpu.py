@@ -34,6 +34,8 @@ import types
 import pytest
 import torch
 
+from elementwise_ref import scale_shift
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 F = torch.nn.functional
@@ -73,22 +75,9 @@ def _acc_of(x):
     return acc
 
 
-def _moments(t, cpg):
-    """float64 two-pass mean / biased variance per (image, group of cpg channels) of t [N,C,H,W]."""
-    n, c = t.shape[:2]
-    v = t.double().reshape(n, c // cpg, -1)
-    mean = v.mean(2)
-    var = ((v - mean[..., None]) ** 2).mean(2)
-    return mean, var
-
-
 def _ss64(t, cpg, weight, bias, eps):
     """(scale, shift) [N,C,2] in float64 of a GroupNorm with cpg channels per group over t, from the definition."""
-    mean, var = _moments(t, cpg)
-    rstd = 1.0 / torch.sqrt(var + eps)
-    sc = rstd.repeat_interleave(cpg, 1) * weight.double()[None]
-    sh = bias.double()[None] - mean.repeat_interleave(cpg, 1) * sc
-    return torch.stack((sc, sh), 2)
+    return scale_shift(t, t.shape[1] // cpg, weight, bias, eps)
 
 
 def _gn_relu64(x, gn):
