@@ -361,6 +361,43 @@ int mp_octree_select(mp_ctx *ctx, const float *prev, int rp, float *cur, int r,
 int mp_octree_select_box(mp_ctx *ctx, const float *prev, int rp, float *cur, int r,
                          const uint64_t *ev_prev, uint64_t *ev_cur, uint64_t *bnd, int box,
                          float balance, uint32_t *packed, int32_t *count, mp_stream stream);
+/* FIXED-BUDGET refinement (the upstream package's Seg3dTopk; un-vendored and unpinned like Seg3dLossless, so the
+ * definition is stated here and restated in numpy in tests/topk_ref.py, which the kernels match bit for bit).
+ * Resolutions obey r[l+1] = 2 r[l] - 1.  num_points[l] is the budget of level l; entry 0 is ignored: level 0
+ * evaluates every node, exactly as mp_recon does.  max_dist[l] is an optional bound (+inf, or a NULL array, for none).
+ * status[0] is 0 or 1 as in mp_recon and status[1+l] the number of points queried at level l.
+ * Each level l >= 1, with r = r[l] and k = num_points[l]:
+ *   1. cur = upsample2x(prev): the same bits as mp_octree_select_box with box 0;
+ *   2. u(v) = fabsf(cur[v] - balance) in f32;
+ *   3. a node is a CANDIDATE if it is not in the evaluated set (the even-coordinate image of the previous level's
+ *      set), u is not NaN and u <= max_dist[l];
+ *   4. selected are the min(k, #candidates) candidates smallest under the key (u, z r^2 + y r + x) compared
+ *      lexicographically: ties in u go to the smaller linear index, whatever order the list is emitted in;
+ *   5. the selected nodes are evaluated, scattered into cur and added to the evaluated set; status[1+l] = their count;
+ *   6. k == 0: the level is only upsampled (count 0, no query launch).
+ * A frame whose level 0 has nothing > balance (status[0] == 0) selects nothing at any level: all its counts are 0 and
+ * its volume is unspecified, as in mp_recon.  The ORDER of `packed` is unspecified; the selected set and the volume
+ * are a pure function of the inputs (integer atomics only: the same bits in every run).  Upstream's names:
+ * uncertainty = -|occ - balance|, and clip_min keeps uncertainty >= clip_min, so max_dist = -clip_min.
+ *
+ * mp_octree_select_topk: one level (steps 1-4 and the evaluated set of step 5) for the level-at-a-time engine; the
+ * caller evaluates `packed` and calls mp_scatter_nodes.  prev must not be NULL (level 0 stays mp_octree_select);
+ * ev_prev / ev_cur / packed as in mp_octree_select, *count is written on the device.  MP_ERR_ARG: k < 0 or k > r^3,
+ * a NaN or negative max_dist, a NULL or misaligned buffer, r != 2 rp - 1. */
+int mp_octree_select_topk(mp_ctx *ctx, const float *prev, int rp, float *cur, int r, const uint64_t *ev_prev,
+                          uint64_t *ev_cur, int64_t k, float max_dist, float balance, uint32_t *packed, int32_t *count,
+                          mp_stream stream);
+/* The fused call: mp_recon_batch_proj with the selection above instead of the lossless rule, 1..mp_max_frames()
+ * frames; every level's nodes of all frames go through one query launch whose grid is sized by the budget
+ * (num_points[l] * n_frames), not by r^3.  num_points: HOST int64[n_levels]; max_dist: HOST float[n_levels] or NULL;
+ * every other argument as in mp_recon_batch_proj.  Fully asynchronous.  MP_ERR_ARG: num_points[l] < 0 or > r[l]^3
+ * (l >= 1), a NaN or negative max_dist[l], NULL or misaligned buffers, resolutions that break r[l+1] = 2 r[l] - 1,
+ * n_frames outside 1..mp_max_frames(). */
+int mp_recon_topk_batch(mp_ctx *ctx, int mlp, int n_frames, const float *const *feat_hwc, int c, int h, int w,
+                        const float *const *calib, const int *projection /*host, may be NULL*/, float z_scale,
+                        const float *b_min, const float *b_max, const int *resolutions, int n_levels,
+                        const int64_t *num_points /*host*/, const float *max_dist /*host, may be NULL*/, float balance,
+                        float *const *volume, int32_t *const *status, const mp_recon_early *early, mp_stream stream);
 /* Conflict re-examination of the upstream engine's faster=False mode.  For each of the first
  * *count nodes of `packed` (just evaluated: values[i]; volume [r^3] still holds the value
  * INTERPOLATED from the coarser level at that node): if (interp - balance) * (value - balance) < 0

@@ -151,6 +151,11 @@ SIGNATURES = {
                                  c_vp, c_vp]),
     "mp_octree_select_box": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_f32, c_vp,
                                      c_vp, c_vp]),
+    "mp_octree_select_topk": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_i64, c_f32, c_f32, c_vp, c_vp,
+                                      c_vp]),
+    "mp_recon_topk_batch": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, _pint, c_f32, _pf32, _pf32,
+                                    _pint, c_int, ctypes.POINTER(c_i64), _pf32, c_f32, c_vp, c_vp,
+                                    ctypes.POINTER(ReconEarly), c_vp]),
     "mp_octree_conflicts": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_f32, c_vp, c_vp, c_vp,
                                     c_vp]),
     "mp_lattice_points": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, _pf32, _pf32, c_vp, c_vp]),

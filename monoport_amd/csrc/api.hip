@@ -247,24 +247,41 @@ static ViewSetDev view_set(int nv, int projection, long long n, long long sn, lo
   return set;
 }
 
+// budget and bound of one top-k level of r^3 nodes
+static int check_topk(mp_ctx *ctx, const char *who, int r, long long k, float max_dist) {
+  if (k < 0 || k > (long long)r * r * r)
+    return fail(ctx, MP_ERR_ARG, "%s: a budget of %lld points for %d^3 nodes", who, k, r);
+  if (max_dist != max_dist || max_dist < 0.0f)
+    return fail(ctx, MP_ERR_ARG, "%s: max_dist must be >= 0 (or +inf for none), got %g", who, (double)max_dist);
+  return MP_OK;
+}
+
 // What mp_recon_batch_proj (views == nullptr: n_frames frames with a projection each, NULL = orthogonal) and
 // mp_recon_views (one frame seen by views->nv maps with projection[0]) do once head, counts and maps are accepted.
+// num_points != nullptr (mp_recon_topk_batch): the fixed-budget selection with these per-level budgets and bounds.
 static int recon_checked(mp_ctx *ctx, const char *who, const Mlp &m, int n_frames, const float *const *feat_hwc, int h,
                          int w, const float *const *calib, const int *projection, float z_scale, const float *b_min,
                          const float *b_max, const int *resolutions, int n_levels, int resolution_code, float balance,
                          int final_level, float *const *volume, int32_t *const *status, const mp_recon_early *early,
-                         const char *early_field, mp_stream stream, const ReconViews *views) {
+                         const char *early_field, mp_stream stream, const ReconViews *views,
+                         const long long *num_points = nullptr, const float *max_dist = nullptr) {
   int rc = check_final_level(ctx, who, final_level);
   if (rc == MP_OK) rc = check_resolutions(ctx, who, resolutions, n_levels, resolution_code);
   if (rc == MP_OK) rc = check_projection(ctx, who, projection, views ? 1 : n_frames);
   if (rc == MP_OK) rc = check_early(ctx, who, early, early_field);
+  for (int l = 1; rc == MP_OK && num_points && l < n_levels; ++l)  // the top-k selection: entry 0 is not looked at
+    rc = check_topk(ctx, who, resolutions[l], num_points[l], max_dist ? max_dist[l] : INFINITY);
   if (rc != MP_OK) return rc;
   DeviceGuard g(ctx->device);
   void *scratch = nullptr;
-  rc = ensure_scratch(ctx, (hipStream_t)stream, n_frames * recon_scratch_bytes(resolutions, n_levels), &scratch);
+  const size_t lossless_bytes = n_frames * recon_scratch_bytes(resolutions, n_levels);
+  const size_t topk_bytes = num_points ? topk_scratch_bytes(n_frames, resolutions[n_levels - 1]) : 0;
+  rc = ensure_scratch(ctx, (hipStream_t)stream, lossless_bytes + topk_bytes, &scratch);
   if (rc != MP_OK) return rc;
+  const ReconTopk topk = {num_points, max_dist, static_cast<unsigned char *>(scratch) + lossless_bytes};
   return launch_recon(ctx, scratch, m, n_frames, feat_hwc, h, w, calib, projection, z_scale, b_min, b_max, resolutions,
-                      n_levels, balance, final_level, volume, status, early, (hipStream_t)stream, views);
+                      n_levels, balance, final_level, volume, status, early, (hipStream_t)stream, views,
+                      num_points ? &topk : nullptr);
 }
 
 }  // namespace mp
@@ -846,6 +863,29 @@ int mp_recon_batch_proj(mp_ctx *ctx, int mlp, int n_frames, const float *const *
                        "flags_dev", stream, nullptr);
 }
 
+int mp_recon_topk_batch(mp_ctx *ctx, int mlp, int n_frames, const float *const *feat_hwc, int c, int h, int w,
+                        const float *const *calib, const int *projection, float z_scale, const float *b_min,
+                        const float *b_max, const int *resolutions, int n_levels, const int64_t *num_points,
+                        const float *max_dist, float balance, float *const *volume, int32_t *const *status,
+                        const mp_recon_early *early, mp_stream stream) {
+  const char *who = "mp_recon_topk_batch";
+  HeadCall call(ctx, mlp, c);
+  if (call.rc != MP_OK) return call.rc;
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (!feat_hwc || !calib || !b_min || !b_max || !resolutions || !num_points || !volume || !status || n_levels < 1 ||
+      n_levels > 8 || h <= 0 || w <= 0)
+    return bad_argument(ctx, who);
+  rc = check_maps(ctx, who, "frame", n_frames, feat_hwc, calib, volume, status);
+  if (rc != MP_OK) return rc;
+  if (call.m->cout != 1) return fail(ctx, MP_ERR_ARG, "%s: needs a 1-channel (occupancy) mlp", who);
+  long long k[8];
+  for (int l = 0; l < n_levels; ++l) k[l] = num_points[l];
+  return recon_checked(ctx, who, *call.m, n_frames, feat_hwc, h, w, calib, projection, z_scale, b_min, b_max,
+                       resolutions, n_levels, MP_ERR_ARG, balance, MP_FINAL_DILATE3, volume, status, early, "flags_dev",
+                       stream, nullptr, k, max_dist);
+}
+
 int mp_recon_views(mp_ctx *ctx, int mlp, int n_views, const float *const *feat_hwc, int c, int h, int w,
                    const float *const *calib, int projection, float z_scale,
                    const float *b_min, const float *b_max, const int *resolutions, int n_levels,
@@ -913,6 +953,32 @@ int mp_octree_select_box(mp_ctx *ctx, const float *prev, int rp, float *cur, int
                          float balance, uint32_t *packed, int32_t *count, mp_stream stream) {
   return octree_select_impl(ctx, prev, rp, cur, r, ev_prev, ev_cur, bnd, prev ? 1 : 0, box, balance,
                             packed, count, stream);
+}
+
+int mp_octree_select_topk(mp_ctx *ctx, const float *prev, int rp, float *cur, int r, const uint64_t *ev_prev,
+                          uint64_t *ev_cur, int64_t k, float max_dist, float balance, uint32_t *packed, int32_t *count,
+                          mp_stream stream) {
+  const char *who = "mp_octree_select_topk";
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!prev || !cur || !ev_prev || !ev_cur || !packed || !count) return bad_argument(ctx, who);
+  if (rp < 2 || r > 1023 || r != 2 * rp - 1) return fail(ctx, MP_ERR_ARG, "%s: needs r == 2 rp - 1 <= 1023", who);
+  if ((reinterpret_cast<uintptr_t>(prev) | reinterpret_cast<uintptr_t>(cur) | reinterpret_cast<uintptr_t>(packed) |
+       reinterpret_cast<uintptr_t>(count)) & 3u)
+    return fail(ctx, MP_ERR_ARG, "%s: prev, cur, packed and count must be 4-byte aligned", who);
+  if ((reinterpret_cast<uintptr_t>(ev_prev) | reinterpret_cast<uintptr_t>(ev_cur)) & 7u)
+    return fail(ctx, MP_ERR_ARG, "%s: ev_prev and ev_cur must be 8-byte aligned", who);
+  int rc = check_topk(ctx, who, r, k, max_dist);
+  if (rc != MP_OK) return rc;
+  DeviceGuard g(ctx->device);
+  const size_t bnd_bytes = ((size_t)r * r * ((r + 63) / 64) * sizeof(uint64_t) + 255) & ~size_t(255);
+  void *scratch = nullptr;
+  rc = ensure_scratch(ctx, (hipStream_t)stream, bnd_bytes + topk_scratch_bytes(1, r), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_octree_select_topk(ctx, scratch, static_cast<unsigned char *>(scratch) + bnd_bytes, prev, rp, cur, r,
+                                   reinterpret_cast<const unsigned long long *>(ev_prev),
+                                   reinterpret_cast<unsigned long long *>(ev_cur), k, max_dist, balance, packed, count,
+                                   (hipStream_t)stream);
 }
 
 int mp_octree_conflicts(mp_ctx *ctx, const uint32_t *packed, const int32_t *count, int64_t capacity,

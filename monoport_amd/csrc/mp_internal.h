@@ -168,6 +168,13 @@ struct ViewLatticeDev : ViewSetDev {
 struct ReconViews {
   int nv, view;
 };
+// launch_recon's second way to SELECT a level's nodes (mp_recon_topk_batch, topk.hip): the num_points[l] most uncertain
+// nodes within max_dist[l] (NULL: no bound) instead of the dilated boundary; scratch: topk_scratch_bytes(n_frames, r_last)
+struct ReconTopk {
+  const long long *num_points;
+  const float *max_dist;
+  void *scratch;
+};
 
 struct Mlp {
   bool used = false;
@@ -322,11 +329,17 @@ int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
                  const int *proj, float z_scale, const float *bmin, const float *bmax, const int *res,
                  int n_levels, float balance, int final_level, float *const *volume,
                  int32_t *const *status, const mp_recon_early *early, hipStream_t st,
-                 const ReconViews *views = nullptr);
+                 const ReconViews *views = nullptr, const ReconTopk *topk = nullptr);
 int launch_octree_select(mp_ctx *ctx, const float *prev, int rp, float *cur, int r,
                          const unsigned long long *ev_prev, unsigned long long *ev_cur,
                          unsigned long long *bnd, int box, float balance, uint32_t *packed,
                          int32_t *count, hipStream_t st);
+// one level of the fixed-budget engine: upsample prev into cur, then topk.hip's selection; bnd: r * r * ceil(r / 64)
+// words the upsample kernel writes its (unused) flags to; topk_scratch: topk_scratch_bytes(1, r)
+size_t topk_scratch_bytes(int n_frames, int r);
+int launch_octree_select_topk(mp_ctx *ctx, void *bnd, void *topk_scratch, const float *prev, int rp, float *cur, int r,
+                              const unsigned long long *ev_prev, unsigned long long *ev_cur, long long k,
+                              float max_dist, float balance, uint32_t *packed, int32_t *count, hipStream_t st);
 int octree_box_of_level(int level);
 int launch_octree_conflicts(mp_ctx *ctx, const uint32_t *packed, const int32_t *count, long long cap,
                             int r, const float *values, const float *vol, float balance,

@@ -15,10 +15,12 @@
 //      exact occupancies straight into the level volume.  For a multi-view head (mp_recon_views) step 3 is
 //      the lattice variant of the multi-view kernel (query_views.hip); steps 1-2 are the same kernels.
 // No host synchronisation anywhere: counts stay on the device (`status`).
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 
 #include "mp_internal.h"
+#include "octree_common.h"
 
 // Reference parity is op-order parity: keep every a*b+c exactly as written (the HIP headers
 // define __fmul_rn & co. as plain operators, which hipcc would otherwise contract into FMAs).
@@ -35,9 +37,6 @@ struct LevelBufs {
   u64 *ev;      // evaluated bits [r][r][w64]
 };
 
-static inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-static inline int words64(int r) { return (r + 63) / 64; }
-
 int octree_box_of_level(int level) { return level == 1 ? 9 : level == 2 ? 7 : 3; }
 
 size_t recon_scratch_bytes(const int *res, int n_levels) {
@@ -52,20 +51,7 @@ size_t recon_scratch_bytes(const int *res, int n_levels) {
   return total + 4096;
 }
 
-// The housekeeping kernels of a level serve ALL frames of a batch in one launch (blockIdx.z = frame; round 5: per
-// frame they were 40-odd launches of 3-25 us between two query launches, each too small to fill the chip): the
-// per-frame pointers travel by value.
-struct FrameBufs {
-  const float *prev[kMaxFrames];   // previous level's volume
-  float *cur[kMaxFrames];          // this level's volume
-  u64 *bnd[kMaxFrames];            // boundary flags of this level
-  const u64 *ev_prev[kMaxFrames];  // evaluated bits of the previous level
-  u64 *ev[kMaxFrames];             // evaluated bits of this level
-  uint32_t *packed[kMaxFrames];    // point list
-  int32_t *count[kMaxFrames];      // its length (device side)
-  int32_t *flag[kMaxFrames];       // level 0: "anything above the threshold" (status[0])
-};
-static_assert(sizeof(FrameBufs) <= 2048 + 64, "kernel argument");
+// FrameBufs: the per-frame pointers of a housekeeping launch (octree_common.h)
 constexpr int kHouseChunk = kMaxFrames;  // frames per housekeeping launch (see launch_recon)
 
 // ---- level 0 ---------------------------------------------------------------------------------
@@ -126,16 +112,6 @@ __global__ void early_flags_kernel(EarlyBufs eb, int n, int32_t *__restrict__ fl
 // order z, then y, then x with weights 0.5/0.5 -- the exact sequence of oracle upsample2x (axis 0
 // first), so values agree bit for bit.  A wave covers 64 parents = 128 fine x positions = two
 // boundary words per fine row.  grid = (ceil(rp * ceil(rp/64) / 4), rp): blockIdx.y is z0.
-__device__ __forceinline__ u64 spread32(u64 x) {  // bit i -> bit 2i
-  x &= 0xffffffffull;
-  x = (x | (x << 16)) & 0x0000ffff0000ffffull;
-  x = (x | (x << 8)) & 0x00ff00ff00ff00ffull;
-  x = (x | (x << 4)) & 0x0f0f0f0f0f0f0f0full;
-  x = (x | (x << 2)) & 0x3333333333333333ull;
-  x = (x | (x << 1)) & 0x5555555555555555ull;
-  return x;
-}
-
 // `rule` (MP_FINAL_*): which nodes get a flag -- 0: 0 < upsampled mask < 1 (every level of the lossless schedule);
 // 1: upsampled mask == 0.5 exactly, i.e. half of the corners with non-zero weight are inside (the last level of
 // the "upstream" schedule); 2: none (the last level of the "interpolate" schedule).
@@ -451,6 +427,25 @@ int launch_octree_select(mp_ctx *ctx, const float *prev, int rp, float *cur, int
   return MP_OK;
 }
 
+int launch_octree_select_topk(mp_ctx *ctx, void *bnd, void *topk_scratch, const float *prev, int rp, float *cur, int r,
+                              const u64 *ev_prev, u64 *ev_cur, long long k, float max_dist, float balance,
+                              uint32_t *packed, int32_t *count, hipStream_t st) {
+  const int w64 = words64(r);
+  FrameBufs fb;
+  std::memset(&fb, 0, sizeof(fb));  // flag[0] == NULL: no gate
+  fb.prev[0] = prev;
+  fb.cur[0] = cur;
+  fb.bnd[0] = static_cast<u64 *>(bnd);
+  fb.ev_prev[0] = ev_prev;
+  fb.ev[0] = ev_cur;
+  fb.packed[0] = packed;
+  fb.count[0] = count;
+  MP_HIP(ctx, hipMemsetAsync(count, 0, sizeof(int32_t), st));
+  hipLaunchKernelGGL(upsample_classify_kernel, dim3((unsigned)((rp * ((rp + 63) / 64) + 3) / 4), (unsigned)rp),
+                     dim3(256), 0, st, fb, rp, r, balance, w64, MP_FINAL_INTERPOLATE);
+  return launch_topk_select(ctx, topk_scratch, fb, 1, rp, r, k, max_dist, balance, st);
+}
+
 int launch_lattice_points(mp_ctx *ctx, const uint32_t *packed, const int32_t *count, long long cap,
                           int stride, int res_final, const float *bmin, const float *bmax,
                           float *pts, hipStream_t st) {
@@ -482,7 +477,7 @@ int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
                  const int *proj, float z_scale, const float *bmin, const float *bmax, const int *res,
                  int n_levels, float balance, int final_level, float *const *volume,
                  int32_t *const *status, const mp_recon_early *early, hipStream_t st,
-                 const ReconViews *views) {
+                 const ReconViews *views, const ReconTopk *topk) {
   // carve the scratch arena: one private set of level buffers per frame
   const size_t per_frame = recon_scratch_bytes(res, n_levels);
   LevelBufs lv[kMaxFrames][8];
@@ -628,6 +623,23 @@ int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
       q.src.level_res = r;
       q.src.n_dev = status[f] + 1 + l;
       q.src.n = 0;
+    }
+    if (topk) {  // fixed budget: upsample only, then the k most uncertain nodes (topk.hip); the lossless rules below
+      const long long k = topk->num_points[l];
+      const float max_dist = topk->max_dist ? topk->max_dist[l] : INFINITY;
+      for (int f0 = 0; f0 < n_frames; f0 += chunk) {
+        const int nf = min(chunk, n_frames - f0);
+        const FrameBufs c = sub(f0, nf);
+        hipLaunchKernelGGL(upsample_classify_kernel,
+                           dim3((unsigned)((rp * ((rp + 63) / 64) + 3) / 4), (unsigned)rp, (unsigned)nf), dim3(256), 0, st,
+                           c, rp, r, balance, w64, MP_FINAL_INTERPOLATE);
+        int rc = launch_topk_select(ctx, topk->scratch, c, nf, rp, r, k, max_dist, balance, st);
+        if (rc != MP_OK) return rc;
+      }
+      if (k == 0) continue;  // only upsampled: status[1 + l] stays 0, no query
+      int rc = eval_level(k * n_frames, true);  // the grid is sized by the budget, not by r^3
+      if (rc != MP_OK) return rc;
+      continue;
     }
     for (int f0 = 0; f0 < n_frames; f0 += chunk) {
       const int nf = min(chunk, n_frames - f0);

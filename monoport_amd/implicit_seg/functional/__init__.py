@@ -1,8 +1,10 @@
-"""``implicit_seg.functional``: the coarse-to-fine ("lossless octree") reconstruction engine.
+"""``implicit_seg.functional``: the coarse-to-fine ("lossless octree") reconstruction engines.
 
 ``Seg3dLossless`` keeps the constructor and call surface the reference uses
 (RTL/main.py:185-195, :392-394) but runs every level on the GPU: upsample + boundary ballot,
 dilation + compaction, fused PIFu query with scatter (csrc/octree.hip, csrc/query.hip).
+
+``Seg3dTopk`` is the fixed-budget engine with the same contract (its docstring; csrc/topk.hip).
 
 PARITY NOTE: the upstream package is not vendored and not version-pinned by the reference, so the
 algorithm here is our restatement of its published scheme; it is checked bit for
@@ -51,14 +53,22 @@ from ...modeling.MonoPortNet import record_query
 from . import utils  # noqa: F401
 
 
-class Seg3dLossless(nn.Module):
-    def __init__(self, query_func, b_min, b_max, resolutions, channels=1, balance_value=0.5,
-                 align_corners=False, visualize=False, debug=False, use_cuda_impl=False,
-                 faster=False, use_shadow=False, final_level="dilate3", validate="always", fuse_views=False,
-                 view=0, **kwargs):
-        super().__init__()
+class _Seg3dEngine(nn.Module):
+    """What Seg3dLossless and Seg3dTopk share: the constructor checks of the upstream surface, and the contract
+    around ``query_func`` -- the coarsest level always goes through it, the fused call serves the rest only if that
+    was one plain MonoPortNet.query whose values the fused kernel reproduces, validated calls build trust
+    (``validate="first"``), everything else runs level by level through ``query_func``.  A subclass says how a level
+    is selected: ``_level_engine`` / ``_generic`` (level-at-a-time) and ``_recon`` / ``_recon_many`` (fused)."""
+
+    faster = True       # the fused path is allowed
+    fuse_views = False  # bind a multi-view query_func to the fused engine
+    view = 0
+
+    def _init_common(self, query_func, b_min, b_max, resolutions, channels, balance_value, align_corners, visualize,
+                     debug, use_cuda_impl, use_shadow, validate, kwargs):
+        name = type(self).__name__
         if kwargs:  # the upstream constructor swallows **kwargs: stay drop-in, but say so
-            warnings.warn("Seg3dLossless: ignoring unknown arguments %s" % sorted(kwargs))
+            warnings.warn("%s: ignoring unknown arguments %s" % (name, sorted(kwargs)))
         self.query_func = query_func
         self.b_min = np.asarray(b_min, np.float32).reshape(-1, 3)
         self.b_max = np.asarray(b_max, np.float32).reshape(-1, 3)
@@ -87,23 +97,12 @@ class Seg3dLossless(nn.Module):
         self.resolutions = res
         self.channels = channels
         self.balance_value = float(balance_value)
-        self.faster = bool(faster)
-        ops._final_level(final_level)  # ValueError for an unknown name
-        if final_level != "dilate3" and not self.faster:
-            raise NotImplementedError("final_level=%r is a variant of the faster=True schedule" % final_level)
-        self.final_level = final_level
-        if fuse_views and not self.faster:
-            raise NotImplementedError("fuse_views=True is a variant of the faster=True schedule")
-        if int(view) != view or view < 0:
-            raise ValueError("view must be a row 0..V-1 of the multi-view result, got %r" % (view,))
-        self.fuse_views = bool(fuse_views)
-        self.view = int(view)
         self.use_cuda_impl = bool(use_cuda_impl)  # same kernels either way (see module docstring)
         self.debug = bool(debug)
         self._status = None    # CPU tensor, or the device tensor of a call whose refinement may still be running
         self._early = threading.local()  # per host thread: the EarlyFlags buffers of its fused calls
         self.last_path = None  # "fused" | "generic": which engine served the last call
-        # "always" (the default of this drop-in class): every call evaluates the coarsest level through
+        # "always" (the default of the drop-in classes): every call evaluates the coarsest level through
         # query_func for real and compares it with the fused kernel -- a closure whose arithmetic changes
         # between frames (a flag, `1 - pred` from some frame on) is honoured on the frame it changes; costs
         # one 17^3 query and one host sync per frame (~0.3 ms).
@@ -121,6 +120,23 @@ class Seg3dLossless(nn.Module):
         # nn.Module.to(device) is called on the engine (RTL/main.py:195): carry a buffer so it
         # has a device like the upstream module does
         self.register_buffer("_device_tag", torch.zeros(1), persistent=False)
+
+    # ---- what a subclass defines: how a level's nodes are selected ----
+    def _level_engine(self, dev):
+        """The level-at-a-time engine (ops.LevelEngine) of one call."""
+        raise NotImplementedError
+
+    def _generic(self, kwargs, dev, level0=None):
+        """ops.recon_generic of one call -> (volume or None, per-level counts)."""
+        raise NotImplementedError
+
+    def _recon(self, b, early=None, expect_level0=None):
+        """The fused reconstruction of a recorded binding -> (volume, status) on the device."""
+        raise NotImplementedError
+
+    def _recon_many(self, bindings, early):
+        """The fused reconstruction of several single-view bindings in one call -> (volumes, status [n,1+levels])."""
+        raise NotImplementedError
 
     @property
     def last_status(self):
@@ -168,8 +184,7 @@ class Seg3dLossless(nn.Module):
                 self._since_check += 1
                 return out
         self._since_check = 0
-        eng = ops.LevelEngine(dev, self.b_min[0], self.b_max[0], self.resolutions,
-                              self.balance_value, self.faster, self.final_level)
+        eng = self._level_engine(dev)
         pts0 = eng.select()
         with record_query(views=self.fuse_views) as rec:
             occ0 = self.query_func(points=pts0[None], **kwargs)
@@ -190,27 +205,17 @@ class Seg3dLossless(nn.Module):
                 self._trusted_key = key
                 return None if nonempty == 0 else volume[None, None]
             self._agreed, self._trusted_key = 0, None
-            warnings.warn("Seg3dLossless: query_func is not a plain MonoPortNet.query call (its "
-                          "values differ from the fused kernel's); using the level-at-a-time engine")
-            volume, counts = ops.recon_generic(self.query_func, kwargs, dev, self.b_min[0],
-                                               self.b_max[0], self.resolutions, self.balance_value,
-                                               self.faster, final_level=self.final_level)
+            warnings.warn("%s: query_func is not a plain MonoPortNet.query call (its values differ from the fused "
+                          "kernel's); using the level-at-a-time engine" % type(self).__name__)
+            volume, counts = self._generic(kwargs, dev)
         else:
-            volume, counts = ops.recon_generic(self.query_func, kwargs, dev, self.b_min[0],
-                                               self.b_max[0], self.resolutions, self.balance_value,
-                                               self.faster, level0=(eng, occ0), final_level=self.final_level)
+            volume, counts = self._generic(kwargs, dev, level0=(eng, occ0))
         self.last_path = "generic"
         self.last_status = torch.tensor([int(volume is not None)] + counts, dtype=torch.int32)
         return None if volume is None else volume[None, None]
 
     VALIDATE_CALLS = 3
     REVALIDATE_EVERY = 32  # a trusted query_func is validated again on every 32nd call
-
-    def _recon(self, b, early=None, expect_level0=None):
-        """The fused reconstruction of a recorded binding: one frame (ops.recon) or, with ``fuse_views``, the V
-        views of one subject (ops.recon_views, row ``self.view``) -> (volume, status) on the device."""
-        return b.recon(self.b_min[0], self.b_max[0], self.resolutions, self.balance_value, self.final_level,
-                       view=self.view, early=early, expect_level0=expect_level0)
 
     def _forward_trusted(self, kwargs):
         """A query_func whose last VALIDATE_CALLS calls were plain MonoPortNet.query calls agreeing
@@ -241,8 +246,9 @@ class Seg3dLossless(nn.Module):
         n = len(kwargs_list)
         if n >= 2 and self.validate == "always" and not getattr(self, "_warned_many", False):
             self._warned_many = True
-            warnings.warn("Seg3dLossless.forward_many on an engine with validate='always' (the class default) serves "
-                          "the frames one by one; construct it with validate='first' to let a coalescing stage batch them")
+            warnings.warn("%s.forward_many on an engine with validate='always' (the class default) serves the frames "
+                          "one by one; construct it with validate='first' to let a coalescing stage batch them"
+                          % type(self).__name__)
         if (n < 2 or n > ops.MAX_FRAMES or not self.faster or self.validate == "always" or self._agreed < self.VALIDATE_CALLS
                 or self._since_check + n >= self.REVALIDATE_EVERY):
             return [self(**kw) for kw in kwargs_list]
@@ -257,12 +263,8 @@ class Seg3dLossless(nn.Module):
                     or b.trust_key(self.view) != self._trusted_key):
                 return [self(**kw) for kw in kwargs_list]  # forward() re-validates
             bindings.append(b)
-        b0 = bindings[0]
         early = self._early_flags(self._device_tag.device, n)
-        volumes, status = ops.recon_batch(b0.mlp, [b.feat_hwc for b in bindings], [b.calib for b in bindings],
-                                          b0.z_scale, self.b_min[0], self.b_max[0], self.resolutions,
-                                          self.balance_value, final_level=self.final_level, early=early,
-                                          projections=[b.projection for b in bindings])
+        volumes, status = self._recon_many(bindings, early)
         flags = early.wait().clone()  # the one host sync of the whole batch: its coarsest level (see forward)
         self._since_check += n
         self.last_status, self.last_path = status[-1], "fused"
@@ -284,9 +286,118 @@ class Seg3dLossless(nn.Module):
         return self._recon(b)
 
 
-class Seg3dTopk(nn.Module):
-    """Imported but never constructed by the reference (RTL/main.py:28)."""
-
-    def __init__(self, *args, **kwargs):
+class Seg3dLossless(_Seg3dEngine):
+    def __init__(self, query_func, b_min, b_max, resolutions, channels=1, balance_value=0.5,
+                 align_corners=False, visualize=False, debug=False, use_cuda_impl=False,
+                 faster=False, use_shadow=False, final_level="dilate3", validate="always", fuse_views=False,
+                 view=0, **kwargs):
         super().__init__()
-        raise NotImplementedError("Seg3dTopk is unused by the reference pipeline")
+        self._init_common(query_func, b_min, b_max, resolutions, channels, balance_value, align_corners, visualize,
+                          debug, use_cuda_impl, use_shadow, validate, kwargs)
+        self.faster = bool(faster)
+        ops._final_level(final_level)  # ValueError for an unknown name
+        if final_level != "dilate3" and not self.faster:
+            raise NotImplementedError("final_level=%r is a variant of the faster=True schedule" % final_level)
+        self.final_level = final_level
+        if fuse_views and not self.faster:
+            raise NotImplementedError("fuse_views=True is a variant of the faster=True schedule")
+        if int(view) != view or view < 0:
+            raise ValueError("view must be a row 0..V-1 of the multi-view result, got %r" % (view,))
+        self.fuse_views = bool(fuse_views)
+        self.view = int(view)
+
+    def _level_engine(self, dev):
+        return ops.LevelEngine(dev, self.b_min[0], self.b_max[0], self.resolutions,
+                               self.balance_value, self.faster, self.final_level)
+
+    def _generic(self, kwargs, dev, level0=None):
+        return ops.recon_generic(self.query_func, kwargs, dev, self.b_min[0], self.b_max[0], self.resolutions,
+                                 self.balance_value, self.faster, level0=level0, final_level=self.final_level)
+
+    def _recon(self, b, early=None, expect_level0=None):
+        """The fused reconstruction of a recorded binding: one frame (ops.recon) or, with ``fuse_views``, the V
+        views of one subject (ops.recon_views, row ``self.view``) -> (volume, status) on the device."""
+        return b.recon(self.b_min[0], self.b_max[0], self.resolutions, self.balance_value, self.final_level,
+                       view=self.view, early=early, expect_level0=expect_level0)
+
+    def _recon_many(self, bindings, early):
+        b0 = bindings[0]
+        return ops.recon_batch(b0.mlp, [b.feat_hwc for b in bindings], [b.calib for b in bindings],
+                               b0.z_scale, self.b_min[0], self.b_max[0], self.resolutions,
+                               self.balance_value, final_level=self.final_level, early=early,
+                               projections=[b.projection for b in bindings])
+
+
+class Seg3dTopk(_Seg3dEngine):
+    """The upstream package's fixed-budget engine (imported at RTL/main.py:28): level l >= 1 evaluates the
+    ``num_points[l]`` most UNCERTAIN nodes -- those whose upsampled value is closest to ``balance_value`` -- instead of
+    as many as the surface needs, so the cost of a frame is bounded and known in advance (entry 0 is ignored: the
+    coarsest level is always evaluated whole).  The signature is recalled from upstream, which the reference neither
+    vendors nor pins; the definition is ours (include/monoport_hip.h, restated in tests/topk_ref.py): ties go to the
+    smaller linear index, the result is the same bits in every run.
+
+    ``clip_mins``: upstream keeps the nodes with uncertainty = -|occ - balance| >= clip_mins[l]; here that is the bound
+    |occ - balance| <= -clip_mins[l] on the candidates of level l (None, or None entries: no bound).
+    ``use_cuda_impl`` and ``faster`` are accepted and select nothing: there is one implementation, the HIP kernels of
+    csrc/topk.hip.  ``align_corners=True``, ``visualize=True``, ``use_shadow=True``, ``channels != 1`` and
+    ``fuse_views`` are not built: NotImplementedError at construction.
+
+    The contract around ``query_func`` is Seg3dLossless's: the coarsest level always goes through it; one plain
+    MonoPortNet.query whose values the fused kernel reproduces is served by ONE asynchronous call
+    (ops.recon_topk), anything else level by level through ``query_func`` (ops.recon_generic with ``num_points``);
+    ``None`` for an empty coarsest level; ``last_status`` / ``last_path``, ``forward_many``, ``forward_async`` and
+    ``validate="first"`` as there."""
+
+    def __init__(self, query_func=None, b_min=None, b_max=None, resolutions=None, num_points=None, clip_mins=None,
+                 channels=1, balance_value=0.5, align_corners=False, visualize=False, debug=False,
+                 use_cuda_impl=False, faster=False, use_shadow=False, validate="always", **kwargs):
+        super().__init__()
+        # the five leading arguments are upstream's required ones; the name stayed constructible without them while it
+        # was a stub that raised this error, and there is no engine to build from nothing
+        missing = [n for n, v in (("query_func", query_func), ("b_min", b_min), ("b_max", b_max),
+                                  ("resolutions", resolutions), ("num_points", num_points)) if v is None]
+        if missing:
+            raise NotImplementedError("Seg3dTopk needs %s" % ", ".join(missing))
+        if kwargs.pop("fuse_views", False):
+            raise NotImplementedError("fuse_views: the fixed-budget engine serves single-view heads only")
+        self._init_common(query_func, b_min, b_max, resolutions, channels, balance_value, align_corners, visualize,
+                          debug, use_cuda_impl, use_shadow, validate, kwargs)
+        res = self.resolutions
+        num_points = [int(k) for k in num_points]
+        if len(num_points) != len(res):
+            raise ValueError("Seg3dTopk: %d resolutions, %d budgets in num_points" % (len(res), len(num_points)))
+        if any(k < 0 for k in num_points):
+            raise ValueError("Seg3dTopk: num_points must not be negative, got %s" % (num_points,))
+        for l, (k, r) in enumerate(zip(num_points, res)):
+            if k > r ** 3:
+                warnings.warn("Seg3dTopk: num_points[%d] = %d clamped to the level's %d^3 nodes" % (l, k, r))
+                num_points[l] = r ** 3
+        self.num_points = num_points
+        self.max_dist = None
+        if clip_mins is not None:
+            if len(clip_mins) != len(res):
+                raise ValueError("Seg3dTopk: %d resolutions, %d bounds in clip_mins" % (len(res), len(clip_mins)))
+            self.max_dist = [float("inf") if c is None else -float(c) for c in clip_mins]
+            if any(not d >= 0 for d in self.max_dist):
+                raise ValueError("Seg3dTopk: clip_mins are bounds on -|occ - balance|: none may be positive or NaN")
+        self.clip_mins = clip_mins
+
+    def _level_engine(self, dev):
+        return ops.LevelEngine(dev, self.b_min[0], self.b_max[0], self.resolutions, self.balance_value,
+                               num_points=self.num_points, max_dist=self.max_dist)
+
+    def _generic(self, kwargs, dev, level0=None):
+        return ops.recon_generic(self.query_func, kwargs, dev, self.b_min[0], self.b_max[0], self.resolutions,
+                                 self.balance_value, level0=level0, num_points=self.num_points,
+                                 max_dist=self.max_dist)
+
+    def _recon(self, b, early=None, expect_level0=None):
+        return ops.recon_topk(b.mlp, b.feat_hwc, b.calib, b.z_scale, self.b_min[0], self.b_max[0], self.resolutions,
+                              self.num_points, self.max_dist, self.balance_value, early=early,
+                              expect_level0=expect_level0, projection=b.projection)
+
+    def _recon_many(self, bindings, early):
+        b0 = bindings[0]
+        return ops.recon_topk_batch(b0.mlp, [b.feat_hwc for b in bindings], [b.calib for b in bindings], b0.z_scale,
+                                    self.b_min[0], self.b_max[0], self.resolutions, self.num_points, self.max_dist,
+                                    self.balance_value, early=early, projections=[b.projection for b in bindings])

@@ -621,7 +621,15 @@ def recon_batch(mlp, feats_hwc, calibs, z_scale, b_min, b_max, resolutions, bala
     on refining; ``expect_level0``: list of [r0,r0,r0] f32 tensors (or None entries).  ``projections``: per-frame
     MP_PROJ_* ints or names (None: all orthogonal).  One mp_recon_batch_proj call, which with no projections is
     mp_recon_batch_early."""
-    who = "recon_batch"
+    return _recon_frames("recon_batch", mlp, feats_hwc, calibs, z_scale, b_min, b_max, resolutions, balance, volumes,
+                         status, early, expect_level0, projections, final_level=_final_level(final_level))
+
+
+def _recon_frames(who, mlp, feats_hwc, calibs, z_scale, b_min, b_max, resolutions, balance, volumes, status, early,
+                  expect_level0, projections, final_level=None, topk=None):
+    """What ``recon_batch`` (``final_level``: the MP_FINAL_* rule, one mp_recon_batch_proj call) and
+    ``recon_topk_batch`` (``topk`` = (num_points, max_dist), one mp_recon_topk_batch call) share: the frames'
+    arguments checked and marshalled, buffers made where the caller gave none."""
     ctx = mlp.ctx
     n = len(feats_hwc)
     h, w, c, dev = _maps(who, feats_hwc)
@@ -639,12 +647,58 @@ def recon_batch(mlp, feats_hwc, calibs, z_scale, b_min, b_max, resolutions, bala
     elif tuple(status.shape) != (n, 1 + len(res)) or not status.is_contiguous() or status.dtype != torch.int32:
         raise ValueError("%s: status must be contiguous int32 [%d,%d]" % (who, n, 1 + len(res)))
     early_arg = _early_arg(who, early, n, expect_level0, res[0])
-    ctx.check(ctx.lib.mp_recon_batch_proj(
-        ctx.handle, mlp.id, n, _ptr_array(feats_hwc), c, h, w, _ptr_array(cals), proj, float(z_scale), _float3(b_min),
-        _float3(b_max), (ctypes.c_int * len(res))(*res), len(res), float(balance), _final_level(final_level),
-        _ptr_array(volumes), _ptr_array(status), early_arg, _stream(volumes[0])), "mp_recon_batch_proj")
+    res_arg = (ctypes.c_int * len(res))(*res)
+    if topk is None:
+        ctx.check(ctx.lib.mp_recon_batch_proj(
+            ctx.handle, mlp.id, n, _ptr_array(feats_hwc), c, h, w, _ptr_array(cals), proj, float(z_scale),
+            _float3(b_min), _float3(b_max), res_arg, len(res), float(balance), final_level,
+            _ptr_array(volumes), _ptr_array(status), early_arg, _stream(volumes[0])), "mp_recon_batch_proj")
+    else:
+        num_points, max_dist = _topk_levels(who, res, *topk)
+        ctx.check(ctx.lib.mp_recon_topk_batch(
+            ctx.handle, mlp.id, n, _ptr_array(feats_hwc), c, h, w, _ptr_array(cals), proj, float(z_scale),
+            _float3(b_min), _float3(b_max), res_arg, len(res), (ctypes.c_int64 * len(res))(*num_points),
+            None if max_dist is None else (ctypes.c_float * len(res))(*max_dist), float(balance),
+            _ptr_array(volumes), _ptr_array(status), early_arg, _stream(volumes[0])), "mp_recon_topk_batch")
     _keep_until_done(dev, cals, expect_level0)
     return volumes, status
+
+
+def _topk_levels(who, res, num_points, max_dist):
+    """Per-level budgets and bounds of the fixed-budget engine -> (ints, floats or None); None bounds mean +inf."""
+    num_points = [int(k) for k in num_points]
+    if len(num_points) != len(res):
+        raise ValueError("%s: %d levels, %d budgets in num_points" % (who, len(res), len(num_points)))
+    if max_dist is not None:
+        max_dist = [float("inf") if d is None else float(d) for d in max_dist]
+        if len(max_dist) != len(res):
+            raise ValueError("%s: %d levels, %d bounds in max_dist" % (who, len(res), len(max_dist)))
+    return num_points, max_dist
+
+
+def recon_topk(mlp, feat_hwc, calib, z_scale, b_min, b_max, resolutions, num_points, max_dist=None, balance=0.5,
+               volume=None, status=None, early=None, expect_level0=None, projection=_lib.PROJ_ORTHOGONAL):
+    """``recon`` with a FIXED BUDGET per level (Seg3dTopk replacement): level l >= 1 evaluates the ``num_points[l]``
+    nodes whose upsampled value is closest to ``balance`` (ties to the smaller linear index; entry 0 is ignored,
+    level 0 evaluates every node), optionally only those within ``max_dist[l]`` of it -- the definition in
+    include/monoport_hip.h, chosen on the device (csrc/topk.hip).  Returns (volume [R,R,R] f32, status
+    int32[1+levels]) on the device, nothing synchronised; the other arguments as in ``recon``."""
+    st = None if status is None else status.reshape(1, -1)
+    volumes, st = recon_topk_batch(mlp, [feat_hwc], [calib], z_scale, b_min, b_max, resolutions, num_points, max_dist,
+                                   balance, None if volume is None else [volume], st, early,
+                                   None if expect_level0 is None else [expect_level0],
+                                   None if _projection(projection) == _lib.PROJ_ORTHOGONAL else [projection])
+    return volumes[0], st[0]
+
+
+def recon_topk_batch(mlp, feats_hwc, calibs, z_scale, b_min, b_max, resolutions, num_points, max_dist=None,
+                     balance=0.5, volumes=None, status=None, early=None, expect_level0=None, projections=None):
+    """``recon_topk`` over up to MAX_FRAMES frames in one mp_recon_topk_batch call (one budget list for all frames):
+    every level's nodes of all frames go through one fused-query launch sized by the budget.  Results equal the
+    single-frame calls bit for bit; a frame with an empty coarsest level has status [0, r0^3, 0, ...].  Arguments as
+    in ``recon_batch``."""
+    return _recon_frames("recon_topk_batch", mlp, feats_hwc, calibs, z_scale, b_min, b_max, resolutions, balance,
+                         volumes, status, early, expect_level0, projections, topk=(num_points, max_dist))
 
 
 def recon_views(mlp, maps, calibs, projection, z_scale, b_min, b_max, resolutions, balance=0.5,
@@ -683,9 +737,18 @@ class LevelEngine:
     3x3x3 neighbourhoods of nodes whose exact value contradicts the interpolated one are evaluated
     too, until no contradiction is left."""
 
-    def __init__(self, device, b_min, b_max, resolutions, balance=0.5, faster=True, final_level="dilate3"):
+    def __init__(self, device, b_min, b_max, resolutions, balance=0.5, faster=True, final_level="dilate3",
+                 num_points=None, max_dist=None):
         self.final_level = final_level
         _final_level(final_level)
+        # the fixed-budget engine (mp_octree_select_topk): levels >= 1 select the num_points[l] most uncertain nodes
+        self.num_points = self.max_dist = None
+        if num_points is not None:
+            if not faster or final_level != "dilate3":
+                raise ValueError("LevelEngine: num_points replaces the selection rules of faster / final_level")
+            self.num_points, self.max_dist = _topk_levels("LevelEngine", list(resolutions), num_points, max_dist)
+        elif max_dist is not None:
+            raise ValueError("LevelEngine: max_dist bounds the num_points selection")
         self.ctx = get_context(device)
         self.dev = torch.device(device)
         self.res = [int(r) for r in resolutions]
@@ -718,8 +781,21 @@ class LevelEngine:
             self.prev, self.ev_prev = self.cur, self.ev_cur
         self.cur = torch.empty((r, r, r), dtype=torch.float32, device=dev)
         self.ev_cur = torch.empty((words,), dtype=torch.int64, device=dev)
-        bnd = torch.empty((words,), dtype=torch.int64, device=dev)
         self.packed = torch.empty((r ** 3,), dtype=torch.int32, device=dev)
+        if self.num_points is not None and level > 0:
+            ctx.check(ctx.lib.mp_octree_select_topk(
+                ctx.handle, _ptr(self.prev), self.res[level - 1], _ptr(self.cur), r, _ptr(self.ev_prev),
+                _ptr(self.ev_cur), self.num_points[level], float("inf") if self.max_dist is None else self.max_dist[level],
+                self.balance, _ptr(self.packed), _ptr(self.count), _stream(self.cur)), "mp_octree_select_topk")
+            self.n = int(self.count.item())
+            self.counts.append(self.n)
+            self.rounds.append(0)
+            if not self.n:
+                return None
+            # the list is filled through atomics: sort it for a reproducible evaluation order (as the conflict rounds)
+            self.packed = torch.sort(self.packed[:self.n])[0].contiguous()
+            return self._points(self.packed, self.n, r)
+        bnd = torch.empty((words,), dtype=torch.int64, device=dev)
         box = 3 if not self.faster else {1: 9, 2: 7}.get(level, 3)
         if self.faster and level == len(self.res) - 1 and level > 0:
             # the last level's rule (mp_octree_select_box: 1 = upsampled mask == 0.5, undilated; 0 = none)
@@ -778,12 +854,13 @@ class LevelEngine:
 
 
 def recon_generic(query_func, kwargs, device, b_min, b_max, resolutions, balance=0.5, faster=True,
-                  level0=None, final_level="dilate3"):
+                  level0=None, final_level="dilate3", num_points=None, max_dist=None):
     """Seg3dLossless for an ARBITRARY ``query_func(points=[1,N,3], **kwargs) -> [1,1,N]`` on top
     of ``LevelEngine``.  ``level0`` = (engine, occupancies) when the caller has already evaluated
-    the coarsest level through the engine.  Returns (volume [R,R,R] or None, per-level counts)."""
+    the coarsest level through the engine.  ``num_points`` / ``max_dist``: the fixed-budget selection (Seg3dTopk,
+    ``LevelEngine``) instead of the lossless rules.  Returns (volume [R,R,R] or None, per-level counts)."""
     if level0 is None:
-        eng = LevelEngine(device, b_min, b_max, resolutions, balance, faster, final_level)
+        eng = LevelEngine(device, b_min, b_max, resolutions, balance, faster, final_level, num_points, max_dist)
         pts = eng.select()
         occ = query_func(points=pts[None], **kwargs)
     else:
