@@ -257,13 +257,13 @@ def upsample2x(a):
 
 
 def dilate_box(mask, k):
-    """(all-ones k^3 conv3d, zero padding k//2) > 0 on a bool volume."""
+    """(all-ones k^3 conv3d, zero padding k//2) > 0 on a bool volume of any shape with sides >= 1."""
     r = k // 2
     m = mask
     for axis in range(3):
         acc = m.copy()
         n = m.shape[axis]
-        for s in range(1, r + 1):
+        for s in range(1, min(r, n - 1) + 1):  # a shift of n or more moves everything out of the volume
             a = [slice(None)] * 3
             b = [slice(None)] * 3
             a[axis] = slice(s, n)

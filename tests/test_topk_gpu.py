@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import topk_ref
+from octree_ref import codes as _codes, pack_bits as _pack_bits
 from monoport_amd import synthetic as syn
 from oracle import pifu_oracle as po  # numpy parts only here (upsample2x); the built oracle is the `oracle` fixture
 
@@ -41,20 +42,6 @@ def _p(t):
 
 def _pp(tensors):
     return (ctypes.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
-
-
-def _pack_bits(mask):
-    """bool [r,r,r] -> the u64 bitset [r*r*ceil(r/64)] of the C-ABI (bit x & 63 of word x >> 6 of row (z, y))."""
-    r = mask.shape[0]
-    w64 = (r + 63) // 64
-    padded = np.zeros((r, r, w64 * 64), bool)
-    padded[:, :, :r] = mask
-    return np.packbits(padded, axis=-1, bitorder="little").view("<u8").reshape(-1).copy()
-
-
-def _codes(lin, r):
-    z, y, x = np.unravel_index(lin, (r, r, r))
-    return np.sort((x | (y << 10) | (z << 20)).astype(np.int64))
 
 
 def _select(abi, prev, ev_prev, k, max_dist=INF, balance=0.5):
