@@ -414,10 +414,22 @@ int mp_lattice_points(mp_ctx *ctx, const uint32_t *packed, const int32_t *count,
 int mp_scatter_nodes(mp_ctx *ctx, const uint32_t *packed, const int32_t *count, int64_t capacity,
                      int r, const float *values, float *volume, mp_stream stream);
 
+/* ---- per-frame and batched forms of the mesh and render calls -------------------------------------------------------
+ * mp_forward_vertices, mp_paint, mp_marching_cubes, mp_mesh_normals, mp_mesh_points and mp_volume_keep_largest are
+ * each the batched call with one frame: mp_<call>(..., p, ...) is mp_<call>_batch(..., 1, &p, ..., gate = NULL), with
+ * the same argument tests, scratch and launches; only the name at the head of an mp_last_error message is that of the
+ * entry called.  The rules of the batched calls are therefore the rules of both forms:
+ *   - a device pointer that is read and is not 4-byte aligned is refused with MP_ERR_ARG ("misaligned buffer for
+ *     frame f"), a NULL one with MP_ERR_ARG ("null buffer for frame f"); nothing is launched.  (The per-frame calls
+ *     used to pass a misaligned pointer on, and neither form of mp_forward_vertices / mp_paint tested alignment.)
+ *   - mp_mesh_normals with max_verts == 0 returns MP_OK without a launch (it used to launch).
+ *   - mp_volume_keep_largest's refusals name mp_volume_keep_largest (they used to name the _batch entry).
+ *   - rows of a capacity of 0 (verts / faces / normals / points) are not looked at and may be NULL. */
+
 /* ---- visible-surface extraction ------------------------------------------------------------ */
 /* forward_vertices (RTL/recon.py:27-89).  volume [R,R,R]; outputs sized for R*R rows:
  * X, Y int64 [R*R]; Z f32 [R*R]; norm f32 [R*R,3]; count (device int32[1]) = rows written,
- * in the reference's row order (x-major, RTL/recon.py:62). */
+ * in the reference's row order (x-major, RTL/recon.py:62).  The batched call with one frame. */
 int mp_forward_vertices(mp_ctx *ctx, const float *volume, int r, int direction, int64_t *x,
                         int64_t *y, float *z, float *norm, int32_t *count, mp_stream stream);
 
@@ -437,7 +449,8 @@ int mp_vertex_points(mp_ctx *ctx, const int64_t *x, const int64_t *y, const floa
                      float *points, mp_stream stream);
 /* image [res,res,3] = 1.0 then image[X[i],Y[i],:] = clamp(values[:,i]*scale + bias, lo, hi);
  * values is [3,capacity] when channel_major != 0 (netC preds, main.py:244-248: scale=bias=0.5)
- * or [capacity,3] otherwise (normals, main.py:220-225: scale=bias=0.5, clamp 0..1). */
+ * or [capacity,3] otherwise (normals, main.py:220-225: scale=bias=0.5, clamp 0..1).  The batched call with one
+ * frame. */
 int mp_paint(mp_ctx *ctx, const int64_t *x, const int64_t *y, const float *values,
              int channel_major, const int32_t *count, int64_t capacity, int res, float scale,
              float bias, float lo, float hi, float *image, mp_stream stream);
@@ -469,7 +482,8 @@ int mp_prepare_inputs(mp_ctx *ctx, const float *segm, int64_t hw, const float *m
  * order ((z*R+y)*R+x)*3 + axis, positioned at the linear crossing and mapped to world space like
  * the octree lattice; triangles in cell order, wound counter-clockwise seen from the outside.
  * verts f32 [max_verts,3], faces int32 [max_faces,3]; counts (device int32[2]) = vertices and
- * faces NEEDED (compare with the capacities to detect truncation). */
+ * faces NEEDED (compare with the capacities to detect truncation).  The batched call with one frame
+ * and no gate. */
 int mp_marching_cubes(mp_ctx *ctx, const float *volume, int r, float level,
                       const float *b_min /*host[3]*/, const float *b_max /*host[3]*/, float *verts,
                       int64_t max_verts, int32_t *faces, int64_t max_faces, int32_t *counts,
@@ -488,12 +502,13 @@ enum { MP_NORMALS_REFERENCE = 0, MP_NORMALS_ACCUMULATE = 1 };
 /* verts f32 [max_verts,3], faces int32 [max_faces,3]; counts (device int32[2]) = vertices and faces present, as
  * mp_marching_cubes writes them: only min(counts[0], max_verts) vertices and min(counts[1], max_faces) faces are
  * read / written (rows of `normals` beyond them are left untouched).  normals f32 [max_verts,3].  A face with an
- * index outside [0, vertices) is skipped (never read out of bounds).  Asynchronous; no float atomics. */
+ * index outside [0, vertices) is skipped (never read out of bounds).  Asynchronous; no float atomics.  The batched
+ * call with one frame: a pointer that is not 4-byte aligned is MP_ERR_ARG, max_verts == 0 is MP_OK without a launch. */
 int mp_mesh_normals(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
                     const int32_t *counts, int mode, float *normals, mp_stream stream);
 /* verts [max_verts,3] -> points [3,max_verts] (the layout mp_query_counted reads, capacity = max_verts) for the
  * first min(counts[0], max_verts) vertices, and count_out (device int32[1]) = that number: the per-vertex colour
- * query of a marching-cubes mesh without a host round trip. */
+ * query of a marching-cubes mesh without a host round trip.  The batched call with one frame. */
 int mp_mesh_points(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *counts, float *points,
                    int32_t *count_out, mp_stream stream);
 
@@ -538,7 +553,8 @@ int mp_mesh_points_batch(mp_ctx *ctx, int n_frames, const float *const *verts, i
  * (-1 without foreground).
  *   A union-find labelling with integer atomics only: the result is a pure function of the input, the same bits in
  * every run.  Six launches; scratch from the stream's arena: 4 * ceil4(r^3) + 1024 bytes (68 MB at 257^3).
- * r^3 >= 2^31: MP_ERR_UNSUPPORTED.  Asynchronous. */
+ * r^3 >= 2^31: MP_ERR_UNSUPPORTED.  Asynchronous.  The batched call with one frame and no gate; its refusals carry
+ * its own name. */
 enum { MP_CONN_6 = 6, MP_CONN_26 = 26 };
 int mp_volume_keep_largest(mp_ctx *ctx, const float *volume, int r, float level, int connectivity, float fill,
                            float *out, int32_t *stats, mp_stream stream);

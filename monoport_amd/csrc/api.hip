@@ -160,6 +160,28 @@ static int check_maps(mp_ctx *ctx, const char *who, const char *what, int n, con
   return MP_OK;
 }
 
+// The n frames of a mesh / render stage's host arrays: every buffer set and 4-byte aligned (the kernels read them as
+// float / int32 / int64).  A `rows` array passed as nullptr is one this call does not read (rows of a capacity of 0);
+// `gate` may be nullptr, and so may each of its entries.
+template <class... P>
+static int check_frames(mp_ctx *ctx, const char *who, int n, const int32_t *const *gate, P... rows) {
+  for (int f = 0; f < n; ++f) {
+    if ((... || (rows && !rows[f]))) return fail(ctx, MP_ERR_ARG, "%s: null buffer for frame %d", who, f);
+    if (((gate ? (uintptr_t)gate[f] : uintptr_t(0)) | ... | (rows ? (uintptr_t)rows[f] : uintptr_t(0))) & 3)
+      return fail(ctx, MP_ERR_ARG, "%s: misaligned buffer for frame %d", who, f);
+  }
+  return MP_OK;
+}
+
+// What a launcher gets of such an array: rows of a capacity of 0 (`rows` == nullptr) are no pointer at all
+template <class T>
+struct FrameRows {
+  T *p[kMaxFrames];
+  FrameRows(T *const *rows, int n) {
+    for (int f = 0; f < n; ++f) p[f] = rows ? rows[f] : nullptr;
+  }
+};
+
 static int check_f32_views(mp_ctx *ctx, const char *who, const Mlp *m) {
   if (m->precision != MP_PREC_F32)
     return fail(ctx, MP_ERR_UNSUPPORTED, "%s: the multi-view kernel is f32 only (head precision %d)", who,
@@ -282,6 +304,138 @@ static int recon_checked(mp_ctx *ctx, const char *who, const Mlp &m, int n_frame
   return launch_recon(ctx, scratch, m, n_frames, feat_hwc, h, w, calib, projection, z_scale, b_min, b_max, resolutions,
                       n_levels, balance, final_level, volume, status, early, (hipStream_t)stream, views,
                       num_points ? &topk : nullptr);
+}
+
+// ---- the mesh and render stages: one checked body each ---------------------------------------------------------------
+// mp_<stage>_batch passes its arguments on; mp_<stage> is the batched call with one frame: it passes 1 and the addresses
+// of its own arguments, so both forms refuse the same and launch the same.  `who` is the entry the caller used.
+
+static int forward_vertices_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *volume, int r,
+                                    int direction, int64_t *const *x, int64_t *const *y, float *const *z,
+                                    float *const *norm, int32_t *const *count, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (!volume || !x || !y || !z || !norm || !count || r < 1 || r > 4096 || direction < MP_DIR_FRONT ||
+      direction > MP_DIR_RIGHT)
+    return bad_argument(ctx, who);
+  rc = check_frames(ctx, who, n_frames, nullptr, volume, x, y, z, norm, count);
+  if (rc != MP_OK) return rc;
+  DeviceGuard g(ctx->device);
+  void *scratch = nullptr;
+  rc = ensure_scratch(ctx, (hipStream_t)stream, (size_t)n_frames * forward_vertices_scratch_bytes(r) + 4096, &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_forward_vertices_batch(ctx, scratch, n_frames, volume, r, direction, x, y, z, norm, count,
+                                       (hipStream_t)stream);
+}
+
+static int paint_checked(mp_ctx *ctx, const char *who, int n_frames, const int64_t *const *x, const int64_t *const *y,
+                         const float *const *values, int channel_major, const int32_t *const *count, int64_t capacity,
+                         int res, float scale, float bias, float lo, float hi, float *const *image, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (!x || !y || !values || !count || !image || capacity < 0 || res < 1) return bad_argument(ctx, who);
+  rc = check_frames(ctx, who, n_frames, nullptr, x, y, values, count, image);
+  if (rc != MP_OK) return rc;
+  DeviceGuard g(ctx->device);
+  return launch_paint_batch(ctx, n_frames, x, y, values, channel_major, count, capacity, res, scale, bias, lo, hi,
+                            image, (hipStream_t)stream);
+}
+
+static int marching_cubes_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *volume, int r,
+                                  float level, const float *b_min, const float *b_max, float *const *verts,
+                                  int64_t max_verts, int32_t *const *faces, int64_t max_faces, int32_t *const *counts,
+                                  const int32_t *const *gate, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (!volume || !b_min || !b_max || !counts || r < 2 || r > 1023 || max_verts < 0 || max_faces < 0 ||
+      (max_verts > 0 && !verts) || (max_faces > 0 && !faces))
+    return bad_argument(ctx, who);
+  if (max_verts == 0) verts = nullptr;
+  if (max_faces == 0) faces = nullptr;
+  rc = check_frames(ctx, who, n_frames, gate, volume, counts, verts, faces);
+  if (rc != MP_OK) return rc;
+  const FrameRows verts_p(verts, n_frames);
+  const FrameRows faces_p(faces, n_frames);
+  DeviceGuard g(ctx->device);
+  void *scratch = nullptr;
+  rc = ensure_scratch(ctx, (hipStream_t)stream, (size_t)n_frames * mc_scratch_bytes(r), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_marching_cubes_batch(ctx, scratch, n_frames, volume, r, level, b_min, b_max, verts_p.p, max_verts,
+                                     faces_p.p, max_faces, counts, gate, (hipStream_t)stream);
+}
+
+static int mesh_normals_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *verts,
+                                int64_t max_verts, const int32_t *const *faces, int64_t max_faces,
+                                const int32_t *const *counts, int mode, float *const *normals, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (!counts || max_verts < 0 || max_faces < 0 || (max_verts > 0 && (!verts || !normals)) ||
+      (max_faces > 0 && !faces) || (mode != MP_NORMALS_REFERENCE && mode != MP_NORMALS_ACCUMULATE))
+    return bad_argument(ctx, who);
+  if (max_verts > 0x7fffffffLL / 3 || max_faces > 0x7fffffffLL / 3)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: capacities beyond 2^31 / 3 need 64-bit indices", who);
+  if (max_verts == 0) verts = nullptr, normals = nullptr;
+  if (max_faces == 0) faces = nullptr;
+  rc = check_frames(ctx, who, n_frames, nullptr, counts, verts, normals, faces);
+  if (rc != MP_OK) return rc;
+  if (max_verts == 0) return MP_OK;
+  const FrameRows faces_p(faces, n_frames);
+  DeviceGuard g(ctx->device);
+  void *scratch = nullptr;
+  rc = ensure_scratch(ctx, (hipStream_t)stream, mesh_normals_scratch_bytes(n_frames, max_verts, max_faces), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_mesh_normals_batch(ctx, scratch, n_frames, verts, max_verts, faces_p.p, max_faces, counts, mode,
+                                   normals, (hipStream_t)stream);
+}
+
+static int mesh_points_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *verts,
+                               int64_t max_verts, const int32_t *const *counts, float *const *points,
+                               int32_t *const *count_out, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (!counts || !count_out || max_verts < 0 || (max_verts > 0 && (!verts || !points))) return bad_argument(ctx, who);
+  if (max_verts == 0) verts = nullptr, points = nullptr;
+  rc = check_frames(ctx, who, n_frames, nullptr, counts, count_out, verts, points);
+  if (rc != MP_OK) return rc;
+  const FrameRows verts_p(verts, n_frames);
+  const FrameRows points_p(points, n_frames);
+  DeviceGuard g(ctx->device);
+  return launch_mesh_points_batch(ctx, n_frames, verts_p.p, max_verts, counts, points_p.p, count_out,
+                                  (hipStream_t)stream);
+}
+
+static int keep_largest_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *volume, int r,
+                                float level, int connectivity, float fill, float *const *out, int32_t *const *stats,
+                                const int32_t *const *gate, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (!volume || !out || !stats || r < 1) return bad_argument(ctx, who);
+  if (connectivity != MP_CONN_6 && connectivity != MP_CONN_26)
+    return fail(ctx, MP_ERR_ARG, "%s: connectivity must be 6 or 26, got %d", who, connectivity);
+  if (!(fill <= level))  // a NaN fill fails this test too
+    return fail(ctx, MP_ERR_ARG, "%s: fill %g would be foreground at level %g", who, (double)fill, (double)level);
+  rc = check_frames(ctx, who, n_frames, gate, volume, out, stats);
+  if (rc != MP_OK) return rc;
+  if (r > 1290)  // 1291^3 > 2^31
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: resolution %d needs 64-bit voxel indices", who, r);
+  DeviceGuard g(ctx->device);
+  void *scratch = nullptr;
+  rc = ensure_scratch(ctx, (hipStream_t)stream, (size_t)n_frames * cc_scratch_bytes(r), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_keep_largest_batch(ctx, scratch, n_frames, volume, r, level, connectivity, fill, out, stats, gate,
+                                   (hipStream_t)stream);
 }
 
 }  // namespace mp
@@ -1020,38 +1174,15 @@ int mp_scatter_nodes(mp_ctx *ctx, const uint32_t *packed, const int32_t *count, 
 
 int mp_forward_vertices(mp_ctx *ctx, const float *volume, int r, int direction, int64_t *x,
                         int64_t *y, float *z, float *norm, int32_t *count, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (!volume || !x || !y || !z || !norm || !count || r < 1 || r > 4096 ||
-      direction < MP_DIR_FRONT || direction > MP_DIR_RIGHT)
-    return fail(ctx, MP_ERR_ARG, "mp_forward_vertices: bad argument");
-  DeviceGuard g(ctx->device);
-  void *scratch = nullptr;
-  int rc = ensure_scratch(ctx, (hipStream_t)stream, forward_vertices_scratch_bytes(r) + 4096, &scratch);
-  if (rc != MP_OK) return rc;
-  return launch_forward_vertices(ctx, scratch, volume, r, direction, x, y, z, norm, count,
-                                 (hipStream_t)stream);
+  return forward_vertices_checked(ctx, "mp_forward_vertices", 1, &volume, r, direction, &x, &y, &z, &norm, &count,
+                                  stream);
 }
 
 int mp_forward_vertices_batch(mp_ctx *ctx, int n_frames, const float *const *volume, int r, int direction,
                               int64_t *const *x, int64_t *const *y, float *const *z, float *const *norm,
                               int32_t *const *count, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (n_frames < 1 || n_frames > kMaxFrames)
-    return fail(ctx, MP_ERR_ARG, "mp_forward_vertices_batch: 1..%d frames per call, got %d", kMaxFrames, n_frames);
-  if (!volume || !x || !y || !z || !norm || !count || r < 1 || r > 4096 || direction < MP_DIR_FRONT ||
-      direction > MP_DIR_RIGHT)
-    return fail(ctx, MP_ERR_ARG, "mp_forward_vertices_batch: bad argument");
-  for (int f = 0; f < n_frames; ++f)
-    if (!volume[f] || !x[f] || !y[f] || !z[f] || !norm[f] || !count[f])
-      return fail(ctx, MP_ERR_ARG, "mp_forward_vertices_batch: null buffer for frame %d", f);
-  DeviceGuard g(ctx->device);
-  void *scratch = nullptr;
-  int rc = ensure_scratch(ctx, (hipStream_t)stream, (size_t)n_frames * forward_vertices_scratch_bytes(r) + 4096, &scratch);
-  if (rc != MP_OK) return rc;
-  return launch_forward_vertices_batch(ctx, scratch, n_frames, volume, r, direction, x, y, z, norm, count,
-                                       (hipStream_t)stream);
+  return forward_vertices_checked(ctx, "mp_forward_vertices_batch", n_frames, volume, r, direction, x, y, z, norm,
+                                  count, stream);
 }
 
 int mp_vertex_points(mp_ctx *ctx, const int64_t *x, const int64_t *y, const float *z,
@@ -1068,30 +1199,15 @@ int mp_vertex_points(mp_ctx *ctx, const int64_t *x, const int64_t *y, const floa
 int mp_paint(mp_ctx *ctx, const int64_t *x, const int64_t *y, const float *values,
              int channel_major, const int32_t *count, int64_t capacity, int res, float scale,
              float bias, float lo, float hi, float *image, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (!x || !y || !values || !count || !image || capacity < 0 || res < 1)
-    return fail(ctx, MP_ERR_ARG, "mp_paint: bad argument");
-  DeviceGuard g(ctx->device);
-  return launch_paint(ctx, x, y, values, channel_major, count, capacity, res, scale, bias, lo, hi,
-                      image, (hipStream_t)stream);
+  return paint_checked(ctx, "mp_paint", 1, &x, &y, &values, channel_major, &count, capacity, res, scale, bias, lo, hi,
+                       &image, stream);
 }
 
 int mp_paint_batch(mp_ctx *ctx, int n_frames, const int64_t *const *x, const int64_t *const *y,
                    const float *const *values, int channel_major, const int32_t *const *count, int64_t capacity,
                    int res, float scale, float bias, float lo, float hi, float *const *image, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (n_frames < 1 || n_frames > kMaxFrames)
-    return fail(ctx, MP_ERR_ARG, "mp_paint_batch: 1..%d frames per call, got %d", kMaxFrames, n_frames);
-  if (!x || !y || !values || !count || !image || capacity < 0 || res < 1)
-    return fail(ctx, MP_ERR_ARG, "mp_paint_batch: bad argument");
-  for (int f = 0; f < n_frames; ++f)
-    if (!x[f] || !y[f] || !values[f] || !count[f] || !image[f])
-      return fail(ctx, MP_ERR_ARG, "mp_paint_batch: null buffer for frame %d", f);
-  DeviceGuard g(ctx->device);
-  return launch_paint_batch(ctx, n_frames, x, y, values, channel_major, count, capacity, res, scale, bias, lo, hi,
-                            image, (hipStream_t)stream);
+  return paint_checked(ctx, "mp_paint_batch", n_frames, x, y, values, channel_major, count, capacity, res, scale,
+                       bias, lo, hi, image, stream);
 }
 
 int mp_visualize(mp_ctx *ctx, const float *image, int res, int size, float *out, uint8_t *mask,
@@ -1118,165 +1234,54 @@ int mp_prepare_inputs(mp_ctx *ctx, const float *segm, int64_t hw, const float *m
 int mp_marching_cubes(mp_ctx *ctx, const float *volume, int r, float level, const float *b_min,
                       const float *b_max, float *verts, int64_t max_verts, int32_t *faces,
                       int64_t max_faces, int32_t *counts, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (!volume || !b_min || !b_max || !counts || r < 2 || r > 1023 || max_verts < 0 ||
-      max_faces < 0 || (max_verts > 0 && !verts) || (max_faces > 0 && !faces))
-    return fail(ctx, MP_ERR_ARG, "mp_marching_cubes: bad argument");
-  DeviceGuard g(ctx->device);
-  void *scratch = nullptr;
-  int rc = ensure_scratch(ctx, (hipStream_t)stream, mc_scratch_bytes(r), &scratch);
-  if (rc != MP_OK) return rc;
-  return launch_marching_cubes(ctx, scratch, volume, r, level, b_min, b_max, verts, max_verts,
-                               faces, max_faces, counts, (hipStream_t)stream);
-}
-
-int mp_mesh_normals(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
-                    const int32_t *counts, int mode, float *normals, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (!counts || max_verts < 0 || max_faces < 0 || (max_verts > 0 && (!verts || !normals)) ||
-      (max_faces > 0 && !faces) || (mode != MP_NORMALS_REFERENCE && mode != MP_NORMALS_ACCUMULATE))
-    return fail(ctx, MP_ERR_ARG, "mp_mesh_normals: bad argument");
-  if (max_verts > 0x7fffffffLL / 3 || max_faces > 0x7fffffffLL / 3)
-    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_mesh_normals: capacities beyond 2^31 / 3 need 64-bit indices");
-  DeviceGuard g(ctx->device);
-  void *scratch = nullptr;
-  int rc = ensure_scratch(ctx, (hipStream_t)stream, mesh_normals_scratch_bytes(1, max_verts, max_faces), &scratch);
-  if (rc != MP_OK) return rc;
-  return launch_mesh_normals(ctx, scratch, verts, max_verts, faces, max_faces, counts, mode, normals,
-                             (hipStream_t)stream);
-}
-
-int mp_mesh_points(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *counts, float *points,
-                   int32_t *count_out, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (!counts || !count_out || max_verts < 0 || (max_verts > 0 && (!verts || !points)))
-    return fail(ctx, MP_ERR_ARG, "mp_mesh_points: bad argument");
-  DeviceGuard g(ctx->device);
-  return launch_mesh_points(ctx, verts, max_verts, counts, points, count_out, (hipStream_t)stream);
+  return marching_cubes_checked(ctx, "mp_marching_cubes", 1, &volume, r, level, b_min, b_max, &verts, max_verts,
+                                &faces, max_faces, &counts, nullptr, stream);
 }
 
 int mp_marching_cubes_batch(mp_ctx *ctx, int n_frames, const float *const *volume, int r, float level,
                             const float *b_min, const float *b_max, float *const *verts, int64_t max_verts,
                             int32_t *const *faces, int64_t max_faces, int32_t *const *counts,
                             const int32_t *const *gate, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (n_frames < 1 || n_frames > kMaxFrames)
-    return fail(ctx, MP_ERR_ARG, "mp_marching_cubes_batch: 1..%d frames per call, got %d", kMaxFrames, n_frames);
-  if (!volume || !b_min || !b_max || !counts || r < 2 || r > 1023 || max_verts < 0 || max_faces < 0 ||
-      (max_verts > 0 && !verts) || (max_faces > 0 && !faces))
-    return fail(ctx, MP_ERR_ARG, "mp_marching_cubes_batch: bad argument");
-  for (int f = 0; f < n_frames; ++f) {
-    if (!volume[f] || !counts[f] || (max_verts > 0 && !verts[f]) || (max_faces > 0 && !faces[f]))
-      return fail(ctx, MP_ERR_ARG, "mp_marching_cubes_batch: null buffer for frame %d", f);
-    if (((uintptr_t)volume[f] | (uintptr_t)counts[f] | (uintptr_t)(gate ? gate[f] : nullptr) |
-         (uintptr_t)(max_verts > 0 ? verts[f] : nullptr) | (uintptr_t)(max_faces > 0 ? faces[f] : nullptr)) & 3)
-      return fail(ctx, MP_ERR_ARG, "mp_marching_cubes_batch: misaligned buffer for frame %d", f);
-  }
-  // a frame without vertex / face rows gets no pointer at all
-  float *verts_p[kMaxFrames];
-  int32_t *faces_p[kMaxFrames];
-  for (int f = 0; f < n_frames; ++f) {
-    verts_p[f] = max_verts > 0 ? verts[f] : nullptr;
-    faces_p[f] = max_faces > 0 ? faces[f] : nullptr;
-  }
-  DeviceGuard g(ctx->device);
-  void *scratch = nullptr;
-  int rc = ensure_scratch(ctx, (hipStream_t)stream, (size_t)n_frames * mc_scratch_bytes(r), &scratch);
-  if (rc != MP_OK) return rc;
-  return launch_marching_cubes_batch(ctx, scratch, n_frames, volume, r, level, b_min, b_max, verts_p, max_verts,
-                                     faces_p, max_faces, counts, gate, (hipStream_t)stream);
+  return marching_cubes_checked(ctx, "mp_marching_cubes_batch", n_frames, volume, r, level, b_min, b_max, verts,
+                                max_verts, faces, max_faces, counts, gate, stream);
+}
+
+int mp_mesh_normals(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                    const int32_t *counts, int mode, float *normals, mp_stream stream) {
+  return mesh_normals_checked(ctx, "mp_mesh_normals", 1, &verts, max_verts, &faces, max_faces, &counts, mode, &normals,
+                              stream);
 }
 
 int mp_mesh_normals_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
                           const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts, int mode,
                           float *const *normals, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (n_frames < 1 || n_frames > kMaxFrames)
-    return fail(ctx, MP_ERR_ARG, "mp_mesh_normals_batch: 1..%d frames per call, got %d", kMaxFrames, n_frames);
-  if (!counts || max_verts < 0 || max_faces < 0 || (max_verts > 0 && (!verts || !normals)) ||
-      (max_faces > 0 && !faces) || (mode != MP_NORMALS_REFERENCE && mode != MP_NORMALS_ACCUMULATE))
-    return fail(ctx, MP_ERR_ARG, "mp_mesh_normals_batch: bad argument");
-  if (max_verts > 0x7fffffffLL / 3 || max_faces > 0x7fffffffLL / 3)
-    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_mesh_normals_batch: capacities beyond 2^31 / 3 need 64-bit indices");
-  const int32_t *faces_p[kMaxFrames];
-  for (int f = 0; f < n_frames; ++f) {
-    if (!counts[f] || (max_verts > 0 && (!verts[f] || !normals[f])) || (max_faces > 0 && !faces[f]))
-      return fail(ctx, MP_ERR_ARG, "mp_mesh_normals_batch: null buffer for frame %d", f);
-    faces_p[f] = max_faces > 0 ? faces[f] : nullptr;
-    if (((uintptr_t)counts[f] | (uintptr_t)faces_p[f] | (uintptr_t)(max_verts > 0 ? verts[f] : nullptr) |
-         (uintptr_t)(max_verts > 0 ? normals[f] : nullptr)) & 3)
-      return fail(ctx, MP_ERR_ARG, "mp_mesh_normals_batch: misaligned buffer for frame %d", f);
-  }
-  if (max_verts == 0) return MP_OK;
-  DeviceGuard g(ctx->device);
-  void *scratch = nullptr;
-  int rc = ensure_scratch(ctx, (hipStream_t)stream, mesh_normals_scratch_bytes(n_frames, max_verts, max_faces), &scratch);
-  if (rc != MP_OK) return rc;
-  return launch_mesh_normals_batch(ctx, scratch, n_frames, verts, max_verts, faces_p, max_faces, counts, mode, normals,
-                                   (hipStream_t)stream);
+  return mesh_normals_checked(ctx, "mp_mesh_normals_batch", n_frames, verts, max_verts, faces, max_faces, counts, mode,
+                              normals, stream);
+}
+
+int mp_mesh_points(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *counts, float *points,
+                   int32_t *count_out, mp_stream stream) {
+  return mesh_points_checked(ctx, "mp_mesh_points", 1, &verts, max_verts, &counts, &points, &count_out, stream);
 }
 
 int mp_mesh_points_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
                          const int32_t *const *counts, float *const *points, int32_t *const *count_out,
                          mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (n_frames < 1 || n_frames > kMaxFrames)
-    return fail(ctx, MP_ERR_ARG, "mp_mesh_points_batch: 1..%d frames per call, got %d", kMaxFrames, n_frames);
-  if (!counts || !count_out || max_verts < 0 || (max_verts > 0 && (!verts || !points)))
-    return fail(ctx, MP_ERR_ARG, "mp_mesh_points_batch: bad argument");
-  const float *verts_p[kMaxFrames];
-  float *points_p[kMaxFrames];
-  for (int f = 0; f < n_frames; ++f) {
-    if (!counts[f] || !count_out[f] || (max_verts > 0 && (!verts[f] || !points[f])))
-      return fail(ctx, MP_ERR_ARG, "mp_mesh_points_batch: null buffer for frame %d", f);
-    verts_p[f] = max_verts > 0 ? verts[f] : nullptr;
-    points_p[f] = max_verts > 0 ? points[f] : nullptr;
-    if (((uintptr_t)counts[f] | (uintptr_t)count_out[f] | (uintptr_t)verts_p[f] | (uintptr_t)points_p[f]) & 3)
-      return fail(ctx, MP_ERR_ARG, "mp_mesh_points_batch: misaligned buffer for frame %d", f);
-  }
-  DeviceGuard g(ctx->device);
-  return launch_mesh_points_batch(ctx, n_frames, verts_p, max_verts, counts, points_p, count_out, (hipStream_t)stream);
+  return mesh_points_checked(ctx, "mp_mesh_points_batch", n_frames, verts, max_verts, counts, points, count_out,
+                             stream);
+}
+
+int mp_volume_keep_largest(mp_ctx *ctx, const float *volume, int r, float level, int connectivity, float fill,
+                           float *out, int32_t *stats, mp_stream stream) {
+  return keep_largest_checked(ctx, "mp_volume_keep_largest", 1, &volume, r, level, connectivity, fill, &out, &stats,
+                              nullptr, stream);
 }
 
 int mp_volume_keep_largest_batch(mp_ctx *ctx, int n_frames, const float *const *volume, int r, float level,
                                  int connectivity, float fill, float *const *out, int32_t *const *stats,
                                  const int32_t *const *gate, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (n_frames < 1 || n_frames > kMaxFrames)
-    return fail(ctx, MP_ERR_ARG, "mp_volume_keep_largest_batch: 1..%d frames per call, got %d", kMaxFrames, n_frames);
-  if (!volume || !out || !stats || r < 1)
-    return fail(ctx, MP_ERR_ARG, "mp_volume_keep_largest_batch: bad argument");
-  if (connectivity != MP_CONN_6 && connectivity != MP_CONN_26)
-    return fail(ctx, MP_ERR_ARG, "mp_volume_keep_largest_batch: connectivity must be 6 or 26, got %d", connectivity);
-  if (!(fill <= level))  // a NaN fill fails this test too
-    return fail(ctx, MP_ERR_ARG, "mp_volume_keep_largest_batch: fill %g would be foreground at level %g", (double)fill,
-                (double)level);
-  for (int f = 0; f < n_frames; ++f) {
-    if (!volume[f] || !out[f] || !stats[f])
-      return fail(ctx, MP_ERR_ARG, "mp_volume_keep_largest_batch: null buffer for frame %d", f);
-    if (((uintptr_t)volume[f] | (uintptr_t)out[f] | (uintptr_t)stats[f] | (uintptr_t)(gate ? gate[f] : nullptr)) & 3)
-      return fail(ctx, MP_ERR_ARG, "mp_volume_keep_largest_batch: misaligned buffer for frame %d", f);
-  }
-  if (r > 1290)  // 1291^3 > 2^31
-    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_volume_keep_largest_batch: resolution %d needs 64-bit voxel indices", r);
-  DeviceGuard g(ctx->device);
-  void *scratch = nullptr;
-  int rc = ensure_scratch(ctx, (hipStream_t)stream, (size_t)n_frames * cc_scratch_bytes(r), &scratch);
-  if (rc != MP_OK) return rc;
-  return launch_keep_largest_batch(ctx, scratch, n_frames, volume, r, level, connectivity, fill, out, stats, gate,
-                                   (hipStream_t)stream);
-}
-
-int mp_volume_keep_largest(mp_ctx *ctx, const float *volume, int r, float level, int connectivity, float fill,
-                           float *out, int32_t *stats, mp_stream stream) {
-  return mp_volume_keep_largest_batch(ctx, 1, &volume, r, level, connectivity, fill, &out, &stats, nullptr, stream);
+  return keep_largest_checked(ctx, "mp_volume_keep_largest_batch", n_frames, volume, r, level, connectivity, fill, out,
+                              stats, gate, stream);
 }
 
 int mp_group_norm(mp_ctx *ctx, const float *x, int n, int c, int64_t hw, int groups,

@@ -268,11 +268,6 @@ int launch_mesh_normals_batch(mp_ctx *ctx, void *scratch, int n_frames, const fl
   return MP_OK;
 }
 
-int launch_mesh_normals(mp_ctx *ctx, void *scratch, const float *verts, long long max_v, const int32_t *faces,
-                        long long max_f, const int32_t *counts, int mode, float *normals, hipStream_t st) {
-  return launch_mesh_normals_batch(ctx, scratch, 1, &verts, max_v, &faces, max_f, &counts, mode, &normals, st);
-}
-
 int launch_mesh_points_batch(mp_ctx *ctx, int n_frames, const float *const *verts, long long max_v,
                              const int32_t *const *counts, float *const *points, int32_t *const *count_out,
                              hipStream_t st) {
@@ -288,11 +283,6 @@ int launch_mesh_points_batch(mp_ctx *ctx, int n_frames, const float *const *vert
   hipLaunchKernelGGL(mesh_points_kernel, dim3(vb ? vb : 1, n_frames), dim3(kMeshBlock), 0, st, fr, max_v);
   MP_HIP(ctx, hipGetLastError());
   return MP_OK;
-}
-
-int launch_mesh_points(mp_ctx *ctx, const float *verts, long long max_v, const int32_t *counts, float *points,
-                       int32_t *count_out, hipStream_t st) {
-  return launch_mesh_points_batch(ctx, 1, &verts, max_v, &counts, &points, &count_out, st);
 }
 
 }  // namespace mp

@@ -195,12 +195,6 @@ struct Mlp {
   MlpPack16 pack16() const;
 };
 
-// mcubes.hip
-size_t mc_scratch_bytes(int r);
-int launch_marching_cubes(mp_ctx *ctx, void *scratch, const float *vol, int r, float level,
-                          const float *bmin, const float *bmax, float *verts, long long max_v,
-                          int32_t *faces, long long max_f, int32_t *counts, hipStream_t st);
-
 }  // namespace mp
 
 struct mp_ctx {
@@ -351,8 +345,6 @@ int launch_lattice_points(mp_ctx *ctx, const uint32_t *packed, const int32_t *co
 int launch_scatter_nodes(mp_ctx *ctx, const uint32_t *packed, const int32_t *count, long long cap,
                          int r, const float *values, float *vol, hipStream_t st);
 // vertices.hip
-int launch_forward_vertices(mp_ctx *ctx, void *scratch, const float *vol, int r, int dir, int64_t *x, int64_t *y,
-                            float *z, float *norm, int32_t *count, hipStream_t st);
 size_t forward_vertices_scratch_bytes(int r);
 int launch_forward_vertices_batch(mp_ctx *ctx, void *scratch, int n_frames, const float *const *vol, int r, int dir,
                                   int64_t *const *x, int64_t *const *y, float *const *z, float *const *norm,
@@ -363,17 +355,11 @@ int launch_paint_batch(mp_ctx *ctx, int n_frames, const int64_t *const *x, const
 int launch_vertex_points(mp_ctx *ctx, const int64_t *x, const int64_t *y, const float *z,
                          const int32_t *count, long long cap, int res, const float *mat16,
                          float *pts, hipStream_t st);
-int launch_paint(mp_ctx *ctx, const int64_t *x, const int64_t *y, const float *vals, int ch_major,
-                 const int32_t *count, long long cap, int res, float scale, float bias, float lo,
-                 float hi, float *image, hipStream_t st);
 
 int launch_visualize(mp_ctx *ctx, const float *image, int res, int size, float *out, uint8_t *mask,
                      hipStream_t st);
 // mcubes.hip
 size_t mc_scratch_bytes(int r);
-int launch_marching_cubes(mp_ctx *ctx, void *scratch, const float *vol, int r, float level,
-                          const float *bmin, const float *bmax, float *verts, long long max_v,
-                          int32_t *faces, long long max_f, int32_t *counts, hipStream_t st);
 // n_frames volumes of one resolution; scratch: n_frames * mc_scratch_bytes(r); gate: NULL or n_frames entries
 int launch_marching_cubes_batch(mp_ctx *ctx, void *scratch, int n_frames, const float *const *vol, int r, float level,
                                 const float *bmin, const float *bmax, float *const *verts, long long max_v,
@@ -393,10 +379,6 @@ int launch_mesh_normals_batch(mp_ctx *ctx, void *scratch, int n_frames, const fl
 int launch_mesh_points_batch(mp_ctx *ctx, int n_frames, const float *const *verts, long long max_v,
                              const int32_t *const *counts, float *const *points, int32_t *const *count_out,
                              hipStream_t st);
-int launch_mesh_normals(mp_ctx *ctx, void *scratch, const float *verts, long long max_v, const int32_t *faces,
-                        long long max_f, const int32_t *counts, int mode, float *normals, hipStream_t st);
-int launch_mesh_points(mp_ctx *ctx, const float *verts, long long max_v, const int32_t *counts, float *points,
-                       int32_t *count_out, hipStream_t st);
 
 // conv3x3.hip
 int launch_conv3x3_pack(mp_ctx *ctx, const float *w, int cout, int cin, float *wp, hipStream_t st);

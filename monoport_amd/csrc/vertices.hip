@@ -194,11 +194,6 @@ int launch_forward_vertices_batch(mp_ctx *ctx, void *scratch, int n_frames, cons
   return MP_OK;
 }
 
-int launch_forward_vertices(mp_ctx *ctx, void *scratch, const float *vol, int r, int dir, int64_t *x,
-                            int64_t *y, float *z, float *norm, int32_t *count, hipStream_t st) {
-  return launch_forward_vertices_batch(ctx, scratch, 1, &vol, r, dir, &x, &y, &z, &norm, &count, st);
-}
-
 // verts = (X, Y, res - Z) (main.py:231-233) through orthogonal(., mat_color) (main.py:237).
 struct Mat34 {
   float m[12];
@@ -292,12 +287,6 @@ int launch_paint_batch(mp_ctx *ctx, int n_frames, const int64_t *const *x, const
   }
   MP_HIP(ctx, hipGetLastError());
   return MP_OK;
-}
-
-int launch_paint(mp_ctx *ctx, const int64_t *x, const int64_t *y, const float *vals, int ch_major,
-                 const int32_t *count, long long cap, int res, float scale, float bias, float lo,
-                 float hi, float *image, hipStream_t st) {
-  return launch_paint_batch(ctx, 1, &x, &y, &vals, ch_major, &count, cap, res, scale, bias, lo, hi, &image, st);
 }
 
 // RTL/main.py:259-281: *255, torch.rot90(k=1, dims [0,1]) (out[i][j] = in[j][res-1-i]), nearest

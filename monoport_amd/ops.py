@@ -152,6 +152,33 @@ def _early_arg(who, early, n, expect, r0):
     return ctypes.byref(early.struct(expect))
 
 
+def _frame_chunks(n):
+    """The slices (f0, f1) of at most MAX_FRAMES frames in which a batched entry point takes n frames."""
+    for f0 in range(0, n, MAX_FRAMES):
+        yield f0, min(f0 + MAX_FRAMES, n)
+
+
+def _one_size_volumes(who, volumes):
+    """The volumes of one mesh / render call (``_cubic_volume`` each; at least one, of one size, on one device) ->
+    (vols, n, r, device)."""
+    vols = [_cubic_volume(v, who) for v in volumes]
+    if not vols:
+        raise ValueError("%s wants at least one volume" % who)
+    r, dev = vols[0].shape[0], vols[0].device
+    if any(v.shape[0] != r or v.device != dev for v in vols):
+        raise ValueError("%s wants cubic volumes of one size on one device" % who)
+    return vols, len(vols), r, dev
+
+
+def _gates(who, gates, n, device):
+    """Checks the per-frame gates of a call: None, or n device int32 tensors (None entries = frame on)."""
+    if gates is not None:
+        if len(gates) != n:
+            raise ValueError("%s: %d volumes, %d gates" % (who, n, len(gates)))
+        if any(g is not None and (g.dtype != torch.int32 or g.numel() < 1 or g.device != device) for g in gates):
+            raise ValueError("%s: a gate is an int32 tensor on the volumes' device" % who)
+
+
 def _keep_until_done(device, *tensor_lists):
     """The call just enqueued reads these tensors on ``device``'s current stream: the allocator must not hand their
     memory to another stream before it has."""
@@ -968,70 +995,59 @@ def plan_wait(waiter, signaller):
         rec.cmds.append((_lib.PLAN_WAIT, bytes(w), 0))
 
 
-def forward_vertices_raw(volume, direction="front"):
-    """mp_forward_vertices: returns capacity-sized (X, Y, Z, norm, count) device tensors."""
-    vol = _cubic_volume(volume, "forward_vertices")
-    r = vol.shape[0]
-    ctx = get_context(vol.device)
+def _forward_vertices(who, volumes, direction):
+    """What forward_vertices_raw and forward_vertices_raw_batch do: per volume (X, Y, Z, norm, count), rows of five
+    tensors."""
+    vols, n, r, dev = _one_size_volumes(who, volumes)
+    ctx = get_context(dev)
     cap = r * r
-    dev = vol.device
-    x = torch.empty((cap,), dtype=torch.int64, device=dev)
-    y = torch.empty((cap,), dtype=torch.int64, device=dev)
-    z = torch.empty((cap,), dtype=torch.float32, device=dev)
-    nrm = torch.empty((cap, 3), dtype=torch.float32, device=dev)
-    count = torch.empty((1,), dtype=torch.int32, device=dev)
-    ctx.check(ctx.lib.mp_forward_vertices(ctx.handle, _ptr(vol), r, DIRECTIONS[direction], _ptr(x),
-                                          _ptr(y), _ptr(z), _ptr(nrm), _ptr(count), _stream(vol)),
-              "mp_forward_vertices")
-    return x, y, z, nrm, count
+    x = torch.empty((n, cap), dtype=torch.int64, device=dev).unbind(0)
+    y = torch.empty((n, cap), dtype=torch.int64, device=dev).unbind(0)
+    z = torch.empty((n, cap), dtype=torch.float32, device=dev).unbind(0)
+    nrm = torch.empty((n, cap, 3), dtype=torch.float32, device=dev).unbind(0)
+    count = torch.empty((n, 1), dtype=torch.int32, device=dev).unbind(0)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_forward_vertices_batch(
+            ctx.handle, f1 - f0, _ptr_array(vols[f0:f1]), r, DIRECTIONS[direction], _ptr_array(x[f0:f1]),
+            _ptr_array(y[f0:f1]), _ptr_array(z[f0:f1]), _ptr_array(nrm[f0:f1]), _ptr_array(count[f0:f1]),
+            _stream(vols[0])), "mp_forward_vertices_batch")
+    _keep_until_done(dev, vols)
+    return list(zip(x, y, z, nrm, count))
+
+
+def forward_vertices_raw(volume, direction="front"):
+    """mp_forward_vertices_batch with one frame: returns capacity-sized (X, Y, Z, norm, count) device tensors."""
+    return _forward_vertices("forward_vertices", [volume], direction)[0]
 
 
 def forward_vertices_raw_batch(volumes, direction="front"):
-    """mp_forward_vertices_batch: ``[forward_vertices_raw(v, direction) for v in volumes]`` (up to MAX_FRAMES cubic
-    volumes of one size) in one set of launches; every frame's (X, Y, Z, norm, count) are views of five tensors."""
-    vols = [_cubic_volume(v, "forward_vertices_raw_batch") for v in volumes]
-    n = len(vols)
-    r = vols[0].shape[0]
-    if any(v.shape[0] != r for v in vols):
-        raise ValueError("forward_vertices_raw_batch wants cubic volumes of one size")
-    dev = vols[0].device
-    ctx = get_context(dev)
-    cap = r * r
-    x = torch.empty((n, cap), dtype=torch.int64, device=dev)
-    y = torch.empty((n, cap), dtype=torch.int64, device=dev)
-    z = torch.empty((n, cap), dtype=torch.float32, device=dev)
-    nrm = torch.empty((n, cap, 3), dtype=torch.float32, device=dev)
-    count = torch.empty((n, 1), dtype=torch.int32, device=dev)
-    out = []
-    for f0 in range(0, n, MAX_FRAMES):
-        f1 = min(f0 + MAX_FRAMES, n)
-        ctx.check(ctx.lib.mp_forward_vertices_batch(
-            ctx.handle, f1 - f0, _ptr_array(vols[f0:f1]), r, DIRECTIONS[direction], _ptr_array(x[f0:f1]),
-            _ptr_array(y[f0:f1]), _ptr_array(z[f0:f1]), _ptr_array(nrm[f0:f1]), _ptr_array(count[f0:f1]), _stream(x)),
-            "mp_forward_vertices_batch")
-    _keep_until_done(dev, vols)
-    for f in range(n):
-        out.append((x[f], y[f], z[f], nrm[f], count[f]))
-    return out
+    """mp_forward_vertices_batch: ``[forward_vertices_raw(v, direction) for v in volumes]`` (cubic volumes of one
+    size) in one set of launches per MAX_FRAMES volumes; every frame's (X, Y, Z, norm, count) are views of five
+    tensors."""
+    return _forward_vertices("forward_vertices_raw_batch", volumes, direction)
 
 
-def paint_batch(xs, ys, values, channel_major, counts, res, scale, bias, lo, hi):
-    """mp_paint_batch: ``[paint(x, y, v, channel_major, c, res, ...) for ...]`` (up to MAX_FRAMES renders of one size,
-    one capacity) in two launches; the images are views of one [n, res, res, 3] tensor."""
+def _paint(xs, ys, values, channel_major, counts, res, scale, bias, lo, hi):
+    """What paint and paint_batch do: per frame an image [res,res,3], rows of one tensor."""
     n = len(xs)
     dev = xs[0].device
     ctx = get_context(dev)
     cap = xs[0].shape[0]
     vals = [_f32c(v) for v in values]
-    images = torch.empty((n, res, res, 3), dtype=torch.float32, device=dev)
-    for f0 in range(0, n, MAX_FRAMES):
-        f1 = min(f0 + MAX_FRAMES, n)
+    images = torch.empty((n, res, res, 3), dtype=torch.float32, device=dev).unbind(0)
+    for f0, f1 in _frame_chunks(n):
         ctx.check(ctx.lib.mp_paint_batch(
             ctx.handle, f1 - f0, _ptr_array(xs[f0:f1]), _ptr_array(ys[f0:f1]), _ptr_array(vals[f0:f1]),
             int(channel_major), _ptr_array(counts[f0:f1]), cap, int(res), float(scale), float(bias), float(lo),
-            float(hi), _ptr_array(images[f0:f1]), _stream(images)), "mp_paint_batch")
+            float(hi), _ptr_array(images[f0:f1]), _stream(images[0])), "mp_paint_batch")
     _keep_until_done(dev, vals)
-    return [images[f] for f in range(n)]
+    return list(images)
+
+
+def paint_batch(xs, ys, values, channel_major, counts, res, scale, bias, lo, hi):
+    """mp_paint_batch: ``[paint(x, y, v, channel_major, c, res, ...) for ...]`` (renders of one size, one capacity)
+    in two launches per MAX_FRAMES renders; the images are views of one [n, res, res, 3] tensor."""
+    return _paint(xs, ys, values, channel_major, counts, res, scale, bias, lo, hi)
 
 
 def vertex_points(x, y, z, count, res, mat):
@@ -1046,15 +1062,9 @@ def vertex_points(x, y, z, count, res, mat):
 
 
 def paint(x, y, values, channel_major, count, res, scale, bias, lo, hi):
-    """canvas of ones [res,res,3] with image[X,Y,:] = clamp(values*scale+bias) (main.py:220-248)."""
-    ctx = get_context(x.device)
-    cap = x.shape[0]
-    image = torch.empty((res, res, 3), dtype=torch.float32, device=x.device)
-    values = _f32c(values)
-    ctx.check(ctx.lib.mp_paint(ctx.handle, _ptr(x), _ptr(y), _ptr(values), int(channel_major),
-                               _ptr(count), cap, int(res), float(scale), float(bias), float(lo),
-                               float(hi), _ptr(image), _stream(image)), "mp_paint")
-    return image
+    """canvas of ones [res,res,3] with image[X,Y,:] = clamp(values*scale+bias) (main.py:220-248): mp_paint_batch
+    with one frame."""
+    return _paint([x], [y], [values], channel_major, [count], res, scale, bias, lo, hi)[0]
 
 
 def visualize(image, size=256):
@@ -1086,27 +1096,6 @@ def prepare_inputs(segm, mean, std, with_color=True):
     return g, c
 
 
-def marching_cubes_raw(volume, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), max_verts=None,
-                       max_faces=None):
-    """mp_marching_cubes: capacity-sized (verts [max_v,3] f32, faces [max_f,3] int32,
-    counts int32[2] = needed vertices / faces) on device, no host sync."""
-    vol = _cubic_volume(volume, "marching_cubes")
-    r = vol.shape[0]
-    ctx = get_context(vol.device)
-    if max_verts is None:
-        max_verts = 12 * r * r  # a closed body at resolution r has O(r^2) surface cells
-    if max_faces is None:
-        max_faces = 2 * max_verts
-    dev = vol.device
-    verts = torch.empty((max_verts, 3), dtype=torch.float32, device=dev)
-    faces = torch.empty((max_faces, 3), dtype=torch.int32, device=dev)
-    counts = torch.empty((2,), dtype=torch.int32, device=dev)
-    ctx.check(ctx.lib.mp_marching_cubes(ctx.handle, _ptr(vol), r, float(level), _float3(b_min), _float3(b_max),
-                                        _ptr(verts), max_verts, _ptr(faces), max_faces,
-                                        _ptr(counts), _stream(vol)), "mp_marching_cubes")
-    return verts, faces, counts
-
-
 # MP_NORMALS_* (include/monoport_hip.h): what the reference's compute_normal computes / what its comments describe
 NORMALS_MODES = {"reference": _lib.NORMALS_REFERENCE, "accumulate": _lib.NORMALS_ACCUMULATE}
 
@@ -1132,43 +1121,20 @@ def _mesh_buffers(verts, faces, counts):
             raise ValueError("verts, faces and counts must live on one device")
 
 
-def mesh_normals_raw(verts, faces, counts, mode="accumulate", out=None):
-    """mp_mesh_normals: verts [max_v,3] f32, faces [max_f,3] int32, counts int32[2] on device (as
-    ``marching_cubes_raw`` returns them) -> normals [max_v,3] f32; rows beyond counts[0] are not written.
-    No host sync."""
-    _mesh_buffers(verts, faces, counts)
-    ctx = get_context(verts.device)
-    if out is None:
-        out = torch.empty_like(verts)
-    ctx.check(ctx.lib.mp_mesh_normals(ctx.handle, _ptr(verts), verts.shape[0], _ptr(faces), faces.shape[0],
-                                      _ptr(counts), _normals_mode(mode), _ptr(out), _stream(verts)),
-              "mp_mesh_normals")
-    return out
-
-
-def mesh_points_raw(verts, counts):
-    """mp_mesh_points: verts [max_v,3] -> (points [3,max_v], count int32[1] = min(counts[0], max_v)) on device,
-    the operands of ``query_counted``.  No host sync."""
-    _mesh_buffers(verts, None, counts)
-    ctx = get_context(verts.device)
-    pts = torch.zeros((3, verts.shape[0]), dtype=torch.float32, device=verts.device)
-    count = torch.empty((1,), dtype=torch.int32, device=verts.device)
-    ctx.check(ctx.lib.mp_mesh_points(ctx.handle, _ptr(verts), verts.shape[0], _ptr(counts), _ptr(pts),
-                                     _ptr(count), _stream(verts)), "mp_mesh_points")
-    return pts, count
-
-
 def _frame_rows(who, what, t, n, shape, dtype, device):
-    """A caller's buffer of a batched mesh call: ``dtype`` [n, *shape] on ``device`` whose frames are each contiguous."""
-    if (t is None or tuple(t.shape) != (n,) + tuple(shape) or t.dtype != dtype or t.device != device
-            or not all(row.is_contiguous() for row in t)):
+    """A caller's buffers of a mesh call, one per frame (a tensor [n, *shape], or a sequence of n tensors [*shape]) ->
+    the sequence of them: ``dtype`` on ``device``, each contiguous."""
+    rows = None if t is None else tuple(t)
+    if rows is None or len(rows) != n or any(
+            r is None or tuple(r.shape) != tuple(shape) or r.dtype != dtype or r.device != device
+            or not r.is_contiguous() for r in rows):
         raise ValueError("%s: %s must be %s %s on %s with contiguous frames"
                          % (who, what, str(dtype).replace("torch.", ""), [n] + list(shape), device))
-    return t
+    return rows
 
 
 def _mesh_frames(who, verts, faces, counts):
-    """The meshes of one batched call (``_mesh_buffers`` each, one capacity for all) -> (n, max_v, max_f, device)."""
+    """The meshes of one call (``_mesh_buffers`` each, one capacity for all) -> (n, max_v, max_f, device)."""
     n = len(verts)
     if n == 0:
         raise ValueError("%s wants at least one mesh" % who)
@@ -1185,6 +1151,47 @@ def _mesh_frames(who, verts, faces, counts):
     return n, max_v, max_f, verts[0].device
 
 
+# Each stage below is one private body over lists of frames; the per-frame wrapper passes one-element lists and returns
+# element 0, so it checks, allocates and launches exactly as its _batch twin does.
+
+def _marching_cubes(who, volumes, level, b_min, b_max, max_verts, max_faces, gates, out):
+    vols, n, r, dev = _one_size_volumes(who, volumes)
+    _gates(who, gates, n, dev)
+    if out is not None:
+        verts, faces, counts = out
+        if max_verts is None:
+            max_verts = verts.shape[1]
+        if max_faces is None:
+            max_faces = faces.shape[1]
+    if max_verts is None:
+        max_verts = 12 * r * r  # a closed body at resolution r has O(r^2) surface cells
+    if max_faces is None:
+        max_faces = 2 * max_verts
+    if out is None:
+        verts = torch.empty((n, max_verts, 3), dtype=torch.float32, device=dev).unbind(0)
+        faces = torch.empty((n, max_faces, 3), dtype=torch.int32, device=dev).unbind(0)
+        counts = torch.empty((n, 2), dtype=torch.int32, device=dev).unbind(0)
+    else:
+        verts = _frame_rows(who, "out[0] (verts)", verts, n, (max_verts, 3), torch.float32, dev)
+        faces = _frame_rows(who, "out[1] (faces)", faces, n, (max_faces, 3), torch.int32, dev)
+        counts = _frame_rows(who, "out[2] (counts)", counts, n, (2,), torch.int32, dev)
+    ctx = get_context(dev)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_marching_cubes_batch(
+            ctx.handle, f1 - f0, _ptr_array(vols[f0:f1]), r, float(level), _float3(b_min), _float3(b_max),
+            _ptr_array(verts[f0:f1]), max_verts, _ptr_array(faces[f0:f1]), max_faces, _ptr_array(counts[f0:f1]),
+            None if gates is None else _ptr_array(gates[f0:f1]), _stream(vols[0])), "mp_marching_cubes_batch")
+    _keep_until_done(dev, vols, gates)
+    return list(zip(verts, faces, counts))
+
+
+def marching_cubes_raw(volume, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), max_verts=None,
+                       max_faces=None):
+    """mp_marching_cubes_batch with one frame: capacity-sized (verts [max_v,3] f32, faces [max_f,3] int32,
+    counts int32[2] = needed vertices / faces) on device, no host sync."""
+    return _marching_cubes("marching_cubes", [volume], level, b_min, b_max, max_verts, max_faces, None, None)[0]
+
+
 def marching_cubes_raw_batch(volumes, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), max_verts=None,
                              max_faces=None, gates=None, out=None):
     """mp_marching_cubes_batch: ``[marching_cubes_raw(v, ...) for v in volumes]`` (cubic volumes of one size, one
@@ -1193,47 +1200,29 @@ def marching_cubes_raw_batch(volumes, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1
     device int32 tensors (or None entries = frame on); a frame whose gate reads 0 gets counts (0, 0) and nothing
     else of it is read or written.  ``out``: (verts [n,max_v,3] f32, faces [n,max_f,3] int32, counts [n,2] int32)
     to write into.  No host sync."""
-    who = "marching_cubes_raw_batch"
-    vols = [_cubic_volume(v, who) for v in volumes]
-    n = len(vols)
-    if n == 0:
-        raise ValueError("%s wants at least one volume" % who)
-    r = vols[0].shape[0]
-    dev = vols[0].device
-    if any(v.shape[0] != r or v.device != dev for v in vols):
-        raise ValueError("%s wants cubic volumes of one size on one device" % who)
-    if gates is not None:
-        if len(gates) != n:
-            raise ValueError("%s: %d volumes, %d gates" % (who, n, len(gates)))
-        if any(g is not None and (g.dtype != torch.int32 or g.numel() < 1 or g.device != dev) for g in gates):
-            raise ValueError("%s: a gate is an int32 tensor on the volumes' device" % who)
-    if out is not None:
-        verts, faces, counts = out
-        if max_verts is None:
-            max_verts = verts.shape[1]
-        if max_faces is None:
-            max_faces = faces.shape[1]
-    if max_verts is None:
-        max_verts = 12 * r * r  # marching_cubes_raw's guess
-    if max_faces is None:
-        max_faces = 2 * max_verts
+    return _marching_cubes("marching_cubes_raw_batch", volumes, level, b_min, b_max, max_verts, max_faces, gates, out)
+
+
+def _mesh_normals(who, verts, faces, counts, mode, out):
+    n, max_v, max_f, dev = _mesh_frames(who, verts, faces, counts)
+    code = _normals_mode(mode)
     if out is None:
-        verts = torch.empty((n, max_verts, 3), dtype=torch.float32, device=dev)
-        faces = torch.empty((n, max_faces, 3), dtype=torch.int32, device=dev)
-        counts = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        out = torch.empty((n, max_v, 3), dtype=torch.float32, device=dev).unbind(0)
     else:
-        _frame_rows(who, "out[0] (verts)", verts, n, (max_verts, 3), torch.float32, dev)
-        _frame_rows(who, "out[1] (faces)", faces, n, (max_faces, 3), torch.int32, dev)
-        _frame_rows(who, "out[2] (counts)", counts, n, (2,), torch.int32, dev)
+        out = _frame_rows(who, "out", out, n, (max_v, 3), torch.float32, dev)
     ctx = get_context(dev)
-    for f0 in range(0, n, MAX_FRAMES):
-        f1 = min(f0 + MAX_FRAMES, n)
-        ctx.check(ctx.lib.mp_marching_cubes_batch(
-            ctx.handle, f1 - f0, _ptr_array(vols[f0:f1]), r, float(level), _float3(b_min), _float3(b_max),
-            _ptr_array(verts[f0:f1]), max_verts, _ptr_array(faces[f0:f1]), max_faces, _ptr_array(counts[f0:f1]),
-            None if gates is None else _ptr_array(gates[f0:f1]), _stream(verts)), "mp_marching_cubes_batch")
-    _keep_until_done(dev, vols, gates)
-    return [(verts[f], faces[f], counts[f]) for f in range(n)]
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_mesh_normals_batch(
+            ctx.handle, f1 - f0, _ptr_array(verts[f0:f1]), max_v, _ptr_array(faces[f0:f1]), max_f,
+            _ptr_array(counts[f0:f1]), code, _ptr_array(out[f0:f1]), _stream(verts[0])), "mp_mesh_normals_batch")
+    return list(out)
+
+
+def mesh_normals_raw(verts, faces, counts, mode="accumulate", out=None):
+    """mp_mesh_normals_batch with one frame: verts [max_v,3] f32, faces [max_f,3] int32, counts int32[2] on device (as
+    ``marching_cubes_raw`` returns them) -> normals [max_v,3] f32 (``out`` itself if given); rows beyond counts[0]
+    are not written.  No host sync."""
+    return _mesh_normals("mesh_normals_raw", [verts], [faces], [counts], mode, None if out is None else [out])[0]
 
 
 def mesh_normals_raw_batch(verts, faces, counts, mode="accumulate", out=None):
@@ -1241,74 +1230,76 @@ def mesh_normals_raw_batch(verts, faces, counts, mode="accumulate", out=None):
     of per-mesh device tensors as ``marching_cubes_raw_batch`` returns them, one capacity) in the launches of ONE
     mesh per MAX_FRAMES meshes; the normals are views of one [n,max_v,3] tensor (``out`` if given), bit for bit what
     the per-mesh call gives; rows beyond a mesh's counts[0] are not written.  No host sync."""
-    who = "mesh_normals_raw_batch"
-    n, max_v, max_f, dev = _mesh_frames(who, verts, faces, counts)
-    code = _normals_mode(mode)
+    return _mesh_normals("mesh_normals_raw_batch", verts, faces, counts, mode, out)
+
+
+def _mesh_points(who, verts, counts, out):
+    n, max_v, _, dev = _mesh_frames(who, verts, None, counts)
     if out is None:
-        out = torch.empty((n, max_v, 3), dtype=torch.float32, device=dev)
+        pts = torch.zeros((n, 3, max_v), dtype=torch.float32, device=dev).unbind(0)
+        count = torch.empty((n, 1), dtype=torch.int32, device=dev).unbind(0)
     else:
-        _frame_rows(who, "out", out, n, (max_v, 3), torch.float32, dev)
+        pts = _frame_rows(who, "out[0] (points)", out[0], n, (3, max_v), torch.float32, dev)
+        count = _frame_rows(who, "out[1] (count)", out[1], n, (1,), torch.int32, dev)
     ctx = get_context(dev)
-    for f0 in range(0, n, MAX_FRAMES):
-        f1 = min(f0 + MAX_FRAMES, n)
-        ctx.check(ctx.lib.mp_mesh_normals_batch(
-            ctx.handle, f1 - f0, _ptr_array(verts[f0:f1]), max_v, _ptr_array(faces[f0:f1]), max_f,
-            _ptr_array(counts[f0:f1]), code, _ptr_array(out[f0:f1]), _stream(out)), "mp_mesh_normals_batch")
-    return [out[f] for f in range(n)]
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_mesh_points_batch(
+            ctx.handle, f1 - f0, _ptr_array(verts[f0:f1]), max_v, _ptr_array(counts[f0:f1]), _ptr_array(pts[f0:f1]),
+            _ptr_array(count[f0:f1]), _stream(verts[0])), "mp_mesh_points_batch")
+    return list(zip(pts, count))
+
+
+def mesh_points_raw(verts, counts):
+    """mp_mesh_points_batch with one frame: verts [max_v,3] -> (points [3,max_v], count int32[1] = min(counts[0],
+    max_v)) on device, the operands of ``query_counted``.  No host sync."""
+    return _mesh_points("mesh_points_raw", [verts], [counts], None)[0]
 
 
 def mesh_points_raw_batch(verts, counts, out=None):
     """mp_mesh_points_batch: ``[mesh_points_raw(v, c) for v, c in zip(verts, counts)]`` in one launch per MAX_FRAMES
     meshes: per mesh (points [3,max_v], count int32[1]), views of two tensors (``out`` = (points [n,3,max_v],
     count [n,1]) if given; else the points start as zeros, as ``mesh_points_raw``'s).  No host sync."""
-    who = "mesh_points_raw_batch"
-    n, max_v, _, dev = _mesh_frames(who, verts, None, counts)
-    if out is None:
-        pts = torch.zeros((n, 3, max_v), dtype=torch.float32, device=dev)
-        count = torch.empty((n, 1), dtype=torch.int32, device=dev)
-    else:
-        pts = _frame_rows(who, "out[0] (points)", out[0], n, (3, max_v), torch.float32, dev)
-        count = _frame_rows(who, "out[1] (count)", out[1], n, (1,), torch.int32, dev)
-    ctx = get_context(dev)
-    for f0 in range(0, n, MAX_FRAMES):
-        f1 = min(f0 + MAX_FRAMES, n)
-        ctx.check(ctx.lib.mp_mesh_points_batch(
-            ctx.handle, f1 - f0, _ptr_array(verts[f0:f1]), max_v, _ptr_array(counts[f0:f1]), _ptr_array(pts[f0:f1]),
-            _ptr_array(count[f0:f1]), _stream(pts)), "mp_mesh_points_batch")
-    return [(pts[f], count[f]) for f in range(n)]
+    return _mesh_points("mesh_points_raw_batch", verts, counts, out)
 
 
 # MP_CONN_* (include/monoport_hip.h): face neighbours / face, edge and corner neighbours
 CONNECTIVITIES = (_lib.CONN_6, _lib.CONN_26)
 
 
-def _keep_largest_args(who, level, connectivity, fill):
+def _keep_largest(who, sdfs, level, connectivity, fill, gates, out):
+    """``out``: None or (volumes, stats), of which either may be None = allocated here."""
+    vols, n, r, dev = _one_size_volumes(who, sdfs)
     if connectivity not in CONNECTIVITIES:
         raise ValueError("%s: connectivity must be one of %s, got %r" % (who, list(CONNECTIVITIES), connectivity))
     if not float(fill) <= float(level):  # a NaN fill fails this test too
         raise ValueError("%s: fill %r would be foreground at level %r" % (who, fill, level))
-    return float(level), int(connectivity), float(fill)
+    _gates(who, gates, n, dev)
+    cleaned, stats = (None, None) if out is None else out
+    if cleaned is None:
+        cleaned = torch.empty((n, r, r, r), dtype=torch.float32, device=dev).unbind(0)
+    else:
+        cleaned = _frame_rows(who, "out[0] (volumes)", cleaned, n, (r, r, r), torch.float32, dev)
+    if stats is None:
+        stats = torch.empty((n, 4), dtype=torch.int32, device=dev).unbind(0)
+    else:
+        stats = _frame_rows(who, "out[1] (stats)", stats, n, (4,), torch.int32, dev)
+    ctx = get_context(dev)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_volume_keep_largest_batch(
+            ctx.handle, f1 - f0, _ptr_array(vols[f0:f1]), r, float(level), int(connectivity), float(fill),
+            _ptr_array(cleaned[f0:f1]), _ptr_array(stats[f0:f1]),
+            None if gates is None else _ptr_array(gates[f0:f1]), _stream(vols[0])), "mp_volume_keep_largest_batch")
+    _keep_until_done(dev, vols, gates)
+    return list(zip(cleaned, stats))
 
 
 def keep_largest_raw(sdf, level=0.5, connectivity=6, fill=0.0, out=None):
-    """mp_volume_keep_largest: the cubic volume with every voxel > level outside its largest connected body
-    (``connectivity`` 6 or 26; ties: the smallest linear index) replaced by ``fill`` -> (volume [R,R,R] f32, stats
-    int32[4] = foreground voxels, components, voxels kept, id of the kept component or -1) on device.  ``out``: a
-    contiguous f32 [R,R,R] tensor to write into (it may be the volume itself).  No host sync."""
-    who = "keep_largest_raw"
-    vol = _cubic_volume(sdf, who)
-    level, connectivity, fill = _keep_largest_args(who, level, connectivity, fill)
-    r = vol.shape[0]
-    if out is None:
-        out = torch.empty_like(vol)
-    elif tuple(out.shape) != (r, r, r) or out.dtype != torch.float32 or out.device != vol.device or not out.is_contiguous():
-        raise ValueError("%s: out must be a contiguous float32 %s on %s" % (who, [r, r, r], vol.device))
-    stats = torch.empty((4,), dtype=torch.int32, device=vol.device)
-    ctx = get_context(vol.device)
-    ctx.check(ctx.lib.mp_volume_keep_largest(ctx.handle, _ptr(vol), r, level, connectivity, fill, _ptr(out),
-                                             _ptr(stats), _stream(vol)), "mp_volume_keep_largest")
-    _keep_until_done(vol.device, [vol])
-    return out, stats
+    """mp_volume_keep_largest_batch with one frame: the cubic volume with every voxel > level outside its largest
+    connected body (``connectivity`` 6 or 26; ties: the smallest linear index) replaced by ``fill`` -> (volume [R,R,R]
+    f32, stats int32[4] = foreground voxels, components, voxels kept, id of the kept component or -1) on device.
+    ``out``: a contiguous f32 [R,R,R] tensor to write into (it may be the volume itself).  No host sync."""
+    return _keep_largest("keep_largest_raw", [sdf], level, connectivity, fill, None,
+                         None if out is None else ([out], None))[0]
 
 
 def keep_largest_raw_batch(sdfs, level=0.5, connectivity=6, fill=0.0, gates=None, out=None):
@@ -1317,36 +1308,7 @@ def keep_largest_raw_batch(sdfs, level=0.5, connectivity=6, fill=0.0, gates=None
     two tensors and bit for bit what the per-volume call gives.  ``gates``: per-frame device int32 tensors (or None
     entries = frame on); a frame whose gate reads 0 gets stats (0, 0, 0, -1) and nothing else of it is read or
     written.  ``out``: (volumes [n,R,R,R] f32, stats [n,4] int32) to write into.  No host sync."""
-    who = "keep_largest_raw_batch"
-    vols = [_cubic_volume(v, who) for v in sdfs]
-    n = len(vols)
-    if n == 0:
-        raise ValueError("%s wants at least one volume" % who)
-    level, connectivity, fill = _keep_largest_args(who, level, connectivity, fill)
-    r = vols[0].shape[0]
-    dev = vols[0].device
-    if any(v.shape[0] != r or v.device != dev for v in vols):
-        raise ValueError("%s wants cubic volumes of one size on one device" % who)
-    if gates is not None:
-        if len(gates) != n:
-            raise ValueError("%s: %d volumes, %d gates" % (who, n, len(gates)))
-        if any(g is not None and (g.dtype != torch.int32 or g.numel() < 1 or g.device != dev) for g in gates):
-            raise ValueError("%s: a gate is an int32 tensor on the volumes' device" % who)
-    if out is None:
-        cleaned = torch.empty((n, r, r, r), dtype=torch.float32, device=dev)
-        stats = torch.empty((n, 4), dtype=torch.int32, device=dev)
-    else:
-        cleaned = _frame_rows(who, "out[0] (volumes)", out[0], n, (r, r, r), torch.float32, dev)
-        stats = _frame_rows(who, "out[1] (stats)", out[1], n, (4,), torch.int32, dev)
-    ctx = get_context(dev)
-    for f0 in range(0, n, MAX_FRAMES):
-        f1 = min(f0 + MAX_FRAMES, n)
-        ctx.check(ctx.lib.mp_volume_keep_largest_batch(
-            ctx.handle, f1 - f0, _ptr_array(vols[f0:f1]), r, level, connectivity, fill, _ptr_array(cleaned[f0:f1]),
-            _ptr_array(stats[f0:f1]), None if gates is None else _ptr_array(gates[f0:f1]), _stream(cleaned)),
-            "mp_volume_keep_largest_batch")
-    _keep_until_done(dev, vols, gates)
-    return [(cleaned[f], stats[f]) for f in range(n)]
+    return _keep_largest("keep_largest_raw_batch", sdfs, level, connectivity, fill, gates, out)
 
 
 def group_norm(x, groups, weight, bias, eps=1e-5, relu=False):

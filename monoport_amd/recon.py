@@ -72,6 +72,32 @@ def color_matrix(b_min, b_max, resolution):
     return mat
 
 
+def _counted_colours(bindings, pts, counts, outs=None):
+    """netC's predictions [3,cap] at the first counts[f] of the points pts[f] [3,cap]: per frame for a list of
+    bindings (one head, at most ops.MAX_FRAMES), of the one frame for a single binding.  One orthogonal frame is the
+    per-frame counted launch; anything else the batched one, with the projection modes if a frame is perspective."""
+    one = not isinstance(bindings, list)
+    if one:
+        bindings, pts, counts = [bindings], [pts], [counts]
+    b0 = bindings[0]
+    ortho = all(b.projection == ops.PROJECTIONS["orthogonal"] for b in bindings)
+    if one and ortho:
+        return ops.query_counted(b0.mlp, b0.feat_hwc, pts[0], counts[0], b0.calib, b0.z_scale)
+    preds = ops.query_counted_batch(b0.mlp, [b.feat_hwc for b in bindings], pts, counts, [b.calib for b in bindings],
+                                    b0.z_scale, outs=outs,
+                                    projections=None if ortho else [b.projection for b in bindings])
+    return preds[0] if one else preds
+
+
+def _bind_netC(who, netC, frames):
+    """The query bindings of a single-view ``netC``, one per frame of ``frames`` = (feature maps, calibration,
+    device to query on); the maps are moved there first (main.py:229-230)."""
+    if netC.surface_classifier.num_views > 1:
+        raise NotImplementedError("%s: netC has num_views = %d; colour the vertices of a multi-view head with "
+                                  "mesh_util.vertex_colors" % (who, netC.surface_classifier.num_views))
+    return [netC.bind([[f.to(device) for f in fs] for fs in feats], calib) for feats, calib, device in frames]
+
+
 @torch.no_grad()
 def colorization(netC, feat_tensor_C, X, Y, Z, calib_tensor, norm=None, resolution=257,
                  mat_color=None):
@@ -90,13 +116,7 @@ def colorization(netC, feat_tensor_C, X, Y, Z, calib_tensor, norm=None, resoluti
     feat_tensor_C = [[f.to(device) for f in feats] for feats in feat_tensor_C]  # main.py:229-230
     X, Y, Z = X.to(device), Y.to(device), Z.to(device)
     pts = ops.vertex_points(X, Y, Z.float(), count.to(device), resolution, mat_color)
-    binding = netC.bind(feat_tensor_C, calib_tensor)
-    if binding.projection == ops.PROJECTIONS["orthogonal"]:
-        preds = ops.query_counted(binding.mlp, binding.feat_hwc, pts, count.to(device), binding.calib,
-                                  binding.z_scale)
-    else:  # a perspective netC: the counted launch with its projection mode
-        preds = ops.query_counted_batch(binding.mlp, [binding.feat_hwc], [pts], [count.to(device)], [binding.calib],
-                                        binding.z_scale, projections=[binding.projection])[0]
+    preds = _counted_colours(netC.bind(feat_tensor_C, calib_tensor), pts, count.to(device))
     return ops.paint(X, Y, preds, 1, count.to(device), resolution, 0.5, 0.5, -np.inf, np.inf)
 
 
@@ -172,12 +192,7 @@ def _mesh_chain(sdf, level, b_min, b_max, normals, binding, max_verts=None, max_
     col = None
     if binding is not None:
         pts, count = ops.mesh_points_raw(verts, counts)
-        if binding.projection == ops.PROJECTIONS["orthogonal"]:
-            preds = ops.query_counted(binding.mlp, binding.feat_hwc, pts, count, binding.calib, binding.z_scale)
-        else:  # a perspective netC: the counted launch with its projection mode
-            preds = ops.query_counted_batch(binding.mlp, [binding.feat_hwc], [pts], [count], [binding.calib],
-                                            binding.z_scale, projections=[binding.projection])[0]
-        col = (preds * 0.5 + 0.5).t()
+        col = (_counted_colours(binding, pts, count) * 0.5 + 0.5).t()
     return verts, faces, counts, nrm, col
 
 
@@ -198,13 +213,7 @@ def reconstruct_mesh(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normal
     _check_clean(clean, level)
     binding = None
     if netC is not None:
-        if netC.surface_classifier.num_views > 1:
-            raise NotImplementedError("reconstruct_mesh: netC has num_views = %d; colour the vertices of a "
-                                      "multi-view head with mesh_util.vertex_colors"
-                                      % netC.surface_classifier.num_views)
-        device = sdf.device
-        feat_tensor_C = [[f.to(device) for f in feats] for feats in feat_tensor_C]
-        binding = netC.bind(feat_tensor_C, calib_tensor)
+        binding = _bind_netC("reconstruct_mesh", netC, [(feat_tensor_C, calib_tensor, sdf.device)])[0]
     verts, faces, counts, nrm, col = _mesh_chain(sdf, level, b_min, b_max, normals, binding, clean=clean)
     nv, nf = (int(c) for c in counts.cpu())
     if nv > verts.shape[0] or nf > faces.shape[0]:
@@ -241,16 +250,10 @@ def _mesh_chain_batch(sdfs, level, b_min, b_max, normals, bindings, gates=None, 
     if bindings is not None:
         pt_out = (out["points"], out["point_counts"]) if "points" in out else None
         pts = ops.mesh_points_raw_batch(verts, counts, out=pt_out)
-        b0 = bindings[0]
-        ortho = all(b.projection == ops.PROJECTIONS["orthogonal"] for b in bindings)
         preds = []
-        for f0 in range(0, n, ops.MAX_FRAMES):
-            f1 = min(f0 + ops.MAX_FRAMES, n)
-            preds += ops.query_counted_batch(
-                b0.mlp, [b.feat_hwc for b in bindings[f0:f1]], [p[0] for p in pts[f0:f1]],
-                [p[1] for p in pts[f0:f1]], [b.calib for b in bindings[f0:f1]], b0.z_scale,
-                outs=None if "preds" not in out else out["preds"][f0:f1],
-                projections=None if ortho else [b.projection for b in bindings[f0:f1]])
+        for f0, f1 in ops._frame_chunks(n):
+            preds += _counted_colours(list(bindings[f0:f1]), [p[0] for p in pts[f0:f1]], [p[1] for p in pts[f0:f1]],
+                                      outs=None if "preds" not in out else out["preds"][f0:f1])
     return [(verts[f], faces[f], counts[f], nrm[f], preds[f]) for f in range(n)]
 
 
@@ -276,10 +279,6 @@ def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), 
     _check_normals(normals)
     _check_clean(clean, level)
     if netC is not None:
-        if netC.surface_classifier.num_views > 1:
-            raise NotImplementedError("reconstruct_mesh_many: netC has num_views = %d; colour the vertices of a "
-                                      "multi-view head with mesh_util.vertex_colors"
-                                      % netC.surface_classifier.num_views)
         if feat_tensors_C is None or calib_tensors is None:
             raise ValueError("reconstruct_mesh_many: netC needs feat_tensors_C and calib_tensors")
         if len(feat_tensors_C) != len(sdfs) or len(calib_tensors) != len(sdfs):
@@ -289,16 +288,14 @@ def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), 
     if len({tuple(sdfs[i].shape[-3:]) for i in idx}) > 1:
         raise ValueError("reconstruct_mesh_many wants volumes of one size, got %s"
                          % sorted({tuple(sdfs[i].shape[-3:]) for i in idx}))
+    bindings = None
+    if netC is not None:
+        bindings = _bind_netC("reconstruct_mesh_many", netC,
+                              [(feat_tensors_C[i], calib_tensors[i], sdfs[i].device) for i in idx])
     meshes = [None] * len(sdfs)
     if not idx:
         return meshes
     live = [sdfs[i] for i in idx]
-    bindings = None
-    if netC is not None:
-        bindings = []
-        for i in idx:
-            feats = [[f.to(sdfs[i].device) for f in fs] for fs in feat_tensors_C[i]]
-            bindings.append(netC.bind(feats, calib_tensors[i]))
     chains = _mesh_chain_batch(live, level, b_min, b_max, normals, bindings, clean=clean)
     sizes = torch.stack([c[2] for c in chains]).cpu().tolist()  # the one host sync
     for k, i in enumerate(idx):
