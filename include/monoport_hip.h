@@ -415,7 +415,8 @@ int mp_scatter_nodes(mp_ctx *ctx, const uint32_t *packed, const int32_t *count, 
                      int r, const float *values, float *volume, mp_stream stream);
 
 /* ---- per-frame and batched forms of the mesh and render calls -------------------------------------------------------
- * mp_forward_vertices, mp_paint, mp_marching_cubes, mp_mesh_normals, mp_mesh_points and mp_volume_keep_largest are
+ * mp_forward_vertices, mp_paint, mp_marching_cubes, mp_mesh_normals, mp_mesh_points, mp_mesh_render and
+ * mp_volume_keep_largest are
  * each the batched call with one frame: mp_<call>(..., p, ...) is mp_<call>_batch(..., 1, &p, ..., gate = NULL), with
  * the same argument tests, scratch and launches; only the name at the head of an mp_last_error message is that of the
  * entry called.  The rules of the batched calls are therefore the rules of both forms:
@@ -538,6 +539,61 @@ int mp_mesh_normals_batch(mp_ctx *ctx, int n_frames, const float *const *verts, 
                           float *const *normals, mp_stream stream);
 int mp_mesh_points_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
                          const int32_t *const *counts, float *const *points, int32_t *const *count_out,
+                         mp_stream stream);
+
+/* ---- mesh rasteriser (no counterpart in the reference, which renders through PyOpenGL and an X server) ----------
+ * A z-buffered picture of a triangle mesh as mp_marching_cubes leaves it, for any camera and any image size, defined
+ * bit for bit (integer atomics only: the picture is a pure function of its inputs, the same bits in every run).
+ * Per image: verts f32 [max_verts,3], faces int32 [max_faces,3], counts (device int32[2]; only min(counts, capacity)
+ * rows are read), a camera calib (12 floats, the rows of [R|t]), an MP_PROJ_* projection and the size H x W (1..4096).
+ *   1 Project.  (x, y, z) of a vertex are the bits mp_orthogonal / mp_perspective give for it (the same device code).
+ *   2 Snap to 1/256 pixel, in f32 and in this order: u = ((x + 1.0f) * (0.5f * H)) * 256.0f, v likewise with y and W;
+ *     X = rintf(u), Y = rintf(v) as integers.  Pixel (i, j) has its centre at (256 i + 128, 256 j + 128): x runs along
+ *     the FIRST image index, as in mp_paint's canvas image[X, Y, :], so the result feeds mp_visualize unchanged, and
+ *     with the identity camera and H = W = R pixel i is lattice column i.  A vertex is invalid if u, v or z is not
+ *     finite or |u| or |v| exceeds 2^22; a face with an invalid vertex, or with an index outside [0, vertices), is
+ *     skipped whole.  There is NO clipping (a face with a vertex behind a perspective camera is drawn from its
+ *     projected vertices as they are) and NO back-face culling.
+ *   3 Cover, in int64: area2 = (X1-X0)(Y2-Y0) - (Y1-Y0)(X2-X0).  Zero: the face is skipped.  Negative: the second and
+ *     third vertex are exchanged with everything attached to them, and area2 negated.  At a pixel centre P,
+ *     e0 = edge(V1,V2,P), e1 = edge(V2,V0,P), e2 = edge(V0,V1,P) with edge(A,B,P) = (Bx-Ax)(Py-Ay) - (By-Ay)(Px-Ax).
+ *     P is covered iff every e_k > 0, or e_k == 0 on an edge A->B with dy < 0 or (dy == 0 and dx > 0), d = B - A (a
+ *     top-left rule: two faces sharing an edge never both cover a centre on it, and never both miss it).
+ *   4 Interpolate, screen-space affine (NOT perspective-correct): w_k = (float)e_k / (float)area2 (int64 -> f32 rounds
+ *     to nearest, the division is IEEE); depth = (w0*z0 + w1*z1) + w2*z2 without FMA; a fragment with a non-finite
+ *     depth is dropped.  Attributes take the same expression per channel, then clamp(a * scale + bias, lo, hi) as
+ *     mp_paint (normals: 0.5, 0.5, 0, 1; raw netC predictions: 0.5, 0.5, -inf, inf; finished colours: 1, 0, -inf, inf);
+ *     attr is [3,max_verts] when channel_major != 0, else [max_verts,3].
+ *   5 Resolve.  Per pixel the fragment with the nearest depth wins, among equal depths the smallest face index:
+ *     MP_NEAREST_MAX_Z (the viewer sits at +z: what mp_forward_vertices(MP_DIR_FRONT) sees) or MP_NEAREST_MIN_Z (depth
+ *     is a distance, the usual perspective case; it compares -depth, an exact sign flip).  One 64-bit integer maximum
+ *     per fragment of key = orderable(depth) << 32 | (0xFFFFFFFF - face), orderable(b) = b ^ (b >> 31 ? 0xFFFFFFFF :
+ *     0x80000000); a cleared key of 0 means "no fragment".
+ * Outputs, any of which may be NULL but not all three: image f32 [H,W,3] (uncovered pixels = background; the
+ * reference's canvas is 1.0), depth f32 [H,W] (the winner's unflipped depth, +0.0 where uncovered), face_id int32
+ * [H,W] (-1 where uncovered).  attr == NULL requires image == NULL.  calib is a HOST float[12].
+ *   Four launches and one memset (raster.hip).  Scratch from the stream's arena: 8 H W (keys, padded to 256 in all) +
+ * 16 max_verts (snapped vertices) + 4 max_faces (the list of faces too large for one thread) bytes per image, + 256.
+ * MP_ERR_ARG: h or w outside 1..4096, an unknown projection or nearest, a NULL or not 4-byte aligned buffer, all three
+ * outputs NULL, image without attr; MP_ERR_UNSUPPORTED: capacities beyond 2^31 / 3.  Asynchronous, nothing
+ * synchronised.  The batched call with one frame and one view. */
+enum { MP_NEAREST_MAX_Z = 0, MP_NEAREST_MIN_Z = 1 };
+int mp_mesh_render(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                   const int32_t *counts, const float *attr, int channel_major, const float *calib /*host[12]*/,
+                   int projection, int nearest, int h, int w, float scale, float bias, float lo, float hi,
+                   float background, float *image, float *depth, int32_t *face_id, mp_stream stream);
+/* The call above over n_frames meshes of one capacity times n_views cameras each, n_frames * n_views in
+ * 1..mp_max_frames() (else MP_ERR_ARG), in ONE set of launches.  verts / faces / counts / attr / image / depth /
+ * face_id are HOST arrays of n_frames device pointers (attr, image, depth, face_id may be NULL as a whole); frame f's
+ * outputs hold its views back to back: image[f] [n_views,H,W,3], depth[f] and face_id[f] [n_views,H,W].  calibs is a
+ * HOST float[n_frames * n_views * 12], frame-major.  Image (f, v) equals mp_mesh_render on frame f's mesh with
+ * camera (f, v) BIT FOR BIT.  A frame whose counts read 0 (a gated-off frame of mp_marching_cubes_batch) gets pure
+ * background.  Refusals as above, for a buffer of any frame, each with an mp_last_error message. */
+int mp_mesh_render_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                         const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts,
+                         const float *const *attr, int channel_major, int n_views, const float *calibs,
+                         int projection, int nearest, int h, int w, float scale, float bias, float lo, float hi,
+                         float background, float *const *image, float *const *depth, int32_t *const *face_id,
                          mp_stream stream);
 
 /* The largest connected body of an occupancy volume [R,R,R] (no counterpart in the reference; the clean-up in front

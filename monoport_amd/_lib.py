@@ -90,6 +90,8 @@ PLAN_CONVK, PLAN_GN_APPLY, PLAN_CONV3X3, PLAN_CONV1X1, PLAN_AVGPOOL2, PLAN_UPSAM
 PROJ_ORTHOGONAL, PROJ_PERSPECTIVE = 0, 1
 # MP_NORMALS_* modes of mp_mesh_normals (include/monoport_hip.h)
 NORMALS_REFERENCE, NORMALS_ACCUMULATE = 0, 1
+# MP_NEAREST_* modes of mp_mesh_render (include/monoport_hip.h)
+NEAREST_MAX_Z, NEAREST_MIN_Z = 0, 1
 # MP_CONN_* connectivities of mp_volume_keep_largest (include/monoport_hip.h)
 CONN_6, CONN_26 = 6, 26
 MAX_VIEWS = 8  # MP_MAX_VIEWS: views per mp_query_views / mp_mlp_forward_views call
@@ -176,6 +178,10 @@ SIGNATURES = {
                                         c_vp, c_vp, c_vp]),
     "mp_mesh_normals_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_vp, c_vp]),
     "mp_mesh_points_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "mp_mesh_render": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, _pf32, c_int, c_int, c_int, c_int, c_f32,
+                               c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    "mp_mesh_render_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_int, _pf32, c_int, c_int,
+                                     c_int, c_int, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "mp_volume_keep_largest": (c_int, [c_vp, c_vp, c_int, c_f32, c_int, c_f32, c_vp, c_vp, c_vp]),
     "mp_volume_keep_largest_batch": (c_int, [c_vp, c_int, c_vp, c_int, c_f32, c_int, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "mp_group_norm": (c_int, [c_vp, c_vp, c_int, c_int, c_i64, c_int, c_vp, c_vp, c_f32, c_int, c_vp,

@@ -414,6 +414,44 @@ static int mesh_points_checked(mp_ctx *ctx, const char *who, int n_frames, const
                                   (hipStream_t)stream);
 }
 
+static int mesh_render_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *verts, int64_t max_verts,
+                               const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts,
+                               const float *const *attr, int channel_major, int n_views, const float *calibs,
+                               int projection, int nearest, int h, int w, float scale, float bias, float lo, float hi,
+                               float background, float *const *image, float *const *depth, int32_t *const *face_id,
+                               mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (n_frames < 1 || n_views < 1 || (long long)n_frames * n_views > kMaxFrames)
+    return fail(ctx, MP_ERR_ARG, "%s: 1..%d images (frames x views) per call, got %d x %d", who, kMaxFrames, n_frames,
+                n_views);
+  if (h < 1 || h > 4096 || w < 1 || w > 4096)
+    return fail(ctx, MP_ERR_ARG, "%s: image size %d x %d outside 1..4096", who, h, w);
+  if (projection != MP_PROJ_ORTHOGONAL && projection != MP_PROJ_PERSPECTIVE)
+    return fail(ctx, MP_ERR_ARG, "%s: unknown projection mode %d", who, projection);
+  if (nearest != MP_NEAREST_MAX_Z && nearest != MP_NEAREST_MIN_Z)
+    return fail(ctx, MP_ERR_ARG, "%s: nearest must be MP_NEAREST_MAX_Z / _MIN_Z, got %d", who, nearest);
+  if (!image && !depth && !face_id) return fail(ctx, MP_ERR_ARG, "%s: no output requested", who);
+  if (image && !attr) return fail(ctx, MP_ERR_ARG, "%s: an image needs attr", who);
+  if (!counts || !calibs || max_verts < 0 || max_faces < 0 || (max_verts > 0 && !verts) || (max_faces > 0 && !faces))
+    return bad_argument(ctx, who);
+  if (max_verts > 0x7fffffffLL / 3 || max_faces > 0x7fffffffLL / 3)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: capacities beyond 2^31 / 3 need 64-bit indices", who);
+  if (max_verts == 0) verts = nullptr;  // rows of a capacity of 0 are not looked at
+  if (max_faces == 0) faces = nullptr;
+  int rc = check_frames(ctx, who, n_frames, nullptr, counts, verts, faces, max_verts > 0 ? attr : nullptr, image, depth,
+                        face_id);
+  if (rc != MP_OK) return rc;
+  DeviceGuard g(ctx->device);
+  void *scratch = nullptr;
+  rc = ensure_scratch(ctx, (hipStream_t)stream,
+                      mesh_render_scratch_bytes(n_frames * n_views, max_verts, max_faces, h, w), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_mesh_render_batch(ctx, scratch, n_frames, n_views, verts, max_verts, faces, max_faces, counts, attr,
+                                  channel_major, calibs, projection, nearest, h, w, scale, bias, lo, hi, background,
+                                  image, depth, face_id, (hipStream_t)stream);
+}
+
 static int keep_largest_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *volume, int r,
                                 float level, int connectivity, float fill, float *const *out, int32_t *const *stats,
                                 const int32_t *const *gate, mp_stream stream) {
@@ -1250,6 +1288,27 @@ int mp_mesh_normals(mp_ctx *ctx, const float *verts, int64_t max_verts, const in
                     const int32_t *counts, int mode, float *normals, mp_stream stream) {
   return mesh_normals_checked(ctx, "mp_mesh_normals", 1, &verts, max_verts, &faces, max_faces, &counts, mode, &normals,
                               stream);
+}
+
+int mp_mesh_render(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                   const int32_t *counts, const float *attr, int channel_major, const float *calib, int projection,
+                   int nearest, int h, int w, float scale, float bias, float lo, float hi, float background,
+                   float *image, float *depth, int32_t *face_id, mp_stream stream) {
+  return mesh_render_checked(ctx, "mp_mesh_render", 1, &verts, max_verts, &faces, max_faces, &counts,
+                             attr ? &attr : nullptr, channel_major, 1, calib, projection, nearest, h, w, scale, bias, lo,
+                             hi, background, image ? &image : nullptr, depth ? &depth : nullptr,
+                             face_id ? &face_id : nullptr, stream);
+}
+
+int mp_mesh_render_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                         const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts,
+                         const float *const *attr, int channel_major, int n_views, const float *calibs,
+                         int projection, int nearest, int h, int w, float scale, float bias, float lo, float hi,
+                         float background, float *const *image, float *const *depth, int32_t *const *face_id,
+                         mp_stream stream) {
+  return mesh_render_checked(ctx, "mp_mesh_render_batch", n_frames, verts, max_verts, faces, max_faces, counts, attr,
+                             channel_major, n_views, calibs, projection, nearest, h, w, scale, bias, lo, hi, background,
+                             image, depth, face_id, stream);
 }
 
 int mp_mesh_normals_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,

@@ -5,6 +5,7 @@ current HIP stream and returns ordinary ``torch.Tensor`` objects that outlive th
 ownership rule of the reference's stage pipeline (RTL/dataloader.py:1048-1054).
 """
 import ctypes
+import math
 import os
 import threading
 
@@ -1260,6 +1261,144 @@ def mesh_points_raw_batch(verts, counts, out=None):
     meshes: per mesh (points [3,max_v], count int32[1]), views of two tensors (``out`` = (points [n,3,max_v],
     count [n,1]) if given; else the points start as zeros, as ``mesh_points_raw``'s).  No host sync."""
     return _mesh_points("mesh_points_raw_batch", verts, counts, out)
+
+
+# MP_NEAREST_* (include/monoport_hip.h): which depth is in front
+NEAREST_MODES = {"max": _lib.NEAREST_MAX_Z, "min": _lib.NEAREST_MIN_Z}
+RENDER_MAX_SIZE = 4096  # mp_mesh_render: H, W in 1..4096
+
+
+def _nearest(mode):
+    if isinstance(mode, str):
+        if mode not in NEAREST_MODES:
+            raise ValueError("nearest must be one of %s, got %r" % (sorted(NEAREST_MODES), mode))
+        return NEAREST_MODES[mode]
+    mode = int(mode)
+    if mode not in NEAREST_MODES.values():
+        raise ValueError("unknown nearest mode %d" % mode)
+    return mode
+
+
+def _render_size(who, res):
+    """``res`` (an int, or (H, W)) -> (H, W), each in 1..RENDER_MAX_SIZE."""
+    h, w = (res, res) if isinstance(res, (int, np.integer)) else tuple(res)
+    h, w = int(h), int(w)
+    if not (1 <= h <= RENDER_MAX_SIZE and 1 <= w <= RENDER_MAX_SIZE):
+        raise ValueError("%s: image size %d x %d outside 1..%d" % (who, h, w, RENDER_MAX_SIZE))
+    return h, w
+
+
+def _view_calibs(who, calibs):
+    """The cameras of one mesh ([4,4], [3,4] or [n_views,>=3,4]; tensor or array) -> host float32 [n_views,12], the
+    rows of [R|t].  The C side reads them on the host: a device tensor costs a copy back."""
+    c = calibs.detach().cpu().numpy() if torch.is_tensor(calibs) else np.asarray(calibs)
+    c = np.asarray(c, np.float32)
+    if c.ndim == 2:
+        c = c[None]
+    if c.ndim != 3 or c.shape[0] < 1 or c.shape[1] < 3 or c.shape[2] != 4:
+        raise ValueError("%s: calibs must be [4,4], [3,4] or [n_views,>=3,4], got %s" % (who, tuple(c.shape)))
+    return np.ascontiguousarray(c[:, :3, :]).reshape(c.shape[0], 12)
+
+
+def _mesh_render(who, verts, faces, counts, attrs, calibs, res, projection, nearest, channel_major, scale, bias, lo, hi,
+                 background, out, capacity=None):
+    """What mesh_render_raw and mesh_render_raw_batch do: per mesh (image [n_views,H,W,3] or None, depth
+    [n_views,H,W], face [n_views,H,W]), rows of three tensors.  ``capacity`` = (max_v, max_f): the meshes' tensors may
+    then be shorter than it (each at least as long as its own counts say; row-major attributes only)."""
+    n = len(verts)
+    if capacity is None:
+        n, max_v, max_f, dev = _mesh_frames(who, verts, faces, counts)
+    else:
+        if n == 0 or len(faces) != n or len(counts) != n:
+            raise ValueError("%s wants at least one mesh, and faces and counts for each" % who)
+        for f in range(n):
+            _mesh_buffers(verts[f], faces[f], counts[f])
+        (max_v, max_f), dev = capacity, verts[0].device
+        if channel_major or any(v.device != dev for v in verts):
+            raise ValueError("%s: meshes of unequal capacity take row-major attributes on one device" % who)
+    h, w = _render_size(who, res)
+    proj, near = _projection(projection), _nearest(nearest)
+    cams = [_view_calibs(who, c) for c in _calib_list(calibs, n, who)]
+    nv = cams[0].shape[0]
+    if any(c.shape[0] != nv for c in cams):
+        raise ValueError("%s: every mesh of a call takes the same number of views" % who)
+    cams = np.stack(cams)  # [n, nv, 12]
+    if attrs is not None:
+        if len(attrs) != n:
+            raise ValueError("%s: %d meshes, %d attribute buffers" % (who, n, len(attrs)))
+        for f, a in enumerate(attrs):
+            rows = verts[f].shape[0]
+            if (a.dtype != torch.float32 or a.device != dev or not a.is_contiguous()
+                    or tuple(a.shape) != ((3, rows) if channel_major else (rows, 3))):
+                raise ValueError("%s: attr must be a contiguous float32 %s tensor on the mesh's device"
+                                 % (who, "[3,V]" if channel_major else "[V,3]"))
+    if out is None:
+        image = None if attrs is None else torch.empty((n, nv, h, w, 3), dtype=torch.float32, device=dev).unbind(0)
+        depth = torch.empty((n, nv, h, w), dtype=torch.float32, device=dev).unbind(0)
+        face = torch.empty((n, nv, h, w), dtype=torch.int32, device=dev).unbind(0)
+    else:
+        image, depth, face = out
+        if image is None and depth is None and face is None:
+            raise ValueError("%s: out names no output" % who)
+        if image is not None and attrs is None:
+            raise ValueError("%s: an image needs attr" % who)
+        if image is not None:
+            image = _frame_rows(who, "out[0] (image)", image, n, (nv, h, w, 3), torch.float32, dev)
+        if depth is not None:
+            depth = _frame_rows(who, "out[1] (depth)", depth, n, (nv, h, w), torch.float32, dev)
+        if face is not None:
+            face = _frame_rows(who, "out[2] (face)", face, n, (nv, h, w), torch.int32, dev)
+    ctx = get_context(dev)
+    vstep = min(nv, MAX_FRAMES)  # image slots of a call: frames x views <= MAX_FRAMES
+    fstep = MAX_FRAMES // vstep
+    hold = None  # what an empty tensor (no address) passes in its place: never read
+    if any(t.numel() == 0 for rows in (verts, faces, attrs or ()) for t in rows):
+        hold = torch.zeros(4, dtype=torch.float32, device=dev)
+
+    def ptrs(rows, f0, f1, v0=None):
+        if rows is None:
+            return None
+        return _ptr_array([(hold if r.numel() == 0 else r) if v0 is None else r[v0:] for r in rows[f0:f1]])
+
+    for v0 in range(0, nv, vstep):
+        v1 = min(v0 + vstep, nv)
+        for f0 in range(0, n, fstep):
+            f1 = min(f0 + fstep, n)
+            cal = np.ascontiguousarray(cams[f0:f1, v0:v1]).reshape(-1)
+            ctx.check(ctx.lib.mp_mesh_render_batch(
+                ctx.handle, f1 - f0, ptrs(verts, f0, f1), max_v, ptrs(faces, f0, f1), max_f, ptrs(counts, f0, f1),
+                ptrs(attrs, f0, f1), int(channel_major), v1 - v0, cal.ctypes.data_as(_lib._pf32), proj, near, h, w,
+                float(scale), float(bias), float(lo), float(hi), float(background), ptrs(image, f0, f1, v0),
+                ptrs(depth, f0, f1, v0), ptrs(face, f0, f1, v0), _stream(verts[0])), "mp_mesh_render_batch")
+    return [(None if image is None else image[f], None if depth is None else depth[f],
+             None if face is None else face[f]) for f in range(n)]
+
+
+def mesh_render_raw(verts, faces, counts, attr, calibs, res, projection="orthogonal", nearest="max",
+                    channel_major=False, scale=1.0, bias=0.0, lo=-math.inf, hi=math.inf, background=1.0, out=None):
+    """mp_mesh_render_batch with one mesh: the z-buffered picture of verts [max_v,3] f32, faces [max_f,3] int32, counts
+    int32[2] on device (as ``marching_cubes_raw`` returns them) under every camera of ``calibs`` ([4,4], [3,4] or
+    [n_views, ...], read on the host) at ``res`` (an int or (H, W)), defined bit for bit in include/monoport_hip.h.
+    ``attr``: None, or per-vertex values [max_v,3] ([3,max_v] with ``channel_major``) painted as clamp(a * scale + bias,
+    lo, hi).  ``nearest``: "max" (the viewer sits at +z, what ``forward_vertices("front")`` sees) or "min" (depth is a
+    distance).  Returns (image [n_views,H,W,3] or None without ``attr``, depth [n_views,H,W], face int32
+    [n_views,H,W]); uncovered pixels hold ``background``, +0.0 and -1.  ``out``: (image, depth, face) buffers to write
+    into; an entry None is an output not computed.  No clipping, no back-face culling, screen-space interpolation.
+    No host sync."""
+    return _mesh_render("mesh_render_raw", [verts], [faces], [counts], None if attr is None else [attr], [calibs], res,
+                        projection, nearest, channel_major, scale, bias, lo, hi, background,
+                        None if out is None else tuple(None if o is None else [o] for o in out))[0]
+
+
+def mesh_render_raw_batch(verts, faces, counts, attrs, calibs, res, projection="orthogonal", nearest="max",
+                          channel_major=False, scale=1.0, bias=0.0, lo=-math.inf, hi=math.inf, background=1.0, out=None):
+    """mp_mesh_render_batch: ``[mesh_render_raw(v, f, c, a, cal, res, ...) for ...]`` (lists of per-mesh device tensors
+    of one capacity, ``attrs`` None or a list, ``calibs`` one camera set per mesh, all of one n_views) in ONE set of
+    launches per MAX_FRAMES images (meshes x views); bit for bit what the per-mesh call gives.  A mesh whose counts
+    read 0 gives pure background.  ``out``: (image [n,n_views,H,W,3], depth [n,n_views,H,W], face [n,n_views,H,W])
+    to write into, entries None = not computed.  No host sync."""
+    return _mesh_render("mesh_render_raw_batch", verts, faces, counts, attrs, calibs, res, projection, nearest,
+                        channel_major, scale, bias, lo, hi, background, out)
 
 
 # MP_CONN_* (include/monoport_hip.h): face neighbours / face, edge and corner neighbours

@@ -308,6 +308,82 @@ def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), 
     return meshes
 
 
+MeshRender = collections.namedtuple("MeshRender", ["image", "depth", "face"])
+MeshRender.__doc__ = """Picture of ``render_mesh``: image [H,W,3] f32 (None without shading), depth [H,W] f32 (+0.0 where
+nothing is seen), face [H,W] int32 (-1 where nothing is seen); with a set of cameras each has a leading [n_views]."""
+
+SHADES = ("colors", "normals", None)
+
+
+def _shade_attr(who, mesh, shade):
+    """The per-vertex values a ``shade`` paints and their (scale, bias, lo, hi): finished colours as they are, normals
+    as main.py:220-225 paints them."""
+    if shade not in SHADES:
+        raise ValueError("%s: shade must be one of %s, got %r" % (who, list(SHADES), shade))
+    if shade is None:
+        return None, (1.0, 0.0, -np.inf, np.inf)
+    attr = mesh.colors if shade == "colors" else mesh.normals
+    if attr is None:
+        raise ValueError("%s: shade=%r, but the mesh has no %s" % (who, shade, shade))
+    return attr, ((1.0, 0.0, -np.inf, np.inf) if shade == "colors" else (0.5, 0.5, 0.0, 1.0))
+
+
+def _single_camera(calibs):
+    return (calibs.dim() if torch.is_tensor(calibs) else np.asarray(calibs).ndim) == 2
+
+
+@torch.no_grad()
+def render_mesh(mesh, calibs, res=257, shade="colors", projection="orthogonal", nearest="max", background=1.0):
+    """The z-buffered picture of a ``Mesh`` on the device (monoport_amd extension; ``ops.mesh_render_raw``): any camera
+    ``calibs`` ([4,4] / [3,4], the convention of the queries; or [n_views, ...] for several pictures in one set of
+    launches), any size ``res`` (int or (H, W)).  ``shade``: "colors" (the mesh's colours), "normals" (its normals * 0.5
+    + 0.5 clamped to [0,1], as the reference paints them) or None (depth and face ids only).  x runs along the first
+    image index as in the painted canvas, so a square image feeds ``visulization`` unchanged.  Returns a
+    ``MeshRender``; None for ``mesh is None``.  No host sync."""
+    if mesh is None:
+        return None
+    return render_mesh_many([mesh], calibs, res, shade, projection, nearest, background)[0]
+
+
+@torch.no_grad()
+def render_mesh_many(meshes, calibs, res=257, shade="colors", projection="orthogonal", nearest="max", background=1.0):
+    """``[render_mesh(m, calibs, ...) for m in meshes]`` in one set of launches per ops.MAX_FRAMES pictures (meshes x
+    views), the same bits.  ``calibs``: one camera set for all meshes (a tensor / array), or a list with one camera set
+    per mesh (those of ``None`` meshes are not looked at; all of one n_views).  ``None`` meshes give ``None``.  The
+    meshes may differ in size: the per-mesh counts are made on the device from the tensors' shapes and the capacity of
+    the call is the largest of them (no row at or beyond a mesh's counts is touched).  No host sync."""
+    who = "render_mesh_many"
+    meshes = list(meshes)
+    idx = [i for i, m in enumerate(meshes) if m is not None]
+    out = [None] * len(meshes)
+    if not idx:
+        return out
+    if isinstance(calibs, (list, tuple)):
+        if len(calibs) != len(meshes):
+            raise ValueError("%s: %d meshes, %d camera sets" % (who, len(meshes), len(calibs)))
+        cams = [calibs[i] for i in idx]
+    else:
+        cams = [calibs] * len(idx)
+    live = [meshes[i] for i in idx]
+    shaded = [_shade_attr(who, m, shade) for m in live]
+    scale, bias, lo, hi = shaded[0][1]
+    dev = live[0].verts.device
+    verts = [m.verts.contiguous() for m in live]
+    faces = [m.faces.contiguous() for m in live]
+    attrs = None if shade is None else [ops._f32c(a) for a, _ in shaded]
+    sizes = torch.tensor([[v.shape[0], f.shape[0]] for v, f in zip(verts, faces)], dtype=torch.int32)
+    if dev.type == "cuda":
+        sizes = sizes.pin_memory().to(dev, non_blocking=True)
+    capacity = (max(v.shape[0] for v in verts), max(f.shape[0] for f in faces))
+    raws = ops._mesh_render(who, verts, faces, list(sizes.unbind(0)), attrs, cams, res, projection, nearest, False,
+                            scale, bias, lo, hi, background, None, capacity=capacity)
+    for i, cam, (image, depth, face) in zip(idx, cams, raws):
+        if _single_camera(cam):
+            image, depth, face = (None if t is None else t[0] for t in (image, depth, face))
+        out[i] = MeshRender(image, depth, face)
+    return out
+
+
 @torch.no_grad()
 def prepare_inputs(segm, mean, std, with_color=True):
     """The two "update input by removing bg" processors of RTL/main.py:352-364 as one HIP kernel:

@@ -23,6 +23,14 @@ with a mesh per frame without / with ``"clean": 6``.  ``--clean --no-slot`` leav
 
     python tools/mesh_timing.py --clean [--passes 5] [--out profiles/keep_largest_timing.json]
 
+``--render`` measures the mesh rasteriser (profiles/mesh_render_timing.json): on the same volume's mesh (normals
+shading), recon.render_mesh / render_mesh_many at 257^2 and 1024^2, 1 and 4 cameras, 1 and 20 meshes per call, in
+milliseconds per picture; beside them the existing way to one picture of the volume (ops.forward_vertices_raw +
+ops.paint, one axis direction at the volume's resolution) and what one more reconstruction of the volume costs (what a
+second view cost before).
+
+    python tools/mesh_timing.py --render [--passes 5] [--out profiles/mesh_render_timing.json]
+
 The protocol of tools/recon_views_timing.py: after a warm-up of all, the passes alternate; a pass is `meshes`
 meshes, wall clock around a final stream sync.  Prints (and writes) one JSON line: per way the median, minimum and
 maximum time per mesh (ms) over the passes.  The verdict fields restate what to check: (b) not slower than (a) by
@@ -58,9 +66,11 @@ def main():
     ap.add_argument("--batched", action="store_true", help="the batched chain and the slot's MESH_BATCH settings")
     ap.add_argument("--clean", action="store_true", help="what keeping the largest connected body costs")
     ap.add_argument("--no-slot", action="store_true", help="with --clean: leave the frame slot out")
+    ap.add_argument("--render", action="store_true", help="the mesh rasteriser against the visible-surface picture")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "keep_largest_timing.json" if a.clean else
+        a.out = os.path.join(ROOT, "profiles", "mesh_render_timing.json" if a.render else
+                             "keep_largest_timing.json" if a.clean else
                              "mesh_batch_timing.json" if a.batched else "mesh_timing.json")
     mlp = ops.PackedMLP.from_layers(DEV, syn.body_mlp("G", noise=0.05, seed=1), 1)
     fh = ops.pack_features(torch.from_numpy(syn.body_feat(256, 128, 128, 2))[None].to(DEV))
@@ -68,6 +78,9 @@ def main():
     vol, status = ops.recon(mlp, fh, cal, syn.Z_SCALE, BMIN, BMAX, RES)
     assert int(status[0].item()) == 1
     vol = vol[None, None]
+    if a.render:
+        write(a, render(a, vol, lambda: ops.recon(mlp, fh, cal, syn.Z_SCALE, BMIN, BMAX, RES)))
+        return
     netC = PIFuNetC()
     with torch.no_grad():
         for i, (w, b) in enumerate(syn.rand_mlp("C", 61, 2.0)):
@@ -184,6 +197,54 @@ def batched(a, vol, netC, feat_C, calib):
         res["many_over_calls"] = round(res["many"]["median_ms"] / res["calls"]["median_ms"], 4)
         out["n%d" % n] = res
         out["vertices"], out["faces"] = int(one.verts.shape[0]), int(one.faces.shape[0])
+    return out
+
+
+def render(a, vol, reconstruct, n=20):
+    """Milliseconds per picture of the mesh rasteriser, of forward_vertices + paint and of one more reconstruction."""
+    mesh = reconstruct_mesh(vol, 0.5, BMIN, BMAX, normals="accumulate")
+    cams = torch.cat([torch.eye(4)[None]] + [recon.pifu_calib(*syn.scene_camera(30 * k), device="cpu")
+                                             for k in (1, 2, 3)])
+    r = vol.shape[-1]
+
+    def surface_picture():
+        for _ in range(n):
+            x, y, _, norm, count = ops.forward_vertices_raw(vol, "front")
+            ops.paint(x, y, norm, False, count, r, 0.5, 0.5, 0.0, 1.0)
+
+    ways = {"forward_vertices_paint_%d" % r: surface_picture,
+            "reconstruction": lambda: [reconstruct() for _ in range(n)]}
+    per = {name: n for name in ways}
+    for size in (257, 1024):
+        for views in (1, 4):
+            c = cams[0] if views == 1 else cams[:views]
+            name = "render_%d_views%d" % (size, views)
+            ways[name + "_frames1"] = (lambda c=c, size=size: [
+                recon.render_mesh(mesh, c, res=size, shade="normals") for _ in range(n)])
+            ways[name + "_frames%d" % n] = (lambda c=c, size=size: recon.render_mesh_many(
+                [mesh] * n, c, res=size, shade="normals"))
+            per[name + "_frames1"] = per[name + "_frames%d" % n] = n * views
+    out = {"resolutions": RES, "passes": a.passes, "unit": "ms per picture", "shade": "normals",
+           "vertices": int(mesh.verts.shape[0]), "faces": int(mesh.faces.shape[0]), "pictures_per_pass": per}
+    one = recon.render_mesh(mesh, cams[0], res=r, shade="normals")
+    x, y, _, _ = recon.forward_vertices(vol, "front")
+    seen = torch.zeros((r, r), dtype=torch.bool, device=vol.device)
+    seen[x, y] = True
+    out["silhouette_pixels"] = int(seen.sum().item())
+    out["silhouette_differs_from_forward_vertices"] = int(((one.face >= 0) != seen).sum().item())
+    for fn in ways.values():  # warm-up of all
+        fn()
+    torch.cuda.synchronize()
+    times = {name: [] for name in ways}
+    for _ in range(a.passes):
+        for name, fn in ways.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = fn()
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) * 1e3 / per[name])
+            del res
+    out.update({name: stats(t) for name, t in times.items()})
     return out
 
 
