@@ -415,8 +415,8 @@ int mp_scatter_nodes(mp_ctx *ctx, const uint32_t *packed, const int32_t *count, 
                      int r, const float *values, float *volume, mp_stream stream);
 
 /* ---- per-frame and batched forms of the mesh and render calls -------------------------------------------------------
- * mp_forward_vertices, mp_paint, mp_marching_cubes, mp_mesh_normals, mp_mesh_points, mp_mesh_render and
- * mp_volume_keep_largest are
+ * mp_forward_vertices, mp_paint, mp_marching_cubes, mp_mesh_simplify, mp_mesh_normals, mp_mesh_points, mp_mesh_render
+ * and mp_volume_keep_largest are
  * each the batched call with one frame: mp_<call>(..., p, ...) is mp_<call>_batch(..., 1, &p, ..., gate = NULL), with
  * the same argument tests, scratch and launches; only the name at the head of an mp_last_error message is that of the
  * entry called.  The rules of the batched calls are therefore the rules of both forms:
@@ -540,6 +540,53 @@ int mp_mesh_normals_batch(mp_ctx *ctx, int n_frames, const float *const *verts, 
 int mp_mesh_points_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
                          const int32_t *const *counts, float *const *points, int32_t *const *count_out,
                          mp_stream stream);
+
+/* ---- mesh simplification (no counterpart in the reference): the level-of-detail dial of the mesh chain -------------
+ * Vertex clustering of a triangle mesh as mp_marching_cubes leaves it, between marching cubes and the normals /
+ * colours.  Defined bit for bit (integer atomics only: the result is a pure function of its inputs, the same bits in
+ * every run).  Per mesh: verts f32 [max_verts,3], faces int32 [max_faces,3], counts (device int32[2]; only nv =
+ * min(counts[0], max_verts) vertices and nf = min(counts[1], max_faces) faces are read), a box b_min / b_max (HOST
+ * float[3]) and n, the cells per axis (the same for x, y and z).
+ *   1 Cell.  Per axis a, on the host in f32: inv_a = (float)n / (b_max_a - b_min_a).  On the device, in f32 and in this
+ *     order: t_a = (v_a - b_min_a) * inv_a; c_a = clamp((int)floorf(t_a), 0, n - 1) (the clamp holds for every t, +-inf
+ *     included: a vertex outside the box belongs to the border cell); key = (c_z * n + c_y) * n + c_x.  A vertex is
+ *     invalid if a coordinate is not finite or |v_a| >= 32768; it joins no cell.
+ *   2 New vertices: one per occupied cell, in ascending key order.  vmap[v] = new index of old vertex v, -1 for an
+ *     invalid one; rows of vmap at or beyond nv are left untouched.
+ *   3 Position: the members' mean in fixed point.  Q_a = llrint((double)v_a * 1048576.0) (ties to even), S_a = the
+ *     int64 sum of Q_a over the members, m = their number, out_a = (float)((double)S_a / ((double)m * 1048576.0)):
+ *     both int64 -> double conversions round to nearest-even, the division is IEEE.  With max_verts <= 2^27 the sum
+ *     cannot overflow; a larger max_verts is MP_ERR_UNSUPPORTED.
+ *   4 Faces.  A face with an index outside [0, nv) or with an invalid vertex is dropped; the others are mapped through
+ *     vmap, and a face with two equal mapped indices is dropped.  Survivors keep their input order and their corner
+ *     order (the winding is kept).  Two faces that land on the same three vertices BOTH stay: removing such pairs is
+ *     not part of this call (every undirected edge of a closed input then still lies in an even number of faces).  An
+ *     output vertex that no surviving face names stays (n = 1: one vertex, no faces; mp_mesh_normals gives it 0).
+ *   5 Outputs: verts_out f32 [max_verts,3] and faces_out int32 [max_faces,3] (the capacities of the inputs: the output
+ *     is never larger, nothing truncates here), counts_out (device int32[2]) = new vertices and faces, vmap int32
+ *     [max_verts] or NULL.  Rows beyond the new counts are left untouched.  Outputs must not alias inputs (MP_ERR_ARG).
+ *     counts reading {0, 0} (a gated-off frame of mp_marching_cubes_batch) gives counts_out = {0, 0} and touches
+ *     nothing else.
+ *   Nine launches and one memset (simplify.hip), asynchronous, nothing synchronised.  Scratch from the stream's arena:
+ * 4 n^3 + 4 ceil(n^3 / 1024) + 32 max_verts + 4 max_faces + 4 ceil(max_faces / 1024) bytes per mesh, + 256 (8.4 MB of
+ * cell table at n = 128, 537 MB at 512).
+ * MP_ERR_ARG: n outside 1..512; b_max_a <= b_min_a, a non-finite bound, or a box so thin that inv_a is not finite; a
+ * NULL or not 4-byte aligned buffer (rows of a capacity of 0 may be NULL); an output that shares a byte with an input.
+ * MP_ERR_UNSUPPORTED: max_verts > 2^27, max_faces > 2^31 / 3.  max_verts == 0: MP_OK, counts_out zeroed.  Each refusal
+ * leaves an mp_last_error message.  The batched call with one frame. */
+int mp_mesh_simplify(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                     const int32_t *counts, const float *b_min /*host[3]*/, const float *b_max /*host[3]*/, int n,
+                     float *verts_out, int32_t *faces_out, int32_t *counts_out, int32_t *vmap, mp_stream stream);
+/* The call above over n_frames (1..mp_max_frames(), else MP_ERR_ARG) meshes of one capacity, with one box and one n
+ * for all, in ONE set of launches.  verts / faces / counts / verts_out / faces_out / counts_out / vmap are HOST arrays
+ * of n_frames device pointers (vmap may be NULL as a whole).  Frame f's outputs equal those of mp_mesh_simplify on
+ * frame f's inputs BIT FOR BIT.  No output of any frame may alias an input of any frame.  Scratch: n_frames times the
+ * per-mesh figure.  Refusals as above, for a buffer of any frame. */
+int mp_mesh_simplify_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                           const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts,
+                           const float *b_min /*host[3]*/, const float *b_max /*host[3]*/, int n,
+                           float *const *verts_out, int32_t *const *faces_out, int32_t *const *counts_out,
+                           int32_t *const *vmap, mp_stream stream);
 
 /* ---- mesh rasteriser (no counterpart in the reference, which renders through PyOpenGL and an X server) ----------
  * A z-buffered picture of a triangle mesh as mp_marching_cubes leaves it, for any camera and any image size, defined

@@ -396,6 +396,72 @@ static int mesh_normals_checked(mp_ctx *ctx, const char *who, int n_frames, cons
                                    normals, (hipStream_t)stream);
 }
 
+// true if [a, a + na) and [b, b + nb) share a byte (either empty or null: no)
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+  const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+  return a && b && na && nb && pa < pb + nb && pb < pa + na;
+}
+
+static int mesh_simplify_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *verts,
+                                 int64_t max_verts, const int32_t *const *faces, int64_t max_faces,
+                                 const int32_t *const *counts, const float *b_min, const float *b_max, int n,
+                                 float *const *verts_out, int32_t *const *faces_out, int32_t *const *counts_out,
+                                 int32_t *const *vmap, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (!counts || !counts_out || !b_min || !b_max || max_verts < 0 || max_faces < 0 ||
+      (max_verts > 0 && (!verts || !verts_out)) || (max_faces > 0 && (!faces || !faces_out)))
+    return bad_argument(ctx, who);
+  if (n < 1 || n > 512) return fail(ctx, MP_ERR_ARG, "%s: 1..512 cells per axis, got %d", who, n);
+  float inv[3];
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(b_min[a]) || !std::isfinite(b_max[a]) || !(b_max[a] > b_min[a]))
+      return fail(ctx, MP_ERR_ARG, "%s: the box needs finite bounds with b_max > b_min, got [%g, %g] on axis %d", who,
+                  (double)b_min[a], (double)b_max[a], a);
+    inv[a] = (float)n / (b_max[a] - b_min[a]);
+    if (!std::isfinite(inv[a]))
+      return fail(ctx, MP_ERR_ARG, "%s: the box is too thin on axis %d for %d cells (%g wide)", who, a, n,
+                  (double)(b_max[a] - b_min[a]));
+  }
+  if (max_verts > (1LL << 27))
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: more than 2^27 vertices could overflow the 64-bit coordinate sums", who);
+  if (max_faces > 0x7fffffffLL / 3)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: capacities beyond 2^31 / 3 need 64-bit indices", who);
+  if (max_verts == 0) verts = nullptr, verts_out = nullptr, vmap = nullptr;  // rows of a capacity of 0 are not looked at
+  if (max_faces == 0) faces = nullptr, faces_out = nullptr;
+  rc = check_frames(ctx, who, n_frames, nullptr, counts, counts_out, verts, verts_out, faces, faces_out, vmap);
+  if (rc != MP_OK) return rc;
+  const size_t vbytes = (size_t)max_verts * 12, fbytes = (size_t)max_faces * 12;
+  for (int f = 0; f < n_frames; ++f) {  // no output of any frame may share a byte with an input of any frame
+    const void *outs[4] = {verts_out ? verts_out[f] : nullptr, faces_out ? faces_out[f] : nullptr, counts_out[f],
+                           vmap ? vmap[f] : nullptr};
+    const size_t out_bytes[4] = {vbytes, fbytes, 8, (size_t)max_verts * 4};
+    for (int i = 0; i < n_frames; ++i) {
+      const void *ins[3] = {verts ? verts[i] : nullptr, faces ? faces[i] : nullptr, counts[i]};
+      const size_t in_bytes[3] = {vbytes, fbytes, 8};
+      for (int o = 0; o < 4; ++o)
+        for (int k = 0; k < 3; ++k)
+          if (ranges_overlap(outs[o], out_bytes[o], ins[k], in_bytes[k]))
+            return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases an input of frame %d", who, f, i);
+    }
+  }
+  DeviceGuard g(ctx->device);
+  if (max_verts == 0) {  // no vertex, hence no face: the counts are all there is to write
+    for (int f = 0; f < n_frames; ++f) MP_HIP(ctx, hipMemsetAsync(counts_out[f], 0, 8, (hipStream_t)stream));
+    return MP_OK;
+  }
+  const FrameRows faces_p(faces, n_frames);
+  const FrameRows faces_out_p(faces_out, n_frames);
+  void *scratch = nullptr;
+  rc = ensure_scratch(ctx, (hipStream_t)stream, mesh_simplify_scratch_bytes(n_frames, n, max_verts, max_faces),
+                      &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_mesh_simplify_batch(ctx, scratch, n_frames, verts, max_verts, faces_p.p, max_faces, counts, b_min, inv,
+                                    n, verts_out, faces_out_p.p, counts_out, vmap, (hipStream_t)stream);
+}
+
 static int mesh_points_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *verts,
                                int64_t max_verts, const int32_t *const *counts, float *const *points,
                                int32_t *const *count_out, mp_stream stream) {
@@ -1316,6 +1382,22 @@ int mp_mesh_normals_batch(mp_ctx *ctx, int n_frames, const float *const *verts, 
                           float *const *normals, mp_stream stream) {
   return mesh_normals_checked(ctx, "mp_mesh_normals_batch", n_frames, verts, max_verts, faces, max_faces, counts, mode,
                               normals, stream);
+}
+
+int mp_mesh_simplify(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                     const int32_t *counts, const float *b_min, const float *b_max, int n, float *verts_out,
+                     int32_t *faces_out, int32_t *counts_out, int32_t *vmap, mp_stream stream) {
+  return mesh_simplify_checked(ctx, "mp_mesh_simplify", 1, &verts, max_verts, &faces, max_faces, &counts, b_min, b_max,
+                               n, &verts_out, &faces_out, &counts_out, vmap ? &vmap : nullptr, stream);
+}
+
+int mp_mesh_simplify_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                           const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts,
+                           const float *b_min, const float *b_max, int n, float *const *verts_out,
+                           int32_t *const *faces_out, int32_t *const *counts_out, int32_t *const *vmap,
+                           mp_stream stream) {
+  return mesh_simplify_checked(ctx, "mp_mesh_simplify_batch", n_frames, verts, max_verts, faces, max_faces, counts,
+                               b_min, b_max, n, verts_out, faces_out, counts_out, vmap, stream);
 }
 
 int mp_mesh_points(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *counts, float *points,

@@ -21,6 +21,7 @@
 // mp_mesh_points_batch; the per-mesh calls are the one-frame case).  Each frame reads its own counts and has its own
 // part of the scratch (MeshScratch), the running total of the segment allocation included.
 #include "mp_internal.h"
+#include "mesh_common.h"
 
 #include <cstring>
 
@@ -29,11 +30,6 @@
 namespace mp {
 
 constexpr int kMeshBlock = 256;
-
-__device__ __forceinline__ int mesh_min(int count, long long cap) {
-  if (count < 0) return 0;
-  return (long long)count < cap ? count : (int)cap;
-}
 
 // normalize_v3 (mesh_util.py:190-198): sqrt(x**2 + y**2 + z**2) left to right, eps = 1e-8 in f32
 __device__ __forceinline__ void normalize_v3(float &x, float &y, float &z) {

@@ -379,6 +379,14 @@ int launch_mesh_normals_batch(mp_ctx *ctx, void *scratch, int n_frames, const fl
 int launch_mesh_points_batch(mp_ctx *ctx, int n_frames, const float *const *verts, long long max_v,
                              const int32_t *const *counts, float *const *points, int32_t *const *count_out,
                              hipStream_t st);
+// simplify.hip: vertex clustering of n_frames meshes of one capacity on an n^3 grid of cells; inv[a] = n / (b_max[a] -
+// b_min[a]) in f32; vmap: nullptr or n_frames entries; scratch: mesh_simplify_scratch_bytes(n_frames, n, ...)
+size_t mesh_simplify_scratch_bytes(int n_frames, int n, long long max_v, long long max_f);
+int launch_mesh_simplify_batch(mp_ctx *ctx, void *scratch, int n_frames, const float *const *verts, long long max_v,
+                               const int32_t *const *faces, long long max_f, const int32_t *const *counts,
+                               const float *bmin, const float *inv, int n, float *const *verts_out,
+                               int32_t *const *faces_out, int32_t *const *counts_out, int32_t *const *vmap,
+                               hipStream_t st);
 // raster.hip: n_frames meshes x n_views cameras (calibs: host, 12 floats per image, frame-major); attr / image / depth /
 // face_id: nullptr or n_frames entries, each frame's views back to back; scratch: mesh_render_scratch_bytes(n_frames *
 // n_views, ...)

@@ -1234,6 +1234,56 @@ def mesh_normals_raw_batch(verts, faces, counts, mode="accumulate", out=None):
     return _mesh_normals("mesh_normals_raw_batch", verts, faces, counts, mode, out)
 
 
+SIMPLIFY_MAX_CELLS = 512  # mp_mesh_simplify: cells per axis in 1..512
+
+
+def _simplify_cells(who, cells):
+    if isinstance(cells, bool) or not isinstance(cells, (int, np.integer)) or not 1 <= cells <= SIMPLIFY_MAX_CELLS:
+        raise ValueError("%s: cells per axis must be an int in 1..%d, got %r" % (who, SIMPLIFY_MAX_CELLS, cells))
+    return int(cells)
+
+
+def _mesh_simplify(who, verts, faces, counts, cells, b_min, b_max, out):
+    n, max_v, max_f, dev = _mesh_frames(who, verts, faces, counts)
+    cells = _simplify_cells(who, cells)
+    if out is None:
+        verts_out = torch.empty((n, max_v, 3), dtype=torch.float32, device=dev).unbind(0)
+        faces_out = torch.empty((n, max_f, 3), dtype=torch.int32, device=dev).unbind(0)
+        counts_out = torch.empty((n, 2), dtype=torch.int32, device=dev).unbind(0)
+        vmap = torch.empty((n, max_v), dtype=torch.int32, device=dev).unbind(0)
+    else:
+        verts_out = _frame_rows(who, "out[0] (verts)", out[0], n, (max_v, 3), torch.float32, dev)
+        faces_out = _frame_rows(who, "out[1] (faces)", out[1], n, (max_f, 3), torch.int32, dev)
+        counts_out = _frame_rows(who, "out[2] (counts)", out[2], n, (2,), torch.int32, dev)
+        vmap = _frame_rows(who, "out[3] (vmap)", out[3], n, (max_v,), torch.int32, dev)
+    ctx = get_context(dev)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_mesh_simplify_batch(
+            ctx.handle, f1 - f0, _ptr_array(verts[f0:f1]), max_v, _ptr_array(faces[f0:f1]), max_f,
+            _ptr_array(counts[f0:f1]), _float3(b_min), _float3(b_max), cells, _ptr_array(verts_out[f0:f1]),
+            _ptr_array(faces_out[f0:f1]), _ptr_array(counts_out[f0:f1]), _ptr_array(vmap[f0:f1]),
+            _stream(verts[0])), "mp_mesh_simplify_batch")
+    return list(zip(verts_out, faces_out, counts_out, vmap))
+
+
+def mesh_simplify_raw(verts, faces, counts, cells, b_min=(-1, -1, -1), b_max=(1, 1, 1), out=None):
+    """mp_mesh_simplify_batch with one frame: the vertex clustering of verts [max_v,3] f32, faces [max_f,3] int32,
+    counts int32[2] on device (as ``marching_cubes_raw`` returns them) on ``cells``^3 cells over the box -> (verts_out
+    [max_v,3], faces_out [max_f,3], counts_out int32[2], vmap int32 [max_v] = new index of every old vertex, -1 for an
+    invalid one); rows beyond the new counts (of vmap: beyond the old vertex count) are not written.  ``out``: these
+    four to write into.  No host sync."""
+    return _mesh_simplify("mesh_simplify_raw", [verts], [faces], [counts], cells, b_min, b_max,
+                          None if out is None else [[o] for o in out])[0]
+
+
+def mesh_simplify_raw_batch(verts, faces, counts, cells, b_min=(-1, -1, -1), b_max=(1, 1, 1), out=None):
+    """mp_mesh_simplify_batch: ``[mesh_simplify_raw(v, f, c, cells, b_min, b_max) for v, f, c in zip(verts, faces,
+    counts)]`` (lists of per-mesh device tensors, one capacity) in ONE set of launches per MAX_FRAMES meshes; the
+    results are views of four tensors (``out`` = (verts [n,max_v,3], faces [n,max_f,3], counts [n,2], vmap [n,max_v])
+    if given), bit for bit what the per-mesh call gives.  No host sync."""
+    return _mesh_simplify("mesh_simplify_raw_batch", verts, faces, counts, cells, b_min, b_max, out)
+
+
 def _mesh_points(who, verts, counts, out):
     n, max_v, _, dev = _mesh_frames(who, verts, None, counts)
     if out is None:

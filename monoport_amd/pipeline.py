@@ -45,7 +45,7 @@ MAX_RECON_BATCH = ops.MAX_FRAMES  # kMaxFrames of the C-ABI (include/monoport_hi
 # 4 and all lie inside each other's spread (0.16-0.19).  The same slots without mesh output: 6.34 / 6.31
 _mb = os.environ.get("MONOPORT_MESH_BATCH", "on")
 MESH_BATCH = 1 if _mb == "off" else min(int(_mb) if _mb.isdigit() and int(_mb) > 0 else MAX_RECON_BATCH, MAX_RECON_BATCH)
-MESH_KEYS = ("normals", "level", "colors", "clean")
+MESH_KEYS = ("normals", "level", "colors", "clean", "simplify")
 
 
 def _mesh_options(mesh, balance, has_netc):
@@ -78,6 +78,14 @@ def _mesh_clean_option(mesh, level):
     return clean
 
 
+def _mesh_simplify_option(mesh):
+    """The ``simplify`` entry of FrameSlot's ``mesh`` argument: None, or the cells per axis of recon.simplify_mesh."""
+    from .recon import _check_simplify
+    simplify = mesh.get("simplify") if isinstance(mesh, dict) else getattr(mesh, "simplify", None)
+    _check_simplify(simplify)
+    return simplify
+
+
 class FrameSlot:
     """Static buffers for ``batch`` in-flight frames (geometry chain of RTL/main.py:366-428, plus
     the netC texture stages :373-441 when ``netC`` is given)."""
@@ -90,7 +98,11 @@ class FrameSlot:
         slot's ``balance``) and ``colors`` (per-vertex netC colours; default: ``netC is not None``) and ``clean`` (None -- the default: nothing
         is allocated or enqueued for it --, or 6 / 26: marching cubes sees only the largest connected body of each
         volume, ``recon.keep_largest`` into copies that live in mesh buffers of one mesh chunk of frames;
-        ``volumes``, the renders and every other consumer see the unchanged volume).  The slot then
+        ``volumes``, the renders and every other consumer see the unchanged volume) and ``simplify`` (None -- the
+        default: nothing is allocated or enqueued for it --, or the cells per axis, 1..512, of ``recon.simplify_mesh``
+        over the slot's box: the vertex clustering runs between marching cubes and the normals / colours, into a second
+        set of vertex / face / count buffers plus the vertex map, 40 bytes per vertex of capacity; normals and colours
+        are those of the simplified mesh and the colour query shrinks with it).  The slot then
         owns static per-frame mesh buffers at the capacities of ``ops.marching_cubes_raw`` (12 r^2 vertices and
         24 r^2 faces: vertices, faces, normals, query points and predictions are about 57 MB per frame at 257^3), the
         batched mesh chain runs behind the octree on the slot's stream, and ``meshes()`` hands the results out."""
@@ -168,6 +180,13 @@ class FrameSlot:
             chunk = min(MESH_BATCH, b)  # the cleaned copies are consumed chunk by chunk (68 MB per frame at 257^3)
             self.mesh_buffers["cleaned"] = torch.empty((chunk, r, r, r), dtype=torch.float32, device=dev)
             self.mesh_buffers["clean_stats"] = torch.zeros((b, 4), dtype=torch.int32, device=dev)
+        # likewise beside ``mesh``: the simplified mesh has buffers of its own (marching cubes' stay its input)
+        self.mesh_simplify = None if mesh is None else _mesh_simplify_option(mesh)
+        if self.mesh_simplify is not None:
+            self.mesh_buffers["simple_verts"] = torch.empty((b, cap_v, 3), dtype=torch.float32, device=dev)
+            self.mesh_buffers["simple_faces"] = torch.empty((b, cap_f, 3), dtype=torch.int32, device=dev)
+            self.mesh_buffers["simple_counts"] = torch.zeros((b, 2), dtype=torch.int32, device=dev)
+            self.mesh_buffers["simple_vmap"] = torch.empty((b, cap_v), dtype=torch.int32, device=dev)
 
     # convenience views for batch == 1 callers
     @property
@@ -291,7 +310,8 @@ class FrameSlot:
             self._mesh_chains[b0:b1] = _mesh_chain_batch(
                 self.volumes[b0:b1], level, self.b_min, self.b_max, normals,
                 [self._mesh_binding(b) for b in range(b0, b1)] if colors else None,
-                gates=[self.status[b, 0:1] for b in range(b0, b1)], out=out, clean=self.mesh_clean)
+                gates=[self.status[b, 0:1] for b in range(b0, b1)], out=out, clean=self.mesh_clean,
+                simplify=self.mesh_simplify)
 
     def meshes(self):
         """The meshes of the current submission, to be called after ``wait()`` (it waits if the caller has not): a
@@ -302,21 +322,27 @@ class FrameSlot:
         exact capacities here: all of its tensors are then fresh ones."""
         if self.mesh is None:
             raise RuntimeError("FrameSlot.meshes(): the slot was made without mesh=...")
-        from .recon import _finish_mesh, _mesh_chain
+        from .recon import _finish_mesh, _mesh_chain, _rerun_exact
         self.wait()
         n = self.n_active
         normals, level, colors = self.mesh
-        host = torch.cat([self.mesh_buffers["counts"][:n], self.status[:n, 0:1]], dim=1).cpu().tolist()
+        # per frame: alive, (vertices, faces) of the mesh [, with ``simplify``: those marching cubes needed]
+        cols = [self.status[:n, 0:1], self.mesh_buffers["counts"][:n]]
+        if self.mesh_simplify is not None:
+            cols.insert(1, self.mesh_buffers["simple_counts"][:n])
+        host = torch.cat(cols, dim=1).cpu().tolist()
         out = []
-        for b, (nv, nf, alive) in enumerate(host):
+        for b, (alive, *sizes) in enumerate(host):
             if not alive:
                 out.append(None)
                 continue
-            chain, short = self._mesh_chains[b], False
-            if nv > chain[0].shape[0] or nf > chain[1].shape[0]:
-                chain, short = _mesh_chain(self.volumes[b], level, self.b_min, self.b_max, normals,
-                                           self._mesh_binding(b) if colors else None, nv, nf,
-                                           clean=self.mesh_clean), True
+
+            def run(max_verts, max_faces):
+                return _mesh_chain(self.volumes[b], level, self.b_min, self.b_max, normals,
+                                   self._mesh_binding(b) if colors else None, max_verts, max_faces,
+                                   clean=self.mesh_clean, simplify=self.mesh_simplify)
+
+            chain, nv, nf, short = _rerun_exact(run, sizes, self._mesh_chains[b])
             out.append(_finish_mesh(chain, nv, nf, raw_preds=not short))
         return out
 

@@ -181,24 +181,58 @@ def _check_clean(clean, level):
         raise ValueError("clean fills the dropped voxels with 0.0: it needs level > 0, got %r" % (level,))
 
 
-def _mesh_chain(sdf, level, b_min, b_max, normals, binding, max_verts=None, max_faces=None, clean=None):
-    """volume [-> its largest body] -> verts, faces -> normals -> colours, enqueued without a host value in
-    between."""
+def _check_simplify(simplify):
+    """The ``simplify`` option of the mesh calls: None, or the cells per axis (an int in 1..512) of the vertex
+    clustering between marching cubes and the normals / colours, over the call's box."""
+    if simplify is not None:
+        ops._simplify_cells("simplify", simplify)
+
+
+def _mesh_chain(sdf, level, b_min, b_max, normals, binding, max_verts=None, max_faces=None, clean=None,
+                simplify=None):
+    """volume [-> its largest body] -> verts, faces [-> their vertex clustering] -> normals -> colours, enqueued
+    without a host value in between.  With ``simplify`` the tuple has a sixth entry, marching cubes' own counts (what
+    the capacities are compared with); verts, faces and counts are then the simplified mesh's."""
     if clean is not None:  # into a scratch volume: the caller's is never modified
         sdf = ops.keep_largest_raw(sdf, level, clean, CLEAN_FILL)[0]
     verts, faces, counts = ops.marching_cubes_raw(sdf, level, b_min, b_max, max_verts=max_verts,
                                                   max_faces=max_faces)
+    if simplify is not None:
+        mc_counts = counts
+        verts, faces, counts, _ = ops.mesh_simplify_raw(verts, faces, counts, simplify, b_min, b_max)
     nrm = ops.mesh_normals_raw(verts, faces, counts, normals) if normals is not None else None
     col = None
     if binding is not None:
         pts, count = ops.mesh_points_raw(verts, counts)
         col = (_counted_colours(binding, pts, count) * 0.5 + 0.5).t()
+    if simplify is not None:
+        return verts, faces, counts, nrm, col, mc_counts
     return verts, faces, counts, nrm, col
+
+
+def _chain_sizes(chain):
+    """The counts a chain leaves on the device, as one tensor: (vertices, faces) of the mesh, followed with
+    ``simplify`` by the (vertices, faces) marching cubes needed."""
+    return chain[2] if len(chain) == 5 else torch.cat([chain[2][:2], chain[5][:2]])
+
+
+def _rerun_exact(run, sizes, chain):
+    """``sizes`` (host list of ``_chain_sizes``) -> (chain, vertices, faces, re-run?): if marching cubes needed more
+    than the chain's capacities, ``run(max_verts, max_faces)`` makes the whole chain again with exact capacities (with
+    ``simplify`` that costs one more host copy, for the new counts)."""
+    nv, nf = sizes[0], sizes[1]
+    need_v, need_f = sizes[-2], sizes[-1]
+    if need_v <= chain[0].shape[0] and need_f <= chain[1].shape[0]:
+        return chain, nv, nf, False
+    chain = run(need_v, need_f)
+    if len(chain) != 5:
+        nv, nf = chain[2].cpu().tolist()[:2]
+    return chain, nv, nf, True
 
 
 @torch.no_grad()
 def reconstruct_mesh(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normals="accumulate", netC=None,
-                     feat_tensor_C=None, calib_tensor=None, clean=None):
+                     feat_tensor_C=None, calib_tensor=None, clean=None, simplify=None):
     """The finished mesh of an occupancy volume [1,1,D,H,W] (or [D,H,W]) as one device chain: marching cubes,
     per-vertex normals (``normals``: "accumulate", "reference" -- mesh_util.compute_normal's two modes -- or
     None to skip them) and, with ``netC``, per-vertex colours netC.query(vertices) * 0.5 + 0.5 as
@@ -206,20 +240,26 @@ def reconstruct_mesh(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normal
     per mesh (the two counts, read after everything is enqueued); if a capacity guess was short the chain
     runs once more with exact capacities.  A multi-view ``netC`` is not served here.  ``clean``: None, or 6 / 26 =
     ``keep_largest(sdf, level, clean)`` in front of marching cubes inside the same chain (into a scratch volume;
-    ``sdf`` is not modified; needs level > 0)."""
+    ``sdf`` is not modified; needs level > 0).  ``simplify``: None, or the cells per axis (1..512) of
+    ``ops.mesh_simplify_raw`` over the box between marching cubes and the normals / colours: the mesh, its normals and
+    its colours are those of the simplified mesh (nothing is averaged; the colour query shrinks with it).  Still one
+    host sync: marching cubes' counts (for the capacity check) and the simplified ones come in one copy."""
     if sdf is None:
         return None
     _check_normals(normals)
     _check_clean(clean, level)
+    _check_simplify(simplify)
     binding = None
     if netC is not None:
         binding = _bind_netC("reconstruct_mesh", netC, [(feat_tensor_C, calib_tensor, sdf.device)])[0]
-    verts, faces, counts, nrm, col = _mesh_chain(sdf, level, b_min, b_max, normals, binding, clean=clean)
-    nv, nf = (int(c) for c in counts.cpu())
-    if nv > verts.shape[0] or nf > faces.shape[0]:
-        verts, faces, counts, nrm, col = _mesh_chain(sdf, level, b_min, b_max, normals, binding, nv, nf, clean=clean)
-    return Mesh(verts[:nv], faces[:nf], None if nrm is None else nrm[:nv],
-                None if col is None else col[:nv].contiguous())
+
+    def run(max_verts=None, max_faces=None):
+        return _mesh_chain(sdf, level, b_min, b_max, normals, binding, max_verts, max_faces, clean=clean,
+                           simplify=simplify)
+
+    chain = run()
+    chain, nv, nf, _ = _rerun_exact(run, _chain_sizes(chain).cpu().tolist(), chain)  # the one host sync
+    return _finish_mesh(chain, nv, nf)
 
 
 def _check_normals(normals):
@@ -227,14 +267,16 @@ def _check_normals(normals):
         raise ValueError("normals must be None or one of %s, got %r" % (sorted(ops.NORMALS_MODES), normals))
 
 
-def _mesh_chain_batch(sdfs, level, b_min, b_max, normals, bindings, gates=None, out=None, clean=None):
+def _mesh_chain_batch(sdfs, level, b_min, b_max, normals, bindings, gates=None, out=None, clean=None, simplify=None):
     """``_mesh_chain`` for volumes of one size, every stage one set of launches for all of them: a list of
     (verts, faces, counts, normals or None, netC predictions [3,max_v] or None) per volume, nothing synchronised
     (``_finish_mesh(..., raw_preds=True)`` turns the predictions of the vertices present into colours).
     ``bindings``: None or one QueryBinding per volume (one head).  ``out``: None or a dict of the caller's buffers
     (verts, faces, counts, normals, points, point_counts, preds: [n, ...] tensors, preds a list; with ``clean`` also
     cleaned [n,R,R,R] and clean_stats [n,4]).  ``clean``: None or the connectivity of ``keep_largest`` in front of
-    marching cubes, under the same gates."""
+    marching cubes, under the same gates.  ``simplify``: None or the cells per axis of the vertex clustering behind
+    marching cubes (``out``: simple_verts, simple_faces, simple_counts, simple_vmap); a gated-off frame's counts of
+    (0, 0) switch it off too.  Each tuple then ends with marching cubes' own counts, as ``_mesh_chain``'s."""
     out = out or {}
     n = len(sdfs)
     if clean is not None:
@@ -243,6 +285,12 @@ def _mesh_chain_batch(sdfs, level, b_min, b_max, normals, bindings, gates=None, 
     mc_out = (out["verts"], out["faces"], out["counts"]) if "verts" in out else None
     raws = ops.marching_cubes_raw_batch(sdfs, level, b_min, b_max, gates=gates, out=mc_out)
     verts, faces, counts = ([r[k] for r in raws] for k in range(3))
+    if simplify is not None:
+        mc_counts = counts
+        sm_out = (tuple(out["simple_" + k] for k in ("verts", "faces", "counts", "vmap"))
+                  if "simple_verts" in out else None)
+        raws = ops.mesh_simplify_raw_batch(verts, faces, counts, simplify, b_min, b_max, out=sm_out)
+        verts, faces, counts = ([r[k] for r in raws] for k in range(3))
     nrm = [None] * n
     if normals is not None:
         nrm = ops.mesh_normals_raw_batch(verts, faces, counts, normals, out=out.get("normals"))
@@ -254,12 +302,14 @@ def _mesh_chain_batch(sdfs, level, b_min, b_max, normals, bindings, gates=None, 
         for f0, f1 in ops._frame_chunks(n):
             preds += _counted_colours(list(bindings[f0:f1]), [p[0] for p in pts[f0:f1]], [p[1] for p in pts[f0:f1]],
                                       outs=None if "preds" not in out else out["preds"][f0:f1])
+    if simplify is not None:
+        return [(verts[f], faces[f], counts[f], nrm[f], preds[f], mc_counts[f]) for f in range(n)]
     return [(verts[f], faces[f], counts[f], nrm[f], preds[f]) for f in range(n)]
 
 
 def _finish_mesh(chain, nv, nf, raw_preds=False):
     """The ``Mesh`` of a chain's capacity-sized tensors once the counts are on the host."""
-    verts, faces, _, nrm, col = chain
+    verts, faces, _, nrm, col = chain[:5]
     if col is not None:  # elementwise: the same bits whether the rows are cut before or after
         col = ((col[:, :nv] * 0.5 + 0.5).t() if raw_preds else col[:nv]).contiguous()
     return Mesh(verts[:nv], faces[:nf], None if nrm is None else nrm[:nv], col)
@@ -267,9 +317,9 @@ def _finish_mesh(chain, nv, nf, raw_preds=False):
 
 @torch.no_grad()
 def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normals="accumulate", netC=None,
-                          feat_tensors_C=None, calib_tensors=None, clean=None):
-    """``[reconstruct_mesh(s, level, b_min, b_max, normals, netC, feat_tensors_C[i], calib_tensors[i], clean) for i, s
-    in enumerate(sdfs)]`` -- every field of every ``Mesh`` the same bits -- with the chain enqueued ONCE for all volumes
+                          feat_tensors_C=None, calib_tensors=None, clean=None, simplify=None):
+    """``[reconstruct_mesh(s, level, b_min, b_max, normals, netC, feat_tensors_C[i], calib_tensors[i], clean, simplify)
+    for i, s in enumerate(sdfs)]`` -- every field of every ``Mesh`` the same bits -- with the chain enqueued ONCE for all volumes
     (batched marching cubes, normals, points and one counted colour query per ops.MAX_FRAMES volumes) and ONE host
     sync for all the counts (monoport_amd extension; the hook of a coalescing stage).  ``None`` entries of ``sdfs``
     give ``None``; the other volumes must be of one size (ValueError).  ``feat_tensors_C`` / ``calib_tensors``: one
@@ -278,6 +328,7 @@ def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), 
     sdfs = list(sdfs)
     _check_normals(normals)
     _check_clean(clean, level)
+    _check_simplify(simplify)
     if netC is not None:
         if feat_tensors_C is None or calib_tensors is None:
             raise ValueError("reconstruct_mesh_many: netC needs feat_tensors_C and calib_tensors")
@@ -296,16 +347,39 @@ def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), 
     if not idx:
         return meshes
     live = [sdfs[i] for i in idx]
-    chains = _mesh_chain_batch(live, level, b_min, b_max, normals, bindings, clean=clean)
-    sizes = torch.stack([c[2] for c in chains]).cpu().tolist()  # the one host sync
+    chains = _mesh_chain_batch(live, level, b_min, b_max, normals, bindings, clean=clean, simplify=simplify)
+    sizes = torch.stack([_chain_sizes(c) for c in chains]).cpu().tolist()  # the one host sync
     for k, i in enumerate(idx):
-        nv, nf = sizes[k]
-        chain, short = chains[k], False
-        if nv > chain[0].shape[0] or nf > chain[1].shape[0]:
-            chain, short = _mesh_chain(live[k], level, b_min, b_max, normals,
-                                       None if bindings is None else bindings[k], nv, nf, clean=clean), True
+        def run(max_verts, max_faces):
+            return _mesh_chain(live[k], level, b_min, b_max, normals, None if bindings is None else bindings[k],
+                               max_verts, max_faces, clean=clean, simplify=simplify)
+
+        chain, nv, nf, short = _rerun_exact(run, sizes[k], chains[k])
         meshes[i] = _finish_mesh(chain, nv, nf, raw_preds=not short)
     return meshes
+
+
+@torch.no_grad()
+def simplify_mesh(mesh, cells, b_min=(-1, -1, -1), b_max=(1, 1, 1), normals="accumulate"):
+    """A smaller mesh by vertex clustering on the device (monoport_amd extension; ``ops.mesh_simplify_raw``): every
+    vertex of ``mesh`` (a ``Mesh``, or a (verts [V,3] f32, faces [F,3] int32) pair) falls into one of ``cells``^3 cells
+    (an int in 1..512) over the box, each occupied cell becomes one vertex at its members' mean, and the faces that do
+    not collapse are kept in order.  Returns (``Mesh``, vmap): normals recomputed on the simplified mesh (``normals``:
+    "accumulate", "reference" or None), ``colors`` None, and vmap int32 [V] = the new index of every old vertex (-1 for
+    one with a non-finite or huge coordinate) to carry attributes over.  One host sync (the two counts).
+    ``(None, None)`` for ``mesh is None``."""
+    if mesh is None:
+        return None, None
+    _check_normals(normals)
+    _check_simplify(cells)
+    verts, faces = ops._f32c(mesh[0]), mesh[1].contiguous()
+    counts = torch.tensor([verts.shape[0], faces.shape[0]], dtype=torch.int32)
+    if verts.device.type == "cuda":
+        counts = counts.pin_memory().to(verts.device, non_blocking=True)
+    v, f, c, vmap = ops.mesh_simplify_raw(verts, faces, counts, cells, b_min, b_max)
+    nrm = ops.mesh_normals_raw(v, f, c, normals) if normals is not None else None
+    nv, nf = c.cpu().tolist()
+    return Mesh(v[:nv], f[:nf], None if nrm is None else nrm[:nv], None), vmap
 
 
 MeshRender = collections.namedtuple("MeshRender", ["image", "depth", "face"])

@@ -31,6 +31,13 @@ second view cost before).
 
     python tools/mesh_timing.py --render [--passes 5] [--out profiles/mesh_render_timing.json]
 
+``--simplify`` measures the level-of-detail dial (profiles/mesh_simplify_timing.json): on the same volume,
+recon.reconstruct_mesh_many of 20 meshes with and without netC colours, and the 20-frame colour slot of ``--batched``
+with a mesh per frame, each at ``simplify`` None / 128 / 64 (normals="accumulate"), per-mesh / per-frame milliseconds,
+with the vertex and face counts at each setting.  ``--simplify --no-slot`` leaves the slot out.
+
+    python tools/mesh_timing.py --simplify [--passes 5] [--out profiles/mesh_simplify_timing.json]
+
 The protocol of tools/recon_views_timing.py: after a warm-up of all, the passes alternate; a pass is `meshes`
 meshes, wall clock around a final stream sync.  Prints (and writes) one JSON line: per way the median, minimum and
 maximum time per mesh (ms) over the passes.  The verdict fields restate what to check: (b) not slower than (a) by
@@ -65,11 +72,13 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--batched", action="store_true", help="the batched chain and the slot's MESH_BATCH settings")
     ap.add_argument("--clean", action="store_true", help="what keeping the largest connected body costs")
-    ap.add_argument("--no-slot", action="store_true", help="with --clean: leave the frame slot out")
+    ap.add_argument("--no-slot", action="store_true", help="with --clean / --simplify: leave the frame slot out")
+    ap.add_argument("--simplify", action="store_true", help="the mesh chain at simplify = None / 128 / 64")
     ap.add_argument("--render", action="store_true", help="the mesh rasteriser against the visible-surface picture")
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "mesh_render_timing.json" if a.render else
+                             "mesh_simplify_timing.json" if a.simplify else
                              "keep_largest_timing.json" if a.clean else
                              "mesh_batch_timing.json" if a.batched else "mesh_timing.json")
     mlp = ops.PackedMLP.from_layers(DEV, syn.body_mlp("G", noise=0.05, seed=1), 1)
@@ -91,6 +100,12 @@ def main():
     feat_C = [[torch.from_numpy(syn.rand_feat(512, 128, 128, 62))[None].to(DEV)]]
     calib = torch.eye(4, device=DEV)[None]
 
+    if a.simplify:
+        out = simplify(a, vol, netC, feat_C, calib)
+        if not a.no_slot:
+            out["slot"] = slot_simplify(a)
+        write(a, out)
+        return
     if a.clean:
         out = clean(a, vol, netC, feat_C, calib)
         if not a.no_slot:
@@ -288,6 +303,40 @@ def slot_clean(a, frames=20):
     out["clean_adds_ms"] = round(out["mesh_clean"]["median_ms"] - out["mesh"]["median_ms"], 4)
     out["clean_stats_frame0"] = pipes["mesh_clean"].slots[0].mesh_buffers["clean_stats"][0].cpu().tolist()
     for p_ in pipes.values():
+        p_.close()
+    return out
+
+
+SIMPLIFY_SETTINGS = (None, 128, 64)
+
+
+def simplify(a, vol, netC, feat_C, calib, n=20):
+    """reconstruct_mesh_many of n meshes at each simplify setting, with and without netC colours."""
+    kwn = dict(netC=netC, feat_tensors_C=[feat_C] * n, calib_tensors=[calib] * n)
+    ways, sizes = {}, {}
+    for cells in SIMPLIFY_SETTINGS:
+        ways["many_colours_%s" % cells] = (lambda cells=cells: reconstruct_mesh_many(
+            [vol] * n, 0.5, BMIN, BMAX, simplify=cells, **kwn))
+        ways["many_%s" % cells] = (lambda cells=cells: reconstruct_mesh_many([vol] * n, 0.5, BMIN, BMAX, simplify=cells))
+        m = reconstruct_mesh(vol, 0.5, BMIN, BMAX, simplify=cells)
+        sizes[str(cells)] = [int(m.verts.shape[0]), int(m.faces.shape[0])]
+    out = {"resolutions": RES, "passes": a.passes, "per_pass": n, "unit": "ms per mesh", "normals": "accumulate",
+           "vertices_faces": sizes}
+    out.update(alternate(ways, a.passes, n))
+    return out
+
+
+def slot_simplify(a, frames=20):
+    """The 20-frame colour slot with a mesh per frame at each simplify setting, per-frame ms of a submission
+    (``meshes()`` included)."""
+    pipes, fn = _slot_pipes(frames, 1, tuple(("mesh_%s" % cells, {"normals": "accumulate", "simplify": cells})
+                                             for cells in SIMPLIFY_SETTINGS))
+    out = {"frames_per_slot": frames, "unit": "ms per frame", "normals": "accumulate", "colors": True}
+    out.update(alternate({name: fn(name) for name in pipes}, a.passes, frames))
+    out["vertices_faces_frame0"] = {}
+    for name, p_ in pipes.items():
+        m = p_.slots[0].meshes()[0]
+        out["vertices_faces_frame0"][name] = [int(m.verts.shape[0]), int(m.faces.shape[0])]
         p_.close()
     return out
 
