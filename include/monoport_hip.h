@@ -415,8 +415,8 @@ int mp_scatter_nodes(mp_ctx *ctx, const uint32_t *packed, const int32_t *count, 
                      int r, const float *values, float *volume, mp_stream stream);
 
 /* ---- per-frame and batched forms of the mesh and render calls -------------------------------------------------------
- * mp_forward_vertices, mp_paint, mp_marching_cubes, mp_mesh_simplify, mp_mesh_normals, mp_mesh_points, mp_mesh_render
- * and mp_volume_keep_largest are
+ * mp_forward_vertices, mp_paint, mp_marching_cubes, mp_mesh_simplify, mp_mesh_smooth, mp_mesh_normals, mp_mesh_points,
+ * mp_mesh_render and mp_volume_keep_largest are
  * each the batched call with one frame: mp_<call>(..., p, ...) is mp_<call>_batch(..., 1, &p, ..., gate = NULL), with
  * the same argument tests, scratch and launches; only the name at the head of an mp_last_error message is that of the
  * entry called.  The rules of the batched calls are therefore the rules of both forms:
@@ -587,6 +587,48 @@ int mp_mesh_simplify_batch(mp_ctx *ctx, int n_frames, const float *const *verts,
                            const float *b_min /*host[3]*/, const float *b_max /*host[3]*/, int n,
                            float *const *verts_out, int32_t *const *faces_out, int32_t *const *counts_out,
                            int32_t *const *vmap, mp_stream stream);
+
+/* ---- mesh smoothing (no counterpart in the reference): Taubin fairing inside the mesh chain -------------------------
+ * lambda | mu passes of the umbrella operator over the one-ring of a triangle mesh as mp_marching_cubes or
+ * mp_mesh_simplify leave it, between the mesh and its normals.  Defined bit for bit (integer atomics only: the result
+ * is a pure function of its inputs, the same bits in every run).  Per mesh: verts f32 [max_verts,3], faces int32
+ * [max_faces,3], counts (device int32[2]; only nv = min(max(counts[0], 0), max_verts) vertices and nf likewise faces
+ * are read), iterations (1..64), lambda and mu (f32, finite) and flags (MP_SMOOTH_PIN_BORDER or 0).
+ *   1 Ring.  A face is valid if all three indices lie in [0, nv).  Its edges are (c0,c1), (c1,c2), (c2,c0); an edge with
+ *     equal ends is skipped.  m(a,b) = the number of (valid face, edge) pairs with ends {a,b}.  N(v) = the b with
+ *     m(v,b) > 0 in ascending index order, d(v) = |N(v)|.  v is a BORDER vertex if some m(v,b) is odd (an open edge
+ *     has m = 1; every edge of a closed mesh, and of a closed mesh after mp_mesh_simplify with its duplicate faces,
+ *     is even: nothing is pinned there).  v is FIXED if d(v) = 0, or if MP_SMOOTH_PIN_BORDER is set and v is a border
+ *     vertex.  A fixed vertex still serves as a neighbour.
+ *   2 Pass with factor phi.  All vertices are updated at once from the previous pass's positions p.  For a vertex that
+ *     is not fixed, per axis: s = +0; for b in N(v) ascending: s = s + p_b; m = s / (float)d; q = p + phi * (m - p).
+ *     Every operation is one IEEE f32 operation (no FMA, the division correctly rounded, denormals kept).  A fixed
+ *     vertex keeps its bits.  Non-finite input follows from the arithmetic: no vertex is declared invalid.
+ *   3 Iterations.  `iterations` times: a pass with lambda, then a pass with mu (Taubin: lambda > 0 > mu, |mu| a
+ *     little larger than lambda, keeps the volume that the plain Laplacian, mu = 0, loses).
+ *   4 Outputs.  verts_out f32 [max_verts,3]: rows [0, nv) written, rows beyond untouched.  ring int32 [max_verts] or
+ *     NULL: d(v), negated for a border vertex, rows beyond nv untouched.  Faces and counts are neither changed nor
+ *     written.  No output may share a byte with an input of any frame (MP_ERR_ARG).  counts reading {0, 0} (a
+ *     gated-off frame of mp_marching_cubes_batch) touch nothing.
+ *   4 + 2 * iterations launches and one memset (smooth.hip), asynchronous, nothing synchronised.  Scratch from the
+ * stream's arena: 24 max_faces + 28 max_verts bytes per mesh, + 256.
+ * MP_ERR_ARG: iterations outside 1..64; lambda or mu not finite; unknown flag bits; a NULL or not 4-byte aligned buffer
+ * (rows of a capacity of 0 may be NULL); an output that shares a byte with an input.  MP_ERR_UNSUPPORTED: max_faces >
+ * 2^31 / 6 (the list of directed edges is indexed in int32).  max_verts == 0: MP_OK, nothing is done.  Each refusal
+ * leaves an mp_last_error message.  The batched call with one frame. */
+enum { MP_SMOOTH_PIN_BORDER = 1 };
+int mp_mesh_smooth(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                   const int32_t *counts, int iterations, float lambda, float mu, int flags, float *verts_out,
+                   int32_t *ring, mp_stream stream);
+/* The call above over n_frames (1..mp_max_frames(), else MP_ERR_ARG) meshes of one capacity, with one set of
+ * parameters for all, in ONE set of launches.  verts / faces / counts / verts_out / ring are HOST arrays of n_frames
+ * device pointers (ring may be NULL as a whole).  Frame f's outputs equal those of mp_mesh_smooth on frame f's inputs
+ * BIT FOR BIT.  No output of any frame may alias an input of any frame.  Scratch: n_frames times the per-mesh figure.
+ * Refusals as above, for a buffer of any frame. */
+int mp_mesh_smooth_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                         const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts, int iterations,
+                         float lambda, float mu, int flags, float *const *verts_out, int32_t *const *ring,
+                         mp_stream stream);
 
 /* ---- mesh rasteriser (no counterpart in the reference, which renders through PyOpenGL and an X server) ----------
  * A z-buffered picture of a triangle mesh as mp_marching_cubes leaves it, for any camera and any image size, defined

@@ -181,6 +181,9 @@ SIGNATURES = {
     "mp_mesh_simplify": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, _pf32, _pf32, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mp_mesh_simplify_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, _pf32, _pf32, c_int, c_vp, c_vp, c_vp,
                                        c_vp, c_vp]),
+    "mp_mesh_smooth": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_f32, c_f32, c_int, c_vp, c_vp, c_vp]),
+    "mp_mesh_smooth_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_f32, c_f32, c_int, c_vp, c_vp,
+                                     c_vp]),
     "mp_mesh_render": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, _pf32, c_int, c_int, c_int, c_int, c_f32,
                                c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "mp_mesh_render_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_int, _pf32, c_int, c_int,

@@ -462,6 +462,53 @@ static int mesh_simplify_checked(mp_ctx *ctx, const char *who, int n_frames, con
                                     n, verts_out, faces_out_p.p, counts_out, vmap, (hipStream_t)stream);
 }
 
+static int mesh_smooth_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *verts,
+                               int64_t max_verts, const int32_t *const *faces, int64_t max_faces,
+                               const int32_t *const *counts, int iterations, float lambda, float mu, int flags,
+                               float *const *verts_out, int32_t *const *ring, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (!counts || max_verts < 0 || max_faces < 0 || (max_verts > 0 && (!verts || !verts_out)) ||
+      (max_faces > 0 && !faces))
+    return bad_argument(ctx, who);
+  if (iterations < 1 || iterations > 64) return fail(ctx, MP_ERR_ARG, "%s: 1..64 iterations, got %d", who, iterations);
+  if (!std::isfinite(lambda) || !std::isfinite(mu))
+    return fail(ctx, MP_ERR_ARG, "%s: lambda and mu must be finite, got %g and %g", who, (double)lambda, (double)mu);
+  if (flags & ~MP_SMOOTH_PIN_BORDER) return fail(ctx, MP_ERR_ARG, "%s: unknown flags 0x%x", who, (unsigned)flags);
+  if (max_faces > 0x7fffffffLL / 6)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: capacities beyond 2^31 / 6 faces need a 64-bit edge list", who);
+  if (max_verts == 0) verts = nullptr, verts_out = nullptr, ring = nullptr;  // rows of a capacity of 0 are not looked at
+  if (max_faces == 0) faces = nullptr;
+  rc = check_frames(ctx, who, n_frames, nullptr, counts, verts, verts_out, faces);
+  if (rc != MP_OK) return rc;
+  if (ring)  // each entry may be NULL: that frame's ring is not wanted
+    for (int f = 0; f < n_frames; ++f)
+      if ((uintptr_t)ring[f] & 3) return fail(ctx, MP_ERR_ARG, "%s: misaligned buffer for frame %d", who, f);
+  const size_t vbytes = (size_t)max_verts * 12, fbytes = (size_t)max_faces * 12;
+  for (int f = 0; f < n_frames; ++f) {  // no output of any frame may share a byte with an input of any frame
+    const void *outs[2] = {verts_out ? verts_out[f] : nullptr, ring ? ring[f] : nullptr};
+    const size_t out_bytes[2] = {vbytes, (size_t)max_verts * 4};
+    for (int i = 0; i < n_frames; ++i) {
+      const void *ins[3] = {verts ? verts[i] : nullptr, faces ? faces[i] : nullptr, counts[i]};
+      const size_t in_bytes[3] = {vbytes, fbytes, 8};
+      for (int o = 0; o < 2; ++o)
+        for (int k = 0; k < 3; ++k)
+          if (ranges_overlap(outs[o], out_bytes[o], ins[k], in_bytes[k]))
+            return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases an input of frame %d", who, f, i);
+    }
+  }
+  if (max_verts == 0) return MP_OK;  // no vertex: nothing to move
+  DeviceGuard g(ctx->device);
+  const FrameRows faces_p(faces, n_frames);
+  void *scratch = nullptr;
+  rc = ensure_scratch(ctx, (hipStream_t)stream, mesh_smooth_scratch_bytes(n_frames, max_verts, max_faces), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_mesh_smooth_batch(ctx, scratch, n_frames, verts, max_verts, faces_p.p, max_faces, counts, iterations,
+                                  lambda, mu, flags & MP_SMOOTH_PIN_BORDER, verts_out, ring, (hipStream_t)stream);
+}
+
 static int mesh_points_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *verts,
                                int64_t max_verts, const int32_t *const *counts, float *const *points,
                                int32_t *const *count_out, mp_stream stream) {
@@ -1398,6 +1445,21 @@ int mp_mesh_simplify_batch(mp_ctx *ctx, int n_frames, const float *const *verts,
                            mp_stream stream) {
   return mesh_simplify_checked(ctx, "mp_mesh_simplify_batch", n_frames, verts, max_verts, faces, max_faces, counts,
                                b_min, b_max, n, verts_out, faces_out, counts_out, vmap, stream);
+}
+
+int mp_mesh_smooth(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                   const int32_t *counts, int iterations, float lambda, float mu, int flags, float *verts_out,
+                   int32_t *ring, mp_stream stream) {
+  return mesh_smooth_checked(ctx, "mp_mesh_smooth", 1, &verts, max_verts, &faces, max_faces, &counts, iterations,
+                             lambda, mu, flags, &verts_out, ring ? &ring : nullptr, stream);
+}
+
+int mp_mesh_smooth_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                         const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts, int iterations,
+                         float lambda, float mu, int flags, float *const *verts_out, int32_t *const *ring,
+                         mp_stream stream) {
+  return mesh_smooth_checked(ctx, "mp_mesh_smooth_batch", n_frames, verts, max_verts, faces, max_faces, counts,
+                             iterations, lambda, mu, flags, verts_out, ring, stream);
 }
 
 int mp_mesh_points(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *counts, float *points,

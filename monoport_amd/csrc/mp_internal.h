@@ -387,6 +387,13 @@ int launch_mesh_simplify_batch(mp_ctx *ctx, void *scratch, int n_frames, const f
                                const float *bmin, const float *inv, int n, float *const *verts_out,
                                int32_t *const *faces_out, int32_t *const *counts_out, int32_t *const *vmap,
                                hipStream_t st);
+// smooth.hip: `iterations` lambda | mu passes over n_frames meshes of one capacity; pin: fix the border vertices; ring:
+// nullptr or n_frames entries (each may be nullptr); scratch: mesh_smooth_scratch_bytes(n_frames, ...)
+size_t mesh_smooth_scratch_bytes(int n_frames, long long max_v, long long max_f);
+int launch_mesh_smooth_batch(mp_ctx *ctx, void *scratch, int n_frames, const float *const *verts, long long max_v,
+                             const int32_t *const *faces, long long max_f, const int32_t *const *counts,
+                             int iterations, float lambda, float mu, int pin, float *const *verts_out,
+                             int32_t *const *ring, hipStream_t st);
 // raster.hip: n_frames meshes x n_views cameras (calibs: host, 12 floats per image, frame-major); attr / image / depth /
 // face_id: nullptr or n_frames entries, each frame's views back to back; scratch: mesh_render_scratch_bytes(n_frames *
 // n_views, ...)

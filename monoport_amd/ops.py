@@ -1284,6 +1284,67 @@ def mesh_simplify_raw_batch(verts, faces, counts, cells, b_min=(-1, -1, -1), b_m
     return _mesh_simplify("mesh_simplify_raw_batch", verts, faces, counts, cells, b_min, b_max, out)
 
 
+SMOOTH_MAX_ITERATIONS = 64  # mp_mesh_smooth: 1..64 iterations of a lambda and a mu pass
+SMOOTH_PIN_BORDER = 1  # MP_SMOOTH_PIN_BORDER
+
+
+def _smooth_params(who, iterations, lam, mu, pin_border):
+    """The parameters of mp_mesh_smooth as the C side takes them: (iterations, lambda, mu, flags)."""
+    if (isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer))
+            or not 1 <= iterations <= SMOOTH_MAX_ITERATIONS):
+        raise ValueError("%s: iterations must be an int in 1..%d, got %r" % (who, SMOOTH_MAX_ITERATIONS, iterations))
+    for name, x in (("lam", lam), ("mu", mu)):
+        if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or \
+                not abs(float(x)) <= float(np.finfo(np.float32).max):  # false for NaN too
+            raise ValueError("%s: %s must be a finite f32 number, got %r" % (who, name, x))
+    if not isinstance(pin_border, (bool, np.bool_)):
+        raise ValueError("%s: pin_border must be a bool, got %r" % (who, pin_border))
+    return int(iterations), float(np.float32(lam)), float(np.float32(mu)), SMOOTH_PIN_BORDER if pin_border else 0
+
+
+def _mesh_smooth(who, verts, faces, counts, iterations, lam, mu, pin_border, out, ring):
+    n, max_v, max_f, dev = _mesh_frames(who, verts, faces, counts)
+    iterations, lam, mu, flags = _smooth_params(who, iterations, lam, mu, pin_border)
+    if out is None:
+        verts_out = torch.empty((n, max_v, 3), dtype=torch.float32, device=dev).unbind(0)
+    else:
+        verts_out = _frame_rows(who, "out", out, n, (max_v, 3), torch.float32, dev)
+    if ring is True:
+        ring = torch.empty((n, max_v), dtype=torch.int32, device=dev).unbind(0)
+    elif ring is not False and ring is not None:
+        ring = _frame_rows(who, "ring", ring, n, (max_v,), torch.int32, dev)
+    else:
+        ring = None
+    ctx = get_context(dev)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_mesh_smooth_batch(
+            ctx.handle, f1 - f0, _ptr_array(verts[f0:f1]), max_v, _ptr_array(faces[f0:f1]), max_f,
+            _ptr_array(counts[f0:f1]), iterations, lam, mu, flags, _ptr_array(verts_out[f0:f1]),
+            None if ring is None else _ptr_array(ring[f0:f1]), _stream(verts[0])), "mp_mesh_smooth_batch")
+    return list(verts_out) if ring is None else list(zip(verts_out, ring))
+
+
+def mesh_smooth_raw(verts, faces, counts, iterations, lam=0.5, mu=-0.53, pin_border=True, out=None, ring=False):
+    """mp_mesh_smooth_batch with one frame: ``iterations`` (1..64) Taubin iterations -- a pass with ``lam``, then one
+    with ``mu``, of the umbrella operator over the one-ring (include/monoport_hip.h) -- on verts [max_v,3] f32, faces
+    [max_f,3] int32, counts int32[2] on device (as ``marching_cubes_raw`` / ``mesh_simplify_raw`` return them) ->
+    verts_out [max_v,3]; rows beyond the vertex count are not written, faces and counts are the input's.
+    ``pin_border``: vertices of an edge that lies in an odd number of faces keep their bits.  ``out``: the tensor to
+    write into.  ``ring``: True, or an int32 [max_v] tensor to write into: the result is then (verts_out, ring), ring =
+    the number of distinct neighbours of every vertex, negated for a border vertex.  No host sync."""
+    return _mesh_smooth("mesh_smooth_raw", [verts], [faces], [counts], iterations, lam, mu, pin_border,
+                        None if out is None else [out], ring if isinstance(ring, bool) or ring is None else [ring])[0]
+
+
+def mesh_smooth_raw_batch(verts, faces, counts, iterations, lam=0.5, mu=-0.53, pin_border=True, out=None,
+                          ring=False):
+    """mp_mesh_smooth_batch: ``[mesh_smooth_raw(v, f, c, iterations, lam, mu, pin_border, ring=ring) for v, f, c in
+    zip(verts, faces, counts)]`` (lists of per-mesh device tensors, one capacity) in ONE set of launches per MAX_FRAMES
+    meshes; the results are views of one tensor each (``out`` = verts [n,max_v,3], ``ring`` = [n,max_v] if given), bit
+    for bit what the per-mesh call gives.  No host sync."""
+    return _mesh_smooth("mesh_smooth_raw_batch", verts, faces, counts, iterations, lam, mu, pin_border, out, ring)
+
+
 def _mesh_points(who, verts, counts, out):
     n, max_v, _, dev = _mesh_frames(who, verts, None, counts)
     if out is None:

@@ -45,7 +45,7 @@ MAX_RECON_BATCH = ops.MAX_FRAMES  # kMaxFrames of the C-ABI (include/monoport_hi
 # 4 and all lie inside each other's spread (0.16-0.19).  The same slots without mesh output: 6.34 / 6.31
 _mb = os.environ.get("MONOPORT_MESH_BATCH", "on")
 MESH_BATCH = 1 if _mb == "off" else min(int(_mb) if _mb.isdigit() and int(_mb) > 0 else MAX_RECON_BATCH, MAX_RECON_BATCH)
-MESH_KEYS = ("normals", "level", "colors", "clean", "simplify")
+MESH_KEYS = ("normals", "level", "colors", "clean", "simplify", "smooth")
 
 
 def _mesh_options(mesh, balance, has_netc):
@@ -86,6 +86,12 @@ def _mesh_simplify_option(mesh):
     return simplify
 
 
+def _mesh_smooth_option(mesh):
+    """The ``smooth`` entry of FrameSlot's ``mesh`` argument: None, or the keyword arguments of ops.mesh_smooth_raw."""
+    from .recon import _check_smooth
+    return _check_smooth(mesh.get("smooth") if isinstance(mesh, dict) else getattr(mesh, "smooth", None))
+
+
 class FrameSlot:
     """Static buffers for ``batch`` in-flight frames (geometry chain of RTL/main.py:366-428, plus
     the netC texture stages :373-441 when ``netC`` is given)."""
@@ -102,7 +108,10 @@ class FrameSlot:
         default: nothing is allocated or enqueued for it --, or the cells per axis, 1..512, of ``recon.simplify_mesh``
         over the slot's box: the vertex clustering runs between marching cubes and the normals / colours, into a second
         set of vertex / face / count buffers plus the vertex map, 40 bytes per vertex of capacity; normals and colours
-        are those of the simplified mesh and the colour query shrinks with it).  The slot then
+        are those of the simplified mesh and the colour query shrinks with it) and ``smooth`` (None -- the default:
+        nothing is allocated or enqueued for it --, the iterations, or the dict of ``recon.reconstruct_mesh``'s
+        ``smooth``: Taubin passes behind marching cubes / the clustering, into one more vertex buffer, 12 bytes per vertex
+        of capacity; vertices and normals are the smoothed mesh's, the colours are queried before smoothing).  The slot then
         owns static per-frame mesh buffers at the capacities of ``ops.marching_cubes_raw`` (12 r^2 vertices and
         24 r^2 faces: vertices, faces, normals, query points and predictions are about 57 MB per frame at 257^3), the
         batched mesh chain runs behind the octree on the slot's stream, and ``meshes()`` hands the results out."""
@@ -187,6 +196,9 @@ class FrameSlot:
             self.mesh_buffers["simple_faces"] = torch.empty((b, cap_f, 3), dtype=torch.int32, device=dev)
             self.mesh_buffers["simple_counts"] = torch.zeros((b, 2), dtype=torch.int32, device=dev)
             self.mesh_buffers["simple_vmap"] = torch.empty((b, cap_v), dtype=torch.int32, device=dev)
+        self.mesh_smooth = None if mesh is None else _mesh_smooth_option(mesh)
+        if self.mesh_smooth is not None:  # the vertices before smoothing stay: the colour query reads them
+            self.mesh_buffers["smooth_verts"] = torch.empty((b, cap_v, 3), dtype=torch.float32, device=dev)
 
     # convenience views for batch == 1 callers
     @property
@@ -311,7 +323,7 @@ class FrameSlot:
                 self.volumes[b0:b1], level, self.b_min, self.b_max, normals,
                 [self._mesh_binding(b) for b in range(b0, b1)] if colors else None,
                 gates=[self.status[b, 0:1] for b in range(b0, b1)], out=out, clean=self.mesh_clean,
-                simplify=self.mesh_simplify)
+                simplify=self.mesh_simplify, smooth=self.mesh_smooth)
 
     def meshes(self):
         """The meshes of the current submission, to be called after ``wait()`` (it waits if the caller has not): a
@@ -340,7 +352,7 @@ class FrameSlot:
             def run(max_verts, max_faces):
                 return _mesh_chain(self.volumes[b], level, self.b_min, self.b_max, normals,
                                    self._mesh_binding(b) if colors else None, max_verts, max_faces,
-                                   clean=self.mesh_clean, simplify=self.mesh_simplify)
+                                   clean=self.mesh_clean, simplify=self.mesh_simplify, smooth=self.mesh_smooth)
 
             chain, nv, nf, short = _rerun_exact(run, sizes, self._mesh_chains[b])
             out.append(_finish_mesh(chain, nv, nf, raw_preds=not short))

@@ -188,11 +188,34 @@ def _check_simplify(simplify):
         ops._simplify_cells("simplify", simplify)
 
 
+SMOOTH_KEYS = ("iterations", "lam", "mu", "pin_border")
+SMOOTH_DEFAULTS = {"iterations": 10, "lam": 0.5, "mu": -0.53, "pin_border": True}
+
+
+def _check_smooth(smooth):
+    """The ``smooth`` option of the mesh calls: None, the iterations (an int in 1..64) of ``ops.mesh_smooth_raw`` at
+    its default factors, or a dict with ``iterations`` and any of ``lam``, ``mu``, ``pin_border``.  -> None, or the
+    keyword arguments of ``ops.mesh_smooth_raw``."""
+    if smooth is None:
+        return None
+    if isinstance(smooth, dict):
+        unknown = sorted(set(smooth) - set(SMOOTH_KEYS))
+        if unknown or "iterations" not in smooth:
+            raise ValueError("smooth: a dict has 'iterations' and any of %s, got %r" % (list(SMOOTH_KEYS[1:]), smooth))
+        kw = dict(SMOOTH_DEFAULTS, **smooth)
+    else:
+        kw = dict(SMOOTH_DEFAULTS, iterations=smooth)
+    ops._smooth_params("smooth", kw["iterations"], kw["lam"], kw["mu"], kw["pin_border"])
+    return kw
+
+
 def _mesh_chain(sdf, level, b_min, b_max, normals, binding, max_verts=None, max_faces=None, clean=None,
-                simplify=None):
-    """volume [-> its largest body] -> verts, faces [-> their vertex clustering] -> normals -> colours, enqueued
-    without a host value in between.  With ``simplify`` the tuple has a sixth entry, marching cubes' own counts (what
-    the capacities are compared with); verts, faces and counts are then the simplified mesh's."""
+                simplify=None, smooth=None):
+    """volume [-> its largest body] -> verts, faces [-> their vertex clustering] [-> Taubin passes] -> normals ->
+    colours, enqueued without a host value in between.  With ``simplify`` the tuple has a sixth entry, marching cubes'
+    own counts (what the capacities are compared with); verts, faces and counts are then the simplified mesh's.
+    ``smooth`` (what ``_check_smooth`` returns): verts and normals are the smoothed mesh's; the colour query takes the
+    positions before smoothing, which lie on the iso-surface."""
     if clean is not None:  # into a scratch volume: the caller's is never modified
         sdf = ops.keep_largest_raw(sdf, level, clean, CLEAN_FILL)[0]
     verts, faces, counts = ops.marching_cubes_raw(sdf, level, b_min, b_max, max_verts=max_verts,
@@ -200,10 +223,13 @@ def _mesh_chain(sdf, level, b_min, b_max, normals, binding, max_verts=None, max_
     if simplify is not None:
         mc_counts = counts
         verts, faces, counts, _ = ops.mesh_simplify_raw(verts, faces, counts, simplify, b_min, b_max)
+    on_surface = verts
+    if smooth is not None:
+        verts = ops.mesh_smooth_raw(verts, faces, counts, **smooth)
     nrm = ops.mesh_normals_raw(verts, faces, counts, normals) if normals is not None else None
     col = None
     if binding is not None:
-        pts, count = ops.mesh_points_raw(verts, counts)
+        pts, count = ops.mesh_points_raw(on_surface, counts)
         col = (_counted_colours(binding, pts, count) * 0.5 + 0.5).t()
     if simplify is not None:
         return verts, faces, counts, nrm, col, mc_counts
@@ -232,7 +258,7 @@ def _rerun_exact(run, sizes, chain):
 
 @torch.no_grad()
 def reconstruct_mesh(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normals="accumulate", netC=None,
-                     feat_tensor_C=None, calib_tensor=None, clean=None, simplify=None):
+                     feat_tensor_C=None, calib_tensor=None, clean=None, simplify=None, smooth=None):
     """The finished mesh of an occupancy volume [1,1,D,H,W] (or [D,H,W]) as one device chain: marching cubes,
     per-vertex normals (``normals``: "accumulate", "reference" -- mesh_util.compute_normal's two modes -- or
     None to skip them) and, with ``netC``, per-vertex colours netC.query(vertices) * 0.5 + 0.5 as
@@ -243,19 +269,24 @@ def reconstruct_mesh(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normal
     ``sdf`` is not modified; needs level > 0).  ``simplify``: None, or the cells per axis (1..512) of
     ``ops.mesh_simplify_raw`` over the box between marching cubes and the normals / colours: the mesh, its normals and
     its colours are those of the simplified mesh (nothing is averaged; the colour query shrinks with it).  Still one
-    host sync: marching cubes' counts (for the capacity check) and the simplified ones come in one copy."""
+    host sync: marching cubes' counts (for the capacity check) and the simplified ones come in one copy.
+    ``smooth``: None, the iterations (1..64), or dict(iterations=, lam=, mu=, pin_border=) of ``smooth_mesh`` behind
+    marching cubes / the clustering: the vertices and normals are the smoothed mesh's, while the colours are queried
+    at the positions before smoothing (on the iso-surface) and so are the bits that ``smooth=None`` gives.  The counts
+    do not change: the one host sync and the re-run are as before."""
     if sdf is None:
         return None
     _check_normals(normals)
     _check_clean(clean, level)
     _check_simplify(simplify)
+    smooth = _check_smooth(smooth)
     binding = None
     if netC is not None:
         binding = _bind_netC("reconstruct_mesh", netC, [(feat_tensor_C, calib_tensor, sdf.device)])[0]
 
     def run(max_verts=None, max_faces=None):
         return _mesh_chain(sdf, level, b_min, b_max, normals, binding, max_verts, max_faces, clean=clean,
-                           simplify=simplify)
+                           simplify=simplify, smooth=smooth)
 
     chain = run()
     chain, nv, nf, _ = _rerun_exact(run, _chain_sizes(chain).cpu().tolist(), chain)  # the one host sync
@@ -267,7 +298,8 @@ def _check_normals(normals):
         raise ValueError("normals must be None or one of %s, got %r" % (sorted(ops.NORMALS_MODES), normals))
 
 
-def _mesh_chain_batch(sdfs, level, b_min, b_max, normals, bindings, gates=None, out=None, clean=None, simplify=None):
+def _mesh_chain_batch(sdfs, level, b_min, b_max, normals, bindings, gates=None, out=None, clean=None, simplify=None,
+                      smooth=None):
     """``_mesh_chain`` for volumes of one size, every stage one set of launches for all of them: a list of
     (verts, faces, counts, normals or None, netC predictions [3,max_v] or None) per volume, nothing synchronised
     (``_finish_mesh(..., raw_preds=True)`` turns the predictions of the vertices present into colours).
@@ -276,7 +308,8 @@ def _mesh_chain_batch(sdfs, level, b_min, b_max, normals, bindings, gates=None, 
     cleaned [n,R,R,R] and clean_stats [n,4]).  ``clean``: None or the connectivity of ``keep_largest`` in front of
     marching cubes, under the same gates.  ``simplify``: None or the cells per axis of the vertex clustering behind
     marching cubes (``out``: simple_verts, simple_faces, simple_counts, simple_vmap); a gated-off frame's counts of
-    (0, 0) switch it off too.  Each tuple then ends with marching cubes' own counts, as ``_mesh_chain``'s."""
+    (0, 0) switch it off too.  Each tuple then ends with marching cubes' own counts, as ``_mesh_chain``'s.
+    ``smooth``: None or what ``_check_smooth`` returns (``out``: smooth_verts); as in ``_mesh_chain``."""
     out = out or {}
     n = len(sdfs)
     if clean is not None:
@@ -291,13 +324,16 @@ def _mesh_chain_batch(sdfs, level, b_min, b_max, normals, bindings, gates=None, 
                   if "simple_verts" in out else None)
         raws = ops.mesh_simplify_raw_batch(verts, faces, counts, simplify, b_min, b_max, out=sm_out)
         verts, faces, counts = ([r[k] for r in raws] for k in range(3))
+    on_surface = verts
+    if smooth is not None:
+        verts = ops.mesh_smooth_raw_batch(verts, faces, counts, out=out.get("smooth_verts"), **smooth)
     nrm = [None] * n
     if normals is not None:
         nrm = ops.mesh_normals_raw_batch(verts, faces, counts, normals, out=out.get("normals"))
     preds = [None] * n
     if bindings is not None:
         pt_out = (out["points"], out["point_counts"]) if "points" in out else None
-        pts = ops.mesh_points_raw_batch(verts, counts, out=pt_out)
+        pts = ops.mesh_points_raw_batch(on_surface, counts, out=pt_out)
         preds = []
         for f0, f1 in ops._frame_chunks(n):
             preds += _counted_colours(list(bindings[f0:f1]), [p[0] for p in pts[f0:f1]], [p[1] for p in pts[f0:f1]],
@@ -317,9 +353,9 @@ def _finish_mesh(chain, nv, nf, raw_preds=False):
 
 @torch.no_grad()
 def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normals="accumulate", netC=None,
-                          feat_tensors_C=None, calib_tensors=None, clean=None, simplify=None):
-    """``[reconstruct_mesh(s, level, b_min, b_max, normals, netC, feat_tensors_C[i], calib_tensors[i], clean, simplify)
-    for i, s in enumerate(sdfs)]`` -- every field of every ``Mesh`` the same bits -- with the chain enqueued ONCE for all volumes
+                          feat_tensors_C=None, calib_tensors=None, clean=None, simplify=None, smooth=None):
+    """``[reconstruct_mesh(s, level, b_min, b_max, normals, netC, feat_tensors_C[i], calib_tensors[i], clean, simplify,
+    smooth) for i, s in enumerate(sdfs)]`` -- every field of every ``Mesh`` the same bits -- with the chain enqueued ONCE for all volumes
     (batched marching cubes, normals, points and one counted colour query per ops.MAX_FRAMES volumes) and ONE host
     sync for all the counts (monoport_amd extension; the hook of a coalescing stage).  ``None`` entries of ``sdfs``
     give ``None``; the other volumes must be of one size (ValueError).  ``feat_tensors_C`` / ``calib_tensors``: one
@@ -329,6 +365,7 @@ def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), 
     _check_normals(normals)
     _check_clean(clean, level)
     _check_simplify(simplify)
+    smooth = _check_smooth(smooth)
     if netC is not None:
         if feat_tensors_C is None or calib_tensors is None:
             raise ValueError("reconstruct_mesh_many: netC needs feat_tensors_C and calib_tensors")
@@ -347,12 +384,13 @@ def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), 
     if not idx:
         return meshes
     live = [sdfs[i] for i in idx]
-    chains = _mesh_chain_batch(live, level, b_min, b_max, normals, bindings, clean=clean, simplify=simplify)
+    chains = _mesh_chain_batch(live, level, b_min, b_max, normals, bindings, clean=clean, simplify=simplify,
+                               smooth=smooth)
     sizes = torch.stack([_chain_sizes(c) for c in chains]).cpu().tolist()  # the one host sync
     for k, i in enumerate(idx):
         def run(max_verts, max_faces):
             return _mesh_chain(live[k], level, b_min, b_max, normals, None if bindings is None else bindings[k],
-                               max_verts, max_faces, clean=clean, simplify=simplify)
+                               max_verts, max_faces, clean=clean, simplify=simplify, smooth=smooth)
 
         chain, nv, nf, short = _rerun_exact(run, sizes[k], chains[k])
         meshes[i] = _finish_mesh(chain, nv, nf, raw_preds=not short)
@@ -380,6 +418,29 @@ def simplify_mesh(mesh, cells, b_min=(-1, -1, -1), b_max=(1, 1, 1), normals="acc
     nrm = ops.mesh_normals_raw(v, f, c, normals) if normals is not None else None
     nv, nf = c.cpu().tolist()
     return Mesh(v[:nv], f[:nf], None if nrm is None else nrm[:nv], None), vmap
+
+
+@torch.no_grad()
+def smooth_mesh(mesh, iterations=10, lam=0.5, mu=-0.53, pin_border=True, normals="accumulate"):
+    """A faired mesh by Taubin smoothing on the device (monoport_amd extension; ``ops.mesh_smooth_raw``, defined in
+    include/monoport_hip.h): ``iterations`` (1..64) times, every vertex of ``mesh`` (a ``Mesh``, or a (verts [V,3] f32,
+    faces [F,3] int32) pair) moves by ``lam`` towards the mean of its one-ring and then by ``mu`` (negative: away from
+    it), which takes the lattice terraces out of a marching-cubes mesh of a sharp field without the shrinkage of plain
+    Laplacian passes (mu = 0).  ``pin_border``: the vertices of open edges stay where they are.  Returns a ``Mesh``
+    with the faces of the input, normals recomputed on the smoothed vertices (``normals``: "accumulate", "reference"
+    or None) and the input's ``colors`` carried over unchanged.  It gains little on a field that is already smooth
+    (DESIGN.md section 4.8.5).  No host sync.  None for ``mesh is None``."""
+    if mesh is None:
+        return None
+    _check_normals(normals)
+    kw = _check_smooth(dict(iterations=iterations, lam=lam, mu=mu, pin_border=pin_border))
+    verts, faces = ops._f32c(mesh[0]), mesh[1].contiguous()
+    counts = torch.tensor([verts.shape[0], faces.shape[0]], dtype=torch.int32)
+    if verts.device.type == "cuda":
+        counts = counts.pin_memory().to(verts.device, non_blocking=True)
+    out = ops.mesh_smooth_raw(verts, faces, counts, **kw)
+    nrm = ops.mesh_normals_raw(out, faces, counts, normals) if normals is not None else None
+    return Mesh(out, faces, nrm, mesh[3] if len(mesh) > 3 else None)
 
 
 MeshRender = collections.namedtuple("MeshRender", ["image", "depth", "face"])

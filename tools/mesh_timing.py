@@ -38,6 +38,14 @@ with the vertex and face counts at each setting.  ``--simplify --no-slot`` leave
 
     python tools/mesh_timing.py --simplify [--passes 5] [--out profiles/mesh_simplify_timing.json]
 
+``--smooth`` measures the Taubin passes (profiles/mesh_smooth_timing.json): on the same volume,
+recon.reconstruct_mesh_many of 20 meshes without colours, with netC colours, and with colours behind ``simplify=128``,
+each at ``smooth`` None / 2 / 10 (normals="accumulate"), per-mesh milliseconds, with the launches that one smoothing
+call enqueues (4 + 2 x iterations kernels and one memset, whatever the number of meshes up to ops.MAX_FRAMES).  The
+comparison is the ``smooth=None`` rows of the same run.
+
+    python tools/mesh_timing.py --smooth [--passes 5] [--out profiles/mesh_smooth_timing.json]
+
 The protocol of tools/recon_views_timing.py: after a warm-up of all, the passes alternate; a pass is `meshes`
 meshes, wall clock around a final stream sync.  Prints (and writes) one JSON line: per way the median, minimum and
 maximum time per mesh (ms) over the passes.  The verdict fields restate what to check: (b) not slower than (a) by
@@ -74,10 +82,12 @@ def main():
     ap.add_argument("--clean", action="store_true", help="what keeping the largest connected body costs")
     ap.add_argument("--no-slot", action="store_true", help="with --clean / --simplify: leave the frame slot out")
     ap.add_argument("--simplify", action="store_true", help="the mesh chain at simplify = None / 128 / 64")
+    ap.add_argument("--smooth", action="store_true", help="the mesh chain at smooth = None / 2 / 10")
     ap.add_argument("--render", action="store_true", help="the mesh rasteriser against the visible-surface picture")
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "mesh_render_timing.json" if a.render else
+                             "mesh_smooth_timing.json" if a.smooth else
                              "mesh_simplify_timing.json" if a.simplify else
                              "keep_largest_timing.json" if a.clean else
                              "mesh_batch_timing.json" if a.batched else "mesh_timing.json")
@@ -100,6 +110,9 @@ def main():
     feat_C = [[torch.from_numpy(syn.rand_feat(512, 128, 128, 62))[None].to(DEV)]]
     calib = torch.eye(4, device=DEV)[None]
 
+    if a.smooth:
+        write(a, smooth(a, vol, netC, feat_C, calib))
+        return
     if a.simplify:
         out = simplify(a, vol, netC, feat_C, calib)
         if not a.no_slot:
@@ -338,6 +351,33 @@ def slot_simplify(a, frames=20):
         m = p_.slots[0].meshes()[0]
         out["vertices_faces_frame0"][name] = [int(m.verts.shape[0]), int(m.faces.shape[0])]
         p_.close()
+    return out
+
+
+SMOOTH_SETTINGS = (None, 2, 10)
+
+
+def smooth(a, vol, netC, feat_C, calib, n=20):
+    """reconstruct_mesh_many of n meshes at each smooth setting: without colours, with netC colours, and with colours
+    behind simplify=128."""
+    kwn = dict(netC=netC, feat_tensors_C=[feat_C] * n, calib_tensors=[calib] * n)
+    ways, sizes = {}, {}
+    for it in SMOOTH_SETTINGS:
+        ways["many_%s" % it] = (lambda it=it: reconstruct_mesh_many([vol] * n, 0.5, BMIN, BMAX, smooth=it))
+        ways["many_colours_%s" % it] = (lambda it=it: reconstruct_mesh_many([vol] * n, 0.5, BMIN, BMAX, smooth=it, **kwn))
+        ways["many_colours_simplify128_%s" % it] = (lambda it=it: reconstruct_mesh_many(
+            [vol] * n, 0.5, BMIN, BMAX, simplify=128, smooth=it, **kwn))
+    for cells in (None, 128):
+        m = reconstruct_mesh(vol, 0.5, BMIN, BMAX, simplify=cells, smooth=2)
+        sizes["simplify_%s" % cells] = [int(m.verts.shape[0]), int(m.faces.shape[0])]
+    out = {"resolutions": RES, "passes": a.passes, "per_pass": n, "unit": "ms per mesh", "normals": "accumulate",
+           "lam_mu": [0.5, -0.53], "vertices_faces": sizes,
+           "launches_per_smoothing_call": {str(it): {"kernels": 4 + 2 * it, "memsets": 1} for it in SMOOTH_SETTINGS if it}}
+    out.update(alternate(ways, a.passes, n))
+    for kind in ("many", "many_colours", "many_colours_simplify128"):
+        for it in SMOOTH_SETTINGS[1:]:
+            out["%s_smooth_%d_adds_ms" % (kind, it)] = round(
+                out["%s_%d" % (kind, it)]["median_ms"] - out["%s_None" % kind]["median_ms"], 4)
     return out
 
 
