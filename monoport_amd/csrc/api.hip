@@ -402,6 +402,28 @@ static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
   return a && b && na && nb && pa < pb + nb && pb < pa + na;
 }
 
+// the buffers of one kind of a batched mesh call: rows[f] is frame f's, `bytes` long (rows null as a whole: none)
+struct FrameSpans {
+  const void *const *rows;
+  size_t bytes;
+  template <typename T>
+  FrameSpans(T *const *r, size_t b) : rows((const void *const *)r), bytes(b) {}
+  const void *of(int f) const { return rows ? rows[f] : nullptr; }
+};
+
+// MP_OK unless an output of some frame shares a byte with an input of some frame
+template <int N_OUT, int N_IN>
+static int check_no_alias(mp_ctx *ctx, const char *who, int n_frames, const FrameSpans (&outs)[N_OUT],
+                          const FrameSpans (&ins)[N_IN]) {
+  for (int f = 0; f < n_frames; ++f)
+    for (int i = 0; i < n_frames; ++i)
+      for (const FrameSpans &o : outs)
+        for (const FrameSpans &k : ins)
+          if (ranges_overlap(o.of(f), o.bytes, k.of(i), k.bytes))
+            return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases an input of frame %d", who, f, i);
+  return MP_OK;
+}
+
 static int mesh_simplify_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *verts,
                                  int64_t max_verts, const int32_t *const *faces, int64_t max_faces,
                                  const int32_t *const *counts, const float *b_min, const float *b_max, int n,
@@ -434,19 +456,10 @@ static int mesh_simplify_checked(mp_ctx *ctx, const char *who, int n_frames, con
   rc = check_frames(ctx, who, n_frames, nullptr, counts, counts_out, verts, verts_out, faces, faces_out, vmap);
   if (rc != MP_OK) return rc;
   const size_t vbytes = (size_t)max_verts * 12, fbytes = (size_t)max_faces * 12;
-  for (int f = 0; f < n_frames; ++f) {  // no output of any frame may share a byte with an input of any frame
-    const void *outs[4] = {verts_out ? verts_out[f] : nullptr, faces_out ? faces_out[f] : nullptr, counts_out[f],
-                           vmap ? vmap[f] : nullptr};
-    const size_t out_bytes[4] = {vbytes, fbytes, 8, (size_t)max_verts * 4};
-    for (int i = 0; i < n_frames; ++i) {
-      const void *ins[3] = {verts ? verts[i] : nullptr, faces ? faces[i] : nullptr, counts[i]};
-      const size_t in_bytes[3] = {vbytes, fbytes, 8};
-      for (int o = 0; o < 4; ++o)
-        for (int k = 0; k < 3; ++k)
-          if (ranges_overlap(outs[o], out_bytes[o], ins[k], in_bytes[k]))
-            return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases an input of frame %d", who, f, i);
-    }
-  }
+  const FrameSpans ins[3] = {{verts, vbytes}, {faces, fbytes}, {counts, 8}};
+  const FrameSpans outs[4] = {{verts_out, vbytes}, {faces_out, fbytes}, {counts_out, 8}, {vmap, (size_t)max_verts * 4}};
+  rc = check_no_alias(ctx, who, n_frames, outs, ins);
+  if (rc != MP_OK) return rc;
   DeviceGuard g(ctx->device);
   if (max_verts == 0) {  // no vertex, hence no face: the counts are all there is to write
     for (int f = 0; f < n_frames; ++f) MP_HIP(ctx, hipMemsetAsync(counts_out[f], 0, 8, (hipStream_t)stream));
@@ -487,18 +500,10 @@ static int mesh_smooth_checked(mp_ctx *ctx, const char *who, int n_frames, const
     for (int f = 0; f < n_frames; ++f)
       if ((uintptr_t)ring[f] & 3) return fail(ctx, MP_ERR_ARG, "%s: misaligned buffer for frame %d", who, f);
   const size_t vbytes = (size_t)max_verts * 12, fbytes = (size_t)max_faces * 12;
-  for (int f = 0; f < n_frames; ++f) {  // no output of any frame may share a byte with an input of any frame
-    const void *outs[2] = {verts_out ? verts_out[f] : nullptr, ring ? ring[f] : nullptr};
-    const size_t out_bytes[2] = {vbytes, (size_t)max_verts * 4};
-    for (int i = 0; i < n_frames; ++i) {
-      const void *ins[3] = {verts ? verts[i] : nullptr, faces ? faces[i] : nullptr, counts[i]};
-      const size_t in_bytes[3] = {vbytes, fbytes, 8};
-      for (int o = 0; o < 2; ++o)
-        for (int k = 0; k < 3; ++k)
-          if (ranges_overlap(outs[o], out_bytes[o], ins[k], in_bytes[k]))
-            return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases an input of frame %d", who, f, i);
-    }
-  }
+  const FrameSpans ins[3] = {{verts, vbytes}, {faces, fbytes}, {counts, 8}};
+  const FrameSpans outs[2] = {{verts_out, vbytes}, {ring, (size_t)max_verts * 4}};
+  rc = check_no_alias(ctx, who, n_frames, outs, ins);
+  if (rc != MP_OK) return rc;
   if (max_verts == 0) return MP_OK;  // no vertex: nothing to move
   DeviceGuard g(ctx->device);
   const FrameRows faces_p(faces, n_frames);

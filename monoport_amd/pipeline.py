@@ -49,7 +49,8 @@ MESH_KEYS = ("normals", "level", "colors", "clean", "simplify", "smooth")
 
 
 def _mesh_options(mesh, balance, has_netc):
-    """FrameSlot's ``mesh`` argument (a dict or an object with these attributes) -> (normals, level, colors)."""
+    """FrameSlot's ``mesh`` argument (a dict or an object with these attributes) -> recon.MeshOptions."""
+    from .recon import mesh_options
     if isinstance(mesh, dict):
         unknown = sorted(set(mesh) - set(MESH_KEYS))
         if unknown:
@@ -58,38 +59,12 @@ def _mesh_options(mesh, balance, has_netc):
     else:
         def get(key, default=None):
             return getattr(mesh, key, default)
-    normals = get("normals", "accumulate")
-    if normals is not None and normals not in ops.NORMALS_MODES:
-        raise ValueError("FrameSlot(mesh=...): normals must be None or one of %s, got %r"
-                         % (sorted(ops.NORMALS_MODES), normals))
-    level = get("level")
-    colors = get("colors")
-    colors = has_netc if colors is None else bool(colors)
-    if colors and not has_netc:
+    level, colors = get("level"), get("colors")
+    opts = mesh_options(get("normals", "accumulate"), float(balance if level is None else level),
+                        has_netc if colors is None else colors, get("clean"), get("simplify"), get("smooth"))
+    if opts.colors and not has_netc:
         raise ValueError("FrameSlot(mesh=...): colors need netC")
-    return normals, float(balance if level is None else level), colors
-
-
-def _mesh_clean_option(mesh, level):
-    """The ``clean`` entry of FrameSlot's ``mesh`` argument: None, or the connectivity of recon.keep_largest."""
-    from .recon import _check_clean
-    clean = mesh.get("clean") if isinstance(mesh, dict) else getattr(mesh, "clean", None)
-    _check_clean(clean, level)
-    return clean
-
-
-def _mesh_simplify_option(mesh):
-    """The ``simplify`` entry of FrameSlot's ``mesh`` argument: None, or the cells per axis of recon.simplify_mesh."""
-    from .recon import _check_simplify
-    simplify = mesh.get("simplify") if isinstance(mesh, dict) else getattr(mesh, "simplify", None)
-    _check_simplify(simplify)
-    return simplify
-
-
-def _mesh_smooth_option(mesh):
-    """The ``smooth`` entry of FrameSlot's ``mesh`` argument: None, or the keyword arguments of ops.mesh_smooth_raw."""
-    from .recon import _check_smooth
-    return _check_smooth(mesh.get("smooth") if isinstance(mesh, dict) else getattr(mesh, "smooth", None))
+    return opts
 
 
 class FrameSlot:
@@ -101,8 +76,8 @@ class FrameSlot:
                  final_level="dilate3", mesh=None):
         """``mesh``: None (no mesh output; nothing is allocated or enqueued for it), or a dict / options object with
         ``normals`` ("accumulate" -- the default --, "reference" or None), ``level`` (the iso-level; default: the
-        slot's ``balance``) and ``colors`` (per-vertex netC colours; default: ``netC is not None``) and ``clean`` (None -- the default: nothing
-        is allocated or enqueued for it --, or 6 / 26: marching cubes sees only the largest connected body of each
+        slot's ``balance``) and ``colors`` (per-vertex netC colours; default: ``netC is not None``) and ``clean`` (None
+        -- the default: nothing is allocated or enqueued for it --, or 6 / 26: marching cubes sees only the largest connected body of each
         volume, ``recon.keep_largest`` into copies that live in mesh buffers of one mesh chunk of frames;
         ``volumes``, the renders and every other consumer see the unchanged volume) and ``simplify`` (None -- the
         default: nothing is allocated or enqueued for it --, or the cells per axis, 1..512, of ``recon.simplify_mesh``
@@ -111,7 +86,8 @@ class FrameSlot:
         are those of the simplified mesh and the colour query shrinks with it) and ``smooth`` (None -- the default:
         nothing is allocated or enqueued for it --, the iterations, or the dict of ``recon.reconstruct_mesh``'s
         ``smooth``: Taubin passes behind marching cubes / the clustering, into one more vertex buffer, 12 bytes per vertex
-        of capacity; vertices and normals are the smoothed mesh's, the colours are queried before smoothing).  The slot then
+        of capacity; vertices and normals are the smoothed mesh's, the colours are queried before smoothing).  ``self.mesh``
+        is the validated ``recon.MeshOptions`` of all six (None without mesh output).  The slot then
         owns static per-frame mesh buffers at the capacities of ``ops.marching_cubes_raw`` (12 r^2 vertices and
         24 r^2 faces: vertices, faces, normals, query points and predictions are about 57 MB per frame at 257^3), the
         batched mesh chain runs behind the octree on the slot's stream, and ``meshes()`` hands the results out."""
@@ -170,35 +146,30 @@ class FrameSlot:
             self.image_c = torch.zeros((b, 3, 512, 512), dtype=torch.float32, device=dev)
         self.mesh = None if mesh is None else _mesh_options(mesh, self.balance, netC is not None)
         if self.mesh is not None:
-            normals, _, colors = self.mesh
+            opts = self.mesh
             cap_v = 12 * r * r  # ops.marching_cubes_raw's capacities
             cap_f = 2 * cap_v
             self.mesh_buffers = {"verts": torch.empty((b, cap_v, 3), dtype=torch.float32, device=dev),
                                  "faces": torch.empty((b, cap_f, 3), dtype=torch.int32, device=dev),
                                  "counts": torch.zeros((b, 2), dtype=torch.int32, device=dev)}
-            if normals is not None:
+            if opts.normals is not None:
                 self.mesh_buffers["normals"] = torch.empty((b, cap_v, 3), dtype=torch.float32, device=dev)
-            if colors:
+            if opts.colors:
                 self.mesh_buffers["points"] = torch.zeros((b, 3, cap_v), dtype=torch.float32, device=dev)
                 self.mesh_buffers["point_counts"] = torch.zeros((b, 1), dtype=torch.int32, device=dev)
                 self.mesh_buffers["preds"] = torch.zeros((b, 3, cap_v), dtype=torch.float32, device=dev)
+            if opts.clean is not None:
+                chunk = min(MESH_BATCH, b)  # the cleaned copies are consumed chunk by chunk (68 MB per frame at 257^3)
+                self.mesh_buffers["cleaned"] = torch.empty((chunk, r, r, r), dtype=torch.float32, device=dev)
+                self.mesh_buffers["clean_stats"] = torch.zeros((b, 4), dtype=torch.int32, device=dev)
+            if opts.simplify is not None:  # buffers of its own: marching cubes' stay its input
+                self.mesh_buffers["simple_verts"] = torch.empty((b, cap_v, 3), dtype=torch.float32, device=dev)
+                self.mesh_buffers["simple_faces"] = torch.empty((b, cap_f, 3), dtype=torch.int32, device=dev)
+                self.mesh_buffers["simple_counts"] = torch.zeros((b, 2), dtype=torch.int32, device=dev)
+                self.mesh_buffers["simple_vmap"] = torch.empty((b, cap_v), dtype=torch.int32, device=dev)
+            if opts.smooth is not None:  # the vertices before smoothing stay: the colour query reads them
+                self.mesh_buffers["smooth_verts"] = torch.empty((b, cap_v, 3), dtype=torch.float32, device=dev)
             self._mesh_chains = [None] * b
-        # kept beside ``mesh`` (which stays the (normals, level, colors) triple)
-        self.mesh_clean = None if mesh is None else _mesh_clean_option(mesh, self.mesh[1])
-        if self.mesh_clean is not None:
-            chunk = min(MESH_BATCH, b)  # the cleaned copies are consumed chunk by chunk (68 MB per frame at 257^3)
-            self.mesh_buffers["cleaned"] = torch.empty((chunk, r, r, r), dtype=torch.float32, device=dev)
-            self.mesh_buffers["clean_stats"] = torch.zeros((b, 4), dtype=torch.int32, device=dev)
-        # likewise beside ``mesh``: the simplified mesh has buffers of its own (marching cubes' stay its input)
-        self.mesh_simplify = None if mesh is None else _mesh_simplify_option(mesh)
-        if self.mesh_simplify is not None:
-            self.mesh_buffers["simple_verts"] = torch.empty((b, cap_v, 3), dtype=torch.float32, device=dev)
-            self.mesh_buffers["simple_faces"] = torch.empty((b, cap_f, 3), dtype=torch.int32, device=dev)
-            self.mesh_buffers["simple_counts"] = torch.zeros((b, 2), dtype=torch.int32, device=dev)
-            self.mesh_buffers["simple_vmap"] = torch.empty((b, cap_v), dtype=torch.int32, device=dev)
-        self.mesh_smooth = None if mesh is None else _mesh_smooth_option(mesh)
-        if self.mesh_smooth is not None:  # the vertices before smoothing stay: the colour query reads them
-            self.mesh_buffers["smooth_verts"] = torch.empty((b, cap_v, 3), dtype=torch.float32, device=dev)
 
     # convenience views for batch == 1 callers
     @property
@@ -296,34 +267,35 @@ class FrameSlot:
         if self.mesh is not None:
             self._mesh_chain(n)
 
-    def _mesh_binding(self, b):
-        """Frame b's colour query as recon._mesh_chain takes it: netC's head on the slot's own map and calibration."""
+    def _mesh_bindings(self, b0, b1):
+        """The colour queries of frames b0..b1 as recon._mesh_chains takes them (netC's head on the slot's own maps and
+        calibrations), None without colours."""
+        if not self.mesh.colors:
+            return None
         from .modeling.MonoPortNet import QueryBinding
-        return QueryBinding(self.netC, self.netC.surface_classifier.packed(), self.feats_hwc_c[b],
-                            self.calib[b:b + 1], Z_SCALE)
+        mlp_c = self.netC.surface_classifier.packed()
+        return [QueryBinding(self.netC, mlp_c, self.feats_hwc_c[b], self.calib[b:b + 1], Z_SCALE)
+                for b in range(b0, b1)]
 
     def _mesh_chain(self, n):
         """Marching cubes -> normals -> points -> netC colours of the slot's n frames into the slot's mesh buffers,
         MESH_BATCH frames per set of launches, each frame gated by its status[b, 0] (the volume of a frame whose
         coarsest octree level is empty is unspecified: its counts become (0, 0) and nothing else of it is touched).  With
         ``clean`` the chain starts with recon.keep_largest of the chunk's volumes, under the same gates."""
-        from .recon import _mesh_chain_batch
-        normals, level, colors = self.mesh
+        from .recon import _mesh_chains
         chunk = MESH_BATCH
-        if self.mesh_clean is not None:  # one chunk's cleaned volumes at a time, in the same buffer
+        if self.mesh.clean is not None:  # one chunk's cleaned volumes at a time, in the same buffer
             chunk = min(chunk, self.mesh_buffers["cleaned"].shape[0])
         for b0 in range(0, n, chunk):
             b1 = min(b0 + chunk, n)
             out = {k: v[b0:b1] for k, v in self.mesh_buffers.items()}
-            if self.mesh_clean is not None:
+            if self.mesh.clean is not None:
                 out["cleaned"] = self.mesh_buffers["cleaned"][:b1 - b0]
-            if colors:
+            if self.mesh.colors:
                 out["preds"] = list(out["preds"])
-            self._mesh_chains[b0:b1] = _mesh_chain_batch(
-                self.volumes[b0:b1], level, self.b_min, self.b_max, normals,
-                [self._mesh_binding(b) for b in range(b0, b1)] if colors else None,
-                gates=[self.status[b, 0:1] for b in range(b0, b1)], out=out, clean=self.mesh_clean,
-                simplify=self.mesh_simplify, smooth=self.mesh_smooth)
+            self._mesh_chains[b0:b1] = _mesh_chains(
+                self.volumes[b0:b1], self.b_min, self.b_max, self.mesh, self._mesh_bindings(b0, b1),
+                gates=[self.status[b, 0:1] for b in range(b0, b1)], out=out)
 
     def meshes(self):
         """The meshes of the current submission, to be called after ``wait()`` (it waits if the caller has not): a
@@ -334,29 +306,21 @@ class FrameSlot:
         exact capacities here: all of its tensors are then fresh ones."""
         if self.mesh is None:
             raise RuntimeError("FrameSlot.meshes(): the slot was made without mesh=...")
-        from .recon import _finish_mesh, _mesh_chain, _rerun_exact
+        from .recon import _collect_meshes, _mesh_chains
         self.wait()
         n = self.n_active
-        normals, level, colors = self.mesh
         # per frame: alive, (vertices, faces) of the mesh [, with ``simplify``: those marching cubes needed]
         cols = [self.status[:n, 0:1], self.mesh_buffers["counts"][:n]]
-        if self.mesh_simplify is not None:
+        if self.mesh.simplify is not None:
             cols.insert(1, self.mesh_buffers["simple_counts"][:n])
         host = torch.cat(cols, dim=1).cpu().tolist()
-        out = []
-        for b, (alive, *sizes) in enumerate(host):
-            if not alive:
-                out.append(None)
-                continue
 
-            def run(max_verts, max_faces):
-                return _mesh_chain(self.volumes[b], level, self.b_min, self.b_max, normals,
-                                   self._mesh_binding(b) if colors else None, max_verts, max_faces,
-                                   clean=self.mesh_clean, simplify=self.mesh_simplify, smooth=self.mesh_smooth)
+        def rerun(b, max_verts, max_faces):
+            return _mesh_chains([self.volumes[b]], self.b_min, self.b_max, self.mesh, self._mesh_bindings(b, b + 1),
+                                max_verts=max_verts, max_faces=max_faces)[0]
 
-            chain, nv, nf, short = _rerun_exact(run, sizes, self._mesh_chains[b])
-            out.append(_finish_mesh(chain, nv, nf, raw_preds=not short))
-        return out
+        return _collect_meshes([chain if row[0] else None for chain, row in zip(self._mesh_chains, host)],
+                               [row[1:] for row in host], rerun)
 
     def prepare(self, warmup=2):
         """Warm up (scratch arenas, GroupNorm accumulator arena); with ``use_graph`` capture the ENCODER into a

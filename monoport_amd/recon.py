@@ -73,20 +73,22 @@ def color_matrix(b_min, b_max, resolution):
 
 
 def _counted_colours(bindings, pts, counts, outs=None):
-    """netC's predictions [3,cap] at the first counts[f] of the points pts[f] [3,cap]: per frame for a list of
-    bindings (one head, at most ops.MAX_FRAMES), of the one frame for a single binding.  One orthogonal frame is the
-    per-frame counted launch; anything else the batched one, with the projection modes if a frame is perspective."""
-    one = not isinstance(bindings, list)
-    if one:
-        bindings, pts, counts = [bindings], [pts], [counts]
-    b0 = bindings[0]
-    ortho = all(b.projection == ops.PROJECTIONS["orthogonal"] for b in bindings)
-    if one and ortho:
-        return ops.query_counted(b0.mlp, b0.feat_hwc, pts[0], counts[0], b0.calib, b0.z_scale)
-    preds = ops.query_counted_batch(b0.mlp, [b.feat_hwc for b in bindings], pts, counts, [b.calib for b in bindings],
-                                    b0.z_scale, outs=outs,
-                                    projections=None if ortho else [b.projection for b in bindings])
-    return preds[0] if one else preds
+    """netC's predictions [3,cap] per frame at the first counts[f] of the points pts[f] [3,cap]: lists with one entry per
+    frame, ``bindings`` of one head.  One orthogonal frame without buffers of the caller's (``outs``) is the per-frame
+    counted launch; anything else the batched one per ops.MAX_FRAMES frames, with the projection modes if a frame is
+    perspective."""
+    n, preds = len(bindings), []
+    for f0, f1 in ops._frame_chunks(n):
+        chunk = bindings[f0:f1]
+        b0 = chunk[0]
+        ortho = all(b.projection == ops.PROJECTIONS["orthogonal"] for b in chunk)
+        if n == 1 and ortho and outs is None:
+            return [ops.query_counted(b0.mlp, b0.feat_hwc, pts[0], counts[0], b0.calib, b0.z_scale)]
+        preds += ops.query_counted_batch(b0.mlp, [b.feat_hwc for b in chunk], pts[f0:f1], counts[f0:f1],
+                                         [b.calib for b in chunk], b0.z_scale,
+                                         outs=None if outs is None else outs[f0:f1],
+                                         projections=None if ortho else [b.projection for b in chunk])
+    return preds
 
 
 def _bind_netC(who, netC, frames):
@@ -116,7 +118,7 @@ def colorization(netC, feat_tensor_C, X, Y, Z, calib_tensor, norm=None, resoluti
     feat_tensor_C = [[f.to(device) for f in feats] for feats in feat_tensor_C]  # main.py:229-230
     X, Y, Z = X.to(device), Y.to(device), Z.to(device)
     pts = ops.vertex_points(X, Y, Z.float(), count.to(device), resolution, mat_color)
-    preds = _counted_colours(netC.bind(feat_tensor_C, calib_tensor), pts, count.to(device))
+    preds = _counted_colours([netC.bind(feat_tensor_C, calib_tensor)], [pts], [count.to(device)])[0]
     return ops.paint(X, Y, preds, 1, count.to(device), resolution, 0.5, 0.5, -np.inf, np.inf)
 
 
@@ -170,90 +172,123 @@ Mesh.__doc__ = """Triangle mesh of ``reconstruct_mesh``: verts [V,3] f32 world c
 normals [V,3] f32 or None, colors [V,3] f32 in [0,1] or None."""
 
 
-def _check_clean(clean, level):
-    """The ``clean`` option of the mesh calls: None, or the connectivity (6 / 26) of ``keep_largest`` in front of
-    marching cubes; dropped voxels become 0.0, which must lie below the level."""
-    if clean is None:
-        return
-    if clean not in ops.CONNECTIVITIES:
-        raise ValueError("clean must be None or one of %s, got %r" % (list(ops.CONNECTIVITIES), clean))
-    if not float(level) > 0.0:
-        raise ValueError("clean fills the dropped voxels with 0.0: it needs level > 0, got %r" % (level,))
-
-
-def _check_simplify(simplify):
-    """The ``simplify`` option of the mesh calls: None, or the cells per axis (an int in 1..512) of the vertex
-    clustering between marching cubes and the normals / colours, over the call's box."""
-    if simplify is not None:
-        ops._simplify_cells("simplify", simplify)
-
-
 SMOOTH_KEYS = ("iterations", "lam", "mu", "pin_border")
 SMOOTH_DEFAULTS = {"iterations": 10, "lam": 0.5, "mu": -0.53, "pin_border": True}
 
-
-def _check_smooth(smooth):
-    """The ``smooth`` option of the mesh calls: None, the iterations (an int in 1..64) of ``ops.mesh_smooth_raw`` at
-    its default factors, or a dict with ``iterations`` and any of ``lam``, ``mu``, ``pin_border``.  -> None, or the
-    keyword arguments of ``ops.mesh_smooth_raw``."""
-    if smooth is None:
-        return None
-    if isinstance(smooth, dict):
-        unknown = sorted(set(smooth) - set(SMOOTH_KEYS))
-        if unknown or "iterations" not in smooth:
-            raise ValueError("smooth: a dict has 'iterations' and any of %s, got %r" % (list(SMOOTH_KEYS[1:]), smooth))
-        kw = dict(SMOOTH_DEFAULTS, **smooth)
-    else:
-        kw = dict(SMOOTH_DEFAULTS, iterations=smooth)
-    ops._smooth_params("smooth", kw["iterations"], kw["lam"], kw["mu"], kw["pin_border"])
-    return kw
+MeshOptions = collections.namedtuple("MeshOptions", ["normals", "level", "colors", "clean", "simplify", "smooth"])
+MeshOptions.__doc__ = """What a mesh chain is asked for, validated by ``mesh_options``: the normals mode or None, the
+iso-level, whether netC colours the vertices, and per optional stage None (nothing allocated or enqueued for it) or its
+setting: ``clean`` the connectivity of ``keep_largest``, ``simplify`` the cells per axis of the vertex clustering,
+``smooth`` the keyword arguments of ``ops.mesh_smooth_raw``."""
 
 
-def _mesh_chain(sdf, level, b_min, b_max, normals, binding, max_verts=None, max_faces=None, clean=None,
-                simplify=None, smooth=None):
-    """volume [-> its largest body] -> verts, faces [-> their vertex clustering] [-> Taubin passes] -> normals ->
-    colours, enqueued without a host value in between.  With ``simplify`` the tuple has a sixth entry, marching cubes'
-    own counts (what the capacities are compared with); verts, faces and counts are then the simplified mesh's.
-    ``smooth`` (what ``_check_smooth`` returns): verts and normals are the smoothed mesh's; the colour query takes the
-    positions before smoothing, which lie on the iso-surface."""
-    if clean is not None:  # into a scratch volume: the caller's is never modified
-        sdf = ops.keep_largest_raw(sdf, level, clean, CLEAN_FILL)[0]
-    verts, faces, counts = ops.marching_cubes_raw(sdf, level, b_min, b_max, max_verts=max_verts,
-                                                  max_faces=max_faces)
+def mesh_options(normals="accumulate", level=0.5, colors=False, clean=None, simplify=None, smooth=None):
+    """The ``MeshOptions`` of the mesh calls' arguments, or ValueError.  ``normals``: None or a mode of
+    ``ops.NORMALS_MODES``.  ``clean``: None, or 6 / 26; dropped voxels become 0.0, which must lie below the level.
+    ``simplify``: None, or an int in 1..512.  ``smooth``: None, the iterations (an int in 1..64) of
+    ``ops.mesh_smooth_raw`` at its default factors, or a dict with ``iterations`` and any of ``lam``, ``mu``,
+    ``pin_border``; the record holds the full keyword dict."""
+    if normals is not None and normals not in ops.NORMALS_MODES:
+        raise ValueError("normals must be None or one of %s, got %r" % (sorted(ops.NORMALS_MODES), normals))
+    if clean is not None:
+        if clean not in ops.CONNECTIVITIES:
+            raise ValueError("clean must be None or one of %s, got %r" % (list(ops.CONNECTIVITIES), clean))
+        if not float(level) > 0.0:
+            raise ValueError("clean fills the dropped voxels with 0.0: it needs level > 0, got %r" % (level,))
     if simplify is not None:
-        mc_counts = counts
-        verts, faces, counts, _ = ops.mesh_simplify_raw(verts, faces, counts, simplify, b_min, b_max)
-    on_surface = verts
+        ops._simplify_cells("simplify", simplify)
     if smooth is not None:
-        verts = ops.mesh_smooth_raw(verts, faces, counts, **smooth)
-    nrm = ops.mesh_normals_raw(verts, faces, counts, normals) if normals is not None else None
-    col = None
-    if binding is not None:
-        pts, count = ops.mesh_points_raw(on_surface, counts)
-        col = (_counted_colours(binding, pts, count) * 0.5 + 0.5).t()
-    if simplify is not None:
-        return verts, faces, counts, nrm, col, mc_counts
-    return verts, faces, counts, nrm, col
+        if isinstance(smooth, dict):
+            unknown = sorted(set(smooth) - set(SMOOTH_KEYS))
+            if unknown or "iterations" not in smooth:
+                raise ValueError("smooth: a dict has 'iterations' and any of %s, got %r"
+                                 % (list(SMOOTH_KEYS[1:]), smooth))
+            smooth = dict(SMOOTH_DEFAULTS, **smooth)
+        else:
+            smooth = dict(SMOOTH_DEFAULTS, iterations=smooth)
+        ops._smooth_params("smooth", smooth["iterations"], smooth["lam"], smooth["mu"], smooth["pin_border"])
+    return MeshOptions(normals, level, bool(colors), clean, simplify, smooth)
 
 
-def _chain_sizes(chain):
+MeshChain = collections.namedtuple("MeshChain", ["verts", "faces", "counts", "normals", "preds", "mc_counts"])
+MeshChain.__doc__ = """What ``_mesh_chains`` leaves on the device for one volume, capacity-sized: verts [max_v,3], faces
+[max_f,3], counts int32[2] of the mesh handed out (the simplified, smoothed one if asked for), its normals [max_v,3] or
+None, netC's raw predictions [3,max_v] or None, and with ``simplify`` marching cubes' own counts (what the capacities
+are compared with), else None."""
+
+
+def _mesh_chains(sdfs, b_min, b_max, opts, bindings=None, gates=None, out=None, max_verts=None, max_faces=None):
+    """volume [-> its largest body] -> verts, faces [-> their vertex clustering] [-> Taubin passes] -> normals ->
+    netC predictions for volumes of one size, every stage one set of launches for all of them and no host value in
+    between: one ``MeshChain`` per volume (the chain of one volume is this on a list of one).  ``opts``: a
+    ``MeshOptions``.  ``bindings``: None or one QueryBinding per volume (one head); the colour query takes the positions
+    before smoothing, which lie on the iso-surface.  ``gates``: as ``ops.marching_cubes_raw_batch``'s, for ``clean``
+    too; a gated-off frame's counts of (0, 0) switch the later stages off.  ``out``: None or a dict of the caller's
+    buffers (verts, faces, counts, normals, points, point_counts: [n, ...] tensors, preds: a list; with ``clean`` also
+    cleaned [n,R,R,R] and clean_stats [n,4], with ``simplify`` simple_verts, simple_faces, simple_counts, simple_vmap,
+    with ``smooth`` smooth_verts).  ``max_verts`` / ``max_faces``: marching cubes' capacities, if not its defaults."""
+    out = out or {}
+    n = len(sdfs)
+    if opts.clean is not None:  # into a scratch volume: the caller's is never modified
+        cc_out = (out["cleaned"], out["clean_stats"]) if "cleaned" in out else None
+        sdfs = [c[0] for c in ops.keep_largest_raw_batch(sdfs, opts.level, opts.clean, CLEAN_FILL, gates=gates,
+                                                         out=cc_out)]
+    mc_out = (out["verts"], out["faces"], out["counts"]) if "verts" in out else None
+    raws = ops.marching_cubes_raw_batch(sdfs, opts.level, b_min, b_max, max_verts=max_verts, max_faces=max_faces,
+                                        gates=gates, out=mc_out)
+    verts, faces, counts = ([r[k] for r in raws] for k in range(3))
+    mc_counts = [None] * n
+    if opts.simplify is not None:
+        mc_counts = counts
+        sm_out = (tuple(out["simple_" + k] for k in ("verts", "faces", "counts", "vmap"))
+                  if "simple_verts" in out else None)
+        raws = ops.mesh_simplify_raw_batch(verts, faces, counts, opts.simplify, b_min, b_max, out=sm_out)
+        verts, faces, counts = ([r[k] for r in raws] for k in range(3))
+    on_surface = verts
+    if opts.smooth is not None:
+        verts = ops.mesh_smooth_raw_batch(verts, faces, counts, out=out.get("smooth_verts"), **opts.smooth)
+    nrm = [None] * n
+    if opts.normals is not None:
+        nrm = ops.mesh_normals_raw_batch(verts, faces, counts, opts.normals, out=out.get("normals"))
+    preds = [None] * n
+    if bindings is not None:
+        pt_out = (out["points"], out["point_counts"]) if "points" in out else None
+        pts = ops.mesh_points_raw_batch(on_surface, counts, out=pt_out)
+        preds = _counted_colours(list(bindings), [p[0] for p in pts], [p[1] for p in pts], outs=out.get("preds"))
+    return [MeshChain(*frame) for frame in zip(verts, faces, counts, nrm, preds, mc_counts)]
+
+
+def _finish_mesh(chain, nv, nf):
+    """The ``Mesh`` of a chain's capacity-sized tensors once the counts are on the host."""
+    col = chain.preds
+    if col is not None:  # elementwise: the same bits as over the whole capacity
+        col = (col[:, :nv] * 0.5 + 0.5).t().contiguous()
+    return Mesh(chain.verts[:nv], chain.faces[:nf], None if chain.normals is None else chain.normals[:nv], col)
+
+
+def _device_sizes(chain):
     """The counts a chain leaves on the device, as one tensor: (vertices, faces) of the mesh, followed with
     ``simplify`` by the (vertices, faces) marching cubes needed."""
-    return chain[2] if len(chain) == 5 else torch.cat([chain[2][:2], chain[5][:2]])
+    return chain.counts if chain.mc_counts is None else torch.cat([chain.counts[:2], chain.mc_counts[:2]])
 
 
-def _rerun_exact(run, sizes, chain):
-    """``sizes`` (host list of ``_chain_sizes``) -> (chain, vertices, faces, re-run?): if marching cubes needed more
-    than the chain's capacities, ``run(max_verts, max_faces)`` makes the whole chain again with exact capacities (with
-    ``simplify`` that costs one more host copy, for the new counts)."""
-    nv, nf = sizes[0], sizes[1]
-    need_v, need_f = sizes[-2], sizes[-1]
-    if need_v <= chain[0].shape[0] and need_f <= chain[1].shape[0]:
-        return chain, nv, nf, False
-    chain = run(need_v, need_f)
-    if len(chain) != 5:
-        nv, nf = chain[2].cpu().tolist()[:2]
-    return chain, nv, nf, True
+def _collect_meshes(chains, sizes, rerun):
+    """The ``Mesh`` of every chain (None for a None) once ``sizes``, per chain the host list of ``_device_sizes``, is
+    there: a chain whose marching cubes needed more than its capacities is made again alone with exact ones by
+    ``rerun(k, max_verts, max_faces)`` (with ``simplify`` that costs one more host copy, for the new counts)."""
+    meshes = []
+    for k, (chain, size) in enumerate(zip(chains, sizes)):
+        if chain is None:
+            meshes.append(None)
+            continue
+        nv, nf = size[0], size[1]
+        need_v, need_f = size[-2], size[-1]
+        if need_v > chain.verts.shape[0] or need_f > chain.faces.shape[0]:
+            chain = rerun(k, need_v, need_f)
+            if chain.mc_counts is not None:
+                nv, nf = chain.counts.cpu().tolist()[:2]
+        meshes.append(_finish_mesh(chain, nv, nf))
+    return meshes
 
 
 @torch.no_grad()
@@ -276,79 +311,16 @@ def reconstruct_mesh(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normal
     do not change: the one host sync and the re-run are as before."""
     if sdf is None:
         return None
-    _check_normals(normals)
-    _check_clean(clean, level)
-    _check_simplify(simplify)
-    smooth = _check_smooth(smooth)
-    binding = None
+    opts = mesh_options(normals, level, netC is not None, clean, simplify, smooth)
+    bindings = None
     if netC is not None:
-        binding = _bind_netC("reconstruct_mesh", netC, [(feat_tensor_C, calib_tensor, sdf.device)])[0]
+        bindings = _bind_netC("reconstruct_mesh", netC, [(feat_tensor_C, calib_tensor, sdf.device)])
 
-    def run(max_verts=None, max_faces=None):
-        return _mesh_chain(sdf, level, b_min, b_max, normals, binding, max_verts, max_faces, clean=clean,
-                           simplify=simplify, smooth=smooth)
+    def run(k=0, max_verts=None, max_faces=None):
+        return _mesh_chains([sdf], b_min, b_max, opts, bindings, max_verts=max_verts, max_faces=max_faces)[0]
 
     chain = run()
-    chain, nv, nf, _ = _rerun_exact(run, _chain_sizes(chain).cpu().tolist(), chain)  # the one host sync
-    return _finish_mesh(chain, nv, nf)
-
-
-def _check_normals(normals):
-    if normals is not None and normals not in ops.NORMALS_MODES:
-        raise ValueError("normals must be None or one of %s, got %r" % (sorted(ops.NORMALS_MODES), normals))
-
-
-def _mesh_chain_batch(sdfs, level, b_min, b_max, normals, bindings, gates=None, out=None, clean=None, simplify=None,
-                      smooth=None):
-    """``_mesh_chain`` for volumes of one size, every stage one set of launches for all of them: a list of
-    (verts, faces, counts, normals or None, netC predictions [3,max_v] or None) per volume, nothing synchronised
-    (``_finish_mesh(..., raw_preds=True)`` turns the predictions of the vertices present into colours).
-    ``bindings``: None or one QueryBinding per volume (one head).  ``out``: None or a dict of the caller's buffers
-    (verts, faces, counts, normals, points, point_counts, preds: [n, ...] tensors, preds a list; with ``clean`` also
-    cleaned [n,R,R,R] and clean_stats [n,4]).  ``clean``: None or the connectivity of ``keep_largest`` in front of
-    marching cubes, under the same gates.  ``simplify``: None or the cells per axis of the vertex clustering behind
-    marching cubes (``out``: simple_verts, simple_faces, simple_counts, simple_vmap); a gated-off frame's counts of
-    (0, 0) switch it off too.  Each tuple then ends with marching cubes' own counts, as ``_mesh_chain``'s.
-    ``smooth``: None or what ``_check_smooth`` returns (``out``: smooth_verts); as in ``_mesh_chain``."""
-    out = out or {}
-    n = len(sdfs)
-    if clean is not None:
-        cc_out = (out["cleaned"], out["clean_stats"]) if "cleaned" in out else None
-        sdfs = [c[0] for c in ops.keep_largest_raw_batch(sdfs, level, clean, CLEAN_FILL, gates=gates, out=cc_out)]
-    mc_out = (out["verts"], out["faces"], out["counts"]) if "verts" in out else None
-    raws = ops.marching_cubes_raw_batch(sdfs, level, b_min, b_max, gates=gates, out=mc_out)
-    verts, faces, counts = ([r[k] for r in raws] for k in range(3))
-    if simplify is not None:
-        mc_counts = counts
-        sm_out = (tuple(out["simple_" + k] for k in ("verts", "faces", "counts", "vmap"))
-                  if "simple_verts" in out else None)
-        raws = ops.mesh_simplify_raw_batch(verts, faces, counts, simplify, b_min, b_max, out=sm_out)
-        verts, faces, counts = ([r[k] for r in raws] for k in range(3))
-    on_surface = verts
-    if smooth is not None:
-        verts = ops.mesh_smooth_raw_batch(verts, faces, counts, out=out.get("smooth_verts"), **smooth)
-    nrm = [None] * n
-    if normals is not None:
-        nrm = ops.mesh_normals_raw_batch(verts, faces, counts, normals, out=out.get("normals"))
-    preds = [None] * n
-    if bindings is not None:
-        pt_out = (out["points"], out["point_counts"]) if "points" in out else None
-        pts = ops.mesh_points_raw_batch(on_surface, counts, out=pt_out)
-        preds = []
-        for f0, f1 in ops._frame_chunks(n):
-            preds += _counted_colours(list(bindings[f0:f1]), [p[0] for p in pts[f0:f1]], [p[1] for p in pts[f0:f1]],
-                                      outs=None if "preds" not in out else out["preds"][f0:f1])
-    if simplify is not None:
-        return [(verts[f], faces[f], counts[f], nrm[f], preds[f], mc_counts[f]) for f in range(n)]
-    return [(verts[f], faces[f], counts[f], nrm[f], preds[f]) for f in range(n)]
-
-
-def _finish_mesh(chain, nv, nf, raw_preds=False):
-    """The ``Mesh`` of a chain's capacity-sized tensors once the counts are on the host."""
-    verts, faces, _, nrm, col = chain[:5]
-    if col is not None:  # elementwise: the same bits whether the rows are cut before or after
-        col = ((col[:, :nv] * 0.5 + 0.5).t() if raw_preds else col[:nv]).contiguous()
-    return Mesh(verts[:nv], faces[:nf], None if nrm is None else nrm[:nv], col)
+    return _collect_meshes([chain], [_device_sizes(chain).cpu().tolist()], run)[0]  # the one host sync
 
 
 @torch.no_grad()
@@ -362,10 +334,7 @@ def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), 
     entry per volume (those of ``None`` volumes are not looked at).  A volume whose capacity guess was short is
     re-run alone with exact capacities, as ``reconstruct_mesh`` does.  A multi-view ``netC`` is not served here."""
     sdfs = list(sdfs)
-    _check_normals(normals)
-    _check_clean(clean, level)
-    _check_simplify(simplify)
-    smooth = _check_smooth(smooth)
+    opts = mesh_options(normals, level, netC is not None, clean, simplify, smooth)
     if netC is not None:
         if feat_tensors_C is None or calib_tensors is None:
             raise ValueError("reconstruct_mesh_many: netC needs feat_tensors_C and calib_tensors")
@@ -384,17 +353,26 @@ def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), 
     if not idx:
         return meshes
     live = [sdfs[i] for i in idx]
-    chains = _mesh_chain_batch(live, level, b_min, b_max, normals, bindings, clean=clean, simplify=simplify,
-                               smooth=smooth)
-    sizes = torch.stack([_chain_sizes(c) for c in chains]).cpu().tolist()  # the one host sync
-    for k, i in enumerate(idx):
-        def run(max_verts, max_faces):
-            return _mesh_chain(live[k], level, b_min, b_max, normals, None if bindings is None else bindings[k],
-                               max_verts, max_faces, clean=clean, simplify=simplify, smooth=smooth)
 
-        chain, nv, nf, short = _rerun_exact(run, sizes[k], chains[k])
-        meshes[i] = _finish_mesh(chain, nv, nf, raw_preds=not short)
+    def rerun(k, max_verts, max_faces):
+        return _mesh_chains([live[k]], b_min, b_max, opts, None if bindings is None else [bindings[k]],
+                            max_verts=max_verts, max_faces=max_faces)[0]
+
+    chains = _mesh_chains(live, b_min, b_max, opts, bindings)
+    sizes = torch.stack([_device_sizes(c) for c in chains]).cpu().tolist()  # the one host sync
+    for i, mesh in zip(idx, _collect_meshes(chains, sizes, rerun)):
+        meshes[i] = mesh
     return meshes
+
+
+def _shape_counts(pairs):
+    """int32 [n,2] = the (vertices, faces) that the shapes of n (verts, faces) pairs give, on the pairs' device (through
+    pinned memory, nothing waited for)."""
+    counts = torch.tensor([[v.shape[0], f.shape[0]] for v, f in pairs], dtype=torch.int32)
+    dev = pairs[0][0].device
+    if dev.type == "cuda":
+        counts = counts.pin_memory().to(dev, non_blocking=True)
+    return counts
 
 
 @torch.no_grad()
@@ -408,12 +386,9 @@ def simplify_mesh(mesh, cells, b_min=(-1, -1, -1), b_max=(1, 1, 1), normals="acc
     ``(None, None)`` for ``mesh is None``."""
     if mesh is None:
         return None, None
-    _check_normals(normals)
-    _check_simplify(cells)
+    mesh_options(normals, simplify=cells)
     verts, faces = ops._f32c(mesh[0]), mesh[1].contiguous()
-    counts = torch.tensor([verts.shape[0], faces.shape[0]], dtype=torch.int32)
-    if verts.device.type == "cuda":
-        counts = counts.pin_memory().to(verts.device, non_blocking=True)
+    counts = _shape_counts([(verts, faces)])[0]
     v, f, c, vmap = ops.mesh_simplify_raw(verts, faces, counts, cells, b_min, b_max)
     nrm = ops.mesh_normals_raw(v, f, c, normals) if normals is not None else None
     nv, nf = c.cpu().tolist()
@@ -432,12 +407,9 @@ def smooth_mesh(mesh, iterations=10, lam=0.5, mu=-0.53, pin_border=True, normals
     (DESIGN.md section 4.8.5).  No host sync.  None for ``mesh is None``."""
     if mesh is None:
         return None
-    _check_normals(normals)
-    kw = _check_smooth(dict(iterations=iterations, lam=lam, mu=mu, pin_border=pin_border))
+    kw = mesh_options(normals, smooth=dict(iterations=iterations, lam=lam, mu=mu, pin_border=pin_border)).smooth
     verts, faces = ops._f32c(mesh[0]), mesh[1].contiguous()
-    counts = torch.tensor([verts.shape[0], faces.shape[0]], dtype=torch.int32)
-    if verts.device.type == "cuda":
-        counts = counts.pin_memory().to(verts.device, non_blocking=True)
+    counts = _shape_counts([(verts, faces)])[0]
     out = ops.mesh_smooth_raw(verts, faces, counts, **kw)
     nrm = ops.mesh_normals_raw(out, faces, counts, normals) if normals is not None else None
     return Mesh(out, faces, nrm, mesh[3] if len(mesh) > 3 else None)
@@ -502,13 +474,10 @@ def render_mesh_many(meshes, calibs, res=257, shade="colors", projection="orthog
     live = [meshes[i] for i in idx]
     shaded = [_shade_attr(who, m, shade) for m in live]
     scale, bias, lo, hi = shaded[0][1]
-    dev = live[0].verts.device
     verts = [m.verts.contiguous() for m in live]
     faces = [m.faces.contiguous() for m in live]
     attrs = None if shade is None else [ops._f32c(a) for a, _ in shaded]
-    sizes = torch.tensor([[v.shape[0], f.shape[0]] for v, f in zip(verts, faces)], dtype=torch.int32)
-    if dev.type == "cuda":
-        sizes = sizes.pin_memory().to(dev, non_blocking=True)
+    sizes = _shape_counts(list(zip(verts, faces)))
     capacity = (max(v.shape[0] for v in verts), max(f.shape[0] for f in faces))
     raws = ops._mesh_render(who, verts, faces, list(sizes.unbind(0)), attrs, cams, res, projection, nearest, False,
                             scale, bias, lo, hi, background, None, capacity=capacity)

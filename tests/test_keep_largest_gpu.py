@@ -383,7 +383,7 @@ def _binding(nets, slot, b):
 def test_slot_clean(nets, ops):
     """Two frames of the synthetic body from two cameras, and a third whose camera looks past the box (its coarsest
     level is empty, its volume unspecified: gated off on the device)."""
-    from monoport_amd.recon import _finish_mesh, _mesh_chain, pifu_calib
+    from monoport_amd.recon import _finish_mesh, _mesh_chains, mesh_options, pifu_calib
     images = torch.stack([torch.from_numpy(syn.synthetic_image(k)) for k in range(3)]).to(DEV)
     away = torch.eye(4, device=DEV)[None]
     away[0, 0, 3] = 5.0
@@ -391,8 +391,9 @@ def test_slot_clean(nets, ops):
     plain = _slot(nets, 3, (17, 33, 65), mesh={"normals": "accumulate"})
     slot = _slot(nets, 3, (17, 33, 65), mesh={"normals": "accumulate", "clean": 6})
     try:
-        # the option lives beside the (normals, level, colors) triple; without it nothing is allocated
-        assert slot.mesh == plain.mesh == ("accumulate", 0.5, True) and slot.mesh_clean == 6 and plain.mesh_clean is None
+        # the option is a field of the slot's record; without it nothing is allocated
+        assert slot.mesh._replace(clean=None) == plain.mesh and tuple(plain.mesh[:3]) == ("accumulate", 0.5, True)
+        assert slot.mesh.clean == 6 and plain.mesh.clean is None
         assert "cleaned" not in plain.mesh_buffers and "clean_stats" not in plain.mesh_buffers
         assert slot.mesh_buffers["cleaned"].shape == (3, 65, 65, 65)
         for s in (plain, slot):
@@ -405,8 +406,9 @@ def test_slot_clean(nets, ops):
             assert torch.equal(slot.renders[b], plain.renders[b]) and torch.equal(slot.renders_tex[b], plain.renders_tex[b])
         assert slot.mesh_buffers["clean_stats"][2].cpu().tolist() == [0, 0, 0, -1]
         for b in range(2):
-            chain = _mesh_chain(slot.volumes[b], 0.5, BMIN, BMAX, "accumulate", _binding(nets, slot, b), clean=6)
-            nv, nf = chain[2].cpu().tolist()
+            chain = _mesh_chains([slot.volumes[b]], BMIN, BMAX, mesh_options("accumulate", 0.5, True, clean=6),
+                                 [_binding(nets, slot, b)])[0]
+            nv, nf = chain.counts.cpu().tolist()
             _same_mesh(got[b], _finish_mesh(chain, nv, nf), "frame %d" % b)
             stats = slot.mesh_buffers["clean_stats"][b].cpu().tolist()
             assert stats == ops.keep_largest_raw(slot.volumes[b], 0.5, 6, 0.0)[1].cpu().tolist() and stats[2] > 1000
@@ -440,7 +442,7 @@ def test_slot_clean_chunks(nets, ops, mesh_batch, monkeypatch):
     """Five frames, the volumes filled in by hand (a floater, one body, a gated-off frame of NaNs, an empty volume,
     noise), in chunks of 2 + 2 + 1 frames and in one: the cleaned copies live in ONE chunk's buffer."""
     from monoport_amd import pipeline
-    from monoport_amd.recon import _finish_mesh, _mesh_chain
+    from monoport_amd.recon import _finish_mesh, _mesh_chains, mesh_options
     if mesh_batch is not None:
         monkeypatch.setattr(pipeline, "MESH_BATCH", mesh_batch)
     vols = [_dev(kl.volume("body_floater33")), _dev(syn.sphere_volume(33)), torch.full((33, 33, 33), float("nan"), device=DEV),
@@ -460,8 +462,8 @@ def test_slot_clean_chunks(nets, ops, mesh_batch, monkeypatch):
         got = slot.meshes()
         assert got[2] is None and got[3].verts.shape[0] == 0
         for b in (0, 1, 3, 4):
-            chain = _mesh_chain(vols[b], 0.5, BMIN, BMAX, "reference", None, clean=26)
-            nv, nf = chain[2].cpu().tolist()
+            chain = _mesh_chains([vols[b]], BMIN, BMAX, mesh_options("reference", 0.5, clean=26))[0]
+            nv, nf = chain.counts.cpu().tolist()
             _same_mesh(got[b], _finish_mesh(chain, nv, nf), "frame %d" % b)
             assert torch.equal(_bits_t(slot.volumes[b]), _bits_t(vols[b]))
         assert [slot.mesh_buffers["clean_stats"][b].cpu().tolist() for b in (0, 2, 3)] == [

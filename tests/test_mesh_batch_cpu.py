@@ -92,16 +92,50 @@ def test_new_entry_points_are_bound_as_the_header_declares():
 
 
 def test_slot_mesh_options():
-    from monoport_amd import pipeline
-    assert pipeline._mesh_options({}, 0.5, True) == ("accumulate", 0.5, True)
-    assert pipeline._mesh_options({"normals": None, "level": 0.25}, 0.5, False) == (None, 0.25, False)
-    assert pipeline._mesh_options({"normals": "reference", "colors": False}, 0.4, True) == ("reference", 0.4, False)
+    from monoport_amd import pipeline, recon
+    assert tuple(pipeline._mesh_options({}, 0.5, True)[:3]) == ("accumulate", 0.5, True)
+    assert tuple(pipeline._mesh_options({"normals": None, "level": 0.25}, 0.5, False)[:3]) == (None, 0.25, False)
+    assert tuple(pipeline._mesh_options({"normals": "reference", "colors": False}, 0.4, True)[:3]) == ("reference", 0.4, False)
 
     class Options:
         normals = "reference"
 
-    assert pipeline._mesh_options(Options(), 0.5, False) == ("reference", 0.5, False)
+    assert tuple(pipeline._mesh_options(Options(), 0.5, False)[:3]) == ("reference", 0.5, False)
     for bad in ({"normals": "area"}, {"colours": True}, {"colors": True}):
         with pytest.raises(ValueError):
             pipeline._mesh_options(bad, 0.5, False)
     assert 1 <= pipeline.MESH_BATCH <= pipeline.MAX_RECON_BATCH
+
+    # clean, simplify, smooth: fields of the same record, from a dict and from an object with attributes alike
+    def as_object(options):
+        return type("Options", (), dict(options))()
+
+    three = dict(iterations=3, lam=0.5, mu=-0.53, pin_border=True)
+    other = dict(iterations=2, lam=0.3, mu=-0.31, pin_border=False)
+    for form in (dict, as_object):
+        opts = pipeline._mesh_options(form({}), 0.5, True)
+        assert isinstance(opts, recon.MeshOptions) and opts._fields[3:] == ("clean", "simplify", "smooth")
+        assert opts.clean is None and opts.simplify is None and opts.smooth is None
+        for key, value, want in (("clean", 6, 6), ("clean", 26, 26), ("simplify", 16, 16), ("simplify", 1, 1),
+                                 ("simplify", 512, 512), ("smooth", 3, three), ("smooth", {"iterations": 3}, three),
+                                 ("smooth", other, other)):
+            opts = pipeline._mesh_options(form({key: value}), 0.5, True)
+            assert getattr(opts, key) == want, (key, value)
+            assert opts._replace(**{key: None}) == pipeline._mesh_options(form({}), 0.5, True), (key, value)
+        assert pipeline._mesh_options(form({"clean": 6, "level": 0.25}), 0.5, False) == recon.MeshOptions(
+            "accumulate", 0.25, False, 6, None, None)
+        with pytest.raises(ValueError, match="clean must be None or one of"):
+            pipeline._mesh_options(form({"clean": 7}), 0.5, True)
+        with pytest.raises(ValueError, match="clean .* level > 0"):
+            pipeline._mesh_options(form({"clean": 6, "level": 0}), 0.5, True)
+        for bad in (0, 513, 16.0):
+            with pytest.raises(ValueError, match="simplify: cells per axis"):
+                pipeline._mesh_options(form({"simplify": bad}), 0.5, True)
+        for bad in (0, 65, -1, 3.0, "3", True, {}, {"lam": 0.5}, {"iterations": 3, "lambda": 0.5},
+                    {"iterations": 3, "mu": float("nan")}, {"iterations": 3, "pin_border": "yes"}):
+            with pytest.raises(ValueError, match="smooth: "):
+                pipeline._mesh_options(form({"smooth": bad}), 0.5, True)
+    with pytest.raises(ValueError, match="normals"):
+        pipeline._mesh_options(as_object({"normals": "area"}), 0.5, True)
+    with pytest.raises(ValueError, match="colors need netC"):
+        pipeline._mesh_options(as_object({"colors": True}), 0.5, False)

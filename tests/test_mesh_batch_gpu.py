@@ -316,9 +316,138 @@ def test_reconstruct_mesh_many(ops, vols33, colour, projection, monkeypatch):
     monkeypatch.setattr(ops, "marching_cubes_raw_batch", short)
     again = reconstruct_mesh_many(sdfs, 0.5, BMIN, BMAX, netC=net, feat_tensors_C=feats, calib_tensors=calibs)
     monkeypatch.undo()
-    assert calls == [None] and again[1] is None
+    # one call for all volumes at the default guess, then each live volume alone at what it needs
+    assert calls == [None, want[0].verts.shape[0], want[2].verts.shape[0]] and again[1] is None
     for i in (0, 2):
         _same_mesh(again[i], want[i], "re-run, frame %d" % i)
+
+
+def _body_floater():
+    """A sphere of radius 0.5 about the origin and a small blob at (0.75, 0.75, 0.75)."""
+    g = ((np.arange(33) + 0.5) / 33) * 2 - 1
+    z, y, x = np.meshgrid(g, g, g, indexing="ij")
+    body = np.sqrt(x * x + y * y + z * z) < 0.5
+    blob = np.sqrt((x - 0.75) ** 2 + (y - 0.75) ** 2 + (z - 0.75) ** 2) < 0.12
+    return np.where(body | blob, 0.9, 0.1).astype(np.float32)
+
+
+THREE = dict(iterations=3, lam=0.5, mu=-0.53, pin_border=True)
+
+
+def _by_hand(ops, vol, binding, clean=None, simplify=None, smooth=None):
+    """reconstruct_mesh(vol, normals="accumulate", netC=...) composed from the raw per-frame calls -> (Mesh, the
+    capacity-sized vertices before and after smoothing, marching cubes' counts).  An orthogonal binding is queried by
+    the per-frame counted call, a perspective one by the batched call of one frame."""
+    from monoport_amd.recon import Mesh
+    if clean is not None:
+        vol = ops.keep_largest_raw(vol, 0.5, clean, 0.0)[0]
+    verts, faces, counts = ops.marching_cubes_raw(vol, 0.5, BMIN, BMAX)
+    mc_counts = counts
+    if simplify is not None:
+        verts, faces, counts, _ = ops.mesh_simplify_raw(verts, faces, counts, simplify, BMIN, BMAX)
+    moved = verts if smooth is None else ops.mesh_smooth_raw(verts, faces, counts, **smooth)
+    nrm = ops.mesh_normals_raw(moved, faces, counts, "accumulate")
+    pts, count = ops.mesh_points_raw(verts, counts)
+    if binding.projection == ops.PROJECTIONS["orthogonal"]:
+        col = ops.query_counted(binding.mlp, binding.feat_hwc, pts, count, binding.calib, binding.z_scale)
+    else:
+        col = ops.query_counted_batch(binding.mlp, [binding.feat_hwc], [pts], [count], [binding.calib], binding.z_scale,
+                                      projections=[binding.projection])[0]
+    nv, nf = counts.cpu().tolist()
+    mesh = Mesh(moved[:nv], faces[:nf], nrm[:nv], (col * 0.5 + 0.5).t()[:nv].contiguous())
+    return mesh, verts, moved, mc_counts.cpu().tolist()
+
+
+def _count_queries(ops, monkeypatch):
+    """-> the list that every counted colour query from now on appends its kind to."""
+    kinds = []
+    for kind in ("query_counted", "query_counted_batch"):
+        def counted(*args, _real=getattr(ops, kind), _kind=kind, **kw):
+            kinds.append(_kind)
+            return _real(*args, **kw)
+
+        monkeypatch.setattr(ops, kind, counted)
+    return kinds
+
+
+def _short_guess(ops, monkeypatch):
+    """Marching cubes with a capacity guess of 100 vertices / 150 faces where the caller names none."""
+    real = ops.marching_cubes_raw_batch
+    monkeypatch.setattr(ops, "marching_cubes_raw_batch",
+                        lambda s, level, lo, hi, max_verts=None, max_faces=None, **kw: real(
+                            s, level, lo, hi, max_verts=max_verts or 100, max_faces=max_faces or 150, **kw))
+
+
+def test_every_option_at_once(ops, colour):
+    """clean, simplify, smooth, normals and colours in one chain: the only combination nothing else composes."""
+    from monoport_amd import recon
+    net, feat = colour["netC"], colour["feat_C"]
+    calib = torch.eye(4, device=DEV)[None]
+    vol = torch.from_numpy(_body_floater()).to(DEV)
+    zeros = torch.zeros((33, 33, 33), device=DEV)
+    before = vol.clone()
+    binding = recon._bind_netC("test", net, [(feat, calib, vol.device)])[0]
+    want, on_surface, moved, mc_counts = _by_hand(ops, vol, binding, clean=6, simplify=16, smooth=THREE)
+    nv = want.verts.shape[0]
+    print("33^3 body + floater, every option: %s from marching cubes, %d vertices kept" % (mc_counts, nv))
+    # every stage did something: the floater is gone, the clustering shrank the mesh, the smoothing moved it
+    assert 50 < nv < mc_counts[0] and float(want.verts.abs().max()) < 0.6
+    assert mc_counts[0] < ops.marching_cubes_raw(vol, 0.5, BMIN, BMAX)[2][0].item()
+    assert not torch.equal(moved[:nv], on_surface[:nv])
+    opts = dict(normals="accumulate", clean=6, simplify=16, smooth=3)
+    got = recon.reconstruct_mesh(vol[None, None], 0.5, BMIN, BMAX, netC=net, feat_tensor_C=feat, calib_tensor=calib,
+                                 **opts)
+    _same_mesh(got, want, "reconstruct_mesh")
+    many = recon.reconstruct_mesh_many([vol, None, zeros], 0.5, BMIN, BMAX, netC=net, feat_tensors_C=[feat, None, feat],
+                                       calib_tensors=[calib, None, calib], **opts)
+    assert len(many) == 3 and many[1] is None
+    _same_mesh(many[0], want, "reconstruct_mesh_many, frame 0")
+    _same_mesh(many[2], _by_hand(ops, zeros, binding, clean=6, simplify=16, smooth=THREE)[0], "frame 2")
+    assert many[2].verts.shape == (0, 3) and many[2].faces.shape == (0, 3) and many[2].colors.shape == (0, 3)
+    assert torch.equal(vol, before)
+
+
+@pytest.mark.parametrize("simplify", [None, 16])
+def test_one_live_volume_in_a_list(ops, vols33, colour, simplify, monkeypatch):
+    """reconstruct_mesh_many is defined against reconstruct_mesh: with one live orthogonal volume it issues that
+    call's per-frame counted query, on the first run and on the re-run with exact capacities alike."""
+    from monoport_amd import recon
+    net, feat = colour["netC"], colour["feat_C"]
+    calib = (torch.eye(4, device=DEV) * 0.9)[None].contiguous()
+    vol = vols33[0]
+    want = recon.reconstruct_mesh(vol, 0.5, BMIN, BMAX, netC=net, feat_tensor_C=feat, calib_tensor=calib,
+                                  simplify=simplify)
+    assert want.verts.shape[0] == (1562 if simplify is None else 285) and want.colors.shape == want.verts.shape
+    kinds = _count_queries(ops, monkeypatch)
+    kw = dict(netC=net, feat_tensors_C=[None, feat], calib_tensors=[None, calib], simplify=simplify)
+    got = recon.reconstruct_mesh_many([None, vol], 0.5, BMIN, BMAX, **kw)
+    assert got[0] is None and kinds == ["query_counted"]
+    _same_mesh(got[1], want, "one live volume")
+    _short_guess(ops, monkeypatch)
+    again = recon.reconstruct_mesh_many([None, vol], 0.5, BMIN, BMAX, **kw)
+    assert again[0] is None and kinds == ["query_counted"] * 3
+    _same_mesh(again[1], want, "one live volume, re-run")
+
+
+def test_perspective_binding_on_one_volume(ops, vols33, colour, monkeypatch):
+    """The other side of the rule: one frame under a perspective camera goes through the batched counted query."""
+    from monoport_amd import recon
+    from monoport_amd.modeling import geometry
+    net = _seeded_netC()
+    net.projection = geometry.perspective
+    feat = colour["feat_C"]
+    calib = torch.tensor([[2.0, 0, 0, 0], [0, 2.0, 0, 0], [0, 0, 1.0, 3.0], [0, 0, 0, 1.0]], device=DEV)[None]
+    vol = vols33[0]
+    binding = recon._bind_netC("test", net, [(feat, calib, vol.device)])[0]
+    assert binding.projection == ops.PROJECTIONS["perspective"]
+    want = _by_hand(ops, vol, binding)[0]
+    kinds = _count_queries(ops, monkeypatch)
+    got = recon.reconstruct_mesh(vol, 0.5, BMIN, BMAX, netC=net, feat_tensor_C=feat, calib_tensor=calib)
+    assert kinds == ["query_counted_batch"]
+    _same_mesh(got, want, "perspective")
+    ortho = recon.reconstruct_mesh(vol, 0.5, BMIN, BMAX, netC=colour["netC"], feat_tensor_C=feat, calib_tensor=calib)
+    assert kinds == ["query_counted_batch", "query_counted"]
+    assert torch.equal(got.verts, ortho.verts) and not torch.equal(got.colors, ortho.colors)  # the projection matters
 
 
 def test_reconstruct_mesh_many_multi_view_head(colour):
@@ -370,7 +499,7 @@ def test_slot_meshes(nets):
     """Frame 0: a synthetic body.  Frame 1: a camera that looks past the box (every query point projects outside the
     image, so netG answers exactly 0 everywhere): its coarsest level is empty and its volume unspecified."""
     from monoport_amd.modeling.MonoPortNet import QueryBinding
-    from monoport_amd.recon import Mesh, _finish_mesh, _mesh_chain, pifu_calib
+    from monoport_amd.recon import Mesh, _finish_mesh, _mesh_chains, mesh_options, pifu_calib
     images = torch.stack([torch.from_numpy(syn.synthetic_image(0)), torch.zeros(3, 512, 512)]).to(DEV)
     away = torch.eye(4, device=DEV)[None]
     away[0, 0, 3] = 5.0
@@ -378,7 +507,7 @@ def test_slot_meshes(nets):
     slot = _slot(nets, 2, (17, 33, 65), mesh={"normals": "accumulate"})
     plain = _slot(nets, 2, (17, 33, 65))
     try:
-        assert slot.mesh == ("accumulate", 0.5, True) and plain.mesh is None and not hasattr(plain, "mesh_buffers")
+        assert tuple(slot.mesh[:3]) == ("accumulate", 0.5, True) and plain.mesh is None and not hasattr(plain, "mesh_buffers")
         with pytest.raises(RuntimeError):
             plain.meshes()
         slot.submit(images, calibs)
@@ -393,8 +522,8 @@ def test_slot_meshes(nets):
         assert slot.mesh_buffers["counts"][1].cpu().tolist() == [0, 0]
         binding = QueryBinding(nets[1], nets[1].surface_classifier.packed(), slot.feats_hwc_c[0], slot.calib[0:1],
                                syn.Z_SCALE)
-        chain = _mesh_chain(slot.volumes[0], 0.5, BMIN, BMAX, "accumulate", binding)
-        nv, nf = chain[2].cpu().tolist()
+        chain = _mesh_chains([slot.volumes[0]], BMIN, BMAX, mesh_options("accumulate", 0.5, True), [binding])[0]
+        nv, nf = chain.counts.cpu().tolist()
         _same_mesh(m, _finish_mesh(chain, nv, nf), "slot frame 0")
         assert float(m.colors.min()) >= 0 and float(m.colors.max()) <= 1 and not (m.normals == 0).all()
         first = Mesh(*[t.clone() for t in m])
@@ -430,7 +559,7 @@ def test_slot_mesh_chain_chunks(ops, nets, vols33, singles33, normals, colors, m
     chain; and a frame that overflows the slot's capacity is re-run alone."""
     from monoport_amd import pipeline
     from monoport_amd.modeling.MonoPortNet import QueryBinding
-    from monoport_amd.recon import Mesh, _finish_mesh, _mesh_chain
+    from monoport_amd.recon import Mesh, _finish_mesh, _mesh_chains, mesh_options
     if mesh_batch is not None:
         monkeypatch.setattr(pipeline, "MESH_BATCH", mesh_batch)
     slot = _slot(nets, 5, (17, 33), mesh={"normals": normals, "colors": colors, "level": 0.5})
@@ -453,8 +582,9 @@ def test_slot_mesh_chain_chunks(ops, nets, vols33, singles33, normals, colors, m
             if got[b] is None:
                 continue
             binding = QueryBinding(nets[1], mlp_c, slot.feats_hwc_c[b], slot.calib[b:b + 1], syn.Z_SCALE) if colors else None
-            chain = _mesh_chain(slot.volumes[b], 0.5, BMIN, BMAX, normals, binding)
-            nv, nf = chain[2].cpu().tolist()
+            chain = _mesh_chains([slot.volumes[b]], BMIN, BMAX, mesh_options(normals, 0.5, colors),
+                                 [binding] if colors else None)[0]
+            nv, nf = chain.counts.cpu().tolist()
             assert (nv, nf) == singles33[i]["need"]
             _same_mesh(got[b], _finish_mesh(chain, nv, nf), "frame %d" % b)
         assert got[3].verts.shape == (0, 3) and got[3].faces.shape == (0, 3)

@@ -224,15 +224,15 @@ def test_reconstruct_mesh_end_to_end(ops, body257, monkeypatch):
     assert none.normals is None and torch.equal(none.colors, colors) and torch.equal(none.verts, verts)
 
     # a forced short capacity: the same mesh through the retry
-    real, calls = ops.marching_cubes_raw, []
+    real, calls = ops.marching_cubes_raw_batch, []
 
-    def short(volume, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), max_verts=None, max_faces=None):
+    def short(volumes, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), max_verts=None, max_faces=None, **kw):
         calls.append((max_verts, max_faces))
         if max_verts is None:
             max_verts, max_faces = 1000, 1500
-        return real(volume, level, b_min, b_max, max_verts=max_verts, max_faces=max_faces)
+        return real(volumes, level, b_min, b_max, max_verts=max_verts, max_faces=max_faces, **kw)
 
-    monkeypatch.setattr(ops, "marching_cubes_raw", short)
+    monkeypatch.setattr(ops, "marching_cubes_raw_batch", short)
     again = reconstruct_mesh(b["vol"], 0.5, BMIN, BMAX, netC=b["netC"], feat_tensor_C=b["feat_C"],
                              calib_tensor=b["calib"])
     monkeypatch.undo()

@@ -362,13 +362,13 @@ def test_reconstruct_mesh_simplify(ops, colour):
             recon.simplify_mesh(plain, bad)
     assert recon.reconstruct_mesh(None, simplify=16) is None
     # a capacity guess that is short: the whole chain runs again with exact capacities
-    real = ops.marching_cubes_raw
+    real = ops.marching_cubes_raw_batch
     try:
-        ops.marching_cubes_raw = lambda s, level, lo, hi, max_verts=None, max_faces=None: real(
-            s, level, lo, hi, max_verts=max_verts or 100, max_faces=max_faces or 150)
+        ops.marching_cubes_raw_batch = lambda s, level, lo, hi, max_verts=None, max_faces=None, **kw: real(
+            s, level, lo, hi, max_verts=max_verts or 100, max_faces=max_faces or 150, **kw)
         _same_mesh(recon.reconstruct_mesh(vol, 0.5, BMIN, BMAX, simplify=16, **kw), got, "short capacities")
     finally:
-        ops.marching_cubes_raw = real
+        ops.marching_cubes_raw_batch = real
 
 
 def _body_floater():
@@ -447,7 +447,8 @@ def test_slot_simplify(nets, mesh_batch, monkeypatch):
 
     plain, slot = make(normals="accumulate"), make(normals="accumulate", simplify=16, clean=6)
     try:
-        assert slot.mesh == plain.mesh and slot.mesh_simplify == 16 and plain.mesh_simplify is None
+        assert slot.mesh._replace(simplify=None, clean=None) == plain.mesh
+        assert slot.mesh.simplify == 16 and slot.mesh.clean == 6 and plain.mesh.simplify is None
         assert not any(k.startswith("simple_") for k in plain.mesh_buffers)
         assert slot.mesh_buffers["simple_verts"].shape == slot.mesh_buffers["verts"].shape
         with pytest.raises(ValueError):
@@ -473,8 +474,9 @@ def test_slot_simplify(nets, mesh_batch, monkeypatch):
         mlp_c = netc.surface_classifier.packed()
         for b in (0, 1, 3, 4):
             binding = QueryBinding(netc, mlp_c, slot.feats_hwc_c[b], slot.calib[b:b + 1], syn.Z_SCALE)
-            chain = recon._mesh_chain(slot.volumes[b], 0.5, BMIN, BMAX, "accumulate", binding, clean=6, simplify=16)
-            nv, nf = chain[2].cpu().tolist()
+            opts = recon.mesh_options("accumulate", 0.5, True, clean=6, simplify=16)
+            chain = recon._mesh_chains([slot.volumes[b]], BMIN, BMAX, opts, [binding])[0]
+            nv, nf = chain.counts.cpu().tolist()
             _same_mesh(got[b], recon._finish_mesh(chain, nv, nf), "frame %d" % b)
             # geometry and normals: the public per-volume call on the slot's volume
             want = recon.reconstruct_mesh(slot.volumes[b], 0.5, BMIN, BMAX, clean=6, simplify=16)

@@ -418,13 +418,13 @@ def test_reconstruct_mesh_smooth(ops, colour):
             recon.reconstruct_mesh_many([vol], smooth=bad)
     assert recon.reconstruct_mesh(None, smooth=3) is None
     # a capacity guess that is short: the whole chain runs again with exact capacities
-    real = ops.marching_cubes_raw
+    real = ops.marching_cubes_raw_batch
     try:
-        ops.marching_cubes_raw = lambda s, level, lo, hi, max_verts=None, max_faces=None: real(
-            s, level, lo, hi, max_verts=max_verts or 100, max_faces=max_faces or 150)
+        ops.marching_cubes_raw_batch = lambda s, level, lo, hi, max_verts=None, max_faces=None, **kw: real(
+            s, level, lo, hi, max_verts=max_verts or 100, max_faces=max_faces or 150, **kw)
         _same_mesh(recon.reconstruct_mesh(vol, 0.5, BMIN, BMAX, smooth=3, **kw), got, "short capacities")
     finally:
-        ops.marching_cubes_raw = real
+        ops.marching_cubes_raw_batch = real
 
 
 def test_reconstruct_mesh_many_smooth(colour):
@@ -499,7 +499,7 @@ def test_slot_smooth(nets, mesh_batch, monkeypatch):
 
     plain, slot = make(normals="accumulate", simplify=16), make(normals="accumulate", smooth=3, simplify=16)
     try:
-        assert slot.mesh == plain.mesh and slot.mesh_smooth == THREE and plain.mesh_smooth is None
+        assert slot.mesh._replace(smooth=None) == plain.mesh and slot.mesh.smooth == THREE and plain.mesh.smooth is None
         assert "smooth_verts" not in plain.mesh_buffers
         assert slot.mesh_buffers["smooth_verts"].shape == slot.mesh_buffers["verts"].shape
         with pytest.raises(ValueError):
@@ -524,8 +524,9 @@ def test_slot_smooth(nets, mesh_batch, monkeypatch):
         mlp_c = netc.surface_classifier.packed()
         for b in (0, 1, 3, 4):
             binding = QueryBinding(netc, mlp_c, slot.feats_hwc_c[b], slot.calib[b:b + 1], syn.Z_SCALE)
-            chain = recon._mesh_chain(slot.volumes[b], 0.5, BMIN, BMAX, "accumulate", binding, simplify=16, smooth=THREE)
-            nv, nf = chain[2].cpu().tolist()
+            opts = recon.mesh_options("accumulate", 0.5, True, simplify=16, smooth=THREE)
+            chain = recon._mesh_chains([slot.volumes[b]], BMIN, BMAX, opts, [binding])[0]
+            nv, nf = chain.counts.cpu().tolist()
             _same_mesh(got[b], recon._finish_mesh(chain, nv, nf), "frame %d" % b)
             # geometry and normals: the public per-volume call on the slot's volume
             want = recon.reconstruct_mesh(slot.volumes[b], 0.5, BMIN, BMAX, simplify=16, smooth=3)
