@@ -31,6 +31,16 @@ __device__ __forceinline__ WStream make_wstream(const float *base, int n_floats,
   return w;
 }
 
+// the lane parts on a descriptor made elsewhere
+__device__ __forceinline__ WStream make_wstream(__amdgpu_buffer_rsrc_t rs, int lane) {
+  WStream w;
+  w.rs = rs;
+  w.lane16 = lane * 16;
+  w.lane4 = lane * 4;
+  w.h16 = (lane >> 5) * 16;
+  return w;
+}
+
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // fragment `idx` (units of 64 x 16 bytes would be idx * 64; here idx is in 16-byte units)

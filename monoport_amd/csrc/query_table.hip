@@ -65,7 +65,11 @@ typedef f32x4 TabRows[kTabQ][4];  // [q][tap]: rows 8 (q0 + q) + 4 h .. + 3 of a
 // borrow a layer-0 chunk buffer, which is idle in those intervals.  The producers' work is placed so
 // that it never has to finish inside a short interval: whole jobs in the long S intervals (6.8 us of
 // MFMA work each), split jobs (loads issued in one interval, blended and written in a later one) in T / U.  Registers: both roles stay under 128, so a CU holds
-// two workgroups = 16 waves, four per SIMD.
+// two workgroups = 16 waves, four per SIMD -- and WITHOUT private memory: no spilled vector register, no stack slot
+// (tests/test_query_tabws_resources.py reads it from the compiler's report).  A reload from private memory is a VMEM
+// instruction on the path the consumers' weight stream shares, and one issued in front of a job's table loads waits
+// for every load in flight (vmcnt counts in order).  What keeps the producers there is marked where it stands: lane
+// constants recomputed per use (lane_here), bases pinned inside the tile loop, the weights kept as two 64-bit pairs.
 constexpr int kWsThreads = 512;
 constexpr int kWsX = 0;                                 // X[3]: [32 points][128 rows] f32, swizzled (16 KB each):
                                                         //   X[0], X[1] layer-0 chunks; X[2], X[1] the 128-row K pairs of layers 2 / 3
@@ -130,6 +134,14 @@ __device__ __forceinline__ TileLoc locate_tile(const int *tend, long long gtile,
   return loc;
 }
 
+// The lane index, counted where it is asked for and opaque to the compiler: nothing derived from it can be
+// hoisted out of a loop or kept in a register across the code of the other role.
+__device__ __forceinline__ int lane_here() {
+  int l;
+  asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+  return l;
+}
+
 // what a producer lane knows about its point
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 struct WsPoint {
@@ -148,11 +160,8 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
   constexpr int P = kTabPts;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
-  const int lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int j = lane & 31, h = lane >> 5;
-  const int swz = h ^ (j & 15);
-  const WStream ws = make_wstream(mlp.base, mlp.n_floats, lane);
+  const __amdgpu_buffer_rsrc_t ws_rs = make_wstream(mlp.base, mlp.n_floats, 0).rs;  // the consumers' weight stream
   float *bz0 = reinterpret_cast<float *>(smem + kWsBZ0);
   float *b13 = reinterpret_cast<float *>(smem + kWsB13);
   int *tend = reinterpret_cast<int *>(smem + kWsTend);
@@ -219,6 +228,11 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
   if (wv < 4) {
     // =============================== consumers: the K loops ===============================
     if (kWsConsumerPrio) __builtin_amdgcn_s_setprio(kWsConsumerPrio);
+    // Each role derives its lane constants from its own count of the lane index: taken once above the split
+    // they are live in registers through the other role's code as well.
+    const int lane = lane_here(), j = lane & 31, h = lane >> 5;
+    const int swz = h ^ (j & 15);
+    const WStream ws = make_wstream(ws_rs, lane);
     const int rs1 = (kHidden[0] / 8) * 64, rs2 = (kHidden[1] / 8) * 64;
     const int a1 = mlp.ah[1] / 4 + (4 * wv) * rs1;
     const int a2 = mlp.ah[2] / 4 + (2 * wv) * rs2;
@@ -365,9 +379,19 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
     // =============================== producers: everything per point ===============================
     const int pw = wv - 4;  // partner of consumer wave pw
     if (kWsProducerPrio) __builtin_amdgcn_s_setprio(kWsProducerPrio);
+    const int lane = lane_here(), j = lane & 31, h = lane >> 5;
+    const int swz = h ^ (j & 15);
     unsigned char *h0 = smem + kWsX;
     int st1 = (j * kTabHbRow | (swz << 4)) ^ (pw << 7);  // see the consumers' store_k
     f32x4 *piece0 = reinterpret_cast<f32x4 *>(smem + kWsX) + (pw * 4) * 64 + lane;  // + region * 16 KB (3 = PB)
+    // This lane's bytes in bz0 (row block pw of a chunk) and in b13 (row block 4 pw of layer 1; layers 2 / 3 step
+    // back by 256 pw / 384 pw).  Like st1 they are pinned inside the tile loop: every other row block is then a
+    // constant displacement of the LDS read -- left to itself the compiler keeps one hoisted address register per
+    // job (32 (4 ck + pw) becomes an OR that no displacement folds) and spills them.
+    int bzl = kWsBZ0 + (8 * pw + h) * 32, b13l = kWsB13 + 512 * pw + 16 * h;
+    // pw for the scalar offsets of the table loads, pinned in the same way: the 60 offsets of a tile's loads are
+    // then scalar additions next to their loads, not 60 scalar registers held (and spilled) across the tile loop
+    int pws = pw;
 
     // (the frame index is wave-uniform, but not provably so for the compiler: without the readfirstlanes every
     // table load is wrapped in a waterfall loop over the descriptor)
@@ -380,6 +404,10 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
                                                fh * fw * kTableRows * 4, 0x00020000);
     };
     float *zvec = reinterpret_cast<float *>(smem + kWsZv);
+    // The once-per-tile steps below (point set-up, outputs, tile lookup) count the lane index afresh (lane_here),
+    // so that it and what they derive from it (j, h, LDS and global addresses) are recomputed where they are used
+    // -- a few VALU instructions per tile -- instead of being hoisted out of the tile loop, one register each,
+    // and spilled.
     // The point of this lane in tile (fi, n0), in two steps so that its round trips hide behind other work:
     // point_load (the coordinates: one dependent load -- the point count comes from LDS) an interval before
     // point_setup (projection, texels, weights, and layer 4's skip row for finish_tile).
@@ -390,7 +418,7 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
     };
     auto point_load = [&](int fi, long long n0, RawPoint &rp) {  // load_point (query_common.h) on the staged frame
       const WsFrame &fr = frames[fi];
-      const long long n = n0 + j;
+      const long long n = n0 + (lane_here() & 31);
       rp.px = rp.py = rp.pz = 0.0f;
       rp.code = 0;
       rp.live = n < fr.npts;
@@ -407,6 +435,7 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
     };
     auto point_setup = [&](int fi, const RawPoint &rp, WsPoint &pt, int zpar) {
       const WsFrame &fr = frames[fi];
+      const int l = lane_here(), j = l & 31, h = l >> 5;
       float cal[12];
 #pragma unroll
       for (int i = 0; i < 12; ++i) cal[i] = fr.cal[i];
@@ -429,20 +458,27 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
       pt.zf = rp.live ? __fmul_rn(z, z_scale) : 0.0f;
       if (pw == 0 && h == 0) zvec[zpar * P + j] = pt.zf;  // the consumers' B operand of the z column
       const bool inside = in_image(x, y);
-      const Taps t = make_taps(x, y, fh, fw, kTableRows, rp.live && inside);
+      // (the map size through opaque scalars: its four int -> float conversions then happen here, once per tile,
+      // instead of sitting in four vector registers for the whole kernel)
+      int mh = fh, mw = fw;
+      asm volatile("" : "+s"(mh), "+s"(mw));
+      const Taps t = make_taps(x, y, mh, mw, kTableRows, rp.live && inside);
       pt.code = rp.code;
       pt.ok = (rp.live ? 1 : 0) | (inside ? 2 : 0) | (fr.proj == MP_PROJ_PERSPECTIVE && non_finite(x, y) ? 4 : 0);
       pt.r4 = 0.0f;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        pt.to[k] = (int)t.o[k] * 4 + 16 * h;
-        pt.tw[k >> 1][k & 1] = t.w[k];
-      }
+      for (int k = 0; k < 4; ++k) pt.to[k] = (int)t.o[k] * 4 + 16 * h;
+      pt.tw[0] = f32x2{t.w[0], t.w[1]};
+      pt.tw[1] = f32x2{t.w[2], t.w[3]};
+      // (each pair made opaque as a 64-bit unit: otherwise the compiler carries the four weights through the tile
+      // loop as scalars and gives every one a register pair of its own for the packed FMAs -- 8 registers, not 4)
+      asm volatile("" : "+v"(pt.tw[0]), "+v"(pt.tw[1]));
     };
     constexpr int K4 = (kHidden[3] + 256 + 1 + 3) & ~3;
     // layer 4's blended skip row of this lane's output (what finish_tile adds): its own round trip, taken in an
     // interval in which the producers have nothing else to do
     auto point_r4 = [&](int fi, WsPoint &pt) {
+      const int h = lane_here() >> 5;
       if (2 * pw + h < COUT && (pt.ok & 1)) {
         const float *row = frames[fi].l0 + kTableL[4] + 2 * pw + h;
         const int o0 = (pt.to[0] - 16 * h) >> 2, o1 = (pt.to[1] - 16 * h) >> 2, o2 = (pt.to[2] - 16 * h) >> 2,
@@ -485,10 +521,9 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
     // layer-0 chunk ck of this lane's point -> X[buf]: this wave's row block 4 ck + pw;
     // lrelu(b0 + z w0z + blend) with bias and z weights from LDS
     auto chunk_finish = [&](const TabRows &tp, const WsPoint &pt, int ck, int buf) {
-      const int rb = 4 * ck + pw;
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const f32x4 *bz = reinterpret_cast<const f32x4 *>(bz0 + (8 * rb + 2 * q + h) * 8);
+      for (int q = 0; q < 4; ++q) {  // row block 4 ck + pw
+        const f32x4 *bz = reinterpret_cast<const f32x4 *>(smem + bzl + (32 * ck + 2 * q) * 32);
         f32x4 v = __builtin_elementwise_fma(bz[1], (f32x4)(pt.zf), bz[0]);
         v = blend4(tp[q], pt, v);
         v = __builtin_elementwise_max(v, v * 0.01f);  // leaky ReLU (SurfaceClassifier.py:58)
@@ -496,10 +531,10 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
       }
     };
     // piece = bias + blend of row block rb of layer l (b13 offset boff) -> PB; the z column is the consumers'
-    auto piece_finish = [&](const TabRows &tp, const WsPoint &pt, int boff, int region) {
+    auto piece_finish = [&](const TabRows &tp, const WsPoint &pt, int bl, int boff, int region) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        const f32x4 b = *reinterpret_cast<const f32x4 *>(b13 + boff + 8 * q + 4 * h);
+        const f32x4 b = *reinterpret_cast<const f32x4 *>(smem + bl + (boff + 8 * q) * 4);
         piece0[region * (kWsXBytes / 16) + q * 64] = blend4(tp[q], pt, b);
       }
     };
@@ -508,8 +543,8 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
     // needs the point was loaded by setup_point a tile earlier -- no global load stands between the
     // partial sums and the store (with them, this was the longest producer interval of the tile: the
     // consumers waited 7 % of their time at its barrier, tools/tab_ws_stamp_probe.py)
-    const int my_o = 2 * pw + h;
     auto finish_tile = [&](const WsPoint &pt, int fi, long long n0) {
+      const int l = lane_here(), j = l & 31, my_o = 2 * pw + (l >> 5);
       if (my_o < COUT && (pt.ok & 1)) {
         const WsFrame &fr = frames[fi];
         const float *red = reinterpret_cast<const float *>(smem + kWsRed);
@@ -557,18 +592,21 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
           setup_point(loc_n.fi, loc_n.n0, nxt, par ^ 1);
           prs_nxt = table_rsrc(loc_n.fi);
         }
-        if (k == 0) asm volatile("" : "+v"(st1));
+        if (k == 0) asm volatile("" : "+v"(st1), "+v"(bzl), "+v"(b13l), "+v"(cur.tw[0]), "+v"(cur.tw[1]), "+s"(pws));
         if (!(k & 1)) {
-          job_issue(tp, prs_cur, cur, kTableL[1] + 32 * (4 * pw + (k >> 1)));
-          piece_finish(tp, cur, 32 * (4 * pw + (k >> 1)), 3);
+          job_issue(tp, prs_cur, cur, kTableL[1] + 32 * (4 * pws + (k >> 1)));
+          piece_finish(tp, cur, b13l, 32 * (k >> 1), 3);
+          // one job after the other, as placed: with registers to spare the compiler would otherwise start the
+          // chunk's loads in the middle of the piece's blend
+          __builtin_amdgcn_sched_barrier(0);
         }
         if (k < 7) {  // chunk k + 1 -> X[(k + 1) & 1] (read in S(k + 1); last read in S(k - 1) / U1)
-          job_issue(tp, prs_cur, cur, kTableL[0] + 32 * (4 * (k + 1) + pw));
+          job_issue(tp, prs_cur, cur, kTableL[0] + 32 * (4 * (k + 1) + pws));
           chunk_finish(tp, cur, k + 1, (k + 1) & 1);
         } else {
           // S7, where the producers have the least to do: the next tile's points (needed in U0) and the
-          // previous tile's outputs.  Nothing is in flight at its top, so the outputs (which wait for a few
-          // spilled values: s_waitcnt vmcnt(0)) go between the point load and the table rows of piece 4.
+          // previous tile's outputs.  Nothing is in flight at its top, so the outputs go between the point load
+          // and the table rows of piece 4.
           // the next tile's points are a chain of dependent steps (count, load, divide, project, texels) on the
           // critical path of the interval: they run at raised priority -- at the consumers' priority or below, a
           // producer instruction waits ~100 cycles for an issue slot between the MFMAs
@@ -576,14 +614,14 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
           RawPoint raw_n = {};
           if (kWsSetupAt == 7 && loc_n.fi >= 0) point_load(loc_n.fi, loc_n.n0, raw_n);
           if (kWsFinishAt == 7 && prev_fi >= 0) finish_tile(prev, prev_fi, prev_n0);
-          if (kWsP4First) job_issue(tp, prs_cur, cur, kTableL[2] + 32 * (2 * pw));  // piece 4 (layer 2, row block 2 pw) in flight
+          if (kWsP4First) job_issue(tp, prs_cur, cur, kTableL[2] + 32 * (2 * pws));  // piece 4 (layer 2, row block 2 pw) in flight
           if (kWsSetupAt == 7 && loc_n.fi >= 0) {
             point_setup(loc_n.fi, raw_n, nxt, par ^ 1);
             if (!kWsR4Late) point_r4(loc_n.fi, nxt);
             prs_nxt = table_rsrc(loc_n.fi);
           }
           if (kWsSetupPrio) __builtin_amdgcn_s_setprio(kWsProducerPrio);
-          if (!kWsP4First) job_issue(tp, prs_cur, cur, kTableL[2] + 32 * (2 * pw));  // with all 64 row registers free until here
+          if (!kWsP4First) job_issue(tp, prs_cur, cur, kTableL[2] + 32 * (2 * pws));  // with all 64 row registers free until here
         }
         __syncthreads();
       }
@@ -593,18 +631,18 @@ __global__ __launch_bounds__(kWsThreads, 4) void pifu_query_tabws_kernel(MlpPack
         finish_tile(prev, prev_fi, prev_n0);
         if (kWsSetupPrio) __builtin_amdgcn_s_setprio(kWsProducerPrio);
       }
-      loc_ahead = gtile + 2 * tile_step < tile_end ? locate_tile(tend, gtile + 2 * tile_step, lane) : no_tile;
+      loc_ahead = gtile + 2 * tile_step < tile_end ? locate_tile(tend, gtile + 2 * tile_step, lane_here()) : no_tile;
       __syncthreads();  // T0: every region holds a K pair of layer 2 or is being filled with one
-      piece_finish(tp, cur, kHidden[1] + 32 * (2 * pw), 2);         // T1: piece 4 -> X[2] (pair 0 was read in T0; read in T2)
-      job_issue(tp, prs_cur, cur, kTableL[2] + 32 * (2 * pw + 1));  //     piece 5 in flight
+      piece_finish(tp, cur, b13l - 256 * pw, kHidden[1], 2);         // T1: piece 4 -> X[2] (pair 0 was read in T0; read in T2)
+      job_issue(tp, prs_cur, cur, kTableL[2] + 32 * (2 * pws + 1));  //     piece 5 in flight
       __syncthreads();
-      piece_finish(tp, cur, kHidden[1] + 32 * (2 * pw + 1), 0);  // T2: piece 5 -> X[0] (pair 1 was read in T1; read in T3)
-      job_issue(tp, prs_cur, cur, kTableL[3] + 32 * pw);         //     piece 6 in flight
+      piece_finish(tp, cur, b13l - 256 * pw, kHidden[1] + 32, 0);  // T2: piece 5 -> X[0] (pair 1 was read in T1; read in T3)
+      job_issue(tp, prs_cur, cur, kTableL[3] + 32 * pws);          //     piece 6 in flight
       __syncthreads();
       if (kWsSetupAt == 7 && kWsR4Late && loc_n.fi >= 0) point_r4(loc_n.fi, nxt);  // T3: nothing else to do
       __syncthreads();  // T3: the consumers read pair 3 in PB and piece 5
-      piece_finish(tp, cur, kHidden[1] + kHidden[2] + 32 * pw, 3);            // U0: piece 6 -> PB (read in U1)
-      if (loc_n.fi >= 0) job_issue(tp, prs_nxt, nxt, kTableL[0] + 32 * pw);  //     the next tile's chunk 0 in flight
+      piece_finish(tp, cur, b13l - 384 * pw, kHidden[1] + kHidden[2], 3);      // U0: piece 6 -> PB (read in U1)
+      if (loc_n.fi >= 0) job_issue(tp, prs_nxt, nxt, kTableL[0] + 32 * pws);  //     the next tile's chunk 0 in flight
       __syncthreads();
       if (loc_n.fi >= 0) {
         chunk_finish(tp, nxt, 0, 0);  // U1: -> X[0] (piece 5 was read in T3)
