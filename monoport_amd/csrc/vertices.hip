@@ -151,8 +151,9 @@ __global__ __launch_bounds__(kEmitBlock) void emit_vertices_kernel(VertFrames fr
   float zz = __fadd_rn(ta, tb);
   zz = zz < 0.0f ? 0.0f : (zz > (float)r ? (float)r : zz);  // clamp keeps NaN (hit at z'=0)
   const float nx = __fsub_rn(v4, v1), ny = __fsub_rn(v3, v1), nz = den;
-  const float len =
-      __fsqrt_rn(__fadd_rn(__fadd_rn(__fmul_rn(nx, nx), __fmul_rn(ny, ny)), __fmul_rn(nz, nz)));
+  // sqrtf, not __fsqrt_rn: the HIP headers define the latter as the native (approximate, ~1 ulp) square root, which
+  // moved a seventh of the normal components by one ulp; sqrtf is the correctly rounded one, as on the host
+  const float len = sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(nx, nx), __fmul_rn(ny, ny)), __fmul_rn(nz, nz)));
   xo[row] = x;
   yo[row] = y;
   zo[row] = zz;

@@ -120,6 +120,35 @@ def gen_forward_vertices():
 
 
 @torch.no_grad()
+def gen_forward_vertices_edges():
+    """The reference's forward_vertices on the adversarial volumes of tests/surface_cases.py: hits at every border of
+    the box and in the last voxel, plateaus, values exactly 0.5, zero-length normals and non-finite entries.  Only
+    the results are stored; the tests rebuild the volumes from the seeds."""
+    import recon as ref_recon
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import surface_cases as sc
+    store = {}
+    cases = [("d40_%s" % kind, sc.depth_case(40, kind)[0], sc.DIRECTIONS) for kind in sc.KINDS]
+    cases.append(("nonfinite", sc.nonfinite_volume(*sc.NONFINITE), ("front", "left")))
+    for name, vol, directions in cases:
+        for d in directions:
+            x, y, z, n = ref_recon.forward_vertices(torch.from_numpy(vol)[None, None], d)
+            key = "%s_%s_" % (name, d)
+            store[key + "X"] = x.numpy().astype(np.int16)  # r <= 40
+            store[key + "Y"] = y.numpy().astype(np.int16)
+            store[key + "Z"] = z.numpy()
+            store[key + "norm"] = n.numpy()
+            assert z.dtype == torch.float32 and n.dtype == torch.float32
+            print("forward_vertices_edges", name, d, x.shape[0], "nan Z:", int(torch.isnan(z).sum()),
+                  "nan normal rows:", int(torch.isnan(n).any(1).sum()))
+    store["meta"] = np.array(["surface_cases.depth_case(40, kind) for smooth/binary/quant, four directions; "
+                              "surface_cases.nonfinite_volume(*NONFINITE), front and left; X, Y as int16"])
+    path = os.path.join(OUT, "forward_vertices_edges.npz")
+    np.savez_compressed(path, **store)
+    print("forward_vertices_edges.npz: %d bytes" % os.path.getsize(path))
+
+
+@torch.no_grad()
 def gen_colorization():
     """RTL/main.py:201-249 driven with the reference's orthogonal + netC.query + recon."""
     import recon as ref_recon
@@ -584,7 +613,7 @@ def gen_obj():
 
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["query", "misc", "vertices", "color", "encoders", "pipeline",
+    which = sys.argv[1:] or ["query", "misc", "vertices", "vertices_edges", "color", "encoders", "pipeline",
                              "dense64", "obj", "pipeline257_color", "main_py"] + sorted(PIPE257_SCENES)
     if "obj" in which:
         gen_obj()
@@ -594,6 +623,8 @@ if __name__ == "__main__":
         gen_index_orthogonal_calib()
     if "vertices" in which:
         gen_forward_vertices()
+    if "vertices_edges" in which:
+        gen_forward_vertices_edges()
     if "color" in which:
         gen_colorization()
     if "encoders" in which:
