@@ -20,6 +20,7 @@ import torch.nn.functional as F
 
 from .. import ops
 
+import contextlib
 import os
 import threading
 
@@ -48,6 +49,36 @@ def set_encoder_conv_precision(precision):
     if precision not in ("f32", "f16x3"):
         raise ValueError("encoder conv precision must be 'f32' or 'f16x3'")
     ENCODER_CONV_PRECISION = precision
+
+
+_repeatable_lock = threading.Lock()
+_repeatable_state = [0, False]  # passes inside, the flag as the first one found it
+
+
+@contextlib.contextmanager
+def _repeatable_convs(x, module):
+    """While an inference pass on the GPU is inside, torch's own convolutions (the per-module paths: sizes the HIP
+    kernels do not take, MONOPORT_ENCODER_CONV=miopen) pick among MIOpen's deterministic solvers only.  Its default
+    choice for Conv2d(128, 64, 3, padding=1) on a 48 x 40 map -- HGFilter on a 384 x 320 image -- gave another
+    rounding of the same sums on 9 of 10 calls (7e-7 there, 1e-5 at the encoder's output), while every kernel of
+    csrc/ is bit-repeatable.  The flag is torch's process-wide one, so passes in several threads share it: the first
+    one in sets it, the last one out puts back what the first found."""
+    if not x.is_cuda or module.training or not _inference_only(x, module):
+        yield
+        return
+    st = _repeatable_state
+    with _repeatable_lock:
+        if st[0] == 0:
+            st[1] = torch.backends.cudnn.deterministic
+            torch.backends.cudnn.deterministic = True
+        st[0] += 1
+    try:
+        yield
+    finally:
+        with _repeatable_lock:
+            st[0] -= 1
+            if st[0] == 0:
+                torch.backends.cudnn.deterministic = st[1]
 
 
 class _GroupNorm(nn.GroupNorm):
@@ -655,30 +686,31 @@ class HGFilter(nn.Module):
             if hwc_out is not None:
                 hwc_out.copy_(flat[-1].reshape(hwc_out.shape))
             return [(o,) for o in flat[:-1]]
-        x = self.bn1(self.conv1(x), relu=True)
-        x = F.avg_pool2d(self.conv2(x), 2, stride=2)
-        x = self.conv4(self.conv3(x))
-        fused = (not self.training and ENCODER_CONV == "hip" and ops.conv1x1_supported(x)
-                 and x.shape[1] == 256)
-        pack_after = hwc_out is not None and not fused  # no producing kernel to write it: pack the NCHW result
-        outputs = []
-        for i in range(self.num_stack):
-            y = getattr(self, "top_m_%d" % i)(getattr(self, "m%d" % i)(x))
-            if fused:
-                out, x = self._tail_fused(i, y, x, None if pack_after else hwc_out,
-                                          want_nchw=keep_nchw or pack_after or not (last_only and hwc_out is not None))
+        with _repeatable_convs(x, self):  # torch's convolutions: the stem, and whatever the kernels do not take
+            x = self.bn1(self.conv1(x), relu=True)
+            x = F.avg_pool2d(self.conv2(x), 2, stride=2)
+            x = self.conv4(self.conv3(x))
+            fused = (not self.training and ENCODER_CONV == "hip" and ops.conv1x1_supported(x)
+                     and x.shape[1] == 256)
+            pack_after = hwc_out is not None and not fused  # no producing kernel to write it: pack the NCHW result
+            outputs = []
+            for i in range(self.num_stack):
+                y = getattr(self, "top_m_%d" % i)(getattr(self, "m%d" % i)(x))
+                if fused:
+                    nchw = keep_nchw or pack_after or not (last_only and hwc_out is not None)
+                    out, x = self._tail_fused(i, y, x, None if pack_after else hwc_out, want_nchw=nchw)
+                    outputs.append((out,))
+                    continue
+                y = getattr(self, "bn_end%d" % i)(getattr(self, "conv_last%d" % i)(y), relu=True)
+                out = getattr(self, "l%d" % i)(y)
                 outputs.append((out,))
-                continue
-            y = getattr(self, "bn_end%d" % i)(getattr(self, "conv_last%d" % i)(y), relu=True)
-            out = getattr(self, "l%d" % i)(y)
-            outputs.append((out,))
-            if i < self.num_stack - 1:
-                x = x + getattr(self, "bl%d" % i)(y) + getattr(self, "al%d" % i)(out)
-        if pack_after:  # train mode / MONOPORT_ENCODER_CONV=miopen / odd shapes: same contract, one more pass
-            last = outputs[-1][0]
-            for b in range(last.shape[0]):
-                ops.pack_features(last[b:b + 1].detach(), out=hwc_out[b])
-        return outputs[-1:] if last_only else outputs
+                if i < self.num_stack - 1:
+                    x = x + getattr(self, "bl%d" % i)(y) + getattr(self, "al%d" % i)(out)
+            if pack_after:  # train mode / MONOPORT_ENCODER_CONV=miopen / odd shapes: same contract, one more pass
+                last = outputs[-1][0]
+                for b in range(last.shape[0]):
+                    ops.pack_features(last[b:b + 1].detach(), out=hwc_out[b])
+            return outputs[-1:] if last_only else outputs
 
 
     def plan_count(self):
@@ -814,7 +846,8 @@ class ResnetFilter(nn.Module):
             cache = self.__dict__.setdefault("_graphs", _GraphedForward())
             key = (tuple(x.shape), str(x.device), ENCODER_CONV_PRECISION, _GraphedForward.fingerprint(self))
             return [cache.run(key, x, lambda xs: (self._forward_dataflow(xs)[0][0],))]
-        return [(_run_sequential(self.model, x),)]
+        with _repeatable_convs(x, self):
+            return [(_run_sequential(self.model, x),)]
 
 
 def PIFuResBlkFilters(*args, **kwargs):

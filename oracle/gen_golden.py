@@ -611,10 +611,61 @@ def gen_obj():
     print("obj_format", int(out["plain_size"]), int(out["color_size"]))
 
 
+@torch.no_grad()
+def gen_rect():
+    """Non-square feature maps (tests/rect_cases.py): the reference's geometry.index on the 48 x 80, 80 x 48, two-row,
+    two-column, one-row and one-column maps, and PIFuNetG / PIFuNetC.query (orthogonal under the scene camera and
+    the identity, one perspective case) on 4096 points each.  Outputs and calibrations only, in one file; the
+    tests rebuild maps, heads, uv and points from the seeds of the case table."""
+    import recon as ref_recon
+    from monoport.lib.modeling.geometry import index, orthogonal, perspective
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import rect_cases as rc
+    store = {}
+    for name in rc.INDEX_CASES:
+        f, uv = rc.index_inputs(name)
+        store[name] = index(torch.from_numpy(f)[None], torch.from_numpy(uv)[None])[0].numpy()
+        print("rect", name, f.shape, store[name].shape)
+    for name, case in rc.QUERY_CASES.items():
+        kind, layers, f, p = rc.query_inputs(name)
+        net = ref_net(kind)
+        load_mlp(net, layers)
+        if case["camera"] == "scene":
+            calib = ref_recon.pifu_calib(*syn.scene_camera(rc.SCENE_STEP), device="cpu")
+        elif case["camera"] == "eye":
+            calib = torch.eye(4)[None]
+        else:
+            calib = torch.from_numpy(rc.persp_calib())
+            net.projection = perspective  # opt_net.projection = "perspective" (MonoPortNet.py:27)
+        feats = [[torch.zeros(1, f.shape[0], 2, 2)]] * 3 + [[torch.from_numpy(f)[None]]]
+        out = net.query(feats, torch.from_numpy(p)[None], calibs=calib)[0][0].numpy()
+        xyz = (perspective if case["camera"] == "persp" else orthogonal)(torch.from_numpy(p)[None], calib)[0].numpy()
+        inside, outside = rc.inside_image(xyz), rc.outside_image(xyz)
+        nan = np.isnan(out).all(0)
+        assert inside.sum() >= rc.MIN_INSIDE and outside.sum() >= rc.MIN_OUTSIDE, (name, inside.sum(), outside.sum())
+        assert (out[:, outside] == 0).all()
+        if case["camera"] == "persp":
+            at = rc.PERSP_AT
+            assert nan[at:at + 4].all() and nan.sum() == 4
+        else:
+            assert not nan.any()
+        store[name] = out
+        store[name + "_calib"] = calib.numpy()
+        print("rect %-14s %s map %s in-image %d outside %d NaN %d range [%.3g, %.3g]"
+              % (name, out.shape, f.shape, int(inside.sum()), int(outside.sum()), int(nan.sum()),
+                 float(np.nanmin(out)), float(np.nanmax(out))))
+    store["meta"] = np.array(["tests/rect_cases.py: INDEX_CASES (rand_feat(256,H,W,seed), uv = RandomState(seed) in "
+                              "+-1.1, corners first) and QUERY_CASES (rand_mlp(kind,seed,2.0), rand_feat(C,H,W,seed), "
+                              "rect_points(H,W,seed); scene_camera(%d), identity, persp_calib())" % rc.SCENE_STEP])
+    path = os.path.join(OUT, rc.FIXTURE + ".npz")
+    np.savez_compressed(path, **store)
+    print("%s.npz: %d bytes" % (rc.FIXTURE, os.path.getsize(path)))
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
     which = sys.argv[1:] or ["query", "misc", "vertices", "vertices_edges", "color", "encoders", "pipeline",
-                             "dense64", "obj", "pipeline257_color", "main_py"] + sorted(PIPE257_SCENES)
+                             "dense64", "obj", "pipeline257_color", "main_py", "rect"] + sorted(PIPE257_SCENES)
     if "obj" in which:
         gen_obj()
     if "query" in which:
@@ -643,3 +694,5 @@ if __name__ == "__main__":
         gen_pipeline257_color()
     if "main_py" in which:
         gen_main_py()
+    if "rect" in which:
+        gen_rect()
