@@ -665,42 +665,6 @@ int mp_stream_release(mp_ctx *ctx, mp_stream stream) {
   return MP_OK;
 }
 
-int mp_stream_create_cu_mask(mp_ctx *ctx, int first_cu, int n_cus, mp_stream *out) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (!out || first_cu < 0 || n_cus < 8 || first_cu + n_cus > ctx->n_cu)
-    return fail(ctx, MP_ERR_ARG, "mp_stream_create_cu_mask: CUs [%d, %d) of %d", first_cu, first_cu + n_cus, ctx->n_cu);
-  DeviceGuard g(ctx->device);
-  std::vector<uint32_t> mask((ctx->n_cu + 31) / 32, 0u);
-  for (int i = first_cu; i < first_cu + n_cus; ++i) mask[i >> 5] |= 1u << (i & 31);
-  hipStream_t st = nullptr;
-  MP_HIP(ctx, hipExtStreamCreateWithCUMask(&st, (uint32_t)mask.size(), mask.data()));
-  ctx->stream_cus[(void *)st] = n_cus;
-  *out = (mp_stream)st;
-  return MP_OK;
-}
-
-int mp_stream_destroy(mp_ctx *ctx, mp_stream stream) {
-  if (!ctx || !stream) return MP_ERR_ARG;
-  {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    auto it = ctx->stream_cus.find((void *)stream);
-    if (it == ctx->stream_cus.end())
-      return fail(ctx, MP_ERR_ARG, "mp_stream_destroy: not a stream of mp_stream_create_cu_mask on this context");
-    ctx->stream_cus.erase(it);
-  }
-  const int rc = mp_stream_release(ctx, stream);  // drains the device, frees the stream's arena
-  DeviceGuard g(ctx->device);
-  MP_HIP(ctx, hipStreamDestroy((hipStream_t)stream));
-  return rc;
-}
-
-int mp_stream_cu_count(mp_ctx *ctx, mp_stream stream) {
-  if (!ctx) return MP_ERR_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  return cus_of(ctx, (hipStream_t)stream);
-}
-
 int mp_memory_stats(mp_ctx *ctx, int64_t *out4) {
   if (!ctx || !out4) return MP_ERR_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);

@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void mfma_clock_probe_kernel(int iters, unsign
 // out[0] = TFLOP/s of the timed launch, out[1] = shader clock in MHz (cycles per 100 MHz reference tick, averaged
 // over the workgroups), out[2] = its duration in ms, out[3] = workgroups.  Synchronises `st`.
 int launch_mfma_clock_probe(mp_ctx *ctx, float ms_target, double *out, hipStream_t st) {
-  const int grid = 2 * cus_of(ctx, st);  // two 4-wave workgroups per CU = two waves per SIMD, as the query kernels run
+  const int grid = 2 * ctx->n_cu;  // two 4-wave workgroups per CU = two waves per SIMD, as the query kernels run
   unsigned long long *clocks = nullptr;
   float *sink = nullptr;
   hipEvent_t e0 = nullptr, e1 = nullptr;

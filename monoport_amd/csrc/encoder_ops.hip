@@ -494,8 +494,7 @@ int launch_upsample_add_gn(mp_ctx *ctx, const float *x, int n, int c, int h, int
   int rc = check_fin(ctx, fin, n, c, partial_cap, "upsample_add_gn");
   if (rc != MP_OK) return rc;
   const int cpg = c / 32;
-  static const bool old_form = getenv("MONOPORT_UPSAMPLE") && getenv("MONOPORT_UPSAMPLE")[0] == 'o';  // A/B: "old"
-  if (!old_form && upsample_gn_banded(c, h, w)) {
+  if (upsample_gn_banded(c, h, w)) {
     hipLaunchKernelGGL(upsample_add_gn_kernel, dim3(n * 32 * kGnSlices), dim3(kGnThreads), 0, st, x, add, y, h, w,
                        cpg, (float)(h - 1) / (float)(2 * h - 1), (float)(w - 1) / (float)(2 * w - 1), fin);
     MP_HIP(ctx, hipGetLastError());

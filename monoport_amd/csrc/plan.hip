@@ -59,11 +59,7 @@ int mp_plan_create(mp_ctx *ctx, int n_side_streams, mp_plan **out) {
   hipSetDevice(ctx->device);
   for (int i = 0; i < n_side_streams; ++i) {
     hipStream_t s = nullptr;
-    // MONOPORT_PLAN_SIDE_PRIORITY (measurement switch): HIP priority of the side streams (lower = served first)
-    static const char *prio_env = getenv("MONOPORT_PLAN_SIDE_PRIORITY");
-    const hipError_t e_create = prio_env ? hipStreamCreateWithPriority(&s, hipStreamNonBlocking, atoi(prio_env))
-                                         : hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e_create != hipSuccess) {
+    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) {
       for (hipStream_t t : p->side) hipStreamDestroy(t);
       delete p;
       hipSetDevice(prev);

@@ -249,7 +249,7 @@ static int launch_query_t(mp_ctx *ctx, const Mlp &m, const QuerySet &set, int h,
   if (max_points <= 0) return MP_OK;
   // every frame of the set rounds its own tail tile up
   const long long tiles = (max_points + kTilePts - 1) / kTilePts + (set.n - 1);
-  const long long grid = query_grid(tiles, (long long)cus_of(ctx, st) * WPS, device_counts);
+  const long long grid = query_grid(tiles, (long long)ctx->n_cu * WPS, device_counts);
   // Launches with few 64-point tiles (long tail on 256 CUs) go to the 32-point kernel
   // (query_small.hip, same bits).  With host-side counts the choice is made here; with device-side
   // counts both kernels are launched and each looks at the counts (the excluded one leaves at its

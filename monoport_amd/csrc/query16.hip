@@ -875,7 +875,7 @@ static int launch_query16_tab_t(mp_ctx *ctx, const Mlp &m, const QuerySet &set, 
   if (const int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kern), kQ16TabLds)) return rc;
   if (max_points <= 0) return MP_OK;
   const long long tiles = (max_points + P - 1) / P + (set.n - 1);
-  const long long grid = query_grid(tiles, cus_of(ctx, st), device_counts);  // one workgroup per CU
+  const long long grid = query_grid(tiles, ctx->n_cu, device_counts);  // one workgroup per CU
   QuerySetDev dset;
   {
     const int rc_set = compact_query_set(ctx, set, dset);
@@ -899,7 +899,7 @@ static int launch_query16_t(mp_ctx *ctx, const Mlp &m, const QuerySet &set, int 
   if (const int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
   if (max_points <= 0) return MP_OK;
   const long long tiles = (max_points + P - 1) / P + (set.n - 1);
-  const long long grid = query_grid(tiles, cus_of(ctx, st), device_counts);
+  const long long grid = query_grid(tiles, ctx->n_cu, device_counts);
   QuerySetDev dset;
   {
     const int rc_set = compact_query_set(ctx, set, dset);

@@ -259,7 +259,7 @@ int launch_query32_t(mp_ctx *ctx, const Mlp &m, const QuerySet &set, int h, int 
   if (const int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
   if (max_points <= 0) return MP_OK;
   const long long tiles = (max_points + kSmallPts - 1) / kSmallPts + (set.n - 1);
-  long long grid = query_grid(tiles, (long long)cus_of(ctx, st) * kT32Wps, device_counts);
+  long long grid = query_grid(tiles, (long long)ctx->n_cu * kT32Wps, device_counts);
   // gated: this kernel only works on launches of < gate_tiles64 64-point tiles
   if (gate_tiles64 > 0 && grid > 2LL * gate_tiles64 + set.n) grid = 2LL * gate_tiles64 + set.n;
   QuerySetDev dset;

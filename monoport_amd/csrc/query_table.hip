@@ -668,15 +668,7 @@ static int launch_query_tabws_t(mp_ctx *ctx, const Mlp &m, const QuerySet &set, 
   const void *kern_id = reinterpret_cast<const void *>(kern);
   if (const int rc = raise_lds_limit(ctx, kern_id, kWsLds)) return rc;
   const long long tiles = (max_points + kTabPts - 1) / kTabPts + (set.n - 1);
-  // MONOPORT_QUERY_WGS_PER_CU (measurement switch, results do not depend on it): 2 = the kernel takes both
-  // workgroup slots of every CU (all of its LDS); 1 = half of them, so that a launch of ANOTHER stream -- a second
-  // slot's query, or its encoder's convolutions -- can be resident next to it
-  static const int wgs_per_cu = [] {
-    const char *e = getenv("MONOPORT_QUERY_WGS_PER_CU");
-    const int v = e ? atoi(e) : 2;
-    return v == 1 ? 1 : 2;
-  }();
-  const long long resident = (long long)cus_of(ctx, st) * wgs_per_cu;
+  const long long resident = (long long)ctx->n_cu * 2;  // the kernel takes both workgroup slots of every CU (all of its LDS)
   // persistent: a workgroup's producers run one chunk ahead of its consumers ACROSS tiles, so a
   // workgroup should see several tiles; never more workgroups than are resident at once
   long long grid = tiles < resident ? tiles : resident;
@@ -684,15 +676,9 @@ static int launch_query_tabws_t(mp_ctx *ctx, const Mlp &m, const QuerySet &set, 
   // neighbour stage is running netG.filter of the next frame on another stream: it gets 8 x the resident workgroups,
   // each with 1 / 8 of the tiles, so that the launch gives its workgroup slots back a few at a time and the encoder's
   // chain of small convolutions gets onto the chip between them instead of waiting for the whole level.  Measured on
-  // the per-frame stage pipeline (tools/per_frame_overlap_probe.py, profiles/r06r_per_frame_grid_mult.txt): 130-131 ->
-  // 136-137 recon/s at 8 x; the query launches alone and the batched headline do not notice (x 1 .. x 16 within noise).
-  // MONOPORT_QUERY_GRID_MULT overrides the factor for every launch (measurement switch; results do not depend on it).
-  static const int grid_mult_env = [] {
-    const char *e = getenv("MONOPORT_QUERY_GRID_MULT");
-    const int v = e ? atoi(e) : 0;
-    return v < 0 ? 0 : v > 64 ? 64 : v;
-  }();
-  const int grid_mult = grid_mult_env ? grid_mult_env : set.n == 1 ? 8 : 1;
+  // the per-frame stage pipeline (profiles/r06r_per_frame_grid_mult.txt): 130-131 -> 136-137 recon/s at 8 x; the query
+  // launches alone and the batched headline do not notice (x 1 .. x 16 within noise).
+  const int grid_mult = set.n == 1 ? 8 : 1;
   if (grid_mult > 1) grid = tiles < resident * grid_mult ? tiles : resident * grid_mult;
   QuerySetDev dset;
   {
@@ -797,7 +783,7 @@ int launch_skip_table(mp_ctx *ctx, const Mlp &m, const float *feat_hwc, int h, i
   const void *kern_id = m.cout == 1 ? reinterpret_cast<const void *>(skip_table_kernel<1>)
                                     : reinterpret_cast<const void *>(skip_table_kernel<3>);
   if (const int rc = raise_lds_limit(ctx, kern_id, lds)) return rc;
-  const long long tiles = texels / 64, resident = (long long)cus_of(ctx, st) * 2;
+  const long long tiles = texels / 64, resident = (long long)ctx->n_cu * 2;
   const dim3 grid((unsigned)(tiles < resident ? tiles : resident));
   if (m.cout == 1)
     hipLaunchKernelGGL(skip_table_kernel<1>, grid, dim3(kQueryThreads), lds, st, m.pack(), feat_hwc, texels, table);

@@ -334,7 +334,7 @@ static int launch_views_t(mp_ctx *ctx, const Mlp &m, const ViewSetDev &set, int 
   const long long gpts = kTilePts / set.nv;
   const long long tiles = (set.n + gpts - 1) / gpts;
   if (tiles <= 0) return MP_OK;
-  const long long grid = query_grid(tiles, (long long)cus_of(ctx, st) * WPS, false);
+  const long long grid = query_grid(tiles, (long long)ctx->n_cu * WPS, false);
   if (const int rc = prof_begin(ctx, st)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kQueryThreads), lds, st, m.pack(), h, w, z_scale, m.act,
                      set);
@@ -361,7 +361,7 @@ int launch_query_views_lattice(mp_ctx *ctx, const Mlp &m, const ViewLatticeDev &
   const long long gpts = kTilePts / set.nv;
   const long long tiles = (max_points + gpts - 1) / gpts;
   if (tiles <= 0) return MP_OK;
-  const long long grid = query_grid(tiles, (long long)cus_of(ctx, st) * WPS, set.src.n_dev != nullptr);
+  const long long grid = query_grid(tiles, (long long)ctx->n_cu * WPS, set.src.n_dev != nullptr);
   if (const int rc = prof_begin(ctx, st)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kQueryThreads), lds, st, m.pack(), h, w, z_scale, m.act,
                      set);

@@ -31,7 +31,7 @@ ENCODER_CONV = os.environ.get("MONOPORT_ENCODER_CONV", "hip")
 # ... on feature maps of at least this height (all of the hourglass's maps: with 32-pixel tiles the
 # kernels match or beat MIOpen's convolution alone down to 32x32 and save its GroupNorm pass,
 # tools/conv_probe.py / profiles/r02m_conv_probe.txt)
-ENCODER_CONV_MIN_H = int(os.environ.get("MONOPORT_ENCODER_CONV_MIN_H", "32"))
+ENCODER_CONV_MIN_H = 32
 # arithmetic of those kernels: "f32" (exact f32 MFMA) or "f16x3" (f32 emulated on f16 MFMA: every
 # operand split into two halves, three MFMAs per product term, f32 accumulation -- the encoder-side
 # counterpart of SurfaceClassifier.set_precision("f16x3"))

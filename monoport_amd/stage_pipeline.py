@@ -44,13 +44,8 @@ import threading
 
 import torch
 
-import os
-
 _END = object()
 _tls = threading.local()
-SWITCH_INTERVAL = float(os.environ.get("MONOPORT_STAGE_SWITCH_INTERVAL", "0"))
-# HIP stream priority per stage index ("4:-1,5:0": lower = served first by the GPU's dispatcher; default 0 for all)
-STAGE_PRIORITY = {int(k): int(v) for k, v in (kv.split(":") for kv in os.environ.get("MONOPORT_STAGE_PRIORITY", "").split(",") if kv)}
 
 
 def stage_kind():
@@ -74,7 +69,7 @@ def stage_stream(device, idx):
     with _STREAMS_LOCK:
         st = _STREAMS.get(key)
         if st is None:
-            st = _STREAMS[key] = torch.cuda.Stream(device=device, priority=STAGE_PRIORITY.get(idx, 0))
+            st = _STREAMS[key] = torch.cuda.Stream(device=device)
     return st
 
 
@@ -240,13 +235,6 @@ class StagePipeline:
                                                   args=(i, fn, queues[i], queues[i + 1]),
                                                   daemon=True))
         self._stop.clear()
-        # CPython hands the interpreter lock to a waiting thread only when the holder blocks or after the switch
-        # interval (5 ms by default): with eight stage threads a frame's hand-over to the next stage can sit behind a
-        # neighbour stage's pure-Python stretch for that long.  A shorter interval while the pipeline runs bounds it
-        # (MONOPORT_STAGE_SWITCH_INTERVAL seconds, 0 = leave the interpreter's setting alone).
-        switch_old = sys.getswitchinterval()
-        if SWITCH_INTERVAL > 0:
-            sys.setswitchinterval(SWITCH_INTERVAL)
         for t in self._threads:
             t.start()
         finished = False
@@ -282,5 +270,3 @@ class StagePipeline:
                     pass
             for t in self._threads:
                 t.join(timeout=5)
-            if SWITCH_INTERVAL > 0:
-                sys.setswitchinterval(switch_old)

@@ -653,12 +653,14 @@ def test_recon_same_bits_with_either_query_tile(ops, oracle):
     assert int(got[0][1][0]) == 1
 
 
-def test_table_query_kernel_is_repeatable_under_perturbed_timing(ops, oracle, monkeypatch):
+def test_table_query_kernel_is_repeatable_under_perturbed_timing(ops, oracle):
     """Race screen for pifu_query_tabws_kernel (producer / consumer waves meeting at 14 barriers per tile, LDS
     regions reused across intervals): the same 8-frame reconstruction and the same scattered query, repeated
     with another stream hammering the GPU in between so that waves interleave differently every time, must
-    return the same bits every time -- and stay within f32 rounding of round 3's kernel (every wave does
-    everything, no hand-offs), which runs in the same process through MONOPORT_TAB_KERNEL=v1."""
+    return the same bits every time -- and stay within f32 rounding of the plain fused kernels (every wave does
+    everything, no hand-offs), which serve the same calls once the tables are released.  That run must also differ
+    from the table kernel's in at least one bit: the comparison is between two implementations (measured on an
+    MI355X: query 4.17e-07, volumes 5.96e-07)."""
     import torch
     dev = torch.device(DEV)
     mlp = ops.PackedMLP.from_layers(dev, syn.rand_mlp("G", 19, 2.0), 1)
@@ -685,14 +687,14 @@ def test_table_query_kernel_is_repeatable_under_perturbed_timing(ops, oracle, mo
             q, v, st = run()
             assert torch.equal(q, first[0]), rep
             assert torch.equal(st, first[2]) and all(torch.equal(a, b) for a, b in zip(v, first[1])), rep
-        monkeypatch.setenv("MONOPORT_TAB_KERNEL", "v1")
-        q1, v1, st1 = run()
     finally:
         ops.skip_table_release(mlp.ctx)
+    q1, v1, st1 = run()  # no tables any more: the plain fused kernels
     torch.cuda.synchronize()
     dq = (q1 - first[0]).abs().max().item()
     dv = max((a - b).abs().max().item() for a, b in zip(v1, first[1]))
-    print("table kernel: 7 identical runs; vs round 3's kernel: query %.3g, volumes %.3g" % (dq, dv))
+    print("table kernel: 7 identical runs; vs the plain kernels: query %.3g, volumes %.3g" % (dq, dv))
+    assert dq > 0 and dv > 0  # another kernel really ran
     assert dq <= 2e-6
     # the rand head's field is not a body: volumes are compared where both kernels evaluated (the same nodes
     # unless a value sits within rounding of the threshold)

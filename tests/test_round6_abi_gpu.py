@@ -1,7 +1,5 @@
 """The C-ABI entry points added in round 6, through ctypes on an MI355X: mp_recon_batch_early (the early hand-over of
-the drop-in engine), CU-masked streams, mp_memory_stats, mp_max_frames."""
-import ctypes
-
+the drop-in engine), mp_memory_stats, mp_max_frames; and that a second stream gives the default stream's bits."""
 import numpy as np
 import pytest
 
@@ -60,62 +58,31 @@ def test_recon_batch_early_hands_over_after_the_coarsest_level(scene):
         ops.recon_batch(mlp, [fh, fh], [cal, cal2], syn.Z_SCALE, BMIN, BMAX, RES, early=early)  # flags for 1 frame
 
 
-def test_cu_masked_stream_runs_the_same_bits(scene):
-    """mp_stream_create_cu_mask: a stream restricted to 64 of the CUs -- the persistent query kernels size their grids
-    from its share (mp_stream_cu_count) and give the same bits as on an ordinary stream; bad ranges are refused;
-    mp_stream_destroy forgets the stream."""
-    from monoport_amd._lib import MonoportError
+def test_another_stream_runs_the_same_bits(scene):
+    """On a second, ordinary stream the table kernel, the plain kernels (volume and status after the table's release) and
+    a scattered query give the same bits as on the default stream."""
     ops = scene["ops"]
     mlp, fh, cal = scene["mlp"], scene["fh"], scene["cal"]
-    ctx, lib = mlp.ctx, mlp.ctx.lib
-    n_cu = lib.mp_stream_cu_count(ctx.handle, None)
-    assert n_cu == torch.cuda.get_device_properties(0).multi_processor_count
     vol_ref, st_ref = ops.recon(mlp, fh, cal, syn.Z_SCALE, BMIN, BMAX, RES)
     pts = torch.from_numpy(syn.rand_points(20000, 5, 1.1))[None].to(DEV)
     out_ref = ops.query(mlp, fh, pts, cal, syn.Z_SCALE)
     table = ops.skip_table(mlp, fh)
     vol_tab, _ = ops.recon(mlp, fh, cal, syn.Z_SCALE, BMIN, BMAX, RES)
-    h = ctypes.c_void_p()
-    ctx.check(lib.mp_stream_create_cu_mask(ctx.handle, 64, 64, ctypes.byref(h)), "mp_stream_create_cu_mask")
+    st = torch.cuda.Stream(device=DEV)
     try:
-        assert lib.mp_stream_cu_count(ctx.handle, h) == 64
-        st = torch.cuda.ExternalStream(h.value, device=DEV)
         st.wait_stream(torch.cuda.current_stream())
-        # torch's allocator notes every stream a tensor was used on (record_stream, ops.recon_batch does it for the
-        # calibration) and records an event on THAT stream when the tensor is freed: nothing that met the masked stream
-        # may outlive it -- private copies of the inputs, gone before the stream is
-        cal_m, pts_m = cal.clone(), pts.clone()
         with torch.cuda.stream(st):
-            vol_m, _ = ops.recon(mlp, fh, cal_m, syn.Z_SCALE, BMIN, BMAX, RES)       # table kernel, 128 workgroups
+            vol_m, _ = ops.recon(mlp, fh, cal, syn.Z_SCALE, BMIN, BMAX, RES)       # table kernel
             table.release()
-            vol_p, st_p = ops.recon(mlp, fh, cal_m, syn.Z_SCALE, BMIN, BMAX, RES)    # plain kernels
-            out_p = ops.query(mlp, fh, pts_m, cal_m, syn.Z_SCALE)
+            vol_p, st_p = ops.recon(mlp, fh, cal, syn.Z_SCALE, BMIN, BMAX, RES)    # plain kernels
+            out_p = ops.query(mlp, fh, pts, cal, syn.Z_SCALE)
             st.synchronize()
         same = (torch.equal(vol_m, vol_tab), torch.equal(vol_p, vol_ref), torch.equal(st_p, st_ref), torch.equal(out_p, out_ref))
-        del vol_m, vol_p, st_p, out_p, cal_m, pts_m
         assert all(same), same
     finally:
         table.release()
         torch.cuda.synchronize()
-    # The stream torch worked on is NOT destroyed here: torch's allocator keeps per-stream state (cached blocks, the
-    # events of record_stream'ed tensors) and would touch a dead stream later -- a caller who wants it gone must drop
-    # every tensor that met it and torch.cuda.empty_cache() first (header).  mp_stream_destroy is exercised on a
-    # stream only the library itself has used:
-    h2 = ctypes.c_void_p()
-    ctx.check(lib.mp_stream_create_cu_mask(ctx.handle, 0, 32, ctypes.byref(h2)), "mp_stream_create_cu_mask")
-    out4 = (ctypes.c_double * 4)()
-    ctx.check(lib.mp_mfma_clock_probe(ctx.handle, ctypes.c_float(5.0), out4, h2), "mp_mfma_clock_probe")
-    full = ops.mfma_clock_probe(DEV, 5.0)
-    print("clock probe on 32 of %d CUs: %.1f TFLOP/s (whole device %.1f)" % (n_cu, out4[0], full["tflops"]))
-    assert int(out4[3]) == 64 and 0.09 < out4[0] / full["tflops"] < 0.16  # 2 workgroups per masked CU; 1/8 of the rate
-    ctx.check(lib.mp_stream_destroy(ctx.handle, h2), "mp_stream_destroy")
-    assert lib.mp_stream_cu_count(ctx.handle, h2) == n_cu  # forgotten: sized like any other stream
-    h = h2
-    for first, n in ((0, 4), (-1, 64), (n_cu - 32, 64)):
-        with pytest.raises(MonoportError):
-            ctx.check(lib.mp_stream_create_cu_mask(ctx.handle, first, n, ctypes.byref(h)), "mp_stream_create_cu_mask")
-    with pytest.raises(MonoportError):
-        ctx.check(lib.mp_stream_destroy(ctx.handle, ctypes.c_void_p(12345)), "mp_stream_destroy")
+        ops.stream_release(st)
 
 
 def test_memory_stats_and_max_frames(scene):
