@@ -89,6 +89,13 @@ int mp_stream_release(mp_ctx *ctx, mp_stream stream);
  * kept for captured graphs, [1] packed MLP weights (all precisions), [2] number of arenas, [3] number of
  * skip tables registered (the tables themselves are the caller's).  Soak tests assert these stay flat. */
 int mp_memory_stats(mp_ctx *ctx, int64_t *out4);
+/* TEST HOOK, not part of any frame: grows the scratch arena of `stream` to at least `bytes`, then sets every byte of
+ * the arena's whole current block (which may be larger than `bytes`; outgrown blocks are not touched) to `value`
+ * (0..255), asynchronously on `stream`, and reports the block's size.  The stages take their temporary memory from
+ * this arena and the pointer never leaves the library, so this is how a test lets a stage start on another stage's
+ * residue.  MP_ERR_ARG, with the device untouched, for a NULL ctx, bytes < 0 or value outside 0..255. */
+int mp_scratch_fill(mp_ctx *ctx, int64_t bytes, int value, int64_t *block_bytes /*host, may be NULL*/,
+                    mp_stream stream);
 /* Frames one fused-query / mp_recon_batch / mp_query_counted_batch call accepts (kMaxFrames). */
 int mp_max_frames(void);
 

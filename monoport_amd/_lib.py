@@ -106,6 +106,7 @@ SIGNATURES = {
     "mp_last_error": (ctypes.c_char_p, [c_vp]),
     "mp_stream_release": (c_int, [c_vp, c_vp]),
     "mp_memory_stats": (c_int, [c_vp, ctypes.POINTER(c_i64)]),
+    "mp_scratch_fill": (c_int, [c_vp, c_i64, c_int, ctypes.POINTER(c_i64), c_vp]),
     "mp_max_frames": (c_int, []),
     "mp_mlp_create": (c_int, [c_vp, c_int, _pint, c_int, _pint]),
     "mp_mlp_load": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp]),

@@ -683,6 +683,23 @@ int mp_memory_stats(mp_ctx *ctx, int64_t *out4) {
   return MP_OK;
 }
 
+// Test hook: the arena pointer never leaves the library, so this is how a test makes a stage start on residue.
+int mp_scratch_fill(mp_ctx *ctx, int64_t bytes, int value, int64_t *block_bytes, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (bytes < 0 || value < 0 || value > 255)
+    return fail(ctx, MP_ERR_ARG, "mp_scratch_fill: %lld bytes of value %d (bytes >= 0, value 0..255)",
+                (long long)bytes, value);
+  DeviceGuard g(ctx->device);
+  void *scratch = nullptr;
+  const int rc = ensure_scratch(ctx, (hipStream_t)stream, (size_t)bytes, &scratch);
+  if (rc != MP_OK) return rc;
+  const size_t block = ctx->arenas[(void *)stream].bytes;  // the whole current block; retired blocks stay as they are
+  if (block) MP_HIP(ctx, hipMemsetAsync(scratch, value, block, (hipStream_t)stream));
+  if (block_bytes) *block_bytes = (int64_t)block;
+  return MP_OK;
+}
+
 int mp_max_frames(void) { return kMaxFrames; }
 
 int mp_mlp_create(mp_ctx *ctx, int n_layers, const int *channels, int last_op, int *mlp_out) {

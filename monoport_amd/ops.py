@@ -2067,6 +2067,20 @@ def memory_stats(device):
     return {"arena_bytes": tot[0], "weight_bytes": tot[1], "arenas": tot[2], "skip_tables": tot[3]}
 
 
+def scratch_fill(device, nbytes, byte, role="query"):
+    """mp_scratch_fill (a test hook): grow the scratch arena that the ``role`` ("query" | "encoder") context of
+    ``device`` keeps for torch's current stream to at least ``nbytes``, set every byte of its current block to ``byte``
+    on that stream, and return the block's size.  The next stage on the stream then starts on that residue."""
+    if role not in ("query", "encoder"):
+        raise ValueError("role must be 'query' or 'encoder', got %r" % (role,))
+    ctx = get_context(device) if role == "query" else get_encoder_context(device)
+    block = ctypes.c_int64(0)
+    st = torch.cuda.current_stream(torch.device(device))
+    ctx.check(ctx.lib.mp_scratch_fill(ctx.handle, int(nbytes), int(byte), ctypes.byref(block),
+                                      ctypes.c_void_p(st.cuda_stream)), "mp_scratch_fill")
+    return int(block.value)
+
+
 def mfma_clock_probe(device, ms_target=20.0, stream=None):
     """What the f32 matrix pipe of ``device`` sustains right now (mp_mfma_clock_probe, csrc/clock_probe.hip):
     {"tflops", "shader_clock_mhz", "ms", "workgroups"} of a register-only MFMA loop of about ``ms_target`` ms."""

@@ -21,6 +21,20 @@ def test_max_frames_matches_the_kernels():
     assert _lib.load().mp_max_frames() == _lib.MAX_FRAMES
 
 
+def test_scratch_fill_refuses_without_a_context():
+    """The test hook mp_scratch_fill returns MP_ERR_ARG for a NULL context before it looks at anything else (no
+    device is touched: this passes on a machine without one), and ops.scratch_fill names its roles."""
+    from monoport_amd import _lib, ops
+    lib = _lib.load()
+    block = ctypes.c_int64(-7)
+    for nbytes, value in ((1024, 0), (0, 255), (-1, 0), (1024, 256)):
+        assert lib.mp_scratch_fill(None, nbytes, value, ctypes.byref(block), None) == -1  # MP_ERR_ARG
+        assert lib.mp_scratch_fill(None, nbytes, value, None, None) == -1
+    assert block.value == -7
+    with pytest.raises(ValueError, match="role"):
+        ops.scratch_fill("cuda:0", 16, 0, role="mesh")
+
+
 def test_importing_ops_does_not_load_the_library(tmp_path):
     """MONOPORT_HIP_LIB is read when _lib is imported: with a missing file there, the import still succeeds and only
     loading raises."""
