@@ -403,6 +403,20 @@ int mp_lattice_points(mp_ctx *ctx, const uint32_t *packed, const int32_t *count,
                       const float *b_max /*host[3]*/, float *points, mp_stream stream);
 int mp_scatter_nodes(mp_ctx *ctx, const uint32_t *packed, const int32_t *count, int64_t capacity,
                      int r, const float *values, float *volume, mp_stream stream);
+/* The ordering step mp_recon_batch* runs between a level's selection and its query (levels of 65 nodes per axis and
+ * more; not for mp_recon_views, mp_recon_topk_batch or the mp_octree_select* entries, whose lists stay as selected):
+ * each frame's list packed[f][0 .. *count[f]) of a level of level_res nodes per axis is sorted IN PLACE by the texel
+ * cell its points sample in an h x w map -- y0 * w + x0 of the first bilinear tap of the point that `stride`,
+ * res_final, b_min, b_max (as mp_lattice_points), calib[f] and projection[f] (NULL: all orthogonal) give, computed
+ * exactly as the query kernels compute it; points outside the image come last.  The order of points of one cell is
+ * unspecified and may differ from call to call.  *count[f] and the entries past it are not written.  A frame with
+ * more than level_res^3 / 8 points is left as it is.  Nothing is synchronised; 1..32 frames. */
+int mp_octree_order_points(mp_ctx *ctx, int n_frames, uint32_t *const *packed /*host[n] of device*/,
+                           const int32_t *const *count /*host[n] of device int32*/,
+                           const float *const *calib /*host[n] of device [3,4]*/,
+                           const int *projection /*host[n] of MP_PROJ_*, may be NULL*/, int level_res, int stride,
+                           int res_final, const float *b_min /*host[3]*/, const float *b_max /*host[3]*/, int h, int w,
+                           mp_stream stream);
 
 /* ---- per-frame and batched forms of the mesh and render calls -------------------------------------------------------
  * mp_forward_vertices, mp_paint, mp_marching_cubes, mp_mesh_simplify, mp_mesh_smooth, mp_mesh_normals, mp_mesh_points,

@@ -5,6 +5,7 @@
 
 #include "mp_internal.h"
 #include "encoder_kernels.h"
+#include "octree_common.h"
 
 namespace mp {
 
@@ -296,7 +297,7 @@ static int recon_checked(mp_ctx *ctx, const char *who, const Mlp &m, int n_frame
   if (rc != MP_OK) return rc;
   DeviceGuard g(ctx->device);
   void *scratch = nullptr;
-  const size_t lossless_bytes = n_frames * recon_scratch_bytes(resolutions, n_levels);
+  const size_t lossless_bytes = n_frames * recon_scratch_bytes(resolutions, n_levels, h, w);
   const size_t topk_bytes = num_points ? topk_scratch_bytes(n_frames, resolutions[n_levels - 1]) : 0;
   rc = ensure_scratch(ctx, (hipStream_t)stream, lossless_bytes + topk_bytes, &scratch);
   if (rc != MP_OK) return rc;
@@ -1297,6 +1298,49 @@ int mp_lattice_points(mp_ctx *ctx, const uint32_t *packed, const int32_t *count,
   DeviceGuard g(ctx->device);
   return launch_lattice_points(ctx, packed, count, capacity, stride, res_final, b_min, b_max,
                                points, (hipStream_t)stream);
+}
+
+int mp_octree_order_points(mp_ctx *ctx, int n_frames, uint32_t *const *packed, const int32_t *const *count,
+                           const float *const *calib, const int *projection, int level_res, int stride, int res_final,
+                           const float *b_min, const float *b_max, int h, int w, mp_stream stream) {
+  const char *who = "mp_octree_order_points";
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (!packed || !count || !calib || !b_min || !b_max || level_res < 2 || level_res > 1023 || stride < 1 ||
+      res_final < 2 || h < 1 || w < 1 || (long long)h * w >= (1ll << 30))
+    return bad_argument(ctx, who);
+  for (int f = 0; f < n_frames; ++f)
+    if (!packed[f] || !count[f] || !calib[f]) return fail(ctx, MP_ERR_ARG, "%s: frame %d has a NULL buffer", who, f);
+  rc = check_projection(ctx, who, projection, n_frames);
+  if (rc != MP_OK) return rc;
+  DeviceGuard g(ctx->device);
+  const long long cap = (long long)level_res * level_res * level_res / 8;
+  const size_t per_frame = point_order_scratch_bytes(cap, h, w);
+  void *scratch = nullptr;
+  rc = ensure_scratch(ctx, (hipStream_t)stream, n_frames * per_frame, &scratch);
+  if (rc != MP_OK) return rc;
+  OrderFrames of;
+  std::memset(&of, 0, sizeof(of));
+  for (int f = 0; f < n_frames; ++f) {
+    of.packed[f] = packed[f];
+    of.count[f] = count[f];
+    of.calib[f] = calib[f];
+    of.proj[f] = projection ? projection[f] : MP_PROJ_ORTHOGONAL;
+    point_order_carve(static_cast<unsigned char *>(scratch) + f * per_frame, cap, of, f);
+  }
+  PointSrc lattice;
+  std::memset(&lattice, 0, sizeof(lattice));
+  lattice.stride = stride;
+  lattice.level_res = level_res;
+  lattice.res_final = (float)res_final;
+  lattice.half_step = (1.0f / (float)res_final) / 2.0f;
+  for (int i = 0; i < 3; ++i) {
+    lattice.bmin[i] = b_min[i];
+    lattice.blen[i] = b_max[i] - b_min[i];
+  }
+  return launch_point_order(ctx, of, n_frames, lattice, h, w, cap, (hipStream_t)stream);
 }
 
 int mp_scatter_nodes(mp_ctx *ctx, const uint32_t *packed, const int32_t *count, int64_t capacity,

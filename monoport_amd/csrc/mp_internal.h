@@ -307,7 +307,8 @@ int launch_concat3_add(mp_ctx *ctx, const float *a, int ca, const float *b, int 
 int launch_prepare_inputs(mp_ctx *ctx, const float *segm, long long hw, const float *mean,
                           const float *std, float *g, float *c, hipStream_t st);
 // octree.hip
-size_t recon_scratch_bytes(const int *res, int n_levels);
+// per frame; h, w: the map size (the histogram of the texel sort, point_order.hip)
+size_t recon_scratch_bytes(const int *res, int n_levels, int h, int w);
 int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
                  const float *const *feat_hwc, int h, int w, const float *const *calib,
                  const int *proj, float z_scale, const float *bmin, const float *bmax, const int *res,

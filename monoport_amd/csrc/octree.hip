@@ -11,6 +11,8 @@
 //   2. select_compact: binary dilation of the flags by the level's box (9^3 / 7^3 / 3^3) as
 //      shift-OR on the 64-bit words, minus the nodes evaluated at earlier levels, popcount +
 //      wave prefix sum + one atomic per wave -> a packed (x | y<<10 | z<<20) point list.
+//      On levels of kOrderMinRes nodes per axis and more the list is then sorted by the texel cell each point
+//      samples (point_order.hip), so that the 32 points of a query tile share table rows.
 //   3. the fused query kernel (query.hip) reads the list and its device-side count, and scatters
 //      exact occupancies straight into the level volume.  For a multi-view head (mp_recon_views) step 3 is
 //      the lattice variant of the multi-view kernel (query_views.hip); steps 1-2 are the same kernels.
@@ -39,7 +41,10 @@ struct LevelBufs {
 
 int octree_box_of_level(int level) { return level == 1 ? 9 : level == 2 ? 7 : 3; }
 
-size_t recon_scratch_bytes(const int *res, int n_levels) {
+// the temporary list of the texel sort (point_order.hip) holds an eighth of a level's nodes
+static long long order_cap(int r) { return (long long)r * r * r / 8; }
+
+size_t recon_scratch_bytes(const int *res, int n_levels, int h, int w) {
   size_t total = 0;
   for (int l = 0; l < n_levels; ++l) {
     const size_t r = res[l];
@@ -48,6 +53,7 @@ size_t recon_scratch_bytes(const int *res, int n_levels) {
   }
   const size_t rl = res[n_levels - 1];
   total += align256(rl * rl * rl * sizeof(uint32_t));  // packed point list (worst case: every node)
+  total += point_order_scratch_bytes(order_cap((int)rl), h, w);  // temporary list + histogram of the texel sort
   return total + 4096;
 }
 
@@ -203,16 +209,30 @@ __global__ __launch_bounds__(256) void upsample_classify_kernel(FrameBufs fb, in
 // (one atomic per wave, waves start in index order), and an item is (w, y in slab, z, slab) with SLABS
 // OF kYSlab ROWS OF y OUTERMOST.  For the reference's turntable cameras (rotation about the y axis,
 // RTL/main.py) world y is image y, so the points of a slab sample kYSlab / 2 + 1 texel rows whatever
-// their x and z -- a few MB of table rows that stay in the XCD's L2 -- and consecutive tiles of 32 points
-// stay compact in image space.  z-major order (MONOPORT_OCTREE_ORDER=z, the round-3 order) revisits a
-// texel once per z plane, 25 MB of rows apart.  Inside a slab the items walk y fastest, so a wave still
-// reads whole rows of flag words next to each other (y alone outermost made them 10 KB apart:
-// select_compact 43 -> 125 us at 257^3).
+// their x and z -- a few MB of table rows that stay in the XCD's L2.  That is all the slabs do: a tile of 32
+// consecutive points is still a few short x-runs from neighbouring y rows (15-32 distinct texel cells), and a
+// tilted camera breaks "world y is image y" anyway; compactness of a TILE in image space, for any camera, comes
+// from the texel sort that launch_recon runs behind this kernel on the finer levels (point_order.hip).
+// z-major order (MONOPORT_OCTREE_ORDER=z, the round-3 order) revisits a texel once per z plane, 25 MB of rows
+// apart.  Inside a slab the items walk y fastest, so a wave still reads whole rows of flag words next to each
+// other (y alone outermost made them 10 KB apart: select_compact 43 -> 125 us at 257^3).
 constexpr int kYSlab = 8;
+// MONOPORT_OCTREE_ORDER, read at every launch (the one A/B switch of the list order): unset = slabs, then the texel
+// sort; y = slabs without the sort; z = z-major without the sort
 static bool octree_y_major() {
   const char *e = getenv("MONOPORT_OCTREE_ORDER");
   return !(e && e[0] == 'z');
 }
+static bool octree_texel_sort() {
+  const char *e = getenv("MONOPORT_OCTREE_ORDER");
+  return !(e && e[0]);
+}
+// The texel sort runs on levels of at least this many nodes per axis.  tools/point_order_probe.py
+// (profiles/point_order_probe.txt: the 20 benchmark frames, one table query launch per level, selection order
+// against texel order, 5 alternating repetitions) cleared levels 65^3, 129^3 and 257^3 -- 6.13 -> 5.33, 11.31 -> 10.25
+// and 43.37 -> 41.08 ms per launch, each gain more than three times the spread of the unsorted repetitions.  Levels
+// below were not measured: they are 6 % of the query time and their launches are too small to fill the chip.
+constexpr int kOrderMinRes = 65;
 
 template <int D, bool YMAJOR>
 __global__ __launch_bounds__(256) void select_compact_kernel(FrameBufs fb, int rp, int w64p, int r, int w64) {
@@ -479,9 +499,11 @@ int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
                  int32_t *const *status, const mp_recon_early *early, hipStream_t st,
                  const ReconViews *views, const ReconTopk *topk) {
   // carve the scratch arena: one private set of level buffers per frame
-  const size_t per_frame = recon_scratch_bytes(res, n_levels);
+  const size_t per_frame = recon_scratch_bytes(res, n_levels, h, w);
   LevelBufs lv[kMaxFrames][8];
   uint32_t *packed[kMaxFrames];
+  OrderFrames order;  // tmp / hist: carved once; packed / count / calib / proj: per level and chunk
+  std::memset(&order, 0, sizeof(order));
   for (int f = 0; f < n_frames; ++f) {
     unsigned char *p = static_cast<unsigned char *>(scratch) + f * per_frame;
     for (int l = 0; l < n_levels; ++l) {
@@ -499,6 +521,8 @@ int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
       p += wb;
     }
     packed[f] = reinterpret_cast<uint32_t *>(p);
+    const size_t rl = res[n_levels - 1];
+    point_order_carve(p + align256(rl * rl * rl * sizeof(uint32_t)), order_cap((int)rl), order, f);
   }
 
   const int rf = res[n_levels - 1];
@@ -649,6 +673,20 @@ int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
                          c, rp, r, balance, w64, rule);
       if (rule != MP_FINAL_INTERPOLATE)
         launch_select(rule == MP_FINAL_UPSTREAM ? 1 : octree_box_of_level(l), st, c, nf, rp, words64(rp), r, w64);
+      if (rule != MP_FINAL_INTERPOLATE && !views && r >= kOrderMinRes && octree_texel_sort()) {
+        OrderFrames of;
+        std::memset(&of, 0, sizeof(of));
+        for (int f = 0; f < nf; ++f) {
+          of.packed[f] = c.packed[f];
+          of.count[f] = c.count[f];
+          of.calib[f] = calib[f0 + f];
+          of.proj[f] = set.it[f0 + f].proj;
+          of.tmp[f] = order.tmp[f0 + f];
+          of.hist[f] = order.hist[f0 + f];
+        }
+        int rc = launch_point_order(ctx, of, nf, set.it[0].src, h, w, order_cap(r), st);
+        if (rc != MP_OK) return rc;
+      }
     }
     if (rule == MP_FINAL_INTERPOLATE) continue;  // status[1 + l] stays 0, no query
     int rc = eval_level((long long)r * r * r * n_frames, true);

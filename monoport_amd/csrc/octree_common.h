@@ -36,6 +36,23 @@ __device__ __forceinline__ u64 spread32(u64 x) {  // bit i -> bit 2i
   return x;
 }
 
+// point_order.hip: a level's point lists sorted in place by the texel cell each point samples (counting sort per frame,
+// blockIdx.z = frame).  A frame's list is packed[f][0 .. *count[f]); calib[f] / proj[f] as in QueryItem; tmp[f]: `cap`
+// entries, hist[f]: h * w + 1 words (point_order_carve lays both out in point_order_scratch_bytes(cap, h, w) bytes).
+// A frame with more than `cap` points keeps its order.  `lattice`: stride, res_final, half_step, bmin, blen of the level.
+struct OrderFrames {
+  uint32_t *packed[kMaxFrames];
+  const int32_t *count[kMaxFrames];
+  const float *calib[kMaxFrames];
+  uint32_t *tmp[kMaxFrames];
+  int32_t *hist[kMaxFrames];
+  int proj[kMaxFrames];
+};
+size_t point_order_scratch_bytes(long long cap, int h, int w);
+void point_order_carve(void *scratch, long long cap, OrderFrames &of, int f);
+int launch_point_order(mp_ctx *ctx, const OrderFrames &of, int n_frames, const PointSrc &lattice, int h, int w,
+                       long long cap, hipStream_t st);
+
 // topk.hip: the fixed-budget selection of one level for n_frames frames (blockIdx.z = frame).  fb.cur holds the
 // upsampled volume, fb.count is zeroed; fb.flag[f] (NULL = frame on) gates frame f on the device.  `scratch`:
 // topk_scratch_bytes(n_frames, r) bytes.

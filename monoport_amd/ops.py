@@ -903,6 +903,29 @@ def recon_generic(query_func, kwargs, device, b_min, b_max, resolutions, balance
     return eng.cur, eng.counts
 
 
+def octree_order_points(packed, counts, calibs, level_res, stride, res_final, b_min, b_max, h, w, projections=None):
+    """mp_octree_order_points: sort each frame's node list (``packed[f]``: int32 codes x | y<<10 | z<<20, the first
+    ``counts[f]`` (device int32[1]) of them) IN PLACE by the texel cell of an [h,w] map its points sample -- the step
+    ``recon_batch`` runs between a level's selection and its query.  The order inside a cell is unspecified; a frame
+    with more than level_res^3 / 8 points is left as it is.  Nothing is synchronised."""
+    who = "octree_order_points"
+    n = len(packed)
+    _check_count(who, "frames", n, MAX_FRAMES)
+    if len(counts) != n or (projections is not None and len(projections) != n):
+        raise ValueError("%s: %d lists, %d counts, %s projections"
+                         % (who, n, len(counts), None if projections is None else len(projections)))
+    dev = packed[0].device
+    if any(p.dtype != torch.int32 or not p.is_contiguous() for p in packed):
+        raise ValueError("%s: the lists must be contiguous int32" % who)
+    ctx = get_context(dev)
+    cals = [_calib_dev(cb, dev) for cb in _calib_list(calibs, n, who)]
+    proj = None if projections is None else (ctypes.c_int * n)(*[_projection(p) for p in projections])
+    ctx.check(ctx.lib.mp_octree_order_points(
+        ctx.handle, n, _ptr_array(packed), _ptr_array(counts), _ptr_array(cals), proj, int(level_res), int(stride),
+        int(res_final), _float3(b_min), _float3(b_max), int(h), int(w), _stream(packed[0])), "mp_octree_order_points")
+    _keep_until_done(dev, cals)
+
+
 def stream_release(stream):
     """Free the scratch arena the context keeps for ``stream`` (a torch.cuda.Stream); call it when
     a stream that made C-ABI calls is retired.  Synchronises the device."""
