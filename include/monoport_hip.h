@@ -333,6 +333,25 @@ int mp_recon_views(mp_ctx *ctx, int mlp, int n_views, const float *const *feat_h
                    float balance, int final_level, int view, float *volume, int32_t *status,
                    const mp_recon_early *early, mp_stream stream);
 
+/* mp_recon_views over n_frames independent subjects that share the head, n_views, `view`, the projection mode, the
+ * box and the resolutions: every octree level evaluates the selected nodes of ALL frames in one launch of the
+ * multi-view kernel (the tiles of the frames form one index space, as in mp_recon_batch), so the coarse levels of a
+ * capture rig's frames fill the machine together.  feat_hwc / calib: HOST arrays of n_frames * n_views device
+ * pointers, frame-major ([f * n_views + v]); volume / status: HOST arrays of n_frames device pointers, each as in
+ * mp_recon_views; early (may be NULL): n_frames entries of expect_level0 and 2 * n_frames flags, as in
+ * mp_recon_batch_early.  Frame f's volume and status equal mp_recon_views on frame f's inputs bit for bit; a frame
+ * whose coarsest level is empty has status[f][0] == 0, an unspecified volume and zero finer counts, and touches
+ * nothing of the other frames.  Fully asynchronous.  Refusals as in mp_recon_views; in addition n_frames outside
+ * 1..mp_max_frames() or n_frames * n_views > MP_MAX_FRAME_VIEWS (mp_max_frame_views(): what the kernel's argument
+ * block holds) returns MP_ERR_ARG.  A refused call launches nothing and leaves the context usable. */
+#define MP_MAX_FRAME_VIEWS 64
+int mp_max_frame_views(void);
+int mp_recon_views_batch(mp_ctx *ctx, int mlp, int n_frames, int n_views, const float *const *feat_hwc, int c, int h,
+                         int w, const float *const *calib, int projection, float z_scale, const float *b_min,
+                         const float *b_max, const int *resolutions, int n_levels, float balance, int final_level,
+                         int view, float *const *volume, int32_t *const *status, const mp_recon_early *early,
+                         mp_stream stream);
+
 /* The same engine one level at a time, for an arbitrary Python ``query_func`` (the general
  * Seg3dLossless contract, RTL/main.py:169-195): the caller evaluates the selected nodes itself.
  *   mp_octree_select: level 0 (prev == NULL) selects every node; otherwise upsamples prev [rp^3]

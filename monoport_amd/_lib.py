@@ -95,6 +95,7 @@ NEAREST_MAX_Z, NEAREST_MIN_Z = 0, 1
 # MP_CONN_* connectivities of mp_volume_keep_largest (include/monoport_hip.h)
 CONN_6, CONN_26 = 6, 26
 MAX_VIEWS = 8  # MP_MAX_VIEWS: views per mp_query_views / mp_mlp_forward_views call
+MAX_FRAME_VIEWS = 64  # MP_MAX_FRAME_VIEWS = mp_max_frame_views(): frames x views per mp_recon_views_batch call
 MAX_FRAMES = 32  # kMaxFrames (csrc/mp_internal.h) = mp_max_frames(): frames per batched query / recon call
 
 # name -> (restype, argtypes); kept in one table so tests can check the exported surface against
@@ -145,6 +146,10 @@ SIGNATURES = {
                                     _pf32, _pint, c_int, c_f32, c_int, c_vp, c_vp, ctypes.POINTER(ReconEarly), c_vp]),
     "mp_recon_views": (c_int, [c_vp, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_int, c_f32, _pf32, _pf32,
                                _pint, c_int, c_f32, c_int, c_int, c_vp, c_vp, ctypes.POINTER(ReconEarly), c_vp]),
+    "mp_max_frame_views": (c_int, []),
+    "mp_recon_views_batch": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_int, c_f32, _pf32,
+                                     _pf32, _pint, c_int, c_f32, c_int, c_int, c_vp, c_vp,
+                                     ctypes.POINTER(ReconEarly), c_vp]),
     "mp_concat3_add": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_i64, c_vp, c_vp]),
     "mp_prepare_inputs": (c_int, [c_vp, c_vp, c_i64, _pf32, _pf32, c_vp, c_vp, c_vp]),
     "mp_octree_select": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_f32, c_vp,

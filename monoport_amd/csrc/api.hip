@@ -280,7 +280,8 @@ static int check_topk(mp_ctx *ctx, const char *who, int r, long long k, float ma
 }
 
 // What mp_recon_batch_proj (views == nullptr: n_frames frames with a projection each, NULL = orthogonal) and
-// mp_recon_views (one frame seen by views->nv maps with projection[0]) do once head, counts and maps are accepted.
+// mp_recon_views / mp_recon_views_batch (n_frames frames seen by views->nv maps each, all with projection[0]) do once
+// head, counts and maps are accepted.
 // num_points != nullptr (mp_recon_topk_batch): the fixed-budget selection with these per-level budgets and bounds.
 static int recon_checked(mp_ctx *ctx, const char *who, const Mlp &m, int n_frames, const float *const *feat_hwc, int h,
                          int w, const float *const *calib, const int *projection, float z_scale, const float *b_min,
@@ -1178,12 +1179,14 @@ int mp_recon_topk_batch(mp_ctx *ctx, int mlp, int n_frames, const float *const *
                        stream, nullptr, k, max_dist);
 }
 
-int mp_recon_views(mp_ctx *ctx, int mlp, int n_views, const float *const *feat_hwc, int c, int h, int w,
-                   const float *const *calib, int projection, float z_scale,
-                   const float *b_min, const float *b_max, const int *resolutions, int n_levels,
-                   float balance, int final_level, int view, float *volume, int32_t *status,
-                   const mp_recon_early *early, mp_stream stream) {
-  const char *who = "mp_recon_views";
+// mp_recon_views (batch == 0: one frame, today's one-frame lattice kernel) and mp_recon_views_batch (batch != 0:
+// n_frames frames on the batched one) refuse the same, in the same order, and end in the same driver call
+static int recon_views_checked(mp_ctx *ctx, const char *who, int mlp, int n_frames, int n_views, int batch,
+                               const float *const *feat_hwc, int c, int h, int w, const float *const *calib,
+                               int projection, float z_scale, const float *b_min, const float *b_max,
+                               const int *resolutions, int n_levels, float balance, int final_level, int view,
+                               float *const *volume, int32_t *const *status, const mp_recon_early *early,
+                               mp_stream stream) {
   HeadCall call(ctx, mlp, c);
   if (call.rc != MP_OK) return call.rc;
   const Mlp *m = call.m;
@@ -1195,15 +1198,47 @@ int mp_recon_views(mp_ctx *ctx, int mlp, int n_views, const float *const *feat_h
                 m->c, m->cout);
   if (view < 0 || view >= n_views)
     return fail(ctx, MP_ERR_ARG, "%s: view %d outside 0..%d", who, view, n_views - 1);
+  if (batch) {
+    rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+    if (rc != MP_OK) return rc;
+    if (n_frames * n_views > kMaxFrameViews)
+      return fail(ctx, MP_ERR_ARG, "%s: at most %d frames x views per call, got %d x %d", who, kMaxFrameViews, n_frames,
+                  n_views);
+  }
   if (!feat_hwc || !calib || !b_min || !b_max || !resolutions || !volume || !status || n_levels < 1 ||
       n_levels > 8 || h <= 0 || w <= 0)
     return bad_argument(ctx, who);
-  rc = check_maps(ctx, who, "view", n_views, feat_hwc, calib);
+  rc = check_maps(ctx, who, "view", n_frames * n_views, feat_hwc, calib);
   if (rc != MP_OK) return rc;
-  const ReconViews views = {n_views, view};
-  return recon_checked(ctx, who, *m, 1, feat_hwc, h, w, calib, &projection, z_scale, b_min, b_max, resolutions,
-                       n_levels, MP_ERR_ARG, balance, final_level, &volume, &status, early, "early->flags_dev", stream,
+  for (int f = 0; f < n_frames; ++f)
+    if (!volume[f] || !status[f]) return fail(ctx, MP_ERR_ARG, "%s: null buffer for frame %d", who, f);
+  const ReconViews views = {n_views, view, batch};
+  return recon_checked(ctx, who, *m, n_frames, feat_hwc, h, w, calib, &projection, z_scale, b_min, b_max, resolutions,
+                       n_levels, MP_ERR_ARG, balance, final_level, volume, status, early, "early->flags_dev", stream,
                        &views);
+}
+
+int mp_recon_views(mp_ctx *ctx, int mlp, int n_views, const float *const *feat_hwc, int c, int h, int w,
+                   const float *const *calib, int projection, float z_scale,
+                   const float *b_min, const float *b_max, const int *resolutions, int n_levels,
+                   float balance, int final_level, int view, float *volume, int32_t *status,
+                   const mp_recon_early *early, mp_stream stream) {
+  // a null volume / status stays this entry's "bad argument"
+  return recon_views_checked(ctx, "mp_recon_views", mlp, 1, n_views, 0, feat_hwc, c, h, w, calib, projection, z_scale,
+                             b_min, b_max, resolutions, n_levels, balance, final_level, view,
+                             volume ? &volume : nullptr, status ? &status : nullptr, early, stream);
+}
+
+int mp_max_frame_views(void) { return kMaxFrameViews; }
+
+int mp_recon_views_batch(mp_ctx *ctx, int mlp, int n_frames, int n_views, const float *const *feat_hwc, int c, int h,
+                         int w, const float *const *calib, int projection, float z_scale, const float *b_min,
+                         const float *b_max, const int *resolutions, int n_levels, float balance, int final_level,
+                         int view, float *const *volume, int32_t *const *status, const mp_recon_early *early,
+                         mp_stream stream) {
+  return recon_views_checked(ctx, "mp_recon_views_batch", mlp, n_frames, n_views, 1, feat_hwc, c, h, w, calib,
+                             projection, z_scale, b_min, b_max, resolutions, n_levels, balance, final_level, view,
+                             volume, status, early, stream);
 }
 
 int mp_recon(mp_ctx *ctx, int mlp, const float *feat_hwc, int c, int h, int w, const float *calib,

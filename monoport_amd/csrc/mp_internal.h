@@ -163,10 +163,39 @@ struct ViewLatticeDev : ViewSetDev {
   float *vol;
   int view;
 };
-// launch_recon's second way to evaluate a level's nodes: feat_hwc / calib are then the nv views' arrays, proj[0]
-// their one projection, and the call has one frame
+// One octree level of n frames x nv views (mp_recon_views_batch): what ViewLatticeDev holds, for every frame of the
+// call.  The frames share nv, view, the projection mode and the lattice fields of PointSrc; per frame: the packed
+// node list, the level's volume and the count (*n_dev, or n where n_dev == nullptr); per (frame, view), frame-major:
+// the map and the calibration.  16 + 40 + 32 * 32 + 2 * 64 * 8 = 2104 B of kernel arguments.
+constexpr int kMaxFrameViews = MP_MAX_FRAME_VIEWS;
+struct ViewFrameDev {
+  const uint32_t *packed;
+  float *vol;
+  const int32_t *n_dev;
+  long long n;
+};
+struct ViewLatticeBatchDev {
+  int nv, proj, view;
+  int n;  // frames
+  int stride, level_res;
+  float res_final, half_step, bmin[3], blen[3];
+  ViewFrameDev it[kMaxFrames];
+  const float *feat[kMaxFrameViews];   // [f * nv + v]
+  const float *calib[kMaxFrameViews];
+#ifdef __HIPCC__
+  __device__ __forceinline__ long long count(int f) const {
+    const int32_t *p = it[f].n_dev;
+    return p ? (long long)*p : it[f].n;
+  }
+#endif
+};
+static_assert(sizeof(ViewLatticeBatchDev) + 256 <= 4096, "kernel arguments: the frames + the MLP descriptor must stay below 4 KB");
+// launch_recon's second way to evaluate a level's nodes: feat_hwc / calib are then the views' arrays ([f * nv + v]
+// of the call's frames), proj[0] their one projection.  batch == 0 (mp_recon_views): one frame on the one-frame
+// lattice kernel; batch != 0 (mp_recon_views_batch): 1..kMaxFrames frames, nv * frames <= kMaxFrameViews, every
+// level of all of them in one launch of the batched lattice kernel
 struct ReconViews {
-  int nv, view;
+  int nv, view, batch;
 };
 // launch_recon's second way to SELECT a level's nodes (mp_recon_topk_batch, topk.hip): the num_points[l] most uncertain
 // nodes within max_dist[l] (NULL: no bound) instead of the dilated boundary; scratch: topk_scratch_bytes(n_frames, r_last)
@@ -274,6 +303,9 @@ int launch_query_views(mp_ctx *ctx, const Mlp &m, const ViewSetDev &set, int h, 
 // set.src.n_dev is set
 int launch_query_views_lattice(mp_ctx *ctx, const Mlp &m, const ViewLatticeDev &set, int h, int w, float z_scale,
                                long long max_points, hipStream_t st);
+// one octree level of mp_recon_views_batch: the frames of `set`, at most max_points nodes EACH
+int launch_query_views_lattice_batch(mp_ctx *ctx, const Mlp &m, const ViewLatticeBatchDev &set, int h, int w,
+                                     float z_scale, long long max_points, hipStream_t st);
 // pack.hip
 int launch_pack_hwc(mp_ctx *ctx, const float *src, int c_src, int h, int w, float *dst, int c_dst,
                     int c_off, hipStream_t st);

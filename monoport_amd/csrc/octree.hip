@@ -15,7 +15,8 @@
 //      samples (point_order.hip), so that the 32 points of a query tile share table rows.
 //   3. the fused query kernel (query.hip) reads the list and its device-side count, and scatters
 //      exact occupancies straight into the level volume.  For a multi-view head (mp_recon_views) step 3 is
-//      the lattice variant of the multi-view kernel (query_views.hip); steps 1-2 are the same kernels.
+//      the lattice variant of the multi-view kernel (query_views.hip), for mp_recon_views_batch its batched form
+//      on all frames at once; steps 1-2 are the same kernels.
 // No host synchronisation anywhere: counts stay on the device (`status`).
 #include <cmath>
 #include <cstdlib>
@@ -498,6 +499,8 @@ int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
                  int n_levels, float balance, int final_level, float *const *volume,
                  int32_t *const *status, const mp_recon_early *early, hipStream_t st,
                  const ReconViews *views, const ReconTopk *topk) {
+  if (views && (views->batch ? n_frames * views->nv > kMaxFrameViews : n_frames != 1))
+    return fail(ctx, MP_ERR_ARG, "multi-view octree: %d frames x %d views", n_frames, views->nv);
   // carve the scratch arena: one private set of level buffers per frame
   const size_t per_frame = recon_scratch_bytes(res, n_levels, h, w);
   LevelBufs lv[kMaxFrames][8];
@@ -533,7 +536,7 @@ int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
     QueryItem &q = set.it[f];
     q.feat = feat_hwc[f];
     q.calib = calib[f];
-    q.proj = proj ? proj[f] : MP_PROJ_ORTHOGONAL;  // NULL: every frame orthogonal
+    q.proj = proj ? proj[views ? 0 : f] : MP_PROJ_ORTHOGONAL;  // NULL: every frame orthogonal; views: one mode
     q.src.packed = packed[f];
     q.src.res_final = (float)rf;
     q.src.half_step = (1.0f / (float)rf) / 2.0f;
@@ -544,10 +547,40 @@ int launch_recon(mp_ctx *ctx, void *scratch, const Mlp &m, int n_frames,
     MP_HIP(ctx, hipMemsetAsync(status[f], 0, sizeof(int32_t) * (1 + n_levels), st));
   }
 
-  // Step 3 of a level: the frames' single-view set through launch_query_set, or (views: one frame) the nv views
-  // of feat_hwc / calib on the level's node list, row views->view of their result into the level's volume
+  // Step 3 of a level: the frames' single-view set through launch_query_set, or (views) the nv views of feat_hwc /
+  // calib on the level's node list, row views->view of their result into the level's volume: one frame on the
+  // one-frame lattice kernel, or (views->batch) all frames in one launch of the batched one
   auto eval_level = [&](long long max_points, bool device_counts) -> int {
     if (!views) return launch_query_set(ctx, m, set, h, w, z_scale, max_points, device_counts, st);
+    if (views->batch) {
+      ViewLatticeBatchDev vb;
+      std::memset(&vb, 0, sizeof(vb));
+      const PointSrc &s0 = set.it[0].src;  // the lattice of the level: the same for every frame
+      vb.nv = views->nv;
+      vb.proj = set.it[0].proj;
+      vb.view = views->view;
+      vb.n = n_frames;
+      vb.stride = s0.stride;
+      vb.level_res = s0.level_res;
+      vb.res_final = s0.res_final;
+      vb.half_step = s0.half_step;
+      for (int i = 0; i < 3; ++i) {
+        vb.bmin[i] = s0.bmin[i];
+        vb.blen[i] = s0.blen[i];
+      }
+      for (int f = 0; f < n_frames; ++f) {
+        const QueryItem &q = set.it[f];
+        vb.it[f].packed = q.src.packed;
+        vb.it[f].vol = q.out;
+        vb.it[f].n_dev = q.src.n_dev;
+        vb.it[f].n = q.src.n;
+      }
+      for (int i = 0; i < n_frames * views->nv; ++i) {
+        vb.feat[i] = feat_hwc[i];
+        vb.calib[i] = calib[i];
+      }
+      return launch_query_views_lattice_batch(ctx, m, vb, h, w, z_scale, max_points / n_frames, st);
+    }
     ViewLatticeDev vs;
     std::memset(&vs, 0, sizeof(vs));
     vs.nv = views->nv;

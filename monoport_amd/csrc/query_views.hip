@@ -25,6 +25,13 @@
 // (x | y<<10 | z<<20, shared by all views) turned into world coordinates by lattice_coord, their number is read
 // from device memory, and only the columns of ONE view write: row `view` of the result, scattered to
 // volume[z,y,x].  Gather, layers, view mean and tile mapping are those of the explicit-point kernel.
+//
+// LATTICE and BATCH (mp_recon_views_batch, one octree level of n frames): the tiles of the frames form one index
+// space as in query_common.h ("tiles of a launch") with P = G: frame f owns the next ceil(count_f / G) global tiles,
+// so a tile never spans two frames, a frame without nodes owns none, and the coarse levels of several frames fill
+// the machine together.  The owner is looked up from the device-side counts at the top of every tile iteration and
+// made wave-uniform there; from then on the tile is a tile of the one-frame lattice kernel on that frame's node
+// list, volume, maps and calibrations (ViewLatticeFrame), line for line.
 #include <cstring>
 
 #include "mp_internal.h"
@@ -117,19 +124,102 @@ __device__ __forceinline__ float column_z(const SET &set, int p, int magic, long
 // DIRECT = true: SurfaceClassifier.forward on explicit features [V][C+1][N] (set.pts[v], row
 // stride set.sc), one output [Cout, N] written by the view-0 columns.
 // LATTICE = true: one octree level (see the head of this file); `set` is then a ViewLatticeDev.
-template <bool LATTICE>
+// BATCH (with LATTICE): the same level of n frames; `set` is then a ViewLatticeBatchDev.
+template <bool LATTICE, bool BATCH = false>
 struct ViewSetArg {
   typedef ViewSetDev type;
 };
 template <>
-struct ViewSetArg<true> {
+struct ViewSetArg<true, false> {
   typedef ViewLatticeDev type;
 };
+template <>
+struct ViewSetArg<true, true> {
+  typedef ViewLatticeBatchDev type;
+};
 
-template <int C, int COUT, int WPS, bool DIRECT, bool LATTICE = false>
+// Frame f of a ViewLatticeBatchDev under the member names of ViewLatticeDev, so that the tile body reads either.
+// feat / calib point at the frame's nv entries INSIDE the kernel arguments: indexing them stays a scalar load.
+struct ViewLatticeFrame {
+  int nv, proj, view;
+  const float *const *feat;
+  const float *const *calib;
+  PointSrc src;
+  float *vol;
+};
+__device__ __forceinline__ ViewLatticeFrame lattice_frame(const ViewLatticeBatchDev &set, int f) {
+  ViewLatticeFrame fr;
+  fr.nv = set.nv;
+  fr.proj = set.proj;
+  fr.view = set.view;
+  fr.feat = set.feat + f * set.nv;
+  fr.calib = set.calib + f * set.nv;
+  fr.src.pts = nullptr;
+  fr.src.sn = fr.src.sc = fr.src.out_stride = 0;
+  fr.src.packed = set.it[f].packed;
+  fr.src.stride = set.stride;
+  fr.src.level_res = set.level_res;
+  fr.src.res_final = set.res_final;
+  fr.src.half_step = set.half_step;
+  for (int i = 0; i < 3; ++i) {
+    fr.src.bmin[i] = set.bmin[i];
+    fr.src.blen[i] = set.blen[i];
+  }
+  fr.src.n_dev = set.it[f].n_dev;
+  fr.src.n = set.it[f].n;
+  fr.vol = set.it[f].vol;
+  return fr;
+}
+__device__ __forceinline__ const ViewSetDev &lattice_frame(const ViewSetDev &set, int) { return set; }
+__device__ __forceinline__ const ViewLatticeDev &lattice_frame(const ViewLatticeDev &set, int) { return set; }
+
+// ceil(n / gpts) for a level's count n (<= 1023^3 < 2^30 - 64) and gpts = floor(64 / V) points per tile, V <= 8:
+// m35 = ceil(2^35 / gpts) <= 2^32 and q = ((n + gpts - 1) m35) >> 35 is the exact quotient, because the excess
+// e = m35 gpts - 2^35 is 0 for a power of two and < gpts <= 21 < 2^5 otherwise, so (n + gpts - 1) e < 2^35; the
+// product stays below 2^62.  Keeps 32 integer divisions out of every tile's lookup.
+__device__ __forceinline__ long long view_tiles(long long n, int gpts, unsigned long long m35) {
+  return (long long)(((unsigned long long)(n + gpts - 1) * m35) >> 35);
+}
+
+// tile_owner (query_common.h) for the frames of a ViewLatticeBatchDev and tiles of gpts points: fi = the frame
+// that owns `gtile` (-1: past the last tile of the last frame), tile0 = its first tile, n = its count.  Every
+// thread reads the same counts, so the result is the same in every lane; the caller makes that known to the
+// compiler (readfirstlane), which keeps the frame's pointers in SGPRs.
+__device__ __forceinline__ void view_tile_owner(const ViewLatticeBatchDev &set, long long gtile, int gpts,
+                                                unsigned long long m35, int &fi_out, long long &tile0_out,
+                                                long long &n_out) {
+  int fi = -1;
+  long long tile0 = 0, n_owner = 0, acc = 0;
+  for (int f0 = 0; f0 < set.n; f0 += 8)  // groups of 8 loads in flight, as in tile_owner
+#pragma unroll
+    for (int fk = 0; fk < 8; ++fk) {
+      const int f = f0 + fk;
+      if (f < set.n) {
+        const long long nf = set.count(f);
+        const long long t = view_tiles(nf, gpts, m35);
+        if (fi < 0 && gtile < acc + t) {
+          fi = f;
+          tile0 = acc;
+          n_owner = nf;
+        }
+        acc += t;
+      }
+    }
+  fi_out = fi;
+  tile0_out = tile0;
+  n_out = n_owner;
+}
+__device__ __forceinline__ long long uniform64(long long v) {
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long long)v);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)v >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+template <int C, int COUT, int WPS, bool DIRECT, bool LATTICE = false, bool BATCH = false>
 __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
-    MlpPack mlp, int fh, int fw, float z_scale, int act, typename ViewSetArg<LATTICE>::type set) {
+    MlpPack mlp, int fh, int fw, float z_scale, int act, typename ViewSetArg<LATTICE, BATCH>::type aset) {
   static_assert(!(DIRECT && LATTICE), "explicit features have no lattice");
+  static_assert(LATTICE || !BATCH, "frames are batched on the lattice only");
   constexpr int ROWB = C * 4;
   constexpr int NGX = C / 8;  // K groups of the feature segment
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -140,21 +230,39 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
   const int lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 31, h = lane >> 5;
-  const int nv = set.nv;
+  const int nv = aset.nv;
   const int gpts = kTilePts / nv;  // points per tile
   const int ncol = gpts * nv;      // live columns
   const int magic = (65536 + nv - 1) / nv;  // column_view
-  long long n_pts;
-  if constexpr (LATTICE)
-    n_pts = set.src.n_dev ? (long long)*set.src.n_dev : set.src.n;  // a level's count lives on the device
-  else
-    n_pts = set.n;
-  const long long tiles = (n_pts + gpts - 1) / gpts;
+  long long n_pts = 0, tiles = 0;
+  unsigned long long m35 = 0;  // view_tiles
+  if constexpr (BATCH) {
+    m35 = ((1ull << 35) + (unsigned)gpts - 1) / (unsigned)gpts;
+  } else {
+    if constexpr (LATTICE)
+      n_pts = aset.src.n_dev ? (long long)*aset.src.n_dev : aset.src.n;  // a level's count lives on the device
+    else
+      n_pts = aset.n;
+    tiles = (n_pts + gpts - 1) / gpts;
+  }
 
   const int swz = h ^ (j & 15);
   const WStream ws = make_wstream(mlp.base, mlp.n_floats, lane);
 
-  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+  for (long long gtile = blockIdx.x; BATCH || gtile < tiles; gtile += gridDim.x) {
+    long long tile = gtile;
+    int fi = 0;
+    if constexpr (BATCH) {
+      // the tile's frame: gtile and the counts are the same for every thread of the workgroup, so all of them
+      // leave the loop in the same trip and take the same number of barriers
+      long long tile0;
+      view_tile_owner(aset, gtile, gpts, m35, fi, tile0, n_pts);
+      fi = __builtin_amdgcn_readfirstlane(fi);
+      if (fi < 0) break;  // past the last tile of the last frame
+      tile = gtile - uniform64(tile0);
+      n_pts = uniform64(n_pts);
+    }
+    const auto &set = lattice_frame(aset, fi);
     const long long n0 = tile * gpts;
 
     // ---------------- gather ----------------
@@ -290,7 +398,8 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
         // the group's z mean, this column's own projection and whether any view is non-finite
         float zsum = 0.0f, xo = 0.0f, yo = 0.0f;
         bool poisoned = false;
-        float *__restrict__ out = set.out[0];
+        float *__restrict__ out = nullptr;
+        if constexpr (!LATTICE) out = set.out[0];
         for (int u = 0; u < nv; ++u) {
           float x, y;
           const float zf = view_z<C, DIRECT, LATTICE>(set, u, n, z_scale, x, y);
@@ -299,7 +408,7 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
           if (u == v) {
             xo = x;
             yo = y;
-            if (!DIRECT && !LATTICE) out = set.out[u];
+            if constexpr (!DIRECT && !LATTICE) out = set.out[u];
           }
         }
         val = fmaf(wz, __fdiv_rn(zsum, (float)nv), val);
@@ -362,6 +471,36 @@ int launch_query_views_lattice(mp_ctx *ctx, const Mlp &m, const ViewLatticeDev &
   const long long tiles = (max_points + gpts - 1) / gpts;
   if (tiles <= 0) return MP_OK;
   const long long grid = query_grid(tiles, (long long)ctx->n_cu * WPS, set.src.n_dev != nullptr);
+  if (const int rc = prof_begin(ctx, st)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kQueryThreads), lds, st, m.pack(), h, w, z_scale, m.act,
+                     set);
+  if (const int rc = prof_end(ctx, st)) return rc;
+  MP_HIP(ctx, hipGetLastError());
+  return MP_OK;
+}
+
+// The same level of set.n frames in one launch: the grid covers the frames' tiles together (each frame's rounded
+// up on its own, as view_tile_owner counts them), so what one frame leaves of the machine the next one fills.
+int launch_query_views_lattice_batch(mp_ctx *ctx, const Mlp &m, const ViewLatticeBatchDev &set, int h, int w,
+                                     float z_scale, long long max_points, hipStream_t st) {
+  if (set.nv < 1 || set.nv > kMaxViews)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "multi-view octree: 1..%d views, got %d", kMaxViews, set.nv);
+  if (m.c != 256 || m.cout != 1 || m.precision != MP_PREC_F32)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "multi-view octree: f32 netG heads (C=256, Cout=1); got C=%d Cout=%d precision %d",
+                m.c, m.cout, m.precision);
+  if (set.view < 0 || set.view >= set.nv)
+    return fail(ctx, MP_ERR_ARG, "multi-view octree: view %d of %d", set.view, set.nv);
+  if (set.n < 1 || set.n > kMaxFrames || set.n * set.nv > kMaxFrameViews)
+    return fail(ctx, MP_ERR_ARG, "multi-view octree: 1..%d frames and at most %d frames x views per launch, got %d x %d",
+                kMaxFrames, kMaxFrameViews, set.n, set.nv);
+  constexpr int C = 256, WPS = 2;
+  constexpr int lds = kTilePts * C * 4 + kHbBytes;
+  auto kern = pifu_query_views_kernel<C, 1, WPS, false, true, true>;
+  if (const int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
+  const long long gpts = kTilePts / set.nv;
+  const long long tiles = (max_points + gpts - 1) / gpts * set.n;
+  if (tiles <= 0) return MP_OK;
+  const long long grid = query_grid(tiles, (long long)ctx->n_cu * WPS, set.it[0].n_dev != nullptr);
   if (const int rc = prof_begin(ctx, st)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kQueryThreads), lds, st, m.pack(), h, w, z_scale, m.act,
                      set);

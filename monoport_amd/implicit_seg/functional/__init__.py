@@ -37,7 +37,8 @@ Constructor flags (upstream names):
                     kernel).  ``view`` (0..V-1) names the row of the [V,1,N] result the caller's
                     ``query_func`` returns: the view-averaged prediction times THAT view's in-image mask
                     (``[:1]`` of RTL/main.py's get_preds()[0][0] is view 0).  Off by default: a multi-view
-                    ``query_func`` then runs on the level-at-a-time engine.
+                    ``query_func`` then runs on the level-at-a-time engine.  ``forward_many`` of a trusted engine
+                    serves such frames through ops.recon_views_batch (all frames of a chunk per octree level).
   ``align_corners=True``, ``visualize=True``, ``use_shadow=True``, ``channels != 1``: not built,
                     NotImplementedError at construction.
 """
@@ -136,6 +137,11 @@ class _Seg3dEngine(nn.Module):
 
     def _recon_many(self, bindings, early):
         """The fused reconstruction of several single-view bindings in one call -> (volumes, status [n,1+levels])."""
+        raise NotImplementedError
+
+    def _recon_many_views(self, bindings):
+        """The fused reconstruction of several multi-view bindings of one ``batch_key`` -> (volumes, status rows,
+        early flags [n,2] on the host)."""
         raise NotImplementedError
 
     @property
@@ -241,8 +247,11 @@ class _Seg3dEngine(nn.Module):
         trusted state (see ``forward``) every frame is bound through its one-point probe and ALL of
         them go through one ``mp_recon_batch`` -- every octree level of all frames in one fused-query
         launch, one host sync for all statuses -- with results identical to the per-frame calls bit
-        for bit.  In any other state (not yet validated, ``validate = "always"``, a re-validation
-        due, a binding that changed) the frames are served one by one by ``forward``."""
+        for bit.  With ``fuse_views`` the frames' multi-view bindings, if they share head, V, ``view``, projection
+        and map size (``ViewsBinding.batch_key``), go through ``ops.recon_views_batch`` in chunks of
+        ``ops.max_view_frames(V)`` frames, one early wait per chunk.  In any other state (not yet validated,
+        ``validate = "always"``, a re-validation due, a binding that changed, bindings that do not batch together) the
+        frames are served one by one by ``forward``."""
         n = len(kwargs_list)
         if n >= 2 and self.validate == "always" and not getattr(self, "_warned_many", False):
             self._warned_many = True
@@ -258,14 +267,21 @@ class _Seg3dEngine(nn.Module):
             with record_query(capture_only=True, views=self.fuse_views) as rec:
                 self.query_func(points=probe, **kw)
             b = rec.binding
-            # a multi-view binding is one point set per call (mp_recon_views): its frames go one by one
-            if (b is None or rec.calls != 1 or not b.batchable
-                    or b.trust_key(self.view) != self._trusted_key):
+            # single-view bindings share one ops.recon_batch call (``batchable``); multi-view bindings of one
+            # ``batch_key`` share ops.recon_views_batch calls (``batch_many``); anything else goes frame by frame
+            many = getattr(b, "batch_many", None)
+            if (b is None or rec.calls != 1 or not (b.batchable or many is not None)
+                    or b.trust_key(self.view) != self._trusted_key
+                    or (many is not None and b.batch_key(self.view) != (bindings or [b])[0].batch_key(self.view))):
                 return [self(**kw) for kw in kwargs_list]  # forward() re-validates
             bindings.append(b)
-        early = self._early_flags(self._device_tag.device, n)
-        volumes, status = self._recon_many(bindings, early)
-        flags = early.wait().clone()  # the one host sync of the whole batch: its coarsest level (see forward)
+        if getattr(bindings[0], "batch_many", None) is not None:
+            # one wait per chunk of ops.max_view_frames(V) frames, each for its coarsest level only
+            volumes, status, flags = self._recon_many_views(bindings)
+        else:
+            early = self._early_flags(self._device_tag.device, n)
+            volumes, status = self._recon_many(bindings, early)
+            flags = early.wait().clone()  # the one host sync of the whole batch: its coarsest level (see forward)
         self._since_check += n
         self.last_status, self.last_path = status[-1], "fused"
         return [None if int(flags[i, 0]) == 0 else volumes[i][None, None] for i in range(n)]
@@ -326,6 +342,12 @@ class Seg3dLossless(_Seg3dEngine):
                                b0.z_scale, self.b_min[0], self.b_max[0], self.resolutions,
                                self.balance_value, final_level=self.final_level, early=early,
                                projections=[b.projection for b in bindings])
+
+    def _recon_many_views(self, bindings):
+        dev = self._device_tag.device
+        return type(bindings[0]).batch_many(bindings, self.b_min[0], self.b_max[0], self.resolutions,
+                                            self.balance_value, self.final_level, view=self.view,
+                                            early_flags=lambda n: self._early_flags(dev, n))
 
 
 class Seg3dTopk(_Seg3dEngine):

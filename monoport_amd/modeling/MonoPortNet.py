@@ -92,6 +92,35 @@ class ViewsBinding:
     def num_views(self):
         return len(self.maps)
 
+    def batch_key(self, view=0):
+        """Bindings with equal keys can share one ops.recon_views_batch call: the same head, V, ``view``, projection
+        and map size.  (``batchable`` stays False: that flag says "a frame of ops.recon_batch".)"""
+        return self.trust_key(view) + (tuple(self.maps[0].shape),)
+
+    @staticmethod
+    def batch_many(bindings, b_min, b_max, resolutions, balance, final_level, view=0, early_flags=None):
+        """The fused reconstructions of several bindings with one ``batch_key``, ops.recon_views_batch in chunks of
+        ``ops.max_view_frames(V)`` -> (volumes, status rows) on the device and, with ``early_flags`` (n ->
+        ops.EarlyFlags for n frames), the frames' (non-empty, differs) flags [n,2] on the host: one wait per chunk,
+        for its coarsest level only.  Results equal the per-frame ``recon`` calls bit for bit."""
+        b0 = bindings[0]
+        key = b0.batch_key(view)
+        if any(b.batch_key(view) != key for b in bindings):
+            raise ValueError("ViewsBinding.batch_many: the bindings differ in head, views, view, projection or map size")
+        step = ops.max_view_frames(b0.num_views)
+        volumes, rows, flags = [], [], []
+        for f0 in range(0, len(bindings), step):
+            chunk = bindings[f0:f0 + step]
+            early = None if early_flags is None else early_flags(len(chunk))
+            vols, status = ops.recon_views_batch(b0.mlp, [b.maps for b in chunk], [b.calibs for b in chunk],
+                                                 b0.projection, b0.z_scale, b_min, b_max, resolutions, balance,
+                                                 final_level=final_level, view=view, early=early)
+            volumes += vols
+            rows += list(status)
+            if early is not None:
+                flags.append(early.wait().clone())
+        return volumes, rows, (torch.cat(flags) if flags else None)
+
 
 class record_query:
     """Context manager (per host thread): counts the ``MonoPortNet.query`` calls made inside it

@@ -27,6 +27,7 @@ class Context:
     def __init__(self, device_index):
         self.lib = _lib.load()
         assert self.lib.mp_max_frames() == MAX_FRAMES, "_lib.MAX_FRAMES and the library's kMaxFrames disagree"
+        assert self.lib.mp_max_frame_views() == MAX_FRAME_VIEWS, "_lib.MAX_FRAME_VIEWS and MP_MAX_FRAME_VIEWS disagree"
         self.device_index = int(device_index)
         handle = ctypes.c_void_p()
         rc = self.lib.mp_create(self.device_index, ctypes.byref(handle))
@@ -83,6 +84,7 @@ def _f32c(t):
 # ---- argument checks and marshalling shared by the wrappers below (no context needed: CPU tensors pass them too) ----
 MAX_FRAMES = _lib.MAX_FRAMES  # kMaxFrames: frames per mp_recon_batch / mp_query_batch / mp_query_counted_batch call
 MAX_VIEWS = _lib.MAX_VIEWS  # MP_MAX_VIEWS
+MAX_FRAME_VIEWS = _lib.MAX_FRAME_VIEWS  # MP_MAX_FRAME_VIEWS: frames x views per mp_recon_views_batch call
 
 
 def _float3(v):
@@ -754,6 +756,52 @@ def recon_views(mlp, maps, calibs, projection, z_scale, b_min, b_max, resolution
         _final_level(final_level), int(view), _ptr(volume), _ptr(status), early_arg, _stream(volume)), "mp_recon_views")
     _keep_until_done(dev, cals, expect)
     return volume, status
+
+
+def max_view_frames(n_views):
+    """Frames of ``n_views`` views one ``recon_views_batch`` call accepts: callers chunk by it."""
+    return min(MAX_FRAMES, MAX_FRAME_VIEWS // int(n_views))
+
+
+def recon_views_batch(mlp, maps, calibs, projection, z_scale, b_min, b_max, resolutions, balance=0.5,
+                      final_level="dilate3", view=0, volumes=None, status=None, early=None, expect_level0=None):
+    """mp_recon_views_batch: ``recon_views`` over n independent frames of V views each in ONE call -- every octree
+    level evaluates the selected nodes of all frames in one launch of the multi-view kernel.  maps: list of n lists of
+    V channels-last maps [H,W,C]; calibs: [n,V,>=3,4] or n sequences of V calibrations; projection, ``view``: one for
+    all frames; volumes: list of n [R,R,R] f32; status: [n, 1+levels] int32.  n <= ``max_view_frames(V)``.  Returns
+    (volumes, status) on the device, nothing synchronised; frame f's equal ``recon_views`` on its maps and
+    calibrations bit for bit.  ``early``: an ``EarlyFlags`` for n frames, ``expect_level0``: n [r0,r0,r0] f32 tensors
+    (or None entries), as in ``recon_batch``."""
+    who = "recon_views_batch"
+    ctx = mlp.ctx
+    n = len(maps)
+    if n == 0 or len(calibs) != n:
+        raise ValueError("%s: %d frames, %d sets of calibrations" % (who, n, len(calibs)))
+    v_n = len(maps[0])
+    _check_count(who, "views", v_n, MAX_VIEWS)
+    if any(len(m) != v_n for m in maps):
+        raise ValueError("%s: every frame needs the same number of views (%d)" % (who, v_n))
+    _check_count(who, "frames of %d views" % v_n, n, max_view_frames(v_n))
+    flat = [m for frame in maps for m in frame]
+    h, w, c, dev = _maps(who, flat)
+    cals = [_calib_dev(cb, dev) for frame in calibs for cb in _calib_list(frame, v_n, who)]
+    res = [int(r) for r in resolutions]
+    if volumes is None:
+        volumes = [torch.empty((res[-1],) * 3, dtype=torch.float32, device=dev) for _ in range(n)]
+    elif len(volumes) != n:
+        raise ValueError("%s: %d frames, %d volumes" % (who, n, len(volumes)))
+    if status is None:
+        status = torch.empty((n, 1 + len(res)), dtype=torch.int32, device=dev)
+    elif tuple(status.shape) != (n, 1 + len(res)) or not status.is_contiguous() or status.dtype != torch.int32:
+        raise ValueError("%s: status must be contiguous int32 [%d,%d]" % (who, n, 1 + len(res)))
+    early_arg = _early_arg(who, early, n, expect_level0, res[0])
+    ctx.check(ctx.lib.mp_recon_views_batch(
+        ctx.handle, mlp.id, n, v_n, _ptr_array(flat), c, h, w, _ptr_array(cals), _projection(projection),
+        float(z_scale), _float3(b_min), _float3(b_max), (ctypes.c_int * len(res))(*res), len(res), float(balance),
+        _final_level(final_level), int(view), _ptr_array(volumes), _ptr_array(status), early_arg,
+        _stream(volumes[0])), "mp_recon_views_batch")
+    _keep_until_done(dev, cals, expect_level0)
+    return volumes, status
 
 
 class LevelEngine:

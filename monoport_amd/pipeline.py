@@ -18,7 +18,10 @@ that host-side launch latency and GPU fill, not thread parallelism, are what mat
   a single frame's coarse levels, 5-25 k points, leave most of the 256 CUs idle);
 * a ``FramePipeline`` round-robins over ``depth`` slots, so independent frames on different
   streams fill the CUs that the coarse octree levels and the small encoder kernels leave idle
-  (``depth`` x ``batch`` frames in flight; BASELINE configs[3] asks for 8).
+  (``depth`` x ``batch`` frames in flight; BASELINE configs[3] asks for 8);
+* a ``ViewsSlot`` is the FrameSlot of a multi-view netG (a capture rig: ``batch`` frames of V views each): one
+  encoder pass over batch x V images, the octree of all frames through ``mp_recon_views_batch``, then the same
+  per-volume stages (``FramePipeline(..., slot_class=ViewsSlot)``).
 """
 import numpy as np
 import torch
@@ -91,10 +94,7 @@ class FrameSlot:
         owns static per-frame mesh buffers at the capacities of ``ops.marching_cubes_raw`` (12 r^2 vertices and
         24 r^2 faces: vertices, faces, normals, query points and predictions are about 57 MB per frame at 257^3), the
         batched mesh chain runs behind the octree on the slot's stream, and ``meshes()`` hands the results out."""
-        for name, net in (("netG", netG), ("netC", netC)):
-            if net is not None and net.surface_classifier.num_views > 1:
-                raise NotImplementedError("FrameSlot: %s has a multi-view head (num_views = %d); the slot runs the "
-                                          "single-view octree / colour engines" % (name, net.surface_classifier.num_views))
+        self.views = self._head_views(netG, netC, mesh)  # images per frame; refuses what the slot class does not run
         self.net = netG
         self.netC = netC
         self.device = torch.device(device)
@@ -106,15 +106,18 @@ class FrameSlot:
         r = self.res[-1]
         dev = self.device
         b = self.batch
+        bv = b * self.views  # images of the slot: the encoder's batch
         self.stream = torch.cuda.Stream(device=dev)
-        self.image = torch.zeros((b, 3, 512, 512), dtype=torch.float32, device=dev)
-        self.calib = torch.eye(4, dtype=torch.float32, device=dev)[None].repeat(b, 1, 1).contiguous()
-        # one [B,128,128,256] channels-last map; feats_hwc[b] are its per-frame views
-        self.feat_hwc_all = torch.empty((b, 128, 128, 256), dtype=torch.float32, device=dev)
-        self.feats_hwc = [self.feat_hwc_all[i] for i in range(b)]
+        self.image = torch.zeros((bv, 3, 512, 512), dtype=torch.float32, device=dev)
+        self.calib = torch.eye(4, dtype=torch.float32, device=dev)[None].repeat(bv, 1, 1).contiguous()
+        # what ``submit`` fills, one row per frame: the buffers themselves, or (ViewsSlot) their [B,V,...] form
+        self.image_in, self.calib_in = self._per_frame(self.image), self._per_frame(self.calib)
+        # one [B,128,128,256] channels-last map; feats_hwc[b] are its per-image views
+        self.feat_hwc_all = torch.empty((bv, 128, 128, 256), dtype=torch.float32, device=dev)
+        self.feats_hwc = [self.feat_hwc_all[i] for i in range(bv)]
         # skip tables of the slot's maps (ops.SKIP_TABLE unless the caller says otherwise) -- only for the MLP
         # precisions whose query kernel reads them (f32, f16x3): a table nobody reads is 16 GFLOP + 128 MB a frame
-        self.skip_table = ((ops.SKIP_TABLE if skip_table is None else bool(skip_table))
+        self.skip_table = ((ops.SKIP_TABLE if skip_table is None else bool(skip_table)) and self.views == 1
                            and ops.table_precision(netG.surface_classifier.precision))
         self.tables = (torch.empty((b, 128, 128, ops.SKIP_TABLE_ROWS), dtype=torch.float32, device=dev)
                        if self.skip_table else None)
@@ -171,6 +174,26 @@ class FrameSlot:
                 self.mesh_buffers["smooth_verts"] = torch.empty((b, cap_v, 3), dtype=torch.float32, device=dev)
             self._mesh_chains = [None] * b
 
+    def _head_views(self, netG, netC, mesh):
+        for name, net in (("netG", netG), ("netC", netC)):
+            if net is not None and net.surface_classifier.num_views > 1:
+                raise NotImplementedError("FrameSlot: %s has a multi-view head (num_views = %d); the slot runs the "
+                                          "single-view octree / colour engines (pipeline.ViewsSlot runs a multi-view "
+                                          "netG)" % (name, net.surface_classifier.num_views))
+        return 1
+
+    def _per_frame(self, buf):
+        return buf
+
+    def _octree(self, mlp, n):
+        """The octree of all frames of the slot level by level: one fused-query launch per level covers every frame
+        (mp_recon_batch takes up to MAX_RECON_BATCH frames per call)."""
+        for b0 in range(0, n, MAX_RECON_BATCH):
+            b1 = min(b0 + MAX_RECON_BATCH, n)
+            ops.recon_batch(mlp, self.feats_hwc[b0:b1], self.calib[b0:b1], Z_SCALE, self.b_min,
+                            self.b_max, self.res, self.balance, volumes=self.volumes[b0:b1],
+                            status=self.status[b0:b1], final_level=self.final_level)
+
     # convenience views for batch == 1 callers
     @property
     def volume(self):
@@ -216,19 +239,13 @@ class FrameSlot:
         r = self.res[-1]
         n = self.n_active
         if not self.hwc_direct:
-            for b in range(n):
+            for b in range(n * self.views):
                 ops.pack_features(feat[b:b + 1], out=self.feats_hwc[b])
         if self.tables is not None:  # f32 / f16x3 heads blend table rows (query_table.hip, query16.hip)
             # (re)made after every encoder pass; the handle of the previous pass unregisters the same
             # pointers only if they still point at its table views, so dropping it here is harmless
             self._table_handle = ops.skip_table_batch(mlp, self.feat_hwc_all[:n], out=self.tables[:n])
-        # the octree of all frames of the slot level by level: one fused-query launch per level
-        # covers every frame (mp_recon_batch takes up to MAX_RECON_BATCH frames per call)
-        for b0 in range(0, n, MAX_RECON_BATCH):
-            b1 = min(b0 + MAX_RECON_BATCH, n)
-            ops.recon_batch(mlp, self.feats_hwc[b0:b1], self.calib[b0:b1], Z_SCALE, self.b_min,
-                            self.b_max, self.res, self.balance, volumes=self.volumes[b0:b1],
-                            status=self.status[b0:b1], final_level=self.final_level)
+        self._octree(mlp, n)
         pts_all = []
         # forward_vertices and the normal renders of all frames of the slot: one set of launches each
         # (mp_forward_vertices_batch, mp_paint_batch), results identical to the per-frame calls
@@ -361,8 +378,8 @@ class FrameSlot:
         # prepare_inputs, an H2D copy from pinned memory): order the slot's copies behind that work
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(self.stream):
-            self._load(self.image, images)
-            self._load(self.calib, calibs)
+            self._load(self.image_in, images)
+            self._load(self.calib_in, calibs)
             if self.netC is not None:
                 self._load(self.image_c, images if images_c is None else images_c)
             self._chain()
@@ -405,11 +422,57 @@ class FrameSlot:
         ops.stream_release(self.stream)
 
 
-class FramePipeline:
-    """Round-robin over ``depth`` FrameSlots of ``batch`` frames each."""
+class ViewsSlot(FrameSlot):
+    """A FrameSlot for a MULTI-VIEW netG (SurfaceClassifier num_views = V > 1, multi-view PIFu): static buffers for
+    ``batch`` in-flight frames of V views each.  ``submit(images [n,V,3,512,512], calibs [n,V,4,4])``; ONE encoder
+    pass over the slot's batch * V images (``use_graph`` and the direct channels-last output as in FrameSlot), then the
+    octree of all frames level by level through ``ops.recon_views_batch`` (mp_recon_views_batch: one launch of the
+    multi-view kernel per level covers every frame of a chunk of ``ops.max_view_frames(V)``), then FrameSlot's
+    per-volume stages unchanged: forward_vertices / paint renders and, with ``mesh={...}``, the mesh chain.
 
-    def __init__(self, netG, device, depth=2, batch=1, **slot_kwargs):
-        self.slots = [FrameSlot(netG, device, batch=batch, **slot_kwargs) for _ in range(depth)]
+    ``view`` (0..V-1): the row of the [V,1,N] result the volumes hold -- the view-averaged prediction times that
+    view's in-image mask (Seg3dLossless(fuse_views=True, view=...)); ``projection``: the one mode of all cameras.
+    No skip tables (the multi-view kernel does not read them).  Not built, NotImplementedError at construction:
+    ``netC`` (a multi-view colour query over the device-counted vertex lists) and hence ``mesh`` colours."""
+
+    def __init__(self, netG, device, *args, view=0, projection="orthogonal", **kwargs):
+        self.view = int(view)
+        self.projection = ops._projection(projection)
+        super().__init__(netG, device, *args, **kwargs)
+
+    def _head_views(self, netG, netC, mesh):
+        v_n = netG.surface_classifier.num_views
+        if v_n < 2:
+            raise ValueError("ViewsSlot: netG has a single-view head; use FrameSlot")
+        if not 0 <= self.view < v_n:
+            raise ValueError("ViewsSlot(view=%d): the head has %d views (rows 0..%d)" % (self.view, v_n, v_n - 1))
+        if netC is not None:
+            raise NotImplementedError("ViewsSlot: netC (multi-view colours over device-counted vertex lists) is not built")
+        colors = None if mesh is None else (mesh.get("colors") if isinstance(mesh, dict) else getattr(mesh, "colors", None))
+        if colors:
+            raise NotImplementedError("ViewsSlot(mesh=...): colours need netC, which the slot does not run")
+        return v_n
+
+    def _per_frame(self, buf):
+        return buf.view(self.batch, self.views, *buf.shape[1:])
+
+    def _octree(self, mlp, n):
+        v_n = self.views
+        step = ops.max_view_frames(v_n)
+        maps = [self.feats_hwc[b * v_n:(b + 1) * v_n] for b in range(n)]
+        for b0 in range(0, n, step):
+            b1 = min(b0 + step, n)
+            ops.recon_views_batch(mlp, maps[b0:b1], self.calib_in[b0:b1], self.projection, Z_SCALE, self.b_min,
+                                  self.b_max, self.res, self.balance, final_level=self.final_level, view=self.view,
+                                  volumes=self.volumes[b0:b1], status=self.status[b0:b1])
+
+
+class FramePipeline:
+    """Round-robin over ``depth`` slots (``slot_class``: FrameSlot, or ViewsSlot for a multi-view netG) of ``batch``
+    frames each."""
+
+    def __init__(self, netG, device, depth=2, batch=1, slot_class=FrameSlot, **slot_kwargs):
+        self.slots = [slot_class(netG, device, batch=batch, **slot_kwargs) for _ in range(depth)]
         self.batch = int(batch)
         self.n_submitted = 0
 
