@@ -664,8 +664,9 @@ int mp_mesh_smooth_batch(mp_ctx *ctx, int n_frames, const float *const *verts, i
  *     the FIRST image index, as in mp_paint's canvas image[X, Y, :], so the result feeds mp_visualize unchanged, and
  *     with the identity camera and H = W = R pixel i is lattice column i.  A vertex is invalid if u, v or z is not
  *     finite or |u| or |v| exceeds 2^22; a face with an invalid vertex, or with an index outside [0, vertices), is
- *     skipped whole.  There is NO clipping (a face with a vertex behind a perspective camera is drawn from its
- *     projected vertices as they are) and NO back-face culling.
+ *     skipped whole.  There is NO clipping in this call (a face with a vertex behind a perspective camera is drawn
+ *     from its projected vertices as they are; mp_mesh_render_clip below clips at a near plane) and NO back-face
+ *     culling.
  *   3 Cover, in int64: area2 = (X1-X0)(Y2-Y0) - (Y1-Y0)(X2-X0).  Zero: the face is skipped.  Negative: the second and
  *     third vertex are exchanged with everything attached to them, and area2 negated.  At a pixel centre P,
  *     e0 = edge(V1,V2,P), e1 = edge(V2,V0,P), e2 = edge(V0,V1,P) with edge(A,B,P) = (Bx-Ax)(Py-Ay) - (By-Ay)(Px-Ax).
@@ -707,6 +708,54 @@ int mp_mesh_render_batch(mp_ctx *ctx, int n_frames, const float *const *verts, i
                          int projection, int nearest, int h, int w, float scale, float bias, float lo, float hi,
                          float background, float *const *image, float *const *depth, int32_t *const *face_id,
                          mp_stream stream);
+/* mp_mesh_render for a free PERSPECTIVE camera: faces are clipped at the plane zc = near, and with
+ * MP_RENDER_PERSPECTIVE_CORRECT depth and attributes are interpolated perspective-correctly.  MP_PROJ_PERSPECTIVE
+ * only; near > 0 and finite.  Stateless: no clipped geometry is stored; the face pass clips each face in registers and
+ * the resolve re-derives the same sub-triangles from the winning face index.  It extends steps 1-5 above as follows;
+ * every operation is one f32 IEEE operation, in the order written, without FMA.
+ *   Camera space.  (xc, yc, zc) of a vertex are the three rows of [R|t] p before the divide: the bits mp_orthogonal
+ *     returns for that calib.  A vertex is INSIDE iff zc >= near (a NaN is not inside; zc == near is).  A face with an
+ *     index out of range or a non-finite camera coordinate is skipped whole.  An inside vertex takes steps 1-2 as
+ *     above (x = xc / zc, y = yc / zc, z = zc); a face with an invalid inside vertex is skipped whole.
+ *   cut(I, O), always from the inside vertex I to the outside vertex O of an edge: t = (near - zI) / (zO - zI);
+ *     xc = xI + t * (xO - xI), yc likewise, zc = near exactly; then x = xc / near, y = yc / near and the snap of step 2
+ *     with its guard; a cut vertex that fails the guard skips the face whole.  Inside / outside is a property of the
+ *     vertex, so two faces sharing an edge compute the same bits for its cut: the cut leaves no crack.
+ *   Faces by their number of inside vertices.  3: steps 2-5 on the snapped vertices, unchanged.  0: skipped.
+ *     1: rotated cyclically so that the inside vertex comes first, (A, B, C): ONE triangle (A, P, Q), P = cut(A, B),
+ *     Q = cut(A, C).  2: rotated cyclically so that the outside vertex comes last, (A, B, C): P = cut(B, C),
+ *     Q = cut(A, C), sub-triangle 0 = (A, B, P), sub-triangle 1 = (A, P, Q).
+ *   Cover (step 3) per sub-triangle, unchanged: area2 (zero: that sub-triangle is skipped), the exchange of its second
+ *     and third vertex, the top-left rule.  The two sub-triangles share the diagonal A-P with identical snapped ends.
+ *   Interpolate (step 4) with the sub-triangle's own area2 and e_k, w_k = (float)e_k / (float)area2; z of a cut vertex
+ *     is near.  Without the flag: depth = (w0*z0 + w1*z1) + w2*z2 and attributes likewise, as above.  With
+ *     MP_RENDER_PERSPECTIVE_CORRECT (for every face, cut or not): q_k = w_k / z_k, s = (q0 + q1) + q2,
+ *     depth = 1.0f / s, an attribute is ((q0*a0 + q1*a1) + q2*a2) / s, then clamp(a * scale + bias, lo, hi).  Every
+ *     z_k >= near > 0.  A fragment with a non-finite depth is dropped.  The attribute of a cut vertex is
+ *     aI + t * (aO - aI) per channel.
+ *   Resolve (step 5).  The key holds the ORIGINAL face index: the tie-break and face_id are those of the unclipped
+ *     call.  The outputs are those of the lowest-numbered sub-triangle of the winning face that covers the centre.
+ *   So for a mesh wholly in front of the plane and flags == 0 the result is mp_mesh_render's BIT FOR BIT.
+ * NOT built: clipping against the side planes (a clipped face that still exceeds the 2^22 snap guard is skipped
+ * whole), a far plane, back-face culling, clipping for orthogonal cameras.
+ *   Launches and scratch as mp_mesh_render, + 16 max_verts bytes per image (the camera-space vertices); a face goes to
+ *   the list of large faces, at most once, when any of its sub-triangles has a box of more than 64 centres.
+ * MP_ERR_ARG: near not finite or <= 0, unknown flag bits, a projection other than MP_PROJ_PERSPECTIVE, and everything
+ * mp_mesh_render refuses; a refused call launches nothing.  The batched call with one frame and one view. */
+enum { MP_RENDER_PERSPECTIVE_CORRECT = 1 };
+int mp_mesh_render_clip(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                        const int32_t *counts, const float *attr, int channel_major, const float *calib /*host[12]*/,
+                        int projection, int nearest, int h, int w, float scale, float bias, float lo, float hi,
+                        float background, float *image, float *depth, int32_t *face_id, float near, int flags,
+                        mp_stream stream);
+/* mp_mesh_render_batch's arguments and contract with the clipped definition: image (f, v) equals mp_mesh_render_clip
+ * on frame f's mesh with camera (f, v) BIT FOR BIT; one near and one flags for all. */
+int mp_mesh_render_clip_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                              const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts,
+                              const float *const *attr, int channel_major, int n_views, const float *calibs,
+                              int projection, int nearest, int h, int w, float scale, float bias, float lo, float hi,
+                              float background, float *const *image, float *const *depth, int32_t *const *face_id,
+                              float near, int flags, mp_stream stream);
 
 /* The largest connected body of an occupancy volume [R,R,R] (no counterpart in the reference; the clean-up in front
  * of marching cubes that drops floating blobs).

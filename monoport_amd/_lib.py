@@ -92,6 +92,8 @@ PROJ_ORTHOGONAL, PROJ_PERSPECTIVE = 0, 1
 NORMALS_REFERENCE, NORMALS_ACCUMULATE = 0, 1
 # MP_NEAREST_* modes of mp_mesh_render (include/monoport_hip.h)
 NEAREST_MAX_Z, NEAREST_MIN_Z = 0, 1
+# MP_RENDER_* flags of mp_mesh_render_clip (include/monoport_hip.h)
+RENDER_PERSPECTIVE_CORRECT = 1
 # MP_CONN_* connectivities of mp_volume_keep_largest (include/monoport_hip.h)
 CONN_6, CONN_26 = 6, 26
 MAX_VIEWS = 8  # MP_MAX_VIEWS: views per mp_query_views / mp_mlp_forward_views call
@@ -193,6 +195,11 @@ SIGNATURES = {
                                c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "mp_mesh_render_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_int, _pf32, c_int, c_int,
                                      c_int, c_int, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    "mp_mesh_render_clip": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, _pf32, c_int, c_int, c_int, c_int,
+                                    c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_f32, c_int, c_vp]),
+    "mp_mesh_render_clip_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_int, _pf32, c_int,
+                                          c_int, c_int, c_int, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_f32,
+                                          c_int, c_vp]),
     "mp_volume_keep_largest": (c_int, [c_vp, c_vp, c_int, c_f32, c_int, c_f32, c_vp, c_vp, c_vp]),
     "mp_volume_keep_largest_batch": (c_int, [c_vp, c_int, c_vp, c_int, c_f32, c_int, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "mp_group_norm": (c_int, [c_vp, c_vp, c_int, c_int, c_i64, c_int, c_vp, c_vp, c_f32, c_int, c_vp,

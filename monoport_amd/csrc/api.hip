@@ -539,7 +539,7 @@ static int mesh_render_checked(mp_ctx *ctx, const char *who, int n_frames, const
                                const float *const *attr, int channel_major, int n_views, const float *calibs,
                                int projection, int nearest, int h, int w, float scale, float bias, float lo, float hi,
                                float background, float *const *image, float *const *depth, int32_t *const *face_id,
-                               mp_stream stream) {
+                               const MeshRenderClip *clip, mp_stream stream) {
   if (!ctx) return MP_ERR_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (n_frames < 1 || n_views < 1 || (long long)n_frames * n_views > kMaxFrames)
@@ -551,6 +551,15 @@ static int mesh_render_checked(mp_ctx *ctx, const char *who, int n_frames, const
     return fail(ctx, MP_ERR_ARG, "%s: unknown projection mode %d", who, projection);
   if (nearest != MP_NEAREST_MAX_Z && nearest != MP_NEAREST_MIN_Z)
     return fail(ctx, MP_ERR_ARG, "%s: nearest must be MP_NEAREST_MAX_Z / _MIN_Z, got %d", who, nearest);
+  if (clip) {
+    if (projection != MP_PROJ_PERSPECTIVE)
+      return fail(ctx, MP_ERR_ARG, "%s: the near plane clips perspective cameras only (MP_PROJ_PERSPECTIVE)", who);
+    if (!std::isfinite(clip->near) || !(clip->near > 0.0f))
+      return fail(ctx, MP_ERR_ARG, "%s: near must be finite and > 0, got %g", who, (double)clip->near);
+    if (clip->flags & ~MP_RENDER_PERSPECTIVE_CORRECT)
+      return fail(ctx, MP_ERR_ARG, "%s: unknown flag bits 0x%x (MP_RENDER_PERSPECTIVE_CORRECT)", who,
+                  (unsigned)(clip->flags & ~MP_RENDER_PERSPECTIVE_CORRECT));
+  }
   if (!image && !depth && !face_id) return fail(ctx, MP_ERR_ARG, "%s: no output requested", who);
   if (image && !attr) return fail(ctx, MP_ERR_ARG, "%s: an image needs attr", who);
   if (!counts || !calibs || max_verts < 0 || max_faces < 0 || (max_verts > 0 && !verts) || (max_faces > 0 && !faces))
@@ -565,11 +574,12 @@ static int mesh_render_checked(mp_ctx *ctx, const char *who, int n_frames, const
   DeviceGuard g(ctx->device);
   void *scratch = nullptr;
   rc = ensure_scratch(ctx, (hipStream_t)stream,
-                      mesh_render_scratch_bytes(n_frames * n_views, max_verts, max_faces, h, w), &scratch);
+                      mesh_render_scratch_bytes(n_frames * n_views, max_verts, max_faces, h, w, clip != nullptr),
+                      &scratch);
   if (rc != MP_OK) return rc;
   return launch_mesh_render_batch(ctx, scratch, n_frames, n_views, verts, max_verts, faces, max_faces, counts, attr,
                                   channel_major, calibs, projection, nearest, h, w, scale, bias, lo, hi, background,
-                                  image, depth, face_id, (hipStream_t)stream);
+                                  image, depth, face_id, clip, (hipStream_t)stream);
 }
 
 static int keep_largest_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *volume, int r,
@@ -1475,7 +1485,7 @@ int mp_mesh_render(mp_ctx *ctx, const float *verts, int64_t max_verts, const int
   return mesh_render_checked(ctx, "mp_mesh_render", 1, &verts, max_verts, &faces, max_faces, &counts,
                              attr ? &attr : nullptr, channel_major, 1, calib, projection, nearest, h, w, scale, bias, lo,
                              hi, background, image ? &image : nullptr, depth ? &depth : nullptr,
-                             face_id ? &face_id : nullptr, stream);
+                             face_id ? &face_id : nullptr, nullptr, stream);
 }
 
 int mp_mesh_render_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
@@ -1486,7 +1496,31 @@ int mp_mesh_render_batch(mp_ctx *ctx, int n_frames, const float *const *verts, i
                          mp_stream stream) {
   return mesh_render_checked(ctx, "mp_mesh_render_batch", n_frames, verts, max_verts, faces, max_faces, counts, attr,
                              channel_major, n_views, calibs, projection, nearest, h, w, scale, bias, lo, hi, background,
-                             image, depth, face_id, stream);
+                             image, depth, face_id, nullptr, stream);
+}
+
+int mp_mesh_render_clip(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                        const int32_t *counts, const float *attr, int channel_major, const float *calib,
+                        int projection, int nearest, int h, int w, float scale, float bias, float lo, float hi,
+                        float background, float *image, float *depth, int32_t *face_id, float near, int flags,
+                        mp_stream stream) {
+  const MeshRenderClip clip = {near, flags};
+  return mesh_render_checked(ctx, "mp_mesh_render_clip", 1, &verts, max_verts, &faces, max_faces, &counts,
+                             attr ? &attr : nullptr, channel_major, 1, calib, projection, nearest, h, w, scale, bias, lo,
+                             hi, background, image ? &image : nullptr, depth ? &depth : nullptr,
+                             face_id ? &face_id : nullptr, &clip, stream);
+}
+
+int mp_mesh_render_clip_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                              const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts,
+                              const float *const *attr, int channel_major, int n_views, const float *calibs,
+                              int projection, int nearest, int h, int w, float scale, float bias, float lo, float hi,
+                              float background, float *const *image, float *const *depth, int32_t *const *face_id,
+                              float near, int flags, mp_stream stream) {
+  const MeshRenderClip clip = {near, flags};
+  return mesh_render_checked(ctx, "mp_mesh_render_clip_batch", n_frames, verts, max_verts, faces, max_faces, counts,
+                             attr, channel_major, n_views, calibs, projection, nearest, h, w, scale, bias, lo, hi,
+                             background, image, depth, face_id, &clip, stream);
 }
 
 int mp_mesh_normals_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,

@@ -419,14 +419,19 @@ int launch_mesh_smooth_batch(mp_ctx *ctx, void *scratch, int n_frames, const flo
                              int32_t *const *ring, hipStream_t st);
 // raster.hip: n_frames meshes x n_views cameras (calibs: host, 12 floats per image, frame-major); attr / image / depth /
 // face_id: nullptr or n_frames entries, each frame's views back to back; scratch: mesh_render_scratch_bytes(n_frames *
-// n_views, ...)
-size_t mesh_render_scratch_bytes(int n_images, long long max_v, long long max_f, int h, int w);
+// n_views, ..., clip != nullptr).  clip: nullptr = mp_mesh_render_batch; else the near plane and MP_RENDER_* flags of
+// mp_mesh_render_clip_batch (perspective cameras only: the caller has checked that)
+struct MeshRenderClip {
+  float near;
+  int flags;
+};
+size_t mesh_render_scratch_bytes(int n_images, long long max_v, long long max_f, int h, int w, bool clip);
 int launch_mesh_render_batch(mp_ctx *ctx, void *scratch, int n_frames, int n_views, const float *const *verts,
                              long long max_v, const int32_t *const *faces, long long max_f,
                              const int32_t *const *counts, const float *const *attr, int ch_major, const float *calibs,
                              int proj, int nearest, int h, int w, float scale, float bias, float lo, float hi,
                              float background, float *const *image, float *const *depth, int32_t *const *face_id,
-                             hipStream_t st);
+                             const MeshRenderClip *clip, hipStream_t st);
 
 // conv3x3.hip
 int launch_conv3x3_pack(mp_ctx *ctx, const float *w, int cout, int cin, float *wp, hipStream_t st);

@@ -1482,11 +1482,29 @@ def _view_calibs(who, calibs):
     return np.ascontiguousarray(c[:, :3, :]).reshape(c.shape[0], 12)
 
 
+def _render_clip(who, projection, near, perspective_correct):
+    """The (near, flags) of mp_mesh_render_clip, or None for the unclipped call (``near`` None)."""
+    if near is None:
+        if perspective_correct:
+            raise ValueError("%s: perspective_correct needs near (the clipped call interpolates)" % who)
+        return None
+    if _projection(projection) != PROJECTIONS["perspective"]:
+        raise ValueError("%s: near clips perspective cameras only, not projection=%r" % (who, projection))
+    near = float(near)
+    if not (math.isfinite(near) and near > 0):
+        raise ValueError("%s: near must be finite and > 0, got %r" % (who, near))
+    return near, (_lib.RENDER_PERSPECTIVE_CORRECT if perspective_correct else 0)
+
+
 def _mesh_render(who, verts, faces, counts, attrs, calibs, res, projection, nearest, channel_major, scale, bias, lo, hi,
-                 background, out, capacity=None):
+                 background, out, capacity=None, near=None, perspective_correct=False):
     """What mesh_render_raw and mesh_render_raw_batch do: per mesh (image [n_views,H,W,3] or None, depth
     [n_views,H,W], face [n_views,H,W]), rows of three tensors.  ``capacity`` = (max_v, max_f): the meshes' tensors may
-    then be shorter than it (each at least as long as its own counts say; row-major attributes only)."""
+    then be shorter than it (each at least as long as its own counts say; row-major attributes only).  ``near``: None
+    = mp_mesh_render_batch, else mp_mesh_render_clip_batch."""
+    clip = None  # the unclipped call pays nothing for the keywords
+    if near is not None or perspective_correct:
+        clip = _render_clip(who, projection, near, perspective_correct)
     n = len(verts)
     if capacity is None:
         n, max_v, max_f, dev = _mesh_frames(who, verts, faces, counts)
@@ -1499,7 +1517,7 @@ def _mesh_render(who, verts, faces, counts, attrs, calibs, res, projection, near
         if channel_major or any(v.device != dev for v in verts):
             raise ValueError("%s: meshes of unequal capacity take row-major attributes on one device" % who)
     h, w = _render_size(who, res)
-    proj, near = _projection(projection), _nearest(nearest)
+    proj, near_mode = _projection(projection), _nearest(nearest)
     cams = [_view_calibs(who, c) for c in _calib_list(calibs, n, who)]
     nv = cams[0].shape[0]
     if any(c.shape[0] != nv for c in cams):
@@ -1547,17 +1565,22 @@ def _mesh_render(who, verts, faces, counts, attrs, calibs, res, projection, near
         for f0 in range(0, n, fstep):
             f1 = min(f0 + fstep, n)
             cal = np.ascontiguousarray(cams[f0:f1, v0:v1]).reshape(-1)
-            ctx.check(ctx.lib.mp_mesh_render_batch(
-                ctx.handle, f1 - f0, ptrs(verts, f0, f1), max_v, ptrs(faces, f0, f1), max_f, ptrs(counts, f0, f1),
-                ptrs(attrs, f0, f1), int(channel_major), v1 - v0, cal.ctypes.data_as(_lib._pf32), proj, near, h, w,
-                float(scale), float(bias), float(lo), float(hi), float(background), ptrs(image, f0, f1, v0),
-                ptrs(depth, f0, f1, v0), ptrs(face, f0, f1, v0), _stream(verts[0])), "mp_mesh_render_batch")
+            args = (ctx.handle, f1 - f0, ptrs(verts, f0, f1), max_v, ptrs(faces, f0, f1), max_f, ptrs(counts, f0, f1),
+                    ptrs(attrs, f0, f1), int(channel_major), v1 - v0, cal.ctypes.data_as(_lib._pf32), proj, near_mode,
+                    h, w, float(scale), float(bias), float(lo), float(hi), float(background),
+                    ptrs(image, f0, f1, v0), ptrs(depth, f0, f1, v0), ptrs(face, f0, f1, v0))
+            if clip is None:
+                ctx.check(ctx.lib.mp_mesh_render_batch(*args, _stream(verts[0])), "mp_mesh_render_batch")
+            else:
+                ctx.check(ctx.lib.mp_mesh_render_clip_batch(*args, clip[0], clip[1], _stream(verts[0])),
+                          "mp_mesh_render_clip_batch")
     return [(None if image is None else image[f], None if depth is None else depth[f],
              None if face is None else face[f]) for f in range(n)]
 
 
 def mesh_render_raw(verts, faces, counts, attr, calibs, res, projection="orthogonal", nearest="max",
-                    channel_major=False, scale=1.0, bias=0.0, lo=-math.inf, hi=math.inf, background=1.0, out=None):
+                    channel_major=False, scale=1.0, bias=0.0, lo=-math.inf, hi=math.inf, background=1.0, out=None,
+                    near=None, perspective_correct=False):
     """mp_mesh_render_batch with one mesh: the z-buffered picture of verts [max_v,3] f32, faces [max_f,3] int32, counts
     int32[2] on device (as ``marching_cubes_raw`` returns them) under every camera of ``calibs`` ([4,4], [3,4] or
     [n_views, ...], read on the host) at ``res`` (an int or (H, W)), defined bit for bit in include/monoport_hip.h.
@@ -1565,22 +1588,29 @@ def mesh_render_raw(verts, faces, counts, attr, calibs, res, projection="orthogo
     lo, hi).  ``nearest``: "max" (the viewer sits at +z, what ``forward_vertices("front")`` sees) or "min" (depth is a
     distance).  Returns (image [n_views,H,W,3] or None without ``attr``, depth [n_views,H,W], face int32
     [n_views,H,W]); uncovered pixels hold ``background``, +0.0 and -1.  ``out``: (image, depth, face) buffers to write
-    into; an entry None is an output not computed.  No clipping, no back-face culling, screen-space interpolation.
-    No host sync."""
+    into; an entry None is an output not computed.  ``near`` None (the default): no clipping, screen-space
+    interpolation (mp_mesh_render_batch).  ``near`` > 0 (``projection="perspective"`` only): mp_mesh_render_clip_batch
+    -- faces are clipped at the plane zc = near, and with ``perspective_correct`` depth and attributes are interpolated
+    perspective-correctly; on a mesh wholly in front of the plane, without ``perspective_correct``, the same bits as
+    the unclipped call.  No side or far planes, no back-face culling.  No host sync."""
     return _mesh_render("mesh_render_raw", [verts], [faces], [counts], None if attr is None else [attr], [calibs], res,
                         projection, nearest, channel_major, scale, bias, lo, hi, background,
-                        None if out is None else tuple(None if o is None else [o] for o in out))[0]
+                        None if out is None else tuple(None if o is None else [o] for o in out), near=near,
+                        perspective_correct=perspective_correct)[0]
 
 
 def mesh_render_raw_batch(verts, faces, counts, attrs, calibs, res, projection="orthogonal", nearest="max",
-                          channel_major=False, scale=1.0, bias=0.0, lo=-math.inf, hi=math.inf, background=1.0, out=None):
+                          channel_major=False, scale=1.0, bias=0.0, lo=-math.inf, hi=math.inf, background=1.0, out=None,
+                          near=None, perspective_correct=False):
     """mp_mesh_render_batch: ``[mesh_render_raw(v, f, c, a, cal, res, ...) for ...]`` (lists of per-mesh device tensors
     of one capacity, ``attrs`` None or a list, ``calibs`` one camera set per mesh, all of one n_views) in ONE set of
     launches per MAX_FRAMES images (meshes x views); bit for bit what the per-mesh call gives.  A mesh whose counts
     read 0 gives pure background.  ``out``: (image [n,n_views,H,W,3], depth [n,n_views,H,W], face [n,n_views,H,W])
-    to write into, entries None = not computed.  No host sync."""
+    to write into, entries None = not computed.  ``near`` / ``perspective_correct`` as in ``mesh_render_raw``
+    (mp_mesh_render_clip_batch).  No host sync."""
     return _mesh_render("mesh_render_raw_batch", verts, faces, counts, attrs, calibs, res, projection, nearest,
-                        channel_major, scale, bias, lo, hi, background, out)
+                        channel_major, scale, bias, lo, hi, background, out, near=near,
+                        perspective_correct=perspective_correct)
 
 
 # MP_CONN_* (include/monoport_hip.h): face neighbours / face, edge and corner neighbours

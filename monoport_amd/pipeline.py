@@ -23,6 +23,8 @@ that host-side launch latency and GPU fill, not thread parallelism, are what mat
   encoder pass over batch x V images, the octree of all frames through ``mp_recon_views_batch``, then the same
   per-volume stages (``FramePipeline(..., slot_class=ViewsSlot)``).
 """
+import collections
+
 import numpy as np
 import torch
 
@@ -49,6 +51,10 @@ MAX_RECON_BATCH = ops.MAX_FRAMES  # kMaxFrames of the C-ABI (include/monoport_hi
 _mb = os.environ.get("MONOPORT_MESH_BATCH", "on")
 MESH_BATCH = 1 if _mb == "off" else min(int(_mb) if _mb.isdigit() and int(_mb) > 0 else MAX_RECON_BATCH, MAX_RECON_BATCH)
 MESH_KEYS = ("normals", "level", "colors", "clean", "simplify", "smooth")
+PICTURE_KEYS = ("views", "res", "shade", "projection", "nearest", "near", "perspective_correct", "background")
+PictureOptions = collections.namedtuple("PictureOptions", PICTURE_KEYS)
+PictureOptions.__doc__ = """What a slot's free-viewpoint pictures are asked for, validated by ``_picture_options``: the
+cameras per frame, the size (H, W), and the arguments of ``recon.render_mesh``."""
 
 
 def _mesh_options(mesh, balance, has_netc):
@@ -70,13 +76,45 @@ def _mesh_options(mesh, balance, has_netc):
     return opts
 
 
+def _picture_options(pictures, mesh):
+    """FrameSlot's ``pictures`` argument (a dict) -> PictureOptions; ``mesh``: the slot's validated MeshOptions or None.
+    Nothing is allocated here."""
+    who = "FrameSlot(pictures=...)"
+    if not isinstance(pictures, dict):
+        raise ValueError("%s: a dict with any of %s, got %r" % (who, list(PICTURE_KEYS), pictures))
+    unknown = sorted(set(pictures) - set(PICTURE_KEYS))
+    if unknown:
+        raise ValueError("%s: unknown keys %s (known: %s)" % (who, unknown, list(PICTURE_KEYS)))
+    if mesh is None:
+        raise ValueError("%s: the pictures are of the slot's meshes; it needs mesh=..." % who)
+    from .recon import SHADES
+    views = pictures.get("views", 1)
+    if isinstance(views, bool) or not isinstance(views, (int, np.integer)) or views < 1:
+        raise ValueError("%s: views must be an int >= 1, got %r" % (who, views))
+    res = ops._render_size(who, pictures.get("res", 257))
+    default = "colors" if mesh.colors else ("normals" if mesh.normals is not None else None)
+    shade = pictures.get("shade", default)
+    if shade not in SHADES:
+        raise ValueError("%s: shade must be one of %s, got %r" % (who, list(SHADES), shade))
+    if shade == "normals" and mesh.normals is None:
+        raise ValueError("%s: shade='normals', but the mesh options have normals=None" % who)
+    if shade == "colors" and not mesh.colors:
+        raise ValueError("%s: shade='colors' needs the mesh's colours (mesh colors, hence netC)" % who)
+    projection, nearest = pictures.get("projection", "orthogonal"), pictures.get("nearest", "max")
+    ops._projection(projection), ops._nearest(nearest)
+    near, correct = pictures.get("near"), bool(pictures.get("perspective_correct", False))
+    ops._render_clip(who, projection, near, correct)
+    return PictureOptions(int(views), res, shade, projection, nearest, None if near is None else float(near), correct,
+                          float(pictures.get("background", 1.0)))
+
+
 class FrameSlot:
     """Static buffers for ``batch`` in-flight frames (geometry chain of RTL/main.py:366-428, plus
     the netC texture stages :373-441 when ``netC`` is given)."""
 
     def __init__(self, netG, device, resolutions=RESOLUTIONS, b_min=(-1, -1, -1), b_max=(1, 1, 1),
                  balance=0.5, feature_hook=None, use_graph=False, netC=None, batch=1, skip_table=None,
-                 final_level="dilate3", mesh=None):
+                 final_level="dilate3", mesh=None, pictures=None):
         """``mesh``: None (no mesh output; nothing is allocated or enqueued for it), or a dict / options object with
         ``normals`` ("accumulate" -- the default --, "reference" or None), ``level`` (the iso-level; default: the
         slot's ``balance``) and ``colors`` (per-vertex netC colours; default: ``netC is not None``) and ``clean`` (None
@@ -93,8 +131,20 @@ class FrameSlot:
         is the validated ``recon.MeshOptions`` of all six (None without mesh output).  The slot then
         owns static per-frame mesh buffers at the capacities of ``ops.marching_cubes_raw`` (12 r^2 vertices and
         24 r^2 faces: vertices, faces, normals, query points and predictions are about 57 MB per frame at 257^3), the
-        batched mesh chain runs behind the octree on the slot's stream, and ``meshes()`` hands the results out."""
+        batched mesh chain runs behind the octree on the slot's stream, and ``meshes()`` hands the results out.
+
+        ``pictures``: None (no free-viewpoint pictures; nothing is allocated or enqueued for them), or a dict with any
+        of ``views`` (cameras per frame, default 1), ``res`` (int or (H, W), default 257), ``shade`` ("normals",
+        "colors" or None; default: what the mesh options provide, colours first) and ``projection``, ``nearest``,
+        ``near``, ``perspective_correct``, ``background`` as ``recon.render_mesh`` takes them.  It needs ``mesh``.
+        ``self.picture_options`` is the validated ``PictureOptions`` (None without pictures).  ``submit`` then takes
+        ``cameras``, the rasteriser (``ops.mesh_render_raw_batch``) runs behind the mesh chain on the slot's stream
+        into the static ``pictures_image`` [batch,views,H,W,3] (None with ``shade=None``), ``pictures_depth`` and
+        ``pictures_face`` [batch,views,H,W], and ``pictures()`` hands the results out."""
         self.views = self._head_views(netG, netC, mesh)  # images per frame; refuses what the slot class does not run
+        # both option records are validated before anything is allocated
+        self.mesh = None if mesh is None else _mesh_options(mesh, float(balance), netC is not None)
+        self.picture_options = None if pictures is None else _picture_options(pictures, self.mesh)
         self.net = netG
         self.netC = netC
         self.device = torch.device(device)
@@ -147,7 +197,6 @@ class FrameSlot:
                                 for _ in range(b)]
             self.mat_color = color_matrix(b_min, b_max, r)
             self.image_c = torch.zeros((b, 3, 512, 512), dtype=torch.float32, device=dev)
-        self.mesh = None if mesh is None else _mesh_options(mesh, self.balance, netC is not None)
         if self.mesh is not None:
             opts = self.mesh
             cap_v = 12 * r * r  # ops.marching_cubes_raw's capacities
@@ -173,6 +222,16 @@ class FrameSlot:
             if opts.smooth is not None:  # the vertices before smoothing stay: the colour query reads them
                 self.mesh_buffers["smooth_verts"] = torch.empty((b, cap_v, 3), dtype=torch.float32, device=dev)
             self._mesh_chains = [None] * b
+            self._reran = []  # frames whose chain ``meshes()`` made again with exact capacities
+        self.pictures_image = self.pictures_depth = self.pictures_face = None
+        if self.picture_options is not None:
+            po = self.picture_options
+            if po.shade is not None:
+                self.pictures_image = torch.empty((b, po.views) + po.res + (3,), dtype=torch.float32, device=dev)
+            self.pictures_depth = torch.empty((b, po.views) + po.res, dtype=torch.float32, device=dev)
+            self.pictures_face = torch.empty((b, po.views) + po.res, dtype=torch.int32, device=dev)
+            # the cameras of the current submission, on the host [batch,views,3,4]; the identity until the first one
+            self._cameras = np.tile(np.eye(4, dtype=np.float32)[:3], (b, po.views, 1, 1))
 
     def _head_views(self, netG, netC, mesh):
         for name, net in (("netG", netG), ("netC", netC)):
@@ -283,6 +342,66 @@ class FrameSlot:
                     self.renders_tex[b] = tex[b - b0]
         if self.mesh is not None:
             self._mesh_chain(n)
+        if self.picture_options is not None:
+            self._render_pictures(n)
+
+    def _render_pictures(self, n):
+        """The pictures of the slot's n frames under their ``views`` cameras each, from the mesh buffers the chain has
+        just filled and its device counts: one set of launches per ops.MAX_FRAMES pictures, no host value in between.
+        A gated-off frame's counts are (0, 0): pure background."""
+        po = self.picture_options
+        chains = self._mesh_chains[:n]
+        attrs, channel_major, paint = None, False, (1.0, 0.0, -np.inf, np.inf)
+        if po.shade == "normals":  # as main.py:220-225 paints them
+            attrs, paint = [c.normals for c in chains], (0.5, 0.5, 0.0, 1.0)
+        elif po.shade == "colors":  # netC's raw predictions [3,cap]; * 0.5 + 0.5 finishes them (recon._finish_mesh)
+            attrs, channel_major, paint = [c.preds for c in chains], True, (0.5, 0.5, -np.inf, np.inf)
+        out = (None if self.pictures_image is None else self.pictures_image[:n], self.pictures_depth[:n],
+               self.pictures_face[:n])
+        ops.mesh_render_raw_batch([c.verts for c in chains], [c.faces for c in chains], [c.counts for c in chains], attrs,
+                                  list(self._cameras[:n]), po.res, po.projection, po.nearest, channel_major, *paint,
+                                  background=po.background, out=out, near=po.near,
+                                  perspective_correct=po.perspective_correct)
+
+    def pictures(self):
+        """The pictures of the current submission, to be called after ``wait()`` (it waits if the caller has not): a
+        list of ``n_active`` entries, a ``recon.MeshRender`` per frame (image [views,H,W,3] or None, depth and face
+        [views,H,W]) or None where ``meshes()`` gives None.  The entries are views of the slot's buffers, valid until
+        the next ``submit``.  It goes through ``meshes()`` (its one device-to-host copy): a frame whose mesh
+        overflowed the slot's capacities is rendered again from the re-run mesh by ``recon.render_mesh``, into fresh
+        tensors: the bits the slot's own launch would have given at a sufficient capacity, except with
+        ``shade="colors"``, where ``render_mesh`` interpolates the Mesh's finished colours and the slot netC's raw
+        predictions (the same picture, not the same last bits).  No slot has overflowed 12 r^2 / 24 r^2 so far."""
+        if self.picture_options is None:
+            raise RuntimeError("FrameSlot.pictures(): the slot was made without pictures=...")
+        from .recon import MeshRender, render_mesh
+        po = self.picture_options
+        out = []
+        for b, mesh in enumerate(self.meshes()):
+            if mesh is None:
+                out.append(None)
+            elif b in self._reran:
+                out.append(render_mesh(mesh, self._cameras[b], po.res, po.shade, po.projection, po.nearest,
+                                       po.background, po.near, po.perspective_correct))
+            else:
+                out.append(MeshRender(None if self.pictures_image is None else self.pictures_image[b],
+                                      self.pictures_depth[b], self.pictures_face[b]))
+        return out
+
+    def _slot_cameras(self, cameras, n):
+        """``submit``'s cameras ([n,views,>=3,4], or [views,>=3,4] / [>=3,4] shared by all frames; tensor or array)
+        -> host float32 [n,views,3,4].  Read on the host, as the rasteriser's calibrations are."""
+        po = self.picture_options
+        c = cameras.detach().cpu().numpy() if torch.is_tensor(cameras) else np.asarray(cameras)
+        c = np.asarray(c, np.float32)
+        if c.ndim == 2:
+            c = c[None]
+        if c.ndim == 3:
+            c = np.broadcast_to(c[None], (n,) + c.shape)
+        if c.ndim != 4 or c.shape[0] != n or c.shape[1] != po.views or c.shape[2] < 3 or c.shape[3] != 4:
+            raise ValueError("submit: cameras must be [%d,%d,4,4] (or [%d,4,4] for all frames), got %s"
+                             % (n, po.views, po.views, tuple(np.shape(cameras))))
+        return np.ascontiguousarray(c[:, :, :3, :])
 
     def _mesh_bindings(self, b0, b1):
         """The colour queries of frames b0..b1 as recon._mesh_chains takes them (netC's head on the slot's own maps and
@@ -326,6 +445,7 @@ class FrameSlot:
         from .recon import _collect_meshes, _mesh_chains
         self.wait()
         n = self.n_active
+        self._reran = []
         # per frame: alive, (vertices, faces) of the mesh [, with ``simplify``: those marching cubes needed]
         cols = [self.status[:n, 0:1], self.mesh_buffers["counts"][:n]]
         if self.mesh.simplify is not None:
@@ -333,6 +453,7 @@ class FrameSlot:
         host = torch.cat(cols, dim=1).cpu().tolist()
 
         def rerun(b, max_verts, max_faces):
+            self._reran.append(b)
             return _mesh_chains([self.volumes[b]], self.b_min, self.b_max, self.mesh, self._mesh_bindings(b, b + 1),
                                 max_verts=max_verts, max_faces=max_faces)[0]
 
@@ -362,9 +483,11 @@ class FrameSlot:
                 self.graph.replay()
             self.stream.synchronize()
 
-    def submit(self, images, calibs, images_c=None):
+    def submit(self, images, calibs, images_c=None, cameras=None):
         """Enqueue the reconstruction of n <= ``batch`` frames: ``images`` [n,3,512,512] (or a list
-        of [1,3,512,512]), ``calibs`` [n,4,4] (or a list of [1,4,4]); returns immediately.  Results
+        of [1,3,512,512]), ``calibs`` [n,4,4] (or a list of [1,4,4]); returns immediately.  ``cameras``: with
+        ``pictures``, the free cameras of the frames' pictures, [n,views,4,4] or [views,4,4] for all frames (read
+        on the host); required then, refused otherwise.  Results
         (``renders``, ``volumes``, ``status``, ``vertices``; entries 0..n-1) are valid after
         ``stream.synchronize()`` and until the next submit on this slot.  A short batch (the tail of
         a stream) still runs the encoder at the slot's batch size -- the graph is captured for it --
@@ -372,8 +495,14 @@ class FrameSlot:
         n = images.shape[0] if torch.is_tensor(images) else len(images)
         if not 1 <= n <= self.batch:
             raise ValueError("slot of %d frames got %d" % (self.batch, n))
+        if (cameras is None) != (self.picture_options is None):
+            raise ValueError("submit: cameras are %s" % ("required by the slot's pictures" if cameras is None else
+                                                         "taken only by a slot made with pictures=..."))
+        host_cameras = None if cameras is None else self._slot_cameras(cameras, n)
         self.wait()  # a slot holds ONE batch: its previous results are overwritten from here on
         self.n_active = n
+        if host_cameras is not None:
+            self._cameras[:n] = host_cameras
         # the caller may have produced the frames asynchronously on ITS stream (segmentation,
         # prepare_inputs, an H2D copy from pinned memory): order the slot's copies behind that work
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
@@ -480,9 +609,9 @@ class FramePipeline:
         for s in self.slots:
             s.prepare()
 
-    def submit(self, images, calibs, images_c=None):
+    def submit(self, images, calibs, images_c=None, cameras=None):
         slot = self.slots[self.n_submitted % len(self.slots)]
-        slot.submit(images, calibs, images_c)
+        slot.submit(images, calibs, images_c, cameras)
         self.n_submitted += 1
         return slot
 

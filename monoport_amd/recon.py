@@ -440,26 +440,34 @@ def _single_camera(calibs):
 
 
 @torch.no_grad()
-def render_mesh(mesh, calibs, res=257, shade="colors", projection="orthogonal", nearest="max", background=1.0):
+def render_mesh(mesh, calibs, res=257, shade="colors", projection="orthogonal", nearest="max", background=1.0,
+                near=None, perspective_correct=False):
     """The z-buffered picture of a ``Mesh`` on the device (monoport_amd extension; ``ops.mesh_render_raw``): any camera
     ``calibs`` ([4,4] / [3,4], the convention of the queries; or [n_views, ...] for several pictures in one set of
     launches), any size ``res`` (int or (H, W)).  ``shade``: "colors" (the mesh's colours), "normals" (its normals * 0.5
     + 0.5 clamped to [0,1], as the reference paints them) or None (depth and face ids only).  x runs along the first
-    image index as in the painted canvas, so a square image feeds ``visulization`` unchanged.  Returns a
-    ``MeshRender``; None for ``mesh is None``.  No host sync."""
+    image index as in the painted canvas, so a square image feeds ``visulization`` unchanged.  ``near`` (> 0, with
+    ``projection="perspective"``): faces are clipped at the plane zc = near, so the camera may stand anywhere, also
+    inside the body; ``perspective_correct`` then interpolates depth and shading perspective-correctly (both as
+    ``ops.mesh_render_raw``; None, the default, is the unclipped call).  Returns a ``MeshRender``; None for ``mesh is
+    None``.  No host sync."""
     if mesh is None:
         return None
-    return render_mesh_many([mesh], calibs, res, shade, projection, nearest, background)[0]
+    return render_mesh_many([mesh], calibs, res, shade, projection, nearest, background, near, perspective_correct)[0]
 
 
 @torch.no_grad()
-def render_mesh_many(meshes, calibs, res=257, shade="colors", projection="orthogonal", nearest="max", background=1.0):
+def render_mesh_many(meshes, calibs, res=257, shade="colors", projection="orthogonal", nearest="max", background=1.0,
+                     near=None, perspective_correct=False):
     """``[render_mesh(m, calibs, ...) for m in meshes]`` in one set of launches per ops.MAX_FRAMES pictures (meshes x
     views), the same bits.  ``calibs``: one camera set for all meshes (a tensor / array), or a list with one camera set
     per mesh (those of ``None`` meshes are not looked at; all of one n_views).  ``None`` meshes give ``None``.  The
     meshes may differ in size: the per-mesh counts are made on the device from the tensors' shapes and the capacity of
-    the call is the largest of them (no row at or beyond a mesh's counts is touched).  No host sync."""
+    the call is the largest of them (no row at or beyond a mesh's counts is touched).  ``near`` / ``perspective_correct``
+    as in ``render_mesh``: one plane for all.  No host sync."""
     who = "render_mesh_many"
+    if near is not None or perspective_correct:  # refused before a list of Nones returns
+        ops._render_clip(who, projection, near, perspective_correct)
     meshes = list(meshes)
     idx = [i for i, m in enumerate(meshes) if m is not None]
     out = [None] * len(meshes)
@@ -480,7 +488,8 @@ def render_mesh_many(meshes, calibs, res=257, shade="colors", projection="orthog
     sizes = _shape_counts(list(zip(verts, faces)))
     capacity = (max(v.shape[0] for v in verts), max(f.shape[0] for f in faces))
     raws = ops._mesh_render(who, verts, faces, list(sizes.unbind(0)), attrs, cams, res, projection, nearest, False,
-                            scale, bias, lo, hi, background, None, capacity=capacity)
+                            scale, bias, lo, hi, background, None, capacity=capacity, near=near,
+                            perspective_correct=perspective_correct)
     for i, cam, (image, depth, face) in zip(idx, cams, raws):
         if _single_camera(cam):
             image, depth, face = (None if t is None else t[0] for t in (image, depth, face))

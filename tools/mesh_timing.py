@@ -11,7 +11,9 @@
 n = 4 and n = 20 meshes, n calls of recon.reconstruct_mesh against ONE recon.reconstruct_mesh_many, with and without
 colours (normals="accumulate" in both), per-mesh milliseconds; and a pipeline.FrameSlot(mesh=...) of 20 frames
 (encoders as a hipGraph, netC, the bench's synthetic frames) with pipeline.MESH_BATCH at 1 / 4 / all frames, alone and
-as three slots submitted back to back, per-frame milliseconds -- next to the same slots without mesh output.
+as three slots submitted back to back, per-frame milliseconds -- next to the same slots without mesh output, and to
+the mesh slot with ``pictures`` (4 clipped, perspective-correct views per frame at 257^2, normals shading;
+``pictures()`` included).
 
     python tools/mesh_timing.py --batched [--passes 5] [--out profiles/mesh_batch_timing.json]
 
@@ -30,6 +32,13 @@ ops.paint, one axis direction at the volume's resolution) and what one more reco
 second view cost before).
 
     python tools/mesh_timing.py --render [--passes 5] [--out profiles/mesh_render_timing.json]
+
+``--render --clip`` adds, in the same passes, the clipped form (profiles/mesh_render_clip_timing.json): the same mesh at
+257^2 under a perspective camera that has the whole body in front of it, through the unclipped call, through
+``near=0.5`` (the same picture, so the difference is the price of the extra setup store and the classification) without
+and with ``perspective_correct``, and with the plane through the body (``near=3.0``); 1 and 20 meshes per call.
+
+    python tools/mesh_timing.py --render --clip [--passes 5] [--out profiles/mesh_render_clip_timing.json]
 
 ``--simplify`` measures the level-of-detail dial (profiles/mesh_simplify_timing.json): on the same volume,
 recon.reconstruct_mesh_many of 20 meshes with and without netC colours, and the 20-frame colour slot of ``--batched``
@@ -84,9 +93,11 @@ def main():
     ap.add_argument("--simplify", action="store_true", help="the mesh chain at simplify = None / 128 / 64")
     ap.add_argument("--smooth", action="store_true", help="the mesh chain at smooth = None / 2 / 10")
     ap.add_argument("--render", action="store_true", help="the mesh rasteriser against the visible-surface picture")
+    ap.add_argument("--clip", action="store_true", help="with --render: the clipped form beside the unclipped call")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "mesh_render_timing.json" if a.render else
+        a.out = os.path.join(ROOT, "profiles", "mesh_render_clip_timing.json" if a.render and a.clip else
+                             "mesh_render_timing.json" if a.render else
                              "mesh_smooth_timing.json" if a.smooth else
                              "mesh_simplify_timing.json" if a.simplify else
                              "keep_largest_timing.json" if a.clean else
@@ -254,6 +265,8 @@ def render(a, vol, reconstruct, n=20):
             per[name + "_frames1"] = per[name + "_frames%d" % n] = n * views
     out = {"resolutions": RES, "passes": a.passes, "unit": "ms per picture", "shade": "normals",
            "vertices": int(mesh.verts.shape[0]), "faces": int(mesh.faces.shape[0]), "pictures_per_pass": per}
+    if a.clip:
+        out["clip"] = clip_ways(mesh, ways, per, n)
     one = recon.render_mesh(mesh, cams[0], res=r, shade="normals")
     x, y, _, _ = recon.forward_vertices(vol, "front")
     seen = torch.zeros((r, r), dtype=torch.bool, device=vol.device)
@@ -274,6 +287,28 @@ def render(a, vol, reconstruct, n=20):
             del res
     out.update({name: stats(t) for name, t in times.items()})
     return out
+
+
+def clip_ways(mesh, ways, per, n):
+    """Adds the perspective rows of ``--clip`` to ``ways`` / ``per``; returns what they draw."""
+    cam = torch.eye(4)
+    cam[0, 0] = cam[1, 1] = 2.5
+    cam[2, 3] = 3.0  # the box [-1, 1]^3 at z = 2 .. 4
+    rows = {"persp": {}, "persp_clip": dict(near=0.5), "persp_clip_correct": dict(near=0.5, perspective_correct=True),
+            "persp_cut": dict(near=3.0), "persp_cut_correct": dict(near=3.0, perspective_correct=True)}
+
+    def one(kw):
+        return recon.render_mesh(mesh, cam, res=257, shade="normals", projection="perspective", nearest="min", **kw)
+
+    for name, kw in rows.items():
+        ways[name + "_257_frames1"] = (lambda kw=kw: [one(kw) for _ in range(n)])
+        ways[name + "_257_frames%d" % n] = (lambda kw=kw: recon.render_mesh_many(
+            [mesh] * n, cam, res=257, shade="normals", projection="perspective", nearest="min", **kw))
+        per[name + "_257_frames1"] = per[name + "_257_frames%d" % n] = n
+    pics = {name: one(kw) for name, kw in rows.items()}
+    return {"camera": "focal 2.5 at z = 3: the body at 2 .. 4", "near_in_front": 0.5, "near_through_the_body": 3.0,
+            "clip_in_front_equals_unclipped": all(torch.equal(x, y) for x, y in zip(pics["persp"], pics["persp_clip"])),
+            "covered_pixels": {name: int((p_.face >= 0).sum().item()) for name, p_ in pics.items()}}
 
 
 def clean(a, vol, netC, feat_C, calib, n=20):
@@ -436,28 +471,41 @@ def slot_mesh_batch(a, frames=20):
     images = torch.stack([torch.from_numpy(syn.synthetic_image(f % 8)) for f in range(frames)]).to(dev)
     calibs = torch.cat([pifu_calib(*syn.scene_camera(3 * f), device=DEV) for f in range(frames)])
     out = {"frames_per_slot": frames, "unit": "ms per frame", "normals": "accumulate", "colors": True}
+    pictures = dict(views=4, res=257, shade="normals", projection="perspective", nearest="min", near=2.5,
+                    perspective_correct=True)
+    cameras = torch.eye(4).repeat(4, 1, 1)
+    cameras[:, 0, 0] = cameras[:, 1, 1] = 2.5
+    cameras[:, 0, 3] = torch.tensor([-0.3, -0.1, 0.1, 0.3])
+    cameras[:, 2, 3] = 3.0  # the box at z = 2 .. 4: the plane at 2.5 cuts the body
+    out["pictures"] = pictures
     for depth in (1, 3):
         pipes = {}
-        for name, mesh in (("mesh", {"normals": "accumulate"}), ("no_mesh", None)):
+        for name, mesh in (("mesh", {"normals": "accumulate"}), ("no_mesh", None), ("pictures", {"normals": "accumulate"})):
             pipes[name] = pipeline.FramePipeline(netg, dev, depth=depth, batch=frames, resolutions=RESOLUTIONS,
                                                  b_min=B_MIN, b_max=B_MAX, feature_hook=hook, use_graph=True,
-                                                 netC=netc, mesh=mesh)
+                                                 netC=netc, mesh=mesh, pictures=pictures if name == "pictures" else None)
             pipes[name].prepare()
 
         def run(name, mesh_batch):
             def fn():
                 pipeline.MESH_BATCH = mesh_batch
-                slots = [pipes[name].submit(images, calibs) for _ in range(depth)]
+                kw = dict(cameras=cameras) if name == "pictures" else {}
+                slots = [pipes[name].submit(images, calibs, **kw) for _ in range(depth)]
                 for s in slots:
-                    if name == "mesh":
+                    if name == "pictures":
+                        assert all(p_ is not None for p_ in s.pictures())
+                    elif name == "mesh":
                         assert all(m is not None for m in s.meshes())
                     else:
                         s.wait()
             return fn
 
         ways = {"mesh_batch_1": run("mesh", 1), "mesh_batch_4": run("mesh", 4), "mesh_batch_all": run("mesh", frames),
-                "no_mesh": run("no_mesh", 4)}
+                "no_mesh": run("no_mesh", 4), "mesh_pictures_batch_all": run("pictures", frames)}
         res = alternate(ways, a.passes, frames * depth)
+        res["pictures_add_ms"] = round(res["mesh_pictures_batch_all"]["median_ms"] - res["mesh_batch_all"]["median_ms"], 4)
+        pic = pipes["pictures"].slots[0].pictures()[0]
+        res["picture_covered_pixels"] = [int((pic.face[v] >= 0).sum().item()) for v in range(4)]
         m = pipes["mesh"].slots[0].meshes()[0]
         res["vertices"], res["faces"] = int(m.verts.shape[0]), int(m.faces.shape[0])
         out["depth%d" % depth] = res
