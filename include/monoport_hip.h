@@ -352,6 +352,25 @@ int mp_recon_views_batch(mp_ctx *ctx, int mlp, int n_frames, int n_views, const 
                          int view, float *const *volume, int32_t *const *status, const mp_recon_early *early,
                          mp_stream stream);
 
+/* mp_query_views over n_frames independent subjects whose point counts live on the device (multi-view netC colours
+ * over the vertex lists forward_vertices / marching cubes counted, without a host round trip): frame f has its own
+ * n_views maps and calibrations (feat_hwc / calib: HOST arrays of n_frames * n_views device pointers, frame-major
+ * [f * n_views + v]) and ONE point set points[f] [3,capacity] (contiguous f32) that all its views see; the frames
+ * share the head, n_views, `view`, the projection mode and `capacity`.  For i < *count[f] (clamped to
+ * [0, capacity] in the kernel; the contract is count <= capacity, as for mp_query_counted), out[f][:, i] of the
+ * [Cout,capacity] output equals row `view` of mp_query_views on frame f's maps and calibrations with the same points
+ * given to every view, bit for bit; everything else of `out` is untouched.  One launch: the tiles of the frames form
+ * one index space and a frame whose count is 0 owns none.  Fully asynchronous, no host sync; registered skip tables
+ * are not used.  n_views outside 1..MP_MAX_VIEWS, a head whose precision is not MP_PREC_F32 or whose (C, Cout) is
+ * outside {256,512} x {1,3} returns MP_ERR_UNSUPPORTED; n_frames outside 1..mp_max_frames(), n_frames * n_views >
+ * MP_MAX_FRAME_VIEWS, `view` outside 0..n_views-1, a bad projection or a null or misaligned buffer returns
+ * MP_ERR_ARG; capacity == 0 returns MP_OK before the frames' buffers are looked at.  A refused call launches nothing
+ * and leaves the context usable. */
+int mp_query_views_counted_batch(mp_ctx *ctx, int mlp, int n_frames, int n_views, const float *const *feat_hwc, int c,
+                                 int h, int w, const float *const *points, int64_t capacity,
+                                 const int32_t *const *count, const float *const *calib, int projection,
+                                 float z_scale, int view, float *const *out, mp_stream stream);
+
 /* The same engine one level at a time, for an arbitrary Python ``query_func`` (the general
  * Seg3dLossless contract, RTL/main.py:169-195): the caller evaluates the selected nodes itself.
  *   mp_octree_select: level 0 (prev == NULL) selects every node; otherwise upsamples prev [rp^3]

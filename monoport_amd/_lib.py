@@ -152,6 +152,8 @@ SIGNATURES = {
     "mp_recon_views_batch": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_int, c_f32, _pf32,
                                      _pf32, _pint, c_int, c_f32, c_int, c_int, c_vp, c_vp,
                                      ctypes.POINTER(ReconEarly), c_vp]),
+    "mp_query_views_counted_batch": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_vp,
+                                             c_vp, c_int, c_f32, c_int, c_vp, c_vp]),
     "mp_concat3_add": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_i64, c_vp, c_vp]),
     "mp_prepare_inputs": (c_int, [c_vp, c_vp, c_i64, _pf32, _pf32, c_vp, c_vp, c_vp]),
     "mp_octree_select": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_f32, c_vp,

@@ -1251,6 +1251,58 @@ int mp_recon_views_batch(mp_ctx *ctx, int mlp, int n_frames, int n_views, const 
                              volume, status, early, stream);
 }
 
+int mp_query_views_counted_batch(mp_ctx *ctx, int mlp, int n_frames, int n_views, const float *const *feat_hwc, int c,
+                                 int h, int w, const float *const *points, int64_t capacity,
+                                 const int32_t *const *count, const float *const *calib, int projection,
+                                 float z_scale, int view, float *const *out, mp_stream stream) {
+  const char *who = "mp_query_views_counted_batch";
+  HeadCall call(ctx, mlp, c);
+  if (call.rc != MP_OK) return call.rc;
+  const Mlp *m = call.m;
+  int rc = check_count(ctx, who, "view", n_views, kMaxViews, MP_ERR_UNSUPPORTED);
+  if (rc == MP_OK) rc = check_f32_views(ctx, who, m);
+  if (rc != MP_OK) return rc;
+  if ((m->c != 256 && m->c != 512) || (m->cout != 1 && m->cout != 3))
+    return fail(ctx, MP_ERR_UNSUPPORTED,
+                "%s: multi-view query kernels are built for C in {256,512}, Cout in {1,3}; got C=%d Cout=%d", who,
+                m->c, m->cout);
+  rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (n_frames * n_views > kMaxFrameViews)
+    return fail(ctx, MP_ERR_ARG, "%s: at most %d frames x views per call, got %d x %d", who, kMaxFrameViews, n_frames,
+                n_views);
+  if (view < 0 || view >= n_views)
+    return fail(ctx, MP_ERR_ARG, "%s: view %d outside 0..%d", who, view, n_views - 1);
+  if (!feat_hwc || !points || !count || !calib || !out || capacity < 0 || h <= 0 || w <= 0)
+    return bad_argument(ctx, who);
+  rc = check_projection(ctx, who, &projection, 1);
+  if (rc != MP_OK || capacity == 0) return rc;  // an empty call returns before its frames' buffers are looked at
+  rc = check_maps(ctx, who, "view", n_frames * n_views, feat_hwc, calib);
+  if (rc == MP_OK) rc = check_frames(ctx, who, n_frames, count, points, out);
+  if (rc != MP_OK) return rc;
+  for (int f = 0; f < n_frames; ++f)
+    if (!count[f]) return fail(ctx, MP_ERR_ARG, "%s: null buffer for frame %d", who, f);
+  for (int i = 0; i < n_frames * n_views; ++i)
+    if ((uintptr_t)calib[i] & 3) return fail(ctx, MP_ERR_ARG, "%s: misaligned buffer for view %d", who, i);
+  ViewPointsBatchDev set = {};
+  set.nv = n_views;
+  set.proj = projection;
+  set.view = view;
+  set.n = n_frames;
+  set.capacity = capacity;
+  for (int f = 0; f < n_frames; ++f) {
+    set.it[f].pts = points[f];
+    set.it[f].out = out[f];
+    set.it[f].n_dev = count[f];
+  }
+  for (int i = 0; i < n_frames * n_views; ++i) {
+    set.feat[i] = feat_hwc[i];
+    set.calib[i] = calib[i];
+  }
+  DeviceGuard g(ctx->device);
+  return launch_query_views_counted_batch(ctx, *m, set, h, w, z_scale, (hipStream_t)stream);
+}
+
 int mp_recon(mp_ctx *ctx, int mlp, const float *feat_hwc, int c, int h, int w, const float *calib,
              float z_scale, const float *b_min, const float *b_max, const int *resolutions,
              int n_levels, float balance, float *volume, int32_t *status, mp_stream stream) {

@@ -190,6 +190,31 @@ struct ViewLatticeBatchDev {
 #endif
 };
 static_assert(sizeof(ViewLatticeBatchDev) + 256 <= 4096, "kernel arguments: the frames + the MLP descriptor must stay below 4 KB");
+// Explicit points of n frames x nv views, counted on the device (mp_query_views_counted_batch): the frames share nv,
+// view, the projection mode and the capacity; per frame: the points [3, capacity] (contiguous, shared by the frame's
+// views), the output [Cout, capacity] (row `view` of the [V,Cout,N] result) and the count *n_dev, which the kernel
+// clamps to [0, capacity]; per (frame, view), frame-major: the map and the calibration.
+// 16 + 8 + 32 * 24 + 2 * 64 * 8 = 1816 B of kernel arguments.
+struct ViewPointsFrameDev {
+  const float *pts;
+  float *out;
+  const int32_t *n_dev;
+};
+struct ViewPointsBatchDev {
+  int nv, proj, view;
+  int n;  // frames
+  long long capacity;
+  ViewPointsFrameDev it[kMaxFrames];
+  const float *feat[kMaxFrameViews];   // [f * nv + v]
+  const float *calib[kMaxFrameViews];
+#ifdef __HIPCC__
+  __device__ __forceinline__ long long count(int f) const {
+    const long long c = (long long)*it[f].n_dev;
+    return c < 0 ? 0 : c > capacity ? capacity : c;
+  }
+#endif
+};
+static_assert(sizeof(ViewPointsBatchDev) + 256 <= 4096, "kernel arguments: the frames + the MLP descriptor must stay below 4 KB");
 // launch_recon's second way to evaluate a level's nodes: feat_hwc / calib are then the views' arrays ([f * nv + v]
 // of the call's frames), proj[0] their one projection.  batch == 0 (mp_recon_views): one frame on the one-frame
 // lattice kernel; batch != 0 (mp_recon_views_batch): 1..kMaxFrames frames, nv * frames <= kMaxFrameViews, every
@@ -306,6 +331,9 @@ int launch_query_views_lattice(mp_ctx *ctx, const Mlp &m, const ViewLatticeDev &
 // one octree level of mp_recon_views_batch: the frames of `set`, at most max_points nodes EACH
 int launch_query_views_lattice_batch(mp_ctx *ctx, const Mlp &m, const ViewLatticeBatchDev &set, int h, int w,
                                      float z_scale, long long max_points, hipStream_t st);
+// mp_query_views_counted_batch: the frames of `set`, at most set.capacity points EACH, counted on the device
+int launch_query_views_counted_batch(mp_ctx *ctx, const Mlp &m, const ViewPointsBatchDev &set, int h, int w,
+                                     float z_scale, hipStream_t st);
 // pack.hip
 int launch_pack_hwc(mp_ctx *ctx, const float *src, int c_src, int h, int w, float *dst, int c_dst,
                     int c_off, hipStream_t st);

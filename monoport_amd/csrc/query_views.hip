@@ -32,6 +32,11 @@
 // the machine together.  The owner is looked up from the device-side counts at the top of every tile iteration and
 // made wave-uniform there; from then on the tile is a tile of the one-frame lattice kernel on that frame's node
 // list, volume, maps and calibrations (ViewLatticeFrame), line for line.
+//
+// BATCH without LATTICE (mp_query_views_counted_batch, explicit points of n frames counted on the device): the same
+// tile ownership over the frames' clamped counts; a frame's tile is a tile of the explicit-point kernel on that
+// frame's [3, capacity] points, shared by its views as a lattice's nodes are (ViewPointsFrame: load_point reads
+// them), and only the columns of ONE view write: row `view`, to out[f][o * capacity + i] for i < count_f.
 #include <cstring>
 
 #include "mp_internal.h"
@@ -75,7 +80,8 @@ __device__ __forceinline__ void column_view(int p, int nv, int magic, int &g, in
 
 // z_feat of point n in view u: the view's projection z times z_scale (MonoPortNet.py:72, :78);
 // DIRECT: row C of view u's explicit feature columns
-// LATTICE: node n of the level's list instead of view u's explicit point
+// LATTICE: point n of set.src, shared by the views (a level's node list, or a counted frame's explicit points),
+// instead of view u's own explicit point
 template <int C, bool DIRECT, bool LATTICE, typename SET>
 __device__ __forceinline__ float view_z(const SET &set, int u, long long n, float z_scale,
                                         float &x, float &y) {
@@ -125,6 +131,7 @@ __device__ __forceinline__ float column_z(const SET &set, int p, int magic, long
 // stride set.sc), one output [Cout, N] written by the view-0 columns.
 // LATTICE = true: one octree level (see the head of this file); `set` is then a ViewLatticeDev.
 // BATCH (with LATTICE): the same level of n frames; `set` is then a ViewLatticeBatchDev.
+// BATCH (without LATTICE): counted explicit points of n frames; `set` is then a ViewPointsBatchDev.
 template <bool LATTICE, bool BATCH = false>
 struct ViewSetArg {
   typedef ViewSetDev type;
@@ -136,6 +143,10 @@ struct ViewSetArg<true, false> {
 template <>
 struct ViewSetArg<true, true> {
   typedef ViewLatticeBatchDev type;
+};
+template <>
+struct ViewSetArg<false, true> {
+  typedef ViewPointsBatchDev type;
 };
 
 // Frame f of a ViewLatticeBatchDev under the member names of ViewLatticeDev, so that the tile body reads either.
@@ -170,6 +181,36 @@ __device__ __forceinline__ ViewLatticeFrame lattice_frame(const ViewLatticeBatch
   fr.vol = set.it[f].vol;
   return fr;
 }
+// Frame f of a ViewPointsBatchDev: explicit points [3, capacity] behind load_point (packed == nullptr), one output
+struct ViewPointsFrame {
+  int nv, proj, view;
+  const float *const *feat;
+  const float *const *calib;
+  PointSrc src;
+  float *out;
+  long long out_stride;
+};
+__device__ __forceinline__ ViewPointsFrame lattice_frame(const ViewPointsBatchDev &set, int f) {
+  ViewPointsFrame fr;
+  fr.nv = set.nv;
+  fr.proj = set.proj;
+  fr.view = set.view;
+  fr.feat = set.feat + f * set.nv;
+  fr.calib = set.calib + f * set.nv;
+  fr.src.pts = set.it[f].pts;
+  fr.src.sn = 1;
+  fr.src.sc = set.capacity;
+  fr.src.out_stride = set.capacity;
+  fr.src.packed = nullptr;
+  fr.src.stride = fr.src.level_res = 0;
+  fr.src.res_final = fr.src.half_step = 0.0f;
+  for (int i = 0; i < 3; ++i) fr.src.bmin[i] = fr.src.blen[i] = 0.0f;
+  fr.src.n_dev = set.it[f].n_dev;
+  fr.src.n = 0;
+  fr.out = set.it[f].out;
+  fr.out_stride = set.capacity;
+  return fr;
+}
 __device__ __forceinline__ const ViewSetDev &lattice_frame(const ViewSetDev &set, int) { return set; }
 __device__ __forceinline__ const ViewLatticeDev &lattice_frame(const ViewLatticeDev &set, int) { return set; }
 
@@ -181,11 +222,13 @@ __device__ __forceinline__ long long view_tiles(long long n, int gpts, unsigned 
   return (long long)(((unsigned long long)(n + gpts - 1) * m35) >> 35);
 }
 
-// tile_owner (query_common.h) for the frames of a ViewLatticeBatchDev and tiles of gpts points: fi = the frame
-// that owns `gtile` (-1: past the last tile of the last frame), tile0 = its first tile, n = its count.  Every
+// tile_owner (query_common.h) for the frames of a ViewLatticeBatchDev / ViewPointsBatchDev and tiles of gpts points:
+// fi = the frame that owns `gtile` (-1: past the last tile of the last frame), tile0 = its first tile, n = its count
+// (set.count: a ViewPointsBatchDev's is clamped to [0, capacity]).  Every
 // thread reads the same counts, so the result is the same in every lane; the caller makes that known to the
 // compiler (readfirstlane), which keeps the frame's pointers in SGPRs.
-__device__ __forceinline__ void view_tile_owner(const ViewLatticeBatchDev &set, long long gtile, int gpts,
+template <typename SET>
+__device__ __forceinline__ void view_tile_owner(const SET &set, long long gtile, int gpts,
                                                 unsigned long long m35, int &fi_out, long long &tile0_out,
                                                 long long &n_out) {
   int fi = -1;
@@ -219,7 +262,8 @@ template <int C, int COUT, int WPS, bool DIRECT, bool LATTICE = false, bool BATC
 __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
     MlpPack mlp, int fh, int fw, float z_scale, int act, typename ViewSetArg<LATTICE, BATCH>::type aset) {
   static_assert(!(DIRECT && LATTICE), "explicit features have no lattice");
-  static_assert(LATTICE || !BATCH, "frames are batched on the lattice only");
+  static_assert(!(DIRECT && BATCH), "explicit features are not batched");
+  constexpr bool SHARED = LATTICE || BATCH;  // one point set for all views, behind load_point
   constexpr int ROWB = C * 4;
   constexpr int NGX = C / 8;  // K groups of the feature segment
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -300,7 +344,7 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
           const bool live_n = p < ncol && n < n_pts;
           fmap[u] = set.feat[v];
           float x = 0.0f, y = 0.0f;
-          if (live_n) (void)view_z<C, false, LATTICE>(set, v, n, z_scale, x, y);
+          if (live_n) (void)view_z<C, false, SHARED>(set, v, n, z_scale, x, y);
           // grid_sample on every finite projection, in the image or not (zero padding)
           t[u] = make_taps(x, y, fh, fw, C, live_n && !non_finite(x, y));
         }
@@ -328,7 +372,7 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
     // z_feat of this wave's two column blocks for the z k-steps of layers 0-2 (lanes 0-31 carry it, 32-63 supply 0)
     float zb[2];
 #pragma unroll
-    for (int cb = 0; cb < 2; ++cb) zb[cb] = h == 0 ? column_z<C, DIRECT, LATTICE>(set, 32 * cb + j, magic, n0, n_pts, ncol, z_scale, false) : 0.0f;
+    for (int cb = 0; cb < 2; ++cb) zb[cb] = h == 0 ? column_z<C, DIRECT, SHARED>(set, 32 * cb + j, magic, n0, n_pts, ncol, z_scale, false) : 0.0f;
     __syncthreads();
 
     // ---------------- layers 0-2, each column on its own features and z (query_mfma.h) ----------------
@@ -374,7 +418,7 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
       // the z row of tmpy: the group mean of z_feat (made here rather than kept live through layers 0-2)
       float zm[2];
 #pragma unroll
-      for (int cb = 0; cb < 2; ++cb) zm[cb] = h == 0 ? column_z<C, DIRECT, LATTICE>(set, 32 * cb + j, magic, n0, n_pts, ncol, z_scale, true) : 0.0f;
+      for (int cb = 0; cb < 2; ++cb) zm[cb] = h == 0 ? column_z<C, DIRECT, SHARED>(set, 32 * cb + j, magic, n0, n_pts, ncol, z_scale, true) : 0.0f;
       gemm_z<1, 2>(acc3, az3, zm);
 #pragma unroll
       for (int n = 0; n < 2; ++n) lrelu(acc3[0][n]);
@@ -399,16 +443,16 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
         float zsum = 0.0f, xo = 0.0f, yo = 0.0f;
         bool poisoned = false;
         float *__restrict__ out = nullptr;
-        if constexpr (!LATTICE) out = set.out[0];
+        if constexpr (!SHARED) out = set.out[0];
         for (int u = 0; u < nv; ++u) {
           float x, y;
-          const float zf = view_z<C, DIRECT, LATTICE>(set, u, n, z_scale, x, y);
+          const float zf = view_z<C, DIRECT, SHARED>(set, u, n, z_scale, x, y);
           zsum = u == 0 ? zf : zsum + zf;
           poisoned = poisoned || (set.proj == MP_PROJ_PERSPECTIVE && non_finite(x, y));
           if (u == v) {
             xo = x;
             yo = y;
-            if constexpr (!DIRECT && !LATTICE) out = set.out[u];
+            if constexpr (!DIRECT && !SHARED) out = set.out[u];
           }
         }
         val = fmaf(wz, __fdiv_rn(zsum, (float)nv), val);
@@ -421,6 +465,12 @@ __global__ __launch_bounds__(kQueryThreads, WPS) void pifu_query_views_kernel(
             const uint32_t code = set.src.packed[n];
             const long long lr = set.src.level_res;
             set.vol[((long long)(code >> 20) * lr + ((code >> 10) & 1023u)) * lr + (code & 1023u)] = r;
+          }
+        } else if constexpr (BATCH) {
+          // row `view` only, to the frame's [Cout, capacity] output; n < n_pts <= capacity
+          if (v == set.view) {
+            const float r = poisoned ? __builtin_nanf("") : in_image(xo, yo) ? activate(val, act) : 0.0f;
+            set.out[o * set.out_stride + n] = r;
           }
         } else {
           // MonoPortNet.py:89 per view; a non-finite view's NaN samples reach every row through the mean
@@ -507,6 +557,49 @@ int launch_query_views_lattice_batch(mp_ctx *ctx, const Mlp &m, const ViewLattic
   if (const int rc = prof_end(ctx, st)) return rc;
   MP_HIP(ctx, hipGetLastError());
   return MP_OK;
+}
+
+template <int C, int COUT, int WPS>
+static int launch_views_counted_t(mp_ctx *ctx, const Mlp &m, const ViewPointsBatchDev &set, int h, int w,
+                                  float z_scale, hipStream_t st) {
+  constexpr int lds = kTilePts * C * 4 + kHbBytes;
+  auto kern = pifu_query_views_kernel<C, COUT, WPS, false, false, true>;
+  if (const int rc = raise_lds_limit(ctx, reinterpret_cast<const void *>(kern), lds)) return rc;
+  const long long gpts = kTilePts / set.nv;
+  const long long tiles = (set.capacity + gpts - 1) / gpts * set.n;
+  if (tiles <= 0) return MP_OK;
+  const long long grid = query_grid(tiles, (long long)ctx->n_cu * WPS, true);
+  if (const int rc = prof_begin(ctx, st)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kQueryThreads), lds, st, m.pack(), h, w, z_scale, m.act,
+                     set);
+  if (const int rc = prof_end(ctx, st)) return rc;
+  MP_HIP(ctx, hipGetLastError());
+  return MP_OK;
+}
+
+// Explicit points of set.n frames, counted on the device: the resident grid strides over the frames' tiles, each
+// frame's rounded up on its own (view_tile_owner); the heads are those of launch_query_views.
+int launch_query_views_counted_batch(mp_ctx *ctx, const Mlp &m, const ViewPointsBatchDev &set, int h, int w,
+                                     float z_scale, hipStream_t st) {
+  const char *who = "mp_query_views_counted_batch";
+  if (set.nv < 1 || set.nv > kMaxViews)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: 1..%d views, got %d", who, kMaxViews, set.nv);
+  if (m.precision != MP_PREC_F32)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: the multi-view kernel is f32 only (head precision %d)", who, m.precision);
+  if (set.view < 0 || set.view >= set.nv) return fail(ctx, MP_ERR_ARG, "%s: view %d of %d", who, set.view, set.nv);
+  if (set.n < 1 || set.n > kMaxFrames || set.n * set.nv > kMaxFrameViews)
+    return fail(ctx, MP_ERR_ARG, "%s: 1..%d frames and at most %d frames x views per launch, got %d x %d", who,
+                kMaxFrames, kMaxFrameViews, set.n, set.nv);
+#define MP_VCASE(CC, CO, WP) \
+  if (m.c == CC && m.cout == CO) return launch_views_counted_t<CC, CO, WP>(ctx, m, set, h, w, z_scale, st);
+  MP_VCASE(256, 1, 2)
+  MP_VCASE(256, 3, 2)
+  MP_VCASE(512, 1, 1)
+  MP_VCASE(512, 3, 1)
+#undef MP_VCASE
+  return fail(ctx, MP_ERR_UNSUPPORTED,
+              "%s: multi-view query kernels are built for C in {256,512}, Cout in {1,3}; got C=%d Cout=%d", who, m.c,
+              m.cout);
 }
 
 int launch_query_views(mp_ctx *ctx, const Mlp &m, const ViewSetDev &set, int h, int w, float z_scale,

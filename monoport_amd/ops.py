@@ -804,6 +804,52 @@ def recon_views_batch(mlp, maps, calibs, projection, z_scale, b_min, b_max, reso
     return volumes, status
 
 
+def query_views_counted_batch(mlp, maps, points, counts, calibs, projection, z_scale, view=0, outs=None):
+    """mp_query_views_counted_batch: ``query_views`` over n independent frames of V views each in ONE launch, on point
+    sets whose sizes live on the device (multi-view netC colours over counted vertex lists).  maps: list of n lists of
+    V channels-last maps [H,W,C]; points: n contiguous f32 [3,cap] tensors (one cap; frame f's points are seen by all
+    its views); counts: n device int32[1] tensors (<= cap); calibs: [n,V,>=3,4] or n sequences of V calibrations;
+    projection, ``view``: one for all frames.  n <= ``max_view_frames(V)``.  Returns the list of n [Cout,cap] tensors
+    (or ``outs``): columns [:count_f] of frame f hold row ``view`` of ``query_views`` on its maps, calibrations and
+    points bit for bit, the other columns are left as they were (zeros in a fresh result).  Nothing is synchronised.
+    f32 heads only; registered skip tables are not used."""
+    who = "query_views_counted_batch"
+    ctx = mlp.ctx
+    n = len(maps)
+    if n == 0 or len(points) != n or len(counts) != n or len(calibs) != n:
+        raise ValueError("%s: %d frames, %d point sets, %d counts, %d sets of calibrations"
+                         % (who, n, len(points), len(counts), len(calibs)))
+    v_n = len(maps[0])
+    _check_count(who, "views", v_n, MAX_VIEWS)
+    if any(len(m) != v_n for m in maps):
+        raise ValueError("%s: every frame needs the same number of views (%d)" % (who, v_n))
+    _check_count(who, "frames of %d views" % v_n, n, max_view_frames(v_n))
+    flat = [m for frame in maps for m in frame]
+    h, w, c, dev = _maps(who, flat)
+    cap = points[0].shape[-1]
+    if any(tuple(p.shape) != (3, cap) or not p.is_contiguous() or p.dtype != torch.float32 for p in points):
+        raise ValueError("%s: the point sets must be contiguous float32 [3,%d]" % (who, cap))
+    if any(k.dtype != torch.int32 or k.numel() < 1 for k in counts):
+        raise ValueError("%s: a count is an int32[1] tensor on the maps' device" % who)
+    frames_cal = [_calib_list(frame, v_n, who) for frame in calibs]
+    if outs is not None:
+        if len(outs) != n:
+            raise ValueError("%s: %d frames, %d outputs" % (who, n, len(outs)))
+        if any(o.dim() != 2 or o.shape[1] != cap or not o.is_contiguous() or o.dtype != torch.float32 for o in outs):
+            raise ValueError("%s: the outputs must be contiguous float32 [Cout,%d]" % (who, cap))
+    cals = [_calib_dev(cb, dev) for frame in frames_cal for cb in frame]
+    if outs is None:
+        outs = [torch.zeros((mlp.cout, cap), dtype=torch.float32, device=dev) for _ in range(n)]
+    elif any(o.shape[0] != mlp.cout for o in outs):
+        raise ValueError("%s: the outputs must be contiguous float32 [%d,%d]" % (who, mlp.cout, cap))
+    ctx.check(ctx.lib.mp_query_views_counted_batch(
+        ctx.handle, mlp.id, n, v_n, _ptr_array(flat), c, h, w, _ptr_array(points), cap, _ptr_array(counts),
+        _ptr_array(cals), _projection(projection), float(z_scale), int(view), _ptr_array(outs), _stream(outs[0])),
+        "mp_query_views_counted_batch")
+    _keep_until_done(dev, cals)
+    return outs
+
+
 class LevelEngine:
     """The coarse-to-fine engine one step at a time, for an ARBITRARY ``query_func``: node
     selection, lattice coordinates, conflict detection and scatter run as HIP kernels

@@ -21,7 +21,8 @@ that host-side launch latency and GPU fill, not thread parallelism, are what mat
   (``depth`` x ``batch`` frames in flight; BASELINE configs[3] asks for 8);
 * a ``ViewsSlot`` is the FrameSlot of a multi-view netG (a capture rig: ``batch`` frames of V views each): one
   encoder pass over batch x V images, the octree of all frames through ``mp_recon_views_batch``, then the same
-  per-volume stages (``FramePipeline(..., slot_class=ViewsSlot)``).
+  per-volume stages (``FramePipeline(..., slot_class=ViewsSlot)``); a ``ColorViewsSlot`` adds a multi-view netC: one
+  more encoder pass and the colours of all frames through ``mp_query_views_counted_batch``.
 """
 import collections
 
@@ -112,6 +113,8 @@ class FrameSlot:
     """Static buffers for ``batch`` in-flight frames (geometry chain of RTL/main.py:366-428, plus
     the netC texture stages :373-441 when ``netC`` is given)."""
 
+    view = 0  # the row of a multi-view head's result (ViewsSlot); a single-view head has the one
+
     def __init__(self, netG, device, resolutions=RESOLUTIONS, b_min=(-1, -1, -1), b_max=(1, 1, 1),
                  balance=0.5, feature_hook=None, use_graph=False, netC=None, batch=1, skip_table=None,
                  final_level="dilate3", mesh=None, pictures=None):
@@ -192,11 +195,12 @@ class FrameSlot:
         self.n_active = b  # frames of the current submission (a stream's last batch may be short)
         if netC is not None:
             from .recon import color_matrix
-            # one channels-last netC map per frame: the colour queries of the whole slot are one launch
+            # one channels-last netC map per image: the colour queries of the whole slot are one launch
             self.feats_hwc_c = [torch.empty((128, 128, 512), dtype=torch.float32, device=dev)
-                                for _ in range(b)]
+                                for _ in range(bv)]
             self.mat_color = color_matrix(b_min, b_max, r)
-            self.image_c = torch.zeros((b, 3, 512, 512), dtype=torch.float32, device=dev)
+            self.image_c = torch.zeros((bv, 3, 512, 512), dtype=torch.float32, device=dev)
+            self.image_c_in = self._per_frame(self.image_c)
         if self.mesh is not None:
             opts = self.mesh
             cap_v = 12 * r * r  # ops.marching_cubes_raw's capacities
@@ -323,19 +327,16 @@ class FrameSlot:
             self.vertices[b] = raws[b]
             self.renders[b] = renders[b]
             if self.netC is not None:
-                # netC.filter(image_c, feat_prior=featG_last) -> cat([prior, featC])
-                # (MonoPortNet.py:41-45) packed straight into one channels-last map per frame
-                ops.pack_features([feat[b:b + 1], feat_c[b:b + 1]], out=self.feats_hwc_c[b])
+                self._pack_colour_maps(b, feat, feat_c)
                 pts_all.append(ops.vertex_points(x, y, z, count, r, self.mat_color))
         if self.netC is not None:
             # netC.query on the visible vertices (RTL/main.py:231-248) of ALL frames of the slot:
-            # one fused-query launch per chunk of 32 frames (14 k points per frame alone would
+            # one fused-query launch per chunk of frames (14 k points per frame alone would
             # leave most CUs idle)
-            for b0 in range(0, n, MAX_RECON_BATCH):
-                b1 = min(b0 + MAX_RECON_BATCH, n)
-                preds = ops.query_counted_batch(
-                    mlp_c, self.feats_hwc_c[b0:b1], pts_all[b0:b1],
-                    [self.vertices[b][4] for b in range(b0, b1)], self.calib[b0:b1], Z_SCALE)
+            step = self._colour_chunk()
+            for b0 in range(0, n, step):
+                b1 = min(b0 + step, n)
+                preds = self._colour_query(mlp_c, b0, b1, pts_all[b0:b1], [self.vertices[b][4] for b in range(b0, b1)])
                 tex = ops.paint_batch([self.vertices[b][0] for b in range(b0, b1)], [self.vertices[b][1] for b in range(b0, b1)],
                                       preds, 1, [self.vertices[b][4] for b in range(b0, b1)], r, 0.5, 0.5, -np.inf, np.inf)
                 for b in range(b0, b1):
@@ -344,6 +345,20 @@ class FrameSlot:
             self._mesh_chain(n)
         if self.picture_options is not None:
             self._render_pictures(n)
+
+    # the netC pieces of the chain that depend on the head's views (ColorViewsSlot overrides them)
+    def _pack_colour_maps(self, b, feat, feat_c):
+        """Frame b's netC map: netC.filter(image_c, feat_prior=featG_last) -> cat([prior, featC]) (MonoPortNet.py:41-45)
+        packed straight into one channels-last map per frame."""
+        ops.pack_features([feat[b:b + 1], feat_c[b:b + 1]], out=self.feats_hwc_c[b])
+
+    def _colour_chunk(self):
+        """Frames per colour-query launch."""
+        return MAX_RECON_BATCH
+
+    def _colour_query(self, mlp_c, b0, b1, pts, counts):
+        """netC's predictions [3,cap] at the counted points of frames b0..b1, one launch."""
+        return ops.query_counted_batch(mlp_c, self.feats_hwc_c[b0:b1], pts, counts, self.calib[b0:b1], Z_SCALE)
 
     def _render_pictures(self, n):
         """The pictures of the slot's n frames under their ``views`` cameras each, from the mesh buffers the chain has
@@ -413,13 +428,17 @@ class FrameSlot:
         return [QueryBinding(self.netC, mlp_c, self.feats_hwc_c[b], self.calib[b:b + 1], Z_SCALE)
                 for b in range(b0, b1)]
 
+    def _mesh_chunk(self):
+        """Frames per set of launches of the mesh chain."""
+        return MESH_BATCH
+
     def _mesh_chain(self, n):
         """Marching cubes -> normals -> points -> netC colours of the slot's n frames into the slot's mesh buffers,
         MESH_BATCH frames per set of launches, each frame gated by its status[b, 0] (the volume of a frame whose
         coarsest octree level is empty is unspecified: its counts become (0, 0) and nothing else of it is touched).  With
         ``clean`` the chain starts with recon.keep_largest of the chunk's volumes, under the same gates."""
         from .recon import _mesh_chains
-        chunk = MESH_BATCH
+        chunk = self._mesh_chunk()
         if self.mesh.clean is not None:  # one chunk's cleaned volumes at a time, in the same buffer
             chunk = min(chunk, self.mesh_buffers["cleaned"].shape[0])
         for b0 in range(0, n, chunk):
@@ -431,7 +450,7 @@ class FrameSlot:
                 out["preds"] = list(out["preds"])
             self._mesh_chains[b0:b1] = _mesh_chains(
                 self.volumes[b0:b1], self.b_min, self.b_max, self.mesh, self._mesh_bindings(b0, b1),
-                gates=[self.status[b, 0:1] for b in range(b0, b1)], out=out)
+                gates=[self.status[b, 0:1] for b in range(b0, b1)], out=out, view=self.view)
 
     def meshes(self):
         """The meshes of the current submission, to be called after ``wait()`` (it waits if the caller has not): a
@@ -455,7 +474,7 @@ class FrameSlot:
         def rerun(b, max_verts, max_faces):
             self._reran.append(b)
             return _mesh_chains([self.volumes[b]], self.b_min, self.b_max, self.mesh, self._mesh_bindings(b, b + 1),
-                                max_verts=max_verts, max_faces=max_faces)[0]
+                                max_verts=max_verts, max_faces=max_faces, view=self.view)[0]
 
         return _collect_meshes([chain if row[0] else None for chain, row in zip(self._mesh_chains, host)],
                                [row[1:] for row in host], rerun)
@@ -510,7 +529,7 @@ class FrameSlot:
             self._load(self.image_in, images)
             self._load(self.calib_in, calibs)
             if self.netC is not None:
-                self._load(self.image_c, images if images_c is None else images_c)
+                self._load(self.image_c_in, images if images_c is None else images_c)
             self._chain()
         self._busy = True
 
@@ -561,20 +580,25 @@ class ViewsSlot(FrameSlot):
 
     ``view`` (0..V-1): the row of the [V,1,N] result the volumes hold -- the view-averaged prediction times that
     view's in-image mask (Seg3dLossless(fuse_views=True, view=...)); ``projection``: the one mode of all cameras.
-    No skip tables (the multi-view kernel does not read them).  Not built, NotImplementedError at construction:
-    ``netC`` (a multi-view colour query over the device-counted vertex lists) and hence ``mesh`` colours."""
+    No skip tables (the multi-view kernel does not read them).  This slot runs no ``netC``: it and hence ``mesh``
+    colours raise NotImplementedError at construction; ``ColorViewsSlot`` is the slot with a multi-view ``netC``."""
 
     def __init__(self, netG, device, *args, view=0, projection="orthogonal", **kwargs):
         self.view = int(view)
         self.projection = ops._projection(projection)
         super().__init__(netG, device, *args, **kwargs)
 
-    def _head_views(self, netG, netC, mesh):
+    def _netg_views(self, netG):
         v_n = netG.surface_classifier.num_views
         if v_n < 2:
-            raise ValueError("ViewsSlot: netG has a single-view head; use FrameSlot")
+            raise ValueError("%s: netG has a single-view head; use FrameSlot" % type(self).__name__)
         if not 0 <= self.view < v_n:
-            raise ValueError("ViewsSlot(view=%d): the head has %d views (rows 0..%d)" % (self.view, v_n, v_n - 1))
+            raise ValueError("%s(view=%d): the head has %d views (rows 0..%d)"
+                             % (type(self).__name__, self.view, v_n, v_n - 1))
+        return v_n
+
+    def _head_views(self, netG, netC, mesh):
+        v_n = self._netg_views(netG)
         if netC is not None:
             raise NotImplementedError("ViewsSlot: netC (multi-view colours over device-counted vertex lists) is not built")
         colors = None if mesh is None else (mesh.get("colors") if isinstance(mesh, dict) else getattr(mesh, "colors", None))
@@ -596,9 +620,60 @@ class ViewsSlot(FrameSlot):
                                   volumes=self.volumes[b0:b1], status=self.status[b0:b1])
 
 
+class ColorViewsSlot(ViewsSlot):
+    """A ViewsSlot with a MULTI-VIEW netC (num_views = netG's V): the texture stages of FrameSlot for frames of V views.
+    ``submit(images [n,V,3,512,512], calibs [n,V,4,4], images_c=None, cameras=None)``.  Behind the geometry of
+    ViewsSlot: ONE netC encoder pass over the slot's batch * V images (``feat_prior`` = the netG map of the same image),
+    packed into batch * V channels-last maps [128,128,512]; ``renders_tex`` from forward_vertices -> vertex_points ->
+    ``ops.query_views_counted_batch`` (mp_query_views_counted_batch: the colours of all frames of a chunk in one launch
+    of the multi-view kernel, on vertex lists counted on the device) -> paint_batch; and with ``mesh={"colors": True}``
+    the mesh chain's colour query through ``ViewsBinding``s on the slot's own maps, which ``pictures={"shade":
+    "colors"}`` rasterises unchanged.  The colours are row ``view`` of netC's [V,3,N] result: the view-averaged
+    prediction under view ``view``'s in-image mask, the row the volumes hold of netG's.  Chunks:
+    ``min(FrameSlot's chunk, ops.max_view_frames(V))`` frames.  A frame whose coarsest octree level is empty stays
+    gated off: the counts it leaves on the device are 0, so it owns no tile of the colour launch."""
+
+    def _head_views(self, netG, netC, mesh):
+        v_n = self._netg_views(netG)
+        if netC is None:
+            raise ValueError("ColorViewsSlot: a multi-view netC is required (ViewsSlot is the slot without colours)")
+        c_n = netC.surface_classifier.num_views
+        if c_n != v_n:
+            raise ValueError("ColorViewsSlot: netC has num_views = %d, netG has %d%s"
+                             % (c_n, v_n, "; a single-view netC cannot colour frames of several views" if c_n < 2 else ""))
+        return v_n
+
+    def _pack_colour_maps(self, b, feat, feat_c):
+        v_n = self.views
+        for i in range(b * v_n, (b + 1) * v_n):
+            ops.pack_features([feat[i:i + 1], feat_c[i:i + 1]], out=self.feats_hwc_c[i])
+
+    def _colour_chunk(self):
+        return min(MAX_RECON_BATCH, ops.max_view_frames(self.views))
+
+    def _mesh_chunk(self):
+        return min(MESH_BATCH, ops.max_view_frames(self.views))
+
+    def _colour_maps(self, b0, b1):
+        v_n = self.views
+        return [self.feats_hwc_c[b * v_n:(b + 1) * v_n] for b in range(b0, b1)]
+
+    def _colour_query(self, mlp_c, b0, b1, pts, counts):
+        return ops.query_views_counted_batch(mlp_c, self._colour_maps(b0, b1), pts, counts, self.calib_in[b0:b1],
+                                             self.projection, Z_SCALE, view=self.view)
+
+    def _mesh_bindings(self, b0, b1):
+        if not self.mesh.colors:
+            return None
+        from .modeling.MonoPortNet import ViewsBinding
+        mlp_c = self.netC.surface_classifier.packed()
+        return [ViewsBinding(self.netC, mlp_c, maps, self.calib_in[b], Z_SCALE, self.projection)
+                for b, maps in zip(range(b0, b1), self._colour_maps(b0, b1))]
+
+
 class FramePipeline:
-    """Round-robin over ``depth`` slots (``slot_class``: FrameSlot, or ViewsSlot for a multi-view netG) of ``batch``
-    frames each."""
+    """Round-robin over ``depth`` slots (``slot_class``: FrameSlot; ViewsSlot for a multi-view netG; ColorViewsSlot for
+    a multi-view netG and netC) of ``batch`` frames each."""
 
     def __init__(self, netG, device, depth=2, batch=1, slot_class=FrameSlot, **slot_kwargs):
         self.slots = [slot_class(netG, device, batch=batch, **slot_kwargs) for _ in range(depth)]

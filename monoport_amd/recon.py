@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .modeling.MonoPortNet import capture_query
+from .modeling.MonoPortNet import ViewsBinding, capture_query
 
 _FLIP_Y = np.diag([1.0, -1.0, 1.0, 1.0])  # RTL/recon.py:6-11
 
@@ -72,12 +72,26 @@ def color_matrix(b_min, b_max, resolution):
     return mat
 
 
-def _counted_colours(bindings, pts, counts, outs=None):
+def _counted_colours(bindings, pts, counts, outs=None, view=0):
     """netC's predictions [3,cap] per frame at the first counts[f] of the points pts[f] [3,cap]: lists with one entry per
     frame, ``bindings`` of one head.  One orthogonal frame without buffers of the caller's (``outs``) is the per-frame
     counted launch; anything else the batched one per ops.MAX_FRAMES frames, with the projection modes if a frame is
-    perspective."""
+    perspective.  ``ViewsBinding``s (a multi-view head; one ``batch_key``): row ``view`` of the head's [V,3,N] result,
+    ops.query_views_counted_batch per ``ops.max_view_frames(V)`` frames."""
     n, preds = len(bindings), []
+    if isinstance(bindings[0], ViewsBinding):
+        b0 = bindings[0]
+        key = b0.batch_key(view)
+        if any(not isinstance(b, ViewsBinding) or b.batch_key(view) != key for b in bindings):
+            raise ValueError("_counted_colours: the bindings differ in head, views, projection or map size")
+        step = ops.max_view_frames(b0.num_views)
+        for f0 in range(0, n, step):
+            chunk = bindings[f0:f0 + step]
+            preds += ops.query_views_counted_batch(b0.mlp, [b.maps for b in chunk], pts[f0:f0 + step],
+                                                   counts[f0:f0 + step], [b.calibs for b in chunk], b0.projection,
+                                                   b0.z_scale, view=view,
+                                                   outs=None if outs is None else outs[f0:f0 + step])
+        return preds
     for f0, f1 in ops._frame_chunks(n):
         chunk = bindings[f0:f1]
         b0 = chunk[0]
@@ -91,12 +105,31 @@ def _counted_colours(bindings, pts, counts, outs=None):
     return preds
 
 
-def _bind_netC(who, netC, frames):
-    """The query bindings of a single-view ``netC``, one per frame of ``frames`` = (feature maps, calibration,
-    device to query on); the maps are moved there first (main.py:229-230)."""
+def _check_colour_view(who, netC, view):
+    """``view`` of the mesh calls against ``netC`` (None: no colours), before anything is bound or enqueued: None keeps
+    the single-view path, an int asks for row ``view`` of a multi-view head."""
+    if view is None or netC is None:
+        if view is not None:
+            raise ValueError("%s: view=%r picks a row of a multi-view netC, and there is no netC" % (who, view))
+        return
+    v_n = netC.surface_classifier.num_views
+    if v_n <= 1:
+        raise ValueError("%s: view=%r needs a multi-view netC; this one has num_views = %d" % (who, view, v_n))
+    if isinstance(view, bool) or not isinstance(view, int) or not 0 <= view < v_n:
+        raise ValueError("%s: view must be an int in 0..%d (netC has %d views), got %r" % (who, v_n - 1, v_n, view))
+
+
+def _bind_netC(who, netC, frames, view=None):
+    """The query bindings of ``netC``, one per frame of ``frames`` = (feature maps, calibration, device to query on);
+    the maps are moved there first (main.py:229-230).  ``view`` None: a single-view head (a multi-view one is refused);
+    an int (checked by ``_check_colour_view``): the ``ViewsBinding``s of a multi-view head, maps of batch V and
+    calibrations [V,4,4] per frame."""
+    if view is not None:
+        return [netC.bind_views([[f.to(device) for f in fs] for fs in feats], calib) for feats, calib, device in frames]
     if netC.surface_classifier.num_views > 1:
         raise NotImplementedError("%s: netC has num_views = %d; colour the vertices of a multi-view head with "
-                                  "mesh_util.vertex_colors" % (who, netC.surface_classifier.num_views))
+                                  "mesh_util.vertex_colors, or pass view= to the mesh calls"
+                                  % (who, netC.surface_classifier.num_views))
     return [netC.bind([[f.to(device) for f in fs] for fs in feats], calib) for feats, calib, device in frames]
 
 
@@ -217,12 +250,14 @@ None, netC's raw predictions [3,max_v] or None, and with ``simplify`` marching c
 are compared with), else None."""
 
 
-def _mesh_chains(sdfs, b_min, b_max, opts, bindings=None, gates=None, out=None, max_verts=None, max_faces=None):
+def _mesh_chains(sdfs, b_min, b_max, opts, bindings=None, gates=None, out=None, max_verts=None, max_faces=None,
+                 view=0):
     """volume [-> its largest body] -> verts, faces [-> their vertex clustering] [-> Taubin passes] -> normals ->
     netC predictions for volumes of one size, every stage one set of launches for all of them and no host value in
     between: one ``MeshChain`` per volume (the chain of one volume is this on a list of one).  ``opts``: a
-    ``MeshOptions``.  ``bindings``: None or one QueryBinding per volume (one head); the colour query takes the positions
-    before smoothing, which lie on the iso-surface.  ``gates``: as ``ops.marching_cubes_raw_batch``'s, for ``clean``
+    ``MeshOptions``.  ``bindings``: None or one QueryBinding per volume (one head), or one ViewsBinding per volume (a
+    multi-view head: the colours are row ``view`` of its result); the colour query takes the positions before
+    smoothing, which lie on the iso-surface.  ``gates``: as ``ops.marching_cubes_raw_batch``'s, for ``clean``
     too; a gated-off frame's counts of (0, 0) switch the later stages off.  ``out``: None or a dict of the caller's
     buffers (verts, faces, counts, normals, points, point_counts: [n, ...] tensors, preds: a list; with ``clean`` also
     cleaned [n,R,R,R] and clean_stats [n,4], with ``simplify`` simple_verts, simple_faces, simple_counts, simple_vmap,
@@ -254,7 +289,8 @@ def _mesh_chains(sdfs, b_min, b_max, opts, bindings=None, gates=None, out=None, 
     if bindings is not None:
         pt_out = (out["points"], out["point_counts"]) if "points" in out else None
         pts = ops.mesh_points_raw_batch(on_surface, counts, out=pt_out)
-        preds = _counted_colours(list(bindings), [p[0] for p in pts], [p[1] for p in pts], outs=out.get("preds"))
+        preds = _counted_colours(list(bindings), [p[0] for p in pts], [p[1] for p in pts], outs=out.get("preds"),
+                                 view=view)
     return [MeshChain(*frame) for frame in zip(verts, faces, counts, nrm, preds, mc_counts)]
 
 
@@ -293,13 +329,18 @@ def _collect_meshes(chains, sizes, rerun):
 
 @torch.no_grad()
 def reconstruct_mesh(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normals="accumulate", netC=None,
-                     feat_tensor_C=None, calib_tensor=None, clean=None, simplify=None, smooth=None):
+                     feat_tensor_C=None, calib_tensor=None, clean=None, simplify=None, smooth=None, view=None):
     """The finished mesh of an occupancy volume [1,1,D,H,W] (or [D,H,W]) as one device chain: marching cubes,
     per-vertex normals (``normals``: "accumulate", "reference" -- mesh_util.compute_normal's two modes -- or
     None to skip them) and, with ``netC``, per-vertex colours netC.query(vertices) * 0.5 + 0.5 as
     ``mesh_util.vertex_colors`` gives them.  Returns a ``Mesh``; None for ``sdf is None``.  One host sync
     per mesh (the two counts, read after everything is enqueued); if a capacity guess was short the chain
-    runs once more with exact capacities.  A multi-view ``netC`` is not served here.  ``clean``: None, or 6 / 26 =
+    runs once more with exact capacities.  ``view``: None for a single-view ``netC`` (a multi-view one then raises
+    NotImplementedError); k in 0..V-1 for a multi-view ``netC`` (num_views = V; ValueError for a single-view one or a k
+    outside): ``feat_tensor_C`` then holds the V views' maps (batch V), ``calib_tensor`` is [V,4,4], and the colours are
+    row k of the head's result on the vertices -- ``netC.query(feats, vertices for every view, calibs)[0][k]``, the
+    view-averaged prediction under view k's in-image mask -- from one counted launch
+    (``ops.query_views_counted_batch``), still without a host value in between.  ``clean``: None, or 6 / 26 =
     ``keep_largest(sdf, level, clean)`` in front of marching cubes inside the same chain (into a scratch volume;
     ``sdf`` is not modified; needs level > 0).  ``simplify``: None, or the cells per axis (1..512) of
     ``ops.mesh_simplify_raw`` over the box between marching cubes and the normals / colours: the mesh, its normals and
@@ -312,12 +353,14 @@ def reconstruct_mesh(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normal
     if sdf is None:
         return None
     opts = mesh_options(normals, level, netC is not None, clean, simplify, smooth)
+    _check_colour_view("reconstruct_mesh", netC, view)
     bindings = None
     if netC is not None:
-        bindings = _bind_netC("reconstruct_mesh", netC, [(feat_tensor_C, calib_tensor, sdf.device)])
+        bindings = _bind_netC("reconstruct_mesh", netC, [(feat_tensor_C, calib_tensor, sdf.device)], view)
 
     def run(k=0, max_verts=None, max_faces=None):
-        return _mesh_chains([sdf], b_min, b_max, opts, bindings, max_verts=max_verts, max_faces=max_faces)[0]
+        return _mesh_chains([sdf], b_min, b_max, opts, bindings, max_verts=max_verts, max_faces=max_faces,
+                            view=view or 0)[0]
 
     chain = run()
     return _collect_meshes([chain], [_device_sizes(chain).cpu().tolist()], run)[0]  # the one host sync
@@ -325,16 +368,19 @@ def reconstruct_mesh(sdf, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normal
 
 @torch.no_grad()
 def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), normals="accumulate", netC=None,
-                          feat_tensors_C=None, calib_tensors=None, clean=None, simplify=None, smooth=None):
+                          feat_tensors_C=None, calib_tensors=None, clean=None, simplify=None, smooth=None, view=None):
     """``[reconstruct_mesh(s, level, b_min, b_max, normals, netC, feat_tensors_C[i], calib_tensors[i], clean, simplify,
-    smooth) for i, s in enumerate(sdfs)]`` -- every field of every ``Mesh`` the same bits -- with the chain enqueued ONCE for all volumes
+    smooth, view) for i, s in enumerate(sdfs)]`` -- every field of every ``Mesh`` the same bits -- with the chain enqueued ONCE for all volumes
     (batched marching cubes, normals, points and one counted colour query per ops.MAX_FRAMES volumes) and ONE host
     sync for all the counts (monoport_amd extension; the hook of a coalescing stage).  ``None`` entries of ``sdfs``
     give ``None``; the other volumes must be of one size (ValueError).  ``feat_tensors_C`` / ``calib_tensors``: one
     entry per volume (those of ``None`` volumes are not looked at).  A volume whose capacity guess was short is
-    re-run alone with exact capacities, as ``reconstruct_mesh`` does.  A multi-view ``netC`` is not served here."""
+    re-run alone with exact capacities, as ``reconstruct_mesh`` does.  ``view``: as in ``reconstruct_mesh``; with a
+    multi-view ``netC`` the colour query of all volumes is one ``ops.query_views_counted_batch`` launch per
+    ``ops.max_view_frames(V)`` volumes."""
     sdfs = list(sdfs)
     opts = mesh_options(normals, level, netC is not None, clean, simplify, smooth)
+    _check_colour_view("reconstruct_mesh_many", netC, view)
     if netC is not None:
         if feat_tensors_C is None or calib_tensors is None:
             raise ValueError("reconstruct_mesh_many: netC needs feat_tensors_C and calib_tensors")
@@ -348,7 +394,7 @@ def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), 
     bindings = None
     if netC is not None:
         bindings = _bind_netC("reconstruct_mesh_many", netC,
-                              [(feat_tensors_C[i], calib_tensors[i], sdfs[i].device) for i in idx])
+                              [(feat_tensors_C[i], calib_tensors[i], sdfs[i].device) for i in idx], view)
     meshes = [None] * len(sdfs)
     if not idx:
         return meshes
@@ -356,9 +402,9 @@ def reconstruct_mesh_many(sdfs, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1), 
 
     def rerun(k, max_verts, max_faces):
         return _mesh_chains([live[k]], b_min, b_max, opts, None if bindings is None else [bindings[k]],
-                            max_verts=max_verts, max_faces=max_faces)[0]
+                            max_verts=max_verts, max_faces=max_faces, view=view or 0)[0]
 
-    chains = _mesh_chains(live, b_min, b_max, opts, bindings)
+    chains = _mesh_chains(live, b_min, b_max, opts, bindings, view=view or 0)
     sizes = torch.stack([_device_sizes(c) for c in chains]).cpu().tolist()  # the one host sync
     for i, mesh in zip(idx, _collect_meshes(chains, sizes, rerun)):
         meshes[i] = mesh
