@@ -776,6 +776,44 @@ int mp_mesh_render_clip_batch(mp_ctx *ctx, int n_frames, const float *const *ver
                               float background, float *const *image, float *const *depth, int32_t *const *face_id,
                               float near, int flags, mp_stream stream);
 
+/* ---- pictures coloured per pixel (deferred shading): netC queried at the visible surface only ------------------------
+ * A render with attr = verts and the paint (1, 0, -inf, inf) is a picture of world-space surface positions.  The two
+ * calls below turn it into a counted point list for mp_query_counted_batch_proj / mp_query_views_counted_batch and put
+ * the predictions back, with no host value in between.  A frame's pictures are ONE flat array, as mp_mesh_render_batch
+ * lays them out: L = n_views * H * W pixels, pixel index p = the linear index into [n_views, H, W].  Both calls are
+ * defined bit for bit and are pure functions of their inputs.
+ *   mp_picture_points.  face_id int32 [L] as the render wrote it (-1 = uncovered), position f32 [L,3] (the render's
+ *     image).  Pixel p is covered iff face_id[p] >= 0.  With p_0 < p_1 < ... the covered pixels in ascending order and
+ *     K their number: for k < min(K, capacity), pixels[k] = p_k and points[c * capacity + k] = position[3 p_k + c],
+ *     the same 32 bits (points f32 [3,capacity], the layout mp_query_counted reads; pixels int32 [capacity]).
+ *     count (device int32[2]): count[0] = min(K, capacity), what the counted queries read; count[1] = K, so
+ *     count[1] > capacity tells a truncated list.  Columns at or beyond count[0] are not written.  The order is
+ *     ascending p, never arrival order: block counts, a scan of them, then the emit (picture.hip, three launches, no
+ *     atomic).  Scratch from the stream's arena: 4 ceil(L / 1024) bytes per frame (the block sums), + 256; it is
+ *     written before it is read, whatever the arena held.  A frame with no covered pixel gets count = {0, 0}.
+ *   mp_picture_paint.  values f32 [3,capacity] channel-major, as the queries write them.  For k < min(count[0],
+ *     capacity) (a negative count[0] is 0) with 0 <= pixels[k] < L: image[3 pixels[k] + c] = clamp(values[c * capacity
+ *     + k] * scale + bias, lo, hi), the two operations and the clamp of mp_paint (raw netC predictions: 0.5, 0.5,
+ *     -inf, inf).  An index outside the range is skipped, never written; no other pixel of image f32 [L,3] is touched.
+ *     With the pixels of mp_picture_points no pixel is named twice; a caller's list that names one twice leaves either
+ *     value.  `image` may be the buffer `position` was read from: the calls are ordered on the stream.  One launch.
+ * MP_ERR_ARG: n_frames outside 1..mp_max_frames(); n_pixels or capacity < 1; a NULL or not 4-byte aligned buffer of any
+ * frame.  MP_ERR_UNSUPPORTED: n_pixels beyond 2^31 / 3.  Each refusal leaves an mp_last_error message and launches
+ * nothing.  Asynchronous, nothing synchronised.  The per-frame calls are the batched ones with one frame; in the
+ * batched ones face_id / position / points / pixels / count / values / image are HOST arrays of n_frames device
+ * pointers (one n_pixels and one capacity for all), blockIdx.y is the frame and one set of launches serves all frames:
+ * frame f's outputs equal the per-frame call's on frame f's inputs BIT FOR BIT. */
+int mp_picture_points(mp_ctx *ctx, const int32_t *face_id, const float *position, int64_t n_pixels, int64_t capacity,
+                      float *points, int32_t *pixels, int32_t *count, mp_stream stream);
+int mp_picture_points_batch(mp_ctx *ctx, int n_frames, const int32_t *const *face_id, const float *const *position,
+                            int64_t n_pixels, int64_t capacity, float *const *points, int32_t *const *pixels,
+                            int32_t *const *count, mp_stream stream);
+int mp_picture_paint(mp_ctx *ctx, const float *values, const int32_t *pixels, const int32_t *count, int64_t capacity,
+                     int64_t n_pixels, float scale, float bias, float lo, float hi, float *image, mp_stream stream);
+int mp_picture_paint_batch(mp_ctx *ctx, int n_frames, const float *const *values, const int32_t *const *pixels,
+                           const int32_t *const *count, int64_t capacity, int64_t n_pixels, float scale, float bias,
+                           float lo, float hi, float *const *image, mp_stream stream);
+
 /* The largest connected body of an occupancy volume [R,R,R] (no counterpart in the reference; the clean-up in front
  * of marching cubes that drops floating blobs).
  *   Foreground: voxels with value > level (marching cubes' "inside"; a NaN and value == level are background).

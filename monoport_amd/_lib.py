@@ -202,6 +202,11 @@ SIGNATURES = {
     "mp_mesh_render_clip_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_int, c_int, _pf32, c_int,
                                           c_int, c_int, c_int, c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp, c_vp, c_f32,
                                           c_int, c_vp]),
+    "mp_picture_points": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "mp_picture_points_batch": (c_int, [c_vp, c_int, c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "mp_picture_paint": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp]),
+    "mp_picture_paint_batch": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32, c_vp,
+                                       c_vp]),
     "mp_volume_keep_largest": (c_int, [c_vp, c_vp, c_int, c_f32, c_int, c_f32, c_vp, c_vp, c_vp]),
     "mp_volume_keep_largest_batch": (c_int, [c_vp, c_int, c_vp, c_int, c_f32, c_int, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "mp_group_norm": (c_int, [c_vp, c_vp, c_int, c_int, c_i64, c_int, c_vp, c_vp, c_f32, c_int, c_vp,

@@ -582,6 +582,53 @@ static int mesh_render_checked(mp_ctx *ctx, const char *who, int n_frames, const
                                   image, depth, face_id, clip, (hipStream_t)stream);
 }
 
+// what mp_picture_points and mp_picture_paint refuse alike, in the header's order; the caller holds the lock
+static int picture_sizes_checked(mp_ctx *ctx, const char *who, int n_frames, int64_t n_pixels, int64_t capacity) {
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (n_pixels < 1 || capacity < 1)
+    return fail(ctx, MP_ERR_ARG, "%s: n_pixels and capacity must be >= 1, got %lld and %lld", who, (long long)n_pixels,
+                (long long)capacity);
+  if (n_pixels > 0x7fffffffLL / 3)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: pictures beyond 2^31 / 3 pixels need 64-bit indices", who);
+  return MP_OK;
+}
+
+static int picture_points_checked(mp_ctx *ctx, const char *who, int n_frames, const int32_t *const *face_id,
+                                  const float *const *position, int64_t n_pixels, int64_t capacity,
+                                  float *const *points, int32_t *const *pixels, int32_t *const *count,
+                                  mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = picture_sizes_checked(ctx, who, n_frames, n_pixels, capacity);
+  if (rc != MP_OK) return rc;
+  if (!face_id || !position || !points || !pixels || !count) return bad_argument(ctx, who);
+  rc = check_frames(ctx, who, n_frames, nullptr, face_id, position, points, pixels, count);
+  if (rc != MP_OK) return rc;
+  DeviceGuard g(ctx->device);
+  void *scratch = nullptr;
+  rc = ensure_scratch(ctx, (hipStream_t)stream, picture_points_scratch_bytes(n_frames, n_pixels), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_picture_points_batch(ctx, scratch, n_frames, face_id, position, n_pixels, capacity, points, pixels,
+                                     count, (hipStream_t)stream);
+}
+
+static int picture_paint_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *values,
+                                 const int32_t *const *pixels, const int32_t *const *count, int64_t capacity,
+                                 int64_t n_pixels, float scale, float bias, float lo, float hi, float *const *image,
+                                 mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = picture_sizes_checked(ctx, who, n_frames, n_pixels, capacity);
+  if (rc != MP_OK) return rc;
+  if (!values || !pixels || !count || !image) return bad_argument(ctx, who);
+  rc = check_frames(ctx, who, n_frames, nullptr, values, pixels, count, image);
+  if (rc != MP_OK) return rc;
+  DeviceGuard g(ctx->device);
+  return launch_picture_paint_batch(ctx, n_frames, values, pixels, count, capacity, n_pixels, scale, bias, lo, hi, image,
+                                    (hipStream_t)stream);
+}
+
 static int keep_largest_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *volume, int r,
                                 float level, int connectivity, float fill, float *const *out, int32_t *const *stats,
                                 const int32_t *const *gate, mp_stream stream) {
@@ -1623,6 +1670,32 @@ int mp_mesh_points_batch(mp_ctx *ctx, int n_frames, const float *const *verts, i
                          mp_stream stream) {
   return mesh_points_checked(ctx, "mp_mesh_points_batch", n_frames, verts, max_verts, counts, points, count_out,
                              stream);
+}
+
+int mp_picture_points(mp_ctx *ctx, const int32_t *face_id, const float *position, int64_t n_pixels, int64_t capacity,
+                      float *points, int32_t *pixels, int32_t *count, mp_stream stream) {
+  return picture_points_checked(ctx, "mp_picture_points", 1, &face_id, &position, n_pixels, capacity, &points, &pixels,
+                                &count, stream);
+}
+
+int mp_picture_points_batch(mp_ctx *ctx, int n_frames, const int32_t *const *face_id, const float *const *position,
+                            int64_t n_pixels, int64_t capacity, float *const *points, int32_t *const *pixels,
+                            int32_t *const *count, mp_stream stream) {
+  return picture_points_checked(ctx, "mp_picture_points_batch", n_frames, face_id, position, n_pixels, capacity, points,
+                                pixels, count, stream);
+}
+
+int mp_picture_paint(mp_ctx *ctx, const float *values, const int32_t *pixels, const int32_t *count, int64_t capacity,
+                     int64_t n_pixels, float scale, float bias, float lo, float hi, float *image, mp_stream stream) {
+  return picture_paint_checked(ctx, "mp_picture_paint", 1, &values, &pixels, &count, capacity, n_pixels, scale, bias, lo,
+                               hi, &image, stream);
+}
+
+int mp_picture_paint_batch(mp_ctx *ctx, int n_frames, const float *const *values, const int32_t *const *pixels,
+                           const int32_t *const *count, int64_t capacity, int64_t n_pixels, float scale, float bias,
+                           float lo, float hi, float *const *image, mp_stream stream) {
+  return picture_paint_checked(ctx, "mp_picture_paint_batch", n_frames, values, pixels, count, capacity, n_pixels, scale,
+                               bias, lo, hi, image, stream);
 }
 
 int mp_volume_keep_largest(mp_ctx *ctx, const float *volume, int r, float level, int connectivity, float fill,

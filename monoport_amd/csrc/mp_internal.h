@@ -460,6 +460,15 @@ int launch_mesh_render_batch(mp_ctx *ctx, void *scratch, int n_frames, int n_vie
                              int proj, int nearest, int h, int w, float scale, float bias, float lo, float hi,
                              float background, float *const *image, float *const *depth, int32_t *const *face_id,
                              const MeshRenderClip *clip, hipStream_t st);
+// picture.hip: the covered pixels of n_frames flat pictures of n_pixels each -> counted point lists in ascending pixel
+// order (scratch: picture_points_scratch_bytes(n_frames, n_pixels)), and the scatter of [3,capacity] values back
+size_t picture_points_scratch_bytes(int n_frames, long long n_pixels);
+int launch_picture_points_batch(mp_ctx *ctx, void *scratch, int n_frames, const int32_t *const *face_id,
+                                const float *const *position, long long n_pixels, long long capacity,
+                                float *const *points, int32_t *const *pixels, int32_t *const *count, hipStream_t st);
+int launch_picture_paint_batch(mp_ctx *ctx, int n_frames, const float *const *values, const int32_t *const *pixels,
+                               const int32_t *const *count, long long capacity, long long n_pixels, float scale,
+                               float bias, float lo, float hi, float *const *image, hipStream_t st);
 
 // conv3x3.hip
 int launch_conv3x3_pack(mp_ctx *ctx, const float *w, int cout, int cin, float *wp, hipStream_t st);

@@ -1659,6 +1659,129 @@ def mesh_render_raw_batch(verts, faces, counts, attrs, calibs, res, projection="
                         perspective_correct=perspective_correct)
 
 
+def _picture_points(who, face_ids, positions, capacity, out):
+    n = len(face_ids)
+    if n == 0 or len(positions) != n:
+        raise ValueError("%s: %d face-id pictures, %d position pictures" % (who, n, len(positions)))
+    dev, npix = face_ids[0].device, face_ids[0].numel()
+    for f, p in zip(face_ids, positions):
+        if (f.dtype != torch.int32 or p.dtype != torch.float32 or f.numel() != npix or p.numel() != 3 * npix
+                or f.device != dev or p.device != dev or not f.is_contiguous() or not p.is_contiguous()):
+            raise ValueError("%s: per frame a contiguous int32 picture of %d face ids and a float32 one of positions "
+                             "[..., 3], on one device" % (who, npix))
+    cap = npix if capacity is None else int(capacity)
+    if npix < 1 or cap < 1:
+        raise ValueError("%s: at least one pixel and a capacity >= 1, got %d and %d" % (who, npix, cap))
+    if out is None:
+        points = torch.zeros((n, 3, cap), dtype=torch.float32, device=dev).unbind(0)
+        pixels = torch.zeros((n, cap), dtype=torch.int32, device=dev).unbind(0)
+        count = torch.empty((n, 2), dtype=torch.int32, device=dev).unbind(0)
+    else:
+        points = _frame_rows(who, "out[0] (points)", out[0], n, (3, cap), torch.float32, dev)
+        pixels = _frame_rows(who, "out[1] (pixels)", out[1], n, (cap,), torch.int32, dev)
+        count = _frame_rows(who, "out[2] (count)", out[2], n, (2,), torch.int32, dev)
+    ctx = get_context(dev)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_picture_points_batch(
+            ctx.handle, f1 - f0, _ptr_array(face_ids[f0:f1]), _ptr_array(positions[f0:f1]), npix, cap,
+            _ptr_array(points[f0:f1]), _ptr_array(pixels[f0:f1]), _ptr_array(count[f0:f1]), _stream(face_ids[0])),
+            "mp_picture_points_batch")
+    return list(zip(points, pixels, count))
+
+
+def picture_points(face_id, position, capacity=None, out=None):
+    """mp_picture_points_batch with one frame: the covered pixels (face_id >= 0) of a frame's pictures -- face_id int32
+    [...] of L pixels as ``mesh_render_raw`` wrote it, position float32 [..., 3] its image for ``attr = verts`` -- in
+    ascending pixel order, bit for bit as include/monoport_hip.h defines it: (points [3,capacity] float32, the operand
+    of ``query_counted``; pixels [capacity] int32; count int32[2] = (entries written, covered pixels)) on the device.
+    ``capacity``: L unless given; ``count[1] > capacity`` tells a truncated list.  ``out``: (points, pixels, count)
+    buffers to write into; fresh ones start as zeros.  No host sync."""
+    return _picture_points("picture_points", [face_id], [position], capacity,
+                           None if out is None else tuple([o] for o in out))[0]
+
+
+def picture_points_batch(face_ids, positions, capacity=None, out=None):
+    """mp_picture_points_batch: ``[picture_points(f, p, capacity) for f, p in zip(face_ids, positions)]`` (pictures of
+    one size) in one set of three launches per MAX_FRAMES frames, the same bits.  ``out``: (points [n,3,capacity],
+    pixels [n,capacity], count [n,2]) to write into.  No host sync."""
+    return _picture_points("picture_points_batch", face_ids, positions, capacity, out)
+
+
+def _picture_paint(who, values, pixels, counts, images, scale, bias, lo, hi):
+    n = len(values)
+    if n == 0 or len(pixels) != n or len(counts) != n or len(images) != n:
+        raise ValueError("%s: %d value sets, %d pixel lists, %d counts, %d images"
+                         % (who, n, len(pixels), len(counts), len(images)))
+    dev, cap, size = values[0].device, pixels[0].numel(), images[0].numel()
+    for v, p, k, im in zip(values, pixels, counts, images):
+        if (tuple(v.shape) != (3, cap) or v.dtype != torch.float32 or p.numel() != cap or p.dtype != torch.int32
+                or k.dtype != torch.int32 or k.numel() < 1 or im.dtype != torch.float32 or im.numel() != size
+                or not (v.is_contiguous() and p.is_contiguous() and im.is_contiguous())
+                or any(t.device != dev for t in (p, k, im))):
+            raise ValueError("%s: per frame contiguous values float32 [3,%d], pixels int32 [%d], an int32 count and a "
+                             "float32 image [..., 3] of one size, on one device" % (who, cap, cap))
+    if cap < 1 or size < 3 or size % 3:
+        raise ValueError("%s: a capacity >= 1 and images [..., 3], got %d and %d floats" % (who, cap, size))
+    ctx = get_context(dev)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_picture_paint_batch(
+            ctx.handle, f1 - f0, _ptr_array(values[f0:f1]), _ptr_array(pixels[f0:f1]), _ptr_array(counts[f0:f1]), cap,
+            size // 3, float(scale), float(bias), float(lo), float(hi), _ptr_array(images[f0:f1]), _stream(values[0])),
+            "mp_picture_paint_batch")
+    return list(images)
+
+
+def picture_paint(values, pixels, count, n_pixels=None, scale=0.5, bias=0.5, lo=-math.inf, hi=math.inf, background=1.0,
+                  out=None):
+    """mp_picture_paint_batch with one frame: out[pixels[k], :] = clamp(values[:, k] * scale + bias, lo, hi) for the
+    first count[0] entries of a list of ``picture_points`` (values float32 [3,capacity], as the counted queries write
+    them); an index outside the image is skipped and no other pixel is touched.  ``out``: the image float32 [..., 3] to
+    paint into, which may be the buffer the positions were read from; None: a fresh [n_pixels,3] image of
+    ``background``.  Returns the image.  No host sync."""
+    if out is None:
+        if n_pixels is None:
+            raise ValueError("picture_paint: without out= it needs n_pixels")
+        out = torch.full((int(n_pixels), 3), float(background), dtype=torch.float32, device=values.device)
+    return _picture_paint("picture_paint", [values], [pixels], [count], [out], scale, bias, lo, hi)[0]
+
+
+def picture_paint_batch(values, pixels, counts, n_pixels=None, scale=0.5, bias=0.5, lo=-math.inf, hi=math.inf,
+                        background=1.0, out=None):
+    """mp_picture_paint_batch: ``[picture_paint(v, p, c, ..., out=o) for ...]`` (lists of one capacity, images of one
+    size) in one launch per MAX_FRAMES frames, the same bits.  ``out``: the images (a list, or [n, ..., 3]); None:
+    fresh [n_pixels,3] images of ``background``.  No host sync."""
+    if out is None:
+        if n_pixels is None:
+            raise ValueError("picture_paint_batch: without out= it needs n_pixels")
+        out = torch.full((len(values), int(n_pixels), 3), float(background), dtype=torch.float32,
+                         device=values[0].device)
+    return _picture_paint("picture_paint_batch", values, pixels, counts, list(out), scale, bias, lo, hi)
+
+
+def render_netc_batch(who, verts, faces, counts, calibs, res, query, projection="orthogonal", nearest="max",
+                      background=1.0, out=None, lists=None, capacity=None, near=None, perspective_correct=False):
+    """Pictures coloured per pixel (deferred shading), no host value in between: (1) the rasteriser with ``attr =
+    verts`` -- a picture of world-space surface positions -- under the pictures' own cameras, projection, ``near`` and
+    ``perspective_correct``; (2) ``picture_points_batch`` over each mesh's views as one flat picture (capacity = its
+    pixels: nothing truncates); (3) ``query(points, counts)``: the caller's counted colour query over all meshes (lists
+    of [3,L] points and int32 counts -> list of raw predictions [3,L]), under the calibrations and projections its maps
+    were made under, chunked by the caller to the query's frame limits; (4) ``picture_paint_batch`` with (0.5, 0.5,
+    -inf, inf) into the picture the positions came from.  Returns what ``_mesh_render`` does: per mesh (image
+    [n_views,H,W,3] = query * 0.5 + 0.5 at covered pixels and ``background`` elsewhere, depth, face).  ``out``: (image,
+    depth or None, face) buffers; ``lists``: (points [n,3,L], pixels [n,L], count [n,2]) buffers.  ``capacity``: as in
+    ``_mesh_render``."""
+    if out is not None and (out[0] is None or out[2] is None):
+        raise ValueError("%s: a picture coloured per pixel needs the image and the face ids" % who)
+    raws = _mesh_render(who, verts, faces, counts, list(verts), calibs, res, projection, nearest, False, 1.0, 0.0,
+                        -math.inf, math.inf, background, out, capacity=capacity, near=near,
+                        perspective_correct=perspective_correct)
+    images, face_ids = [r[0] for r in raws], [r[2] for r in raws]
+    found = _picture_points(who, face_ids, images, None, lists)
+    preds = query([f[0] for f in found], [f[2] for f in found])
+    _picture_paint(who, list(preds), [f[1] for f in found], [f[2] for f in found], images, 0.5, 0.5, -math.inf, math.inf)
+    return raws
+
+
 # MP_CONN_* (include/monoport_hip.h): face neighbours / face, edge and corner neighbours
 CONNECTIVITIES = (_lib.CONN_6, _lib.CONN_26)
 

@@ -77,9 +77,9 @@ def _mesh_options(mesh, balance, has_netc):
     return opts
 
 
-def _picture_options(pictures, mesh):
-    """FrameSlot's ``pictures`` argument (a dict) -> PictureOptions; ``mesh``: the slot's validated MeshOptions or None.
-    Nothing is allocated here."""
+def _picture_options(pictures, mesh, has_netc=False):
+    """FrameSlot's ``pictures`` argument (a dict) -> PictureOptions; ``mesh``: the slot's validated MeshOptions or None;
+    ``has_netc``: whether the slot runs a netC (``shade="netC"`` queries it per pixel).  Nothing is allocated here."""
     who = "FrameSlot(pictures=...)"
     if not isinstance(pictures, dict):
         raise ValueError("%s: a dict with any of %s, got %r" % (who, list(PICTURE_KEYS), pictures))
@@ -101,6 +101,8 @@ def _picture_options(pictures, mesh):
         raise ValueError("%s: shade='normals', but the mesh options have normals=None" % who)
     if shade == "colors" and not mesh.colors:
         raise ValueError("%s: shade='colors' needs the mesh's colours (mesh colors, hence netC)" % who)
+    if shade == "netC" and not has_netc:
+        raise ValueError("%s: shade='netC' queries the slot's netC per pixel, and the slot has none" % who)
     projection, nearest = pictures.get("projection", "orthogonal"), pictures.get("nearest", "max")
     ops._projection(projection), ops._nearest(nearest)
     near, correct = pictures.get("near"), bool(pictures.get("perspective_correct", False))
@@ -143,11 +145,16 @@ class FrameSlot:
         ``self.picture_options`` is the validated ``PictureOptions`` (None without pictures).  ``submit`` then takes
         ``cameras``, the rasteriser (``ops.mesh_render_raw_batch``) runs behind the mesh chain on the slot's stream
         into the static ``pictures_image`` [batch,views,H,W,3] (None with ``shade=None``), ``pictures_depth`` and
-        ``pictures_face`` [batch,views,H,W], and ``pictures()`` hands the results out."""
+        ``pictures_face`` [batch,views,H,W], and ``pictures()`` hands the results out.  ``shade="netC"`` colours the
+        pictures per pixel (``recon.render_mesh(shade="netC")``): it needs the slot's ``netC`` but NOT the mesh's
+        colours -- with ``mesh={"colors": False}`` the per-vertex colour query is never enqueued, which is the saving --
+        and the slot then also owns, per frame of L = views * H * W pixels, the static lists of the covered pixels
+        (points [3,L], pixels [L], predictions [3,L], count [2]: 28 bytes per pixel); ``pictures_image`` holds the
+        surface positions first and the colours in the end."""
         self.views = self._head_views(netG, netC, mesh)  # images per frame; refuses what the slot class does not run
         # both option records are validated before anything is allocated
         self.mesh = None if mesh is None else _mesh_options(mesh, float(balance), netC is not None)
-        self.picture_options = None if pictures is None else _picture_options(pictures, self.mesh)
+        self.picture_options = None if pictures is None else _picture_options(pictures, self.mesh, netC is not None)
         self.net = netG
         self.netC = netC
         self.device = torch.device(device)
@@ -234,6 +241,12 @@ class FrameSlot:
                 self.pictures_image = torch.empty((b, po.views) + po.res + (3,), dtype=torch.float32, device=dev)
             self.pictures_depth = torch.empty((b, po.views) + po.res, dtype=torch.float32, device=dev)
             self.pictures_face = torch.empty((b, po.views) + po.res, dtype=torch.int32, device=dev)
+            if po.shade == "netC":  # the covered pixels of a frame's views as one counted list
+                n_pix = po.views * po.res[0] * po.res[1]
+                self.picture_lists = {"points": torch.zeros((b, 3, n_pix), dtype=torch.float32, device=dev),
+                                      "pixels": torch.zeros((b, n_pix), dtype=torch.int32, device=dev),
+                                      "preds": torch.zeros((b, 3, n_pix), dtype=torch.float32, device=dev),
+                                      "count": torch.zeros((b, 2), dtype=torch.int32, device=dev)}
             # the cameras of the current submission, on the host [batch,views,3,4]; the identity until the first one
             self._cameras = np.tile(np.eye(4, dtype=np.float32)[:3], (b, po.views, 1, 1))
 
@@ -356,9 +369,25 @@ class FrameSlot:
         """Frames per colour-query launch."""
         return MAX_RECON_BATCH
 
-    def _colour_query(self, mlp_c, b0, b1, pts, counts):
-        """netC's predictions [3,cap] at the counted points of frames b0..b1, one launch."""
-        return ops.query_counted_batch(mlp_c, self.feats_hwc_c[b0:b1], pts, counts, self.calib[b0:b1], Z_SCALE)
+    def _colour_query(self, mlp_c, b0, b1, pts, counts, outs=None):
+        """netC's predictions [3,cap] at the counted points of frames b0..b1, one launch (``outs``: into these)."""
+        return ops.query_counted_batch(mlp_c, self.feats_hwc_c[b0:b1], pts, counts, self.calib[b0:b1], Z_SCALE,
+                                       outs=outs)
+
+    def _picture_colours(self, n):
+        """``ops.render_netc_batch``'s query over the slot's n frames: the ``_colour_query`` hook per chunk of frames,
+        into the static predictions.  A frame's ``views`` pictures are one list, so the hook's per-frame maps and
+        calibrations are the list's."""
+        mlp_c = self.netC.surface_classifier.packed()
+        step = self._colour_chunk()
+        outs = list(self.picture_lists["preds"][:n])
+
+        def query(pts, counts):
+            for b0 in range(0, n, step):
+                b1 = min(b0 + step, n)
+                self._colour_query(mlp_c, b0, b1, pts[b0:b1], counts[b0:b1], outs=outs[b0:b1])
+            return outs
+        return query
 
     def _render_pictures(self, n):
         """The pictures of the slot's n frames under their ``views`` cameras each, from the mesh buffers the chain has
@@ -366,6 +395,15 @@ class FrameSlot:
         A gated-off frame's counts are (0, 0): pure background."""
         po = self.picture_options
         chains = self._mesh_chains[:n]
+        if po.shade == "netC":  # positions -> covered pixels -> netC at them -> colours, behind the mesh chain
+            lists = self.picture_lists
+            ops.render_netc_batch("FrameSlot", [c.verts for c in chains], [c.faces for c in chains],
+                                  [c.counts for c in chains], list(self._cameras[:n]), po.res, self._picture_colours(n),
+                                  po.projection, po.nearest, po.background,
+                                  out=(self.pictures_image[:n], self.pictures_depth[:n], self.pictures_face[:n]),
+                                  lists=(lists["points"][:n], lists["pixels"][:n], lists["count"][:n]), near=po.near,
+                                  perspective_correct=po.perspective_correct)
+            return
         attrs, channel_major, paint = None, False, (1.0, 0.0, -np.inf, np.inf)
         if po.shade == "normals":  # as main.py:220-225 paints them
             attrs, paint = [c.normals for c in chains], (0.5, 0.5, 0.0, 1.0)
@@ -386,15 +424,20 @@ class FrameSlot:
         overflowed the slot's capacities is rendered again from the re-run mesh by ``recon.render_mesh``, into fresh
         tensors: the bits the slot's own launch would have given at a sufficient capacity, except with
         ``shade="colors"``, where ``render_mesh`` interpolates the Mesh's finished colours and the slot netC's raw
-        predictions (the same picture, not the same last bits).  No slot has overflowed 12 r^2 / 24 r^2 so far."""
+        predictions (the same picture, not the same last bits); with ``shade="netC"`` they are the same bits again,
+        because both paths query netC at the same points.  No slot has overflowed 12 r^2 / 24 r^2 so far."""
         if self.picture_options is None:
             raise RuntimeError("FrameSlot.pictures(): the slot was made without pictures=...")
-        from .recon import MeshRender, render_mesh
+        from .recon import MeshRender, _render_meshes, render_mesh
         po = self.picture_options
         out = []
         for b, mesh in enumerate(self.meshes()):
             if mesh is None:
                 out.append(None)
+            elif b in self._reran and po.shade == "netC":  # recon.render_mesh(shade="netC") on the slot's own maps
+                out.append(MeshRender(*_render_meshes(
+                    "FrameSlot.pictures", [mesh], [self._cameras[b]], po.res, po.shade, po.projection, po.nearest,
+                    po.background, po.near, po.perspective_correct, self._colour_bindings(b, b + 1), self.view)[0]))
             elif b in self._reran:
                 out.append(render_mesh(mesh, self._cameras[b], po.res, po.shade, po.projection, po.nearest,
                                        po.background, po.near, po.perspective_correct))
@@ -421,8 +464,10 @@ class FrameSlot:
     def _mesh_bindings(self, b0, b1):
         """The colour queries of frames b0..b1 as recon._mesh_chains takes them (netC's head on the slot's own maps and
         calibrations), None without colours."""
-        if not self.mesh.colors:
-            return None
+        return self._colour_bindings(b0, b1) if self.mesh.colors else None
+
+    def _colour_bindings(self, b0, b1):
+        """netC's head on the slot's own maps and calibrations, one query binding per frame b0..b1."""
         from .modeling.MonoPortNet import QueryBinding
         mlp_c = self.netC.surface_classifier.packed()
         return [QueryBinding(self.netC, mlp_c, self.feats_hwc_c[b], self.calib[b:b + 1], Z_SCALE)
@@ -658,13 +703,11 @@ class ColorViewsSlot(ViewsSlot):
         v_n = self.views
         return [self.feats_hwc_c[b * v_n:(b + 1) * v_n] for b in range(b0, b1)]
 
-    def _colour_query(self, mlp_c, b0, b1, pts, counts):
+    def _colour_query(self, mlp_c, b0, b1, pts, counts, outs=None):
         return ops.query_views_counted_batch(mlp_c, self._colour_maps(b0, b1), pts, counts, self.calib_in[b0:b1],
-                                             self.projection, Z_SCALE, view=self.view)
+                                             self.projection, Z_SCALE, view=self.view, outs=outs)
 
-    def _mesh_bindings(self, b0, b1):
-        if not self.mesh.colors:
-            return None
+    def _colour_bindings(self, b0, b1):
         from .modeling.MonoPortNet import ViewsBinding
         mlp_c = self.netC.surface_classifier.packed()
         return [ViewsBinding(self.netC, mlp_c, maps, self.calib_in[b], Z_SCALE, self.projection)

@@ -465,20 +465,30 @@ MeshRender = collections.namedtuple("MeshRender", ["image", "depth", "face"])
 MeshRender.__doc__ = """Picture of ``render_mesh``: image [H,W,3] f32 (None without shading), depth [H,W] f32 (+0.0 where
 nothing is seen), face [H,W] int32 (-1 where nothing is seen); with a set of cameras each has a leading [n_views]."""
 
-SHADES = ("colors", "normals", None)
+SHADES = ("colors", "normals", "netC", None)
 
 
 def _shade_attr(who, mesh, shade):
     """The per-vertex values a ``shade`` paints and their (scale, bias, lo, hi): finished colours as they are, normals
-    as main.py:220-225 paints them."""
+    as main.py:220-225 paints them.  "netC" paints no per-vertex value: the picture is coloured per pixel."""
     if shade not in SHADES:
         raise ValueError("%s: shade must be one of %s, got %r" % (who, list(SHADES), shade))
-    if shade is None:
+    if shade is None or shade == "netC":
         return None, (1.0, 0.0, -np.inf, np.inf)
     attr = mesh.colors if shade == "colors" else mesh.normals
     if attr is None:
         raise ValueError("%s: shade=%r, but the mesh has no %s" % (who, shade, shade))
     return attr, ((1.0, 0.0, -np.inf, np.inf) if shade == "colors" else (0.5, 0.5, 0.0, 1.0))
+
+
+def _check_shade_netC(who, shade, netC, view):
+    """``shade`` against ``netC`` / ``view`` of the render calls, before anything is bound or enqueued."""
+    if shade == "netC" and netC is None:
+        raise ValueError("%s: shade='netC' colours the picture per pixel with netC= (and its feature maps and "
+                         "calibration)" % who)
+    if shade != "netC" and netC is not None:
+        raise ValueError("%s: netC= is what shade='netC' queries; shade=%r does not use it" % (who, shade))
+    _check_colour_view(who, netC, view)
 
 
 def _single_camera(calibs):
@@ -487,34 +497,55 @@ def _single_camera(calibs):
 
 @torch.no_grad()
 def render_mesh(mesh, calibs, res=257, shade="colors", projection="orthogonal", nearest="max", background=1.0,
-                near=None, perspective_correct=False):
+                near=None, perspective_correct=False, netC=None, feat_tensor_C=None, calib_tensor=None, view=None):
     """The z-buffered picture of a ``Mesh`` on the device (monoport_amd extension; ``ops.mesh_render_raw``): any camera
     ``calibs`` ([4,4] / [3,4], the convention of the queries; or [n_views, ...] for several pictures in one set of
     launches), any size ``res`` (int or (H, W)).  ``shade``: "colors" (the mesh's colours), "normals" (its normals * 0.5
-    + 0.5 clamped to [0,1], as the reference paints them) or None (depth and face ids only).  x runs along the first
-    image index as in the painted canvas, so a square image feeds ``visulization`` unchanged.  ``near`` (> 0, with
-    ``projection="perspective"``): faces are clipped at the plane zc = near, so the camera may stand anywhere, also
-    inside the body; ``perspective_correct`` then interpolates depth and shading perspective-correctly (both as
-    ``ops.mesh_render_raw``; None, the default, is the unclipped call).  Returns a ``MeshRender``; None for ``mesh is
-    None``.  No host sync."""
+    + 0.5 clamped to [0,1], as the reference paints them), "netC" (below) or None (depth and face ids only).  x runs
+    along the first image index as in the painted canvas, so a square image feeds ``visulization`` unchanged.  ``near``
+    (> 0, with ``projection="perspective"``): faces are clipped at the plane zc = near, so the camera may stand
+    anywhere, also inside the body; ``perspective_correct`` then interpolates depth and shading perspective-correctly
+    (both as ``ops.mesh_render_raw``; None, the default, is the unclipped call).  Returns a ``MeshRender``; None for
+    ``mesh is None``.  No host sync.
+
+    ``shade="netC"`` colours the picture per pixel (deferred shading): the rasteriser interpolates the world-space
+    surface position of every covered pixel, ``netC`` (with ``feat_tensor_C`` and ``calib_tensor``, the frame's own
+    input maps and calibration, as ``reconstruct_mesh`` takes them) is queried at those points only, and ``image``
+    holds ``netC.query(point) * 0.5 + 0.5`` there and ``background`` elsewhere; ``depth`` and ``face`` are those of
+    ``shade=None``.  The mesh needs neither colours nor normals, the query costs the covered pixels instead of the
+    vertices, and the texture keeps netC's detail whatever the mesh density.  ``view``: None for a single-view
+    ``netC``, k for row k of a multi-view one, as in ``reconstruct_mesh``.  ``shade="netC"`` without ``netC``, and
+    ``netC`` with any other shade, are ValueErrors raised before anything is enqueued."""
+    _check_shade_netC("render_mesh", shade, netC, view)
     if mesh is None:
         return None
-    return render_mesh_many([mesh], calibs, res, shade, projection, nearest, background, near, perspective_correct)[0]
+    return render_mesh_many([mesh], calibs, res, shade, projection, nearest, background, near, perspective_correct,
+                            netC=netC, feat_tensors_C=[feat_tensor_C], calib_tensors=[calib_tensor], view=view)[0]
 
 
 @torch.no_grad()
 def render_mesh_many(meshes, calibs, res=257, shade="colors", projection="orthogonal", nearest="max", background=1.0,
-                     near=None, perspective_correct=False):
+                     near=None, perspective_correct=False, netC=None, feat_tensors_C=None, calib_tensors=None,
+                     view=None):
     """``[render_mesh(m, calibs, ...) for m in meshes]`` in one set of launches per ops.MAX_FRAMES pictures (meshes x
     views), the same bits.  ``calibs``: one camera set for all meshes (a tensor / array), or a list with one camera set
     per mesh (those of ``None`` meshes are not looked at; all of one n_views).  ``None`` meshes give ``None``.  The
     meshes may differ in size: the per-mesh counts are made on the device from the tensors' shapes and the capacity of
     the call is the largest of them (no row at or beyond a mesh's counts is touched).  ``near`` / ``perspective_correct``
-    as in ``render_mesh``: one plane for all.  No host sync."""
+    as in ``render_mesh``: one plane for all.  With ``shade="netC"``: ``feat_tensors_C`` / ``calib_tensors`` hold one
+    entry per mesh (those of ``None`` meshes are not looked at), and the colour query of all meshes is one counted
+    launch per ops.MAX_FRAMES meshes (``ops.max_view_frames(V)`` with ``view``).  No host sync."""
     who = "render_mesh_many"
+    _check_shade_netC(who, shade, netC, view)
     if near is not None or perspective_correct:  # refused before a list of Nones returns
         ops._render_clip(who, projection, near, perspective_correct)
     meshes = list(meshes)
+    if netC is not None:
+        if feat_tensors_C is None or calib_tensors is None:
+            raise ValueError("%s: netC needs feat_tensors_C and calib_tensors" % who)
+        if len(feat_tensors_C) != len(meshes) or len(calib_tensors) != len(meshes):
+            raise ValueError("%s: %d meshes, %d feature sets, %d calibrations"
+                             % (who, len(meshes), len(feat_tensors_C), len(calib_tensors)))
     idx = [i for i, m in enumerate(meshes) if m is not None]
     out = [None] * len(meshes)
     if not idx:
@@ -525,22 +556,38 @@ def render_mesh_many(meshes, calibs, res=257, shade="colors", projection="orthog
         cams = [calibs[i] for i in idx]
     else:
         cams = [calibs] * len(idx)
-    live = [meshes[i] for i in idx]
-    shaded = [_shade_attr(who, m, shade) for m in live]
-    scale, bias, lo, hi = shaded[0][1]
-    verts = [m.verts.contiguous() for m in live]
-    faces = [m.faces.contiguous() for m in live]
-    attrs = None if shade is None else [ops._f32c(a) for a, _ in shaded]
-    sizes = _shape_counts(list(zip(verts, faces)))
-    capacity = (max(v.shape[0] for v in verts), max(f.shape[0] for f in faces))
-    raws = ops._mesh_render(who, verts, faces, list(sizes.unbind(0)), attrs, cams, res, projection, nearest, False,
-                            scale, bias, lo, hi, background, None, capacity=capacity, near=near,
-                            perspective_correct=perspective_correct)
+    bindings = None
+    if netC is not None:
+        bindings = _bind_netC(who, netC, [(feat_tensors_C[i], calib_tensors[i], meshes[i].verts.device) for i in idx],
+                              view)
+    raws = _render_meshes(who, [meshes[i] for i in idx], cams, res, shade, projection, nearest, background, near,
+                          perspective_correct, bindings, view or 0)
     for i, cam, (image, depth, face) in zip(idx, cams, raws):
         if _single_camera(cam):
             image, depth, face = (None if t is None else t[0] for t in (image, depth, face))
         out[i] = MeshRender(image, depth, face)
     return out
+
+
+def _render_meshes(who, live, cams, res, shade, projection, nearest, background, near, perspective_correct,
+                   bindings=None, view=0):
+    """The raw pictures (image, depth, face; each [n_views, ...]) of the meshes ``live`` (no None) under one camera set
+    each.  ``shade="netC"``: ``bindings``, one query binding of netC per mesh (``_bind_netC``; a slot passes those on
+    its own maps), colour the pictures per pixel through ``ops.render_netc_batch``."""
+    shaded = [_shade_attr(who, m, shade) for m in live]
+    scale, bias, lo, hi = shaded[0][1]
+    verts = [m.verts.contiguous() for m in live]
+    faces = [m.faces.contiguous() for m in live]
+    sizes = list(_shape_counts(list(zip(verts, faces))).unbind(0))
+    capacity = (max(v.shape[0] for v in verts), max(f.shape[0] for f in faces))
+    if shade == "netC":
+        return ops.render_netc_batch(who, verts, faces, sizes, cams, res,
+                                     lambda pts, counts: _counted_colours(bindings, pts, counts, view=view),
+                                     projection, nearest, background, capacity=capacity, near=near,
+                                     perspective_correct=perspective_correct)
+    attrs = None if shade is None else [ops._f32c(a) for a, _ in shaded]
+    return ops._mesh_render(who, verts, faces, sizes, attrs, cams, res, projection, nearest, False, scale, bias, lo, hi,
+                            background, None, capacity=capacity, near=near, perspective_correct=perspective_correct)
 
 
 @torch.no_grad()

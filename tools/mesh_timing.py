@@ -55,6 +55,15 @@ comparison is the ``smooth=None`` rows of the same run.
 
     python tools/mesh_timing.py --smooth [--passes 5] [--out profiles/mesh_smooth_timing.json]
 
+``--deferred`` measures pictures coloured per pixel (profiles/mesh_deferred_timing.json): 20-frame colour slots on
+the 257^3 body, in one session with alternating passes, (a) colours on the mesh and ``shade="colors"`` at 257^2 with 1
+view -- the per-vertex colour query -- against (b) ``"colors": False`` and ``shade="netC"`` -- netC at the covered pixels
+only -- at 257^2 with 1 view, at 257^2 with 4 views and at 1024^2 with 1 view, per-frame milliseconds of a submission
+(``pictures()`` included), with the covered pixels per picture beside the vertex count.  The cameras are turned off the
+axes.
+
+    python tools/mesh_timing.py --deferred [--passes 5] [--out profiles/mesh_deferred_timing.json]
+
 The protocol of tools/recon_views_timing.py: after a warm-up of all, the passes alternate; a pass is `meshes`
 meshes, wall clock around a final stream sync.  Prints (and writes) one JSON line: per way the median, minimum and
 maximum time per mesh (ms) over the passes.  The verdict fields restate what to check: (b) not slower than (a) by
@@ -94,14 +103,19 @@ def main():
     ap.add_argument("--smooth", action="store_true", help="the mesh chain at smooth = None / 2 / 10")
     ap.add_argument("--render", action="store_true", help="the mesh rasteriser against the visible-surface picture")
     ap.add_argument("--clip", action="store_true", help="with --render: the clipped form beside the unclipped call")
+    ap.add_argument("--deferred", action="store_true", help="slot pictures coloured per vertex against per pixel")
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "mesh_render_clip_timing.json" if a.render and a.clip else
                              "mesh_render_timing.json" if a.render else
+                             "mesh_deferred_timing.json" if a.deferred else
                              "mesh_smooth_timing.json" if a.smooth else
                              "mesh_simplify_timing.json" if a.simplify else
                              "keep_largest_timing.json" if a.clean else
                              "mesh_batch_timing.json" if a.batched else "mesh_timing.json")
+    if a.deferred:
+        write(a, slot_deferred(a))
+        return
     mlp = ops.PackedMLP.from_layers(DEV, syn.body_mlp("G", noise=0.05, seed=1), 1)
     fh = ops.pack_features(torch.from_numpy(syn.body_feat(256, 128, 128, 2))[None].to(DEV))
     cal = torch.from_numpy(orc.pifu_calib(*syn.scene_camera(30))).to(DEV)
@@ -416,8 +430,34 @@ def smooth(a, vol, netC, feat_C, calib, n=20):
     return out
 
 
+def slot_deferred(a, frames=20):
+    """The 20-frame colour slot with pictures: today's per-vertex colours against netC at the covered pixels, per-frame ms
+    of a submission (``pictures()`` included), and what each picture covers."""
+    cams = torch.cat([recon.pifu_calib(*syn.scene_camera(30 * k + 15), device="cpu") for k in range(4)])
+    mesh_c, mesh_n = {"normals": "accumulate", "colors": True}, {"normals": "accumulate", "colors": False}
+    rows = (("vertex_colours_257_views1", mesh_c, dict(views=1, res=257, shade="colors"), cams[:1]),
+            ("netC_257_views1", mesh_n, dict(views=1, res=257, shade="netC"), cams[:1]),
+            ("netC_257_views4", mesh_n, dict(views=4, res=257, shade="netC"), cams),
+            ("netC_1024_views1", mesh_n, dict(views=1, res=1024, shade="netC"), cams[:1]))
+    pipes, fn = _slot_pipes(frames, 1, rows)
+    out = {"frames_per_slot": frames, "unit": "ms per frame", "normals": "accumulate",
+           "cameras": "scene_camera(15 + 30 k): turned off the axes"}
+    out.update(alternate({name: fn(name) for name in pipes}, a.passes, frames))
+    out["covered_pixels_per_picture_frame0"], out["vertices_frame0"] = {}, {}
+    for name, p_ in pipes.items():
+        slot = p_.slots[0]
+        pic, m = slot.pictures()[0], slot.meshes()[0]
+        out["covered_pixels_per_picture_frame0"][name] = [int((f >= 0).sum().item()) for f in pic.face]
+        out["vertices_frame0"][name] = int(m.verts.shape[0])
+        p_.close()
+    base = out["vertex_colours_257_views1"]["median_ms"]
+    out["netC_257_views1_minus_vertex_colours_ms"] = round(out["netC_257_views1"]["median_ms"] - base, 4)
+    return out
+
+
 def _slot_pipes(frames, depth, meshes):
-    """FramePipelines of the bench's synthetic frames, one per (name, mesh option), and fn(name) -> a submission."""
+    """FramePipelines of the bench's synthetic frames, one per (name, mesh option[, pictures option, cameras]), and
+    fn(name) -> a submission."""
     from bench_common import B_MAX, B_MIN, RESOLUTIONS, build_netc, build_netg
     from monoport_amd import pipeline
     from monoport_amd.recon import pifu_calib
@@ -435,17 +475,19 @@ def _slot_pipes(frames, depth, meshes):
     hook.hwc = hook_hwc
     images = torch.stack([torch.from_numpy(syn.synthetic_image(f % 8)) for f in range(frames)]).to(dev)
     calibs = torch.cat([pifu_calib(*syn.scene_camera(3 * f), device=DEV) for f in range(frames)])
-    pipes = {}
-    for name, mesh in meshes:
+    pipes, cameras = {}, {}
+    for name, mesh, *pictures in meshes:
+        kw = dict(pictures=pictures[0]) if pictures else {}
+        cameras[name] = dict(cameras=pictures[1]) if pictures else {}
         pipes[name] = pipeline.FramePipeline(netg, dev, depth=depth, batch=frames, resolutions=RESOLUTIONS,
                                              b_min=B_MIN, b_max=B_MAX, feature_hook=hook, use_graph=True,
-                                             netC=netc, mesh=mesh)
+                                             netC=netc, mesh=mesh, **kw)
         pipes[name].prepare()
 
     def fn(name):
         def run():
-            for s in [pipes[name].submit(images, calibs) for _ in range(depth)]:
-                assert all(m is not None for m in s.meshes())
+            for s in [pipes[name].submit(images, calibs, **cameras[name]) for _ in range(depth)]:
+                assert all(m is not None for m in (s.pictures() if cameras[name] else s.meshes()))
         return run
     return pipes, fn
 
