@@ -82,7 +82,8 @@ def _project(p, calib, projection):
 
 def cpu_views(layers, f, p, calibs, projection, last_op, sample_outside=True):
     """torch-CPU restatement: per view project, grid_sample (zero padding), layers 0-2, means, layers 3-4, masks.
-    sample_outside=False: the plain single-view kernel's sampling instead (out-of-image views get zero features)."""
+    sample_outside=False: the plain single-view kernel's sampling instead (out-of-image views get zero features).
+    Runs at the precision of its inputs: float64 layers, maps, points and calibrations give the float64 model."""
     v_n = f.shape[0]
     feats, masks = [], []
     for v in range(v_n):
@@ -90,7 +91,8 @@ def cpu_views(layers, f, p, calibs, projection, last_op, sample_outside=True):
         s = F.grid_sample(torch.from_numpy(f[v])[None], xyz[:2].T[None, :, None], align_corners=True)[0, :, :, 0]
         if not sample_outside:
             s = s * ((xyz[0] >= -1) & (xyz[0] <= 1) & (xyz[1] >= -1) & (xyz[1] <= 1)).float()[None]
-        feats.append(torch.cat([s, xyz[2:3] * syn.Z_SCALE], 0))
+        # z_scale reaches the kernels and the oracle as a float32: the same value when the inputs are float64
+        feats.append(torch.cat([s, xyz[2:3] * float(np.float32(syn.Z_SCALE))], 0))
         masks.append(((xyz[0] >= -1) & (xyz[0] <= 1) & (xyz[1] >= -1) & (xyz[1] <= 1)).float())
     return mlp_views(layers, torch.stack(feats), last_op, masks)
 
@@ -108,7 +110,8 @@ def mlp_views(layers, feature, last_op, masks=None):
         if i == 2:
             y = y.view(-1, v_n, y.shape[1], y.shape[2]).mean(1)
             tmpy = feature.view(-1, v_n, feature.shape[1], feature.shape[2]).mean(1)
-    y = torch.sigmoid(y) if last_op == 1 else torch.tanh(y)
+    if last_op != 0:  # 0: none (SurfaceClassifier(last_op=None)), 1: sigmoid, 2: tanh
+        y = torch.sigmoid(y) if last_op == 1 else torch.tanh(y)
     if masks is None:
         return y
     return torch.stack([m[None] * y[0] for m in masks])
