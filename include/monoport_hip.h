@@ -814,6 +814,78 @@ int mp_picture_paint_batch(mp_ctx *ctx, int n_frames, const float *const *values
                            const int32_t *const *count, int64_t capacity, int64_t n_pixels, float scale, float bias,
                            float lo, float hi, float *const *image, mp_stream stream);
 
+/* ---- the scene behind the subject (RTL/scene.py, RTL/main.py: the textured floor and mask * render + (1 - mask) *
+ * background): a mip pyramid, a texture lookup per pixel and a composite by coverage or by depth ----------------------
+ * The floor goes through the rasteriser above with attr = (u, v, 0) per vertex and the paint (1, 0, -inf, inf): its
+ * image is then a UV picture.  The calls below turn it into the textured picture and put the subject's picture over
+ * it.  A frame's pictures are ONE flat array as mp_mesh_render_batch lays them out: L = n_views * H * W pixels.  All
+ * calls are pure functions of their inputs, defined bit for bit: every float operation below is ONE IEEE f32 +, - or *,
+ * in the order written, without FMA; there is no sqrt, log or division (scene.hip; no atomics, no scratch).
+ *   Pyramid.  A texture f32 [ht,wt,3] (ht, wt in 1..8192) has levels 0..levels-1, levels in 1..14 and no more than
+ *     reach 1 x 1 (1 + floor(log2(max(ht, wt)))).  Level 0 is the texture (h_0 = ht, w_0 = wt); h_l = max(1, h_{l-1}
+ *     >> 1), w_l likewise.  Texel (i, j, c) of level l is ((a + b) + (c' + d)) * 0.25f with a, b = level l-1 at row
+ *     min(2i, h-1), columns min(2j, w-1) and min(2j+1, w-1), and c', d the same columns of row min(2i+1, h-1) (h, w those
+ *     of level l-1).  The levels lie back to back, level l at float offset sum_{k<l} 3 h_k w_k, each [h_l,w_l,3].
+ *     mp_texture_pyramid_floats: the float count of all `levels` levels (host only, no context); 0 for sizes out of
+ *     range.  mp_texture_mips: tex -> pyramid, one launch per level (a set-up call); the two may not overlap.
+ *   mp_picture_texture.  uv f32 [L,3] (channels u, v, unused), face_id int32 [L], both as the rasteriser wrote them;
+ *     image f32 [L,3]; EVERY pixel of image is written.  With pixel p = (view, i, j), i along H:
+ *     Covered iff face_id >= 0 and |u| <= 65536 and |v| <= 65536 (a NaN and an infinity fail).  Any other pixel gets
+ *       `background` in all three channels.
+ *     Level.  S = u * (float)wt, T = v * (float)ht.  Along axis i: for each of (i+1, j) and (i-1, j) that lies in the
+ *       same view and is covered, dS = S' - S, dT = T' - T, d2 = (dS * dS) + (dT * dT); rho2_i = the smaller of the
+ *       available d2, or 0 with none (the smaller, so that a uv seam of a packed mesh does not force the coarsest level
+ *       along the seam).  rho2_j likewise with (i, j+1) and (i, j-1); rho2 = rho2_i > rho2_j ? rho2_i : rho2_j.
+ *       level = the number of l in 0..levels-2 with rho2 > 2^(2l+1): nearest-mip selection, level 1 from a step of
+ *       sqrt(2) texels per pixel on.
+ *     Lookup, bilinear in that level (h, w its size): s = u * (float)w - 0.5f, s0 = floorf(s), fs = s - s0, columns
+ *       x0 = (int)s0 and x1 = x0 + 1; t = v * (float)h - 0.5f, rows y0, y1 and ft likewise.  Each index k of n is
+ *       wrapped: MP_WRAP_REPEAT ((k % n) + n) % n, MP_WRAP_CLAMP min(max(k, 0), n - 1).  With cXY the texel at column
+ *       xX, row yY: value = (c00 * (1.0f - fs) + c10 * fs) * (1.0f - ft) + (c01 * (1.0f - fs) + c11 * fs) * ft.
+ *     Paint.  clamp(value * scale + bias, lo, hi) as mp_paint (o < lo ? lo : (o > hi ? hi : o)).
+ *     One launch, one thread per pixel: 16 B read (+ up to 4 neighbours, cached) and 12 B written per pixel, and twelve
+ *     texels per covered one.  image may not share a byte with uv, face_id or the pyramid (a pixel reads its
+ *     neighbours' uv): image == uv is refused.
+ *   mp_picture_composite.  Per pixel, from front (image f32 [L,3], depth f32 [L], face_id int32 [L]) and back (the
+ *     same three): a picture is covered where its face_id >= 0.  Front shows where it is covered and (back is
+ *     uncovered, or mode == MP_COMPOSITE_OVER, or back is not STRICTLY nearer: !(db < df) with MP_NEAREST_MIN_Z,
+ *     !(db > df) with MP_NEAREST_MAX_Z; a tie and a NaN go to front).  Else back shows where it is covered.  Outputs:
+ *     image f32 [L,3] and depth f32 [L] take the showing picture's values as their 32-bit patterns, `background` and
+ *     +0.0 where neither is covered; mask uint8 [L]: 0 = neither, 1 = back, 2 = front.  depth and mask may be NULL.
+ *     MP_COMPOSITE_OVER is the reference's mask composite (the subject always over the floor); MP_COMPOSITE_DEPTH lets
+ *     a part of the scene in front of the subject hide it.  image / depth may BE front's (or back's) image / depth of
+ *     the same frame -- the composite in place --, because a thread reads its own pixel before it writes it; any other
+ *     byte shared between an output and an input is refused.  One launch: 40 B read, 17 B written per pixel.
+ * MP_ERR_ARG: n_frames outside 1..mp_max_frames(); ht, wt or levels out of range; n_views < 1, h or w outside 1..4096,
+ * n_pixels < 1; an unknown wrap, mode or nearest; a NULL or not 4-byte aligned buffer of any frame (mask: any
+ * alignment); the aliasing above.  MP_ERR_UNSUPPORTED: L beyond 2^31 / 3.  Each refusal leaves an mp_last_error
+ * message and launches nothing.  Asynchronous, nothing synchronised, no scratch arena.  The per-frame calls are the
+ * batched ones with one frame; in the batched ones uv / face_id / image / front_* / back_* / depth / mask are HOST
+ * arrays of n_frames device pointers (one pyramid and one size for all), blockIdx.y is the frame: frame f's outputs
+ * equal the per-frame call's on frame f's inputs BIT FOR BIT.
+ * NOT built: trilinear and anisotropic filtering, alpha, shadows of the subject on the scene. */
+enum { MP_WRAP_REPEAT = 0, MP_WRAP_CLAMP = 1 };
+enum { MP_COMPOSITE_OVER = 0, MP_COMPOSITE_DEPTH = 1 };
+int64_t mp_texture_pyramid_floats(int ht, int wt, int levels);
+int mp_texture_mips(mp_ctx *ctx, const float *tex, int ht, int wt, int levels, float *pyramid, mp_stream stream);
+int mp_picture_texture(mp_ctx *ctx, const float *uv, const int32_t *face_id, int n_views, int h, int w,
+                       const float *pyramid, int ht, int wt, int levels, int wrap, float scale, float bias, float lo,
+                       float hi, float background, float *image, mp_stream stream);
+int mp_picture_texture_batch(mp_ctx *ctx, int n_frames, const float *const *uv, const int32_t *const *face_id,
+                             int n_views, int h, int w, const float *pyramid, int ht, int wt, int levels, int wrap,
+                             float scale, float bias, float lo, float hi, float background, float *const *image,
+                             mp_stream stream);
+int mp_picture_composite(mp_ctx *ctx, const float *front_image, const float *front_depth, const int32_t *front_face,
+                         const float *back_image, const float *back_depth, const int32_t *back_face, int64_t n_pixels,
+                         int mode, int nearest, float background, float *image, float *depth, uint8_t *mask,
+                         mp_stream stream);
+int mp_picture_composite_batch(mp_ctx *ctx, int n_frames, const float *const *front_image,
+                               const float *const *front_depth, const int32_t *const *front_face,
+                               const float *const *back_image, const float *const *back_depth,
+                               const int32_t *const *back_face, int64_t n_pixels, int mode, int nearest,
+                               float background, float *const *image, float *const *depth, uint8_t *const *mask,
+                               mp_stream stream);
+
 /* The largest connected body of an occupancy volume [R,R,R] (no counterpart in the reference; the clean-up in front
  * of marching cubes that drops floating blobs).
  *   Foreground: voxels with value > level (marching cubes' "inside"; a NaN and value == level are background).

@@ -94,6 +94,9 @@ NORMALS_REFERENCE, NORMALS_ACCUMULATE = 0, 1
 NEAREST_MAX_Z, NEAREST_MIN_Z = 0, 1
 # MP_RENDER_* flags of mp_mesh_render_clip (include/monoport_hip.h)
 RENDER_PERSPECTIVE_CORRECT = 1
+# MP_WRAP_* of mp_picture_texture and MP_COMPOSITE_* of mp_picture_composite (include/monoport_hip.h)
+WRAP_REPEAT, WRAP_CLAMP = 0, 1
+COMPOSITE_OVER, COMPOSITE_DEPTH = 0, 1
 # MP_CONN_* connectivities of mp_volume_keep_largest (include/monoport_hip.h)
 CONN_6, CONN_26 = 6, 26
 MAX_VIEWS = 8  # MP_MAX_VIEWS: views per mp_query_views / mp_mlp_forward_views call
@@ -207,6 +210,16 @@ SIGNATURES = {
     "mp_picture_paint": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp]),
     "mp_picture_paint_batch": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_f32, c_f32, c_f32, c_f32, c_vp,
                                        c_vp]),
+    "mp_texture_pyramid_floats": (c_i64, [c_int, c_int, c_int]),
+    "mp_texture_mips": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]),
+    "mp_picture_texture": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int, c_f32, c_f32,
+                                   c_f32, c_f32, c_f32, c_vp, c_vp]),
+    "mp_picture_texture_batch": (c_int, [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_int, c_int,
+                                         c_f32, c_f32, c_f32, c_f32, c_f32, c_vp, c_vp]),
+    "mp_picture_composite": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_f32, c_vp, c_vp,
+                                     c_vp, c_vp]),
+    "mp_picture_composite_batch": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_f32,
+                                           c_vp, c_vp, c_vp, c_vp]),
     "mp_volume_keep_largest": (c_int, [c_vp, c_vp, c_int, c_f32, c_int, c_f32, c_vp, c_vp, c_vp]),
     "mp_volume_keep_largest_batch": (c_int, [c_vp, c_int, c_vp, c_int, c_f32, c_int, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "mp_group_norm": (c_int, [c_vp, c_vp, c_int, c_int, c_i64, c_int, c_vp, c_vp, c_f32, c_int, c_vp,

@@ -629,6 +629,112 @@ static int picture_paint_checked(mp_ctx *ctx, const char *who, int n_frames, con
                                     (hipStream_t)stream);
 }
 
+// what the texture calls refuse alike: the caller holds the lock
+static int texture_sizes_checked(mp_ctx *ctx, const char *who, int ht, int wt, int levels) {
+  if (ht < 1 || ht > 8192 || wt < 1 || wt > 8192)
+    return fail(ctx, MP_ERR_ARG, "%s: texture size %d x %d outside 1..8192", who, ht, wt);
+  if (!texture_sizes_ok(ht, wt, levels))
+    return fail(ctx, MP_ERR_ARG, "%s: levels must be in 1..14 and no more than reach 1 x 1 from %d x %d, got %d", who,
+                ht, wt, levels);
+  return MP_OK;
+}
+
+static int texture_mips_checked(mp_ctx *ctx, const char *who, const float *tex, int ht, int wt, int levels,
+                                float *pyramid, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = texture_sizes_checked(ctx, who, ht, wt, levels);
+  if (rc != MP_OK) return rc;
+  if (!tex || !pyramid) return bad_argument(ctx, who);
+  if (((uintptr_t)tex | (uintptr_t)pyramid) & 3) return fail(ctx, MP_ERR_ARG, "%s: misaligned buffer", who);
+  if (ranges_overlap(tex, (size_t)ht * wt * 12, pyramid, (size_t)texture_pyramid_floats(ht, wt, levels) * 4))
+    return fail(ctx, MP_ERR_ARG, "%s: the pyramid aliases the texture", who);
+  DeviceGuard g(ctx->device);
+  return launch_texture_mips(ctx, tex, ht, wt, levels, pyramid, (hipStream_t)stream);
+}
+
+static int picture_texture_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *uv,
+                                   const int32_t *const *face_id, int n_views, int h, int w, const float *pyramid,
+                                   int ht, int wt, int levels, int wrap, float scale, float bias, float lo, float hi,
+                                   float background, float *const *image, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (n_views < 1 || h < 1 || h > 4096 || w < 1 || w > 4096)
+    return fail(ctx, MP_ERR_ARG, "%s: n_views >= 1 and an image size in 1..4096, got %d views of %d x %d", who, n_views,
+                h, w);
+  const long long n_pixels = (long long)n_views * h * w;
+  if (n_pixels > 0x7fffffffLL / 3)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: pictures beyond 2^31 / 3 pixels need 64-bit indices", who);
+  rc = texture_sizes_checked(ctx, who, ht, wt, levels);
+  if (rc != MP_OK) return rc;
+  if (wrap != MP_WRAP_REPEAT && wrap != MP_WRAP_CLAMP)
+    return fail(ctx, MP_ERR_ARG, "%s: wrap must be MP_WRAP_REPEAT / _CLAMP, got %d", who, wrap);
+  if (!uv || !face_id || !image || !pyramid) return bad_argument(ctx, who);
+  if ((uintptr_t)pyramid & 3) return fail(ctx, MP_ERR_ARG, "%s: misaligned pyramid", who);
+  rc = check_frames(ctx, who, n_frames, nullptr, uv, face_id, image);
+  if (rc != MP_OK) return rc;
+  // a pixel reads its neighbours' uv: the image may not be the UV picture, nor share a byte with any input
+  const size_t bytes = (size_t)n_pixels * 12;
+  const FrameSpans ins[2] = {{uv, bytes}, {face_id, (size_t)n_pixels * 4}};
+  const FrameSpans outs[1] = {{image, bytes}};
+  rc = check_no_alias(ctx, who, n_frames, outs, ins);
+  if (rc != MP_OK) return rc;
+  for (int f = 0; f < n_frames; ++f)
+    if (ranges_overlap(image[f], bytes, pyramid, (size_t)texture_pyramid_floats(ht, wt, levels) * 4))
+      return fail(ctx, MP_ERR_ARG, "%s: the image of frame %d aliases the pyramid", who, f);
+  DeviceGuard g(ctx->device);
+  return launch_picture_texture_batch(ctx, n_frames, uv, face_id, n_pixels, h, w, pyramid, ht, wt, levels, wrap, scale,
+                                      bias, lo, hi, background, image, (hipStream_t)stream);
+}
+
+static int picture_composite_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *front_image,
+                                     const float *const *front_depth, const int32_t *const *front_face,
+                                     const float *const *back_image, const float *const *back_depth,
+                                     const int32_t *const *back_face, int64_t n_pixels, int mode, int nearest,
+                                     float background, float *const *image, float *const *depth, uint8_t *const *mask,
+                                     mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (n_pixels < 1) return fail(ctx, MP_ERR_ARG, "%s: n_pixels must be >= 1, got %lld", who, (long long)n_pixels);
+  if (n_pixels > 0x7fffffffLL / 3)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: pictures beyond 2^31 / 3 pixels need 64-bit indices", who);
+  if (mode != MP_COMPOSITE_OVER && mode != MP_COMPOSITE_DEPTH)
+    return fail(ctx, MP_ERR_ARG, "%s: mode must be MP_COMPOSITE_OVER / _DEPTH, got %d", who, mode);
+  if (nearest != MP_NEAREST_MAX_Z && nearest != MP_NEAREST_MIN_Z)
+    return fail(ctx, MP_ERR_ARG, "%s: nearest must be MP_NEAREST_MAX_Z / _MIN_Z, got %d", who, nearest);
+  if (!front_image || !front_depth || !front_face || !back_image || !back_depth || !back_face || !image)
+    return bad_argument(ctx, who);
+  rc = check_frames(ctx, who, n_frames, nullptr, front_image, front_depth, front_face, back_image, back_depth,
+                    back_face, image, depth);
+  if (rc != MP_OK) return rc;
+  if (mask)  // bytes: no alignment asked
+    for (int f = 0; f < n_frames; ++f)
+      if (!mask[f]) return fail(ctx, MP_ERR_ARG, "%s: null buffer for frame %d", who, f);
+  // an output may BE an input of its own kind and frame (a thread reads its pixel before it writes it); any other
+  // shared byte is refused
+  const size_t px = (size_t)n_pixels;
+  const FrameSpans ins[6] = {{front_image, px * 12}, {back_image, px * 12}, {front_depth, px * 4},
+                             {back_depth, px * 4},   {front_face, px * 4},  {back_face, px * 4}};
+  const FrameSpans outs[3] = {{image, px * 12}, {depth, px * 4}, {mask, px}};
+  for (int f = 0; f < n_frames; ++f)
+    for (int i = 0; i < n_frames; ++i)
+      for (int o = 0; o < 3; ++o)
+        for (int k = 0; k < 6; ++k) {
+          if (!ranges_overlap(outs[o].of(f), outs[o].bytes, ins[k].of(i), ins[k].bytes)) continue;
+          const bool same_kind = (o == 0 && k < 2) || (o == 1 && (k == 2 || k == 3));
+          if (!(same_kind && f == i && outs[o].of(f) == ins[k].of(i)))
+            return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases an input of frame %d", who, f, i);
+        }
+  DeviceGuard g(ctx->device);
+  return launch_picture_composite_batch(ctx, n_frames, front_image, front_depth, front_face, back_image, back_depth,
+                                        back_face, n_pixels, mode, nearest, background, image, depth, mask,
+                                        (hipStream_t)stream);
+}
+
 static int keep_largest_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *volume, int r,
                                 float level, int connectivity, float fill, float *const *out, int32_t *const *stats,
                                 const int32_t *const *gate, mp_stream stream) {
@@ -1696,6 +1802,49 @@ int mp_picture_paint_batch(mp_ctx *ctx, int n_frames, const float *const *values
                            float lo, float hi, float *const *image, mp_stream stream) {
   return picture_paint_checked(ctx, "mp_picture_paint_batch", n_frames, values, pixels, count, capacity, n_pixels, scale,
                                bias, lo, hi, image, stream);
+}
+
+int64_t mp_texture_pyramid_floats(int ht, int wt, int levels) {
+  return texture_sizes_ok(ht, wt, levels) ? (int64_t)texture_pyramid_floats(ht, wt, levels) : 0;
+}
+
+int mp_texture_mips(mp_ctx *ctx, const float *tex, int ht, int wt, int levels, float *pyramid, mp_stream stream) {
+  return texture_mips_checked(ctx, "mp_texture_mips", tex, ht, wt, levels, pyramid, stream);
+}
+
+int mp_picture_texture(mp_ctx *ctx, const float *uv, const int32_t *face_id, int n_views, int h, int w,
+                       const float *pyramid, int ht, int wt, int levels, int wrap, float scale, float bias, float lo,
+                       float hi, float background, float *image, mp_stream stream) {
+  return picture_texture_checked(ctx, "mp_picture_texture", 1, &uv, &face_id, n_views, h, w, pyramid, ht, wt, levels,
+                                 wrap, scale, bias, lo, hi, background, &image, stream);
+}
+
+int mp_picture_texture_batch(mp_ctx *ctx, int n_frames, const float *const *uv, const int32_t *const *face_id,
+                             int n_views, int h, int w, const float *pyramid, int ht, int wt, int levels, int wrap,
+                             float scale, float bias, float lo, float hi, float background, float *const *image,
+                             mp_stream stream) {
+  return picture_texture_checked(ctx, "mp_picture_texture_batch", n_frames, uv, face_id, n_views, h, w, pyramid, ht, wt,
+                                 levels, wrap, scale, bias, lo, hi, background, image, stream);
+}
+
+int mp_picture_composite(mp_ctx *ctx, const float *front_image, const float *front_depth, const int32_t *front_face,
+                         const float *back_image, const float *back_depth, const int32_t *back_face, int64_t n_pixels,
+                         int mode, int nearest, float background, float *image, float *depth, uint8_t *mask,
+                         mp_stream stream) {
+  return picture_composite_checked(ctx, "mp_picture_composite", 1, &front_image, &front_depth, &front_face, &back_image,
+                                   &back_depth, &back_face, n_pixels, mode, nearest, background, &image,
+                                   depth ? &depth : nullptr, mask ? &mask : nullptr, stream);
+}
+
+int mp_picture_composite_batch(mp_ctx *ctx, int n_frames, const float *const *front_image,
+                               const float *const *front_depth, const int32_t *const *front_face,
+                               const float *const *back_image, const float *const *back_depth,
+                               const int32_t *const *back_face, int64_t n_pixels, int mode, int nearest,
+                               float background, float *const *image, float *const *depth, uint8_t *const *mask,
+                               mp_stream stream) {
+  return picture_composite_checked(ctx, "mp_picture_composite_batch", n_frames, front_image, front_depth, front_face,
+                                   back_image, back_depth, back_face, n_pixels, mode, nearest, background, image, depth,
+                                   mask, stream);
 }
 
 int mp_volume_keep_largest(mp_ctx *ctx, const float *volume, int r, float level, int connectivity, float fill,

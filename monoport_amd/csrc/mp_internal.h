@@ -469,6 +469,22 @@ int launch_picture_points_batch(mp_ctx *ctx, void *scratch, int n_frames, const 
 int launch_picture_paint_batch(mp_ctx *ctx, int n_frames, const float *const *values, const int32_t *const *pixels,
                                const int32_t *const *count, long long capacity, long long n_pixels, float scale,
                                float bias, float lo, float hi, float *const *image, hipStream_t st);
+// scene.hip: the mip pyramid of a texture [ht,wt,3] (one launch per level), its lookup per pixel of n_frames UV
+// pictures of n_pixels = n_views * h * w each, and the composite of two pictures per frame (depth / mask: nullptr or
+// n_frames entries).  No scratch.  texture_sizes_ok: ht, wt in 1..8192, levels in 1..14 and no more than reach 1 x 1
+bool texture_sizes_ok(int ht, int wt, int levels);
+long long texture_pyramid_floats(int ht, int wt, int levels);
+int launch_texture_mips(mp_ctx *ctx, const float *tex, int ht, int wt, int levels, float *pyramid, hipStream_t st);
+int launch_picture_texture_batch(mp_ctx *ctx, int n_frames, const float *const *uv, const int32_t *const *face_id,
+                                 long long n_pixels, int h, int w, const float *pyramid, int ht, int wt, int levels,
+                                 int wrap, float scale, float bias, float lo, float hi, float background,
+                                 float *const *image, hipStream_t st);
+int launch_picture_composite_batch(mp_ctx *ctx, int n_frames, const float *const *front_image,
+                                   const float *const *front_depth, const int32_t *const *front_face,
+                                   const float *const *back_image, const float *const *back_depth,
+                                   const int32_t *const *back_face, long long n_pixels, int mode, int nearest,
+                                   float background, float *const *image, float *const *depth, uint8_t *const *mask,
+                                   hipStream_t st);
 
 // conv3x3.hip
 int launch_conv3x3_pack(mp_ctx *ctx, const float *w, int cout, int cin, float *wp, hipStream_t st);

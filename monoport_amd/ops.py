@@ -1782,6 +1782,174 @@ def render_netc_batch(who, verts, faces, counts, calibs, res, query, projection=
     return raws
 
 
+# MP_WRAP_* / MP_COMPOSITE_* (include/monoport_hip.h)
+WRAP_MODES = {"repeat": _lib.WRAP_REPEAT, "clamp": _lib.WRAP_CLAMP}
+COMPOSITE_MODES = {"over": _lib.COMPOSITE_OVER, "depth": _lib.COMPOSITE_DEPTH}
+TEXTURE_MAX_SIZE = 8192  # mp_texture_mips: ht, wt in 1..8192
+TEXTURE_MAX_LEVELS = 14
+
+
+def _named_mode(who, what, table, mode):
+    if isinstance(mode, str) and mode in table:
+        return table[mode]
+    if not isinstance(mode, (str, bool)) and isinstance(mode, (int, np.integer)) and int(mode) in table.values():
+        return int(mode)
+    raise ValueError("%s: %s must be one of %s, got %r" % (who, what, sorted(table), mode))
+
+
+def texture_levels(ht, wt):
+    """The levels of the full mip chain of a ht x wt texture, down to 1 x 1."""
+    return max(int(ht), int(wt)).bit_length()
+
+
+def texture_pyramid_floats(ht, wt, levels=None):
+    """mp_texture_pyramid_floats: the float count of a ht x wt texture's pyramid of ``levels`` levels (None: the full
+    chain).  Host only."""
+    ht, wt = int(ht), int(wt)
+    if not (1 <= ht <= TEXTURE_MAX_SIZE and 1 <= wt <= TEXTURE_MAX_SIZE):
+        raise ValueError("texture size %d x %d outside 1..%d" % (ht, wt, TEXTURE_MAX_SIZE))
+    levels = texture_levels(ht, wt) if levels is None else int(levels)
+    if not 1 <= levels <= min(TEXTURE_MAX_LEVELS, texture_levels(ht, wt)):
+        raise ValueError("levels must be in 1..%d for a %d x %d texture, got %d"
+                         % (min(TEXTURE_MAX_LEVELS, texture_levels(ht, wt)), ht, wt, levels))
+    return int(_lib.load().mp_texture_pyramid_floats(ht, wt, levels))
+
+
+def texture_mips(tex, levels=None, out=None):
+    """mp_texture_mips: the mip pyramid of ``tex`` (float32 [Ht,Wt,3] on the device) as one flat float32 tensor, level 0
+    (a copy of ``tex``) first, each level the 2x2 box of the one below, bit for bit as include/monoport_hip.h defines
+    it.  ``levels``: None = the full chain down to 1 x 1.  Returns (pyramid, levels).  A set-up call: one launch per
+    level.  No host sync."""
+    if tex.dtype != torch.float32 or tex.dim() != 3 or tex.shape[2] != 3 or not tex.is_contiguous():
+        raise ValueError("texture_mips: tex must be a contiguous float32 [Ht,Wt,3] tensor")
+    ht, wt = int(tex.shape[0]), int(tex.shape[1])
+    levels = texture_levels(ht, wt) if levels is None else int(levels)
+    n = texture_pyramid_floats(ht, wt, levels)
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=tex.device)
+    elif out.dtype != torch.float32 or out.numel() != n or out.device != tex.device or not out.is_contiguous():
+        raise ValueError("texture_mips: out must be a contiguous float32 tensor of %d elements on %s" % (n, tex.device))
+    ctx = get_context(tex.device)
+    ctx.check(ctx.lib.mp_texture_mips(ctx.handle, _ptr(tex), ht, wt, levels, _ptr(out), _stream(tex)), "mp_texture_mips")
+    return out, levels
+
+
+def _flat_pictures(who, what, rows, n, dtype, per_pixel, npix, dev):
+    rows = list(rows)
+    if len(rows) != n or any(r.dtype != dtype or r.numel() != per_pixel * npix or r.device != dev
+                             or not r.is_contiguous() for r in rows):
+        raise ValueError("%s: %s must be %d contiguous %s pictures of %d pixels on %s"
+                         % (who, what, n, str(dtype).replace("torch.", ""), npix, dev))
+    return rows
+
+
+def picture_texture_batch(uvs, face_ids, pyramid, tex_size, levels, wrap="repeat", scale=1.0, bias=0.0, lo=-math.inf,
+                          hi=math.inf, background=1.0, out=None, who="picture_texture_batch"):
+    """mp_picture_texture_batch: per frame the textured picture of a UV picture.  ``uvs``: float32 [n_views,H,W,3] per
+    frame (channels u, v, unused: the rasteriser's image for ``attr = (u, v, 0)``), ``face_ids`` its int32
+    [n_views,H,W]; ``pyramid``, ``levels`` as ``texture_mips`` returns them for a texture of ``tex_size`` = (Ht, Wt).
+    A covered pixel (face id >= 0, finite uv within +-65536) takes the nearest mip level for its uv steps to its
+    neighbours, a bilinear lookup there (``wrap``: "repeat" or "clamp") and clamp(value * scale + bias, lo, hi); every
+    other pixel takes ``background``.  Defined bit for bit in include/monoport_hip.h.  ``out``: the images to write
+    (not the UV pictures: a pixel reads its neighbours); None: fresh ones.  One launch per MAX_FRAMES frames; no host
+    sync.  Returns the list of images."""
+    n = len(uvs)
+    if n == 0 or uvs[0].dim() != 4 or uvs[0].shape[3] != 3:
+        raise ValueError("%s: at least one UV picture [n_views,H,W,3]" % who)
+    nv, h, w = (int(s) for s in uvs[0].shape[:3])
+    dev, npix = uvs[0].device, nv * h * w
+    uvs = _flat_pictures(who, "uvs", uvs, n, torch.float32, 3, npix, dev)
+    face_ids = _flat_pictures(who, "face_ids", face_ids, n, torch.int32, 1, npix, dev)
+    ht, wt = int(tex_size[0]), int(tex_size[1])
+    if (pyramid.dtype != torch.float32 or pyramid.device != dev or not pyramid.is_contiguous()
+            or pyramid.numel() != texture_pyramid_floats(ht, wt, levels)):
+        raise ValueError("%s: pyramid must be the contiguous float32 pyramid of a %d x %d texture with %d levels on %s"
+                         % (who, ht, wt, levels, dev))
+    wrap = _named_mode(who, "wrap", WRAP_MODES, wrap)
+    if out is None:
+        out = torch.empty((n, nv, h, w, 3), dtype=torch.float32, device=dev).unbind(0)
+    else:
+        out = _flat_pictures(who, "out", out, n, torch.float32, 3, npix, dev)
+    ctx = get_context(dev)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_picture_texture_batch(
+            ctx.handle, f1 - f0, _ptr_array(uvs[f0:f1]), _ptr_array(face_ids[f0:f1]), nv, h, w, _ptr(pyramid), ht, wt,
+            int(levels), wrap, float(scale), float(bias), float(lo), float(hi), float(background),
+            _ptr_array(out[f0:f1]), _stream(uvs[0])), "mp_picture_texture_batch")
+    return list(out)
+
+
+def picture_composite_batch(fronts, backs, mode="depth", nearest="max", background=1.0, out=None,
+                            who="picture_composite_batch"):
+    """mp_picture_composite_batch: per frame the composite of ``fronts[f]`` over ``backs[f]``, each (image float32
+    [...,3], depth float32 [...], face int32 [...]) of one size.  The front shows where it is covered (face >= 0) and
+    the back is not, or ``mode`` is "over", or -- ``mode="depth"`` -- the back is not strictly nearer under ``nearest``
+    ("max" / "min", as the renders take it); else the back shows where it is covered; else ``background`` and depth
+    +0.0.  ``out``: (images, depths or None, masks or None) to write; the images / depths may be the fronts' own (the
+    composite in place).  None: fresh ones.  Returns per frame (image, depth, mask uint8: 0 neither, 1 back, 2 front).
+    One launch per MAX_FRAMES frames; no host sync."""
+    n = len(fronts)
+    if n == 0 or len(backs) != n:
+        raise ValueError("%s: %d front pictures, %d back pictures" % (who, n, len(backs)))
+    dev, npix = fronts[0][2].device, fronts[0][2].numel()
+    if npix < 1:
+        raise ValueError("%s: at least one pixel" % who)
+    cols = []
+    for what, pics in (("fronts", fronts), ("backs", backs)):
+        if any(p is None or len(p) < 3 or p[0] is None for p in pics):
+            raise ValueError("%s: every picture of %s needs an image, a depth and face ids" % (who, what))
+        cols.append(_flat_pictures(who, what + " (image)", [p[0] for p in pics], n, torch.float32, 3, npix, dev))
+        cols.append(_flat_pictures(who, what + " (depth)", [p[1] for p in pics], n, torch.float32, 1, npix, dev))
+        cols.append(_flat_pictures(who, what + " (face)", [p[2] for p in pics], n, torch.int32, 1, npix, dev))
+    mode = _named_mode(who, "composite", COMPOSITE_MODES, mode)
+    near_mode = _nearest(nearest)
+    shape = tuple(fronts[0][2].shape)
+    if out is None:
+        image = torch.empty((n,) + shape + (3,), dtype=torch.float32, device=dev).unbind(0)
+        depth = torch.empty((n,) + shape, dtype=torch.float32, device=dev).unbind(0)
+        mask = torch.empty((n,) + shape, dtype=torch.uint8, device=dev).unbind(0)
+    else:
+        image = _flat_pictures(who, "out[0] (image)", out[0], n, torch.float32, 3, npix, dev)
+        depth = None if out[1] is None else _flat_pictures(who, "out[1] (depth)", out[1], n, torch.float32, 1, npix, dev)
+        mask = None if out[2] is None else _flat_pictures(who, "out[2] (mask)", out[2], n, torch.uint8, 1, npix, dev)
+    ctx = get_context(dev)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_picture_composite_batch(
+            ctx.handle, f1 - f0, *[_ptr_array(c[f0:f1]) for c in cols], npix, mode, near_mode, float(background),
+            _ptr_array(image[f0:f1]), None if depth is None else _ptr_array(depth[f0:f1]),
+            None if mask is None else _ptr_array(mask[f0:f1]), _stream(fronts[0][2])), "mp_picture_composite_batch")
+    return [(image[f], None if depth is None else depth[f], None if mask is None else mask[f]) for f in range(n)]
+
+
+def render_scene_batch(who, scene, calibs, res, projection="orthogonal", nearest="max", near=None,
+                       perspective_correct=False, background=1.0, out=None, uv=None):
+    """The textured pictures of ``scene`` (a ``recon.Scene``: verts, faces, counts, attr = (u, v, 0) per vertex, pyramid,
+    tex_size, levels, wrap) under one camera set per frame (``calibs``: a list, all of one n_views), no host value in
+    between: (1) the rasteriser with the scene's tensors repeated per frame and its uv as the attribute, under the
+    pictures' own camera, ``near`` and ``perspective_correct``, into a UV picture; (2) ``picture_texture_batch`` into
+    the image.  Returns what ``_mesh_render`` does: per frame (image [n_views,H,W,3], depth, face).  ``out``: (image,
+    depth, face) buffers; ``uv``: the UV pictures' buffers [n,n_views,H,W,3] (scratch of the call)."""
+    n = len(calibs)
+    if n == 0:
+        raise ValueError("%s: at least one camera set" % who)
+    if out is None:
+        if uv is not None:
+            raise ValueError("%s: uv= buffers go with out=" % who)
+    else:
+        if any(o is None for o in out):
+            raise ValueError("%s: a scene picture has an image, a depth and face ids" % who)
+        if uv is None:
+            uv = [torch.empty_like(o) for o in out[0]]
+    raws = _mesh_render(who, [scene.verts] * n, [scene.faces] * n, [scene.counts] * n, [scene.attr] * n, list(calibs),
+                        res, projection, nearest, False, 1.0, 0.0, -math.inf, math.inf, background,
+                        None if out is None else (uv, out[1], out[2]), near=near,
+                        perspective_correct=perspective_correct)
+    images =picture_texture_batch([r[0] for r in raws], [r[2] for r in raws], scene.pyramid, scene.tex_size,
+                                   scene.levels, scene.wrap, background=background,
+                                   out=None if out is None else out[0], who=who)
+    return [(im, r[1], r[2]) for im, r in zip(images, raws)]
+
+
 # MP_CONN_* (include/monoport_hip.h): face neighbours / face, edge and corner neighbours
 CONNECTIVITIES = (_lib.CONN_6, _lib.CONN_26)
 

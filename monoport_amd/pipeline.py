@@ -52,10 +52,12 @@ MAX_RECON_BATCH = ops.MAX_FRAMES  # kMaxFrames of the C-ABI (include/monoport_hi
 _mb = os.environ.get("MONOPORT_MESH_BATCH", "on")
 MESH_BATCH = 1 if _mb == "off" else min(int(_mb) if _mb.isdigit() and int(_mb) > 0 else MAX_RECON_BATCH, MAX_RECON_BATCH)
 MESH_KEYS = ("normals", "level", "colors", "clean", "simplify", "smooth")
-PICTURE_KEYS = ("views", "res", "shade", "projection", "nearest", "near", "perspective_correct", "background")
-PictureOptions = collections.namedtuple("PictureOptions", PICTURE_KEYS)
+PICTURE_KEYS = ("views", "res", "shade", "projection", "nearest", "near", "perspective_correct", "background", "scene",
+                "composite")
+PictureOptions = collections.namedtuple("PictureOptions", PICTURE_KEYS, defaults=(None, "depth"))
 PictureOptions.__doc__ = """What a slot's free-viewpoint pictures are asked for, validated by ``_picture_options``: the
-cameras per frame, the size (H, W), and the arguments of ``recon.render_mesh``."""
+cameras per frame, the size (H, W), the arguments of ``recon.render_mesh``, and the ``recon.Scene`` behind the subject
+(None: none) with the ``composite`` mode ("depth" or "over") that puts the subject's picture over it."""
 
 
 def _mesh_options(mesh, balance, has_netc):
@@ -107,8 +109,17 @@ def _picture_options(pictures, mesh, has_netc=False):
     ops._projection(projection), ops._nearest(nearest)
     near, correct = pictures.get("near"), bool(pictures.get("perspective_correct", False))
     ops._render_clip(who, projection, near, correct)
+    scene, composite = pictures.get("scene"), pictures.get("composite", "depth")
+    if scene is not None:
+        from .recon import Scene
+        if not isinstance(scene, Scene):
+            raise ValueError("%s: scene must be a recon.Scene, got %r" % (who, type(scene).__name__))
+        if shade is None:
+            raise ValueError("%s: a scene is composited with the subject's image; shade=None renders none" % who)
+    if not isinstance(composite, str) or composite not in ops.COMPOSITE_MODES:
+        raise ValueError("%s: composite must be one of %s, got %r" % (who, sorted(ops.COMPOSITE_MODES), composite))
     return PictureOptions(int(views), res, shade, projection, nearest, None if near is None else float(near), correct,
-                          float(pictures.get("background", 1.0)))
+                          float(pictures.get("background", 1.0)), scene, composite)
 
 
 class FrameSlot:
@@ -150,7 +161,14 @@ class FrameSlot:
         colours -- with ``mesh={"colors": False}`` the per-vertex colour query is never enqueued, which is the saving --
         and the slot then also owns, per frame of L = views * H * W pixels, the static lists of the covered pixels
         (points [3,L], pixels [L], predictions [3,L], count [2]: 28 bytes per pixel); ``pictures_image`` holds the
-        surface positions first and the colours in the end."""
+        surface positions first and the colours in the end.  ``scene`` (a ``recon.Scene``; default None: nothing is
+        allocated or enqueued for it) puts a textured scene behind the subject: behind the subject's picture the slot
+        renders the scene under the same cameras into static ``scene_uv`` / ``scene_image`` / ``scene_depth`` /
+        ``scene_face`` buffers (``ops.render_scene_batch``) and composites in place into ``pictures_image`` /
+        ``pictures_depth`` (``composite``: "depth", the default, or "over"; ``ops.picture_composite_batch``), filling the
+        static ``pictures_mask`` [batch,views,H,W] uint8 (0 neither, 1 scene, 2 subject), with no host value in
+        between; ``pictures()`` then returns ``recon.ScenePicture``s, the bare scene for an empty frame.  It needs a
+        ``shade``, and runs behind the paint of ``shade="netC"`` as behind any other."""
         self.views = self._head_views(netG, netC, mesh)  # images per frame; refuses what the slot class does not run
         # both option records are validated before anything is allocated
         self.mesh = None if mesh is None else _mesh_options(mesh, float(balance), netC is not None)
@@ -234,7 +252,7 @@ class FrameSlot:
                 self.mesh_buffers["smooth_verts"] = torch.empty((b, cap_v, 3), dtype=torch.float32, device=dev)
             self._mesh_chains = [None] * b
             self._reran = []  # frames whose chain ``meshes()`` made again with exact capacities
-        self.pictures_image = self.pictures_depth = self.pictures_face = None
+        self.pictures_image = self.pictures_depth = self.pictures_face = self.pictures_mask = None
         if self.picture_options is not None:
             po = self.picture_options
             if po.shade is not None:
@@ -247,6 +265,13 @@ class FrameSlot:
                                       "pixels": torch.zeros((b, n_pix), dtype=torch.int32, device=dev),
                                       "preds": torch.zeros((b, 3, n_pix), dtype=torch.float32, device=dev),
                                       "count": torch.zeros((b, 2), dtype=torch.int32, device=dev)}
+            if po.scene is not None:  # the scene's own pictures (44 bytes per pixel) and the composite's mask
+                shape = (b, po.views) + po.res
+                self.scene_uv = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
+                self.scene_image = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
+                self.scene_depth = torch.empty(shape, dtype=torch.float32, device=dev)
+                self.scene_face = torch.empty(shape, dtype=torch.int32, device=dev)
+                self.pictures_mask = torch.empty(shape, dtype=torch.uint8, device=dev)
             # the cameras of the current submission, on the host [batch,views,3,4]; the identity until the first one
             self._cameras = np.tile(np.eye(4, dtype=np.float32)[:3], (b, po.views, 1, 1))
 
@@ -392,7 +417,22 @@ class FrameSlot:
     def _render_pictures(self, n):
         """The pictures of the slot's n frames under their ``views`` cameras each, from the mesh buffers the chain has
         just filled and its device counts: one set of launches per ops.MAX_FRAMES pictures, no host value in between.
-        A gated-off frame's counts are (0, 0): pure background."""
+        A gated-off frame's counts are (0, 0): pure background.  With a ``scene``: its textured picture under the same
+        cameras, and the composite in place, follow on the same stream."""
+        self._render_subjects(n)
+        po = self.picture_options
+        if po.scene is not None:  # the scene under the same cameras, then the composite in place
+            backs = ops.render_scene_batch("FrameSlot", po.scene, list(self._cameras[:n]), po.res, po.projection,
+                                           po.nearest, po.near, po.perspective_correct, po.background,
+                                           out=(self.scene_image[:n], self.scene_depth[:n], self.scene_face[:n]),
+                                           uv=self.scene_uv[:n])
+            fronts = list(zip(self.pictures_image[:n], self.pictures_depth[:n], self.pictures_face[:n]))
+            ops.picture_composite_batch(fronts, backs, po.composite, po.nearest, po.background,
+                                        out=(self.pictures_image[:n], self.pictures_depth[:n], self.pictures_mask[:n]),
+                                        who="FrameSlot")
+
+    def _render_subjects(self, n):
+        """The pictures of the n frames' meshes alone, into ``pictures_image`` / ``pictures_depth`` / ``pictures_face``."""
         po = self.picture_options
         chains = self._mesh_chains[:n]
         if po.shade == "netC":  # positions -> covered pixels -> netC at them -> colours, behind the mesh chain
@@ -425,14 +465,19 @@ class FrameSlot:
         tensors: the bits the slot's own launch would have given at a sufficient capacity, except with
         ``shade="colors"``, where ``render_mesh`` interpolates the Mesh's finished colours and the slot netC's raw
         predictions (the same picture, not the same last bits); with ``shade="netC"`` they are the same bits again,
-        because both paths query netC at the same points.  No slot has overflowed 12 r^2 / 24 r^2 so far."""
+        because both paths query netC at the same points.  No slot has overflowed 12 r^2 / 24 r^2 so far.  With a
+        ``scene`` every entry is a ``recon.ScenePicture`` (image, depth, face, mask) of the subject composited over the
+        scene -- the bare scene where ``meshes()`` gives None --, and a re-rendered frame is composited again over the
+        slot's own picture of the scene."""
         if self.picture_options is None:
             raise RuntimeError("FrameSlot.pictures(): the slot was made without pictures=...")
         from .recon import MeshRender, _render_meshes, render_mesh
         po = self.picture_options
         out = []
         for b, mesh in enumerate(self.meshes()):
-            if mesh is None:
+            if po.scene is not None:
+                out.append(self._scene_picture(b, mesh))
+            elif mesh is None:
                 out.append(None)
             elif b in self._reran and po.shade == "netC":  # recon.render_mesh(shade="netC") on the slot's own maps
                 out.append(MeshRender(*_render_meshes(
@@ -445,6 +490,20 @@ class FrameSlot:
                 out.append(MeshRender(None if self.pictures_image is None else self.pictures_image[b],
                                       self.pictures_depth[b], self.pictures_face[b]))
         return out
+
+    def _scene_picture(self, b, mesh):
+        """Frame b's ``recon.ScenePicture``: views of the slot's buffers, or -- for a frame whose mesh ``meshes()`` made
+        again -- the re-rendered subject composited over the slot's own picture of the scene, into fresh tensors."""
+        from .recon import ScenePicture, _render_meshes, composite
+        po = self.picture_options
+        if mesh is None or b not in self._reran:
+            return ScenePicture(self.pictures_image[b], self.pictures_depth[b], self.pictures_face[b],
+                                self.pictures_mask[b])
+        bindings = self._colour_bindings(b, b + 1) if po.shade == "netC" else None
+        front = _render_meshes("FrameSlot.pictures", [mesh], [self._cameras[b]], po.res, po.shade, po.projection,
+                               po.nearest, po.background, po.near, po.perspective_correct, bindings, self.view)[0]
+        return composite(front, (self.scene_image[b], self.scene_depth[b], self.scene_face[b]), po.composite,
+                         po.nearest, po.background)
 
     def _slot_cameras(self, cameras, n):
         """``submit``'s cameras ([n,views,>=3,4], or [views,>=3,4] / [>=3,4] shared by all frames; tensor or array)

@@ -590,6 +590,142 @@ def _render_meshes(who, live, cams, res, shade, projection, nearest, background,
                             background, None, capacity=capacity, near=near, perspective_correct=perspective_correct)
 
 
+ScenePicture = collections.namedtuple("ScenePicture", ["image", "depth", "face", "mask"])
+ScenePicture.__doc__ = """A picture of ``composite``: image [H,W,3] f32 and depth [H,W] f32 of whichever of the two
+pictures shows at a pixel (``background`` and +0.0 where neither does), face [H,W] int32 = the FRONT picture's face ids
+(-1 wherever the front is not covered, also where it is hidden), mask [H,W] uint8 = 0 neither, 1 back (the scene), 2
+front (the subject); with a set of cameras each has a leading [n_views]."""
+
+
+class Scene:
+    """A textured triangle mesh behind the subject, on the device (RTL/scene.py's floor): ``verts`` [V,3] f32, ``faces``
+    [F,3] int, ``uv`` [V,2] f32 per vertex, ``texture`` [Ht,Wt,3] -- uint8 (divided by 255 into f32) or f32; tensors or
+    arrays.  ``wrap``: "repeat" or "clamp".  ``flip_v`` (the default): the texture's rows are flipped once at upload,
+    as the reference's ``Render.set_texture`` does, so OBJ / GL uv (v = 0 at the bottom of the picture file) need no
+    change; without it v = 0 is row 0.  The mip pyramid is built once here (``ops.texture_mips``; ``levels`` None = the
+    full chain).  Holds ``verts``, ``faces``, ``counts`` (int32 [2] on the device), ``attr`` [V,3] = (u, v, 0),
+    ``pyramid``, ``tex_size`` (Ht, Wt), ``levels``, ``wrap``."""
+
+    def __init__(self, verts, faces, uv, texture, wrap="repeat", flip_v=True, levels=None, device="cuda"):
+        dev = torch.device(device)
+        ops._named_mode("Scene", "wrap", ops.WRAP_MODES, wrap)
+        verts = torch.as_tensor(np.asarray(verts.detach().cpu()) if torch.is_tensor(verts) else np.asarray(verts))
+        faces = torch.as_tensor(np.asarray(faces.detach().cpu()) if torch.is_tensor(faces) else np.asarray(faces))
+        uv = torch.as_tensor(np.asarray(uv.detach().cpu()) if torch.is_tensor(uv) else np.asarray(uv))
+        tex = texture.detach().cpu() if torch.is_tensor(texture) else torch.as_tensor(np.ascontiguousarray(texture))
+        if verts.dim() != 2 or verts.shape[1] != 3 or faces.dim() != 2 or faces.shape[1] != 3:
+            raise ValueError("Scene: verts [V,3] and faces [F,3], got %s and %s" % (tuple(verts.shape), tuple(faces.shape)))
+        if tuple(uv.shape) != (verts.shape[0], 2):
+            raise ValueError("Scene: uv must be [%d,2], one per vertex, got %s" % (verts.shape[0], tuple(uv.shape)))
+        if tex.dim() != 3 or tex.shape[2] != 3 or tex.dtype not in (torch.uint8, torch.float32):
+            raise ValueError("Scene: texture must be uint8 or float32 [Ht,Wt,3], got %s %s" % (tex.dtype, tuple(tex.shape)))
+        ht, wt = int(tex.shape[0]), int(tex.shape[1])
+        self.levels = ops.texture_levels(ht, wt) if levels is None else int(levels)
+        ops.texture_pyramid_floats(ht, wt, self.levels)  # refuses a size or a level count out of range
+        if tex.dtype == torch.uint8:
+            tex = tex.to(torch.float32) / 255.0
+        if flip_v:
+            tex = tex.flip(0)
+        attr = torch.zeros((verts.shape[0], 3), dtype=torch.float32)
+        attr[:, :2] = uv.to(torch.float32)
+        self.wrap, self.tex_size = wrap, (ht, wt)
+        self.verts = verts.to(torch.float32).contiguous().to(dev)
+        self.faces = faces.to(torch.int32).contiguous().to(dev)
+        self.attr = attr.to(dev)
+        self.counts = torch.tensor([verts.shape[0], faces.shape[0]], dtype=torch.int32).to(dev)
+        self.texture = tex.contiguous().to(dev)  # level 0 as uploaded (after the flip)
+        self.pyramid, _ = ops.texture_mips(self.texture, self.levels)
+
+    @classmethod
+    def from_packed(cls, vert_data, uv_data, texture, **kw):
+        """The reference's layout (RTL/scene.py ``_load_floor``): ``vert_data`` [3F,3] and ``uv_data`` [3F,2], three
+        rows per face; the faces are ``arange(3F).reshape(F, 3)``."""
+        n = int(np.shape(vert_data)[0])
+        if n % 3 or n == 0:
+            raise ValueError("Scene.from_packed: vert_data holds three rows per face, got %d rows" % n)
+        return cls(vert_data, np.arange(n, dtype=np.int32).reshape(-1, 3), uv_data, texture, **kw)
+
+
+def _check_scene(who, scene):
+    if not isinstance(scene, Scene):
+        raise ValueError("%s: scene must be a recon.Scene, got %r" % (who, type(scene).__name__))
+
+
+def _camera_sets(who, calibs, n):
+    if isinstance(calibs, (list, tuple)):
+        if len(calibs) != n:
+            raise ValueError("%s: %d pictures, %d camera sets" % (who, n, len(calibs)))
+        return list(calibs)
+    return [calibs] * n
+
+
+@torch.no_grad()
+def render_scene(scene, calibs, res=257, projection="orthogonal", nearest="max", near=None, perspective_correct=False,
+                 background=1.0):
+    """The textured picture of a ``Scene`` under ``calibs`` ([4,4] / [3,4], or [n_views, ...]): the rasteriser writes a
+    UV picture (``near`` / ``perspective_correct`` as in ``render_mesh``), ``ops.picture_texture_batch`` looks the
+    texture up per pixel at the nearest mip level, bilinearly.  Returns a ``MeshRender``; pixels the scene does not
+    cover hold ``background``.  No host sync.  The scene goes through the rasteriser as any mesh does: a clipped face
+    that still projects beyond its 2^22 snap guard is dropped whole (``near`` far below 0.05 with a 3 m floor at
+    1024^2); the side planes are not clipped."""
+    _check_scene("render_scene", scene)
+    image, depth, face = ops.render_scene_batch("render_scene", scene, [calibs], res, projection, nearest, near,
+                                                perspective_correct, background)[0]
+    if _single_camera(calibs):
+        image, depth, face = image[0], depth[0], face[0]
+    return MeshRender(image, depth, face)
+
+
+@torch.no_grad()
+def composite(front, back, mode="depth", nearest="max", background=1.0):
+    """``front`` over ``back`` (``MeshRender``s of one size, each with an image): ``mode="over"`` is the reference's
+    mask composite -- the front wherever it is covered --, ``mode="depth"`` also lets the back hide the front where the
+    back is strictly nearer under ``nearest`` ("max" / "min", as both were rendered).  Returns a ``ScenePicture`` of
+    fresh tensors.  Defined bit for bit in include/monoport_hip.h (mp_picture_composite).  No host sync."""
+    image, depth, mask = ops.picture_composite_batch([tuple(front)[:3]], [tuple(back)[:3]], mode, nearest, background,
+                                                     who="composite")[0]
+    return ScenePicture(image, depth, front[2], mask)
+
+
+@torch.no_grad()
+def render_mesh_many_in_scene(meshes, scene, calibs, res=257, shade="colors", projection="orthogonal", nearest="max",
+                              background=1.0, near=None, perspective_correct=False, composite="depth", netC=None,
+                              feat_tensors_C=None, calib_tensors=None, view=None):
+    """``render_mesh_many`` of ``meshes`` composited over ``render_scene`` of ``scene`` under the same cameras
+    (``calibs``: one camera set for all, or a list with one per mesh), ``composite``: "depth" or "over".  Returns a
+    list of ``ScenePicture``s; a ``None`` mesh gives the bare scene (mask in {0, 1}, face -1).  ``shade`` may not be
+    None: the composite is of images.  Two more launches per ops.MAX_FRAMES pictures than the two renders; no host
+    sync."""
+    who = "render_mesh_many_in_scene"
+    _check_scene(who, scene)
+    if shade is None:
+        raise ValueError("%s: the composite is of images; shade=None renders none" % who)
+    ops._named_mode(who, "composite", ops.COMPOSITE_MODES, composite)
+    meshes = list(meshes)
+    if not meshes:
+        return []
+    cams = _camera_sets(who, calibs, len(meshes))
+    fronts = render_mesh_many(meshes, calibs, res, shade, projection, nearest, background, near, perspective_correct,
+                              netC=netC, feat_tensors_C=feat_tensors_C, calib_tensors=calib_tensors, view=view)
+    backs = ops.render_scene_batch(who, scene, cams, res, projection, nearest, near, perspective_correct, background)
+    pairs = []
+    for front, back, cam in zip(fronts, backs, cams):
+        if front is None:  # no subject: an uncovered picture of the scene's size
+            front = (torch.full_like(back[0], float(background)), torch.zeros_like(back[1]),
+                     torch.full_like(back[2], -1))
+        elif _single_camera(cam):
+            front = tuple(t[None] for t in front)
+        pairs.append(front)
+    done = ops.picture_composite_batch(pairs, backs, composite, nearest, background, who=who)
+    out = []
+    for (image, depth, mask), front, cam in zip(done, pairs, cams):
+        face = front[2]
+        if _single_camera(cam):
+            image, depth, face, mask = image[0], depth[0], face[0], mask[0]
+        out.append(ScenePicture(image, depth, face, mask))
+    return out
+
+
 @torch.no_grad()
 def prepare_inputs(segm, mean, std, with_color=True):
     """The two "update input by removing bg" processors of RTL/main.py:352-364 as one HIP kernel:

@@ -64,6 +64,14 @@ axes.
 
     python tools/mesh_timing.py --deferred [--passes 5] [--out profiles/mesh_deferred_timing.json]
 
+``--scene`` measures the scene behind the subject (profiles/mesh_scene_timing.json): 20-frame slots on the 257^3 body
+with normal-shaded pictures under a free perspective camera (near plane, perspective-correct), in one session with
+alternating passes, without and with ``scene=`` -- a 3 m floor of two triangles textured with a 2048^2 checker, full
+mip chain, composited by depth -- at one 257^2 and one 1024^2 view, per-frame milliseconds of a submission
+(``pictures()`` included), with the composite's mask counts of frame 0.  The rows without the scene are the comparison.
+
+    python tools/mesh_timing.py --scene [--passes 5] [--out profiles/mesh_scene_timing.json]
+
 The protocol of tools/recon_views_timing.py: after a warm-up of all, the passes alternate; a pass is `meshes`
 meshes, wall clock around a final stream sync.  Prints (and writes) one JSON line: per way the median, minimum and
 maximum time per mesh (ms) over the passes.  The verdict fields restate what to check: (b) not slower than (a) by
@@ -104,17 +112,22 @@ def main():
     ap.add_argument("--render", action="store_true", help="the mesh rasteriser against the visible-surface picture")
     ap.add_argument("--clip", action="store_true", help="with --render: the clipped form beside the unclipped call")
     ap.add_argument("--deferred", action="store_true", help="slot pictures coloured per vertex against per pixel")
+    ap.add_argument("--scene", action="store_true", help="slot pictures with and without a textured scene behind them")
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "mesh_render_clip_timing.json" if a.render and a.clip else
                              "mesh_render_timing.json" if a.render else
                              "mesh_deferred_timing.json" if a.deferred else
+                             "mesh_scene_timing.json" if a.scene else
                              "mesh_smooth_timing.json" if a.smooth else
                              "mesh_simplify_timing.json" if a.simplify else
                              "keep_largest_timing.json" if a.clean else
                              "mesh_batch_timing.json" if a.batched else "mesh_timing.json")
     if a.deferred:
         write(a, slot_deferred(a))
+        return
+    if a.scene:
+        write(a, slot_scene(a))
         return
     mlp = ops.PackedMLP.from_layers(DEV, syn.body_mlp("G", noise=0.05, seed=1), 1)
     fh = ops.pack_features(torch.from_numpy(syn.body_feat(256, 128, 128, 2))[None].to(DEV))
@@ -452,6 +465,39 @@ def slot_deferred(a, frames=20):
         p_.close()
     base = out["vertex_colours_257_views1"]["median_ms"]
     out["netC_257_views1_minus_vertex_colours_ms"] = round(out["netC_257_views1"]["median_ms"] - base, 4)
+    return out
+
+
+def slot_scene(a, frames=20):
+    """The 20-frame slot with normal-shaded pictures under a free perspective camera, with and without a textured 3 m
+    floor (a 2048^2 checker, full mip chain) composited behind the subject by depth: per-frame ms of a submission
+    (``pictures()`` included) at one 257^2 and one 1024^2 view, and what the composite shows in frame 0."""
+    i, j = np.meshgrid(np.arange(2048), np.arange(2048), indexing="ij")
+    tex = np.stack([(((i // 64) + (j // 64)) % 2) * 200 + 40, i // 8, j // 8], -1).astype(np.uint8)
+    y = -0.9
+    floor = recon.Scene([[-1.5, y, -1.5], [1.5, y, -1.5], [1.5, y, 1.5], [-1.5, y, 1.5]], [[0, 1, 2], [0, 2, 3]],
+                        [[0, 0], [1, 0], [1, 1], [0, 1]], tex, device=DEV)
+    c, s_ = np.cos(-0.35), np.sin(-0.35)  # from above: the floor fills the lower part
+    cam = np.eye(4, dtype=np.float32)
+    cam[:3, :3] = np.diag([2.0, 2.0, 1.0]) @ np.array([[1, 0, 0], [0, c, -s_], [0, s_, c]])
+    cam[:3, 3] = [0.0, 0.0, 2.6]
+    cam = torch.from_numpy(cam)[None]
+    mesh = {"normals": "accumulate", "colors": False}
+    base = dict(views=1, shade="normals", projection="perspective", nearest="min", near=0.3, perspective_correct=True)
+    rows = (("plain_257", mesh, dict(base, res=257), cam), ("scene_257", mesh, dict(base, res=257, scene=floor), cam),
+            ("plain_1024", mesh, dict(base, res=1024), cam), ("scene_1024", mesh, dict(base, res=1024, scene=floor), cam))
+    pipes, fn = _slot_pipes(frames, 1, rows)
+    out = {"frames_per_slot": frames, "unit": "ms per frame", "texture": [2048, 2048], "levels": floor.levels,
+           "camera": "perspective, turned -0.35 rad about x (looking down), near 0.3, perspective-correct"}
+    out.update(alternate({name: fn(name) for name in pipes}, a.passes, frames))
+    out["mask_counts_frame0"] = {}
+    for name, p_ in pipes.items():
+        pic = p_.slots[0].pictures()[0]
+        if hasattr(pic, "mask"):
+            out["mask_counts_frame0"][name] = torch.bincount(pic.mask.reshape(-1).long(), minlength=3).tolist()
+        p_.close()
+    for res in ("257", "1024"):
+        out["scene_%s_minus_plain_ms" % res] = round(out["scene_" + res]["median_ms"] - out["plain_" + res]["median_ms"], 4)
     return out
 
 
