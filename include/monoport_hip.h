@@ -863,7 +863,8 @@ int mp_picture_paint_batch(mp_ctx *ctx, int n_frames, const float *const *values
  * batched ones with one frame; in the batched ones uv / face_id / image / front_* / back_* / depth / mask are HOST
  * arrays of n_frames device pointers (one pyramid and one size for all), blockIdx.y is the frame: frame f's outputs
  * equal the per-frame call's on frame f's inputs BIT FOR BIT.
- * NOT built: trilinear and anisotropic filtering, alpha, shadows of the subject on the scene. */
+ * NOT built: trilinear and anisotropic filtering, alpha.  Shadows of the subject on the scene: mp_picture_shadow
+ * below. */
 enum { MP_WRAP_REPEAT = 0, MP_WRAP_CLAMP = 1 };
 enum { MP_COMPOSITE_OVER = 0, MP_COMPOSITE_DEPTH = 1 };
 int64_t mp_texture_pyramid_floats(int ht, int wt, int levels);
@@ -885,6 +886,57 @@ int mp_picture_composite_batch(mp_ctx *ctx, int n_frames, const float *const *fr
                                const int32_t *const *back_face, int64_t n_pixels, int mode, int nearest,
                                float background, float *const *image, float *const *depth, uint8_t *const *mask,
                                mp_stream stream);
+
+/* ---- the shadow of the subject on a picture: a shadow map looked up per pixel, filtered, and the pixel darkened -------
+ * A shadow map is what mp_mesh_render(_clip) writes WITHOUT an image for the caster under the light's camera: map_depth
+ * f32 [hs,ws] and map_face int32 [hs,ws] (hs, ws in 1..4096), rendered with `nearest`.  The receiver is a picture of L
+ * pixels (L = n_views * H * W as mp_mesh_render_batch lays them out): image_in f32 [L,3], face_id int32 [L] and
+ * position f32 [L,3], the rasteriser's image for attr = verts with the paint (1, 0, -inf, inf): the world-space point
+ * each pixel shows.  light_calib: HOST, 12 floats, the rows of [R|t] of the light; projection: its MP_PROJ_* mode.
+ * bias: finite, >= 0; radius: 0..3; strength: in [0, 1].  Outputs: image_out f32 [L,3] and shade f32 [L]; either may
+ * be NULL, not both; image_in is NULL exactly when image_out is.  A pure function of its inputs, defined bit for bit:
+ * every float operation of steps 3-6 is ONE IEEE f32 +, - or *, in the order written, without FMA; there is no sqrt,
+ * log or division (scene.hip; no atomics, no scratch).  Per pixel:
+ *   1. Uncovered.  face_id < 0: shade 0.
+ *   2. Projection.  (x, y, z) = the bits mp_orthogonal / mp_perspective give for the pixel's position under
+ *      light_calib (the device code of step 1 of the rasteriser; z is the camera-space row).  A non-finite x, y or z:
+ *      shade 0.  MP_PROJ_PERSPECTIVE and a z that is not > 0: shade 0.
+ *   3. Map coordinates, in the rasteriser's pixel-centre convention (texel i has its centre at x = (2 i + 1) / hs - 1):
+ *      a = (x + 1.0f) * (0.5f * (float)hs) - 0.5f, b = (y + 1.0f) * (0.5f * (float)ws) - 0.5f.  |a| or |b| > 2^22:
+ *      shade 0.  i0 = floorf(a), fa = a - i0; j0 = floorf(b), fb = b - j0.
+ *   4. Tap.  occ(i, j) = 1.0f if 0 <= i < hs, 0 <= j < ws, map_face[i,j] >= 0 and the map is STRICTLY nearer than the
+ *      pixel by more than the bias: map_depth[i,j] + bias < z with MP_NEAREST_MIN_Z, map_depth[i,j] - bias > z with
+ *      MP_NEAREST_MAX_Z.  Else 0.0f: a tap outside the map, an uncovered texel, a tie, a NaN.
+ *   5. Filter, a (2r+1)^2 box of bilinear lookups over the (2r+2)^2 texels (i0 + di, j0 + dj), di, dj = -r..r+1, each
+ *      touched once.  wi(di) = 1.0f - fa at di = -r, fa at di = r+1, 1.0f between; wj(dj) likewise with fb.
+ *      row(di) = 0.0f, then row = row + wj(dj) * occ(i0 + di, j0 + dj) for dj ascending; total = 0.0f, then total =
+ *      total + wi(di) * row(di) for di ascending.  shade = min(total * k_r, 1.0f), k_r the f32 nearest to
+ *      1 / (2r+1)^2.  Occluded weight is what is summed: a pixel nothing occludes has shade +0.0 exactly.
+ *   6. Paint.  shade (if given) is written for EVERY pixel: 0 where steps 1-3 say so.  Where shade == 0, image_out
+ *      takes image_in's 32-bit patterns (in place: the pixel is not written at all).  Else factor = 1.0f - strength *
+ *      shade and image_out[c] = image_in[c] * factor.
+ * So a map without a caster (all face ids < 0) and strength == 0 both leave the picture's bits unchanged.
+ * image_out may BE image_in of the same frame (in place); any other byte shared between an output and an input is
+ * refused.  One launch, one thread per pixel: 16 B (+ 12 B with an image) read and up to 16 B written per pixel,
+ * (2r+2)^2 gathers of 8 B from the map per pixel that reaches step 4; no other pixel touches the map.
+ * MP_ERR_ARG: n_frames outside 1..mp_max_frames(); n_pixels < 1; hs or ws outside 1..4096; an unknown projection or
+ * nearest; a bias that is negative or not finite; a radius outside 0..3; a strength outside [0, 1] or NaN; no output,
+ * image_in without image_out or the reverse; a NULL or not 4-byte aligned buffer of any frame; the aliasing above.
+ * MP_ERR_UNSUPPORTED: L beyond 2^31 / 3.  Each refusal leaves an mp_last_error message and launches nothing.
+ * Asynchronous, nothing synchronised, no scratch arena.  The per-frame call is the batched one with one frame; in the
+ * batched one image_in / position / face_id / map_depth / map_face / image_out / shade are HOST arrays of n_frames
+ * device pointers and light_calibs a HOST array of n_frames * 12 floats (one map size and one parameter set for all),
+ * blockIdx.y is the frame: frame f's outputs equal the per-frame call's on frame f's inputs BIT FOR BIT.
+ * NOT built: the scene casting shadows, more than one light, coloured or area lights, a varying penumbra, cascades. */
+int mp_picture_shadow(mp_ctx *ctx, const float *image_in, const float *position, const int32_t *face_id,
+                      int64_t n_pixels, const float *map_depth, const int32_t *map_face, int hs, int ws,
+                      const float *light_calib, int projection, int nearest, float bias, int radius, float strength,
+                      float *image_out, float *shade, mp_stream stream);
+int mp_picture_shadow_batch(mp_ctx *ctx, int n_frames, const float *const *image_in, const float *const *position,
+                            const int32_t *const *face_id, int64_t n_pixels, const float *const *map_depth,
+                            const int32_t *const *map_face, int hs, int ws, const float *light_calibs, int projection,
+                            int nearest, float bias, int radius, float strength, float *const *image_out,
+                            float *const *shade, mp_stream stream);
 
 /* The largest connected body of an occupancy volume [R,R,R] (no counterpart in the reference; the clean-up in front
  * of marching cubes that drops floating blobs).

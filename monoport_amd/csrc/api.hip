@@ -735,6 +735,55 @@ static int picture_composite_checked(mp_ctx *ctx, const char *who, int n_frames,
                                         (hipStream_t)stream);
 }
 
+static int picture_shadow_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *image_in,
+                                  const float *const *position, const int32_t *const *face_id, int64_t n_pixels,
+                                  const float *const *map_depth, const int32_t *const *map_face, int hs, int ws,
+                                  const float *light_calibs, int projection, int nearest, float bias, int radius,
+                                  float strength, float *const *image_out, float *const *shade, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (n_pixels < 1) return fail(ctx, MP_ERR_ARG, "%s: n_pixels must be >= 1, got %lld", who, (long long)n_pixels);
+  if (n_pixels > 0x7fffffffLL / 3)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: pictures beyond 2^31 / 3 pixels need 64-bit indices", who);
+  if (hs < 1 || hs > 4096 || ws < 1 || ws > 4096)
+    return fail(ctx, MP_ERR_ARG, "%s: shadow map size %d x %d outside 1..4096", who, hs, ws);
+  if (projection != MP_PROJ_ORTHOGONAL && projection != MP_PROJ_PERSPECTIVE)
+    return fail(ctx, MP_ERR_ARG, "%s: unknown projection mode %d", who, projection);
+  if (nearest != MP_NEAREST_MAX_Z && nearest != MP_NEAREST_MIN_Z)
+    return fail(ctx, MP_ERR_ARG, "%s: nearest must be MP_NEAREST_MAX_Z / _MIN_Z, got %d", who, nearest);
+  if (!std::isfinite(bias) || !(bias >= 0.0f))
+    return fail(ctx, MP_ERR_ARG, "%s: bias must be finite and >= 0, got %g", who, (double)bias);
+  if (radius < 0 || radius > 3) return fail(ctx, MP_ERR_ARG, "%s: radius must be in 0..3, got %d", who, radius);
+  if (!(strength >= 0.0f && strength <= 1.0f))
+    return fail(ctx, MP_ERR_ARG, "%s: strength must be in [0, 1], got %g", who, (double)strength);
+  if (!image_out && !shade) return fail(ctx, MP_ERR_ARG, "%s: no output requested", who);
+  if (!image_in != !image_out)
+    return fail(ctx, MP_ERR_ARG, "%s: image_in and image_out go together (both, or neither)", who);
+  if (!position || !face_id || !map_depth || !map_face || !light_calibs) return bad_argument(ctx, who);
+  rc = check_frames(ctx, who, n_frames, nullptr, image_in, position, face_id, map_depth, map_face, image_out, shade);
+  if (rc != MP_OK) return rc;
+  // image_out may BE image_in of the same frame (a thread reads its pixel before it writes it); any other byte shared
+  // between an output and an input is refused
+  const size_t px = (size_t)n_pixels, texels = (size_t)hs * ws;
+  const FrameSpans ins[5] = {{image_in, px * 12}, {position, px * 12}, {face_id, px * 4},
+                             {map_depth, texels * 4}, {map_face, texels * 4}};
+  const FrameSpans outs[2] = {{image_out, px * 12}, {shade, px * 4}};
+  for (int f = 0; f < n_frames; ++f)
+    for (int i = 0; i < n_frames; ++i)
+      for (int o = 0; o < 2; ++o)
+        for (int k = 0; k < 5; ++k) {
+          if (!ranges_overlap(outs[o].of(f), outs[o].bytes, ins[k].of(i), ins[k].bytes)) continue;
+          if (!(o == 0 && k == 0 && f == i && outs[o].of(f) == ins[k].of(i)))
+            return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases an input of frame %d", who, f, i);
+        }
+  DeviceGuard g(ctx->device);
+  return launch_picture_shadow_batch(ctx, n_frames, image_in, position, face_id, n_pixels, map_depth, map_face, hs, ws,
+                                     light_calibs, projection, nearest, bias, radius, strength, image_out, shade,
+                                     (hipStream_t)stream);
+}
+
 static int keep_largest_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *volume, int r,
                                 float level, int connectivity, float fill, float *const *out, int32_t *const *stats,
                                 const int32_t *const *gate, mp_stream stream) {
@@ -1845,6 +1894,25 @@ int mp_picture_composite_batch(mp_ctx *ctx, int n_frames, const float *const *fr
   return picture_composite_checked(ctx, "mp_picture_composite_batch", n_frames, front_image, front_depth, front_face,
                                    back_image, back_depth, back_face, n_pixels, mode, nearest, background, image, depth,
                                    mask, stream);
+}
+
+int mp_picture_shadow(mp_ctx *ctx, const float *image_in, const float *position, const int32_t *face_id,
+                      int64_t n_pixels, const float *map_depth, const int32_t *map_face, int hs, int ws,
+                      const float *light_calib, int projection, int nearest, float bias, int radius, float strength,
+                      float *image_out, float *shade, mp_stream stream) {
+  return picture_shadow_checked(ctx, "mp_picture_shadow", 1, image_in ? &image_in : nullptr, &position, &face_id,
+                                n_pixels, &map_depth, &map_face, hs, ws, light_calib, projection, nearest, bias, radius,
+                                strength, image_out ? &image_out : nullptr, shade ? &shade : nullptr, stream);
+}
+
+int mp_picture_shadow_batch(mp_ctx *ctx, int n_frames, const float *const *image_in, const float *const *position,
+                            const int32_t *const *face_id, int64_t n_pixels, const float *const *map_depth,
+                            const int32_t *const *map_face, int hs, int ws, const float *light_calibs, int projection,
+                            int nearest, float bias, int radius, float strength, float *const *image_out,
+                            float *const *shade, mp_stream stream) {
+  return picture_shadow_checked(ctx, "mp_picture_shadow_batch", n_frames, image_in, position, face_id, n_pixels,
+                                map_depth, map_face, hs, ws, light_calibs, projection, nearest, bias, radius, strength,
+                                image_out, shade, stream);
 }
 
 int mp_volume_keep_largest(mp_ctx *ctx, const float *volume, int r, float level, int connectivity, float fill,

@@ -485,6 +485,14 @@ int launch_picture_composite_batch(mp_ctx *ctx, int n_frames, const float *const
                                    const int32_t *const *back_face, long long n_pixels, int mode, int nearest,
                                    float background, float *const *image, float *const *depth, uint8_t *const *mask,
                                    hipStream_t st);
+// scene.hip: the shadow of n_frames shadow maps [hs,ws] (depth, face ids: what the rasteriser wrote under each frame's
+// light, light_calibs: host, 12 floats per frame) on n_frames pictures of n_pixels each.  image_in / image_out: both
+// nullptr or both n_frames entries (image_out[f] may be image_in[f]); shade: nullptr or n_frames entries.  radius 0..3
+int launch_picture_shadow_batch(mp_ctx *ctx, int n_frames, const float *const *image_in, const float *const *position,
+                                const int32_t *const *face_id, long long n_pixels, const float *const *map_depth,
+                                const int32_t *const *map_face, int hs, int ws, const float *light_calibs, int proj,
+                                int nearest, float bias, int radius, float strength, float *const *image_out,
+                                float *const *shade, hipStream_t st);
 
 // conv3x3.hip
 int launch_conv3x3_pack(mp_ctx *ctx, const float *w, int cout, int cin, float *wp, hipStream_t st);

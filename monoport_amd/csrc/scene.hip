@@ -1,14 +1,17 @@
-// The scene behind the subject (mp_texture_mips / mp_picture_texture / mp_picture_composite, include/monoport_hip.h):
-// a mip pyramid of a texture, the texture looked up per pixel of a UV picture the rasteriser wrote, and the composite
-// of two pictures by coverage or by depth.
+// The scene behind the subject (mp_texture_mips / mp_picture_texture / mp_picture_composite / mp_picture_shadow,
+// include/monoport_hip.h): a mip pyramid of a texture, the texture looked up per pixel of a UV picture the rasteriser
+// wrote, the composite of two pictures by coverage or by depth, and the shadow a shadow map casts on a picture.
 //   texture_mip        one thread per texel of a level: the 2x2 box of the level below (level 0: the copy)
 //   picture_texture    one thread per pixel: covered?, the level from the uv steps to its four neighbours, four texels
 //                      of that level, the paint
 //   picture_composite  one thread per pixel: which of the two pictures shows; its values as 32-bit patterns
-// All three are streaming kernels and defined bit for bit: every float operation is one IEEE f32 +, - or * in the order
+//   picture_shadow     one thread per pixel: its position under the light, (2r+2)^2 taps of the light's depth map, the
+//                      darkened pixel (the projection is the rasteriser's own: query_common.h, FMA and division there)
+// All four are streaming kernels and defined bit for bit: every float operation is one IEEE f32 +, - or * in the order
 // the header writes (no sqrt, log or division, whose rounding could differ from numpy's), no atomics, no scratch.
-// blockIdx.y is the frame; the per-frame pointers travel by value (TextureFrames, CompositeFrames).
+// blockIdx.y is the frame; the per-frame pointers travel by value (TextureFrames, CompositeFrames, ShadowFrames).
 #include "mp_internal.h"
+#include "query_common.h"
 
 #include <cstring>
 
@@ -35,7 +38,18 @@ struct CompositeFrames {
   uint32_t *depth[kMaxFrames];  // nullptr: not wanted
   uint8_t *mask[kMaxFrames];    // nullptr: not wanted
 };
+struct ShadowFrames {
+  const uint32_t *image_in[kMaxFrames];  // [L,3]; nullptr: no image
+  const float *position[kMaxFrames];     // [L,3]
+  const int32_t *face[kMaxFrames];       // [L]
+  const float *map_depth[kMaxFrames];    // [hs,ws]
+  const int32_t *map_face[kMaxFrames];   // [hs,ws]
+  uint32_t *image_out[kMaxFrames];       // nullptr: no image; may be image_in
+  float *shade[kMaxFrames];              // nullptr: not wanted
+  float cal[kMaxFrames][12];             // the light's [R|t]
+};
 static_assert(sizeof(TextureFrames) + 256 <= 4096 && sizeof(CompositeFrames) + 256 <= 4096, "scene: kernel arguments");
+static_assert(sizeof(ShadowFrames) + 256 <= 4096, "picture_shadow: kernel arguments");
 
 static int mip_size(int n) { return n > 1 ? n >> 1 : 1; }
 
@@ -181,6 +195,81 @@ __global__ __launch_bounds__(kSceneBlock) void picture_composite(CompositeFrames
   if (fr.mask[f]) fr.mask[f][p] = m;
 }
 
+constexpr float kShadowMost = 4194304.0f;  // 2^22: map coordinates beyond it are outside every map (and stay inside int32)
+
+// shade of one point under the light: 0 for a point that fails steps 2-3 of the definition, touching no map memory
+__device__ __forceinline__ float shadow_shade(const float *__restrict__ cal, int proj, int nearest, float px, float py,
+                                              float pz, const float *__restrict__ map_depth,
+                                              const int32_t *__restrict__ map_face, int hs, int ws, float bias, int radius,
+                                              float k_r) {
+  float x, y, z;
+  project_mode(cal, proj, px, py, pz, x, y, z);
+  if (!(__builtin_isfinite(x) && __builtin_isfinite(y) && __builtin_isfinite(z))) return 0.0f;
+  if (proj == MP_PROJ_PERSPECTIVE && !(z > 0.0f)) return 0.0f;
+  const float a = (x + 1.0f) * (0.5f * (float)hs) - 0.5f;
+  const float b = (y + 1.0f) * (0.5f * (float)ws) - 0.5f;
+  if (fabsf(a) > kShadowMost || fabsf(b) > kShadowMost) return 0.0f;
+  const float af = floorf(a), bf = floorf(b);
+  const float fa = a - af, fb = b - bf;
+  const int i0 = (int)af, j0 = (int)bf;
+  // no tap inside the map: nothing occludes
+  if (i0 + radius + 1 < 0 || i0 - radius >= hs || j0 + radius + 1 < 0 || j0 - radius >= ws) return 0.0f;
+  const float ga = 1.0f - fa, gb = 1.0f - fb;
+  float total = 0.0f;
+  for (int di = -radius; di <= radius + 1; ++di) {
+    const int i = i0 + di;
+    const bool row_in = i >= 0 && i < hs;
+    float row = 0.0f;
+    for (int dj = -radius; dj <= radius + 1; ++dj) {
+      const int j = j0 + dj;
+      float occ = 0.0f;
+      if (row_in && j >= 0 && j < ws) {
+        const long long t = (long long)i * ws + j;
+        if (map_face[t] >= 0) {
+          const float d = map_depth[t];
+          const bool nearer = nearest == MP_NEAREST_MIN_Z ? (d + bias < z) : (d - bias > z);  // a tie, a NaN: not
+          occ = nearer ? 1.0f : 0.0f;
+        }
+      }
+      const float wj = dj == -radius ? gb : (dj == radius + 1 ? fb : 1.0f);
+      row = row + wj * occ;
+    }
+    const float wi = di == -radius ? ga : (di == radius + 1 ? fa : 1.0f);
+    total = total + wi * row;
+  }
+  const float s = total * k_r;
+  return s < 1.0f ? s : 1.0f;
+}
+
+// no __restrict__ on the images: image_out may be image_in; a thread reads its pixel, then writes it
+__global__ __launch_bounds__(kSceneBlock) void picture_shadow(ShadowFrames fr, int n_pixels, int hs, int ws, int proj,
+                                                              int nearest, float bias, int radius, float k_r,
+                                                              float strength) {
+  const long long p = (long long)blockIdx.x * kSceneBlock + threadIdx.x;
+  if (p >= n_pixels) return;
+  const int f = blockIdx.y;
+  float s = 0.0f;
+  if (fr.face[f][p] >= 0) {  // an uncovered span costs a wavefront its face ids only
+    const float *__restrict__ pos = fr.position[f];
+    s = shadow_shade(fr.cal[f], proj, nearest, pos[3 * p], pos[3 * p + 1], pos[3 * p + 2], fr.map_depth[f],
+                     fr.map_face[f], hs, ws, bias, radius, k_r);
+  }
+  if (fr.shade[f]) fr.shade[f][p] = s;
+  uint32_t *out = fr.image_out[f];
+  if (!out) return;
+  const uint32_t *in = fr.image_in[f];
+  if (s == 0.0f) {
+    if (out != in) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) out[3 * p + c] = in[3 * p + c];
+    }
+    return;
+  }
+  const float factor = 1.0f - strength * s;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) out[3 * p + c] = __float_as_uint(__uint_as_float(in[3 * p + c]) * factor);
+}
+
 static unsigned scene_blocks(long long n) { return (unsigned)((n + kSceneBlock - 1) / kSceneBlock); }
 
 int launch_texture_mips(mp_ctx *ctx, const float *tex, int ht, int wt, int levels, float *pyramid, hipStream_t st) {
@@ -233,6 +322,30 @@ int launch_picture_composite_batch(mp_ctx *ctx, int n_frames, const float *const
   std::memcpy(&bg, &background, 4);
   hipLaunchKernelGGL(picture_composite, dim3(scene_blocks(n_pixels), n_frames), dim3(kSceneBlock), 0, st, fr,
                      (int)n_pixels, mode, nearest, bg);
+  MP_HIP(ctx, hipGetLastError());
+  return MP_OK;
+}
+
+int launch_picture_shadow_batch(mp_ctx *ctx, int n_frames, const float *const *image_in, const float *const *position,
+                                const int32_t *const *face_id, long long n_pixels, const float *const *map_depth,
+                                const int32_t *const *map_face, int hs, int ws, const float *light_calibs, int proj,
+                                int nearest, float bias, int radius, float strength, float *const *image_out,
+                                float *const *shade, hipStream_t st) {
+  static const float k_r[4] = {1.0f, 1.0f / 9.0f, 1.0f / 25.0f, 1.0f / 49.0f};  // the f32 nearest to 1 / (2r+1)^2
+  ShadowFrames fr;
+  std::memset(&fr, 0, sizeof(fr));
+  for (int f = 0; f < n_frames; ++f) {
+    fr.image_in[f] = image_in ? reinterpret_cast<const uint32_t *>(image_in[f]) : nullptr;
+    fr.position[f] = position[f];
+    fr.face[f] = face_id[f];
+    fr.map_depth[f] = map_depth[f];
+    fr.map_face[f] = map_face[f];
+    fr.image_out[f] = image_out ? reinterpret_cast<uint32_t *>(image_out[f]) : nullptr;
+    fr.shade[f] = shade ? shade[f] : nullptr;
+    std::memcpy(fr.cal[f], light_calibs + 12 * (size_t)f, 12 * sizeof(float));
+  }
+  hipLaunchKernelGGL(picture_shadow, dim3(scene_blocks(n_pixels), n_frames), dim3(kSceneBlock), 0, st, fr,
+                     (int)n_pixels, hs, ws, proj, nearest, bias, radius, k_r[radius], strength);
   MP_HIP(ctx, hipGetLastError());
   return MP_OK;
 }

@@ -1921,14 +1921,96 @@ def picture_composite_batch(fronts, backs, mode="depth", nearest="max", backgrou
     return [(image[f], None if depth is None else depth[f], None if mask is None else mask[f]) for f in range(n)]
 
 
+SHADOW_MAX_RADIUS = 3  # mp_picture_shadow: radius in 0..3
+SHADOW_MAX_SIZE = 4096  # its map: Hs, Ws in 1..4096
+
+
+def shadow_params(who, bias, radius, strength):
+    """(bias, radius, strength) of mp_picture_shadow as (float, int, float), or the ValueError of a value it refuses."""
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= int(radius) <= SHADOW_MAX_RADIUS:
+        raise ValueError("%s: radius must be an int in 0..%d, got %r" % (who, SHADOW_MAX_RADIUS, radius))
+    bias, strength = float(bias), float(strength)
+    if not (math.isfinite(bias) and bias >= 0):
+        raise ValueError("%s: bias must be finite and >= 0, got %r" % (who, bias))
+    if not 0.0 <= strength <= 1.0:
+        raise ValueError("%s: strength must be in [0, 1], got %r" % (who, strength))
+    return bias, int(radius), strength
+
+
+def picture_shadow_batch(images, positions, face_ids, map_depths, map_faces, light_calibs, projection="orthogonal",
+                         nearest="min", bias=0.0, radius=1, strength=0.6, out=None, with_shade=False,
+                         who="picture_shadow_batch"):
+    """mp_picture_shadow_batch: per frame the shadow that a shadow map casts on a picture.  ``positions``: float32
+    [...,3] per frame, the world-space point every pixel shows (the rasteriser's image for ``attr = verts``, paint (1, 0,
+    -inf, inf)), ``face_ids`` its int32 [...]; ``images``: the float32 [...,3] pictures to darken, or None (the shade
+    alone).  ``map_depths`` / ``map_faces``: per frame the float32 / int32 [Hs,Ws] that the rasteriser wrote for the
+    caster under the light (``nearest`` as it was rendered with); ``light_calibs``: one [4,4] / [3,4] for all frames, or
+    one per frame (read on the host); ``projection`` the light's.  A covered pixel whose point lies behind the map's
+    surface by more than ``bias`` -- over a (2 radius + 1)^2 box of bilinear lookups -- has shade 1, and the image is
+    multiplied by 1 - strength * shade; a pixel with shade 0 keeps its bits.  Defined bit for bit in
+    include/monoport_hip.h.  ``out``: (images or None, shades or None) to write; the images may be ``images`` themselves
+    (in place).  None: fresh images (where ``images`` is given) and, with ``with_shade`` or without images, fresh
+    shades.  Returns per frame (image or None, shade or None).  One launch per MAX_FRAMES frames; no host sync."""
+    n = len(positions)
+    if n == 0 or positions[0].dim() < 2 or positions[0].shape[-1] != 3:
+        raise ValueError("%s: at least one position picture [...,3]" % who)
+    shape = tuple(positions[0].shape[:-1])
+    dev, npix = positions[0].device, positions[0].numel() // 3
+    if npix < 1:
+        raise ValueError("%s: at least one pixel" % who)
+    positions = _flat_pictures(who, "positions", positions, n, torch.float32, 3, npix, dev)
+    face_ids = _flat_pictures(who, "face_ids", face_ids, n, torch.int32, 1, npix, dev)
+    if images is not None:
+        images = _flat_pictures(who, "images", images, n, torch.float32, 3, npix, dev)
+    map_depths, map_faces = list(map_depths), list(map_faces)
+    if len(map_depths) != n or len(map_faces) != n or map_depths[0].dim() != 2:
+        raise ValueError("%s: per frame a shadow map [Hs,Ws] of depths and one of face ids" % who)
+    hs, ws = (int(s) for s in map_depths[0].shape)
+    if not (1 <= hs <= SHADOW_MAX_SIZE and 1 <= ws <= SHADOW_MAX_SIZE):
+        raise ValueError("%s: shadow map size %d x %d outside 1..%d" % (who, hs, ws, SHADOW_MAX_SIZE))
+    map_depths = _frame_rows(who, "map_depths", map_depths, n, (hs, ws), torch.float32, dev)
+    map_faces = _frame_rows(who, "map_faces", map_faces, n, (hs, ws), torch.int32, dev)
+    proj, near_mode = _projection(projection), _nearest(nearest)
+    bias, radius, strength = shadow_params(who, bias, radius, strength)
+    lights = list(light_calibs) if isinstance(light_calibs, (list, tuple)) else [light_calibs] * n
+    if len(lights) != n:
+        raise ValueError("%s: %d frames, %d light calibrations" % (who, n, len(lights)))
+    cal = np.stack([_view_calibs(who, c) for c in lights])
+    if cal.shape[1] != 1:
+        raise ValueError("%s: one light per frame" % who)
+    cal = np.ascontiguousarray(cal.reshape(n, 12))
+    if out is None:
+        image = None if images is None else torch.empty((n,) + shape + (3,), dtype=torch.float32, device=dev).unbind(0)
+        shade = (torch.empty((n,) + shape, dtype=torch.float32, device=dev).unbind(0)
+                 if (with_shade or images is None) else None)
+    else:
+        image = None if out[0] is None else _flat_pictures(who, "out[0] (image)", out[0], n, torch.float32, 3, npix, dev)
+        shade = None if out[1] is None else _flat_pictures(who, "out[1] (shade)", out[1], n, torch.float32, 1, npix, dev)
+    if image is None and shade is None:
+        raise ValueError("%s: out names no output" % who)
+    if (image is None) != (images is None):
+        raise ValueError("%s: an image is written exactly where images are given" % who)
+    ctx = get_context(dev)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_picture_shadow_batch(
+            ctx.handle, f1 - f0, None if images is None else _ptr_array(images[f0:f1]), _ptr_array(positions[f0:f1]),
+            _ptr_array(face_ids[f0:f1]), npix, _ptr_array(map_depths[f0:f1]), _ptr_array(map_faces[f0:f1]), hs, ws,
+            np.ascontiguousarray(cal[f0:f1]).ctypes.data_as(_lib._pf32), proj, near_mode, bias, radius, strength,
+            None if image is None else _ptr_array(image[f0:f1]), None if shade is None else _ptr_array(shade[f0:f1]),
+            _stream(positions[0])), "mp_picture_shadow_batch")
+    return [(None if image is None else image[f], None if shade is None else shade[f]) for f in range(n)]
+
+
 def render_scene_batch(who, scene, calibs, res, projection="orthogonal", nearest="max", near=None,
-                       perspective_correct=False, background=1.0, out=None, uv=None):
+                       perspective_correct=False, background=1.0, out=None, uv=None, positions=None):
     """The textured pictures of ``scene`` (a ``recon.Scene``: verts, faces, counts, attr = (u, v, 0) per vertex, pyramid,
     tex_size, levels, wrap) under one camera set per frame (``calibs``: a list, all of one n_views), no host value in
     between: (1) the rasteriser with the scene's tensors repeated per frame and its uv as the attribute, under the
     pictures' own camera, ``near`` and ``perspective_correct``, into a UV picture; (2) ``picture_texture_batch`` into
     the image.  Returns what ``_mesh_render`` does: per frame (image [n_views,H,W,3], depth, face).  ``out``: (image,
-    depth, face) buffers; ``uv``: the UV pictures' buffers [n,n_views,H,W,3] (scratch of the call)."""
+    depth, face) buffers; ``uv``: the UV pictures' buffers [n,n_views,H,W,3] (scratch of the call).  ``positions``:
+    None, or buffers [n,n_views,H,W,3] that a second pass of the rasteriser with ``attr = scene.verts`` fills with the
+    world-space point of every pixel (what ``picture_shadow_batch`` reads); nothing more is enqueued without them."""
     n = len(calibs)
     if n == 0:
         raise ValueError("%s: at least one camera set" % who)
@@ -1944,6 +2026,10 @@ def render_scene_batch(who, scene, calibs, res, projection="orthogonal", nearest
                         res, projection, nearest, False, 1.0, 0.0, -math.inf, math.inf, background,
                         None if out is None else (uv, out[1], out[2]), near=near,
                         perspective_correct=perspective_correct)
+    if positions is not None:  # the same faces under the same cameras and flags: the face ids are the UV pass's
+        _mesh_render(who, [scene.verts] * n, [scene.faces] * n, [scene.counts] * n, [scene.verts] * n, list(calibs),
+                     res, projection, nearest, False, 1.0, 0.0, -math.inf, math.inf, background,
+                     (positions, None, None), near=near, perspective_correct=perspective_correct)
     images =picture_texture_batch([r[0] for r in raws], [r[2] for r in raws], scene.pyramid, scene.tex_size,
                                    scene.levels, scene.wrap, background=background,
                                    out=None if out is None else out[0], who=who)

@@ -168,7 +168,12 @@ class FrameSlot:
         ``pictures_depth`` (``composite``: "depth", the default, or "over"; ``ops.picture_composite_batch``), filling the
         static ``pictures_mask`` [batch,views,H,W] uint8 (0 neither, 1 scene, 2 subject), with no host value in
         between; ``pictures()`` then returns ``recon.ScenePicture``s, the bare scene for an empty frame.  It needs a
-        ``shade``, and runs behind the paint of ``shade="netC"`` as behind any other."""
+        ``shade``, and runs behind the paint of ``shade="netC"`` as behind any other.  A scene with a ``light``
+        (``recon.Scene(light=recon.Light(...))``; the light belongs to the scene, the option keys do not change) also
+        shows each frame's shadow on it: the slot then owns ``shadow_depth`` / ``shadow_face`` [batch,Hs,Ws] (the
+        frames' shadow maps, rendered from the chain's mesh buffers), ``scene_pos`` (the scene's world-space positions)
+        and ``scene_lit`` (the shadowed scene, which the composite takes; ``scene_image`` stays unshadowed), all filled
+        on the slot's stream.  Without a light none of them exists and nothing more is enqueued."""
         self.views = self._head_views(netG, netC, mesh)  # images per frame; refuses what the slot class does not run
         # both option records are validated before anything is allocated
         self.mesh = None if mesh is None else _mesh_options(mesh, float(balance), netC is not None)
@@ -272,6 +277,12 @@ class FrameSlot:
                 self.scene_depth = torch.empty(shape, dtype=torch.float32, device=dev)
                 self.scene_face = torch.empty(shape, dtype=torch.int32, device=dev)
                 self.pictures_mask = torch.empty(shape, dtype=torch.uint8, device=dev)
+                if po.scene.light is not None:  # the subjects' shadow maps, the scene's positions and its lit image
+                    hs, ws = po.scene.light.res
+                    self.shadow_depth = torch.empty((b, hs, ws), dtype=torch.float32, device=dev)
+                    self.shadow_face = torch.empty((b, hs, ws), dtype=torch.int32, device=dev)
+                    self.scene_pos = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
+                    self.scene_lit = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
             # the cameras of the current submission, on the host [batch,views,3,4]; the identity until the first one
             self._cameras = np.tile(np.eye(4, dtype=np.float32)[:3], (b, po.views, 1, 1))
 
@@ -418,14 +429,31 @@ class FrameSlot:
         """The pictures of the slot's n frames under their ``views`` cameras each, from the mesh buffers the chain has
         just filled and its device counts: one set of launches per ops.MAX_FRAMES pictures, no host value in between.
         A gated-off frame's counts are (0, 0): pure background.  With a ``scene``: its textured picture under the same
-        cameras, and the composite in place, follow on the same stream."""
+        cameras, and the composite in place, follow on the same stream.  With a light in the scene: the n frames' shadow
+        maps from the same mesh buffers (a gated-off frame's map is uncovered: no shadow), the scene's positions, and
+        the shadow of ``scene_image`` into ``scene_lit``, which the composite then takes; ``scene_image`` stays
+        unshadowed for ``_scene_picture``."""
         self._render_subjects(n)
         po = self.picture_options
         if po.scene is not None:  # the scene under the same cameras, then the composite in place
+            light = po.scene.light if hasattr(self, "scene_lit") else None
+            if light is not None:
+                chains = self._mesh_chains[:n]
+                ops.mesh_render_raw_batch([c.verts for c in chains], [c.faces for c in chains],
+                                          [c.counts for c in chains], None, [light.calib] * n, light.res,
+                                          light.projection, light.nearest,
+                                          out=(None, self.shadow_depth[:n].unsqueeze(1), self.shadow_face[:n].unsqueeze(1)),
+                                          near=light.near, perspective_correct=light.near is not None)
             backs = ops.render_scene_batch("FrameSlot", po.scene, list(self._cameras[:n]), po.res, po.projection,
                                            po.nearest, po.near, po.perspective_correct, po.background,
                                            out=(self.scene_image[:n], self.scene_depth[:n], self.scene_face[:n]),
-                                           uv=self.scene_uv[:n])
+                                           uv=self.scene_uv[:n], positions=None if light is None else self.scene_pos[:n])
+            if light is not None:
+                ops.picture_shadow_batch(list(self.scene_image[:n]), list(self.scene_pos[:n]), list(self.scene_face[:n]),
+                                         list(self.shadow_depth[:n]), list(self.shadow_face[:n]), light.calib,
+                                         light.projection, light.nearest, light.bias, light.radius, light.strength,
+                                         out=(list(self.scene_lit[:n]), None), who="FrameSlot")
+                backs = [(lit, back[1], back[2]) for lit, back in zip(self.scene_lit[:n], backs)]
             fronts = list(zip(self.pictures_image[:n], self.pictures_depth[:n], self.pictures_face[:n]))
             ops.picture_composite_batch(fronts, backs, po.composite, po.nearest, po.background,
                                         out=(self.pictures_image[:n], self.pictures_depth[:n], self.pictures_mask[:n]),
@@ -502,7 +530,13 @@ class FrameSlot:
         bindings = self._colour_bindings(b, b + 1) if po.shade == "netC" else None
         front = _render_meshes("FrameSlot.pictures", [mesh], [self._cameras[b]], po.res, po.shade, po.projection,
                                po.nearest, po.background, po.near, po.perspective_correct, bindings, self.view)[0]
-        return composite(front, (self.scene_image[b], self.scene_depth[b], self.scene_face[b]), po.composite,
+        back = self.scene_image[b]
+        if hasattr(self, "scene_lit"):  # the shadow anew, from the re-run mesh's own map, on the unshadowed picture
+            from .recon import shade_shadow, shadow_map
+            light = po.scene.light
+            back = shade_shadow((back, self.scene_depth[b], self.scene_face[b]), self.scene_pos[b],
+                                shadow_map([mesh], light)[0], light)[0]
+        return composite(front, (back, self.scene_depth[b], self.scene_face[b]), po.composite,
                          po.nearest, po.background)
 
     def _slot_cameras(self, cameras, n):

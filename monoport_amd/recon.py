@@ -597,6 +597,84 @@ pictures shows at a pixel (``background`` and +0.0 where neither does), face [H,
 front (the subject); with a set of cameras each has a leading [n_views]."""
 
 
+class Light:
+    """The one light of a ``Scene``: a camera from which the subject's shadow map is rendered (monoport_amd extension;
+    mp_picture_shadow in include/monoport_hip.h).  ``calib``: [4,4] / [3,4], the rows of [R|t] as every camera here;
+    ``projection``: "orthogonal" (a directional light) or "perspective" (a spot); ``res``: the map's size, an int or
+    (Hs, Ws), each in 1..4096; ``near`` (perspective lights only): the map is then rendered with the clipped rasteriser
+    and ``perspective_correct=True``, so the light may stand close to the subject; ``bias`` (finite, >= 0): how much
+    nearer than a point the map must be to shadow it; ``radius`` (0..3): the (2 radius + 1)^2 box of bilinear lookups
+    that softens the edge; ``strength`` in [0, 1]: a fully shadowed pixel is multiplied by 1 - strength; ``nearest``:
+    "min" (the default: depth is the distance along the light) or "max", what the map is rendered and compared with.
+    Everything is validated here, before any allocation; a Light holds host values only."""
+
+    def __init__(self, calib, projection="orthogonal", res=512, near=None, bias=0.0, radius=1, strength=0.6,
+                 nearest="min"):
+        who = "Light"
+        cal = ops._view_calibs(who, calib)
+        if cal.shape[0] != 1:
+            raise ValueError("%s: calib must be one [4,4] or [3,4] camera, got %d" % (who, cal.shape[0]))
+        if not np.isfinite(cal).all():
+            raise ValueError("%s: calib must be finite" % who)
+        if not isinstance(projection, str) or projection not in ops.PROJECTIONS:
+            raise ValueError("%s: projection must be one of %s, got %r" % (who, sorted(ops.PROJECTIONS), projection))
+        if not isinstance(nearest, str) or nearest not in ops.NEAREST_MODES:
+            raise ValueError("%s: nearest must be one of %s, got %r" % (who, sorted(ops.NEAREST_MODES), nearest))
+        try:
+            hs, ws = (res, res) if isinstance(res, (int, np.integer)) and not isinstance(res, bool) else tuple(res)
+            ok = all(isinstance(s, (int, np.integer)) and not isinstance(s, bool) for s in (hs, ws))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok or not (1 <= hs <= ops.SHADOW_MAX_SIZE and 1 <= ws <= ops.SHADOW_MAX_SIZE):
+            raise ValueError("%s: res must be an int or (Hs, Ws) in 1..%d, got %r" % (who, ops.SHADOW_MAX_SIZE, res))
+        if near is not None:
+            near = ops._render_clip(who, projection, near, True)[0]
+        self.bias, self.radius, self.strength = ops.shadow_params(who, bias, radius, strength)
+        self.calib = cal.reshape(3, 4).copy()
+        self.projection, self.nearest, self.res, self.near = projection, nearest, (int(hs), int(ws)), near
+
+    @classmethod
+    def directional(cls, direction, b_min=(-1, -1, -1), b_max=(1, 1, 1), **kw):
+        """A directional light whose rays travel along ``direction`` (any length), fitted to the box [b_min, b_max].
+        In float64, then rounded to f32: d = direction / |direction|; e = the coordinate axis with the smallest |d . e|
+        (the first of equals); x = (e x d) / |e x d|, y = d x x, so (x, y, d) is a right-handed orthonormal frame; c =
+        (b_min + b_max) / 2 and rho = |b_max - b_min| / 2 * (1 + 2^-20), the box's bounding sphere with a margin for
+        the rounding.  The rows of the calib are [x / rho | -x . c / rho], [y / rho | -y . c / rho] and [d | rho -
+        d . c]: the sphere fills [-1, 1]^2 of the map and the depth, the distance along the light from the plane that
+        touches the sphere on the light's side, runs from 0 to 2 rho -- hence ``nearest="min"``.  ``kw``: ``res``,
+        ``bias``, ``radius``, ``strength``."""
+        who = "Light.directional"
+        d = np.asarray(direction, np.float64).reshape(-1)
+        lo, hi = np.asarray(b_min, np.float64).reshape(-1), np.asarray(b_max, np.float64).reshape(-1)
+        if d.shape != (3,) or not np.isfinite(d).all() or not np.linalg.norm(d) > 0:
+            raise ValueError("%s: direction must be three finite values, not all zero, got %r" % (who, direction))
+        box = lo.shape == (3,) and hi.shape == (3,) and np.isfinite(lo).all() and np.isfinite(hi).all()
+        if not box or not (hi > lo).all():
+            raise ValueError("%s: b_min < b_max must be the finite corners of a box, got %r and %r"
+                             % (who, b_min, b_max))
+        for k in ("projection", "near", "nearest"):
+            if k in kw:
+                raise ValueError("%s: a directional light is orthogonal with nearest='min'; %s= is not taken"
+                                 % (who, k))
+        d = d / np.linalg.norm(d)
+        e = np.zeros(3)
+        e[int(np.argmin(np.abs(d)))] = 1.0
+        x = np.cross(e, d)
+        x /= np.linalg.norm(x)
+        y = np.cross(d, x)
+        c, rho = (lo + hi) / 2, np.linalg.norm(hi - lo) / 2 * (1 + 2.0 ** -20)
+        calib = np.zeros((3, 4))
+        calib[0, :3], calib[0, 3] = x / rho, -x.dot(c) / rho
+        calib[1, :3], calib[1, 3] = y / rho, -y.dot(c) / rho
+        calib[2, :3], calib[2, 3] = d, rho - d.dot(c)
+        return cls(calib.astype(np.float32), "orthogonal", nearest="min", **kw)
+
+
+def _check_light(who, light):
+    if not isinstance(light, Light):
+        raise ValueError("%s: light must be a recon.Light, got %r" % (who, type(light).__name__))
+
+
 class Scene:
     """A textured triangle mesh behind the subject, on the device (RTL/scene.py's floor): ``verts`` [V,3] f32, ``faces``
     [F,3] int, ``uv`` [V,2] f32 per vertex, ``texture`` [Ht,Wt,3] -- uint8 (divided by 255 into f32) or f32; tensors or
@@ -604,9 +682,14 @@ class Scene:
     as the reference's ``Render.set_texture`` does, so OBJ / GL uv (v = 0 at the bottom of the picture file) need no
     change; without it v = 0 is row 0.  The mip pyramid is built once here (``ops.texture_mips``; ``levels`` None = the
     full chain).  Holds ``verts``, ``faces``, ``counts`` (int32 [2] on the device), ``attr`` [V,3] = (u, v, 0),
-    ``pyramid``, ``tex_size`` (Ht, Wt), ``levels``, ``wrap``."""
+    ``pyramid``, ``tex_size`` (Ht, Wt), ``levels``, ``wrap``, ``light``.  ``light``: None, or the ``Light`` under which
+    the subject casts its shadow on this scene (``render_mesh_many_in_scene``, ``render_scene(casters=)``, a slot's
+    pictures).  The light belongs to the scene: the picture options of a slot do not change."""
 
-    def __init__(self, verts, faces, uv, texture, wrap="repeat", flip_v=True, levels=None, device="cuda"):
+    def __init__(self, verts, faces, uv, texture, wrap="repeat", flip_v=True, levels=None, device="cuda", light=None):
+        if light is not None:
+            _check_light("Scene", light)
+        self.light = light
         dev = torch.device(device)
         ops._named_mode("Scene", "wrap", ops.WRAP_MODES, wrap)
         verts = torch.as_tensor(np.asarray(verts.detach().cpu()) if torch.is_tensor(verts) else np.asarray(verts))
@@ -660,17 +743,80 @@ def _camera_sets(who, calibs, n):
 
 
 @torch.no_grad()
+def shadow_map(meshes, light, device=None):
+    """Per mesh the shadow map (depth [Hs,Ws] f32, face [Hs,Ws] int32) of ``light``: the rasteriser's depth and face
+    ids of the mesh under the light's camera, without an image -- through the clipped, perspective-correct call where
+    the light has a ``near``.  A ``None`` mesh gives an all-uncovered map (depth +0.0, face -1), which shadows nothing.
+    One set of launches per ops.MAX_FRAMES meshes; no host sync.  ``device``: where the maps of ``None`` meshes live
+    (None: the first mesh's, "cuda" without any)."""
+    who = "shadow_map"
+    _check_light(who, light)
+    meshes = list(meshes)
+    idx = [i for i, m in enumerate(meshes) if m is not None]
+    if device is None:
+        device = meshes[idx[0]].verts.device if idx else "cuda"
+    hs, ws = light.res
+    out = [None] * len(meshes)
+    if idx:
+        raws = _render_meshes(who, [meshes[i] for i in idx], [light.calib] * len(idx), light.res, None,
+                              light.projection, light.nearest, 1.0, light.near, light.near is not None)
+        for i, (_, depth, face) in zip(idx, raws):
+            out[i] = (depth[0], face[0])
+    for i, m in enumerate(meshes):
+        if m is None:
+            out[i] = (torch.zeros((hs, ws), dtype=torch.float32, device=device),
+                      torch.full((hs, ws), -1, dtype=torch.int32, device=device))
+    return out
+
+
+@torch.no_grad()
+def shade_shadow(picture, positions, maps, light):
+    """The shadow of ``maps`` = (depth, face) (``shadow_map`` of the caster under ``light``) on ``picture`` (image
+    [...,3] f32, depth, face [...] int32; a ``MeshRender`` or a tuple), whose ``positions`` [...,3] f32 hold the
+    world-space point of every pixel (a render with the vertices as the attribute).  The generic call: the caller may
+    shade the subject's own picture with its own map and a ``bias`` (self-shadowing).  Returns (image, shade): fresh
+    tensors, the image's bits unchanged wherever the shade is 0.  Defined bit for bit in include/monoport_hip.h
+    (mp_picture_shadow).  No host sync."""
+    _check_light("shade_shadow", light)
+    return ops.picture_shadow_batch([picture[0].contiguous()], [positions.contiguous()], [picture[2].contiguous()],
+                                    [maps[0]], [maps[1]], light.calib, light.projection, light.nearest, light.bias,
+                                    light.radius, light.strength, with_shade=True, who="shade_shadow")[0]
+
+
+def _scene_pictures(who, scene, casters, cams, res, projection, nearest, near, perspective_correct, background):
+    """Per camera set the raw picture (image, depth, face; each [n_views, ...]) of ``scene``.  With ``scene.light`` and
+    any caster (``casters``: None, or one Mesh or None per camera set): the shadow maps of the casters, the scene's UV
+    and position pictures, the texture lookup, and the shadow in place on the scene's image.  Else exactly
+    ``ops.render_scene_batch``."""
+    light = scene.light
+    if light is None or casters is None or all(m is None for m in casters):
+        return ops.render_scene_batch(who, scene, cams, res, projection, nearest, near, perspective_correct, background)
+    maps = shadow_map(casters, light, device=scene.verts.device)
+    nv = ops._view_calibs(who, cams[0]).shape[0]
+    h, w = ops._render_size(who, res)
+    positions = torch.empty((len(cams), nv, h, w, 3), dtype=torch.float32, device=scene.verts.device).unbind(0)
+    backs = ops.render_scene_batch(who, scene, cams, res, projection, nearest, near, perspective_correct, background,
+                                   positions=positions)
+    images = [b[0] for b in backs]
+    ops.picture_shadow_batch(images, positions, [b[2] for b in backs], [m[0] for m in maps], [m[1] for m in maps],
+                             light.calib, light.projection, light.nearest, light.bias, light.radius, light.strength,
+                             out=(images, None), who=who)
+    return backs
+
+
+@torch.no_grad()
 def render_scene(scene, calibs, res=257, projection="orthogonal", nearest="max", near=None, perspective_correct=False,
-                 background=1.0):
+                 background=1.0, casters=None):
     """The textured picture of a ``Scene`` under ``calibs`` ([4,4] / [3,4], or [n_views, ...]): the rasteriser writes a
     UV picture (``near`` / ``perspective_correct`` as in ``render_mesh``), ``ops.picture_texture_batch`` looks the
     texture up per pixel at the nearest mip level, bilinearly.  Returns a ``MeshRender``; pixels the scene does not
     cover hold ``background``.  No host sync.  The scene goes through the rasteriser as any mesh does: a clipped face
     that still projects beyond its 2^22 snap guard is dropped whole (``near`` far below 0.05 with a 3 m floor at
-    1024^2); the side planes are not clipped."""
+    1024^2); the side planes are not clipped.  ``casters``: None, or the ``Mesh`` whose shadow falls on the scene under
+    ``scene.light`` (ignored without a light): the picture is then the shadowed one."""
     _check_scene("render_scene", scene)
-    image, depth, face = ops.render_scene_batch("render_scene", scene, [calibs], res, projection, nearest, near,
-                                                perspective_correct, background)[0]
+    image, depth, face = _scene_pictures("render_scene", scene, None if casters is None else [casters], [calibs], res,
+                                         projection, nearest, near, perspective_correct, background)[0]
     if _single_camera(calibs):
         image, depth, face = image[0], depth[0], face[0]
     return MeshRender(image, depth, face)
@@ -695,7 +841,9 @@ def render_mesh_many_in_scene(meshes, scene, calibs, res=257, shade="colors", pr
     (``calibs``: one camera set for all, or a list with one per mesh), ``composite``: "depth" or "over".  Returns a
     list of ``ScenePicture``s; a ``None`` mesh gives the bare scene (mask in {0, 1}, face -1).  ``shade`` may not be
     None: the composite is of images.  Two more launches per ops.MAX_FRAMES pictures than the two renders; no host
-    sync."""
+    sync.  With ``scene.light`` every mesh also casts its shadow on its own picture of the scene before the composite:
+    its shadow map under the light, a position pass of the scene and ``ops.picture_shadow_batch``; without a light
+    nothing more is enqueued than before."""
     who = "render_mesh_many_in_scene"
     _check_scene(who, scene)
     if shade is None:
@@ -707,7 +855,7 @@ def render_mesh_many_in_scene(meshes, scene, calibs, res=257, shade="colors", pr
     cams = _camera_sets(who, calibs, len(meshes))
     fronts = render_mesh_many(meshes, calibs, res, shade, projection, nearest, background, near, perspective_correct,
                               netC=netC, feat_tensors_C=feat_tensors_C, calib_tensors=calib_tensors, view=view)
-    backs = ops.render_scene_batch(who, scene, cams, res, projection, nearest, near, perspective_correct, background)
+    backs = _scene_pictures(who, scene, meshes, cams, res, projection, nearest, near, perspective_correct, background)
     pairs = []
     for front, back, cam in zip(fronts, backs, cams):
         if front is None:  # no subject: an uncovered picture of the scene's size

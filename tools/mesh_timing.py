@@ -72,6 +72,13 @@ mip chain, composited by depth -- at one 257^2 and one 1024^2 view, per-frame mi
 
     python tools/mesh_timing.py --scene [--passes 5] [--out profiles/mesh_scene_timing.json]
 
+``--shadow`` measures the subject's shadow on that scene (profiles/mesh_shadow_timing.json): the ``--scene`` set-up, the
+slots WITH the scene, each without and with ``light=`` on it -- ``Light.directional`` from above and the side, fitted to
+the scene's box, a 512^2 map, radius 1 -- at one 257^2 and one 1024^2 view, with the shadowed pixels of frame 0.  The
+rows without a light are the comparison.
+
+    python tools/mesh_timing.py --shadow [--passes 5] [--out profiles/mesh_shadow_timing.json]
+
 The protocol of tools/recon_views_timing.py: after a warm-up of all, the passes alternate; a pass is `meshes`
 meshes, wall clock around a final stream sync.  Prints (and writes) one JSON line: per way the median, minimum and
 maximum time per mesh (ms) over the passes.  The verdict fields restate what to check: (b) not slower than (a) by
@@ -113,12 +120,14 @@ def main():
     ap.add_argument("--clip", action="store_true", help="with --render: the clipped form beside the unclipped call")
     ap.add_argument("--deferred", action="store_true", help="slot pictures coloured per vertex against per pixel")
     ap.add_argument("--scene", action="store_true", help="slot pictures with and without a textured scene behind them")
+    ap.add_argument("--shadow", action="store_true", help="slot pictures over a scene, without and with a light on it")
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "mesh_render_clip_timing.json" if a.render and a.clip else
                              "mesh_render_timing.json" if a.render else
                              "mesh_deferred_timing.json" if a.deferred else
                              "mesh_scene_timing.json" if a.scene else
+                             "mesh_shadow_timing.json" if a.shadow else
                              "mesh_smooth_timing.json" if a.smooth else
                              "mesh_simplify_timing.json" if a.simplify else
                              "keep_largest_timing.json" if a.clean else
@@ -128,6 +137,9 @@ def main():
         return
     if a.scene:
         write(a, slot_scene(a))
+        return
+    if a.shadow:
+        write(a, slot_shadow(a))
         return
     mlp = ops.PackedMLP.from_layers(DEV, syn.body_mlp("G", noise=0.05, seed=1), 1)
     fh = ops.pack_features(torch.from_numpy(syn.body_feat(256, 128, 128, 2))[None].to(DEV))
@@ -468,15 +480,13 @@ def slot_deferred(a, frames=20):
     return out
 
 
-def slot_scene(a, frames=20):
-    """The 20-frame slot with normal-shaded pictures under a free perspective camera, with and without a textured 3 m
-    floor (a 2048^2 checker, full mip chain) composited behind the subject by depth: per-frame ms of a submission
-    (``pictures()`` included) at one 257^2 and one 1024^2 view, and what the composite shows in frame 0."""
+def _scene_setup(light=None):
+    """The floor, the camera, the mesh options and the picture options that --scene and --shadow share."""
     i, j = np.meshgrid(np.arange(2048), np.arange(2048), indexing="ij")
     tex = np.stack([(((i // 64) + (j // 64)) % 2) * 200 + 40, i // 8, j // 8], -1).astype(np.uint8)
     y = -0.9
     floor = recon.Scene([[-1.5, y, -1.5], [1.5, y, -1.5], [1.5, y, 1.5], [-1.5, y, 1.5]], [[0, 1, 2], [0, 2, 3]],
-                        [[0, 0], [1, 0], [1, 1], [0, 1]], tex, device=DEV)
+                        [[0, 0], [1, 0], [1, 1], [0, 1]], tex, device=DEV, light=light)
     c, s_ = np.cos(-0.35), np.sin(-0.35)  # from above: the floor fills the lower part
     cam = np.eye(4, dtype=np.float32)
     cam[:3, :3] = np.diag([2.0, 2.0, 1.0]) @ np.array([[1, 0, 0], [0, c, -s_], [0, s_, c]])
@@ -484,6 +494,45 @@ def slot_scene(a, frames=20):
     cam = torch.from_numpy(cam)[None]
     mesh = {"normals": "accumulate", "colors": False}
     base = dict(views=1, shade="normals", projection="perspective", nearest="min", near=0.3, perspective_correct=True)
+    return floor, cam, mesh, base
+
+
+def slot_shadow(a, frames=20):
+    """The --scene slots with the floor, without and with a directional light on it (a 512^2 shadow map, radius 1):
+    per-frame ms of a submission (``pictures()`` included) at one 257^2 and one 1024^2 view, and the pixels of frame 0
+    that the shadow darkens."""
+    sun = recon.Light.directional((0.4, -1.0, 0.3), (-1.5, -0.9, -1.5), (1.5, 1.0, 1.5), res=512, radius=1)
+    floor, cam, mesh, base = _scene_setup()
+    lit = _scene_setup(sun)[0]
+    rows = (("scene_257", mesh, dict(base, res=257, scene=floor), cam), ("lit_257", mesh, dict(base, res=257, scene=lit), cam),
+            ("scene_1024", mesh, dict(base, res=1024, scene=floor), cam),
+            ("lit_1024", mesh, dict(base, res=1024, scene=lit), cam))
+    pipes, fn = _slot_pipes(frames, 1, rows)
+    out = {"frames_per_slot": frames, "unit": "ms per frame", "shadow_map": list(sun.res), "radius": sun.radius,
+           "light": "directional (0.4, -1, 0.3), fitted to the box of the floor and the body",
+           "camera": "perspective, turned -0.35 rad about x (looking down), near 0.3, perspective-correct"}
+    out.update(alternate({name: fn(name) for name in pipes}, a.passes, frames))
+    out["shadowed_pixels_frame0"] = {}
+    for name, p_ in pipes.items():
+        slot = p_.slots[0]
+        slot.pictures()
+        if hasattr(slot, "scene_lit"):
+            out["shadowed_pixels_frame0"][name] = int((slot.scene_lit[0] != slot.scene_image[0]).any(-1).sum().item())
+        p_.close()
+    for res in ("257", "1024"):
+        lit_row, plain = out["lit_" + res], out["scene_" + res]
+        out["lit_%s_minus_scene_ms" % res] = round(lit_row["median_ms"] - plain["median_ms"], 4)
+        out["lit_%s_inside_the_spread" % res] = bool(
+            lit_row["median_ms"] - plain["median_ms"] <= max(lit_row["max_ms"] - lit_row["min_ms"],
+                                                             plain["max_ms"] - plain["min_ms"]))
+    return out
+
+
+def slot_scene(a, frames=20):
+    """The 20-frame slot with normal-shaded pictures under a free perspective camera, with and without a textured 3 m
+    floor (a 2048^2 checker, full mip chain) composited behind the subject by depth: per-frame ms of a submission
+    (``pictures()`` included) at one 257^2 and one 1024^2 view, and what the composite shows in frame 0."""
+    floor, cam, mesh, base = _scene_setup()
     rows = (("plain_257", mesh, dict(base, res=257), cam), ("scene_257", mesh, dict(base, res=257, scene=floor), cam),
             ("plain_1024", mesh, dict(base, res=1024), cam), ("scene_1024", mesh, dict(base, res=1024, scene=floor), cam))
     pipes, fn = _slot_pipes(frames, 1, rows)
