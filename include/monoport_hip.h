@@ -938,6 +938,62 @@ int mp_picture_shadow_batch(mp_ctx *ctx, int n_frames, const float *const *image
                             int nearest, float bias, int radius, float strength, float *const *image_out,
                             float *const *shade, mp_stream stream);
 
+/* ---- lighting the subject per pixel: second-order spherical harmonics and one directional light at the normal -------
+ * The reference's lighting model (its SH fragment shader and ShRender: nine basis values at the normal, nine RGB
+ * coefficients, a gamma, clamp(albedo * shading, 0, 1)), plus one directional light that mp_picture_shadow's shade can
+ * occlude.  A frame's pictures are one flat array of L = n_views * H * W pixels as mp_mesh_render_batch lays them out.
+ * Per frame: normal f32 [L,3], the rasteriser's image for attr = the mesh's normals with the paint (1, 0, -inf, inf);
+ * face_id int32 [L]; albedo f32 [L,3], or NULL as a whole and then albedo_rgb (HOST, 3 floats) is every pixel's albedo;
+ * visibility f32 [L] or NULL: the `shade` of mp_picture_shadow, 1 = the light is fully occluded.  Per call, HOST:
+ * sh, 27 floats [9][3] (coefficient i, channel c at sh[3 i + c]); direct_dir[3], the direction the light TRAVELS, and
+ * direct_rgb[3] (all three == 0: there is no direct term); gamma (finite, > 0); normal_mats, NULL or n_frames * n_views
+ * row-major 3x3 matrices, frame-major: SH is then evaluated at the normal turned into the camera's frame (the
+ * reference's ModelMat * a_Normal); background: what an uncovered pixel of image_out holds without an albedo buffer.
+ * Outputs: image_out f32 [L,3] and shading f32 [L,3]; either may be NULL, not both.  A pure function of its inputs,
+ * defined bit for bit: every float operation is ONE IEEE f32 +, -, *, / or sqrtf (the correctly rounded ones), in the
+ * order written, without FMA (light.hip; no atomics, no scratch).  max0(a) is a where a > 0, else +0.0 (a NaN, a -0.0:
+ * +0.0).  Per pixel p:
+ *   1. Uncovered.  face_id < 0: shading = (0, 0, 0); image_out takes albedo's 32-bit patterns (in place: the pixel is
+ *      not written at all), or `background` three times without an albedo buffer.
+ *   2. The world normal.  s = (nx*nx + ny*ny) + nz*nz.  s not finite or not > 0: u = (0, 0, 0).  Else len = sqrtf(s),
+ *      u = (nx / len, ny / len, nz / len).
+ *   3. The SH normal.  Without normal_mats: m = u, the same bits.  With them, M = the matrix of the pixel's frame and
+ *      view p / (L / n_views): t_r = (M[r][0]*ux + M[r][1]*uy) + M[r][2]*uz for r = 0, 1, 2, and m = t normalised by
+ *      the rule of step 2.
+ *   4. The basis, with c1..c5 the f32 nearest to 0.429043, 0.511664, 0.743125, 0.886227, 0.247708 and d1 = 2.0f * c1,
+ *      d2 = 2.0f * c2 (exact): H0 = c4, H1 = d2 * my, H2 = d2 * mz, H3 = d2 * mx, H4 = (d1 * mx) * my,
+ *      H5 = (d1 * my) * mz, H6 = ((c3 * mz) * mz) - c5, H7 = (d1 * mz) * mx, H8 = c1 * ((mx * mx) - (my * my)).
+ *      res_c = 0.0f, then res_c = res_c + H[i] * sh[3 i + c] for i = 0..8 ascending.
+ *   5. The direct term (skipped as a whole where direct_rgb is all zero), always on the WORLD normal u:
+ *      k = max0(-((dx*ux + dy*uy) + dz*uz)); vis = 1.0f - visibility[p], or 1.0f without the buffer;
+ *      res_c = res_c + (k * vis) * direct_rgb[c].
+ *   6. Gamma.  gamma == 1.0f: nothing (the bit-exact form).  Else res_c = powf(max0(res_c), 1.0f / gamma), the one
+ *      step held to a tolerance instead of the bits (1.0f / gamma is one f32 division on the host).
+ *   7. shading[c] = res_c; image_out[c] = clamp(albedo_c * res_c): v < 0 gives 0, v > 1 gives 1, else v (mp_paint's
+ *      clamp: a NaN stays).
+ * image_out may BE albedo of the same frame (in place); any other byte shared between an output and an input, or
+ * between the two outputs, is refused.  One launch, one thread per pixel: 16 B (+ 12 B albedo, + 4 B visibility) read
+ * and up to 24 B written per covered pixel; an uncovered span reads its face ids only.
+ * MP_ERR_ARG: n_frames outside 1..mp_max_frames(); n_pixels < 1; n_views < 1 or not a divisor of n_pixels; with
+ * normal_mats, n_frames * n_views > 32 (what the kernel's argument block holds); sh, direct_dir or direct_rgb NULL;
+ * albedo and albedo_rgb both NULL or both given; a gamma that is not finite or <= 0; a non-finite value among sh,
+ * direct_dir, direct_rgb, albedo_rgb, background or normal_mats; no output; a NULL or not 4-byte aligned buffer of any
+ * frame; the aliasing above.  MP_ERR_UNSUPPORTED: L beyond 2^31 / 3.  Each refusal leaves an mp_last_error message and
+ * launches nothing.  Asynchronous, nothing synchronised, no scratch arena.  The per-frame call is the batched one with
+ * one frame; in the batched one normal / face_id / albedo / visibility / image_out / shading are HOST arrays of
+ * n_frames device pointers (one parameter set for all), blockIdx.y is the frame: frame f's outputs equal the per-frame
+ * call's on frame f's inputs BIT FOR BIT.
+ * NOT built: lighting the scene by the same model, several lights, specular terms, precomputed radiance transfer. */
+int mp_picture_light(mp_ctx *ctx, const float *normal, const int32_t *face_id, const float *albedo,
+                     const float *albedo_rgb, const float *visibility, int64_t n_pixels, int n_views, const float *sh,
+                     const float *direct_dir, const float *direct_rgb, float gamma, const float *normal_mats,
+                     float background, float *image_out, float *shading, mp_stream stream);
+int mp_picture_light_batch(mp_ctx *ctx, int n_frames, const float *const *normal, const int32_t *const *face_id,
+                           const float *const *albedo, const float *albedo_rgb, const float *const *visibility,
+                           int64_t n_pixels, int n_views, const float *sh, const float *direct_dir,
+                           const float *direct_rgb, float gamma, const float *normal_mats, float background,
+                           float *const *image_out, float *const *shading, mp_stream stream);
+
 /* The largest connected body of an occupancy volume [R,R,R] (no counterpart in the reference; the clean-up in front
  * of marching cubes that drops floating blobs).
  *   Foreground: voxels with value > level (marching cubes' "inside"; a NaN and value == level are background).

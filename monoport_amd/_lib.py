@@ -224,6 +224,10 @@ SIGNATURES = {
                                   c_int, c_f32, c_vp, c_vp, c_vp]),
     "mp_picture_shadow_batch": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, _pf32, c_int,
                                         c_int, c_f32, c_int, c_f32, c_vp, c_vp, c_vp]),
+    "mp_picture_light": (c_int, [c_vp, c_vp, c_vp, c_vp, _pf32, c_vp, c_i64, c_int, _pf32, _pf32, _pf32, c_f32, _pf32,
+                                 c_f32, c_vp, c_vp, c_vp]),
+    "mp_picture_light_batch": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, _pf32, c_vp, c_i64, c_int, _pf32, _pf32, _pf32,
+                                       c_f32, _pf32, c_f32, c_vp, c_vp, c_vp]),
     "mp_volume_keep_largest": (c_int, [c_vp, c_vp, c_int, c_f32, c_int, c_f32, c_vp, c_vp, c_vp]),
     "mp_volume_keep_largest_batch": (c_int, [c_vp, c_int, c_vp, c_int, c_f32, c_int, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "mp_group_norm": (c_int, [c_vp, c_vp, c_int, c_int, c_i64, c_int, c_vp, c_vp, c_f32, c_int, c_vp,

@@ -784,6 +784,69 @@ static int picture_shadow_checked(mp_ctx *ctx, const char *who, int n_frames, co
                                      (hipStream_t)stream);
 }
 
+static bool all_finite(const float *v, size_t n) {
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+
+static int picture_light_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *normal,
+                                 const int32_t *const *face_id, const float *const *albedo, const float *albedo_rgb,
+                                 const float *const *visibility, int64_t n_pixels, int n_views, const float *sh,
+                                 const float *direct_dir, const float *direct_rgb, float gamma,
+                                 const float *normal_mats, float background, float *const *image_out,
+                                 float *const *shading, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (n_pixels < 1) return fail(ctx, MP_ERR_ARG, "%s: n_pixels must be >= 1, got %lld", who, (long long)n_pixels);
+  if (n_pixels > 0x7fffffffLL / 3)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: pictures beyond 2^31 / 3 pixels need 64-bit indices", who);
+  if (n_views < 1 || n_pixels % n_views != 0)
+    return fail(ctx, MP_ERR_ARG, "%s: n_views must be >= 1 and divide n_pixels = %lld, got %d", who,
+                (long long)n_pixels, n_views);
+  if (normal_mats && (long long)n_frames * n_views > kLightMaxMats)
+    return fail(ctx, MP_ERR_ARG, "%s: at most %d normal matrices (frames x views) per call, got %d x %d", who,
+                kLightMaxMats, n_frames, n_views);
+  if (!sh || !direct_dir || !direct_rgb || !normal || !face_id) return bad_argument(ctx, who);
+  if (!albedo == !albedo_rgb)
+    return fail(ctx, MP_ERR_ARG, "%s: either albedo buffers or a constant albedo_rgb, not %s", who,
+                albedo ? "both" : "neither");
+  if (!std::isfinite(gamma) || !(gamma > 0.0f))
+    return fail(ctx, MP_ERR_ARG, "%s: gamma must be finite and > 0, got %g", who, (double)gamma);
+  if (!all_finite(sh, 27) || !all_finite(direct_dir, 3) || !all_finite(direct_rgb, 3) ||
+      (albedo_rgb && !all_finite(albedo_rgb, 3)) || !std::isfinite(background) ||
+      (normal_mats && !all_finite(normal_mats, (size_t)9 * n_frames * n_views)))
+    return fail(ctx, MP_ERR_ARG, "%s: sh, direct_dir, direct_rgb, albedo_rgb, background and normal_mats must be finite",
+                who);
+  if (!image_out && !shading) return fail(ctx, MP_ERR_ARG, "%s: no output requested", who);
+  rc = check_frames(ctx, who, n_frames, nullptr, normal, face_id, albedo, visibility, image_out, shading);
+  if (rc != MP_OK) return rc;
+  // image_out may BE albedo of the same frame (a thread reads its pixel before it writes it); any other byte shared
+  // between an output and an input, or between the two outputs, is refused
+  const size_t px = (size_t)n_pixels;
+  const FrameSpans ins[4] = {{albedo, px * 12}, {normal, px * 12}, {face_id, px * 4}, {visibility, px * 4}};
+  const FrameSpans outs[2] = {{image_out, px * 12}, {shading, px * 12}};
+  for (int f = 0; f < n_frames; ++f)
+    for (int i = 0; i < n_frames; ++i) {
+      for (int o = 0; o < 2; ++o)
+        for (int k = 0; k < 4; ++k) {
+          if (!ranges_overlap(outs[o].of(f), outs[o].bytes, ins[k].of(i), ins[k].bytes)) continue;
+          if (!(o == 0 && k == 0 && f == i && outs[o].of(f) == ins[k].of(i)))
+            return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases an input of frame %d", who, f, i);
+        }
+      if (ranges_overlap(outs[0].of(f), px * 12, outs[1].of(i), px * 12) ||
+          (f != i && (ranges_overlap(outs[0].of(f), px * 12, outs[0].of(i), px * 12) ||
+                      ranges_overlap(outs[1].of(f), px * 12, outs[1].of(i), px * 12))))
+        return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases an output of frame %d", who, f, i);
+    }
+  DeviceGuard g(ctx->device);
+  return launch_picture_light_batch(ctx, n_frames, normal, face_id, albedo, albedo_rgb, visibility, n_pixels, n_views,
+                                    sh, direct_dir, direct_rgb, gamma, normal_mats, background, image_out, shading,
+                                    (hipStream_t)stream);
+}
+
 static int keep_largest_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *volume, int r,
                                 float level, int connectivity, float fill, float *const *out, int32_t *const *stats,
                                 const int32_t *const *gate, mp_stream stream) {
@@ -1913,6 +1976,26 @@ int mp_picture_shadow_batch(mp_ctx *ctx, int n_frames, const float *const *image
   return picture_shadow_checked(ctx, "mp_picture_shadow_batch", n_frames, image_in, position, face_id, n_pixels,
                                 map_depth, map_face, hs, ws, light_calibs, projection, nearest, bias, radius, strength,
                                 image_out, shade, stream);
+}
+
+int mp_picture_light(mp_ctx *ctx, const float *normal, const int32_t *face_id, const float *albedo,
+                     const float *albedo_rgb, const float *visibility, int64_t n_pixels, int n_views, const float *sh,
+                     const float *direct_dir, const float *direct_rgb, float gamma, const float *normal_mats,
+                     float background, float *image_out, float *shading, mp_stream stream) {
+  return picture_light_checked(ctx, "mp_picture_light", 1, &normal, &face_id, albedo ? &albedo : nullptr, albedo_rgb,
+                               visibility ? &visibility : nullptr, n_pixels, n_views, sh, direct_dir, direct_rgb, gamma,
+                               normal_mats, background, image_out ? &image_out : nullptr,
+                               shading ? &shading : nullptr, stream);
+}
+
+int mp_picture_light_batch(mp_ctx *ctx, int n_frames, const float *const *normal, const int32_t *const *face_id,
+                           const float *const *albedo, const float *albedo_rgb, const float *const *visibility,
+                           int64_t n_pixels, int n_views, const float *sh, const float *direct_dir,
+                           const float *direct_rgb, float gamma, const float *normal_mats, float background,
+                           float *const *image_out, float *const *shading, mp_stream stream) {
+  return picture_light_checked(ctx, "mp_picture_light_batch", n_frames, normal, face_id, albedo, albedo_rgb, visibility,
+                               n_pixels, n_views, sh, direct_dir, direct_rgb, gamma, normal_mats, background, image_out,
+                               shading, stream);
 }
 
 int mp_volume_keep_largest(mp_ctx *ctx, const float *volume, int r, float level, int connectivity, float fill,

@@ -493,6 +493,16 @@ int launch_picture_shadow_batch(mp_ctx *ctx, int n_frames, const float *const *i
                                 const int32_t *const *map_face, int hs, int ws, const float *light_calibs, int proj,
                                 int nearest, float bias, int radius, float strength, float *const *image_out,
                                 float *const *shade, hipStream_t st);
+// light.hip: n_frames pictures of n_pixels = n_views * (pixels per view) each, lit by one parameter set (sh[27],
+// direct_dir[3], direct_rgb[3], gamma, background: host).  albedo: nullptr (then albedo_rgb[3], host) or n_frames
+// entries; visibility, image_out (may be albedo[f]), shading: nullptr or n_frames entries.  normal_mats: nullptr or
+// host, n_frames * n_views (<= kLightMaxMats) row-major 3x3
+constexpr int kLightMaxMats = 32;
+int launch_picture_light_batch(mp_ctx *ctx, int n_frames, const float *const *normal, const int32_t *const *face_id,
+                               const float *const *albedo, const float *albedo_rgb, const float *const *visibility,
+                               long long n_pixels, int n_views, const float *sh, const float *direct_dir,
+                               const float *direct_rgb, float gamma, const float *normal_mats, float background,
+                               float *const *image_out, float *const *shading, hipStream_t st);
 
 // conv3x3.hip
 int launch_conv3x3_pack(mp_ctx *ctx, const float *w, int cout, int cin, float *wp, hipStream_t st);

@@ -1759,7 +1759,8 @@ def picture_paint_batch(values, pixels, counts, n_pixels=None, scale=0.5, bias=0
 
 
 def render_netc_batch(who, verts, faces, counts, calibs, res, query, projection="orthogonal", nearest="max",
-                      background=1.0, out=None, lists=None, capacity=None, near=None, perspective_correct=False):
+                      background=1.0, out=None, lists=None, capacity=None, near=None, perspective_correct=False,
+                      positions_hook=None):
     """Pictures coloured per pixel (deferred shading), no host value in between: (1) the rasteriser with ``attr =
     verts`` -- a picture of world-space surface positions -- under the pictures' own cameras, projection, ``near`` and
     ``perspective_correct``; (2) ``picture_points_batch`` over each mesh's views as one flat picture (capacity = its
@@ -1769,13 +1770,16 @@ def render_netc_batch(who, verts, faces, counts, calibs, res, query, projection=
     -inf, inf) into the picture the positions came from.  Returns what ``_mesh_render`` does: per mesh (image
     [n_views,H,W,3] = query * 0.5 + 0.5 at covered pixels and ``background`` elsewhere, depth, face).  ``out``: (image,
     depth or None, face) buffers; ``lists``: (points [n,3,L], pixels [n,L], count [n,2]) buffers.  ``capacity``: as in
-    ``_mesh_render``."""
+    ``_mesh_render``.  ``positions_hook(positions, face_ids)``: called between (1) and (4), while the images still
+    hold the positions -- what a self-shadow reads (``self_shades``), so that no second position pass is needed."""
     if out is not None and (out[0] is None or out[2] is None):
         raise ValueError("%s: a picture coloured per pixel needs the image and the face ids" % who)
     raws = _mesh_render(who, verts, faces, counts, list(verts), calibs, res, projection, nearest, False, 1.0, 0.0,
                         -math.inf, math.inf, background, out, capacity=capacity, near=near,
                         perspective_correct=perspective_correct)
     images, face_ids = [r[0] for r in raws], [r[2] for r in raws]
+    if positions_hook is not None:
+        positions_hook(images, face_ids)
     found = _picture_points(who, face_ids, images, None, lists)
     preds = query([f[0] for f in found], [f[2] for f in found])
     _picture_paint(who, list(preds), [f[1] for f in found], [f[2] for f in found], images, 0.5, 0.5, -math.inf, math.inf)
@@ -1999,6 +2003,185 @@ def picture_shadow_batch(images, positions, face_ids, map_depths, map_faces, lig
             None if image is None else _ptr_array(image[f0:f1]), None if shade is None else _ptr_array(shade[f0:f1]),
             _stream(positions[0])), "mp_picture_shadow_batch")
     return [(None if image is None else image[f], None if shade is None else shade[f]) for f in range(n)]
+
+
+def _finite_floats(who, what, value, shape):
+    try:
+        a = np.array(value.detach().cpu().numpy() if torch.is_tensor(value) else value, dtype=np.float32)
+    except (TypeError, ValueError):
+        a = None
+    if a is None or a.shape != shape or not np.isfinite(a).all():
+        raise ValueError("%s: %s must be finite float values of shape %s, got %r" % (who, what, shape, value))
+    return np.ascontiguousarray(a)
+
+
+def light_params(who, sh, direct=None, gamma=1.0, albedo_rgb=None):
+    """(sh [9,3], direct_dir [3], direct_rgb [3], gamma, albedo_rgb [3] or None) of mp_picture_light as float32 host
+    values, or the ValueError of a value it refuses.  ``direct``: None (no direct light: zeros), or a (direction the
+    light travels, rgb) pair, passed on as given (the caller normalises the direction)."""
+    sh = _finite_floats(who, "sh", sh, (9, 3))
+    if direct is None:
+        ddir, drgb = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    else:
+        try:
+            ddir, drgb = direct
+        except (TypeError, ValueError):
+            raise ValueError("%s: direct must be None or a (direction, rgb) pair, got %r" % (who, direct)) from None
+        ddir = _finite_floats(who, "direct's direction", ddir, (3,))
+        drgb = _finite_floats(who, "direct's rgb", drgb, (3,))
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)):
+        raise ValueError("%s: gamma must be a number, got %r" % (who, gamma))
+    gamma = float(np.float32(gamma))
+    if not (math.isfinite(gamma) and gamma > 0):
+        raise ValueError("%s: gamma must be finite and > 0, got %r" % (who, gamma))
+    if albedo_rgb is not None:
+        albedo_rgb = _finite_floats(who, "albedo", albedo_rgb, (3,))
+    return sh, ddir, drgb, gamma, albedo_rgb
+
+
+def normal_mats_of(who, calibs):
+    """The [n_views,3,3] float32 normal matrices of one camera set: the 3x3 of each view's [R|t], which
+    ``picture_light_batch`` applies to the unit normal and normalises again (so a scaled rotation is a rotation)."""
+    return np.ascontiguousarray(_view_calibs(who, calibs).reshape(-1, 3, 4)[:, :, :3])
+
+
+def picture_light_batch(normals, face_ids, albedos, sh, direct=None, gamma=1.0, normal_mats=None, visibilities=None,
+                        albedo_rgb=None, n_views=None, background=1.0, out=None, with_shading=False,
+                        who="picture_light_batch"):
+    """mp_picture_light_batch: per frame the lit picture of a normal picture.  ``normals``: float32 [...,3] per frame,
+    the rasteriser's image for ``attr = mesh normals`` with the paint (1, 0, -inf, inf), ``face_ids`` its int32 [...];
+    ``albedos``: the float32 [...,3] pictures to light, or None with a constant ``albedo_rgb`` (r, g, b).  ``sh``: [9,3]
+    second-order spherical-harmonic coefficients; ``direct``: None, or a (direction the light travels, rgb) pair;
+    ``visibilities``: None, or per frame the float32 [...] ``shade`` of ``picture_shadow_batch`` (1 = the direct light
+    is occluded); ``gamma``: 1.0 (nothing, the bit-exact form) or the exponent's inverse; ``normal_mats``: None (SH at
+    the world normal) or host [n_views,3,3] for all frames / [n,n_views,3,3]: SH at the normal in each camera's frame;
+    ``n_views``: the views of a frame's picture (None: the leading dimension of a [n_views,H,W,3] picture, else 1).
+    Covered pixels hold clamp(albedo * shading, 0, 1), uncovered ones the albedo's bits (``background`` without albedo
+    pictures) and shading 0.  Defined bit for bit in include/monoport_hip.h.  ``out``: (images or None, shadings or
+    None) to write; the images may be ``albedos`` themselves (in place).  None: fresh images and, with
+    ``with_shading``, fresh shadings [...,3].  Returns per frame (image or None, shading or None).  One launch per
+    MAX_FRAMES frames (with ``normal_mats``: per MAX_FRAMES frames x views); no host sync."""
+    n = len(normals)
+    if n == 0 or normals[0].dim() < 2 or normals[0].shape[-1] != 3:
+        raise ValueError("%s: at least one normal picture [...,3]" % who)
+    shape = tuple(normals[0].shape[:-1])
+    dev, npix = normals[0].device, normals[0].numel() // 3
+    if npix < 1:
+        raise ValueError("%s: at least one pixel" % who)
+    if n_views is None:
+        n_views = int(shape[0]) if len(shape) == 3 else 1
+    if isinstance(n_views, bool) or not isinstance(n_views, (int, np.integer)) or n_views < 1 or npix % n_views:
+        raise ValueError("%s: n_views must be an int >= 1 that divides the %d pixels, got %r" % (who, npix, n_views))
+    nv = int(n_views)
+    normals = _flat_pictures(who, "normals", normals, n, torch.float32, 3, npix, dev)
+    face_ids = _flat_pictures(who, "face_ids", face_ids, n, torch.int32, 1, npix, dev)
+    if albedos is not None:
+        albedos = _flat_pictures(who, "albedos", albedos, n, torch.float32, 3, npix, dev)
+    if visibilities is not None:
+        visibilities = _flat_pictures(who, "visibilities", visibilities, n, torch.float32, 1, npix, dev)
+    if (albedos is None) == (albedo_rgb is None):
+        raise ValueError("%s: either albedo pictures or a constant albedo_rgb, not %s"
+                         % (who, "neither" if albedos is None else "both"))
+    sh, ddir, drgb, gamma, albedo_rgb = light_params(who, sh, direct, gamma, albedo_rgb)
+    background = float(background)
+    if not math.isfinite(background):
+        raise ValueError("%s: background must be finite, got %r" % (who, background))
+    mats = None
+    if normal_mats is not None:
+        mats = np.asarray(normal_mats, np.float32)
+        if mats.shape == (nv, 3, 3):
+            mats = np.broadcast_to(mats, (n, nv, 3, 3))
+        if mats.shape != (n, nv, 3, 3) or not np.isfinite(mats).all():
+            raise ValueError("%s: normal_mats must be finite [%d,3,3] or [%d,%d,3,3], got %s"
+                             % (who, nv, n, nv, tuple(np.shape(normal_mats))))
+    if out is None:
+        image = torch.empty((n,) + shape + (3,), dtype=torch.float32, device=dev).unbind(0)
+        shading = torch.empty((n,) + shape + (3,), dtype=torch.float32, device=dev).unbind(0) if with_shading else None
+    else:
+        image = None if out[0] is None else _flat_pictures(who, "out[0] (image)", out[0], n, torch.float32, 3, npix, dev)
+        shading = (None if out[1] is None
+                   else _flat_pictures(who, "out[1] (shading)", out[1], n, torch.float32, 3, npix, dev))
+    if image is None and shading is None:
+        raise ValueError("%s: out names no output" % who)
+    ctx = get_context(dev)
+    # with matrices a call holds frames x views <= MAX_FRAMES of them: a frame's views are then split as its pixels are
+    vstep = nv if mats is None else min(nv, MAX_FRAMES)
+    fstep = MAX_FRAMES if mats is None else MAX_FRAMES // vstep
+
+    def ptrs(rows, f0, f1, v0, v1):
+        if rows is None:
+            return None
+        return _ptr_array([r if (v0, v1) == (0, nv) else r.view(nv, -1)[v0:v1] for r in rows[f0:f1]])
+
+    pf = lambda a: None if a is None else np.ascontiguousarray(a).ctypes.data_as(_lib._pf32)  # noqa: E731
+    for v0 in range(0, nv, vstep):
+        v1 = min(v0 + vstep, nv)
+        for f0 in range(0, n, fstep):
+            f1 = min(f0 + fstep, n)
+            m = None if mats is None else np.ascontiguousarray(mats[f0:f1, v0:v1])
+            ctx.check(ctx.lib.mp_picture_light_batch(
+                ctx.handle, f1 - f0, ptrs(normals, f0, f1, v0, v1), ptrs(face_ids, f0, f1, v0, v1),
+                ptrs(albedos, f0, f1, v0, v1), pf(albedo_rgb), ptrs(visibilities, f0, f1, v0, v1),
+                npix // nv * (v1 - v0), v1 - v0, pf(sh), pf(ddir), pf(drgb), gamma, pf(m), background,
+                ptrs(image, f0, f1, v0, v1), ptrs(shading, f0, f1, v0, v1), _stream(normals[0])),
+                "mp_picture_light_batch")
+    return [(None if image is None else image[f], None if shading is None else shading[f]) for f in range(n)]
+
+
+def self_shades(who, positions, face_ids, lighting, shadow, out=None):
+    """Per subject the shade [n_views,H,W] of its own shadow map on its own surface: ``picture_shadow_batch`` for the
+    shade alone on the position pictures, against ``shadow`` = (the scene's ``recon.Light``, map depths, map faces) with
+    the bias ``lighting.self_shadow``.  ``out``: the shades' buffers."""
+    light, map_depths, map_faces = shadow
+    return [s[1] for s in picture_shadow_batch(
+        None, list(positions), list(face_ids), map_depths, map_faces, light.calib, light.projection, light.nearest,
+        lighting.self_shadow, light.radius, light.strength, out=None if out is None else (None, list(out)), who=who)]
+
+
+def light_pictures_batch(who, verts, faces, counts, normals, calibs, res, lighting, images, projection="orthogonal",
+                         nearest="max", background=1.0, near=None, perspective_correct=False, capacity=None, shadow=None,
+                         buffers=None, shades=None):
+    """The subjects' pictures ``images`` (per mesh [n_views,H,W,3], as ``_mesh_render`` / ``render_netc_batch`` left
+    them) lit in place by ``lighting`` (a ``recon.Lighting``: sh, direct_dir, direct_rgb, gamma, frame, albedo,
+    self_shadow), no host value in between: (1) a second pass of the rasteriser with ``attr = normals`` (per mesh
+    [V,3]) under the pictures' own cameras, ``near`` and ``perspective_correct``: the same faces, so the same face
+    ids; (2) with ``lighting.self_shadow``: a pass with ``attr = verts`` and ``picture_shadow_batch`` for the shade
+    alone, against ``shadow`` = (the scene's ``recon.Light``, map depths, map faces: one shadow map per mesh) with the
+    bias ``self_shadow``; (3) ``picture_light_batch``: the images are the albedo and the output, or -- with a constant
+    ``lighting.albedo`` -- the output only.  ``frame="camera"`` takes the 3x3 of every view's calib as its normal
+    matrix.  ``buffers``: None (fresh), or a dict with ``normal`` [n,n_views,H,W,3], ``face`` [n,n_views,H,W] and, for
+    the self-shadow, ``pos`` [n,n_views,H,W,3] and ``shade`` [n,n_views,H,W].  ``shades``: the self-shadow's shades
+    where the caller has made them from a position picture it had (``render_netc_batch``'s hook): step (2) is then
+    skipped.  Returns (per mesh the normal pass's (image, None, face), the shades or None)."""
+    n = len(verts)
+    out = None if buffers is None else (buffers["normal"], None, buffers["face"])
+    cams = _calib_list(calibs, n, who)
+    if out is None:  # fresh: the depth comes with them and is dropped
+        nraws = [(r[0], None, r[2]) for r in _mesh_render(
+            who, verts, faces, counts, normals, cams, res, projection, nearest, False, 1.0, 0.0, -math.inf, math.inf,
+            background, None, capacity=capacity, near=near, perspective_correct=perspective_correct)]
+    else:
+        nraws = _mesh_render(who, verts, faces, counts, normals, cams, res, projection, nearest, False, 1.0, 0.0,
+                             -math.inf, math.inf, background, out, capacity=capacity, near=near,
+                             perspective_correct=perspective_correct)
+    face_ids = [r[2] for r in nraws]
+    if lighting.self_shadow is None:
+        shades = None
+    elif shades is None:
+        pos = _mesh_render(who, verts, faces, counts, list(verts), cams, res, projection, nearest, False, 1.0, 0.0,
+                           -math.inf, math.inf, background, None if buffers is None else (buffers["pos"], None, None),
+                           capacity=capacity, near=near, perspective_correct=perspective_correct)
+        if buffers is None:
+            pos = [(p[0], None, None) for p in pos]
+        shades = self_shades(who, [p[0] for p in pos], face_ids, lighting, shadow,
+                             None if buffers is None else buffers["shade"][:n])
+    nv = nraws[0][0].shape[0]
+    mats = np.stack([normal_mats_of(who, c) for c in cams]) if lighting.frame == "camera" else None
+    direct = None if lighting.direct is None else (lighting.direct_dir, lighting.direct_rgb)
+    picture_light_batch([r[0] for r in nraws], face_ids, None if lighting.albedo is not None else list(images),
+                        lighting.sh, direct, lighting.gamma, mats, shades, lighting.albedo, nv, background,
+                        out=(list(images), None), who=who)
+    return nraws, shades
 
 
 def render_scene_batch(who, scene, calibs, res, projection="orthogonal", nearest="max", near=None,

@@ -130,7 +130,7 @@ class FrameSlot:
 
     def __init__(self, netG, device, resolutions=RESOLUTIONS, b_min=(-1, -1, -1), b_max=(1, 1, 1),
                  balance=0.5, feature_hook=None, use_graph=False, netC=None, batch=1, skip_table=None,
-                 final_level="dilate3", mesh=None, pictures=None):
+                 final_level="dilate3", mesh=None, pictures=None, lighting=None):
         """``mesh``: None (no mesh output; nothing is allocated or enqueued for it), or a dict / options object with
         ``normals`` ("accumulate" -- the default --, "reference" or None), ``level`` (the iso-level; default: the
         slot's ``balance``) and ``colors`` (per-vertex netC colours; default: ``netC is not None``) and ``clean`` (None
@@ -173,11 +173,29 @@ class FrameSlot:
         shows each frame's shadow on it: the slot then owns ``shadow_depth`` / ``shadow_face`` [batch,Hs,Ws] (the
         frames' shadow maps, rendered from the chain's mesh buffers), ``scene_pos`` (the scene's world-space positions)
         and ``scene_lit`` (the shadowed scene, which the composite takes; ``scene_image`` stays unshadowed), all filled
-        on the slot's stream.  Without a light none of them exists and nothing more is enqueued."""
+        on the slot's stream.  Without a light none of them exists and nothing more is enqueued.
+
+        ``lighting`` (a ``recon.Lighting``; None, the default: nothing is allocated or enqueued for it, and it is not a
+        ``pictures`` key) lights the subject's picture per pixel before the composite, as ``recon.render_mesh(lighting=)``
+        does: the slot then owns ``light_normal`` [batch,views,H,W,3] and ``light_face`` [batch,views,H,W] (a second
+        pass of the rasteriser with the chain's normals as the attribute) and, with ``lighting.self_shadow`` (it needs
+        the scene's light), ``light_shade`` [batch,views,H,W] (the subject's own shade under the frame's shadow map) and
+        ``light_pos`` [batch,views,H,W,3] (the subject's positions; not with ``shade="netC"``, whose position picture
+        is read before it is painted over); all filled on the slot's stream with no host value
+        in between, then ``ops.picture_light_batch`` in place on ``pictures_image``.  It needs pictures with a
+        ``shade``, the mesh's normals, and for ``shade="normals"`` a constant ``lighting.albedo``."""
         self.views = self._head_views(netG, netC, mesh)  # images per frame; refuses what the slot class does not run
-        # both option records are validated before anything is allocated
+        # the option records are validated before anything is allocated
         self.mesh = None if mesh is None else _mesh_options(mesh, float(balance), netC is not None)
         self.picture_options = None if pictures is None else _picture_options(pictures, self.mesh, netC is not None)
+        self.lighting = lighting
+        if lighting is not None:
+            from .recon import _check_lighting_options
+            po = self.picture_options
+            if po is None:
+                raise ValueError("FrameSlot(lighting=...): lighting shades the slot's pictures; it needs pictures=...")
+            _check_lighting_options("FrameSlot(lighting=...)", lighting, po.shade, self.mesh.normals is not None,
+                                    None if po.scene is None else po.scene.light)
         self.net = netG
         self.netC = netC
         self.device = torch.device(device)
@@ -283,6 +301,14 @@ class FrameSlot:
                     self.shadow_face = torch.empty((b, hs, ws), dtype=torch.int32, device=dev)
                     self.scene_pos = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
                     self.scene_lit = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
+            if self.lighting is not None:  # the normal pass and, for the self-shadow, the subject's positions and shade
+                shape = (b, po.views) + po.res
+                self.light_normal = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
+                self.light_face = torch.empty(shape, dtype=torch.int32, device=dev)
+                if self.lighting.self_shadow is not None:
+                    if po.shade != "netC":
+                        self.light_pos = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
+                    self.light_shade = torch.empty(shape, dtype=torch.float32, device=dev)
             # the cameras of the current submission, on the host [batch,views,3,4]; the identity until the first one
             self._cameras = np.tile(np.eye(4, dtype=np.float32)[:3], (b, po.views, 1, 1))
 
@@ -432,18 +458,20 @@ class FrameSlot:
         cameras, and the composite in place, follow on the same stream.  With a light in the scene: the n frames' shadow
         maps from the same mesh buffers (a gated-off frame's map is uncovered: no shadow), the scene's positions, and
         the shadow of ``scene_image`` into ``scene_lit``, which the composite then takes; ``scene_image`` stays
-        unshadowed for ``_scene_picture``."""
-        self._render_subjects(n)
+        unshadowed for ``_scene_picture``.  With ``lighting``: the subjects' pictures are lit in place before the
+        composite (``ops.light_pictures_batch`` into the slot's ``light_*`` buffers); its ``self_shadow`` reads the
+        frames' shadow maps, which are then rendered first."""
         po = self.picture_options
+        light = po.scene.light if hasattr(self, "scene_lit") else None
+        maps_first = self.lighting is not None and self.lighting.self_shadow is not None
+        if maps_first:
+            self._shadow_maps(n, light)
+        self._render_subjects(n)
+        if self.lighting is not None:
+            self._light_subjects(n, light)
         if po.scene is not None:  # the scene under the same cameras, then the composite in place
-            light = po.scene.light if hasattr(self, "scene_lit") else None
-            if light is not None:
-                chains = self._mesh_chains[:n]
-                ops.mesh_render_raw_batch([c.verts for c in chains], [c.faces for c in chains],
-                                          [c.counts for c in chains], None, [light.calib] * n, light.res,
-                                          light.projection, light.nearest,
-                                          out=(None, self.shadow_depth[:n].unsqueeze(1), self.shadow_face[:n].unsqueeze(1)),
-                                          near=light.near, perspective_correct=light.near is not None)
+            if light is not None and not maps_first:
+                self._shadow_maps(n, light)
             backs = ops.render_scene_batch("FrameSlot", po.scene, list(self._cameras[:n]), po.res, po.projection,
                                            po.nearest, po.near, po.perspective_correct, po.background,
                                            out=(self.scene_image[:n], self.scene_depth[:n], self.scene_face[:n]),
@@ -459,18 +487,51 @@ class FrameSlot:
                                         out=(self.pictures_image[:n], self.pictures_depth[:n], self.pictures_mask[:n]),
                                         who="FrameSlot")
 
+    def _shadow_maps(self, n, light):
+        """The n frames' shadow maps under the scene's light, from the chain's mesh buffers."""
+        chains = self._mesh_chains[:n]
+        ops.mesh_render_raw_batch([c.verts for c in chains], [c.faces for c in chains],
+                                  [c.counts for c in chains], None, [light.calib] * n, light.res,
+                                  light.projection, light.nearest,
+                                  out=(None, self.shadow_depth[:n].unsqueeze(1), self.shadow_face[:n].unsqueeze(1)),
+                                  near=light.near, perspective_correct=light.near is not None)
+
+    def _light_subjects(self, n, light):
+        """``lighting`` on the n frames' pictures, in place, from the chain's normals (a gated-off frame's normal pass
+        is uncovered: its picture keeps its bits)."""
+        po, chains = self.picture_options, self._mesh_chains[:n]
+        buffers = {"normal": self.light_normal[:n], "face": self.light_face[:n]}
+        shadow = shades = None
+        if self.lighting.self_shadow is not None:
+            shadow = (light, list(self.shadow_depth[:n]), list(self.shadow_face[:n]))
+            if po.shade == "netC":  # made by _render_subjects' hook from the colour query's position picture
+                shades = list(self.light_shade[:n])
+            else:
+                buffers.update(pos=self.light_pos[:n], shade=self.light_shade[:n])
+        ops.light_pictures_batch("FrameSlot", [c.verts for c in chains], [c.faces for c in chains],
+                                 [c.counts for c in chains], [c.normals for c in chains], list(self._cameras[:n]),
+                                 po.res, self.lighting, list(self.pictures_image[:n]), po.projection, po.nearest,
+                                 po.background, po.near, po.perspective_correct, shadow=shadow, buffers=buffers,
+                                 shades=shades)
+
     def _render_subjects(self, n):
         """The pictures of the n frames' meshes alone, into ``pictures_image`` / ``pictures_depth`` / ``pictures_face``."""
         po = self.picture_options
         chains = self._mesh_chains[:n]
         if po.shade == "netC":  # positions -> covered pixels -> netC at them -> colours, behind the mesh chain
             lists = self.picture_lists
+            hook = None
+            if self.lighting is not None and self.lighting.self_shadow is not None:
+                def hook(positions, face_ids):  # the self-shadow's shade, while the images hold the positions
+                    ops.self_shades("FrameSlot", positions, face_ids, self.lighting,
+                                    (po.scene.light, list(self.shadow_depth[:n]), list(self.shadow_face[:n])),
+                                    self.light_shade[:n])
             ops.render_netc_batch("FrameSlot", [c.verts for c in chains], [c.faces for c in chains],
                                   [c.counts for c in chains], list(self._cameras[:n]), po.res, self._picture_colours(n),
                                   po.projection, po.nearest, po.background,
                                   out=(self.pictures_image[:n], self.pictures_depth[:n], self.pictures_face[:n]),
                                   lists=(lists["points"][:n], lists["pixels"][:n], lists["count"][:n]), near=po.near,
-                                  perspective_correct=po.perspective_correct)
+                                  perspective_correct=po.perspective_correct, positions_hook=hook)
             return
         attrs, channel_major, paint = None, False, (1.0, 0.0, -np.inf, np.inf)
         if po.shade == "normals":  # as main.py:220-225 paints them
@@ -510,7 +571,12 @@ class FrameSlot:
             elif b in self._reran and po.shade == "netC":  # recon.render_mesh(shade="netC") on the slot's own maps
                 out.append(MeshRender(*_render_meshes(
                     "FrameSlot.pictures", [mesh], [self._cameras[b]], po.res, po.shade, po.projection, po.nearest,
-                    po.background, po.near, po.perspective_correct, self._colour_bindings(b, b + 1), self.view)[0]))
+                    po.background, po.near, po.perspective_correct, self._colour_bindings(b, b + 1), self.view,
+                    self.lighting)[0]))
+            elif b in self._reran and self.lighting is not None:
+                out.append(MeshRender(*_render_meshes(
+                    "FrameSlot.pictures", [mesh], [self._cameras[b]], po.res, po.shade, po.projection, po.nearest,
+                    po.background, po.near, po.perspective_correct, lighting=self.lighting)[0]))
             elif b in self._reran:
                 out.append(render_mesh(mesh, self._cameras[b], po.res, po.shade, po.projection, po.nearest,
                                        po.background, po.near, po.perspective_correct))
@@ -528,14 +594,18 @@ class FrameSlot:
             return ScenePicture(self.pictures_image[b], self.pictures_depth[b], self.pictures_face[b],
                                 self.pictures_mask[b])
         bindings = self._colour_bindings(b, b + 1) if po.shade == "netC" else None
-        front = _render_meshes("FrameSlot.pictures", [mesh], [self._cameras[b]], po.res, po.shade, po.projection,
-                               po.nearest, po.background, po.near, po.perspective_correct, bindings, self.view)[0]
-        back = self.scene_image[b]
-        if hasattr(self, "scene_lit"):  # the shadow anew, from the re-run mesh's own map, on the unshadowed picture
+        maps = None
+        if hasattr(self, "scene_lit"):  # the re-run mesh's own shadow map
             from .recon import shade_shadow, shadow_map
             light = po.scene.light
-            back = shade_shadow((back, self.scene_depth[b], self.scene_face[b]), self.scene_pos[b],
-                                shadow_map([mesh], light)[0], light)[0]
+            maps = shadow_map([mesh], light)
+        self_shadow = self.lighting is not None and self.lighting.self_shadow is not None
+        front = _render_meshes("FrameSlot.pictures", [mesh], [self._cameras[b]], po.res, po.shade, po.projection,
+                               po.nearest, po.background, po.near, po.perspective_correct, bindings, self.view,
+                               self.lighting, (light, maps) if self_shadow else None)[0]
+        back = self.scene_image[b]
+        if maps is not None:  # the shadow anew, from that map, on the unshadowed picture
+            back = shade_shadow((back, self.scene_depth[b], self.scene_face[b]), self.scene_pos[b], maps[0], light)[0]
         return composite(front, (back, self.scene_depth[b], self.scene_face[b]), po.composite,
                          po.nearest, po.background)
 

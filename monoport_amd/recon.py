@@ -497,7 +497,8 @@ def _single_camera(calibs):
 
 @torch.no_grad()
 def render_mesh(mesh, calibs, res=257, shade="colors", projection="orthogonal", nearest="max", background=1.0,
-                near=None, perspective_correct=False, netC=None, feat_tensor_C=None, calib_tensor=None, view=None):
+                near=None, perspective_correct=False, netC=None, feat_tensor_C=None, calib_tensor=None, view=None,
+                lighting=None):
     """The z-buffered picture of a ``Mesh`` on the device (monoport_amd extension; ``ops.mesh_render_raw``): any camera
     ``calibs`` ([4,4] / [3,4], the convention of the queries; or [n_views, ...] for several pictures in one set of
     launches), any size ``res`` (int or (H, W)).  ``shade``: "colors" (the mesh's colours), "normals" (its normals * 0.5
@@ -515,18 +516,28 @@ def render_mesh(mesh, calibs, res=257, shade="colors", projection="orthogonal", 
     ``shade=None``.  The mesh needs neither colours nor normals, the query costs the covered pixels instead of the
     vertices, and the texture keeps netC's detail whatever the mesh density.  ``view``: None for a single-view
     ``netC``, k for row k of a multi-view one, as in ``reconstruct_mesh``.  ``shade="netC"`` without ``netC``, and
-    ``netC`` with any other shade, are ValueErrors raised before anything is enqueued."""
+    ``netC`` with any other shade, are ValueErrors raised before anything is enqueued.
+
+    ``lighting`` (a ``Lighting``; None, the default: nothing more is enqueued): the image is lit per pixel -- a second
+    pass of the rasteriser with the mesh's normals as the attribute, under the same camera, ``near`` and flags, then
+    ``ops.picture_light_batch`` in place: clamp(albedo * shading, 0, 1) at the covered pixels, where the albedo is the
+    picture's own colours (``shade="colors"`` / ``"netC"``) or the lighting's constant ``albedo`` (``shade="normals"``).
+    ``shade=None``, ``shade="normals"`` without a constant albedo, a mesh without normals and a ``self_shadow`` (which
+    needs a scene's light: ``render_mesh_many_in_scene``) are ValueErrors raised before anything is enqueued."""
     _check_shade_netC("render_mesh", shade, netC, view)
+    if lighting is not None:
+        _check_lighting("render_mesh", lighting, shade, [mesh], None)
     if mesh is None:
         return None
     return render_mesh_many([mesh], calibs, res, shade, projection, nearest, background, near, perspective_correct,
-                            netC=netC, feat_tensors_C=[feat_tensor_C], calib_tensors=[calib_tensor], view=view)[0]
+                            netC=netC, feat_tensors_C=[feat_tensor_C], calib_tensors=[calib_tensor], view=view,
+                            lighting=lighting)[0]
 
 
 @torch.no_grad()
 def render_mesh_many(meshes, calibs, res=257, shade="colors", projection="orthogonal", nearest="max", background=1.0,
                      near=None, perspective_correct=False, netC=None, feat_tensors_C=None, calib_tensors=None,
-                     view=None):
+                     view=None, lighting=None):
     """``[render_mesh(m, calibs, ...) for m in meshes]`` in one set of launches per ops.MAX_FRAMES pictures (meshes x
     views), the same bits.  ``calibs``: one camera set for all meshes (a tensor / array), or a list with one camera set
     per mesh (those of ``None`` meshes are not looked at; all of one n_views).  ``None`` meshes give ``None``.  The
@@ -534,12 +545,23 @@ def render_mesh_many(meshes, calibs, res=257, shade="colors", projection="orthog
     the call is the largest of them (no row at or beyond a mesh's counts is touched).  ``near`` / ``perspective_correct``
     as in ``render_mesh``: one plane for all.  With ``shade="netC"``: ``feat_tensors_C`` / ``calib_tensors`` hold one
     entry per mesh (those of ``None`` meshes are not looked at), and the colour query of all meshes is one counted
-    launch per ops.MAX_FRAMES meshes (``ops.max_view_frames(V)`` with ``view``).  No host sync."""
-    who = "render_mesh_many"
+    launch per ops.MAX_FRAMES meshes (``ops.max_view_frames(V)`` with ``view``).  ``lighting``: as in ``render_mesh``,
+    one for all meshes; the normal pass and the lighting are one set of launches per ops.MAX_FRAMES pictures more.  No
+    host sync."""
+    return _render_mesh_many("render_mesh_many", meshes, calibs, res, shade, projection, nearest, background, near,
+                             perspective_correct, netC, feat_tensors_C, calib_tensors, view, lighting, None)
+
+
+def _render_mesh_many(who, meshes, calibs, res, shade, projection, nearest, background, near, perspective_correct, netC,
+                      feat_tensors_C, calib_tensors, view, lighting, shadow):
+    """``render_mesh_many``; ``shadow``: None, or (the scene's Light, one shadow map per entry of ``meshes``) for the
+    lighting's ``self_shadow``."""
     _check_shade_netC(who, shade, netC, view)
+    meshes = list(meshes)
+    if lighting is not None:
+        _check_lighting(who, lighting, shade, meshes, None if shadow is None else shadow[0])
     if near is not None or perspective_correct:  # refused before a list of Nones returns
         ops._render_clip(who, projection, near, perspective_correct)
-    meshes = list(meshes)
     if netC is not None:
         if feat_tensors_C is None or calib_tensors is None:
             raise ValueError("%s: netC needs feat_tensors_C and calib_tensors" % who)
@@ -560,8 +582,12 @@ def render_mesh_many(meshes, calibs, res=257, shade="colors", projection="orthog
     if netC is not None:
         bindings = _bind_netC(who, netC, [(feat_tensors_C[i], calib_tensors[i], meshes[i].verts.device) for i in idx],
                               view)
+    if lighting is None or lighting.self_shadow is None:
+        shadow = None
+    else:
+        shadow = (shadow[0], [shadow[1][i] for i in idx])
     raws = _render_meshes(who, [meshes[i] for i in idx], cams, res, shade, projection, nearest, background, near,
-                          perspective_correct, bindings, view or 0)
+                          perspective_correct, bindings, view or 0, lighting, shadow)
     for i, cam, (image, depth, face) in zip(idx, cams, raws):
         if _single_camera(cam):
             image, depth, face = (None if t is None else t[0] for t in (image, depth, face))
@@ -570,24 +596,41 @@ def render_mesh_many(meshes, calibs, res=257, shade="colors", projection="orthog
 
 
 def _render_meshes(who, live, cams, res, shade, projection, nearest, background, near, perspective_correct,
-                   bindings=None, view=0):
+                   bindings=None, view=0, lighting=None, shadow=None):
     """The raw pictures (image, depth, face; each [n_views, ...]) of the meshes ``live`` (no None) under one camera set
     each.  ``shade="netC"``: ``bindings``, one query binding of netC per mesh (``_bind_netC``; a slot passes those on
-    its own maps), colour the pictures per pixel through ``ops.render_netc_batch``."""
+    its own maps), colour the pictures per pixel through ``ops.render_netc_batch``.  ``lighting`` (checked by the
+    caller): the images are then lit in place (``ops.light_pictures_batch``); ``shadow``: for its ``self_shadow``, (the
+    scene's Light, the shadow maps of ``live`` as ``shadow_map`` gives them)."""
     shaded = [_shade_attr(who, m, shade) for m in live]
     scale, bias, lo, hi = shaded[0][1]
     verts = [m.verts.contiguous() for m in live]
     faces = [m.faces.contiguous() for m in live]
     sizes = list(_shape_counts(list(zip(verts, faces))).unbind(0))
     capacity = (max(v.shape[0] for v in verts), max(f.shape[0] for f in faces))
+    if lighting is not None and shadow is not None:
+        shadow = (shadow[0], [m[0] for m in shadow[1]], [m[1] for m in shadow[1]])
+    shades = None
     if shade == "netC":
-        return ops.render_netc_batch(who, verts, faces, sizes, cams, res,
+        hook = None
+        if lighting is not None and lighting.self_shadow is not None:  # the positions are there before the paint
+            def hook(positions, face_ids):
+                nonlocal shades
+                shades = ops.self_shades(who, positions, face_ids, lighting, shadow)
+        raws = ops.render_netc_batch(who, verts, faces, sizes, cams, res,
                                      lambda pts, counts: _counted_colours(bindings, pts, counts, view=view),
                                      projection, nearest, background, capacity=capacity, near=near,
-                                     perspective_correct=perspective_correct)
-    attrs = None if shade is None else [ops._f32c(a) for a, _ in shaded]
-    return ops._mesh_render(who, verts, faces, sizes, attrs, cams, res, projection, nearest, False, scale, bias, lo, hi,
-                            background, None, capacity=capacity, near=near, perspective_correct=perspective_correct)
+                                     perspective_correct=perspective_correct, positions_hook=hook)
+    else:
+        attrs = None if shade is None else [ops._f32c(a) for a, _ in shaded]
+        raws = ops._mesh_render(who, verts, faces, sizes, attrs, cams, res, projection, nearest, False, scale, bias, lo,
+                                hi, background, None, capacity=capacity, near=near,
+                                perspective_correct=perspective_correct)
+    if lighting is not None:
+        ops.light_pictures_batch(who, verts, faces, sizes, [ops._f32c(m.normals) for m in live], cams, res, lighting,
+                                 [r[0] for r in raws], projection, nearest, background, near, perspective_correct,
+                                 capacity=capacity, shadow=shadow, shades=shades)
+    return raws
 
 
 ScenePicture = collections.namedtuple("ScenePicture", ["image", "depth", "face", "mask"])
@@ -673,6 +716,92 @@ class Light:
 def _check_light(who, light):
     if not isinstance(light, Light):
         raise ValueError("%s: light must be a recon.Light, got %r" % (who, type(light).__name__))
+
+
+LIGHTING_FRAMES = ("world", "camera")
+
+
+class Lighting:
+    """How the subject is lit per pixel (the reference's spherical-harmonic lighting model, its SH shader and
+    ShRender; mp_picture_light in include/monoport_hip.h): shading = the nine second-order SH basis values at the
+    pixel's normal times ``sh`` [9,3] (coefficient, rgb), plus -- ``direct``: None, or a (direction the light travels,
+    rgb) pair; the direction is normalised here in float64 -- max(-direction . normal, 0) * rgb, raised to 1 / ``gamma``
+    (1.0, the default: nothing, and the bit-exact form; the reference uses 2.2); the picture is clamp(albedo * shading,
+    0, 1).  ``frame``: "world" (SH at the world normal) or "camera" (SH at the normal turned by the 3x3 of each view's
+    calib and normalised again, the reference's ModelMat * a_Normal); the direct term is always on the world normal.
+    ``albedo``: None (the albedo is the picture's own colours: ``shade="colors"`` / ``"netC"``) or a constant (r, g, b)
+    "clay" for ``shade="normals"``.  ``self_shadow``: None, or a bias >= 0: the scene's ``Light`` then also shadows the
+    subject itself -- its own shadow map looked up at its own surface, nearer by more than the bias -- and the shade
+    takes the direct term away (1 = fully occluded), the SH term stays.  Everything is validated here; a Lighting holds
+    host values only."""
+
+    def __init__(self, sh, direct=None, gamma=1.0, frame="world", albedo=None, self_shadow=None):
+        who = "Lighting"
+        if direct is not None:
+            try:
+                direction, rgb = direct
+                d = np.asarray(direction, np.float64).reshape(-1)
+            except (TypeError, ValueError):
+                raise ValueError("%s: direct must be None or a (direction, rgb) pair, got %r" % (who, direct)) from None
+            if d.shape != (3,) or not np.isfinite(d).all() or not np.linalg.norm(d) > 0:
+                raise ValueError("%s: direct's direction must be three finite values, not all zero, got %r"
+                                 % (who, direction))
+            direct = ((d / np.linalg.norm(d)).astype(np.float32), rgb)
+        self.sh, self.direct_dir, self.direct_rgb, self.gamma, self.albedo = ops.light_params(who, sh, direct, gamma,
+                                                                                             albedo)
+        self.direct = None if direct is None else (self.direct_dir, self.direct_rgb)
+        if not isinstance(frame, str) or frame not in LIGHTING_FRAMES:
+            raise ValueError("%s: frame must be one of %s, got %r" % (who, list(LIGHTING_FRAMES), frame))
+        self.frame = frame
+        if self_shadow is not None:
+            if isinstance(self_shadow, bool) or not isinstance(self_shadow, (int, float, np.integer, np.floating)):
+                raise ValueError("%s: self_shadow must be None or a bias >= 0, got %r" % (who, self_shadow))
+            self_shadow = float(self_shadow)
+            if not (np.isfinite(self_shadow) and self_shadow >= 0):
+                raise ValueError("%s: self_shadow must be None or a finite bias >= 0, got %r" % (who, self_shadow))
+        self.self_shadow = self_shadow
+
+    @classmethod
+    def ambient(cls, rgb, **kw):
+        """Light of the same colour from everywhere: only coefficient 0 is set, so that the shading is ``rgb`` exactly
+        wherever rgb / c4 * c4 rounds back to rgb -- the coefficient is the f32 nearest to rgb / c4, moved by an ulp
+        where that product misses."""
+        rgb = ops._finite_floats("Lighting.ambient", "rgb", rgb, (3,))
+        c4 = np.float32(0.886227)
+        coeff = (rgb / c4).astype(np.float32)
+        for c in range(3):  # H0 * coeff == rgb on the bits, if a neighbour of the quotient gives it
+            for cand in (coeff[c], np.nextafter(coeff[c], np.float32(np.inf)), np.nextafter(coeff[c], np.float32(-np.inf))):
+                if np.float32(c4 * cand) == rgb[c]:
+                    coeff[c] = cand
+                    break
+        sh = np.zeros((9, 3), np.float32)
+        sh[0] = coeff
+        return cls(sh, **kw)
+
+
+def _check_lighting(who, lighting, shade, meshes, scene_light):
+    """``lighting`` against the shade, the meshes (None entries skipped) and the scene's light, before anything is
+    enqueued."""
+    _check_lighting_options(who, lighting, shade, not any(m is not None and m.normals is None for m in meshes),
+                            scene_light)
+
+
+def _check_lighting_options(who, lighting, shade, has_normals, scene_light):
+    """``_check_lighting`` for a caller that knows whether its meshes have normals (a slot's mesh options)."""
+    if not isinstance(lighting, Lighting):
+        raise ValueError("%s: lighting must be a recon.Lighting, got %r" % (who, type(lighting).__name__))
+    if shade is None:
+        raise ValueError("%s: lighting shades an image; shade=None renders none" % who)
+    if shade == "normals" and lighting.albedo is None:
+        raise ValueError("%s: shade='normals' is lit as clay: lighting needs a constant albedo=(r, g, b)" % who)
+    if shade != "normals" and lighting.albedo is not None:
+        raise ValueError("%s: lighting.albedo is the clay of shade='normals'; shade=%r has its own colours"
+                         % (who, shade))
+    if not has_normals:
+        raise ValueError("%s: lighting needs the mesh's normals, and the mesh has none" % who)
+    if lighting.self_shadow is not None and scene_light is None:
+        raise ValueError("%s: lighting.self_shadow looks the subject up in the shadow map of the scene's light; there "
+                         "is no scene light" % who)
 
 
 class Scene:
@@ -783,15 +912,48 @@ def shade_shadow(picture, positions, maps, light):
                                     light.radius, light.strength, with_shade=True, who="shade_shadow")[0]
 
 
-def _scene_pictures(who, scene, casters, cams, res, projection, nearest, near, perspective_correct, background):
+@torch.no_grad()
+def light_picture(picture, normals, lighting, calibs=None, visibility=None):
+    """``picture`` (image [...,3] f32 or None, depth, face [...] int32; a ``MeshRender`` or a tuple) lit by ``lighting``
+    at the ``normals`` [...,3] f32 of its pixels (a render with the mesh's normals as the attribute and the paint (1, 0,
+    -inf, inf)): the generic call of ``render_mesh(lighting=)``.  The image is the albedo; with a constant
+    ``lighting.albedo`` it is not read and may be None.  ``calibs``: the picture's cameras ([4,4] / [3,4] for a picture
+    [H,W,3], [n_views, ...] for [n_views,H,W,3]), needed for ``frame="camera"``; ``visibility``: None, or the shade
+    [...] of ``shade_shadow`` (1 = the direct light is occluded; ``lighting.self_shadow`` is not looked at here).
+    Returns (image, shading): fresh tensors [...,3]; uncovered pixels keep the albedo's bits (1.0 without an image) and
+    have shading 0.  Defined bit for bit in include/monoport_hip.h (mp_picture_light).  No host sync."""
+    who = "light_picture"
+    if not isinstance(lighting, Lighting):
+        raise ValueError("%s: lighting must be a recon.Lighting, got %r" % (who, type(lighting).__name__))
+    image, face = picture[0], picture[2]
+    if (image is None) == (lighting.albedo is None):
+        raise ValueError("%s: the albedo is either the picture's image or lighting.albedo, not %s"
+                         % (who, "neither" if image is None else "both"))
+    nv = int(normals.shape[0]) if normals.dim() == 4 else 1
+    mats = None
+    if lighting.frame == "camera":
+        if calibs is None:
+            raise ValueError("%s: frame='camera' needs the picture's calibs" % who)
+        mats = ops.normal_mats_of(who, calibs)
+        if mats.shape[0] != nv:
+            raise ValueError("%s: a picture of %d views, %d cameras" % (who, nv, mats.shape[0]))
+    return ops.picture_light_batch([normals.contiguous()], [face.contiguous()],
+                                   None if image is None else [image.contiguous()], lighting.sh, lighting.direct,
+                                   lighting.gamma, mats, None if visibility is None else [visibility.contiguous()],
+                                   lighting.albedo, nv, with_shading=True, who=who)[0]
+
+
+def _scene_pictures(who, scene, casters, cams, res, projection, nearest, near, perspective_correct, background,
+                    maps=None):
     """Per camera set the raw picture (image, depth, face; each [n_views, ...]) of ``scene``.  With ``scene.light`` and
-    any caster (``casters``: None, or one Mesh or None per camera set): the shadow maps of the casters, the scene's UV
-    and position pictures, the texture lookup, and the shadow in place on the scene's image.  Else exactly
-    ``ops.render_scene_batch``."""
+    any caster (``casters``: None, or one Mesh or None per camera set): the shadow maps of the casters (``maps``: those,
+    where the caller has made them), the scene's UV and position pictures, the texture lookup, and the shadow in place
+    on the scene's image.  Else exactly ``ops.render_scene_batch``."""
     light = scene.light
     if light is None or casters is None or all(m is None for m in casters):
         return ops.render_scene_batch(who, scene, cams, res, projection, nearest, near, perspective_correct, background)
-    maps = shadow_map(casters, light, device=scene.verts.device)
+    if maps is None:
+        maps = shadow_map(casters, light, device=scene.verts.device)
     nv = ops._view_calibs(who, cams[0]).shape[0]
     h, w = ops._render_size(who, res)
     positions = torch.empty((len(cams), nv, h, w, 3), dtype=torch.float32, device=scene.verts.device).unbind(0)
@@ -836,26 +998,37 @@ def composite(front, back, mode="depth", nearest="max", background=1.0):
 @torch.no_grad()
 def render_mesh_many_in_scene(meshes, scene, calibs, res=257, shade="colors", projection="orthogonal", nearest="max",
                               background=1.0, near=None, perspective_correct=False, composite="depth", netC=None,
-                              feat_tensors_C=None, calib_tensors=None, view=None):
+                              feat_tensors_C=None, calib_tensors=None, view=None, lighting=None):
     """``render_mesh_many`` of ``meshes`` composited over ``render_scene`` of ``scene`` under the same cameras
     (``calibs``: one camera set for all, or a list with one per mesh), ``composite``: "depth" or "over".  Returns a
     list of ``ScenePicture``s; a ``None`` mesh gives the bare scene (mask in {0, 1}, face -1).  ``shade`` may not be
     None: the composite is of images.  Two more launches per ops.MAX_FRAMES pictures than the two renders; no host
     sync.  With ``scene.light`` every mesh also casts its shadow on its own picture of the scene before the composite:
     its shadow map under the light, a position pass of the scene and ``ops.picture_shadow_batch``; without a light
-    nothing more is enqueued than before."""
+    nothing more is enqueued than before.  ``lighting`` (a ``Lighting``; None: nothing more is enqueued) lights the
+    subject's image as in ``render_mesh``, before the composite; the scene keeps its texture and its shadow.  With
+    ``lighting.self_shadow`` (it needs ``scene.light``) the subject is also looked up in its own shadow map, with that
+    bias: a position pass of the subject and ``ops.picture_shadow_batch`` for the shade alone, which takes the direct
+    term away where it is 1; with ``shade="netC"`` the position picture of the colour query is the one it reads."""
     who = "render_mesh_many_in_scene"
     _check_scene(who, scene)
     if shade is None:
         raise ValueError("%s: the composite is of images; shade=None renders none" % who)
     ops._named_mode(who, "composite", ops.COMPOSITE_MODES, composite)
     meshes = list(meshes)
+    if lighting is not None:
+        _check_lighting(who, lighting, shade, meshes, scene.light)
     if not meshes:
         return []
     cams = _camera_sets(who, calibs, len(meshes))
-    fronts = render_mesh_many(meshes, calibs, res, shade, projection, nearest, background, near, perspective_correct,
-                              netC=netC, feat_tensors_C=feat_tensors_C, calib_tensors=calib_tensors, view=view)
-    backs = _scene_pictures(who, scene, meshes, cams, res, projection, nearest, near, perspective_correct, background)
+    maps = None
+    if lighting is not None and lighting.self_shadow is not None and any(m is not None for m in meshes):
+        maps = shadow_map(meshes, scene.light, device=scene.verts.device)  # one set for the subject and the scene
+    fronts = _render_mesh_many("render_mesh_many", meshes, calibs, res, shade, projection, nearest, background, near,
+                               perspective_correct, netC, feat_tensors_C, calib_tensors, view, lighting,
+                               None if lighting is None or lighting.self_shadow is None else (scene.light, maps))
+    backs = _scene_pictures(who, scene, meshes, cams, res, projection, nearest, near, perspective_correct, background,
+                            maps)
     pairs = []
     for front, back, cam in zip(fronts, backs, cams):
         if front is None:  # no subject: an uncovered picture of the scene's size

@@ -79,6 +79,14 @@ rows without a light are the comparison.
 
     python tools/mesh_timing.py --shadow [--passes 5] [--out profiles/mesh_shadow_timing.json]
 
+``--lighting`` measures the per-pixel lighting of the subject (profiles/mesh_lighting_timing.json): the ``--shadow``
+slots WITH the light on the scene, each without and with ``lighting=`` -- clay albedo, random second-order SH
+coefficients, a direct term along the sun, evaluated in the camera's frame, with the self-shadow (bias 0.02) -- at one
+257^2 and one 1024^2 view, with the subject's pixels of frame 0 that the lighting changes.  The rows without
+``lighting=`` are the comparison.
+
+    python tools/mesh_timing.py --lighting [--passes 5] [--out profiles/mesh_lighting_timing.json]
+
 The protocol of tools/recon_views_timing.py: after a warm-up of all, the passes alternate; a pass is `meshes`
 meshes, wall clock around a final stream sync.  Prints (and writes) one JSON line: per way the median, minimum and
 maximum time per mesh (ms) over the passes.  The verdict fields restate what to check: (b) not slower than (a) by
@@ -121,6 +129,7 @@ def main():
     ap.add_argument("--deferred", action="store_true", help="slot pictures coloured per vertex against per pixel")
     ap.add_argument("--scene", action="store_true", help="slot pictures with and without a textured scene behind them")
     ap.add_argument("--shadow", action="store_true", help="slot pictures over a scene, without and with a light on it")
+    ap.add_argument("--lighting", action="store_true", help="the --shadow slots without and with lighting= on the subject")
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "mesh_render_clip_timing.json" if a.render and a.clip else
@@ -128,6 +137,7 @@ def main():
                              "mesh_deferred_timing.json" if a.deferred else
                              "mesh_scene_timing.json" if a.scene else
                              "mesh_shadow_timing.json" if a.shadow else
+                             "mesh_lighting_timing.json" if a.lighting else
                              "mesh_smooth_timing.json" if a.smooth else
                              "mesh_simplify_timing.json" if a.simplify else
                              "keep_largest_timing.json" if a.clean else
@@ -140,6 +150,9 @@ def main():
         return
     if a.shadow:
         write(a, slot_shadow(a))
+        return
+    if a.lighting:
+        write(a, slot_lighting(a))
         return
     mlp = ops.PackedMLP.from_layers(DEV, syn.body_mlp("G", noise=0.05, seed=1), 1)
     fh = ops.pack_features(torch.from_numpy(syn.body_feat(256, 128, 128, 2))[None].to(DEV))
@@ -528,6 +541,43 @@ def slot_shadow(a, frames=20):
     return out
 
 
+def slot_lighting(a, frames=20):
+    """The --shadow slots with the light on the scene, without and with ``lighting=`` on the subject (clay, SH in the
+    camera's frame, a direct term along the sun, the self-shadow): per-frame ms of a submission (``pictures()``
+    included) at one 257^2 and one 1024^2 view, and the pixels of frame 0 that the lighting changes."""
+    direction = (0.4, -1.0, 0.3)
+    sun = recon.Light.directional(direction, (-1.5, -0.9, -1.5), (1.5, 1.0, 1.5), res=512, radius=1)
+    floor, cam, mesh, base = _scene_setup(sun)
+    sh = np.random.RandomState(0).uniform(-0.2, 0.4, (9, 3)).astype(np.float32)
+    sh[0] += 0.8
+    lighting = recon.Lighting(sh, direct=(direction, (0.9, 0.85, 0.8)), frame="camera", albedo=(0.8, 0.7, 0.6),
+                              self_shadow=0.02)
+    rows = []
+    for res in (257, 1024):
+        rows.append(("shadow_%d" % res, mesh, dict(base, res=res, scene=floor), cam))
+        rows.append(("lighting_%d" % res, mesh, dict(base, res=res, scene=floor), cam, dict(lighting=lighting)))
+    pipes, fn = _slot_pipes(frames, 1, rows)
+    out = {"frames_per_slot": frames, "unit": "ms per frame", "shadow_map": list(sun.res), "radius": sun.radius,
+           "light": "directional (0.4, -1, 0.3), fitted to the box of the floor and the body",
+           "lighting": "clay albedo, 9 x 3 SH coefficients in the camera's frame, a direct term along the light, "
+                       "self_shadow 0.02, gamma 1",
+           "camera": "perspective, turned -0.35 rad about x (looking down), near 0.3, perspective-correct"}
+    out.update(alternate({name: fn(name) for name in pipes}, a.passes, frames))
+    pictures = {}
+    for name, p_ in pipes.items():
+        pictures[name] = p_.slots[0].pictures()[0].image.clone()
+        p_.close()
+    out["lit_pixels_frame0"] = {}
+    for res in ("257", "1024"):
+        lit_row, plain = out["lighting_" + res], out["shadow_" + res]
+        out["lit_pixels_frame0"][res] = int((pictures["lighting_" + res] != pictures["shadow_" + res]).any(-1).sum().item())
+        out["lighting_%s_minus_shadow_ms" % res] = round(lit_row["median_ms"] - plain["median_ms"], 4)
+        out["lighting_%s_inside_the_spread" % res] = bool(
+            lit_row["median_ms"] - plain["median_ms"] <= max(lit_row["max_ms"] - lit_row["min_ms"],
+                                                             plain["max_ms"] - plain["min_ms"]))
+    return out
+
+
 def slot_scene(a, frames=20):
     """The 20-frame slot with normal-shaded pictures under a free perspective camera, with and without a textured 3 m
     floor (a 2048^2 checker, full mip chain) composited behind the subject by depth: per-frame ms of a submission
@@ -573,6 +623,8 @@ def _slot_pipes(frames, depth, meshes):
     pipes, cameras = {}, {}
     for name, mesh, *pictures in meshes:
         kw = dict(pictures=pictures[0]) if pictures else {}
+        if len(pictures) > 2:  # further keywords of the slot (lighting=)
+            kw.update(pictures[2])
         cameras[name] = dict(cameras=pictures[1]) if pictures else {}
         pipes[name] = pipeline.FramePipeline(netg, dev, depth=depth, batch=frames, resolutions=RESOLUTIONS,
                                              b_min=B_MIN, b_max=B_MAX, feature_hook=hook, use_graph=True,
