@@ -983,7 +983,8 @@ int mp_picture_shadow_batch(mp_ctx *ctx, int n_frames, const float *const *image
  * one frame; in the batched one normal / face_id / albedo / visibility / image_out / shading are HOST arrays of
  * n_frames device pointers (one parameter set for all), blockIdx.y is the frame: frame f's outputs equal the per-frame
  * call's on frame f's inputs BIT FOR BIT.
- * NOT built: lighting the scene by the same model, several lights, specular terms, precomputed radiance transfer. */
+ * NOT built: lighting the scene by the same model, several lights, specular terms.  Precomputed radiance transfer is
+ * mp_mesh_transfer + mp_picture_light_transfer below. */
 int mp_picture_light(mp_ctx *ctx, const float *normal, const int32_t *face_id, const float *albedo,
                      const float *albedo_rgb, const float *visibility, int64_t n_pixels, int n_views, const float *sh,
                      const float *direct_dir, const float *direct_rgb, float gamma, const float *normal_mats,
@@ -993,6 +994,79 @@ int mp_picture_light_batch(mp_ctx *ctx, int n_frames, const float *const *normal
                            int64_t n_pixels, int n_views, const float *sh, const float *direct_dir,
                            const float *direct_rgb, float gamma, const float *normal_mats, float background,
                            float *const *image_out, float *const *shading, mp_stream stream);
+
+/* ---- self-occluded SH lighting: radiance transfer traced in the occupancy volume -------------------------------------
+ * The reference's PRT shaders shade with nine precomputed radiance-transfer coefficients per vertex (shading_c =
+ * sum_k prt_k * SHCoeffs[k][c]): the cosine lobe masked by what the body itself occludes.  Here they are traced per
+ * frame through the occupancy volume the mesh was cut from.  All float operations below are single IEEE f32 + - * /,
+ * sqrtf and floorf in the order written, without FMA (transfer.hip; no float atomics, no scratch arena, 0 B private).
+ *
+ * mp_volume_bits: one bit per voxel of a cubic volume [R,R,R] (z, y, x) f32, 1 <= R <= MP_TRANSFER_MAX_RES.  Word
+ * (z*R + y)*WX + (x >> 5) with WX = ceil(R / 32), bit x & 31, set iff v > level (a NaN voxel is empty); padding bits
+ * are 0.  `bits` is the CALLER's buffer of mp_volume_bits_words(R) 32-bit words (0 for an R out of range): the first
+ * R*R*WX words are the bits defined here, what follows is the tracer's private data (one bit per 8^3 block), written by
+ * the same call.  Batched: `gates` as in mp_marching_cubes_batch (NULL, or per frame NULL / a device int32: a frame
+ * whose gate reads 0 is neither read nor written).  MP_ERR_ARG: n_frames outside 1..mp_max_frames(), R out of range, a
+ * NULL or not 4-byte aligned buffer, bits sharing a byte with a volume or with another frame's bits.
+ *
+ * mp_mesh_transfer: per call HOST b_min[3], b_max[3], R, n_dirs = D (a multiple of 64, 64..MP_TRANSFER_MAX_DIRS),
+ * weight, bias_w and step_w (world units), max_steps = J (1..2^24); DEVICE tables dirs f32 [D,3] and basis f32 [D,9].
+ * Per frame verts [max_verts,3], normals [max_verts,3], counts (device int32, [0] = vertices), bits (of mp_volume_bits
+ * at the same R).  Outputs mask u64 [max_verts, D/64] (bit d & 63 of word d >> 6: direction d is seen) and prt f32
+ * [max_verts,9]; either may be NULL, not both.  Rows at or beyond counts[0] are not written.  Per vertex p, normal n:
+ *   1. u = n normalised by step 2 of mp_picture_light (a zero or non-finite normal: u = 0).
+ *   2. vox_a = R / (b_max_a - b_min_a).
+ *   3. g_a = ((p_a - b_min_a) / (b_max_a - b_min_a)) * R.  Voxel i covers [i, i+1): the inverse of marching cubes'
+ *      lattice coordinate.
+ *   4. o_a = g_a + (bias_w * u_a) * vox_a.
+ *   5. Direction d = (wx, wy, wz): k_d = (wx*ux + wy*uy) + wz*uz.  k_d > 0 false (a NaN included): bit d = 0, nothing
+ *      is traced.  Else delta_a = (step_w * w_a) * vox_a.
+ *   6. For j = 0..J-1: s_a = o_a + ((float)j * delta_a).  Not (s_a >= 0 && s_a < R) on some axis: the ray has left,
+ *      bit d = 1, stop.  Else voxel (int)floorf(s) set in bits: bit d = 0, stop.  A ray that uses up J samples: bit 1.
+ *   7. acc_k = 0.0f; for d ascending over the set bits acc_k = acc_k + (k_d * basis[d][k]); prt_k = acc_k * weight.
+ * The mask is an integer result and the sum has one order, so the outputs are defined bit for bit.  One thread per
+ * vertex; empty 8^3 blocks are skipped exactly (samples are indexed by j and monotone in j).
+ * MP_ERR_ARG: the ranges above; non-finite b_min / b_max or b_max <= b_min; non-finite weight / bias_w / step_w or
+ * step_w <= 0; no output; a NULL or misaligned buffer (mask: 8 bytes); an output sharing a byte with an input (dirs
+ * and basis included) or with another output.  MP_ERR_UNSUPPORTED: max_verts beyond 2^31 / 9.
+ *
+ * mp_mesh_transfer_shade: out [max_verts,3]: t_c = 0.0f, then t_c = t_c + prt_k * sh[3 k + c] for k = 0..8 (sh: HOST,
+ * 27 finite floats) -- the reference's evaluateLightingModelPRT.  Linear in prt, so rasterising t as the attribute with
+ * the paint (1, 0, -inf, inf) equals interpolating the nine coefficients.
+ *
+ * mp_picture_light_transfer: mp_picture_light with one more per-frame input, ambient f32 [L,3] (the rasterised t),
+ * which replaces step 4: res_c = ambient_c.  Steps 1, 2, 5, 6, 7 are unchanged and run in the same kernel body.
+ * `normal` may be NULL where direct_rgb is all zero.  No normal_mats: the camera frame would need the reference's band
+ * rotation, which is not built.  Refusals as mp_picture_light's, ambient counting as an input.
+ * All of these are asynchronous, synchronise nothing, and the per-frame call is the batched one with one frame. */
+#define MP_TRANSFER_MAX_RES 513
+#define MP_TRANSFER_MAX_DIRS 512
+int64_t mp_volume_bits_words(int r);
+int mp_volume_bits(mp_ctx *ctx, const float *volume, int r, float level, uint32_t *bits, mp_stream stream);
+int mp_volume_bits_batch(mp_ctx *ctx, int n_frames, const float *const *volume, int r, float level,
+                         uint32_t *const *bits, const int32_t *const *gates, mp_stream stream);
+int mp_mesh_transfer(mp_ctx *ctx, const float *verts, const float *normals, int64_t max_verts, const int32_t *counts,
+                     const uint32_t *bits, int r, const float *b_min, const float *b_max, int n_dirs, const float *dirs,
+                     const float *basis, float weight, float bias_w, float step_w, int max_steps, uint64_t *mask,
+                     float *prt, mp_stream stream);
+int mp_mesh_transfer_batch(mp_ctx *ctx, int n_frames, const float *const *verts, const float *const *normals,
+                           int64_t max_verts, const int32_t *const *counts, const uint32_t *const *bits, int r,
+                           const float *b_min, const float *b_max, int n_dirs, const float *dirs, const float *basis,
+                           float weight, float bias_w, float step_w, int max_steps, uint64_t *const *mask,
+                           float *const *prt, mp_stream stream);
+int mp_mesh_transfer_shade(mp_ctx *ctx, const float *prt, int64_t max_verts, const int32_t *counts, const float *sh,
+                           float *out, mp_stream stream);
+int mp_mesh_transfer_shade_batch(mp_ctx *ctx, int n_frames, const float *const *prt, int64_t max_verts,
+                                 const int32_t *const *counts, const float *sh, float *const *out, mp_stream stream);
+int mp_picture_light_transfer(mp_ctx *ctx, const float *normal, const int32_t *face_id, const float *albedo,
+                              const float *albedo_rgb, const float *visibility, const float *ambient, int64_t n_pixels,
+                              const float *direct_dir, const float *direct_rgb, float gamma, float background,
+                              float *image_out, float *shading, mp_stream stream);
+int mp_picture_light_transfer_batch(mp_ctx *ctx, int n_frames, const float *const *normal,
+                                    const int32_t *const *face_id, const float *const *albedo, const float *albedo_rgb,
+                                    const float *const *visibility, const float *const *ambient, int64_t n_pixels,
+                                    const float *direct_dir, const float *direct_rgb, float gamma, float background,
+                                    float *const *image_out, float *const *shading, mp_stream stream);
 
 /* The largest connected body of an occupancy volume [R,R,R] (no counterpart in the reference; the clean-up in front
  * of marching cubes that drops floating blobs).

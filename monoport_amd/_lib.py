@@ -228,6 +228,19 @@ SIGNATURES = {
                                  c_f32, c_vp, c_vp, c_vp]),
     "mp_picture_light_batch": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, _pf32, c_vp, c_i64, c_int, _pf32, _pf32, _pf32,
                                        c_f32, _pf32, c_f32, c_vp, c_vp, c_vp]),
+    "mp_picture_light_transfer": (c_int, [c_vp, c_vp, c_vp, c_vp, _pf32, c_vp, c_vp, c_i64, _pf32, _pf32, c_f32, c_f32,
+                                          c_vp, c_vp, c_vp]),
+    "mp_picture_light_transfer_batch": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, _pf32, c_vp, c_vp, c_i64, _pf32, _pf32,
+                                                c_f32, c_f32, c_vp, c_vp, c_vp]),
+    "mp_volume_bits_words": (c_i64, [c_int]),
+    "mp_volume_bits": (c_int, [c_vp, c_vp, c_int, c_f32, c_vp, c_vp]),
+    "mp_volume_bits_batch": (c_int, [c_vp, c_int, c_vp, c_int, c_f32, c_vp, c_vp, c_vp]),
+    "mp_mesh_transfer": (c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, _pf32, _pf32, c_int, c_vp, c_vp, c_f32,
+                                 c_f32, c_f32, c_int, c_vp, c_vp, c_vp]),
+    "mp_mesh_transfer_batch": (c_int, [c_vp, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, _pf32, _pf32, c_int, c_vp,
+                                       c_vp, c_f32, c_f32, c_f32, c_int, c_vp, c_vp, c_vp]),
+    "mp_mesh_transfer_shade": (c_int, [c_vp, c_vp, c_i64, c_vp, _pf32, c_vp, c_vp]),
+    "mp_mesh_transfer_shade_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, _pf32, c_vp, c_vp]),
     "mp_volume_keep_largest": (c_int, [c_vp, c_vp, c_int, c_f32, c_int, c_f32, c_vp, c_vp, c_vp]),
     "mp_volume_keep_largest_batch": (c_int, [c_vp, c_int, c_vp, c_int, c_f32, c_int, c_f32, c_vp, c_vp, c_vp, c_vp]),
     "mp_group_norm": (c_int, [c_vp, c_vp, c_int, c_int, c_i64, c_int, c_vp, c_vp, c_f32, c_int, c_vp,

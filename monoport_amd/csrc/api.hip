@@ -792,10 +792,10 @@ static bool all_finite(const float *v, size_t n) {
 
 static int picture_light_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *normal,
                                  const int32_t *const *face_id, const float *const *albedo, const float *albedo_rgb,
-                                 const float *const *visibility, int64_t n_pixels, int n_views, const float *sh,
-                                 const float *direct_dir, const float *direct_rgb, float gamma,
-                                 const float *normal_mats, float background, float *const *image_out,
-                                 float *const *shading, mp_stream stream) {
+                                 const float *const *visibility, const float *const *ambient, bool transfer,
+                                 int64_t n_pixels, int n_views, const float *sh, const float *direct_dir,
+                                 const float *direct_rgb, float gamma, const float *normal_mats, float background,
+                                 float *const *image_out, float *const *shading, mp_stream stream) {
   if (!ctx) return MP_ERR_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
   int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
@@ -809,29 +809,33 @@ static int picture_light_checked(mp_ctx *ctx, const char *who, int n_frames, con
   if (normal_mats && (long long)n_frames * n_views > kLightMaxMats)
     return fail(ctx, MP_ERR_ARG, "%s: at most %d normal matrices (frames x views) per call, got %d x %d", who,
                 kLightMaxMats, n_frames, n_views);
-  if (!sh || !direct_dir || !direct_rgb || !normal || !face_id) return bad_argument(ctx, who);
+  // mp_picture_light_transfer: ambient stands in for sh; the normals are read by the direct term only
+  if (!direct_dir || !direct_rgb || !face_id || (transfer ? !ambient : !sh || !normal)) return bad_argument(ctx, who);
   if (!albedo == !albedo_rgb)
     return fail(ctx, MP_ERR_ARG, "%s: either albedo buffers or a constant albedo_rgb, not %s", who,
                 albedo ? "both" : "neither");
   if (!std::isfinite(gamma) || !(gamma > 0.0f))
     return fail(ctx, MP_ERR_ARG, "%s: gamma must be finite and > 0, got %g", who, (double)gamma);
-  if (!all_finite(sh, 27) || !all_finite(direct_dir, 3) || !all_finite(direct_rgb, 3) ||
+  if ((sh && !all_finite(sh, 27)) || !all_finite(direct_dir, 3) || !all_finite(direct_rgb, 3) ||
       (albedo_rgb && !all_finite(albedo_rgb, 3)) || !std::isfinite(background) ||
       (normal_mats && !all_finite(normal_mats, (size_t)9 * n_frames * n_views)))
     return fail(ctx, MP_ERR_ARG, "%s: sh, direct_dir, direct_rgb, albedo_rgb, background and normal_mats must be finite",
                 who);
   if (!image_out && !shading) return fail(ctx, MP_ERR_ARG, "%s: no output requested", who);
-  rc = check_frames(ctx, who, n_frames, nullptr, normal, face_id, albedo, visibility, image_out, shading);
+  if (transfer && !normal && (direct_rgb[0] != 0.0f || direct_rgb[1] != 0.0f || direct_rgb[2] != 0.0f))
+    return fail(ctx, MP_ERR_ARG, "%s: the direct term needs the normal pictures", who);
+  rc = check_frames(ctx, who, n_frames, nullptr, normal, face_id, albedo, visibility, ambient, image_out, shading);
   if (rc != MP_OK) return rc;
   // image_out may BE albedo of the same frame (a thread reads its pixel before it writes it); any other byte shared
   // between an output and an input, or between the two outputs, is refused
   const size_t px = (size_t)n_pixels;
-  const FrameSpans ins[4] = {{albedo, px * 12}, {normal, px * 12}, {face_id, px * 4}, {visibility, px * 4}};
+  const FrameSpans ins[5] = {{albedo, px * 12}, {normal, px * 12}, {face_id, px * 4}, {visibility, px * 4},
+                             {ambient, px * 12}};
   const FrameSpans outs[2] = {{image_out, px * 12}, {shading, px * 12}};
   for (int f = 0; f < n_frames; ++f)
     for (int i = 0; i < n_frames; ++i) {
       for (int o = 0; o < 2; ++o)
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < 5; ++k) {
           if (!ranges_overlap(outs[o].of(f), outs[o].bytes, ins[k].of(i), ins[k].bytes)) continue;
           if (!(o == 0 && k == 0 && f == i && outs[o].of(f) == ins[k].of(i)))
             return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases an input of frame %d", who, f, i);
@@ -842,9 +846,126 @@ static int picture_light_checked(mp_ctx *ctx, const char *who, int n_frames, con
         return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases an output of frame %d", who, f, i);
     }
   DeviceGuard g(ctx->device);
-  return launch_picture_light_batch(ctx, n_frames, normal, face_id, albedo, albedo_rgb, visibility, n_pixels, n_views,
-                                    sh, direct_dir, direct_rgb, gamma, normal_mats, background, image_out, shading,
+  return launch_picture_light_batch(ctx, n_frames, normal, face_id, albedo, albedo_rgb, visibility, ambient, n_pixels,
+                                    n_views, sh, direct_dir, direct_rgb, gamma, normal_mats, background, image_out,
+                                    shading, (hipStream_t)stream);
+}
+
+static int volume_bits_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *volume, int r,
+                               float level, uint32_t *const *bits, const int32_t *const *gate, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (!volume || !bits) return bad_argument(ctx, who);
+  if (r < 1 || r > MP_TRANSFER_MAX_RES)
+    return fail(ctx, MP_ERR_ARG, "%s: resolution must be 1..%d, got %d", who, MP_TRANSFER_MAX_RES, r);
+  rc = check_frames(ctx, who, n_frames, gate, volume, bits);
+  if (rc != MP_OK) return rc;
+  const FrameSpans outs[1] = {{bits, (size_t)volume_bits_words(r) * 4}};
+  const FrameSpans ins[1] = {{volume, (size_t)r * r * r * 4}};
+  rc = check_no_alias(ctx, who, n_frames, outs, ins);
+  if (rc != MP_OK) return rc;
+  for (int f = 0; f < n_frames; ++f)
+    for (int i = 0; i < f; ++i)
+      if (ranges_overlap(outs[0].of(f), outs[0].bytes, outs[0].of(i), outs[0].bytes))
+        return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases an output of frame %d", who, f, i);
+  DeviceGuard g(ctx->device);
+  return launch_volume_bits_batch(ctx, n_frames, volume, r, level, bits, gate, (hipStream_t)stream);
+}
+
+static int mesh_transfer_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *verts,
+                                 const float *const *normals, int64_t max_verts, const int32_t *const *counts,
+                                 const uint32_t *const *bits, int r, const float *b_min, const float *b_max, int n_dirs,
+                                 const float *dirs, const float *basis, float weight, float bias_w, float step_w,
+                                 int max_steps, uint64_t *const *mask, float *const *prt, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (!counts || !bits || !b_min || !b_max || !dirs || !basis || max_verts < 0 || (max_verts > 0 && (!verts || !normals)))
+    return bad_argument(ctx, who);
+  if (r < 1 || r > MP_TRANSFER_MAX_RES)
+    return fail(ctx, MP_ERR_ARG, "%s: resolution must be 1..%d, got %d", who, MP_TRANSFER_MAX_RES, r);
+  if (n_dirs < 64 || n_dirs > MP_TRANSFER_MAX_DIRS || n_dirs % 64 != 0)
+    return fail(ctx, MP_ERR_ARG, "%s: n_dirs must be a multiple of 64 in 64..%d, got %d", who, MP_TRANSFER_MAX_DIRS,
+                n_dirs);
+  if (max_steps < 1 || max_steps > (1 << 24))
+    return fail(ctx, MP_ERR_ARG, "%s: max_steps must be 1..2^24, got %d", who, max_steps);
+  if (!all_finite(b_min, 3) || !all_finite(b_max, 3) || !(b_max[0] > b_min[0]) || !(b_max[1] > b_min[1]) ||
+      !(b_max[2] > b_min[2]))
+    return fail(ctx, MP_ERR_ARG, "%s: b_min and b_max must be finite with b_max > b_min on every axis", who);
+  if (!std::isfinite(weight) || !std::isfinite(bias_w) || !std::isfinite(step_w) || !(step_w > 0.0f))
+    return fail(ctx, MP_ERR_ARG, "%s: weight, bias_w and step_w must be finite and step_w > 0", who);
+  if (!mask && !prt) return fail(ctx, MP_ERR_ARG, "%s: no output requested", who);
+  if (max_verts > 0x7fffffffLL / 9)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: capacities beyond 2^31 / 9 are not supported", who);
+  if (((uintptr_t)dirs | (uintptr_t)basis) & 3) return fail(ctx, MP_ERR_ARG, "%s: misaligned table", who);
+  if (max_verts == 0) verts = nullptr, normals = nullptr;
+  rc = check_frames(ctx, who, n_frames, nullptr, counts, bits, verts, normals, max_verts ? prt : nullptr);
+  if (rc != MP_OK) return rc;
+  if (mask && max_verts)
+    for (int f = 0; f < n_frames; ++f)
+      if (!mask[f] || ((uintptr_t)mask[f] & 7))
+        return fail(ctx, MP_ERR_ARG, "%s: null or misaligned mask for frame %d", who, f);
+  if (max_verts == 0) return MP_OK;
+  const size_t nv = (size_t)max_verts;
+  const FrameSpans outs[2] = {{mask, nv * (size_t)(n_dirs / 64) * 8}, {prt, nv * 36}};
+  const FrameSpans ins[4] = {{verts, nv * 12}, {normals, nv * 12}, {counts, 4}, {bits, (size_t)volume_bits_words(r) * 4}};
+  rc = check_no_alias(ctx, who, n_frames, outs, ins);
+  if (rc != MP_OK) return rc;
+  for (int f = 0; f < n_frames; ++f)
+    for (int i = 0; i < n_frames; ++i)
+      if (ranges_overlap(outs[0].of(f), outs[0].bytes, outs[1].of(i), outs[1].bytes) ||
+          (f != i && (ranges_overlap(outs[0].of(f), outs[0].bytes, outs[0].of(i), outs[0].bytes) ||
+                      ranges_overlap(outs[1].of(f), outs[1].bytes, outs[1].of(i), outs[1].bytes))))
+        return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases an output of frame %d", who, f, i);
+  // the per-call device tables are inputs of every frame
+  for (int f = 0; f < n_frames; ++f)
+    for (const FrameSpans &o : outs)
+      if (ranges_overlap(o.of(f), o.bytes, dirs, (size_t)n_dirs * 12) ||
+          ranges_overlap(o.of(f), o.bytes, basis, (size_t)n_dirs * 36))
+        return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases dirs or basis", who, f);
+  TransferRays rays;
+  for (int a = 0; a < 3; ++a) rays.bmin[a] = b_min[a], rays.bmax[a] = b_max[a];
+  rays.r = r;
+  rays.n_dirs = n_dirs;
+  rays.max_steps = max_steps;
+  rays.dirs = dirs;
+  rays.basis = basis;
+  rays.weight = weight;
+  rays.bias_w = bias_w;
+  rays.step_w = step_w;
+  DeviceGuard g(ctx->device);
+  return launch_mesh_transfer_batch(ctx, n_frames, verts, normals, max_verts, counts, bits, rays, mask, prt,
                                     (hipStream_t)stream);
+}
+
+static int transfer_shade_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *prt,
+                                  int64_t max_verts, const int32_t *const *counts, const float *sh, float *const *out,
+                                  mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (!counts || !sh || max_verts < 0 || (max_verts > 0 && (!prt || !out))) return bad_argument(ctx, who);
+  if (!all_finite(sh, 27)) return fail(ctx, MP_ERR_ARG, "%s: sh must be finite", who);
+  if (max_verts > 0x7fffffffLL / 9)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: capacities beyond 2^31 / 9 are not supported", who);
+  if (max_verts == 0) prt = nullptr, out = nullptr;
+  rc = check_frames(ctx, who, n_frames, nullptr, counts, prt, out);
+  if (rc != MP_OK) return rc;
+  if (max_verts == 0) return MP_OK;
+  const FrameSpans outs[1] = {{out, (size_t)max_verts * 12}};
+  const FrameSpans ins[2] = {{prt, (size_t)max_verts * 36}, {counts, 4}};
+  rc = check_no_alias(ctx, who, n_frames, outs, ins);
+  if (rc != MP_OK) return rc;
+  for (int f = 0; f < n_frames; ++f)
+    for (int i = 0; i < f; ++i)
+      if (ranges_overlap(outs[0].of(f), outs[0].bytes, outs[0].of(i), outs[0].bytes))
+        return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases an output of frame %d", who, f, i);
+  DeviceGuard g(ctx->device);
+  return launch_mesh_transfer_shade_batch(ctx, n_frames, prt, max_verts, counts, sh, out, (hipStream_t)stream);
 }
 
 static int keep_largest_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *volume, int r,
@@ -1983,8 +2104,8 @@ int mp_picture_light(mp_ctx *ctx, const float *normal, const int32_t *face_id, c
                      const float *direct_dir, const float *direct_rgb, float gamma, const float *normal_mats,
                      float background, float *image_out, float *shading, mp_stream stream) {
   return picture_light_checked(ctx, "mp_picture_light", 1, &normal, &face_id, albedo ? &albedo : nullptr, albedo_rgb,
-                               visibility ? &visibility : nullptr, n_pixels, n_views, sh, direct_dir, direct_rgb, gamma,
-                               normal_mats, background, image_out ? &image_out : nullptr,
+                               visibility ? &visibility : nullptr, nullptr, false, n_pixels, n_views, sh, direct_dir,
+                               direct_rgb, gamma, normal_mats, background, image_out ? &image_out : nullptr,
                                shading ? &shading : nullptr, stream);
 }
 
@@ -1994,8 +2115,68 @@ int mp_picture_light_batch(mp_ctx *ctx, int n_frames, const float *const *normal
                            const float *direct_rgb, float gamma, const float *normal_mats, float background,
                            float *const *image_out, float *const *shading, mp_stream stream) {
   return picture_light_checked(ctx, "mp_picture_light_batch", n_frames, normal, face_id, albedo, albedo_rgb, visibility,
-                               n_pixels, n_views, sh, direct_dir, direct_rgb, gamma, normal_mats, background, image_out,
-                               shading, stream);
+                               nullptr, false, n_pixels, n_views, sh, direct_dir, direct_rgb, gamma, normal_mats,
+                               background, image_out, shading, stream);
+}
+
+int mp_picture_light_transfer(mp_ctx *ctx, const float *normal, const int32_t *face_id, const float *albedo,
+                              const float *albedo_rgb, const float *visibility, const float *ambient, int64_t n_pixels,
+                              const float *direct_dir, const float *direct_rgb, float gamma, float background,
+                              float *image_out, float *shading, mp_stream stream) {
+  return picture_light_checked(ctx, "mp_picture_light_transfer", 1, normal ? &normal : nullptr, &face_id,
+                               albedo ? &albedo : nullptr, albedo_rgb, visibility ? &visibility : nullptr,
+                               ambient ? &ambient : nullptr, true, n_pixels, 1, nullptr, direct_dir, direct_rgb, gamma,
+                               nullptr, background, image_out ? &image_out : nullptr, shading ? &shading : nullptr,
+                               stream);
+}
+
+int mp_picture_light_transfer_batch(mp_ctx *ctx, int n_frames, const float *const *normal,
+                                    const int32_t *const *face_id, const float *const *albedo, const float *albedo_rgb,
+                                    const float *const *visibility, const float *const *ambient, int64_t n_pixels,
+                                    const float *direct_dir, const float *direct_rgb, float gamma, float background,
+                                    float *const *image_out, float *const *shading, mp_stream stream) {
+  return picture_light_checked(ctx, "mp_picture_light_transfer_batch", n_frames, normal, face_id, albedo, albedo_rgb,
+                               visibility, ambient, true, n_pixels, 1, nullptr, direct_dir, direct_rgb, gamma, nullptr,
+                               background, image_out, shading, stream);
+}
+
+int64_t mp_volume_bits_words(int r) { return r < 1 || r > MP_TRANSFER_MAX_RES ? 0 : (int64_t)volume_bits_words(r); }
+
+int mp_volume_bits(mp_ctx *ctx, const float *volume, int r, float level, uint32_t *bits, mp_stream stream) {
+  return volume_bits_checked(ctx, "mp_volume_bits", 1, &volume, r, level, &bits, nullptr, stream);
+}
+
+int mp_volume_bits_batch(mp_ctx *ctx, int n_frames, const float *const *volume, int r, float level,
+                         uint32_t *const *bits, const int32_t *const *gates, mp_stream stream) {
+  return volume_bits_checked(ctx, "mp_volume_bits_batch", n_frames, volume, r, level, bits, gates, stream);
+}
+
+int mp_mesh_transfer(mp_ctx *ctx, const float *verts, const float *normals, int64_t max_verts, const int32_t *counts,
+                     const uint32_t *bits, int r, const float *b_min, const float *b_max, int n_dirs, const float *dirs,
+                     const float *basis, float weight, float bias_w, float step_w, int max_steps, uint64_t *mask,
+                     float *prt, mp_stream stream) {
+  return mesh_transfer_checked(ctx, "mp_mesh_transfer", 1, &verts, &normals, max_verts, &counts, &bits, r, b_min, b_max,
+                               n_dirs, dirs, basis, weight, bias_w, step_w, max_steps, mask ? &mask : nullptr,
+                               prt ? &prt : nullptr, stream);
+}
+
+int mp_mesh_transfer_batch(mp_ctx *ctx, int n_frames, const float *const *verts, const float *const *normals,
+                           int64_t max_verts, const int32_t *const *counts, const uint32_t *const *bits, int r,
+                           const float *b_min, const float *b_max, int n_dirs, const float *dirs, const float *basis,
+                           float weight, float bias_w, float step_w, int max_steps, uint64_t *const *mask,
+                           float *const *prt, mp_stream stream) {
+  return mesh_transfer_checked(ctx, "mp_mesh_transfer_batch", n_frames, verts, normals, max_verts, counts, bits, r,
+                               b_min, b_max, n_dirs, dirs, basis, weight, bias_w, step_w, max_steps, mask, prt, stream);
+}
+
+int mp_mesh_transfer_shade(mp_ctx *ctx, const float *prt, int64_t max_verts, const int32_t *counts, const float *sh,
+                           float *out, mp_stream stream) {
+  return transfer_shade_checked(ctx, "mp_mesh_transfer_shade", 1, &prt, max_verts, &counts, sh, &out, stream);
+}
+
+int mp_mesh_transfer_shade_batch(mp_ctx *ctx, int n_frames, const float *const *prt, int64_t max_verts,
+                                 const int32_t *const *counts, const float *sh, float *const *out, mp_stream stream) {
+  return transfer_shade_checked(ctx, "mp_mesh_transfer_shade_batch", n_frames, prt, max_verts, counts, sh, out, stream);
 }
 
 int mp_volume_keep_largest(mp_ctx *ctx, const float *volume, int r, float level, int connectivity, float fill,

@@ -21,6 +21,7 @@ struct LightFrames {
   const float *vis[kMaxFrames];        // [L]; nullptr: nothing occludes the light
   uint32_t *image[kMaxFrames];         // nullptr: not wanted; may be albedo
   float *shading[kMaxFrames];          // nullptr: not wanted
+  const float *ambient[kMaxFrames];    // [L,3]; picture_light<true> only: the SH term, given per pixel
   float mats[kLightMaxMats][9];        // frame-major, then view; unused without has_mats
 };
 struct LightParams {
@@ -31,20 +32,10 @@ struct LightParams {
 };
 static_assert(sizeof(LightFrames) + sizeof(LightParams) + 256 <= 4096, "picture_light: kernel arguments");
 
-// v / |v|, or (0, 0, 0) where |v|^2 is not finite or not > 0 (a zero, a NaN, an inf, an overflow)
-__device__ __forceinline__ void light_normalise(float x, float y, float z, float &ox, float &oy, float &oz) {
-  const float s = (x * x + y * y) + z * z;
-  if (!(__builtin_isfinite(s) && s > 0.0f)) {
-    ox = oy = oz = 0.0f;
-    return;
-  }
-  const float len = sqrtf(s);  // the correctly rounded one (vertices.hip)
-  ox = x / len;
-  oy = y / len;
-  oz = z / len;
-}
-
 // no __restrict__ on albedo / image: image may be albedo; a thread reads its pixel, then writes it
+// kAmbient (mp_picture_light_transfer): res starts from ambient[p] instead of the basis at the normal; the normal
+// picture may then be nullptr where there is no direct term
+template <bool kAmbient>
 __global__ __launch_bounds__(kLightBlock) void picture_light(LightFrames fr, LightParams pa, int n_pixels) {
   const long long p = (long long)blockIdx.x * kLightBlock + threadIdx.x;
   if (p >= n_pixels) return;
@@ -69,32 +60,37 @@ __global__ __launch_bounds__(kLightBlock) void picture_light(LightFrames fr, Lig
     return;
   }
   const float *__restrict__ nrm = fr.normal[f];
-  float nx, ny, nz;
-  light_normalise(nrm[3 * p], nrm[3 * p + 1], nrm[3 * p + 2], nx, ny, nz);
-  float mx = nx, my = ny, mz = nz;  // the SH normal
-  if (pa.has_mats) {
-    const float *m = fr.mats[f * pa.n_views + (int)(p / pa.view_pixels)];
-    const float tx = (m[0] * nx + m[1] * ny) + m[2] * nz;
-    const float ty = (m[3] * nx + m[4] * ny) + m[5] * nz;
-    const float tz = (m[6] * nx + m[7] * ny) + m[8] * nz;
-    light_normalise(tx, ty, tz, mx, my, mz);
-  }
-  const float c1 = 0.429043f, c2 = 0.511664f, c3 = 0.743125f, c4 = 0.886227f, c5 = 0.247708f;
-  float h[9];
-  h[0] = c4;
-  h[1] = (2.0f * c2) * my;
-  h[2] = (2.0f * c2) * mz;
-  h[3] = (2.0f * c2) * mx;
-  h[4] = ((2.0f * c1) * mx) * my;
-  h[5] = ((2.0f * c1) * my) * mz;
-  h[6] = ((c3 * mz) * mz) - c5;
-  h[7] = ((2.0f * c1) * mz) * mx;
-  h[8] = c1 * ((mx * mx) - (my * my));
+  float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+  if (!kAmbient || nrm) light_normalise(nrm[3 * p], nrm[3 * p + 1], nrm[3 * p + 2], nx, ny, nz);
   float res[3] = {0.0f, 0.0f, 0.0f};
+  if constexpr (kAmbient) {
 #pragma unroll
-  for (int i = 0; i < 9; ++i) {
+    for (int c = 0; c < 3; ++c) res[c] = fr.ambient[f][3 * p + c];
+  } else {
+    float mx = nx, my = ny, mz = nz;  // the SH normal
+    if (pa.has_mats) {
+      const float *m = fr.mats[f * pa.n_views + (int)(p / pa.view_pixels)];
+      const float tx = (m[0] * nx + m[1] * ny) + m[2] * nz;
+      const float ty = (m[3] * nx + m[4] * ny) + m[5] * nz;
+      const float tz = (m[6] * nx + m[7] * ny) + m[8] * nz;
+      light_normalise(tx, ty, tz, mx, my, mz);
+    }
+    const float c1 = 0.429043f, c2 = 0.511664f, c3 = 0.743125f, c4 = 0.886227f, c5 = 0.247708f;
+    float h[9];
+    h[0] = c4;
+    h[1] = (2.0f * c2) * my;
+    h[2] = (2.0f * c2) * mz;
+    h[3] = (2.0f * c2) * mx;
+    h[4] = ((2.0f * c1) * mx) * my;
+    h[5] = ((2.0f * c1) * my) * mz;
+    h[6] = ((c3 * mz) * mz) - c5;
+    h[7] = ((2.0f * c1) * mz) * mx;
+    h[8] = c1 * ((mx * mx) - (my * my));
 #pragma unroll
-    for (int c = 0; c < 3; ++c) res[c] = res[c] + h[i] * pa.sh[3 * i + c];
+    for (int i = 0; i < 9; ++i) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) res[c] = res[c] + h[i] * pa.sh[3 * i + c];
+    }
   }
   if (pa.has_direct) {  // on the world normal, whatever the SH frame
     const float t = -((pa.dir[0] * nx + pa.dir[1] * ny) + pa.dir[2] * nz);
@@ -126,7 +122,8 @@ __global__ __launch_bounds__(kLightBlock) void picture_light(LightFrames fr, Lig
 
 int launch_picture_light_batch(mp_ctx *ctx, int n_frames, const float *const *normal, const int32_t *const *face_id,
                                const float *const *albedo, const float *albedo_rgb, const float *const *visibility,
-                               long long n_pixels, int n_views, const float *sh, const float *direct_dir,
+                               const float *const *ambient, long long n_pixels, int n_views, const float *sh,
+                               const float *direct_dir,
                                const float *direct_rgb, float gamma, const float *normal_mats, float background,
                                float *const *image_out, float *const *shading, hipStream_t st) {
   LightFrames fr;
@@ -134,7 +131,8 @@ int launch_picture_light_batch(mp_ctx *ctx, int n_frames, const float *const *no
   std::memset(&fr, 0, sizeof(fr));
   std::memset(&pa, 0, sizeof(pa));
   for (int f = 0; f < n_frames; ++f) {
-    fr.normal[f] = normal[f];
+    fr.normal[f] = normal ? normal[f] : nullptr;
+    fr.ambient[f] = ambient ? ambient[f] : nullptr;
     fr.face[f] = face_id[f];
     fr.albedo[f] = albedo ? reinterpret_cast<const uint32_t *>(albedo[f]) : nullptr;
     fr.vis[f] = visibility ? visibility[f] : nullptr;
@@ -142,7 +140,7 @@ int launch_picture_light_batch(mp_ctx *ctx, int n_frames, const float *const *no
     fr.shading[f] = shading ? shading[f] : nullptr;
   }
   if (normal_mats) std::memcpy(fr.mats, normal_mats, sizeof(float) * 9 * (size_t)n_frames * n_views);
-  std::memcpy(pa.sh, sh, sizeof(pa.sh));
+  if (sh) std::memcpy(pa.sh, sh, sizeof(pa.sh));
   for (int c = 0; c < 3; ++c) {
     pa.dir[c] = direct_dir[c];
     pa.rgb[c] = direct_rgb[c];
@@ -155,8 +153,11 @@ int launch_picture_light_batch(mp_ctx *ctx, int n_frames, const float *const *no
   pa.has_direct = direct_rgb[0] != 0.0f || direct_rgb[1] != 0.0f || direct_rgb[2] != 0.0f;
   pa.n_views = n_views;
   pa.view_pixels = (int)(n_pixels / n_views);
-  hipLaunchKernelGGL(picture_light, dim3((unsigned)((n_pixels + kLightBlock - 1) / kLightBlock), n_frames),
-                     dim3(kLightBlock), 0, st, fr, pa, (int)n_pixels);
+  const dim3 grid((unsigned)((n_pixels + kLightBlock - 1) / kLightBlock), n_frames);
+  if (ambient)
+    hipLaunchKernelGGL(picture_light<true>, grid, dim3(kLightBlock), 0, st, fr, pa, (int)n_pixels);
+  else
+    hipLaunchKernelGGL(picture_light<false>, grid, dim3(kLightBlock), 0, st, fr, pa, (int)n_pixels);
   MP_HIP(ctx, hipGetLastError());
   return MP_OK;
 }

@@ -496,13 +496,44 @@ int launch_picture_shadow_batch(mp_ctx *ctx, int n_frames, const float *const *i
 // light.hip: n_frames pictures of n_pixels = n_views * (pixels per view) each, lit by one parameter set (sh[27],
 // direct_dir[3], direct_rgb[3], gamma, background: host).  albedo: nullptr (then albedo_rgb[3], host) or n_frames
 // entries; visibility, image_out (may be albedo[f]), shading: nullptr or n_frames entries.  normal_mats: nullptr or
-// host, n_frames * n_views (<= kLightMaxMats) row-major 3x3
+// host, n_frames * n_views (<= kLightMaxMats) row-major 3x3.  ambient: nullptr, or n_frames entries [n_pixels,3] that
+// stand in for the SH term (mp_picture_light_transfer: sh and normal_mats unused, normal may be nullptr)
 constexpr int kLightMaxMats = 32;
 int launch_picture_light_batch(mp_ctx *ctx, int n_frames, const float *const *normal, const int32_t *const *face_id,
                                const float *const *albedo, const float *albedo_rgb, const float *const *visibility,
-                               long long n_pixels, int n_views, const float *sh, const float *direct_dir,
-                               const float *direct_rgb, float gamma, const float *normal_mats, float background,
-                               float *const *image_out, float *const *shading, hipStream_t st);
+                               const float *const *ambient, long long n_pixels, int n_views, const float *sh,
+                               const float *direct_dir, const float *direct_rgb, float gamma, const float *normal_mats,
+                               float background, float *const *image_out, float *const *shading, hipStream_t st);
+#ifdef __HIPCC__
+// v / |v|, or (0, 0, 0) where |v|^2 is not finite or not > 0 (a zero, a NaN, an inf, an overflow)
+__device__ __forceinline__ void light_normalise(float x, float y, float z, float &ox, float &oy, float &oz) {
+  const float s = (x * x + y * y) + z * z;
+  if (!(__builtin_isfinite(s) && s > 0.0f)) {
+    ox = oy = oz = 0.0f;
+    return;
+  }
+  const float len = sqrtf(s);  // the correctly rounded one (vertices.hip)
+  ox = x / len;
+  oy = y / len;
+  oz = z / len;
+}
+#endif
+// transfer.hip: occupancy bits of n_frames volumes of one resolution (fine bits, then one bit per 8^3 block), the
+// radiance transfer of n_frames meshes traced through them, and its product with the lighting's coefficients
+long long volume_bits_words(int r);
+int launch_volume_bits_batch(mp_ctx *ctx, int n_frames, const float *const *vol, int r, float level,
+                             uint32_t *const *bits, const int32_t *const *gate, hipStream_t st);
+struct TransferRays {  // host values of one call
+  float bmin[3], bmax[3];
+  int r, n_dirs, max_steps;
+  const float *dirs, *basis;  // device [n_dirs,3], [n_dirs,9]
+  float weight, bias_w, step_w;
+};
+int launch_mesh_transfer_batch(mp_ctx *ctx, int n_frames, const float *const *verts, const float *const *normals,
+                               long long max_v, const int32_t *const *counts, const uint32_t *const *bits,
+                               const TransferRays &rays, uint64_t *const *mask, float *const *prt, hipStream_t st);
+int launch_mesh_transfer_shade_batch(mp_ctx *ctx, int n_frames, const float *const *prt, long long max_v,
+                                     const int32_t *const *counts, const float *sh, float *const *out, hipStream_t st);
 
 // conv3x3.hip
 int launch_conv3x3_pack(mp_ctx *ctx, const float *w, int cout, int cin, float *wp, hipStream_t st);

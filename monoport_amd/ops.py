@@ -2140,7 +2140,7 @@ def self_shades(who, positions, face_ids, lighting, shadow, out=None):
 
 def light_pictures_batch(who, verts, faces, counts, normals, calibs, res, lighting, images, projection="orthogonal",
                          nearest="max", background=1.0, near=None, perspective_correct=False, capacity=None, shadow=None,
-                         buffers=None, shades=None):
+                         buffers=None, shades=None, transfers=None):
     """The subjects' pictures ``images`` (per mesh [n_views,H,W,3], as ``_mesh_render`` / ``render_netc_batch`` left
     them) lit in place by ``lighting`` (a ``recon.Lighting``: sh, direct_dir, direct_rgb, gamma, frame, albedo,
     self_shadow), no host value in between: (1) a second pass of the rasteriser with ``attr = normals`` (per mesh
@@ -2150,9 +2150,13 @@ def light_pictures_batch(who, verts, faces, counts, normals, calibs, res, lighti
     bias ``self_shadow``; (3) ``picture_light_batch``: the images are the albedo and the output, or -- with a constant
     ``lighting.albedo`` -- the output only.  ``frame="camera"`` takes the 3x3 of every view's calib as its normal
     matrix.  ``buffers``: None (fresh), or a dict with ``normal`` [n,n_views,H,W,3], ``face`` [n,n_views,H,W] and, for
-    the self-shadow, ``pos`` [n,n_views,H,W,3] and ``shade`` [n,n_views,H,W].  ``shades``: the self-shadow's shades
+    the self-shadow, ``pos`` [n,n_views,H,W,3] and ``shade`` [n,n_views,H,W], for the transfer ``ambient``
+    [n,n_views,H,W,3] and ``transfer_shade`` [n,max_v,3].  ``shades``: the self-shadow's shades
     where the caller has made them from a position picture it had (``render_netc_batch``'s hook): step (2) is then
-    skipped.  Returns (per mesh the normal pass's (image, None, face), the shades or None)."""
+    skipped.  ``transfers`` (with ``lighting.transfer``): per mesh the [V,9] radiance transfer of its vertices
+    (``mesh_transfer_raw``); the SH term is then a third pass of the rasteriser with ``attr = mesh_transfer_shade`` and
+    step (3) is ``picture_light_transfer_batch``.  Returns (per mesh the normal pass's (image, None, face), the shades or
+    None)."""
     n = len(verts)
     out = None if buffers is None else (buffers["normal"], None, buffers["face"])
     cams = _calib_list(calibs, n, who)
@@ -2176,12 +2180,235 @@ def light_pictures_batch(who, verts, faces, counts, normals, calibs, res, lighti
         shades = self_shades(who, [p[0] for p in pos], face_ids, lighting, shadow,
                              None if buffers is None else buffers["shade"][:n])
     nv = nraws[0][0].shape[0]
-    mats = np.stack([normal_mats_of(who, c) for c in cams]) if lighting.frame == "camera" else None
     direct = None if lighting.direct is None else (lighting.direct_dir, lighting.direct_rgb)
+    if transfers is not None:  # the SH term is the rasterised product of the vertices' transfer and sh
+        sizes = [c.contiguous() for c in counts]
+        if buffers is None:  # meshes of their own sizes: one launch per size (the call's spans are its capacity's)
+            ts, by_size = [None] * n, {}
+            for f, t in enumerate(transfers):
+                by_size.setdefault(int(t.shape[0]), []).append(f)
+            for fs in by_size.values():
+                rows = _mesh_transfer_shade(who, [_f32c(transfers[f]) for f in fs], [sizes[f] for f in fs], lighting.sh,
+                                            None)
+                for f, row in zip(fs, rows):
+                    ts[f] = row
+        else:
+            ts = _mesh_transfer_shade(who, list(transfers), sizes, lighting.sh, buffers["transfer_shade"])
+        araws = _mesh_render(who, verts, faces, counts, ts, cams, res, projection, nearest, False, 1.0, 0.0, -math.inf,
+                             math.inf, background, None if buffers is None else (buffers["ambient"], None, None),
+                             capacity=capacity, near=near, perspective_correct=perspective_correct)
+        picture_light_transfer_batch([r[0] for r in araws], [r[0] for r in nraws], face_ids,
+                                     None if lighting.albedo is not None else list(images), direct, lighting.gamma,
+                                     shades, lighting.albedo, background, out=(list(images), None), who=who)
+        return nraws, shades
+    mats = np.stack([normal_mats_of(who, c) for c in cams]) if lighting.frame == "camera" else None
     picture_light_batch([r[0] for r in nraws], face_ids, None if lighting.albedo is not None else list(images),
                         lighting.sh, direct, lighting.gamma, mats, shades, lighting.albedo, nv, background,
                         out=(list(images), None), who=who)
     return nraws, shades
+
+
+TRANSFER_MAX_RES = 513  # MP_TRANSFER_MAX_RES
+TRANSFER_MAX_DIRS = 512  # MP_TRANSFER_MAX_DIRS
+
+
+def volume_bits_words(r):
+    """mp_volume_bits_words: the 32-bit words of a ``volume_bits`` buffer at resolution ``r``: r * r * ceil(r / 32)
+    words of occupancy bits, then the tracer's private block bits."""
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 1 <= r <= TRANSFER_MAX_RES:
+        raise ValueError("volume_bits_words: resolution must be an int in 1..%d, got %r" % (TRANSFER_MAX_RES, r))
+    nb = (r + 7) // 8
+    return r * r * ((r + 31) // 32) + (nb ** 3 + 31) // 32
+
+
+def _volume_bits(who, volumes, level, gates, out):
+    vols, n, r, dev = _one_size_volumes(who, volumes)
+    words = volume_bits_words(r)
+    _gates(who, gates, n, dev)
+    if out is None:
+        out = torch.empty((n, words), dtype=torch.int32, device=dev).unbind(0)
+    else:
+        out = _frame_rows(who, "out", out, n, (words,), torch.int32, dev)
+    ctx = get_context(dev)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_volume_bits_batch(
+            ctx.handle, f1 - f0, _ptr_array(vols[f0:f1]), r, float(level), _ptr_array(out[f0:f1]),
+            None if gates is None else _ptr_array(gates[f0:f1]), _stream(vols[0])), "mp_volume_bits_batch")
+    _keep_until_done(dev, vols, gates)
+    return list(out)
+
+
+def volume_bits_raw(volume, level=0.5, out=None):
+    """mp_volume_bits_batch with one frame: the occupancy bits of a cubic f32 volume [R,R,R], R <= 513, as int32
+    [volume_bits_words(R)] on the device: bit x & 31 of word (z*R + y) * ceil(R/32) + (x >> 5) is set iff v > level (a
+    NaN is empty, padding bits are 0); the words past R * R * ceil(R/32) are ``mesh_transfer``'s own.  No host sync."""
+    return _volume_bits("volume_bits_raw", [volume], level, None, None if out is None else [out])[0]
+
+
+def volume_bits_raw_batch(volumes, level=0.5, gates=None, out=None):
+    """mp_volume_bits_batch: ``[volume_bits_raw(v, level) for v in volumes]`` in two launches per MAX_FRAMES volumes,
+    the same bits.  ``gates``: as ``marching_cubes_raw_batch``; a gated-off frame is not read or written.  ``out``:
+    int32 [n, words] to write into."""
+    return _volume_bits("volume_bits_raw_batch", volumes, level, gates, out)
+
+
+def transfer_params(who, r, b_min, b_max, n_dirs, dirs, basis, weight, bias_w, step_w, max_steps):
+    """The host values of mp_mesh_transfer checked: the ValueError of one it refuses."""
+    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 1 <= r <= TRANSFER_MAX_RES:
+        raise ValueError("%s: resolution must be an int in 1..%d, got %r" % (who, TRANSFER_MAX_RES, r))
+    if (isinstance(n_dirs, bool) or not isinstance(n_dirs, (int, np.integer)) or n_dirs % 64
+            or not 64 <= n_dirs <= TRANSFER_MAX_DIRS):
+        raise ValueError("%s: n_dirs must be a multiple of 64 in 64..%d, got %r" % (who, TRANSFER_MAX_DIRS, n_dirs))
+    if isinstance(max_steps, bool) or not isinstance(max_steps, (int, np.integer)) or not 1 <= max_steps <= 1 << 24:
+        raise ValueError("%s: max_steps must be an int in 1..2^24, got %r" % (who, max_steps))
+    lo, hi = _finite_floats(who, "b_min", b_min, (3,)), _finite_floats(who, "b_max", b_max, (3,))
+    if not (hi > lo).all():
+        raise ValueError("%s: b_max must be > b_min on every axis, got %r and %r" % (who, b_min, b_max))
+    vals = [float(np.float32(v)) for v in (weight, bias_w, step_w)]
+    if not all(math.isfinite(v) for v in vals) or not vals[2] > 0:
+        raise ValueError("%s: weight, bias_w and step_w must be finite and step_w > 0, got %r" % (who, vals))
+    for what, t, k in (("dirs", dirs, 3), ("basis", basis, 9)):
+        if (not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (n_dirs, k)
+                or not t.is_contiguous()):
+            raise ValueError("%s: %s must be a contiguous float32 [%d,%d] tensor" % (who, what, n_dirs, k))
+    return lo, hi, vals
+
+
+def _mesh_transfer(who, verts, normals, counts, bits, r, b_min, b_max, dirs, basis, weight, bias_w, step_w, max_steps,
+                   want, out):
+    """``want``: (mask, prt) booleans; ``out``: None or (masks or None, prts or None) to write into."""
+    n, max_v, _, dev = _mesh_frames(who, verts, None, counts)
+    n_dirs = int(dirs.shape[0]) if torch.is_tensor(dirs) and dirs.dim() == 2 else 0
+    lo, hi, (weight, bias_w, step_w) = transfer_params(who, r, b_min, b_max, n_dirs, dirs, basis, weight, bias_w,
+                                                       step_w, max_steps)
+    if dirs.device != dev or basis.device != dev:
+        raise ValueError("%s: dirs and basis must live on the meshes' device" % who)
+    normals = _frame_rows(who, "normals", normals, n, (max_v, 3), torch.float32, dev)
+    bits = _frame_rows(who, "bits", bits, n, (volume_bits_words(r),), torch.int32, dev)
+    words = n_dirs // 64
+    if out is None:
+        mask = torch.empty((n, max_v, words), dtype=torch.int64, device=dev).unbind(0) if want[0] else None
+        prt = torch.empty((n, max_v, 9), dtype=torch.float32, device=dev).unbind(0) if want[1] else None
+    else:
+        mask = None if out[0] is None else _frame_rows(who, "out[0] (mask)", out[0], n, (max_v, words), torch.int64, dev)
+        prt = None if out[1] is None else _frame_rows(who, "out[1] (prt)", out[1], n, (max_v, 9), torch.float32, dev)
+    if mask is None and prt is None:
+        raise ValueError("%s: no output requested" % who)
+    ctx = get_context(dev)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_mesh_transfer_batch(
+            ctx.handle, f1 - f0, _ptr_array(verts[f0:f1]), _ptr_array(normals[f0:f1]), max_v,
+            _ptr_array(counts[f0:f1]), _ptr_array(bits[f0:f1]), int(r), _float3(lo), _float3(hi), n_dirs, _ptr(dirs),
+            _ptr(basis), weight, bias_w, step_w, int(max_steps), None if mask is None else _ptr_array(mask[f0:f1]),
+            None if prt is None else _ptr_array(prt[f0:f1]), _stream(verts[0])), "mp_mesh_transfer_batch")
+    _keep_until_done(dev, verts, normals, counts, bits, [dirs, basis])
+    return [(None if mask is None else mask[f], None if prt is None else prt[f]) for f in range(n)]
+
+
+def mesh_transfer_raw(verts, normals, counts, bits, r, b_min, b_max, dirs, basis, weight, bias_w, step_w, max_steps,
+                      want=(True, True), out=None):
+    """mp_mesh_transfer_batch with one frame: verts / normals [max_v,3] f32, counts int32[2], bits (``volume_bits_raw``
+    at resolution ``r``) on the device; ``dirs`` [D,3] and ``basis`` [D,9] device f32 tables; weight, bias_w, step_w
+    (world units) and max_steps host values -> (mask int64 [max_v, D/64]: the 64-bit visibility words, bit d & 63 of
+    word d >> 6; prt f32 [max_v,9]); either is None where ``want`` = (mask, prt) says so.  Rows beyond counts[0] are
+    not written.  Defined bit for bit in include/monoport_hip.h.  No host sync."""
+    return _mesh_transfer("mesh_transfer_raw", [verts], [normals], [counts], [bits], r, b_min, b_max, dirs, basis,
+                          weight, bias_w, step_w, max_steps, want,
+                          None if out is None else tuple(None if o is None else [o] for o in out))[0]
+
+
+def mesh_transfer_raw_batch(verts, normals, counts, bits, r, b_min, b_max, dirs, basis, weight, bias_w, step_w,
+                            max_steps, want=(True, True), out=None):
+    """mp_mesh_transfer_batch: ``mesh_transfer_raw`` per mesh (one capacity, one resolution, one parameter set) in one
+    launch per MAX_FRAMES meshes, the same bits.  ``out``: (mask [n,max_v,D/64] int64 or None, prt [n,max_v,9] f32 or
+    None)."""
+    return _mesh_transfer("mesh_transfer_raw_batch", verts, normals, counts, bits, r, b_min, b_max, dirs, basis, weight,
+                          bias_w, step_w, max_steps, want, out)
+
+
+def _mesh_transfer_shade(who, prts, counts, sh, out):
+    n = len(prts)
+    if n == 0 or len(counts) != n:
+        raise ValueError("%s: at least one mesh, and one counts per mesh" % who)
+    sh = _finite_floats(who, "sh", sh, (9, 3))
+    dev, max_v = prts[0].device, prts[0].shape[0]
+    counts = _frame_rows(who, "counts", counts, n, (2,), torch.int32, dev)
+    prts = _frame_rows(who, "prt", prts, n, (max_v, 9), torch.float32, dev)
+    if out is None:
+        out = torch.empty((n, max_v, 3), dtype=torch.float32, device=dev).unbind(0)
+    else:
+        out = _frame_rows(who, "out", out, n, (max_v, 3), torch.float32, dev)
+    if max_v == 0:
+        return list(out)
+    ctx = get_context(dev)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_mesh_transfer_shade_batch(
+            ctx.handle, f1 - f0, _ptr_array(prts[f0:f1]), max_v, _ptr_array(counts[f0:f1]),
+            sh.ctypes.data_as(_lib._pf32), _ptr_array(out[f0:f1]), _stream(prts[0])), "mp_mesh_transfer_shade_batch")
+    _keep_until_done(dev, prts, counts)
+    return list(out)
+
+
+def mesh_transfer_shade_raw(prt, counts, sh, out=None):
+    """mp_mesh_transfer_shade_batch with one frame: prt [max_v,9] f32 and ``sh`` [9,3] (host) -> t [max_v,3] f32, t_c =
+    sum over k ascending of prt_k * sh[k][c] from 0.0f; rows beyond counts[0] are not written.  No host sync."""
+    return _mesh_transfer_shade("mesh_transfer_shade_raw", [prt], [counts], sh, None if out is None else [out])[0]
+
+
+def mesh_transfer_shade_raw_batch(prts, counts, sh, out=None):
+    """mp_mesh_transfer_shade_batch: ``mesh_transfer_shade_raw`` per mesh in one launch per MAX_FRAMES meshes."""
+    return _mesh_transfer_shade("mesh_transfer_shade_raw_batch", prts, counts, sh, out)
+
+
+def picture_light_transfer_batch(ambients, normals, face_ids, albedos, direct=None, gamma=1.0, visibilities=None,
+                                 albedo_rgb=None, background=1.0, out=None, with_shading=False,
+                                 who="picture_light_transfer_batch"):
+    """mp_picture_light_transfer_batch: ``picture_light_batch`` with the SH term given per pixel: ``ambients``, per frame
+    float32 [...,3], the rasteriser's image for ``attr = mesh_transfer_shade_raw``'s t with the paint (1, 0, -inf, inf).
+    ``normals`` may be None without a ``direct`` term.  No ``normal_mats``: the camera frame is not built.  Everything
+    else, the outputs and the return value as ``picture_light_batch``."""
+    n = len(ambients)
+    if n == 0 or ambients[0].dim() < 2 or ambients[0].shape[-1] != 3:
+        raise ValueError("%s: at least one ambient picture [...,3]" % who)
+    shape = tuple(ambients[0].shape[:-1])
+    dev, npix = ambients[0].device, ambients[0].numel() // 3
+    if npix < 1:
+        raise ValueError("%s: at least one pixel" % who)
+    ambients = _flat_pictures(who, "ambients", ambients, n, torch.float32, 3, npix, dev)
+    if normals is not None:
+        normals = _flat_pictures(who, "normals", normals, n, torch.float32, 3, npix, dev)
+    face_ids = _flat_pictures(who, "face_ids", face_ids, n, torch.int32, 1, npix, dev)
+    if albedos is not None:
+        albedos = _flat_pictures(who, "albedos", albedos, n, torch.float32, 3, npix, dev)
+    if visibilities is not None:
+        visibilities = _flat_pictures(who, "visibilities", visibilities, n, torch.float32, 1, npix, dev)
+    if (albedos is None) == (albedo_rgb is None):
+        raise ValueError("%s: either albedo pictures or a constant albedo_rgb, not %s"
+                         % (who, "neither" if albedos is None else "both"))
+    _, ddir, drgb, gamma, albedo_rgb = light_params(who, np.zeros((9, 3), np.float32), direct, gamma, albedo_rgb)
+    if normals is None and drgb.any():
+        raise ValueError("%s: the direct term needs the normal pictures" % who)
+    background = float(background)
+    if not math.isfinite(background):
+        raise ValueError("%s: background must be finite, got %r" % (who, background))
+    if out is None:
+        image = torch.empty((n,) + shape + (3,), dtype=torch.float32, device=dev).unbind(0)
+        shading = torch.empty((n,) + shape + (3,), dtype=torch.float32, device=dev).unbind(0) if with_shading else None
+    else:
+        image = None if out[0] is None else _flat_pictures(who, "out[0] (image)", out[0], n, torch.float32, 3, npix, dev)
+        shading = (None if out[1] is None
+                   else _flat_pictures(who, "out[1] (shading)", out[1], n, torch.float32, 3, npix, dev))
+    if image is None and shading is None:
+        raise ValueError("%s: out names no output" % who)
+    ctx = get_context(dev)
+    pf = lambda a: None if a is None else np.ascontiguousarray(a).ctypes.data_as(_lib._pf32)  # noqa: E731
+    pa = lambda rows, f0, f1: None if rows is None else _ptr_array(list(rows[f0:f1]))  # noqa: E731
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_picture_light_transfer_batch(
+            ctx.handle, f1 - f0, pa(normals, f0, f1), pa(face_ids, f0, f1), pa(albedos, f0, f1), pf(albedo_rgb),
+            pa(visibilities, f0, f1), pa(ambients, f0, f1), npix, pf(ddir), pf(drgb), gamma, background,
+            pa(image, f0, f1), pa(shading, f0, f1), _stream(ambients[0])), "mp_picture_light_transfer_batch")
+    return [(None if image is None else image[f], None if shading is None else shading[f]) for f in range(n)]
 
 
 def render_scene_batch(who, scene, calibs, res, projection="orthogonal", nearest="max", near=None,

@@ -183,12 +183,21 @@ class FrameSlot:
         ``light_pos`` [batch,views,H,W,3] (the subject's positions; not with ``shade="netC"``, whose position picture
         is read before it is painted over); all filled on the slot's stream with no host value
         in between, then ``ops.picture_light_batch`` in place on ``pictures_image``.  It needs pictures with a
-        ``shade``, the mesh's normals, and for ``shade="normals"`` a constant ``lighting.albedo``."""
+        ``shade``, the mesh's normals, and for ``shade="normals"`` a constant ``lighting.albedo``.  With
+        ``lighting.transfer`` (a ``recon.Transfer``; without it none of this exists) the SH term is self-occluded: the
+        slot also owns ``transfer_bits`` [batch, ops.volume_bits_words(R)] int32 (packed inside the mesh chunk loop from
+        the volume marching cubes reads -- with ``clean`` the cleaned one --, under the frames' gates), ``transfer_prt``
+        [batch,cap_v,9], ``transfer_shade`` [batch,cap_v,3] and ``light_ambient`` [batch,views,H,W,3], and enqueues
+        ``ops.mesh_transfer_raw_batch``, the shade, a third pass of the rasteriser and
+        ``ops.picture_light_transfer_batch``; a frame whose mesh ``meshes()`` made again is traced again through its
+        bits."""
         self.views = self._head_views(netG, netC, mesh)  # images per frame; refuses what the slot class does not run
         # the option records are validated before anything is allocated
         self.mesh = None if mesh is None else _mesh_options(mesh, float(balance), netC is not None)
         self.picture_options = None if pictures is None else _picture_options(pictures, self.mesh, netC is not None)
         self.lighting = lighting
+        self._traces = getattr(lighting, "transfer", None) is not None  # the SH term is self-occluded
+        self._reran_transfer = {}  # frame -> the transfer ``meshes()`` traced for its re-run mesh
         if lighting is not None:
             from .recon import _check_lighting_options
             po = self.picture_options
@@ -309,6 +318,12 @@ class FrameSlot:
                     if po.shade != "netC":
                         self.light_pos = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
                     self.light_shade = torch.empty(shape, dtype=torch.float32, device=dev)
+                if self._traces:  # the volumes' bits, the vertices' transfer and its picture
+                    cap_v = self.mesh_buffers["verts"].shape[1]
+                    self.transfer_bits = torch.empty((b, ops.volume_bits_words(r)), dtype=torch.int32, device=dev)
+                    self.transfer_prt = torch.empty((b, cap_v, 9), dtype=torch.float32, device=dev)
+                    self.transfer_shade = torch.empty((b, cap_v, 3), dtype=torch.float32, device=dev)
+                    self.light_ambient = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
             # the cameras of the current submission, on the host [batch,views,3,4]; the identity until the first one
             self._cameras = np.tile(np.eye(4, dtype=np.float32)[:3], (b, po.views, 1, 1))
 
@@ -496,11 +511,35 @@ class FrameSlot:
                                   out=(None, self.shadow_depth[:n].unsqueeze(1), self.shadow_face[:n].unsqueeze(1)),
                                   near=light.near, perspective_correct=light.near is not None)
 
+    def _trace(self, chains, bits, out):
+        """The radiance transfer [cap,9] of the chains' vertices through their frames' ``bits`` (``out``: into it)."""
+        t = self.lighting.transfer
+        r = self.res[-1]
+        bias_w, step_w, steps = t.rays(r, self.b_min, self.b_max)
+        dirs, basis = t.tables(self.device)
+        return [p[1] for p in ops.mesh_transfer_raw_batch(
+            [c.verts for c in chains], [c.normals for c in chains], [c.counts for c in chains], list(bits), r,
+            self.b_min, self.b_max, dirs, basis, t.weight, bias_w, step_w, steps, want=(False, True),
+            out=None if out is None else (None, out))]
+
+    def _with_transfer(self, b, mesh):
+        """A re-run frame's mesh with the transfer ``meshes()`` traced for it, where the lighting wants one."""
+        if mesh is None or not self._traces:
+            return mesh
+        from .recon import with_transfer
+        return with_transfer(mesh, self._reran_transfer[b][:mesh.verts.shape[0]])
+
     def _light_subjects(self, n, light):
         """``lighting`` on the n frames' pictures, in place, from the chain's normals (a gated-off frame's normal pass
-        is uncovered: its picture keeps its bits)."""
+        is uncovered: its picture keeps its bits).  With ``lighting.transfer``: the transfer of the n frames' vertices
+        through the bits the mesh chain packed, then its shade and one more pass of the rasteriser, first."""
         po, chains = self.picture_options, self._mesh_chains[:n]
         buffers = {"normal": self.light_normal[:n], "face": self.light_face[:n]}
+        transfers = None
+        if self._traces:
+            cap = chains[0].verts.shape[0]  # the chain's capacity: the leading rows of the slot's buffers
+            transfers = self._trace(chains, self.transfer_bits[:n], self.transfer_prt[:n, :cap])
+            buffers.update(ambient=self.light_ambient[:n], transfer_shade=self.transfer_shade[:n, :cap])
         shadow = shades = None
         if self.lighting.self_shadow is not None:
             shadow = (light, list(self.shadow_depth[:n]), list(self.shadow_face[:n]))
@@ -512,7 +551,7 @@ class FrameSlot:
                                  [c.counts for c in chains], [c.normals for c in chains], list(self._cameras[:n]),
                                  po.res, self.lighting, list(self.pictures_image[:n]), po.projection, po.nearest,
                                  po.background, po.near, po.perspective_correct, shadow=shadow, buffers=buffers,
-                                 shades=shades)
+                                 shades=shades, transfers=transfers)
 
     def _render_subjects(self, n):
         """The pictures of the n frames' meshes alone, into ``pictures_image`` / ``pictures_depth`` / ``pictures_face``."""
@@ -564,6 +603,8 @@ class FrameSlot:
         po = self.picture_options
         out = []
         for b, mesh in enumerate(self.meshes()):
+            if b in self._reran:
+                mesh = self._with_transfer(b, mesh)
             if po.scene is not None:
                 out.append(self._scene_picture(b, mesh))
             elif mesh is None:
@@ -658,7 +699,8 @@ class FrameSlot:
                 out["preds"] = list(out["preds"])
             self._mesh_chains[b0:b1] = _mesh_chains(
                 self.volumes[b0:b1], self.b_min, self.b_max, self.mesh, self._mesh_bindings(b0, b1),
-                gates=[self.status[b, 0:1] for b in range(b0, b1)], out=out, view=self.view)
+                gates=[self.status[b, 0:1] for b in range(b0, b1)], out=out, view=self.view,
+                bits_out=self.transfer_bits[b0:b1] if self._traces else None)
 
     def meshes(self):
         """The meshes of the current submission, to be called after ``wait()`` (it waits if the caller has not): a
@@ -673,6 +715,7 @@ class FrameSlot:
         self.wait()
         n = self.n_active
         self._reran = []
+        self._reran_transfer = {}
         # per frame: alive, (vertices, faces) of the mesh [, with ``simplify``: those marching cubes needed]
         cols = [self.status[:n, 0:1], self.mesh_buffers["counts"][:n]]
         if self.mesh.simplify is not None:
@@ -681,8 +724,11 @@ class FrameSlot:
 
         def rerun(b, max_verts, max_faces):
             self._reran.append(b)
-            return _mesh_chains([self.volumes[b]], self.b_min, self.b_max, self.mesh, self._mesh_bindings(b, b + 1),
-                                max_verts=max_verts, max_faces=max_faces, view=self.view)[0]
+            chain = _mesh_chains([self.volumes[b]], self.b_min, self.b_max, self.mesh, self._mesh_bindings(b, b + 1),
+                                 max_verts=max_verts, max_faces=max_faces, view=self.view)[0]
+            if self._traces:  # traced again through the frame's bits, which the slot still holds
+                self._reran_transfer[b] = self._trace([chain], self.transfer_bits[b:b + 1], None)[0]
+            return chain
 
         return _collect_meshes([chain if row[0] else None for chain, row in zip(self._mesh_chains, host)],
                                [row[1:] for row in host], rerun)

@@ -1,6 +1,7 @@
 """Drop-ins for RTL/recon.py (``pifu_calib``, ``forward_vertices``) and for the colorization
 closure of RTL/main.py:201-249, on top of the HIP kernels in csrc/vertices.hip."""
 import collections
+import math
 
 import numpy as np
 import torch
@@ -251,7 +252,7 @@ are compared with), else None."""
 
 
 def _mesh_chains(sdfs, b_min, b_max, opts, bindings=None, gates=None, out=None, max_verts=None, max_faces=None,
-                 view=0):
+                 view=0, bits_out=None):
     """volume [-> its largest body] -> verts, faces [-> their vertex clustering] [-> Taubin passes] -> normals ->
     netC predictions for volumes of one size, every stage one set of launches for all of them and no host value in
     between: one ``MeshChain`` per volume (the chain of one volume is this on a list of one).  ``opts``: a
@@ -261,13 +262,18 @@ def _mesh_chains(sdfs, b_min, b_max, opts, bindings=None, gates=None, out=None, 
     too; a gated-off frame's counts of (0, 0) switch the later stages off.  ``out``: None or a dict of the caller's
     buffers (verts, faces, counts, normals, points, point_counts: [n, ...] tensors, preds: a list; with ``clean`` also
     cleaned [n,R,R,R] and clean_stats [n,4], with ``simplify`` simple_verts, simple_faces, simple_counts, simple_vmap,
-    with ``smooth`` smooth_verts).  ``max_verts`` / ``max_faces``: marching cubes' capacities, if not its defaults."""
+    with ``smooth`` smooth_verts).  ``max_verts`` / ``max_faces``: marching cubes' capacities, if not its defaults.
+    ``bits_out``: None, or int32 [n, ops.volume_bits_words(R)]: the occupancy bits (``ops.volume_bits_raw_batch``) of
+    the volumes marching cubes reads -- with ``clean`` the cleaned ones: a dropped blob casts no occlusion -- under
+    the same gates."""
     out = out or {}
     n = len(sdfs)
     if opts.clean is not None:  # into a scratch volume: the caller's is never modified
         cc_out = (out["cleaned"], out["clean_stats"]) if "cleaned" in out else None
         sdfs = [c[0] for c in ops.keep_largest_raw_batch(sdfs, opts.level, opts.clean, CLEAN_FILL, gates=gates,
                                                          out=cc_out)]
+    if bits_out is not None:
+        ops.volume_bits_raw_batch(sdfs, opts.level, gates=gates, out=bits_out)
     mc_out = (out["verts"], out["faces"], out["counts"]) if "verts" in out else None
     raws = ops.marching_cubes_raw_batch(sdfs, opts.level, b_min, b_max, max_verts=max_verts, max_faces=max_faces,
                                         gates=gates, out=mc_out)
@@ -629,7 +635,8 @@ def _render_meshes(who, live, cams, res, shade, projection, nearest, background,
     if lighting is not None:
         ops.light_pictures_batch(who, verts, faces, sizes, [ops._f32c(m.normals) for m in live], cams, res, lighting,
                                  [r[0] for r in raws], projection, nearest, background, near, perspective_correct,
-                                 capacity=capacity, shadow=shadow, shades=shades)
+                                 capacity=capacity, shadow=shadow, shades=shades,
+                                 transfers=None if lighting.transfer is None else [m.transfer for m in live])
     return raws
 
 
@@ -718,6 +725,117 @@ def _check_light(who, light):
         raise ValueError("%s: light must be a recon.Light, got %r" % (who, type(light).__name__))
 
 
+class Transfer:
+    """How the radiance transfer of a mesh is traced through its occupancy volume (monoport_amd extension;
+    mp_mesh_transfer in include/monoport_hip.h).  ``directions``: D rays per vertex, a multiple of 64 in 64..512;
+    ``bias``: how far along the normal a ray starts, ``step``: the distance between its samples, ``reach``: None (a ray
+    runs until it leaves the box: J = ceil(sqrt(3) R / step) + 2 samples) or how far it runs (J = ceil(reach / step))
+    -- all three in voxels, turned into world units with the box's smallest voxel edge (``rays``).  Built here in
+    float64 and rounded to f32 once: the spherical Fibonacci directions z_d = 1 - (2 d + 1) / D, phi_d = d pi (3 -
+    sqrt 5), (x, y) = sqrt(1 - z^2) (cos phi, sin phi); the real SH basis at each, in the order of the lighting's H: 1;
+    y, z, x; xy, yz, 3 z^2 - 1, zx, x^2 - y^2 with the exact constants sqrt(1/4pi), sqrt(3/4pi), sqrt(15/4pi),
+    sqrt(5/16pi), sqrt(15/16pi); ``weight`` = f32(4 pi / D).  prt_k is then the quadrature of (cosine lobe * visibility *
+    Y_k) over the sphere: for an unoccluded vertex A_l Y_lm(n) with A = (pi, 2 pi / 3, pi / 4), which times the
+    radiance coefficients is what ``Lighting``'s H(n) . sh gives.  Everything is validated here; a Transfer holds host
+    values only (``tables(device)`` caches the device copies)."""
+
+    def __init__(self, directions=128, bias=1.5, step=1.0, reach=None):
+        who = "Transfer"
+        d = directions
+        if isinstance(d, bool) or not isinstance(d, (int, np.integer)) or d % 64 or not 64 <= d <= ops.TRANSFER_MAX_DIRS:
+            raise ValueError("%s: directions must be a multiple of 64 in 64..%d, got %r"
+                             % (who, ops.TRANSFER_MAX_DIRS, directions))
+        for what, v, ok in (("bias", bias, lambda v: v >= 0), ("step", step, lambda v: v > 0),
+                            ("reach", reach, lambda v: v > 0)):
+            if v is None and what == "reach":
+                continue
+            if (isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating))
+                    or not math.isfinite(float(v)) or not ok(float(v))):
+                raise ValueError("%s: %s must be a finite number %s, got %r"
+                                 % (who, what, ">= 0" if what == "bias" else "> 0", v))
+        self.directions, self.bias, self.step = int(d), float(bias), float(step)
+        self.reach = None if reach is None else float(reach)
+        i = np.arange(self.directions, dtype=np.float64)
+        z = 1.0 - (2.0 * i + 1.0) / self.directions
+        phi = i * math.pi * (3.0 - math.sqrt(5.0))
+        rho = np.sqrt(1.0 - z * z)
+        x, y = rho * np.cos(phi), rho * np.sin(phi)
+        c0, c1 = math.sqrt(1 / (4 * math.pi)), math.sqrt(3 / (4 * math.pi))
+        c2, c20, c22 = math.sqrt(15 / (4 * math.pi)), math.sqrt(5 / (16 * math.pi)), math.sqrt(15 / (16 * math.pi))
+        basis = np.stack([np.full_like(z, c0), c1 * y, c1 * z, c1 * x, c2 * x * y, c2 * y * z, c20 * (3 * z * z - 1),
+                          c2 * z * x, c22 * (x * x - y * y)], axis=1)
+        self.dirs = np.ascontiguousarray(np.stack([x, y, z], axis=1).astype(np.float32))
+        self.basis = np.ascontiguousarray(basis.astype(np.float32))
+        self.weight = float(np.float32(4.0 * math.pi / self.directions))
+        self._tables = {}
+
+    def rays(self, r, b_min, b_max):
+        """(bias_w, step_w, max_steps) at resolution ``r`` in the box: voxels times the smallest voxel edge, as f32."""
+        edge = float(np.min((np.asarray(b_max, np.float64) - np.asarray(b_min, np.float64)).reshape(3))) / r
+        steps = (math.ceil(math.sqrt(3.0) * r / self.step) + 2 if self.reach is None
+                 else math.ceil(self.reach / self.step))
+        return float(np.float32(self.bias * edge)), float(np.float32(self.step * edge)), max(1, int(steps))
+
+    def tables(self, device):
+        """The (dirs [D,3], basis [D,9]) f32 tensors on ``device``, made once per device."""
+        key = str(torch.device(device))
+        if key not in self._tables:
+            self._tables[key] = (torch.from_numpy(self.dirs).to(device), torch.from_numpy(self.basis).to(device))
+        return self._tables[key]
+
+
+class TransferMesh(Mesh):
+    """A ``Mesh`` (the same four fields, so it unpacks, compares and clones as one) that also carries ``.transfer``,
+    the [V,9] radiance transfer of its vertices (``with_transfer``)."""
+    transfer = None
+
+
+def with_transfer(mesh, prt):
+    """``mesh`` with ``prt`` ([V,9] f32, ``mesh_transfer``'s first result) as its ``.transfer``: what a render call with
+    ``Lighting(transfer=...)`` wants of every mesh.  None for ``mesh is None``."""
+    if mesh is None:
+        return None
+    if not torch.is_tensor(prt) or prt.dim() != 2 or tuple(prt.shape) != (mesh.verts.shape[0], 9):
+        raise ValueError("with_transfer: prt must be a [V,9] tensor for the mesh's %d vertices, got %r"
+                         % (mesh.verts.shape[0], None if not torch.is_tensor(prt) else tuple(prt.shape)))
+    out = TransferMesh(*mesh)
+    out.transfer = prt
+    return out
+
+
+@torch.no_grad()
+def volume_bits(sdf, level=0.5):
+    """The occupancy bits of a cubic volume (``ops.volume_bits_raw``): int32 [ops.volume_bits_words(R)] on the device,
+    one bit per voxel set iff v > level, then the tracer's block bits.  No host sync."""
+    return ops.volume_bits_raw(sdf, level)
+
+
+@torch.no_grad()
+def mesh_transfer(mesh, sdf, transfer, level=0.5, b_min=(-1, -1, -1), b_max=(1, 1, 1)):
+    """The radiance transfer of ``mesh``'s vertices, traced through the volume ``sdf`` the mesh was cut from (with
+    ``clean``: the cleaned one) at ``level`` in the box [b_min, b_max], as ``transfer`` (a ``Transfer``) says: (prt
+    [V,9] f32, mask int64 [V, D/64]: bit d & 63 of word d >> 6 is set where direction d faces away from the surface and
+    reaches the box's edge (or the end of its reach) unoccluded).  The mesh needs normals.  No host sync."""
+    who = "mesh_transfer"
+    if not isinstance(transfer, Transfer):
+        raise ValueError("%s: transfer must be a recon.Transfer, got %r" % (who, type(transfer).__name__))
+    if mesh.normals is None:
+        raise ValueError("%s: the rays start along the mesh's normals, and the mesh has none" % who)
+    vol = ops._cubic_volume(sdf, who)
+    r = int(vol.shape[0])
+    bias_w, step_w, steps = transfer.rays(r, b_min, b_max)
+    verts, normals = ops._f32c(mesh.verts), ops._f32c(mesh.normals)
+    counts = _shape_counts([(verts, mesh.faces)])[0]
+    dirs, basis = transfer.tables(verts.device)
+    if verts.shape[0] == 0:  # nothing to trace: nothing is enqueued
+        return (torch.empty((0, 9), dtype=torch.float32, device=verts.device),
+                torch.empty((0, transfer.directions // 64), dtype=torch.int64, device=verts.device))
+    bits = ops.volume_bits_raw(vol, level)
+    mask, prt = ops.mesh_transfer_raw(verts, normals, counts, bits, r, b_min, b_max, dirs, basis, transfer.weight,
+                                      bias_w, step_w, steps)
+    return prt, mask
+
+
 LIGHTING_FRAMES = ("world", "camera")
 
 
@@ -732,11 +850,20 @@ class Lighting:
     ``albedo``: None (the albedo is the picture's own colours: ``shade="colors"`` / ``"netC"``) or a constant (r, g, b)
     "clay" for ``shade="normals"``.  ``self_shadow``: None, or a bias >= 0: the scene's ``Light`` then also shadows the
     subject itself -- its own shadow map looked up at its own surface, nearer by more than the bias -- and the shade
-    takes the direct term away (1 = fully occluded), the SH term stays.  Everything is validated here; a Lighting holds
-    host values only."""
+    takes the direct term away (1 = fully occluded), the SH term stays.  ``transfer``: None, or a ``Transfer``: the SH
+    term is then self-occluded -- the nine basis values at the normal give way to the radiance transfer of each vertex
+    (``mesh_transfer`` + ``with_transfer``: the cosine lobe masked by what the body itself hides, the reference's PRT
+    shaders), interpolated over the picture; every mesh rendered must carry ``.transfer`` and ``frame`` must be
+    "world".  Everything is validated here; a Lighting holds host values only."""
 
-    def __init__(self, sh, direct=None, gamma=1.0, frame="world", albedo=None, self_shadow=None):
+    def __init__(self, sh, direct=None, gamma=1.0, frame="world", albedo=None, self_shadow=None, transfer=None):
         who = "Lighting"
+        if transfer is not None and not isinstance(transfer, Transfer):
+            raise ValueError("%s: transfer must be None or a recon.Transfer, got %r" % (who, type(transfer).__name__))
+        if transfer is not None and frame == "camera":
+            raise ValueError("%s: transfer is traced in the world frame; frame='camera' would need the band rotation "
+                             "of the coefficients, which is not built" % who)
+        self.transfer = transfer
         if direct is not None:
             try:
                 direction, rgb = direct
@@ -784,6 +911,14 @@ def _check_lighting(who, lighting, shade, meshes, scene_light):
     enqueued."""
     _check_lighting_options(who, lighting, shade, not any(m is not None and m.normals is None for m in meshes),
                             scene_light)
+    if lighting.transfer is not None:
+        for m in meshes:
+            if m is None:
+                continue
+            t = getattr(m, "transfer", None)
+            if not torch.is_tensor(t) or t.dim() != 2 or tuple(t.shape) != (m.verts.shape[0], 9):
+                raise ValueError("%s: lighting.transfer needs every mesh's radiance transfer [V,9]: "
+                                 "with_transfer(mesh, mesh_transfer(...)[0])" % who)
 
 
 def _check_lighting_options(who, lighting, shade, has_normals, scene_light):
@@ -799,6 +934,8 @@ def _check_lighting_options(who, lighting, shade, has_normals, scene_light):
                          % (who, shade))
     if not has_normals:
         raise ValueError("%s: lighting needs the mesh's normals, and the mesh has none" % who)
+    if lighting.transfer is not None and lighting.frame == "camera":
+        raise ValueError("%s: lighting.transfer is traced in the world frame; frame='camera' is not built" % who)
     if lighting.self_shadow is not None and scene_light is None:
         raise ValueError("%s: lighting.self_shadow looks the subject up in the shadow map of the scene's light; there "
                          "is no scene light" % who)

@@ -87,6 +87,14 @@ coefficients, a direct term along the sun, evaluated in the camera's frame, with
 
     python tools/mesh_timing.py --lighting [--passes 5] [--out profiles/mesh_lighting_timing.json]
 
+``--transfer`` measures the self-occluded SH term (profiles/mesh_transfer_timing.json): per mesh in a batch of 20 on
+the 257^3 body, the occupancy bits, the radiance transfer and its shade each alone at D = 64, 128 and 256 directions,
+with the samples the definition visits per second and the share of them that lie in empty 8^3 blocks (what the
+tracer may skip); then the ``--lighting`` slots (without the self-shadow, SH in the world frame) without and with
+``transfer=`` at one 257^2 and one 1024^2 view, alternated in one session.
+
+    python tools/mesh_timing.py --transfer [--passes 5] [--out profiles/mesh_transfer_timing.json]
+
 The protocol of tools/recon_views_timing.py: after a warm-up of all, the passes alternate; a pass is `meshes`
 meshes, wall clock around a final stream sync.  Prints (and writes) one JSON line: per way the median, minimum and
 maximum time per mesh (ms) over the passes.  The verdict fields restate what to check: (b) not slower than (a) by
@@ -130,6 +138,7 @@ def main():
     ap.add_argument("--scene", action="store_true", help="slot pictures with and without a textured scene behind them")
     ap.add_argument("--shadow", action="store_true", help="slot pictures over a scene, without and with a light on it")
     ap.add_argument("--lighting", action="store_true", help="the --shadow slots without and with lighting= on the subject")
+    ap.add_argument("--transfer", action="store_true", help="bits, transfer and shade per mesh; lit slots with transfer=")
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "mesh_render_clip_timing.json" if a.render and a.clip else
@@ -138,6 +147,7 @@ def main():
                              "mesh_scene_timing.json" if a.scene else
                              "mesh_shadow_timing.json" if a.shadow else
                              "mesh_lighting_timing.json" if a.lighting else
+                             "mesh_transfer_timing.json" if a.transfer else
                              "mesh_smooth_timing.json" if a.smooth else
                              "mesh_simplify_timing.json" if a.simplify else
                              "keep_largest_timing.json" if a.clean else
@@ -153,6 +163,12 @@ def main():
         return
     if a.lighting:
         write(a, slot_lighting(a))
+        return
+    if a.transfer:
+        out = transfer_kernels(a)
+        if not a.no_slot:
+            out["slot"] = slot_transfer(a)
+        write(a, out)
         return
     mlp = ops.PackedMLP.from_layers(DEV, syn.body_mlp("G", noise=0.05, seed=1), 1)
     fh = ops.pack_features(torch.from_numpy(syn.body_feat(256, 128, 128, 2))[None].to(DEV))
@@ -575,6 +591,122 @@ def slot_lighting(a, frames=20):
         out["lighting_%s_inside_the_spread" % res] = bool(
             lit_row["median_ms"] - plain["median_ms"] <= max(lit_row["max_ms"] - lit_row["min_ms"],
                                                              plain["max_ms"] - plain["min_ms"]))
+    return out
+
+
+def _definition_samples(verts, normals, occ, blocks, t, r, rays):
+    """The samples mp_mesh_transfer's definition visits on one mesh, and those of them in an empty 8^3 block: the same
+    f32 expressions in torch, every sample of every ray (no skipping), a chunk of vertices at a time."""
+    bias_w, step_w, steps = rays
+    dirs = torch.from_numpy(t.dirs).to(DEV)
+    f = torch.float32
+    lo, hi = torch.tensor(BMIN, dtype=f, device=DEV), torch.tensor(BMAX, dtype=f, device=DEV)
+    vox = r / (hi - lo)
+    s2 = (normals * normals).sum(1, keepdim=True)
+    u = torch.where(torch.isfinite(s2) & (s2 > 0), normals / s2.sqrt(), torch.zeros_like(normals))
+    o = ((verts - lo) / (hi - lo)) * r + (bias_w * u) * vox
+    delta = (step_w * dirs) * vox
+    visited = empty = 0
+    for v0 in range(0, verts.shape[0], 16384):
+        oc, uc = o[v0:v0 + 16384], u[v0:v0 + 16384]
+        vi, di = torch.nonzero((uc @ dirs.t()) > 0, as_tuple=True)
+        for j in range(steps):
+            if vi.numel() == 0:
+                break
+            s = oc[vi] + float(j) * delta[di]
+            inside = ((s >= 0) & (s < r)).all(1)
+            vi, di, s = vi[inside], di[inside], s[inside]
+            visited += int(inside.numel())
+            c = s.floor().long()
+            empty += int((~blocks[c[:, 2] >> 3, c[:, 1] >> 3, c[:, 0] >> 3]).sum().item())
+            hit = occ[c[:, 2], c[:, 1], c[:, 0]]
+            vi, di = vi[~hit], di[~hit]
+    return visited, empty
+
+
+def transfer_kernels(a, n=20):
+    """Per mesh in a batch of ``n`` on the 257^3 body: mp_volume_bits, mp_mesh_transfer and mp_mesh_transfer_shade each
+    alone, at D = 64, 128 and 256."""
+    mlp = ops.PackedMLP.from_layers(DEV, syn.body_mlp("G", noise=0.05, seed=1), 1)
+    fh = ops.pack_features(torch.from_numpy(syn.body_feat(256, 128, 128, 2))[None].to(DEV))
+    cal = torch.from_numpy(orc.pifu_calib(*syn.scene_camera(30))).to(DEV)
+    vol, status = ops.recon(mlp, fh, cal, syn.Z_SCALE, BMIN, BMAX, RES)
+    assert int(status[0].item()) == 1
+    r = int(vol.shape[-1])
+    mesh = reconstruct_mesh(vol[None, None], 0.5, BMIN, BMAX, normals="accumulate")
+    nv = int(mesh.verts.shape[0])
+    vols = [vol.clone() for _ in range(n)]
+    verts, normals = [mesh.verts.contiguous().clone() for _ in range(n)], [mesh.normals.contiguous().clone() for _ in range(n)]
+    counts = [torch.tensor([nv, int(mesh.faces.shape[0])], dtype=torch.int32, device=DEV) for _ in range(n)]
+    bits = torch.empty((n, ops.volume_bits_words(r)), dtype=torch.int32, device=DEV)
+    prt = torch.empty((n, nv, 9), dtype=torch.float32, device=DEV)
+    shade = torch.empty((n, nv, 3), dtype=torch.float32, device=DEV)
+    sh = np.random.RandomState(0).uniform(-0.2, 0.4, (9, 3)).astype(np.float32)
+    occ = vol.reshape(r, r, r) > 0.5
+    nb = (r + 7) // 8
+    padded = torch.zeros((nb * 8,) * 3, dtype=torch.bool, device=DEV)
+    padded[:r, :r, :r] = occ
+    blocks = padded.reshape(nb, 8, nb, 8, nb, 8).any(5).any(3).any(1)
+    out = {"resolution": r, "vertices": nv, "meshes_per_call": n, "unit": "ms per mesh", "passes": a.passes,
+           "bias": 1.5, "step": 1.0, "bits_kib_per_frame": round(bits.shape[1] * 4 / 1024, 1),
+           "occupied_blocks_share": round(float(blocks.float().mean().item()), 4),
+           "one_more_reconstruction_ms": 5.75}
+    ways = {"bits": lambda: ops.volume_bits_raw_batch(vols, 0.5, out=bits)}
+    tables = {}
+    for d in (64, 128, 256):
+        t = recon.Transfer(d)
+        rays = t.rays(r, BMIN, BMAX)
+        tables[d] = (t, rays)
+        dirs, basis = t.tables(DEV)
+
+        def trace(dirs=dirs, basis=basis, t=t, rays=rays):
+            ops.mesh_transfer_raw_batch(verts, normals, counts, list(bits), r, BMIN, BMAX, dirs, basis, t.weight, *rays,
+                                        want=(False, True), out=(None, prt))
+        ways["transfer_%d" % d] = trace
+    ways["shade"] = lambda: ops.mesh_transfer_shade_raw_batch(list(prt), counts, sh, out=shade)
+    out.update(alternate(ways, a.passes, n))
+    for d, (t, rays) in tables.items():
+        visited, empty = _definition_samples(verts[0], normals[0], occ, blocks, t, r, rays)
+        row = out["transfer_%d" % d]
+        row["max_steps"] = rays[2]
+        row["definition_samples_per_mesh"] = visited
+        row["definition_samples_per_s"] = round(visited / (row["median_ms"] * 1e-3))
+        row["samples_in_empty_blocks_share"] = round(empty / max(visited, 1), 4)
+        row["costs_more_than_one_reconstruction"] = bool(row["median_ms"] > out["one_more_reconstruction_ms"])
+    return out
+
+
+def slot_transfer(a, frames=20):
+    """The --lighting slots (clay, SH in the world frame, a direct term, no self-shadow) without and with ``transfer=``:
+    per-frame ms of a submission (``pictures()`` included) at one 257^2 and one 1024^2 view."""
+    direction = (0.4, -1.0, 0.3)
+    sun = recon.Light.directional(direction, (-1.5, -0.9, -1.5), (1.5, 1.0, 1.5), res=512, radius=1)
+    floor, cam, mesh, base = _scene_setup(sun)
+    sh = np.random.RandomState(0).uniform(-0.2, 0.4, (9, 3)).astype(np.float32)
+    sh[0] += 0.8
+    kw = dict(direct=(direction, (0.9, 0.85, 0.8)), albedo=(0.8, 0.7, 0.6))
+    rows = []
+    for res in (257, 1024):
+        rows.append(("lighting_%d" % res, mesh, dict(base, res=res, scene=floor), cam,
+                     dict(lighting=recon.Lighting(sh, **kw))))
+        rows.append(("transfer_%d" % res, mesh, dict(base, res=res, scene=floor), cam,
+                     dict(lighting=recon.Lighting(sh, transfer=recon.Transfer(128), **kw))))
+    pipes, fn = _slot_pipes(frames, 1, rows)
+    out = {"frames_per_slot": frames, "unit": "ms per frame", "directions": 128, "bias": 1.5, "step": 1.0,
+           "lighting": "clay albedo, 9 x 3 SH coefficients in the world frame, a direct term along the light, gamma 1",
+           "camera": "perspective, turned -0.35 rad about x (looking down), near 0.3, perspective-correct"}
+    out.update(alternate({name: fn(name) for name in pipes}, a.passes, frames))
+    pictures = {}
+    for name, p_ in pipes.items():
+        pictures[name] = p_.slots[0].pictures()[0].image.clone()
+        p_.close()
+    out["changed_pixels_frame0"] = {}
+    for res in ("257", "1024"):
+        with_t, plain = out["transfer_" + res], out["lighting_" + res]
+        out["changed_pixels_frame0"][res] = int((pictures["transfer_" + res] != pictures["lighting_" + res]).any(-1).sum().item())
+        out["transfer_%s_minus_lighting_ms" % res] = round(with_t["median_ms"] - plain["median_ms"], 4)
+        out["transfer_%s_spread_ms" % res] = round(max(with_t["max_ms"] - with_t["min_ms"],
+                                                       plain["max_ms"] - plain["min_ms"]), 4)
     return out
 
 
