@@ -4,6 +4,7 @@ Every function here enqueues hand-written HIP kernels from libmonoport_hip.so on
 current HIP stream and returns ordinary ``torch.Tensor`` objects that outlive the call -- the
 ownership rule of the reference's stage pipeline (RTL/dataloader.py:1048-1054).
 """
+import collections
 import ctypes
 import math
 import os
@@ -1542,6 +1543,23 @@ def _render_clip(who, projection, near, perspective_correct):
     return near, (_lib.RENDER_PERSPECTIVE_CORRECT if perspective_correct else 0)
 
 
+Raster = collections.namedtuple("Raster", ["res", "projection", "nearest", "background", "near", "perspective_correct"])
+Raster.__doc__ = """How the rasteriser draws whatever it is given, validated by ``raster``: the size (H, W), the
+projection, which depth is in front, what uncovered pixels hold, and the near plane with its interpolation (None and
+False: the unclipped call).  Every pass of one picture -- colours, positions, normals, transfer, the scene -- takes the
+same record."""
+
+
+def raster(who, res, projection="orthogonal", nearest="max", background=1.0, near=None, perspective_correct=False):
+    """The ``Raster`` of a render call's arguments, or the ValueError of the first one it refuses."""
+    res = _render_size(who, res)
+    _projection(projection), _nearest(nearest)
+    if near is not None or perspective_correct:
+        _render_clip(who, projection, near, perspective_correct)
+    return Raster(res, projection, nearest, float(background), None if near is None else float(near),
+                  bool(perspective_correct))
+
+
 def _mesh_render(who, verts, faces, counts, attrs, calibs, res, projection, nearest, channel_major, scale, bias, lo, hi,
                  background, out, capacity=None, near=None, perspective_correct=False):
     """What mesh_render_raw and mesh_render_raw_batch do: per mesh (image [n_views,H,W,3] or None, depth
@@ -1622,6 +1640,16 @@ def _mesh_render(who, verts, faces, counts, attrs, calibs, res, projection, near
                           "mp_mesh_render_clip_batch")
     return [(None if image is None else image[f], None if depth is None else depth[f],
              None if face is None else face[f]) for f in range(n)]
+
+
+def _attr_pass(who, verts, faces, counts, attrs, calibs, ras, out=None, capacity=None, channel_major=False,
+               paint=(1.0, 0.0, -math.inf, math.inf)):
+    """One pass of the rasteriser under the ``Raster`` ``ras``: ``_mesh_render`` of the row-major attributes ``attrs``
+    (None: depth and face ids alone) as they are -- positions, normals, uv, transfer shades.  Only a subject's own shade
+    names another ``paint`` (scale, bias, lo, hi) or ``channel_major`` attributes."""
+    return _mesh_render(who, verts, faces, counts, attrs, calibs, ras.res, ras.projection, ras.nearest, channel_major,
+                        *paint, ras.background, out, capacity=capacity, near=ras.near,
+                        perspective_correct=ras.perspective_correct)
 
 
 def mesh_render_raw(verts, faces, counts, attr, calibs, res, projection="orthogonal", nearest="max",
@@ -1758,12 +1786,11 @@ def picture_paint_batch(values, pixels, counts, n_pixels=None, scale=0.5, bias=0
     return _picture_paint("picture_paint_batch", values, pixels, counts, list(out), scale, bias, lo, hi)
 
 
-def render_netc_batch(who, verts, faces, counts, calibs, res, query, projection="orthogonal", nearest="max",
-                      background=1.0, out=None, lists=None, capacity=None, near=None, perspective_correct=False,
+def render_netc_batch(who, verts, faces, counts, calibs, ras, query, out=None, lists=None, capacity=None,
                       positions_hook=None):
     """Pictures coloured per pixel (deferred shading), no host value in between: (1) the rasteriser with ``attr =
-    verts`` -- a picture of world-space surface positions -- under the pictures' own cameras, projection, ``near`` and
-    ``perspective_correct``; (2) ``picture_points_batch`` over each mesh's views as one flat picture (capacity = its
+    verts`` -- a picture of world-space surface positions -- under the pictures' own cameras and ``Raster`` ``ras``;
+    (2) ``picture_points_batch`` over each mesh's views as one flat picture (capacity = its
     pixels: nothing truncates); (3) ``query(points, counts)``: the caller's counted colour query over all meshes (lists
     of [3,L] points and int32 counts -> list of raw predictions [3,L]), under the calibrations and projections its maps
     were made under, chunked by the caller to the query's frame limits; (4) ``picture_paint_batch`` with (0.5, 0.5,
@@ -1774,9 +1801,7 @@ def render_netc_batch(who, verts, faces, counts, calibs, res, query, projection=
     hold the positions -- what a self-shadow reads (``self_shades``), so that no second position pass is needed."""
     if out is not None and (out[0] is None or out[2] is None):
         raise ValueError("%s: a picture coloured per pixel needs the image and the face ids" % who)
-    raws = _mesh_render(who, verts, faces, counts, list(verts), calibs, res, projection, nearest, False, 1.0, 0.0,
-                        -math.inf, math.inf, background, out, capacity=capacity, near=near,
-                        perspective_correct=perspective_correct)
+    raws = _attr_pass(who, verts, faces, counts, list(verts), calibs, ras, out, capacity)
     images, face_ids = [r[0] for r in raws], [r[2] for r in raws]
     if positions_hook is not None:
         positions_hook(images, face_ids)
@@ -2138,13 +2163,12 @@ def self_shades(who, positions, face_ids, lighting, shadow, out=None):
         lighting.self_shadow, light.radius, light.strength, out=None if out is None else (None, list(out)), who=who)]
 
 
-def light_pictures_batch(who, verts, faces, counts, normals, calibs, res, lighting, images, projection="orthogonal",
-                         nearest="max", background=1.0, near=None, perspective_correct=False, capacity=None, shadow=None,
+def light_pictures_batch(who, verts, faces, counts, normals, calibs, ras, lighting, images, capacity=None, shadow=None,
                          buffers=None, shades=None, transfers=None):
-    """The subjects' pictures ``images`` (per mesh [n_views,H,W,3], as ``_mesh_render`` / ``render_netc_batch`` left
+    """The subjects' pictures ``images`` (per mesh [n_views,H,W,3], as ``_attr_pass`` / ``render_netc_batch`` left
     them) lit in place by ``lighting`` (a ``recon.Lighting``: sh, direct_dir, direct_rgb, gamma, frame, albedo,
     self_shadow), no host value in between: (1) a second pass of the rasteriser with ``attr = normals`` (per mesh
-    [V,3]) under the pictures' own cameras, ``near`` and ``perspective_correct``: the same faces, so the same face
+    [V,3]) under the pictures' own cameras and ``Raster`` ``ras``: the same faces, so the same face
     ids; (2) with ``lighting.self_shadow``: a pass with ``attr = verts`` and ``picture_shadow_batch`` for the shade
     alone, against ``shadow`` = (the scene's ``recon.Light``, map depths, map faces: one shadow map per mesh) with the
     bias ``self_shadow``; (3) ``picture_light_batch``: the images are the albedo and the output, or -- with a constant
@@ -2158,26 +2182,21 @@ def light_pictures_batch(who, verts, faces, counts, normals, calibs, res, lighti
     step (3) is ``picture_light_transfer_batch``.  Returns (per mesh the normal pass's (image, None, face), the shades or
     None)."""
     n = len(verts)
-    out = None if buffers is None else (buffers["normal"], None, buffers["face"])
     cams = _calib_list(calibs, n, who)
-    if out is None:  # fresh: the depth comes with them and is dropped
-        nraws = [(r[0], None, r[2]) for r in _mesh_render(
-            who, verts, faces, counts, normals, cams, res, projection, nearest, False, 1.0, 0.0, -math.inf, math.inf,
-            background, None, capacity=capacity, near=near, perspective_correct=perspective_correct)]
-    else:
-        nraws = _mesh_render(who, verts, faces, counts, normals, cams, res, projection, nearest, False, 1.0, 0.0,
-                             -math.inf, math.inf, background, out, capacity=capacity, near=near,
-                             perspective_correct=perspective_correct)
+    background = ras.background
+
+    def attr_pass(attrs, image, face=None):
+        """(image, None, face or None) per mesh: into the caller's buffers, or fresh (the depth that comes with fresh
+        ones is dropped)."""
+        out = None if buffers is None else (buffers[image], None, None if face is None else buffers[face])
+        return [(r[0], None, r[2]) for r in _attr_pass(who, verts, faces, counts, attrs, cams, ras, out, capacity)]
+
+    nraws = attr_pass(normals, "normal", "face")
     face_ids = [r[2] for r in nraws]
     if lighting.self_shadow is None:
         shades = None
     elif shades is None:
-        pos = _mesh_render(who, verts, faces, counts, list(verts), cams, res, projection, nearest, False, 1.0, 0.0,
-                           -math.inf, math.inf, background, None if buffers is None else (buffers["pos"], None, None),
-                           capacity=capacity, near=near, perspective_correct=perspective_correct)
-        if buffers is None:
-            pos = [(p[0], None, None) for p in pos]
-        shades = self_shades(who, [p[0] for p in pos], face_ids, lighting, shadow,
+        shades = self_shades(who, [p[0] for p in attr_pass(list(verts), "pos")], face_ids, lighting, shadow,
                              None if buffers is None else buffers["shade"][:n])
     nv = nraws[0][0].shape[0]
     direct = None if lighting.direct is None else (lighting.direct_dir, lighting.direct_rgb)
@@ -2194,9 +2213,7 @@ def light_pictures_batch(who, verts, faces, counts, normals, calibs, res, lighti
                     ts[f] = row
         else:
             ts = _mesh_transfer_shade(who, list(transfers), sizes, lighting.sh, buffers["transfer_shade"])
-        araws = _mesh_render(who, verts, faces, counts, ts, cams, res, projection, nearest, False, 1.0, 0.0, -math.inf,
-                             math.inf, background, None if buffers is None else (buffers["ambient"], None, None),
-                             capacity=capacity, near=near, perspective_correct=perspective_correct)
+        araws = attr_pass(ts, "ambient")
         picture_light_transfer_batch([r[0] for r in araws], [r[0] for r in nraws], face_ids,
                                      None if lighting.albedo is not None else list(images), direct, lighting.gamma,
                                      shades, lighting.albedo, background, out=(list(images), None), who=who)
@@ -2411,12 +2428,11 @@ def picture_light_transfer_batch(ambients, normals, face_ids, albedos, direct=No
     return [(None if image is None else image[f], None if shading is None else shading[f]) for f in range(n)]
 
 
-def render_scene_batch(who, scene, calibs, res, projection="orthogonal", nearest="max", near=None,
-                       perspective_correct=False, background=1.0, out=None, uv=None, positions=None):
+def render_scene_batch(who, scene, calibs, ras, out=None, uv=None, positions=None):
     """The textured pictures of ``scene`` (a ``recon.Scene``: verts, faces, counts, attr = (u, v, 0) per vertex, pyramid,
     tex_size, levels, wrap) under one camera set per frame (``calibs``: a list, all of one n_views), no host value in
     between: (1) the rasteriser with the scene's tensors repeated per frame and its uv as the attribute, under the
-    pictures' own camera, ``near`` and ``perspective_correct``, into a UV picture; (2) ``picture_texture_batch`` into
+    pictures' own cameras and ``Raster`` ``ras``, into a UV picture; (2) ``picture_texture_batch`` into
     the image.  Returns what ``_mesh_render`` does: per frame (image [n_views,H,W,3], depth, face).  ``out``: (image,
     depth, face) buffers; ``uv``: the UV pictures' buffers [n,n_views,H,W,3] (scratch of the call).  ``positions``:
     None, or buffers [n,n_views,H,W,3] that a second pass of the rasteriser with ``attr = scene.verts`` fills with the
@@ -2432,16 +2448,12 @@ def render_scene_batch(who, scene, calibs, res, projection="orthogonal", nearest
             raise ValueError("%s: a scene picture has an image, a depth and face ids" % who)
         if uv is None:
             uv = [torch.empty_like(o) for o in out[0]]
-    raws = _mesh_render(who, [scene.verts] * n, [scene.faces] * n, [scene.counts] * n, [scene.attr] * n, list(calibs),
-                        res, projection, nearest, False, 1.0, 0.0, -math.inf, math.inf, background,
-                        None if out is None else (uv, out[1], out[2]), near=near,
-                        perspective_correct=perspective_correct)
+    mesh = ([scene.verts] * n, [scene.faces] * n, [scene.counts] * n)
+    raws = _attr_pass(who, *mesh, [scene.attr] * n, list(calibs), ras, None if out is None else (uv, out[1], out[2]))
     if positions is not None:  # the same faces under the same cameras and flags: the face ids are the UV pass's
-        _mesh_render(who, [scene.verts] * n, [scene.faces] * n, [scene.counts] * n, [scene.verts] * n, list(calibs),
-                     res, projection, nearest, False, 1.0, 0.0, -math.inf, math.inf, background,
-                     (positions, None, None), near=near, perspective_correct=perspective_correct)
-    images =picture_texture_batch([r[0] for r in raws], [r[2] for r in raws], scene.pyramid, scene.tex_size,
-                                   scene.levels, scene.wrap, background=background,
+        _attr_pass(who, *mesh, [scene.verts] * n, list(calibs), ras, (positions, None, None))
+    images = picture_texture_batch([r[0] for r in raws], [r[2] for r in raws], scene.pyramid, scene.tex_size,
+                                   scene.levels, scene.wrap, background=ras.background,
                                    out=None if out is None else out[0], who=who)
     return [(im, r[1], r[2]) for im, r in zip(images, raws)]
 

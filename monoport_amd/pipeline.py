@@ -54,10 +54,18 @@ MESH_BATCH = 1 if _mb == "off" else min(int(_mb) if _mb.isdigit() and int(_mb) >
 MESH_KEYS = ("normals", "level", "colors", "clean", "simplify", "smooth")
 PICTURE_KEYS = ("views", "res", "shade", "projection", "nearest", "near", "perspective_correct", "background", "scene",
                 "composite")
-PictureOptions = collections.namedtuple("PictureOptions", PICTURE_KEYS, defaults=(None, "depth"))
-PictureOptions.__doc__ = """What a slot's free-viewpoint pictures are asked for, validated by ``_picture_options``: the
-cameras per frame, the size (H, W), the arguments of ``recon.render_mesh``, and the ``recon.Scene`` behind the subject
-(None: none) with the ``composite`` mode ("depth" or "over") that puts the subject's picture over it."""
+
+
+class PictureOptions(collections.namedtuple("PictureOptions", PICTURE_KEYS, defaults=(None, "depth"))):
+    """What a slot's free-viewpoint pictures are asked for, validated by ``_picture_options``: the cameras per frame,
+    the size (H, W), the arguments of ``recon.render_mesh``, and the ``recon.Scene`` behind the subject (None: none)
+    with the ``composite`` mode ("depth" or "over") that puts the subject's picture over it."""
+    __slots__ = ()
+
+    @property
+    def raster(self):
+        """The six fields every pass of the rasteriser takes, as the ``ops.Raster`` of the ``recon`` bodies."""
+        return ops.Raster(self.res, self.projection, self.nearest, self.background, self.near, self.perspective_correct)
 
 
 def _mesh_options(mesh, balance, has_netc):
@@ -94,7 +102,9 @@ def _picture_options(pictures, mesh, has_netc=False):
     views = pictures.get("views", 1)
     if isinstance(views, bool) or not isinstance(views, (int, np.integer)) or views < 1:
         raise ValueError("%s: views must be an int >= 1, got %r" % (who, views))
-    res = ops._render_size(who, pictures.get("res", 257))
+    ras = ops.raster(who, pictures.get("res", 257), pictures.get("projection", "orthogonal"),
+                     pictures.get("nearest", "max"), pictures.get("background", 1.0), pictures.get("near"),
+                     pictures.get("perspective_correct", False))
     default = "colors" if mesh.colors else ("normals" if mesh.normals is not None else None)
     shade = pictures.get("shade", default)
     if shade not in SHADES:
@@ -105,10 +115,6 @@ def _picture_options(pictures, mesh, has_netc=False):
         raise ValueError("%s: shade='colors' needs the mesh's colours (mesh colors, hence netC)" % who)
     if shade == "netC" and not has_netc:
         raise ValueError("%s: shade='netC' queries the slot's netC per pixel, and the slot has none" % who)
-    projection, nearest = pictures.get("projection", "orthogonal"), pictures.get("nearest", "max")
-    ops._projection(projection), ops._nearest(nearest)
-    near, correct = pictures.get("near"), bool(pictures.get("perspective_correct", False))
-    ops._render_clip(who, projection, near, correct)
     scene, composite = pictures.get("scene"), pictures.get("composite", "depth")
     if scene is not None:
         from .recon import Scene
@@ -118,8 +124,8 @@ def _picture_options(pictures, mesh, has_netc=False):
             raise ValueError("%s: a scene is composited with the subject's image; shade=None renders none" % who)
     if not isinstance(composite, str) or composite not in ops.COMPOSITE_MODES:
         raise ValueError("%s: composite must be one of %s, got %r" % (who, sorted(ops.COMPOSITE_MODES), composite))
-    return PictureOptions(int(views), res, shade, projection, nearest, None if near is None else float(near), correct,
-                          float(pictures.get("background", 1.0)), scene, composite)
+    return PictureOptions(int(views), ras.res, shade, ras.projection, ras.nearest, ras.near, ras.perspective_correct,
+                          ras.background, scene, composite)
 
 
 class FrameSlot:
@@ -154,43 +160,37 @@ class FrameSlot:
         "colors" or None; default: what the mesh options provide, colours first) and ``projection``, ``nearest``,
         ``near``, ``perspective_correct``, ``background`` as ``recon.render_mesh`` takes them.  It needs ``mesh``.
         ``self.picture_options`` is the validated ``PictureOptions`` (None without pictures).  ``submit`` then takes
-        ``cameras``, the rasteriser (``ops.mesh_render_raw_batch``) runs behind the mesh chain on the slot's stream
-        into the static ``pictures_image`` [batch,views,H,W,3] (None with ``shade=None``), ``pictures_depth`` and
-        ``pictures_face`` [batch,views,H,W], and ``pictures()`` hands the results out.  ``shade="netC"`` colours the
+        ``cameras``, the pictures are rendered behind the mesh chain on the slot's stream, with no host value in
+        between (``_render_pictures``: what is enqueued is written once, in ``recon._subject_pictures`` and
+        ``recon._scene_pictures``, and this docstring only names the buffers), and ``pictures()`` hands the results out:
+        the static ``pictures_image`` [batch,views,H,W,3] (None with ``shade=None``), ``pictures_depth`` and
+        ``pictures_face`` [batch,views,H,W].  ``shade="netC"`` colours the
         pictures per pixel (``recon.render_mesh(shade="netC")``): it needs the slot's ``netC`` but NOT the mesh's
         colours -- with ``mesh={"colors": False}`` the per-vertex colour query is never enqueued, which is the saving --
         and the slot then also owns, per frame of L = views * H * W pixels, the static lists of the covered pixels
         (points [3,L], pixels [L], predictions [3,L], count [2]: 28 bytes per pixel); ``pictures_image`` holds the
         surface positions first and the colours in the end.  ``scene`` (a ``recon.Scene``; default None: nothing is
-        allocated or enqueued for it) puts a textured scene behind the subject: behind the subject's picture the slot
-        renders the scene under the same cameras into static ``scene_uv`` / ``scene_image`` / ``scene_depth`` /
-        ``scene_face`` buffers (``ops.render_scene_batch``) and composites in place into ``pictures_image`` /
-        ``pictures_depth`` (``composite``: "depth", the default, or "over"; ``ops.picture_composite_batch``), filling the
-        static ``pictures_mask`` [batch,views,H,W] uint8 (0 neither, 1 scene, 2 subject), with no host value in
-        between; ``pictures()`` then returns ``recon.ScenePicture``s, the bare scene for an empty frame.  It needs a
-        ``shade``, and runs behind the paint of ``shade="netC"`` as behind any other.  A scene with a ``light``
-        (``recon.Scene(light=recon.Light(...))``; the light belongs to the scene, the option keys do not change) also
-        shows each frame's shadow on it: the slot then owns ``shadow_depth`` / ``shadow_face`` [batch,Hs,Ws] (the
-        frames' shadow maps, rendered from the chain's mesh buffers), ``scene_pos`` (the scene's world-space positions)
-        and ``scene_lit`` (the shadowed scene, which the composite takes; ``scene_image`` stays unshadowed), all filled
-        on the slot's stream.  Without a light none of them exists and nothing more is enqueued.
+        allocated or enqueued for it) puts a textured scene behind the subject (``composite``: "depth", the default,
+        or "over"): static ``scene_uv`` / ``scene_image`` / ``scene_depth`` / ``scene_face`` buffers, the composite in
+        place in ``pictures_image`` / ``pictures_depth``, and ``pictures_mask`` [batch,views,H,W] uint8 (0 neither, 1
+        scene, 2 subject); ``pictures()`` then returns ``recon.ScenePicture``s, the bare scene for an empty frame.  It
+        needs a ``shade``.  A scene with a ``light`` (``recon.Scene(light=recon.Light(...))``; the light belongs to the
+        scene, the option keys do not change) also shows each frame's shadow on it: the slot then owns
+        ``shadow_depth`` / ``shadow_face`` [batch,Hs,Ws] (the frames' shadow maps), ``scene_pos`` (the scene's
+        world-space positions) and ``scene_lit`` (the shadowed scene, which the composite takes; ``scene_image`` stays
+        unshadowed).  Without a light none of them exists and nothing more is enqueued.
 
         ``lighting`` (a ``recon.Lighting``; None, the default: nothing is allocated or enqueued for it, and it is not a
         ``pictures`` key) lights the subject's picture per pixel before the composite, as ``recon.render_mesh(lighting=)``
-        does: the slot then owns ``light_normal`` [batch,views,H,W,3] and ``light_face`` [batch,views,H,W] (a second
-        pass of the rasteriser with the chain's normals as the attribute) and, with ``lighting.self_shadow`` (it needs
-        the scene's light), ``light_shade`` [batch,views,H,W] (the subject's own shade under the frame's shadow map) and
-        ``light_pos`` [batch,views,H,W,3] (the subject's positions; not with ``shade="netC"``, whose position picture
-        is read before it is painted over); all filled on the slot's stream with no host value
-        in between, then ``ops.picture_light_batch`` in place on ``pictures_image``.  It needs pictures with a
-        ``shade``, the mesh's normals, and for ``shade="normals"`` a constant ``lighting.albedo``.  With
-        ``lighting.transfer`` (a ``recon.Transfer``; without it none of this exists) the SH term is self-occluded: the
-        slot also owns ``transfer_bits`` [batch, ops.volume_bits_words(R)] int32 (packed inside the mesh chunk loop from
-        the volume marching cubes reads -- with ``clean`` the cleaned one --, under the frames' gates), ``transfer_prt``
-        [batch,cap_v,9], ``transfer_shade`` [batch,cap_v,3] and ``light_ambient`` [batch,views,H,W,3], and enqueues
-        ``ops.mesh_transfer_raw_batch``, the shade, a third pass of the rasteriser and
-        ``ops.picture_light_transfer_batch``; a frame whose mesh ``meshes()`` made again is traced again through its
-        bits."""
+        does: the slot then owns ``light_normal`` [batch,views,H,W,3] and ``light_face`` [batch,views,H,W] and, with
+        ``lighting.self_shadow`` (it needs the scene's light), ``light_shade`` [batch,views,H,W] and ``light_pos``
+        [batch,views,H,W,3] (not with ``shade="netC"``, whose position picture is read before it is painted over).  It
+        needs pictures with a ``shade``, the mesh's normals, and for ``shade="normals"`` a constant
+        ``lighting.albedo``.  With ``lighting.transfer`` (a ``recon.Transfer``; without it none of this exists) the SH
+        term is self-occluded: the slot also owns ``transfer_bits`` [batch, ops.volume_bits_words(R)] int32 (packed
+        inside the mesh chunk loop from the volume marching cubes reads -- with ``clean`` the cleaned one --, under the
+        frames' gates), ``transfer_prt`` [batch,cap_v,9], ``transfer_shade`` [batch,cap_v,3] and ``light_ambient``
+        [batch,views,H,W,3]; a frame whose mesh ``meshes()`` made again is traced again through its bits."""
         self.views = self._head_views(netG, netC, mesh)  # images per frame; refuses what the slot class does not run
         # the option records are validated before anything is allocated
         self.mesh = None if mesh is None else _mesh_options(mesh, float(balance), netC is not None)
@@ -468,48 +468,39 @@ class FrameSlot:
 
     def _render_pictures(self, n):
         """The pictures of the slot's n frames under their ``views`` cameras each, from the mesh buffers the chain has
-        just filled and its device counts: one set of launches per ops.MAX_FRAMES pictures, no host value in between.
-        A gated-off frame's counts are (0, 0): pure background.  With a ``scene``: its textured picture under the same
-        cameras, and the composite in place, follow on the same stream.  With a light in the scene: the n frames' shadow
-        maps from the same mesh buffers (a gated-off frame's map is uncovered: no shadow), the scene's positions, and
-        the shadow of ``scene_image`` into ``scene_lit``, which the composite then takes; ``scene_image`` stays
-        unshadowed for ``_scene_picture``.  With ``lighting``: the subjects' pictures are lit in place before the
-        composite (``ops.light_pictures_batch`` into the slot's ``light_*`` buffers); its ``self_shadow`` reads the
-        frames' shadow maps, which are then rendered first."""
-        po = self.picture_options
+        just filled and its device counts, into the slot's static buffers: ``recon._shadow_maps`` (with a light in the
+        scene), ``recon._subject_pictures`` and ``recon._scene_pictures`` (with a scene) with ``out=`` the slot's
+        buffers -- what ``recon.render_mesh_many(_in_scene)`` enqueues, in the same order, with no host value in
+        between.  A gated-off frame's counts are (0, 0): pure background, an uncovered shadow map, a picture that keeps
+        its bits under the lighting.  With ``lighting.transfer`` the transfer of the n frames' vertices is traced
+        first, through the bits the mesh chain packed.  The shadowed scene goes to ``scene_lit``; ``scene_image``
+        stays unshadowed for ``_rerun_picture``."""
+        from .recon import _chain_subjects, _scene_pictures, _shadow_maps, _subject_pictures
+        po, chains, cams = self.picture_options, self._mesh_chains[:n], list(self._cameras[:n])
         light = po.scene.light if hasattr(self, "scene_lit") else None
-        maps_first = self.lighting is not None and self.lighting.self_shadow is not None
-        if maps_first:
-            self._shadow_maps(n, light)
-        self._render_subjects(n)
+        out = {"image": None if self.pictures_image is None else self.pictures_image[:n],
+               "depth": self.pictures_depth[:n], "face": self.pictures_face[:n]}
+        if po.shade == "netC":
+            out["lists"] = tuple(self.picture_lists[k][:n] for k in ("points", "pixels", "count"))
+        transfers = None
         if self.lighting is not None:
-            self._light_subjects(n, light)
+            out["light"] = {k: getattr(self, "light_" + k)[:n] for k in ("normal", "face", "pos", "shade", "ambient")
+                            if hasattr(self, "light_" + k)}
+            if self._traces:
+                cap = chains[0].verts.shape[0]  # the chain's capacity: the leading rows of the slot's buffers
+                transfers = self._trace(chains, self.transfer_bits[:n], self.transfer_prt[:n, :cap])
+                out["light"]["transfer_shade"] = self.transfer_shade[:n, :cap]
+        subjects = _chain_subjects(chains, po.shade, transfers)
+        maps = None if light is None else _shadow_maps("FrameSlot", subjects, light,
+                                                       (self.shadow_depth[:n], self.shadow_face[:n]))
+        fronts = _subject_pictures("FrameSlot", subjects, cams, po.raster, po.shade,
+                                   self._picture_colours(n) if po.shade == "netC" else None, self.lighting,
+                                   None if light is None else (light,) + maps, out)
         if po.scene is not None:  # the scene under the same cameras, then the composite in place
-            if light is not None and not maps_first:
-                self._shadow_maps(n, light)
-            backs = ops.render_scene_batch("FrameSlot", po.scene, list(self._cameras[:n]), po.res, po.projection,
-                                           po.nearest, po.near, po.perspective_correct, po.background,
-                                           out=(self.scene_image[:n], self.scene_depth[:n], self.scene_face[:n]),
-                                           uv=self.scene_uv[:n], positions=None if light is None else self.scene_pos[:n])
-            if light is not None:
-                ops.picture_shadow_batch(list(self.scene_image[:n]), list(self.scene_pos[:n]), list(self.scene_face[:n]),
-                                         list(self.shadow_depth[:n]), list(self.shadow_face[:n]), light.calib,
-                                         light.projection, light.nearest, light.bias, light.radius, light.strength,
-                                         out=(list(self.scene_lit[:n]), None), who="FrameSlot")
-                backs = [(lit, back[1], back[2]) for lit, back in zip(self.scene_lit[:n], backs)]
-            fronts = list(zip(self.pictures_image[:n], self.pictures_depth[:n], self.pictures_face[:n]))
-            ops.picture_composite_batch(fronts, backs, po.composite, po.nearest, po.background,
-                                        out=(self.pictures_image[:n], self.pictures_depth[:n], self.pictures_mask[:n]),
-                                        who="FrameSlot")
-
-    def _shadow_maps(self, n, light):
-        """The n frames' shadow maps under the scene's light, from the chain's mesh buffers."""
-        chains = self._mesh_chains[:n]
-        ops.mesh_render_raw_batch([c.verts for c in chains], [c.faces for c in chains],
-                                  [c.counts for c in chains], None, [light.calib] * n, light.res,
-                                  light.projection, light.nearest,
-                                  out=(None, self.shadow_depth[:n].unsqueeze(1), self.shadow_face[:n].unsqueeze(1)),
-                                  near=light.near, perspective_correct=light.near is not None)
+            names = ("scene_image", "scene_depth", "scene_face", "scene_uv", "scene_pos", "scene_lit", "pictures_image",
+                     "pictures_depth", "pictures_mask")
+            _scene_pictures("FrameSlot", po.scene, cams, po.raster, maps, fronts, po.composite,
+                            {k: getattr(self, k)[:n] for k in names if hasattr(self, k)})
 
     def _trace(self, chains, bits, out):
         """The radiance transfer [cap,9] of the chains' vertices through their frames' ``bits`` (``out``: into it)."""
@@ -529,69 +520,14 @@ class FrameSlot:
         from .recon import with_transfer
         return with_transfer(mesh, self._reran_transfer[b][:mesh.verts.shape[0]])
 
-    def _light_subjects(self, n, light):
-        """``lighting`` on the n frames' pictures, in place, from the chain's normals (a gated-off frame's normal pass
-        is uncovered: its picture keeps its bits).  With ``lighting.transfer``: the transfer of the n frames' vertices
-        through the bits the mesh chain packed, then its shade and one more pass of the rasteriser, first."""
-        po, chains = self.picture_options, self._mesh_chains[:n]
-        buffers = {"normal": self.light_normal[:n], "face": self.light_face[:n]}
-        transfers = None
-        if self._traces:
-            cap = chains[0].verts.shape[0]  # the chain's capacity: the leading rows of the slot's buffers
-            transfers = self._trace(chains, self.transfer_bits[:n], self.transfer_prt[:n, :cap])
-            buffers.update(ambient=self.light_ambient[:n], transfer_shade=self.transfer_shade[:n, :cap])
-        shadow = shades = None
-        if self.lighting.self_shadow is not None:
-            shadow = (light, list(self.shadow_depth[:n]), list(self.shadow_face[:n]))
-            if po.shade == "netC":  # made by _render_subjects' hook from the colour query's position picture
-                shades = list(self.light_shade[:n])
-            else:
-                buffers.update(pos=self.light_pos[:n], shade=self.light_shade[:n])
-        ops.light_pictures_batch("FrameSlot", [c.verts for c in chains], [c.faces for c in chains],
-                                 [c.counts for c in chains], [c.normals for c in chains], list(self._cameras[:n]),
-                                 po.res, self.lighting, list(self.pictures_image[:n]), po.projection, po.nearest,
-                                 po.background, po.near, po.perspective_correct, shadow=shadow, buffers=buffers,
-                                 shades=shades, transfers=transfers)
-
-    def _render_subjects(self, n):
-        """The pictures of the n frames' meshes alone, into ``pictures_image`` / ``pictures_depth`` / ``pictures_face``."""
-        po = self.picture_options
-        chains = self._mesh_chains[:n]
-        if po.shade == "netC":  # positions -> covered pixels -> netC at them -> colours, behind the mesh chain
-            lists = self.picture_lists
-            hook = None
-            if self.lighting is not None and self.lighting.self_shadow is not None:
-                def hook(positions, face_ids):  # the self-shadow's shade, while the images hold the positions
-                    ops.self_shades("FrameSlot", positions, face_ids, self.lighting,
-                                    (po.scene.light, list(self.shadow_depth[:n]), list(self.shadow_face[:n])),
-                                    self.light_shade[:n])
-            ops.render_netc_batch("FrameSlot", [c.verts for c in chains], [c.faces for c in chains],
-                                  [c.counts for c in chains], list(self._cameras[:n]), po.res, self._picture_colours(n),
-                                  po.projection, po.nearest, po.background,
-                                  out=(self.pictures_image[:n], self.pictures_depth[:n], self.pictures_face[:n]),
-                                  lists=(lists["points"][:n], lists["pixels"][:n], lists["count"][:n]), near=po.near,
-                                  perspective_correct=po.perspective_correct, positions_hook=hook)
-            return
-        attrs, channel_major, paint = None, False, (1.0, 0.0, -np.inf, np.inf)
-        if po.shade == "normals":  # as main.py:220-225 paints them
-            attrs, paint = [c.normals for c in chains], (0.5, 0.5, 0.0, 1.0)
-        elif po.shade == "colors":  # netC's raw predictions [3,cap]; * 0.5 + 0.5 finishes them (recon._finish_mesh)
-            attrs, channel_major, paint = [c.preds for c in chains], True, (0.5, 0.5, -np.inf, np.inf)
-        out = (None if self.pictures_image is None else self.pictures_image[:n], self.pictures_depth[:n],
-               self.pictures_face[:n])
-        ops.mesh_render_raw_batch([c.verts for c in chains], [c.faces for c in chains], [c.counts for c in chains], attrs,
-                                  list(self._cameras[:n]), po.res, po.projection, po.nearest, channel_major, *paint,
-                                  background=po.background, out=out, near=po.near,
-                                  perspective_correct=po.perspective_correct)
-
     def pictures(self):
         """The pictures of the current submission, to be called after ``wait()`` (it waits if the caller has not): a
         list of ``n_active`` entries, a ``recon.MeshRender`` per frame (image [views,H,W,3] or None, depth and face
         [views,H,W]) or None where ``meshes()`` gives None.  The entries are views of the slot's buffers, valid until
         the next ``submit``.  It goes through ``meshes()`` (its one device-to-host copy): a frame whose mesh
-        overflowed the slot's capacities is rendered again from the re-run mesh by ``recon.render_mesh``, into fresh
+        overflowed the slot's capacities is rendered again from the re-run mesh (``_rerun_picture``), into fresh
         tensors: the bits the slot's own launch would have given at a sufficient capacity, except with
-        ``shade="colors"``, where ``render_mesh`` interpolates the Mesh's finished colours and the slot netC's raw
+        ``shade="colors"``, where the re-run interpolates the Mesh's finished colours and the slot netC's raw
         predictions (the same picture, not the same last bits); with ``shade="netC"`` they are the same bits again,
         because both paths query netC at the same points.  No slot has overflowed 12 r^2 / 24 r^2 so far.  With a
         ``scene`` every entry is a ``recon.ScenePicture`` (image, depth, face, mask) of the subject composited over the
@@ -599,56 +535,45 @@ class FrameSlot:
         slot's own picture of the scene."""
         if self.picture_options is None:
             raise RuntimeError("FrameSlot.pictures(): the slot was made without pictures=...")
-        from .recon import MeshRender, _render_meshes, render_mesh
-        po = self.picture_options
+        from .recon import MeshRender, ScenePicture
         out = []
         for b, mesh in enumerate(self.meshes()):
-            if b in self._reran:
-                mesh = self._with_transfer(b, mesh)
-            if po.scene is not None:
-                out.append(self._scene_picture(b, mesh))
-            elif mesh is None:
-                out.append(None)
-            elif b in self._reran and po.shade == "netC":  # recon.render_mesh(shade="netC") on the slot's own maps
-                out.append(MeshRender(*_render_meshes(
-                    "FrameSlot.pictures", [mesh], [self._cameras[b]], po.res, po.shade, po.projection, po.nearest,
-                    po.background, po.near, po.perspective_correct, self._colour_bindings(b, b + 1), self.view,
-                    self.lighting)[0]))
-            elif b in self._reran and self.lighting is not None:
-                out.append(MeshRender(*_render_meshes(
-                    "FrameSlot.pictures", [mesh], [self._cameras[b]], po.res, po.shade, po.projection, po.nearest,
-                    po.background, po.near, po.perspective_correct, lighting=self.lighting)[0]))
-            elif b in self._reran:
-                out.append(render_mesh(mesh, self._cameras[b], po.res, po.shade, po.projection, po.nearest,
-                                       po.background, po.near, po.perspective_correct))
+            if mesh is not None and b in self._reran:
+                out.append(self._rerun_picture(b, self._with_transfer(b, mesh)))
+            elif self.picture_options.scene is not None:
+                out.append(ScenePicture(self.pictures_image[b], self.pictures_depth[b], self.pictures_face[b],
+                                        self.pictures_mask[b]))
             else:
-                out.append(MeshRender(None if self.pictures_image is None else self.pictures_image[b],
-                                      self.pictures_depth[b], self.pictures_face[b]))
+                out.append(None if mesh is None else MeshRender(
+                    None if self.pictures_image is None else self.pictures_image[b], self.pictures_depth[b],
+                    self.pictures_face[b]))
         return out
 
-    def _scene_picture(self, b, mesh):
-        """Frame b's ``recon.ScenePicture``: views of the slot's buffers, or -- for a frame whose mesh ``meshes()`` made
-        again -- the re-rendered subject composited over the slot's own picture of the scene, into fresh tensors."""
-        from .recon import ScenePicture, _render_meshes, composite
-        po = self.picture_options
-        if mesh is None or b not in self._reran:
-            return ScenePicture(self.pictures_image[b], self.pictures_depth[b], self.pictures_face[b],
-                                self.pictures_mask[b])
-        bindings = self._colour_bindings(b, b + 1) if po.shade == "netC" else None
-        maps = None
-        if hasattr(self, "scene_lit"):  # the re-run mesh's own shadow map
-            from .recon import shade_shadow, shadow_map
-            light = po.scene.light
-            maps = shadow_map([mesh], light)
-        self_shadow = self.lighting is not None and self.lighting.self_shadow is not None
-        front = _render_meshes("FrameSlot.pictures", [mesh], [self._cameras[b]], po.res, po.shade, po.projection,
-                               po.nearest, po.background, po.near, po.perspective_correct, bindings, self.view,
-                               self.lighting, (light, maps) if self_shadow else None)[0]
-        back = self.scene_image[b]
-        if maps is not None:  # the shadow anew, from that map, on the unshadowed picture
-            back = shade_shadow((back, self.scene_depth[b], self.scene_face[b]), self.scene_pos[b], maps[0], light)[0]
-        return composite(front, (back, self.scene_depth[b], self.scene_face[b]), po.composite,
-                         po.nearest, po.background)
+    def _rerun_picture(self, b, mesh):
+        """Frame b again from its re-run ``Mesh``, into fresh tensors: the bodies of ``_render_pictures`` on the
+        subjects of ``[mesh]`` with ``out=None`` -- netC bound to the slot's own maps, the shadow map made afresh for
+        this mesh, and the slot's own unshadowed picture of the scene (and its positions) as the back picture."""
+        from .recon import (MeshRender, ScenePicture, _counted_colours, _mesh_subjects, _scene_pictures, _shadow_maps,
+                            _subject_pictures)
+        po, who, cams = self.picture_options, "FrameSlot.pictures", [self._cameras[b]]
+        subjects = _mesh_subjects(who, [mesh], po.shade, self.lighting)
+        colours = None
+        if po.shade == "netC":  # recon.render_mesh(shade="netC") on the slot's own maps
+            bindings = self._colour_bindings(b, b + 1)
+
+            def colours(pts, counts):
+                return _counted_colours(bindings, pts, counts, view=self.view)
+        light = po.scene.light if hasattr(self, "scene_lit") else None
+        maps = None if light is None else _shadow_maps(who, subjects, light)
+        front = _subject_pictures(who, subjects, cams, po.raster, po.shade, colours, self.lighting,
+                                  None if light is None else (light,) + maps)[0]
+        if po.scene is None:
+            return MeshRender(*front)
+        back = ([self.scene_image[b]], [self.scene_depth[b]], [self.scene_face[b]],
+                None if light is None else [self.scene_pos[b]])
+        image, depth, mask = _scene_pictures(who, po.scene, cams, po.raster, maps, [front], po.composite,
+                                             back=back)[1][0]
+        return ScenePicture(image, depth, front[2], mask)
 
     def _slot_cameras(self, cameras, n):
         """``submit``'s cameras ([n,views,>=3,4], or [views,>=3,4] / [>=3,4] shared by all frames; tensor or array)

@@ -474,17 +474,47 @@ nothing is seen), face [H,W] int32 (-1 where nothing is seen); with a set of cam
 SHADES = ("colors", "normals", "netC", None)
 
 
-def _shade_attr(who, mesh, shade):
-    """The per-vertex values a ``shade`` paints and their (scale, bias, lo, hi): finished colours as they are, normals
-    as main.py:220-225 paints them.  "netC" paints no per-vertex value: the picture is coloured per pixel."""
+_Subjects = collections.namedtuple("_Subjects", ["verts", "faces", "counts", "capacity", "attrs", "channel_major",
+                                                 "paint", "normals", "transfers"],
+                                   defaults=(None, None, False, (1.0, 0.0, -np.inf, np.inf), None, None))
+_Subjects.__doc__ = """What a set of pictures is of, one list entry per subject: verts, faces and the device counts;
+``capacity`` (max_v, max_f) where the subjects' tensors are cut to their own sizes, None where all share one capacity;
+the per-vertex values ``attrs`` that the shade paints (None: ``shade`` None or "netC") with their layout and their
+(scale, bias, lo, hi); the normals (None where no lighting reads them) and, for a ``Lighting.transfer``, the radiance
+transfers."""
+NORMALS_PAINT = (0.5, 0.5, 0.0, 1.0)  # as main.py:220-225 paints them
+
+
+def _mesh_subjects(who, meshes, shade=None, lighting=None):
+    """The ``_Subjects`` of live ``Mesh``es (no None): counts from the tensors' shapes, the capacity of the call the
+    largest of them, finished colours painted as they are."""
     if shade not in SHADES:
         raise ValueError("%s: shade must be one of %s, got %r" % (who, list(SHADES), shade))
-    if shade is None or shade == "netC":
-        return None, (1.0, 0.0, -np.inf, np.inf)
-    attr = mesh.colors if shade == "colors" else mesh.normals
-    if attr is None:
-        raise ValueError("%s: shade=%r, but the mesh has no %s" % (who, shade, shade))
-    return attr, ((1.0, 0.0, -np.inf, np.inf) if shade == "colors" else (0.5, 0.5, 0.0, 1.0))
+    s = _Subjects([m.verts.contiguous() for m in meshes], [m.faces.contiguous() for m in meshes], None)
+    s = s._replace(counts=list(_shape_counts(list(zip(s.verts, s.faces))).unbind(0)),
+                   capacity=(max(v.shape[0] for v in s.verts), max(f.shape[0] for f in s.faces)))
+    if shade in ("colors", "normals"):
+        attrs = [m.colors if shade == "colors" else m.normals for m in meshes]
+        if any(a is None for a in attrs):
+            raise ValueError("%s: shade=%r, but the mesh has no %s" % (who, shade, shade))
+        s = s._replace(attrs=[ops._f32c(a) for a in attrs], paint=NORMALS_PAINT if shade == "normals" else s.paint)
+    if lighting is not None:
+        s = s._replace(normals=[ops._f32c(m.normals) for m in meshes],
+                       transfers=None if lighting.transfer is None else [m.transfer for m in meshes])
+    return s
+
+
+def _chain_subjects(chains, shade, transfers=None):
+    """The ``_Subjects`` of ``MeshChain``s (a slot's): the chains' own device counts, one capacity; ``shade="colors"``
+    paints netC's raw predictions [3,cap] channel-major, * 0.5 + 0.5 behind the interpolation (``_finish_mesh``'s
+    factors), which costs no transposing launch -- and is why the capacity may not be cut."""
+    s = _Subjects([c.verts for c in chains], [c.faces for c in chains], [c.counts for c in chains],
+                  normals=[c.normals for c in chains], transfers=transfers)
+    if shade == "normals":
+        return s._replace(attrs=s.normals, paint=NORMALS_PAINT)
+    if shade == "colors":
+        return s._replace(attrs=[c.preds for c in chains], channel_major=True, paint=(0.5, 0.5, -np.inf, np.inf))
+    return s
 
 
 def _check_shade_netC(who, shade, netC, view):
@@ -554,20 +584,26 @@ def render_mesh_many(meshes, calibs, res=257, shade="colors", projection="orthog
     launch per ops.MAX_FRAMES meshes (``ops.max_view_frames(V)`` with ``view``).  ``lighting``: as in ``render_mesh``,
     one for all meshes; the normal pass and the lighting are one set of launches per ops.MAX_FRAMES pictures more.  No
     host sync."""
-    return _render_mesh_many("render_mesh_many", meshes, calibs, res, shade, projection, nearest, background, near,
-                             perspective_correct, netC, feat_tensors_C, calib_tensors, view, lighting, None)
+    ras = ops.raster("render_mesh_many", res, projection, nearest, background, near, perspective_correct)
+    raws, cams, _ = _render_mesh_many("render_mesh_many", meshes, calibs, ras, shade, netC, feat_tensors_C,
+                                      calib_tensors, view, lighting)
+    return [None if raw is None else MeshRender(*_squeezed(raw, cam)) for raw, cam in zip(raws, cams)]
 
 
-def _render_mesh_many(who, meshes, calibs, res, shade, projection, nearest, background, near, perspective_correct, netC,
-                      feat_tensors_C, calib_tensors, view, lighting, shadow):
-    """``render_mesh_many``; ``shadow``: None, or (the scene's Light, one shadow map per entry of ``meshes``) for the
-    lighting's ``self_shadow``."""
+def _squeezed(tensors, cam):
+    """A picture's tensors [n_views, ...] as the caller of one [4,4] / [3,4] camera gets them: without the leading 1."""
+    return tuple(None if t is None else t[0] for t in tensors) if _single_camera(cam) else tensors
+
+
+def _render_mesh_many(who, meshes, calibs, ras, shade, netC, feat_tensors_C, calib_tensors, view, lighting, light=None):
+    """``render_mesh_many`` under the ``ops.Raster`` ``ras`` -> (per mesh the raw picture (image, depth, face; each
+    [n_views, ...]) or None, per mesh its camera set, the shadow maps).  ``light``: None, or the scene's ``Light``: the
+    live meshes' shadow maps under it are rendered first (``_shadow_maps``), for the lighting's ``self_shadow`` and for
+    the caller's scene, and returned as (depths, faces), one entry per mesh, an uncovered map for a None."""
     _check_shade_netC(who, shade, netC, view)
     meshes = list(meshes)
     if lighting is not None:
-        _check_lighting(who, lighting, shade, meshes, None if shadow is None else shadow[0])
-    if near is not None or perspective_correct:  # refused before a list of Nones returns
-        ops._render_clip(who, projection, near, perspective_correct)
+        _check_lighting(who, lighting, shade, meshes, light)
     if netC is not None:
         if feat_tensors_C is None or calib_tensors is None:
             raise ValueError("%s: netC needs feat_tensors_C and calib_tensors" % who)
@@ -575,68 +611,64 @@ def _render_mesh_many(who, meshes, calibs, res, shade, projection, nearest, back
             raise ValueError("%s: %d meshes, %d feature sets, %d calibrations"
                              % (who, len(meshes), len(feat_tensors_C), len(calib_tensors)))
     idx = [i for i, m in enumerate(meshes) if m is not None]
-    out = [None] * len(meshes)
+    raws = [None] * len(meshes)
     if not idx:
-        return out
-    if isinstance(calibs, (list, tuple)):
-        if len(calibs) != len(meshes):
-            raise ValueError("%s: %d meshes, %d camera sets" % (who, len(meshes), len(calibs)))
-        cams = [calibs[i] for i in idx]
-    else:
-        cams = [calibs] * len(idx)
-    bindings = None
+        return raws, list(raws), None
+    cams = _camera_sets(who, calibs, len(meshes), "meshes")
+    colours = None
     if netC is not None:
         bindings = _bind_netC(who, netC, [(feat_tensors_C[i], calib_tensors[i], meshes[i].verts.device) for i in idx],
                               view)
+
+        def colours(pts, counts):
+            return _counted_colours(bindings, pts, counts, view=view or 0)
+    subjects = _mesh_subjects(who, [meshes[i] for i in idx], shade, lighting)
+    maps = shadow = None
+    if light is not None:  # a None mesh casts no shadow
+        shadow = (light,) + _shadow_maps(who, subjects, light)
+        maps = tuple([hole] * len(meshes) for hole in _uncovered_map(light, subjects.verts[0].device))
+        for k, i in enumerate(idx):
+            maps[0][i], maps[1][i] = shadow[1][k], shadow[2][k]
+    live = _subject_pictures(who, subjects, [cams[i] for i in idx], ras, shade, colours, lighting, shadow)
+    for i, raw in zip(idx, live):
+        raws[i] = raw
+    return raws, cams, maps
+
+
+def _subject_pictures(who, subjects, cams, ras, shade, colours=None, lighting=None, shadow=None, out=None):
+    """THE picture of a set of subjects, for the render calls, a slot and a slot's re-run alike: per subject the raw
+    (image, depth, face; each [n_views, ...]) of ``subjects`` (a ``_Subjects``) under one camera set each and the
+    ``ops.Raster`` ``ras``.  (1) ``shade="netC"``: ``ops.render_netc_batch`` -- positions, covered pixels, ``colours``
+    (the counted query ``(points, counts) -> predictions``: ``_counted_colours`` over bindings, or a slot's
+    ``_picture_colours``), paint -- with the self-shadow's shade made from the position picture before the paint
+    covers it; any other shade: one pass with the subjects' attributes and paint.  (2) ``lighting`` (checked by the
+    caller): ``ops.light_pictures_batch`` in place on the images.  ``shadow``: (the scene's ``Light``, map depths, map
+    faces) as ``_shadow_maps`` gives them, read only by a ``lighting.self_shadow``.  ``out``: None (fresh tensors), or
+    a dict of the caller's buffers, each [n, ...]: ``image`` (None with ``shade=None``), ``depth``, ``face``; for
+    ``shade="netC"`` ``lists`` = (points, pixels, count) as ``ops.render_netc_batch`` takes them; for the lighting
+    ``light``, the ``buffers`` dict of ``ops.light_pictures_batch``.  A new picture stage is one block here."""
+    s, out = subjects, out or {}
+    pics = (out["image"], out["depth"], out["face"]) if "depth" in out else None
+    buffers = out.get("light")
     if lighting is None or lighting.self_shadow is None:
         shadow = None
-    else:
-        shadow = (shadow[0], [shadow[1][i] for i in idx])
-    raws = _render_meshes(who, [meshes[i] for i in idx], cams, res, shade, projection, nearest, background, near,
-                          perspective_correct, bindings, view or 0, lighting, shadow)
-    for i, cam, (image, depth, face) in zip(idx, cams, raws):
-        if _single_camera(cam):
-            image, depth, face = (None if t is None else t[0] for t in (image, depth, face))
-        out[i] = MeshRender(image, depth, face)
-    return out
-
-
-def _render_meshes(who, live, cams, res, shade, projection, nearest, background, near, perspective_correct,
-                   bindings=None, view=0, lighting=None, shadow=None):
-    """The raw pictures (image, depth, face; each [n_views, ...]) of the meshes ``live`` (no None) under one camera set
-    each.  ``shade="netC"``: ``bindings``, one query binding of netC per mesh (``_bind_netC``; a slot passes those on
-    its own maps), colour the pictures per pixel through ``ops.render_netc_batch``.  ``lighting`` (checked by the
-    caller): the images are then lit in place (``ops.light_pictures_batch``); ``shadow``: for its ``self_shadow``, (the
-    scene's Light, the shadow maps of ``live`` as ``shadow_map`` gives them)."""
-    shaded = [_shade_attr(who, m, shade) for m in live]
-    scale, bias, lo, hi = shaded[0][1]
-    verts = [m.verts.contiguous() for m in live]
-    faces = [m.faces.contiguous() for m in live]
-    sizes = list(_shape_counts(list(zip(verts, faces))).unbind(0))
-    capacity = (max(v.shape[0] for v in verts), max(f.shape[0] for f in faces))
-    if lighting is not None and shadow is not None:
-        shadow = (shadow[0], [m[0] for m in shadow[1]], [m[1] for m in shadow[1]])
     shades = None
     if shade == "netC":
         hook = None
-        if lighting is not None and lighting.self_shadow is not None:  # the positions are there before the paint
+        if shadow is not None:  # the positions are there before the paint
             def hook(positions, face_ids):
                 nonlocal shades
-                shades = ops.self_shades(who, positions, face_ids, lighting, shadow)
-        raws = ops.render_netc_batch(who, verts, faces, sizes, cams, res,
-                                     lambda pts, counts: _counted_colours(bindings, pts, counts, view=view),
-                                     projection, nearest, background, capacity=capacity, near=near,
-                                     perspective_correct=perspective_correct, positions_hook=hook)
+                shades = ops.self_shades(who, positions, face_ids, lighting, shadow,
+                                         None if buffers is None else buffers["shade"])
+        raws = ops.render_netc_batch(who, s.verts, s.faces, s.counts, cams, ras, colours, out=pics,
+                                     lists=out.get("lists"), capacity=s.capacity, positions_hook=hook)
     else:
-        attrs = None if shade is None else [ops._f32c(a) for a, _ in shaded]
-        raws = ops._mesh_render(who, verts, faces, sizes, attrs, cams, res, projection, nearest, False, scale, bias, lo,
-                                hi, background, None, capacity=capacity, near=near,
-                                perspective_correct=perspective_correct)
+        raws = ops._attr_pass(who, s.verts, s.faces, s.counts, s.attrs, cams, ras, pics, s.capacity, s.channel_major,
+                              s.paint)
     if lighting is not None:
-        ops.light_pictures_batch(who, verts, faces, sizes, [ops._f32c(m.normals) for m in live], cams, res, lighting,
-                                 [r[0] for r in raws], projection, nearest, background, near, perspective_correct,
-                                 capacity=capacity, shadow=shadow, shades=shades,
-                                 transfers=None if lighting.transfer is None else [m.transfer for m in live])
+        ops.light_pictures_batch(who, s.verts, s.faces, s.counts, s.normals, cams, ras, lighting, [r[0] for r in raws],
+                                 capacity=s.capacity, shadow=shadow, buffers=buffers, shades=shades,
+                                 transfers=s.transfers)
     return raws
 
 
@@ -1000,10 +1032,10 @@ def _check_scene(who, scene):
         raise ValueError("%s: scene must be a recon.Scene, got %r" % (who, type(scene).__name__))
 
 
-def _camera_sets(who, calibs, n):
+def _camera_sets(who, calibs, n, what="pictures"):
     if isinstance(calibs, (list, tuple)):
         if len(calibs) != n:
-            raise ValueError("%s: %d pictures, %d camera sets" % (who, n, len(calibs)))
+            raise ValueError("%s: %d %s, %d camera sets" % (who, n, what, len(calibs)))
         return list(calibs)
     return [calibs] * n
 
@@ -1021,18 +1053,28 @@ def shadow_map(meshes, light, device=None):
     idx = [i for i, m in enumerate(meshes) if m is not None]
     if device is None:
         device = meshes[idx[0]].verts.device if idx else "cuda"
-    hs, ws = light.res
     out = [None] * len(meshes)
     if idx:
-        raws = _render_meshes(who, [meshes[i] for i in idx], [light.calib] * len(idx), light.res, None,
-                              light.projection, light.nearest, 1.0, light.near, light.near is not None)
-        for i, (_, depth, face) in zip(idx, raws):
-            out[i] = (depth[0], face[0])
-    for i, m in enumerate(meshes):
-        if m is None:
-            out[i] = (torch.zeros((hs, ws), dtype=torch.float32, device=device),
-                      torch.full((hs, ws), -1, dtype=torch.int32, device=device))
-    return out
+        for i, depth, face in zip(idx, *_shadow_maps(who, _mesh_subjects(who, [meshes[i] for i in idx]), light)):
+            out[i] = (depth, face)
+    return [_uncovered_map(light, device) if m is None else m for m in out]
+
+
+def _uncovered_map(light, device):
+    """The (depth, face) shadow map of no caster at all: it shadows nothing."""
+    return (torch.zeros(light.res, dtype=torch.float32, device=device),
+            torch.full(light.res, -1, dtype=torch.int32, device=device))
+
+
+def _shadow_maps(who, subjects, light, out=None):
+    """The shadow maps of ``subjects`` (a ``_Subjects``) under ``light`` -> (depths, faces), per subject a [Hs,Ws]: one
+    pass of the rasteriser under the light's camera without an image, clipped and perspective-correct where the light
+    has a ``near``.  ``out``: None, or the caller's (depth [n,Hs,Ws], face [n,Hs,Ws])."""
+    s, n = subjects, len(subjects.verts)
+    ras = ops.raster(who, light.res, light.projection, light.nearest, 1.0, light.near, light.near is not None)
+    raws = ops._attr_pass(who, s.verts, s.faces, s.counts, None, [light.calib] * n, ras,
+                          None if out is None else (None, out[0].unsqueeze(1), out[1].unsqueeze(1)), s.capacity)
+    return [r[1][0] for r in raws], [r[2][0] for r in raws]
 
 
 @torch.no_grad()
@@ -1080,27 +1122,43 @@ def light_picture(picture, normals, lighting, calibs=None, visibility=None):
                                    lighting.albedo, nv, with_shading=True, who=who)[0]
 
 
-def _scene_pictures(who, scene, casters, cams, res, projection, nearest, near, perspective_correct, background,
-                    maps=None):
-    """Per camera set the raw picture (image, depth, face; each [n_views, ...]) of ``scene``.  With ``scene.light`` and
-    any caster (``casters``: None, or one Mesh or None per camera set): the shadow maps of the casters (``maps``: those,
-    where the caller has made them), the scene's UV and position pictures, the texture lookup, and the shadow in place
-    on the scene's image.  Else exactly ``ops.render_scene_batch``."""
-    light = scene.light
-    if light is None or casters is None or all(m is None for m in casters):
-        return ops.render_scene_batch(who, scene, cams, res, projection, nearest, near, perspective_correct, background)
-    if maps is None:
-        maps = shadow_map(casters, light, device=scene.verts.device)
-    nv = ops._view_calibs(who, cams[0]).shape[0]
-    h, w = ops._render_size(who, res)
-    positions = torch.empty((len(cams), nv, h, w, 3), dtype=torch.float32, device=scene.verts.device).unbind(0)
-    backs = ops.render_scene_batch(who, scene, cams, res, projection, nearest, near, perspective_correct, background,
-                                   positions=positions)
-    images = [b[0] for b in backs]
-    ops.picture_shadow_batch(images, positions, [b[2] for b in backs], [m[0] for m in maps], [m[1] for m in maps],
-                             light.calib, light.projection, light.nearest, light.bias, light.radius, light.strength,
-                             out=(images, None), who=who)
-    return backs
+def _scene_pictures(who, scene, cams, ras, maps=None, fronts=None, composite="depth", out=None, back=None):
+    """THE scene behind a set of pictures, for the render calls, a slot and a slot's re-run alike -> (per camera set the
+    raw picture (image, depth, face; each [n_views, ...]) of ``scene`` under the ``ops.Raster`` ``ras``, per camera set
+    the composite (image, depth, mask) or None).  (1) ``ops.render_scene_batch``, with the scene's positions where
+    there is a shadow to cast -- or ``back`` = (images, depths, faces, positions), the caller's own pictures of the
+    scene, which are then only read; (2) ``maps`` (None: no light, or no caster) = the (depths, faces) of
+    ``_shadow_maps``, one per camera set: ``ops.picture_shadow_batch`` with ``scene.light`` on the scene's image;
+    (3) ``fronts`` (None: the scene alone): per camera set the subject's raw picture, put over the scene by
+    ``ops.picture_composite_batch`` in the mode ``composite``.  ``out``: None (fresh tensors; the shadow falls on the
+    scene's image in place), or a dict of the caller's buffers, each [n, ...]: ``scene_image``, ``scene_depth``,
+    ``scene_face``, ``scene_uv``, with ``maps`` ``scene_pos`` and ``scene_lit`` -- a separate lit image, which the
+    composite then takes while ``scene_image`` stays unshadowed --, with ``fronts`` ``pictures_image``,
+    ``pictures_depth`` (they may be the fronts' own: the composite in place) and ``pictures_mask``."""
+    out = out or {}
+    if back is None:
+        positions = None
+        if maps is not None:
+            positions = out.get("scene_pos")
+            if positions is None:
+                nv = ops._view_calibs(who, cams[0]).shape[0]
+                positions = torch.empty((len(cams), nv) + ras.res + (3,), dtype=torch.float32,
+                                        device=scene.verts.device).unbind(0)
+        pics = (out["scene_image"], out["scene_depth"], out["scene_face"]) if "scene_image" in out else None
+        backs = ops.render_scene_batch(who, scene, cams, ras, out=pics, uv=out.get("scene_uv"), positions=positions)
+        lit = out.get("scene_lit", [b[0] for b in backs])
+    else:
+        backs, positions, lit = list(zip(*back[:3])), back[3], None
+    if maps is not None:
+        light = scene.light
+        lit = ops.picture_shadow_batch([b[0] for b in backs], list(positions), [b[2] for b in backs], maps[0], maps[1],
+                                       light.calib, light.projection, light.nearest, light.bias, light.radius,
+                                       light.strength, out=None if lit is None else (list(lit), None), who=who)
+        backs = [(shadowed[0], b[1], b[2]) for shadowed, b in zip(lit, backs)]
+    if fronts is None:
+        return backs, None
+    pics = (out["pictures_image"], out["pictures_depth"], out["pictures_mask"]) if "pictures_mask" in out else None
+    return backs, ops.picture_composite_batch(fronts, backs, composite, ras.nearest, ras.background, out=pics, who=who)
 
 
 @torch.no_grad()
@@ -1113,12 +1171,13 @@ def render_scene(scene, calibs, res=257, projection="orthogonal", nearest="max",
     that still projects beyond its 2^22 snap guard is dropped whole (``near`` far below 0.05 with a 3 m floor at
     1024^2); the side planes are not clipped.  ``casters``: None, or the ``Mesh`` whose shadow falls on the scene under
     ``scene.light`` (ignored without a light): the picture is then the shadowed one."""
-    _check_scene("render_scene", scene)
-    image, depth, face = _scene_pictures("render_scene", scene, None if casters is None else [casters], [calibs], res,
-                                         projection, nearest, near, perspective_correct, background)[0]
-    if _single_camera(calibs):
-        image, depth, face = image[0], depth[0], face[0]
-    return MeshRender(image, depth, face)
+    who = "render_scene"
+    _check_scene(who, scene)
+    ras = ops.raster(who, res, projection, nearest, background, near, perspective_correct)
+    maps = None
+    if scene.light is not None and casters is not None:
+        maps = tuple(zip(*shadow_map([casters], scene.light, device=scene.verts.device)))
+    return MeshRender(*_squeezed(_scene_pictures(who, scene, [calibs], ras, maps)[0][0], calibs))
 
 
 @torch.no_grad()
@@ -1140,13 +1199,12 @@ def render_mesh_many_in_scene(meshes, scene, calibs, res=257, shade="colors", pr
     (``calibs``: one camera set for all, or a list with one per mesh), ``composite``: "depth" or "over".  Returns a
     list of ``ScenePicture``s; a ``None`` mesh gives the bare scene (mask in {0, 1}, face -1).  ``shade`` may not be
     None: the composite is of images.  Two more launches per ops.MAX_FRAMES pictures than the two renders; no host
-    sync.  With ``scene.light`` every mesh also casts its shadow on its own picture of the scene before the composite:
-    its shadow map under the light, a position pass of the scene and ``ops.picture_shadow_batch``; without a light
-    nothing more is enqueued than before.  ``lighting`` (a ``Lighting``; None: nothing more is enqueued) lights the
-    subject's image as in ``render_mesh``, before the composite; the scene keeps its texture and its shadow.  With
-    ``lighting.self_shadow`` (it needs ``scene.light``) the subject is also looked up in its own shadow map, with that
-    bias: a position pass of the subject and ``ops.picture_shadow_batch`` for the shade alone, which takes the direct
-    term away where it is 1; with ``shade="netC"`` the position picture of the colour query is the one it reads."""
+    sync.  With ``scene.light`` every mesh also casts its shadow on its own picture of the scene before the composite;
+    without a light nothing more is enqueued than before.  ``lighting`` (a ``Lighting``; None: nothing more is
+    enqueued) lights the subject's image as in ``render_mesh``, before the composite; the scene keeps its texture and
+    its shadow.  With ``lighting.self_shadow`` (it needs ``scene.light``) the subject is also looked up in its own
+    shadow map, with that bias, which takes the direct term away where the shade is 1.  What is enqueued, and in which
+    order: ``_shadow_maps``, ``_subject_pictures``, ``_scene_pictures``."""
     who = "render_mesh_many_in_scene"
     _check_scene(who, scene)
     if shade is None:
@@ -1158,30 +1216,19 @@ def render_mesh_many_in_scene(meshes, scene, calibs, res=257, shade="colors", pr
     if not meshes:
         return []
     cams = _camera_sets(who, calibs, len(meshes))
-    maps = None
-    if lighting is not None and lighting.self_shadow is not None and any(m is not None for m in meshes):
-        maps = shadow_map(meshes, scene.light, device=scene.verts.device)  # one set for the subject and the scene
-    fronts = _render_mesh_many("render_mesh_many", meshes, calibs, res, shade, projection, nearest, background, near,
-                               perspective_correct, netC, feat_tensors_C, calib_tensors, view, lighting,
-                               None if lighting is None or lighting.self_shadow is None else (scene.light, maps))
-    backs = _scene_pictures(who, scene, meshes, cams, res, projection, nearest, near, perspective_correct, background,
-                            maps)
-    pairs = []
-    for front, back, cam in zip(fronts, backs, cams):
+    ras = ops.raster("render_mesh_many", res, projection, nearest, background, near, perspective_correct)
+    fronts, _, maps = _render_mesh_many("render_mesh_many", meshes, calibs, ras, shade, netC, feat_tensors_C,
+                                        calib_tensors, view, lighting, scene.light)
+    nv = ops._view_calibs(who, cams[0]).shape[0]
+    for i, front in enumerate(fronts):
         if front is None:  # no subject: an uncovered picture of the scene's size
-            front = (torch.full_like(back[0], float(background)), torch.zeros_like(back[1]),
-                     torch.full_like(back[2], -1))
-        elif _single_camera(cam):
-            front = tuple(t[None] for t in front)
-        pairs.append(front)
-    done = ops.picture_composite_batch(pairs, backs, composite, nearest, background, who=who)
-    out = []
-    for (image, depth, mask), front, cam in zip(done, pairs, cams):
-        face = front[2]
-        if _single_camera(cam):
-            image, depth, face, mask = image[0], depth[0], face[0], mask[0]
-        out.append(ScenePicture(image, depth, face, mask))
-    return out
+            shape = (nv,) + ras.res
+            fronts[i] = (torch.full(shape + (3,), ras.background, dtype=torch.float32, device=scene.verts.device),
+                         torch.zeros(shape, dtype=torch.float32, device=scene.verts.device),
+                         torch.full(shape, -1, dtype=torch.int32, device=scene.verts.device))
+    _, done = _scene_pictures(who, scene, cams, ras, maps, fronts, composite)
+    return [ScenePicture(*_squeezed((image, depth, front[2], mask), cam))
+            for (image, depth, mask), front, cam in zip(done, fronts, cams)]
 
 
 @torch.no_grad()

@@ -184,4 +184,4 @@ def test_ops_wrappers_check_their_lists_before_any_device_work():
     with pytest.raises(ValueError, match="picture_paint_batch"):
         ops.picture_paint_batch([values], [pixels, pixels], [count], out=[pos.clone()])
     with pytest.raises(ValueError, match="face ids"):
-        ops.render_netc_batch("who", [], [], [], [], 8, None, out=(torch.zeros(1), None, None))
+        ops.render_netc_batch("who", [], [], [], [], ops.raster("who", 8), None, out=(torch.zeros(1), None, None))

@@ -63,6 +63,40 @@ def test_picture_options_record():
     assert isinstance(got.near, float) and got.perspective_correct is True
 
 
+def test_raster_record():
+    """ops.Raster: the six rasteriser arguments as one record, made by ops.raster with the checks and texts of the
+    render calls, and what PictureOptions.raster hands to the recon bodies."""
+    from monoport_amd import ops
+    from monoport_amd.pipeline import _picture_options
+    from monoport_amd.recon import mesh_options
+    who = "FrameSlot(pictures=...)"
+    assert ops.Raster._fields == ("res", "projection", "nearest", "background", "near", "perspective_correct")
+    colours = mesh_options(None, colors=True)
+    got = _picture_options({}, colours).raster
+    assert isinstance(got, ops.Raster) and got == ops.raster(who, 257)
+    assert got == ((257, 257), "orthogonal", "max", 1.0, None, False)
+    got = _picture_options(dict(views=4, res=(40, 24), shade=None, projection="perspective", nearest="min", near=2,
+                                perspective_correct=1, background=0), colours).raster
+    assert got == ops.raster(who, (40, 24), "perspective", "min", 0, 2, 1)
+    assert got == ((40, 24), "perspective", "min", 0.0, 2.0, True)
+    assert isinstance(got.near, float) and isinstance(got.background, float) and got.perspective_correct is True
+    for res in (0, 4097, (16, 0), (5000, 16)):
+        with pytest.raises(ValueError, match="who: image size"):
+            ops.raster("who", res)
+    with pytest.raises(ValueError, match="projection must be one of"):
+        ops.raster("who", 8, "fisheye")
+    with pytest.raises(ValueError, match="nearest must be one of"):
+        ops.raster("who", 8, nearest="closest")
+    with pytest.raises(ValueError, match="who: near clips perspective cameras only"):
+        ops.raster("who", 8, near=0.5)
+    with pytest.raises(ValueError, match="who: perspective_correct needs near"):
+        ops.raster("who", 8, "perspective", perspective_correct=True)
+    for near in (0.0, -2.0, math.inf, math.nan):
+        with pytest.raises(ValueError, match="who: near must be"):
+            ops.raster("who", 8, "perspective", near=near)
+    assert ops.raster("who", 8, "perspective", near=3) == ((8, 8), "perspective", "max", 1.0, 3.0, False)
+
+
 def test_render_keywords_are_refused_without_a_device():
     import os
     import re
