@@ -1068,6 +1068,59 @@ int mp_picture_light_transfer_batch(mp_ctx *ctx, int n_frames, const float *cons
                                     const float *direct_dir, const float *direct_rgb, float gamma, float background,
                                     float *const *image_out, float *const *shading, mp_stream stream);
 
+/* Pictures as bytes (RTL/main.py:541-553: np.uint8(...), cv2.imencode(".jpg", ...)): the 8-bit picture and the JPEG
+ * file of a float picture, made on the device.  The definition is this library's own, all-integer after step 1, and
+ * tests/jpeg_ref.py restates it in numpy: the device's bytes equal the restatement's, the same in every run.
+ *   Container: baseline sequential DCT JPEG in JFIF: 8-bit samples, components Y, Cb, Cr with ids 1, 2, 3, Huffman
+ * coding with the four tables of ITU-T T.81 Annex K.3 (selector 0 for Y, 1 for Cb / Cr).  Segments: SOI, APP0 (JFIF
+ * 1.01, no units, 1:1), DQT 0, DQT 1, SOF0, DHT (DC 0, AC 0, DC 1, AC 1), DRI, SOS, the entropy-coded data with RSTm
+ * between restart intervals, EOI.  The header is 629 bytes.
+ *   Given a picture [H,W,3] f32 (1 <= H, W <= MP_JPEG_MAX_SIDE):
+ *   1. 8 bit: t = x > 0 ? (x < 1 ? x : 1) : 0 (a NaN: 0), u = (int)((t * 255) + 0.5): the multiply and the add are two
+ *      separately rounded f32 operations (no FMA), the conversion truncates.  mp_picture_u8 is this step alone:
+ *      image [n_pixels,3] f32 -> out [n_pixels,3] uint8; n_pixels == 0: MP_OK; a null or misaligned (4 bytes) image, a
+ *      null out, n_pixels < 0 or out overlapping image: MP_ERR_ARG; n_pixels > 2^31 / 3: MP_ERR_UNSUPPORTED.
+ *   2. Padding to a multiple of the MCU (8 x 8 for MP_JPEG_444, 16 x 16 for MP_JPEG_420) by repeating the last column
+ *      and row of u.
+ *   3. Colour, int32 with an arithmetic >>:  Y = (19595 R + 38470 G + 7471 B + 32768) >> 16,
+ *      Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,
+ *      Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16.
+ *   4. Subsampling: MP_JPEG_444 (H = V = 1 everywhere) or MP_JPEG_420 (Y 2 x 2): Cb and Cr are then the 2 x 2 box
+ *      (a + b + c + d + 2) >> 2 of step 3's values.
+ *   5. Forward DCT per 8 x 8 block P (row y, column x) with C[u][x] = rint(8192 a(u) cos((2x + 1) u pi / 16)),
+ *      a(0) = sqrt(1/8), a(u > 0) = 1/2, computed once in float64 (64 integer literals):
+ *      rows A[y][u] = (sum_x C[u][x] (P[y][x] - 128) + 1024) >> 11, columns F[v][u] = (sum_y C[v][y] A[y][u] + 16384)
+ *      >> 15.  Every intermediate fits int32; |F| <= 1024.
+ *   6. Quantisation: the Annex K.1 tables scaled as the IJG library scales them: s = 5000 / quality below 50, else
+ *      200 - 2 quality; Q = clamp((base s + 50) / 100, 1, 255) in integer division; the coefficient is
+ *      sign(F) ((|F| + (Q >> 1)) / Q), put into zig-zag order.
+ *   7. Entropy coding: MCUs in raster order, the blocks of an MCU as Y00 Y01 Y10 Y11 Cb Cr (420) or Y Cb Cr (444).
+ *      Per block the DC difference to the previous block of the same component (0 at the start of a restart interval)
+ *      as category + magnitude bits, the AC coefficients as (run, size) symbols with ZRL (0xF0) for runs above 15, and
+ *      EOB (0x00) unless coefficient 63 is non-zero: at most 1660 bits.  A restart interval is `restart` MCUs (1..65535;
+ *      0: the MCUs of one MCU row) and DRI carries it; each interval is padded with 1-bits to a byte, every 0xFF data
+ *      byte is followed by 0x00, and RST(k mod 8) follows interval k except the last.
+ *   mp_picture_jpeg: n pictures of one size, CONTIGUOUS: images [n,H,W,3] f32 (a slot's pictures already are), so
+ *   the call takes one base pointer, no pointer arrays, and is not bound by mp_max_frames() (n <= 65535).  out
+ *   [n,capacity] uint8 receives file i at out + i * capacity; info [n,2] int32 = {bytes of file i, overflowed}.  The size
+ *   of a file is known on the device before any of it is written: where it exceeds `capacity`, NOTHING of that picture
+ *   is written, info[i] = {the size it needs, 1}, and the other pictures are unaffected; no store lands past capacity
+ *   under any input.  A second call with capacity >= info[i][0] gives the bytes a sufficient capacity would have given.
+ *   mp_jpeg_max_bytes: what no file of that geometry exceeds: 629 + 416 per block (208 bytes of bit string, doubled for
+ *   stuffing) + 2 per interval; 0 for a geometry mp_picture_jpeg refuses.  Typical files are a small fraction of it.
+ *   Six launches (transform, block coding, interval scan, interval merge, offsets, emit), integer atomics only, nothing
+ *   allocated: 552 bytes of the stream's scratch arena per block and 12 per interval.  Asynchronous, no host value.
+ *   Refusals (a message, nothing launched): h or w outside 1..MP_JPEG_MAX_SIDE, an unknown subsampling, n > 65535:
+ *   MP_ERR_UNSUPPORTED; quality outside 1..100, restart outside 0..65535, n < 1, capacity below the header's 629 bytes or
+ *   above 2^31, a null or misaligned (4 bytes: images, info) buffer, out / info overlapping images or each other:
+ *   MP_ERR_ARG. */
+#define MP_JPEG_MAX_SIDE 4096
+enum { MP_JPEG_444 = 0, MP_JPEG_420 = 1 };
+int mp_picture_u8(mp_ctx *ctx, const float *image, int64_t n_pixels, uint8_t *out, mp_stream stream);
+int64_t mp_jpeg_max_bytes(int h, int w, int subsampling, int restart);
+int mp_picture_jpeg(mp_ctx *ctx, const float *images, int n, int h, int w, int quality, int subsampling, int restart,
+                    uint8_t *out, int64_t capacity, int32_t *info, mp_stream stream);
+
 /* The largest connected body of an occupancy volume [R,R,R] (no counterpart in the reference; the clean-up in front
  * of marching cubes that drops floating blobs).
  *   Foreground: voxels with value > level (marching cubes' "inside"; a NaN and value == level are background).

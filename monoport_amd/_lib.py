@@ -99,6 +99,8 @@ WRAP_REPEAT, WRAP_CLAMP = 0, 1
 COMPOSITE_OVER, COMPOSITE_DEPTH = 0, 1
 # MP_CONN_* connectivities of mp_volume_keep_largest (include/monoport_hip.h)
 CONN_6, CONN_26 = 6, 26
+# MP_JPEG_* subsamplings of mp_picture_jpeg (include/monoport_hip.h)
+JPEG_444, JPEG_420 = 0, 1
 MAX_VIEWS = 8  # MP_MAX_VIEWS: views per mp_query_views / mp_mlp_forward_views call
 MAX_FRAME_VIEWS = 64  # MP_MAX_FRAME_VIEWS = mp_max_frame_views(): frames x views per mp_recon_views_batch call
 MAX_FRAMES = 32  # kMaxFrames (csrc/mp_internal.h) = mp_max_frames(): frames per batched query / recon call
@@ -232,6 +234,9 @@ SIGNATURES = {
                                           c_vp, c_vp, c_vp]),
     "mp_picture_light_transfer_batch": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, _pf32, c_vp, c_vp, c_i64, _pf32, _pf32,
                                                 c_f32, c_f32, c_vp, c_vp, c_vp]),
+    "mp_picture_u8": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "mp_jpeg_max_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
+    "mp_picture_jpeg": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_vp]),
     "mp_volume_bits_words": (c_i64, [c_int]),
     "mp_volume_bits": (c_int, [c_vp, c_vp, c_int, c_f32, c_vp, c_vp]),
     "mp_volume_bits_batch": (c_int, [c_vp, c_int, c_vp, c_int, c_f32, c_vp, c_vp, c_vp]),

@@ -2140,6 +2140,63 @@ int mp_picture_light_transfer_batch(mp_ctx *ctx, int n_frames, const float *cons
                                background, image_out, shading, stream);
 }
 
+int mp_picture_u8(mp_ctx *ctx, const float *image, int64_t n_pixels, uint8_t *out, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (n_pixels < 0) return fail(ctx, MP_ERR_ARG, "mp_picture_u8: n_pixels %lld", (long long)n_pixels);
+  if (n_pixels > 0x7fffffffLL / 3)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "mp_picture_u8: n_pixels %lld (at most 2^31 / 3)", (long long)n_pixels);
+  if (n_pixels == 0) return MP_OK;
+  if (!image || !out || ((uintptr_t)image & 3u))
+    return fail(ctx, MP_ERR_ARG, "mp_picture_u8: a null or misaligned buffer");
+  if (ranges_overlap(out, (size_t)n_pixels * 3, image, (size_t)n_pixels * 12))
+    return fail(ctx, MP_ERR_ARG, "mp_picture_u8: out aliases image");
+  DeviceGuard g(ctx->device);
+  return launch_picture_u8(ctx, image, n_pixels, out, (hipStream_t)stream);
+}
+
+static bool jpeg_geometry_ok(int h, int w, int subsampling, int restart) {
+  return h >= 1 && h <= MP_JPEG_MAX_SIDE && w >= 1 && w <= MP_JPEG_MAX_SIDE &&
+         (subsampling == MP_JPEG_444 || subsampling == MP_JPEG_420) && restart >= 0 && restart <= 65535;
+}
+
+int64_t mp_jpeg_max_bytes(int h, int w, int subsampling, int restart) {
+  return jpeg_geometry_ok(h, w, subsampling, restart) ? (int64_t)jpeg_max_bytes(h, w, subsampling == MP_JPEG_420, restart)
+                                                      : 0;
+}
+
+int mp_picture_jpeg(mp_ctx *ctx, const float *images, int n, int h, int w, int quality, int subsampling, int restart,
+                    uint8_t *out, int64_t capacity, int32_t *info, mp_stream stream) {
+  const char *who = "mp_picture_jpeg";
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (h < 1 || h > MP_JPEG_MAX_SIDE || w < 1 || w > MP_JPEG_MAX_SIDE)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: a picture of %d x %d (sides 1..%d)", who, h, w, MP_JPEG_MAX_SIDE);
+  if (subsampling != MP_JPEG_444 && subsampling != MP_JPEG_420)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: subsampling %d (MP_JPEG_444 or MP_JPEG_420)", who, subsampling);
+  if (quality < 1 || quality > 100) return fail(ctx, MP_ERR_ARG, "%s: quality %d (1..100)", who, quality);
+  if (restart < 0 || restart > 65535)
+    return fail(ctx, MP_ERR_ARG, "%s: restart %d (0: one MCU row, or 1..65535 MCUs)", who, restart);
+  if (n < 1) return fail(ctx, MP_ERR_ARG, "%s: n %d pictures", who, n);
+  if (n > 65535) return fail(ctx, MP_ERR_UNSUPPORTED, "%s: n %d pictures (at most 65535 per call)", who, n);
+  if (capacity < jpeg_header_bytes() || capacity > ((int64_t)1 << 31))
+    return fail(ctx, MP_ERR_ARG, "%s: capacity %lld (at least the header's %d bytes, at most 2^31)", who,
+                (long long)capacity, jpeg_header_bytes());
+  if (!images || !out || !info || ((uintptr_t)images & 3u) || ((uintptr_t)info & 3u))
+    return fail(ctx, MP_ERR_ARG, "%s: a null or misaligned buffer", who);
+  const size_t in_bytes = (size_t)n * h * w * 12, out_bytes = (size_t)n * (size_t)capacity, info_bytes = (size_t)n * 8;
+  if (ranges_overlap(out, out_bytes, images, in_bytes) || ranges_overlap(info, info_bytes, images, in_bytes) ||
+      ranges_overlap(out, out_bytes, info, info_bytes))
+    return fail(ctx, MP_ERR_ARG, "%s: out / info aliases images or each other", who);
+  DeviceGuard g(ctx->device);
+  const int s420 = subsampling == MP_JPEG_420;
+  void *scratch = nullptr;
+  const int rc = ensure_scratch(ctx, (hipStream_t)stream, jpeg_scratch_bytes(n, h, w, s420, restart), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_picture_jpeg(ctx, scratch, images, n, h, w, quality, s420, restart, out, capacity, info,
+                             (hipStream_t)stream);
+}
+
 int64_t mp_volume_bits_words(int r) { return r < 1 || r > MP_TRANSFER_MAX_RES ? 0 : (int64_t)volume_bits_words(r); }
 
 int mp_volume_bits(mp_ctx *ctx, const float *volume, int r, float level, uint32_t *bits, mp_stream stream) {

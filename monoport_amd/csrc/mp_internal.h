@@ -504,6 +504,15 @@ int launch_picture_light_batch(mp_ctx *ctx, int n_frames, const float *const *no
                                const float *const *ambient, long long n_pixels, int n_views, const float *sh,
                                const float *direct_dir, const float *direct_rgb, float gamma, const float *normal_mats,
                                float background, float *const *image_out, float *const *shading, hipStream_t st);
+// jpeg.hip: [n_pixels,3] f32 -> uint8, and n pictures [h,w,3] f32 of one size -> n baseline JFIF files in out [n,capacity]
+// with info [n,2] = {bytes, overflowed}; s420: 0 = 4:4:4, 1 = 4:2:0; restart: MCUs per interval, 0 = one MCU row;
+// scratch: jpeg_scratch_bytes(n, ...).  jpeg_max_bytes: what no file of that geometry exceeds
+int launch_picture_u8(mp_ctx *ctx, const float *image, long long n_pixels, uint8_t *out, hipStream_t st);
+int jpeg_header_bytes();
+long long jpeg_max_bytes(int h, int w, int s420, int restart);
+size_t jpeg_scratch_bytes(int n, int h, int w, int s420, int restart);
+int launch_picture_jpeg(mp_ctx *ctx, void *scratch, const float *images, int n, int h, int w, int quality, int s420,
+                        int restart, uint8_t *out, long long capacity, int32_t *info, hipStream_t st);
 #ifdef __HIPCC__
 // v / |v|, or (0, 0, 0) where |v|^2 is not finite or not > 0 (a zero, a NaN, an inf, an overflow)
 __device__ __forceinline__ void light_normalise(float x, float y, float z, float &ox, float &oy, float &oz) {

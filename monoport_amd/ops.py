@@ -2458,6 +2458,95 @@ def render_scene_batch(who, scene, calibs, ras, out=None, uv=None, positions=Non
     return [(im, r[1], r[2]) for im, r in zip(images, raws)]
 
 
+# MP_JPEG_* (include/monoport_hip.h)
+JPEG_SUBSAMPLINGS = {"444": _lib.JPEG_444, "420": _lib.JPEG_420}
+JPEG_MAX_SIDE = 4096  # MP_JPEG_MAX_SIDE
+JPEG_HEADER_BYTES = 629
+
+
+def picture_u8_raw(image, out=None):
+    """mp_picture_u8: float32 [...,3] -> uint8 of the same shape, clamp(x, 0, 1) * 255 + 0.5 truncated (two f32
+    operations, a NaN gives 0): step 1 of the JPEG definition in include/monoport_hip.h.  ``out``: a contiguous uint8
+    tensor of that shape to write into.  No host sync."""
+    who = "picture_u8_raw"
+    if not isinstance(image, torch.Tensor) or image.dtype != torch.float32 or image.dim() < 1 or image.shape[-1] != 3:
+        raise ValueError("%s: image must be a float32 tensor [...,3]" % who)
+    image = image.contiguous()
+    if out is None:
+        out = torch.empty(image.shape, dtype=torch.uint8, device=image.device)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.shape != image.shape
+          or not out.is_contiguous() or out.device != image.device):
+        raise ValueError("%s: out must be a contiguous uint8 tensor %s on %s" % (who, tuple(image.shape), image.device))
+    ctx = get_context(image.device)
+    ctx.check(ctx.lib.mp_picture_u8(ctx.handle, _ptr(image), image.numel() // 3, _ptr(out), _stream(image)),
+              "mp_picture_u8")
+    return out
+
+
+def jpeg_params(who, quality, subsampling, restart):
+    """(quality, MP_JPEG_* subsampling, restart with 0 for the default) of mp_picture_jpeg as ints, checked."""
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= quality <= 100:
+        raise ValueError("%s: quality must be an int in 1..100, got %r" % (who, quality))
+    sub = _named_mode(who, "subsampling", JPEG_SUBSAMPLINGS, subsampling)
+    if restart is None:
+        restart = 0
+    elif isinstance(restart, bool) or not isinstance(restart, (int, np.integer)) or not 1 <= restart <= 65535:
+        raise ValueError("%s: restart must be None (one MCU row) or an int in 1..65535 MCUs, got %r" % (who, restart))
+    return int(quality), sub, int(restart)
+
+
+def jpeg_max_bytes(h, w, subsampling="420", restart=None):
+    """mp_jpeg_max_bytes: what no JPEG file of an [h,w,3] picture exceeds at any content and quality: the 629-byte
+    header + 416 bytes per 8x8 block + 2 per restart interval.  Typical files are a small fraction of it."""
+    who = "jpeg_max_bytes"
+    _, sub, restart = jpeg_params(who, 90, subsampling, restart)
+    for side in (h, w):
+        if isinstance(side, bool) or not isinstance(side, (int, np.integer)) or not 1 <= side <= JPEG_MAX_SIDE:
+            raise ValueError("%s: h and w must be ints in 1..%d, got %r x %r" % (who, JPEG_MAX_SIDE, h, w))
+    return int(_lib.load().mp_jpeg_max_bytes(int(h), int(w), sub, restart))
+
+
+def picture_jpeg_raw(images, quality=90, subsampling="420", restart=None, capacity=None, out=None, info=None):
+    """mp_picture_jpeg: ``images`` float32 [n,H,W,3] (contiguous: one base pointer, any n up to 65535) -> (out uint8
+    [n,capacity], info int32 [n,2]) on the device: file i is ``out[i, :info[i, 0]]`` where ``info[i, 1] == 0``; where it
+    is 1 the file did not fit, nothing of it was written and ``info[i, 0]`` is the capacity it needs.  Baseline JFIF with
+    restart intervals of ``restart`` MCUs (None: one MCU row), defined byte for byte in include/monoport_hip.h.
+    ``capacity``: None = ``jpeg_max_bytes`` (never overflows), else bytes per picture (>= the 629-byte header).  ``out`` /
+    ``info``: contiguous tensors to write into (``out`` gives the capacity).  One set of six launches; no host sync."""
+    who = "picture_jpeg_raw"
+    if (not isinstance(images, torch.Tensor) or images.dtype != torch.float32 or images.dim() != 4
+            or images.shape[-1] != 3 or not images.is_contiguous()):
+        raise ValueError("%s: images must be a contiguous float32 tensor [n,H,W,3]" % who)
+    n, h, w = (int(v) for v in images.shape[:3])
+    if n < 1 or not (1 <= h <= JPEG_MAX_SIDE and 1 <= w <= JPEG_MAX_SIDE):
+        raise ValueError("%s: at least one picture with sides in 1..%d, got %s" % (who, JPEG_MAX_SIDE, tuple(images.shape)))
+    quality, sub, restart = jpeg_params(who, quality, subsampling, restart)
+    dev = images.device
+    if out is not None:
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != n
+                or not out.is_contiguous() or out.device != dev):
+            raise ValueError("%s: out must be a contiguous uint8 tensor [%d,capacity] on %s" % (who, n, dev))
+        if capacity is not None and int(capacity) != out.shape[1]:
+            raise ValueError("%s: capacity %r against an out of %d bytes per picture" % (who, capacity, out.shape[1]))
+        capacity = int(out.shape[1])
+    elif capacity is None:
+        capacity = jpeg_max_bytes(h, w, subsampling, restart or None)
+    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < JPEG_HEADER_BYTES:
+        raise ValueError("%s: capacity must be an int >= the header's %d bytes, got %r" % (who, JPEG_HEADER_BYTES, capacity))
+    if info is None:
+        info = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    elif (not isinstance(info, torch.Tensor) or info.dtype != torch.int32 or info.shape != (n, 2)
+          or not info.is_contiguous() or info.device != dev):
+        raise ValueError("%s: info must be a contiguous int32 tensor [%d,2] on %s" % (who, n, dev))
+    if out is None:
+        out = torch.empty((n, int(capacity)), dtype=torch.uint8, device=dev)
+    ctx = get_context(dev)
+    ctx.check(ctx.lib.mp_picture_jpeg(ctx.handle, _ptr(images), n, h, w, quality, sub, restart, _ptr(out), int(capacity),
+                                      _ptr(info), _stream(images)), "mp_picture_jpeg")
+    _keep_until_done(dev, [images])
+    return out, info
+
+
 # MP_CONN_* (include/monoport_hip.h): face neighbours / face, edge and corner neighbours
 CONNECTIVITIES = (_lib.CONN_6, _lib.CONN_26)
 

@@ -133,6 +133,8 @@ class FrameSlot:
     the netC texture stages :373-441 when ``netC`` is given)."""
 
     view = 0  # the row of a multi-view head's result (ViewsSlot); a single-view head has the one
+    jpeg = None  # the ``recon.Jpeg`` of ``encode_pictures``; None: nothing is allocated or enqueued for it
+    _chained = False  # the chain has been enqueued at least once (``prepare`` / ``submit``)
 
     def __init__(self, netG, device, resolutions=RESOLUTIONS, b_min=(-1, -1, -1), b_max=(1, 1, 1),
                  balance=0.5, feature_hook=None, use_graph=False, netC=None, batch=1, skip_table=None,
@@ -381,6 +383,7 @@ class FrameSlot:
 
     @torch.no_grad()
     def _chain(self):
+        self._chained = True
         mlp = self.net.surface_classifier.packed()
         if self.graph is not None:
             self.graph.replay()  # the batched encoder(s) as one hipGraph launch
@@ -435,6 +438,8 @@ class FrameSlot:
             self._mesh_chain(n)
         if self.picture_options is not None:
             self._render_pictures(n)
+        if self.jpeg is not None:
+            self._encode_pictures(n)
 
     # the netC pieces of the chain that depend on the head's views (ColorViewsSlot overrides them)
     def _pack_colour_maps(self, b, feat, feat_c):
@@ -548,6 +553,62 @@ class FrameSlot:
                     None if self.pictures_image is None else self.pictures_image[b], self.pictures_depth[b],
                     self.pictures_face[b]))
         return out
+
+    def encode_pictures(self, jpeg):
+        """Encode the slot's pictures on the device from now on: ``jpeg`` is a ``recon.Jpeg``.  To be called before the
+        first ``prepare`` / ``submit``; it needs pictures with a ``shade``.  The slot then owns the static
+        ``jpeg_bytes`` [batch * views, capacity] uint8 (``jpeg.capacity_for`` the pictures' size) and ``jpeg_info``
+        [batch * views, 2] int32, and the chain enqueues ONE mp_picture_jpeg over the active frames' pictures behind
+        ``_render_pictures`` on the slot's stream -- behind the composite with a scene, behind the lighting without one
+        -- with no host value in between; ``jpegs()`` hands the files out.  A slot on which this was never called
+        allocates and enqueues nothing for it."""
+        from .recon import Jpeg
+        who = "%s.encode_pictures" % type(self).__name__
+        if not isinstance(jpeg, Jpeg):
+            raise ValueError("%s: jpeg must be a recon.Jpeg, got %r" % (who, type(jpeg).__name__))
+        po = self.picture_options
+        if po is None:
+            raise ValueError("%s: the slot was made without pictures=..." % who)
+        if po.shade is None:
+            raise ValueError("%s: the slot's pictures have shade=None: there is no image to encode" % who)
+        if self._chained:
+            raise RuntimeError("%s: to be called before the first prepare / submit" % who)
+        n = self.batch * po.views
+        self.jpeg_bytes = torch.empty((n, jpeg.capacity_for(*po.res)), dtype=torch.uint8, device=self.device)
+        self.jpeg_info = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
+        self.jpeg = jpeg
+
+    def _encode_pictures(self, n):
+        """One mp_picture_jpeg over the n active frames' pictures: they are one contiguous [n * views,H,W,3] block."""
+        po, j = self.picture_options, self.jpeg
+        rows = n * po.views
+        ops.picture_jpeg_raw(self.pictures_image[:n].view((rows,) + po.res + (3,)), j.quality, j.subsampling, j.restart,
+                             out=self.jpeg_bytes[:rows], info=self.jpeg_info[:rows])
+
+    def jpegs(self):
+        """The JPEG files of the current submission's pictures, to be called after ``wait()`` (it waits if the caller
+        has not): a list of ``n_active`` entries, each a list of ``views`` ``bytes``, or None where ``pictures()`` gives
+        None.  One device-to-host copy of ``jpeg_info`` and one of the used prefixes of ``jpeg_bytes`` (besides
+        ``meshes()``' own).  A frame whose mesh ``meshes()`` made again, or one of whose files exceeded the capacity,
+        is encoded from the picture ``pictures()`` returns (``recon.encode_jpeg``): the same bytes a sufficient
+        capacity gives."""
+        if self.jpeg is None:
+            raise RuntimeError("%s.jpegs(): encode_pictures(jpeg) was never called on this slot" % type(self).__name__)
+        from .recon import _collect_jpegs, encode_jpeg
+        pictures = self.pictures()
+        v = self.picture_options.views
+        rows = self.n_active * v
+        info = self.jpeg_info[:rows].cpu().numpy()
+        again = [pic is not None and (b in self._reran or bool(info[b * v:(b + 1) * v, 1].any()))
+                 for b, pic in enumerate(pictures)]
+        mine = info.copy()
+        for b, pic in enumerate(pictures):
+            if pic is None or again[b]:
+                mine[b * v:(b + 1) * v] = (0, 0)  # nothing of these rows is copied
+        shape = (rows,) + self.picture_options.res + (3,)
+        files = _collect_jpegs(self.pictures_image[:self.n_active].view(shape), self.jpeg_bytes, mine, self.jpeg)
+        return [None if pic is None else (encode_jpeg(pic.image, self.jpeg) if again[b] else files[b * v:(b + 1) * v])
+                for b, pic in enumerate(pictures)]
 
     def _rerun_picture(self, b, mesh):
         """Frame b again from its re-run ``Mesh``, into fresh tensors: the bodies of ``_render_pictures`` on the
@@ -866,6 +927,11 @@ class FramePipeline:
         slot.submit(images, calibs, images_c, cameras)
         self.n_submitted += 1
         return slot
+
+    def encode_pictures(self, jpeg):
+        """``FrameSlot.encode_pictures`` on every slot: before ``prepare`` / the first ``submit``."""
+        for s in self.slots:
+            s.encode_pictures(jpeg)
 
     def synchronize(self):
         for s in self.slots:

@@ -1122,6 +1122,93 @@ def light_picture(picture, normals, lighting, calibs=None, visibility=None):
                                    lighting.albedo, nv, with_shading=True, who=who)[0]
 
 
+class Jpeg:
+    """How pictures are encoded on the device (mp_picture_jpeg in include/monoport_hip.h: baseline JFIF with restart
+    intervals, byte for byte this library's own definition; what the reference's server loop does with cv2.imencode).
+    ``quality``: 1..100, scaled as the IJG library scales the Annex K tables; ``subsampling``: "420" (chroma 2 x 2, the
+    default) or "444"; ``restart``: MCUs per restart interval, 1..65535, or None = the MCUs of one MCU row (the unit of
+    parallel work; the marker and the padding cost a few percent of the file).  ``capacity``: bytes reserved per picture,
+    at least the 629-byte header; None = ``4096 + H * W * 3 // 4`` -- a quarter of the 8-bit picture, several times a
+    typical file at quality 90 --, never more than ``ops.jpeg_max_bytes``.  A file that does not fit is reported by the
+    device and encoded again alone at its exact size (``encode_jpeg``, ``FrameSlot.jpegs``): the capacity never
+    changes the bytes.  Everything is validated here; a Jpeg holds host values only."""
+
+    def __init__(self, quality=90, subsampling="420", restart=None, capacity=None):
+        who = "Jpeg"
+        self.quality, sub, restart = ops.jpeg_params(who, quality, subsampling, restart)
+        self.subsampling = {v: k for k, v in ops.JPEG_SUBSAMPLINGS.items()}[sub]
+        self.restart = restart or None
+        if capacity is not None:
+            if (isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer))
+                    or not ops.JPEG_HEADER_BYTES <= capacity <= 2 ** 31):
+                raise ValueError("%s: capacity must be None or an int in %d..2^31 bytes, got %r"
+                                 % (who, ops.JPEG_HEADER_BYTES, capacity))
+            capacity = int(capacity)
+        self.capacity = capacity
+
+    def capacity_for(self, h, w):
+        """Bytes reserved per [h,w,3] picture."""
+        if self.capacity is not None:
+            return self.capacity
+        return min(4096 + h * w * 3 // 4, ops.jpeg_max_bytes(h, w, self.subsampling, self.restart))
+
+
+def picture_u8(image):
+    """``image`` float32 [...,3] (a picture of this module: values in [0, 1]) -> uint8 of the same shape on the device:
+    (int)(clamp(x, 0, 1) * 255 + 0.5), a NaN gives 0 -- the reference's np.uint8 of its pictures, and step 1 of the
+    JPEG definition in include/monoport_hip.h.  For a display or a video encoder.  No host sync."""
+    return ops.picture_u8_raw(image)
+
+
+def _jpeg_images(who, pictures):
+    """(images [n,H,W,3] contiguous float32, whether ``pictures`` was one [H,W,3] picture)."""
+    image = pictures.image if hasattr(pictures, "image") and not torch.is_tensor(pictures) else pictures
+    if image is None:
+        raise ValueError("%s: the picture has no image (it was rendered with shade=None)" % who)
+    if not torch.is_tensor(image) or image.dtype != torch.float32 or image.dim() not in (3, 4) or image.shape[-1] != 3:
+        raise ValueError("%s: pictures must be a MeshRender, a ScenePicture or a float32 tensor [H,W,3] / [n,H,W,3]" % who)
+    return (image[None] if image.dim() == 3 else image).contiguous(), image.dim() == 3
+
+
+def _collect_jpegs(images, out, info, jpeg):
+    """The files of ``images`` [n,H,W,3] from what mp_picture_jpeg left in ``out`` [n,capacity] under the HOST rows
+    ``info`` [n,2]: one copy of the used prefixes; a picture that overflowed is encoded again alone at the size the
+    device reported, which gives the bytes a sufficient capacity would have given."""
+    fits = [i for i in range(len(info)) if not info[i][1]]
+    used = max([int(info[i][0]) for i in fits], default=0)
+    host = out[:len(info), :used].cpu().numpy() if fits else None
+    files = []
+    for i in range(len(info)):
+        size = int(info[i][0])
+        if info[i][1]:
+            again, again_info = ops.picture_jpeg_raw(images[i:i + 1], jpeg.quality, jpeg.subsampling, jpeg.restart,
+                                                     capacity=size)
+            row = again_info.cpu().numpy()[0]
+            if tuple(row) != (size, 0):
+                raise RuntimeError("encode_jpeg: a picture of %d bytes gave %s at that capacity" % (size, tuple(row)))
+            files.append(again[0].cpu().numpy().tobytes())
+        else:
+            files.append(host[i, :size].tobytes())
+    return files
+
+
+def encode_jpeg(pictures, jpeg=None):
+    """The JPEG files of ``pictures`` (a ``MeshRender`` / ``ScenePicture`` with an image, or a float32 image tensor
+    [H,W,3] or [n,H,W,3] on the device) under ``jpeg`` (a ``Jpeg``; None: its defaults), encoded on the device:
+    ``bytes`` for one [H,W,3] picture, a list of ``bytes`` for [n,H,W,3].  One device-to-host copy of the sizes, then
+    one of the used prefixes; a picture whose file exceeded ``jpeg``'s capacity is encoded again alone at the size the
+    device reported.  Any JPEG decoder reads the files; tests/jpeg_ref.py restates them byte for byte."""
+    who = "encode_jpeg"
+    jpeg = Jpeg() if jpeg is None else jpeg
+    if not isinstance(jpeg, Jpeg):
+        raise ValueError("%s: jpeg must be a recon.Jpeg, got %r" % (who, type(jpeg).__name__))
+    images, single = _jpeg_images(who, pictures)
+    out, info = ops.picture_jpeg_raw(images, jpeg.quality, jpeg.subsampling, jpeg.restart,
+                                     capacity=jpeg.capacity_for(int(images.shape[1]), int(images.shape[2])))
+    files = _collect_jpegs(images, out, info.cpu().numpy(), jpeg)
+    return files[0] if single else files
+
+
 def _scene_pictures(who, scene, cams, ras, maps=None, fronts=None, composite="depth", out=None, back=None):
     """THE scene behind a set of pictures, for the render calls, a slot and a slot's re-run alike -> (per camera set the
     raw picture (image, depth, face; each [n_views, ...]) of ``scene`` under the ``ops.Raster`` ``ras``, per camera set

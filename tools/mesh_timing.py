@@ -95,6 +95,13 @@ tracer may skip); then the ``--lighting`` slots (without the self-shadow, SH in 
 
     python tools/mesh_timing.py --transfer [--passes 5] [--out profiles/mesh_transfer_timing.json]
 
+``--jpeg`` measures the pictures' encoding (profiles/mesh_jpeg_timing.json): mp_picture_jpeg alone, per picture in a
+batch of 20 lit pictures at 257^2 and 1024^2, quality 90, 420 and 444, with the median file size; then the
+``--lighting`` slots without and with ``encode_pictures``, with ``pictures()`` against ``jpegs()`` as the consumer, and,
+where Pillow is importable, the way to a JPEG without it: ``pictures()``, ``.cpu()``, Pillow ``save``.
+
+    python tools/mesh_timing.py --jpeg [--passes 5] [--out profiles/mesh_jpeg_timing.json]
+
 The protocol of tools/recon_views_timing.py: after a warm-up of all, the passes alternate; a pass is `meshes`
 meshes, wall clock around a final stream sync.  Prints (and writes) one JSON line: per way the median, minimum and
 maximum time per mesh (ms) over the passes.  The verdict fields restate what to check: (b) not slower than (a) by
@@ -139,6 +146,7 @@ def main():
     ap.add_argument("--shadow", action="store_true", help="slot pictures over a scene, without and with a light on it")
     ap.add_argument("--lighting", action="store_true", help="the --shadow slots without and with lighting= on the subject")
     ap.add_argument("--transfer", action="store_true", help="bits, transfer and shade per mesh; lit slots with transfer=")
+    ap.add_argument("--jpeg", action="store_true", help="mp_picture_jpeg alone; the --lighting slots with encode_pictures")
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "mesh_render_clip_timing.json" if a.render and a.clip else
@@ -148,6 +156,7 @@ def main():
                              "mesh_shadow_timing.json" if a.shadow else
                              "mesh_lighting_timing.json" if a.lighting else
                              "mesh_transfer_timing.json" if a.transfer else
+                             "mesh_jpeg_timing.json" if a.jpeg else
                              "mesh_smooth_timing.json" if a.smooth else
                              "mesh_simplify_timing.json" if a.simplify else
                              "keep_largest_timing.json" if a.clean else
@@ -163,6 +172,9 @@ def main():
         return
     if a.lighting:
         write(a, slot_lighting(a))
+        return
+    if a.jpeg:
+        write(a, slot_jpeg(a))
         return
     if a.transfer:
         out = transfer_kernels(a)
@@ -594,6 +606,81 @@ def slot_lighting(a, frames=20):
     return out
 
 
+def slot_jpeg(a, frames=20):
+    """mp_picture_jpeg alone on a batch of ``frames`` lit pictures (ms per picture, bytes per file) at 257^2 and 1024^2,
+    quality 90, 420 and 444; then the --lighting slots without and with ``encode_pictures``, with ``pictures()`` against
+    ``jpegs()`` as the consumer (ms per frame of a submission); and, where Pillow is importable, the only way to a JPEG
+    without the feature: ``pictures()``, ``.cpu()``, Pillow ``save`` on the host."""
+    import io
+    try:
+        from PIL import Image
+    except ImportError:
+        Image = None
+    direction = (0.4, -1.0, 0.3)
+    sun = recon.Light.directional(direction, (-1.5, -0.9, -1.5), (1.5, 1.0, 1.5), res=512, radius=1)
+    floor, cam, mesh, base = _scene_setup(sun)
+    sh = np.random.RandomState(0).uniform(-0.2, 0.4, (9, 3)).astype(np.float32)
+    sh[0] += 0.8
+    lighting = recon.Lighting(sh, direct=(direction, (0.9, 0.85, 0.8)), frame="camera", albedo=(0.8, 0.7, 0.6),
+                              self_shadow=0.02)
+    jpeg = recon.Jpeg(quality=90, subsampling="420")
+    rows = []
+    for res in (257, 1024):
+        opts = dict(base, res=res, scene=floor)
+        rows.append(("pictures_%d" % res, mesh, opts, cam, dict(lighting=lighting)))
+        rows.append(("encode_%d" % res, mesh, opts, cam, dict(lighting=lighting, encode_pictures=jpeg)))
+    pipes, fn = _slot_pipes(frames, 1, rows)
+
+    def on_host(s):
+        files = []
+        for pic in s.pictures():
+            u8 = (pic.image.clamp(0, 1) * 255 + 0.5).to(torch.uint8).cpu().numpy()
+            for v in range(u8.shape[0]):
+                buf = io.BytesIO()
+                Image.fromarray(u8[v]).save(buf, "JPEG", quality=90, subsampling=2)
+                files.append(buf.getvalue())
+        return files
+
+    ways = {}
+    for res in (257, 1024):
+        ways["pictures_%d" % res] = fn("pictures_%d" % res)
+        ways["encode_%d_pictures" % res] = fn("encode_%d" % res)
+        ways["encode_%d_jpegs" % res] = fn("encode_%d" % res, lambda s: s.jpegs())
+        if Image is not None:
+            ways["host_pillow_%d" % res] = fn("pictures_%d" % res, on_host)
+    out = {"frames_per_slot": frames, "unit": "ms per frame", "quality": 90, "pillow": Image is not None,
+           "slots": "the --lighting slots: one view, the floor with its light, clay lighting with the self-shadow",
+           "consumers": "pictures(): views of the device buffers; jpegs(): the files as bytes on the host; host_pillow: "
+                        "pictures(), 8 bit on the device, .cpu(), Pillow save at quality 90, 420"}
+    out.update(alternate(ways, a.passes, frames))
+    # the kernels alone, on the pictures the slots made
+    kernels = {}
+    out["file_bytes"] = {}
+    for res in (257, 1024):
+        slot = pipes["encode_%d" % res].slots[0]
+        files = slot.jpegs()
+        out["file_bytes"]["%d_420_slot" % res] = stats([len(f[0]) for f in files])["median_ms"]
+        images = slot.pictures_image[:frames].reshape(frames, res, res, 3).clone()
+        for sub in ("420", "444"):
+            cap = recon.Jpeg(subsampling=sub).capacity_for(res, res)
+            bufs = (torch.empty((frames, cap), dtype=torch.uint8, device=DEV),
+                    torch.empty((frames, 2), dtype=torch.int32, device=DEV))
+            kernels["mp_picture_jpeg_%d_%s" % (res, sub)] = (
+                lambda images=images, sub=sub, bufs=bufs: ops.picture_jpeg_raw(images, 90, sub, None, out=bufs[0],
+                                                                               info=bufs[1]))
+            info = kernels["mp_picture_jpeg_%d_%s" % (res, sub)]()[1].cpu().numpy()
+            assert not info[:, 1].any()
+            out["file_bytes"]["%d_%s" % (res, sub)] = float(np.median(info[:, 0]))
+    for p_ in pipes.values():
+        p_.close()
+    out["kernels_unit"] = "ms per picture, a batch of %d" % frames
+    out["kernels"] = alternate(kernels, a.passes, frames)
+    for res in ("257", "1024"):
+        out["encode_%s_jpegs_minus_pictures_ms" % res] = round(
+            out["encode_%s_jpegs" % res]["median_ms"] - out["pictures_" + res]["median_ms"], 4)
+    return out
+
+
 def _definition_samples(verts, normals, occ, blocks, t, r, rays):
     """The samples mp_mesh_transfer's definition visits on one mesh, and those of them in an empty 8^3 block: the same
     f32 expressions in torch, every sample of every ray (no skipping), a chunk of vertices at a time."""
@@ -757,16 +844,20 @@ def _slot_pipes(frames, depth, meshes):
         kw = dict(pictures=pictures[0]) if pictures else {}
         if len(pictures) > 2:  # further keywords of the slot (lighting=)
             kw.update(pictures[2])
+        kw.pop("encode_pictures", None)
         cameras[name] = dict(cameras=pictures[1]) if pictures else {}
         pipes[name] = pipeline.FramePipeline(netg, dev, depth=depth, batch=frames, resolutions=RESOLUTIONS,
                                              b_min=B_MIN, b_max=B_MAX, feature_hook=hook, use_graph=True,
                                              netC=netc, mesh=mesh, **kw)
+        if len(pictures) > 2 and "encode_pictures" in pictures[2]:  # --jpeg: files behind the pictures
+            pipes[name].encode_pictures(pictures[2]["encode_pictures"])
         pipes[name].prepare()
 
-    def fn(name):
+    def fn(name, consume=None):
         def run():
             for s in [pipes[name].submit(images, calibs, **cameras[name]) for _ in range(depth)]:
-                assert all(m is not None for m in (s.pictures() if cameras[name] else s.meshes()))
+                got = consume(s) if consume else (s.pictures() if cameras[name] else s.meshes())
+                assert all(m is not None for m in got)
         return run
     return pipes, fn
 
