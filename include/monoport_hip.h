@@ -863,8 +863,8 @@ int mp_picture_paint_batch(mp_ctx *ctx, int n_frames, const float *const *values
  * batched ones with one frame; in the batched ones uv / face_id / image / front_* / back_* / depth / mask are HOST
  * arrays of n_frames device pointers (one pyramid and one size for all), blockIdx.y is the frame: frame f's outputs
  * equal the per-frame call's on frame f's inputs BIT FOR BIT.
- * NOT built: trilinear and anisotropic filtering, alpha.  Shadows of the subject on the scene: mp_picture_shadow
- * below. */
+ * NOT built: trilinear and anisotropic filtering; the composite has no alpha (the subject's coverage comes with
+ * mp_picture_resolve below).  Shadows of the subject on the scene: mp_picture_shadow below. */
 enum { MP_WRAP_REPEAT = 0, MP_WRAP_CLAMP = 1 };
 enum { MP_COMPOSITE_OVER = 0, MP_COMPOSITE_DEPTH = 1 };
 int64_t mp_texture_pyramid_floats(int ht, int wt, int levels);
@@ -886,6 +886,55 @@ int mp_picture_composite_batch(mp_ctx *ctx, int n_frames, const float *const *fr
                                const int32_t *const *back_face, int64_t n_pixels, int mode, int nearest,
                                float background, float *const *image, float *const *depth, uint8_t *const *mask,
                                mp_stream stream);
+
+/* ---- anti-aliasing: the resolve of a supersampled picture (the reference's multi_sample_rate attachments and their
+ * blit) --------------------------------------------------------------------------------------------------------------
+ * The rasteriser puts a vertex at u = (x + 1) * 0.5 * H pixels and pixel i has its centre at i + 0.5, so a picture of
+ * s H x s W under the same camera samples every pixel of the H x W one on a regular s x s grid inside it.  Every pass
+ * above (attributes, positions, normals, transfer, uv, texture, shadow, lighting, composite) runs at s times the size;
+ * this call then makes the final picture, once.  samples = s in 2..4; the inputs are pictures [s h, s w] (s h, s w in
+ * 1..4096), the outputs [h, w]: image f32 [.,.,3], depth f32, face_id int32, mask uint8 (the composite's 0 / 1 / 2),
+ * coverage f32.  Sample (a, b) of output pixel (i, j) is input pixel (s i + a, s j + b); the samples are visited in
+ * row-major order of (a, b).  A pure function of its inputs, defined bit for bit (resolve.hip; one launch, one thread
+ * per output pixel, no atomics, no scratch):
+ *   image_out[i,j,c] = (((x_0 + x_1) + x_2) + ... + x_{s s - 1}) / (float)(s s): sequential single IEEE f32 additions
+ *     starting FROM the first sample (not from 0), without FMA, then one IEEE division.  A region of equal samples x
+ *     therefore keeps its bits for s = 2 (2x and 4x are exact and fl(3x) + x rounds to 4x), and for s = 4 wherever x
+ *     has at most 20 significant bits, so that every partial sum is exact: the backgrounds and flat colours 0, 1, 0.5,
+ *     k / 256.  Any other x may move by a few ulps at s = 4 (fewer than 8), and so may any x at s = 3; a sum beyond
+ *     the f32 range is an infinity.  A NaN sample gives a NaN of unspecified payload.
+ *   A sample is the SUBJECT's iff mask == 2 when a mask is given, else iff face_id >= 0.  coverage[i,j] = (float)count
+ *     / (float)(s s), count the subject's samples: the subject's alpha.  image_out - (1 - coverage) * background is the
+ *     premultiplied subject for a consumer who composites elsewhere (with a scene the scene's samples are in image_out
+ *     too: the edge between subject and scene is blended here, correctly, which an alpha against a background is not).
+ *   A sample SHOWS iff mask != 0 when a mask is given, else iff face_id >= 0.  depth_out / face_out = the depth bits and
+ *     the face id of the showing sample that is nearest under `nearest`: the one with the largest key, key = the
+ *     rasteriser's orderable key (b ^ (b >> 31 ? 0xFFFFFFFF : 0x80000000) of the bits b) of depth with
+ *     MP_NEAREST_MAX_Z, of -depth (the sign bit flipped) with MP_NEAREST_MIN_Z; among equal keys the first in sample
+ *     order.  No showing sample: +0.0 and -1.  The face id may be -1 where the scene is nearest.
+ *   mask_out = the largest of the samples' masks.
+ * Every output needs its input: image_out image; depth_out and face_out BOTH depth and face_id; mask_out mask; coverage
+ * mask or face_id.  Any output may be NULL, not all; an input nobody needs may be NULL.  No output may share a byte with
+ * an input.  MP_ERR_ARG: samples outside 2..4; n_frames or n_views < 1, n_frames * n_views beyond mp_max_frames(); h or
+ * w < 1, samples * h or samples * w beyond 4096; an unknown nearest; no output; an output without its input; a NULL or
+ * not 4-byte aligned buffer of any frame (mask, mask_out: any alignment); the aliasing above.  Each refusal leaves an
+ * mp_last_error message, launches nothing and writes nothing.  Asynchronous, nothing synchronised, no scratch arena.
+ * Inputs that are all 16-byte aligned are read with wider loads (s = 2, 4); the bits do not depend on it.  Traffic per
+ * output pixel: s s (12 + 4 + 4 + 1) B read with everything given, 25 B written.
+ * mp_picture_resolve_batch: image / depth / face_id / mask / *_out / coverage are HOST arrays of n_frames device
+ * pointers, or NULL as a whole; a frame's n_views pictures lie back to back ([n_views, s h, s w] in, [n_views, h, w]
+ * out); one launch serves all, blockIdx.y the picture: frame f's outputs equal the single call's on frame f's inputs
+ * BIT FOR BIT.
+ * NOT built: filters wider than the pixel's own box, gamma-correct (linear-light) averaging, edge-only multisampling
+ * that shades once per pixel, the composite of two already resolved pictures. */
+int mp_picture_resolve(mp_ctx *ctx, const float *image, const float *depth, const int32_t *face_id,
+                       const uint8_t *mask, int h, int w, int samples, int nearest, float *image_out, float *depth_out,
+                       int32_t *face_out, uint8_t *mask_out, float *coverage, mp_stream stream);
+int mp_picture_resolve_batch(mp_ctx *ctx, int n_frames, int n_views, const float *const *image,
+                             const float *const *depth, const int32_t *const *face_id, const uint8_t *const *mask,
+                             int h, int w, int samples, int nearest, float *const *image_out, float *const *depth_out,
+                             int32_t *const *face_out, uint8_t *const *mask_out, float *const *coverage,
+                             mp_stream stream);
 
 /* ---- the shadow of the subject on a picture: a shadow map looked up per pixel, filtered, and the pixel darkened -------
  * A shadow map is what mp_mesh_render(_clip) writes WITHOUT an image for the caster under the light's camera: map_depth

@@ -222,6 +222,10 @@ SIGNATURES = {
                                      c_vp, c_vp]),
     "mp_picture_composite_batch": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_f32,
                                            c_vp, c_vp, c_vp, c_vp]),
+    "mp_picture_resolve": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp,
+                                   c_vp, c_vp]),
+    "mp_picture_resolve_batch": (c_int, [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp,
+                                         c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mp_picture_shadow": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, _pf32, c_int, c_int, c_f32,
                                   c_int, c_f32, c_vp, c_vp, c_vp]),
     "mp_picture_shadow_batch": (c_int, [c_vp, c_int, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int, c_int, _pf32, c_int,

@@ -735,6 +735,45 @@ static int picture_composite_checked(mp_ctx *ctx, const char *who, int n_frames,
                                         (hipStream_t)stream);
 }
 
+static int picture_resolve_checked(mp_ctx *ctx, const char *who, int n_frames, int n_views, const float *const *image,
+                                   const float *const *depth, const int32_t *const *face_id,
+                                   const uint8_t *const *mask, int h, int w, int samples, int nearest,
+                                   float *const *image_out, float *const *depth_out, int32_t *const *face_out,
+                                   uint8_t *const *mask_out, float *const *coverage, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (samples < 2 || samples > 4) return fail(ctx, MP_ERR_ARG, "%s: samples must be in 2..4, got %d", who, samples);
+  if (n_frames < 1 || n_views < 1 || (long long)n_frames * n_views > kMaxFrames)
+    return fail(ctx, MP_ERR_ARG, "%s: 1..%d pictures (frames x views) per call, got %d x %d", who, kMaxFrames, n_frames,
+                n_views);
+  if (h < 1 || w < 1 || (long long)samples * h > 4096 || (long long)samples * w > 4096)
+    return fail(ctx, MP_ERR_ARG, "%s: h, w >= 1 and samples * h, samples * w in 1..4096, got %d x %d at %d samples", who,
+                h, w, samples);
+  if (nearest != MP_NEAREST_MAX_Z && nearest != MP_NEAREST_MIN_Z)
+    return fail(ctx, MP_ERR_ARG, "%s: nearest must be MP_NEAREST_MAX_Z / _MIN_Z, got %d", who, nearest);
+  if (!image_out && !depth_out && !face_out && !mask_out && !coverage)
+    return fail(ctx, MP_ERR_ARG, "%s: no output is asked for", who);
+  if (image_out && !image) return fail(ctx, MP_ERR_ARG, "%s: image_out needs image", who);
+  if ((depth_out || face_out) && !(depth && face_id))
+    return fail(ctx, MP_ERR_ARG, "%s: depth_out and face_out need depth and face_id", who);
+  if (mask_out && !mask) return fail(ctx, MP_ERR_ARG, "%s: mask_out needs mask", who);
+  if (coverage && !mask && !face_id) return fail(ctx, MP_ERR_ARG, "%s: coverage needs mask or face_id", who);
+  int rc = check_frames(ctx, who, n_frames, nullptr, image, depth, face_id, image_out, depth_out, face_out, coverage);
+  if (rc != MP_OK) return rc;
+  for (int f = 0; f < n_frames; ++f)  // bytes: no alignment asked
+    if ((mask && !mask[f]) || (mask_out && !mask_out[f]))
+      return fail(ctx, MP_ERR_ARG, "%s: null buffer for frame %d", who, f);
+  const size_t coarse = (size_t)n_views * h * w, fine = coarse * samples * samples;
+  const FrameSpans ins[4] = {{image, fine * 12}, {depth, fine * 4}, {face_id, fine * 4}, {mask, fine}};
+  const FrameSpans outs[5] = {
+      {image_out, coarse * 12}, {depth_out, coarse * 4}, {face_out, coarse * 4}, {mask_out, coarse}, {coverage, coarse * 4}};
+  rc = check_no_alias(ctx, who, n_frames, outs, ins);
+  if (rc != MP_OK) return rc;
+  DeviceGuard g(ctx->device);
+  return launch_picture_resolve_batch(ctx, n_frames, n_views, image, depth, face_id, mask, h, w, samples, nearest,
+                                      image_out, depth_out, face_out, mask_out, coverage, (hipStream_t)stream);
+}
+
 static int picture_shadow_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *image_in,
                                   const float *const *position, const int32_t *const *face_id, int64_t n_pixels,
                                   const float *const *map_depth, const int32_t *const *map_face, int hs, int ws,
@@ -2078,6 +2117,25 @@ int mp_picture_composite_batch(mp_ctx *ctx, int n_frames, const float *const *fr
   return picture_composite_checked(ctx, "mp_picture_composite_batch", n_frames, front_image, front_depth, front_face,
                                    back_image, back_depth, back_face, n_pixels, mode, nearest, background, image, depth,
                                    mask, stream);
+}
+
+int mp_picture_resolve(mp_ctx *ctx, const float *image, const float *depth, const int32_t *face_id,
+                       const uint8_t *mask, int h, int w, int samples, int nearest, float *image_out, float *depth_out,
+                       int32_t *face_out, uint8_t *mask_out, float *coverage, mp_stream stream) {
+  return picture_resolve_checked(ctx, "mp_picture_resolve", 1, 1, image ? &image : nullptr, depth ? &depth : nullptr,
+                                 face_id ? &face_id : nullptr, mask ? &mask : nullptr, h, w, samples, nearest,
+                                 image_out ? &image_out : nullptr, depth_out ? &depth_out : nullptr,
+                                 face_out ? &face_out : nullptr, mask_out ? &mask_out : nullptr,
+                                 coverage ? &coverage : nullptr, stream);
+}
+
+int mp_picture_resolve_batch(mp_ctx *ctx, int n_frames, int n_views, const float *const *image,
+                             const float *const *depth, const int32_t *const *face_id, const uint8_t *const *mask,
+                             int h, int w, int samples, int nearest, float *const *image_out, float *const *depth_out,
+                             int32_t *const *face_out, uint8_t *const *mask_out, float *const *coverage,
+                             mp_stream stream) {
+  return picture_resolve_checked(ctx, "mp_picture_resolve_batch", n_frames, n_views, image, depth, face_id, mask, h, w,
+                                 samples, nearest, image_out, depth_out, face_out, mask_out, coverage, stream);
 }
 
 int mp_picture_shadow(mp_ctx *ctx, const float *image_in, const float *position, const int32_t *face_id,

@@ -485,6 +485,14 @@ int launch_picture_composite_batch(mp_ctx *ctx, int n_frames, const float *const
                                    const int32_t *const *back_face, long long n_pixels, int mode, int nearest,
                                    float background, float *const *image, float *const *depth, uint8_t *const *mask,
                                    hipStream_t st);
+// resolve.hip: the resolve of n_frames x n_views (<= kMaxFrames) supersampled pictures [samples h, samples w] to [h,w];
+// a frame's views lie back to back.  Every array: nullptr (the plane is not given / not wanted) or n_frames entries.
+// samples 2..4.  No scratch.
+int launch_picture_resolve_batch(mp_ctx *ctx, int n_frames, int n_views, const float *const *image,
+                                 const float *const *depth, const int32_t *const *face_id, const uint8_t *const *mask,
+                                 int h, int w, int samples, int nearest, float *const *image_out,
+                                 float *const *depth_out, int32_t *const *face_out, uint8_t *const *mask_out,
+                                 float *const *coverage, hipStream_t st);
 // scene.hip: the shadow of n_frames shadow maps [hs,ws] (depth, face ids: what the rasteriser wrote under each frame's
 // light, light_calibs: host, 12 floats per frame) on n_frames pictures of n_pixels each.  image_in / image_out: both
 // nullptr or both n_frames entries (image_out[f] may be image_in[f]); shade: nullptr or n_frames entries.  radius 0..3

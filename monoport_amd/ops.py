@@ -1543,21 +1543,62 @@ def _render_clip(who, projection, near, perspective_correct):
     return near, (_lib.RENDER_PERSPECTIVE_CORRECT if perspective_correct else 0)
 
 
-Raster = collections.namedtuple("Raster", ["res", "projection", "nearest", "background", "near", "perspective_correct"])
-Raster.__doc__ = """How the rasteriser draws whatever it is given, validated by ``raster``: the size (H, W), the
-projection, which depth is in front, what uncovered pixels hold, and the near plane with its interpolation (None and
-False: the unclipped call).  Every pass of one picture -- colours, positions, normals, transfer, the scene -- takes the
-same record."""
+RESOLVE_MAX_SAMPLES = 4  # mp_picture_resolve: samples in 2..4 (1: no resolve)
 
 
-def raster(who, res, projection="orthogonal", nearest="max", background=1.0, near=None, perspective_correct=False):
+class Raster(collections.namedtuple("Raster", ["res", "projection", "nearest", "background", "near",
+                                               "perspective_correct"])):
+    """How the rasteriser draws whatever it is given, validated by ``raster``: the size (H, W), the projection, which
+    depth is in front, what uncovered pixels hold, and the near plane with its interpolation (None and False: the
+    unclipped call).  Every pass of one picture -- colours, positions, normals, transfer, the scene -- takes the same
+    record.  ``samples`` (1, the default: none) is the anti-aliasing of the FINAL picture: the passes then run under
+    ``fine_raster`` of the record, at ``samples`` times ``res``, and ``picture_resolve_batch`` brings the result back
+    to ``res``.  It is the record's last field but not one of the tuple's: the record still unpacks and compares as
+    the six arguments of a pass, which is all a pass reads."""
+
+    def __new__(cls, res, projection, nearest, background, near, perspective_correct, samples=1):
+        self = super().__new__(cls, res, projection, nearest, background, near, perspective_correct)
+        self.samples = samples
+        return self
+
+    def _replace(self, samples=None, **kwargs):
+        return type(self)(*super()._replace(**kwargs), samples=self.samples if samples is None else samples)
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + ", samples=%r)" % self.samples
+
+
+def _samples(who, samples):
+    """``samples`` of a render call: an int in 1..RESOLVE_MAX_SAMPLES."""
+    if (isinstance(samples, bool) or not isinstance(samples, (int, np.integer))
+            or not 1 <= samples <= RESOLVE_MAX_SAMPLES):
+        raise ValueError("%s: samples must be an int in 1..%d, got %r" % (who, RESOLVE_MAX_SAMPLES, samples))
+    return int(samples)
+
+
+def raster(who, res, projection="orthogonal", nearest="max", background=1.0, near=None, perspective_correct=False,
+           samples=1):
     """The ``Raster`` of a render call's arguments, or the ValueError of the first one it refuses."""
     res = _render_size(who, res)
     _projection(projection), _nearest(nearest)
     if near is not None or perspective_correct:
         _render_clip(who, projection, near, perspective_correct)
+    samples = _samples(who, samples)
+    if samples * max(res) > RENDER_MAX_SIZE:
+        raise ValueError("%s: samples = %d renders %d x %d at %d x %d, outside 1..%d"
+                         % (who, samples, res[0], res[1], samples * res[0], samples * res[1], RENDER_MAX_SIZE))
     return Raster(res, projection, nearest, float(background), None if near is None else float(near),
-                  bool(perspective_correct))
+                  bool(perspective_correct), samples)
+
+
+def fine_raster(ras):
+    """THE record under which every pass of a picture of ``ras`` runs: ``ras`` itself without anti-aliasing, else the
+    same camera, plane and background at ``ras.samples`` times the size -- pixel (s i + a, s j + b) of it is sample
+    (a, b) of pixel (i, j), because a vertex lands at (x + 1) * 0.5 * H pixels.  The near-plane clip and the 2^22 snap
+    guard act at that size; a light's shadow map keeps its own."""
+    if ras.samples == 1:
+        return ras
+    return ras._replace(res=(ras.samples * ras.res[0], ras.samples * ras.res[1]), samples=1)
 
 
 def _mesh_render(who, verts, faces, counts, attrs, calibs, res, projection, nearest, channel_major, scale, bias, lo, hi,
@@ -1948,6 +1989,85 @@ def picture_composite_batch(fronts, backs, mode="depth", nearest="max", backgrou
             _ptr_array(image[f0:f1]), None if depth is None else _ptr_array(depth[f0:f1]),
             None if mask is None else _ptr_array(mask[f0:f1]), _stream(fronts[0][2])), "mp_picture_composite_batch")
     return [(image[f], None if depth is None else depth[f], None if mask is None else mask[f]) for f in range(n)]
+
+
+def picture_resolve_batch(images, depths, faces, masks, samples, nearest="max", out=None,
+                          who="picture_resolve_batch"):
+    """mp_picture_resolve_batch: per frame the final picture of one rendered at ``samples`` (2..4) times its size.
+    ``images`` (float32 [n_views,s H,s W,3] per frame), ``depths`` (float32 [n_views,s H,s W]), ``faces`` (int32, the
+    same) and ``masks`` (uint8, the same: a composite's 0 / 1 / 2): each a list with one tensor per frame, or None; a
+    frame without a leading n_views ([s H,s W,...]) is one view.  Per output pixel over its s x s samples: the image is
+    their mean (sequential f32 additions in row-major sample order, one division), ``coverage`` the fraction that is
+    the subject's (mask == 2, or face >= 0 without masks), depth and face those of the nearest sample that shows
+    (mask != 0, or face >= 0) under ``nearest`` ("max" / "min", as the renders take it; +0.0 and -1 where none does),
+    the mask the largest.  Defined bit for bit in include/monoport_hip.h.  Returns per frame (image, depth, face, mask,
+    coverage), each shaped as its frame's input at 1 / s the size, None for an output whose input is missing (image
+    needs ``images``; depth and face need ``depths`` and ``faces``; mask needs ``masks``; coverage needs ``masks`` or
+    ``faces``).  ``out``: None (fresh tensors for every output that can be made), or (images, depths, faces, masks,
+    coverages) to write into, each a list / [n, ...] tensor or None = not computed.  One launch per MAX_FRAMES
+    pictures (frames x views); no host sync."""
+    if (isinstance(samples, bool) or not isinstance(samples, (int, np.integer))
+            or not 2 <= samples <= RESOLVE_MAX_SAMPLES):
+        raise ValueError("%s: samples must be an int in 2..%d, got %r" % (who, RESOLVE_MAX_SAMPLES, samples))
+    s = int(samples)
+    near_mode = _nearest(nearest)
+    planes = [None if p is None else list(p) for p in (images, depths, faces, masks)]
+    lead = next((p for p in planes[1:] + planes[:1] if p is not None), None)
+    if lead is None or len(lead) == 0:
+        raise ValueError("%s: at least one frame of images, depths, faces or masks" % who)
+    n, dev = len(lead), lead[0].device
+    shape = tuple(lead[0].shape[:-1]) if lead is planes[0] else tuple(lead[0].shape)
+    if len(shape) not in (2, 3) or shape[-2] % s or shape[-1] % s or shape[-2] < s or shape[-1] < s:
+        raise ValueError("%s: pictures [n_views,s H,s W] or [s H,s W] with s = %d, got %s" % (who, s, shape))
+    nv, (h, w) = (shape[0] if len(shape) == 3 else 1), (shape[-2] // s, shape[-1] // s)
+    if s * h > RENDER_MAX_SIZE or s * w > RENDER_MAX_SIZE:
+        raise ValueError("%s: image size %d x %d outside 1..%d" % (who, s * h, s * w, RENDER_MAX_SIZE))
+    fine, small = nv * s * h * s * w, shape[:-2] + (h, w)
+    kinds = (("images", torch.float32, 3), ("depths", torch.float32, 1), ("faces", torch.int32, 1),
+             ("masks", torch.uint8, 1))
+    for k, (what, dtype, per) in enumerate(kinds):
+        if planes[k] is not None:
+            planes[k] = _flat_pictures(who, what, planes[k], n, dtype, per, fine, dev)
+    have = (planes[0] is not None, planes[1] is not None and planes[2] is not None,
+            planes[1] is not None and planes[2] is not None, planes[3] is not None,
+            planes[3] is not None or planes[2] is not None)
+    outs_of = (("image", torch.float32, 3), ("depth", torch.float32, 1), ("face", torch.int32, 1),
+               ("mask", torch.uint8, 1), ("coverage", torch.float32, 1))
+    if out is None:
+        outs = [torch.empty((n,) + small + ((3,) if per == 3 else ()), dtype=dtype, device=dev).unbind(0) if ok else None
+                for ok, (_, dtype, per) in zip(have, outs_of)]
+    else:
+        if len(out) != 5:
+            raise ValueError("%s: out is (images, depths, faces, masks, coverages), entries None = not computed" % who)
+        outs = []
+        for k, (ok, (what, dtype, per)) in enumerate(zip(have, outs_of)):
+            if out[k] is not None and not ok:
+                raise ValueError("%s: out[%d] (%s) needs its input" % (who, k, what))
+            outs.append(None if out[k] is None else
+                        _flat_pictures(who, "out[%d] (%s)" % (k, what), out[k], n, dtype, per, nv * h * w, dev))
+    if all(o is None for o in outs):
+        raise ValueError("%s: out names no output" % who)
+    ctx = get_context(dev)
+    vstep = min(nv, MAX_FRAMES)  # pictures of a call: frames x views <= MAX_FRAMES
+    fstep = MAX_FRAMES // vstep
+
+    def ptrs(rows, f0, f1, v0, per_view):
+        if rows is None:
+            return None
+        return _ptr_array([r.reshape(-1)[v0 * per_view:] for r in rows[f0:f1]])
+
+    for v0 in range(0, nv, vstep):
+        v1 = min(v0 + vstep, nv)
+        for f0 in range(0, n, fstep):
+            f1 = min(f0 + fstep, n)
+            ctx.check(ctx.lib.mp_picture_resolve_batch(
+                ctx.handle, f1 - f0, v1 - v0,
+                *[ptrs(p, f0, f1, v0, s * h * s * w * per) for p, (_, _, per) in zip(planes, kinds)],
+                h, w, s, near_mode,
+                *[ptrs(o, f0, f1, v0, h * w * per) for o, (_, _, per) in zip(outs, outs_of)],
+                _stream(lead[0])), "mp_picture_resolve_batch")
+    return [tuple(None if o is None else o[f].view(small + ((3,) if per == 3 else ()))
+                  for o, (_, _, per) in zip(outs, outs_of)) for f in range(n)]
 
 
 SHADOW_MAX_RADIUS = 3  # mp_picture_shadow: radius in 0..3

@@ -54,18 +54,27 @@ MESH_BATCH = 1 if _mb == "off" else min(int(_mb) if _mb.isdigit() and int(_mb) >
 MESH_KEYS = ("normals", "level", "colors", "clean", "simplify", "smooth")
 PICTURE_KEYS = ("views", "res", "shade", "projection", "nearest", "near", "perspective_correct", "background", "scene",
                 "composite")
+PICTURE_OPTION_KEYS = PICTURE_KEYS + ("samples",)  # what a ``pictures`` dict may hold
 
 
 class PictureOptions(collections.namedtuple("PictureOptions", PICTURE_KEYS, defaults=(None, "depth"))):
     """What a slot's free-viewpoint pictures are asked for, validated by ``_picture_options``: the cameras per frame,
     the size (H, W), the arguments of ``recon.render_mesh``, and the ``recon.Scene`` behind the subject (None: none)
-    with the ``composite`` mode ("depth" or "over") that puts the subject's picture over it."""
-    __slots__ = ()
+    with the ``composite`` mode ("depth" or "over") that puts the subject's picture over it.  ``samples`` (1: none), the
+    anti-aliasing of the final pictures, is the record's last option but rides beside the tuple's fields, as in
+    ``ops.Raster``: the tuple stays what one pass at ``res`` is asked for."""
+
+    def __new__(cls, *args, samples=1, **kwargs):
+        self = super().__new__(cls, *args, **kwargs)
+        self.samples = samples
+        return self
 
     @property
     def raster(self):
-        """The six fields every pass of the rasteriser takes, as the ``ops.Raster`` of the ``recon`` bodies."""
-        return ops.Raster(self.res, self.projection, self.nearest, self.background, self.near, self.perspective_correct)
+        """The fields every pass of the rasteriser takes and ``samples``, as the ``ops.Raster`` of the ``recon``
+        bodies."""
+        return ops.Raster(self.res, self.projection, self.nearest, self.background, self.near, self.perspective_correct,
+                          self.samples)
 
 
 def _mesh_options(mesh, balance, has_netc):
@@ -92,10 +101,10 @@ def _picture_options(pictures, mesh, has_netc=False):
     ``has_netc``: whether the slot runs a netC (``shade="netC"`` queries it per pixel).  Nothing is allocated here."""
     who = "FrameSlot(pictures=...)"
     if not isinstance(pictures, dict):
-        raise ValueError("%s: a dict with any of %s, got %r" % (who, list(PICTURE_KEYS), pictures))
-    unknown = sorted(set(pictures) - set(PICTURE_KEYS))
+        raise ValueError("%s: a dict with any of %s, got %r" % (who, list(PICTURE_OPTION_KEYS), pictures))
+    unknown = sorted(set(pictures) - set(PICTURE_OPTION_KEYS))
     if unknown:
-        raise ValueError("%s: unknown keys %s (known: %s)" % (who, unknown, list(PICTURE_KEYS)))
+        raise ValueError("%s: unknown keys %s (known: %s)" % (who, unknown, list(PICTURE_OPTION_KEYS)))
     if mesh is None:
         raise ValueError("%s: the pictures are of the slot's meshes; it needs mesh=..." % who)
     from .recon import SHADES
@@ -104,7 +113,7 @@ def _picture_options(pictures, mesh, has_netc=False):
         raise ValueError("%s: views must be an int >= 1, got %r" % (who, views))
     ras = ops.raster(who, pictures.get("res", 257), pictures.get("projection", "orthogonal"),
                      pictures.get("nearest", "max"), pictures.get("background", 1.0), pictures.get("near"),
-                     pictures.get("perspective_correct", False))
+                     pictures.get("perspective_correct", False), pictures.get("samples", 1))
     default = "colors" if mesh.colors else ("normals" if mesh.normals is not None else None)
     shade = pictures.get("shade", default)
     if shade not in SHADES:
@@ -125,7 +134,7 @@ def _picture_options(pictures, mesh, has_netc=False):
     if not isinstance(composite, str) or composite not in ops.COMPOSITE_MODES:
         raise ValueError("%s: composite must be one of %s, got %r" % (who, sorted(ops.COMPOSITE_MODES), composite))
     return PictureOptions(int(views), ras.res, shade, ras.projection, ras.nearest, ras.near, ras.perspective_correct,
-                          ras.background, scene, composite)
+                          ras.background, scene, composite, samples=ras.samples)
 
 
 class FrameSlot:
@@ -163,8 +172,9 @@ class FrameSlot:
         ``near``, ``perspective_correct``, ``background`` as ``recon.render_mesh`` takes them.  It needs ``mesh``.
         ``self.picture_options`` is the validated ``PictureOptions`` (None without pictures).  ``submit`` then takes
         ``cameras``, the pictures are rendered behind the mesh chain on the slot's stream, with no host value in
-        between (``_render_pictures``: what is enqueued is written once, in ``recon._subject_pictures`` and
-        ``recon._scene_pictures``, and this docstring only names the buffers), and ``pictures()`` hands the results out:
+        between (``_render_pictures``: what is enqueued is written once, in ``recon._resolved_pictures`` and the two
+        bodies it runs, ``recon._subject_pictures`` and ``recon._scene_pictures``, and this docstring only names the
+        buffers), and ``pictures()`` hands the results out:
         the static ``pictures_image`` [batch,views,H,W,3] (None with ``shade=None``), ``pictures_depth`` and
         ``pictures_face`` [batch,views,H,W].  ``shade="netC"`` colours the
         pictures per pixel (``recon.render_mesh(shade="netC")``): it needs the slot's ``netC`` but NOT the mesh's
@@ -180,7 +190,18 @@ class FrameSlot:
         scene, the option keys do not change) also shows each frame's shadow on it: the slot then owns
         ``shadow_depth`` / ``shadow_face`` [batch,Hs,Ws] (the frames' shadow maps), ``scene_pos`` (the scene's
         world-space positions) and ``scene_lit`` (the shadowed scene, which the composite takes; ``scene_image`` stays
-        unshadowed).  Without a light none of them exists and nothing more is enqueued.
+        unshadowed).  Without a light none of them exists and nothing more is enqueued.  ``samples`` (1, the default:
+        nothing is allocated or enqueued for it, and ``pictures_coverage`` is None) anti-aliases the pictures as
+        ``recon.render_mesh(samples=)`` does: with s in 2..4 every pass and the composite run at s times ``res`` (s * res
+        may not exceed 4096) in working buffers of that size -- ``fine_image`` / ``fine_depth`` / ``fine_face`` /
+        ``fine_mask`` for the subject and the composite, and the ``scene_*``, ``light_*`` buffers and the ``shade="netC"``
+        lists above, all s * s times their size --, and ONE resolve, enqueued behind the composite (behind the lighting
+        without a scene) on the slot's stream, fills ``pictures_image`` / ``pictures_depth`` / ``pictures_face`` /
+        ``pictures_mask``, which stay [batch,views,H,W,...], and ``pictures_coverage`` [batch,views,H,W] f32, the
+        subject's alpha; ``pictures()`` then returns ``recon.ResolvedPicture``s and ``jpegs()`` encodes the resolved
+        image.  Memory: the per-pixel bytes above times s * s (20 bytes per pixel of subject and composite, 44 of the
+        scene, 28 of the netC lists, ...: at 1024^2, one view and s = 2 the subject and scene alone grow from 64 to
+        256 MB per frame) plus 25 bytes per final pixel; ``shade="netC"`` queries s * s times the points.
 
         ``lighting`` (a ``recon.Lighting``; None, the default: nothing is allocated or enqueued for it, and it is not a
         ``pictures`` key) lights the subject's picture per pixel before the composite, as ``recon.render_mesh(lighting=)``
@@ -287,25 +308,34 @@ class FrameSlot:
             self._mesh_chains = [None] * b
             self._reran = []  # frames whose chain ``meshes()`` made again with exact capacities
         self.pictures_image = self.pictures_depth = self.pictures_face = self.pictures_mask = None
+        self.pictures_coverage = None
         if self.picture_options is not None:
             po = self.picture_options
-            if po.shade is not None:
-                self.pictures_image = torch.empty((b, po.views) + po.res + (3,), dtype=torch.float32, device=dev)
-            self.pictures_depth = torch.empty((b, po.views) + po.res, dtype=torch.float32, device=dev)
-            self.pictures_face = torch.empty((b, po.views) + po.res, dtype=torch.int32, device=dev)
+            fres = ops.fine_raster(po.raster).res  # the size every pass runs at: ``samples`` times ``res``
+
+            def pictures(res, mask):
+                shape = (b, po.views) + res
+                return (None if po.shade is None else torch.empty(shape + (3,), dtype=torch.float32, device=dev),
+                        torch.empty(shape, dtype=torch.float32, device=dev),
+                        torch.empty(shape, dtype=torch.int32, device=dev),
+                        torch.empty(shape, dtype=torch.uint8, device=dev) if mask else None)
+            if po.samples > 1:  # the passes work in fine_*; the resolve fills pictures_*
+                self.fine_image, self.fine_depth, self.fine_face, self.fine_mask = pictures(fres, po.scene is not None)
+                self.pictures_coverage = torch.empty((b, po.views) + po.res, dtype=torch.float32, device=dev)
+            (self.pictures_image, self.pictures_depth, self.pictures_face,
+             self.pictures_mask) = pictures(po.res, po.scene is not None)
             if po.shade == "netC":  # the covered pixels of a frame's views as one counted list
-                n_pix = po.views * po.res[0] * po.res[1]
+                n_pix = po.views * fres[0] * fres[1]
                 self.picture_lists = {"points": torch.zeros((b, 3, n_pix), dtype=torch.float32, device=dev),
                                       "pixels": torch.zeros((b, n_pix), dtype=torch.int32, device=dev),
                                       "preds": torch.zeros((b, 3, n_pix), dtype=torch.float32, device=dev),
                                       "count": torch.zeros((b, 2), dtype=torch.int32, device=dev)}
-            if po.scene is not None:  # the scene's own pictures (44 bytes per pixel) and the composite's mask
-                shape = (b, po.views) + po.res
+            if po.scene is not None:  # the scene's own pictures (44 bytes per pixel); the composite's mask is above
+                shape = (b, po.views) + fres
                 self.scene_uv = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
                 self.scene_image = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
                 self.scene_depth = torch.empty(shape, dtype=torch.float32, device=dev)
                 self.scene_face = torch.empty(shape, dtype=torch.int32, device=dev)
-                self.pictures_mask = torch.empty(shape, dtype=torch.uint8, device=dev)
                 if po.scene.light is not None:  # the subjects' shadow maps, the scene's positions and its lit image
                     hs, ws = po.scene.light.res
                     self.shadow_depth = torch.empty((b, hs, ws), dtype=torch.float32, device=dev)
@@ -313,7 +343,7 @@ class FrameSlot:
                     self.scene_pos = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
                     self.scene_lit = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
             if self.lighting is not None:  # the normal pass and, for the self-shadow, the subject's positions and shade
-                shape = (b, po.views) + po.res
+                shape = (b, po.views) + fres
                 self.light_normal = torch.empty(shape + (3,), dtype=torch.float32, device=dev)
                 self.light_face = torch.empty(shape, dtype=torch.int32, device=dev)
                 if self.lighting.self_shadow is not None:
@@ -480,11 +510,11 @@ class FrameSlot:
         its bits under the lighting.  With ``lighting.transfer`` the transfer of the n frames' vertices is traced
         first, through the bits the mesh chain packed.  The shadowed scene goes to ``scene_lit``; ``scene_image``
         stays unshadowed for ``_rerun_picture``."""
-        from .recon import _chain_subjects, _scene_pictures, _shadow_maps, _subject_pictures
+        from .recon import _chain_subjects, _resolved_pictures, _shadow_maps
         po, chains, cams = self.picture_options, self._mesh_chains[:n], list(self._cameras[:n])
         light = po.scene.light if hasattr(self, "scene_lit") else None
-        out = {"image": None if self.pictures_image is None else self.pictures_image[:n],
-               "depth": self.pictures_depth[:n], "face": self.pictures_face[:n]}
+        image, depth, face, mask = self._working_pictures()
+        out = {"image": None if image is None else image[:n], "depth": depth[:n], "face": face[:n]}
         if po.shade == "netC":
             out["lists"] = tuple(self.picture_lists[k][:n] for k in ("points", "pixels", "count"))
         transfers = None
@@ -498,14 +528,23 @@ class FrameSlot:
         subjects = _chain_subjects(chains, po.shade, transfers)
         maps = None if light is None else _shadow_maps("FrameSlot", subjects, light,
                                                        (self.shadow_depth[:n], self.shadow_face[:n]))
-        fronts = _subject_pictures("FrameSlot", subjects, cams, po.raster, po.shade,
-                                   self._picture_colours(n) if po.shade == "netC" else None, self.lighting,
-                                   None if light is None else (light,) + maps, out)
         if po.scene is not None:  # the scene under the same cameras, then the composite in place
-            names = ("scene_image", "scene_depth", "scene_face", "scene_uv", "scene_pos", "scene_lit", "pictures_image",
-                     "pictures_depth", "pictures_mask")
-            _scene_pictures("FrameSlot", po.scene, cams, po.raster, maps, fronts, po.composite,
-                            {k: getattr(self, k)[:n] for k in names if hasattr(self, k)})
+            names = ("scene_image", "scene_depth", "scene_face", "scene_uv", "scene_pos", "scene_lit")
+            out.update({k: getattr(self, k)[:n] for k in names if hasattr(self, k)})
+            out.update(pictures_image=image[:n], pictures_depth=depth[:n], pictures_mask=mask[:n])
+        if po.samples > 1:  # the resolve, behind the composite (the lighting without a scene), into the pictures_*
+            out["resolved"] = tuple(None if t is None else t[:n] for t in (
+                self.pictures_image, self.pictures_depth, self.pictures_face, self.pictures_mask, self.pictures_coverage))
+        _resolved_pictures("FrameSlot", subjects, cams, po.raster, po.shade,
+                           self._picture_colours(n) if po.shade == "netC" else None, self.lighting,
+                           None if light is None else (light,) + maps, po.scene, maps, po.composite, out=out)
+
+    def _working_pictures(self):
+        """(image, depth, face, mask) that the passes and the composite write: the ``pictures_*`` themselves, or with
+        ``samples`` > 1 the ``fine_*`` at ``samples`` times the size, which the resolve then reads."""
+        if self.picture_options.samples > 1:
+            return self.fine_image, self.fine_depth, self.fine_face, self.fine_mask
+        return self.pictures_image, self.pictures_depth, self.pictures_face, self.pictures_mask
 
     def _trace(self, chains, bits, out):
         """The radiance transfer [cap,9] of the chains' vertices through their frames' ``bits`` (``out``: into it)."""
@@ -537,14 +576,21 @@ class FrameSlot:
         because both paths query netC at the same points.  No slot has overflowed 12 r^2 / 24 r^2 so far.  With a
         ``scene`` every entry is a ``recon.ScenePicture`` (image, depth, face, mask) of the subject composited over the
         scene -- the bare scene where ``meshes()`` gives None --, and a re-rendered frame is composited again over the
-        slot's own picture of the scene."""
+        slot's own picture of the scene.  With ``samples`` > 1 every entry is a ``recon.ResolvedPicture`` (image, depth,
+        face, mask -- None without a scene --, coverage), views of the resolved ``pictures_*`` buffers; a re-rendered
+        frame goes through the same fine passes and its own resolve."""
         if self.picture_options is None:
             raise RuntimeError("FrameSlot.pictures(): the slot was made without pictures=...")
-        from .recon import MeshRender, ScenePicture
+        from .recon import MeshRender, ResolvedPicture, ScenePicture
         out = []
         for b, mesh in enumerate(self.meshes()):
             if mesh is not None and b in self._reran:
                 out.append(self._rerun_picture(b, self._with_transfer(b, mesh)))
+            elif self.picture_options.samples > 1:
+                out.append(None if mesh is None and self.picture_options.scene is None else ResolvedPicture(
+                    None if self.pictures_image is None else self.pictures_image[b], self.pictures_depth[b],
+                    self.pictures_face[b], None if self.pictures_mask is None else self.pictures_mask[b],
+                    self.pictures_coverage[b]))
             elif self.picture_options.scene is not None:
                 out.append(ScenePicture(self.pictures_image[b], self.pictures_depth[b], self.pictures_face[b],
                                         self.pictures_mask[b]))
@@ -614,8 +660,8 @@ class FrameSlot:
         """Frame b again from its re-run ``Mesh``, into fresh tensors: the bodies of ``_render_pictures`` on the
         subjects of ``[mesh]`` with ``out=None`` -- netC bound to the slot's own maps, the shadow map made afresh for
         this mesh, and the slot's own unshadowed picture of the scene (and its positions) as the back picture."""
-        from .recon import (MeshRender, ScenePicture, _counted_colours, _mesh_subjects, _scene_pictures, _shadow_maps,
-                            _subject_pictures)
+        from .recon import (MeshRender, ResolvedPicture, ScenePicture, _counted_colours, _mesh_subjects,
+                            _resolved_pictures, _shadow_maps)
         po, who, cams = self.picture_options, "FrameSlot.pictures", [self._cameras[b]]
         subjects = _mesh_subjects(who, [mesh], po.shade, self.lighting)
         colours = None
@@ -626,15 +672,19 @@ class FrameSlot:
                 return _counted_colours(bindings, pts, counts, view=self.view)
         light = po.scene.light if hasattr(self, "scene_lit") else None
         maps = None if light is None else _shadow_maps(who, subjects, light)
-        front = _subject_pictures(who, subjects, cams, po.raster, po.shade, colours, self.lighting,
-                                  None if light is None else (light,) + maps)[0]
+        back = None
+        if po.scene is not None:
+            back = ([self.scene_image[b]], [self.scene_depth[b]], [self.scene_face[b]],
+                    None if light is None else [self.scene_pos[b]])
+        fronts, done, resolved = _resolved_pictures(who, subjects, cams, po.raster, po.shade, colours, self.lighting,
+                                                    None if light is None else (light,) + maps, po.scene, maps,
+                                                    po.composite, back=back)
+        if resolved is not None:
+            return ResolvedPicture(*resolved[0])
         if po.scene is None:
-            return MeshRender(*front)
-        back = ([self.scene_image[b]], [self.scene_depth[b]], [self.scene_face[b]],
-                None if light is None else [self.scene_pos[b]])
-        image, depth, mask = _scene_pictures(who, po.scene, cams, po.raster, maps, [front], po.composite,
-                                             back=back)[1][0]
-        return ScenePicture(image, depth, front[2], mask)
+            return MeshRender(*fronts[0])
+        image, depth, mask = done[0]
+        return ScenePicture(image, depth, fronts[0][2], mask)
 
     def _slot_cameras(self, cameras, n):
         """``submit``'s cameras ([n,views,>=3,4], or [views,>=3,4] / [>=3,4] shared by all frames; tensor or array)

@@ -534,7 +534,7 @@ def _single_camera(calibs):
 @torch.no_grad()
 def render_mesh(mesh, calibs, res=257, shade="colors", projection="orthogonal", nearest="max", background=1.0,
                 near=None, perspective_correct=False, netC=None, feat_tensor_C=None, calib_tensor=None, view=None,
-                lighting=None):
+                samples=1, lighting=None):
     """The z-buffered picture of a ``Mesh`` on the device (monoport_amd extension; ``ops.mesh_render_raw``): any camera
     ``calibs`` ([4,4] / [3,4], the convention of the queries; or [n_views, ...] for several pictures in one set of
     launches), any size ``res`` (int or (H, W)).  ``shade``: "colors" (the mesh's colours), "normals" (its normals * 0.5
@@ -559,7 +559,19 @@ def render_mesh(mesh, calibs, res=257, shade="colors", projection="orthogonal", 
     ``ops.picture_light_batch`` in place: clamp(albedo * shading, 0, 1) at the covered pixels, where the albedo is the
     picture's own colours (``shade="colors"`` / ``"netC"``) or the lighting's constant ``albedo`` (``shade="normals"``).
     ``shade=None``, ``shade="normals"`` without a constant albedo, a mesh without normals and a ``self_shadow`` (which
-    needs a scene's light: ``render_mesh_many_in_scene``) are ValueErrors raised before anything is enqueued."""
+    needs a scene's light: ``render_mesh_many_in_scene``) are ValueErrors raised before anything is enqueued.
+
+    ``samples`` (1, the default: exactly the calls and tensors above): s in 2..4 anti-aliases the picture.  Every pass
+    -- the shade, the positions of ``shade="netC"``, the normals and transfer of ``lighting`` -- runs under the same
+    camera at s times ``res`` (s * res may not exceed 4096; the near-plane clip and the 2^22 snap guard act at that
+    size), which samples every pixel on a regular s x s grid, and ``ops.picture_resolve_batch`` averages once at the
+    end: one launch more.  Returns a ``ResolvedPicture`` (image, depth, face, mask None, coverage = the subject's
+    alpha): bit for bit the resolve, as include/monoport_hip.h defines it, of this call at ``res * s``.  The working
+    pictures cost s * s times the memory, and ``shade="netC"`` queries every covered fine sample: s * s times the
+    points.  A ``samples`` outside 1..4 and an s * res beyond 4096 are ValueErrors raised before anything is
+    enqueued."""
+    if type(samples) is not int or samples != 1:  # refused here also for ``mesh is None``
+        ops.raster("render_mesh", res, projection, nearest, background, near, perspective_correct, samples)
     _check_shade_netC("render_mesh", shade, netC, view)
     if lighting is not None:
         _check_lighting("render_mesh", lighting, shade, [mesh], None)
@@ -567,13 +579,13 @@ def render_mesh(mesh, calibs, res=257, shade="colors", projection="orthogonal", 
         return None
     return render_mesh_many([mesh], calibs, res, shade, projection, nearest, background, near, perspective_correct,
                             netC=netC, feat_tensors_C=[feat_tensor_C], calib_tensors=[calib_tensor], view=view,
-                            lighting=lighting)[0]
+                            lighting=lighting, samples=samples)[0]
 
 
 @torch.no_grad()
 def render_mesh_many(meshes, calibs, res=257, shade="colors", projection="orthogonal", nearest="max", background=1.0,
                      near=None, perspective_correct=False, netC=None, feat_tensors_C=None, calib_tensors=None,
-                     view=None, lighting=None):
+                     view=None, samples=1, lighting=None):
     """``[render_mesh(m, calibs, ...) for m in meshes]`` in one set of launches per ops.MAX_FRAMES pictures (meshes x
     views), the same bits.  ``calibs``: one camera set for all meshes (a tensor / array), or a list with one camera set
     per mesh (those of ``None`` meshes are not looked at; all of one n_views).  ``None`` meshes give ``None``.  The
@@ -582,11 +594,14 @@ def render_mesh_many(meshes, calibs, res=257, shade="colors", projection="orthog
     as in ``render_mesh``: one plane for all.  With ``shade="netC"``: ``feat_tensors_C`` / ``calib_tensors`` hold one
     entry per mesh (those of ``None`` meshes are not looked at), and the colour query of all meshes is one counted
     launch per ops.MAX_FRAMES meshes (``ops.max_view_frames(V)`` with ``view``).  ``lighting``: as in ``render_mesh``,
-    one for all meshes; the normal pass and the lighting are one set of launches per ops.MAX_FRAMES pictures more.  No
-    host sync."""
-    ras = ops.raster("render_mesh_many", res, projection, nearest, background, near, perspective_correct)
-    raws, cams, _ = _render_mesh_many("render_mesh_many", meshes, calibs, ras, shade, netC, feat_tensors_C,
-                                      calib_tensors, view, lighting)
+    one for all meshes; the normal pass and the lighting are one set of launches per ops.MAX_FRAMES pictures more.
+    ``samples``: as in ``render_mesh`` -- 1 changes nothing; 2..4 give ``ResolvedPicture``s, every pass at ``samples``
+    times ``res`` and one resolve per ops.MAX_FRAMES pictures at the end (``_resolved_pictures``).  No host sync."""
+    ras = ops.raster("render_mesh_many", res, projection, nearest, background, near, perspective_correct, samples)
+    raws, cams, _, resolved = _render_mesh_many("render_mesh_many", meshes, calibs, ras, shade, netC, feat_tensors_C,
+                                                calib_tensors, view, lighting)
+    if resolved is not None:
+        return [None if pic is None else ResolvedPicture(*_squeezed(pic, cam)) for pic, cam in zip(resolved, cams)]
     return [None if raw is None else MeshRender(*_squeezed(raw, cam)) for raw, cam in zip(raws, cams)]
 
 
@@ -595,13 +610,17 @@ def _squeezed(tensors, cam):
     return tuple(None if t is None else t[0] for t in tensors) if _single_camera(cam) else tensors
 
 
-def _render_mesh_many(who, meshes, calibs, ras, shade, netC, feat_tensors_C, calib_tensors, view, lighting, light=None):
-    """``render_mesh_many`` under the ``ops.Raster`` ``ras`` -> (per mesh the raw picture (image, depth, face; each
-    [n_views, ...]) or None, per mesh its camera set, the shadow maps).  ``light``: None, or the scene's ``Light``: the
-    live meshes' shadow maps under it are rendered first (``_shadow_maps``), for the lighting's ``self_shadow`` and for
-    the caller's scene, and returned as (depths, faces), one entry per mesh, an uncovered map for a None."""
+def _render_mesh_many(who, meshes, calibs, ras, shade, netC, feat_tensors_C, calib_tensors, view, lighting, scene=None,
+                      composite="depth", who_scene=None):
+    """``render_mesh_many`` under the ``ops.Raster`` ``ras``, through ``_resolved_pictures`` -> what that returns, with
+    the camera sets: (per mesh the raw picture (image, depth, face; each [n_views, ...]) or None, per mesh its camera
+    set, the composites or None, the resolved pictures or None).  ``scene``: None, or the ``Scene`` behind the meshes
+    (``render_mesh_many_in_scene``, which names itself in ``who_scene``): a None mesh then gives an uncovered picture
+    over the bare scene, and under the scene's ``Light`` the live meshes' shadow maps are rendered first
+    (``_shadow_maps``), for the lighting's ``self_shadow`` and for the scene, an uncovered map for a None mesh."""
     _check_shade_netC(who, shade, netC, view)
     meshes = list(meshes)
+    light = None if scene is None else scene.light
     if lighting is not None:
         _check_lighting(who, lighting, shade, meshes, light)
     if netC is not None:
@@ -611,28 +630,89 @@ def _render_mesh_many(who, meshes, calibs, ras, shade, netC, feat_tensors_C, cal
             raise ValueError("%s: %d meshes, %d feature sets, %d calibrations"
                              % (who, len(meshes), len(feat_tensors_C), len(calib_tensors)))
     idx = [i for i, m in enumerate(meshes) if m is not None]
-    raws = [None] * len(meshes)
-    if not idx:
-        return raws, list(raws), None
+    if not idx and scene is None:
+        return [None] * len(meshes), [None] * len(meshes), None, None
     cams = _camera_sets(who, calibs, len(meshes), "meshes")
-    colours = None
-    if netC is not None:
-        bindings = _bind_netC(who, netC, [(feat_tensors_C[i], calib_tensors[i], meshes[i].verts.device) for i in idx],
-                              view)
+    colours = subjects = maps = shadow = None
+    if idx:
+        if netC is not None:
+            bindings = _bind_netC(who, netC,
+                                  [(feat_tensors_C[i], calib_tensors[i], meshes[i].verts.device) for i in idx], view)
 
-        def colours(pts, counts):
-            return _counted_colours(bindings, pts, counts, view=view or 0)
-    subjects = _mesh_subjects(who, [meshes[i] for i in idx], shade, lighting)
-    maps = shadow = None
-    if light is not None:  # a None mesh casts no shadow
-        shadow = (light,) + _shadow_maps(who, subjects, light)
-        maps = tuple([hole] * len(meshes) for hole in _uncovered_map(light, subjects.verts[0].device))
-        for k, i in enumerate(idx):
-            maps[0][i], maps[1][i] = shadow[1][k], shadow[2][k]
-    live = _subject_pictures(who, subjects, [cams[i] for i in idx], ras, shade, colours, lighting, shadow)
-    for i, raw in zip(idx, live):
-        raws[i] = raw
-    return raws, cams, maps
+            def colours(pts, counts):
+                return _counted_colours(bindings, pts, counts, view=view or 0)
+        subjects = _mesh_subjects(who, [meshes[i] for i in idx], shade, lighting)
+        if light is not None:  # a None mesh casts no shadow
+            shadow = (light,) + _shadow_maps(who, subjects, light)
+            maps = tuple([hole] * len(meshes) for hole in _uncovered_map(light, subjects.verts[0].device))
+            for k, i in enumerate(idx):
+                maps[0][i], maps[1][i] = shadow[1][k], shadow[2][k]
+    fronts, done, resolved = _resolved_pictures(who, subjects, cams, ras, shade, colours, lighting, shadow, scene, maps,
+                                                composite, live=idx, who_scene=who_scene)
+    return fronts, cams, done, resolved
+
+
+ResolvedPicture = collections.namedtuple("ResolvedPicture", ["image", "depth", "face", "mask", "coverage"])
+ResolvedPicture.__doc__ = """An anti-aliased picture (``samples`` > 1; ``resolve_picture``): every pixel is the box of the
+s x s samples that the passes took inside it.  image [H,W,3] f32 = their mean (None with ``shade=None``), depth [H,W] f32
+and face [H,W] int32 = those of the nearest sample that shows (+0.0 and -1 where none does; with a scene the face is the
+subject's, -1 where the scene is nearest), mask [H,W] uint8 = the largest of the composite's 0 / 1 / 2 (None without a
+scene), coverage [H,W] f32 = the fraction of the samples that is the subject's: its alpha, and ``image - (1 - coverage) *
+background`` the premultiplied subject (without a scene).  With a set of cameras each has a leading [n_views]."""
+
+
+def _resolved_pictures(who, subjects, cams, ras, shade, colours=None, lighting=None, shadow=None, scene=None, maps=None,
+                       composite="depth", live=None, out=None, back=None, who_scene=None):
+    """THE pictures under the ``ops.Raster`` ``ras`` with its ``samples``, for the render calls, a slot and a slot's
+    re-run alike; the one place that knows about supersampling.  Every pass runs under ``ops.fine_raster(ras)`` -- at
+    ``samples`` times ``ras.res``, under the same cameras -- through the two bodies below, and the resolve runs once at
+    the end: (1) ``_subject_pictures`` of ``subjects`` (None: no subject at all) under the camera sets ``cams[i]`` for
+    i in ``live`` (None: every one); (2) with a ``scene``: ``_scene_pictures`` under all of ``cams`` -- the bare scene
+    without subjects, else the composite, a picture outside ``live`` being an uncovered one of the scene's size;
+    (3) ``ras.samples`` > 1: ``ops.picture_resolve_batch`` of the composites (image, depth and mask theirs, the face
+    ids the subject's), else of the scene's, else of the live subjects' pictures.  -> (per camera set the subject's
+    raw picture or None, per camera set the composite (image, depth, mask) or the bare scene's raw picture or None
+    without a scene, per camera set the resolved (image, depth, face, mask, coverage) or None with ``samples`` = 1 --
+    then nothing is enqueued or allocated beyond (1) and (2)).  ``shade="netC"`` queries every covered FINE sample:
+    ``samples``^2 times the points.  ``out``: None, or the caller's buffers: the keys of ``_subject_pictures`` and
+    ``_scene_pictures`` at the fine size, and ``resolved`` = (image, depth, face, mask, coverage) at ``ras.res``, each
+    [n, ...] or None.  ``back``: as in ``_scene_pictures``, at the fine size."""
+    fine, out, n, who_scene = ops.fine_raster(ras), out or {}, len(cams), who_scene or who
+    bare = subjects is None and live is None  # the scene alone: nothing is composited
+    live = list(range(n)) if live is None else list(live)
+    fronts, done = [None] * n, None
+    if subjects is not None:
+        for i, raw in zip(live, _subject_pictures(who, subjects, [cams[i] for i in live], fine, shade, colours,
+                                                  lighting, shadow, out)):
+            fronts[i] = raw
+    if scene is not None and bare:
+        done = _scene_pictures(who_scene, scene, cams, fine, maps, out=out, back=back)[0]
+    elif scene is not None:
+        nv = ops._view_calibs(who_scene, cams[0]).shape[0]
+        for i in range(n):
+            if fronts[i] is None:  # no subject: an uncovered picture of the scene's size
+                shape, dev = (nv,) + fine.res, scene.verts.device
+                fronts[i] = (torch.full(shape + (3,), fine.background, dtype=torch.float32, device=dev),
+                             torch.zeros(shape, dtype=torch.float32, device=dev),
+                             torch.full(shape, -1, dtype=torch.int32, device=dev))
+        done = _scene_pictures(who_scene, scene, cams, fine, maps, fronts, composite, out, back)[1]
+    if ras.samples == 1:
+        return fronts, done, None
+    masks, where = None, range(n)
+    if scene is None:
+        pics, where = [fronts[i] for i in live], live
+    elif bare:
+        pics = done
+    else:
+        pics, masks = [(d[0], d[1], f[2]) for d, f in zip(done, fronts)], [d[2] for d in done]
+    resolved = [None] * n
+    if pics:
+        got = ops.picture_resolve_batch(None if pics[0][0] is None else [p[0] for p in pics], [p[1] for p in pics],
+                                        [p[2] for p in pics], masks, ras.samples, ras.nearest, out.get("resolved"),
+                                        who=who_scene)
+        for i, pic in zip(where, got):
+            resolved[i] = pic
+    return fronts, done, resolved
 
 
 def _subject_pictures(who, subjects, cams, ras, shade, colours=None, lighting=None, shadow=None, out=None):
@@ -1250,21 +1330,27 @@ def _scene_pictures(who, scene, cams, ras, maps=None, fronts=None, composite="de
 
 @torch.no_grad()
 def render_scene(scene, calibs, res=257, projection="orthogonal", nearest="max", near=None, perspective_correct=False,
-                 background=1.0, casters=None):
+                 background=1.0, samples=1, casters=None):
     """The textured picture of a ``Scene`` under ``calibs`` ([4,4] / [3,4], or [n_views, ...]): the rasteriser writes a
     UV picture (``near`` / ``perspective_correct`` as in ``render_mesh``), ``ops.picture_texture_batch`` looks the
     texture up per pixel at the nearest mip level, bilinearly.  Returns a ``MeshRender``; pixels the scene does not
     cover hold ``background``.  No host sync.  The scene goes through the rasteriser as any mesh does: a clipped face
     that still projects beyond its 2^22 snap guard is dropped whole (``near`` far below 0.05 with a 3 m floor at
     1024^2); the side planes are not clipped.  ``casters``: None, or the ``Mesh`` whose shadow falls on the scene under
-    ``scene.light`` (ignored without a light): the picture is then the shadowed one."""
+    ``scene.light`` (ignored without a light): the picture is then the shadowed one.  ``samples``: as in
+    ``render_mesh`` -- 1 changes nothing; 2..4 run the UV pass, the texture lookup (whose mip level then follows the
+    finer uv steps) and the shadow at ``samples`` times ``res`` and return the ``ResolvedPicture`` (mask None; coverage =
+    the scene's own)."""
     who = "render_scene"
     _check_scene(who, scene)
-    ras = ops.raster(who, res, projection, nearest, background, near, perspective_correct)
+    ras = ops.raster(who, res, projection, nearest, background, near, perspective_correct, samples)
     maps = None
     if scene.light is not None and casters is not None:
         maps = tuple(zip(*shadow_map([casters], scene.light, device=scene.verts.device)))
-    return MeshRender(*_squeezed(_scene_pictures(who, scene, [calibs], ras, maps)[0][0], calibs))
+    _, backs, resolved = _resolved_pictures(who, None, [calibs], ras, None, scene=scene, maps=maps)
+    if resolved is not None:
+        return ResolvedPicture(*_squeezed(resolved[0], calibs))
+    return MeshRender(*_squeezed(backs[0], calibs))
 
 
 @torch.no_grad()
@@ -1279,9 +1365,30 @@ def composite(front, back, mode="depth", nearest="max", background=1.0):
 
 
 @torch.no_grad()
+def resolve_picture(picture, samples, nearest="max"):
+    """The final picture of ``picture`` -- a ``MeshRender`` or a ``ScenePicture`` (or such a tuple) rendered at
+    ``samples`` (2..4) times the final size, [s H,s W,...] or [n_views,s H,s W,...] -- as a ``ResolvedPicture`` of fresh
+    tensors: the generic call of the render calls' ``samples=``, which give the same bits.  Per pixel over its s x s
+    samples: the mean of the image (None stays None), the depth and face of the nearest sample that shows under
+    ``nearest`` ("max" / "min", as the picture was rendered), the largest mask, and ``coverage`` = the fraction of
+    samples that is the subject's (mask == 2; without a mask face >= 0).  Defined bit for bit in include/monoport_hip.h
+    (mp_picture_resolve).  No host sync."""
+    who = "resolve_picture"
+    picture = tuple(picture)
+    if len(picture) not in (3, 4) or picture[1] is None or picture[2] is None:
+        raise ValueError("%s: picture must be a MeshRender (image, depth, face) or a ScenePicture (image, depth, face, "
+                         "mask)" % who)
+    image, depth, face = picture[:3]
+    mask = picture[3] if len(picture) == 4 else None
+    return ResolvedPicture(*ops.picture_resolve_batch(
+        None if image is None else [image.contiguous()], [depth.contiguous()], [face.contiguous()],
+        None if mask is None else [mask.contiguous()], samples, nearest, who=who)[0])
+
+
+@torch.no_grad()
 def render_mesh_many_in_scene(meshes, scene, calibs, res=257, shade="colors", projection="orthogonal", nearest="max",
                               background=1.0, near=None, perspective_correct=False, composite="depth", netC=None,
-                              feat_tensors_C=None, calib_tensors=None, view=None, lighting=None):
+                              feat_tensors_C=None, calib_tensors=None, view=None, samples=1, lighting=None):
     """``render_mesh_many`` of ``meshes`` composited over ``render_scene`` of ``scene`` under the same cameras
     (``calibs``: one camera set for all, or a list with one per mesh), ``composite``: "depth" or "over".  Returns a
     list of ``ScenePicture``s; a ``None`` mesh gives the bare scene (mask in {0, 1}, face -1).  ``shade`` may not be
@@ -1291,7 +1398,11 @@ def render_mesh_many_in_scene(meshes, scene, calibs, res=257, shade="colors", pr
     enqueued) lights the subject's image as in ``render_mesh``, before the composite; the scene keeps its texture and
     its shadow.  With ``lighting.self_shadow`` (it needs ``scene.light``) the subject is also looked up in its own
     shadow map, with that bias, which takes the direct term away where the shade is 1.  What is enqueued, and in which
-    order: ``_shadow_maps``, ``_subject_pictures``, ``_scene_pictures``."""
+    order: ``_shadow_maps``, ``_subject_pictures``, ``_scene_pictures`` -- all through ``_resolved_pictures``.
+    ``samples``: as in ``render_mesh`` -- 1 changes nothing; with 2..4 the subject's passes, the scene's and the
+    composite run at ``samples`` times ``res`` (the shadow map keeps the light's own size), so that the edges between
+    subject and scene are blended from composited samples, and one resolve at the end gives ``ResolvedPicture``s:
+    ``mask`` the largest of the composite's masks, ``coverage`` the fraction of samples where the subject shows."""
     who = "render_mesh_many_in_scene"
     _check_scene(who, scene)
     if shade is None:
@@ -1303,17 +1414,11 @@ def render_mesh_many_in_scene(meshes, scene, calibs, res=257, shade="colors", pr
     if not meshes:
         return []
     cams = _camera_sets(who, calibs, len(meshes))
-    ras = ops.raster("render_mesh_many", res, projection, nearest, background, near, perspective_correct)
-    fronts, _, maps = _render_mesh_many("render_mesh_many", meshes, calibs, ras, shade, netC, feat_tensors_C,
-                                        calib_tensors, view, lighting, scene.light)
-    nv = ops._view_calibs(who, cams[0]).shape[0]
-    for i, front in enumerate(fronts):
-        if front is None:  # no subject: an uncovered picture of the scene's size
-            shape = (nv,) + ras.res
-            fronts[i] = (torch.full(shape + (3,), ras.background, dtype=torch.float32, device=scene.verts.device),
-                         torch.zeros(shape, dtype=torch.float32, device=scene.verts.device),
-                         torch.full(shape, -1, dtype=torch.int32, device=scene.verts.device))
-    _, done = _scene_pictures(who, scene, cams, ras, maps, fronts, composite)
+    ras = ops.raster("render_mesh_many", res, projection, nearest, background, near, perspective_correct, samples)
+    fronts, _, done, resolved = _render_mesh_many("render_mesh_many", meshes, calibs, ras, shade, netC, feat_tensors_C,
+                                                  calib_tensors, view, lighting, scene, composite, who)
+    if resolved is not None:
+        return [ResolvedPicture(*_squeezed(pic, cam)) for pic, cam in zip(resolved, cams)]
     return [ScenePicture(*_squeezed((image, depth, front[2], mask), cam))
             for (image, depth, mask), front, cam in zip(done, fronts, cams)]
 

@@ -102,6 +102,15 @@ where Pillow is importable, the way to a JPEG without it: ``pictures()``, ``.cpu
 
     python tools/mesh_timing.py --jpeg [--passes 5] [--out profiles/mesh_jpeg_timing.json]
 
+``--samples`` measures anti-aliasing (profiles/mesh_samples_timing.json): mp_picture_resolve_batch alone, per picture
+in a batch of 20 composited pictures (image, depth, face ids and mask in; all five planes out) at the final sizes 257^2
+and 1024^2 for ``samples`` = 2 and 4, with the achieved GB/s (bytes read plus bytes written), beside a device-to-device
+copy that moves the same number of bytes, timed in the same alternating passes; then the ``--jpeg`` slots (the floor
+with its light, clay lighting with the self-shadow, ``encode_pictures``, ``jpegs()`` as the consumer) at ``samples``
+absent / 2 / 4 with one 257^2 view and absent / 2 with one 1024^2 view (4096 is the size limit).
+
+    python tools/mesh_timing.py --samples [--passes 5] [--out profiles/mesh_samples_timing.json]
+
 The protocol of tools/recon_views_timing.py: after a warm-up of all, the passes alternate; a pass is `meshes`
 meshes, wall clock around a final stream sync.  Prints (and writes) one JSON line: per way the median, minimum and
 maximum time per mesh (ms) over the passes.  The verdict fields restate what to check: (b) not slower than (a) by
@@ -147,6 +156,7 @@ def main():
     ap.add_argument("--lighting", action="store_true", help="the --shadow slots without and with lighting= on the subject")
     ap.add_argument("--transfer", action="store_true", help="bits, transfer and shade per mesh; lit slots with transfer=")
     ap.add_argument("--jpeg", action="store_true", help="mp_picture_jpeg alone; the --lighting slots with encode_pictures")
+    ap.add_argument("--samples", action="store_true", help="mp_picture_resolve alone; the --jpeg slots at samples 1 / 2 / 4")
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "mesh_render_clip_timing.json" if a.render and a.clip else
@@ -157,6 +167,7 @@ def main():
                              "mesh_lighting_timing.json" if a.lighting else
                              "mesh_transfer_timing.json" if a.transfer else
                              "mesh_jpeg_timing.json" if a.jpeg else
+                             "mesh_samples_timing.json" if a.samples else
                              "mesh_smooth_timing.json" if a.smooth else
                              "mesh_simplify_timing.json" if a.simplify else
                              "keep_largest_timing.json" if a.clean else
@@ -175,6 +186,12 @@ def main():
         return
     if a.jpeg:
         write(a, slot_jpeg(a))
+        return
+    if a.samples:
+        out = resolve_kernels(a)
+        if not a.no_slot:
+            out["slot"] = slot_samples(a)
+        write(a, out)
         return
     if a.transfer:
         out = transfer_kernels(a)
@@ -678,6 +695,97 @@ def slot_jpeg(a, frames=20):
     for res in ("257", "1024"):
         out["encode_%s_jpegs_minus_pictures_ms" % res] = round(
             out["encode_%s_jpegs" % res]["median_ms"] - out["pictures_" + res]["median_ms"], 4)
+    return out
+
+
+def resolve_kernels(a, n=20):
+    """mp_picture_resolve_batch alone on a batch of ``n`` pictures with every plane given and wanted, per picture, at
+    the final sizes 257^2 and 1024^2 for samples 2 and 4, beside a device-to-device copy that moves the same number of
+    bytes (read plus written) -- all in the same alternating passes."""
+    out = {"pictures_per_call": n, "unit": "ms per picture", "planes": "image, depth, face ids, mask in; image, depth, "
+           "face ids, mask, coverage out", "bytes": "read plus written, per picture"}
+    ways, traffic, keep, ctx = {}, {}, [], ops.get_context(torch.device(DEV))
+    for res in (257, 1024):
+        for s in (2, 4):
+            fine = (n, 1, s * res, s * res)
+            ins = ([t for t in torch.rand(fine + (3,), device=DEV)], [t for t in torch.rand(fine, device=DEV)],
+                   [t for t in torch.randint(-1, 1000, fine, dtype=torch.int32, device=DEV)],
+                   [t for t in torch.randint(0, 3, fine, dtype=torch.uint8, device=DEV)])
+            small = (n, 1, res, res)
+            outs = (torch.empty(small + (3,), device=DEV), torch.empty(small, device=DEV),
+                    torch.empty(small, dtype=torch.int32, device=DEV), torch.empty(small, dtype=torch.uint8, device=DEV),
+                    torch.empty(small, device=DEV))
+            name = "resolve_%d_s%d" % (res, s)
+            traffic[name] = 21 * (s * res) ** 2 + 25 * res ** 2
+            args = ([ops._ptr_array(p) for p in ins] + [res, res, s, ops.NEAREST_MODES["min"]]
+                    + [ops._ptr_array(list(o)) for o in outs] + [ops._stream(outs[0])])
+            keep.append((ins, outs))
+            # the entry point itself, on pointer arrays made once; the wrapper's checks cost the host ~0.5 ms a call
+            ways[name] = lambda args=args: ctx.check(ctx.lib.mp_picture_resolve_batch(ctx.handle, n, 1, *args), name)
+            if (res, s) == (257, 2):
+                ways["wrapper_257_s2"] = lambda ins=ins, outs=outs: ops.picture_resolve_batch(*ins, 2, "min", out=outs)
+                traffic["wrapper_257_s2"] = traffic[name]
+            src = torch.empty(n * traffic[name] // 2, dtype=torch.uint8, device=DEV)
+            dst = torch.empty_like(src)
+            traffic["copy_%d_s%d" % (res, s)] = 2 * (traffic[name] // 2)
+            ways["copy_%d_s%d" % (res, s)] = lambda src=src, dst=dst: dst.copy_(src)
+    out.update(alternate(ways, a.passes, n))  # wall clock of ONE call and a sync: the host side of the call included
+    # the device alone: events around calls enqueued back to back (200 at 257^2, 20 at 1024^2), in alternating passes
+    device = {name: [] for name in ways}
+    for _ in range(a.passes):
+        for name, fn in ways.items():
+            reps = 200 if "_257_" in name else 20
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0.record()
+            for _k in range(reps):
+                fn()
+            t1.record()
+            torch.cuda.synchronize()
+            device[name].append(t0.elapsed_time(t1) / reps / n)
+    out["device"] = {name: stats(t) for name, t in device.items()}
+    out["device_unit"] = ("ms per picture between two events around calls enqueued back to back: 200 at 257^2, 20 at "
+                          "1024^2")
+    out["bytes_per_picture"] = traffic
+    out["gb_per_s"] = {name: round(traffic[name] / (out["device"][name]["median_ms"] * 1e-3) / 1e9, 1) for name in ways}
+    out["gb_per_s_wall_clock_of_one_call"] = {name: round(traffic[name] / (out[name]["median_ms"] * 1e-3) / 1e9, 1)
+                                              for name in ways}
+    out["resolve_over_copy_rate"] = {k[8:]: round(out["gb_per_s"][k] / out["gb_per_s"]["copy_" + k[8:]], 3)
+                                     for k in ways if k.startswith("resolve_")}
+    return out
+
+
+def slot_samples(a, frames=20):
+    """The --jpeg slots WITH ``encode_pictures`` -- one view, the floor with its light, clay lighting with the
+    self-shadow, ``jpegs()`` as the consumer -- at ``samples`` absent / 2 / 4 for 257^2 and absent / 2 for 1024^2:
+    per-frame ms of a submission, and the pixels of frame 0 whose coverage is strictly between 0 and 1."""
+    direction = (0.4, -1.0, 0.3)
+    sun = recon.Light.directional(direction, (-1.5, -0.9, -1.5), (1.5, 1.0, 1.5), res=512, radius=1)
+    floor, cam, mesh, base = _scene_setup(sun)
+    sh = np.random.RandomState(0).uniform(-0.2, 0.4, (9, 3)).astype(np.float32)
+    sh[0] += 0.8
+    lighting = recon.Lighting(sh, direct=(direction, (0.9, 0.85, 0.8)), frame="camera", albedo=(0.8, 0.7, 0.6),
+                              self_shadow=0.02)
+    more = dict(lighting=lighting, encode_pictures=recon.Jpeg(quality=90, subsampling="420"))
+    out = {"frames_per_slot": frames, "unit": "ms per frame", "consumer": "jpegs()",
+           "slots": "the --jpeg slots: one view, the floor with its light, clay lighting with the self-shadow, "
+                    "encode_pictures at quality 90, 420"}
+    out["edge_pixels_frame0"] = {}
+    for res, counts in ((257, (1, 2, 4)), (1024, (1, 2))):  # one size at a time: the working buffers are large
+        rows = [("samples%d_%d" % (s, res), mesh, dict(base, res=res, scene=floor, **({} if s == 1 else {"samples": s})),
+                 cam, more) for s in counts]
+        pipes, fn = _slot_pipes(frames, 1, rows)
+        out.update(alternate({name: fn(name, lambda s_: s_.jpegs()) for name in pipes}, a.passes, frames))
+        for name, p_ in pipes.items():
+            cov = p_.slots[0].pictures_coverage
+            if cov is not None:
+                out["edge_pixels_frame0"][name] = int(((cov[0] > 0) & (cov[0] < 1)).sum().item())
+            p_.close()
+        del pipes, fn
+        torch.cuda.empty_cache()
+        for s in counts[1:]:
+            out["samples%d_%d_minus_samples1_ms" % (s, res)] = round(
+                out["samples%d_%d" % (s, res)]["median_ms"] - out["samples1_%d" % res]["median_ms"], 4)
     return out
 
 
