@@ -1170,6 +1170,73 @@ int64_t mp_jpeg_max_bytes(int h, int w, int subsampling, int restart);
 int mp_picture_jpeg(mp_ctx *ctx, const float *images, int n, int h, int w, int quality, int subsampling, int restart,
                     uint8_t *out, int64_t capacity, int32_t *info, mp_stream stream);
 
+/* Pictures as lossless bytes, with their alpha (the reference reads and writes .png throughout its data side): the PNG
+ * file of a float picture, made on the device.  As for JPEG the definition is this library's own, all-integer after the
+ * samples, and tests/png_ref.py restates it in numpy byte for byte; zlib and any PNG reader give the samples back.
+ *   Container: the PNG signature, IHDR (bit depth 8 with colour type 2 (MP_PNG_RGB8) or 6 (MP_PNG_RGBA8), bit depth 16
+ * with colour type 0 (MP_PNG_GRAY16); compression 0, filter 0, no interlace), the zlib stream cut into IDAT chunks of
+ * MP_PNG_IDAT_BYTES data bytes (the last one shorter), IEND.  Byte k of the zlib stream is byte
+ * 41 + 12 (k / MP_PNG_IDAT_BYTES) + k of the file, so every chunk's CRC-32 stands alone.  16-bit samples are big-endian.
+ *   Samples.  RGB8: step 1 of the JPEG definition.  RGBA8: the same rule on alpha [H,W] f32 as the fourth byte; with
+ * `unmatte` (a resolved pixel is c = a s + (1 - a) bg and PNG alpha is straight) the colour of a pixel with a > 0 is
+ * s = (c - (1 - a) * bg) / a in four separately rounded f32 operations, then the 8-bit rule; a <= 0 or a NaN: colour
+ * and alpha 0.  GRAY16: t = (d - lo) * scale (two operations), t > 0 ? (t < 1 ? t : 1) : 0 (a NaN: 0),
+ * u = (int)((t * 65535) + 0.5), two operations.  mp_picture_u16 (depth [n_pixels] -> uint16 [n_pixels], host order) and
+ * mp_picture_rgba8 (image [n_pixels,3], alpha [n_pixels] -> [n_pixels,4]) are these steps alone, refusing as
+ * mp_picture_u8 does, and a non-finite lo, scale or background (MP_ERR_ARG).
+ *   Filtering, bpp = 3, 4 or 2: every scanline is its filter type and its filtered bytes.  MP_PNG_NONE .. MP_PNG_PAETH
+ * use that type on every line; MP_PNG_ADAPTIVE takes per line the type with the smallest sum of min(b, 256 - b) over
+ * its filtered bytes, the lowest type on a tie.  The filtered bytes of all lines are the stream x of S = H (1 + W bpp)
+ * bytes.
+ *   Deflate.  x is cut into blocks of MP_PNG_BLOCK_BYTES = 4096 bytes (the last one shorter); a block is also the parse
+ * unit.  Every block is a dynamic-Huffman block, the last one with BFINAL.
+ *   Matching: the candidate distances are those of 1, bpp, 2 bpp, stride - bpp, stride, stride + bpp and 2 stride
+ * (stride = 1 + W bpp) that lie in 1..32768, ascending, without repeats.  The run of d at i is the count of j = i, i + 1,
+ * ... with j - d >= 0 and x[j] == x[j - d], stopped at the block's end and at 258 (sources may lie before the block).
+ * The match at i is the longest run if it is >= 3, the smallest distance on a tie.
+ *   Parse: greedy from the block's first byte: a match where there is one (then i += length), else the literal x[i];
+ * then the end-of-block symbol.  Lengths and distances map to symbols and extra bits by RFC 1951 (258 is symbol 285).
+ *   Codes: the counts of the 286 literal/length symbols and of the 30 distance symbols of the block give code lengths:
+ * no used symbol: all 0 (one distance code of length 0 is sent: HDIST = 1); one: length 1; else a Huffman tree built by
+ * joining, 'used symbols - 1' times, the live node with the smallest (weight, index) and then the next one, where a
+ * leaf's index is its symbol and a joined node's index follows every earlier index.  Where the deepest leaf exceeds 15,
+ * every non-zero count becomes (c + 1) >> 1 and the tree is built again.  Codes are canonical.  HLIT and HDIST drop
+ * trailing zero lengths (257 and 1 at least).  The HLIT + HDIST lengths as one sequence are run-length coded from the
+ * left: a run of zeros as 18 (11..138) while >= 11 remain, then 17 (3..10), then single 0s; a run of v > 0 as v, then
+ * 16 (3..6) while >= 3 remain, then single v.  Those 19 symbols get lengths by the same rule with limit 7; HCLEN drops
+ * trailing zeros in the RFC's order (4 at least).
+ *   Stream: 0x78 0x01, the blocks back to back, bits LSB first with Huffman codes bit-reversed, zero bits to a byte,
+ * Adler-32 of x big-endian.
+ *   mp_png_max_bytes: a token covers at least one byte and costs at most 16 bits per byte (a literal: 15; three bytes
+ * of match: 15 + 5 + 15 + 13), a block adds at most 3 + 14 + 19 * 3 + 316 * 7 + 15 = 2301 bits = 288 bytes:
+ * z = 6 + 2 S + 288 ceil(S / 4096), file = 57 + 12 ceil(z / MP_PNG_IDAT_BYTES) + z; 0 for a geometry the call refuses.
+ *   mp_picture_png: n pictures of one size, CONTIGUOUS: images [n,H,W,3] f32 ([n,H,W] for MP_PNG_GRAY16), alpha [n,H,W]
+ * f32 for MP_PNG_RGBA8, else null.  out, capacity, info and overflow are those of mp_picture_jpeg, word for word: the
+ * size is known on the device before any byte is written, an overflowing picture writes NOTHING and reports the size it
+ * needs, the others are unaffected, no store lands past capacity, and a second call at the reported size gives the
+ * bytes a sufficient capacity gives.  lo and scale are read for MP_PNG_GRAY16, background with unmatte != 0.
+ *   Six launches (samples + filter, block coding, sizes, clearing the stream words, emit, framing + CRC), integer
+ * atomics only, nothing allocated: of the stream's scratch arena 3 bytes per filtered byte, 352 per block, and per
+ * picture min(capacity, mp_png_max_bytes) + 16.  Asynchronous, no host value.
+ *   Refusals (a message, nothing launched): h or w outside 1..MP_PNG_MAX_SIDE, an unknown format or filter, n > 65535:
+ * MP_ERR_UNSUPPORTED; n < 1, capacity below MP_PNG_MIN_BYTES or above 2^31, a null or misaligned (4 bytes: images,
+ * alpha, info) buffer, alpha given without MP_PNG_RGBA8 or missing with it, unmatte without alpha, a non-finite lo,
+ * scale or background, out / info overlapping the inputs or each other: MP_ERR_ARG. */
+#define MP_PNG_MAX_SIDE 4096
+#define MP_PNG_BLOCK_BYTES 4096
+#define MP_PNG_IDAT_BYTES 8192
+#define MP_PNG_MIN_BYTES 57
+enum { MP_PNG_RGB8 = 0, MP_PNG_RGBA8 = 1, MP_PNG_GRAY16 = 2 };
+enum { MP_PNG_NONE = 0, MP_PNG_SUB = 1, MP_PNG_UP = 2, MP_PNG_AVERAGE = 3, MP_PNG_PAETH = 4, MP_PNG_ADAPTIVE = 5 };
+int mp_picture_u16(mp_ctx *ctx, const float *depth, int64_t n_pixels, float lo, float scale, uint16_t *out,
+                   mp_stream stream);
+int mp_picture_rgba8(mp_ctx *ctx, const float *image, const float *alpha, int64_t n_pixels, int unmatte,
+                     float background, uint8_t *out, mp_stream stream);
+int64_t mp_png_max_bytes(int h, int w, int format);
+int mp_picture_png(mp_ctx *ctx, const float *images, const float *alpha, int n, int h, int w, int format, int filter,
+                   float lo, float scale, int unmatte, float background, uint8_t *out, int64_t capacity, int32_t *info,
+                   mp_stream stream);
+
 /* The largest connected body of an occupancy volume [R,R,R] (no counterpart in the reference; the clean-up in front
  * of marching cubes that drops floating blobs).
  *   Foreground: voxels with value > level (marching cubes' "inside"; a NaN and value == level are background).

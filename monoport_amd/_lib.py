@@ -101,6 +101,9 @@ COMPOSITE_OVER, COMPOSITE_DEPTH = 0, 1
 CONN_6, CONN_26 = 6, 26
 # MP_JPEG_* subsamplings of mp_picture_jpeg (include/monoport_hip.h)
 JPEG_444, JPEG_420 = 0, 1
+# MP_PNG_* formats and filters of mp_picture_png (include/monoport_hip.h)
+PNG_RGB8, PNG_RGBA8, PNG_GRAY16 = 0, 1, 2
+PNG_NONE, PNG_SUB, PNG_UP, PNG_AVERAGE, PNG_PAETH, PNG_ADAPTIVE = 0, 1, 2, 3, 4, 5
 MAX_VIEWS = 8  # MP_MAX_VIEWS: views per mp_query_views / mp_mlp_forward_views call
 MAX_FRAME_VIEWS = 64  # MP_MAX_FRAME_VIEWS = mp_max_frame_views(): frames x views per mp_recon_views_batch call
 MAX_FRAMES = 32  # kMaxFrames (csrc/mp_internal.h) = mp_max_frames(): frames per batched query / recon call
@@ -241,6 +244,11 @@ SIGNATURES = {
     "mp_picture_u8": (c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
     "mp_jpeg_max_bytes": (c_i64, [c_int, c_int, c_int, c_int]),
     "mp_picture_jpeg": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp, c_vp]),
+    "mp_picture_u16": (c_int, [c_vp, c_vp, c_i64, c_f32, c_f32, c_vp, c_vp]),
+    "mp_picture_rgba8": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_f32, c_vp, c_vp]),
+    "mp_png_max_bytes": (c_i64, [c_int, c_int, c_int]),
+    "mp_picture_png": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_f32, c_f32, c_int, c_f32,
+                               c_vp, c_i64, c_vp, c_vp]),
     "mp_volume_bits_words": (c_i64, [c_int]),
     "mp_volume_bits": (c_int, [c_vp, c_vp, c_int, c_f32, c_vp, c_vp]),
     "mp_volume_bits_batch": (c_int, [c_vp, c_int, c_vp, c_int, c_f32, c_vp, c_vp, c_vp]),

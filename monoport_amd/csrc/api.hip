@@ -2255,6 +2255,92 @@ int mp_picture_jpeg(mp_ctx *ctx, const float *images, int n, int h, int w, int q
                              (hipStream_t)stream);
 }
 
+int mp_picture_u16(mp_ctx *ctx, const float *depth, int64_t n_pixels, float lo, float scale, uint16_t *out,
+                   mp_stream stream) {
+  const char *who = "mp_picture_u16";
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (n_pixels < 0) return fail(ctx, MP_ERR_ARG, "%s: n_pixels %lld", who, (long long)n_pixels);
+  if (n_pixels > 0x7fffffffLL)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: n_pixels %lld (at most 2^31)", who, (long long)n_pixels);
+  if (!std::isfinite(lo) || !std::isfinite(scale)) return fail(ctx, MP_ERR_ARG, "%s: a non-finite lo or scale", who);
+  if (n_pixels == 0) return MP_OK;
+  if (!depth || !out || ((uintptr_t)depth & 3u) || ((uintptr_t)out & 1u))
+    return fail(ctx, MP_ERR_ARG, "%s: a null or misaligned buffer", who);
+  if (ranges_overlap(out, (size_t)n_pixels * 2, depth, (size_t)n_pixels * 4))
+    return fail(ctx, MP_ERR_ARG, "%s: out aliases depth", who);
+  DeviceGuard g(ctx->device);
+  return launch_picture_u16(ctx, depth, n_pixels, lo, scale, out, (hipStream_t)stream);
+}
+
+int mp_picture_rgba8(mp_ctx *ctx, const float *image, const float *alpha, int64_t n_pixels, int unmatte,
+                     float background, uint8_t *out, mp_stream stream) {
+  const char *who = "mp_picture_rgba8";
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (n_pixels < 0) return fail(ctx, MP_ERR_ARG, "%s: n_pixels %lld", who, (long long)n_pixels);
+  if (n_pixels > 0x7fffffffLL / 4)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: n_pixels %lld (at most 2^31 / 4)", who, (long long)n_pixels);
+  if (!std::isfinite(background)) return fail(ctx, MP_ERR_ARG, "%s: a non-finite background", who);
+  if (n_pixels == 0) return MP_OK;
+  if (!image || !alpha || !out || ((uintptr_t)image & 3u) || ((uintptr_t)alpha & 3u) || ((uintptr_t)out & 3u))
+    return fail(ctx, MP_ERR_ARG, "%s: a null or misaligned buffer", who);
+  if (ranges_overlap(out, (size_t)n_pixels * 4, image, (size_t)n_pixels * 12) ||
+      ranges_overlap(out, (size_t)n_pixels * 4, alpha, (size_t)n_pixels * 4))
+    return fail(ctx, MP_ERR_ARG, "%s: out aliases image or alpha", who);
+  DeviceGuard g(ctx->device);
+  return launch_picture_rgba8(ctx, image, alpha, n_pixels, unmatte != 0, background, out, (hipStream_t)stream);
+}
+
+static bool png_geometry_ok(int h, int w, int format) {
+  return h >= 1 && h <= MP_PNG_MAX_SIDE && w >= 1 && w <= MP_PNG_MAX_SIDE && format >= MP_PNG_RGB8 &&
+         format <= MP_PNG_GRAY16;
+}
+
+int64_t mp_png_max_bytes(int h, int w, int format) {
+  return png_geometry_ok(h, w, format) ? (int64_t)png_max_bytes(h, w, format) : 0;
+}
+
+int mp_picture_png(mp_ctx *ctx, const float *images, const float *alpha, int n, int h, int w, int format, int filter,
+                   float lo, float scale, int unmatte, float background, uint8_t *out, int64_t capacity, int32_t *info,
+                   mp_stream stream) {
+  const char *who = "mp_picture_png";
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (h < 1 || h > MP_PNG_MAX_SIDE || w < 1 || w > MP_PNG_MAX_SIDE)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: a picture of %d x %d (sides 1..%d)", who, h, w, MP_PNG_MAX_SIDE);
+  if (format < MP_PNG_RGB8 || format > MP_PNG_GRAY16)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: format %d (MP_PNG_RGB8, MP_PNG_RGBA8 or MP_PNG_GRAY16)", who, format);
+  if (filter < MP_PNG_NONE || filter > MP_PNG_ADAPTIVE)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: filter %d (MP_PNG_NONE .. MP_PNG_ADAPTIVE)", who, filter);
+  if (n < 1) return fail(ctx, MP_ERR_ARG, "%s: n %d pictures", who, n);
+  if (n > 65535) return fail(ctx, MP_ERR_UNSUPPORTED, "%s: n %d pictures (at most 65535 per call)", who, n);
+  if (capacity < png_min_bytes() || capacity > ((int64_t)1 << 31))
+    return fail(ctx, MP_ERR_ARG, "%s: capacity %lld (at least the smallest file's %d bytes, at most 2^31)", who,
+                (long long)capacity, png_min_bytes());
+  if (alpha && format != MP_PNG_RGBA8) return fail(ctx, MP_ERR_ARG, "%s: alpha for a format without it", who);
+  if (!alpha && format == MP_PNG_RGBA8) return fail(ctx, MP_ERR_ARG, "%s: MP_PNG_RGBA8 without alpha", who);
+  if (unmatte && !alpha) return fail(ctx, MP_ERR_ARG, "%s: unmatte without alpha", who);
+  if (!std::isfinite(lo) || !std::isfinite(scale) || !std::isfinite(background))
+    return fail(ctx, MP_ERR_ARG, "%s: a non-finite lo, scale or background", who);
+  if (!images || !out || !info || ((uintptr_t)images & 3u) || ((uintptr_t)alpha & 3u) || ((uintptr_t)info & 3u))
+    return fail(ctx, MP_ERR_ARG, "%s: a null or misaligned buffer", who);
+  const size_t px = (size_t)n * h * w, in_bytes = px * (format == MP_PNG_GRAY16 ? 4 : 12);
+  const size_t al_bytes = alpha ? px * 4 : 0, out_bytes = (size_t)n * (size_t)capacity, info_bytes = (size_t)n * 8;
+  if (ranges_overlap(out, out_bytes, images, in_bytes) || ranges_overlap(info, info_bytes, images, in_bytes) ||
+      ranges_overlap(out, out_bytes, info, info_bytes) ||
+      (alpha && (ranges_overlap(out, out_bytes, alpha, al_bytes) || ranges_overlap(info, info_bytes, alpha, al_bytes))))
+    return fail(ctx, MP_ERR_ARG, "%s: out / info aliases images, alpha or each other", who);
+  DeviceGuard g(ctx->device);
+  PngCall c;
+  c.n = n, c.h = h, c.w = w, c.format = format, c.filter = filter, c.unmatte = unmatte != 0;
+  c.lo = lo, c.scale = scale, c.background = background, c.capacity = capacity;
+  void *scratch = nullptr;
+  const int rc = ensure_scratch(ctx, (hipStream_t)stream, png_scratch_bytes(c), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_picture_png(ctx, scratch, images, alpha, c, out, info, (hipStream_t)stream);
+}
+
 int64_t mp_volume_bits_words(int r) { return r < 1 || r > MP_TRANSFER_MAX_RES ? 0 : (int64_t)volume_bits_words(r); }
 
 int mp_volume_bits(mp_ctx *ctx, const float *volume, int r, float level, uint32_t *bits, mp_stream stream) {

@@ -521,6 +521,23 @@ long long jpeg_max_bytes(int h, int w, int s420, int restart);
 size_t jpeg_scratch_bytes(int n, int h, int w, int s420, int restart);
 int launch_picture_jpeg(mp_ctx *ctx, void *scratch, const float *images, int n, int h, int w, int quality, int s420,
                         int restart, uint8_t *out, long long capacity, int32_t *info, hipStream_t st);
+// png.hip: the 16-bit and RGBA samples, and n pictures of one size -> n PNG files in out [n,capacity] with info [n,2] =
+// {bytes, overflowed}.  format / filter: MP_PNG_* (checked by the caller); alpha: nullptr or [n,h,w]; scratch:
+// png_scratch_bytes(n, ..., capacity).  png_max_bytes: what no file of that geometry exceeds
+struct PngCall {  // host values of one call
+  int n, h, w, format, filter, unmatte;
+  float lo, scale, background;
+  long long capacity;
+};
+int launch_picture_u16(mp_ctx *ctx, const float *depth, long long n_pixels, float lo, float scale, uint16_t *out,
+                       hipStream_t st);
+int launch_picture_rgba8(mp_ctx *ctx, const float *image, const float *alpha, long long n_pixels, int unmatte,
+                         float background, uint8_t *out, hipStream_t st);
+int png_min_bytes();
+long long png_max_bytes(int h, int w, int format);
+size_t png_scratch_bytes(const PngCall &c);
+int launch_picture_png(mp_ctx *ctx, void *scratch, const float *images, const float *alpha, const PngCall &c,
+                       uint8_t *out, int32_t *info, hipStream_t st);
 #ifdef __HIPCC__
 // v / |v|, or (0, 0, 0) where |v|^2 is not finite or not > 0 (a zero, a NaN, an inf, an overflow)
 __device__ __forceinline__ void light_normalise(float x, float y, float z, float &ox, float &oy, float &oz) {

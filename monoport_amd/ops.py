@@ -2667,6 +2667,137 @@ def picture_jpeg_raw(images, quality=90, subsampling="420", restart=None, capaci
     return out, info
 
 
+# MP_PNG_* (include/monoport_hip.h)
+PNG_FORMATS = {"rgb8": _lib.PNG_RGB8, "rgba8": _lib.PNG_RGBA8, "gray16": _lib.PNG_GRAY16}
+PNG_FILTERS = {"none": _lib.PNG_NONE, "sub": _lib.PNG_SUB, "up": _lib.PNG_UP, "average": _lib.PNG_AVERAGE,
+               "paeth": _lib.PNG_PAETH, "adaptive": _lib.PNG_ADAPTIVE}
+PNG_MAX_SIDE = 4096  # MP_PNG_MAX_SIDE
+PNG_MIN_BYTES = 57   # MP_PNG_MIN_BYTES
+
+
+def _finite_float(who, what, value):
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(np.float32(value)):
+        raise ValueError("%s: %s must be a finite number, got %r" % (who, what, value))
+    return float(np.float32(value))
+
+
+def png_params(who, format="rgb8", filter="adaptive", lo=0.0, scale=1.0, unmatte=None):
+    """(MP_PNG_* format, MP_PNG_* filter, lo, scale, unmatte flag, background) of mp_picture_png, checked.  ``unmatte``:
+    None, or the background value the colour is freed of (RGBA8 only)."""
+    fmt = _named_mode(who, "format", PNG_FORMATS, format)
+    flt = _named_mode(who, "filter", PNG_FILTERS, filter)
+    lo, scale = _finite_float(who, "lo", lo), _finite_float(who, "scale", scale)
+    if unmatte is not None and fmt != _lib.PNG_RGBA8:
+        raise ValueError("%s: unmatte needs an alpha (format 'rgba8')" % who)
+    return fmt, flt, lo, scale, int(unmatte is not None), 0.0 if unmatte is None else _finite_float(who, "unmatte", unmatte)
+
+
+def png_max_bytes(h, w, format="rgb8"):
+    """mp_png_max_bytes: what no PNG file of an [h,w] picture in ``format`` exceeds at any content: 16 bits per filtered
+    byte, 288 bytes per 4096-byte block, the container.  Typical files are a small fraction of it."""
+    who = "png_max_bytes"
+    fmt = _named_mode(who, "format", PNG_FORMATS, format)
+    for side in (h, w):
+        if isinstance(side, bool) or not isinstance(side, (int, np.integer)) or not 1 <= side <= PNG_MAX_SIDE:
+            raise ValueError("%s: h and w must be ints in 1..%d, got %r x %r" % (who, PNG_MAX_SIDE, h, w))
+    return int(_lib.load().mp_png_max_bytes(int(h), int(w), fmt))
+
+
+def _sample_out(who, out, shape, dtype, dev):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if (not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != tuple(shape)
+            or not out.is_contiguous() or out.device != dev):
+        raise ValueError("%s: out must be a contiguous %s tensor %s on %s" % (who, dtype, tuple(shape), dev))
+    return out
+
+
+def picture_u16_raw(depth, lo=0.0, scale=1.0, out=None):
+    """mp_picture_u16: float32 [...] -> uint16 of the same shape, clamp((d - lo) * scale, 0, 1) * 65535 + 0.5 truncated
+    (separately rounded f32 operations, a NaN gives 0): the GRAY16 samples of the PNG definition.  No host sync."""
+    who = "picture_u16_raw"
+    if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32:
+        raise ValueError("%s: depth must be a float32 tensor" % who)
+    lo, scale = _finite_float(who, "lo", lo), _finite_float(who, "scale", scale)
+    depth = depth.contiguous()
+    out = _sample_out(who, out, depth.shape, torch.uint16, depth.device)
+    ctx = get_context(depth.device)
+    ctx.check(ctx.lib.mp_picture_u16(ctx.handle, _ptr(depth), depth.numel(), lo, scale, _ptr(out), _stream(depth)),
+              "mp_picture_u16")
+    _keep_until_done(depth.device, [depth])
+    return out
+
+
+def picture_rgba8_raw(image, alpha, unmatte=None, out=None):
+    """mp_picture_rgba8: image float32 [...,3] and alpha float32 [...] -> uint8 [...,4]: the RGBA8 samples of the PNG
+    definition; ``unmatte``: None, or the background value the colour is freed of.  No host sync."""
+    who = "picture_rgba8_raw"
+    if not isinstance(image, torch.Tensor) or image.dtype != torch.float32 or image.dim() < 1 or image.shape[-1] != 3:
+        raise ValueError("%s: image must be a float32 tensor [...,3]" % who)
+    if (not isinstance(alpha, torch.Tensor) or alpha.dtype != torch.float32 or alpha.shape != image.shape[:-1]
+            or alpha.device != image.device):
+        raise ValueError("%s: alpha must be a float32 tensor %s on %s" % (who, tuple(image.shape[:-1]), image.device))
+    bg = 0.0 if unmatte is None else _finite_float(who, "unmatte", unmatte)
+    image, alpha = image.contiguous(), alpha.contiguous()
+    out = _sample_out(who, out, tuple(alpha.shape) + (4,), torch.uint8, image.device)
+    ctx = get_context(image.device)
+    ctx.check(ctx.lib.mp_picture_rgba8(ctx.handle, _ptr(image), _ptr(alpha), alpha.numel(), int(unmatte is not None), bg,
+                                       _ptr(out), _stream(image)), "mp_picture_rgba8")
+    _keep_until_done(image.device, [image, alpha])
+    return out
+
+
+def picture_png_raw(images, alpha=None, format="rgb8", filter="adaptive", lo=0.0, scale=1.0, unmatte=None,
+                    capacity=None, out=None, info=None):
+    """mp_picture_png: ``images`` float32 [n,H,W,3] ([n,H,W] for 'gray16'; contiguous, any n up to 65535) and, for
+    'rgba8', ``alpha`` float32 [n,H,W] -> (out uint8 [n,capacity], info int32 [n,2]) on the device, as
+    ``picture_jpeg_raw`` returns them: file i is ``out[i, :info[i, 0]]`` where ``info[i, 1] == 0``; where it is 1 nothing
+    of it was written and ``info[i, 0]`` is the capacity it needs.  The files are defined byte for byte in
+    include/monoport_hip.h.  ``capacity``: None = ``png_max_bytes`` (never overflows).  One set of six launches; no host
+    sync."""
+    who = "picture_png_raw"
+    fmt, flt, lo, scale, un, bg = png_params(who, format, filter, lo, scale, unmatte)
+    gray = fmt == _lib.PNG_GRAY16
+    if (not isinstance(images, torch.Tensor) or images.dtype != torch.float32 or images.dim() != (3 if gray else 4)
+            or (not gray and images.shape[-1] != 3) or not images.is_contiguous()):
+        raise ValueError("%s: images must be a contiguous float32 tensor %s" % (who, "[n,H,W]" if gray else "[n,H,W,3]"))
+    n, h, w = (int(v) for v in images.shape[:3])
+    if n < 1 or not (1 <= h <= PNG_MAX_SIDE and 1 <= w <= PNG_MAX_SIDE):
+        raise ValueError("%s: at least one picture with sides in 1..%d, got %s" % (who, PNG_MAX_SIDE, tuple(images.shape)))
+    dev = images.device
+    if (fmt == _lib.PNG_RGBA8) != (alpha is not None):
+        raise ValueError("%s: alpha goes with format 'rgba8' and with no other" % who)
+    if alpha is not None and (not isinstance(alpha, torch.Tensor) or alpha.dtype != torch.float32
+                              or tuple(alpha.shape) != (n, h, w) or not alpha.is_contiguous() or alpha.device != dev):
+        raise ValueError("%s: alpha must be a contiguous float32 tensor [%d,%d,%d] on %s" % (who, n, h, w, dev))
+    if out is not None:
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != n
+                or not out.is_contiguous() or out.device != dev):
+            raise ValueError("%s: out must be a contiguous uint8 tensor [%d,capacity] on %s" % (who, n, dev))
+        if capacity is not None and int(capacity) != out.shape[1]:
+            raise ValueError("%s: capacity %r against an out of %d bytes per picture" % (who, capacity, out.shape[1]))
+        capacity = int(out.shape[1])
+    elif capacity is None:
+        capacity = png_max_bytes(h, w, fmt)
+    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < PNG_MIN_BYTES:
+        raise ValueError("%s: capacity must be an int >= the smallest file's %d bytes, got %r"
+                         % (who, PNG_MIN_BYTES, capacity))
+    if info is None:
+        info = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    elif (not isinstance(info, torch.Tensor) or info.dtype != torch.int32 or info.shape != (n, 2)
+          or not info.is_contiguous() or info.device != dev):
+        raise ValueError("%s: info must be a contiguous int32 tensor [%d,2] on %s" % (who, n, dev))
+    if out is None:
+        out = torch.empty((n, int(capacity)), dtype=torch.uint8, device=dev)
+    ctx = get_context(dev)
+    ctx.check(ctx.lib.mp_picture_png(ctx.handle, _ptr(images), None if alpha is None else _ptr(alpha), n, h, w, fmt, flt,
+                                     lo, scale, un, bg, _ptr(out), int(capacity), _ptr(info), _stream(images)),
+              "mp_picture_png")
+    _keep_until_done(dev, [images, alpha])
+    return out, info
+
+
 # MP_CONN_* (include/monoport_hip.h): face neighbours / face, edge and corner neighbours
 CONNECTIVITIES = (_lib.CONN_6, _lib.CONN_26)
 

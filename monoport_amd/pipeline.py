@@ -143,6 +143,7 @@ class FrameSlot:
 
     view = 0  # the row of a multi-view head's result (ViewsSlot); a single-view head has the one
     jpeg = None  # the ``recon.Jpeg`` of ``encode_pictures``; None: nothing is allocated or enqueued for it
+    png = None   # the ``recon.Png`` of ``encode_pictures``; None likewise
     _chained = False  # the chain has been enqueued at least once (``prepare`` / ``submit``)
 
     def __init__(self, netG, device, resolutions=RESOLUTIONS, b_min=(-1, -1, -1), b_max=(1, 1, 1),
@@ -470,6 +471,8 @@ class FrameSlot:
             self._render_pictures(n)
         if self.jpeg is not None:
             self._encode_pictures(n)
+        if self.png is not None:
+            self._encode_png(n)
 
     # the netC pieces of the chain that depend on the head's views (ColorViewsSlot overrides them)
     def _pack_colour_maps(self, b, feat, feat_c):
@@ -601,28 +604,39 @@ class FrameSlot:
         return out
 
     def encode_pictures(self, jpeg):
-        """Encode the slot's pictures on the device from now on: ``jpeg`` is a ``recon.Jpeg``.  To be called before the
-        first ``prepare`` / ``submit``; it needs pictures with a ``shade``.  The slot then owns the static
-        ``jpeg_bytes`` [batch * views, capacity] uint8 (``jpeg.capacity_for`` the pictures' size) and ``jpeg_info``
-        [batch * views, 2] int32, and the chain enqueues ONE mp_picture_jpeg over the active frames' pictures behind
-        ``_render_pictures`` on the slot's stream -- behind the composite with a scene, behind the lighting without one
-        -- with no host value in between; ``jpegs()`` hands the files out.  A slot on which this was never called
-        allocates and enqueues nothing for it."""
-        from .recon import Jpeg
+        """Encode the slot's pictures on the device from now on: ``jpeg`` is a ``recon.Jpeg`` or a ``recon.Png``; a slot
+        may have one of each.  To be called before the first ``prepare`` / ``submit``; a Jpeg and a Png of the image need
+        pictures with a ``shade``.  The slot then owns the static ``jpeg_bytes`` [batch * views, capacity] uint8 (the
+        codec's ``capacity_for`` the pictures' size) and ``jpeg_info`` [batch * views, 2] int32 -- ``png_bytes`` and
+        ``png_info`` for a Png --, and the chain enqueues ONE mp_picture_jpeg (mp_picture_png) over the active frames'
+        pictures behind ``_render_pictures`` on the slot's stream -- behind the composite with a scene, behind the
+        lighting without one, behind the resolve with ``samples`` -- with no host value in between; ``jpegs()``
+        (``pngs()``) hands the files out.  A Png with ``alpha="coverage"`` needs ``samples`` > 1; with
+        ``alpha="subject"`` the slot also owns ``png_alpha`` [batch, views, H, W] f32, filled by one op per submission.
+        A slot on which this was never called allocates and enqueues nothing for it."""
+        from .recon import Jpeg, Png
         who = "%s.encode_pictures" % type(self).__name__
-        if not isinstance(jpeg, Jpeg):
-            raise ValueError("%s: jpeg must be a recon.Jpeg, got %r" % (who, type(jpeg).__name__))
+        if not isinstance(jpeg, (Jpeg, Png)):
+            raise ValueError("%s: jpeg must be a recon.Jpeg (or a recon.Png), got %r" % (who, type(jpeg).__name__))
         po = self.picture_options
         if po is None:
             raise ValueError("%s: the slot was made without pictures=..." % who)
-        if po.shade is None:
+        depth = isinstance(jpeg, Png) and jpeg.plane == "depth"
+        if po.shade is None and not depth:
             raise ValueError("%s: the slot's pictures have shade=None: there is no image to encode" % who)
+        if isinstance(jpeg, Png) and jpeg.alpha == "coverage" and po.samples < 2:
+            raise ValueError("%s: alpha='coverage' needs pictures with samples > 1" % who)
         if self._chained:
             raise RuntimeError("%s: to be called before the first prepare / submit" % who)
         n = self.batch * po.views
-        self.jpeg_bytes = torch.empty((n, jpeg.capacity_for(*po.res)), dtype=torch.uint8, device=self.device)
-        self.jpeg_info = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
-        self.jpeg = jpeg
+        out = torch.empty((n, jpeg.capacity_for(*po.res)), dtype=torch.uint8, device=self.device)
+        info = torch.zeros((n, 2), dtype=torch.int32, device=self.device)
+        if isinstance(jpeg, Jpeg):
+            self.jpeg_bytes, self.jpeg_info, self.jpeg = out, info, jpeg
+            return
+        if jpeg.alpha == "subject":
+            self.png_alpha = torch.empty((self.batch, po.views) + po.res, dtype=torch.float32, device=self.device)
+        self.png_bytes, self.png_info, self.png = out, info, jpeg
 
     def _encode_pictures(self, n):
         """One mp_picture_jpeg over the n active frames' pictures: they are one contiguous [n * views,H,W,3] block."""
@@ -630,6 +644,49 @@ class FrameSlot:
         rows = n * po.views
         ops.picture_jpeg_raw(self.pictures_image[:n].view((rows,) + po.res + (3,)), j.quality, j.subsampling, j.restart,
                              out=self.jpeg_bytes[:rows], info=self.jpeg_info[:rows])
+
+    def _png_planes(self, n):
+        """(planes, alpha) of the n active frames for mp_picture_png: contiguous views of the slot's buffers."""
+        from .recon import _subject_alpha
+        po, p = self.picture_options, self.png
+        rows = (n * po.views,) + po.res
+        alpha = None
+        if p.alpha == "coverage":
+            alpha = self.pictures_coverage[:n].view(rows)
+        elif p.alpha == "subject":
+            mask = None if self.pictures_mask is None else self.pictures_mask[:n]
+            alpha = _subject_alpha(mask, self.pictures_face[:n], out=self.png_alpha[:n]).view(rows)
+        if p.plane == "depth":
+            return self.pictures_depth[:n].view(rows), alpha
+        return self.pictures_image[:n].view(rows + (3,)), alpha
+
+    def _encode_png(self, n):
+        """One mp_picture_png over the n active frames' pictures."""
+        from .recon import _png_raw
+        rows = n * self.picture_options.views
+        planes, alpha = self._png_planes(n)
+        _png_raw(self.png, planes, alpha, out=self.png_bytes[:rows], info=self.png_info[:rows])
+
+    def _encoded(self, out, info, encode):
+        """The files an encoding call of the chain left in ``out`` / ``info`` for the current submission: a list of
+        ``n_active`` entries, each a list of ``views`` ``bytes``, or None where ``pictures()`` gives None.  One
+        device-to-host copy of ``info`` and one of the used prefixes of ``out``.  A frame whose mesh ``meshes()`` made
+        again, or one of whose files exceeded the capacity, is encoded from the picture ``pictures()`` returns
+        (``encode(picture)``): the same bytes a sufficient capacity gives."""
+        from .recon import _collect_files
+        pictures = self.pictures()
+        v = self.picture_options.views
+        rows = self.n_active * v
+        info = info[:rows].cpu().numpy()
+        again = [pic is not None and (b in self._reran or bool(info[b * v:(b + 1) * v, 1].any()))
+                 for b, pic in enumerate(pictures)]
+        mine = info.copy()
+        for b, pic in enumerate(pictures):
+            if pic is None or again[b]:
+                mine[b * v:(b + 1) * v] = (0, 0)  # nothing of these rows is copied
+        files = _collect_files(type(self).__name__, out, mine, None)
+        return [None if pic is None else (encode(pic) if again[b] else files[b * v:(b + 1) * v])
+                for b, pic in enumerate(pictures)]
 
     def jpegs(self):
         """The JPEG files of the current submission's pictures, to be called after ``wait()`` (it waits if the caller
@@ -640,21 +697,16 @@ class FrameSlot:
         capacity gives."""
         if self.jpeg is None:
             raise RuntimeError("%s.jpegs(): encode_pictures(jpeg) was never called on this slot" % type(self).__name__)
-        from .recon import _collect_jpegs, encode_jpeg
-        pictures = self.pictures()
-        v = self.picture_options.views
-        rows = self.n_active * v
-        info = self.jpeg_info[:rows].cpu().numpy()
-        again = [pic is not None and (b in self._reran or bool(info[b * v:(b + 1) * v, 1].any()))
-                 for b, pic in enumerate(pictures)]
-        mine = info.copy()
-        for b, pic in enumerate(pictures):
-            if pic is None or again[b]:
-                mine[b * v:(b + 1) * v] = (0, 0)  # nothing of these rows is copied
-        shape = (rows,) + self.picture_options.res + (3,)
-        files = _collect_jpegs(self.pictures_image[:self.n_active].view(shape), self.jpeg_bytes, mine, self.jpeg)
-        return [None if pic is None else (encode_jpeg(pic.image, self.jpeg) if again[b] else files[b * v:(b + 1) * v])
-                for b, pic in enumerate(pictures)]
+        from .recon import encode_jpeg
+        return self._encoded(self.jpeg_bytes, self.jpeg_info, lambda pic: encode_jpeg(pic.image, self.jpeg))
+
+    def pngs(self):
+        """The PNG files of the current submission's pictures: what ``jpegs()`` is for a ``recon.Jpeg``, for the slot's
+        ``recon.Png``, with ``recon.encode_png`` for the frames that are encoded again."""
+        if self.png is None:
+            raise RuntimeError("%s.pngs(): encode_pictures(png) was never called on this slot" % type(self).__name__)
+        from .recon import encode_png
+        return self._encoded(self.png_bytes, self.png_info, lambda pic: encode_png(pic, self.png))
 
     def _rerun_picture(self, b, mesh):
         """Frame b again from its re-run ``Mesh``, into fresh tensors: the bodies of ``_render_pictures`` on the

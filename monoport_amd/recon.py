@@ -1250,9 +1250,9 @@ def _jpeg_images(who, pictures):
     return (image[None] if image.dim() == 3 else image).contiguous(), image.dim() == 3
 
 
-def _collect_jpegs(images, out, info, jpeg):
-    """The files of ``images`` [n,H,W,3] from what mp_picture_jpeg left in ``out`` [n,capacity] under the HOST rows
-    ``info`` [n,2]: one copy of the used prefixes; a picture that overflowed is encoded again alone at the size the
+def _collect_files(who, out, info, again):
+    """The files that an encoding call left in ``out`` [n,capacity] under the HOST rows ``info`` [n,2]: one copy of the
+    used prefixes; a picture that overflowed is encoded again alone, ``again(i, size)`` -> (out, info) at the size the
     device reported, which gives the bytes a sufficient capacity would have given."""
     fits = [i for i in range(len(info)) if not info[i][1]]
     used = max([int(info[i][0]) for i in fits], default=0)
@@ -1261,15 +1261,20 @@ def _collect_jpegs(images, out, info, jpeg):
     for i in range(len(info)):
         size = int(info[i][0])
         if info[i][1]:
-            again, again_info = ops.picture_jpeg_raw(images[i:i + 1], jpeg.quality, jpeg.subsampling, jpeg.restart,
-                                                     capacity=size)
+            bytes_again, again_info = again(i, size)
             row = again_info.cpu().numpy()[0]
             if tuple(row) != (size, 0):
-                raise RuntimeError("encode_jpeg: a picture of %d bytes gave %s at that capacity" % (size, tuple(row)))
-            files.append(again[0].cpu().numpy().tobytes())
+                raise RuntimeError("%s: a picture of %d bytes gave %s at that capacity" % (who, size, tuple(row)))
+            files.append(bytes_again[0].cpu().numpy().tobytes())
         else:
             files.append(host[i, :size].tobytes())
     return files
+
+
+def _collect_jpegs(images, out, info, jpeg):
+    """``_collect_files`` for what mp_picture_jpeg left of ``images`` [n,H,W,3]."""
+    return _collect_files("encode_jpeg", out, info, lambda i, size: ops.picture_jpeg_raw(
+        images[i:i + 1], jpeg.quality, jpeg.subsampling, jpeg.restart, capacity=size))
 
 
 def encode_jpeg(pictures, jpeg=None):
@@ -1286,6 +1291,146 @@ def encode_jpeg(pictures, jpeg=None):
     out, info = ops.picture_jpeg_raw(images, jpeg.quality, jpeg.subsampling, jpeg.restart,
                                      capacity=jpeg.capacity_for(int(images.shape[1]), int(images.shape[2])))
     files = _collect_jpegs(images, out, info.cpu().numpy(), jpeg)
+    return files[0] if single else files
+
+
+class Png:
+    """How pictures are encoded losslessly on the device (mp_picture_png in include/monoport_hip.h: this library's own
+    deflate inside a standard PNG container, byte for byte defined; the reference's .png files).  ``filter``: "none",
+    "sub", "up", "average", "paeth", or "adaptive" (per scanline the smallest sum of absolute values, the default).
+    ``alpha``: None = 8-bit RGB; "coverage" = 8-bit RGBA with a ``ResolvedPicture``'s coverage (``samples`` > 1);
+    "subject" = RGBA with 1.0 where the mask says subject (2) -- without a mask where a face shows -- else 0.0.
+    ``unmatte``: None, or the background value the pictures were rendered over: the colour then becomes the subject's
+    own, (c - (1 - a) * unmatte) / a, so that the file composites over anything.  ``plane="depth"`` with
+    ``depth_range=(lo, hi)`` writes the depth picture as 16-bit grey, (d - lo) / (hi - lo) clamped to [0, 1] times 65535,
+    and refuses alpha.  ``capacity``: bytes reserved per picture, at least 57; None = ``4096 + raw // 2`` with raw the
+    bytes of the samples, never more than ``ops.png_max_bytes``.  A file that does not fit is reported by the device
+    and encoded again alone at its exact size: the capacity never changes the bytes.  Everything is validated here; a
+    Png holds host values only."""
+
+    def __init__(self, filter="adaptive", alpha=None, unmatte=None, plane="image", depth_range=None, capacity=None):
+        who = "Png"
+        if plane not in ("image", "depth"):
+            raise ValueError("%s: plane must be 'image' or 'depth', got %r" % (who, plane))
+        if alpha not in (None, "coverage", "subject"):
+            raise ValueError("%s: alpha must be None, 'coverage' or 'subject', got %r" % (who, alpha))
+        lo, scale = 0.0, 1.0
+        if plane == "depth":
+            if alpha is not None or unmatte is not None:
+                raise ValueError("%s: plane='depth' is 16-bit grey: it takes no alpha and no unmatte" % who)
+            ok = isinstance(depth_range, (tuple, list)) and len(depth_range) == 2
+            if ok:
+                lo, hi = (ops._finite_float(who, "depth_range", v) for v in depth_range)
+                with np.errstate(all="ignore"):
+                    scale = float(np.float32(1) / (np.float32(hi) - np.float32(lo)))
+                ok = hi > lo and np.isfinite(scale)
+            if not ok:
+                raise ValueError("%s: plane='depth' needs depth_range=(lo, hi) with finite lo < hi, got %r"
+                                 % (who, depth_range))
+            depth_range = (lo, hi)
+        elif depth_range is not None:
+            raise ValueError("%s: depth_range goes with plane='depth'" % who)
+        if unmatte is not None and alpha is None:
+            raise ValueError("%s: unmatte needs an alpha" % who)
+        self.format = "gray16" if plane == "depth" else ("rgb8" if alpha is None else "rgba8")
+        _, flt, self.lo, self.scale, _, bg = ops.png_params(who, self.format, filter, lo, scale, unmatte)
+        self.filter = {v: k for k, v in ops.PNG_FILTERS.items()}[flt]
+        self.alpha, self.plane, self.depth_range = alpha, plane, depth_range
+        self.unmatte = None if unmatte is None else bg
+        if capacity is not None:
+            if (isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer))
+                    or not ops.PNG_MIN_BYTES <= capacity <= 2 ** 31):
+                raise ValueError("%s: capacity must be None or an int in %d..2^31 bytes, got %r"
+                                 % (who, ops.PNG_MIN_BYTES, capacity))
+            capacity = int(capacity)
+        self.capacity = capacity
+
+    def capacity_for(self, h, w):
+        """Bytes reserved per [h,w] picture."""
+        if self.capacity is not None:
+            return self.capacity
+        raw = h * w * {"rgb8": 3, "rgba8": 4, "gray16": 2}[self.format]
+        return min(4096 + raw // 2, ops.png_max_bytes(h, w, self.format))
+
+
+def picture_u16(depth, lo=0.0, hi=1.0):
+    """``depth`` float32 [...] -> uint16 of the same shape on the device: (int)(clamp((d - lo) / (hi - lo), 0, 1) * 65535
+    + 0.5) with the scale 1 / (hi - lo) taken once in f32, a NaN gives 0: the samples of ``Png(plane="depth",
+    depth_range=(lo, hi))``.  No host sync."""
+    p = Png(plane="depth", depth_range=(lo, hi))
+    return ops.picture_u16_raw(depth, p.lo, p.scale)
+
+
+def picture_rgba8(image, alpha, unmatte=None):
+    """``image`` float32 [...,3] and ``alpha`` float32 [...] -> uint8 [...,4] on the device: the samples of an RGBA
+    ``Png`` (``unmatte``: None, or the background the colour is freed of).  No host sync."""
+    return ops.picture_rgba8_raw(image, alpha, unmatte)
+
+
+def _subject_alpha(mask, face, out=None):
+    """1.0 where the mask says subject (2) -- without a mask where a face shows --, else 0.0: one op on the stream."""
+    if out is None:
+        out = torch.empty((face if mask is None else mask).shape, dtype=torch.float32,
+                          device=(face if mask is None else mask).device)
+    return torch.ge(face, 0, out=out) if mask is None else torch.eq(mask, 2, out=out)
+
+
+def _png_inputs(who, pictures, png, alpha):
+    """(planes [n,H,W,3] or [n,H,W] contiguous float32, alpha [n,H,W] or None, whether ``pictures`` was one picture)."""
+    plain = torch.is_tensor(pictures)
+    depth = png.plane == "depth"
+    if plain:
+        plane = pictures
+    else:
+        plane = getattr(pictures, "depth" if depth else "image", None) if hasattr(pictures, "face") else pictures
+        if plane is None and hasattr(pictures, "face"):
+            raise ValueError("%s: the picture has no image (it was rendered with shade=None)" % who)
+    dims = (2, 3) if depth else (3, 4)
+    if (not torch.is_tensor(plane) or plane.dtype != torch.float32 or plane.dim() not in dims
+            or (not depth and plane.shape[-1] != 3)):
+        raise ValueError("%s: pictures must be a MeshRender, a ScenePicture, a ResolvedPicture or a float32 tensor %s"
+                         % (who, "[H,W] / [n,H,W]" if depth else "[H,W,3] / [n,H,W,3]"))
+    single = plane.dim() == dims[0]
+    if alpha is not None:
+        if not plain or png.alpha is None:
+            raise ValueError("%s: the alpha keyword goes with a plain image tensor and a Png with an alpha" % who)
+        want = tuple(plane.shape[:-1])
+        if (not torch.is_tensor(alpha) or alpha.dtype != torch.float32 or tuple(alpha.shape) != want
+                or alpha.device != plane.device):
+            raise ValueError("%s: alpha must be a float32 tensor %s on %s" % (who, want, plane.device))
+    elif png.alpha is not None:
+        if plain:
+            raise ValueError("%s: a plain tensor needs the alpha keyword for a Png with alpha=%r" % (who, png.alpha))
+        if png.alpha == "coverage":
+            alpha = getattr(pictures, "coverage", None)
+            if alpha is None:
+                raise ValueError("%s: alpha='coverage' needs a ResolvedPicture (samples > 1)" % who)
+        else:
+            alpha = _subject_alpha(getattr(pictures, "mask", None), pictures.face)
+    lead = (lambda t: (t[None] if single else t).contiguous())
+    return lead(plane), None if alpha is None else lead(alpha), single
+
+
+def _png_raw(png, planes, alpha, **kw):
+    return ops.picture_png_raw(planes, alpha, png.format, png.filter, png.lo, png.scale, png.unmatte, **kw)
+
+
+def encode_png(pictures, png=None, alpha=None):
+    """The PNG files of ``pictures`` (what ``encode_jpeg`` takes, or a ``ResolvedPicture``; with ``plane="depth"`` the
+    depth picture, or a float32 tensor [H,W] / [n,H,W]) under ``png`` (a ``Png``; None: its defaults), encoded on the
+    device: ``bytes`` for one picture, a list of ``bytes`` for n.  ``alpha``: for a plain image tensor and a ``Png`` with
+    an alpha, the float32 [H,W] / [n,H,W] tensor that is it.  One device-to-host copy of the sizes, then one of the used
+    prefixes; a picture whose file exceeded ``png``'s capacity is encoded again alone at the size the device reported.
+    zlib and any PNG reader give back exactly the 8-bit or 16-bit samples; tests/png_ref.py restates the files byte for
+    byte."""
+    who = "encode_png"
+    png = Png() if png is None else png
+    if not isinstance(png, Png):
+        raise ValueError("%s: png must be a recon.Png, got %r" % (who, type(png).__name__))
+    planes, alpha, single = _png_inputs(who, pictures, png, alpha)
+    out, info = _png_raw(png, planes, alpha, capacity=png.capacity_for(int(planes.shape[1]), int(planes.shape[2])))
+    files = _collect_files(who, out, info.cpu().numpy(), lambda i, size: _png_raw(
+        png, planes[i:i + 1], None if alpha is None else alpha[i:i + 1], capacity=size))
     return files[0] if single else files
 
 

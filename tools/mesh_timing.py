@@ -102,6 +102,13 @@ where Pillow is importable, the way to a JPEG without it: ``pictures()``, ``.cpu
 
     python tools/mesh_timing.py --jpeg [--passes 5] [--out profiles/mesh_jpeg_timing.json]
 
+``--png`` measures the lossless encoding (profiles/mesh_png_timing.json): mp_picture_png alone, per picture in a batch
+of 20 lit pictures at 257^2 and 1024^2 for 8-bit RGB, 8-bit RGBA (the subject's mask as alpha) and the 16-bit depth, with
+the median file size; then the 20-frame lit slot with ``pngs()`` as the consumer against ``pictures()``, ``.cpu()`` and
+Pillow ``save(compress_level=6)`` on the host, alternated in one session.
+
+    python tools/mesh_timing.py --png [--passes 5] [--out profiles/mesh_png_timing.json]
+
 ``--samples`` measures anti-aliasing (profiles/mesh_samples_timing.json): mp_picture_resolve_batch alone, per picture
 in a batch of 20 composited pictures (image, depth, face ids and mask in; all five planes out) at the final sizes 257^2
 and 1024^2 for ``samples`` = 2 and 4, with the achieved GB/s (bytes read plus bytes written), beside a device-to-device
@@ -156,6 +163,7 @@ def main():
     ap.add_argument("--lighting", action="store_true", help="the --shadow slots without and with lighting= on the subject")
     ap.add_argument("--transfer", action="store_true", help="bits, transfer and shade per mesh; lit slots with transfer=")
     ap.add_argument("--jpeg", action="store_true", help="mp_picture_jpeg alone; the --lighting slots with encode_pictures")
+    ap.add_argument("--png", action="store_true", help="mp_picture_png alone; the --lighting slots with a recon.Png")
     ap.add_argument("--samples", action="store_true", help="mp_picture_resolve alone; the --jpeg slots at samples 1 / 2 / 4")
     a = ap.parse_args()
     if a.out is None:
@@ -167,6 +175,7 @@ def main():
                              "mesh_lighting_timing.json" if a.lighting else
                              "mesh_transfer_timing.json" if a.transfer else
                              "mesh_jpeg_timing.json" if a.jpeg else
+                             "mesh_png_timing.json" if a.png else
                              "mesh_samples_timing.json" if a.samples else
                              "mesh_smooth_timing.json" if a.smooth else
                              "mesh_simplify_timing.json" if a.simplify else
@@ -186,6 +195,9 @@ def main():
         return
     if a.jpeg:
         write(a, slot_jpeg(a))
+        return
+    if a.png:
+        write(a, slot_png(a))
         return
     if a.samples:
         out = resolve_kernels(a)
@@ -695,6 +707,80 @@ def slot_jpeg(a, frames=20):
     for res in ("257", "1024"):
         out["encode_%s_jpegs_minus_pictures_ms" % res] = round(
             out["encode_%s_jpegs" % res]["median_ms"] - out["pictures_" + res]["median_ms"], 4)
+    return out
+
+
+def slot_png(a, frames=20):
+    """mp_picture_png alone on a batch of ``frames`` lit pictures (ms per picture, bytes per file) at 257^2 and 1024^2
+    for RGB8, RGBA8 (alpha: the subject's mask) and GRAY16 (the depth over 0..6); then the --lighting slots without and
+    with a ``recon.Png``, with ``pictures()`` against ``pngs()`` as the consumer (ms per frame of a submission), and the
+    way to a PNG without the feature: ``pictures()``, ``.cpu()``, Pillow ``save(compress_level=6)`` on the host."""
+    import io
+    from PIL import Image
+    direction = (0.4, -1.0, 0.3)
+    sun = recon.Light.directional(direction, (-1.5, -0.9, -1.5), (1.5, 1.0, 1.5), res=512, radius=1)
+    floor, cam, mesh, base = _scene_setup(sun)
+    sh = np.random.RandomState(0).uniform(-0.2, 0.4, (9, 3)).astype(np.float32)
+    sh[0] += 0.8
+    lighting = recon.Lighting(sh, direct=(direction, (0.9, 0.85, 0.8)), frame="camera", albedo=(0.8, 0.7, 0.6),
+                              self_shadow=0.02)
+    png = recon.Png()
+    rows = []
+    for res in (257, 1024):
+        opts = dict(base, res=res, scene=floor)
+        rows.append(("pictures_%d" % res, mesh, opts, cam, dict(lighting=lighting)))
+        rows.append(("encode_%d" % res, mesh, opts, cam, dict(lighting=lighting, encode_pictures=png)))
+    pipes, fn = _slot_pipes(frames, 1, rows)
+
+    def on_host(s):
+        files = []
+        for pic in s.pictures():
+            u8 = (pic.image.clamp(0, 1) * 255 + 0.5).to(torch.uint8).cpu().numpy()
+            for v in range(u8.shape[0]):
+                buf = io.BytesIO()
+                Image.fromarray(u8[v]).save(buf, "PNG", compress_level=6)
+                files.append(buf.getvalue())
+        return files
+
+    ways = {}
+    for res in (257, 1024):
+        ways["pictures_%d" % res] = fn("pictures_%d" % res)
+        ways["encode_%d_pictures" % res] = fn("encode_%d" % res)
+        ways["encode_%d_pngs" % res] = fn("encode_%d" % res, lambda s: s.pngs())
+        ways["host_pillow_%d" % res] = fn("pictures_%d" % res, on_host)
+    out = {"frames_per_slot": frames, "unit": "ms per frame", "filter": "adaptive",
+           "slots": "the --lighting slots: one view, the floor with its light, clay lighting with the self-shadow",
+           "consumers": "pictures(): views of the device buffers; pngs(): the files as bytes on the host; host_pillow: "
+                        "pictures(), 8 bit on the device, .cpu(), Pillow save at compress_level 6"}
+    out.update(alternate(ways, a.passes, frames))
+    kernels = {}
+    out["file_bytes"] = {}
+    for res in (257, 1024):
+        slot = pipes["encode_%d" % res].slots[0]
+        out["file_bytes"]["%d_rgb8_slot" % res] = stats([len(f[0]) for f in slot.pngs()])["median_ms"]
+        out["file_bytes"]["%d_rgb8_pillow" % res] = float(np.median([len(f) for f in on_host(slot)]))
+        planes = {"rgb8": (slot.pictures_image[:frames].reshape(frames, res, res, 3).clone(), None),
+                  "gray16": (slot.pictures_depth[:frames].reshape(frames, res, res).clone(), None)}
+        planes["rgba8"] = (planes["rgb8"][0], (slot.pictures_mask[:frames].reshape(frames, res, res) == 2).float())
+        for fmt, (images, alpha) in planes.items():
+            cap = 4096 + res * res * {"rgb8": 3, "rgba8": 4, "gray16": 2}[fmt] // 2
+            bufs = (torch.empty((frames, cap), dtype=torch.uint8, device=DEV),
+                    torch.empty((frames, 2), dtype=torch.int32, device=DEV))
+            name = "mp_picture_png_%d_%s" % (res, fmt)
+            kernels[name] = (lambda images=images, alpha=alpha, fmt=fmt, bufs=bufs: ops.picture_png_raw(
+                images, alpha, fmt, "adaptive", 0.0, 1.0 / 6.0, out=bufs[0], info=bufs[1]))
+            info = kernels[name]()[1].cpu().numpy()
+            assert not info[:, 1].any()
+            out["file_bytes"]["%d_%s" % (res, fmt)] = float(np.median(info[:, 0]))
+    for p_ in pipes.values():
+        p_.close()
+    out["kernels_unit"] = "ms per picture, a batch of %d" % frames
+    out["kernels"] = alternate(kernels, a.passes, frames)
+    for res in ("257", "1024"):
+        out["encode_%s_pngs_minus_pictures_ms" % res] = round(
+            out["encode_%s_pngs" % res]["median_ms"] - out["pictures_" + res]["median_ms"], 4)
+        out["pngs_over_host_pillow_%s" % res] = round(
+            out["encode_%s_pngs" % res]["median_ms"] / out["host_pillow_" + res]["median_ms"], 4)
     return out
 
 
