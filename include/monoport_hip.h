@@ -1237,6 +1237,92 @@ int mp_picture_png(mp_ctx *ctx, const float *images, const float *alpha, int n, 
                    float lo, float scale, int unmatte, float background, uint8_t *out, int64_t capacity, int32_t *info,
                    mp_stream stream);
 
+/* Meshes as bytes (the reference writes .obj text on the host, mesh_util.save_obj_mesh*): the binary glTF 2.0 file
+ * (.glb) of a mesh as the chain leaves it, quantised under KHR_mesh_quantization and laid out on the device.  No entropy
+ * coder: every stage is a stream.  As for JPEG and PNG the definition is this library's own, byte for byte, the same
+ * bytes in every run; tests/glb_ref.py restates it in numpy and reads the files back by the glTF specification alone.
+ *   Counts: nv = min(max(counts[0], 0), max_verts), nf = min(max(counts[1], 0), max_faces), as in mp_mesh_smooth.  The
+ * attribute set is `flags`: MP_GLB_NORMALS (normals given), MP_GLB_COLORS (colors given).
+ *   Container: the 12-byte header ("glTF", uint32 2, uint32 total length), one chunk (uint32 length, "JSON", the text)
+ * padded with spaces to the next length L with L % 8 == 4 -- a multiple of 4, and the binary data then starts at a
+ * multiple of 8 in the file --, one chunk (uint32 length, "BIN\0", the data) padded with zeros to 4 bytes.  All
+ * integers little-endian.  EMPTY mesh (nv == 0 or nf == 0; a gated-off frame's counts are {0, 0}): the fixed file of
+ * MP_GLB_MIN_BYTES = 100 bytes, the header and the JSON chunk
+ *   {"asset":{"version":"2.0","generator":"monoport_amd"},"scene":0,"scenes":[{}]}
+ * padded with two spaces; no BIN chunk.
+ *   JSON of a mesh, without any white space but the padding of the numbers, in this order, where [N] is present with
+ * MP_GLB_NORMALS, [C] with MP_GLB_COLORS, k = the number of attributes (1..3) and c = k - 1:
+ *   {"asset":{"version":"2.0","generator":"monoport_amd"},"extensionsUsed":["KHR_mesh_quantization"],
+ *   "extensionsRequired":["KHR_mesh_quantization"],"scene":0,"scenes":[{"nodes":[0]}],
+ *   "nodes":[{"mesh":0,"translation":[T,T,T],"scale":[S,S,S]}],"materials":[{"doubleSided":true}],
+ *   "meshes":[{"primitives":[{"attributes":{"POSITION":0[N: ,"NORMAL":1][C: ,"COLOR_0":c]},"indices":k,"material":0,
+ *   "mode":4}]}],"accessors":[
+ *   {"bufferView":0,"componentType":5123,"count":<nv>,"type":"VEC3","min":[<m>,<m>,<m>],"max":[<m>,<m>,<m>]}
+ *   [N: ,{"bufferView":1,"componentType":5120,"normalized":true,"count":<nv>,"type":"VEC3"}]
+ *   [C: ,{"bufferView":c,"componentType":5121,"normalized":true,"count":<nv>,"type":"VEC3"}]
+ *   ,{"bufferView":k,"componentType":<ct>,"count":<3 nf>,"type":"SCALAR"}],"bufferViews":[
+ *   {"buffer":0,"byteOffset":<o>,"byteLength":<l>,"byteStride":8,"target":34962}
+ *   [N: ,{"buffer":0,"byteOffset":<o>,"byteLength":<l>,"byteStride":4,"target":34962}]
+ *   [C: ,{"buffer":0,"byteOffset":<o>,"byteLength":<l>,"byteStride":4,"target":34962}]
+ *   ,{"buffer":0,"byteOffset":<o>,"byteLength":<l>,"target":34963}],"buffers":[{"byteLength":<b>}]}
+ * (the line breaks above are not part of the text).  T = b_min[a] and S = (b_max[a] - b_min[a]) / 65535 in double from
+ * the host's f32 box, printed as %24.17g.  Every number in <> depends on the mesh and is a right-aligned decimal
+ * padded with leading spaces to a fixed width: 10 for counts, offsets and lengths, 4 for <ct> (5123 UNSIGNED_SHORT or
+ * 5125 UNSIGNED_INT), 5 for <m>.  The text has a constant length per attribute set: the host builds it once per call
+ * and the device fills the numbers in.  The winding of the chain is kept; the material is double-sided.
+ *   Views, in the order positions, normals, colours, indices, back to back (each starts at a multiple of 4):
+ * positions 8 nv bytes, normals 4 nv, colours 4 nv, indices 6 nf (16-bit) or 12 nf bytes; <b> = the BIN chunk's
+ * length = their sum rounded up to 4.  mp_glb_bytes(nv, nf, flags) = 12 + 8 + L(flags) + 8 + <b>, or MP_GLB_MIN_BYTES
+ * for an empty mesh, or 0 for negative counts or unknown flags; mp_glb_max_bytes(max_verts, max_faces, flags) =
+ * mp_glb_bytes at the capacities: what no mesh within them exceeds.
+ *   POSITION: UNSIGNED_SHORT VEC3, not normalised, 8 bytes per vertex: x, y, z, and a zero uint16.  Per axis
+ * inv_a = 65535.0f / (b_max[a] - b_min[a]) in f32 on the host; t = (x - b_min[a]) * inv_a as two separately rounded f32
+ * operations (no FMA); q = t > 0 ? (t < 65535 ? (int)(t + 0.5f) : 65535) : 0, so a NaN gives 0.  The node's translation
+ * and scale take q back into the box.  <m>: min and max are the exact extremes of q per axis over the nv vertices.
+ *   NORMAL: BYTE VEC3, normalised, 4 bytes per vertex: x, y, z, and a zero byte.  t = n != n ? 0 : (n > -1 ? (n < 1 ?
+ * n : 1) : -1); q = (int)((t * 127.0f) + (t < 0 ? -0.5f : 0.5f)), two operations.
+ *   COLOR_0: UNSIGNED_BYTE VEC3, normalised, 4 bytes per vertex: r, g, b, and a zero byte.  c = (p * color_scale) +
+ * color_bias in two operations, then step 1 of the JPEG definition (mp_picture_u8) on c.  colors is [max_verts,3]
+ * (MP_GLB_COLOR_ROWS) or [3,max_verts] (MP_GLB_COLOR_PLANES): the chain's raw netC predictions as planes with (0.5, 0.5)
+ * give the bytes of the finished colours as rows with (1, 0).
+ *   Indices: UNSIGNED_SHORT if nv <= 65535 (index 65535 then never occurs), else UNSIGNED_INT: chosen per mesh on the
+ * device.  Faces and corners keep their order.  An index i becomes min(max(i, 0), nv - 1); the chain makes none outside.
+ *   mp_mesh_glb: verts f32 [max_verts,3], faces int32 [max_faces,3], counts device int32[2], normals f32 [max_verts,3]
+ * or NULL, colors f32 or NULL, b_min / b_max HOST float[3].  out, capacity, info and overflow are those of
+ * mp_picture_jpeg, word for word: out [n,capacity] bytes, info int32 [n,2] = {bytes of file f, overflowed}; the size is
+ * known on the device before any byte is written, a mesh whose file exceeds capacity writes NOTHING and reports the
+ * size it needs, the others are unaffected, no store lands past capacity under any input, and a second call at the
+ * reported size gives the bytes a sufficient capacity gives.  Bytes of a row beyond its file are not written.
+ *   Three launches for all frames (sizes, info and the reset of the extremes; the attributes and indices with the
+ * extremes by a wave reduction and integer atomics into 64 partial slots per frame; the slots joined, the header and
+ * the JSON with its numbers), nothing allocated, no host value, asynchronous; 8 KB per frame of the stream's scratch
+ * arena (64 slots of one 128-byte line), every word that is read written before.  Rows of `out` that are 4-byte aligned in memory are written in whole dwords (8 bytes per position); any other
+ * row byte by byte, to the same bytes.
+ *   Refusals (a message, nothing launched): n_frames outside 1..mp_max_frames(), a negative capacity of vertices or
+ * faces, a NULL or misaligned (4 bytes; out: any) buffer (verts / normals / colors may be NULL with max_verts == 0,
+ * faces with max_faces == 0), an output overlapping an input or the other output, a non-finite box or one without
+ * b_max > b_min on an axis or too thin for inv_a to be finite, a non-finite color_scale or color_bias, an unknown
+ * color_layout, capacity below MP_GLB_MIN_BYTES or above 2^31: MP_ERR_ARG; capacities for which mp_glb_max_bytes
+ * reaches 2^31: MP_ERR_UNSUPPORTED. */
+#define MP_GLB_MIN_BYTES 100
+enum { MP_GLB_NORMALS = 1, MP_GLB_COLORS = 2 };
+enum { MP_GLB_COLOR_ROWS = 0, MP_GLB_COLOR_PLANES = 1 };
+int64_t mp_glb_bytes(int64_t nv, int64_t nf, int flags);
+int64_t mp_glb_max_bytes(int64_t max_verts, int64_t max_faces, int flags);
+int mp_mesh_glb(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                const int32_t *counts, const float *normals, const float *colors, int color_layout, float color_scale,
+                float color_bias, const float *b_min, const float *b_max, uint8_t *out, int64_t capacity, int32_t *info,
+                mp_stream stream);
+/* The call above over n_frames (1..mp_max_frames(), else MP_ERR_ARG) meshes of one capacity in the same three
+ * launches: verts / faces / counts are HOST arrays of n_frames device pointers, normals / colors such arrays or NULL
+ * as a whole; out [n_frames,capacity], info [n_frames,2].  Frame f's bytes and info equal the single call's BIT FOR
+ * BIT. */
+int mp_mesh_glb_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                      const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts,
+                      const float *const *normals, const float *const *colors, int color_layout, float color_scale,
+                      float color_bias, const float *b_min, const float *b_max, uint8_t *out, int64_t capacity,
+                      int32_t *info, mp_stream stream);
+
 /* The largest connected body of an occupancy volume [R,R,R] (no counterpart in the reference; the clean-up in front
  * of marching cubes that drops floating blobs).
  *   Foreground: voxels with value > level (marching cubes' "inside"; a NaN and value == level are background).

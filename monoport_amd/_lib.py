@@ -104,6 +104,9 @@ JPEG_444, JPEG_420 = 0, 1
 # MP_PNG_* formats and filters of mp_picture_png (include/monoport_hip.h)
 PNG_RGB8, PNG_RGBA8, PNG_GRAY16 = 0, 1, 2
 PNG_NONE, PNG_SUB, PNG_UP, PNG_AVERAGE, PNG_PAETH, PNG_ADAPTIVE = 0, 1, 2, 3, 4, 5
+# MP_GLB_* attribute flags and colour layouts of mp_mesh_glb (include/monoport_hip.h)
+GLB_NORMALS, GLB_COLORS = 1, 2
+GLB_COLOR_ROWS, GLB_COLOR_PLANES = 0, 1
 MAX_VIEWS = 8  # MP_MAX_VIEWS: views per mp_query_views / mp_mlp_forward_views call
 MAX_FRAME_VIEWS = 64  # MP_MAX_FRAME_VIEWS = mp_max_frame_views(): frames x views per mp_recon_views_batch call
 MAX_FRAMES = 32  # kMaxFrames (csrc/mp_internal.h) = mp_max_frames(): frames per batched query / recon call
@@ -249,6 +252,12 @@ SIGNATURES = {
     "mp_png_max_bytes": (c_i64, [c_int, c_int, c_int]),
     "mp_picture_png": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_f32, c_f32, c_int, c_f32,
                                c_vp, c_i64, c_vp, c_vp]),
+    "mp_glb_bytes": (c_i64, [c_i64, c_i64, c_int]),
+    "mp_glb_max_bytes": (c_i64, [c_i64, c_i64, c_int]),
+    "mp_mesh_glb": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_int, c_f32, c_f32, c_vp, c_vp,
+                            c_vp, c_i64, c_vp, c_vp]),
+    "mp_mesh_glb_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_int, c_f32, c_f32, c_vp,
+                                  c_vp, c_vp, c_i64, c_vp, c_vp]),
     "mp_volume_bits_words": (c_i64, [c_int]),
     "mp_volume_bits": (c_int, [c_vp, c_vp, c_int, c_f32, c_vp, c_vp]),
     "mp_volume_bits_batch": (c_int, [c_vp, c_int, c_vp, c_int, c_f32, c_vp, c_vp, c_vp]),

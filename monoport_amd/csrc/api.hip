@@ -2038,6 +2038,92 @@ int mp_mesh_smooth_batch(mp_ctx *ctx, int n_frames, const float *const *verts, i
                              iterations, lambda, mu, flags, verts_out, ring, stream);
 }
 
+static bool glb_flags_ok(int flags) { return (flags & ~(MP_GLB_NORMALS | MP_GLB_COLORS)) == 0; }
+
+int64_t mp_glb_bytes(int64_t nv, int64_t nf, int flags) {
+  if (nv < 0 || nf < 0 || nv > (1LL << 40) || nf > (1LL << 40) || !glb_flags_ok(flags)) return 0;
+  return (int64_t)glb_bytes(nv, nf, flags);
+}
+
+int64_t mp_glb_max_bytes(int64_t max_verts, int64_t max_faces, int flags) {
+  return mp_glb_bytes(max_verts, max_faces, flags);
+}
+
+static int mesh_glb_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *verts, int64_t max_verts,
+                            const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts,
+                            const float *const *normals, const float *const *colors, int color_layout,
+                            float color_scale, float color_bias, const float *b_min, const float *b_max, uint8_t *out,
+                            int64_t capacity, int32_t *info, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (!counts || !b_min || !b_max || !out || !info || ((uintptr_t)info & 3u) || max_verts < 0 || max_faces < 0 ||
+      (max_verts > 0 && !verts) || (max_faces > 0 && !faces))
+    return bad_argument(ctx, who);
+  if (color_layout != MP_GLB_COLOR_ROWS && color_layout != MP_GLB_COLOR_PLANES)
+    return fail(ctx, MP_ERR_ARG, "%s: color_layout %d (MP_GLB_COLOR_ROWS or MP_GLB_COLOR_PLANES)", who, color_layout);
+  if (!std::isfinite(color_scale) || !std::isfinite(color_bias))
+    return fail(ctx, MP_ERR_ARG, "%s: a non-finite color_scale or color_bias", who);
+  GlbCall c;
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(b_min[a]) || !std::isfinite(b_max[a]) || !(b_max[a] > b_min[a]))
+      return fail(ctx, MP_ERR_ARG, "%s: the box needs finite bounds with b_max > b_min, got [%g, %g] on axis %d", who,
+                  (double)b_min[a], (double)b_max[a], a);
+    c.b_min[a] = b_min[a], c.b_max[a] = b_max[a];
+    c.inv[a] = 65535.0f / (b_max[a] - b_min[a]);
+    if (!std::isfinite(c.inv[a]))
+      return fail(ctx, MP_ERR_ARG, "%s: the box is too thin on axis %d for 16-bit positions (%g wide)", who, a,
+                  (double)(b_max[a] - b_min[a]));
+  }
+  if (capacity < MP_GLB_MIN_BYTES || capacity > ((int64_t)1 << 31))
+    return fail(ctx, MP_ERR_ARG, "%s: capacity %lld (at least the empty file's %d bytes, at most 2^31)", who,
+                (long long)capacity, MP_GLB_MIN_BYTES);
+  const int flags = (normals ? MP_GLB_NORMALS : 0) | (colors ? MP_GLB_COLORS : 0);
+  if (max_verts > (1LL << 40) || max_faces > (1LL << 40) || glb_bytes(max_verts, max_faces, flags) >= (1LL << 31))
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: capacities of %lld vertices and %lld faces: a file could reach 2^31 bytes",
+                who, (long long)max_verts, (long long)max_faces);
+  if (max_verts == 0) verts = nullptr, normals = nullptr, colors = nullptr;  // rows of a capacity of 0 are not looked at
+  if (max_faces == 0) faces = nullptr;
+  rc = check_frames(ctx, who, n_frames, nullptr, counts, verts, faces, normals, colors);
+  if (rc != MP_OK) return rc;
+  const size_t vbytes = (size_t)max_verts * 12, out_bytes = (size_t)n_frames * (size_t)capacity;
+  const size_t info_bytes = (size_t)n_frames * 8;
+  if (ranges_overlap(out, out_bytes, info, info_bytes)) return fail(ctx, MP_ERR_ARG, "%s: out aliases info", who);
+  const FrameSpans ins[5] = {{verts, vbytes}, {faces, (size_t)max_faces * 12}, {counts, 8}, {normals, vbytes},
+                             {colors, vbytes}};
+  for (int f = 0; f < n_frames; ++f)
+    for (const FrameSpans &k : ins)
+      if (ranges_overlap(out, out_bytes, k.of(f), k.bytes) || ranges_overlap(info, info_bytes, k.of(f), k.bytes))
+        return fail(ctx, MP_ERR_ARG, "%s: out or info aliases an input of frame %d", who, f);
+  DeviceGuard g(ctx->device);
+  c.n_frames = n_frames, c.color_planes = color_layout == MP_GLB_COLOR_PLANES;
+  c.max_v = max_verts, c.max_f = max_faces, c.capacity = capacity;
+  c.color_scale = color_scale, c.color_bias = color_bias;
+  void *scratch = nullptr;
+  rc = ensure_scratch(ctx, (hipStream_t)stream, glb_scratch_bytes(n_frames), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_mesh_glb_batch(ctx, scratch, c, verts, faces, counts, normals, colors, out, info, (hipStream_t)stream);
+}
+
+int mp_mesh_glb(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                const int32_t *counts, const float *normals, const float *colors, int color_layout, float color_scale,
+                float color_bias, const float *b_min, const float *b_max, uint8_t *out, int64_t capacity, int32_t *info,
+                mp_stream stream) {
+  return mesh_glb_checked(ctx, "mp_mesh_glb", 1, &verts, max_verts, &faces, max_faces, &counts,
+                          normals ? &normals : nullptr, colors ? &colors : nullptr, color_layout, color_scale,
+                          color_bias, b_min, b_max, out, capacity, info, stream);
+}
+
+int mp_mesh_glb_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                      const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts,
+                      const float *const *normals, const float *const *colors, int color_layout, float color_scale,
+                      float color_bias, const float *b_min, const float *b_max, uint8_t *out, int64_t capacity,
+                      int32_t *info, mp_stream stream) {
+  return mesh_glb_checked(ctx, "mp_mesh_glb_batch", n_frames, verts, max_verts, faces, max_faces, counts, normals,
+                          colors, color_layout, color_scale, color_bias, b_min, b_max, out, capacity, info, stream);
+}
+
 int mp_mesh_points(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *counts, float *points,
                    int32_t *count_out, mp_stream stream) {
   return mesh_points_checked(ctx, "mp_mesh_points", 1, &verts, max_verts, &counts, &points, &count_out, stream);

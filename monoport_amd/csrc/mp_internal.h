@@ -538,6 +538,21 @@ long long png_max_bytes(int h, int w, int format);
 size_t png_scratch_bytes(const PngCall &c);
 int launch_picture_png(mp_ctx *ctx, void *scratch, const float *images, const float *alpha, const PngCall &c,
                        uint8_t *out, int32_t *info, hipStream_t st);
+// glb.hip: n_frames meshes of one capacity -> n_frames binary glTF files in out [n,capacity] with info [n,2] = {bytes,
+// overflowed}.  normals / colors: nullptr as a whole, or one pointer per frame; inv: 65535 / (b_max - b_min) per axis;
+// scratch: glb_scratch_bytes(n_frames).  glb_bytes: the closed form of the file size (flags: MP_GLB_*, checked by the
+// caller; counts >= 0)
+struct GlbCall {  // host values of one call
+  int n_frames, color_planes;
+  long long max_v, max_f, capacity;
+  float color_scale, color_bias;
+  float b_min[3], b_max[3], inv[3];
+};
+long long glb_bytes(long long nv, long long nf, int flags);
+size_t glb_scratch_bytes(int n_frames);
+int launch_mesh_glb_batch(mp_ctx *ctx, void *scratch, const GlbCall &c, const float *const *verts,
+                          const int32_t *const *faces, const int32_t *const *counts, const float *const *normals,
+                          const float *const *colors, uint8_t *out, int32_t *info, hipStream_t st);
 #ifdef __HIPCC__
 // v / |v|, or (0, 0, 0) where |v|^2 is not finite or not > 0 (a zero, a NaN, an inf, an overflow)
 __device__ __forceinline__ void light_normalise(float x, float y, float z, float &ox, float &oy, float &oz) {

@@ -1463,6 +1463,94 @@ def mesh_smooth_raw_batch(verts, faces, counts, iterations, lam=0.5, mu=-0.53, p
     return _mesh_smooth("mesh_smooth_raw_batch", verts, faces, counts, iterations, lam, mu, pin_border, out, ring)
 
 
+# MP_GLB_* (include/monoport_hip.h)
+GLB_COLOR_LAYOUTS = {"rows": _lib.GLB_COLOR_ROWS, "planes": _lib.GLB_COLOR_PLANES}
+GLB_MIN_BYTES = 100  # MP_GLB_MIN_BYTES: the empty file
+
+
+def _glb_flags(normals, colors):
+    return (_lib.GLB_NORMALS if normals else 0) | (_lib.GLB_COLORS if colors else 0)
+
+
+def glb_bytes(nv, nf, normals=True, colors=True):
+    """mp_glb_bytes: the size of the binary glTF file of a mesh of ``nv`` vertices and ``nf`` faces with or without
+    normals and colours -- a closed form (include/monoport_hip.h); the empty file's 100 bytes if either count is 0."""
+    for v in (nv, nf):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError("glb_bytes: nv and nf must be ints >= 0, got %r and %r" % (nv, nf))
+    return int(_lib.load().mp_glb_bytes(int(nv), int(nf), _glb_flags(normals, colors)))
+
+
+def glb_max_bytes(max_verts, max_faces, normals=True, colors=True):
+    """mp_glb_max_bytes: what no file of a mesh within these capacities exceeds: ``glb_bytes`` at the capacities."""
+    for v in (max_verts, max_faces):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError("glb_max_bytes: the capacities must be ints >= 0, got %r and %r" % (max_verts, max_faces))
+    return int(_lib.load().mp_glb_max_bytes(int(max_verts), int(max_faces), _glb_flags(normals, colors)))
+
+
+def _mesh_glb(who, verts, faces, counts, normals, colors, color_layout, color_scale, color_bias, b_min, b_max,
+              capacity, out, info):
+    n, max_v, max_f, dev = _mesh_frames(who, verts, faces, counts)
+    layout = _named_mode(who, "color_layout", GLB_COLOR_LAYOUTS, color_layout)
+    scale, bias = _finite_float(who, "color_scale", color_scale), _finite_float(who, "color_bias", color_bias)
+    if normals is not None:
+        normals = _frame_rows(who, "normals", normals, n, (max_v, 3), torch.float32, dev)
+    if colors is not None:
+        colors = _frame_rows(who, "colors", colors, n, (3, max_v) if layout == _lib.GLB_COLOR_PLANES else (max_v, 3),
+                             torch.float32, dev)
+    if out is not None:
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != n
+                or not out.is_contiguous() or out.device != dev):
+            raise ValueError("%s: out must be a contiguous uint8 tensor [%d,capacity] on %s" % (who, n, dev))
+        if capacity is not None and int(capacity) != out.shape[1]:
+            raise ValueError("%s: capacity %r against an out of %d bytes per mesh" % (who, capacity, out.shape[1]))
+        capacity = int(out.shape[1])
+    elif capacity is None:
+        capacity = glb_max_bytes(max_v, max_f, normals is not None, colors is not None)
+    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < GLB_MIN_BYTES:
+        raise ValueError("%s: capacity must be an int >= the empty file's %d bytes, got %r"
+                         % (who, GLB_MIN_BYTES, capacity))
+    if info is None:
+        info = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    elif (not isinstance(info, torch.Tensor) or info.dtype != torch.int32 or tuple(info.shape) != (n, 2)
+          or not info.is_contiguous() or info.device != dev):
+        raise ValueError("%s: info must be a contiguous int32 tensor [%d,2] on %s" % (who, n, dev))
+    if out is None:
+        out = torch.empty((n, int(capacity)), dtype=torch.uint8, device=dev)
+    ctx = get_context(dev)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_mesh_glb_batch(
+            ctx.handle, f1 - f0, _ptr_array(verts[f0:f1]), max_v, _ptr_array(faces[f0:f1]), max_f,
+            _ptr_array(counts[f0:f1]), None if normals is None else _ptr_array(normals[f0:f1]),
+            None if colors is None else _ptr_array(colors[f0:f1]), layout, scale, bias, _float3(b_min), _float3(b_max),
+            _ptr(out[f0:f1]), int(capacity), _ptr(info[f0:f1]), _stream(verts[0])), "mp_mesh_glb_batch")
+    _keep_until_done(dev, verts, faces, counts, normals, colors)
+    return out, info
+
+
+def mesh_glb_raw(verts, faces, counts, normals=None, colors=None, color_layout="rows", color_scale=1.0,
+                 color_bias=0.0, b_min=(-1, -1, -1), b_max=(1, 1, 1), capacity=None, out=None, info=None):
+    """mp_mesh_glb_batch with one frame: the quantised binary glTF file of verts [max_v,3] f32, faces [max_f,3] int32,
+    counts int32[2] on device (as the mesh chain leaves them), with ``normals`` [max_v,3] and ``colors`` ([max_v,3]
+    under "rows", [3,max_v] under "planes"; byte = the 8-bit rule on ``p * color_scale + color_bias``) if given ->
+    (out uint8 [1,capacity], info int32 [1,2]) as ``picture_jpeg_raw`` returns them: the file is ``out[0, :info[0, 0]]``
+    where ``info[0, 1] == 0``; where it is 1 nothing was written and ``info[0, 0]`` is the capacity it needs.
+    ``capacity``: None = ``glb_max_bytes`` (never overflows).  Three launches; no host sync."""
+    return _mesh_glb("mesh_glb_raw", [verts], [faces], [counts], None if normals is None else [normals],
+                     None if colors is None else [colors], color_layout, color_scale, color_bias, b_min, b_max,
+                     capacity, out, info)
+
+
+def mesh_glb_raw_batch(verts, faces, counts, normals=None, colors=None, color_layout="rows", color_scale=1.0,
+                       color_bias=0.0, b_min=(-1, -1, -1), b_max=(1, 1, 1), capacity=None, out=None, info=None):
+    """mp_mesh_glb_batch: the files of ``mesh_glb_raw`` for lists of per-mesh device tensors of one capacity (``normals``
+    / ``colors``: None, or one tensor per mesh) in ONE set of three launches per MAX_FRAMES meshes -> (out uint8
+    [n,capacity], info int32 [n,2]), row f byte for byte what the per-mesh call gives.  No host sync."""
+    return _mesh_glb("mesh_glb_raw_batch", verts, faces, counts, normals, colors, color_layout, color_scale,
+                     color_bias, b_min, b_max, capacity, out, info)
+
+
 def _mesh_points(who, verts, counts, out):
     n, max_v, _, dev = _mesh_frames(who, verts, None, counts)
     if out is None:

@@ -144,6 +144,7 @@ class FrameSlot:
     view = 0  # the row of a multi-view head's result (ViewsSlot); a single-view head has the one
     jpeg = None  # the ``recon.Jpeg`` of ``encode_pictures``; None: nothing is allocated or enqueued for it
     png = None   # the ``recon.Png`` of ``encode_pictures``; None likewise
+    glb = None   # the ``recon.Glb`` of ``encode_meshes``; None likewise
     _chained = False  # the chain has been enqueued at least once (``prepare`` / ``submit``)
 
     def __init__(self, netG, device, resolutions=RESOLUTIONS, b_min=(-1, -1, -1), b_max=(1, 1, 1),
@@ -789,6 +790,63 @@ class FrameSlot:
                 self.volumes[b0:b1], self.b_min, self.b_max, self.mesh, self._mesh_bindings(b0, b1),
                 gates=[self.status[b, 0:1] for b in range(b0, b1)], out=out, view=self.view,
                 bits_out=self.transfer_bits[b0:b1] if self._traces else None)
+            if self.glb is not None:
+                self._encode_meshes(b0, b1)
+
+    def encode_meshes(self, glb):
+        """Encode the slot's meshes on the device from now on: ``glb`` is a ``recon.Glb``.  To be called before the first
+        ``prepare`` / ``submit``, on a slot with ``mesh=...`` whose options provide what ``glb`` asks for (normals,
+        colours).  The slot then owns the static ``glb_bytes`` [batch, capacity] uint8 (``glb.capacity_for`` the mesh
+        buffers' capacities) and ``glb_info`` [batch, 2] int32, and the chain enqueues ONE mp_mesh_glb_batch per chunk
+        of the mesh chain, behind that chunk on the slot's stream, with no host value in between: the chain's raw netC
+        predictions go in as planes with (0.5, 0.5), which gives the bytes of the finished colours.  ``glbs()`` hands the
+        files out.  A slot on which this was never called allocates and enqueues nothing for it."""
+        from .recon import Glb
+        who = "%s.encode_meshes" % type(self).__name__
+        if not isinstance(glb, Glb):
+            raise ValueError("%s: glb must be a recon.Glb, got %r" % (who, type(glb).__name__))
+        if self.mesh is None:
+            raise ValueError("%s: the slot was made without mesh=..." % who)
+        if glb.normals and self.mesh.normals is None:
+            raise ValueError("%s: glb asks for normals and the slot's meshes have none (mesh normals=None)" % who)
+        if glb.colors and not self.mesh.colors:
+            raise ValueError("%s: glb asks for colors and the slot's meshes have none (no netC, or colors=False)" % who)
+        if self._chained:
+            raise RuntimeError("%s: to be called before the first prepare / submit" % who)
+        cap_v, cap_f = self.mesh_buffers["verts"].shape[1], self.mesh_buffers["faces"].shape[1]
+        self.glb_bytes = torch.empty((self.batch, glb.capacity_for(cap_v, cap_f)), dtype=torch.uint8,
+                                     device=self.device)
+        self.glb_info = torch.zeros((self.batch, 2), dtype=torch.int32, device=self.device)
+        self.glb = glb
+
+    def _encode_meshes(self, b0, b1):
+        """One mp_mesh_glb_batch over the chains of frames b0..b1 as the chunk left them."""
+        chains = self._mesh_chains[b0:b1]
+        ops.mesh_glb_raw_batch([c.verts for c in chains], [c.faces for c in chains], [c.counts for c in chains],
+                               [c.normals for c in chains] if self.glb.normals else None,
+                               [c.preds for c in chains] if self.glb.colors else None, "planes", 0.5, 0.5,
+                               self.b_min, self.b_max, out=self.glb_bytes[b0:b1], info=self.glb_info[b0:b1])
+
+    def glbs(self):
+        """The binary glTF files of the current submission's meshes, to be called after ``wait()`` (it waits if the
+        caller has not): a list of ``n_active`` entries, ``bytes`` per frame or None where ``meshes()`` gives None.  One
+        device-to-host copy of ``glb_info`` and one of the used prefixes of ``glb_bytes`` (besides ``meshes()``' own).  A
+        frame whose mesh ``meshes()`` made again, or whose file exceeded the capacity, is encoded from its ``Mesh``
+        (``recon.encode_glb``): the same bytes a sufficient capacity gives."""
+        if self.glb is None:
+            raise RuntimeError("%s.glbs(): encode_meshes(glb) was never called on this slot" % type(self).__name__)
+        from .recon import Glb, _collect_files, encode_glb
+        meshes = self.meshes()
+        info = self.glb_info[:self.n_active].cpu().numpy()
+        again = [m is not None and (b in self._reran or bool(info[b, 1])) for b, m in enumerate(meshes)]
+        mine = info.copy()
+        for b, m in enumerate(meshes):
+            if m is None or again[b]:
+                mine[b] = (0, 0)  # nothing of this row is copied
+        files = _collect_files(type(self).__name__, self.glb_bytes, mine, None)
+        exact = Glb(self.glb.normals, self.glb.colors)  # the file's own size: no second overflow
+        return [None if m is None else (encode_glb(m, exact, self.b_min, self.b_max) if again[b] else files[b])
+                for b, m in enumerate(meshes)]
 
     def meshes(self):
         """The meshes of the current submission, to be called after ``wait()`` (it waits if the caller has not): a
@@ -1034,6 +1092,11 @@ class FramePipeline:
         """``FrameSlot.encode_pictures`` on every slot: before ``prepare`` / the first ``submit``."""
         for s in self.slots:
             s.encode_pictures(jpeg)
+
+    def encode_meshes(self, glb):
+        """``FrameSlot.encode_meshes`` on every slot: before ``prepare`` / the first ``submit``."""
+        for s in self.slots:
+            s.encode_meshes(glb)
 
     def synchronize(self):
         for s in self.slots:

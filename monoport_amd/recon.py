@@ -1434,6 +1434,81 @@ def encode_png(pictures, png=None, alpha=None):
     return files[0] if single else files
 
 
+class Glb:
+    """How meshes are written on the device (mp_mesh_glb in include/monoport_hip.h: binary glTF 2.0 under
+    KHR_mesh_quantization, byte for byte this library's own definition; what the reference's ``save_obj_mesh*`` write as
+    text on the host): 16-bit positions on the reconstruction box, with ``normals`` signed bytes, with ``colors`` bytes,
+    16-bit indices below 65 536 vertices.  ``capacity``: bytes reserved per mesh, at least the empty file's 100; None =
+    the file of a mesh of a quarter of the buffers' capacities (the 257^3 body fills about a ninth of a slot's 12 r^2
+    vertices and 24 r^2 faces), never more than ``ops.glb_max_bytes``.  A file that does not fit is reported by the
+    device and encoded again alone at its exact size (``encode_glb``, ``FrameSlot.glbs``): the capacity never changes
+    the bytes.  Everything is validated here; a Glb holds host values only."""
+
+    def __init__(self, normals=True, colors=True, capacity=None):
+        who = "Glb"
+        for name, flag in (("normals", normals), ("colors", colors)):
+            if not isinstance(flag, (bool, np.bool_)):
+                raise ValueError("%s: %s must be a bool, got %r" % (who, name, flag))
+        self.normals, self.colors = bool(normals), bool(colors)
+        if capacity is not None:
+            if (isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer))
+                    or not ops.GLB_MIN_BYTES <= capacity <= 2 ** 31):
+                raise ValueError("%s: capacity must be None or an int in %d..2^31 bytes, got %r"
+                                 % (who, ops.GLB_MIN_BYTES, capacity))
+            capacity = int(capacity)
+        self.capacity = capacity
+
+    def capacity_for(self, max_verts, max_faces):
+        """Bytes reserved per mesh in buffers of these capacities."""
+        if self.capacity is not None:
+            return self.capacity
+        return min(ops.glb_bytes(max_verts // 4, max_faces // 4, self.normals, self.colors),
+                   ops.glb_max_bytes(max_verts, max_faces, self.normals, self.colors))
+
+
+def encode_glb(meshes, glb=None, b_min=(-1, -1, -1), b_max=(1, 1, 1)):
+    """The binary glTF files of ``meshes`` (a ``Mesh`` on the device, or a list of them) under ``glb`` (a ``Glb``; None:
+    its defaults), laid out on the device: ``bytes`` for one mesh, a list of ``bytes`` for a list.  ``b_min`` / ``b_max``:
+    the box the 16-bit positions span (the reconstruction's; a vertex outside is clamped onto it).  A mesh without the
+    normals or colours ``glb`` asks for is a ValueError that names it.  Without a ``glb.capacity`` every file gets its
+    exact size, which the host knows from the shapes; one host-to-device copy of the counts, one device-to-host copy of
+    the sizes, then one of the used prefixes; a mesh whose file exceeded ``glb.capacity`` is encoded again alone at the
+    size the device reported.  Any glTF 2.0 reader that knows KHR_mesh_quantization loads the files; tests/glb_ref.py
+    restates them byte for byte."""
+    who = "encode_glb"
+    glb = Glb() if glb is None else glb
+    if not isinstance(glb, Glb):
+        raise ValueError("%s: glb must be a recon.Glb, got %r" % (who, type(glb).__name__))
+    single = isinstance(meshes, Mesh)
+    meshes = [meshes] if single else list(meshes)
+    for k, m in enumerate(meshes):
+        if not isinstance(m, Mesh):
+            raise ValueError("%s: mesh %d is not a recon.Mesh but %r" % (who, k, type(m).__name__))
+        for name, wanted, have in (("normals", glb.normals, m.normals), ("colors", glb.colors, m.colors)):
+            if wanted and have is None:
+                raise ValueError("%s: mesh %d has no %s and glb asks for them" % (who, k, name))
+    if not meshes:
+        return []
+    dev = meshes[0].verts.device
+    sizes = [(int(m.verts.shape[0]), int(m.faces.shape[0])) for m in meshes]
+    capacity = glb.capacity
+    if capacity is None:
+        capacity = max(ops.glb_bytes(nv, nf, glb.normals, glb.colors) for nv, nf in sizes)
+    counts = torch.tensor(sizes, dtype=torch.int32).to(dev)
+    out = torch.empty((len(meshes), capacity), dtype=torch.uint8, device=dev)
+    info = torch.empty((len(meshes), 2), dtype=torch.int32, device=dev)
+
+    def encode(i, **kw):  # the meshes differ in size: one call each, into their rows
+        m = meshes[i]
+        return ops.mesh_glb_raw(m.verts.contiguous(), m.faces.contiguous(), counts[i],
+                                m.normals.contiguous() if glb.normals else None,
+                                m.colors.contiguous() if glb.colors else None, "rows", 1.0, 0.0, b_min, b_max, **kw)
+    for i in range(len(meshes)):
+        encode(i, out=out[i:i + 1], info=info[i:i + 1])
+    files = _collect_files(who, out, info.cpu().numpy(), lambda i, size: encode(i, capacity=size))
+    return files[0] if single else files
+
+
 def _scene_pictures(who, scene, cams, ras, maps=None, fronts=None, composite="depth", out=None, back=None):
     """THE scene behind a set of pictures, for the render calls, a slot and a slot's re-run alike -> (per camera set the
     raw picture (image, depth, face; each [n_views, ...]) of ``scene`` under the ``ops.Raster`` ``ras``, per camera set

@@ -118,6 +118,15 @@ absent / 2 / 4 with one 257^2 view and absent / 2 with one 1024^2 view (4096 is 
 
     python tools/mesh_timing.py --samples [--passes 5] [--out profiles/mesh_samples_timing.json]
 
+``--glb`` measures the meshes' way out (profiles/mesh_glb_timing.json): mp_mesh_glb_batch alone, per mesh in a batch of
+20 coloured meshes of the 257^3 body at simplify = None / 128 / 64, with the file size and the achieved GB/s (bytes read
+plus bytes written), beside a device-to-device copy that moves the same number of bytes and beside the host route it
+replaces (the tensors' ``.cpu()`` and the numpy packing of tests/glb_ref.py), in the same alternating passes; then the
+20-frame colour slot with a mesh per frame, ``meshes()`` against ``glbs()`` as the consumer and against ``meshes()``,
+``.cpu()`` and the numpy packing.
+
+    python tools/mesh_timing.py --glb [--passes 5] [--out profiles/mesh_glb_timing.json]
+
 The protocol of tools/recon_views_timing.py: after a warm-up of all, the passes alternate; a pass is `meshes`
 meshes, wall clock around a final stream sync.  Prints (and writes) one JSON line: per way the median, minimum and
 maximum time per mesh (ms) over the passes.  The verdict fields restate what to check: (b) not slower than (a) by
@@ -165,6 +174,7 @@ def main():
     ap.add_argument("--jpeg", action="store_true", help="mp_picture_jpeg alone; the --lighting slots with encode_pictures")
     ap.add_argument("--png", action="store_true", help="mp_picture_png alone; the --lighting slots with a recon.Png")
     ap.add_argument("--samples", action="store_true", help="mp_picture_resolve alone; the --jpeg slots at samples 1 / 2 / 4")
+    ap.add_argument("--glb", action="store_true", help="mp_mesh_glb_batch alone; the colour slot with encode_meshes")
     a = ap.parse_args()
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "mesh_render_clip_timing.json" if a.render and a.clip else
@@ -177,6 +187,7 @@ def main():
                              "mesh_jpeg_timing.json" if a.jpeg else
                              "mesh_png_timing.json" if a.png else
                              "mesh_samples_timing.json" if a.samples else
+                             "mesh_glb_timing.json" if a.glb else
                              "mesh_smooth_timing.json" if a.smooth else
                              "mesh_simplify_timing.json" if a.simplify else
                              "keep_largest_timing.json" if a.clean else
@@ -232,6 +243,12 @@ def main():
 
     if a.smooth:
         write(a, smooth(a, vol, netC, feat_C, calib))
+        return
+    if a.glb:
+        out = glb_kernels(a, vol, netC, feat_C, calib)
+        if not a.no_slot:
+            out["slot"] = slot_glb(a)
+        write(a, out)
         return
     if a.simplify:
         out = simplify(a, vol, netC, feat_C, calib)
@@ -494,6 +511,84 @@ def slot_simplify(a, frames=20):
     for name, p_ in pipes.items():
         m = p_.slots[0].meshes()[0]
         out["vertices_faces_frame0"][name] = [int(m.verts.shape[0]), int(m.faces.shape[0])]
+        p_.close()
+    return out
+
+
+def _glb_ref():
+    """The numpy restatement of the file (tests/glb_ref.py): the host route's packing."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import glb_ref
+    return glb_ref
+
+
+def _host_glb(glb_ref, mesh):
+    """The host route: every tensor of the ``Mesh`` to the host, packed by numpy."""
+    return glb_ref.encode(mesh.verts.cpu().numpy(), mesh.faces.cpu().numpy(), None, mesh.normals.cpu().numpy(),
+                          mesh.colors.cpu().numpy(), b_min=BMIN, b_max=BMAX)
+
+
+def glb_kernels(a, vol, netC, feat_C, calib, n=20):
+    """mp_mesh_glb_batch over n coloured meshes (each its own buffers) at each simplify setting, a device copy of the
+    same bytes, and the host route."""
+    glb_ref = _glb_ref()
+    out = {"resolutions": RES, "passes": a.passes, "per_pass": n, "unit": "ms per mesh", "launches_per_call": 3,
+           "settings": {}}
+    ways = {}
+    for cells in SIMPLIFY_SETTINGS:
+        m = reconstruct_mesh(vol, 0.5, BMIN, BMAX, netC=netC, feat_tensor_C=feat_C, calib_tensor=calib, simplify=cells)
+        nv, nf = int(m.verts.shape[0]), int(m.faces.shape[0])
+        size = ops.glb_bytes(nv, nf)
+        moved = 36 * nv + 12 * nf + size  # f32 position, normal, colour and int32 corners in; the file out
+        frames = [[t.clone() for t in (m.verts, m.faces, m.normals, m.colors)] for _ in range(n)]
+        counts = torch.tensor([[nv, nf]] * n, dtype=torch.int32).to(DEV)
+        files = torch.empty((n, size), dtype=torch.uint8, device=DEV)
+        info = torch.empty((n, 2), dtype=torch.int32, device=DEV)
+        src = torch.empty((n * moved // 2,), dtype=torch.uint8, device=DEV)
+        dst = torch.empty_like(src)
+
+        def encode(frames=frames, counts=counts, files=files, info=info):
+            return ops.mesh_glb_raw_batch([f[0] for f in frames], [f[1] for f in frames], list(counts),
+                                          [f[2] for f in frames], [f[3] for f in frames], "rows", 1.0, 0.0, BMIN, BMAX,
+                                          out=files, info=info)
+        encode()
+        torch.cuda.synchronize()
+        want = _host_glb(glb_ref, m)
+        same = all(tuple(row) == (size, 0) for row in info.cpu().tolist()) and all(
+            files[i].cpu().numpy().tobytes() == want for i in (0, n - 1))
+        key = str(cells)
+        out["settings"][key] = {"vertices": nv, "faces": nf, "file_bytes": size, "bytes_moved": moved,
+                                "bytes_of_f32_tensors": 36 * nv + 12 * nf, "device_file_equals_host_packing": bool(same)}
+        ways["glb_%s" % key] = encode
+        ways["copy_%s" % key] = (lambda src=src, dst=dst: dst.copy_(src))
+        ways["host_%s" % key] = (lambda m=m: [_host_glb(glb_ref, m) for _ in range(n)])
+    out.update(alternate(ways, a.passes, n))
+    for key, st in out["settings"].items():
+        for way in ("glb", "copy"):
+            st[way + "_gb_per_s"] = round(st["bytes_moved"] / (out["%s_%s" % (way, key)]["median_ms"] * 1e6), 1)
+        st["glb_over_copy"] = round(out["glb_%s" % key]["median_ms"] / out["copy_%s" % key]["median_ms"], 3)
+    return out
+
+
+def slot_glb(a, frames=20):
+    """The 20-frame colour slot with a mesh per frame: ``meshes()`` as the consumer, ``glbs()`` on a slot with
+    ``encode_meshes``, and ``meshes()`` + ``.cpu()`` + the numpy packing; per-frame ms of a submission."""
+    glb_ref = _glb_ref()
+    mesh = {"normals": "accumulate"}
+    pipes, fn = _slot_pipes(frames, 1, (("mesh", mesh), ("mesh_glb", mesh)), glbs={"mesh_glb": recon.Glb()})
+    ways = {"meshes": fn("mesh"), "glbs": fn("mesh_glb", lambda s: s.glbs()),
+            "meshes_cpu_numpy": fn("mesh", lambda s: [_host_glb(glb_ref, m) for m in s.meshes()])}
+    out = {"frames_per_slot": frames, "unit": "ms per frame", "normals": "accumulate", "colors": True}
+    out.update(alternate(ways, a.passes, frames))
+    slot = pipes["mesh_glb"].slots[0]
+    files, meshes = slot.glbs(), slot.meshes()
+    out["file_bytes_frame0"] = len(files[0])
+    out["vertices_faces_frame0"] = [int(meshes[0].verts.shape[0]), int(meshes[0].faces.shape[0])]
+    out["capacity_bytes"] = int(slot.glb_bytes.shape[1])
+    out["overflowed_frames"] = int(slot.glb_info[:, 1].sum().item())
+    out["files_equal_host_packing"] = bool(all(f == _host_glb(glb_ref, m) for f, m in zip(files, meshes)))
+    out["glbs_adds_ms"] = round(out["glbs"]["median_ms"] - out["meshes"]["median_ms"], 4)
+    for p_ in pipes.values():
         p_.close()
     return out
 
@@ -1013,9 +1108,9 @@ def slot_scene(a, frames=20):
     return out
 
 
-def _slot_pipes(frames, depth, meshes):
+def _slot_pipes(frames, depth, meshes, glbs=None):
     """FramePipelines of the bench's synthetic frames, one per (name, mesh option[, pictures option, cameras]), and
-    fn(name) -> a submission."""
+    fn(name) -> a submission.  ``glbs``: None, or {name: the ``recon.Glb`` of that pipeline's ``encode_meshes``}."""
     from bench_common import B_MAX, B_MIN, RESOLUTIONS, build_netc, build_netg
     from monoport_amd import pipeline
     from monoport_amd.recon import pifu_calib
@@ -1045,6 +1140,8 @@ def _slot_pipes(frames, depth, meshes):
                                              netC=netc, mesh=mesh, **kw)
         if len(pictures) > 2 and "encode_pictures" in pictures[2]:  # --jpeg: files behind the pictures
             pipes[name].encode_pictures(pictures[2]["encode_pictures"])
+        if glbs and name in glbs:
+            pipes[name].encode_meshes(glbs[name])
         pipes[name].prepare()
 
     def fn(name, consume=None):
