@@ -1323,6 +1323,110 @@ int mp_mesh_glb_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int6
                       float color_bias, const float *b_min, const float *b_max, uint8_t *out, int64_t capacity,
                       int32_t *info, mp_stream stream);
 
+/* A texture atlas of a mesh (the reference's data side loads textured meshes throughout; COLOR_0 above carries one
+ * netC sample per vertex, which a simplified mesh has few of): every face gets a small right triangle of its own in a
+ * square picture, and mp_mesh_atlas writes that picture as the G-buffer of a render in TEXTURE space -- face ids and
+ * world positions, laid out exactly as one view of H = W = A of the rasteriser's, so that mp_picture_points, the
+ * counted netC queries, mp_picture_paint and mp_picture_png run on it unchanged.  Bit for bit, a pure function of its
+ * inputs; tests/atlas_ref.py restates it in numpy.
+ *   Sizes: the atlas side A is a power of two in MP_ATLAS_MIN_SIZE..MP_ATLAS_MAX_SIZE (64..4096: (k + 0.5) / A is
+ * exact in f32 and A <= MP_PNG_MAX_SIDE), the cell side T is in MP_ATLAS_MIN_CELL..MP_ATLAS_MAX_CELL (4..64),
+ * G = A / T (integer division) cells per row and per column; the texels beyond G T are unused.  The atlas holds 2 G^2
+ * faces.  Counts: nv and nf as in mp_mesh_glb, and nf = 0 where nv == 0; an index i becomes min(max(i, 0), nv - 1).
+ *   Cells: face f < F = min(nf, 2 G^2) lives in cell q = f >> 1, at column q % G and row q / G; texel rows count from
+ * the top (row 0 is v = 0, glTF's UV origin).  With (i, j) = the (column, row) of a texel inside its cell:
+ *   h = f & 1 = 0, the lower half: leg l = T - 2, corners at (0,0), (l,0), (0,l); it owns every texel with
+ *     i + j <= T - 1 (the diagonal T - 1 is its gutter); a = i, b = j.
+ *   h = 1, the upper half: leg l = T - 3, corners at (T-1,T-1), (T-1-l,T-1), (T-1,T-1-l); it owns i + j >= T (the
+ *     diagonal T is its gutter); a = T-1-i, b = T-1-j.
+ * Every bilinear footprint of a point inside a face's UV triangle, its edges and corners included, then lies in that
+ * face's own texels.
+ *   An owned texel gets face_id = f and, with v0, v1, v2 the face's vertices, s = (float)a / (float)l and
+ * t = (float)b / (float)l, position = (v0 + s * (v1 - v0)) + t * (v2 - v0) per axis: six f32 operations, each rounded
+ * separately, no FMA; gutter texels (a + b > l) are the same map extrapolated.  EVERY other texel -- the unused half of
+ * an odd last pair, cells past the last face, the margins -- gets face_id = -1 and position = (background, background,
+ * background): all A^2 texels are written whatever the buffers held.  info int32[2] = {F, nf}: info[1] > info[0]
+ * tells an atlas that is too small (the faces from F on are laid out nowhere).
+ *   UVs are not stored: corner k of face f has (u, v) = ((x_k + 0.5) / A, (y_k + 0.5) / A) with (x_k, y_k) the texel
+ * of that corner in the picture (the cell's origin plus the corner above), exact in f32.
+ *   mp_mesh_atlas: verts f32 [max_verts,3], faces int32 [max_faces,3], counts device int32[2]; face_id int32 [A A],
+ * position f32 [A A,3], info device int32[2].  One launch, one thread per texel, no atomics, no scratch, nothing
+ * allocated, asynchronous.  mp_mesh_atlas_batch: n_frames meshes of one capacity in the same ONE launch (host arrays of
+ * device pointers); frame f equals the single call BIT FOR BIT.
+ *   Refusals (a message, nothing launched): atlas_size not a power of two in 64..4096, cell outside 4..64, n_frames
+ * outside 1..mp_max_frames(), a negative capacity, a NULL or misaligned (4 bytes) buffer (verts may be NULL with
+ * max_verts == 0, faces with max_faces == 0), an output overlapping an input or another output, a non-finite
+ * background: MP_ERR_ARG; capacities beyond 2^31 / 3: MP_ERR_UNSUPPORTED. */
+#define MP_ATLAS_MIN_SIZE 64
+#define MP_ATLAS_MAX_SIZE 4096
+#define MP_ATLAS_MIN_CELL 4
+#define MP_ATLAS_MAX_CELL 64
+int mp_mesh_atlas(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                  const int32_t *counts, int atlas_size, int cell, float background, int32_t *face_id, float *position,
+                  int32_t *info, mp_stream stream);
+int mp_mesh_atlas_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                        const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts, int atlas_size,
+                        int cell, float background, int32_t *const *face_id, float *const *position,
+                        int32_t *const *info, mp_stream stream);
+
+/* Textured meshes as bytes: the .glb of a mesh with the atlas above as its base colour texture, the image inside the
+ * file.  Container, padding, the fixed-width number template, out / capacity / info, POSITION and NORMAL quantisation
+ * are those of mp_mesh_glb, word for word; tests/glb_texture_ref.py restates the file byte for byte.
+ *   Primitive: NOT indexed ("mode":4 without "indices"): 3 nf vertices in face-corner order, vertex 3 f + k = corner k
+ * of face f, because a vertex's UV differs per face.  nv, nf and the clamp of an index as in mp_mesh_glb; the mesh is
+ * EMPTY (the fixed 100-byte file, the image not looked at) where nv == 0 or nf == 0.
+ *   Attributes: POSITION and, with MP_GLB_NORMALS, NORMAL of the corner's vertex, 8 and 4 bytes as above; POSITION's
+ * min / max are the exact extremes over the 3 nf corners.  TEXCOORD_0: FLOAT VEC2, 8 bytes: the closed form of the
+ * atlas (atlas_size, cell).  COLOR_0 is refused together with a texture: glTF multiplies the two.
+ *   JSON, with [N] as above, c = 1 + [N], k = c + 1:
+ *   {"asset":{"version":"2.0","generator":"monoport_amd"},"extensionsUsed":["KHR_mesh_quantization"],
+ *   "extensionsRequired":["KHR_mesh_quantization"],"scene":0,"scenes":[{"nodes":[0]}],
+ *   "nodes":[{"mesh":0,"translation":[T,T,T],"scale":[S,S,S]}],"materials":[{"doubleSided":true,
+ *   "pbrMetallicRoughness":{"baseColorTexture":{"index":0},"metallicFactor":0,"roughnessFactor":1}}],
+ *   "textures":[{"sampler":0,"source":0}],
+ *   "samplers":[{"magFilter":9729,"minFilter":9729,"wrapS":33071,"wrapT":33071}],
+ *   "images":[{"bufferView":k,"mimeType":"image/png"}],
+ *   "meshes":[{"primitives":[{"attributes":{"POSITION":0[N: ,"NORMAL":1],"TEXCOORD_0":c},"material":0,"mode":4}]}],
+ *   "accessors":[
+ *   {"bufferView":0,"componentType":5123,"count":<3 nf>,"type":"VEC3","min":[<m>,<m>,<m>],"max":[<m>,<m>,<m>]}
+ *   [N: ,{"bufferView":1,"componentType":5120,"normalized":true,"count":<3 nf>,"type":"VEC3"}]
+ *   ,{"bufferView":c,"componentType":5126,"count":<3 nf>,"type":"VEC2"}],"bufferViews":[
+ *   {"buffer":0,"byteOffset":<o>,"byteLength":<l>,"byteStride":8,"target":34962}
+ *   [N: ,{"buffer":0,"byteOffset":<o>,"byteLength":<l>,"byteStride":4,"target":34962}]
+ *   ,{"buffer":0,"byteOffset":<o>,"byteLength":<l>,"byteStride":8,"target":34962}
+ *   ,{"buffer":0,"byteOffset":<o>,"byteLength":<l>}],"buffers":[{"byteLength":<b>}]}
+ * Linear filtering without a mip chain (mips would bleed across cells), clamped at the edges.
+ *   Views, back to back: positions 24 nf bytes, normals 12 nf, texture coordinates 24 nf, then the IMAGE as the last
+ * view, so that every other offset is a closed form of nf: the p = png_info[f][0] bytes of row f of `png`, the file
+ * mp_picture_png (MP_PNG_RGB8, a picture [A,A]) wrote before on the same stream, copied as they are; <b> = the sum
+ * rounded up to 4 with zeros.  mp_glb_textured_bytes(nf, flags, png_bytes) = 12 + 8 + L + 8 + <b>, MP_GLB_MIN_BYTES
+ * for nf == 0, 0 for negative arguments or flags other than MP_GLB_NORMALS; mp_glb_textured_max_bytes(max_faces, flags,
+ * atlas_size) = the same with mp_png_max_bytes(A, A, MP_PNG_RGB8), 0 where that is 0.
+ *   info[f] = {bytes, code}: code 0: the file is out[f][:bytes]; 1: the file exceeds `capacity`: NOTHING is written
+ * and bytes is the size it needs; 2: the mesh has more faces than the atlas's 2 G^2, or its image is unusable
+ * (png_info[f][1] != 0: the PNG overflowed; or png_info[f][0] outside MP_PNG_MIN_BYTES..png_capacity): NOTHING is
+ * written and bytes is 0.
+ *   mp_mesh_glb_textured: verts, faces, counts, normals (or NULL), b_min, b_max, out, capacity, info as in mp_mesh_glb;
+ * colors must be NULL; png uint8 [png_capacity] and png_info int32[2] on the device.  Three launches as there (the PNG
+ * is copied by the second), integer atomics only for POSITION's extremes, 8 KB per frame of the stream's scratch
+ * arena, no host value, asynchronous.  mp_mesh_glb_textured_batch: n_frames meshes in the same three launches, png
+ * [n_frames,png_capacity] and png_info [n_frames,2] CONTIGUOUS as mp_picture_png leaves them; frame f equals the single
+ * call BIT FOR BIT.
+ *   Refusals: those of mp_mesh_glb and of mp_mesh_atlas's sizes; colors given, a NULL png or png_info, a misaligned
+ * png_info, png_capacity below MP_PNG_MIN_BYTES or above 2^31, out or info overlapping png or png_info: MP_ERR_ARG;
+ * capacities for which mp_glb_textured_max_bytes reaches 2^31: MP_ERR_UNSUPPORTED. */
+int64_t mp_glb_textured_bytes(int64_t nf, int flags, int64_t png_bytes);
+int64_t mp_glb_textured_max_bytes(int64_t max_faces, int flags, int atlas_size);
+int mp_mesh_glb_textured(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                         const int32_t *counts, const float *normals, const float *colors, int atlas_size, int cell,
+                         const uint8_t *png, int64_t png_capacity, const int32_t *png_info, const float *b_min,
+                         const float *b_max, uint8_t *out, int64_t capacity, int32_t *info, mp_stream stream);
+int mp_mesh_glb_textured_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                               const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts,
+                               const float *const *normals, const float *const *colors, int atlas_size, int cell,
+                               const uint8_t *png, int64_t png_capacity, const int32_t *png_info, const float *b_min,
+                               const float *b_max, uint8_t *out, int64_t capacity, int32_t *info, mp_stream stream);
+
 /* The largest connected body of an occupancy volume [R,R,R] (no counterpart in the reference; the clean-up in front
  * of marching cubes that drops floating blobs).
  *   Foreground: voxels with value > level (marching cubes' "inside"; a NaN and value == level are background).

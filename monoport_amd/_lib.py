@@ -258,6 +258,15 @@ SIGNATURES = {
                             c_vp, c_i64, c_vp, c_vp]),
     "mp_mesh_glb_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_int, c_f32, c_f32, c_vp,
                                   c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "mp_mesh_atlas": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_f32, c_vp, c_vp, c_vp, c_vp]),
+    "mp_mesh_atlas_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_int, c_f32, c_vp, c_vp, c_vp,
+                                    c_vp]),
+    "mp_glb_textured_bytes": (c_i64, [c_i64, c_int, c_i64]),
+    "mp_glb_textured_max_bytes": (c_i64, [c_i64, c_int, c_int]),
+    "mp_mesh_glb_textured": (c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_i64, c_vp,
+                                     c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "mp_mesh_glb_textured_batch": (c_int, [c_vp, c_int, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_int, c_int, c_vp,
+                                           c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "mp_volume_bits_words": (c_i64, [c_int]),
     "mp_volume_bits": (c_int, [c_vp, c_vp, c_int, c_f32, c_vp, c_vp]),
     "mp_volume_bits_batch": (c_int, [c_vp, c_int, c_vp, c_int, c_f32, c_vp, c_vp, c_vp]),

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "lib", "obj")
 LIB = os.path.join(HERE, "lib", "libmonoport_hip.so")
-SOURCES = ["api.hip", "pack.hip", "query.hip", "query_small.hip", "query_table.hip", "query16.hip", "query_views.hip", "octree.hip", "point_order.hip", "topk.hip", "vertices.hip", "mcubes.hip", "mesh.hip", "simplify.hip", "smooth.hip", "raster.hip", "picture.hip", "scene.hip", "light.hip", "transfer.hip", "jpeg.hip", "png.hip", "glb.hip", "components.hip",
+SOURCES = ["api.hip", "pack.hip", "query.hip", "query_small.hip", "query_table.hip", "query16.hip", "query_views.hip", "octree.hip", "point_order.hip", "topk.hip", "vertices.hip", "mcubes.hip", "mesh.hip", "simplify.hip", "smooth.hip", "raster.hip", "picture.hip", "scene.hip", "light.hip", "transfer.hip", "jpeg.hip", "png.hip", "glb.hip", "atlas.hip", "components.hip",
            "encoder_ops.hip", "conv3x3.hip", "conv_wino.hip", "convim2col.hip", "plan.hip", "clock_probe.hip", "resolve.hip"]
 HEADERS = [os.path.join(CSRC, "mp_internal.h"), os.path.join(CSRC, "query_common.h"),
            os.path.join(CSRC, "encoder_kernels.h"), os.path.join(CSRC, "gn_tail.h"),

@@ -2049,6 +2049,25 @@ int64_t mp_glb_max_bytes(int64_t max_verts, int64_t max_faces, int flags) {
   return mp_glb_bytes(max_verts, max_faces, flags);
 }
 
+// the box of the 16-bit positions and the capacity of a file, as mp_mesh_glb and mp_mesh_glb_textured refuse them
+static int glb_box_checked(mp_ctx *ctx, const char *who, const float *b_min, const float *b_max, int64_t capacity,
+                           GlbCall *c) {
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(b_min[a]) || !std::isfinite(b_max[a]) || !(b_max[a] > b_min[a]))
+      return fail(ctx, MP_ERR_ARG, "%s: the box needs finite bounds with b_max > b_min, got [%g, %g] on axis %d", who,
+                  (double)b_min[a], (double)b_max[a], a);
+    c->b_min[a] = b_min[a], c->b_max[a] = b_max[a];
+    c->inv[a] = 65535.0f / (b_max[a] - b_min[a]);
+    if (!std::isfinite(c->inv[a]))
+      return fail(ctx, MP_ERR_ARG, "%s: the box is too thin on axis %d for 16-bit positions (%g wide)", who, a,
+                  (double)(b_max[a] - b_min[a]));
+  }
+  if (capacity < MP_GLB_MIN_BYTES || capacity > ((int64_t)1 << 31))
+    return fail(ctx, MP_ERR_ARG, "%s: capacity %lld (at least the empty file's %d bytes, at most 2^31)", who,
+                (long long)capacity, MP_GLB_MIN_BYTES);
+  return MP_OK;
+}
+
 static int mesh_glb_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *verts, int64_t max_verts,
                             const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts,
                             const float *const *normals, const float *const *colors, int color_layout,
@@ -2066,19 +2085,8 @@ static int mesh_glb_checked(mp_ctx *ctx, const char *who, int n_frames, const fl
   if (!std::isfinite(color_scale) || !std::isfinite(color_bias))
     return fail(ctx, MP_ERR_ARG, "%s: a non-finite color_scale or color_bias", who);
   GlbCall c;
-  for (int a = 0; a < 3; ++a) {
-    if (!std::isfinite(b_min[a]) || !std::isfinite(b_max[a]) || !(b_max[a] > b_min[a]))
-      return fail(ctx, MP_ERR_ARG, "%s: the box needs finite bounds with b_max > b_min, got [%g, %g] on axis %d", who,
-                  (double)b_min[a], (double)b_max[a], a);
-    c.b_min[a] = b_min[a], c.b_max[a] = b_max[a];
-    c.inv[a] = 65535.0f / (b_max[a] - b_min[a]);
-    if (!std::isfinite(c.inv[a]))
-      return fail(ctx, MP_ERR_ARG, "%s: the box is too thin on axis %d for 16-bit positions (%g wide)", who, a,
-                  (double)(b_max[a] - b_min[a]));
-  }
-  if (capacity < MP_GLB_MIN_BYTES || capacity > ((int64_t)1 << 31))
-    return fail(ctx, MP_ERR_ARG, "%s: capacity %lld (at least the empty file's %d bytes, at most 2^31)", who,
-                (long long)capacity, MP_GLB_MIN_BYTES);
+  rc = glb_box_checked(ctx, who, b_min, b_max, capacity, &c);
+  if (rc != MP_OK) return rc;
   const int flags = (normals ? MP_GLB_NORMALS : 0) | (colors ? MP_GLB_COLORS : 0);
   if (max_verts > (1LL << 40) || max_faces > (1LL << 40) || glb_bytes(max_verts, max_faces, flags) >= (1LL << 31))
     return fail(ctx, MP_ERR_UNSUPPORTED, "%s: capacities of %lld vertices and %lld faces: a file could reach 2^31 bytes",
@@ -2122,6 +2130,155 @@ int mp_mesh_glb_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int6
                       int32_t *info, mp_stream stream) {
   return mesh_glb_checked(ctx, "mp_mesh_glb_batch", n_frames, verts, max_verts, faces, max_faces, counts, normals,
                           colors, color_layout, color_scale, color_bias, b_min, b_max, out, capacity, info, stream);
+}
+
+// the atlas's sizes, as mp_mesh_atlas and mp_mesh_glb_textured refuse them
+static int atlas_sizes_checked(mp_ctx *ctx, const char *who, int atlas_size, int cell) {
+  if (atlas_size < MP_ATLAS_MIN_SIZE || atlas_size > MP_ATLAS_MAX_SIZE || (atlas_size & (atlas_size - 1)))
+    return fail(ctx, MP_ERR_ARG, "%s: atlas_size must be a power of two in %d..%d, got %d", who, MP_ATLAS_MIN_SIZE,
+                MP_ATLAS_MAX_SIZE, atlas_size);
+  if (cell < MP_ATLAS_MIN_CELL || cell > MP_ATLAS_MAX_CELL)
+    return fail(ctx, MP_ERR_ARG, "%s: cell must be in %d..%d, got %d", who, MP_ATLAS_MIN_CELL, MP_ATLAS_MAX_CELL, cell);
+  return MP_OK;
+}
+
+static int mesh_atlas_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *verts, int64_t max_verts,
+                              const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts,
+                              int atlas_size, int cell, float background, int32_t *const *face_id,
+                              float *const *position, int32_t *const *info, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = atlas_sizes_checked(ctx, who, atlas_size, cell);
+  if (rc != MP_OK) return rc;
+  rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (!counts || !face_id || !position || !info || max_verts < 0 || max_faces < 0 || (max_verts > 0 && !verts) ||
+      (max_faces > 0 && !faces))
+    return bad_argument(ctx, who);
+  if (!std::isfinite(background)) return fail(ctx, MP_ERR_ARG, "%s: a non-finite background", who);
+  if (max_verts > 0x7fffffffLL / 3 || max_faces > 0x7fffffffLL / 3)
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: capacities beyond 2^31 / 3 need 64-bit indices", who);
+  if (max_verts == 0) verts = nullptr;  // rows of a capacity of 0 are not looked at
+  if (max_faces == 0) faces = nullptr;
+  rc = check_frames(ctx, who, n_frames, nullptr, counts, verts, faces, face_id, position, info);
+  if (rc != MP_OK) return rc;
+  const size_t texels = (size_t)atlas_size * (size_t)atlas_size;
+  const FrameSpans outs[3] = {{face_id, texels * 4}, {position, texels * 12}, {info, 8}};
+  const FrameSpans ins[3] = {{verts, (size_t)max_verts * 12}, {faces, (size_t)max_faces * 12}, {counts, 8}};
+  rc = check_no_alias(ctx, who, n_frames, outs, ins);
+  if (rc != MP_OK) return rc;
+  for (int f = 0; f < n_frames; ++f)  // no output shares a byte with another output, of any frame
+    for (int i = 0; i < n_frames; ++i)
+      for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b)
+          if ((f != i || a != b) && ranges_overlap(outs[a].of(f), outs[a].bytes, outs[b].of(i), outs[b].bytes))
+            return fail(ctx, MP_ERR_ARG, "%s: an output of frame %d aliases an output of frame %d", who, f, i);
+  DeviceGuard g(ctx->device);
+  return launch_mesh_atlas_batch(ctx, n_frames, verts, max_verts, faces, max_faces, counts, atlas_size, cell, background,
+                                 face_id, position, info, (hipStream_t)stream);
+}
+
+int mp_mesh_atlas(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                  const int32_t *counts, int atlas_size, int cell, float background, int32_t *face_id, float *position,
+                  int32_t *info, mp_stream stream) {
+  return mesh_atlas_checked(ctx, "mp_mesh_atlas", 1, &verts, max_verts, &faces, max_faces, &counts, atlas_size, cell,
+                            background, &face_id, &position, &info, stream);
+}
+
+int mp_mesh_atlas_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                        const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts, int atlas_size,
+                        int cell, float background, int32_t *const *face_id, float *const *position,
+                        int32_t *const *info, mp_stream stream) {
+  return mesh_atlas_checked(ctx, "mp_mesh_atlas_batch", n_frames, verts, max_verts, faces, max_faces, counts,
+                            atlas_size, cell, background, face_id, position, info, stream);
+}
+
+int64_t mp_glb_textured_bytes(int64_t nf, int flags, int64_t png_bytes) {
+  if (nf < 0 || png_bytes < 0 || nf > (1LL << 40) || png_bytes > (1LL << 40) || (flags & ~MP_GLB_NORMALS)) return 0;
+  return (int64_t)glb_textured_bytes(nf, flags, png_bytes);
+}
+
+int64_t mp_glb_textured_max_bytes(int64_t max_faces, int flags, int atlas_size) {
+  if (atlas_size < MP_ATLAS_MIN_SIZE || atlas_size > MP_ATLAS_MAX_SIZE || (atlas_size & (atlas_size - 1))) return 0;
+  const int64_t png = mp_png_max_bytes(atlas_size, atlas_size, MP_PNG_RGB8);
+  return png > 0 ? mp_glb_textured_bytes(max_faces, flags, png) : 0;
+}
+
+static int mesh_glb_textured_checked(mp_ctx *ctx, const char *who, int n_frames, const float *const *verts,
+                                     int64_t max_verts, const int32_t *const *faces, int64_t max_faces,
+                                     const int32_t *const *counts, const float *const *normals, bool colors,
+                                     int atlas_size, int cell, const uint8_t *png, int64_t png_capacity,
+                                     const int32_t *png_info, const float *b_min, const float *b_max, uint8_t *out,
+                                     int64_t capacity, int32_t *info, mp_stream stream) {
+  if (!ctx) return MP_ERR_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  int rc = check_count(ctx, who, "frame", n_frames, kMaxFrames, MP_ERR_ARG);
+  if (rc != MP_OK) return rc;
+  if (colors)
+    return fail(ctx, MP_ERR_ARG, "%s: COLOR_0 together with a texture: glTF multiplies the two; colors must be NULL", who);
+  rc = atlas_sizes_checked(ctx, who, atlas_size, cell);
+  if (rc != MP_OK) return rc;
+  if (!counts || !b_min || !b_max || !out || !info || ((uintptr_t)info & 3u) || !png || !png_info ||
+      ((uintptr_t)png_info & 3u) || max_verts < 0 || max_faces < 0 || (max_verts > 0 && !verts) ||
+      (max_faces > 0 && !faces))
+    return bad_argument(ctx, who);
+  GlbCall c;
+  rc = glb_box_checked(ctx, who, b_min, b_max, capacity, &c);
+  if (rc != MP_OK) return rc;
+  if (png_capacity < MP_PNG_MIN_BYTES || png_capacity > ((int64_t)1 << 31))
+    return fail(ctx, MP_ERR_ARG, "%s: png_capacity %lld (at least a PNG's %d bytes, at most 2^31)", who,
+                (long long)png_capacity, MP_PNG_MIN_BYTES);
+  const int flags = normals ? MP_GLB_NORMALS : 0;
+  if (max_verts > 0x7fffffffLL / 3 || max_faces > (1LL << 40) ||
+      mp_glb_textured_max_bytes(max_faces, flags, atlas_size) >= (1LL << 31))
+    return fail(ctx, MP_ERR_UNSUPPORTED, "%s: capacities of %lld vertices and %lld faces: a file could reach 2^31 bytes",
+                who, (long long)max_verts, (long long)max_faces);
+  if (max_verts == 0) verts = nullptr, normals = nullptr;  // rows of a capacity of 0 are not looked at
+  if (max_faces == 0) faces = nullptr;
+  rc = check_frames(ctx, who, n_frames, nullptr, counts, verts, faces, normals);
+  if (rc != MP_OK) return rc;
+  const size_t vbytes = (size_t)max_verts * 12, out_bytes = (size_t)n_frames * (size_t)capacity;
+  const size_t info_bytes = (size_t)n_frames * 8, png_bytes = (size_t)n_frames * (size_t)png_capacity;
+  if (ranges_overlap(out, out_bytes, info, info_bytes)) return fail(ctx, MP_ERR_ARG, "%s: out aliases info", who);
+  for (const void *o : {(const void *)out, (const void *)info}) {
+    const size_t ob = o == (const void *)out ? out_bytes : info_bytes;
+    if (ranges_overlap(o, ob, png, png_bytes) || ranges_overlap(o, ob, png_info, info_bytes))
+      return fail(ctx, MP_ERR_ARG, "%s: out or info aliases png or png_info", who);
+  }
+  const FrameSpans ins[4] = {{verts, vbytes}, {faces, (size_t)max_faces * 12}, {counts, 8}, {normals, vbytes}};
+  for (int f = 0; f < n_frames; ++f)
+    for (const FrameSpans &k : ins)
+      if (ranges_overlap(out, out_bytes, k.of(f), k.bytes) || ranges_overlap(info, info_bytes, k.of(f), k.bytes))
+        return fail(ctx, MP_ERR_ARG, "%s: out or info aliases an input of frame %d", who, f);
+  DeviceGuard g(ctx->device);
+  c.n_frames = n_frames, c.color_planes = 0;
+  c.max_v = max_verts, c.max_f = max_faces, c.capacity = capacity;
+  c.color_scale = 1.0f, c.color_bias = 0.0f;
+  const GlbTextureCall tc = {atlas_size, cell, png, (long long)png_capacity, png_info};
+  void *scratch = nullptr;
+  rc = ensure_scratch(ctx, (hipStream_t)stream, glb_scratch_bytes(n_frames), &scratch);
+  if (rc != MP_OK) return rc;
+  return launch_mesh_glb_textured_batch(ctx, scratch, c, tc, verts, faces, counts, normals, out, info,
+                                        (hipStream_t)stream);
+}
+
+int mp_mesh_glb_textured(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *faces, int64_t max_faces,
+                         const int32_t *counts, const float *normals, const float *colors, int atlas_size, int cell,
+                         const uint8_t *png, int64_t png_capacity, const int32_t *png_info, const float *b_min,
+                         const float *b_max, uint8_t *out, int64_t capacity, int32_t *info, mp_stream stream) {
+  return mesh_glb_textured_checked(ctx, "mp_mesh_glb_textured", 1, &verts, max_verts, &faces, max_faces, &counts,
+                                   normals ? &normals : nullptr, colors != nullptr, atlas_size, cell, png, png_capacity,
+                                   png_info, b_min, b_max, out, capacity, info, stream);
+}
+
+int mp_mesh_glb_textured_batch(mp_ctx *ctx, int n_frames, const float *const *verts, int64_t max_verts,
+                               const int32_t *const *faces, int64_t max_faces, const int32_t *const *counts,
+                               const float *const *normals, const float *const *colors, int atlas_size, int cell,
+                               const uint8_t *png, int64_t png_capacity, const int32_t *png_info, const float *b_min,
+                               const float *b_max, uint8_t *out, int64_t capacity, int32_t *info, mp_stream stream) {
+  return mesh_glb_textured_checked(ctx, "mp_mesh_glb_textured_batch", n_frames, verts, max_verts, faces, max_faces,
+                                   counts, normals, colors != nullptr, atlas_size, cell, png, png_capacity, png_info,
+                                   b_min, b_max, out, capacity, info, stream);
 }
 
 int mp_mesh_points(mp_ctx *ctx, const float *verts, int64_t max_verts, const int32_t *counts, float *points,

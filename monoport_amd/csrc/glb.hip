@@ -18,6 +18,8 @@
 // A frame whose file exceeds the capacity is left by the last two kernels before their first store.  A row of `out`
 // that is not 4-byte aligned in memory (an odd capacity) is written byte by byte.
 // Every float operation is one IEEE f32 operation in the order the header states.
+// The textured file (mp_mesh_glb_textured[_batch]) is the same three kernels over another layout: the second half of
+// this file.
 #include "mp_internal.h"
 #include "mesh_common.h"
 
@@ -423,6 +425,335 @@ int launch_mesh_glb_batch(mp_ctx *ctx, void *scratch, const GlbCall &c, const fl
   const dim3 grid((unsigned)((items + kGlbBlock - 1) / kGlbBlock), c.n_frames);
   if (grid.x) hipLaunchKernelGGL(glb_pack_kernel, grid, dim3(kGlbBlock), 0, st, fr, g);
   hipLaunchKernelGGL(glb_header_kernel, dim3(c.n_frames), dim3(kGlbBlock), 0, st, fr, g, tp);
+  MP_HIP(ctx, hipGetLastError());
+  return MP_OK;
+}
+
+// ---- the textured file (mp_mesh_glb_textured[_batch]) ---------------------------------------------------------------
+// The same three kernels over another layout: 3 nf corner vertices instead of nv indexed ones, TEXCOORD_0 as the
+// closed form of the atlas, and the PNG of the atlas as the last buffer view, copied by the pack kernel four bytes per
+// thread.  Only the image's length, and with it the BIN chunk's, the buffer's and the file's, come from the device.
+//   glb_tex_layout_kernel   info (code 2: too many faces for the atlas, or no usable image) and the extremes' reset
+//   glb_tex_pack_kernel     thread i: corner i -> position, normal, UV, the extremes as above; image word i
+//   glb_tex_header_kernel   the slots joined, header, JSON, BIN chunk header; or the fixed empty file
+constexpr int kGlbTexJsonMax = 2048;
+constexpr int kPngMinBytes = 57;  // MP_PNG_MIN_BYTES
+
+enum GlbTexHole { kTexHoleNc, kTexHoleMin, kTexHoleMax = kTexHoleMin + 3, kTexHolePosOff = kTexHoleMax + 3,
+                  kTexHolePosLen, kTexHoleNrmOff, kTexHoleNrmLen, kTexHoleUvOff, kTexHoleUvLen, kTexHoleImgOff,
+                  kTexHoleImgLen, kTexHoleBin };
+
+struct GlbTexFrames {
+  const float *verts[kMaxFrames];
+  const int32_t *faces[kMaxFrames];
+  const int32_t *counts[kMaxFrames];
+  const float *normals[kMaxFrames];  // all nullptr without MP_GLB_NORMALS
+};
+struct GlbTexGeom {
+  long long max_v, max_f, capacity, png_capacity;
+  int flags, json_len, size, cell, grid;
+  float b_min[3], inv[3];
+  const uint8_t *png;
+  const int32_t *png_info;
+  uint8_t *out;
+  int32_t *info;
+  int *state;
+};
+struct GlbTexTemplate {
+  uint32_t json[kGlbTexJsonMax / 4];
+  uint32_t empty[kGlbEmptyWords];
+  GlbHoleAt holes[kGlbHolesMax];
+  int n_holes;
+};
+static_assert(sizeof(GlbTexFrames) + sizeof(GlbTexGeom) + sizeof(GlbTexTemplate) + 64 <= 4096,
+              "mp_mesh_glb_textured: kernel arguments");
+
+struct GlbTexLayout {
+  int nv, nf, empty, code;  // code: 0, or 2 = no file at all
+  long long off_n, off_t, off_img, img, bin, total;
+};
+__host__ __device__ inline GlbTexLayout glb_tex_layout(long long nv, long long nf, int flags, int json_len,
+                                                       long long png_bytes) {
+  GlbTexLayout l;
+  l.nv = (int)nv, l.nf = (int)nf;
+  l.empty = nv == 0 || nf == 0;
+  l.code = 0;
+  l.off_n = 24 * nf;
+  l.off_t = l.off_n + ((flags & MP_GLB_NORMALS) ? 12 * nf : 0);
+  l.off_img = l.off_t + 24 * nf;
+  l.img = png_bytes;
+  l.bin = (l.off_img + l.img + 3) & ~3LL;
+  l.total = l.empty ? MP_GLB_MIN_BYTES : kGlbPrefix + json_len + 8 + l.bin;
+  return l;
+}
+
+__device__ __forceinline__ GlbTexLayout glb_tex_frame_layout(const GlbTexFrames &fr, const GlbTexGeom &g, int f) {
+  const int32_t *__restrict__ counts = fr.counts[f];
+  const int32_t *__restrict__ pi = g.png_info + 2 * f;
+  const long long png_bytes = pi[0];
+  GlbTexLayout l = glb_tex_layout(mesh_min(counts[0], g.max_v), mesh_min(counts[1], g.max_f), g.flags, g.json_len,
+                                  png_bytes);
+  if (!l.empty && (l.nf > 2LL * g.grid * g.grid || pi[1] != 0 || png_bytes < kPngMinBytes || png_bytes > g.png_capacity))
+    l.code = 2, l.total = 0;
+  return l;
+}
+
+__global__ __launch_bounds__(kGlbSlots) void glb_tex_layout_kernel(GlbTexFrames fr, GlbTexGeom g) {
+  const int f = blockIdx.x;
+  if (threadIdx.x == 0) {
+    const GlbTexLayout l = glb_tex_frame_layout(fr, g, f);
+    g.info[2 * f + 0] = (int32_t)l.total;
+    g.info[2 * f + 1] = l.code ? l.code : (l.total > g.capacity);
+  }
+  int *__restrict__ st = g.state + ((long long)f * kGlbSlots + threadIdx.x) * kGlbSlotInts;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) st[k] = 65535, st[3 + k] = 0;
+}
+
+__global__ __launch_bounds__(kGlbBlock) void glb_tex_pack_kernel(GlbTexFrames fr, GlbTexGeom g) {
+  const int f = blockIdx.y;
+  const GlbTexLayout l = glb_tex_frame_layout(fr, g, f);
+  if (l.empty || l.code || l.total > g.capacity) return;
+  const long long i = (long long)blockIdx.x * kGlbBlock + threadIdx.x;
+  const long long first = (long long)blockIdx.x * kGlbBlock;
+  const long long nc = 3LL * l.nf, words = (l.img + 3) >> 2;
+  if (first >= nc && first >= words) return;
+  uint8_t *row = g.out + (long long)f * g.capacity;
+  const bool dwords = ((uintptr_t)row & 3u) == 0;
+  uint8_t *bin = row + kGlbPrefix + g.json_len + 8;
+
+  if (first + (threadIdx.x & ~63u) < nc) {  // the wave holds corners
+    int lo[3] = {65535, 65535, 65535}, hi[3] = {0, 0, 0};
+    if (i < nc) {
+      const int face = (int)(i / 3), k = (int)(i - 3LL * face);
+      const int v = (int)glb_index(fr.faces[f][i], l.nv);
+      const float *__restrict__ verts = fr.verts[f];
+      int q[3];
+#pragma unroll
+      for (int a = 0; a < 3; ++a) lo[a] = hi[a] = q[a] = glb_position(verts[3LL * v + a], g.b_min[a], g.inv[a]);
+      put64(bin + 8 * i, (uint32_t)q[0] | ((uint32_t)q[1] << 16), (uint32_t)q[2], dwords);
+      if (g.flags & MP_GLB_NORMALS) {
+        const float *__restrict__ nrm = fr.normals[f];
+        put32(bin + l.off_n + 4 * i,
+              glb_normal(nrm[3LL * v + 0]) | (glb_normal(nrm[3LL * v + 1]) << 8) | (glb_normal(nrm[3LL * v + 2]) << 16),
+              dwords);
+      }
+      // the corner's texel: the cell's origin plus (0,0), (l,0), (0,l), mirrored in the upper half
+      const int cellq = face >> 1, h = face & 1, leg = g.cell - 2 - h;
+      const int ci = k == 1 ? leg : 0, cj = k == 2 ? leg : 0;
+      const int x = (cellq % g.grid) * g.cell + (h ? g.cell - 1 - ci : ci);
+      const int y = (cellq / g.grid) * g.cell + (h ? g.cell - 1 - cj : cj);
+      const float u = ((float)x + 0.5f) / (float)g.size, w = ((float)y + 0.5f) / (float)g.size;  // exact
+      put64(bin + l.off_t + 8 * i, __float_as_uint(u), __float_as_uint(w), dwords);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int a = __shfl_xor(lo[k], o), b = __shfl_xor(hi[k], o);
+        lo[k] = a < lo[k] ? a : lo[k];
+        hi[k] = b > hi[k] ? b : hi[k];
+      }
+    }
+    if ((threadIdx.x & 63) == 0) {
+      const int wave = blockIdx.x * (kGlbBlock / 64) + (threadIdx.x >> 6);
+      int *st = g.state + ((long long)f * kGlbSlots + (wave & (kGlbSlots - 1))) * kGlbSlotInts;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        if (lo[k] < __atomic_load_n(&st[k], __ATOMIC_RELAXED)) atomicMin(&st[k], lo[k]);
+        if (hi[k] > __atomic_load_n(&st[3 + k], __ATOMIC_RELAXED)) atomicMax(&st[3 + k], hi[k]);
+      }
+    }
+  }
+
+  if (i >= words) return;  // image word i: four bytes of the PNG, zeros beyond its end
+  const uint8_t *__restrict__ src = g.png + (long long)f * g.png_capacity + 4 * i;
+  uint32_t v = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (4 * i + k < l.img) v |= (uint32_t)src[k] << (8 * k);
+  put32(bin + l.off_img + 4 * i, v, dwords);
+}
+
+__device__ __forceinline__ long long glb_tex_hole_value(int kind, const GlbTexLayout &l, const int *ext) {
+  switch (kind) {
+    case kTexHoleNc: return 3LL * l.nf;
+    case kTexHolePosOff: return 0;
+    case kTexHolePosLen: return l.off_n;
+    case kTexHoleNrmOff: return l.off_n;
+    case kTexHoleNrmLen: return 12LL * l.nf;
+    case kTexHoleUvOff: return l.off_t;
+    case kTexHoleUvLen: return 24LL * l.nf;
+    case kTexHoleImgOff: return l.off_img;
+    case kTexHoleImgLen: return l.img;
+    case kTexHoleBin: return l.bin;
+    default: return ext[kind - kTexHoleMin];  // kTexHoleMin .. kTexHoleMax + 2
+  }
+}
+
+__global__ __launch_bounds__(kGlbBlock) void glb_tex_header_kernel(GlbTexFrames fr, GlbTexGeom g, GlbTexTemplate tp) {
+  __shared__ uint32_t file[(kGlbPrefix + kGlbTexJsonMax + 8) / 4];
+  __shared__ int ext[6];
+  const int f = blockIdx.x;
+  const GlbTexLayout l = glb_tex_frame_layout(fr, g, f);
+  if (l.code || l.total > g.capacity) return;
+  uint8_t *row = g.out + (long long)f * g.capacity;
+  const bool dwords = ((uintptr_t)row & 3u) == 0;
+  if (l.empty) {
+    for (int i = threadIdx.x; i < kGlbEmptyWords; i += kGlbBlock) put32(row + 4 * i, tp.empty[i], dwords);
+    return;
+  }
+  if (threadIdx.x < kGlbSlots) {
+    const int *__restrict__ st = g.state + ((long long)f * kGlbSlots + threadIdx.x) * kGlbSlotInts;
+    int lo[3], hi[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) lo[k] = st[k], hi[k] = st[3 + k];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const int a = __shfl_xor(lo[k], o), b = __shfl_xor(hi[k], o);
+        lo[k] = a < lo[k] ? a : lo[k];
+        hi[k] = b > hi[k] ? b : hi[k];
+      }
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) ext[k] = lo[k], ext[3 + k] = hi[k];
+    }
+  }
+  const int json_words = g.json_len / 4;
+  for (int i = threadIdx.x; i < json_words; i += kGlbBlock) file[kGlbPrefix / 4 + i] = tp.json[i];
+  if (threadIdx.x == 0) {
+    file[0] = 0x46546C67u;  // "glTF"
+    file[1] = 2u;
+    file[2] = (uint32_t)l.total;
+    file[3] = (uint32_t)g.json_len;
+    file[4] = 0x4E4F534Au;  // "JSON"
+    file[kGlbPrefix / 4 + json_words] = (uint32_t)l.bin;
+    file[kGlbPrefix / 4 + json_words + 1] = 0x004E4942u;  // "BIN\0"
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < tp.n_holes) {
+    const GlbHoleAt h = tp.holes[threadIdx.x];
+    long long v = glb_tex_hole_value(h.kind, l, ext);
+    uint8_t *text = reinterpret_cast<uint8_t *>(file) + kGlbPrefix + h.at;
+    for (int j = h.width - 1; j >= 0; --j) {
+      text[j] = (v > 0 || j == h.width - 1) ? (uint8_t)('0' + v % 10) : (uint8_t)' ';
+      v /= 10;
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < kGlbPrefix / 4 + json_words + 2; i += kGlbBlock) put32(row + 4 * i, file[i], dwords);
+}
+
+namespace {
+
+// the JSON text of a textured mesh under `flags` (MP_GLB_NORMALS or 0) with its holes, padded to a length % 8 == 4
+GlbText glb_tex_text(int flags, const float *b_min, const float *b_max) {
+  const bool nrm = flags & MP_GLB_NORMALS;
+  const int c = 1 + nrm, k = c + 1;
+  GlbText t;
+  t.put(kGlbAsset);
+  t.put(",\"extensionsUsed\":[\"KHR_mesh_quantization\"],\"extensionsRequired\":[\"KHR_mesh_quantization\"]");
+  t.put(",\"scene\":0,\"scenes\":[{\"nodes\":[0]}],\"nodes\":[{\"mesh\":0,\"translation\":[");
+  for (int a = 0; a < 3; ++a) t.put(a ? "," : ""), t.real((double)b_min[a]);
+  t.put("],\"scale\":[");
+  for (int a = 0; a < 3; ++a) t.put(a ? "," : ""), t.real(((double)b_max[a] - (double)b_min[a]) / 65535.0);
+  t.put("]}],\"materials\":[{\"doubleSided\":true,\"pbrMetallicRoughness\":{\"baseColorTexture\":{\"index\":0},"
+        "\"metallicFactor\":0,\"roughnessFactor\":1}}],\"textures\":[{\"sampler\":0,\"source\":0}],"
+        "\"samplers\":[{\"magFilter\":9729,\"minFilter\":9729,\"wrapS\":33071,\"wrapT\":33071}],"
+        "\"images\":[{\"bufferView\":");
+  t.integer(k);
+  t.put(",\"mimeType\":\"image/png\"}],\"meshes\":[{\"primitives\":[{\"attributes\":{\"POSITION\":0");
+  if (nrm) t.put(",\"NORMAL\":1");
+  t.put(",\"TEXCOORD_0\":"), t.integer(c);
+  t.put("},\"material\":0,\"mode\":4}]}],\"accessors\":[{\"bufferView\":0,\"componentType\":5123,\"count\":");
+  t.hole(kTexHoleNc, 10);
+  t.put(",\"type\":\"VEC3\",\"min\":[");
+  for (int a = 0; a < 3; ++a) t.put(a ? "," : ""), t.hole(kTexHoleMin + a, 5);
+  t.put("],\"max\":[");
+  for (int a = 0; a < 3; ++a) t.put(a ? "," : ""), t.hole(kTexHoleMax + a, 5);
+  t.put("]}");
+  if (nrm) {
+    t.put(",{\"bufferView\":1,\"componentType\":5120,\"normalized\":true,\"count\":");
+    t.hole(kTexHoleNc, 10);
+    t.put(",\"type\":\"VEC3\"}");
+  }
+  t.put(",{\"bufferView\":"), t.integer(c);
+  t.put(",\"componentType\":5126,\"count\":"), t.hole(kTexHoleNc, 10);
+  t.put(",\"type\":\"VEC2\"}],\"bufferViews\":[");
+  const int views[4][2] = {{kTexHolePosOff, kTexHolePosLen}, {kTexHoleNrmOff, kTexHoleNrmLen},
+                           {kTexHoleUvOff, kTexHoleUvLen}, {kTexHoleImgOff, kTexHoleImgLen}};
+  const bool present[4] = {true, nrm, true, true};
+  const char *const tails[4] = {",\"byteStride\":8,\"target\":34962}", ",\"byteStride\":4,\"target\":34962}",
+                                ",\"byteStride\":8,\"target\":34962}", "}"};
+  for (int v = 0; v < 4; ++v) {
+    if (!present[v]) continue;
+    t.put(v ? ",{\"buffer\":0,\"byteOffset\":" : "{\"buffer\":0,\"byteOffset\":");
+    t.hole(views[v][0], 10);
+    t.put(",\"byteLength\":"), t.hole(views[v][1], 10);
+    t.put(tails[v]);
+  }
+  t.put("],\"buffers\":[{\"byteLength\":"), t.hole(kTexHoleBin, 10);
+  t.put("}]}");
+  t.s.append((size_t)((12 - t.s.size() % 8) % 8), ' ');
+  return t;
+}
+
+int glb_tex_json_len(int flags) {
+  const float lo[3] = {0, 0, 0}, hi[3] = {1, 1, 1};
+  return (int)glb_tex_text(flags, lo, hi).s.size();
+}
+
+}  // namespace
+
+long long glb_textured_bytes(long long nf, int flags, long long png_bytes) {
+  return glb_tex_layout(nf ? 1 : 0, nf, flags, glb_tex_json_len(flags), png_bytes).total;
+}
+
+int launch_mesh_glb_textured_batch(mp_ctx *ctx, void *scratch, const GlbCall &c, const GlbTextureCall &tc,
+                                   const float *const *verts, const int32_t *const *faces,
+                                   const int32_t *const *counts, const float *const *normals, uint8_t *out,
+                                   int32_t *info, hipStream_t st) {
+  GlbTexFrames fr;
+  std::memset(&fr, 0, sizeof(fr));
+  for (int f = 0; f < c.n_frames; ++f) {
+    fr.verts[f] = verts ? verts[f] : nullptr;
+    fr.faces[f] = faces ? faces[f] : nullptr;
+    fr.counts[f] = counts[f];
+    fr.normals[f] = normals ? normals[f] : nullptr;
+  }
+  GlbTexGeom g;
+  std::memset(&g, 0, sizeof(g));
+  g.max_v = c.max_v, g.max_f = c.max_f, g.capacity = c.capacity, g.png_capacity = tc.png_capacity;
+  g.flags = normals ? MP_GLB_NORMALS : 0;
+  g.size = tc.size, g.cell = tc.cell, g.grid = tc.size / tc.cell;
+  for (int a = 0; a < 3; ++a) g.b_min[a] = c.b_min[a], g.inv[a] = c.inv[a];
+  g.png = tc.png, g.png_info = tc.png_info;
+  g.out = out, g.info = info, g.state = static_cast<int *>(scratch);
+  const GlbText text = glb_tex_text(g.flags, c.b_min, c.b_max);
+  const std::string empty = std::string(kGlbAsset) + ",\"scene\":0,\"scenes\":[{}]}  ";
+  if (text.s.size() > (size_t)kGlbTexJsonMax || text.s.size() % 8 != 4 ||
+      (int)text.s.size() != glb_tex_json_len(g.flags) || text.n_holes > kGlbHolesMax ||
+      empty.size() != MP_GLB_MIN_BYTES - kGlbPrefix)
+    return fail(ctx, MP_ERR_STATE, "mp_mesh_glb_textured: a JSON text of %zu bytes", text.s.size());
+  g.json_len = (int)text.s.size();
+  GlbTexTemplate tp;
+  std::memset(&tp, 0, sizeof(tp));
+  std::memcpy(tp.json, text.s.data(), text.s.size());
+  std::memcpy(tp.holes, text.holes, sizeof(text.holes));
+  tp.n_holes = text.n_holes;
+  const uint32_t head[5] = {0x46546C67u, 2u, MP_GLB_MIN_BYTES, MP_GLB_MIN_BYTES - kGlbPrefix, 0x4E4F534Au};
+  std::memcpy(tp.empty, head, sizeof(head));
+  std::memcpy(tp.empty + 5, empty.data(), empty.size());
+
+  hipLaunchKernelGGL(glb_tex_layout_kernel, dim3(c.n_frames), dim3(kGlbSlots), 0, st, fr, g);
+  const long long words = (tc.png_capacity + 3) / 4, corners = 3 * c.max_f;
+  const long long items = corners > words ? corners : words;
+  const dim3 grid((unsigned)((items + kGlbBlock - 1) / kGlbBlock), c.n_frames);
+  hipLaunchKernelGGL(glb_tex_pack_kernel, grid, dim3(kGlbBlock), 0, st, fr, g);
+  hipLaunchKernelGGL(glb_tex_header_kernel, dim3(c.n_frames), dim3(kGlbBlock), 0, st, fr, g, tp);
   MP_HIP(ctx, hipGetLastError());
   return MP_OK;
 }

@@ -553,6 +553,26 @@ size_t glb_scratch_bytes(int n_frames);
 int launch_mesh_glb_batch(mp_ctx *ctx, void *scratch, const GlbCall &c, const float *const *verts,
                           const int32_t *const *faces, const int32_t *const *counts, const float *const *normals,
                           const float *const *colors, uint8_t *out, int32_t *info, hipStream_t st);
+// glb.hip: the textured file: GlbCall without its colour fields, and the atlas (size, cell) with the PNGs of the
+// frames' atlases, png [n,png_capacity] and png_info [n,2] on the device.  Scratch: glb_scratch_bytes(n_frames).
+// glb_textured_bytes: the closed form (flags: MP_GLB_NORMALS or 0, checked by the caller; nf, png_bytes >= 0)
+struct GlbTextureCall {
+  int size, cell;
+  const uint8_t *png;
+  long long png_capacity;
+  const int32_t *png_info;
+};
+long long glb_textured_bytes(long long nf, int flags, long long png_bytes);
+int launch_mesh_glb_textured_batch(mp_ctx *ctx, void *scratch, const GlbCall &c, const GlbTextureCall &tc,
+                                   const float *const *verts, const int32_t *const *faces,
+                                   const int32_t *const *counts, const float *const *normals, uint8_t *out,
+                                   int32_t *info, hipStream_t st);
+// atlas.hip: the texture-space G-buffer of n_frames meshes of one capacity: face_id [size^2], position [size^2,3] and
+// info[2] per frame.  size: a power of two >= 64; cell: 4..64 (checked by the caller).  No scratch
+int launch_mesh_atlas_batch(mp_ctx *ctx, int n_frames, const float *const *verts, long long max_v,
+                            const int32_t *const *faces, long long max_f, const int32_t *const *counts, int size,
+                            int cell, float background, int32_t *const *face_id, float *const *position,
+                            int32_t *const *info, hipStream_t st);
 #ifdef __HIPCC__
 // v / |v|, or (0, 0, 0) where |v|^2 is not finite or not > 0 (a zero, a NaN, an inf, an overflow)
 __device__ __forceinline__ void light_normalise(float x, float y, float z, float &ox, float &oy, float &oz) {

@@ -1551,6 +1551,159 @@ def mesh_glb_raw_batch(verts, faces, counts, normals=None, colors=None, color_la
                      color_bias, b_min, b_max, capacity, out, info)
 
 
+# MP_ATLAS_* (include/monoport_hip.h)
+ATLAS_MIN_SIZE, ATLAS_MAX_SIZE = 64, 4096
+ATLAS_MIN_CELL, ATLAS_MAX_CELL = 4, 64
+
+
+def atlas_params(who, size, cell):
+    """(A, T) of mp_mesh_atlas, checked: A a power of two in 64..4096, T in 4..64."""
+    for name, v in (("size", size), ("cell", cell)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError("%s: %s must be an int, got %r" % (who, name, v))
+    if not ATLAS_MIN_SIZE <= size <= ATLAS_MAX_SIZE or size & (size - 1):
+        raise ValueError("%s: size must be a power of two in %d..%d, got %r" % (who, ATLAS_MIN_SIZE, ATLAS_MAX_SIZE, size))
+    if not ATLAS_MIN_CELL <= cell <= ATLAS_MAX_CELL:
+        raise ValueError("%s: cell must be in %d..%d, got %r" % (who, ATLAS_MIN_CELL, ATLAS_MAX_CELL, cell))
+    return int(size), int(cell)
+
+
+def atlas_faces(size, cell):
+    """The faces an atlas of side ``size`` with cells of side ``cell`` holds: 2 G^2 with G = size // cell."""
+    size, cell = atlas_params("atlas_faces", size, cell)
+    return 2 * (size // cell) ** 2
+
+
+def _mesh_atlas(who, verts, faces, counts, size, cell, background, out):
+    n, max_v, max_f, dev = _mesh_frames(who, verts, faces, counts)
+    size, cell = atlas_params(who, size, cell)
+    background = _finite_float(who, "background", background)
+    if out is None:
+        face_id = torch.empty((n, size, size), dtype=torch.int32, device=dev).unbind(0)
+        position = torch.empty((n, size, size, 3), dtype=torch.float32, device=dev).unbind(0)
+        info = torch.empty((n, 2), dtype=torch.int32, device=dev).unbind(0)
+    else:
+        face_id = _frame_rows(who, "out[0] (face_id)", out[0], n, (size, size), torch.int32, dev)
+        position = _frame_rows(who, "out[1] (position)", out[1], n, (size, size, 3), torch.float32, dev)
+        info = _frame_rows(who, "out[2] (info)", out[2], n, (2,), torch.int32, dev)
+    ctx = get_context(dev)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_mesh_atlas_batch(
+            ctx.handle, f1 - f0, _ptr_array(verts[f0:f1]), max_v, _ptr_array(faces[f0:f1]), max_f,
+            _ptr_array(counts[f0:f1]), size, cell, background, _ptr_array(face_id[f0:f1]),
+            _ptr_array(position[f0:f1]), _ptr_array(info[f0:f1]), _stream(verts[0])), "mp_mesh_atlas_batch")
+    _keep_until_done(dev, verts, faces, counts)
+    return list(zip(face_id, position, info))
+
+
+def mesh_atlas_raw(verts, faces, counts, size, cell, background=0.5, out=None):
+    """mp_mesh_atlas_batch with one frame: the texture-space G-buffer of verts [max_v,3] f32, faces [max_f,3] int32,
+    counts int32[2] on device in an atlas of side ``size`` (a power of two in 64..4096) with cells of side ``cell``
+    (4..64), bit for bit as include/monoport_hip.h defines it -> (face_id int32 [size,size], position float32
+    [size,size,3], info int32[2] = (faces laid out, faces of the mesh)): what one view of the rasteriser with ``attr =
+    verts`` is in screen space, for ``picture_points`` / ``picture_paint`` / ``picture_png_raw``.  Texels of no face
+    hold -1 and ``background``; every texel is written.  ``out``: these three to write into.  One launch; no host
+    sync."""
+    return _mesh_atlas("mesh_atlas_raw", [verts], [faces], [counts], size, cell, background,
+                       None if out is None else tuple([o] for o in out))[0]
+
+
+def mesh_atlas_raw_batch(verts, faces, counts, size, cell, background=0.5, out=None):
+    """mp_mesh_atlas_batch: ``[mesh_atlas_raw(v, f, c, size, cell, background) for ...]`` (lists of per-mesh device
+    tensors of one capacity) in ONE launch per MAX_FRAMES meshes, the same bits.  ``out``: (face_id [n,size,size],
+    position [n,size,size,3], info [n,2]) to write into.  No host sync."""
+    return _mesh_atlas("mesh_atlas_raw_batch", verts, faces, counts, size, cell, background, out)
+
+
+def glb_textured_bytes(nf, png_bytes, normals=True):
+    """mp_glb_textured_bytes: the size of the textured binary glTF file of a mesh of ``nf`` faces whose image is a PNG
+    of ``png_bytes`` bytes -- a closed form (include/monoport_hip.h); the empty file's 100 bytes for ``nf`` == 0."""
+    for v in (nf, png_bytes):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError("glb_textured_bytes: nf and png_bytes must be ints >= 0, got %r and %r" % (nf, png_bytes))
+    return int(_lib.load().mp_glb_textured_bytes(int(nf), _glb_flags(normals, False), int(png_bytes)))
+
+
+def glb_textured_max_bytes(max_faces, size, normals=True):
+    """mp_glb_textured_max_bytes: what no textured file of a mesh of at most ``max_faces`` faces with an atlas of side
+    ``size`` exceeds: ``glb_textured_bytes`` with ``png_max_bytes(size, size)``."""
+    if isinstance(max_faces, bool) or not isinstance(max_faces, (int, np.integer)) or max_faces < 0:
+        raise ValueError("glb_textured_max_bytes: max_faces must be an int >= 0, got %r" % (max_faces,))
+    size, _ = atlas_params("glb_textured_max_bytes", size, ATLAS_MIN_CELL)
+    return int(_lib.load().mp_glb_textured_max_bytes(int(max_faces), _glb_flags(normals, False), size))
+
+
+def _mesh_glb_textured(who, verts, faces, counts, normals, colors, size, cell, png, png_info, b_min, b_max, capacity,
+                       out, info):
+    n, max_v, max_f, dev = _mesh_frames(who, verts, faces, counts)
+    size, cell = atlas_params(who, size, cell)
+    if colors is not None:
+        raise ValueError("%s: COLOR_0 together with a texture: glTF multiplies the two; colors must be None" % who)
+    if normals is not None:
+        normals = _frame_rows(who, "normals", normals, n, (max_v, 3), torch.float32, dev)
+    if (not isinstance(png, torch.Tensor) or png.dtype != torch.uint8 or png.dim() != 2 or png.shape[0] != n
+            or not png.is_contiguous() or png.device != dev or png.shape[1] < PNG_MIN_BYTES):
+        raise ValueError("%s: png must be a contiguous uint8 tensor [%d,png_capacity >= %d] on %s"
+                         % (who, n, PNG_MIN_BYTES, dev))
+    if (not isinstance(png_info, torch.Tensor) or png_info.dtype != torch.int32 or tuple(png_info.shape) != (n, 2)
+            or not png_info.is_contiguous() or png_info.device != dev):
+        raise ValueError("%s: png_info must be a contiguous int32 tensor [%d,2] on %s" % (who, n, dev))
+    if out is not None:
+        if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.dim() != 2 or out.shape[0] != n
+                or not out.is_contiguous() or out.device != dev):
+            raise ValueError("%s: out must be a contiguous uint8 tensor [%d,capacity] on %s" % (who, n, dev))
+        if capacity is not None and int(capacity) != out.shape[1]:
+            raise ValueError("%s: capacity %r against an out of %d bytes per mesh" % (who, capacity, out.shape[1]))
+        capacity = int(out.shape[1])
+    elif capacity is None:
+        capacity = glb_textured_bytes(max_f, int(png.shape[1]), normals is not None)
+    if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or capacity < GLB_MIN_BYTES:
+        raise ValueError("%s: capacity must be an int >= the empty file's %d bytes, got %r"
+                         % (who, GLB_MIN_BYTES, capacity))
+    if info is None:
+        info = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    elif (not isinstance(info, torch.Tensor) or info.dtype != torch.int32 or tuple(info.shape) != (n, 2)
+          or not info.is_contiguous() or info.device != dev):
+        raise ValueError("%s: info must be a contiguous int32 tensor [%d,2] on %s" % (who, n, dev))
+    if out is None:
+        out = torch.empty((n, int(capacity)), dtype=torch.uint8, device=dev)
+    ctx = get_context(dev)
+    for f0, f1 in _frame_chunks(n):
+        ctx.check(ctx.lib.mp_mesh_glb_textured_batch(
+            ctx.handle, f1 - f0, _ptr_array(verts[f0:f1]), max_v, _ptr_array(faces[f0:f1]), max_f,
+            _ptr_array(counts[f0:f1]), None if normals is None else _ptr_array(normals[f0:f1]), None, size, cell,
+            _ptr(png[f0:f1]), int(png.shape[1]), _ptr(png_info[f0:f1]), _float3(b_min), _float3(b_max),
+            _ptr(out[f0:f1]), int(capacity), _ptr(info[f0:f1]), _stream(verts[0])), "mp_mesh_glb_textured_batch")
+    _keep_until_done(dev, verts, faces, counts, normals, [png, png_info])
+    return out, info
+
+
+def mesh_glb_textured_raw(verts, faces, counts, size, cell, png, png_info, normals=None, colors=None,
+                          b_min=(-1, -1, -1), b_max=(1, 1, 1), capacity=None, out=None, info=None):
+    """mp_mesh_glb_textured_batch with one frame: the binary glTF file of verts [max_v,3] f32, faces [max_f,3] int32,
+    counts int32[2] on device as a NOT indexed primitive of 3 nf corner vertices -- 16-bit positions, with ``normals``
+    [max_v,3] signed bytes, TEXCOORD_0 the closed form of the atlas (``size``, ``cell``) -- and, as its base colour
+    texture inside the file, the PNG ``png`` uint8 [1,png_capacity] with ``png_info`` int32 [1,2] that
+    ``picture_png_raw`` ("rgb8") made of the atlas's image -> (out uint8 [1,capacity], info int32 [1,2] = (bytes, code)):
+    code 0 the file is ``out[0, :bytes]``; 1 nothing was written and ``bytes`` is the capacity it needs; 2 nothing was
+    written: more faces than the atlas holds, or the PNG itself had overflowed.  ``colors`` must stay None: glTF
+    multiplies COLOR_0 into the texture.  ``capacity``: None = the size at ``max_f`` faces and a PNG of
+    ``png_capacity`` (never code 1).  Three launches; no host sync."""
+    return _mesh_glb_textured("mesh_glb_textured_raw", [verts], [faces], [counts],
+                              None if normals is None else [normals], colors, size, cell, png, png_info, b_min, b_max,
+                              capacity, out, info)
+
+
+def mesh_glb_textured_raw_batch(verts, faces, counts, size, cell, png, png_info, normals=None, colors=None,
+                                b_min=(-1, -1, -1), b_max=(1, 1, 1), capacity=None, out=None, info=None):
+    """mp_mesh_glb_textured_batch: the files of ``mesh_glb_textured_raw`` for lists of per-mesh device tensors of one
+    capacity (``normals``: None, or one tensor per mesh; ``png`` [n,png_capacity], ``png_info`` [n,2]) in ONE set of
+    three launches per MAX_FRAMES meshes -> (out uint8 [n,capacity], info int32 [n,2]), row f byte for byte what the
+    per-mesh call gives.  No host sync."""
+    return _mesh_glb_textured("mesh_glb_textured_raw_batch", verts, faces, counts, normals, colors, size, cell, png,
+                              png_info, b_min, b_max, capacity, out, info)
+
+
 def _mesh_points(who, verts, counts, out):
     n, max_v, _, dev = _mesh_frames(who, verts, None, counts)
     if out is None:
@@ -1934,10 +2087,19 @@ def render_netc_batch(who, verts, faces, counts, calibs, ras, query, out=None, l
     images, face_ids = [r[0] for r in raws], [r[2] for r in raws]
     if positions_hook is not None:
         positions_hook(images, face_ids)
+    paint_netc(who, face_ids, images, query, lists)
+    return raws
+
+
+def paint_netc(who, face_ids, images, query, lists=None):
+    """Steps (2) to (4) of ``render_netc_batch`` on G-buffers that are already there -- per frame a face-id picture and
+    an image [..., 3] that holds the world positions of its covered pixels, from the rasteriser (screen space) or from
+    ``mesh_atlas_raw_batch`` (texture space): the covered pixels' point lists, ``query(points, counts)``, and the paint
+    with (0.5, 0.5, -inf, inf) into ``images``, in place.  Returns ``images``."""
     found = _picture_points(who, face_ids, images, None, lists)
     preds = query([f[0] for f in found], [f[2] for f in found])
     _picture_paint(who, list(preds), [f[1] for f in found], [f[2] for f in found], images, 0.5, 0.5, -math.inf, math.inf)
-    return raws
+    return images
 
 
 # MP_WRAP_* / MP_COMPOSITE_* (include/monoport_hip.h)

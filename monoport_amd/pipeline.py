@@ -800,7 +800,15 @@ class FrameSlot:
         buffers' capacities) and ``glb_info`` [batch, 2] int32, and the chain enqueues ONE mp_mesh_glb_batch per chunk
         of the mesh chain, behind that chunk on the slot's stream, with no host value in between: the chain's raw netC
         predictions go in as planes with (0.5, 0.5), which gives the bytes of the finished colours.  ``glbs()`` hands the
-        files out.  A slot on which this was never called allocates and enqueues nothing for it."""
+        files out.  A slot on which this was never called allocates and enqueues nothing for it.
+
+        With ``glb.texture`` (a ``recon.Atlas`` of side A) the slot needs its ``netC`` -- not the mesh's colours: with
+        ``mesh={"colors": False}`` the per-vertex query is never enqueued -- and also owns ``atlas_face`` [batch,A,A],
+        ``atlas_image`` [batch,A,A,3], ``atlas_info`` [batch,2], the point / pixel / prediction / count lists of A^2
+        entries per frame (``atlas_lists``), ``atlas_png`` [batch, the atlas's PNG capacity] and ``atlas_png_info``.
+        Behind each chunk of the mesh chain it then enqueues the atlas, the covered texels' lists, netC through the
+        ``_colour_query`` hook (a ``ColorViewsSlot``'s with its ``view``), the paint, one mp_picture_png and one
+        mp_mesh_glb_textured_batch.  A slot with a plain ``Glb`` has none of these attributes."""
         from .recon import Glb
         who = "%s.encode_meshes" % type(self).__name__
         if not isinstance(glb, Glb):
@@ -811,31 +819,83 @@ class FrameSlot:
             raise ValueError("%s: glb asks for normals and the slot's meshes have none (mesh normals=None)" % who)
         if glb.colors and not self.mesh.colors:
             raise ValueError("%s: glb asks for colors and the slot's meshes have none (no netC, or colors=False)" % who)
+        if glb.texture is not None and self.netC is None:
+            raise ValueError("%s: glb.texture is baked from netC, which this slot does not run" % who)
         if self._chained:
             raise RuntimeError("%s: to be called before the first prepare / submit" % who)
         cap_v, cap_f = self.mesh_buffers["verts"].shape[1], self.mesh_buffers["faces"].shape[1]
         self.glb_bytes = torch.empty((self.batch, glb.capacity_for(cap_v, cap_f)), dtype=torch.uint8,
                                      device=self.device)
         self.glb_info = torch.zeros((self.batch, 2), dtype=torch.int32, device=self.device)
+        if glb.texture is not None:  # 28 bytes per texel of lists, as ``picture_lists``, and 16 of pictures
+            b, a, dev = self.batch, glb.texture.size, self.device
+            self.atlas_face = torch.empty((b, a, a), dtype=torch.int32, device=dev)
+            self.atlas_image = torch.empty((b, a, a, 3), dtype=torch.float32, device=dev)
+            self.atlas_info = torch.zeros((b, 2), dtype=torch.int32, device=dev)
+            self.atlas_lists = {"points": torch.zeros((b, 3, a * a), dtype=torch.float32, device=dev),
+                                "pixels": torch.zeros((b, a * a), dtype=torch.int32, device=dev),
+                                "preds": torch.zeros((b, 3, a * a), dtype=torch.float32, device=dev),
+                                "count": torch.zeros((b, 2), dtype=torch.int32, device=dev)}
+            self.atlas_png = torch.empty((b, glb.texture.png_capacity()), dtype=torch.uint8, device=dev)
+            self.atlas_png_info = torch.zeros((b, 2), dtype=torch.int32, device=dev)
         self.glb = glb
 
     def _encode_meshes(self, b0, b1):
         """One mp_mesh_glb_batch over the chains of frames b0..b1 as the chunk left them."""
         chains = self._mesh_chains[b0:b1]
+        if self.glb.texture is not None:
+            return self._encode_textured_meshes(b0, b1)
         ops.mesh_glb_raw_batch([c.verts for c in chains], [c.faces for c in chains], [c.counts for c in chains],
                                [c.normals for c in chains] if self.glb.normals else None,
                                [c.preds for c in chains] if self.glb.colors else None, "planes", 0.5, 0.5,
                                self.b_min, self.b_max, out=self.glb_bytes[b0:b1], info=self.glb_info[b0:b1])
+
+    def _encode_textured_meshes(self, b0, b1):
+        """The textured files of frames b0..b1 behind their chunk of the mesh chain, into the slot's static buffers, with
+        no host value in between: ``recon._bake`` (one mp_mesh_atlas_batch, the covered texels' lists, the
+        ``_colour_query`` hook per chunk of frames, the paint), ONE mp_picture_png, ONE mp_mesh_glb_textured_batch."""
+        from .recon import _bake, _chain_subjects, _png_raw
+        who, atlas, chains = "%s.encode_meshes" % type(self).__name__, self.glb.texture, self._mesh_chains[b0:b1]
+        mlp_c = self.netC.surface_classifier.packed()
+        step = self._colour_chunk()
+        outs = list(self.atlas_lists["preds"][b0:b1])
+
+        def query(pts, counts):
+            for c0 in range(0, b1 - b0, step):
+                c1 = min(c0 + step, b1 - b0)
+                self._colour_query(mlp_c, b0 + c0, b0 + c1, pts[c0:c1], counts[c0:c1], outs=outs[c0:c1])
+            return outs
+        out = dict(face=self.atlas_face[b0:b1], image=self.atlas_image[b0:b1], info=self.atlas_info[b0:b1],
+                   lists=tuple(self.atlas_lists[k][b0:b1] for k in ("points", "pixels", "count")))
+        _bake(who, _chain_subjects(chains, None), atlas, query, out)
+        _png_raw(atlas.png, self.atlas_image[b0:b1], None, out=self.atlas_png[b0:b1], info=self.atlas_png_info[b0:b1])
+        ops.mesh_glb_textured_raw_batch([c.verts for c in chains], [c.faces for c in chains], [c.counts for c in chains],
+                                        atlas.size, atlas.cell, self.atlas_png[b0:b1], self.atlas_png_info[b0:b1],
+                                        [c.normals for c in chains] if self.glb.normals else None, None, self.b_min,
+                                        self.b_max, out=self.glb_bytes[b0:b1], info=self.glb_info[b0:b1])
+
+    def _glb_again(self, b, mesh):
+        """Frame b's file from its ``Mesh`` at the file's own size: ``recon.encode_glb``; a textured one with the
+        slot's own maps and calibration (``_colour_bindings``)."""
+        from .recon import Glb, _counted_colours, _encode_glb_textured, encode_glb
+        exact = Glb(self.glb.normals, self.glb.colors, texture=self.glb.texture)  # no second overflow
+        if self.glb.texture is None:
+            return encode_glb(mesh, exact, self.b_min, self.b_max)
+        bindings = self._colour_bindings(b, b + 1)
+        return _encode_glb_textured("%s.glbs" % type(self).__name__, [mesh], exact, self.b_min, self.b_max,
+                                    lambda pts, counts: _counted_colours(bindings, pts, counts, view=self.view or 0))[0]
 
     def glbs(self):
         """The binary glTF files of the current submission's meshes, to be called after ``wait()`` (it waits if the
         caller has not): a list of ``n_active`` entries, ``bytes`` per frame or None where ``meshes()`` gives None.  One
         device-to-host copy of ``glb_info`` and one of the used prefixes of ``glb_bytes`` (besides ``meshes()``' own).  A
         frame whose mesh ``meshes()`` made again, or whose file exceeded the capacity, is encoded from its ``Mesh``
-        (``recon.encode_glb``): the same bytes a sufficient capacity gives."""
+        (``recon.encode_glb``): the same bytes a sufficient capacity gives.  With ``glb.texture`` such a frame's texture
+        is baked again with the slot's own maps and calibration, and so is one whose image exceeded the atlas's PNG
+        capacity; a mesh with more faces than the atlas holds raises a ValueError that names both numbers."""
         if self.glb is None:
             raise RuntimeError("%s.glbs(): encode_meshes(glb) was never called on this slot" % type(self).__name__)
-        from .recon import Glb, _collect_files, encode_glb
+        from .recon import _collect_files
         meshes = self.meshes()
         info = self.glb_info[:self.n_active].cpu().numpy()
         again = [m is not None and (b in self._reran or bool(info[b, 1])) for b, m in enumerate(meshes)]
@@ -844,9 +904,7 @@ class FrameSlot:
             if m is None or again[b]:
                 mine[b] = (0, 0)  # nothing of this row is copied
         files = _collect_files(type(self).__name__, self.glb_bytes, mine, None)
-        exact = Glb(self.glb.normals, self.glb.colors)  # the file's own size: no second overflow
-        return [None if m is None else (encode_glb(m, exact, self.b_min, self.b_max) if again[b] else files[b])
-                for b, m in enumerate(meshes)]
+        return [None if m is None else (self._glb_again(b, m) if again[b] else files[b]) for b, m in enumerate(meshes)]
 
     def meshes(self):
         """The meshes of the current submission, to be called after ``wait()`` (it waits if the caller has not): a

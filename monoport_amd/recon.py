@@ -1434,6 +1434,116 @@ def encode_png(pictures, png=None, alpha=None):
     return files[0] if single else files
 
 
+class Atlas:
+    """The texture of a mesh file (mp_mesh_atlas in include/monoport_hip.h): a square picture of side ``size`` (a power
+    of two in 64..4096) cut into cells of side ``cell`` (4..64), two faces per cell, each face a right triangle of its
+    own with a gutter, so that a viewer's bilinear lookup never leaves the face.  ``faces`` = 2 (size // cell)^2 is what
+    the atlas holds; the detail is ``cell`` texels along a face's legs whatever the mesh density.  ``filter``: the PNG
+    filter of the image (``Png``'s); ``background``: the colour of texels no face owns; ``png_capacity``: bytes
+    reserved per image, None = ``Png``'s own default for a picture of that size.  Everything is validated here; an
+    Atlas holds host values only."""
+
+    def __init__(self, size=1024, cell=8, filter="adaptive", background=0.5, png_capacity=None):
+        who = "Atlas"
+        self.size, self.cell = ops.atlas_params(who, size, cell)
+        self.background = ops._finite_float(who, "background", background)
+        self.png = Png(filter=filter, capacity=png_capacity)
+        self.filter = self.png.filter
+        self.faces = ops.atlas_faces(self.size, self.cell)
+
+    def png_capacity(self):
+        """Bytes reserved per image."""
+        return self.png.capacity_for(self.size, self.size)
+
+
+def _check_colour_field(who, colors, points):
+    """``colors(points)`` of ``bake_texture``: raw predictions [3,K] f32 for points [3,K]."""
+    got = colors(points)
+    if (not torch.is_tensor(got) or got.dtype != torch.float32 or got.shape != points.shape
+            or got.device != points.device):
+        raise ValueError("%s: colors(points [3,K]) must return a float32 tensor [3,K] on the points' device, got %r"
+                         % (who, tuple(got.shape) if torch.is_tensor(got) else type(got).__name__))
+    return got.contiguous()
+
+
+def _atlas_query(who, meshes, netC, feat_tensors_C, calib_tensors, view, colors):
+    """The counted colour query ``(points, counts) -> predictions`` of ``bake_texture`` / ``encode_glb``: netC on the
+    meshes' own maps and calibrations, as ``render_mesh_many(shade="netC")`` binds it, or the caller's ``colors``."""
+    if (netC is None) == (colors is None):
+        raise ValueError("%s: a texture is baked from netC= (with its feature maps and calibrations) or from colors=, "
+                         "one of the two" % who)
+    if colors is not None:
+        if not callable(colors) or feat_tensors_C is not None or calib_tensors is not None or view is not None:
+            raise ValueError("%s: colors= is a callable points [3,K] -> [3,K] and takes no maps, calibrations or view"
+                             % who)
+        return lambda pts, counts: [_check_colour_field(who, colors, p) for p in pts]
+    _check_colour_view(who, netC, view)
+    if feat_tensors_C is None or calib_tensors is None:
+        raise ValueError("%s: netC needs feat_tensors_C and calib_tensors" % who)
+    if len(feat_tensors_C) != len(meshes) or len(calib_tensors) != len(meshes):
+        raise ValueError("%s: %d meshes, %d feature sets, %d calibrations"
+                         % (who, len(meshes), len(feat_tensors_C), len(calib_tensors)))
+    bindings = _bind_netC(who, netC, [(feat_tensors_C[i], calib_tensors[i], m.verts.device)
+                                      for i, m in enumerate(meshes)], view)
+    return lambda pts, counts: _counted_colours(bindings, pts, counts, view=view or 0)
+
+
+def _bake(who, subjects, atlas, query, out=None):
+    """THE baked texture of a set of subjects (a ``_Subjects``: a call's meshes or a slot's chains), for
+    ``bake_texture``, ``encode_glb`` and a slot alike: ``ops.mesh_atlas_raw_batch`` -- the G-buffer in texture space --
+    then ``ops.paint_netc``, the body of ``shade="netC"``: the covered texels' points, ``query``, the paint in place.
+    -> (images, face_ids, infos), lists with one entry per subject.  ``out``: None (fresh tensors), or a dict of the
+    caller's buffers, each [n, ...]: ``face``, ``image``, ``info`` and ``lists`` = (points, pixels, count)."""
+    s, out = subjects, out or {}
+    buffers = (out["face"], out["image"], out["info"]) if "face" in out else None
+    if s.capacity is None or all(v.shape[0] == s.verts[0].shape[0] for v in s.verts) \
+            and all(f.shape[0] == s.faces[0].shape[0] for f in s.faces):
+        made = ops.mesh_atlas_raw_batch(s.verts, s.faces, s.counts, atlas.size, atlas.cell, atlas.background, buffers)
+    else:  # meshes cut to their own sizes: one launch each
+        made = [ops.mesh_atlas_raw(v, f, c, atlas.size, atlas.cell, atlas.background,
+                                   None if buffers is None else tuple(b[i] for b in buffers))
+                for i, (v, f, c) in enumerate(zip(s.verts, s.faces, s.counts))]
+    faces, images = [m[0] for m in made], [m[1] for m in made]
+    ops.paint_netc(who, faces, images, query, out.get("lists"))
+    return images, faces, [m[2] for m in made]
+
+
+def _texture_meshes(who, meshes):
+    single = isinstance(meshes, Mesh)
+    meshes = [meshes] if single else list(meshes)
+    for k, m in enumerate(meshes):
+        if not isinstance(m, Mesh):
+            raise ValueError("%s: mesh %d is not a recon.Mesh but %r" % (who, k, type(m).__name__))
+    return meshes, single
+
+
+@torch.no_grad()
+def bake_texture(meshes, atlas, netC=None, feat_tensors_C=None, calib_tensors=None, view=None, colors=None):
+    """The texture of ``meshes`` (a ``Mesh`` on the device, or a list of them) in ``atlas`` (an ``Atlas``), baked on
+    the device: (image [n,A,A,3] f32, face_id [n,A,A] int32) -- without the leading n for a single ``Mesh``.  Every
+    texel a face owns holds ``netC.query(point) * 0.5 + 0.5`` at the surface point under it (gutter texels: the face's
+    plane extrapolated), every other texel ``atlas.background`` and face id -1: what ``render_mesh(shade="netC")`` is
+    for one camera, for the whole surface.  ``netC`` with ``feat_tensors_C`` / ``calib_tensors`` (for a list one entry per
+    mesh, as ``render_mesh_many`` takes them; for a single ``Mesh`` its own, as ``render_mesh``'s ``feat_tensor_C`` /
+    ``calib_tensor``) and ``view``; or ``colors``: a callable ``points [3,K] -> [3,K]`` raw
+    predictions that takes the place of the netC query (a colour field of the caller's own; only the covered texels'
+    values are used).  Faces beyond ``atlas.faces`` are laid out nowhere (``encode_glb`` refuses such a mesh).  One
+    atlas launch, the point lists, one counted query, one paint: no host sync."""
+    who = "bake_texture"
+    if not isinstance(atlas, Atlas):
+        raise ValueError("%s: atlas must be a recon.Atlas, got %r" % (who, type(atlas).__name__))
+    meshes, single = _texture_meshes(who, meshes)
+    if single and feat_tensors_C is not None and calib_tensors is not None:  # a single mesh's own, as render_mesh's
+        feat_tensors_C, calib_tensors = [feat_tensors_C], [calib_tensors]
+    query = _atlas_query(who, meshes, netC, feat_tensors_C, calib_tensors, view, colors)
+    if not meshes:
+        return []
+    images, faces, _ = _bake(who, _mesh_subjects(who, meshes), atlas, query)
+    if single:
+        return images[0], faces[0]
+    return torch.stack(list(images)), torch.stack(list(faces))
+
+
 class Glb:
     """How meshes are written on the device (mp_mesh_glb in include/monoport_hip.h: binary glTF 2.0 under
     KHR_mesh_quantization, byte for byte this library's own definition; what the reference's ``save_obj_mesh*`` write as
@@ -1442,14 +1552,25 @@ class Glb:
     the file of a mesh of a quarter of the buffers' capacities (the 257^3 body fills about a ninth of a slot's 12 r^2
     vertices and 24 r^2 faces), never more than ``ops.glb_max_bytes``.  A file that does not fit is reported by the
     device and encoded again alone at its exact size (``encode_glb``, ``FrameSlot.glbs``): the capacity never changes
-    the bytes.  Everything is validated here; a Glb holds host values only."""
+    the bytes.  ``texture``: None, or an ``Atlas``: the file then carries netC as a base colour texture instead of
+    COLOR_0 (mp_mesh_glb_textured: an unindexed primitive with TEXCOORD_0 and the atlas's PNG inside the file);
+    ``colors`` then defaults to False, and ``colors=True`` is refused, because glTF multiplies COLOR_0 into the texture.
+    Everything is validated here; a Glb holds host values only."""
 
-    def __init__(self, normals=True, colors=True, capacity=None):
+    _UNSET = object()  # ``colors`` left to its default: True without a texture, False with one
+
+    def __init__(self, normals=True, colors=_UNSET, capacity=None, texture=None):
         who = "Glb"
+        if texture is not None and not isinstance(texture, Atlas):
+            raise ValueError("%s: texture must be None or a recon.Atlas, got %r" % (who, type(texture).__name__))
+        if colors is Glb._UNSET:
+            colors = texture is None
         for name, flag in (("normals", normals), ("colors", colors)):
             if not isinstance(flag, (bool, np.bool_)):
                 raise ValueError("%s: %s must be a bool, got %r" % (who, name, flag))
-        self.normals, self.colors = bool(normals), bool(colors)
+        if colors and texture is not None:
+            raise ValueError("%s: colors=True together with texture=: glTF multiplies COLOR_0 into the texture" % who)
+        self.normals, self.colors, self.texture = bool(normals), bool(colors), texture
         if capacity is not None:
             if (isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer))
                     or not ops.GLB_MIN_BYTES <= capacity <= 2 ** 31):
@@ -1462,11 +1583,53 @@ class Glb:
         """Bytes reserved per mesh in buffers of these capacities."""
         if self.capacity is not None:
             return self.capacity
+        if self.texture is not None:  # no more faces than the atlas holds, and the image at its own capacity
+            t = self.texture
+            return min(ops.glb_textured_bytes(min(max_faces // 4, t.faces), t.png_capacity(), self.normals),
+                       ops.glb_textured_max_bytes(max_faces, t.size, self.normals))
         return min(ops.glb_bytes(max_verts // 4, max_faces // 4, self.normals, self.colors),
                    ops.glb_max_bytes(max_verts, max_faces, self.normals, self.colors))
 
 
-def encode_glb(meshes, glb=None, b_min=(-1, -1, -1), b_max=(1, 1, 1)):
+def _encode_glb_textured(who, meshes, glb, b_min, b_max, query):
+    """``encode_glb`` under ``glb.texture``: the bake (``_bake``), ONE mp_picture_png over the atlases' images, one
+    mp_mesh_glb_textured per mesh.  Two device-to-host copies of sizes (the PNGs', the files'), then the used prefixes;
+    an image that exceeded the atlas's PNG capacity is encoded again at the size the device reported, and so is a file."""
+    atlas = glb.texture
+    for k, m in enumerate(meshes):
+        if m.verts.shape[0] and m.faces.shape[0] > atlas.faces:
+            raise ValueError("%s: mesh %d has %d faces and Atlas(%d, %d) holds %d: simplify the mesh, or take a larger "
+                             "atlas or smaller cells" % (who, k, m.faces.shape[0], atlas.size, atlas.cell, atlas.faces))
+    subjects = _mesh_subjects(who, meshes)
+    images, _, _ = _bake(who, subjects, atlas, query)
+    images = torch.stack(list(images))
+    png, png_info = _png_raw(atlas.png, images, None, capacity=atlas.png_capacity())
+    sizes = png_info.cpu().numpy()
+    if sizes[:, 1].any():  # the same bytes at a sufficient capacity
+        png, png_info = _png_raw(atlas.png, images, None, capacity=int(sizes[:, 0].max()))
+        sizes = png_info.cpu().numpy()
+    shapes = [(int(m.verts.shape[0]), int(m.faces.shape[0])) for m in meshes]
+    capacity = glb.capacity
+    if capacity is None:
+        capacity = max(ops.glb_textured_bytes(nf if nv else 0, int(size), glb.normals)
+                       for (nv, nf), size in zip(shapes, sizes[:, 0]))
+    out = torch.empty((len(meshes), capacity), dtype=torch.uint8, device=images.device)
+    info = torch.empty((len(meshes), 2), dtype=torch.int32, device=images.device)
+
+    def encode(i, **kw):
+        return ops.mesh_glb_textured_raw(subjects.verts[i], subjects.faces[i], subjects.counts[i], atlas.size,
+                                         atlas.cell, png[i:i + 1], png_info[i:i + 1],
+                                         meshes[i].normals.contiguous() if glb.normals else None, None, b_min, b_max, **kw)
+    for i in range(len(meshes)):
+        encode(i, out=out[i:i + 1], info=info[i:i + 1])
+    host = info.cpu().numpy()
+    if (host[:, 1] == 2).any():
+        raise RuntimeError("%s: the device refused mesh %d (info %s)" % (who, int(np.argmax(host[:, 1] == 2)), host))
+    return _collect_files(who, out, host, lambda i, size: encode(i, capacity=size))
+
+
+def encode_glb(meshes, glb=None, b_min=(-1, -1, -1), b_max=(1, 1, 1), netC=None, feat_tensors_C=None,
+               calib_tensors=None, view=None, colors=None):
     """The binary glTF files of ``meshes`` (a ``Mesh`` on the device, or a list of them) under ``glb`` (a ``Glb``; None:
     its defaults), laid out on the device: ``bytes`` for one mesh, a list of ``bytes`` for a list.  ``b_min`` / ``b_max``:
     the box the 16-bit positions span (the reconstruction's; a vertex outside is clamped onto it).  A mesh without the
@@ -1474,21 +1637,31 @@ def encode_glb(meshes, glb=None, b_min=(-1, -1, -1), b_max=(1, 1, 1)):
     exact size, which the host knows from the shapes; one host-to-device copy of the counts, one device-to-host copy of
     the sizes, then one of the used prefixes; a mesh whose file exceeded ``glb.capacity`` is encoded again alone at the
     size the device reported.  Any glTF 2.0 reader that knows KHR_mesh_quantization loads the files; tests/glb_ref.py
-    restates them byte for byte."""
+    restates them byte for byte.  With ``glb.texture`` (an ``Atlas``) the texture is baked first, as ``bake_texture``
+    does from ``netC`` / ``feat_tensors_C`` / ``calib_tensors`` / ``view`` or from ``colors`` (all refused without a
+    texture), encoded as a PNG on the device and written into the file (tests/glb_texture_ref.py); a mesh with more
+    faces than the atlas holds is a ValueError raised before anything is enqueued."""
     who = "encode_glb"
     glb = Glb() if glb is None else glb
     if not isinstance(glb, Glb):
         raise ValueError("%s: glb must be a recon.Glb, got %r" % (who, type(glb).__name__))
-    single = isinstance(meshes, Mesh)
-    meshes = [meshes] if single else list(meshes)
+    meshes, single = _texture_meshes(who, meshes)
     for k, m in enumerate(meshes):
-        if not isinstance(m, Mesh):
-            raise ValueError("%s: mesh %d is not a recon.Mesh but %r" % (who, k, type(m).__name__))
         for name, wanted, have in (("normals", glb.normals, m.normals), ("colors", glb.colors, m.colors)):
             if wanted and have is None:
                 raise ValueError("%s: mesh %d has no %s and glb asks for them" % (who, k, name))
+    if glb.texture is None:
+        if any(a is not None for a in (netC, feat_tensors_C, calib_tensors, view, colors)):
+            raise ValueError("%s: netC=, its maps, view= and colors= bake glb.texture, and this Glb has none" % who)
+    else:
+        if single and feat_tensors_C is not None and calib_tensors is not None:  # a single mesh's own
+            feat_tensors_C, calib_tensors = [feat_tensors_C], [calib_tensors]
+        query = _atlas_query(who, meshes, netC, feat_tensors_C, calib_tensors, view, colors)
     if not meshes:
         return []
+    if glb.texture is not None:
+        files = _encode_glb_textured(who, meshes, glb, b_min, b_max, query)
+        return files[0] if single else files
     dev = meshes[0].verts.device
     sizes = [(int(m.verts.shape[0]), int(m.faces.shape[0])) for m in meshes]
     capacity = glb.capacity

@@ -127,6 +127,14 @@ replaces (the tensors' ``.cpu()`` and the numpy packing of tests/glb_ref.py), in
 
     python tools/mesh_timing.py --glb [--passes 5] [--out profiles/mesh_glb_timing.json]
 
+``--texture`` measures the textured way out (profiles/mesh_texture_timing.json): 20-frame colour slots with a mesh per
+frame of the 257^3 body at ``simplify=64``, ``glbs()`` as the consumer: with COLOR_0 (``recon.Glb()``), with
+``recon.Glb(texture=recon.Atlas(1024, 8))`` and with ``Atlas(2048, 16)`` (whose slots run no per-vertex colour query), and
+the same textured file made through the host: ``meshes()``, ``.cpu()`` of the tensors and of netC's bake, the numpy
+restatement's writer (tests/glb_texture_ref.py) and Pillow's PNG encoder.  It states the texels queried per frame.
+
+    python tools/mesh_timing.py --texture [--passes 5] [--out profiles/mesh_texture_timing.json]
+
 The protocol of tools/recon_views_timing.py: after a warm-up of all, the passes alternate; a pass is `meshes`
 meshes, wall clock around a final stream sync.  Prints (and writes) one JSON line: per way the median, minimum and
 maximum time per mesh (ms) over the passes.  The verdict fields restate what to check: (b) not slower than (a) by
@@ -175,9 +183,11 @@ def main():
     ap.add_argument("--png", action="store_true", help="mp_picture_png alone; the --lighting slots with a recon.Png")
     ap.add_argument("--samples", action="store_true", help="mp_picture_resolve alone; the --jpeg slots at samples 1 / 2 / 4")
     ap.add_argument("--glb", action="store_true", help="mp_mesh_glb_batch alone; the colour slot with encode_meshes")
+    ap.add_argument("--texture", action="store_true", help="the colour slot's glbs() with COLOR_0 against a baked atlas")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "mesh_render_clip_timing.json" if a.render and a.clip else
+        a.out = os.path.join(ROOT, "profiles", "mesh_texture_timing.json" if a.texture else
+                             "mesh_render_clip_timing.json" if a.render and a.clip else
                              "mesh_render_timing.json" if a.render else
                              "mesh_deferred_timing.json" if a.deferred else
                              "mesh_scene_timing.json" if a.scene else
@@ -192,6 +202,9 @@ def main():
                              "mesh_simplify_timing.json" if a.simplify else
                              "keep_largest_timing.json" if a.clean else
                              "mesh_batch_timing.json" if a.batched else "mesh_timing.json")
+    if a.texture:
+        write(a, slot_texture(a))
+        return
     if a.deferred:
         write(a, slot_deferred(a))
         return
@@ -588,6 +601,61 @@ def slot_glb(a, frames=20):
     out["overflowed_frames"] = int(slot.glb_info[:, 1].sum().item())
     out["files_equal_host_packing"] = bool(all(f == _host_glb(glb_ref, m) for f, m in zip(files, meshes)))
     out["glbs_adds_ms"] = round(out["glbs"]["median_ms"] - out["meshes"]["median_ms"], 4)
+    for p_ in pipes.values():
+        p_.close()
+    return out
+
+
+TEXTURE_ATLASES = ((1024, 8), (2048, 16))
+
+
+def _host_textured_glb(refs, slot, b, mesh, atlas):
+    """The host route of a textured file: the mesh's tensors and netC's bake (on the slot's own maps) to the host, the
+    image through Pillow's PNG encoder, the file through the numpy restatement's writer."""
+    import io
+    from PIL import Image
+    glb_ref, tex_ref = refs
+    nchw = slot.feats_hwc_c[b].permute(2, 0, 1)[None].contiguous()
+    image, _ = recon.bake_texture(mesh, atlas, netC=slot.netC, feat_tensors_C=[[nchw]], calib_tensors=slot.calib[b:b + 1])
+    png = io.BytesIO()
+    Image.fromarray(glb_ref.to_u8(image.cpu().numpy()).astype(np.uint8)).save(png, format="PNG")
+    return tex_ref.encode(mesh.verts.cpu().numpy(), mesh.faces.cpu().numpy(), atlas.size, atlas.cell, png.getvalue(), None,
+                          mesh.normals.cpu().numpy(), BMIN, BMAX)[0]
+
+
+def slot_texture(a, frames=20, simplify=64):
+    """The 20-frame colour slot with a simplified mesh per frame, ``glbs()`` as the consumer: COLOR_0 against a baked
+    atlas of two sizes, and the textured file through the host; per-frame ms of a submission."""
+    glb_ref = _glb_ref()
+    import glb_texture_ref as tex_ref
+    coloured = {"normals": "accumulate", "simplify": simplify}
+    bare = dict(coloured, colors=False)
+    atlases = {"atlas_%d_%d" % st: recon.Atlas(*st) for st in TEXTURE_ATLASES}
+    glbs = dict({"color_0": recon.Glb()}, **{k: recon.Glb(texture=t) for k, t in atlases.items()})
+    pipes, fn = _slot_pipes(frames, 1, (("color_0", coloured), ("bare", bare)) + tuple((k, bare) for k in atlases), glbs=glbs)
+    first = next(iter(atlases))
+    ways = {name: fn(name, lambda s: s.glbs()) for name in glbs}
+    ways["host_" + first] = fn("bare", lambda s: [_host_textured_glb((glb_ref, tex_ref), s, b, m, atlases[first])
+                                                  for b, m in enumerate(s.meshes())])
+    out = {"frames_per_slot": frames, "unit": "ms per frame", "normals": "accumulate", "simplify": simplify,
+           "resolutions": RES}
+    out.update(alternate(ways, a.passes, frames))
+    for name in glbs:
+        slot = pipes[name].slots[0]
+        files, meshes = slot.glbs(), slot.meshes()
+        st = {"file_bytes_frame0": len(files[0]), "capacity_bytes": int(slot.glb_bytes.shape[1]),
+              "vertices_faces_frame0": [int(meshes[0].verts.shape[0]), int(meshes[0].faces.shape[0])],
+              "frames_encoded_again": int((slot.glb_info[:, 1] != 0).sum().item())}
+        if name in atlases:
+            counts = slot.atlas_lists["count"][:, 1].cpu().tolist()
+            st.update(atlas_faces=atlases[name].faces, texels_queried_per_frame=int(np.mean(counts)),
+                      texels_queried_frame0=int(counts[0]), png_bytes_frame0=int(slot.atlas_png_info[0, 0].item()),
+                      png_capacity=int(slot.atlas_png.shape[1]),
+                      adds_ms_over_color_0=round(out[name]["median_ms"] - out["color_0"]["median_ms"], 4))
+            got = tex_ref.read(files[0])
+            st["image_decodes_to_the_bake"] = bool(np.array_equal(
+                tex_ref.decode_png(got["png"]), glb_ref.to_u8(slot.atlas_image[0].cpu().numpy())))
+        out[name + "_file"] = st
     for p_ in pipes.values():
         p_.close()
     return out
